@@ -17,12 +17,19 @@ N > 1: one process per GPU, every rank reconstructs its own scenes: embarrassing
 -> "scaling": "weak".  `python bench.py --gpus N` works bare: when WORLD_SIZE is not set it re-executes itself under
 `python -m torch.distributed.run --nproc-per-node N` (rendezvous on 127.0.0.1); under an existing torchrun launch it uses that.
 
-Output (rank 0): the LAST stdout line is the contract line, compact (<= 4 KB, contract_line()): metric / value / ms_per_step / config / dtype, `roofline`
-of the dominant kernel, {frac, ms} of the other three, `cpu_baseline` (the reference's own modules as timed on this host type when the stamped file of this
-round matches, kind "reference"; else the oracle port timed live, kind "port") and one max-error number per stage vs the reference (`parity`).  The full
-record -- `parity_fullsize`, `c3` (BASELINE config 3), `ref_config` (V=32 / 96^3 / 256^3), `config5` (256^3 / 1024^2 / 512^3), `fp32_whole_step_ms`,
-`cpu_baseline_reference`, `parity_reference` detail, `trained_regime`, `pipelined`, `dropin` -- is the stdout line BEFORE it and bench_extra.json.
-`--quick` skips the extra blocks.
+A plain run (`--gpus 1 --steps K --warmup W`) sets up, warms up, times the K steps, writes the last step's outputs when `--dump-outputs DIR`
+is given, and prints the result line: nothing else runs on the GPU.  `--full` adds everything else, after the timed steps: the exhaustive-colour
+pass, `pipelined`, `c3`, the per-kernel rooflines, `cpu_baseline` and the parity blocks, and the extra configurations below.
+
+Output (rank 0): the LAST stdout line is the contract line, compact (<= 4 KB, contract_line()): metric / value / ms_per_step / config / dtype; with
+`--full` also `roofline` of the dominant kernel, {frac, ms} of the other three, `cpu_baseline` (the reference's own modules as timed on this host type when
+the stamped file of this round matches, kind "reference"; else the oracle port timed live, kind "port") and one max-error number per stage vs the reference
+(`parity`).  The full record -- with `--full`: `parity_fullsize`, `c3` (BASELINE config 3), `ref_config` (V=32 / 96^3 / 256^3), `config5`
+(256^3 / 1024^2 / 512^3), `fp32_whole_step_ms`, `cpu_baseline_reference`, `parity_reference` detail, `trained_regime`, `pipelined`, `dropin` -- is the
+stdout line BEFORE it and bench_extra.json.  `--full --quick` skips the extra blocks (c3 / pipelined / ref_config / config5 / fp32 / dropin).
+
+`--dump-outputs DIR`: what the last timed step returned (the rendered image's per-ray results, the mesh, seeded samples of the latent volume and of the
+extraction SDF grid) as DIR/<name>.npy in float32 / float64, at most 64 MB; the inputs are seeded, so two builds can be compared output for output.
 """
 import argparse
 import importlib
@@ -691,6 +698,48 @@ def emit(result):
     print(contract_line(result), flush=True)
 
 
+DUMP_BUDGET = 64 << 20         # bytes: --dump-outputs writes at most this much
+DUMP_RAY_ROWS = 1 << 18        # rays beyond this (--ray-scale > 2): a fixed seeded sample of the rays
+DUMP_MESH_ROWS = 1 << 19       # mesh vertices / triangles beyond this: a fixed seeded sample of the rows
+DUMP_FIELD_SAMPLES = 1 << 20   # entries of the latent volume / the extraction SDF grid: a fixed seeded sample
+
+
+def _sample_rows(t, n, seed):
+    """The first dimension of ``t`` cut to a fixed seeded sample of ``n`` rows (kept in order) when it is longer."""
+    if t.shape[0] <= n:
+        return t
+    idx = np.sort(np.random.default_rng(seed).choice(t.shape[0], n, replace=False))
+    return t[torch.from_numpy(idx).to(t.device)]
+
+
+def dump_outputs(path, vol, outs, mesh):
+    """--dump-outputs: what the last timed step returned to its caller, as ``path``/<name>.npy in float32 / float64 -- the rendered image's per-ray
+    results (seeded ray samples beyond DUMP_RAY_ROWS), the mesh (vertices, triangles as float64 indices, vertex colours; seeded row samples beyond
+    DUMP_MESH_ROWS), the mesh / voxel counts, and seeded samples of the two large fields (latent volume, extraction SDF grid).  At most ~47 MB by
+    these caps.  Inputs are seeded, so two builds compare output for output."""
+    verts, tris, rgb, u = mesh
+    per_ray = lambda k: _sample_rows(torch.cat([o[k] for o in outs]), DUMP_RAY_ROWS, 0)
+    arrays = {"color": per_ray("color"), "depth": per_ray("depth"), "weights_sum": per_ray("weights_sum"), "depth_var": per_ray("depth_var"),
+              "color_mask": per_ray("color_mask"),
+              "mesh_counts": torch.tensor([verts.shape[0], tris.shape[0], int(vol["n_voxels"])], dtype=torch.float64),
+              "mesh_vertices": _sample_rows(verts, DUMP_MESH_ROWS, 1), "mesh_vertex_colors": _sample_rows(rgb, DUMP_MESH_ROWS, 1),
+              "mesh_triangles": _sample_rows(tris, DUMP_MESH_ROWS, 2),
+              "volume_sample": _sample_rows(vol["vol_cl"].reshape(-1), DUMP_FIELD_SAMPLES, 3),
+              "sdf_grid_sample": _sample_rows(u.reshape(-1), DUMP_FIELD_SAMPLES, 4)}
+    host = {}
+    for k, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float64 if a.dtype.kind in "iu" and a.dtype.itemsize > 2 else np.float32)        # integer indices stay exact
+        host[k] = a
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_BUDGET:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes (budget {DUMP_BUDGET})")
+    os.makedirs(path, exist_ok=True)
+    for k, a in host.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+
+
 def reexec_under_torchrun(n):
     """`python bench.py --gpus N` invoked bare: start N ranks on this node (one per GPU) through torch.distributed.run."""
     import socket
@@ -714,7 +763,10 @@ def main():
     ap.add_argument("--ray-chunk", type=int, default=1 << 18)
     ap.add_argument("--cpu-rays", type=int, default=8192)
     ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--quick", action="store_true", help="only the contract's line (no c3 / ref_config / config5 / fp32 / dropin blocks)")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, everything beyond the headline figure: exhaustive colour pass, pipelined, c3, "
+                                                        "rooflines, cpu_baseline / parity, fp32, trained_regime, ref_config, config5, dropin (default: off)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's outputs as DIR/<name>.npy (float32 / float64, <= 64 MB)")
+    ap.add_argument("--quick", action="store_true", help="with --full: only the contract's line (no c3 / ref_config / config5 / fp32 / dropin blocks)")
     ap.add_argument("--no-dropin", action="store_true", help="skip the `dropin` block (the reference's own timing brackets on the drop-in surface, warm and in fresh processes)")
     ap.add_argument("--same-scene", action="store_true", help="re-reconstruct one scene every step (round-1 behaviour; A/B knob)")
     ap.add_argument("--backend", default=None, help="torch.distributed backend (default nccl = RCCL; gloo for the CPU plumbing test)")
@@ -801,9 +853,11 @@ def main():
         print({k: st[k] for k in ("num_device_alloc", "num_device_free", "num_alloc_retries", "reserved_bytes.all.peak", "allocated_bytes.all.peak")}, file=sys.stderr)
     n_rays = inp["rays_o"].shape[0]
     ms_step = dt / a.steps * 1e3
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, vol, outs, mesh)
     c3 = piped = None
     exhaustive = None
-    if world == 1 and config.weight_cull() > 0:
+    if a.full and world == 1 and config.weight_cull() > 0:
         # the same K scenes once more with the colour network on EVERY occupied sample (weight_cull = 0: the reference's work, the value of rounds 1-4):
         # the contract's `value` above runs with the tolerance-bounded removal (a ray's colour moves by <= 7.6e-6); both are on the line
         old_cull, config.WEIGHT_CULL = config.WEIGHT_CULL, 0.0
@@ -825,21 +879,16 @@ def main():
             v_ = o_ = m_ = None
         finally:
             config.WEIGHT_CULL = old_cull
-    if not a.quick and world == 1 and a.streams > 1 and not a.same_scene and not a.ckpt:
+    if a.full and not a.quick and world == 1 and a.streams > 1 and not a.same_scene and not a.ckpt:
         vol_keep = (vol, outs, mesh)
         piped = pipelined_block(dev, a, inp, scene_imgs[a.warmup:], a.streams)
         vol, outs, mesh = vol_keep
-    if not a.quick:
+    if a.full and not a.quick:
         scene_imgs = None
         c3 = c3_block(dev, wt, inp, a, rank, world)          # all ranks take part (barrier + max-over-ranks clock inside)
     result = None
     if rank == 0:
-        kt = kernel_times(wt, vol, inp, outs, a.vol)
-        V, C = a.views, 16
         n_vox = int(vol["n_voxels"])
-        cv_bytes = V * C * 256 * 256 * 4 + n_vox * (2 * C * 4 + 16) + a.vol ** 3
-        nvp, npts = kt["n_valid_points"], kt["n_points"]
-        rl = network_rooflines(kt, V, wt.sdf_precision, wt.color_precision)
         dtype = {"f16x3": "f32 (matrix products as 3 f16 MFMAs on split operands, fp32 accumulate)", "fp32": "f32"}[a.precision]
         result = {
             "metric": "rays/sec + mesh-extract wall-clock per scene (8x256^2 views, 128^3 vol)", "value": world * n_rays / (ms_step * 1e-3),
@@ -858,6 +907,14 @@ def main():
             "render_rays_per_s": n_rays / (tm.mean("render") * 1e-3), "mesh_extract_ms": tm.mean("mesh"),
             "volume_build_ms": tm.mean("volume"), "render_ms": tm.mean("render"),
             "mesh": {"vertices": int(mesh[0].shape[0]), "triangles": int(mesh[1].shape[0])}, "kept_voxels": n_vox,
+        }
+    if rank == 0 and a.full:
+        kt = kernel_times(wt, vol, inp, outs, a.vol)
+        V, C = a.views, 16
+        cv_bytes = V * C * 256 * 256 * 4 + n_vox * (2 * C * 4 + 16) + a.vol ** 3
+        nvp, npts = kt["n_valid_points"], kt["n_points"]
+        rl = network_rooflines(kt, V, wt.sdf_precision, wt.color_precision)
+        result.update({
             "occupied_points": nvp, "sampled_points": npts,
             "list_sort_ms": kt.get("list_sort_ms"),      # csrc/list_sort.hip: the occupied-point list grouped by view-visibility signature (inside every render call)
             # dominant kernel of a step = the colour network: ALGORITHMIC FLOP (38,544 per (point, view)) x occupied
@@ -875,7 +932,7 @@ def main():
             "roofline_costvol": {"kernel": "k_costvol_gather<16>", "bound": "hbm", "achieved": cv_bytes / (kt["costvol_gather_ms"] * 1e-3) / 1e9,
                                  "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": cv_bytes / (kt["costvol_gather_ms"] * 1e-3) / 1e9 / HBM_PEAK_GBS,
                                  "traffic": pmc_traffic("k_costvol_gather"), "algorithmic_bytes": cv_bytes, "ms": kt["costvol_gather_ms"]},
-        }
+        })
         if c3 is not None:
             result["c3"] = c3
         if piped is not None:

@@ -1,6 +1,7 @@
 """Small seeded scenes for the tests, built with the ORACLE only (no reference, no GPU)."""
 import functools
 import importlib
+import os
 
 import numpy as np
 import torch
@@ -8,6 +9,7 @@ import torch
 from oracle import recon as O
 
 pkg = importlib.import_module("one-2-3-45_amd")
+SMALL_SCENE_DENSE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "small_scene_dense.npz")
 
 
 def costreg_oracle_weights(sd):
@@ -56,3 +58,14 @@ def rays_for(scene, n, seed=0, center=True):
     else:
         sel = rng.integers(0, H * W, n)
     return ro[sel].copy(), rd[sel].copy()
+
+
+def stored_small_scene_dense():
+    """small_scene()'s latent volume [1,16,20,20,20] as stored in tests/golden/small_scene_dense.npz (written by
+    `PYTHONPATH=. python tests/scene_util.py`).  The CPU build of that volume (sparse convolutions) rounds differently on different host CPUs, by
+    ~2e-6; a test whose result amplifies such differences takes the stored volume, so that it sees the same input on every host."""
+    return torch.from_numpy(np.load(SMALL_SCENE_DENSE)["dense"])
+
+
+if __name__ == "__main__":
+    np.savez_compressed(SMALL_SCENE_DENSE, dense=small_scene()["dense"].numpy())

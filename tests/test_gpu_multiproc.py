@@ -17,7 +17,7 @@ def test_two_ranks_on_the_gpu_bare_invocation():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["O2345_BENCH_EXTRA_FILE"] = ""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--share-gpu", "--steps", "2", "--warmup", "1",
-                        "--no-cpu", "--vol", "64", "--ray-scale", "1", "--mesh-res", "96"],
+                        "--full", "--no-cpu", "--vol", "64", "--ray-scale", "1", "--mesh-res", "96"],
                        capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -100,7 +100,7 @@ def test_eight_ranks_on_the_one_gpu_functional():
     env["O2345_BENCH_EXTRA_FILE"] = ""
     env["OMP_NUM_THREADS"] = "4"                         # eight ranks on one host: no thread oversubscription
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--backend", "gloo", "--share-gpu", "--steps", "1", "--warmup", "1",
-                        "--no-cpu", "--vol", "64", "--ray-scale", "1", "--mesh-res", "64"],
+                        "--full", "--no-cpu", "--vol", "64", "--ray-scale", "1", "--mesh-res", "64"],
                        capture_output=True, text=True, timeout=1500, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

@@ -8,7 +8,7 @@ import torch
 
 from oracle import mc as omc
 from oracle import recon as O
-from scene_util import color_t, costreg_oracle_weights, rays_for, sdfW_t, small_scene
+from scene_util import color_t, costreg_oracle_weights, rays_for, sdfW_t, small_scene, stored_small_scene_dense
 
 pytestmark = pytest.mark.gpu
 pkg = importlib.import_module("one-2-3-45_amd")
@@ -481,6 +481,11 @@ def test_render(dev, ops, nrays, precision):
           quantities of all rays within 1e-3, sample lists within one coarse section, rays with coinciding sample lists tight."""
     import fullsize_util as FU
     s = small_scene()
+    # the stored volume (scene_util.stored_small_scene_dense): the hierarchical sampler of (3) amplifies the ~2e-6 by which the CPU build of the
+    # volume differs between host CPUs; both sides below read the same volume on every host
+    dense = stored_small_scene_dense()
+    close(dense, s["dense"], rel=1e-4, what="stored volume vs this host's build")
+    s = dict(s, dense=dense)
     d = dev_scene(s, dev, ops)
     sc = s["sc"]
     ro, rd = rays_for(s, nrays, seed=nrays)
