@@ -102,6 +102,15 @@ def _report_whole_image():
               f"fallbacks by reason: {st['fallbacks_by_reason'] or 'none'}", file=sys.stderr)
 
 
+def _report_packs():
+    """One line at exit: the mirrors' packed operands by (kind, device) (recon.pack_stats) -- under nn.DataParallel on several devices every device
+    appears once per kind and weight version, not once per forward."""
+    mod = sys.modules.get(f"{PKG}.recon.packs")
+    st = mod.pack_stats() if mod is not None else {}
+    if st:
+        print("o2345 packed operands: " + ", ".join(f"{k}@{d} x{n}" for (k, d), n in sorted(st.items())), file=sys.stderr)
+
+
 def activate():
     """Everything the launcher does before the reference script starts: thread-pool sizes (before anything imports torch: the pools read them at start-up;
     an explicit OMP_NUM_THREADS of the user wins), the host allocator setting, the import hook, the exit report.  Idempotent."""
@@ -112,6 +121,7 @@ def activate():
         install()
         import atexit
         atexit.register(_report_whole_image)
+        atexit.register(_report_packs)
 
 
 def main():

@@ -2,6 +2,8 @@
 csrc/featmaps.hip top-down path and pyramid).  Mirrors models/featurenet.py:12-91 and trainer_generic.py:1104-1125; the nn.Conv2d /
 InPlaceABN modules only hold the parameters, so state-dict keys are identical to the reference's (``conv0.0.conv.weight``,
 ``conv0.0.bn.{weight,bias,running_mean,running_var}``, ...)."""
+import importlib
+
 import torch
 import torch.nn as nn
 
@@ -10,6 +12,28 @@ from . import ops
 
 def _prepack_after_load(module, incompatible_keys):
     module.prepack()                      # (a load_state_dict post hook must return None)
+
+
+_packs_mod = None
+
+
+def _packs():
+    """recon.packs (imported on first use: recon imports this module)."""
+    global _packs_mod
+    if _packs_mod is None:
+        _packs_mod = importlib.import_module("one-2-3-45_amd.recon.packs")
+    return _packs_mod
+
+
+def _cached_conv_pack(owner, name, precision):
+    """The kernel packing of the nn.Conv2d ``owner.<name>`` in ``owner``'s pack cache (shared with every nn.DataParallel replica of ``owner``): keyed by
+    the SOURCE module's weight (object, storage, version counter) and the numerical mode, packed once per device."""
+    P = _packs()
+    w = P.param(owner._modules[name], "weight")
+    src = owner._packs.source(owner)
+    sw = w if src is owner else P.param(src._modules[name], "weight")
+    key = P.params_key((sw,)) + (ops.conv_x3(precision),)
+    return owner._packs.get("conv", w.device, key, lambda: ops.conv2d_pack(w.detach(), precision), slot=name)
 
 
 def packed_weight(conv, precision=None):
@@ -25,9 +49,13 @@ def packed_weight(conv, precision=None):
 
 
 def invalidate_packed(module):
-    """Drop every cached weight packing below ``module`` (after parameter updates through ``.data``, which no version counter sees)."""
+    """Drop every cached weight packing below ``module`` (after parameter updates through ``.data``, which no version counter sees): the mirrors'
+    pack caches (shared with their nn.DataParallel replicas) and the packings ``packed_weight`` keeps on plain convolutions."""
     for m in module.modules():
-        for attr in ("_o2345_packed_key", "_blob_key", "_key", "_costreg_key"):      # conv packings, SDF blob, colour blobs, packed sparse CNN
+        cache = m.__dict__.get("_packs")
+        if cache is not None:
+            cache.clear()
+        for attr in ("_o2345_packed_key", "_blob_key", "_key", "_costreg_key"):
             if hasattr(m, attr):
                 setattr(m, attr, None)
 
@@ -77,13 +105,18 @@ class ConvBnReLU(nn.Module):
         self.conv = nn.Conv2d(cin, cout, k, stride=stride, padding=pad, bias=False)
         self.bn = InPlaceABN(cout)
         self.precision = None                             # None = the global mode; SceneWeights sets its own (set_precision)
+        self._packs = _packs().PackCache(self)            # the weight packing per device, shared with every nn.DataParallel replica
+
+    def packed(self):
+        """The kernel packing of the convolution weight for this object's numerical mode (packed once per device and weight version)."""
+        return _cached_conv_pack(self, "conv", self.precision)
 
     def raw(self, x, in_scale_shift=None, nhwc_offset=None):
         """-> (raw conv output, this layer's ABN (scale | shift)); ``in_scale_shift``: x is itself a raw output to be activated on load;
         ``nhwc_offset``: x is a channel-last map whose channels nhwc_offset .. + cin are the input."""
         bn = self.bn                                      # ops.conv2d raises for CPU tensors: there is no CPU fallback
         return ops.conv2d(x.contiguous().float(), self.conv.weight.detach(), None, self.conv.stride[0], in_scale_shift, bn.slope,
-                          bn=(bn.weight.detach(), bn.bias.detach(), bn.eps, bn.abs_gamma), packed=packed_weight(self.conv, self.precision),
+                          bn=(bn.weight.detach(), bn.bias.detach(), bn.eps, bn.abs_gamma), packed=self.packed(),
                           precision=self.precision, nhwc_offset=nhwc_offset)
 
     def forward(self, x):
@@ -109,15 +142,18 @@ class FeatureNet(nn.Module):
         self.smooth1 = nn.Conv2d(32, 16, 3, padding=1)
         self.smooth0 = nn.Conv2d(32, 8, 3, padding=1)
         self.precision = None
+        self._packs = _packs().PackCache(self)            # toplayer / smooth1 / smooth0 packings per device, shared with every nn.DataParallel replica
         # convolution weights are packed for the kernels when they are LOADED, not inside the first forward
         self.register_load_state_dict_post_hook(_prepack_after_load)
 
     def prepack(self):
         if self.toplayer.weight.is_cuda:
             with torch.cuda.device(self.toplayer.weight.device):
-                for m in self.modules():
-                    if isinstance(m, nn.Conv2d) and m is not self.lat1 and m is not self.lat0:      # the 1x1 laterals run inside fpn_level, unpacked
-                        packed_weight(m, self.precision)
+                for m in self.modules():                  # the 1x1 laterals run inside fpn_level, unpacked
+                    if isinstance(m, ConvBnReLU):
+                        m.packed()
+                for name in ("toplayer", "smooth1", "smooth0"):
+                    _cached_conv_pack(self, name, self.precision)
         return self
 
     def forward(self, x):
@@ -132,12 +168,12 @@ class FeatureNet(nn.Module):
         (c0, ss0), (c1, ss1), (c2, ss2) = raws
         slope = self.conv0[0].bn.slope
         pr = self.precision
-        f2, _ = ops.conv2d(c2, self.toplayer.weight.detach(), self.toplayer.bias.detach(), 1, ss2, slope, packed=packed_weight(self.toplayer, pr), precision=pr)
+        f2, _ = ops.conv2d(c2, self.toplayer.weight.detach(), self.toplayer.bias.detach(), 1, ss2, slope, packed=_cached_conv_pack(self, "toplayer", pr), precision=pr)
         # top-down path: lateral 1x1 convolution + x2 bilinear up-sampling + add, one kernel per level (csrc/featmaps.hip)
         f1 = ops.fpn_level(c1, f2, self.lat1.weight.detach(), self.lat1.bias.detach(), ss1, slope)
         f0 = ops.fpn_level(c0, f1, self.lat0.weight.detach(), self.lat0.bias.detach(), ss0, slope)
-        s1, _ = ops.conv2d(f1, self.smooth1.weight.detach(), self.smooth1.bias.detach(), packed=packed_weight(self.smooth1, pr), precision=pr)
-        s0, _ = ops.conv2d(f0, self.smooth0.weight.detach(), self.smooth0.bias.detach(), packed=packed_weight(self.smooth0, pr), precision=pr)
+        s1, _ = ops.conv2d(f1, self.smooth1.weight.detach(), self.smooth1.bias.detach(), packed=_cached_conv_pack(self, "smooth1", pr), precision=pr)
+        s0, _ = ops.conv2d(f0, self.smooth0.weight.detach(), self.smooth0.bias.detach(), packed=_cached_conv_pack(self, "smooth0", pr), precision=pr)
         return [f2, s1, s0]
 
 

@@ -2,6 +2,7 @@
 Every function validates dtype / device / contiguity, passes raw pointers, and raises on a non-zero status."""
 import ctypes
 import functools
+import threading
 
 import numpy as np
 import torch
@@ -77,19 +78,24 @@ def to_host_numpy(*tensors):
 
 
 _preloaded = set()
+_preload_lock = threading.Lock()
 
 
 def preload(device):
-    """Load every code object of the library on ``device`` now (o2345_preload) -- once per device and process.  The mirrors call it when weights are loaded,
-    so that the HIP runtime's lazy per-translation-unit loading (5 - 60 ms each) does not land inside the first timed call of a fresh process."""
+    """Load every code object of the library on ``device`` now (o2345_preload) -- once per device and process.  The mirrors call it when weights are loaded
+    and on the first packing for a device (recon/packs.py: an nn.DataParallel replica's device), so that the HIP runtime's lazy per-translation-unit loading
+    (5 - 60 ms each) does not land inside the first timed call of a fresh process.  Thread-safe: nn.DataParallel's device threads may call it at once."""
     device = torch.device(device)
     if device.type != "cuda" or device in _preloaded:
         return
-    with torch.cuda.device(device):
-        check(_lib.lib().o2345_preload(), "preload")
-        if config.warm_aten():
-            _warm_aten(device)
-    _preloaded.add(device)
+    with _preload_lock:
+        if device in _preloaded:
+            return
+        with torch.cuda.device(device):
+            check(_lib.lib().o2345_preload(), "preload")
+            if config.warm_aten():
+                _warm_aten(device)
+        _preloaded.add(device)
 
 
 def _warm_aten(device):
@@ -118,7 +124,10 @@ _ws_cache = {}
 
 
 def _workspace(nbytes, device, tag="ws"):
-    """Scratch buffer per (purpose, device, stream): two streams of one device never share scratch memory."""
+    """Scratch buffer per (purpose, device, stream): two streams of one device never share scratch memory.  Host threads are safe as long as each
+    enqueues on its OWN stream: nn.DataParallel gives every replica its own device (its thread's key differs by device); two threads that launch onto
+    ONE stream of ONE device would overwrite each other's scratch between launches -- code that runs replicas on one device (tests) gives each thread
+    its own stream."""
     key = (tag, str(device), torch.cuda.current_stream(device).cuda_stream)
     t = _ws_cache.get(key)
     if t is None or t.numel() < nbytes:

@@ -4,3 +4,4 @@ from .sparse_sdf_network import SparseSdfNetwork, LatentSDFLayer  # noqa: F401
 from .rendering_network import GeneralRenderingNetwork  # noqa: F401
 from .sparse_neus_renderer import SparseNeuSRenderer, Projector  # noqa: F401
 from .fields import SingleVarianceNetwork  # noqa: F401
+from .packs import pack_stats  # noqa: F401

@@ -5,6 +5,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .. import config, ops, weights
+from .packs import PackCache, param, params_key
 
 
 def _prepack_after_load(module, incompatible_keys):
@@ -52,40 +53,42 @@ class GeneralRenderingNetwork(nn.Module):
                 if isinstance(m, nn.Linear):
                     nn.init.kaiming_normal_(m.weight.data)
                     nn.init.zeros_(m.bias.data)
-        self._xblob = self._mblob = self._key = None
+        self._packs = PackCache(self)       # per-device (x3, MFMA) blobs, shared with every nn.DataParallel replica (recon/packs.py)
         # packed for the kernels when the weights are LOADED (the runner loads its checkpoint before the first timed call), not inside the first query
         self.register_load_state_dict_post_hook(_prepack_after_load)
 
     _LINEARS = (("ray_dir_fc", (0, 2)), ("base_fc", (0, 2)), ("vis_fc", (0, 2)), ("vis_fc2", (0, 2)), ("rgb_fc", (0, 2, 4)))
+    _NAMES = ("s",) + tuple(f"{name}.{i}.{n}" for name, idx in _LINEARS for i in idx for n in ("weight", "bias"))     # state-dict keys, in _params() order
 
     def _params(self):
         """The CURRENT Parameter objects in a fixed order, read from the modules' own tables on every call (no cached list: load_state_dict(assign=True),
         `m.weight = nn.Parameter(...)` and parametrisation removal REPLACE the objects) and without walking the module tree (named_parameters() costs
         0.2 ms, and render() asks per 512-ray chunk)."""
-        ps = [self._parameters["s"]]
+        ps = [param(self, "s")]
         for name, idx in self._LINEARS:
             seq = self._modules[name]._modules
             for i in idx:
-                lin = seq[str(i)]._parameters
-                ps.append(lin["weight"])
-                ps.append(lin["bias"])
+                lin = seq[str(i)]
+                ps.append(param(lin, "weight"))
+                ps.append(param(lin, "bias"))
         return ps
 
     def weights_key(self):
         """Identity of the current parameters (objects, storages, version counters): changes with any load / assignment / in-place update."""
-        return tuple((id(p), p.data_ptr(), p._version) for p in self._params())
+        return params_key(self._params())
 
     def _blobs(self):
-        """(x3 blob, fp32-MFMA blob) of the current parameters; re-packed only when a parameter changed (object identity / data pointer / version counter)."""
+        """(x3 blob, fp32-MFMA blob) of the current parameters; packed once per device, re-packed only when a parameter of the SOURCE module (this one, or
+        the module this nn.DataParallel replica was made from) changed (object identity / data pointer / version counter)."""
         ps = self._params()
-        key = tuple((id(p), p.data_ptr(), p._version) for p in ps)
-        if key != self._key:
-            sd = {k: v.detach() for k, v in self.state_dict().items()}
-            dev = ps[0].device
-            self._xblob = torch.from_numpy(weights.packed_color_x3_blob(sd)).to(dev)
-            self._mblob = torch.from_numpy(weights.packed_color_mfma_blob(sd)).to(dev)
-            self._key = key
-        return self._xblob, self._mblob
+        src = self._packs.source(self)
+        key = params_key(ps if src is self else src._params())
+        dev = ps[0].device
+
+        def make():
+            sd = {k: p.detach() for k, p in zip(self._NAMES, ps)}
+            return torch.from_numpy(weights.packed_color_x3_blob(sd)).to(dev), torch.from_numpy(weights.packed_color_mfma_blob(sd)).to(dev)
+        return self._packs.get("colour", dev, key, make)
 
     def prepack(self):
         """Pack the parameters for the kernels now and run ONE tiny launch of the colour kernel (its first launch in a process costs ~10 ms in the HIP

@@ -2,6 +2,7 @@
 models/projector.py:11-425; general rendering, lod 0)."""
 import contextlib
 import os
+import threading
 
 import numpy as np
 import torch
@@ -14,6 +15,7 @@ from .sparse_sdf_network import _attr_cache, channel_last
 
 # process-wide sums of every renderer's whole-image counters (SparseNeuSRenderer.whole_image_stats); dropin.py prints them once at exit
 WHOLE_IMAGE_TOTALS = dict(images=0, chunks_served=0, plain_calls=0, fallbacks_by_reason={})
+_COUNT_LOCK = threading.Lock()             # nn.DataParallel's device threads count into the shared dicts at once
 
 
 def _scene_maps(feature_maps, color_maps, w2cs, intrinsics):
@@ -104,15 +106,18 @@ class SparseNeuSRenderer(nn.Module):
         self.n_samples, self.n_importance, self.n_outside, self.perturb, self.alpha_type = n_samples, n_importance, n_outside, perturb, alpha_type
         self.rendering_projector = Projector()
         self.if_fitted_rendering = False
-        self._image, self._side = None, None                             # whole-image mode (render())
+        self._image = None                                               # whole-image mode (render())
         # counters and the abandonment count live in ONE dict object: nn.DataParallel re-creates its per-device replicas from this module on every forward
         # (shallow copies of __dict__), so anything a replica must remember for the next image -- "the mode switched itself off" -- has to be shared by reference
         self._stats = dict(images=0, chunks_served=0, plain_calls=0, fallbacks_by_reason={}, abandoned=0)
-        # the side stream of the whole-image mode: created with the renderer (the first stream a process creates costs 6 ms in the HIP runtime -- not inside
+        # the side streams of the whole-image mode, one per (device, caller's stream), in ONE dict shared with every nn.DataParallel replica: replicas on
+        # different devices get their own, and two replica threads on one device with their own streams never enqueue onto one side stream (ops._workspace:
+        # scratch is per stream).  The first is created with the renderer (the first stream a process creates costs 6 ms in the HIP runtime -- not inside
         # the first val_step bracket); the networks are on their device when the trainer builds the renderer (exp_runner_generic_blender_val.py:93-129)
+        self._sides = {}
         p = next(iter(sdf_network.parameters()), None) if isinstance(sdf_network, nn.Module) else None
         if self.whole_image and p is not None and p.is_cuda:
-            self._side = torch.cuda.Stream(device=p.device)
+            self._side_stream(p.device)
 
     @torch.no_grad()
     def get_pts_mask_for_conditional_volume(self, pts, mask_volume):
@@ -183,11 +188,20 @@ class SparseNeuSRenderer(nn.Module):
                     enabled=bool(self.whole_image and self._abandoned < self.WHOLE_IMAGE_MAX_ABANDONED))
 
     def _count(self, key, reason=None):
-        for st in (self._stats, WHOLE_IMAGE_TOTALS):
-            if reason is None:
-                st[key] += 1
-            else:
-                st[key][reason] = st[key].get(reason, 0) + 1
+        with _COUNT_LOCK:
+            for st in (self._stats, WHOLE_IMAGE_TOTALS):
+                if reason is None:
+                    st[key] += 1
+                else:
+                    st[key][reason] = st[key].get(reason, 0) + 1
+
+    def _side_stream(self, dev, create=True):
+        """The side stream of the caller's current stream on ``dev`` (created on first use unless ``create`` is False -> None)."""
+        key = (str(dev), torch.cuda.current_stream(dev).cuda_stream)
+        side = self._sides.get(key)
+        if side is None and create:
+            side = self._sides.setdefault(key, torch.cuda.Stream(device=dev))
+        return side
 
     def _max_image_rays(self, dev):
         """The largest image rendered whole: WHOLE_IMAGE_MAX_RAYS, and no more than fits in WHOLE_IMAGE_MEMORY_FRACTION of the memory that is available now
@@ -202,8 +216,8 @@ class SparseNeuSRenderer(nn.Module):
         """Release the cached image.  Batches still running on the side stream read the scene's tensors and the ray storage, which were allocated on the
         caller's stream: the caller's stream waits for the side stream first, so nothing the caller frees next can be reused under those kernels."""
         c, self._image = self._image, None
-        if c is not None and self._side is not None and c["dev"].type == "cuda" and any(not bt["joined"] for bt in c["batches"]):
-            torch.cuda.current_stream(c["dev"]).wait_stream(self._side)
+        if c is not None and c.get("side") is not None and any(not bt["joined"] for bt in c["batches"]):
+            torch.cuda.current_stream(c["dev"]).wait_stream(c["side"])
 
     @staticmethod
     def _chunk_of_image(t):
@@ -309,10 +323,10 @@ class SparseNeuSRenderer(nn.Module):
         starts = sorted(set(starts))
         bounds = [(k0, k1) for k0, k1 in zip(starts, starts[1:] + [K]) if k1 > k0]
         cur = torch.cuda.current_stream(dev) if dev.type == "cuda" else None
+        side = None
         if nb > 1:
-            if self._side is None or self._side.device != dev:
-                self._side = torch.cuda.Stream(device=dev)
-            self._side.wait_stream(cur)                                     # the scene's tensors were produced on the caller's stream
+            side = self._side_stream(dev)
+            side.wait_stream(cur)                                           # the scene's tensors were produced on the caller's stream
         # the host stream of the K calls of the trainer's loop, in the reference's order: per call t_rand = torch.rand(z_vals.shape) (:506-515, only when
         # perturb > 0), then pts_random = torch.rand([1024, 3]) (:606); the generator is then put back to where it stands after the FIRST call
         states, batches = [], []
@@ -328,7 +342,7 @@ class SparseNeuSRenderer(nn.Module):
                         t_b[ra:rb] = torch.rand(rb - ra, self.n_samples)
                     p_b[k - bi] = torch.rand([1024, 3])
                     states.append(torch.get_rng_state())
-                with (torch.cuda.stream(self._side) if nb > 1 else contextlib.nullcontext()):
+                with (torch.cuda.stream(side) if nb > 1 else contextlib.nullcontext()):
                     o = ops.render_rays(scene, io_[a0:a1], id_[a0:a1], nr, fr, self.n_samples, self.n_importance, inv_s, air, bg, qcam,
                                         t_rand=t_b.to(dev, non_blocking=True) if perturb > 0 else None, want_scalars=True, segment_rays=R)
                     pts_random = p_b.to(dev, non_blocking=True).view(-1, 3) * 2 - 1
@@ -341,7 +355,7 @@ class SparseNeuSRenderer(nn.Module):
                     ev = None
                     if nb > 1:
                         ev = torch.cuda.Event()
-                        ev.record(self._side)
+                        ev.record(side)
                 batches.append(dict(a0=a0, k0=bi, o=o, rows=rows, sdf_random=sdf_random, event=ev, joined=False))
         except BaseException:
             torch.set_rng_state(rng_before)                                  # a failed call must not leave the host generator advanced by a whole image
@@ -354,7 +368,7 @@ class SparseNeuSRenderer(nn.Module):
                            args=[(t, t._version) for t in args], near=(near, getattr(near, "_version", None)), far=(far, getattr(far, "_version", None)),
                            perturb=float(perturb) > 0, air=alpha_inter_ratio, bg=background_rgb, var=(var, var._version, var.data_ptr()), inv_s=inv_s,
                            wkeys=(sdf_network.sdf_layer.weights_key(), rendering_network.weights_key()), nets=(sdf_network, rendering_network),
-                           ns=(self.n_samples, self.n_importance), dev=dev)
+                           ns=(self.n_samples, self.n_importance), dev=dev, side=side)
         self._count("images")
         self._count("chunks_served")
         return self._pack_rows(self._image, 0, R, 0)
@@ -412,8 +426,9 @@ class SparseNeuSRenderer(nn.Module):
                 # left in torch's cache go back to the driver, and THIS call is served the way the reference serves it -- one 512-ray chunk
                 self._image, self.whole_image = None, False
                 self._count("fallbacks_by_reason", "oom")
-                if self._side is not None:
-                    torch.cuda.current_stream(dev).wait_stream(self._side)
+                side = self._side_stream(dev, create=False) if dev.type == "cuda" else None
+                if side is not None:
+                    torch.cuda.current_stream(dev).wait_stream(side)
                 torch.cuda.empty_cache()
         # ---- one plain call
         self._count("plain_calls")

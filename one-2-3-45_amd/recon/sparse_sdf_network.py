@@ -1,5 +1,6 @@
 """SparseSdfNetwork on the HIP back end (mirror of models/sparse_sdf_network.py:35-499, lod 0 path)."""
 import importlib
+import threading
 
 import numpy as np
 import torch
@@ -9,6 +10,7 @@ from .. import config, ops, weights
 from ..costreg import CostRegNet
 from ..featurenet import ConvBnReLU
 from ..weights import COSTREG_LAYERS
+from .packs import PackCache, param, params_key
 
 def _prepack_after_load(module, incompatible_keys):
     module.prepack(resolutions=config.prepack_resolutions())                      # (a load_state_dict post hook must return None)
@@ -41,6 +43,7 @@ def _attr_cache(t, name, key, make):
 
 
 _CL_BY_STORAGE = {}        # (data_ptr, shape, device) -> (weakref of the channel-first volume get_conditional_volume returned, its version, channel-last copy)
+_CL_LOCK = threading.Lock()
 
 
 def _register_channel_last(cf, cl):
@@ -48,10 +51,11 @@ def _register_channel_last(cf, cl):
     (trainer_generic.py:1330-1345), a new tensor object on the same storage and version counter -- without this its first use re-laid the volume out through
     an ATen copy kernel (12 ms on the first call of a process, inside the reference's "export mesh time" bracket)."""
     import weakref
-    for k in [k for k, (ref, _, _) in _CL_BY_STORAGE.items() if ref() is None]:
-        del _CL_BY_STORAGE[k]
     cf._o2345_cl = ((cf._version,), cl)
-    _CL_BY_STORAGE[(cf.data_ptr(), tuple(cf.shape), str(cf.device))] = (weakref.ref(cf), cf._version, cl)
+    with _CL_LOCK:                       # nn.DataParallel's device threads register volumes at once: the prune walks the dict while others insert
+        for k in [k for k, (ref, _, _) in _CL_BY_STORAGE.items() if ref() is None]:
+            del _CL_BY_STORAGE[k]
+        _CL_BY_STORAGE[(cf.data_ptr(), tuple(cf.shape), str(cf.device))] = (weakref.ref(cf), cf._version, cl)
 
 
 def _channel_last_of_view(volume):
@@ -98,35 +102,48 @@ class LatentSDFLayer(nn.Module):
                     nn.init.normal_(lin.weight, 0.0, np.sqrt(2) / np.sqrt(128))
                     nn.init.constant_(lin.weight[:, -16:], 0.0)
             setattr(self, f"lin{l}", nn.utils.weight_norm(lin))
-        self._blob, self._blob_key, self._W, self._grid_tabs = None, None, None, {}
+        self._packs = PackCache(self)       # per-device blob / grid tables, shared with every nn.DataParallel replica (recon/packs.py)
+
+    _NAMES = tuple(f"lin{l}.{n}" for l in range(3) for n in ("bias", "weight_g", "weight_v"))        # state-dict keys, in _params() order
 
     def _params(self):
         """The parameters in a fixed order without walking the module tree (named_parameters() costs 0.2 ms, and render() asks per 512-ray chunk)."""
-        return [m._parameters[n] for m in (self.lin0, self.lin1, self.lin2) for n in ("bias", "weight_g", "weight_v")]
+        return [param(m, n) for m in (self.lin0, self.lin1, self.lin2) for n in ("bias", "weight_g", "weight_v")]
 
     def weights_key(self):
         """Identity of the current parameters (objects, storages, version counters): changes with any load / assignment / in-place update."""
-        return tuple((id(p), p.data_ptr(), p._version) for p in self._params())
+        return params_key(self._params())
+
+    def _source_key(self):
+        """weights_key() of the SOURCE module (this one, or the module this nn.DataParallel replica was made from): what the pack cache is keyed by."""
+        return params_key(self._packs.source(self)._params())
+
+    def _packed(self):
+        """(blob on the parameters' device, folded weights W) of the current parameters; packed once per device and source parameters."""
+        ps = self._params()
+        dev = ps[0].device
+        src = self._packs.source(self)
+        key = params_key(ps if src is self else src._params())
+
+        def make():
+            W = weights.sdf_weights_from_state_dict({k: p.detach() for k, p in zip(self._NAMES, ps)}, "")
+            return torch.from_numpy(weights.packed_sdf_blob(W)).to(dev), W
+        return self._packs.get("sdf_blob", dev, key, make)
 
     def blob(self):
-        ps = self._params()
-        key = tuple((id(p), p.data_ptr(), p._version) for p in ps)
-        if self._blob is None or key != self._blob_key:
-            W = weights.sdf_weights_from_state_dict({k: v.detach() for k, v in self.state_dict().items()}, "")
-            self._blob = torch.from_numpy(weights.packed_sdf_blob(W)).to(ps[0].device)
-            self._blob_key, self._W, self._grid_tabs = key, W, {}
-        return self._blob
+        return self._packed()[0]
 
     def grid_tables(self, resolution):
         """Layer 0 tabulated for the extraction lattice (csrc/sdf_mlp_x3.hip TAB form; rebuilt when a parameter changes)."""
         if config.sdf_precision() != "f16x3":
             return None
-        blob = self.blob()
+        blob, W = self._packed()
         R = int(resolution)
-        if R not in self._grid_tabs:
-            axes, bias = weights.packed_sdf_grid_tables(self._W, R)
-            self._grid_tabs[R] = ops.sdf_grid_tables(torch.from_numpy(axes).to(blob.device), torch.from_numpy(bias).to(blob.device))
-        return self._grid_tabs[R]
+
+        def make():
+            axes, bias = weights.packed_sdf_grid_tables(W, R)
+            return ops.sdf_grid_tables(torch.from_numpy(axes).to(blob.device), torch.from_numpy(bias).to(blob.device))
+        return self._packs.get("sdf_grid", blob.device, self._source_key(), make, slot=R)
 
 
 class _SparseCostRegNet(nn.Module):
@@ -161,7 +178,7 @@ class SparseSdfNetwork(nn.Module):
         self.sparse_costreg_net = _SparseCostRegNet(d_in=d_pyramid_feature_compress * 2 + (16 if lod > 0 else 0), d_out=regnet_d_out)
         self.sdf_layer = LatentSDFLayer(d_in=3, d_out=hidden_dim + 1, d_hidden=hidden_dim, n_layers=num_sdf_layers, multires=multires,
                                         geometric_init=True, weight_norm=True, activation=activation, d_conditional_feature=16)
-        self._lattice = {}
+        self._packs = PackCache(self)       # packed sparse CNN + voxel lattice per device, shared with every nn.DataParallel replica (recon/packs.py)
         # weights are packed for the kernels when they are LOADED (the runner loads its checkpoint before the first timed call,
         # exp_runner_generic_blender_val.py:485-512), not inside the first query
         self.register_load_state_dict_post_hook(_prepack_after_load)
@@ -176,8 +193,7 @@ class SparseSdfNetwork(nn.Module):
         with torch.cuda.device(p.device):
             self.sdf_layer.blob()
             self._costreg(p.device)
-            from ..featurenet import packed_weight
-            packed_weight(self.compress_layer.conv, self.compress_layer.precision)
+            self.compress_layer.packed()
             for R in resolutions:
                 self.sdf_layer.grid_tables(R)
                 # extract_geometry returns the R^3 field as numpy through a pinned block (ops.to_host_numpy): the first hipHostMalloc of that size costs ~5 ms;
@@ -193,32 +209,35 @@ class SparseSdfNetwork(nn.Module):
                 ops.sdf_mlp(blob, vol, pts, variant=variant)
             if config.sdf_precision() == "f16x3":
                 ops.sdf_mlp(blob, vol, None, variant=0, grid_R=2, sign=-1.0, grid_tables=self.sdf_layer.grid_tables(2))
-                self.sdf_layer._grid_tabs.pop(2, None)
+                self.sdf_layer._packs.discard("sdf_grid", p.device, slot=2)
         return self
 
     def _voxel_lattice(self, D, device):
         """generate_grid (ops/generate_grids.py:4-19): the voxel-index lattice [1,3,D,D,D] only depends on the volume size -- built once per (size, device)
         (five launches; at prepack time for the configured vol_dims), returned read-only by contract."""
-        lk = (tuple(D), str(device))
-        if lk not in self._lattice:
-            self._lattice = {lk: torch.stack(torch.meshgrid(*[torch.arange(d, dtype=torch.float32, device=device) for d in D], indexing="ij"))[None]}
-        return self._lattice[lk]
+        D = tuple(D)
+        return self._packs.get("lattice", device, D,
+                               lambda: torch.stack(torch.meshgrid(*[torch.arange(d, dtype=torch.float32, device=device) for d in D], indexing="ij"))[None])
 
     def _costreg(self, device):
-        """The packed sparse CNN of the current parameters (re-packed only when a parameter changes)."""
+        """The packed sparse CNN of the current parameters (re-packed only when a parameter of the source module changes)."""
         # the CURRENT parameter objects on every call (10 blocks x (kernel, BN weight, BN bias): a cached list goes stale when load_state_dict(assign=True)
         # or a direct assignment replaces the Parameter objects); read from the modules' own tables, no walk over the module tree
-        ps = []
+        src = self._packs.source(self)
+        sd = self._costreg_params(self)
+        key = params_key((sd if src is self else self._costreg_params(src)).values()) + (config.color_precision(),)
+        return self._packs.get("costreg", device, key, lambda: CostRegNet({k: v.detach() for k, v in sd.items()}, device))
+
+    @staticmethod
+    def _costreg_params(net):
+        """{state-dict key (below sparse_costreg_net.): parameter} of the three parameters of each block that the packed network reads."""
+        sd = {}
         for name, _, _ in COSTREG_LAYERS:
-            net = self.sparse_costreg_net._modules[name]._modules["net"]._modules
-            ps.append(net["0"]._parameters["kernel"])
-            ps.append(net["1"]._parameters["weight"])
-            ps.append(net["1"]._parameters["bias"])
-        key = (str(device),) + tuple((id(p), p.data_ptr(), p._version) for p in ps)
-        if getattr(self, "_costreg_key", None) != key:
-            sd = {k: v.detach() for k, v in self.sparse_costreg_net.state_dict().items()}
-            self._costreg_net, self._costreg_key = CostRegNet(sd, device), key
-        return self._costreg_net
+            blk = net.sparse_costreg_net._modules[name]._modules["net"]._modules
+            sd[f"{name}.net.0.kernel"] = param(blk["0"], "kernel")
+            sd[f"{name}.net.1.weight"] = param(blk["1"], "weight")
+            sd[f"{name}.net.1.bias"] = param(blk["1"], "bias")
+        return sd
 
     # ------------------------------------------------------------------------------------------------ cost volume
     @torch.no_grad()
