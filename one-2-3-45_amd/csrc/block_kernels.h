@@ -1,0 +1,108 @@
+// Small non-matrix kernels and block-level steps shared by several translation units (costvol.hip, sparse.hip, mcubes.hip, convnet.hip).
+// The kernels live in an anonymous namespace: every unit that launches one instantiates its own copy in its own code object, so o2345_preload
+// and the runtime's per-unit loading see them as before.
+#pragma once
+#include "common.h"
+
+namespace o2345 {
+
+constexpr int IDX_BLOCK = 256;          // threads per block of the index / compaction kernels
+
+// fixed-order sum of (s, q) over a 256-thread block: wave butterflies, then (w0 + w1) + (w2 + w3) -- deterministic.  Returns true in thread 0,
+// which then holds the block sums; the other threads return false and must not use s, q.
+__device__ __forceinline__ bool block_sum2_256(double& s, double& q) {
+    __shared__ double sm[2][4];
+    for (int off = 32; off; off >>= 1) { s += __shfl_xor(s, off); q += __shfl_xor(q, off); }
+    if ((threadIdx.x & 63) == 0) { sm[0][threadIdx.x >> 6] = s; sm[1][threadIdx.x >> 6] = q; }
+    __syncthreads();
+    if (threadIdx.x != 0) return false;
+    s = (sm[0][0] + sm[0][1]) + (sm[0][2] + sm[0][3]);
+    q = (sm[1][0] + sm[1][1]) + (sm[1][2] + sm[1][3]);
+    return true;
+}
+
+// batch statistics of channel c -> the (scale, shift) pair of InPlaceABN: s = sum x, q = sum x^2 over `count` values, biased variance;
+// abs_gamma selects the |gamma| + eps convention of inplace_abn; (mean, var) also go to mean_var when it is not null
+__device__ __forceinline__ void abn_scale_shift(double s, double q, double count, int c, int C, const float* __restrict__ gamma,
+                                                const float* __restrict__ beta, float eps, int abs_gamma, float* __restrict__ scale_shift,
+                                                float* __restrict__ mean_var = nullptr) {
+    const double mean = s / count;
+    double var = q / count - mean * mean;
+    if (var < 0.0) var = 0.0;
+    float g = gamma[c];
+    if (abs_gamma) g = fabsf(g) + eps;
+    const float inv = (float)(1.0 / sqrt(var + (double)eps));
+    scale_shift[c] = g * inv;
+    scale_shift[C + c] = beta[c] - (float)mean * g * inv;
+    if (mean_var) { mean_var[c] = (float)mean; mean_var[C + c] = (float)var; }
+}
+
+namespace {
+
+// exclusive scan of n ints in place by ONE 1024-thread block (n <= a few 100k block totals); *total = the sum
+template <typename Total>
+__global__ __launch_bounds__(1024) void k_scan_small(int* __restrict__ a, int n, Total* __restrict__ total) {
+    __shared__ int part[1024];
+    const int t = threadIdx.x;
+    const int per = (n + 1023) / 1024;
+    const int lo = t * per, hi = min(n, lo + per);
+    int s = 0;
+    for (int i = lo; i < hi; ++i) s += a[i];
+    part[t] = s;
+    __syncthreads();
+    for (int off = 1; off < 1024; off <<= 1) {       // Hillis-Steele inclusive scan over the 1024 partials
+        int v = (t >= off) ? part[t - off] : 0;
+        __syncthreads();
+        part[t] += v;
+        __syncthreads();
+    }
+    int run = part[t] - s;
+    for (int i = lo; i < hi; ++i) {
+        int v = a[i];
+        a[i] = run;
+        run += v;
+    }
+    if (t == 1023) *total = (Total)part[1023];
+}
+
+// [V,C,HW] -> [V,HW,C] through a 64-pixel x C LDS tile (coalesced reads and writes).  ACT: y = leaky_relu(x * ss[c] + ss[C + c], slope) on the
+// way, also written in NCHW to y_nchw when that is not null; y_nhwc may be null then.
+template <int C, bool ACT>
+__global__ __launch_bounds__(256) void k_nchw_to_nhwc(const float* __restrict__ x, const float* __restrict__ ss, float slope, int HW,
+                                                      float* __restrict__ y_nchw, float* __restrict__ y_nhwc) {
+    __shared__ float tile[C][65];
+    const int v = blockIdx.y, p0 = blockIdx.x * 64;
+    const float* src = x + (size_t)v * C * HW;
+    for (int i = threadIdx.x; i < C * 64; i += 256) {
+        const int c = i / 64, p = i % 64;
+        float t = 0.f;
+        if (p0 + p < HW) {
+            t = src[(size_t)c * HW + p0 + p];
+            if (ACT) {
+                t = t * ss[c] + ss[C + c];
+                t = t >= 0.f ? t : t * slope;
+                if (y_nchw) y_nchw[((size_t)v * C + c) * HW + p0 + p] = t;
+            }
+        }
+        tile[c][p] = t;
+    }
+    if (!y_nhwc) return;
+    __syncthreads();
+    float* dst = y_nhwc + (size_t)v * HW * C;
+    for (int i = threadIdx.x; i < C * 64; i += 256) {
+        const int p = i / C, c = i % C;
+        if (p0 + p < HW) dst[(size_t)(p0 + p) * C + c] = tile[c][p];
+    }
+}
+
+// launches k_nchw_to_nhwc<C, ACT> for the runtime channel count C, one of C0, Cs... (the caller has checked it; the last one is the fallback)
+template <bool ACT, int C0, int... Cs>
+void launch_nchw_to_nhwc(int C, const float* x, const float* ss, float slope, int V, long long HW, float* y_nchw, float* y_nhwc, hipStream_t s) {
+    if constexpr (sizeof...(Cs) > 0) {
+        if (C != C0) return launch_nchw_to_nhwc<ACT, Cs...>(C, x, ss, slope, V, HW, y_nchw, y_nhwc, s);
+    }
+    hipLaunchKernelGGL((k_nchw_to_nhwc<C0, ACT>), dim3(cdiv(HW, 64), V), dim3(256), 0, s, x, ss, slope, (int)HW, y_nchw, y_nhwc);
+}
+
+}  // namespace
+}  // namespace o2345

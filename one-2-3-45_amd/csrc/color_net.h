@@ -5,14 +5,11 @@
 #pragma once
 #include "common.h"
 #include "geom_math.h"
+#include "split_f16.h"
 
 namespace o2345 {
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
 #define MFMA32(a, b, c) __builtin_amdgcn_mfma_f32_32x32x2f32((a), (b), (c), 0, 0, 0)
-typedef _Float16 h16x8 __attribute__((ext_vector_type(8)));
-typedef __fp16 h16x2 __attribute__((ext_vector_type(2)));
-#define MFMA_F16(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_f16((a), (b), (c), 0, 0, 0)
 
 // ---- blob layout (floats) -- must match weights.CM_SEGS / CM_BIAS -------------------------------------------------
 constexpr int CM_A_RD0 = 0;                         // [1][2][64]
@@ -129,33 +126,9 @@ __device__ __forceinline__ void cm_run(f32x16 (&acc)[NB], const float* A /* + la
     }
 }
 
-// split-f16 form of the same step loop: b[] is the per-half operand list of the fp32 form, consumed 8 per MFMA step
-struct Split8 { h16x8 hi, lo; };
-typedef _Float16 hh16x2 __attribute__((ext_vector_type(2)));
-// hi = f16(x) rounded toward zero, lo = f16(x - hi) with the exact difference from one v_fma_mix_f32 (see csrc/sdf_mlp_x3.hip)
-__device__ __forceinline__ float opaque_minus_one() {
-    float m1 = -1.f;
-    asm volatile("" : "+v"(m1));
-    return m1;
-}
-template <int N>
-__device__ __forceinline__ Split8 split8(const float (&b)[N], int s0, float m1) {      // s0 compile-time after unrolling
-    union { h16x8 v8; h16x2 v2[4]; hh16x2 w2[4]; } hi, lo;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const float x = (s0 + 2 * i < N) ? b[s0 + 2 * i < N ? s0 + 2 * i : 0] : 0.f;
-        const float y = (s0 + 2 * i + 1 < N) ? b[s0 + 2 * i + 1 < N ? s0 + 2 * i + 1 : 0] : 0.f;
-        hi.v2[i] = __builtin_amdgcn_cvt_pkrtz(x, y);
-        // (the v_fma_mixlo_f16 / v_fma_mixhi_f16 form of csrc/sdf_mlp_x3.hip was measured here too: 40.9 vs 39.6 ms for k_color_pts -- the two-instruction
-        // asm block constrains the scheduler more than it saves -- so the colour kernels keep the three-instruction C form; -DO2345_COLOR_SPLIT_MIXLO=1: A/B)
-#if defined(O2345_COLOR_SPLIT_MIXLO) && O2345_COLOR_SPLIT_MIXLO
-        lo.v2[i] = __builtin_bit_cast(h16x2, split_lo_pair_bits(__builtin_bit_cast(unsigned, hi.v2[i]), x, y));
-#else
-        lo.v2[i] = __builtin_amdgcn_cvt_pkrtz(__builtin_fmaf((float)hi.w2[i][0], m1, x), __builtin_fmaf((float)hi.w2[i][1], m1, y));
-#endif
-    }
-    return {hi.v8, lo.v8};
-}
+// split-f16 form of the same step loop (csrc/split_f16.h): b[] is the per-half operand list of the fp32 form, consumed 8 per MFMA step.  lo in the
+// C form: the asm form measured 40.9 vs 39.6 ms for k_color_pts (the two-instruction asm block constrains the scheduler more than it saves).
+// The three MFMA loops are written out here: routed through mfma_x3 they come out with a different register assignment in k_color_pts.
 template <int NB, int N>
 __device__ __forceinline__ void cx_run(f32x16 (&acc)[NB], const float4* A /* segment + lane */, const float (&b)[N], float m1) {
     constexpr int NS = (N + 7) / 8;

@@ -2,7 +2,7 @@
 // `FeatureNet`; models/sparse_sdf_network.py:171-173 `compress_layer`).  nn.Conv2d + InPlaceABN pairs become ONE pass per layer:
 //
 //   * the convolution reads the RAW output of the previous convolution and applies that layer's batch-norm + leaky ReLU while it stages
-//     the input tile in LDS (y = max(t, slope t), t = x scale + shift -- the same arithmetic as the stand-alone ABN kernel of sparse.hip);
+//     the input tile in LDS (y = max(t, slope t), t = x scale + shift -- the same arithmetic as k_nchw_to_nhwc<C, true> of block_kernels.h);
 //   * it writes its own raw output once and, for layers followed by InPlaceABN, the per-channel sum / sum of squares of its tile
 //     (fp32 inside a wave, doubles across waves and blocks, fixed order: deterministic);  k_conv_stats_finish turns them into the
 //     (scale, shift) pair the NEXT kernel applies on load.  The activated tensor is never materialised unless a caller asks for it.
@@ -11,6 +11,8 @@
 // ([cin][ky][kx][cout] packing: the cout weights of one tap are one s_load_dwordx8/x16, the FMAs take them as SGPR operands); a thread owns one
 // output pixel and all (or a block's share of the) output channels.  8 views x 256^2: 17.8 GFLOP for all 16 convolutions.
 #include "common.h"
+#include "block_kernels.h"
+#include "split_f16.h"
 
 namespace o2345 {
 
@@ -143,25 +145,10 @@ __global__ __launch_bounds__(256) void k_conv2d(ConvArgs a) {
 // one block per channel: batch statistics -> (scale, shift) of InPlaceABN (|gamma| + eps convention selectable, as in sparse.hip)
 __global__ __launch_bounds__(256) void k_conv_stats_finish(const double* __restrict__ part, int nblk, double count, int C, const float* __restrict__ gamma,
                                                            const float* __restrict__ beta, float eps, int abs_gamma, float* __restrict__ scale_shift) {
-    __shared__ double sm[2][4];
     const int c = blockIdx.x;
     double s = 0.0, q = 0.0;
     for (int b = threadIdx.x; b < nblk; b += 256) { s += part[((size_t)c * nblk + b) * 2]; q += part[((size_t)c * nblk + b) * 2 + 1]; }
-    for (int off = 32; off; off >>= 1) { s += __shfl_xor(s, off); q += __shfl_xor(q, off); }
-    if ((threadIdx.x & 63) == 0) { sm[0][threadIdx.x >> 6] = s; sm[1][threadIdx.x >> 6] = q; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        s = (sm[0][0] + sm[0][1]) + (sm[0][2] + sm[0][3]);
-        q = (sm[1][0] + sm[1][1]) + (sm[1][2] + sm[1][3]);
-        const double mean = s / count;
-        double var = q / count - mean * mean;
-        if (var < 0.0) var = 0.0;
-        float g = gamma[c];
-        if (abs_gamma) g = fabsf(g) + eps;
-        const float inv = (float)(1.0 / sqrt(var + (double)eps));
-        scale_shift[c] = g * inv;
-        scale_shift[C + c] = beta[c] - (float)mean * g * inv;
-    }
+    if (block_sum2_256(s, q)) abn_scale_shift(s, q, count, c, C, gamma, beta, eps, abs_gamma, scale_shift);
 }
 
 // nn.Conv2d weight [COUT][CIN][K][K] -> [CIN][K][K][COUT]
@@ -172,47 +159,15 @@ __global__ void k_conv_pack(const float* __restrict__ w, int cout, int cin, int 
     out[i] = w[((size_t)co * cin + ci) * kk + t];
 }
 
-// stand-alone application of a (scale, shift) pair + leaky ReLU: NCHW and / or channel-last output (the compress layer's feature maps)
-template <int C>
-__global__ __launch_bounds__(256) void k_ss_apply(const float* __restrict__ x /*[V,C,HW]*/, const float* __restrict__ ss, float slope, int HW,
-                                                  float* __restrict__ y_nchw, float* __restrict__ y_nhwc) {
-    __shared__ float tile[C][65];
-    const int v = blockIdx.y, p0 = blockIdx.x * 64;
-    const float* src = x + (size_t)v * C * HW;
-    for (int i = threadIdx.x; i < C * 64; i += 256) {
-        const int c = i / 64, p = i % 64;
-        float t = 0.f;
-        if (p0 + p < HW) {
-            t = src[(size_t)c * HW + p0 + p] * ss[c] + ss[C + c];
-            t = t >= 0.f ? t : t * slope;
-            if (y_nchw) y_nchw[((size_t)v * C + c) * HW + p0 + p] = t;
-        }
-        tile[c][p] = t;
-    }
-    if (!y_nhwc) return;
-    __syncthreads();
-    float* dst = y_nhwc + (size_t)v * HW * C;
-    for (int i = threadIdx.x; i < C * 64; i += 256) {
-        const int p = i / C, c = i % C;
-        if (p0 + p < HW) dst[(size_t)(p0 + p) * C + c] = tile[c][p];
-    }
-}
-
 // ---- matrix-core form (default numerical mode, config.py "f16x3") ---------------------------------------------------------------------------
 // The same convolution as an implicit GEMM  D[co][pixel] = sum over (tap, ci) W[co][ci][tap] * act(in)[ci][pixel + tap]  on
-// v_mfma_f32_32x32x16_f16 in the split-f16 form of csrc/sparse_mfma.hip (hi*hi + hi*lo + lo*hi, fp32 accumulate, fp32-class accuracy).
+// v_mfma_f32_32x32x16_f16 in the split-f16 form of csrc/split_f16.h (hi*hi + hi*lo + lo*hi, fp32 accumulate, fp32-class accuracy).
 // A wave owns ROWS row segments of 32 output pixels (B column = lane & 31) and all <= 32 output channels; a k step is (tap, 16-channel group):
 // the two wave halves supply 8 input channels each.  A workgroup (4 waves, 32 x 4*ROWS output pixels) stages its whole input tile once, all
 // channels: activation (the producer's ABN, on load) and the f16 split happen ONCE per staged value, the halves go to LDS as 16-byte items
 // [hi|lo][channel octet][pixel] so that a B operand is one conflict-free ds_read_b128; one barrier, then the wave runs its K*K*CINP/16 steps.
 // The A operands (weights, [tap][group][hi|lo][64 lanes][8 f16], packed by k_conv_pack_x3) stream from L2 through a buffer descriptor a few
 // steps ahead -- 2 KB per step, identical for every wave of the grid.
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-typedef _Float16 h16x8 __attribute__((ext_vector_type(8)));
-typedef __fp16 h16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 hh16x2 __attribute__((ext_vector_type(2)));
-#define MFMA_F16(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_f16((a), (b), (c), 0, 0, 0)
-
 struct AOpX { h16x8 hi, lo; };
 __device__ __forceinline__ AOpX conv_a_fetch(__amdgpu_buffer_rsrc_t rs, int step, int lane) {
     AOpX r;
@@ -239,8 +194,7 @@ __global__ __launch_bounds__(256) void k_conv2d_x3(ConvArgs a, int cin, int cout
     const int gx0 = bx * 32 * STRIDE - PAD, gy0 = by * TH * STRIDE - PAD;
     const float* src = a.in + (size_t)v * a.view_stride;
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)a.w, 0, K * K * NU * 2048, 0x00020000);
-    float m1 = -1.f;
-    asm volatile("" : "+v"(m1));                                                 // keeps fma(hi, -1, x) a v_fma_mix_f32 (see sdf_mlp_x3.hip)
+    const float m1 = opaque_minus_one();
     // ---- stage the whole input tile, all channel groups at once: ONE global round trip per tile (staging group by group exposed one HBM latency
     //      per group and two barriers -- the matrix pipe was busy 23 % of the time); loads are unconditional (clamped pixel / channel), what lies
     //      outside the image or beyond cin is zeroed after the activation (zero padding applies to the ACTIVATED input)
@@ -277,12 +231,9 @@ __global__ __launch_bounds__(256) void k_conv2d_x3(ConvArgs a, int cin, int cout
                         }
                         x[t] = (pix_in[jj] && c < cin) ? val : 0.f;
                     }
-                    union { h16x8 v8; h16x2 v2[4]; hh16x2 w2[4]; float4 f4; } bh, bl;
+                    union { h16x2 v2[4]; float4 f4; } bh, bl;
 #pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        bh.v2[q] = __builtin_amdgcn_cvt_pkrtz(x[2 * q], x[2 * q + 1]);
-                        bl.v2[q] = __builtin_amdgcn_cvt_pkrtz(__builtin_fmaf((float)bh.w2[q][0], m1, x[2 * q]), __builtin_fmaf((float)bh.w2[q][1], m1, x[2 * q + 1]));
-                    }
+                    for (int q = 0; q < 4; ++q) split_pair(x[2 * q], x[2 * q + 1], m1, bh.v2[q], bl.v2[q]);
                     plane[0][oct][r] = bh.f4;
                     plane[1][oct][r] = bl.f4;
                 }
@@ -379,8 +330,7 @@ __global__ __launch_bounds__(256) void k_conv2d_x3_staged(ConvArgs a, int cin, i
     const int gx0 = bx * 32 * STRIDE - PAD, gy0 = by * TH * STRIDE - PAD;
     const float* src = a.in + (size_t)v * a.view_stride;
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)a.w, 0, K * K * NU * 2048, 0x00020000);
-    float m1 = -1.f;
-    asm volatile("" : "+v"(m1));                                                 // keeps fma(hi, -1, x) a v_fma_mix_f32 (see sdf_mlp_x3.hip)
+    const float m1 = opaque_minus_one();
     f32x16 acc[ROWS];
 #pragma unroll
     for (int r = 0; r < ROWS; ++r)
@@ -427,11 +377,10 @@ __global__ __launch_bounds__(256) void k_conv2d_x3_staged(ConvArgs a, int cin, i
                         val = fmaxf(val, val * a.slope);
                     }
                     val = (pix_in[jj] && c < cin) ? val : 0.f;
-                    union { h16x2 v2; hh16x2 w2; } bh, bl;
-                    bh.v2 = __builtin_amdgcn_cvt_pkrtz(val, 0.f);
-                    bl.v2 = __builtin_amdgcn_cvt_pkrtz(__builtin_fmaf((float)bh.w2[0], m1, val), 0.f);
-                    ph[8 * r] = bh.w2[0];
-                    pl[8 * r] = bl.w2[0];
+                    _Float16 hi, lo;
+                    split_one(val, m1, hi, lo);
+                    ph[8 * r] = hi;
+                    pl[8 * r] = lo;
                 }
             }
         } else {
@@ -452,12 +401,9 @@ __global__ __launch_bounds__(256) void k_conv2d_x3_staged(ConvArgs a, int cin, i
                         }
                         x[t] = (pix_in[jj] && c < cin) ? val : 0.f;
                     }
-                    union { h16x8 v8; h16x2 v2[4]; hh16x2 w2[4]; float4 f4; } bh, bl;
+                    union { h16x2 v2[4]; float4 f4; } bh, bl;
 #pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        bh.v2[q] = __builtin_amdgcn_cvt_pkrtz(x[2 * q], x[2 * q + 1]);
-                        bl.v2[q] = __builtin_amdgcn_cvt_pkrtz(__builtin_fmaf((float)bh.w2[q][0], m1, x[2 * q]), __builtin_fmaf((float)bh.w2[q][1], m1, x[2 * q + 1]));
-                    }
+                    for (int q = 0; q < 4; ++q) split_pair(x[2 * q], x[2 * q + 1], m1, bh.v2[q], bl.v2[q]);
                     plane[0][oct][r] = bh.f4;
                     plane[1][oct][r] = bl.f4;
                 }
@@ -684,12 +630,7 @@ int o2345_conv2d_x3(const float* in, int V, int cin, int Hi, int Wi, int in_pixe
 int o2345_scale_shift_act(const float* x, int V, int C, int H, int W, const float* scale_shift, float slope, float* y_nchw, float* y_nhwc, void* stream) {
     O2345_REQUIRE(x && scale_shift && (y_nchw || y_nhwc), "scale_shift_act: null pointer");
     O2345_REQUIRE(C == 8 || C == 16 || C == 32, "scale_shift_act: C must be 8, 16 or 32 (got %d)", C);
-    const long long HW = (long long)H * W;
-    const dim3 grid(cdiv(HW, 64), V);
-    hipStream_t s = (hipStream_t)stream;
-    if (C == 32) hipLaunchKernelGGL(k_ss_apply<32>, grid, dim3(256), 0, s, x, scale_shift, slope, (int)HW, y_nchw, y_nhwc);
-    else if (C == 16) hipLaunchKernelGGL(k_ss_apply<16>, grid, dim3(256), 0, s, x, scale_shift, slope, (int)HW, y_nchw, y_nhwc);
-    else hipLaunchKernelGGL(k_ss_apply<8>, grid, dim3(256), 0, s, x, scale_shift, slope, (int)HW, y_nchw, y_nhwc);
+    launch_nchw_to_nhwc<true, 32, 16, 8>(C, x, scale_shift, slope, V, (long long)H * W, y_nchw, y_nhwc, (hipStream_t)stream);
     return check_launch("scale_shift_act");
 }
 

@@ -15,10 +15,9 @@
 #include "common.h"
 #include "geom_math.h"
 #include "costvol_math.h"
+#include "block_kernels.h"
 
 namespace o2345 {
-
-constexpr int IDX_BLOCK = 256;
 
 // ---- pass 1a: visible-view count per voxel + per-block number of kept voxels -----------------------------------
 __global__ __launch_bounds__(IDX_BLOCK) void k_vis_count(const float* __restrict__ proj, int V, int H, int W, VolGeom g,
@@ -37,31 +36,6 @@ __global__ __launch_bounds__(IDX_BLOCK) void k_vis_count(const float* __restrict
     int tot;
     (void)block_prefix<IDX_BLOCK / 64>(v < nvox && c > min_views, wtot, tot);
     if (threadIdx.x == 0) block_tot[blockIdx.x] = tot;
-}
-
-// ---- generic: exclusive scan of n ints by ONE 1024-thread block (n <= a few 100k block totals) -----------------
-__global__ __launch_bounds__(1024) void k_scan_small(int* __restrict__ a, int n, int* __restrict__ total) {
-    __shared__ int part[1024];
-    const int t = threadIdx.x;
-    const int per = (n + 1023) / 1024;
-    const int lo = t * per, hi = min(n, lo + per);
-    int s = 0;
-    for (int i = lo; i < hi; ++i) s += a[i];
-    part[t] = s;
-    __syncthreads();
-    for (int off = 1; off < 1024; off <<= 1) {       // Hillis-Steele inclusive scan over the 1024 partials
-        int v = (t >= off) ? part[t - off] : 0;
-        __syncthreads();
-        part[t] += v;
-        __syncthreads();
-    }
-    int run = part[t] - s;
-    for (int i = lo; i < hi; ++i) {
-        int v = a[i];
-        a[i] = run;
-        run += v;
-    }
-    if (t == 1023) *total = part[1023];
 }
 
 // ---- pass 1b: assign rows in voxel (x-major) order ---------------------------------------------------------------
@@ -252,26 +226,6 @@ __global__ __launch_bounds__(256) void k_prune_dilate(const float* __restrict__ 
     out[v] = hit ? 1 : 0;
 }
 
-// ---- NCHW -> NHWC re-layout of the (compressed) feature maps: [V,C,H,W] -> [V,H,W,C] ---------------------------
-// 64-pixel x C tile through LDS so that both the read and the write are coalesced.
-template <int C>
-__global__ __launch_bounds__(256) void k_nchw_to_nhwc(const float* __restrict__ in, float* __restrict__ out, int HW) {
-    __shared__ float tile[C][65];
-    const int v = blockIdx.y;
-    const int p0 = blockIdx.x * 64;
-    const float* src = in + (size_t)v * C * HW;
-    float* dst = out + (size_t)v * HW * C;
-    for (int i = threadIdx.x; i < C * 64; i += 256) {
-        int c = i / 64, p = i % 64;
-        tile[c][p] = (p0 + p < HW) ? src[(size_t)c * HW + p0 + p] : 0.f;
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < C * 64; i += 256) {
-        int p = i / C, c = i % C;
-        if (p0 + p < HW) dst[(size_t)(p0 + p) * C + c] = tile[c][p];
-    }
-}
-
 // ---- a7: rows -> dense volumes ------------------------------------------------------------------------------------
 template <int C>
 __global__ __launch_bounds__(256) void k_scatter_dense(const float* __restrict__ rows /*[N,C]*/,
@@ -325,7 +279,7 @@ int o2345_costvol_index(const float* proj, int V, int H, int W, int dx, int dy, 
     hipStream_t s = (hipStream_t)stream;
     int* block_tot = (int*)workspace;
     hipLaunchKernelGGL(k_vis_count, dim3(nb), dim3(IDX_BLOCK), 0, s, proj, V, H, W, g, min_views, cnt, block_tot);
-    hipLaunchKernelGGL(k_scan_small, dim3(1), dim3(1024), 0, s, block_tot, (int)nb, n_rows_dev);
+    hipLaunchKernelGGL(k_scan_small<int>, dim3(1), dim3(1024), 0, s, block_tot, (int)nb, n_rows_dev);
     hipLaunchKernelGGL(k_vis_assign, dim3(nb), dim3(IDX_BLOCK), 0, s, cnt, g, min_views, block_tot, row_of_voxel, coords);
     return check_launch("costvol_index");
 }
@@ -386,11 +340,7 @@ int o2345_prune_dilate(const float* sdf, const float* mask, int D, float thresho
 int o2345_nchw_to_nhwc(const float* in, float* out, int V, int C, int H, int W, void* stream) {
     O2345_REQUIRE(in && out, "nchw_to_nhwc: null pointer");
     O2345_REQUIRE(C == 16 || C == 8 || C == 64, "nchw_to_nhwc: C must be 8, 16 or 64 (got %d)", C);
-    dim3 grid(cdiv((long long)H * W, 64), V);
-    hipStream_t s = (hipStream_t)stream;
-    if (C == 16) hipLaunchKernelGGL(k_nchw_to_nhwc<16>, grid, dim3(256), 0, s, in, out, H * W);
-    else if (C == 8) hipLaunchKernelGGL(k_nchw_to_nhwc<8>, grid, dim3(256), 0, s, in, out, H * W);
-    else hipLaunchKernelGGL(k_nchw_to_nhwc<64>, grid, dim3(256), 0, s, in, out, H * W);
+    launch_nchw_to_nhwc<false, 16, 8, 64>(C, in, nullptr, 0.f, V, (long long)H * W, nullptr, out, (hipStream_t)stream);
     return check_launch("nchw_to_nhwc");
 }
 
@@ -412,6 +362,6 @@ int o2345_scatter_dense(const float* rows, const int32_t* row_of_voxel, int C, l
 namespace o2345 {
 int preload_costvol() {
     hipFuncAttributes at;
-    return (int)hipFuncGetAttributes(&at, (const void*)(k_scan_small));
+    return (int)hipFuncGetAttributes(&at, (const void*)(k_scan_small<int>));
 }
 }  // namespace o2345

@@ -7,6 +7,7 @@
 // cell in traversal order, table order inside a cell.  Deterministic: counts -> exclusive scans -> emit, no atomics.
 // Everything stays on the device; u (67 MB at 256^3) is read three times, HBM-bound.
 #include "common.h"
+#include "block_kernels.h"
 #include <math.h>
 #include "mc_tables.h"
 
@@ -108,26 +109,6 @@ __global__ __launch_bounds__(256) void k_mc_count(const float* __restrict__ u, M
     (void)block_scan_excl(sv, lds, tv);
     (void)block_scan_excl(st, lds, tt);
     if (threadIdx.x == 0) { vblock[blockIdx.x] = tv; tblock[blockIdx.x] = tt; }
-}
-
-__global__ __launch_bounds__(1024) void k_scan_small3(int* __restrict__ a, int n, long long* __restrict__ total) {
-    __shared__ int part[1024];
-    const int t = threadIdx.x;
-    const int per = (n + 1023) / 1024;
-    const int lo = t * per, hi = min(n, lo + per);
-    int s = 0;
-    for (int i = lo; i < hi; ++i) s += a[i];
-    part[t] = s;
-    __syncthreads();
-    for (int off = 1; off < 1024; off <<= 1) {
-        int v = (t >= off) ? part[t - off] : 0;
-        __syncthreads();
-        part[t] += v;
-        __syncthreads();
-    }
-    int run = part[t] - s;
-    for (int i = lo; i < hi; ++i) { int v = a[i]; a[i] = run; run += v; }
-    if (t == 1023) *total = (long long)part[1023];
 }
 
 __global__ __launch_bounds__(256) void k_mc_offsets(McGrid g, const uint8_t* __restrict__ vcnt, const uint16_t* __restrict__ tcase,
@@ -246,8 +227,8 @@ int o2345_marching_cubes_count(const float* u, int n0, int n1, int n2, double is
     const unsigned nb = (unsigned)((n + MC_TILE - 1) / MC_TILE);
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(k_mc_count, dim3(nb), dim3(256), 0, s, u, g, vcnt, tcase, vblock, tblock);
-    hipLaunchKernelGGL(k_scan_small3, dim3(1), dim3(1024), 0, s, vblock, (int)nb, totals);
-    hipLaunchKernelGGL(k_scan_small3, dim3(1), dim3(1024), 0, s, tblock, (int)nb, totals + 1);
+    hipLaunchKernelGGL(k_scan_small<long long>, dim3(1), dim3(1024), 0, s, vblock, (int)nb, totals);
+    hipLaunchKernelGGL(k_scan_small<long long>, dim3(1), dim3(1024), 0, s, tblock, (int)nb, totals + 1);
     hipLaunchKernelGGL(k_mc_offsets, dim3(nb), dim3(256), 0, s, g, vcnt, tcase, vblock, tblock, vbase, tbase);
     int rc = check_launch("marching_cubes_count");
     if (rc) return rc;
@@ -283,6 +264,6 @@ int o2345_marching_cubes_emit(const float* u, int n0, int n1, int n2, double iso
 namespace o2345 {
 int preload_mcubes() {
     hipFuncAttributes at;
-    return (int)hipFuncGetAttributes(&at, (const void*)(k_scan_small3));
+    return (int)hipFuncGetAttributes(&at, (const void*)(k_scan_small<long long>));
 }
 }  // namespace o2345

@@ -3,10 +3,9 @@
 #include "common.h"
 #include "geom_math.h"
 #include "pe_math.h"
+#include "split_f16.h"
 
 namespace o2345 {
-
-using f32x16 = __attribute__((ext_vector_type(16))) float;
 
 // ---- blob geometry (must match one-2-3-45_amd/weights.py) --------------------------------------------------------
 constexpr int ST0 = 20;          // layer-0 k steps  (40 PE slots = 39 + 1 pad)

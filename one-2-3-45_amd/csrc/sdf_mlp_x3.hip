@@ -1,50 +1,18 @@
-// SDF network on the f16 matrix cores at fp32-class accuracy ("f16x3" split precision).
+// SDF network on the f16 matrix cores at fp32-class accuracy ("f16x3" split precision, csrc/split_f16.h).
 //
 // v_mfma_f32_32x32x2_f32 runs at 1/16 of the f16/bf16 matrix rate, and csrc/sdf_mlp.hip is bound by it.  Here every fp32
-// operand x is split into two halves, x = hi + lo with hi = f16(x), lo = f16(x - hi) (22 significant bits together; gfx950's
-// MFMA honours f16 subnormals and forms exact products, checked on hardware), and a product of two such operands is
-// accumulated in fp32 as  hi*hi + hi*lo + lo*hi  (the dropped lo*lo term is 2^-22 relative): three
-// v_mfma_f32_32x32x16_f16 per 16 k instead of eight fp32 MFMAs, 5.3x less matrix time at ~4e-7 absolute error on O(1)
-// results (the fp32 MFMA chain itself carries ~1e-7).  Weights are split on the host (weights.pack_sdf_blob), activations
-// in registers: hi = f16(x) rounded toward zero, lo = f16(x - hi) with the exact difference from one v_fma_mix_f32:
-// 2 VALU instructions per value.  Domain: |x| < 65504 (activations here are O(1)).
+// operand is split into f16 halves hi + lo and a product costs three v_mfma_f32_32x32x16_f16 per 16 k instead of eight fp32
+// MFMAs: 5.3x less matrix time at ~4e-7 absolute error on O(1) results (the fp32 MFMA chain itself carries ~1e-7).  Weights are
+// split on the host (weights.pack_sdf_blob), activations in registers.  Domain: |x| < 65504 (activations here are O(1)).
 // Lane layout, blob order and the register chaining between layers: two wave halves supply 8 k values each of a 16-k step (weights.kcol_h / neuron_of).
 #include "sdf_common.h"
 
 namespace o2345 {
 
-typedef _Float16 h16x8 __attribute__((ext_vector_type(8)));
-typedef __fp16 h16x2 __attribute__((ext_vector_type(2)));
-#define MFMA_F16(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_f16((a), (b), (c), 0, 0, 0)
-
-struct Split8 { h16x8 hi, lo; };
-
-// hi = f16(x) (round toward zero, two values per v_cvt_pkrtz_f16_f32), lo = f16(x - hi): the subtraction is one
-// v_fma_mix_f32 per value (f16 operand converted in flight, exact incl. f16 subnormals -- checked on hardware).  The
-// multiplier -1 is kept opaque to the optimiser (g_m1), which would otherwise rewrite fma(hi, -1, x) into cvt + sub.
-typedef _Float16 hh16x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ float opaque_minus_one() {
-    float m1 = -1.f;
-    asm volatile("" : "+v"(m1));
-    return m1;
-}
-__device__ __forceinline__ Split8 split8(const float* v, float m1) {
-    union { h16x8 v8; h16x2 v2[4]; hh16x2 w2[4]; unsigned u[4]; } hi, lo;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const float a = v[2 * i], b = v[2 * i + 1];
-        hi.v2[i] = __builtin_amdgcn_cvt_pkrtz(a, b);
-#if O2345_SPLIT_MIXLO
-        lo.u[i] = split_lo_pair_bits(hi.u[i], a, b);
-#else
-        lo.v2[i] = __builtin_amdgcn_cvt_pkrtz(__builtin_fmaf((float)hi.w2[i][0], m1, a), __builtin_fmaf((float)hi.w2[i][1], m1, b));
-#endif
-    }
-    return {hi.v8, lo.v8};
-}
+// lo in the asm form (split_f16.h): k_sdf_grad_x3 falls below the 256-register line and loses its 224 bytes of scratch per lane, 11.9 -> 9.9 ms on 29.5 M points
+constexpr bool MIXLO = true;
 
 // acc[ob] += W[ob][step] * b for NB output blocks, split precision.  A: LDS, [NB][NST][hi|lo][64 lanes] float4.
-// Term-major order: consecutive MFMAs go to different accumulators.
 template <int NB, int NST, int B0 = 0, int B1 = NB>
 __device__ __forceinline__ void mma_x3_part(f32x16 (&acc)[NB], const float4* A, int lane, int step, const Split8& b) {
     h16x8 ahi[B1 - B0], alo[B1 - B0];
@@ -53,12 +21,7 @@ __device__ __forceinline__ void mma_x3_part(f32x16 (&acc)[NB], const float4* A, 
         ahi[ob - B0] = __builtin_bit_cast(h16x8, A[((ob * NST + step) * 2 + 0) * 64 + lane]);
         alo[ob - B0] = __builtin_bit_cast(h16x8, A[((ob * NST + step) * 2 + 1) * 64 + lane]);
     }
-#pragma unroll
-    for (int ob = B0; ob < B1; ++ob) acc[ob] = MFMA_F16(alo[ob - B0], b.hi, acc[ob]);
-#pragma unroll
-    for (int ob = B0; ob < B1; ++ob) acc[ob] = MFMA_F16(ahi[ob - B0], b.lo, acc[ob]);
-#pragma unroll
-    for (int ob = B0; ob < B1; ++ob) acc[ob] = MFMA_F16(ahi[ob - B0], b.hi, acc[ob]);
+    mfma_x3<B1 - B0>(acc + B0, ahi, alo, b);
     __builtin_amdgcn_sched_barrier(0);
 }
 template <int NB, int NST>
@@ -84,7 +47,7 @@ __global__ __launch_bounds__(512) void k_sdf_mlp_x3(SdfArgs a) {
     for (int i = threadIdx.x; i < MISC_SIZE; i += blockDim.x) lds[L_MISC + i] = a.blob[OFFX_MISC + i];           // b0, b1 in the t domain
     __syncthreads();
     const int lane = threadIdx.x & 63, j = lane & 31, h = lane >> 5;
-    const float m1 = opaque_minus_one();
+    const float m1 = opaque_minus_one();         // not read by the asm form of lo, but dropping it re-allocates the kernel's registers
     const float4* A0 = reinterpret_cast<const float4*>(lds + L_A0);
     const float4* A1 = reinterpret_cast<const float4*>(lds + L_A1);
     const float* misc = lds + L_MISC;
@@ -164,7 +127,7 @@ __global__ __launch_bounds__(512) void k_sdf_mlp_x3(SdfArgs a) {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) acc[nb][r] = misc[MISC_B0 + (nb * 16 + r) * 2 + h];
 #pragma unroll
-            for (int s = 0; s < STX0; ++s) mma_x3<4, STX0>(acc, A0, lane, s, split8(pe + 8 * s, m1));
+            for (int s = 0; s < STX0; ++s) mma_x3<4, STX0>(acc, A0, lane, s, split8<MIXLO>(pe, 8 * s, m1));
         }
         Split8 hb[8];                   // softplus(layer 0), split, as the 8 hidden k-step operands of layer 1
 #pragma unroll
@@ -175,7 +138,7 @@ __global__ __launch_bounds__(512) void k_sdf_mlp_x3(SdfArgs a) {
                 const f32x2 sp = softplus_t_pair(f32x2{acc[nb][r], acc[nb][r + 1]});
                 hv[r] = sp[0]; hv[r + 1] = sp[1];
             }
-            hb[2 * nb] = split8(hv, m1); hb[2 * nb + 1] = split8(hv + 8, m1);
+            hb[2 * nb] = split8<MIXLO>(hv, 0, m1); hb[2 * nb + 1] = split8<MIXLO>(hv, 8, m1);
         }
         // ---- layer 1 -------------------------------------------------------------------------------------------------------------------
 #pragma unroll
@@ -184,7 +147,7 @@ __global__ __launch_bounds__(512) void k_sdf_mlp_x3(SdfArgs a) {
             for (int r = 0; r < 16; ++r) acc[nb][r] = misc[MISC_B1 + (nb * 16 + r) * 2 + h];
 #pragma unroll
         for (int s = 0; s < 8; ++s) mma_x3<4, STH1>(acc, A1, lane, s, hb[s]);
-        mma_x3<4, STH1>(acc, A1, lane, 8, split8(lat, m1));
+        mma_x3<4, STH1>(acc, A1, lane, 8, split8<MIXLO>(lat, 0, m1));
         // ---- SDF output row: fp32 dot product ------------------------------------------------------------------------------------------
         float yh = 0.f;
 #pragma unroll
@@ -220,15 +183,6 @@ __device__ __forceinline__ AReg<NB> a_fetch(__amdgpu_buffer_rsrc_t rs, int sec_o
         r.lo[ob] = __builtin_bit_cast(h16x8, __builtin_amdgcn_raw_buffer_load_b128(rs, lane * 16, base + 1024, 0));
     }
     return r;
-}
-template <int NBA, int NB>
-__device__ __forceinline__ void mma_x3_regs(f32x16 (&acc)[NBA], int blk0, const AReg<NB>& A, const Split8& b) {
-#pragma unroll
-    for (int ob = 0; ob < NB; ++ob) acc[blk0 + ob] = MFMA_F16(A.lo[ob], b.hi, acc[blk0 + ob]);
-#pragma unroll
-    for (int ob = 0; ob < NB; ++ob) acc[blk0 + ob] = MFMA_F16(A.hi[ob], b.lo, acc[blk0 + ob]);
-#pragma unroll
-    for (int ob = 0; ob < NB; ++ob) acc[blk0 + ob] = MFMA_F16(A.hi[ob], b.hi, acc[blk0 + ob]);
 }
 
 // SDF + analytic gradient (sparse_sdf_network.py:476-499 obtains it with autograd), every product split-f16.
@@ -303,7 +257,7 @@ __global__ __launch_bounds__(512) void k_sdf_grad_x3(SdfArgs a) {
             }
 #pragma unroll
             for (int t = 0; t < 8; ++t) ylat += misc[MISC_W2L + 8 * h + t] * lat[t];
-            latx = split8(lat, m1);
+            latx = split8<MIXLO>(lat, 0, m1);
         }
         // ---- positional encoding: fp32 values (needed again for sin' / cos') and their split form ----------------------------------
         Split8 pex[STX0];
@@ -322,7 +276,7 @@ __global__ __launch_bounds__(512) void k_sdf_grad_x3(SdfArgs a) {
             pe[19] = h ? 0.f : py;
             pe[20] = pe[21] = pe[22] = pe[23] = 0.f;
 #pragma unroll
-            for (int s = 0; s < STX0; ++s) pex[s] = split8(pe + 8 * s, m1);
+            for (int s = 0; s < STX0; ++s) pex[s] = split8<MIXLO>(pe, 8 * s, m1);
         }
         // sin / cos are needed again for the chain rule at the very end; hi + lo reproduces them to 2^-21 (one v_fma_mix_f32 each),
         // which frees the 18 fp32 registers for the whole network
@@ -344,7 +298,7 @@ __global__ __launch_bounds__(512) void k_sdf_grad_x3(SdfArgs a) {
                 const f32x2 sp = softplus_t_pair(f32x2{acc[nb][r], acc[nb][r + 1]});
                 hv[r] = sp[0]; hv[r + 1] = sp[1];
             }
-            hb[2 * nb] = split8(hv, m1); hb[2 * nb + 1] = split8(hv + 8, m1);
+            hb[2 * nb] = split8<MIXLO>(hv, 0, m1); hb[2 * nb + 1] = split8<MIXLO>(hv, 8, m1);
         }
         // ---- layer 1 ------------------------------------------------------------------------------------------------------------------------
 #pragma unroll
@@ -370,7 +324,7 @@ __global__ __launch_bounds__(512) void k_sdf_grad_x3(SdfArgs a) {
                 yh = fmaf(w2a, v[0], yh); yh = fmaf(w2b, v[1], yh);
                 gv[r] = w2a * d[0]; gv[r + 1] = w2b * d[1];
             }
-            g1x[2 * nb] = split8(gv, m1); g1x[2 * nb + 1] = split8(gv + 8, m1);
+            g1x[2 * nb] = split8<MIXLO>(gv, 0, m1); g1x[2 * nb + 1] = split8<MIXLO>(gv, 8, m1);
         }
         float y0 = fmaf(yh, SOFTPLUS_INV_SCALE, ylat);
         y0 += __shfl_xor(y0, 32);
@@ -386,7 +340,7 @@ __global__ __launch_bounds__(512) void k_sdf_grad_x3(SdfArgs a) {
 #pragma unroll
         for (int s = 0; s < 8; ++s) {
             // streamed blocks first, then their registers are refilled for the next step while the LDS blocks run (single buffer)
-            mma_x3_regs<5, 2>(g, 3, tcur, g1x[s]);
+            mfma_x3<2>(g + 3, tcur.hi, tcur.lo, g1x[s]);
             __builtin_amdgcn_sched_barrier(0);
             if (s + 1 < 8) tcur = a_fetch<2, STHB>(rs, OFFX_A1T, lane, 3, s + 1);
             mma_x3_part<5, STHB, 0, 3>(g, A1T, lane, s, g1x[s]);
@@ -411,8 +365,8 @@ __global__ __launch_bounds__(512) void k_sdf_grad_x3(SdfArgs a) {
             float gv[16];
 #pragma unroll
             for (int r = 0; r < 16; ++r) gv[r] = g[nb][r] * softplus_t_d(a0r[0][r]);
-            mma_x3_regs<2, 2>(gp, 0, ta, split8(gv, m1));
-            mma_x3_regs<2, 2>(gp, 0, tb, split8(gv + 8, m1));
+            mfma_x3<2>(gp, ta.hi, ta.lo, split8<MIXLO>(gv, 0, m1));
+            mfma_x3<2>(gp, tb.hi, tb.lo, split8<MIXLO>(gv, 8, m1));
             __builtin_amdgcn_sched_barrier(0);
         }
         float gx[3] = {0.f, 0.f, 0.f};

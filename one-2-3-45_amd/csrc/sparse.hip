@@ -12,6 +12,7 @@
 // BatchNorm uses batch statistics (the reference never calls .eval()): fp64 column sums in a deterministic
 // two-stage reduction, then a fused normalise + ReLU (+ skip add) pass.
 #include "common.h"
+#include "block_kernels.h"
 
 namespace o2345 {
 
@@ -64,8 +65,6 @@ __global__ void k_mark_coarse(const int* __restrict__ coords, int n, int ts, con
                 flag[((size_t)cand[0][ix] * lc.ny + cand[1][iy]) * lc.nz + cand[2][iz]] = 1;
 }
 
-constexpr int IDX_BLOCK = 256;
-
 __global__ __launch_bounds__(IDX_BLOCK) void k_flag_count(const uint8_t* __restrict__ flag, long long ncell,
                                                           int* __restrict__ block_tot) {
     __shared__ int wtot[IDX_BLOCK / 64];
@@ -73,30 +72,6 @@ __global__ __launch_bounds__(IDX_BLOCK) void k_flag_count(const uint8_t* __restr
     int tot;
     (void)block_prefix<IDX_BLOCK / 64>(v < ncell && flag[v], wtot, tot);
     if (threadIdx.x == 0) block_tot[blockIdx.x] = tot;
-}
-
-__global__ __launch_bounds__(1024) void k_scan_small2(int* __restrict__ a, int n, int* __restrict__ total) {
-    __shared__ int part[1024];
-    const int t = threadIdx.x;
-    const int per = (n + 1023) / 1024;
-    const int lo = t * per, hi = min(n, lo + per);
-    int s = 0;
-    for (int i = lo; i < hi; ++i) s += a[i];
-    part[t] = s;
-    __syncthreads();
-    for (int off = 1; off < 1024; off <<= 1) {
-        int v = (t >= off) ? part[t - off] : 0;
-        __syncthreads();
-        part[t] += v;
-        __syncthreads();
-    }
-    int run = part[t] - s;
-    for (int i = lo; i < hi; ++i) {
-        int v = a[i];
-        a[i] = run;
-        run += v;
-    }
-    if (t == 1023) *total = part[1023];
 }
 
 __global__ __launch_bounds__(IDX_BLOCK) void k_flag_assign(const uint8_t* __restrict__ flag, Lattice l, int ts,
@@ -193,25 +168,10 @@ template <int C>
 __global__ __launch_bounds__(256) void k_col_finish(const double* __restrict__ part, int nblocks, int n, const float* __restrict__ gamma,
                                                     const float* __restrict__ beta, float eps, int abs_gamma,
                                                     float* __restrict__ scale_shift /*[2,C]*/, float* __restrict__ mean_var /*[2,C] or null*/) {
-    __shared__ double sm[2][4];
     const int c = blockIdx.x;
     double s = 0.0, s2 = 0.0;
     for (int b = threadIdx.x; b < nblocks; b += 256) { s += part[((size_t)b * 2 + 0) * C + c]; s2 += part[((size_t)b * 2 + 1) * C + c]; }
-    for (int off = 32; off; off >>= 1) { s += __shfl_xor(s, off); s2 += __shfl_xor(s2, off); }
-    if ((threadIdx.x & 63) == 0) { sm[0][threadIdx.x >> 6] = s; sm[1][threadIdx.x >> 6] = s2; }
-    __syncthreads();
-    if (threadIdx.x != 0) return;
-    s = (sm[0][0] + sm[0][1]) + (sm[0][2] + sm[0][3]);
-    s2 = (sm[1][0] + sm[1][1]) + (sm[1][2] + sm[1][3]);
-    const double mean = s / n;
-    double var = s2 / n - mean * mean;          // biased batch variance
-    if (var < 0.0) var = 0.0;
-    float g = gamma[c];
-    if (abs_gamma) g = fabsf(g) + eps;          // inplace_abn convention
-    const float inv = (float)(1.0 / sqrt(var + (double)eps));
-    scale_shift[c] = g * inv;
-    scale_shift[C + c] = beta[c] - (float)mean * g * inv;
-    if (mean_var) { mean_var[c] = (float)mean; mean_var[C + c] = (float)var; }
+    if (block_sum2_256(s, s2)) abn_scale_shift(s, s2, (double)n, c, C, gamma, beta, eps, abs_gamma, scale_shift, mean_var);
 }
 
 // x: [n, C] rows (channel-last).  slope = 0 -> ReLU, 0.01 -> leaky ReLU (InPlaceABN).  skip may be null.
@@ -258,6 +218,7 @@ __global__ __launch_bounds__(256) void k_nchw_partial(const float* __restrict__ 
     }
 }
 
+// one thread per channel, partials summed serially in index order (the tree order of k_col_finish would change the results in the last bits)
 __global__ void k_nchw_finish(const double* __restrict__ part, int nb_per_c, long long count, int C,
                               const float* __restrict__ gamma, const float* __restrict__ beta, float eps, int abs_gamma,
                               float* __restrict__ scale_shift) {
@@ -265,41 +226,7 @@ __global__ void k_nchw_finish(const double* __restrict__ part, int nb_per_c, lon
     if (c >= C) return;
     double s = 0.0, s2 = 0.0;
     for (int b = 0; b < nb_per_c; ++b) { s += part[((size_t)c * nb_per_c + b) * 2]; s2 += part[((size_t)c * nb_per_c + b) * 2 + 1]; }
-    const double mean = s / count;
-    double var = s2 / count - mean * mean;
-    if (var < 0.0) var = 0.0;
-    float g = gamma[c];
-    if (abs_gamma) g = fabsf(g) + eps;
-    const float inv = (float)(1.0 / sqrt(var + (double)eps));
-    scale_shift[c] = g * inv;
-    scale_shift[C + c] = beta[c] - (float)mean * g * inv;
-}
-
-// fused normalise + leaky ReLU + NCHW -> NHWC re-layout (the cost-volume gather wants channel-last maps)
-template <int C>
-__global__ __launch_bounds__(256) void k_abn_apply_nhwc(const float* __restrict__ x /*[V,C,HW]*/,
-                                                        const float* __restrict__ scale_shift, float slope, int HW,
-                                                        float* __restrict__ y_nchw /*or null*/, float* __restrict__ y_nhwc /*or null*/) {
-    __shared__ float tile[C][65];
-    const int v = blockIdx.y, p0 = blockIdx.x * 64;
-    const float* src = x + (size_t)v * C * HW;
-    for (int i = threadIdx.x; i < C * 64; i += 256) {
-        const int c = i / 64, p = i % 64;
-        float t = 0.f;
-        if (p0 + p < HW) {
-            t = src[(size_t)c * HW + p0 + p] * scale_shift[c] + scale_shift[C + c];
-            t = t >= 0.f ? t : t * slope;
-            if (y_nchw) y_nchw[((size_t)v * C + c) * HW + p0 + p] = t;
-        }
-        tile[c][p] = t;
-    }
-    if (!y_nhwc) return;
-    __syncthreads();
-    float* dst = y_nhwc + (size_t)v * HW * C;
-    for (int i = threadIdx.x; i < C * 64; i += 256) {
-        const int p = i / C, c = i % C;
-        if (p0 + p < HW) dst[(size_t)(p0 + p) * C + c] = tile[c][p];
-    }
+    abn_scale_shift(s, s2, (double)count, c, C, gamma, beta, eps, abs_gamma, scale_shift);
 }
 
 }  // namespace o2345
@@ -336,7 +263,7 @@ int o2345_sparse_downsample(const int32_t* coords_fine, int n_fine, int ts, int 
         hipLaunchKernelGGL(k_mark_coarse, dim3(cdiv(n_fine, 256)), dim3(256), 0, s, coords_fine, n_fine, ts, cmin, lc, flag);
     }
     hipLaunchKernelGGL(k_flag_count, dim3(nb), dim3(IDX_BLOCK), 0, s, flag, ncell, block_tot);
-    hipLaunchKernelGGL(k_scan_small2, dim3(1), dim3(1024), 0, s, block_tot, (int)nb, n_coarse_dev);
+    hipLaunchKernelGGL(k_scan_small<int>, dim3(1), dim3(1024), 0, s, block_tot, (int)nb, n_coarse_dev);
     hipLaunchKernelGGL(k_flag_assign, dim3(nb), dim3(IDX_BLOCK), 0, s, flag, lc, 2 * ts, block_tot, row_of_cell, coords_coarse);
     return check_launch("sparse_downsample");
 }
@@ -408,10 +335,7 @@ int o2345_abn_nchw(const float* x, int V, int C, int H, int W, const float* gamm
     float* ss = (float*)(part + (size_t)C * nbc * 2);
     hipLaunchKernelGGL(k_nchw_partial, dim3(nbc, C), dim3(256), 0, s, x, V, C, HW, part, nbc);
     hipLaunchKernelGGL(k_nchw_finish, dim3(1), dim3(64), 0, s, part, nbc, (long long)V * HW, C, gamma, beta, eps, abs_gamma, ss);
-    dim3 grid(cdiv(HW, 64), V);
-    if (C == 32) hipLaunchKernelGGL(k_abn_apply_nhwc<32>, grid, dim3(256), 0, s, x, ss, slope, (int)HW, y_nchw, y_nhwc);
-    else if (C == 16) hipLaunchKernelGGL(k_abn_apply_nhwc<16>, grid, dim3(256), 0, s, x, ss, slope, (int)HW, y_nchw, y_nhwc);
-    else hipLaunchKernelGGL(k_abn_apply_nhwc<8>, grid, dim3(256), 0, s, x, ss, slope, (int)HW, y_nchw, y_nhwc);
+    launch_nchw_to_nhwc<true, 32, 16, 8>(C, x, ss, slope, V, HW, y_nchw, y_nhwc, s);      // normalise + leaky ReLU + NCHW -> NHWC in one pass
     return check_launch("abn_nchw");
 }
 

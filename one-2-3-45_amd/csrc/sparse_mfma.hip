@@ -3,7 +3,7 @@
 //
 //   out[co][row] = sum over (neighbour k, input channel ci) of  W[k][ci][co] * in[ nbr(row, k) ][ci]
 //
-// D[co][row] on v_mfma_f32_32x32x16_f16 in the split-f16 form of csrc/sdf_mlp_x3.hip (hi*hi + hi*lo + lo*hi, fp32 accumulate,
+// D[co][row] on v_mfma_f32_32x32x16_f16 in the split-f16 form of csrc/split_f16.h (hi*hi + hi*lo + lo*hi, fp32 accumulate,
 // fp32-class accuracy): a wave owns 32 output rows (B column = lane & 31); the two wave halves supply 8 input channels each of
 // one 16-channel group of one neighbour, so a k step is (neighbour, channel group).  The B operand is gathered straight
 // from the neighbour's row (two dwordx4 per lane) and split in registers; the A operand (weights, [27][CIN/16][blocks][hi|lo]
@@ -12,14 +12,9 @@
 // (wave-uniform ballot), which removes 7/8 of the steps of the transposed mode.
 // The thread-per-row fp32 VALU kernel remains the strict-fp32 path.
 #include "common.h"
+#include "split_f16.h"
 
 namespace o2345 {
-
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-typedef _Float16 h16x8 __attribute__((ext_vector_type(8)));
-typedef __fp16 h16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 hh16x2 __attribute__((ext_vector_type(2)));
-#define MFMA_F16(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_f16((a), (b), (c), 0, 0, 0)
 
 struct Lattice3 { int nx, ny, nz; };
 
@@ -65,8 +60,7 @@ __global__ __launch_bounds__(LDSW ? 1024 : 256) void k_sparse_conv_x3(const floa
     }
     const int lane = threadIdx.x & 63, j = lane & 31, h = lane >> 5;
     const int nwave = blockDim.x >> 6, ntiles = (n_out + 31) / 32;
-    float m1 = -1.f;
-    asm volatile("" : "+v"(m1));                                     // keeps fma(hi, -1, x) a v_fma_mix_f32 (see sdf_mlp_x3.hip)
+    const float m1 = opaque_minus_one();
   // XCD-contiguous schedule (common.h): block b runs on XCD b % 8 and every XCD has its own L2; one contiguous eighth of the row list per XCD
   // (the list is x-major: an eighth = a slab of x-planes) instead of tiles dealt round-robin over the blocks (-20 % on the stride-2 layer of the
   // finest level; the finest same-resolution layer does not move: it is bound by the L1's access rate)
@@ -116,19 +110,7 @@ __global__ __launch_bounds__(LDSW ? 1024 : 256) void k_sparse_conv_x3(const floa
             float4 v0 = make_float4(0.f, 0.f, 0.f, 0.f), v1 = v0;
             if (r >= 0) { v0 = src[4 * u]; v1 = src[4 * u + 1]; }
             const float x[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
-            union { h16x8 v8; h16x2 v2[4]; hh16x2 w2[4]; } bh, bl;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                bh.v2[i] = __builtin_amdgcn_cvt_pkrtz(x[2 * i], x[2 * i + 1]);
-                bl.v2[i] = __builtin_amdgcn_cvt_pkrtz(__builtin_fmaf((float)bh.w2[i][0], m1, x[2 * i]),
-                                                      __builtin_fmaf((float)bh.w2[i][1], m1, x[2 * i + 1]));
-            }
-#pragma unroll
-            for (int nb = 0; nb < NB; ++nb) acc[nb] = MFMA_F16(cur.lo[nb], bh.v8, acc[nb]);
-#pragma unroll
-            for (int nb = 0; nb < NB; ++nb) acc[nb] = MFMA_F16(cur.hi[nb], bl.v8, acc[nb]);
-#pragma unroll
-            for (int nb = 0; nb < NB; ++nb) acc[nb] = MFMA_F16(cur.hi[nb], bh.v8, acc[nb]);
+            mfma_x3<NB>(acc, cur.hi, cur.lo, split8(x, 0, m1));
             if (u + 1 < NU) cur = nxt;
         }
     }
@@ -175,8 +157,7 @@ __global__ __launch_bounds__(BRICK_THREADS) void k_sparse_conv_brick_32_16(const
             dst[i] = (m < 16) ? src[((k * 2 + (g >> 1)) * 2 + half) * 64 + m + 32 * (g & 1)] : make_float4(0.f, 0.f, 0.f, 0.f);
         }
     }
-    float m1 = -1.f;
-    asm volatile("" : "+v"(m1));
+    const float m1 = opaque_minus_one();
     const int lane = threadIdx.x & 63, n16 = lane & 15, g = lane >> 4, wave = threadIdx.x >> 6;
     const int nbx = (lin.nx + BRX - 1) / BRX, nby = (lin.ny + BRY - 1) / BRY, nbz = (lin.nz + BRZ - 1) / BRZ;
     const int nbricks = nbx * nby * nbz;
@@ -218,13 +199,10 @@ __global__ __launch_bounds__(BRICK_THREADS) void k_sparse_conv_brick_32_16(const
             const int it = threadIdx.x + i * BRICK_THREADS;
             if (it >= HALO * 4) break;
             const int site = it >> 2, c8 = it & 3;
-            union { h16x8 v8; h16x2 v2[4]; hh16x2 w2[4]; float4 f4; } bh, bl;
+            union { h16x2 v2[4]; float4 f4; } bh, bl;
             const float xv[8] = {va[i].x, va[i].y, va[i].z, va[i].w, vb[i].x, vb[i].y, vb[i].z, vb[i].w};
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                bh.v2[j] = __builtin_amdgcn_cvt_pkrtz(xv[2 * j], xv[2 * j + 1]);
-                bl.v2[j] = __builtin_amdgcn_cvt_pkrtz(__builtin_fmaf((float)bh.w2[j][0], m1, xv[2 * j]), __builtin_fmaf((float)bh.w2[j][1], m1, xv[2 * j + 1]));
-            }
+            for (int j = 0; j < 4; ++j) split_pair(xv[2 * j], xv[2 * j + 1], m1, bh.v2[j], bl.v2[j]);
             float4* d = reinterpret_cast<float4*>(hl + site * SITE_F);
             d[c8] = bh.f4;
             d[4 + c8] = bl.f4;
