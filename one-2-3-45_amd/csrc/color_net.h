@@ -68,6 +68,8 @@ struct ColorMArgs {
                               //   bit 2  k_color_pts evaluates EVERY view (no skipping of views that see none of a tile's points): +13 % (the round-2 kernel)
                               //   bit 3  k_color_pts: block-interleaved tile schedule instead of one contiguous eighth of the list per XCD -- with view
                               //          skipping a tile's cost depends on where its rays look: -1 % at 8 views, -20 % at 32 views
+                              //   bit 4  k_color_pts evaluates zero-weight pooling views (no skipping, in pass A, of a view that every point of the tile
+                              //          sees with pooling weight 0; bit 2 turns this skipping off as well)
 };
 
 inline int color_sched_mode() { return knobs().color_sched; }
@@ -143,29 +145,6 @@ __device__ __forceinline__ void cx_run(f32x16 (&acc)[NB], const float4* A /* seg
         }
 #pragma unroll
         for (int nb = 0; nb < NB; ++nb) acc[nb] = MFMA_F16(alo[nb], sp.hi, acc[nb]);
-#pragma unroll
-        for (int nb = 0; nb < NB; ++nb) acc[nb] = MFMA_F16(ahi[nb], sp.lo, acc[nb]);
-#pragma unroll
-        for (int nb = 0; nb < NB; ++nb) acc[nb] = MFMA_F16(ahi[nb], sp.hi, acc[nb]);
-        __builtin_amdgcn_sched_barrier(0);
-    }
-}
-// the same with the accumulators STARTING from `init` (the first matrix instruction of every block reads it as its C operand and writes `acc`: no
-// register copies of a value that must stay live, e.g. the view-independent rows shared by all views of a point)
-template <int NB, int N>
-__device__ __forceinline__ void cx_run_from(f32x16 (&acc)[NB], const f32x16 (&init)[NB], const float4* A, const float (&b)[N], float m1) {
-    constexpr int NS = (N + 7) / 8;
-#pragma unroll
-    for (int s = 0; s < NS; ++s) {
-        const Split8 sp = split8(b, 8 * s, m1);
-        h16x8 ahi[NB], alo[NB];
-#pragma unroll
-        for (int nb = 0; nb < NB; ++nb) {
-            ahi[nb] = __builtin_bit_cast(h16x8, A[((nb * NS + s) * 2 + 0) * 64]);
-            alo[nb] = __builtin_bit_cast(h16x8, A[((nb * NS + s) * 2 + 1) * 64]);
-        }
-#pragma unroll
-        for (int nb = 0; nb < NB; ++nb) acc[nb] = MFMA_F16(alo[nb], sp.hi, s == 0 ? init[nb] : acc[nb]);
 #pragma unroll
         for (int nb = 0; nb < NB; ++nb) acc[nb] = MFMA_F16(ahi[nb], sp.lo, acc[nb]);
 #pragma unroll

@@ -17,7 +17,7 @@
 //   pass B   per view: gather + ray_dir_fc again (recomputed: 59 floats x V per point do not fit anywhere), base_fc, vis_fc,
 //            vis_fc2, rgb_fc exactly as in color_mfma.hip, and an online softmax over the views (running max / sum / rgb).
 // View-uniform data (projection rows, camera centres) is read through scalar loads.  V is a run-time loop bound: no power-of-two
-// padding of the view count, any V >= 1.  LDS holds the operand blobs only (<= 100 KB).
+// padding of the view count, any V >= 1.  LDS holds the operand blobs (without A_S) and one slot of shared rows per wave (<= 148 KB).
 #include "color_net.h"
 
 namespace o2345 {
@@ -83,30 +83,108 @@ __device__ __forceinline__ void direction_layer2(const float* lds, int tail, int
         for (int r = 0; r < 16; r += 2) { const f32x2 e2 = celu2(acc2[b][r], acc2[b][r + 1]); rf[16 * b + r] += e2[0]; rf[16 * b + r + 1] += e2[1]; }
 }
 
-// 512-thread workgroups (2 waves per SIMD, <= 256 VGPRs: no spills; measured 45.2 ms vs 46.0 ms with 768 threads / 168 VGPRs / 140 B of spills)
-constexpr int CP_THREADS = 512;
+// The view-independent rows of base_fc.0 (A_S, 36 KB in either form, read once per tile) come straight from the blob in global memory, where they stay
+// L2-resident: not staging them leaves the LDS room for the per-wave slots of their result (below).  They are read through a buffer descriptor: the k-step
+// offsets go to the scalar offset operand (64-bit per-load addresses cost 72 VGPRs, hoisted out of the tile loop).  The next k-step's operands are
+// requested before this step's matrix work (an L2 hit takes about as long as one step's matrix instructions).  Same operations in the same order as
+// cx_run / cm_run.
+constexpr int CP_AS_BYTES = 2 * 9 * 512 * 4;                              // == 2 * 72 * 64 * 4 (fp32 form)
+template <int NB, int N>
+__device__ __forceinline__ void cx_run_global(f32x16 (&acc)[NB], __amdgpu_buffer_rsrc_t rs, int lane, const float (&b)[N], float m1) {
+    constexpr int NS = (N + 7) / 8;
+    auto fetch = [&](int nb, int s, int k) { return __builtin_bit_cast(h16x8, __builtin_amdgcn_raw_buffer_load_b128(rs, lane * 16, ((nb * NS + s) * 2 + k) * 1024, 0)); };
+    h16x8 cur[NB][2], nxt[NB][2];
+#pragma unroll
+    for (int nb = 0; nb < NB; ++nb) { cur[nb][0] = fetch(nb, 0, 0); cur[nb][1] = fetch(nb, 0, 1); }
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+        if (s + 1 < NS) {
+#pragma unroll
+            for (int nb = 0; nb < NB; ++nb) { nxt[nb][0] = fetch(nb, s + 1, 0); nxt[nb][1] = fetch(nb, s + 1, 1); }
+        }
+        const Split8 sp = split8(b, 8 * s, m1);
+#pragma unroll
+        for (int nb = 0; nb < NB; ++nb) acc[nb] = MFMA_F16(cur[nb][1], sp.hi, acc[nb]);
+#pragma unroll
+        for (int nb = 0; nb < NB; ++nb) acc[nb] = MFMA_F16(cur[nb][0], sp.lo, acc[nb]);
+#pragma unroll
+        for (int nb = 0; nb < NB; ++nb) acc[nb] = MFMA_F16(cur[nb][0], sp.hi, acc[nb]);
+#pragma unroll
+        for (int nb = 0; nb < NB; ++nb) { cur[nb][0] = nxt[nb][0]; cur[nb][1] = nxt[nb][1]; }
+        __builtin_amdgcn_sched_barrier(0);
+    }
+}
+template <int NB, int N>
+__device__ __forceinline__ void cm_run_global(f32x16 (&acc)[NB], __amdgpu_buffer_rsrc_t rs, int lane, const float (&b)[N]) {
+    auto fetch = [&](int nb, int r) { return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, lane * 4, (nb * N + r) * 256, 0)); };
+    float cur[NB], nxt[NB];
+#pragma unroll
+    for (int nb = 0; nb < NB; ++nb) cur[nb] = fetch(nb, 0);
+#pragma unroll
+    for (int r = 0; r < N; ++r) {
+        if (r + 1 < N) {
+#pragma unroll
+            for (int nb = 0; nb < NB; ++nb) nxt[nb] = fetch(nb, r + 1);
+        }
+#pragma unroll
+        for (int nb = 0; nb < NB; ++nb) acc[nb] = MFMA32(cur[nb], b[r], acc[nb]);
+#pragma unroll
+        for (int nb = 0; nb < NB; ++nb) cur[nb] = nxt[nb];
+        __builtin_amdgcn_sched_barrier(0);
+    }
+}
+
+// Those rows' result (incl. bias: 2 accumulator blocks = 32 floats per lane) is the starting accumulator of every view's base_fc.0 in pass B.  It waits in
+// an 8 KB LDS slot per wave, [block][quarter][64 lanes][4 floats] (conflict-free 16-byte accesses), instead of 32 registers live through pass B: that is
+// what brings the kernel under 168 VGPRs, i.e. 3 waves per SIMD.  Each lane reads back only what it wrote: no barrier.
+__device__ __forceinline__ void sh_store(float4* slot, const f32x16 (&sh)[2]) {
+#pragma unroll
+    for (int nb = 0; nb < 2; ++nb)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) slot[(nb * 4 + q) * 64] = make_float4(sh[nb][4 * q], sh[nb][4 * q + 1], sh[nb][4 * q + 2], sh[nb][4 * q + 3]);
+}
+__device__ __forceinline__ void sh_load(f32x16 (&acc)[2], const float4* slot) {
+#pragma unroll
+    for (int nb = 0; nb < 2; ++nb)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const float4 t = slot[(nb * 4 + q) * 64];
+            acc[nb][4 * q] = t.x; acc[nb][4 * q + 1] = t.y; acc[nb][4 * q + 2] = t.z; acc[nb][4 * q + 3] = t.w;
+        }
+}
+
+// 768-thread workgroups: 3 waves per SIMD, <= 168 VGPRs.  Nothing spills inside a view loop; the f16x3 forms keep a few tile-level values (indices,
+// addresses) in scratch.  (Earlier forms: 512 threads at 199 VGPRs; a 768-thread build that kept the shared rows in registers spilled 140 B and lost,
+// 46.0 vs 45.2 ms.)
+constexpr int CP_THREADS = 768;
+constexpr int CP_SH_FLOATS = 2 * 16 * 64;                                  // one wave's slot of shared rows
+// dynamic LDS: [A segments | biases and per-lane vectors] [scalars (4)] [one shared-row slot per wave]
+constexpr size_t color_pts_lds_bytes(int x3) {
+    return (size_t)((x3 ? CX_A_END + CM_W_S - CM_BIAS0 : CM_W_S) + 4 + (CP_THREADS / 64) * CP_SH_FLOATS) * sizeof(float);
+}
+static_assert(color_pts_lds_bytes(1) <= 160 * 1024 && color_pts_lds_bytes(0) <= 160 * 1024, "k_color_pts: LDS of a CU exceeded");
 template <bool X3, bool FEATS>
 __global__ __launch_bounds__(CP_THREADS) void k_color_pts(ColorMArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    // staged: [A segments | biases and per-lane vectors] [scalars (4)] [A_S]  -- the VALU weight rows W_S of color_mfma.hip are skipped
+    // staged: [A segments | biases and per-lane vectors] [scalars (4)]  -- the VALU weight rows W_S of color_mfma.hip are skipped, A_S is read from global memory
     constexpr int HEAD = X3 ? (CX_A_END + CM_W_S - CM_BIAS0) : CM_W_S;       // floats before W_S in the blob
     constexpr int SRC_S = X3 ? (CX_TOTAL - 4) : CM_S;                       // scalars in the blob
-    constexpr int NAS = X3 ? 2 * 9 * 512 : 2 * 72 * 64;
     constexpr int TAIL = X3 ? CX_A_END - CM_BIAS0 : 0;                      // shift of the bias block, as in color_mfma.hip
-    constexpr int L_S = HEAD, L_AS = HEAD + 4;                              // LDS offsets of the scalars and of A_S
+    constexpr int L_S = HEAD, L_SH = HEAD + 4;                              // LDS offsets of the scalars and of the shared-row slots
     for (int i = threadIdx.x * 4; i < HEAD; i += blockDim.x * 4)
         *reinterpret_cast<float4*>(lds + i) = *reinterpret_cast<const float4*>(a.blob + i);
-    for (int i = threadIdx.x * 4; i < 4 + NAS; i += blockDim.x * 4)
-        *reinterpret_cast<float4*>(lds + L_S + i) = *reinterpret_cast<const float4*>(a.blob + SRC_S + i);
+    if (threadIdx.x == 0) *reinterpret_cast<float4*>(lds + L_S) = *reinterpret_cast<const float4*>(a.blob + SRC_S);
     __syncthreads();
     const int lane = threadIdx.x & 63, j = lane & 31, h = lane >> 5;
     const int wave = threadIdx.x >> 6, nwave = blockDim.x >> 6;
+    float4* const sh_slot = reinterpret_cast<float4*>(lds + L_SH + wave * CP_SH_FLOATS) + lane;
     const long long n = a.n_dev ? (long long)*a.n_dev : a.n;
     const float m1 = X3 ? opaque_minus_one() : -1.f;
     const float s_abs = fabsf(lds[L_S]) * LOG2E;
     const int V = a.V;
     const bool skip_views = V <= 64 && !(a.sched & 4);              // bit 2 of O2345_COLOR_SCHED: evaluate every view (A/B runs)
-    const int base_prio = (a.sched & 1) ? (wave >> 2) : 0;          // waves w and w + 4 share a SIMD (cyclic SIMD assignment)
+    const bool skip_zero = skip_views && !(a.sched & 16);           // bit 4: evaluate zero-weight pooling views in pass A
+    const int base_prio = (a.sched & 1) ? (wave >> 2) : 0;          // waves w, w + 4 and w + 8 share a SIMD (cyclic SIMD assignment over 4 SIMDs)
     if (a.sched & 1) set_wave_prio(base_prio);
     // bit 3 of O2345_COLOR_SCHED: block-interleaved tiles instead of one contiguous eighth of the list per XCD (A/B: with view skipping the
     // cost of a tile depends on where its rays look, and a contiguous eighth of the image is not an eighth of the work)
@@ -178,17 +256,27 @@ __global__ __launch_bounds__(CP_THREADS) void k_color_pts(ColorMArgs a) {
         float wsum = 0.f, nvis = 0.f;
         unsigned long long active = 0ull;            // wave-uniform: views that see at least one point of the tile
         {
-            float mean[32], m2[32];
+            // M2 waits in this wave's shared-row slot (free until the shared rows), read and written back once per evaluated view: 32 registers
+            // fewer in pass A.  `fresh` (wave-uniform): no view evaluated yet, M2 = 0.
+            float mean[32];
 #pragma unroll
-            for (int c = 0; c < 32; ++c) { mean[c] = 0.f; m2[c] = 0.f; }
+            for (int c = 0; c < 32; ++c) mean[c] = 0.f;
+            bool fresh = true;
 #pragma unroll 1
             for (int v = 0; v < V; ++v) {
+                asm volatile("" ::: "memory");              // keeps M2 in the LDS (no promotion of the slot to registers across the view loop)
                 const ViewGeom g = FEATS ? feat_geom(a, v, slot, s_abs) : view_geom(a, v, px, py, pz, qx, qy, qz, gvalid, s_abs);
                 // A view that sees NONE of the tile's 32 points (wave-uniform test) contributes exactly nothing to this pass: raw = 0 leaves wsum,
                 // nvis, mean and M2 bit-unchanged.  Points of a tile are neighbours (32 adjacent rays at one sample index), so visibility is
                 // coherent: at BASELINE config 2 a point is seen by 4.8 of the 8 views on average and 37 % of the (tile, view) pairs are skipped.
                 if (skip_views && __builtin_amdgcn_ballot_w64(g.m != 0.f) == 0ull) continue;
-                active |= 1ull << (v & 63);
+                active |= 1ull << (v & 63);                  // pass B evaluates the view
+                const float raw = (g.e - emin) * g.m;
+                nvis += g.m;
+                // The same holds for a view that the tile's points see, but all with pooling weight raw = 0: emin comes from exactly the operations
+                // that give g.e (same dot product, same exp2, no contraction), so for every point its view of smallest e has raw = 0 exactly, and
+                // neighbouring points share that view.  Such a view leaves wsum, mean and M2 bit-unchanged; it still counts in nvis and in pass B.
+                if (skip_zero && __builtin_amdgcn_ballot_w64(live && raw != 0.f) == 0ull) continue;
                 ++st_a;
                 float rf[32];
                 if constexpr (FEATS) load_feats(a, h, v, slot, rf);
@@ -202,35 +290,52 @@ __global__ __launch_bounds__(CP_THREADS) void k_color_pts(ColorMArgs a) {
                     direction_layer1<X3>(lds, TAIL, lane, h, g, m1, d16);
                     direction_layer2<X3>(lds, TAIL, lane, h, d16, m1, rf);
                 }
-                const float raw = (g.e - emin) * g.m;
-                nvis += g.m;
                 wsum += raw;
                 const float r0 = raw > 0.f ? raw * crcp(wsum) : 0.f;
                 // one Newton step on the quotient: raw / wsum to <= 1 ulp
                 const float rq = raw > 0.f ? fmaf(fmaf(-wsum, r0, raw), crcp(wsum), r0) : 0.f;
 #pragma unroll
-                for (int c = 0; c < 32; ++c) {
-                    const float d = rf[c] - mean[c];
-                    mean[c] = fmaf(rq, d, mean[c]);
-                    m2[c] = fmaf(raw * d, rf[c] - mean[c], m2[c]);
+                for (int q = 0; q < 8; ++q) {
+                    float4 t = fresh ? make_float4(0.f, 0.f, 0.f, 0.f) : sh_slot[q * 64];
+                    float* m2 = reinterpret_cast<float*>(&t);
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        const int c = 4 * q + k;
+                        const float d = rf[c] - mean[c];
+                        mean[c] = fmaf(rq, d, mean[c]);
+                        m2[k] = fmaf(raw * d, rf[c] - mean[c], m2[k]);
+                    }
+                    sh_slot[q * 64] = t;
                 }
+                fresh = false;
             }
             // the reference normalises the weights by (sum + 1e-8): w_v = raw_v / (wsum + 1e-8), S = sum w_v <= 1
             //   mean_ref = sum w x = S mean_w,   var_ref = sum w (x - mean_ref)^2 = M2 / (wsum + 1e-8) + S (1 - S)^2 mean_w^2
             const float rden = crcp(wsum + 1e-8f);
             const float S = wsum * rden, k2 = S * (1.f - S) * (1.f - S);
+            asm volatile("" ::: "memory");
 #pragma unroll
-            for (int c = 0; c < 32; ++c) {
-                bs[8 + c] = S * mean[c];
-                bs[40 + c] = fmaf(k2 * mean[c], mean[c], m2[c] * rden);
+            for (int q = 0; q < 8; ++q) {
+                const float4 t = fresh ? make_float4(0.f, 0.f, 0.f, 0.f) : sh_slot[q * 64];
+                const float m2[4] = {t.x, t.y, t.z, t.w};
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const int c = 4 * q + k;
+                    bs[8 + c] = S * mean[c];
+                    bs[40 + c] = fmaf(k2 * mean[c], mean[c], m2[k] * rden);
+                }
             }
         }
         const float rden = crcp(wsum + 1e-8f);
         // ---- view-independent rows of base_fc.0, once per point: sh = bias + W_shared [geo | mean | var] -------------------------
-        f32x16 sh[2];
-        cm_bias<2>(sh, lds + TAIL + CM_B_B0, h);
-        if constexpr (X3) cx_run<2, 72>(sh, reinterpret_cast<const float4*>(lds + L_AS) + lane, bs, m1);
-        else cm_run<2, 72, 72>(sh, lds + L_AS + lane, 0, bs);
+        {
+            f32x16 sh[2];
+            cm_bias<2>(sh, lds + TAIL + CM_B_B0, h);
+            const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)(a.blob + (X3 ? CX_A_S : CM_A_S)), 0, CP_AS_BYTES, 0x00020000);
+            if constexpr (X3) cx_run_global<2, 72>(sh, rs, lane, bs, m1);
+            else cm_run_global<2, 72>(sh, rs, lane, bs);
+            sh_store(sh_slot, sh);
+        }
         // ---- pass B: per view network, online softmax over the views ------------------------------------------------------------------
         float smax = -INFINITY, ssum = 0.f, o0 = 0.f, o1 = 0.f, o2 = 0.f;
         // A masked view enters the softmax with score -1e9: its blending weight is exp2(-1e9 - max) = 0 EXACTLY as soon as the point has one
@@ -263,8 +368,8 @@ __global__ __launch_bounds__(CP_THREADS) void k_color_pts(ColorMArgs a) {
             f32x16 x32[1];
             {
                 f32x16 acc[2];
-                if constexpr (X3) cx_run_from<2, 32>(acc, sh, reinterpret_cast<const float4*>(lds + CX_A_B0) + lane, rf, m1);
-                else { acc[0] = sh[0]; acc[1] = sh[1]; cm_layer<X3, 2, 32>(acc, lds, lane, CM_A_B0, CX_A_B0, rf, m1); }
+                sh_load(acc, sh_slot);
+                cm_layer<X3, 2, 32>(acc, lds, lane, CM_A_B0, CX_A_B0, rf, m1);
                 float hb[32];
 #pragma unroll
                 for (int b = 0; b < 2; ++b)
@@ -374,7 +479,7 @@ int color_pts_launch(int x3, const float* blob, const float* vol_cl, const float
     const long long per_block = (long long)(threads / 64) * 32;
     long long want = n_dev ? n_cu : (n + per_block - 1) / per_block;
     const unsigned grid = persistent_grid(want, n_cu);
-    const size_t lds = (size_t)(x3 ? (CX_A_END + CM_W_S - CM_BIAS0) + 4 + 2 * 9 * 512 : CM_W_S + 4 + 2 * 72 * 64) * sizeof(float);
+    const size_t lds = color_pts_lds_bytes(x3);
     hipStream_t s = (hipStream_t)stream;
     if (x3) {
         O2345_ENSURE_LDS((k_color_pts<true, false>), lds);
@@ -454,7 +559,7 @@ int color_feats_launch(int x3, const float* blob, const float* geo, const float*
     const int n_cu = cu_count();
     const long long per_block = (long long)(CP_THREADS / 64) * 32;
     const unsigned grid = persistent_grid((n + per_block - 1) / per_block, n_cu);
-    const size_t lds = (size_t)(x3 ? (CX_A_END + CM_W_S - CM_BIAS0) + 4 + 2 * 9 * 512 : CM_W_S + 4 + 2 * 72 * 64) * sizeof(float);
+    const size_t lds = color_pts_lds_bytes(x3);
     hipStream_t s = (hipStream_t)stream;
     if (x3) {
         O2345_ENSURE_LDS((k_color_pts<true, true>), lds);

@@ -90,7 +90,7 @@ __device__ __forceinline__ int block_prefix(bool pred, int* lds_wave_tot /*[NWAV
 // Debug / A-B knobs of the library, read from the environment ONCE (first use; function-local static: thread-safe, and no getenv on a launch path --
 // getenv is not safe against a concurrent setenv, and the library is used from one host thread per stream / device):
 //   O2345_LIST_SORT=0     render call: keep the occupied-point list in emission order (no grouping by view-visibility signature)
-//   O2345_COLOR_SCHED=n   scheduling bits of the colour kernel (color_net.h), default 10
+//   O2345_COLOR_SCHED=n   scheduling and skipping bits of the colour kernel (color_net.h), default 10
 //   O2345_SPARSE_BRICK=0  finest sparse convolution in the gather form instead of the LDS-tiled brick form
 //   O2345_FLAT_SCHED=1    persistent network kernels: flat block-interleaved tile schedule (odd grid) instead of one eighth of the list per XCD
 //   O2345_COLOR_KERNEL=tiles  (only in a -DO2345_TILES_KERNEL test build) the (point, view)-column colour kernel instead of k_color_pts
