@@ -44,7 +44,9 @@ const char* o2345_last_error(void);
  * per-ray near / far; caller-owned colour work counters; per-call scalars) and layout-checked (o2345_render_io_*), o2345_camera_terms,
  * `identity_rows` on o2345_sparse_conv3d_x3, no process-global state left in the library (the colour work counters are a caller-owned buffer). */
 /* 210 = ABI 2.1 (round 5): O2345RenderIO gains `segment_rays` (the reference's two per-CALL rules applied per segment of a fused call: a whole image
- * behind the trainer's unchanged 512-ray chunk loop) and `weight_cull` (tolerance-bounded colour work removal); o2345_ray_composite is unchanged. */
+ * behind the trainer's unchanged 512-ray chunk loop) and `weight_cull` (tolerance-bounded colour work removal); o2345_ray_composite is unchanged.
+ * Additive since 2.1 (no existing entry changed, the version stays 210): the asset export entries o2345_mesh_bounds_workspace_bytes,
+ * o2345_mesh_asset_vertices, o2345_mesh_asset_indices, o2345_obj_text_bytes, o2345_obj_text, o2345_obj_text_host. */
 int o2345_version(void);
 /* Layout self-description of O2345RenderIO as THIS library was compiled (sizeof, and offsetof of every field in declaration order): a binding
  * asserts its own struct against it at load time (one-2-3-45_amd/_lib.py does) -- a field added on one side only cannot corrupt calls silently.
@@ -354,8 +356,42 @@ int o2345_mc_verts_to_world(double* verts, long long n, int grid_R, const double
  * face_records m x 13 bytes.  Plain host code (up to four threads), no device work, no stream. */
 int o2345_ply_records_host(const double* vertices, long long n, const uint8_t* colors, int color_channels, const long long* faces, long long m,
                            uint8_t* vertex_records, uint8_t* face_records);
+
+/* ---- asset export (additive since 2.1; replaces utils/utils.py:31-47, convert_mesh_format: mesh.ply -> trimesh -> re-oriented mesh.glb / mesh.obj) -----
+ * Output frame: the reference's two rotations and x flip compose to the exact swap (x, y, z) -> (x, z, y) (z-up -> glTF's y-up), and every face is
+ * reversed (a, b, c) -> (c, b, a).  Positions are the float32 positions of o2345_mesh_pack_vertices with columns 1 and 2 exchanged, bit for bit.
+ *
+ * mesh_asset_vertices (replaces utils/utils.py:34-40): verts_idx, bounds and matrices as for o2345_mesh_pack_vertices; rgb device fp32 [n,3] or NULL;
+ * grad device fp32 [n,3] (SDF gradient in the reconstruction frame) or NULL.  Outputs, all device: positions float32 [n,3]; rgba uint8 [n,4] (written
+ * iff rgb; truncating quantisation, alpha 255; 4-byte aligned); normals float32 [n,3] (written iff grad): normalize(grad) through the 3x3 of trans_mat
+ * when given, renormalised, swapped -- towards increasing SDF; (0, 1, 0) for a zero or non-finite gradient; bounds float32 [6] = per-axis min then max of
+ * positions (glTF's POSITION accessor needs them), from a two-stage reduction through `workspace` (o2345_mesh_bounds_workspace_bytes(n) bytes, 4-byte
+ * aligned): deterministic, no floating-point atomics.  n = 0 writes nothing. */
+size_t o2345_mesh_bounds_workspace_bytes(long long n);
+int o2345_mesh_asset_vertices(const double* verts_idx, long long n, int grid_R, const float* bound_min, const float* bound_max, const float* scale_mat,
+                              const float* trans_mat, const float* rgb, const float* grad, float* positions, uint8_t* rgba, float* normals,
+                              float* bounds, void* workspace, size_t workspace_bytes, void* stream);
+/* replaces utils/utils.py:41 (np.fliplr(mesh.faces)): tris device int32 / int64 [m,3] (index_bytes 4 / 8) -> indices uint32 [m,3], winding reversed. */
+int o2345_mesh_asset_indices(const void* tris, int index_bytes, long long m, uint32_t* indices, void* stream);
+/* OBJ text (replaces utils/utils.py:42-44, mesh.export(file_type='obj', include_color=True)): fixed-width ASCII records, n vertex records, then n
+ * normal records when normals are given, then m face records; record i of a kind starts at i * its length.
+ *   coordinate field " %*.8f", 1 + (1 + K + 1 + 8) bytes, K = integer digits of the largest |coordinate| after rounding to 8 decimals (1 .. 9; the caller
+ *   takes it from `bounds`); colour field " %.8f" of c / 255, 11 bytes;
+ *   "v" + 3 coordinate fields [+ 3 colour fields] + "\n";  "vn" + 3 x " %11.8f" + "\n";
+ *   "f" + 3 x " %*d" + "\n" (1-based, width = decimal digits of n), or with normals 3 x " a//a", each token right-aligned in 2 * digits(n) + 2 bytes.
+ * Digits are printf's: correctly rounded, ties to even, "-0.00000000" for a negative value that rounds to zero.
+ * obj_text_bytes: the byte count (HOST function; 0 for K outside 1 .. 9).  obj_text: positions / rgba (or NULL) / normals (or NULL) / indices as written by
+ * the two entries above, all device; color_table device uint8 [256,11], entry c = " %.8f" % (c / 255.0) (needed iff rgba); text device uint8
+ * [obj_text_bytes], any alignment.  Indices must be < n. */
+size_t o2345_obj_text_bytes(long long n, long long m, int K, int colors, int normals);
+int o2345_obj_text(const float* positions, const uint8_t* rgba, const float* normals, long long n, const uint32_t* indices, long long m, int K,
+                   const uint8_t* color_table, uint8_t* text, void* stream);
+/* The same text for a mesh that is already on the HOST (what convert_mesh_format does after trimesh.load_mesh, utils/utils.py:31-47): host pointers in the
+ * layouts above, text host uint8 [obj_text_bytes].  Plain host code (up to four threads), no device work, no stream. */
+int o2345_obj_text_host(const float* positions, const uint8_t* rgba, const float* normals, long long n, const uint32_t* indices, long long m, int K,
+                        uint8_t* text);
 /* Load every code object of the library on the current device now (the HIP runtime loads a translation unit's kernels at its first launch: 5 - 60 ms
- * each for the 15 units of this library, which otherwise land inside the first calls of a fresh process).  Launches nothing that touches user memory. */
+ * each for the 16 units of this library, which otherwise land inside the first calls of a fresh process).  Launches nothing that touches user memory. */
 int o2345_preload(void);
 
 #ifdef __cplusplus

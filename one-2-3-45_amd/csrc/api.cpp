@@ -27,6 +27,7 @@ int preload_color_maps();
 int preload_color_pts();
 int preload_mcubes();
 int preload_mesh_pack();
+int preload_mesh_export();
 int preload_featmaps();
 int preload_convnet();
 }
@@ -48,6 +49,7 @@ int o2345_preload(void) {
     if ((e = o2345::preload_color_pts())) bad = e;
     if ((e = o2345::preload_mcubes())) bad = e;
     if ((e = o2345::preload_mesh_pack())) bad = e;
+    if ((e = o2345::preload_mesh_export())) bad = e;
     if ((e = o2345::preload_featmaps())) bad = e;
     if ((e = o2345::preload_convnet())) bad = e;
     O2345_REQUIRE(bad == 0, "preload: hipFuncGetAttributes failed (%s)", hipGetErrorString((hipError_t)bad));

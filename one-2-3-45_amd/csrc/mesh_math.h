@@ -1,0 +1,143 @@
+// Per-element mesh arithmetic shared by the serialisation kernels (mesh_pack.hip: PLY records; mesh_export.hip: GLB buffers and OBJ text) and by
+// their host-side packers: the marching-cubes index -> output frame transform, the colour quantisation, and the fixed-width decimal fields of the
+// OBJ records.  One definition each, so that a PLY, a GLB and an OBJ of one mesh carry the same float32 positions and the same uint8 colours.
+#pragma once
+#include "common.h"
+#include <math.h>
+
+namespace o2345 {
+
+struct MeshXform {
+    double inv_rm1;            // 1 / (R - 1)   (the reference divides; kept as a division below)
+    int R;
+    double bmin[3], bext[3];   // bound_min, bound_max - bound_min
+    int has_scale; double s, t[3];          // scale_mat[0,0], scale_mat[:3,3]
+    int has_trans; double T[12];            // rows 0..2 of trans_mat (4x4, row-major)
+};
+
+// host: the kernel argument from the C ABI's host arrays (bound_min[3], bound_max[3], scale_mat / trans_mat 4x4 row-major fp32 or NULL)
+inline MeshXform mesh_xform(int grid_R, const float* bound_min, const float* bound_max, const float* scale_mat, const float* trans_mat) {
+    MeshXform x{};
+    x.R = grid_R;
+    for (int d = 0; d < 3; ++d) { x.bmin[d] = (double)bound_min[d]; x.bext[d] = (double)(bound_max[d] - bound_min[d]); }   // fp32 subtraction, as torch does
+    x.has_scale = scale_mat != nullptr;
+    if (scale_mat) { x.s = (double)scale_mat[0]; x.t[0] = (double)scale_mat[3]; x.t[1] = (double)scale_mat[7]; x.t[2] = (double)scale_mat[11]; }
+    x.has_trans = trans_mat != nullptr;
+    if (trans_mat) for (int k = 0; k < 12; ++k) x.T[k] = (double)trans_mat[k];
+    return x;
+}
+
+// Index coordinates of vertex i -> the reference's export frame in fp64 (sparse_neus_renderer.py:936: v / (R - 1) * (bmax - bmin) + bmin;
+// trainer_generic.py:1365-1372: * s + t, then trans @ [v, 1]), rounded to float32 once, at the end -- what trimesh's PLY exporter stores.
+O2345_HD void mesh_vertex_f32(const double* __restrict__ vidx, long long i, const MeshXform& x, float f[3]) {
+    double v[3];
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+        v[d] = vidx[3 * i + d] / (double)(x.R - 1) * x.bext[d] + x.bmin[d];        // sparse_neus_renderer.py:936
+        if (x.has_scale) v[d] = v[d] * x.s + x.t[d];
+    }
+    if (x.has_trans) {
+        double w[3];
+#pragma unroll
+        for (int r = 0; r < 3; ++r) w[r] = ((x.T[4 * r] * v[0] + x.T[4 * r + 1] * v[1]) + x.T[4 * r + 2] * v[2]) + x.T[4 * r + 3];
+        v[0] = w[0]; v[1] = w[1]; v[2] = w[2];
+    }
+    f[0] = (float)v[0]; f[1] = (float)v[1]; f[2] = (float)v[2];
+}
+
+// np.array(color * 255, dtype=uint8) (trainer_generic.py:1377): truncation
+O2345_HD uint8_t mesh_colour_u8(float c) { return (uint8_t)(int)(c * 255.f); }
+
+// ---- OBJ text fields ------------------------------------------------------------------------------------------------------------------------
+// Every field is written right to left into exactly `width` bytes, whatever the value: a value that needs more room than the host planned for
+// loses its leading characters, it never moves a neighbour.
+
+// " %*.8f" of a float32 in `width` = 1 (space) + 1 (sign) + K + 1 + 8 bytes.  (double)|v| * 1e8 is exact (24-bit significand x 5^8 < 2^53), so rint
+// (to nearest, ties to even) and integer digit extraction give printf's correctly rounded digits; the sign comes from the sign bit ("-0.00000000").
+O2345_HD void obj_fixed8(uint8_t* dst, int width, float v) {
+    int p = width - 1;
+    if (!(fabsf(v) <= 3.4028234e38f)) {                  // printf's "nan" / "inf" / "-inf"
+        const bool nan = v != v;
+        dst[p--] = nan ? 'n' : 'f'; if (p >= 0) dst[p--] = nan ? 'a' : 'n'; if (p >= 0) dst[p--] = nan ? 'n' : 'i';
+        if (!nan && v < 0.f && p >= 0) dst[p--] = '-';
+        while (p >= 0) dst[p--] = ' ';
+        return;
+    }
+    const double a = rint((double)fabsf(v) * 1e8);
+    const unsigned long long q = a < 1.8e19 ? (unsigned long long)a : 0ull;
+    unsigned frac = (unsigned)(q % 100000000ull);
+    unsigned long long ip = q / 100000000ull;
+    for (int k = 0; k < 8 && p >= 0; ++k) { dst[p--] = (uint8_t)('0' + frac % 10u); frac /= 10u; }
+    if (p >= 0) dst[p--] = '.';
+    do { if (p >= 0) dst[p--] = (uint8_t)('0' + (unsigned)(ip % 10ull)); ip /= 10ull; } while (ip);
+    if (__builtin_signbit(v) && p >= 0) dst[p--] = '-';
+    while (p >= 0) dst[p--] = ' ';
+}
+
+// "%*u" right-aligned in `width` bytes; returns the position left of the first digit
+O2345_HD int obj_uint(uint8_t* dst, int p, unsigned v) {
+    do { if (p >= 0) dst[p--] = (uint8_t)('0' + v % 10u); v /= 10u; } while (v);
+    return p;
+}
+
+struct ObjLayout {
+    int K;             // integer digits of a coordinate field
+    int dn;            // decimal digits of the vertex count
+    int colours, normals;
+    int v_len, vn_len, f_len;
+};
+
+O2345_HD int obj_digits(unsigned long long v) { int d = 1; while (v >= 10ull) { v /= 10ull; ++d; } return d; }
+
+O2345_HD ObjLayout obj_layout(long long n, int K, int colours, int normals) {
+    ObjLayout L;
+    L.K = K; L.dn = obj_digits((unsigned long long)(n > 0 ? n : 0)); L.colours = colours; L.normals = normals;
+    L.v_len = 1 + 3 * (K + 11) + (colours ? 33 : 0) + 1;
+    L.vn_len = 2 + 3 * 12 + 1;
+    L.f_len = 1 + 3 * (1 + (normals ? 2 * L.dn + 2 : L.dn)) + 1;
+    return L;
+}
+
+// "v" + 3 coordinate fields [+ 3 colour fields from the 256 x 11-byte table " %.8f" % (c / 255)] + "\n"
+O2345_HD void obj_vertex_record(uint8_t* dst, const ObjLayout& L, const float* pos, const uint8_t* rgba, const uint8_t* table) {
+    dst[0] = 'v';
+    const int w = L.K + 11;
+#pragma unroll
+    for (int d = 0; d < 3; ++d) obj_fixed8(dst + 1 + d * w, w, pos[d]);
+    uint8_t* c = dst + 1 + 3 * w;
+    if (L.colours) {
+        for (int d = 0; d < 3; ++d, c += 11) {
+            const uint8_t* t = table + 11 * (int)rgba[d];
+            for (int k = 0; k < 11; ++k) c[k] = t[k];
+        }
+    }
+    c[0] = '\n';
+}
+
+// "vn" + 3 x " %11.8f" + "\n"
+O2345_HD void obj_normal_record(uint8_t* dst, const float* nrm) {
+    dst[0] = 'v'; dst[1] = 'n';
+#pragma unroll
+    for (int d = 0; d < 3; ++d) obj_fixed8(dst + 2 + d * 12, 12, nrm[d]);
+    dst[38] = '\n';
+}
+
+// "f" + 3 x " %*d" (1-based) + "\n", or 3 x " a//a" with each token right-aligned in 2 * dn + 2 bytes
+O2345_HD void obj_face_record(uint8_t* dst, const ObjLayout& L, const uint32_t* idx) {
+    dst[0] = 'f';
+    const int w = 1 + (L.normals ? 2 * L.dn + 2 : L.dn);
+    for (int d = 0; d < 3; ++d) {
+        uint8_t* o = dst + 1 + d * w;
+        const unsigned a = idx[d] + 1u;
+        int p = obj_uint(o, w - 1, a);
+        if (L.normals) {
+            if (p >= 0) o[p--] = '/';
+            if (p >= 0) o[p--] = '/';
+            p = obj_uint(o, p, a);
+        }
+        while (p >= 0) o[p--] = ' ';
+    }
+    dst[1 + 3 * w] = '\n';
+}
+
+}  // namespace o2345

@@ -6,6 +6,7 @@
 // Arithmetic follows the reference's numpy expressions in fp64 (verts / (R-1) * (bmax - bmin) + bmin; * s + t; trans @ [v,1])
 // and rounds to float32 only in the record, as trimesh's PLY exporter does.
 #include "common.h"
+#include "mesh_math.h"
 #include <string.h>
 #include <thread>
 #include <vector>
@@ -23,37 +24,18 @@ __global__ __launch_bounds__(256) void k_verts_to_world(double* __restrict__ v, 
     v[i] = v[i] / div * e + o;
 }
 
-struct MeshXform {
-    double inv_rm1;            // 1 / (R - 1)   (the reference divides; kept as a division below)
-    int R;
-    double bmin[3], bext[3];   // bound_min, bound_max - bound_min
-    int has_scale; double s, t[3];          // scale_mat[0,0], scale_mat[:3,3]
-    int has_trans; double T[12];            // rows 0..2 of trans_mat (4x4, row-major)
-};
-
 __global__ __launch_bounds__(256) void k_pack_vertices(const double* __restrict__ vidx /*[n,3] index coords*/, long long n, MeshXform x,
                                                        const float* __restrict__ rgb /*[n,3] or null*/, uint8_t* __restrict__ rec,
                                                        int stride) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    double v[3];
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-        v[d] = vidx[3 * i + d] / (double)(x.R - 1) * x.bext[d] + x.bmin[d];        // sparse_neus_renderer.py:936
-        if (x.has_scale) v[d] = v[d] * x.s + x.t[d];
-    }
-    if (x.has_trans) {
-        double w[3];
-#pragma unroll
-        for (int r = 0; r < 3; ++r) w[r] = ((x.T[4 * r] * v[0] + x.T[4 * r + 1] * v[1]) + x.T[4 * r + 2] * v[2]) + x.T[4 * r + 3];
-        v[0] = w[0]; v[1] = w[1]; v[2] = w[2];
-    }
     uint8_t* o = rec + i * stride;
-    const float f[3] = {(float)v[0], (float)v[1], (float)v[2]};
+    float f[3];
+    mesh_vertex_f32(vidx, i, x, f);                      // mesh_math.h: shared with the GLB / OBJ vertex kernel (mesh_export.hip)
     __builtin_memcpy(o, f, 12);
     if (rgb) {
 #pragma unroll
-        for (int c = 0; c < 3; ++c) o[12 + c] = (uint8_t)(int)(rgb[3 * i + c] * 255.f);    // np.array(color * 255, dtype=uint8): truncation
+        for (int c = 0; c < 3; ++c) o[12 + c] = mesh_colour_u8(rgb[3 * i + c]);
         o[15] = 255;
     }
 }
@@ -82,13 +64,7 @@ int o2345_mesh_pack_vertices(const double* verts_idx, long long n, int grid_R, c
     O2345_REQUIRE(bound_min && bound_max && grid_R >= 2, "mesh_pack_vertices: bad bounds / resolution");
     if (n <= 0) return 0;
     O2345_REQUIRE(verts_idx && vertex_records, "mesh_pack_vertices: null pointer");
-    MeshXform x{};
-    x.R = grid_R;
-    for (int d = 0; d < 3; ++d) { x.bmin[d] = (double)bound_min[d]; x.bext[d] = (double)(bound_max[d] - bound_min[d]); }   // fp32 subtraction, as torch does
-    x.has_scale = scale_mat != nullptr;
-    if (scale_mat) { x.s = (double)scale_mat[0]; x.t[0] = (double)scale_mat[3]; x.t[1] = (double)scale_mat[7]; x.t[2] = (double)scale_mat[11]; }
-    x.has_trans = trans_mat != nullptr;
-    if (trans_mat) for (int k = 0; k < 12; ++k) x.T[k] = (double)trans_mat[k];
+    const MeshXform x = mesh_xform(grid_R, bound_min, bound_max, scale_mat, trans_mat);
     hipLaunchKernelGGL(k_pack_vertices, dim3(cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, verts_idx, n, x, rgb, vertex_records, rgb ? 16 : 12);
     return check_launch("mesh_pack_vertices");
 }

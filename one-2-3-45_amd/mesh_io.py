@@ -5,7 +5,17 @@
 ``export_mesh`` is the device path: marching-cubes index coordinates, the frame transforms and the uint8 colours are turned into
 the two record arrays by csrc/mesh_pack.hip, copied to the host once and written with a single ``write``.
 ``write_ply`` / ``read_ply`` are the host-side (numpy) file layer, also used by the ``trimesh`` shim.
-trimesh itself is not vendored with the reference (requirements.txt); the header text follows its published PLY template."""
+trimesh itself is not vendored with the reference (requirements.txt); the header text follows its published PLY template.
+
+Asset formats (the reference's utils/utils.py:31-47, convert_mesh_format behind run.py --output_format): binary glTF (``.glb``) and vertex-coloured
+Wavefront OBJ (``.obj``) in the asset frame -- (x, y, z) -> (x, z, y), z-up -> glTF's y-up, every face reversed; the reference's two rotations and
+x flip compose to exactly that.  ``write_glb`` / ``write_obj`` / ``read_glb`` / ``read_obj`` / ``convert_mesh`` are the host layer (numpy, no GPU) and the
+DEFINITION of the two files; ``export_asset`` is the device path (csrc/mesh_export.hip): buffers and OBJ text are produced on the device, one D2H copy
+per buffer, one file write.  No byte parity with trimesh's own OBJ / GLB writers is claimed (trimesh is not available to compare against)."""
+import json
+import os
+import struct
+
 import numpy as np
 
 _VERTEX = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
@@ -109,3 +119,268 @@ def export_mesh(path, verts_idx, tris, grid_R, bound_min=(-1.0, -1.0, -1.0), bou
     vrec, frec = ops.mesh_pack(verts_idx, tris, grid_R, bound_min, bound_max, scale_mat, trans_mat, vertex_colors)
     write_records(path, vrec.cpu().numpy(), frec.cpu().numpy(), vertex_colors is not None)
     return int(verts_idx.shape[0]), int(tris.shape[0])
+
+
+# ------------------------------------------------------------------------------------------------------------------ asset formats (GLB / OBJ)
+def to_asset_frame(vertices, faces):
+    """PLY frame -> asset frame: y and z exchanged (a reflection), every face reversed (the two cancel: outward faces stay outward)."""
+    return np.ascontiguousarray(np.asarray(vertices)[:, [0, 2, 1]]), np.ascontiguousarray(np.asarray(faces)[:, ::-1])
+
+
+def _rgba(colors, n):
+    if colors is None:
+        return None
+    c = np.ascontiguousarray(colors, np.uint8)
+    if c.ndim != 2 or c.shape[0] != n or c.shape[1] not in (3, 4):
+        raise ValueError(f"colors must be [N,3] or [N,4] uint8 for N = {n} vertices, got {c.shape}")
+    if c.shape[1] == 3:
+        c = np.concatenate([c, np.full((n, 1), 255, np.uint8)], 1)
+    return c
+
+
+def _host_mesh(positions, faces, colors, normals):
+    p = np.ascontiguousarray(positions, np.float32).reshape(-1, 3)
+    f = np.ascontiguousarray(faces).reshape(-1, 3)
+    if f.size and (f.min() < 0 or f.max() >= p.shape[0]):
+        raise ValueError(f"faces index outside 0 .. {p.shape[0] - 1}")
+    nr = None if normals is None else np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+    if nr is not None and nr.shape[0] != p.shape[0]:
+        raise ValueError(f"normals must be [N,3] for N = {p.shape[0]} vertices, got {nr.shape}")
+    return p, f.astype(np.uint32), _rgba(colors, p.shape[0]), nr
+
+
+_GLB_MAGIC, _GLB_JSON, _GLB_BIN = 0x46546C67, 0x4E4F534A, 0x004E4942
+
+
+def glb_json(n, m, colors, normals, pos_min, pos_max):
+    """The JSON chunk (bytes, space-padded to a multiple of 4): one buffer, views in the order indices / POSITION / COLOR_0 / NORMAL, one accessor per
+    view, one mesh with one triangle primitive, one node, one scene.  Fixed key order and separators: the bytes are reproducible."""
+    views, accessors, off = [], [], 0
+
+    def add(nbytes, target, accessor):
+        nonlocal off
+        views.append({"buffer": 0, "byteOffset": off, "byteLength": nbytes, "target": target})
+        accessors.append(dict({"bufferView": len(views) - 1, "byteOffset": 0}, **accessor))
+        off += (nbytes + 3) // 4 * 4
+        return len(accessors) - 1
+
+    num = lambda a: [float(x) + 0.0 for x in a]                       # + 0.0: one spelling of zero
+    indices = add(12 * m, 34963, {"componentType": 5125, "count": 3 * m, "type": "SCALAR"})
+    attrs = {"POSITION": add(12 * n, 34962, {"componentType": 5126, "count": n, "type": "VEC3", "min": num(pos_min), "max": num(pos_max)})}
+    if colors:
+        attrs["COLOR_0"] = add(4 * n, 34962, {"componentType": 5121, "normalized": True, "count": n, "type": "VEC4"})
+    if normals:
+        attrs["NORMAL"] = add(12 * n, 34962, {"componentType": 5126, "count": n, "type": "VEC3"})
+    doc = {"asset": {"version": "2.0", "generator": "o2345-hip"}, "scene": 0, "scenes": [{"nodes": [0]}], "nodes": [{"mesh": 0}],
+           "meshes": [{"primitives": [{"attributes": attrs, "indices": indices, "mode": 4}]}], "accessors": accessors, "bufferViews": views,
+           "buffers": [{"byteLength": off}]}
+    js = json.dumps(doc, separators=(",", ":")).encode("ascii")
+    return js + b" " * (-len(js) % 4)
+
+
+def write_glb_buffers(path, indices, positions, rgba, normals, bounds):
+    """GLB from its four buffers as they sit in the file (host arrays: indices uint32 [M,3], positions float32 [N,3], rgba uint8 [N,4] or None, normals
+    float32 [N,3] or None; bounds [2,3] = per-axis min, max of positions): 12-byte header, JSON chunk, BIN chunk; every view is a multiple of 4 bytes."""
+    n, m = positions.shape[0], indices.shape[0]
+    if n == 0 or m == 0:
+        raise ValueError("GLB export: an empty mesh has no valid glTF form (accessors need count >= 1)")
+    bounds = np.asarray(bounds, np.float32).reshape(2, 3)
+    js = glb_json(n, m, rgba is not None, normals is not None, bounds[0], bounds[1])
+    parts = [np.ascontiguousarray(a).reshape(-1).view(np.uint8) for a in (indices, positions, rgba, normals) if a is not None]
+    nbin = sum(a.size for a in parts)
+    assert indices.dtype.itemsize == 4 and positions.dtype == np.float32 and nbin % 4 == 0
+    with open(path, "wb") as f:
+        f.write(struct.pack("<III", _GLB_MAGIC, 2, 12 + 8 + len(js) + 8 + nbin) + struct.pack("<II", len(js), _GLB_JSON) + js + struct.pack("<II", nbin, _GLB_BIN))
+        for a in parts:
+            f.write(a.data)
+
+
+def write_glb(path, positions, faces, colors=None, normals=None):
+    """Host arrays in (positions [N,3] float, faces [M,3] int, colors [N,3|4] uint8 or None, normals [N,3] float or None), ALREADY in the asset frame."""
+    p, f, c, nr = _host_mesh(positions, faces, colors, normals)
+    if p.shape[0] == 0 or f.shape[0] == 0:
+        raise ValueError("GLB export: an empty mesh has no valid glTF form (accessors need count >= 1)")
+    write_glb_buffers(path, f, p, c, nr, np.stack([p.min(0), p.max(0)]))
+
+
+_GLB_TYPES = {5121: ("u1", 1), 5125: ("<u4", 4), 5126: ("<f4", 4)}
+_GLB_WIDTH = {"SCALAR": 1, "VEC3": 3, "VEC4": 4}
+
+
+def read_glb(path):
+    """Parser for the files written above -> (positions float32 [N,3], faces int32 [M,3], colors uint8 [N,4] or None, normals float32 [N,3] or None)."""
+    raw = open(path, "rb").read()
+    magic, version, total = struct.unpack_from("<III", raw, 0)
+    assert magic == _GLB_MAGIC and version == 2 and total == len(raw)
+    jlen, jtype = struct.unpack_from("<II", raw, 12)
+    assert jtype == _GLB_JSON
+    doc = json.loads(raw[20:20 + jlen].decode("ascii"))
+    blen, btype = struct.unpack_from("<II", raw, 20 + jlen)
+    assert btype == _GLB_BIN and 28 + jlen + blen == len(raw)
+    base = 28 + jlen
+
+    def accessor(i):
+        a = doc["accessors"][i]
+        v = doc["bufferViews"][a["bufferView"]]
+        dt, _ = _GLB_TYPES[a["componentType"]]
+        w = _GLB_WIDTH[a["type"]]
+        return np.frombuffer(raw, dt, a["count"] * w, base + v["byteOffset"] + a.get("byteOffset", 0)).reshape(-1, w)
+
+    prim = doc["meshes"][0]["primitives"][0]
+    at = prim["attributes"]
+    faces = accessor(prim["indices"]).reshape(-1, 3).astype(np.int32)
+    return (accessor(at["POSITION"]).copy(), faces, accessor(at["COLOR_0"]).copy() if "COLOR_0" in at else None,
+            accessor(at["NORMAL"]).copy() if "NORMAL" in at else None)
+
+
+def obj_coordinate_digits(bounds):
+    """K of the OBJ coordinate field: integer digits of the largest |coordinate| once rounded to 8 decimals (at least 1).  ``bounds``: any array holding
+    the per-axis min and max (or the coordinates themselves).  Refuses non-finite values and K > 9 (the packers format through a 64-bit integer)."""
+    b = np.asarray(bounds, np.float64)
+    a = float(np.abs(b).max()) if b.size else 0.0
+    if not np.isfinite(a) or a >= 1e9:
+        raise ValueError(f"OBJ export: largest |coordinate| {a} is not finite or needs more than 9 integer digits")
+    K = len(str(int(np.rint(a * 1e8)) // 10 ** 8))                      # a * 1e8 is exact in fp64 for a float32 a: 24-bit significand x 5^8 < 2^53
+    if K > 9:
+        raise ValueError(f"OBJ export: largest |coordinate| {a} needs more than 9 integer digits")
+    return K
+
+
+def obj_text_bytes(n, m, K, colors, normals):
+    """Closed-form size of the OBJ text (== o2345_obj_text_bytes): every record of a kind has the same length."""
+    dn = len(str(int(n)))
+    return n * (1 + 3 * (K + 11) + (33 if colors else 0) + 1) + (n * 39 if normals else 0) + m * (1 + 3 * (1 + (2 * dn + 2 if normals else dn)) + 1)
+
+
+_OBJ_TABLE = None
+
+
+def obj_color_table():
+    """256 x 11 bytes: entry c is " %.8f" % (c / 255) -- the colour field of an OBJ vertex record, formatted once."""
+    global _OBJ_TABLE
+    if _OBJ_TABLE is None:
+        _OBJ_TABLE = np.frombuffer("".join(" %.8f" % (c / 255.0) for c in range(256)).encode("ascii"), np.uint8).reshape(256, 11).copy()
+    return _OBJ_TABLE
+
+
+def obj_text_numpy(positions, indices, rgba, normals, K):
+    """The OBJ text from printf-style formatting on the host (the definition the library's packers are tested against): float32 positions / normals
+    widened to float64 (exact), "%*.8f" rounds correctly."""
+    n, dn, w = positions.shape[0], len(str(positions.shape[0])), K + 10
+    vfmt = "v" + (" %%%d.8f" % w) * 3 + (" %.8f" * 3 if rgba is not None else "") + "\n"
+    rows = positions.astype(np.float64).tolist()
+    if rgba is not None:
+        rows = [r + c for r, c in zip(rows, (rgba[:, :3].astype(np.float64) / 255.0).tolist())]
+    out = [vfmt % tuple(r) for r in rows]
+    if normals is not None:
+        out += ["vn %11.8f %11.8f %11.8f\n" % tuple(r) for r in normals.astype(np.float64).tolist()]
+    faces = (indices.astype(np.int64) + 1).tolist()
+    if normals is not None:
+        ffmt = "f" + (" %%%ds" % (2 * dn + 2)) * 3 + "\n"
+        out += [ffmt % tuple("%d//%d" % (a, a) for a in r) for r in faces]
+    else:
+        ffmt = "f" + (" %%%dd" % dn) * 3 + "\n"
+        out += [ffmt % tuple(r) for r in faces]
+    return "".join(out).encode("ascii")
+
+
+def write_obj_numpy(path, positions, faces, colors=None, normals=None):
+    """The OBJ file from host formatting alone (the definition write_obj and the device path are tested against)."""
+    p, f, c, nr = _host_mesh(positions, faces, colors, normals)
+    with open(path, "wb") as fh:
+        fh.write(obj_text_numpy(p, f, c, nr, obj_coordinate_digits(p)))
+
+
+def write_obj(path, positions, faces, colors=None, normals=None):
+    """Host arrays in (as write_glb), ALREADY in the asset frame -> vertex-coloured OBJ of fixed-width records ("v x y z [r g b]", "vn", "f a b c" or
+    "f a//a b//b c//c", 1-based).  The text is packed by the library's host-side packer (o2345_obj_text_host; a few threads, no device work); without a
+    loadable library the host formatter writes the same bytes, seconds slower per million records."""
+    import ctypes
+    from . import _lib
+    p, f, c, nr = _host_mesh(positions, faces, colors, normals)
+    K = obj_coordinate_digits(p)
+    try:
+        L = _lib.lib()
+    except (RuntimeError, OSError, AttributeError) as e:
+        global _WARNED
+        if not _WARNED:
+            import warnings
+            warnings.warn(f"o2345 mesh_io.write_obj: libo2345_hip.so is not loadable ({e}); formatting the OBJ on the host (same bytes)")
+            _WARNED = True
+        with open(path, "wb") as fh:
+            fh.write(obj_text_numpy(p, f, c, nr, K))
+        return
+    text = np.empty(obj_text_bytes(p.shape[0], f.shape[0], K, c is not None, nr is not None), np.uint8)
+    assert text.size == L.o2345_obj_text_bytes(p.shape[0], f.shape[0], K, int(c is not None), int(nr is not None))
+    P = lambda a: None if a is None or a.size == 0 else a.ctypes.data_as(ctypes.c_void_p)
+    _lib.check(L.o2345_obj_text_host(P(p), P(c), P(nr), p.shape[0], P(f), f.shape[0], K, P(text)), "obj_text_host")
+    with open(path, "wb") as fh:
+        fh.write(text.data)
+
+
+def read_obj(path):
+    """Parser for the files written above -> (positions float64 [N,3], faces int32 [M,3] 0-based, colors uint8 [N,3] or None, normals float64 [N,3] or
+    None).  Positions stay float64: the decimal text is not the float32 it came from, only within 0.5e-8 of it."""
+    v, vn, f = [], [], []
+    with open(path, "r", encoding="ascii") as fh:
+        for line in fh:
+            t = line.split()
+            if not t:
+                continue
+            if t[0] == "v":
+                v.append([float(x) for x in t[1:]])
+            elif t[0] == "vn":
+                vn.append([float(x) for x in t[1:]])
+            elif t[0] == "f":
+                f.append([int(x.split("/")[0]) - 1 for x in t[1:]])
+    va = np.asarray(v, np.float64).reshape(len(v), -1) if v else np.zeros((0, 3))
+    cols = np.rint(va[:, 3:6] * 255.0).astype(np.uint8) if va.shape[1] >= 6 else None
+    return (np.ascontiguousarray(va[:, :3]), np.asarray(f, np.int32).reshape(-1, 3), cols, np.asarray(vn, np.float64).reshape(-1, 3) if vn else None)
+
+
+def _asset_ext(path):
+    ext = os.path.splitext(str(path))[1].lower()
+    if ext not in (".glb", ".obj", ".ply"):
+        raise ValueError(f"mesh export: format {ext!r} of {path!r} is not one of .ply, .glb, .obj")
+    return ext
+
+
+def convert_mesh(ply_path, out_path):
+    """convert_mesh_format (utils/utils.py:31-47) for a mesh already on disk: read the PLY, exchange y and z, reverse the faces, write ``out_path`` by its
+    extension (.glb or .obj) with the PLY's vertex colours.  Returns ``out_path``."""
+    ext = _asset_ext(out_path)
+    if ext == ".ply":
+        raise ValueError("convert_mesh: the output is .glb or .obj")
+    v, f, c = read_ply(ply_path)
+    v, f = to_asset_frame(v, f)
+    (write_glb if ext == ".glb" else write_obj)(out_path, v, f, c)
+    return out_path
+
+
+def export_asset(path, verts_idx, tris, grid_R, bound_min=(-1.0, -1.0, -1.0), bound_max=(1.0, 1.0, 1.0), scale_mat=None, trans_mat=None,
+                 vertex_colors=None, normals=None):
+    """Device path by extension: ``.ply`` -> export_mesh (reconstruction frame, unchanged); ``.glb`` / ``.obj`` -> asset frame.  Arguments as for export_mesh;
+    ``normals``: the SDF gradient at the vertices, fp32 [N,3] on the device (exported as unit normals), or None.  Buffers and OBJ text are produced on
+    the device (csrc/mesh_export.hip), copied to the host once each and written in one go.  Returns (n_vertices, n_triangles)."""
+    ext = _asset_ext(path)
+    if ext == ".ply":
+        return export_mesh(path, verts_idx, tris, grid_R, bound_min, bound_max, scale_mat, trans_mat, vertex_colors)
+    from . import ops
+    n, m = int(verts_idx.shape[0]), int(tris.shape[0])
+    if n == 0 or m == 0:
+        if ext == ".glb":
+            raise ValueError("GLB export: an empty mesh has no valid glTF form (accessors need count >= 1)")
+        open(path, "wb").close()                                      # a valid OBJ with no records
+        return n, m
+    pos, rgba, nrm, idx, bounds = ops.mesh_asset_pack(verts_idx, tris, grid_R, bound_min, bound_max, scale_mat, trans_mat, vertex_colors, normals)
+    if ext == ".glb":
+        host = ops.to_host_numpy(*[t for t in (idx, pos, rgba, nrm, bounds) if t is not None])
+        h_idx, h_pos = host[0].view(np.uint32), host[1]
+        h_rgba = host[2] if rgba is not None else None
+        h_nrm = host[2 + (rgba is not None)] if nrm is not None else None
+        write_glb_buffers(path, h_idx, h_pos, h_rgba, h_nrm, host[-1])
+    else:
+        text = ops.obj_text(pos, idx, rgba, nrm, bounds=bounds)
+        with open(path, "wb") as fh:
+            fh.write(ops.to_host_numpy(text)[0].data)
+    return n, m

@@ -7,7 +7,7 @@ import threading
 import numpy as np
 import torch
 
-from . import _lib, config
+from . import _lib, config, mesh_io
 from ._lib import check
 
 
@@ -785,6 +785,62 @@ def mesh_pack(verts_idx, tris, grid_R, bound_min=(-1.0, -1.0, -1.0), bound_max=(
                                      _p(vrec, torch.uint8), _stream()), "mesh_pack_vertices")
     check(L.o2345_mesh_pack_faces(_p(tris, tris.dtype), 8 if tris.dtype == torch.int64 else 4, m, _p(frec, torch.uint8), _stream()), "mesh_pack_faces")
     return vrec, frec
+
+
+@_on_device
+def mesh_asset_pack(verts_idx, tris, grid_R, bound_min=(-1.0, -1.0, -1.0), bound_max=(1.0, 1.0, 1.0), scale_mat=None, trans_mat=None, rgb=None, grad=None):
+    """Index-space vertices (fp64 [N,3]) + triangles -> the buffers of a GLB / OBJ in the asset frame (utils/utils.py:31-47: (x, y, z) -> (x, z, y),
+    faces reversed): (positions float32 [N,3], rgba uint8 [N,4] or None, normals float32 [N,3] or None, indices uint32-valued int32 storage [M,3],
+    bounds float32 [2,3] = per-axis min, max of positions), all on the device.  ``rgb`` fp32 [N,3] in [0,1]; ``grad`` fp32 [N,3], the SDF gradient."""
+    dev = verts_idx.device
+    n, m = verts_idx.shape[0], tris.shape[0]
+    host = lambda a: None if a is None else np.ascontiguousarray((a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)), np.float32)
+    bmin, bmax = host(bound_min).reshape(3), host(bound_max).reshape(3)
+    sm, tm = host(scale_mat), host(trans_mat)
+    sm = None if sm is None else sm.reshape(-1, 4, 4)[0].copy()
+    tm = None if tm is None else tm.reshape(-1, 4, 4)[0].copy()
+    cp = lambda a: None if a is None else a.ctypes.data_as(ctypes.c_void_p)
+    pos = torch.empty(n, 3, dtype=torch.float32, device=dev)
+    rgba = None if rgb is None else torch.empty(n, 4, dtype=torch.uint8, device=dev)
+    nrm = None if grad is None else torch.empty(n, 3, dtype=torch.float32, device=dev)
+    idx = torch.empty(m, 3, dtype=torch.int32, device=dev)              # uint32 bit patterns (torch has no general uint32): vertex counts stay below 2^31
+    bounds = torch.empty(2, 3, dtype=torch.float32, device=dev)
+    L = _lib.lib()
+    wsb = L.o2345_mesh_bounds_workspace_bytes(n)
+    ws = _workspace(wsb, dev, "mesh_bounds")
+    check(L.o2345_mesh_asset_vertices(_p(verts_idx, torch.float64), n, int(grid_R), cp(bmin), cp(bmax), cp(sm), cp(tm), _p(rgb), _p(grad), _p(pos),
+                                      _p(rgba, torch.uint8), _p(nrm), _p(bounds), _p(ws, torch.uint8), wsb, _stream()), "mesh_asset_vertices")
+    check(L.o2345_mesh_asset_indices(_p(tris, tris.dtype), 8 if tris.dtype == torch.int64 else 4, m, _p(idx, torch.int32), _stream()), "mesh_asset_indices")
+    return pos, rgba, nrm, idx, bounds
+
+
+_obj_tables = {}
+
+
+def _obj_color_table(device):
+    """mesh_io.obj_color_table() (256 x 11 bytes, formatted once on the host) on ``device``, kept per device."""
+    key = str(device)
+    if key not in _obj_tables:
+        _obj_tables[key] = torch.from_numpy(mesh_io.obj_color_table()).to(device)
+    return _obj_tables[key]
+
+
+@_on_device
+def obj_text(positions, indices, rgba=None, normals=None, K=None, bounds=None):
+    """The buffers of mesh_asset_pack -> the bytes of a Wavefront OBJ (uint8 tensor on the device): fixed-width "v" [+ colour], "vn", "f" records
+    (include/o2345.h).  ``K``: integer digits of the coordinate fields; taken from ``bounds`` (one small D2H copy) when not given."""
+    n, m = positions.shape[0], indices.shape[0]
+    if K is None:
+        K = mesh_io.obj_coordinate_digits(bounds.cpu().numpy() if torch.is_tensor(bounds) else bounds) if n else 1
+    L = _lib.lib()
+    nbytes = L.o2345_obj_text_bytes(n, m, int(K), int(rgba is not None), int(normals is not None))
+    if not 1 <= int(K) <= 9:
+        raise ValueError(f"obj_text: K = {K} integer digits (1 .. 9)")
+    text = torch.empty(nbytes, dtype=torch.uint8, device=positions.device)
+    table = _obj_color_table(positions.device) if rgba is not None else None
+    check(L.o2345_obj_text(_p(positions), _p(rgba, torch.uint8), _p(normals), n, _p(indices, torch.int32), m, int(K), _p(table, torch.uint8),
+                           _p(text, torch.uint8), _stream()), "obj_text")
+    return text
 
 
 @_on_device

@@ -186,24 +186,29 @@ def render_scene_split(wt, imgs, affine_mats, origin, D, voxel_size, proj, cam_p
     return sh.gather_ray_blocks(block, rays_o.shape[0], per, device=dev), vol
 
 
-@torch.no_grad()
-def extract_mesh(wt, vol, proj, cam_pos, resolution, return_index_verts=False):
-    """extract_fields + marching cubes + vertex colouring (trainer_generic.py:1309-1363), all on the device."""
+def _mesh_fields(wt, vol, proj, cam_pos, resolution):
+    """The device work of extract_mesh, once: (verts fp64 in [-1, 1], verts_idx fp64 index coordinates, tris, rgb, u, grad).  ``grad`` is the SDF gradient
+    at the vertices that the colour network takes as its normal input (None for an empty mesh): the asset export reuses it for the NORMAL attribute."""
     prec = wt.sdf_precision
     u = ops.sdf_mlp(wt.sdf_blob, vol["vol_cl"], None, variant=0, grid_R=resolution, sign=-1.0, precision=prec, grid_tables=wt.grid_tables(resolution))["sdf"]
     u = u.view(resolution, resolution, resolution)
     verts_idx, tris = ops.marching_cubes(u, 0.0)
     verts = (verts_idx / (resolution - 1.0) * 2.0 - 1.0)                      # sparse_neus_renderer.py:936
     pts = verts.to(torch.float32).contiguous()
-    if return_index_verts:
-        verts = verts_idx
     if pts.shape[0] == 0:
-        return verts, tris, torch.zeros(0, 3, device=pts.device), u
+        return verts, verts_idx, tris, torch.zeros(0, 3, device=pts.device), u, None
     g = ops.sdf_mlp(wt.sdf_blob, vol["vol_cl"], pts, variant=2, precision=prec)["grad"]
     x3 = wt.color_precision == "f16x3"
     rgb, _ = ops.color_points(wt.color_xblob if x3 else wt.color_mblob, vol["vol_cl"], vol["maskvol"], vol["cmaps"], proj, cam_pos, pts, normals=g,
                               want_nviews=False, mfma="x3" if x3 else True)
-    return verts, tris, rgb, u
+    return verts, verts_idx, tris, rgb, u, g
+
+
+@torch.no_grad()
+def extract_mesh(wt, vol, proj, cam_pos, resolution, return_index_verts=False):
+    """extract_fields + marching cubes + vertex colouring (trainer_generic.py:1309-1363), all on the device."""
+    verts, verts_idx, tris, rgb, u, _ = _mesh_fields(wt, vol, proj, cam_pos, resolution)
+    return (verts_idx if return_index_verts else verts), tris, rgb, u
 
 
 @torch.no_grad()
@@ -218,17 +223,38 @@ def export_mesh_ply(path, wt, vol, proj, cam_pos, resolution, scale_mat=None, tr
 
 
 @torch.no_grad()
-def reconstruct_folder(root_dir, name, wt, out_ply, D=96, resolution=256, render_val_image=False):
+def export_mesh_asset(path, wt, vol, proj, cam_pos, resolution, scale_mat=None, trans_mat=None, normals=False):
+    """export_mesh_ply followed by convert_mesh_format (utils/utils.py:31-47) without the PLY in between: the coloured mesh as ``.glb`` or ``.obj`` in the
+    asset frame ((x, y, z) -> (x, z, y), faces reversed), buffers / text packed on the device (csrc/mesh_export.hip).  ``normals=True`` adds unit vertex
+    normals from the SDF gradient the vertex colouring already computed.  A ``.ply`` path gives export_mesh_ply's file.  Returns (n_vertices, n_triangles)."""
+    from . import mesh_io
+    _, verts_idx, tris, rgb, _, g = _mesh_fields(wt, vol, proj, cam_pos, resolution)
+    return mesh_io.export_asset(path, verts_idx, tris, resolution, scale_mat=scale_mat, trans_mat=trans_mat,
+                                vertex_colors=rgb if verts_idx.shape[0] else None, normals=g if normals else None)
+
+
+@torch.no_grad()
+def reconstruct_folder(root_dir, name, wt, out_ply, D=96, resolution=256, render_val_image=False, output_format=None):
     """run.py's reconstruction stage without the reference tree: Zero123-style folder (dataset.SceneFolder) -> coloured mesh (binary PLY in
-    the original frame), optionally the val image of the target view.  Returns dict(vertices, triangles, kept_voxels[, color, depth])."""
-    from . import dataset
+    the original frame), optionally the val image of the target view.  ``output_format`` ".obj" / ".glb" (run.py --output_format) also writes
+    ``mesh<ext>`` next to ``out_ply`` in the asset frame, from the same device buffers.  Returns dict(vertices, triangles, kept_voxels, ply[, asset]
+    [, color, depth])."""
+    import os
+    from . import dataset, mesh_io
+    if output_format not in (None, ".ply", ".obj", ".glb"):
+        raise ValueError(f"reconstruct_folder: output_format {output_format!r} is not one of '.ply', '.obj', '.glb'")
     s = dataset.SceneFolder(root_dir, "export_mesh", specific_dataset_name=name)[0]
     dev = wt.device
     T = lambda t: t.to(dev).contiguous().float()
     vol = build_volume(wt, T(s["images"]), T(s["affine_mats"]), s["partial_vol_origin"].numpy(), D, 2.0 / (D - 1))
     proj, cam_pos = camera_terms(T(s["intrinsics"]), T(s["w2cs"]))
-    nv, nt = export_mesh_ply(out_ply, wt, vol, proj, cam_pos, resolution, scale_mat=s["scale_mat"], trans_mat=s["trans_mat"])
-    out = {"vertices": nv, "triangles": nt, "kept_voxels": int(vol["n_voxels"])}
+    _, verts_idx, tris, rgb, _, _ = _mesh_fields(wt, vol, proj, cam_pos, resolution)
+    rgb = rgb if verts_idx.shape[0] else None
+    nv, nt = mesh_io.export_mesh(out_ply, verts_idx, tris, resolution, scale_mat=s["scale_mat"], trans_mat=s["trans_mat"], vertex_colors=rgb)
+    out = {"vertices": nv, "triangles": nt, "kept_voxels": int(vol["n_voxels"]), "ply": str(out_ply)}
+    if output_format in (".obj", ".glb"):
+        out["asset"] = os.path.join(os.path.dirname(str(out_ply)), "mesh" + output_format)
+        mesh_io.export_asset(out["asset"], verts_idx, tris, resolution, scale_mat=s["scale_mat"], trans_mat=s["trans_mat"], vertex_colors=rgb)
     if render_val_image:
         r = render(wt, vol, proj, cam_pos, T(s["rays"]["rays_o"]), T(s["rays"]["rays_v"]), float(s["query_near_far"][0]), float(s["query_near_far"][1]),
                    T(s["query_c2w"][:3, 3]))
