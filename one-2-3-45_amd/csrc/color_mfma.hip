@@ -317,11 +317,8 @@ static int color_mfma_launch(bool x3, const float* blob, const float* vol_cl, co
         a.sched = color_sched_mode();
         int G = 4;
         while (G < V) G <<= 1;
-        const int n_cu = cu_count();
         const int threads = 768, ppt = 32 / G;
-        const long long per_block = (long long)(threads / 64) * ppt;
-        long long want = n_dev ? n_cu : (n + per_block - 1) / per_block;
-        const unsigned grid = persistent_grid(want, n_cu);
+        const unsigned grid = network_grid(n, n_dev, threads, ppt);
         const size_t lds = (size_t)((x3 ? CX_TOTAL : CM_TOTAL) + (threads / 64) * ppt * (2 * 64 + 4)) * sizeof(float);
         hipStream_t s = (hipStream_t)stream;
 #define O2345_CM_CASE(GG, XX)                                                                                              \

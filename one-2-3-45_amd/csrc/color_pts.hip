@@ -474,11 +474,8 @@ int color_pts_launch(int x3, const float* blob, const float* vol_cl, const float
     ColorMArgs a{blob, vol_cl, maskvol, D, cmaps, proj, cam_pos, V, H, W, pts, index, n_dev, n, query_cam, normals, out_rgb, out_nviews};
     a.sched = color_sched_mode();
     a.stats = stats_dev;
-    const int n_cu = cu_count();
     const int threads = CP_THREADS;
-    const long long per_block = (long long)(threads / 64) * 32;
-    long long want = n_dev ? n_cu : (n + per_block - 1) / per_block;
-    const unsigned grid = persistent_grid(want, n_cu);
+    const unsigned grid = network_grid(n, n_dev, threads, 32);
     const size_t lds = color_pts_lds_bytes(x3);
     hipStream_t s = (hipStream_t)stream;
     if (x3) {
@@ -556,9 +553,7 @@ int color_feats_launch(int x3, const float* blob, const float* geo, const float*
     ColorMArgs a{};
     a.blob = blob; a.V = V; a.n = n; a.out_rgb = out_rgb; a.out_nviews = out_nviews;
     a.f_geo = geo; a.f_rgb = rgb_feat; a.f_rdiff = ray_diff; a.f_mask = mask;
-    const int n_cu = cu_count();
-    const long long per_block = (long long)(CP_THREADS / 64) * 32;
-    const unsigned grid = persistent_grid((n + per_block - 1) / per_block, n_cu);
+    const unsigned grid = network_grid(n, nullptr, CP_THREADS, 32);
     const size_t lds = color_pts_lds_bytes(x3);
     hipStream_t s = (hipStream_t)stream;
     if (x3) {

@@ -140,6 +140,14 @@ inline unsigned persistent_grid(long long want, int n_cu) {
     return g;
 }
 
+// host side: grid of a persistent network kernel whose workgroups of `threads` threads take `units_per_wave` units (points, rays) per wave and tile;
+// with a device-side count (n_dev) the size is unknown here and every compute unit gets a workgroup
+inline unsigned network_grid(long long n, const void* n_dev, int threads, int units_per_wave) {
+    const int n_cu = cu_count();
+    const long long per_block = (long long)(threads / 64) * units_per_wave;
+    return persistent_grid(n_dev ? n_cu : (n + per_block - 1) / per_block, n_cu);
+}
+
 #if defined(__HIPCC__)
 // Tile schedule of the persistent network kernels.  Workgroups are dispatched round-robin over the 8 XCDs (block b runs on XCD
 // b % 8) and every XCD has its own 4 MB L2: handing consecutive tiles to consecutive blocks makes each XCD stream the whole

@@ -19,11 +19,8 @@ namespace o2345 {
 template <int VARIANT>
 __global__ __launch_bounds__(512) void k_sdf_mlp(SdfArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    // ---- stage the wide-layer blobs in LDS ------------------------------------------------------------------------
-    // VAR_SDF : A0 | A1 | misc           VAR_FULL : A1 | A2 | misc          VAR_GRAD : A1 | A1T | misc
-    constexpr int N_A0 = 4 * ST0 * 64, N_A1 = 4 * ST1 * 64, N_A1T = 5 * STB * 64;
-    constexpr int L_FIRST = (VARIANT == VAR_SDF) ? N_A0 : N_A1;
-    constexpr int L_SECOND = (VARIANT == VAR_SDF) ? N_A1 : (VARIANT == VAR_FULL ? N_A1 : N_A1T);
+    // ---- stage the wide-layer blobs in LDS (layout: sdf_common.h) ---------------------------------------------------
+    constexpr int L_FIRST = sdf_lds_first(VARIANT), L_SECOND = sdf_lds_second(VARIANT);
     {
         const float* src1 = a.blob + (VARIANT == VAR_SDF ? OFF_A0 : OFF_A1);
         const float* src2 = a.blob + (VARIANT == VAR_SDF ? OFF_A1 : (VARIANT == VAR_FULL ? OFF_A2 : OFF_A1T));
@@ -48,71 +45,30 @@ __global__ __launch_bounds__(512) void k_sdf_mlp(SdfArgs a) {
     const int wave = threadIdx.x >> 6, nwave = blockDim.x >> 6;
     const TileSched ts = tile_schedule(n, 32, wave, nwave);
     for (long long tile = ts.first; tile < ts.end; tile += ts.stride) {
-        const long long t0 = tile * 32;
-        const long long i = t0 + j;
+        const long long i = tile * 32 + j;
         const bool live = i < n;
-        long long slot = live ? (a.index ? (long long)a.index[i] : i) : 0;
-        float px, py, pz;
-        if (a.pts) {
-            px = live ? a.pts[slot * 3 + 0] : 0.f; py = live ? a.pts[slot * 3 + 1] : 0.f; pz = live ? a.pts[slot * 3 + 2] : 0.f;
-        } else {
-            const int R = a.R;
-            const unsigned us = (unsigned)slot, uR = (unsigned)R;          // R^3 < 2^32: 32-bit divisions (the 64-bit ones cost 240 instructions)
-            const unsigned uq = us / uR;
-            const int iz = (int)(us - uq * uR), ix = (int)(uq / uR), iy = (int)(uq - (uq / uR) * uR);
-            px = lin11(ix, R); py = lin11(iy, R); pz = lin11(iz, R);
-        }
-        // ---- trilinear latent (this half's 8 channels), reference semantics; optional Jacobian ----------------
+        const TilePoint pt = sdf_tile_point(a, a.pts != nullptr, i, live);
+        const long long slot = pt.slot;
+        const float px = pt.px, py = pt.py, pz = pt.pz;
+        // ---- trilinear latent (this half's 8 channels), or the caller's ---------------------------------------------
         float lat[8];
-#pragma unroll
-        for (int c = 0; c < 8; ++c) lat[c] = 0.f;
         if (a.lat_in) {
+#pragma unroll
+            for (int c = 0; c < 8; ++c) lat[c] = 0.f;
             if (live) {
                 const float4* p4 = reinterpret_cast<const float4*>(a.lat_in + slot * 16 + 8 * h);
                 const float4 v0 = p4[0], v1 = p4[1];
                 lat[0] = v0.x; lat[1] = v0.y; lat[2] = v0.z; lat[3] = v0.w; lat[4] = v1.x; lat[5] = v1.y; lat[6] = v1.z; lat[7] = v1.w;
             }
         } else {
-            const Taps3D tp = trilinear_ref_taps(px, py, pz, a.D);
-            if (tp.ok && live) {
-#pragma unroll
-                for (int dx = 0; dx < 2; ++dx)
-#pragma unroll
-                    for (int dy = 0; dy < 2; ++dy)
-#pragma unroll
-                        for (int dz = 0; dz < 2; ++dz) {
-                            const size_t vox = ((size_t)tp.ix[dx] * a.D + tp.iy[dy]) * a.D + tp.iz[dz];
-                            const float4* p4 = reinterpret_cast<const float4*>(a.vol_cl + vox * 16 + 8 * h);
-                            const float4 v0 = p4[0], v1 = p4[1];
-                            const float v[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
-                            const float w = tp.fz[dz] * tp.fy[dy] * tp.fx[dx];
-#pragma unroll
-                            for (int c = 0; c < 8; ++c) lat[c] = fmaf(v[c], w, lat[c]);
-                        }
-            }
+            latent_gather(a.vol_cl, a.D, px, py, pz, h, live, lat);
         }
-        // ---- positional encoding: this half's 20 slots --------------------------------------------------------------
-        // slots 0..8: sin of combo (9h+t); 9..17: cos of combo (9h+t-9); combo c = 3*freq + dim; 18: x|z; 19: y|0
         float pe[20];
-        const float p3[3] = {px, py, pz};
-#pragma unroll
-        for (int t = 0; t < 9; ++t) {
-            const int c = 9 * h + t;            // h is wave-half uniform
-            const int d = t % 3;                // (9h + t) % 3 == t % 3
-            const float f = (float)(1 << (c / 3));
-            float s, co;
-            sincos_pe(p3[d] * f, s, co);
-            pe[t] = s; pe[9 + t] = co;
-        }
-        pe[18] = h ? pz : px;
-        pe[19] = h ? 0.f : py;
+        pe_half(px, py, pz, h, pe);
 
         // ---- layer 0 ---------------------------------------------------------------------------------------------------
         f32x16 acc[4];
-#pragma unroll
-        for (int nb = 0; nb < 4; ++nb)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[nb][r] = misc[MISC_B0 + (nb * 16 + r) * 2 + h];
+        acc_from_bias(acc, misc, MISC_B0, h);
         mma_run<4, ST0, 20, A0G>(acc, A0, 0, lane, 0, pe);
         f32x16 h0[4];
 #pragma unroll
@@ -124,10 +80,7 @@ __global__ __launch_bounds__(512) void k_sdf_mlp(SdfArgs a) {
             }
 
         // ---- layer 1 ---------------------------------------------------------------------------------------------------
-#pragma unroll
-        for (int nb = 0; nb < 4; ++nb)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[nb][r] = misc[MISC_B1 + (nb * 16 + r) * 2 + h];
+        acc_from_bias(acc, misc, MISC_B1, h);
 #pragma unroll
         for (int kb = 0; kb < 4; ++kb) mma_block16<4, ST1, false>(acc, A1, lane, kb * 16, h0[kb]);
         mma_run<4, ST1, 8, false>(acc, A1, 0, lane, 64, lat);
@@ -149,10 +102,7 @@ __global__ __launch_bounds__(512) void k_sdf_mlp(SdfArgs a) {
             }
         // ---- output layer ------------------------------------------------------------------------------------------------
         if (VARIANT == VAR_FULL) {
-#pragma unroll
-            for (int nb = 0; nb < 4; ++nb)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[nb][r] = misc[MISC_B2 + (nb * 16 + r) * 2 + h];
+            acc_from_bias(acc, misc, MISC_B2, h);
 #pragma unroll
             for (int kb = 0; kb < 4; ++kb) mma_block16<4, ST1, false>(acc, A2, lane, kb * 16, h1[kb]);
             mma_run<4, ST1, 8, false>(acc, A2, 0, lane, 64, lat);
@@ -181,10 +131,7 @@ __global__ __launch_bounds__(512) void k_sdf_mlp(SdfArgs a) {
         // ---- backward: d sdf / d x ----------------------------------------------------------------------------------------
         if (VARIANT == VAR_GRAD) {
             f32x16 g[5];
-#pragma unroll
-            for (int nb = 0; nb < 5; ++nb)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) g[nb][r] = 0.f;
+            acc_zero(g);
 #pragma unroll
             for (int kb = 0; kb < 4; ++kb) mma_block16<5, STB, false>(g, A1T, lane, kb * 16, g1[kb]);
             // g[0..3] = d/d h0 (same lane layout as h0) ; g[4][0..7] = d/d latent channel 8h+t (through layer 1)
@@ -194,59 +141,20 @@ __global__ __launch_bounds__(512) void k_sdf_mlp(SdfArgs a) {
 #pragma unroll
             for (int nb = 0; nb < 4; ++nb) {
                 f32x16 a0r[1];
-#pragma unroll
-                for (int r = 0; r < 16; ++r) a0r[0][r] = misc[MISC_B0 + (nb * 16 + r) * 2 + h];
+                acc_from_bias(a0r, misc, MISC_B0 + nb * 32, h);
                 mma_run<1, ST0, 20, A0G>(a0r, A0, nb, lane, 0, pe);
 #pragma unroll
                 for (int r = 0; r < 16; ++r) g0[nb][r] = g[nb][r] * softplus100_d(a0r[0][r]);
             }
             f32x16 gp[2];
-#pragma unroll
-            for (int nb = 0; nb < 2; ++nb)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) gp[nb][r] = 0.f;
+            acc_zero(gp);
 #pragma unroll
             for (int kb = 0; kb < 4; ++kb) mma_block16<2, STB, true>(gp, A0T, lane, kb * 16, g0[kb]);
-            // gp[0][r] = d/d pe slot r (r<16), gp[1][0..3] = slots 16..19
-            float gx[3] = {0.f, 0.f, 0.f};
+            float gx[3], gl[8];
+            pe_chain_rule(gp, h, [&](int slot_) { return pe[slot_]; }, gx);
 #pragma unroll
-            for (int t = 0; t < 9; ++t) {
-                const int c = 9 * h + t;
-                const int d = t % 3;
-                const float f = (float)(1 << (c / 3));
-                const float gs = gp[0][t];                                  // d/d sin slot
-                const float gc = (9 + t < 16) ? gp[0][9 + t] : gp[1][9 + t - 16];
-                gx[d] += (gs * pe[9 + t] - gc * pe[t]) * f;                 // sin' = f cos ; cos' = -f sin
-            }
-            if (h) gx[2] += gp[1][2]; else { gx[0] += gp[1][2]; gx[1] += gp[1][3]; }
-            // latent path: the trilinear Jacobian is not kept across the network (24 registers): gather the 8 taps again
-            // (L2 hits) and contract d sdf / d latent with it on the fly
-            {
-                float gl[8];
-#pragma unroll
-                for (int t = 0; t < 8; ++t) gl[t] = g[4][t] + misc[MISC_W2L + 8 * h + t];
-                const Taps3D tp = trilinear_ref_taps(px, py, pz, a.D);
-                if (tp.ok && live) {
-                    const float half_span = (float)(a.D - 1) * 0.5f;
-#pragma unroll
-                    for (int dx = 0; dx < 2; ++dx)
-#pragma unroll
-                        for (int dy = 0; dy < 2; ++dy)
-#pragma unroll
-                            for (int dz = 0; dz < 2; ++dz) {
-                                const size_t vox = ((size_t)tp.ix[dx] * a.D + tp.iy[dy]) * a.D + tp.iz[dz];
-                                const float4* p4 = reinterpret_cast<const float4*>(a.vol_cl + vox * 16 + 8 * h);
-                                const float4 v0 = p4[0], v1 = p4[1];
-                                const float v[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
-                                float dv = 0.f;
-#pragma unroll
-                                for (int c = 0; c < 8; ++c) dv = fmaf(v[c], gl[c], dv);
-                                gx[0] = fmaf((dx ? half_span : -half_span) * tp.fy[dy] * tp.fz[dz], dv, gx[0]);
-                                gx[1] = fmaf((dy ? half_span : -half_span) * tp.fx[dx] * tp.fz[dz], dv, gx[1]);
-                                gx[2] = fmaf((dz ? half_span : -half_span) * tp.fx[dx] * tp.fy[dy], dv, gx[2]);
-                            }
-                }
-            }
+            for (int t = 0; t < 8; ++t) gl[t] = g[4][t] + misc[MISC_W2L + 8 * h + t];
+            latent_grad(a.vol_cl, a.D, px, py, pz, h, live, gl, gx);
 #pragma unroll
             for (int d = 0; d < 3; ++d) gx[d] += __shfl_xor(gx[d], 32);
             if (live && h == 0 && a.out_grad) {
@@ -285,27 +193,11 @@ int o2345_sdf_mlp_ex(int variant, const float* blob, const float* vol_cl, int D,
     O2345_REQUIRE(variant >= 0 && variant <= 2, "sdf_mlp: bad variant %d", variant);
     O2345_REQUIRE(variant != VAR_GRAD || out_grad, "sdf_mlp: gradient variant needs out_grad");
     if (n <= 0 && !n_dev) return 0;
-    SdfArgs a{blob, vol_cl, D, pts, index, n_dev, n, grid_R, sign, out_sdf, out_feat, out_lat, out_grad, lat_in};
-    hipStream_t s = (hipStream_t)stream;
-    const int n_cu = cu_count();
-    const int threads = 512;
-    const long long per_block = (threads / 64) * 32;
-    long long want = n_dev ? n_cu : (n + per_block - 1) / per_block;
-    const unsigned grid = persistent_grid(want, n_cu);
-    constexpr size_t N_A0 = 4 * ST0 * 64, N_A1 = 4 * ST1 * 64, N_A1T = 5 * STB * 64;
-    size_t lds_floats = (variant == VAR_SDF ? N_A0 + N_A1 : variant == VAR_FULL ? 2 * N_A1 : N_A1 + N_A1T) + MISC_SIZE;
-    size_t lds_bytes = lds_floats * sizeof(float);
-    if (variant == VAR_SDF) {
-        O2345_ENSURE_LDS(k_sdf_mlp<VAR_SDF>, lds_bytes);
-        hipLaunchKernelGGL(k_sdf_mlp<VAR_SDF>, dim3(grid), dim3(threads), lds_bytes, s, a);
-    } else if (variant == VAR_FULL) {
-        O2345_ENSURE_LDS(k_sdf_mlp<VAR_FULL>, lds_bytes);
-        hipLaunchKernelGGL(k_sdf_mlp<VAR_FULL>, dim3(grid), dim3(threads), lds_bytes, s, a);
-    } else {
-        O2345_ENSURE_LDS(k_sdf_mlp<VAR_GRAD>, lds_bytes);
-        hipLaunchKernelGGL(k_sdf_mlp<VAR_GRAD>, dim3(grid), dim3(threads), lds_bytes, s, a);
-    }
-    return check_launch("sdf_mlp");
+    const SdfArgs a{blob, vol_cl, D, pts, index, n_dev, n, grid_R, sign, out_sdf, out_feat, out_lat, out_grad, lat_in};
+#define O2345_SDF_VARIANT(V) sdf_launch<k_sdf_mlp<V>, sdf_lds_floats(V)>
+    static int (*const launch[3])(const char*, const SdfArgs&, void*) = {O2345_SDF_VARIANT(VAR_SDF), O2345_SDF_VARIANT(VAR_FULL), O2345_SDF_VARIANT(VAR_GRAD)};
+#undef O2345_SDF_VARIANT
+    return launch[variant]("sdf_mlp", a, stream);
 }
 
 }  // extern "C"

@@ -9,9 +9,6 @@
 
 namespace o2345 {
 
-// lo in the asm form (split_f16.h): k_sdf_grad_x3 falls below the 256-register line and loses its 224 bytes of scratch per lane, 11.9 -> 9.9 ms on 29.5 M points
-constexpr bool MIXLO = true;
-
 // acc[ob] += W[ob][step] * b for NB output blocks, split precision.  A: LDS, [NB][NST][hi|lo][64 lanes] float4.
 template <int NB, int NST, int B0 = 0, int B1 = NB>
 __device__ __forceinline__ void mma_x3_part(f32x16 (&acc)[NB], const float4* A, int lane, int step, const Split8& b) {
@@ -40,9 +37,8 @@ __device__ __forceinline__ void mma_x3(f32x16 (&acc)[NB], const float4* A, int l
 template <bool TAB>
 __global__ __launch_bounds__(512) void k_sdf_mlp_x3(SdfArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    constexpr int N_A0 = 4 * STX0 * 2 * 256, N_A1 = 4 * STH1 * 2 * 256;
-    constexpr int L_A0 = 0, L_A1 = N_A0, L_MISC = N_A0 + N_A1;
-    for (int i = threadIdx.x * 4; i < N_A0 + N_A1; i += blockDim.x * 4)           // the two sections are adjacent in the blob
+    constexpr int L_A0 = 0, L_A1 = NX_A0, L_MISC = NX_A0 + NX_A1;                 // LDSX_MLP_FLOATS (sdf_common.h)
+    for (int i = threadIdx.x * 4; i < L_MISC; i += blockDim.x * 4)                // the two sections are adjacent in the blob
         *reinterpret_cast<float4*>(lds + i) = *reinterpret_cast<const float4*>(a.blob + OFFX_A0 + i);
     for (int i = threadIdx.x; i < MISC_SIZE; i += blockDim.x) lds[L_MISC + i] = a.blob[OFFX_MISC + i];           // b0, b1 in the t domain
     __syncthreads();
@@ -56,49 +52,17 @@ __global__ __launch_bounds__(512) void k_sdf_mlp_x3(SdfArgs a) {
     const int wave = threadIdx.x >> 6, nwave = blockDim.x >> 6;
     const TileSched ts = tile_schedule(n, 32, wave, nwave);
     for (long long tile = ts.first; tile < ts.end; tile += ts.stride) {
-        const long long t0 = tile * 32;
-        const long long i = t0 + j;
+        const long long i = tile * 32 + j;
         const bool live = i < n;
-        long long slot = live ? (a.index ? (long long)a.index[i] : i) : 0;
-        float px, py, pz;
-        int ix = 0, iy = 0, iz = 0;
-        if (!TAB && a.pts) {
-            px = live ? a.pts[slot * 3 + 0] : 0.f; py = live ? a.pts[slot * 3 + 1] : 0.f; pz = live ? a.pts[slot * 3 + 2] : 0.f;
-        } else {
-            const int R = a.R;
-            const unsigned us = (unsigned)slot, uR = (unsigned)R;          // R^3 < 2^32: 32-bit divisions (the 64-bit ones cost 240 instructions)
-            const unsigned uq = us / uR;
-            iz = (int)(us - uq * uR); ix = (int)(uq / uR); iy = (int)(uq - (uq / uR) * uR);
-            px = lin11(ix, R); py = lin11(iy, R); pz = lin11(iz, R);
-        }
-        // ---- trilinear latent: this half's 8 channels (reference edge semantics) ---------------------------------------------
+        const TilePoint pt = sdf_tile_point(a, !TAB && a.pts, i, live);
+        const long long slot = pt.slot;
         float lat[8];
-#pragma unroll
-        for (int c = 0; c < 8; ++c) lat[c] = 0.f;
-        {
-            const Taps3D tp = trilinear_ref_taps(px, py, pz, a.D);
-            if (tp.ok && live) {
-#pragma unroll
-                for (int dx = 0; dx < 2; ++dx)
-#pragma unroll
-                    for (int dy = 0; dy < 2; ++dy)
-#pragma unroll
-                        for (int dz = 0; dz < 2; ++dz) {
-                            const size_t vox = ((size_t)tp.ix[dx] * a.D + tp.iy[dy]) * a.D + tp.iz[dz];
-                            const float4* p4 = reinterpret_cast<const float4*>(a.vol_cl + vox * 16 + 8 * h);
-                            const float4 v0 = p4[0], v1 = p4[1];
-                            const float v[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
-                            const float w = tp.fz[dz] * tp.fy[dy] * tp.fx[dx];
-#pragma unroll
-                            for (int c = 0; c < 8; ++c) lat[c] = fmaf(v[c], w, lat[c]);
-                        }
-            }
-        }
+        latent_gather(a.vol_cl, a.D, pt.px, pt.py, pt.pz, h, live, lat);
         f32x16 acc[4];
         if constexpr (TAB) {
             // ---- layer 0 from the tables ------------------------------------------------------------------------------------------------------
-            const float4* txy = reinterpret_cast<const float4*>(a.tab_xy + ((size_t)ix * a.R + iy) * 128 + 64 * h);
-            const float4* tz = reinterpret_cast<const float4*>(a.tab_z + (size_t)iz * 128 + 64 * h);
+            const float4* txy = reinterpret_cast<const float4*>(a.tab_xy + ((size_t)pt.ix * a.R + pt.iy) * 128 + 64 * h);
+            const float4* tz = reinterpret_cast<const float4*>(a.tab_z + (size_t)pt.iz * 128 + 64 * h);
 #pragma unroll
             for (int nb = 0; nb < 4; ++nb)
 #pragma unroll
@@ -107,44 +71,17 @@ __global__ __launch_bounds__(512) void k_sdf_mlp_x3(SdfArgs a) {
                     acc[nb][4 * q] = u.x + w.x; acc[nb][4 * q + 1] = u.y + w.y; acc[nb][4 * q + 2] = u.z + w.z; acc[nb][4 * q + 3] = u.w + w.w;
                 }
         } else {
-            // ---- positional encoding: this half's 20 slots (+4 zero pads to fill three k steps) -------------------------------------
+            // ---- layer 0 on the positional encoding (+4 zero pads to fill three k steps) ------------------------------------------------
             float pe[24];
-            const float p3[3] = {px, py, pz};
-#pragma unroll
-            for (int t = 0; t < 9; ++t) {
-                const int c = 9 * h + t;
-                const float f = (float)(1 << (c / 3));
-                float s, co;
-                sincos_pe(p3[t % 3] * f, s, co);
-                pe[t] = s; pe[9 + t] = co;
-            }
-            pe[18] = h ? pz : px;
-            pe[19] = h ? 0.f : py;
-            pe[20] = pe[21] = pe[22] = pe[23] = 0.f;
-            // ---- layer 0 -------------------------------------------------------------------------------------------------------------------
-#pragma unroll
-            for (int nb = 0; nb < 4; ++nb)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[nb][r] = misc[MISC_B0 + (nb * 16 + r) * 2 + h];
+            pe_half(pt.px, pt.py, pt.pz, h, pe);
+            acc_from_bias(acc, misc, MISC_B0, h);
 #pragma unroll
             for (int s = 0; s < STX0; ++s) mma_x3<4, STX0>(acc, A0, lane, s, split8<MIXLO>(pe, 8 * s, m1));
         }
         Split8 hb[8];                   // softplus(layer 0), split, as the 8 hidden k-step operands of layer 1
-#pragma unroll
-        for (int nb = 0; nb < 4; ++nb) {
-            float hv[16];
-#pragma unroll
-            for (int r = 0; r < 16; r += 2) {
-                const f32x2 sp = softplus_t_pair(f32x2{acc[nb][r], acc[nb][r + 1]});
-                hv[r] = sp[0]; hv[r + 1] = sp[1];
-            }
-            hb[2 * nb] = split8<MIXLO>(hv, 0, m1); hb[2 * nb + 1] = split8<MIXLO>(hv, 8, m1);
-        }
+        softplus_split(acc, hb, m1);
         // ---- layer 1 -------------------------------------------------------------------------------------------------------------------
-#pragma unroll
-        for (int nb = 0; nb < 4; ++nb)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[nb][r] = misc[MISC_B1 + (nb * 16 + r) * 2 + h];
+        acc_from_bias(acc, misc, MISC_B1, h);
 #pragma unroll
         for (int s = 0; s < 8; ++s) mma_x3<4, STH1>(acc, A1, lane, s, hb[s]);
         mma_x3<4, STH1>(acc, A1, lane, 8, split8<MIXLO>(lat, 0, m1));
@@ -193,8 +130,7 @@ __device__ __forceinline__ AReg<NB> a_fetch(__amdgpu_buffer_rsrc_t rs, int sec_o
 // d sdf / d latent on the fly.
 __global__ __launch_bounds__(512) void k_sdf_grad_x3(SdfArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    constexpr int N_A0 = 4 * STX0 * 2 * 256, N_A1 = 4 * STH1 * 2 * 256, N_A1T3 = 3 * STHB * 2 * 256;
-    constexpr int L_A0 = 0, L_A1 = N_A0, L_A1T = N_A0 + N_A1, L_MISC = N_A0 + N_A1 + N_A1T3;
+    constexpr int L_A0 = 0, L_A1 = NX_A0, L_A1T = NX_A0 + NX_A1, L_MISC = NX_A0 + NX_A1 + NX_A1T3;       // LDSX_GRAD_FLOATS (sdf_common.h)
     for (int i = threadIdx.x * 4; i < L_MISC; i += blockDim.x * 4)                // the three sections are adjacent in the blob
         *reinterpret_cast<float4*>(lds + i) = *reinterpret_cast<const float4*>(a.blob + OFFX_A0 + i);
     for (int i = threadIdx.x; i < MISC_SIZE; i += blockDim.x) lds[L_MISC + i] = a.blob[OFFX_MISC + i];           // b0, b1 in the t domain
@@ -217,44 +153,17 @@ __global__ __launch_bounds__(512) void k_sdf_grad_x3(SdfArgs a) {
     const long long iters = wave0_first < ts.end ? (ts.end - wave0_first + ts.stride - 1) / ts.stride : 0;
     for (long long it = 0; it < iters; ++it) {
         const long long tile = ts.first + it * ts.stride;
-        const long long t0 = tile * 32;
-        const long long i = t0 + j;
+        const long long i = tile * 32 + j;
         const bool live = tile < ts.end && i < n;
-        long long slot = live ? (a.index ? (long long)a.index[i] : i) : 0;
-        float px, py, pz;
-        if (a.pts) {
-            px = live ? a.pts[slot * 3 + 0] : 0.f; py = live ? a.pts[slot * 3 + 1] : 0.f; pz = live ? a.pts[slot * 3 + 2] : 0.f;
-        } else {
-            const int R = a.R;
-            const unsigned us = (unsigned)slot, uR = (unsigned)R;          // R^3 < 2^32: 32-bit divisions (the 64-bit ones cost 240 instructions)
-            const unsigned uq = us / uR;
-            const int iz = (int)(us - uq * uR), ix = (int)(uq / uR), iy = (int)(uq - (uq / uR) * uR);
-            px = lin11(ix, R); py = lin11(iy, R); pz = lin11(iz, R);
-        }
+        const TilePoint pt = sdf_tile_point(a, a.pts != nullptr, i, live);
+        const long long slot = pt.slot;
+        const float px = pt.px, py = pt.py, pz = pt.pz;
         // ---- trilinear latent (this half's 8 channels) ----------------------------------------------------------------------------
         Split8 latx;
         float ylat = 0.f;                       // latent part of the SDF output row
         {
             float lat[8];
-#pragma unroll
-            for (int c = 0; c < 8; ++c) lat[c] = 0.f;
-            const Taps3D tp = trilinear_ref_taps(px, py, pz, a.D);
-            if (tp.ok && live) {
-#pragma unroll
-                for (int dx = 0; dx < 2; ++dx)
-#pragma unroll
-                    for (int dy = 0; dy < 2; ++dy)
-#pragma unroll
-                        for (int dz = 0; dz < 2; ++dz) {
-                            const size_t vox = ((size_t)tp.ix[dx] * a.D + tp.iy[dy]) * a.D + tp.iz[dz];
-                            const float4* p4 = reinterpret_cast<const float4*>(a.vol_cl + vox * 16 + 8 * h);
-                            const float4 v0 = p4[0], v1 = p4[1];
-                            const float v[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
-                            const float w = tp.fz[dz] * tp.fy[dy] * tp.fx[dx];
-#pragma unroll
-                            for (int c = 0; c < 8; ++c) lat[c] = fmaf(v[c], w, lat[c]);
-                        }
-            }
+            latent_gather(a.vol_cl, a.D, px, py, pz, h, live, lat);
 #pragma unroll
             for (int t = 0; t < 8; ++t) ylat += misc[MISC_W2L + 8 * h + t] * lat[t];
             latx = split8<MIXLO>(lat, 0, m1);
@@ -263,18 +172,7 @@ __global__ __launch_bounds__(512) void k_sdf_grad_x3(SdfArgs a) {
         Split8 pex[STX0];
         {
             float pe[24];
-            const float p3[3] = {px, py, pz};
-#pragma unroll
-            for (int t = 0; t < 9; ++t) {
-                const int c = 9 * h + t;
-                const float f = (float)(1 << (c / 3));
-                float s, co;
-                sincos_pe(p3[t % 3] * f, s, co);
-                pe[t] = s; pe[9 + t] = co;
-            }
-            pe[18] = h ? pz : px;
-            pe[19] = h ? 0.f : py;
-            pe[20] = pe[21] = pe[22] = pe[23] = 0.f;
+            pe_half(px, py, pz, h, pe);
 #pragma unroll
             for (int s = 0; s < STX0; ++s) pex[s] = split8<MIXLO>(pe, 8 * s, m1);
         }
@@ -283,49 +181,19 @@ __global__ __launch_bounds__(512) void k_sdf_grad_x3(SdfArgs a) {
         auto pe_at = [&](int idx) { return (float)pex[idx >> 3].hi[idx & 7] + (float)pex[idx >> 3].lo[idx & 7]; };
         // ---- layer 0 ------------------------------------------------------------------------------------------------------------------------
         f32x16 acc[4];
-#pragma unroll
-        for (int nb = 0; nb < 4; ++nb)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[nb][r] = misc[MISC_B0 + (nb * 16 + r) * 2 + h];
+        acc_from_bias(acc, misc, MISC_B0, h);
 #pragma unroll
         for (int s = 0; s < STX0; ++s) mma_x3<4, STX0>(acc, A0, lane, s, pex[s]);
         Split8 hb[8];
-#pragma unroll
-        for (int nb = 0; nb < 4; ++nb) {
-            float hv[16];
-#pragma unroll
-            for (int r = 0; r < 16; r += 2) {
-                const f32x2 sp = softplus_t_pair(f32x2{acc[nb][r], acc[nb][r + 1]});
-                hv[r] = sp[0]; hv[r + 1] = sp[1];
-            }
-            hb[2 * nb] = split8<MIXLO>(hv, 0, m1); hb[2 * nb + 1] = split8<MIXLO>(hv, 8, m1);
-        }
+        softplus_split(acc, hb, m1);
         // ---- layer 1 ------------------------------------------------------------------------------------------------------------------------
-#pragma unroll
-        for (int nb = 0; nb < 4; ++nb)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[nb][r] = misc[MISC_B1 + (nb * 16 + r) * 2 + h];
+        acc_from_bias(acc, misc, MISC_B1, h);
 #pragma unroll
         for (int s = 0; s < 8; ++s) mma_x3<4, STH1>(acc, A1, lane, s, hb[s]);
         mma_x3<4, STH1>(acc, A1, lane, 8, latx);
         AReg<2> tcur = a_fetch<2, STHB>(rs, OFFX_A1T, lane, 3, 0);             // first streamed operands of the backward pass
         Split8 g1x[8];                  // d sdf / d a1 = w2row * softplus'(a1), split, as the backward k-step operands
-        // (t domain, weights.py SOFTPLUS_SCALE: d sdf / d a1 = w2row * softplus'(a1) stays in the a domain -- the backward operands are the unscaled ones --
-        // and the SDF row's hidden sum over s' = softplus * 100 / ln 2 loses the factor once per point)
-        float yh = 0.f;
-#pragma unroll
-        for (int nb = 0; nb < 4; ++nb) {
-            float gv[16];
-#pragma unroll
-            for (int r = 0; r < 16; r += 2) {
-                f32x2 d;
-                const f32x2 v = softplus_t_pair(f32x2{acc[nb][r], acc[nb][r + 1]}, d);
-                const float w2a = misc[MISC_W2H + (nb * 16 + r) * 2 + h], w2b = misc[MISC_W2H + (nb * 16 + r + 1) * 2 + h];
-                yh = fmaf(w2a, v[0], yh); yh = fmaf(w2b, v[1], yh);
-                gv[r] = w2a * d[0]; gv[r + 1] = w2b * d[1];
-            }
-            g1x[2 * nb] = split8<MIXLO>(gv, 0, m1); g1x[2 * nb + 1] = split8<MIXLO>(gv, 8, m1);
-        }
+        const float yh = softplus_split_grad(acc, misc, h, g1x, m1);
         float y0 = fmaf(yh, SOFTPLUS_INV_SCALE, ylat);
         y0 += __shfl_xor(y0, 32);
         y0 += misc[MISC_B2];
@@ -333,10 +201,7 @@ __global__ __launch_bounds__(512) void k_sdf_grad_x3(SdfArgs a) {
         __syncthreads();                    // align the waves for the streamed phase (see the loop head)
         // ---- backward through layer 1: g[0..3] = d/d h0 (lane layout of h0), g[4][0..7] = d/d latent channel 8h+t ------------------
         f32x16 g[5];
-#pragma unroll
-        for (int nb = 0; nb < 5; ++nb)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) g[nb][r] = 0.f;
+        acc_zero(g);
 #pragma unroll
         for (int s = 0; s < 8; ++s) {
             // streamed blocks first, then their registers are refilled for the next step while the LDS blocks run (single buffer)
@@ -347,17 +212,13 @@ __global__ __launch_bounds__(512) void k_sdf_grad_x3(SdfArgs a) {
         }
         // ---- backward through layer 0: softplus'(a0) from a block-by-block re-evaluation; transposed operands streamed -------------
         f32x16 gp[2];
-#pragma unroll
-        for (int nb = 0; nb < 2; ++nb)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) gp[nb][r] = 0.f;
+        acc_zero(gp);
 #pragma unroll
         for (int nb = 0; nb < 4; ++nb) {
             const AReg<2> ta = a_fetch<2, STHB>(rs, OFFX_A0T, lane, 0, 2 * nb);
             __builtin_amdgcn_sched_barrier(0);
             f32x16 a0r[1];
-#pragma unroll
-            for (int r = 0; r < 16; ++r) a0r[0][r] = misc[MISC_B0 + (nb * 16 + r) * 2 + h];
+            acc_from_bias(a0r, misc, MISC_B0 + nb * 32, h);
 #pragma unroll
             for (int s = 0; s < STX0; ++s) mma_x3_part<1, STX0, 0, 1>(a0r, A0 + nb * STX0 * 2 * 64, lane, s, pex[s]);
             const AReg<2> tb = a_fetch<2, STHB>(rs, OFFX_A0T, lane, 0, 2 * nb + 1);     // covered by the softplus' block and ta's MFMAs
@@ -369,44 +230,12 @@ __global__ __launch_bounds__(512) void k_sdf_grad_x3(SdfArgs a) {
             mfma_x3<2>(gp, tb.hi, tb.lo, split8<MIXLO>(gv, 8, m1));
             __builtin_amdgcn_sched_barrier(0);
         }
-        float gx[3] = {0.f, 0.f, 0.f};
+        // ---- chain rule through the encoding, then the latent path -----------------------------------------------------------------------
+        float gx[3], gl[8];
+        pe_chain_rule(gp, h, pe_at, gx);
 #pragma unroll
-        for (int t = 0; t < 9; ++t) {
-            const int c = 9 * h + t;
-            const int d = t % 3;
-            const float f = (float)(1 << (c / 3));
-            const float gs = gp[0][t];
-            const float gc = (9 + t < 16) ? gp[0][9 + t] : gp[1][9 + t - 16];
-            gx[d] += (gs * pe_at(9 + t) - gc * pe_at(t)) * f;           // sin' = f cos ; cos' = -f sin
-        }
-        if (h) gx[2] += gp[1][2]; else { gx[0] += gp[1][2]; gx[1] += gp[1][3]; }
-        // ---- latent path: gather the 8 taps again and contract d sdf / d latent with the trilinear Jacobian -----------------------------
-        {
-            float gl[8];
-#pragma unroll
-            for (int t = 0; t < 8; ++t) gl[t] = g[4][t] + misc[MISC_W2L + 8 * h + t];
-            const Taps3D tp = trilinear_ref_taps(px, py, pz, a.D);
-            if (tp.ok && live) {
-                const float half_span = (float)(a.D - 1) * 0.5f;
-#pragma unroll
-                for (int dx = 0; dx < 2; ++dx)
-#pragma unroll
-                    for (int dy = 0; dy < 2; ++dy)
-#pragma unroll
-                        for (int dz = 0; dz < 2; ++dz) {
-                            const size_t vox = ((size_t)tp.ix[dx] * a.D + tp.iy[dy]) * a.D + tp.iz[dz];
-                            const float4* p4 = reinterpret_cast<const float4*>(a.vol_cl + vox * 16 + 8 * h);
-                            const float4 v0 = p4[0], v1 = p4[1];
-                            const float v[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
-                            float dv = 0.f;
-#pragma unroll
-                            for (int c = 0; c < 8; ++c) dv = fmaf(v[c], gl[c], dv);
-                            gx[0] = fmaf((dx ? half_span : -half_span) * tp.fy[dy] * tp.fz[dz], dv, gx[0]);
-                            gx[1] = fmaf((dy ? half_span : -half_span) * tp.fx[dx] * tp.fz[dz], dv, gx[1]);
-                            gx[2] = fmaf((dz ? half_span : -half_span) * tp.fx[dx] * tp.fy[dy], dv, gx[2]);
-                        }
-            }
-        }
+        for (int t = 0; t < 8; ++t) gl[t] = g[4][t] + misc[MISC_W2L + 8 * h + t];
+        latent_grad(a.vol_cl, a.D, px, py, pz, h, live, gl, gx);
 #pragma unroll
         for (int d = 0; d < 3; ++d) gx[d] += __shfl_xor(gx[d], 32);
         if (live && h == 0 && a.out_grad) {
@@ -421,40 +250,28 @@ using namespace o2345;
 
 extern "C" {
 
+// argument check shared by the three split-f16 entry points
+static int sdf_x3_check(const char* what, bool pointers, int D, bool has_pts, int grid_R) {
+    O2345_REQUIRE(pointers, "%s: null pointer", what);
+    O2345_REQUIRE(D >= 2, "%s: bad volume side %d", what, D);
+    O2345_REQUIRE(has_pts || (grid_R >= 2 && grid_R <= 1600), "%s: need points or a grid resolution in [2, 1600]", what);
+    return 0;
+}
+
 int o2345_sdf_grad_x3(const float* blob, const float* vol_cl, int D, const float* pts, const int32_t* index, const int32_t* n_dev,
                       long long n, int grid_R, float sign, float* out_sdf, float* out_grad, void* stream) {
-    O2345_REQUIRE(blob && vol_cl && out_sdf && out_grad, "sdf_grad_x3: null pointer");
-    O2345_REQUIRE(D >= 2, "sdf_grad_x3: bad volume side %d", D);
-    O2345_REQUIRE(pts || (grid_R >= 2 && grid_R <= 1600), "sdf_grad_x3: need points or a grid resolution in [2, 1600]");
+    if (const int rc = sdf_x3_check("sdf_grad_x3", blob && vol_cl && out_sdf && out_grad, D, pts, grid_R)) return rc;
     if (n <= 0 && !n_dev) return 0;
-    SdfArgs a{blob, vol_cl, D, pts, index, n_dev, n, grid_R, sign, out_sdf, nullptr, nullptr, out_grad, nullptr};
-    const int n_cu = cu_count();
-    const int threads = 512;
-    const long long per_block = (threads / 64) * 32;
-    long long want = n_dev ? n_cu : (n + per_block - 1) / per_block;
-    const unsigned grid = persistent_grid(want, n_cu);
-    const size_t lds_bytes = (size_t)(4 * STX0 * 2 * 256 + 4 * STH1 * 2 * 256 + 3 * STHB * 2 * 256 + MISC_SIZE) * sizeof(float);
-    O2345_ENSURE_LDS(k_sdf_grad_x3, lds_bytes);
-    hipLaunchKernelGGL(k_sdf_grad_x3, dim3(grid), dim3(threads), lds_bytes, (hipStream_t)stream, a);
-    return check_launch("sdf_grad_x3");
+    const SdfArgs a{blob, vol_cl, D, pts, index, n_dev, n, grid_R, sign, out_sdf, nullptr, nullptr, out_grad, nullptr};
+    return sdf_launch<k_sdf_grad_x3, LDSX_GRAD_FLOATS>("sdf_grad_x3", a, stream);
 }
 
 int o2345_sdf_mlp_x3(const float* blob, const float* vol_cl, int D, const float* pts, const int32_t* index, const int32_t* n_dev,
                      long long n, int grid_R, float sign, float* out_sdf, void* stream) {
-    O2345_REQUIRE(blob && vol_cl && out_sdf, "sdf_mlp_x3: null pointer");
-    O2345_REQUIRE(D >= 2, "sdf_mlp_x3: bad volume side %d", D);
-    O2345_REQUIRE(pts || (grid_R >= 2 && grid_R <= 1600), "sdf_mlp_x3: need points or a grid resolution in [2, 1600]");
+    if (const int rc = sdf_x3_check("sdf_mlp_x3", blob && vol_cl && out_sdf, D, pts, grid_R)) return rc;
     if (n <= 0 && !n_dev) return 0;
-    SdfArgs a{blob, vol_cl, D, pts, index, n_dev, n, grid_R, sign, out_sdf, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    const int n_cu = cu_count();
-    const int threads = 512;
-    const long long per_block = (threads / 64) * 32;
-    long long want = n_dev ? n_cu : (n + per_block - 1) / per_block;
-    const unsigned grid = persistent_grid(want, n_cu);
-    const size_t lds_bytes = (size_t)(4 * STX0 * 2 * 256 + 4 * STH1 * 2 * 256 + MISC_SIZE) * sizeof(float);
-    O2345_ENSURE_LDS(k_sdf_mlp_x3<false>, lds_bytes);
-    hipLaunchKernelGGL(k_sdf_mlp_x3<false>, dim3(grid), dim3(threads), lds_bytes, (hipStream_t)stream, a);
-    return check_launch("sdf_mlp_x3");
+    const SdfArgs a{blob, vol_cl, D, pts, index, n_dev, n, grid_R, sign, out_sdf, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    return sdf_launch<k_sdf_mlp_x3<false>, LDSX_MLP_FLOATS>("sdf_mlp_x3", a, stream);
 }
 
 // tab_xy[(ix * R + iy)][c] = tab_axes[0][ix][c] + tab_axes[1][iy][c] + bias[c]   (c = 128 lane-ordered columns; summed in doubles)
@@ -474,18 +291,10 @@ int o2345_sdf_grid_tables(const float* tab_axes, const float* bias_lane_order, i
 // x-major lattice linspace(-1,1,R)^3.  tab_xy [R*R,128] from o2345_sdf_grid_tables, tab_z [R,128] = the z table (tab_axes + 2*R*128).
 int o2345_sdf_grid_x3(const float* blob, const float* vol_cl, int D, int grid_R, float sign, const float* tab_xy, const float* tab_z, float* out_sdf,
                       void* stream) {
-    O2345_REQUIRE(blob && vol_cl && out_sdf && tab_xy && tab_z, "sdf_grid_x3: null pointer");
-    O2345_REQUIRE(D >= 2 && grid_R >= 2 && grid_R <= 1600, "sdf_grid_x3: bad sizes");
+    if (const int rc = sdf_x3_check("sdf_grid_x3", blob && vol_cl && out_sdf && tab_xy && tab_z, D, false, grid_R)) return rc;
     const long long n = (long long)grid_R * grid_R * grid_R;
-    SdfArgs a{blob, vol_cl, D, nullptr, nullptr, nullptr, n, grid_R, sign, out_sdf, nullptr, nullptr, nullptr, nullptr, tab_xy, tab_z};
-    const int n_cu = cu_count();
-    const int threads = 512;
-    const long long per_block = (threads / 64) * 32;
-    const unsigned grid = persistent_grid((n + per_block - 1) / per_block, n_cu);
-    const size_t lds_bytes = (size_t)(4 * STX0 * 2 * 256 + 4 * STH1 * 2 * 256 + MISC_SIZE) * sizeof(float);
-    O2345_ENSURE_LDS(k_sdf_mlp_x3<true>, lds_bytes);
-    hipLaunchKernelGGL(k_sdf_mlp_x3<true>, dim3(grid), dim3(threads), lds_bytes, (hipStream_t)stream, a);
-    return check_launch("sdf_grid_x3");
+    const SdfArgs a{blob, vol_cl, D, nullptr, nullptr, nullptr, n, grid_R, sign, out_sdf, nullptr, nullptr, nullptr, nullptr, tab_xy, tab_z};
+    return sdf_launch<k_sdf_mlp_x3<true>, LDSX_MLP_FLOATS>("sdf_grid_x3", a, stream);
 }
 
 }  // extern "C"

@@ -124,7 +124,7 @@ def packed_sdf_grid_tables(W, R):
     return both[:3 * int(R) * 128].reshape(3, int(R), 128), both[3 * int(R) * 128:]
 
 
-# ---- geometry of the SDF blob: keep in sync with csrc/sdf_mlp.hip -----------------------------------------------------
+# ---- geometry of the SDF blob: keep in sync with csrc/sdf_common.h ---------------------------------------------------
 ST0, ST1, STB = 20, 72, 64
 OFF_A0 = 0
 OFF_A1 = OFF_A0 + 4 * ST0 * 64
@@ -134,23 +134,17 @@ OFF_A0T = OFF_A1T + 5 * STB * 64
 OFF_MISC = OFF_A0T + 2 * STB * 64
 MISC_B0, MISC_B1, MISC_B2, MISC_W2H, MISC_W2L, MISC_SIZE = 0, 128, 256, 384, 512, 528
 SDF_F32_FLOATS = OFF_MISC + MISC_SIZE
-# reserved: former bf16 copies of the wide-layer operands ([block][k-step of 16][64 lanes][8 bf16 = 4 floats]); the offsets of the split-f16 sections depend on it.
-# Its first MISC_SIZE floats hold the split-f16 kernels' own MISC block (OFFX_MISC): the same rows with b0 and b1 in the SOFTPLUS_SCALE domain (below).
-STH1, STHB = 9, 8
-OFFH_A1 = SDF_F32_FLOATS
-OFFX_MISC = OFFH_A1
+# the split-f16 kernels' own MISC block: the same rows with b0 and b1 in the SOFTPLUS_SCALE domain (below)
+OFFX_MISC = SDF_F32_FLOATS
 # Softplus(beta = 100) on the hardware exp2 / log2 units is  softplus(a) = (ln 2 / 100) (max(t, 0) + log2(1 + 2^-|t|)),  t = a * 100 / ln 2.  The split-f16
 # kernels keep every pre-activation in the t domain and every hidden activation as s' = softplus(a) * 100 / ln 2: the factor is folded into the packed
 # operands in float64 before they are rounded -- layer 0's weights and bias and layer 1's LATENT columns and bias carry 100 / ln 2, layer 1's hidden
 # columns nothing (the factors of s' and of t cancel), the SDF row's hidden part is summed unscaled and multiplied by ln 2 / 100 once per point.  One
 # multiply less per softplus (5 instead of 6 instructions; 256 softplus per point), no multiply-add at its end.  The backward operands are unchanged.
 SOFTPLUS_SCALE = 100.0 / np.log(2.0)
-OFFH_A1T = OFFH_A1 + 4 * STH1 * 64 * 4
-OFFH_A0T = OFFH_A1T + 5 * STHB * 64 * 4
-SDF_BF16_END = OFFH_A0T + 2 * STHB * 64 * 4
 # split-f16 ("f16x3") copies (csrc/sdf_mlp_x3.hip): [block][k-step of 16][hi|lo][64 lanes][8 f16 = 4 floats]
-STX0 = 3
-OFFX_A0 = SDF_BF16_END
+STX0, STH1, STHB = 3, 9, 8           # k steps of 16: layer 0 (2 x 20 PE slots padded to 2 x 24), layer 1 (8 hidden + 1 latent), backward (128 upstream neurons)
+OFFX_A0 = OFFX_MISC + MISC_SIZE
 OFFX_A1 = OFFX_A0 + 4 * STX0 * 2 * 256
 OFFX_A1T = OFFX_A1 + 4 * STH1 * 2 * 256
 OFFX_A0T = OFFX_A1T + 5 * STHB * 2 * 256
@@ -309,7 +303,6 @@ def pack_sdf_blob(W):
             for ob in range(2):
                 cols = np.array([pe_index(int(ob * 16 + r), int(h)) if ob * 16 + r < 20 else -1 for r, h in zip(r_row, h_row)])
                 F_A0T[ob, st, :, t] = np.where(cols >= 0, w0[n, np.maximum(cols, 0)], 0.0)
-    # floats OFFH_A1 .. SDF_BF16_END are reserved (they held the bf16 operand copies of the removed bf16 mode; the split-f16 sections keep their offsets)
     for off, F in ((OFFX_A0, F_A0), (OFFX_A1, F_A1), (OFFX_A1T, F_A1T), (OFFX_A0T, F_A0T)):
         hi, lo = f16_split(F)
         sec = blob[off:off + F.size].view(np.float16).reshape(F.shape[0], F.shape[1], 2, 64, 8)

@@ -356,9 +356,11 @@ def test_sdf_mlp(dev, ops, n):
 
 
 
-@pytest.mark.parametrize("n", [31, 20011])
+@pytest.mark.parametrize("n", [1, 31, 257, 20011])
 def test_sdf_mlp_x3(dev, ops, n):
-    """Split-f16 ("f16x3") forward kernel: same tolerance as the exact fp32 MFMA kernel (default `close`), and within 2e-6 of it."""
+    """Split-f16 ("f16x3") forward kernel: same tolerance as the exact fp32 MFMA kernel (default `close`), and within 2e-6 of it.  n = 1: one live
+    lane; n = 257: two workgroups, the second with one wave on a tile and seven on the empty iteration that the gradient kernel's workgroup barrier
+    needs."""
     s = small_scene()
     d = dev_scene(s, dev, ops)
     W = sdfW_t(s["sdfW"])
@@ -394,6 +396,24 @@ def test_sdf_mlp_x3_large_activations(dev, ops):
     assert scale > 5.0                                                   # the scaling did reach the network
     assert float((a["sdf"] - b["sdf"]).abs().max()) <= 2e-5 * scale
     assert float((a["grad"] - b["grad"]).abs().max()) <= 1e-4 * float(b["grad"].abs().max())
+
+
+@pytest.mark.parametrize("prec,variant", [("fp32", 0), ("fp32", 1), ("fp32", 2), ("f16x3", 0), ("f16x3", 2)])
+def test_sdf_lattice_equals_explicit_points(dev, ops, prec, variant):
+    """The lattice mode (points decoded from the slot, csrc/sdf_common.h sdf_tile_point) against the same kernel given the lattice as explicit
+    points: every output bit for bit.  The points come from the CPU's linspace, which the kernels' lin11 reproduces exactly."""
+    s = small_scene()
+    d = dev_scene(s, dev, ops)
+    R = 9
+    lin = torch.linspace(-1, 1, R)
+    pts = torch.stack(torch.meshgrid(lin, lin, lin, indexing="ij"), -1).reshape(-1, 3).contiguous()
+    a = ops.sdf_mlp(d["sdf_blob"], d["vol_cl"], None, variant=variant, grid_R=R, precision=prec)
+    b = ops.sdf_mlp(d["sdf_blob"], d["vol_cl"], pts.to(dev), variant=variant, precision=prec)
+    assert set(a) == set(b) == [{"sdf"}, {"sdf", "feat"}, {"sdf", "grad"}][variant]
+    for k in a:
+        assert a[k].shape == b[k].shape and a[k].shape[0] == R ** 3
+        assert torch.equal(a[k].view(torch.int32), b[k].view(torch.int32)), (k, float((a[k] - b[k]).abs().max()))
+    assert bool(torch.isfinite(a["sdf"]).all()) and float(a["sdf"].abs().max()) > 0.0
 
 
 def test_sdf_mlp_indexed_and_grid(dev, ops):
