@@ -33,26 +33,50 @@ O2345_HD float mask_at(const float* __restrict__ maskvol, int D, float x, float 
     return v < 0 ? 0.f : maskvol[v];
 }
 
+// occupancy of the sample point at depth z of ray r: nearest voxel of the mask volume
+O2345_HD bool point_in_mask(const RayGeom& g, int r, float z, const float* __restrict__ maskvol, int D) {
+    float x, y, w;
+    ray_point(g, r, z, x, y, w);
+    return mask_at(maskvol, D, x, y, w) > 0.f;
+}
+
 // ---- per-ray list accessors ----------------------------------------------------------------------------------------------------------------
 // The sampler math below is written ONCE, against an accessor: rows of ONE ray's sorted lists (depth z, SDF, point-inside-mask flag), a scratch
-// row for the section weights, and a sink for the new depths.  Two accessors exist: GlobalRay (the sample-major global arrays, a[s * R + r]: the
-// host-check build and the definition of the semantics) and LdsRay (csrc/render.hip: the lists of 64 rays staged in LDS, a[s * 64 + lane]: every
-// access of the serial per-ray chains costs an LDS round trip instead of a dependent trip to L2 / HBM).
+// row for the section weights, and a sink for the new depths.  GlobalRay is the accessor on the sample-major global arrays, a[s * R + r]: the
+// streaming kernel, the host-check build and the definition of the semantics.  The occupancy flag (0 / 1) comes from the byte list m_ that travels
+// with the lists, or, without one (m_ null: the stage entry, the host-check build), from the mask volume.
 struct GlobalRay {
-    RayGeom g; int r; size_t R;
-    const float* z_; const float* sdf_; float* w_; float* out_;
-    const float* maskvol; int D;
+    const float* z_; const float* sdf_; const uint8_t* m_; float* w_; float* out_;
+    size_t R; int r; RayGeom g; const float* maskvol; int D;
     O2345_HD float z(int s) const { return z_[(size_t)s * R + r]; }
     O2345_HD float sdf(int s) const { return sdf_[(size_t)s * R + r]; }
-    O2345_HD float msk(int s, float zs) const {            // occupancy of the sample point (nearest voxel of the mask volume)
-        float x, y, w;
-        ray_point(g, r, zs, x, y, w);
-        return mask_at(maskvol, D, x, y, w);
+    O2345_HD float msk(int s, float zs) const {
+        if (m_) return (float)m_[(size_t)s * R + r];
+        return point_in_mask(g, r, zs, maskvol, D) ? 1.f : 0.f;
     }
     O2345_HD void set_w(int s, float v) { w_[(size_t)s * R + r] = v; }
     O2345_HD float w(int s) const { return w_[(size_t)s * R + r]; }
     O2345_HD void out(int t, float v) { out_[(size_t)t * R + r] = v; }
 };
+
+// One step of the transmittance chain every serial scan of the sampler runs: the weight w = alpha * T of a section / sample with opacity alpha, and
+// T <- T * (1 - alpha + 1e-7) for the next one.
+O2345_HD float transmit_step(float& T, float alpha) {
+    const float w = alpha * T;
+    T = T * (1.f - alpha + 1e-7f);
+    return w;
+}
+
+// sample_pdf(det = True): u_t of the new sample t, and its depth once the walk / search has found the first k with cdf[k] > u_t (or k = S: `last`):
+// linear in u between c_lo = cdf[k - 1] at zlo = z[k - 1] and c_hi = cdf[k] at zhi = z[min(k, S - 1)] (render_utils.py:36-50).
+O2345_HD float upsample_u(int n_imp, int t) { return linspace_at(0.5f / (float)n_imp, 1.f - 0.5f / (float)n_imp, n_imp, t); }
+O2345_HD float inverse_cdf_z(float u, float c_lo, float c_hi, bool last, float zlo, float zhi) {
+    const float ca = last ? c_lo : c_hi;                      // above == below only when k == S
+    float den = ca - c_lo;
+    if (den < 1e-5f) den = 1.f;
+    const float tt = (u - c_lo) / den;
+    return zlo + tt * (zhi - zlo);
+}
 
 // One section [s, s + 1] of up_sample (:89-107): the opacity alpha_s from the two samples' depth / SDF / occupancy and the slope of the PREVIOUS
 // section (prev_dot; 0 for the first).  dot_raw_out = this section's slope (the next section's prev_dot).  Independent of the running transmittance.
@@ -71,7 +95,7 @@ O2345_HD float upsample_section_alpha(float z0, float s0, float m0, float z1, fl
 
 // up_sample + sample_pdf(det=True): from S sorted samples (z, sdf) of one ray produce n_imp new z values (a.out(t, z_new), t < n_imp).
 // STREAMING form: both passes touch the lists at statically known, ascending rows, a block of CB rows is requested before any of it is used -- with
-// the global-memory accessor every block is ONE round trip with 3 x CB loads in flight (round 3 paid a dependent trip per sample), and no pass indexes
+// the global-memory accessor every block is ONE round trip with 3 x CB loads in flight (instead of a dependent trip per sample), and no pass indexes
 // a list at a data-dependent position.  The arithmetic, operation by operation and in the same order, is the reference's:
 //   pass 1 (:84-107)  section weights w_s = alpha_s * T_s + 1e-5 with the running transmittance T, and their sum;
 //   pass 2 (render_utils.py:24-50)  cdf_k = cdf_{k-1} + w_{k-1} / sum; for the ascending u_t the search index k only moves forward, so the inverse
@@ -98,8 +122,7 @@ O2345_HD void upsample_core(A& a, int S, float inv_s, int n_imp) {
                 float dot_raw;
                 const float alpha = upsample_section_alpha(z0, s0, m0, z1, s1, m1, prev_dot, inv_s, dot_raw);
                 prev_dot = dot_raw;
-                const float w = alpha * T + 1e-5f;            // sample_pdf: weights + 1e-5
-                T = T * (1.f - alpha + 1e-7f);
+                const float w = transmit_step(T, alpha) + 1e-5f;            // sample_pdf: weights + 1e-5
                 a.set_w(sb + k, w);
                 wsum += w;
                 z0 = z1; s0 = s1; m0 = m1;
@@ -110,7 +133,7 @@ O2345_HD void upsample_core(A& a, int S, float inv_s, int n_imp) {
     // sample is emitted at some k >= 1 with below = k - 1, above = min(k, S - 1).
     int t = 0;
     float c_lo = 0.f, c_hi = 0.f;
-    float u = linspace_at(0.5f / (float)n_imp, 1.f - 0.5f / (float)n_imp, n_imp, 0);
+    float u = upsample_u(n_imp, 0);
     float zlo = a.z(0);                                       // z[k - 1]
     for (int kb = 1; kb <= S && t < n_imp; kb += CB) {
         float wb[CB], zb[CB];
@@ -128,14 +151,9 @@ O2345_HD void upsample_core(A& a, int S, float inv_s, int n_imp) {
                 if (k < S) c_hi = c_hi + wb[j] / wsum;
                 const float zhi = zb[j];
                 while (t < n_imp && (k == S || c_hi > u)) {
-                    const float cb = c_lo;
-                    const float ca = (k == S) ? cb : c_hi;                     // above == below only when k == S
-                    float den = ca - cb;
-                    if (den < 1e-5f) den = 1.f;
-                    const float tt = (u - cb) / den;
-                    a.out(t, zlo + tt * (zhi - zlo));
+                    a.out(t, inverse_cdf_z(u, c_lo, c_hi, k == S, zlo, zhi));
                     ++t;
-                    u = linspace_at(0.5f / (float)n_imp, 1.f - 0.5f / (float)n_imp, n_imp, t < n_imp ? t : n_imp - 1);
+                    u = upsample_u(n_imp, t < n_imp ? t : n_imp - 1);
                 }
                 zlo = zhi;
             }
@@ -147,7 +165,7 @@ O2345_HD void upsample_core(A& a, int S, float inv_s, int n_imp) {
 O2345_HD void upsample_ray(const RayGeom& g, int r, const float* __restrict__ z, const float* __restrict__ sdf, int S,
                            float inv_s, const float* __restrict__ maskvol, int D, float* __restrict__ wbuf,
                            int n_imp, float* __restrict__ new_z) {
-    GlobalRay a{g, r, (size_t)g.R, z, sdf, wbuf, new_z, maskvol, D};
+    GlobalRay a{z, sdf, nullptr, wbuf, new_z, (size_t)g.R, r, g, maskvol, D};
     upsample_core(a, S, inv_s, n_imp);
 }
 
@@ -259,12 +277,16 @@ O2345_HD void merge_core_fixed(A& a, int S, float (&nz)[N], float (&ns)[N], unsi
 
 // cat_z_vals on the global sample-major arrays: merge n_new samples (new_z/new_sdf [n_new][R]) into the sorted list (z/sdf [S][R]) in place
 // (capacity S + n_new).  Equal keys keep existing samples first.  (The new block is also left sorted in new_z / new_sdf, as before.)
-struct GlobalMerge {
-    float* z_; float* sdf_; size_t R; int r;
+// tag: one byte per sample that moves with it (the occupancy flag), in the list m_ -- or nowhere (m_ null).
+struct GlobalMergeTag {
+    float* z_; float* sdf_; uint8_t* m_; size_t R; int r;
     O2345_HD float z(int i) const { return z_[(size_t)i * R + r]; }
     O2345_HD float sdf(int i) const { return sdf_[(size_t)i * R + r]; }
-    O2345_HD unsigned tag(int) const { return 0u; }
-    O2345_HD void put(int i, float zv, float sv, unsigned) { z_[(size_t)i * R + r] = zv; sdf_[(size_t)i * R + r] = sv; }
+    O2345_HD unsigned tag(int i) const { return m_ ? m_[(size_t)i * R + r] : 0u; }
+    O2345_HD void put(int i, float zv, float sv, unsigned t) {
+        z_[(size_t)i * R + r] = zv; sdf_[(size_t)i * R + r] = sv;
+        if (m_) m_[(size_t)i * R + r] = (uint8_t)t;
+    }
 };
 O2345_HD void merge_ray(int r, int R, float* __restrict__ z, float* __restrict__ sdf, int S, float* __restrict__ new_z,
                         float* __restrict__ new_sdf, int n_new) {
@@ -274,7 +296,7 @@ O2345_HD void merge_ray(int r, int R, float* __restrict__ z, float* __restrict__
     for (int base = 0; base < n_new; base += NMAX) {                 // blocks of at most NMAX new samples (the renderer uses 16)
         const int nb = n_new - base < NMAX ? n_new - base : NMAX;
         for (int j = 0; j < nb; ++j) { nz[j] = new_z[(size_t)(base + j) * R + r]; ns[j] = new_sdf[(size_t)(base + j) * R + r]; nt[j] = 0u; }
-        GlobalMerge a{z, sdf, (size_t)R, r};
+        GlobalMergeTag a{z, sdf, nullptr, (size_t)R, r};
         ArrayBlock blk{nz, ns, nt};
         merge_core(a, S + base, blk, nb);
         for (int j = 0; j < nb; ++j) { new_z[(size_t)(base + j) * R + r] = nz[j]; new_sdf[(size_t)(base + j) * R + r] = ns[j]; }
@@ -309,6 +331,41 @@ O2345_HD float composite_sample_alpha(float dx, float dy, float dz, float gx, fl
     return fminf(fmaxf(alpha, 0.f), 1.f) * m;
 }
 
+// The ordered accumulation of one ray (:373-429), sample by sample in the reference's order: transmittance, weights, colour / depth sums, gradient
+// error, samples seen by >= 2 views; finish() writes the per-ray outputs; then the depth variance, a second ordered pass over (mid depth, weight).
+// The one-lane-per-ray kernel feeds it from registers (blocks of CB samples loaded first), the sixteen-lane kernel's lane 0 out of LDS.
+struct CompositeSums {
+    float T = 1.f, wsum = 0.f, wmax = 0.f, asum = 0.f, c0 = 0.f, c1 = 0.f, c2 = 0.f, dep = 0.f, ge = 0.f, gm = 0.f, dv = 0.f;
+    int n_seen = 0;
+    // gerr = m * (|gradient| - 1)^2.  -> the sample's weight
+    O2345_HD float add(float alpha, float r_, float g_, float b_, float mid_z, float gerr, float m, bool seen) {
+        const float w = transmit_step(T, alpha);
+        wsum += w; wmax = fmaxf(wmax, w); asum += alpha;
+        c0 += r_ * w; c1 += g_ * w; c2 += b_ * w;
+        dep += mid_z * w;
+        ge += gerr; gm += m;
+        n_seen += seen ? 1 : 0;
+        return w;
+    }
+    O2345_HD void finish(const CompositeOut& o, int r, float background) const {
+        const float bg = background * (1.f - wsum);
+        o.color[3 * r] = c0 + bg; o.color[3 * r + 1] = c1 + bg; o.color[3 * r + 2] = c2 + bg;
+        o.depth[r] = dep;
+        o.weights_sum[r] = wsum; o.weights_max[r] = wmax; o.alpha_sum[r] = asum;
+        o.grad_err[2 * r] = ge; o.grad_err[2 * r + 1] = gm;
+        o.color_mask[r] = n_seen > 8 ? 1 : 0;
+    }
+    O2345_HD void add_var(float mid_z, float w) {
+        const float d = mid_z - dep;
+        dv += d * d * w;
+    }
+    O2345_HD void finish_var(const CompositeOut& o, int r) const { o.depth_var[r] = dv; }
+};
+O2345_HD float gradient_error(float gx, float gy, float gz, float m) {
+    const float gn = sqrtf(gx * gx + gy * gy + gz * gz) - 1.f;
+    return m * (gn * gn);
+}
+
 O2345_HD void composite_ray(const RayGeom& g, int r, int S, const float* __restrict__ mid_z,
                             const float* __restrict__ dists, const float* __restrict__ pm, const float* __restrict__ sdf,
                             const float* __restrict__ grad /*[S*R,3]*/, const float* __restrict__ rgb /*[S*R,3]*/,
@@ -316,8 +373,7 @@ O2345_HD void composite_ray(const RayGeom& g, int r, int S, const float* __restr
                             float background, const CompositeOut& o) {
     const int R = g.R;
     const float dx = g.rays_d[3 * r], dy = g.rays_d[3 * r + 1], dz = g.rays_d[3 * r + 2];
-    float T = 1.f, wsum = 0.f, wmax = 0.f, asum = 0.f, c0 = 0.f, c1 = 0.f, c2 = 0.f, dep = 0.f, ge = 0.f, gm = 0.f;
-    int n_seen = 0;
+    CompositeSums sum;
     // The per-sample inputs do not depend on the running transmittance: a block of CB samples is LOADED first (11 values each, all loads of the
     // block in flight together), then the serial chain runs over registers -- the arithmetic and its order are those of a plain loop over s.
     constexpr int CB = 8;
@@ -342,26 +398,12 @@ O2345_HD void composite_ray(const RayGeom& g, int r, int S, const float* __restr
                 const float gx = bg[k][0], gy = bg[k][1], gz = bg[k][2];
                 float pc;
                 const float alpha = composite_sample_alpha(dx, dy, dz, gx, gy, gz, m, bd[k], bs[k], inv_s, alpha_inter_ratio, pc);
-                const float w = alpha * T;
-                T = T * (1.f - alpha + 1e-7f);
-                wout[p] = w;
+                wout[p] = sum.add(alpha, bc[k][0], bc[k][1], bc[k][2], bz[k], gradient_error(gx, gy, gz, m), m, bn[k] >= 2);
                 cout_[p] = pc;
-                wsum += w; wmax = fmaxf(wmax, w); asum += alpha;
-                c0 += bc[k][0] * w; c1 += bc[k][1] * w; c2 += bc[k][2] * w;
-                dep += bz[k] * w;
-                const float gn = sqrtf(gx * gx + gy * gy + gz * gz) - 1.f;
-                ge += m * (gn * gn); gm += m;
-                n_seen += bn[k] >= 2 ? 1 : 0;
             }
         }
     }
-    const float bg = background * (1.f - wsum);
-    o.color[3 * r] = c0 + bg; o.color[3 * r + 1] = c1 + bg; o.color[3 * r + 2] = c2 + bg;
-    o.depth[r] = dep;
-    o.weights_sum[r] = wsum; o.weights_max[r] = wmax; o.alpha_sum[r] = asum;
-    o.grad_err[2 * r] = ge; o.grad_err[2 * r + 1] = gm;
-    o.color_mask[r] = n_seen > 8 ? 1 : 0;
-    float dv = 0.f;
+    sum.finish(o, r, background);
     for (int sb = 0; sb < S; sb += CB) {
         float bz[CB], bw[CB];
 #pragma unroll
@@ -372,12 +414,9 @@ O2345_HD void composite_ray(const RayGeom& g, int r, int S, const float* __restr
         }
 #pragma unroll
         for (int k = 0; k < CB; ++k)
-            if (sb + k < S) {
-                const float d = bz[k] - dep;
-                dv += d * d * bw[k];
-            }
+            if (sb + k < S) sum.add_var(bz[k], bw[k]);
     }
-    o.depth_var[r] = dv;
+    sum.finish_var(o, r);
 }
 
 }  // namespace o2345

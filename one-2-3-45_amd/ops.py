@@ -588,6 +588,18 @@ def list_sort_by_visibility(pts, index, proj, H, W, count=None, want_keys=False)
 _SCENE_KEYS = ("sdf_blob", "vol_cl", "maskvol", "cmaps", "proj", "cam_pos")
 
 
+def _color_network(scene, what):
+    """-> (entry point, blob) of the colour network the scene's precision selects: o2345_color_points_x3 with color_x3_blob in f16x3 mode (when the scene
+    has that blob), else o2345_color_points_mfma with color_mfma_blob."""
+    xb, mb = scene.get("color_x3_blob"), scene.get("color_mfma_blob")
+    L = _lib.lib()
+    if xb is not None and config.color_precision(scene.get("color_precision")) == "f16x3":
+        return L.o2345_color_points_x3, xb
+    if mb is None:
+        raise ValueError(f"{what}: scene needs color_x3_blob (f16x3 mode) or color_mfma_blob (fp32 mode)")
+    return L.o2345_color_points_mfma, mb
+
+
 @_on_device
 def render_rays(scene, rays_o, rays_d, near, far, n_samples=64, n_importance=64, inv_s=None, alpha_inter_ratio=1.0,
                 background=1.0, query_cam=None, want_z=False, t_rand=None, sample_dist=None, want_scalars=False, color_stats=None,
@@ -642,11 +654,9 @@ def render_rays(scene, rays_o, rays_d, near, far, n_samples=64, n_importance=64,
     io = _lib.RenderIO()
     for k in _SCENE_KEYS:
         setattr(io, k, scene[k].data_ptr())
-    xb, mb = scene.get("color_x3_blob"), scene.get("color_mfma_blob")
-    use_x3 = xb is not None and config.color_precision(scene.get("color_precision")) == "f16x3"
-    if not use_x3 and mb is None:
-        raise ValueError("render_rays: scene needs color_x3_blob (f16x3 mode) or color_mfma_blob (fp32 mode)")
-    io.color_x3_blob = _p(xb).value if use_x3 else None
+    fn, blob = _color_network(scene, "render_rays")
+    mb = scene.get("color_mfma_blob")
+    io.color_x3_blob = _p(blob).value if fn is L.o2345_color_points_x3 else None
     io.color_mfma_blob = _p(mb).value if mb is not None else None
     io.t_rand = _p(t_rand).value if t_rand is not None else None
     io.sdf_mode = 2 if config.sdf_precision(scene.get("sdf_precision")) == "f16x3" else 0
@@ -754,11 +764,8 @@ def render_core(scene, rays_o, rays_d, z, sample_dist, inv_s, alpha_inter_ratio=
     nviews = torch.zeros(S * R, dtype=torch.uint8, device=z.device)
     check(_lib.lib().o2345_view_count_unlisted(_p(pts), S * R, _p(o["pm"]), _p(scene["maskvol"]), D, _p(scene["proj"]), V, H, W,
                                                _p(nviews, torch.uint8), _stream()), "view_count_unlisted")
-    xb, mb = scene.get("color_x3_blob"), scene.get("color_mfma_blob")
-    use_x3 = xb is not None and config.color_precision(scene.get("color_precision")) == "f16x3"
-    L = _lib.lib()
-    fn = L.o2345_color_points_x3 if use_x3 else L.o2345_color_points_mfma
-    check(fn(_p(xb if use_x3 else mb), _p(scene["vol_cl"]), _p(scene["maskvol"]), D, _p(scene["cmaps"]), _p(scene["proj"]), _p(scene["cam_pos"]), V, H, W,
+    fn, blob = _color_network(scene, "render_core")
+    check(fn(_p(blob), _p(scene["vol_cl"]), _p(scene["maskvol"]), D, _p(scene["cmaps"]), _p(scene["proj"]), _p(scene["cam_pos"]), V, H, W,
              _p(pts), _p(lst, torch.int32), None, n, _p(query_cam), None, _p(o["rgb"]), _p(nviews, torch.uint8), None, _stream()), "color_points")
     c = ray_composite(rays_o, rays_d, o["mid_z"], o["dists"], o["pm"], o["sdf"], o["grad"], o["rgb"], nviews.view(S, R), inv_s, alpha_inter_ratio, background)
     c.update(mid_z=o["mid_z"], dists=o["dists"], pm=o["pm"], sdf=o["sdf"], grad=o["grad"], rgb=o["rgb"], nviews=nviews.view(S, R), list=lst, z_vals=z)

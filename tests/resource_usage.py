@@ -15,7 +15,7 @@ def kernel_usage(source, name_pattern, key, tmp_path):
     """Compile csrc/``source`` for the device only.  -> {key(match): {"VGPRs", "AGPRs", "ScratchSize", "Occupancy", "LDS"}} for every kernel whose
     mangled name matches ``name_pattern``."""
     src = os.path.join(build.CSRC, source)
-    cmd = [HIPCC] + build.FLAGS + build.EXTRA_FLAGS[source] + ["--offload-device-only", "-c", src, "-o", str(tmp_path / (source + ".o")),
+    cmd = [HIPCC] + build.FLAGS + build.EXTRA_FLAGS.get(source, []) + ["--offload-device-only", "-c", src, "-o", str(tmp_path / (source + ".o")),
                                                                "-Rpass-analysis=kernel-resource-usage"]
     r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     assert r.returncode == 0, r.stdout[-4000:]

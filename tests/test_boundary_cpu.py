@@ -69,6 +69,19 @@ def test_render_call_validates_its_arguments_before_touching_the_device():
     assert lib.o2345_render_rays(None, dummy, ctypes.c_size_t(ws_bytes), None) != 0 and b"null pointer" in lib.o2345_last_error()
 
 
+def test_render_workspace_size_is_pinned(lib_instance):
+    """o2345_render_workspace_bytes is the sum of one layout (csrc/render.hip, RenderLayout) the render call carves every buffer from.  The expected sizes
+    were recorded from the library at commit 306a2ce, which computed them with three hand-kept offset formulas: below and above the streaming threshold
+    (with and without the scratch rows), with and without the list sort (2^20 sample slots, at most 32 views), an n_importance / 4 that is no power of
+    two, and the scratch rows forced on for a small batch (O2345_RAY_STREAM_MIN=1)."""
+    want = {(7, 64, 64, 8): 27648, (512, 64, 64, 8): 1974784, (8192, 64, 64, 8): 44438784, (8192, 64, 64, 40): 35785728, (80, 48, 80, 4): 312064,
+            (262144, 64, 64, 8): 1421953792}
+    lib = lib_instance({})
+    for shape, size in want.items():
+        assert lib.o2345_render_workspace_bytes(*shape) == size, shape
+    assert lib_instance({"O2345_RAY_STREAM_MIN": "1"}).o2345_render_workspace_bytes(512, 64, 64, 8) == 2236928
+
+
 def test_render_io_has_one_declaration_and_the_binding_checks_it(tmp_path):
     """O2345RenderIO is declared in include/o2345.h only: csrc/ compiles that header (common.h includes it), the ctypes Structure is generated from its
     text, and the loaded library's own sizeof / offsetof table is compared at load time.  A field added to ONE side only must fail loudly."""
