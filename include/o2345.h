@@ -46,7 +46,8 @@ const char* o2345_last_error(void);
 /* 210 = ABI 2.1 (round 5): O2345RenderIO gains `segment_rays` (the reference's two per-CALL rules applied per segment of a fused call: a whole image
  * behind the trainer's unchanged 512-ray chunk loop) and `weight_cull` (tolerance-bounded colour work removal); o2345_ray_composite is unchanged.
  * Additive since 2.1 (no existing entry changed, the version stays 210): the asset export entries o2345_mesh_bounds_workspace_bytes,
- * o2345_mesh_asset_vertices, o2345_mesh_asset_indices, o2345_obj_text_bytes, o2345_obj_text, o2345_obj_text_host. */
+ * o2345_mesh_asset_vertices, o2345_mesh_asset_indices, o2345_obj_text_bytes, o2345_obj_text, o2345_obj_text_host; the mesh component entries
+ * o2345_mesh_components_workspace_bytes, o2345_mesh_components_count, o2345_mesh_components_emit. */
 int o2345_version(void);
 /* Layout self-description of O2345RenderIO as THIS library was compiled (sizeof, and offsetof of every field in declaration order): a binding
  * asserts its own struct against it at load time (one-2-3-45_amd/_lib.py does) -- a field added on one side only cannot corrupt calls silently.
@@ -339,6 +340,24 @@ int o2345_marching_cubes_count(const float* u, int n0, int n1, int n2, double is
 int o2345_marching_cubes_emit(const float* u, int n0, int n1, int n2, double iso, void* workspace, double* verts,
                               void* tris, int index_bytes, void* stream);
 
+/* ---- mesh components (additive since 2.1: drops the detached blobs of an extracted mesh before it is coloured and written; the reference has no such step,
+ * its users run mesh.split() afterwards) -------------------------------------------------------------------------------------------------
+ * Component: vertices connected through triangles that share vertex INDICES; a vertex no triangle references is a component with 0 faces.  Label of a
+ * vertex: the smallest vertex index of its component.  Size: its number of faces.  Selection: min_faces = n keeps components with >= n faces;
+ * keep_largest keeps only the one with the most faces (ties: smaller label), among what min_faces left; with any selection active 0-face components
+ * are dropped; with none (min_faces <= 0, keep_largest = 0) everything is kept.  A triangle is kept iff its first vertex is.  Exact and deterministic.
+ * tris device int32 / int64 [nt,3] (index_bytes 4 / 8); nv, nt >= 0, nv * 3 < 2^31.  workspace: mesh_components_workspace_bytes(nv, nt) bytes, 16-byte aligned.
+ * count() (synchronises the stream once) returns on the HOST the number of components, of kept components, of kept vertices and triangles, and writes
+ * the labels (device int32 [nv]) when `labels` is not NULL; a triangle index outside [0, nv) is an error.  emit() (same workspace, untouched in between):
+ * verts device fp64 [nv,3] -> verts_out [nv_kept,3] bit for bit and in order, tris_out [nt_kept,3] (same index width) renumbered by the exclusive scan of
+ * the vertex keep flags, kept_out device int32 [nv_kept] = new -> old vertex index.  Any output may be NULL. */
+size_t o2345_mesh_components_workspace_bytes(long long nv, long long nt);
+int o2345_mesh_components_count(const void* tris, int index_bytes, long long nv, long long nt, long long min_faces, int keep_largest, void* workspace,
+                                size_t workspace_bytes, int* labels, long long* n_components_host, long long* n_components_kept_host,
+                                long long* nv_kept_host, long long* nt_kept_host, void* stream);
+int o2345_mesh_components_emit(const double* verts, const void* tris, int index_bytes, long long nv, long long nt, void* workspace, double* verts_out,
+                               void* tris_out, int* kept_out, void* stream);
+
 /* ---- mesh serialisation (replaces the numpy / trimesh tail of validate_mesh and validate_colored_mesh,
  * models/trainer_generic.py:1287-1303, 1365-1382: index -> world frame, scale_mat, trans_mat, uint8 colours, PLY records) -----
  * verts_idx: device fp64 [n,3] index coordinates on an R^3 grid (o2345_marching_cubes_emit); bound_min/max [3], scale_mat and
@@ -391,7 +410,7 @@ int o2345_obj_text(const float* positions, const uint8_t* rgba, const float* nor
 int o2345_obj_text_host(const float* positions, const uint8_t* rgba, const float* normals, long long n, const uint32_t* indices, long long m, int K,
                         uint8_t* text);
 /* Load every code object of the library on the current device now (the HIP runtime loads a translation unit's kernels at its first launch: 5 - 60 ms
- * each for the 16 units of this library, which otherwise land inside the first calls of a fresh process).  Launches nothing that touches user memory. */
+ * each for the 17 units of this library, which otherwise land inside the first calls of a fresh process).  Launches nothing that touches user memory. */
 int o2345_preload(void);
 
 #ifdef __cplusplus

@@ -68,3 +68,32 @@ def prepack_resolutions():
     v = os.environ.get("O2345_PREPACK_RESOLUTIONS", "256")
     return tuple(int(x) for x in v.replace(",", " ").split())
 
+
+# ---- mesh component filter (csrc/mesh_components.hip; mesh_io.filter_components is the host twin) ----------------------------------------------------
+# O2345_MESH_MIN_COMPONENT_FACES=n drops the connected components of the extracted mesh with fewer than n faces; O2345_MESH_KEEP_LARGEST=1 keeps only the
+# component with the most faces (ties: the smaller label), among what the threshold left.  Both off by default ("" or "0" = off, like the other knobs): the
+# mesh is then what marching cubes found, as before.  The filter runs on the device between marching cubes and vertex colouring.
+def _non_negative_int(name, text):
+    t = text.strip()
+    if t == "":
+        return 0
+    if not t.isdigit():
+        raise ValueError(f"{name} must be a non-negative integer, got {text!r}")
+    return int(t)
+
+
+MESH_MIN_COMPONENT_FACES = _non_negative_int("O2345_MESH_MIN_COMPONENT_FACES", os.environ.get("O2345_MESH_MIN_COMPONENT_FACES", ""))
+MESH_KEEP_LARGEST = _non_negative_int("O2345_MESH_KEEP_LARGEST", os.environ.get("O2345_MESH_KEEP_LARGEST", "")) != 0
+
+
+def mesh_min_component_faces(n=None):
+    """None -> the configured default; anything else must be a non-negative integer."""
+    if n is None:
+        return MESH_MIN_COMPONENT_FACES
+    if isinstance(n, bool) or int(n) != n or n < 0:
+        raise ValueError(f"min_component_faces must be a non-negative integer, got {n!r}")
+    return int(n)
+
+
+def mesh_keep_largest(k=None):
+    return MESH_KEEP_LARGEST if k is None else bool(k)

@@ -1,4 +1,4 @@
-// Small non-matrix kernels and block-level steps shared by several translation units (costvol.hip, sparse.hip, mcubes.hip, convnet.hip).
+// Small non-matrix kernels and block-level steps shared by several translation units (costvol.hip, sparse.hip, mcubes.hip, mesh_components.hip, convnet.hip).
 // The kernels live in an anonymous namespace: every unit that launches one instantiates its own copy in its own code object, so o2345_preload
 // and the runtime's per-unit loading see them as before.
 #pragma once
@@ -19,6 +19,25 @@ __device__ __forceinline__ bool block_sum2_256(double& s, double& q) {
     s = (sm[0][0] + sm[0][1]) + (sm[0][2] + sm[0][3]);
     q = (sm[1][0] + sm[1][1]) + (sm[1][2] + sm[1][3]);
     return true;
+}
+
+// block-wide exclusive scan of one int per thread (256 threads); lds is free again on return: mcubes.hip, mesh_components.hip
+__device__ __forceinline__ int block_scan_excl(int v, int* lds /*[5]*/, int& total) {
+    int inc = v;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        int t = __shfl_up(inc, off);
+        if ((threadIdx.x & 63) >= off) inc += t;
+    }
+    const int w = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 63) lds[w] = inc;
+    __syncthreads();
+    int base = 0, tot = 0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) { int t = lds[i]; if (i < w) base += t; tot += t; }
+    total = tot;
+    __syncthreads();
+    return base + inc - v;
 }
 
 // batch statistics of channel c -> the (scale, shift) pair of InPlaceABN: s = sum x, q = sum x^2 over `count` values, biased variance;

@@ -67,25 +67,6 @@ __device__ __forceinline__ void mc_point_counts(const float* __restrict__ u, con
     }
 }
 
-// block-wide exclusive scan of one int per thread (256 threads)
-__device__ __forceinline__ int block_scan_excl(int v, int* lds /*[5]*/, int& total) {
-    int inc = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        int t = __shfl_up(inc, off);
-        if ((threadIdx.x & 63) >= off) inc += t;
-    }
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 63) lds[w] = inc;
-    __syncthreads();
-    int base = 0, tot = 0;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) { int t = lds[i]; if (i < w) base += t; tot += t; }
-    total = tot;
-    __syncthreads();
-    return base + inc - v;
-}
-
 __global__ __launch_bounds__(256) void k_mc_count(const float* __restrict__ u, McGrid g, uint8_t* __restrict__ vcnt,
                                                   uint16_t* __restrict__ tcase, int* __restrict__ vblock, int* __restrict__ tblock) {
     __shared__ int lds[5];

@@ -11,7 +11,8 @@ Asset formats (the reference's utils/utils.py:31-47, convert_mesh_format behind 
 Wavefront OBJ (``.obj``) in the asset frame -- (x, y, z) -> (x, z, y), z-up -> glTF's y-up, every face reversed; the reference's two rotations and
 x flip compose to exactly that.  ``write_glb`` / ``write_obj`` / ``read_glb`` / ``read_obj`` / ``convert_mesh`` are the host layer (numpy, no GPU) and the
 DEFINITION of the two files; ``export_asset`` is the device path (csrc/mesh_export.hip): buffers and OBJ text are produced on the device, one D2H copy
-per buffer, one file write.  No byte parity with trimesh's own OBJ / GLB writers is claimed (trimesh is not available to compare against)."""
+per buffer, one file write.  ``component_labels`` / ``filter_components`` are the host twin (and definition) of the device component filter
+(csrc/mesh_components.hip).  No byte parity with trimesh's own OBJ / GLB writers is claimed (trimesh is not available to compare against)."""
 import json
 import os
 import struct
@@ -345,13 +346,76 @@ def _asset_ext(path):
     return ext
 
 
-def convert_mesh(ply_path, out_path):
+# ------------------------------------------------------------------------------------------------------------------ connected components
+def component_labels(faces, n_vertices):
+    """Label of every vertex of an indexed triangle mesh: the smallest vertex index of its connected component (vertices connected through triangles that
+    share vertex indices; an unreferenced vertex is its own component).  int32 [n_vertices].  The host twin of ops.mesh_component_labels and the
+    DEFINITION of its result.  Hook + pointer jumping: every round hooks each root under the smallest root it shares an edge with, then compresses all
+    paths by repeated parent[parent]; the number of components at least halves per round, so the cost does not grow with the mesh diameter (label
+    propagation needs one sweep per step of the longest shortest path)."""
+    n = int(n_vertices)
+    f = np.asarray(faces).reshape(-1, 3).astype(np.int64, copy=False)
+    if f.size and (f.min() < 0 or f.max() >= n):
+        raise ValueError(f"faces index outside 0 .. {n - 1}")
+    parent = np.arange(n, dtype=np.int64)
+    u = np.concatenate([f[:, 0], f[:, 1]])
+    v = np.concatenate([f[:, 1], f[:, 2]])
+    while u.size:
+        pu, pv = parent[u], parent[v]                                  # roots: every path is fully compressed here
+        live = pu != pv
+        if not live.any():
+            break
+        u, v, pu, pv = u[live], v[live], pu[live], pv[live]
+        np.minimum.at(parent, np.maximum(pu, pv), np.minimum(pu, pv))  # larger root under the smallest neighbouring root: parent[x] <= x, no cycles
+        while True:
+            pp = parent[parent]
+            if np.array_equal(pp, parent):
+                break
+            parent = pp
+    return parent.astype(np.int32)
+
+
+def filter_components(verts, faces, colors=None, normals=None, min_faces=0, keep_largest=False):
+    """Drop connected components by face count (host twin of ops.mesh_filter_components, and the definition of its result).  ``min_faces = n`` keeps the
+    components with at least n faces, ``keep_largest`` only the one with the most faces (ties: the smaller label) among what ``min_faces`` left; whenever
+    one of them is active, vertices that no face references are dropped too.  Kept vertices and faces stay in their original order; faces are
+    renumbered; vertex rows (and colours, normals) are copied as they are.  Returns (verts, faces, colors, normals, kept, info): ``kept`` int32 new -> old
+    vertex index, ``info`` = {"components", "components_kept"}.  With nothing selected the inputs are returned as they are (kept = all)."""
+    v = np.asarray(verts)
+    f = np.asarray(faces).reshape(-1, 3)
+    n = v.shape[0]
+    min_faces = int(min_faces)
+    if min_faces < 0:
+        raise ValueError(f"min_faces must be >= 0, got {min_faces}")
+    lab = component_labels(f, n)
+    n_comp = int(np.count_nonzero(lab == np.arange(n)))
+    if min_faces == 0 and not keep_largest:
+        return verts, faces, colors, normals, np.arange(n, dtype=np.int32), {"components": n_comp, "components_kept": n_comp}
+    size = np.bincount(lab[f[:, 0]], minlength=n) if f.shape[0] else np.zeros(n, np.int64)      # faces per label
+    good = size >= max(min_faces, 1)
+    if keep_largest and good.any():
+        best = int(np.argmax(np.where(good, size, -1)))                # argmax returns the FIRST maximum: the smaller label
+        good = np.zeros(n, bool)
+        good[best] = True
+    keep_v = good[lab]
+    kept = np.flatnonzero(keep_v).astype(np.int32)
+    new_index = np.cumsum(keep_v) - keep_v                             # exclusive scan of the keep flags
+    keep_f = keep_v[f[:, 0]] if f.shape[0] else np.zeros(0, bool)
+    f_out = new_index[f[keep_f]].astype(f.dtype)
+    take = lambda a: None if a is None else np.asarray(a)[kept]
+    return v[kept], f_out, take(colors), take(normals), kept, {"components": n_comp, "components_kept": int(np.count_nonzero(good))}
+
+
+def convert_mesh(ply_path, out_path, min_component_faces=0, keep_largest=False):
     """convert_mesh_format (utils/utils.py:31-47) for a mesh already on disk: read the PLY, exchange y and z, reverse the faces, write ``out_path`` by its
-    extension (.glb or .obj) with the PLY's vertex colours.  Returns ``out_path``."""
+    extension (.glb or .obj) with the PLY's vertex colours.  ``min_component_faces`` / ``keep_largest``: filter_components on the way (off by default).
+    Returns ``out_path``."""
     ext = _asset_ext(out_path)
     if ext == ".ply":
         raise ValueError("convert_mesh: the output is .glb or .obj")
     v, f, c = read_ply(ply_path)
+    if min_component_faces or keep_largest:
+        v, f, c, _, _, _ = filter_components(v, f, c, None, min_component_faces, keep_largest)
     v, f = to_asset_frame(v, f)
     (write_glb if ext == ".glb" else write_obj)(out_path, v, f, c)
     return out_path

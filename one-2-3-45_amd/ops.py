@@ -878,3 +878,49 @@ def marching_cubes(u, iso=0.0, index_dtype=torch.int64):
     check(L.o2345_marching_cubes_emit(_p(u), n0, n1, n2, float(iso), _p(ws, torch.uint8), _p(verts, torch.float64),
                                       _p(tris, index_dtype), 8 if index_dtype == torch.int64 else 4, _stream()), "marching_cubes_emit")
     return verts, tris
+
+
+# ---------------------------------------------------------------------------------------------------------- mesh components
+def _mesh_components_count(tris, nv, min_faces, keep_largest, labels):
+    """Pass 1 of the two-call protocol -> (workspace, components, components_kept, nv_kept, nt_kept)."""
+    if tris.dtype not in (torch.int32, torch.int64) or tris.dim() != 2 or tris.shape[1] != 3:
+        raise ValueError(f"expected triangles [M,3] int32 or int64, got {tuple(tris.shape)} {tris.dtype}")
+    L = _lib.lib()
+    nt = tris.shape[0]
+    wsb = L.o2345_mesh_components_workspace_bytes(nv, nt)
+    ws = _workspace(wsb, tris.device, "mesh_components")
+    nc, nck, nvk, ntk = (ctypes.c_longlong() for _ in range(4))
+    check(L.o2345_mesh_components_count(_p(tris, tris.dtype), 8 if tris.dtype == torch.int64 else 4, nv, nt, min(int(min_faces), 2 ** 31 - 1), int(bool(keep_largest)),
+                                        _p(ws, torch.uint8), wsb, _p(labels, torch.int32), ctypes.byref(nc), ctypes.byref(nck), ctypes.byref(nvk),
+                                        ctypes.byref(ntk), _stream()), "mesh_components_count")
+    return ws, nc.value, nck.value, nvk.value, ntk.value
+
+
+@_on_device
+def mesh_component_labels(tris, n_vertices):
+    """tris [M,3] int32 / int64 on the device -> int32 [n_vertices]: the smallest vertex index of every vertex's connected component
+    (== mesh_io.component_labels, exactly)."""
+    labels = torch.empty(int(n_vertices), dtype=torch.int32, device=tris.device)
+    _mesh_components_count(tris, int(n_vertices), 0, False, labels)
+    return labels
+
+
+@_on_device
+def mesh_filter_components(verts_idx, tris, min_faces=0, keep_largest=False):
+    """Drops connected components of a mesh on the device by face count (== mesh_io.filter_components, exactly; definitions in csrc/mesh_components.hip).
+    verts_idx fp64 [N,3], tris [M,3] int32 / int64 -> (verts, tris, kept, info): kept vertices / triangles in their original order, triangles renumbered,
+    ``kept`` int32 new -> old vertex index (gather any per-vertex attribute with it), ``info`` = {"components", "components_kept"}.
+    With nothing selected no kernel is launched: the inputs are returned as they are, ``kept`` and ``info`` are None."""
+    min_faces = config.mesh_min_component_faces(min_faces)
+    if min_faces == 0 and not keep_largest:
+        return verts_idx, tris, None, None
+    nv = verts_idx.shape[0]
+    ws, nc, nck, nvk, ntk = _mesh_components_count(tris, nv, min_faces, keep_largest, None)
+    dev = verts_idx.device
+    verts = torch.empty(nvk, 3, dtype=torch.float64, device=dev)
+    tris_out = torch.empty(ntk, 3, dtype=tris.dtype, device=dev)
+    kept = torch.empty(nvk, dtype=torch.int32, device=dev)
+    check(_lib.lib().o2345_mesh_components_emit(_p(verts_idx, torch.float64), _p(tris, tris.dtype), 8 if tris.dtype == torch.int64 else 4, nv, tris.shape[0],
+                                                _p(ws, torch.uint8), _p(verts, torch.float64), _p(tris_out, tris.dtype), _p(kept, torch.int32), _stream()),
+          "mesh_components_emit")
+    return verts, tris_out, kept, {"components": nc, "components_kept": nck}

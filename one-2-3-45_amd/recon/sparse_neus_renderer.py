@@ -8,7 +8,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from .. import ops
+from .. import config, ops
 from .rendering_network import DeferredColour
 from .sparse_sdf_network import _attr_cache, channel_last
 
@@ -504,6 +504,10 @@ class SparseNeuSRenderer(nn.Module):
             e = torch.nn.functional.interpolate((1 - occupancy_mask)[None, None].float(), [resolution] * 3, mode="nearest")[0, 0] > 0
             u = torch.where(e.to(u.device), torch.full_like(u, -100.0), u)
         v, t = ops.marching_cubes(u.contiguous(), float(threshold))
+        # O2345_MESH_MIN_COMPONENT_FACES / O2345_MESH_KEEP_LARGEST (config.py; both off by default: nothing is launched): small components are dropped on
+        # the device, so the unchanged runner's validate_colored_mesh colours and writes the filtered mesh; u is returned as it is
+        if config.MESH_MIN_COMPONENT_FACES or config.MESH_KEEP_LARGEST:
+            v, t, _, _ = ops.mesh_filter_components(v, t, config.MESH_MIN_COMPONENT_FACES, config.MESH_KEEP_LARGEST)
         # the reference returns numpy (vertices float64 in world units, triangles, u): index -> world on the device (fp64, the expression numpy would
         # evaluate), then three copies into pinned memory and one synchronisation
         if v.shape[0]:

@@ -4,6 +4,9 @@ fed the same arrays.  Two meshes: BASELINE config 2 (8 views, 128^3 volume, 256^
   stage_ms   fields on the device -> file on a tmpfs path: packing kernels + D2H copies + file write, host clock around a call that ends synchronised
   whole_ms   pipeline.export_mesh_ply / export_mesh_asset: SDF lattice + marching cubes + vertex colours + the stage above
   kernel_ms  the packing kernels alone, HIP events
+  components the component filter (csrc/mesh_components.hip, keep_largest) on the config's mesh: its kernels alone (HIP events around the two-call
+             protocol, which synchronises once in the middle) next to marching cubes on the same field, the gradient + colour time with and without
+             it, and the filtered stage / whole-export variants inside the same alternating loops as the unfiltered ones
 Medians over --reps calls after --warmup calls; the ratio against the PLY of the SAME run is what to read.  Prints one JSON line.
 
     python tools/time_mesh_export.py [--reps 9] [--warmup 3] [--skip-512]
@@ -57,8 +60,10 @@ def med_events(fn, reps, warmup):
 def one_mesh(dev, wt, tmp, D, R, ray_scale, a, numpy_writer):
     inp = bench.make_inputs(dev, 8, 0, ray_scale)
     vol = pipeline.build_volume(wt, inp["imgs"], inp["aff"], inp["origin"], D, 2.0 / (D - 1))
-    _, verts_idx, tris, rgb, _, g = pipeline._mesh_fields(wt, vol, inp["proj"], inp["cam_pos"], R)
+    _, verts_idx, tris, rgb, u, g = pipeline._mesh_fields(wt, vol, inp["proj"], inp["cam_pos"], R)
     n, m = int(verts_idx.shape[0]), int(tris.shape[0])
+    cc = {}
+    _, f_verts, f_tris, f_rgb, _, _ = pipeline._mesh_fields(wt, vol, inp["proj"], inp["cam_pos"], R, keep_largest=True, info=cc)
     P = lambda e: os.path.join(tmp, "mesh" + e)
     res = {"volume": D, "grid": R, "vertices": n, "triangles": m}
     stage = {
@@ -66,6 +71,9 @@ def one_mesh(dev, wt, tmp, D, R, ray_scale, a, numpy_writer):
         "glb": lambda: mio.export_asset(P(".glb"), verts_idx, tris, R, vertex_colors=rgb),
         "obj": lambda: mio.export_asset(P(".obj"), verts_idx, tris, R, vertex_colors=rgb),
         "glb_normals": lambda: mio.export_asset(P("_n.glb"), verts_idx, tris, R, vertex_colors=rgb, normals=g),
+        "ply_largest": lambda: mio.export_mesh(P("_l.ply"), f_verts, f_tris, R, vertex_colors=f_rgb),
+        "glb_largest": lambda: mio.export_asset(P("_l.glb"), f_verts, f_tris, R, vertex_colors=f_rgb),
+        "obj_largest": lambda: mio.export_asset(P("_l.obj"), f_verts, f_tris, R, vertex_colors=f_rgb),
     }
     # alternate the variants inside one loop: drift of the shared host hits all of them alike
     for fn in stage.values():
@@ -99,12 +107,41 @@ def one_mesh(dev, wt, tmp, D, R, ray_scale, a, numpy_writer):
         "asset_pack_normals": med_events(lambda: ops.mesh_asset_pack(verts_idx, tris, R, rgb=rgb, grad=g), a.reps, a.warmup),
         "obj_text": med_events(lambda: ops.obj_text(pos, idx, rgba, None, K=K), a.reps, a.warmup),
     }
+    # the component filter: kernels alone next to marching cubes on the same field, and what it saves downstream (gradient + colours of dropped vertices)
+    def grad_color(vi):
+        pts = (vi / (R - 1.0) * 2.0 - 1.0).to(torch.float32).contiguous()
+        gg = ops.sdf_mlp(wt.sdf_blob, vol["vol_cl"], pts, variant=2, precision=wt.sdf_precision)["grad"]
+        x3 = wt.color_precision == "f16x3"
+        ops.color_points(wt.color_xblob if x3 else wt.color_mblob, vol["vol_cl"], vol["maskvol"], vol["cmaps"], inp["proj"], inp["cam_pos"], pts, normals=gg,
+                         want_nviews=False, mfma="x3" if x3 else True)
+    res["components"] = dict(cc, vertices_kept=int(f_verts.shape[0]), triangles_kept=int(f_tris.shape[0]), kernel_ms={
+        "marching_cubes": med_events(lambda: ops.marching_cubes(u, 0.0), a.reps, a.warmup),
+        "filter_keep_largest": med_events(lambda: ops.mesh_filter_components(verts_idx, tris, keep_largest=True), a.reps, a.warmup),
+        "labels_only": med_events(lambda: ops.mesh_component_labels(tris, n), a.reps, a.warmup),
+        "grad_color_all": med_events(lambda: grad_color(verts_idx), a.reps, a.warmup),
+        "grad_color_kept": med_events(lambda: grad_color(f_verts), a.reps, a.warmup),
+    })
+    A = (wt, vol, inp["proj"], inp["cam_pos"], R)
     whole = {
-        "ply": lambda: pipeline.export_mesh_ply(P(".ply"), wt, vol, inp["proj"], inp["cam_pos"], R),
-        "glb": lambda: pipeline.export_mesh_asset(P(".glb"), wt, vol, inp["proj"], inp["cam_pos"], R),
-        "obj": lambda: pipeline.export_mesh_asset(P(".obj"), wt, vol, inp["proj"], inp["cam_pos"], R),
+        "ply": lambda: pipeline.export_mesh_ply(P(".ply"), *A),
+        "glb": lambda: pipeline.export_mesh_asset(P(".glb"), *A),
+        "obj": lambda: pipeline.export_mesh_asset(P(".obj"), *A),
+        "ply_largest": lambda: pipeline.export_mesh_ply(P("_l.ply"), *A, keep_largest=True),
+        "glb_largest": lambda: pipeline.export_mesh_asset(P("_l.glb"), *A, keep_largest=True),
+        "obj_largest": lambda: pipeline.export_mesh_asset(P("_l.obj"), *A, keep_largest=True),
     }
-    res["whole_ms"] = {k: med(fn, max(3, a.reps // 3), 1) for k, fn in whole.items()}
+    # alternated like the stage variants; the spread (min .. max) of each is what a difference between two of them has to exceed
+    for fn in whole.values():
+        fn()
+    wacc = {k: [] for k in whole}
+    for _ in range(max(3, a.reps)):
+        for k, fn in whole.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            wacc[k].append((time.perf_counter() - t0) * 1e3)
+    res["whole_ms"] = {k: {"median_ms": statistics.median(v), "min_ms": min(v), "max_ms": max(v)} for k, v in wacc.items()}
     return res
 
 
