@@ -47,7 +47,8 @@ const char* o2345_last_error(void);
  * behind the trainer's unchanged 512-ray chunk loop) and `weight_cull` (tolerance-bounded colour work removal); o2345_ray_composite is unchanged.
  * Additive since 2.1 (no existing entry changed, the version stays 210): the asset export entries o2345_mesh_bounds_workspace_bytes,
  * o2345_mesh_asset_vertices, o2345_mesh_asset_indices, o2345_obj_text_bytes, o2345_obj_text, o2345_obj_text_host; the mesh component entries
- * o2345_mesh_components_workspace_bytes, o2345_mesh_components_count, o2345_mesh_components_emit. */
+ * o2345_mesh_components_workspace_bytes, o2345_mesh_components_count, o2345_mesh_components_emit; the adjacency and smoothing entries
+ * o2345_mesh_adjacency_workspace_bytes, o2345_mesh_adjacency_count, o2345_mesh_adjacency_emit, o2345_mesh_smooth. */
 int o2345_version(void);
 /* Layout self-description of O2345RenderIO as THIS library was compiled (sizeof, and offsetof of every field in declaration order): a binding
  * asserts its own struct against it at load time (one-2-3-45_amd/_lib.py does) -- a field added on one side only cannot corrupt calls silently.
@@ -357,6 +358,27 @@ int o2345_mesh_components_count(const void* tris, int index_bytes, long long nv,
                                 long long* nv_kept_host, long long* nt_kept_host, void* stream);
 int o2345_mesh_components_emit(const double* verts, const void* tris, int index_bytes, long long nv, long long nt, void* workspace, double* verts_out,
                                void* tris_out, int* kept_out, void* stream);
+
+/* ---- vertex adjacency and Taubin smoothing (additive since 2.1; the reference has no such step, its users smooth the mesh in another tool) ----------
+ * Adjacency: every triangle (a, b, c) contributes the ordered pairs (a,b), (b,a), (b,c), (c,b), (c,a), (a,c), minus those with equal ends.  Row v of the
+ * CSR table holds the distinct second elements of the pairs that start at v, ascending; the multiplicity of u in row v (the number of such pairs) is the
+ * number of triangles on edge {u, v}; boundary[v] = 1 iff some entry of row v has multiplicity exactly 1.  An unreferenced vertex has an empty row and
+ * boundary 0.  Independent of face order and of the rotation of a triangle's indices.  Exact and deterministic.
+ * tris device int32 / int64 [nt,3] (index_bytes 4 / 8); 0 <= nv < 2^30, 6 * nt < 2^31.  workspace: mesh_adjacency_workspace_bytes(nv, nt) bytes, 16-byte
+ * aligned.  count() builds the whole table inside the workspace and returns its number of entries on the HOST (synchronises the stream once); a triangle
+ * index outside [0, nv) is an error.  emit() (same workspace and nv, untouched in between) writes offsets device int32 [nv + 1], neighbours device int32
+ * [n_entries] (may be NULL when that is 0) and boundary device uint8 [nv].
+ * Smoothing: one step with factor f computes every vertex from the OLD positions in fp64: acc = 0; acc = acc + p[u] over the neighbours u in ascending
+ * order, per coordinate; m = acc / deg; d = m - p[v]; p'[v] = p[v] + f * d with separate multiply and add.  A vertex with deg = 0, or with boundary[v] = 1
+ * when `boundary_or_null` is given, keeps its value bit for bit.  mesh_smooth runs `iterations` times step(lam), then step(mu) unless mu == 0
+ * (0 < lam <= 1, mu <= 0, both finite: Taubin's filter; mu = 0 is plain Laplacian smoothing).  verts_in device fp64 [nv,3] is only read; the result is in
+ * verts_out [nv,3] for every iteration count (0: a copy); verts_tmp [nv,3] is scratch (may be NULL when at most one step runs).  The three must differ. */
+size_t o2345_mesh_adjacency_workspace_bytes(long long nv, long long nt);
+int o2345_mesh_adjacency_count(const void* tris, int index_bytes, long long nv, long long nt, void* workspace, size_t workspace_bytes,
+                               long long* n_entries_host, void* stream);
+int o2345_mesh_adjacency_emit(void* workspace, long long nv, int* offsets, int* neighbours, unsigned char* boundary, void* stream);
+int o2345_mesh_smooth(const double* verts_in, long long nv, const int* offsets, const int* neighbours, const unsigned char* boundary_or_null, int iterations,
+                      double lam, double mu, double* verts_tmp, double* verts_out, void* stream);
 
 /* ---- mesh serialisation (replaces the numpy / trimesh tail of validate_mesh and validate_colored_mesh,
  * models/trainer_generic.py:1287-1303, 1365-1382: index -> world frame, scale_mat, trans_mat, uint8 colours, PLY records) -----

@@ -97,3 +97,54 @@ def mesh_min_component_faces(n=None):
 
 def mesh_keep_largest(k=None):
     return MESH_KEEP_LARGEST if k is None else bool(k)
+
+
+# ---- mesh smoothing (csrc/mesh_smooth.hip; mesh_io.smooth_vertices is the host twin) -------------------------------------------------------------------
+# O2345_MESH_SMOOTH_ITERATIONS=n runs n iterations of Taubin's lambda|mu filter on the extracted mesh's vertex positions, on the device, after the vertex
+# colours were taken at the unsmoothed vertices ("" or "0" = off, the default: the mesh is then what marching cubes found, and nothing is launched).
+# O2345_MESH_SMOOTH_LAMBDA (0.5, in (0, 1]) and O2345_MESH_SMOOTH_MU (-0.53, <= 0; 0 = plain Laplacian smoothing, which shrinks the shape) are the two
+# factors of one iteration; O2345_MESH_SMOOTH_PIN_BOUNDARY (1) keeps the vertices on open edges (the rim of a mesh cut by the volume's faces) in place.
+def _finite_float(name, text, default, ok, what):
+    t = text.strip()
+    if t == "":
+        return default
+    try:
+        x = float(t)
+    except ValueError:
+        x = float("nan")
+    if not (x == x and abs(x) != float("inf") and ok(x)):
+        raise ValueError(f"{name} must be {what}, got {text!r}")
+    return x
+
+
+MESH_SMOOTH_ITERATIONS = _non_negative_int("O2345_MESH_SMOOTH_ITERATIONS", os.environ.get("O2345_MESH_SMOOTH_ITERATIONS", ""))
+MESH_SMOOTH_LAMBDA = _finite_float("O2345_MESH_SMOOTH_LAMBDA", os.environ.get("O2345_MESH_SMOOTH_LAMBDA", ""), 0.5, lambda x: 0.0 < x <= 1.0, "in (0, 1]")
+MESH_SMOOTH_MU = _finite_float("O2345_MESH_SMOOTH_MU", os.environ.get("O2345_MESH_SMOOTH_MU", ""), -0.53, lambda x: x <= 0.0, "finite and <= 0")
+_pin = os.environ.get("O2345_MESH_SMOOTH_PIN_BOUNDARY", "")
+MESH_SMOOTH_PIN_BOUNDARY = True if _pin.strip() == "" else _non_negative_int("O2345_MESH_SMOOTH_PIN_BOUNDARY", _pin) != 0
+del _pin
+
+
+def mesh_smooth_iterations(n=None):
+    """None -> the configured default; anything else must be a non-negative integer."""
+    if n is None:
+        return MESH_SMOOTH_ITERATIONS
+    if isinstance(n, bool) or int(n) != n or n < 0:
+        raise ValueError(f"smooth_iterations must be a non-negative integer, got {n!r}")
+    return int(n)
+
+
+def mesh_smooth_lambda(lam=None):
+    if lam is None:
+        return MESH_SMOOTH_LAMBDA
+    return _finite_float("lam", repr(float(lam)), None, lambda x: 0.0 < x <= 1.0, "in (0, 1]")
+
+
+def mesh_smooth_mu(mu=None):
+    if mu is None:
+        return MESH_SMOOTH_MU
+    return _finite_float("mu", repr(float(mu)), None, lambda x: x <= 0.0, "finite and <= 0")
+
+
+def mesh_smooth_pin_boundary(p=None):
+    return MESH_SMOOTH_PIN_BOUNDARY if p is None else bool(p)

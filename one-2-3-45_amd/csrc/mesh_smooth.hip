@@ -1,0 +1,395 @@
+// Vertex adjacency of an indexed triangle mesh as a CSR table built on the device, and Taubin's lambda|mu smoothing of the vertex positions over it.
+// Equal to the host twin (mesh_io.vertex_adjacency / smooth_vertices) to the last bit: the table is integer work, the smoothing step is a sequential
+// fp64 sum in a defined order (ascending neighbour index) followed by one division, one subtraction, one multiplication and one addition, never fused.
+//
+// Definitions
+//   pairs      every triangle (a, b, c) contributes the ordered pairs (a,b), (b,a), (b,c), (c,b), (c,a), (a,c), minus those with equal ends.
+//   row v      the distinct second elements of the pairs whose first element is v, ascending.  The multiplicity of u in row v is the number of such
+//              pairs = the number of triangles on edge {u, v}.
+//   boundary   boundary[v] = 1 iff some entry of row v has multiplicity exactly 1.  A vertex no triangle references: empty row, boundary 0.
+//   step(f)    Jacobi: for every v from the OLD positions, per coordinate acc = 0; acc = acc + p[u] for u ascending; m = acc / deg; d = m - p[v];
+//              p'[v] = p[v] + f * d.  deg = 0, or boundary[v] with pinning on: p'[v] = p[v] bit for bit.
+//   smooth     `iterations` times: step(lam), then step(mu) unless mu == 0.
+//
+// Build: capacities by integer atomicAdd per triangle corner, exclusive scan, slots claimed with an integer atomic cursor (the order inside a raw row is
+// arbitrary), then every row is sorted and its duplicates collapsed, which makes the result independent of that order.  Rows of at most ADJ_SHORT raw
+// entries (marching-cubes meshes: 8 - 24) are sorted by their own thread in registers; longer ones (the centre of a fan) go on a list and get one block
+// each, which rank-sorts the row.  No float atomics anywhere.
+#include "common.h"
+#include "block_kernels.h"
+
+namespace o2345 {
+
+constexpr int ADJ_ITEMS = 8;                        // items per thread of the scan kernels
+constexpr int ADJ_TILE = IDX_BLOCK * ADJ_ITEMS;     // per block
+constexpr int ADJ_SHORT = 32;                       // raw entries a thread sorts in registers
+constexpr int ADJ_LONG_GRID = 64;                   // blocks of the long-row kernels (each loops over the list)
+constexpr int ADJ_PAD = 0x7FFFFFFF;                 // sorts behind every vertex index
+
+// device scalars of one build (workspace head)
+struct AdjTotals {
+    long long n_raw, n_entries;                     // written by k_scan_small
+    unsigned long long n_bad;                       // triangles with an index outside [0, nv)
+    int n_long;                                     // rows on the long list
+};
+
+template <typename IDX>
+__device__ __forceinline__ bool adj_triangle(const IDX* __restrict__ tris, long long t, int nv, int& a, int& b, int& c) {
+    const long long ia = (long long)tris[3 * t], ib = (long long)tris[3 * t + 1], ic = (long long)tris[3 * t + 2];
+    a = (int)ia; b = (int)ib; c = (int)ic;
+    return ia >= 0 && ia < nv && ib >= 0 && ib < nv && ic >= 0 && ic < nv;
+}
+
+__global__ __launch_bounds__(256) void k_adj_init(int* __restrict__ cap, int nv, AdjTotals* __restrict__ tot) {
+    const long long v = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (v == 0) *tot = AdjTotals{0ll, 0ll, 0ull, 0};
+    if (v < nv) cap[v] = 0;
+}
+
+// cap[v] = raw entries of row v
+template <typename IDX>
+__global__ __launch_bounds__(256) void k_adj_capacity(const IDX* __restrict__ tris, long long nt, int nv, int* __restrict__ cap, AdjTotals* __restrict__ tot) {
+    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= nt) return;
+    int a, b, c;
+    if (!adj_triangle(tris, t, nv, a, b, c)) { atomicAdd(&tot->n_bad, 1ull); return; }
+    const int na = (a != b) + (a != c), nb = (b != a) + (b != c), nc = (c != a) + (c != b);
+    if (na) atomicAdd(cap + a, na);
+    if (nb) atomicAdd(cap + b, nb);
+    if (nc) atomicAdd(cap + c, nc);
+}
+
+// sum of a[] per tile of ADJ_TILE -> block_total[blockIdx.x]
+__global__ __launch_bounds__(256) void k_adj_tile_sum(const int* __restrict__ a, long long n, int* __restrict__ block_total) {
+    __shared__ int lds[5];
+    const long long i0 = (long long)blockIdx.x * ADJ_TILE + threadIdx.x;
+    int s = 0;
+#pragma unroll
+    for (int k = 0; k < ADJ_ITEMS; ++k) s += (i0 + k * 256 < n) ? a[i0 + k * 256] : 0;
+    int total;
+    (void)block_scan_excl(s, lds, total);
+    if (threadIdx.x == 0) block_total[blockIdx.x] = total;
+}
+
+// out[i] (and out2[i]) = exclusive scan of a[] (block_base: the exclusive scan of block_total)
+__global__ __launch_bounds__(256) void k_adj_tile_scan(const int* __restrict__ a, long long n, const int* __restrict__ block_base, int* __restrict__ out,
+                                                       int* __restrict__ out2) {
+    __shared__ int lds[5];
+    const long long i0 = (long long)blockIdx.x * ADJ_TILE + threadIdx.x;
+    int run = block_base[blockIdx.x];
+#pragma unroll
+    for (int k = 0; k < ADJ_ITEMS; ++k) {
+        const long long i = i0 + k * 256;
+        const int x = i < n ? a[i] : 0;
+        int total;
+        const int at = run + block_scan_excl(x, lds, total);
+        if (i < n) {
+            out[i] = at;
+            if (out2) out2[i] = at;
+        }
+        run += total;
+    }
+}
+
+// every corner claims the slots of its (at most two) pairs with one atomic; cursor[v] starts at the row's first slot and ends behind its last
+template <typename IDX>
+__global__ __launch_bounds__(256) void k_adj_fill(const IDX* __restrict__ tris, long long nt, int nv, int* __restrict__ cursor, int* __restrict__ raw) {
+    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= nt) return;
+    int a, b, c;
+    if (!adj_triangle(tris, t, nv, a, b, c)) return;
+    const int na = (a != b) + (a != c), nb = (b != a) + (b != c), nc = (c != a) + (c != b);      // as k_adj_capacity counted them
+    if (na) { int s = atomicAdd(cursor + a, na); if (a != b) raw[s++] = b; if (a != c) raw[s] = c; }
+    if (nb) { int s = atomicAdd(cursor + b, nb); if (b != c) raw[s++] = c; if (b != a) raw[s] = a; }
+    if (nc) { int s = atomicAdd(cursor + c, nc); if (c != a) raw[s++] = a; if (c != b) raw[s] = b; }
+}
+
+__device__ __forceinline__ void adj_cmpswap(int& x, int& y) {
+    const int lo = min(x, y), hi = max(x, y);
+    x = lo; y = hi;
+}
+
+// bitonic network over N registers, ascending (every index is a compile-time constant after unrolling)
+template <int N>
+__device__ __forceinline__ void adj_sort_regs(int (&r)[N]) {
+#pragma unroll
+    for (int k = 2; k <= N; k <<= 1) {
+#pragma unroll
+        for (int j = k >> 1; j > 0; j >>= 1) {
+#pragma unroll
+            for (int i = 0; i < N; ++i) {
+                const int l = i ^ j;
+                if (l > i) {
+                    if ((i & k) == 0) adj_cmpswap(r[i], r[l]);
+                    else adj_cmpswap(r[l], r[i]);
+                }
+            }
+        }
+    }
+}
+
+// a row of at most N raw entries: sorted, duplicates collapsed, written back to the head of its own raw segment -> degree; boundary flag by reference
+template <int N>
+__device__ __forceinline__ int adj_short_row(int* __restrict__ row, int d, int& boundary) {
+    int r[N];
+#pragma unroll
+    for (int k = 0; k < N; ++k) r[k] = k < d ? row[k] : ADJ_PAD;
+    adj_sort_regs<N>(r);
+    int deg = 0, bnd = 0;
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+        const bool valid = r[k] != ADJ_PAD;
+        const bool first = k == 0 || r[k] != r[k - 1];
+        const bool last = k == N - 1 || r[k] != r[k + 1];
+        if (valid && first) {
+            row[deg++] = r[k];
+            bnd |= last ? 1 : 0;
+        }
+    }
+    boundary = bnd;
+    return deg;
+}
+
+// one thread per vertex: short rows are finished here (cap[v] becomes the degree), long ones are listed
+__global__ __launch_bounds__(256) void k_adj_rows(int nv, const int* __restrict__ rawoff, int* __restrict__ cap, int* __restrict__ raw, unsigned char* __restrict__ bnd,
+                                                  int* __restrict__ long_list, AdjTotals* __restrict__ tot) {
+    const long long v = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (v >= nv) return;
+    const int d = cap[v];
+    if (d > ADJ_SHORT) { long_list[atomicAdd(&tot->n_long, 1)] = (int)v; return; }
+    int b = 0, deg = 0;
+    if (d > 16) deg = adj_short_row<ADJ_SHORT>(raw + rawoff[v], d, b);
+    else if (d > 0) deg = adj_short_row<16>(raw + rawoff[v], d, b);
+    cap[v] = deg;
+    bnd[v] = (unsigned char)b;
+}
+
+// one block per listed row: rank sort into tmp (position = entries that are smaller + equal entries in front), then heads of runs compacted back into
+// the row's own raw segment in order.  O(d^2 / 256) comparisons per thread.
+__global__ __launch_bounds__(256) void k_adj_long_rows(const int* __restrict__ rawoff, const int* __restrict__ cursor, int* __restrict__ cap, int* __restrict__ raw,
+                                                       int* __restrict__ tmp, unsigned char* __restrict__ bnd, const int* __restrict__ long_list,
+                                                       const AdjTotals* __restrict__ tot) {
+    __shared__ int lds[5];
+    __shared__ int any_single;
+    const int n_long = tot->n_long;
+    for (int r = blockIdx.x; r < n_long; r += gridDim.x) {
+        const int v = long_list[r];
+        const int base = rawoff[v], d = cursor[v] - base;
+        int* row = raw + base;
+        int* srt = tmp + base;
+        if (threadIdx.x == 0) any_single = 0;
+        for (int i = threadIdx.x; i < d; i += 256) {
+            const int x = row[i];
+            int pos = 0;
+            for (int j = 0; j < d; ++j) {
+                const int y = row[j];
+                pos += (y < x || (y == x && j < i)) ? 1 : 0;
+            }
+            srt[pos] = x;
+        }
+        __syncthreads();                                            // srt complete (this block wrote all of it); row is free from here on
+        int run = 0;
+        for (int k0 = 0; k0 < d; k0 += 256) {                       // uniform trip count: block_scan_excl synchronises
+            const int k = k0 + threadIdx.x;
+            const int x = k < d ? srt[k] : ADJ_PAD;
+            const bool first = k < d && (k == 0 || srt[k - 1] != x);
+            const bool last = k < d && (k == d - 1 || srt[k + 1] != x);
+            int total;
+            const int at = run + block_scan_excl(first ? 1 : 0, lds, total);
+            if (first) row[at] = x;
+            if (first && last) any_single = 1;
+            run += total;
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) { cap[v] = run; bnd[v] = (unsigned char)(any_single ? 1 : 0); }
+        __syncthreads();                                            // any_single is reset by the next row
+    }
+}
+
+// CSR out: one thread per vertex copies its row unless the row is on the long list (raw count above ADJ_SHORT); the ADJ_LONG_GRID blocks behind the
+// vertex blocks copy the listed rows, one block per row (an empty list costs them one load)
+__global__ __launch_bounds__(256) void k_adj_emit(int nv, unsigned vertex_blocks, const int* __restrict__ rawoff, const int* __restrict__ cursor,
+                                                  const int* __restrict__ deg, const int* __restrict__ off, const int* __restrict__ raw,
+                                                  const unsigned char* __restrict__ bnd, const int* __restrict__ long_list, const AdjTotals* __restrict__ tot,
+                                                  int* __restrict__ offsets, int* __restrict__ neighbours, unsigned char* __restrict__ boundary) {
+    if (blockIdx.x >= vertex_blocks) {
+        const int n_long = tot->n_long;
+        for (int r = blockIdx.x - vertex_blocks; r < n_long; r += gridDim.x - vertex_blocks) {
+            const int v = long_list[r];
+            const int d = deg[v], o = off[v], base = rawoff[v];
+            for (int k = threadIdx.x; k < d; k += 256) neighbours[o + k] = raw[base + k];
+        }
+        return;
+    }
+    const long long v = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (v == nv) offsets[nv] = (int)tot->n_entries;
+    if (v >= nv) return;
+    const int o = off[v], base = rawoff[v];
+    offsets[v] = o;
+    boundary[v] = bnd[v];
+    if (cursor[v] - base > ADJ_SHORT) return;
+    const int d = deg[v];
+    for (int k = 0; k < d; ++k) neighbours[o + k] = raw[base + k];
+}
+
+// one Jacobi step with factor f, one thread per vertex; -ffp-contract=off (build.py) and the explicit _rn forms keep multiply and add apart
+__global__ __launch_bounds__(256) void k_smooth_step(const double* __restrict__ pin, double* __restrict__ pout, int nv, const int* __restrict__ offsets,
+                                                     const int* __restrict__ neighbours, const unsigned char* __restrict__ boundary, double f) {
+    const long long v = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (v >= nv) return;
+    const int lo = offsets[v], hi = offsets[v + 1];
+    const double px = pin[3 * v], py = pin[3 * v + 1], pz = pin[3 * v + 2];
+    double ox = px, oy = py, oz = pz;
+    if (hi > lo && !(boundary && boundary[v])) {
+        double ax = 0.0, ay = 0.0, az = 0.0;
+        for (int k = lo; k < hi; ++k) {
+            const long long u = neighbours[k];
+            ax = __dadd_rn(ax, pin[3 * u]);
+            ay = __dadd_rn(ay, pin[3 * u + 1]);
+            az = __dadd_rn(az, pin[3 * u + 2]);
+        }
+        const double deg = (double)(hi - lo);
+        ox = __dadd_rn(px, __dmul_rn(f, __dsub_rn(__ddiv_rn(ax, deg), px)));
+        oy = __dadd_rn(py, __dmul_rn(f, __dsub_rn(__ddiv_rn(ay, deg), py)));
+        oz = __dadd_rn(pz, __dmul_rn(f, __dsub_rn(__ddiv_rn(az, deg), pz)));
+    }
+    pout[3 * v] = ox; pout[3 * v + 1] = oy; pout[3 * v + 2] = oz;
+}
+
+struct AdjCarve {
+    AdjTotals* tot;
+    int *cap, *rawoff, *cursor, *off, *long_list, *vblock, *raw, *tmp;
+    unsigned char* bnd;
+    unsigned nbv;
+};
+
+static size_t adj_pad(size_t bytes) { return (bytes + 15) / 16 * 16; }
+
+// everything pass 2 reads lies in front of the one nt-sized buffer it needs (raw), so the layout up to there depends on nv alone
+static AdjCarve adj_carve(void* ws, long long nv, long long nt) {
+    AdjCarve c;
+    c.nbv = cdiv(nv, ADJ_TILE);
+    const size_t vb = adj_pad((size_t)nv * sizeof(int));
+    char* p = (char*)ws;
+    c.tot = (AdjTotals*)p; p += 64;
+    c.cap = (int*)p; p += vb;                       // raw entries per row, then the degree
+    c.rawoff = (int*)p; p += vb;
+    c.cursor = (int*)p; p += vb;
+    c.off = (int*)p; p += vb;                       // exclusive scan of the degrees
+    c.long_list = (int*)p; p += vb;
+    c.vblock = (int*)p; p += adj_pad((size_t)c.nbv * sizeof(int));
+    c.bnd = (unsigned char*)p; p += adj_pad((size_t)nv);
+    c.raw = (int*)p; p += adj_pad((size_t)nt * 6 * sizeof(int));
+    c.tmp = (int*)p;                                // long rows only
+    return c;
+}
+
+static_assert(sizeof(AdjTotals) <= 64, "AdjTotals must fit the workspace head");
+
+static bool adj_sizes_ok(long long nv, long long nt) { return nv >= 0 && nt >= 0 && nv < (1ll << 30) && nt < (1ll << 31) && 6 * nt < (1ll << 31); }
+
+}  // namespace o2345
+
+using namespace o2345;
+
+extern "C" {
+
+size_t o2345_mesh_adjacency_workspace_bytes(long long nv, long long nt) {
+    if (!adj_sizes_ok(nv, nt)) return 0;
+    return 64 + 5 * adj_pad((size_t)nv * sizeof(int)) + adj_pad((size_t)cdiv(nv, ADJ_TILE) * sizeof(int)) + 2 * adj_pad((size_t)nt * 6 * sizeof(int)) +
+           adj_pad((size_t)nv);
+}
+
+// Pass 1 of the two-call protocol: the whole build into the workspace; returns the number of CSR entries on the HOST (synchronises the stream once --
+// the caller must allocate `neighbours`).
+int o2345_mesh_adjacency_count(const void* tris, int index_bytes, long long nv, long long nt, void* workspace, size_t workspace_bytes, long long* n_entries_host,
+                               void* stream) {
+    O2345_REQUIRE(index_bytes == 4 || index_bytes == 8, "mesh_adjacency_count: index_bytes must be 4 or 8");
+    O2345_REQUIRE(adj_sizes_ok(nv, nt), "mesh_adjacency_count: bad sizes (nv must stay below 2^30 and 6 * nt below 2^31)");
+    O2345_REQUIRE(n_entries_host && workspace && (nt == 0 || tris), "mesh_adjacency_count: null pointer");
+    O2345_REQUIRE(workspace_bytes >= o2345_mesh_adjacency_workspace_bytes(nv, nt), "mesh_adjacency_count: workspace too small");
+    O2345_REQUIRE(((uintptr_t)workspace & 15) == 0, "mesh_adjacency_count: workspace must be 16-byte aligned");
+    const AdjCarve c = adj_carve(workspace, nv, nt);
+    hipStream_t s = (hipStream_t)stream;
+    const int n = (int)nv;
+    const unsigned gv = cdiv(nv > 0 ? nv : 1, 256), gt = cdiv(nt, 256);
+    hipLaunchKernelGGL(k_adj_init, dim3(gv), dim3(256), 0, s, c.cap, n, c.tot);
+    if (nv > 0) {
+        if (nt > 0) {
+            if (index_bytes == 4) hipLaunchKernelGGL(k_adj_capacity<int>, dim3(gt), dim3(256), 0, s, (const int*)tris, nt, n, c.cap, c.tot);
+            else hipLaunchKernelGGL(k_adj_capacity<long long>, dim3(gt), dim3(256), 0, s, (const long long*)tris, nt, n, c.cap, c.tot);
+        }
+        hipLaunchKernelGGL(k_adj_tile_sum, dim3(c.nbv), dim3(256), 0, s, c.cap, nv, c.vblock);
+        hipLaunchKernelGGL(k_scan_small<long long>, dim3(1), dim3(1024), 0, s, c.vblock, (int)c.nbv, &c.tot->n_raw);
+        hipLaunchKernelGGL(k_adj_tile_scan, dim3(c.nbv), dim3(256), 0, s, c.cap, nv, c.vblock, c.rawoff, c.cursor);
+        if (nt > 0) {
+            if (index_bytes == 4) hipLaunchKernelGGL(k_adj_fill<int>, dim3(gt), dim3(256), 0, s, (const int*)tris, nt, n, c.cursor, c.raw);
+            else hipLaunchKernelGGL(k_adj_fill<long long>, dim3(gt), dim3(256), 0, s, (const long long*)tris, nt, n, c.cursor, c.raw);
+        }
+        hipLaunchKernelGGL(k_adj_rows, dim3(gv), dim3(256), 0, s, n, c.rawoff, c.cap, c.raw, c.bnd, c.long_list, c.tot);
+        if (nt > 0) hipLaunchKernelGGL(k_adj_long_rows, dim3(ADJ_LONG_GRID), dim3(256), 0, s, c.rawoff, c.cursor, c.cap, c.raw, c.tmp, c.bnd, c.long_list, c.tot);
+        hipLaunchKernelGGL(k_adj_tile_sum, dim3(c.nbv), dim3(256), 0, s, c.cap, nv, c.vblock);
+        hipLaunchKernelGGL(k_scan_small<long long>, dim3(1), dim3(1024), 0, s, c.vblock, (int)c.nbv, &c.tot->n_entries);
+        hipLaunchKernelGGL(k_adj_tile_scan, dim3(c.nbv), dim3(256), 0, s, c.cap, nv, c.vblock, c.off, (int*)nullptr);
+    } else if (nt > 0) {                                            // no vertex: every triangle is out of range
+        if (index_bytes == 4) hipLaunchKernelGGL(k_adj_capacity<int>, dim3(gt), dim3(256), 0, s, (const int*)tris, nt, n, c.cap, c.tot);
+        else hipLaunchKernelGGL(k_adj_capacity<long long>, dim3(gt), dim3(256), 0, s, (const long long*)tris, nt, n, c.cap, c.tot);
+    }
+    int rc = check_launch("mesh_adjacency_count");
+    if (rc) return rc;
+    AdjTotals h;
+    hipError_t e = hipMemcpyAsync(&h, c.tot, sizeof h, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    O2345_REQUIRE(e == hipSuccess, "mesh_adjacency_count: %s", hipGetErrorString(e));
+    O2345_REQUIRE(h.n_bad == 0, "mesh_adjacency_count: %llu triangles index outside 0 .. %lld", h.n_bad, nv - 1);
+    *n_entries_host = h.n_entries;
+    return 0;
+}
+
+// Pass 2: offsets int32 [nv + 1], neighbours int32 [n_entries], boundary uint8 [nv], from the workspace of pass 1 (same nv, untouched in between).
+// neighbours may be NULL when the table is empty.
+int o2345_mesh_adjacency_emit(void* workspace, long long nv, int* offsets, int* neighbours, unsigned char* boundary, void* stream) {
+    O2345_REQUIRE(nv >= 0 && nv < (1ll << 30), "mesh_adjacency_emit: bad sizes");
+    O2345_REQUIRE(workspace && offsets && (nv == 0 || boundary), "mesh_adjacency_emit: null pointer");
+    const AdjCarve c = adj_carve(workspace, nv, 0);
+    const unsigned vertex_blocks = cdiv(nv + 1, 256);
+    hipLaunchKernelGGL(k_adj_emit, dim3(vertex_blocks + ADJ_LONG_GRID), dim3(256), 0, (hipStream_t)stream, (int)nv, vertex_blocks, c.rawoff, c.cursor, c.cap, c.off, c.raw,
+                       c.bnd, c.long_list, c.tot, offsets, neighbours, boundary);
+    return check_launch("mesh_adjacency_emit");
+}
+
+// `iterations` times step(lam) [, step(mu) unless mu == 0], ping-pong between verts_tmp and verts_out so that the last step writes verts_out;
+// verts_in is only read.  iterations == 0 copies.  verts_tmp may be NULL when there is a single step or none.
+int o2345_mesh_smooth(const double* verts_in, long long nv, const int* offsets, const int* neighbours, const unsigned char* boundary_or_null, int iterations,
+                      double lam, double mu, double* verts_tmp, double* verts_out, void* stream) {
+    O2345_REQUIRE(nv >= 0 && nv < (1ll << 30), "mesh_smooth: bad sizes (nv must stay below 2^30)");
+    O2345_REQUIRE(iterations >= 0, "mesh_smooth: iterations must be >= 0, got %d", iterations);
+    O2345_REQUIRE(lam > 0.0 && lam <= 1.0 && mu <= 0.0 && mu >= -1.7976931348623157e308, "mesh_smooth: need 0 < lam <= 1 and finite mu <= 0, got %g, %g", lam, mu);
+    const long long steps = (long long)iterations * (mu != 0.0 ? 2 : 1);
+    O2345_REQUIRE(nv == 0 || (verts_in && verts_out && offsets && (steps < 2 || verts_tmp)), "mesh_smooth: null pointer");
+    if (nv == 0) return 0;
+    O2345_REQUIRE(verts_out != verts_in && verts_tmp != verts_in && verts_tmp != verts_out, "mesh_smooth: verts_in, verts_tmp and verts_out must differ");
+    hipStream_t s = (hipStream_t)stream;
+    if (steps == 0) {
+        O2345_HIP(hipMemcpyAsync(verts_out, verts_in, (size_t)nv * 3 * sizeof(double), hipMemcpyDeviceToDevice, s));
+        return 0;
+    }
+    const double* src = verts_in;
+    for (long long i = 0; i < steps; ++i) {
+        double* dst = ((steps - 1 - i) & 1) ? verts_tmp : verts_out;
+        const double f = (mu != 0.0 && (i & 1)) ? mu : lam;
+        hipLaunchKernelGGL(k_smooth_step, dim3(cdiv(nv, 256)), dim3(256), 0, s, src, dst, (int)nv, offsets, neighbours, boundary_or_null, f);
+        src = dst;
+    }
+    return check_launch("mesh_smooth");
+}
+
+}  // extern "C"
+
+// o2345_preload (csrc/api.cpp): querying one kernel makes the HIP runtime load this translation unit's code object on the current device
+namespace o2345 {
+int preload_mesh_smooth() {
+    hipFuncAttributes at;
+    return (int)hipFuncGetAttributes(&at, (const void*)k_smooth_step);
+}
+}  // namespace o2345

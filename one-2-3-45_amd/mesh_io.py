@@ -12,7 +12,8 @@ Wavefront OBJ (``.obj``) in the asset frame -- (x, y, z) -> (x, z, y), z-up -> g
 x flip compose to exactly that.  ``write_glb`` / ``write_obj`` / ``read_glb`` / ``read_obj`` / ``convert_mesh`` are the host layer (numpy, no GPU) and the
 DEFINITION of the two files; ``export_asset`` is the device path (csrc/mesh_export.hip): buffers and OBJ text are produced on the device, one D2H copy
 per buffer, one file write.  ``component_labels`` / ``filter_components`` are the host twin (and definition) of the device component filter
-(csrc/mesh_components.hip).  No byte parity with trimesh's own OBJ / GLB writers is claimed (trimesh is not available to compare against)."""
+(csrc/mesh_components.hip); ``vertex_adjacency`` / ``smooth_vertices`` are the host twin (and definition) of the device adjacency table and Taubin
+smoothing (csrc/mesh_smooth.hip).  No byte parity with trimesh's own OBJ / GLB writers is claimed (trimesh is not available to compare against)."""
 import json
 import os
 import struct
@@ -406,16 +407,100 @@ def filter_components(verts, faces, colors=None, normals=None, min_faces=0, keep
     return v[kept], f_out, take(colors), take(normals), kept, {"components": n_comp, "components_kept": int(np.count_nonzero(good))}
 
 
-def convert_mesh(ply_path, out_path, min_component_faces=0, keep_largest=False):
+# ------------------------------------------------------------------------------------------------------------------ adjacency and smoothing
+def vertex_adjacency(faces, n_vertices):
+    """Vertex -> neighbours table of an indexed triangle mesh in CSR form: (offsets int32 [n + 1], neighbours int32 [E], boundary uint8 [n]).  The host twin of
+    ops.mesh_vertex_adjacency and the DEFINITION of its result.  Every triangle (a, b, c) contributes the ordered pairs (a,b), (b,a), (b,c), (c,b), (c,a),
+    (a,c), minus those with equal ends; row v holds the distinct second elements of the pairs that start at v, ascending; the multiplicity of u in row v
+    (the number of such pairs) is the number of triangles on edge {u, v}, and ``boundary[v] = 1`` iff some entry of row v has multiplicity exactly 1.  A
+    vertex no triangle references has an empty row and boundary 0.  Independent of face order and of the rotation of a triangle's indices."""
+    n = int(n_vertices)
+    f = np.asarray(faces).reshape(-1, 3).astype(np.int64, copy=False)
+    if n < 0 or n >= 2 ** 30 or 6 * f.shape[0] >= 2 ** 31:
+        raise ValueError(f"vertex_adjacency: bad sizes ({n} vertices, {f.shape[0]} faces; the table is int32)")
+    if f.size and (f.min() < 0 or f.max() >= n):
+        raise ValueError(f"faces index outside 0 .. {n - 1}")
+    a, b, c = f[:, 0], f[:, 1], f[:, 2]
+    src, dst = np.concatenate([a, b, b, c, c, a]), np.concatenate([b, a, c, b, a, c])
+    proper = src != dst
+    pairs, mult = np.unique(src[proper] * max(n, 1) + dst[proper], return_counts=True)      # sorted by (first, second): the rows in order, ascending inside
+    first, second = pairs // max(n, 1), pairs % max(n, 1)
+    offsets = np.zeros(n + 1, np.int32)
+    offsets[1:] = np.cumsum(np.bincount(first, minlength=n))
+    boundary = np.zeros(n, np.uint8)
+    boundary[first[mult == 1]] = 1
+    return offsets, second.astype(np.int32), boundary
+
+
+def _check_smooth_args(iterations, lam, mu):
+    if isinstance(iterations, (bool, np.bool_)) or not isinstance(iterations, (int, np.integer)) or iterations < 0:
+        raise ValueError(f"smooth: iterations must be a non-negative integer, got {iterations!r}")
+    lam, mu = float(lam), float(mu)
+    if not (np.isfinite(lam) and 0.0 < lam <= 1.0):
+        raise ValueError(f"smooth: lam must be in (0, 1], got {lam!r}")
+    if not (np.isfinite(mu) and mu <= 0.0):
+        raise ValueError(f"smooth: mu must be finite and <= 0, got {mu!r}")
+    return int(iterations), lam, mu
+
+
+def smooth_vertices(verts, faces, iterations, lam=0.5, mu=-0.53, pin_boundary=True):
+    """Taubin's lambda|mu smoothing of the vertex positions (host twin of ops.mesh_smooth, and the definition of its result, to the last bit) -> float64 [N,3].
+    ``iterations`` times: one step with factor ``lam``, then one with ``mu`` unless ``mu == 0`` (plain Laplacian smoothing, which shrinks the shape).
+    One step with factor f, every vertex from the OLD positions, in float64: acc = 0; acc = acc + p[u] over the neighbours u of v in ascending order (one
+    sequential sum per coordinate); m = acc / deg; d = m - p[v]; p'[v] = p[v] + f * d, multiply and add apart.  A vertex without neighbours, or a boundary
+    vertex (vertex_adjacency) while ``pin_boundary`` is on, keeps its value bit for bit: the rim of a mesh cut open by the volume's faces stays where it
+    is.  The adjacency is built once; faces and vertex count never change.  ``iterations == 0`` returns ``verts`` itself."""
+    iterations, lam, mu = _check_smooth_args(iterations, lam, mu)
+    if iterations == 0:
+        return verts
+    p = np.array(verts, dtype=np.float64).reshape(-1, 3)               # a copy: the input is never written
+    n = p.shape[0]
+    offsets, nbr, boundary = vertex_adjacency(faces, n)
+    off = offsets.astype(np.int64)
+    deg = off[1:] - off[:-1]
+    moving = np.flatnonzero((deg > 0) & ((boundary == 0) | (not pin_boundary)))
+    if moving.size == 0:
+        return p
+    # the sum is sequential over the neighbour RANK k = 0 .. max degree - 1, vectorised over the rows that have a k-th entry: with the moving rows sorted
+    # by falling degree those are a prefix (np.add.reduceat / sum(axis) would add in numpy's own pairwise order, which is not the definition)
+    rows = moving[np.argsort(-deg[moving], kind="stable")]
+    rdeg, start = deg[rows], off[rows]
+    have = np.searchsorted(-rdeg, -np.arange(int(rdeg[0])), side="left")         # rows with degree > k = the first have[k] of them
+    divisor = rdeg.astype(np.float64)[:, None]
+
+    def step(p, f):
+        acc = np.zeros((rows.size, 3), np.float64)
+        for k, m in enumerate(have):
+            acc[:m] = acc[:m] + p[nbr[start[:m] + k]]
+        mean = acc / divisor
+        d = mean - p[rows]
+        fd = f * d
+        out = p.copy()
+        out[rows] = p[rows] + fd
+        return out
+
+    for _ in range(iterations):
+        p = step(p, lam)
+        if mu != 0.0:
+            p = step(p, mu)
+    return p
+
+
+def convert_mesh(ply_path, out_path, min_component_faces=0, keep_largest=False, smooth_iterations=0):
     """convert_mesh_format (utils/utils.py:31-47) for a mesh already on disk: read the PLY, exchange y and z, reverse the faces, write ``out_path`` by its
     extension (.glb or .obj) with the PLY's vertex colours.  ``min_component_faces`` / ``keep_largest``: filter_components on the way (off by default).
-    Returns ``out_path``."""
+    ``smooth_iterations`` (0 = off): smooth_vertices with its default factors and pinning, after the filter, on the file's float32 positions cast to
+    float64, the result cast back to float32.  That is NOT byte-equal to the device export with the same count, which smooths the float64 index
+    coordinates before the frame transform rounds them to float32.  Returns ``out_path``."""
     ext = _asset_ext(out_path)
     if ext == ".ply":
         raise ValueError("convert_mesh: the output is .glb or .obj")
+    smooth_iterations = _check_smooth_args(smooth_iterations, 0.5, -0.53)[0]
     v, f, c = read_ply(ply_path)
     if min_component_faces or keep_largest:
         v, f, c, _, _, _ = filter_components(v, f, c, None, min_component_faces, keep_largest)
+    if smooth_iterations:
+        v = smooth_vertices(v.astype(np.float64), f, smooth_iterations).astype(np.float32)
     v, f = to_asset_frame(v, f)
     (write_glb if ext == ".glb" else write_obj)(out_path, v, f, c)
     return out_path

@@ -924,3 +924,46 @@ def mesh_filter_components(verts_idx, tris, min_faces=0, keep_largest=False):
                                                 _p(ws, torch.uint8), _p(verts, torch.float64), _p(tris_out, tris.dtype), _p(kept, torch.int32), _stream()),
           "mesh_components_emit")
     return verts, tris_out, kept, {"components": nc, "components_kept": nck}
+
+
+# ---------------------------------------------------------------------------------------------------------- mesh adjacency and smoothing
+@_on_device
+def mesh_vertex_adjacency(tris, n_vertices):
+    """tris [M,3] int32 / int64 on the device -> (offsets int32 [n + 1], neighbours int32 [E], boundary uint8 [n]): the vertex -> neighbours table in CSR
+    form, rows ascending, and the flag of the vertices on an edge with one triangle (== mesh_io.vertex_adjacency, exactly; definitions in
+    csrc/mesh_smooth.hip)."""
+    if tris.dtype not in (torch.int32, torch.int64) or tris.dim() != 2 or tris.shape[1] != 3:
+        raise ValueError(f"expected triangles [M,3] int32 or int64, got {tuple(tris.shape)} {tris.dtype}")
+    L = _lib.lib()
+    nv, nt, dev = int(n_vertices), tris.shape[0], tris.device
+    wsb = L.o2345_mesh_adjacency_workspace_bytes(nv, nt)
+    ws = _workspace(wsb, dev, "mesh_adjacency")
+    ne = ctypes.c_longlong()
+    check(L.o2345_mesh_adjacency_count(_p(tris, tris.dtype), 8 if tris.dtype == torch.int64 else 4, nv, nt, _p(ws, torch.uint8), wsb, ctypes.byref(ne), _stream()),
+          "mesh_adjacency_count")
+    offsets = torch.empty(nv + 1, dtype=torch.int32, device=dev)
+    neighbours = torch.empty(ne.value, dtype=torch.int32, device=dev)
+    boundary = torch.empty(nv, dtype=torch.uint8, device=dev)
+    check(L.o2345_mesh_adjacency_emit(_p(ws, torch.uint8), nv, _p(offsets, torch.int32), _p(neighbours, torch.int32), _p(boundary, torch.uint8), _stream()),
+          "mesh_adjacency_emit")
+    return offsets, neighbours, boundary
+
+
+@_on_device
+def mesh_smooth(verts_idx, tris, iterations, lam=None, mu=None, pin_boundary=None):
+    """Taubin's lambda|mu smoothing of a mesh's vertex positions on the device (== mesh_io.smooth_vertices, to the last bit; definitions in
+    csrc/mesh_smooth.hip).  verts_idx fp64 [N,3], tris [M,3] int32 / int64 -> a new fp64 [N,3] tensor; the input is not written.  ``lam`` / ``mu`` /
+    ``pin_boundary``: None = the config default (0.5, -0.53, pinned).  With ``iterations == 0`` nothing is launched and ``verts_idx`` itself is returned."""
+    iterations = config.mesh_smooth_iterations(iterations)
+    lam, mu, pin = config.mesh_smooth_lambda(lam), config.mesh_smooth_mu(mu), config.mesh_smooth_pin_boundary(pin_boundary)
+    if iterations == 0:
+        return verts_idx
+    if iterations >= 2 ** 30:
+        raise ValueError(f"mesh_smooth: {iterations} iterations")
+    nv = verts_idx.shape[0]
+    offsets, neighbours, boundary = mesh_vertex_adjacency(tris, nv)
+    out = torch.empty(nv, 3, dtype=torch.float64, device=verts_idx.device)
+    tmp = _workspace(24 * nv, verts_idx.device, "mesh_smooth")
+    check(_lib.lib().o2345_mesh_smooth(_p(verts_idx, torch.float64), nv, _p(offsets, torch.int32), _p(neighbours, torch.int32), _p(boundary, torch.uint8) if pin else None,
+                                       iterations, lam, mu, _p(tmp, torch.uint8), _p(out, torch.float64), _stream()), "mesh_smooth")
+    return out

@@ -1,0 +1,281 @@
+"""Vertex adjacency and Taubin smoothing on the CPU: the host twin (mesh_io.vertex_adjacency / smooth_vertices / convert_mesh's smoothing), which DEFINES
+what the device kernels (csrc/mesh_smooth.hip, tests/test_gpu_mesh_smooth.py) must return, plus the C ABI's declarations and the four config knobs.
+
+Row v of the table = the distinct neighbours of v, ascending; boundary[v] = v lies on an edge with exactly one triangle.  One smoothing step moves every
+vertex by f times (mean of its neighbours - itself), all from the old positions; an iteration is a step with lam and one with mu."""
+import ctypes
+import importlib
+import importlib.util
+import os
+
+import numpy as np
+import pytest
+
+import mesh_components_util as mcu
+import mesh_smooth_util as msu
+
+mio = importlib.import_module("one-2-3-45_amd.mesh_io")
+HERE = os.path.dirname(os.path.abspath(__file__))
+GOLDEN = os.path.join(HERE, "golden", "mc_skimage.npz")
+
+
+def _rows(adj):
+    off, nbr, _ = adj
+    return [nbr[off[v]:off[v + 1]].tolist() for v in range(len(off) - 1)]
+
+
+def _same(a, b):
+    return all(x.dtype == y.dtype and x.shape == y.shape and x.tobytes() == y.tobytes() for x, y in zip(a, b))
+
+
+def test_adjacency_of_a_hand_made_mesh():
+    """two triangles sharing edge {1, 2}, a degenerate one, vertices 4 and 6 unreferenced"""
+    f = np.array([[0, 1, 2], [2, 1, 3], [5, 5, 3]], np.int64)
+    off, nbr, bnd = mio.vertex_adjacency(f, 7)
+    assert off.dtype == np.int32 and nbr.dtype == np.int32 and bnd.dtype == np.uint8 and off.shape == (8,) and bnd.shape == (7,)
+    assert _rows((off, nbr, bnd)) == [[1, 2], [0, 2, 3], [0, 1, 3], [1, 2, 5], [], [3], []]
+    # {1,2} has two triangles, every other proper edge one; (5,5,3) contributes (5,3) and (3,5) twice each, so that edge counts two
+    assert bnd.tolist() == [1, 1, 1, 1, 0, 0, 0]
+    assert int(off[-1]) == len(nbr) == 12
+
+
+def test_adjacency_does_not_depend_on_face_order_or_index_rotation():
+    d = np.load(GOLDEN)
+    f, n = d["noise_cube:faces"], int(d["noise_cube:verts"].shape[0])
+    want = mio.vertex_adjacency(f, n)
+    rng = np.random.default_rng(11)
+    shuffled = f[rng.permutation(len(f))]
+    k = rng.integers(0, 3, len(f))
+    rotated = np.stack([shuffled[np.arange(len(f)), (k + j) % 3] for j in range(3)], 1)
+    assert not np.array_equal(rotated, f)
+    assert _same(mio.vertex_adjacency(shuffled, n), want) and _same(mio.vertex_adjacency(rotated, n), want)
+    assert _same(mio.vertex_adjacency(f.astype(np.int32), n), want)
+
+
+def test_adjacency_of_the_grid_patch():
+    n = 20
+    v, f, rim = msu.grid_patch(n)
+    off, nbr, bnd = mio.vertex_adjacency(f, n * n)
+    deg = np.diff(off)
+    assert int(bnd.sum()) == 4 * n - 4 == 76 and np.array_equal(bnd.astype(bool), rim)
+    assert int(deg.max()) == 6 and (deg[~rim] == 6).all() and int(deg.min()) == 2
+    assert all(r == sorted(set(r)) for r in _rows((off, nbr, bnd)))
+
+
+def test_closed_surfaces_have_no_boundary_vertex():
+    d = np.load(GOLDEN)
+    for name in ("torus", "two_spheres"):
+        f, n = d[name + ":faces"], int(d[name + ":verts"].shape[0])
+        off, nbr, bnd = mio.vertex_adjacency(f, n)
+        assert not bnd.any() and (np.diff(off) >= 3).all(), name
+        # symmetric: u in row v <=> v in row u
+        first = np.repeat(np.arange(n), np.diff(off))
+        assert np.array_equal(np.unique(first.astype(np.int64) * n + nbr), np.unique(nbr.astype(np.int64) * n + first)), name
+
+
+@pytest.mark.parametrize("nt", [1, 5, 300])
+def test_fan_and_disjoint_triangles(nt):
+    f, n = mcu.fan(nt)
+    off, nbr, bnd = mio.vertex_adjacency(f, n)
+    ref = np.zeros(n, bool)
+    ref[np.unique(f)] = True
+    deg = np.diff(off)
+    assert np.array_equal(bnd.astype(bool), ref) and (deg[~ref] == 0).all() and deg[3] == nt + 1          # unreferenced: empty row, not boundary
+    f, n = mcu.disjoint(nt)
+    off, nbr, bnd = mio.vertex_adjacency(f, n)
+    ref = np.zeros(n, bool)
+    ref[np.unique(f)] = True
+    deg = np.diff(off)
+    assert np.array_equal(bnd.astype(bool), ref) and (deg[ref] == 2).all() and (deg[~ref] == 0).all() and (~ref).sum() > 0
+
+
+def test_adjacency_edge_cases():
+    off, nbr, bnd = mio.vertex_adjacency(np.zeros((0, 3), np.int64), 4)
+    assert off.tolist() == [0] * 5 and nbr.shape == (0,) and bnd.tolist() == [0] * 4
+    off, nbr, bnd = mio.vertex_adjacency(np.zeros((0, 3), np.int64), 0)
+    assert off.tolist() == [0] and nbr.shape == (0,) and bnd.shape == (0,)
+    for bad in ([[0, 1, 4]], [[0, -1, 2]]):
+        with pytest.raises(ValueError, match="index outside"):
+            mio.vertex_adjacency(np.array(bad), 4)
+    for nt in (0, 1, 2, 7):
+        f, n = msu.bipyramid(nt)
+        off, nbr, bnd = mio.vertex_adjacency(f, n)
+        assert not bnd.any() and (nt < 3 or (off[1] - off[0] == nt and off[2] - off[1] == nt))
+
+
+def test_taubin_smooths_without_shrinking_and_the_laplacian_shrinks():
+    v, f = msu.noisy_icosphere()
+    assert v.shape == (2562, 3)
+    m0, s0 = msu.radial(v)
+    assert abs(s0 - 0.0197) < 0.0005
+    t = mio.smooth_vertices(v, f, 10)
+    m1, s1 = msu.radial(t)
+    assert t.dtype == np.float64 and t.shape == v.shape
+    assert s1 < 0.010 and abs(m1 - m0) < 0.002, (s1, m1 - m0)
+    lap = mio.smooth_vertices(v, f, 10, mu=0.0)
+    m2, s2 = msu.radial(lap)
+    assert abs(m2 - m0) > 0.010 and m2 < m0 and s2 < s0, (m2 - m0, s2)
+    # explicit defaults are the defaults
+    assert mio.smooth_vertices(v, f, 10, lam=0.5, mu=-0.53, pin_boundary=True).tobytes() == t.tobytes()
+
+
+def test_one_step_is_the_written_definition():
+    """a scalar loop that follows the definition word for word, against the vectorised twin, on a mesh with unequal valences"""
+    d = np.load(GOLDEN)
+    f, n = d["noise_cube:faces"], int(d["noise_cube:verts"].shape[0])
+    v = np.random.default_rng(4).normal(size=(n, 3)) * np.array([1.0, 1e-3, 1e3])
+    off, nbr, bnd = mio.vertex_adjacency(f, n)
+    assert bnd.any() and not bnd.all() and len(set(np.diff(off).tolist())) > 3
+    for pin, lam, mu, its in ((True, 0.5, -0.53, 2), (False, 1.0, 0.0, 3), (False, 0.3, -0.31, 1)):
+        p = v.copy()
+        for _ in range(its):
+            for fac in ((lam, mu) if mu != 0 else (lam,)):
+                q = p.copy()
+                for i in range(n):
+                    row = nbr[off[i]:off[i + 1]]
+                    if len(row) == 0 or (pin and bnd[i]):
+                        continue
+                    for c in range(3):
+                        acc = np.float64(0.0)
+                        for u_ in row:
+                            acc = acc + p[u_, c]
+                        dd = acc / np.float64(len(row)) - p[i, c]
+                        q[i, c] = p[i, c] + np.float64(fac) * dd
+                p = q
+        got = mio.smooth_vertices(v, f, its, lam=lam, mu=mu, pin_boundary=pin)
+        assert got.tobytes() == p.tobytes(), (pin, lam, mu, its)
+
+
+def test_pinning_keeps_the_rim():
+    n = 20
+    v0, f, rim = msu.grid_patch(n)
+    v = v0.copy()
+    v[:, 2] = 0.3 * np.random.default_rng(9).standard_normal(n * n)
+    pinned = mio.smooth_vertices(v, f, 10)
+    assert pinned[rim].tobytes() == v[rim].tobytes()
+    assert pinned[~rim, 2].std() < 0.5 * v[~rim, 2].std()
+    free = mio.smooth_vertices(v, f, 10, pin_boundary=False)
+    assert (free[rim] != v[rim]).any(axis=1).all()
+    # a fan is all rim: pinned, nothing moves
+    ff, fn = mcu.fan(9)
+    fv = np.random.default_rng(1).normal(size=(fn, 3))
+    assert mio.smooth_vertices(fv, ff, 3).tobytes() == fv.tobytes()
+    moved = mio.smooth_vertices(fv, ff, 3, pin_boundary=False)
+    ref = np.zeros(fn, bool)
+    ref[np.unique(ff)] = True
+    assert moved[~ref].tobytes() == fv[~ref].tobytes() and (moved[ref] != fv[ref]).any(axis=1).all()
+
+
+def test_smooth_argument_handling():
+    v, f, _ = msu.grid_patch(5)
+    assert mio.smooth_vertices(v, f, 0) is v
+    lst = v.tolist()
+    assert mio.smooth_vertices(lst, f, 0) is lst
+    before = v.tobytes()
+    out = mio.smooth_vertices(v, f, 2, pin_boundary=False)
+    assert out is not v and v.tobytes() == before                      # the shared input is read-only and stays as it is
+    assert mio.smooth_vertices(v.astype(np.float32), f, 1).dtype == np.float64
+    for kw in (dict(iterations=-1), dict(iterations=1.5), dict(iterations=True), dict(iterations="3"), dict(iterations=1, lam=0.0), dict(iterations=1, lam=1.01),
+               dict(iterations=1, lam=float("nan")), dict(iterations=1, mu=0.1), dict(iterations=1, mu=float("-inf")), dict(iterations=0, lam=2.0)):
+        with pytest.raises(ValueError):
+            mio.smooth_vertices(v, f, **kw)
+    with pytest.raises(ValueError, match="index outside"):
+        mio.smooth_vertices(v, np.array([[0, 1, 25]]), 1)
+
+
+@pytest.mark.parametrize("ext", [".glb", ".obj"])
+def test_convert_mesh_with_smoothing_is_filter_then_twin_then_writer(tmp_path, ext):
+    d = np.load(GOLDEN)
+    v, f = d["noise_cube:verts"].astype(np.float32), d["noise_cube:faces"]
+    c = np.random.default_rng(2).integers(0, 256, (v.shape[0], 4)).astype(np.uint8)
+    c[:, 3] = 255
+    ply = str(tmp_path / "m.ply")
+    mio.write_ply(ply, v, f, c)
+    writer = mio.write_glb if ext == ".glb" else mio.write_obj
+    B = lambda p: open(p, "rb").read()
+    for i, kw in enumerate((dict(), dict(keep_largest=True), dict(min_component_faces=20))):
+        out = mio.convert_mesh(ply, str(tmp_path / f"s{i}{ext}"), smooth_iterations=3, **kw)
+        rv, rf, rc = mio.read_ply(ply)
+        if kw:
+            rv, rf, rc, _, _, _ = mio.filter_components(rv, rf, rc, None, kw.get("min_component_faces", 0), kw.get("keep_largest", False))
+        sv = mio.smooth_vertices(rv.astype(np.float64), rf, 3).astype(np.float32)
+        assert sv.shape == rv.shape and not np.array_equal(sv, rv)
+        av, af = mio.to_asset_frame(sv, rf)
+        want = str(tmp_path / f"want{i}{ext}")
+        writer(want, av, af, rc)
+        assert B(out) == B(want), kw
+        # smoothing off: the file convert_mesh always wrote
+        plain, off = str(tmp_path / f"p{i}{ext}"), str(tmp_path / f"o{i}{ext}")
+        mio.convert_mesh(ply, plain, **kw)
+        mio.convert_mesh(ply, off, smooth_iterations=0, **kw)
+        assert B(plain) == B(off) != B(out)
+    with pytest.raises(ValueError):
+        mio.convert_mesh(ply, str(tmp_path / ("bad" + ext)), smooth_iterations=-2)
+
+
+def test_cabi_declares_and_exports_the_adjacency_and_smoothing_entries():
+    L = importlib.import_module("one-2-3-45_amd._lib")
+    protos = L.parse_header()
+    names = ("o2345_mesh_adjacency_workspace_bytes", "o2345_mesh_adjacency_count", "o2345_mesh_adjacency_emit", "o2345_mesh_smooth")
+    assert all(n in protos for n in names)
+    assert protos["o2345_mesh_smooth"][1][6:8] == [ctypes.c_double, ctypes.c_double] and protos["o2345_mesh_adjacency_workspace_bytes"][0] is ctypes.c_size_t
+    lib = L.lib()
+    assert all(hasattr(lib, n) for n in names) and lib.o2345_version() == 210
+    small, big = lib.o2345_mesh_adjacency_workspace_bytes(0, 0), lib.o2345_mesh_adjacency_workspace_bytes(1000, 2000)
+    assert 0 < small < big and big >= 4 * (1000 + 6 * 2000)
+    # argument checks come before any device work
+    ne = ctypes.c_longlong()
+    err = lambda: lib.o2345_last_error()
+    assert lib.o2345_mesh_adjacency_count(None, 2, 3, 1, None, 0, ctypes.byref(ne), None) != 0 and b"index_bytes" in err()
+    assert lib.o2345_mesh_adjacency_count(None, 4, 3, 1, None, 0, ctypes.byref(ne), None) != 0 and b"null pointer" in err()
+    assert lib.o2345_mesh_adjacency_count(None, 4, 2 ** 30, 1, None, 0, ctypes.byref(ne), None) != 0 and b"bad sizes" in err()
+    assert lib.o2345_mesh_adjacency_count(None, 8, 3, (2 ** 31 + 5) // 6, None, 0, ctypes.byref(ne), None) != 0 and b"bad sizes" in err()
+    assert lib.o2345_mesh_adjacency_count(None, 8, 3, -1, None, 0, ctypes.byref(ne), None) != 0 and b"bad sizes" in err()
+    assert lib.o2345_mesh_adjacency_emit(None, 3, None, None, None, None) != 0 and b"null pointer" in err()
+    assert lib.o2345_mesh_adjacency_emit(None, 2 ** 30, None, None, None, None) != 0 and b"bad sizes" in err()
+    smooth = lambda nv, it, lam, mu: lib.o2345_mesh_smooth(None, nv, None, None, None, it, lam, mu, None, None, None)
+    assert smooth(3, 1, 0.5, -0.53) != 0 and b"null pointer" in err()
+    assert smooth(2 ** 30, 1, 0.5, -0.53) != 0 and b"bad sizes" in err()
+    assert smooth(3, -1, 0.5, -0.53) != 0 and b"iterations" in err()
+    for lam, mu in ((0.0, -0.5), (1.5, -0.5), (float("nan"), -0.5), (0.5, 0.1), (0.5, float("-inf")), (0.5, float("nan"))):
+        assert smooth(3, 1, lam, mu) != 0 and b"lam" in err(), (lam, mu)
+    assert smooth(0, 4, 0.5, -0.53) == 0                                # an empty mesh: nothing to do, nothing launched
+
+
+KNOBS = ("O2345_MESH_SMOOTH_ITERATIONS", "O2345_MESH_SMOOTH_LAMBDA", "O2345_MESH_SMOOTH_MU", "O2345_MESH_SMOOTH_PIN_BOUNDARY")
+
+
+def _fresh_config(monkeypatch, **env):
+    for k in KNOBS:
+        monkeypatch.delenv(k, raising=False)
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    path = importlib.import_module("one-2-3-45_amd.config").__file__
+    spec = importlib.util.spec_from_file_location("o2345_config_under_test", path)
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)                      # a private copy: the package's own config module is not touched
+    return mod
+
+
+def test_config_knobs(monkeypatch):
+    c = _fresh_config(monkeypatch)
+    assert (c.MESH_SMOOTH_ITERATIONS, c.MESH_SMOOTH_LAMBDA, c.MESH_SMOOTH_MU, c.MESH_SMOOTH_PIN_BOUNDARY) == (0, 0.5, -0.53, True)
+    assert (c.mesh_smooth_iterations(), c.mesh_smooth_lambda(), c.mesh_smooth_mu(), c.mesh_smooth_pin_boundary()) == (0, 0.5, -0.53, True)
+    c = _fresh_config(monkeypatch, **{k: "" for k in KNOBS})
+    assert (c.MESH_SMOOTH_ITERATIONS, c.MESH_SMOOTH_LAMBDA, c.MESH_SMOOTH_MU, c.MESH_SMOOTH_PIN_BOUNDARY) == (0, 0.5, -0.53, True)
+    c = _fresh_config(monkeypatch, O2345_MESH_SMOOTH_ITERATIONS=" 10 ", O2345_MESH_SMOOTH_LAMBDA="0.33", O2345_MESH_SMOOTH_MU=" -0.34", O2345_MESH_SMOOTH_PIN_BOUNDARY="0")
+    assert (c.MESH_SMOOTH_ITERATIONS, c.MESH_SMOOTH_LAMBDA, c.MESH_SMOOTH_MU, c.MESH_SMOOTH_PIN_BOUNDARY) == (10, 0.33, -0.34, False)
+    assert (c.mesh_smooth_iterations(), c.mesh_smooth_lambda(), c.mesh_smooth_mu(), c.mesh_smooth_pin_boundary()) == (10, 0.33, -0.34, False)
+    # an explicit argument wins over the environment
+    assert (c.mesh_smooth_iterations(0), c.mesh_smooth_lambda(1.0), c.mesh_smooth_mu(0), c.mesh_smooth_pin_boundary(True)) == (0, 1.0, 0.0, True)
+    assert _fresh_config(monkeypatch, O2345_MESH_SMOOTH_MU="0", O2345_MESH_SMOOTH_LAMBDA="1", O2345_MESH_SMOOTH_PIN_BOUNDARY="1").MESH_SMOOTH_MU == 0.0
+    bad = {"O2345_MESH_SMOOTH_ITERATIONS": ("-1", "many", "2.5"), "O2345_MESH_SMOOTH_LAMBDA": ("0", "1.5", "-0.5", "nan", "inf", "half"),
+           "O2345_MESH_SMOOTH_MU": ("0.53", "nan", "-inf", "minus"), "O2345_MESH_SMOOTH_PIN_BOUNDARY": ("-1", "yes", "0.5")}
+    for k, values in bad.items():
+        for v in values:
+            with pytest.raises(ValueError):
+                _fresh_config(monkeypatch, **{k: v})
+    for call in (lambda: c.mesh_smooth_iterations(-3), lambda: c.mesh_smooth_iterations(2.5), lambda: c.mesh_smooth_iterations(True), lambda: c.mesh_smooth_lambda(0.0),
+                 lambda: c.mesh_smooth_lambda(float("nan")), lambda: c.mesh_smooth_mu(0.5), lambda: c.mesh_smooth_mu(float("-inf"))):
+        with pytest.raises(ValueError):
+            call()

@@ -7,11 +7,15 @@ fed the same arrays.  Two meshes: BASELINE config 2 (8 views, 128^3 volume, 256^
   components the component filter (csrc/mesh_components.hip, keep_largest) on the config's mesh: its kernels alone (HIP events around the two-call
              protocol, which synchronises once in the middle) next to marching cubes on the same field, the gradient + colour time with and without
              it, and the filtered stage / whole-export variants inside the same alternating loops as the unfiltered ones
+  smooth     Taubin smoothing (csrc/mesh_smooth.hip), 10 iterations with the config's factors, on the config's mesh: the adjacency build alone (two-call
+             protocol, one synchronisation), the 20 step launches alone on a table built before, the whole op, the host twin (mesh_io.smooth_vertices,
+             host clock, one call) on the same mesh, and whole-export variants inside the same alternating loop as the unsmoothed ones
 Medians over --reps calls after --warmup calls; the ratio against the PLY of the SAME run is what to read.  Prints one JSON line.
 
     python tools/time_mesh_export.py [--reps 9] [--warmup 3] [--skip-512]
 """
 import argparse
+import ctypes
 import importlib
 import json
 import os
@@ -121,6 +125,30 @@ def one_mesh(dev, wt, tmp, D, R, ray_scale, a, numpy_writer):
         "grad_color_all": med_events(lambda: grad_color(verts_idx), a.reps, a.warmup),
         "grad_color_kept": med_events(lambda: grad_color(f_verts), a.reps, a.warmup),
     })
+    # Taubin smoothing, 10 iterations: table, steps, both; the host twin on the same arrays as the yardstick
+    config = importlib.import_module("one-2-3-45_amd.config")
+    L = importlib.import_module("one-2-3-45_amd._lib").lib()
+    IT = 10
+    offsets, neighbours, boundary = ops.mesh_vertex_adjacency(tris, n)
+    s_tmp, s_out = torch.empty_like(verts_idx), torch.empty_like(verts_idx)
+    ptr = lambda t: ctypes.c_void_p(t.data_ptr())
+    def steps():
+        rc = L.o2345_mesh_smooth(ptr(verts_idx), n, ptr(offsets), ptr(neighbours), ptr(boundary) if config.mesh_smooth_pin_boundary() else None, IT,
+                                 config.mesh_smooth_lambda(), config.mesh_smooth_mu(), ptr(s_tmp), ptr(s_out), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+        assert rc == 0, L.o2345_last_error()
+    hv, hf = verts_idx.cpu().numpy(), tris.cpu().numpy()
+    t0 = time.perf_counter()
+    mio.vertex_adjacency(hf, n)
+    t1 = time.perf_counter()
+    twin = mio.smooth_vertices(hv, hf, IT, config.mesh_smooth_lambda(), config.mesh_smooth_mu(), config.mesh_smooth_pin_boundary())
+    t2 = time.perf_counter()
+    deg = (offsets[1:] - offsets[:-1])
+    res["smooth"] = {"iterations": IT, "entries": int(neighbours.shape[0]), "max_degree": int(deg.max()) if n else 0, "boundary_vertices": int(boundary.sum()),
+                     "equals_host_twin": ops.mesh_smooth(verts_idx, tris, IT).cpu().numpy().tobytes() == twin.tobytes(),
+                     "kernel_ms": {"adjacency": med_events(lambda: ops.mesh_vertex_adjacency(tris, n), a.reps, a.warmup),
+                                   "steps": med_events(steps, a.reps, a.warmup),
+                                   "mesh_smooth": med_events(lambda: ops.mesh_smooth(verts_idx, tris, IT), a.reps, a.warmup)},
+                     "host_adjacency_ms_once": (t1 - t0) * 1e3, "host_twin_ms_once": (t2 - t1) * 1e3}
     A = (wt, vol, inp["proj"], inp["cam_pos"], R)
     whole = {
         "ply": lambda: pipeline.export_mesh_ply(P(".ply"), *A),
@@ -129,6 +157,9 @@ def one_mesh(dev, wt, tmp, D, R, ray_scale, a, numpy_writer):
         "ply_largest": lambda: pipeline.export_mesh_ply(P("_l.ply"), *A, keep_largest=True),
         "glb_largest": lambda: pipeline.export_mesh_asset(P("_l.glb"), *A, keep_largest=True),
         "obj_largest": lambda: pipeline.export_mesh_asset(P("_l.obj"), *A, keep_largest=True),
+        "ply_smooth10": lambda: pipeline.export_mesh_ply(P("_s.ply"), *A, smooth_iterations=IT),
+        "glb_smooth10": lambda: pipeline.export_mesh_asset(P("_s.glb"), *A, smooth_iterations=IT),
+        "obj_smooth10": lambda: pipeline.export_mesh_asset(P("_s.obj"), *A, smooth_iterations=IT),
     }
     # alternated like the stage variants; the spread (min .. max) of each is what a difference between two of them has to exceed
     for fn in whole.values():
