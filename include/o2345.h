@@ -48,7 +48,8 @@ const char* o2345_last_error(void);
  * Additive since 2.1 (no existing entry changed, the version stays 210): the asset export entries o2345_mesh_bounds_workspace_bytes,
  * o2345_mesh_asset_vertices, o2345_mesh_asset_indices, o2345_obj_text_bytes, o2345_obj_text, o2345_obj_text_host; the mesh component entries
  * o2345_mesh_components_workspace_bytes, o2345_mesh_components_count, o2345_mesh_components_emit; the adjacency and smoothing entries
- * o2345_mesh_adjacency_workspace_bytes, o2345_mesh_adjacency_count, o2345_mesh_adjacency_emit, o2345_mesh_smooth. */
+ * o2345_mesh_adjacency_workspace_bytes, o2345_mesh_adjacency_count, o2345_mesh_adjacency_emit, o2345_mesh_smooth; the decimation entries
+ * o2345_mesh_decimate_workspace_bytes, o2345_mesh_decimate_count, o2345_mesh_decimate_emit. */
 int o2345_version(void);
 /* Layout self-description of O2345RenderIO as THIS library was compiled (sizeof, and offsetof of every field in declaration order): a binding
  * asserts its own struct against it at load time (one-2-3-45_amd/_lib.py does) -- a field added on one side only cannot corrupt calls silently.
@@ -379,6 +380,29 @@ int o2345_mesh_adjacency_count(const void* tris, int index_bytes, long long nv, 
 int o2345_mesh_adjacency_emit(void* workspace, long long nv, int* offsets, int* neighbours, unsigned char* boundary, void* stream);
 int o2345_mesh_smooth(const double* verts_in, long long nv, const int* offsets, const int* neighbours, const unsigned char* boundary_or_null, int iterations,
                       double lam, double mu, double* verts_tmp, double* verts_out, void* stream);
+
+/* ---- decimation by vertex clustering (additive since 2.1; the reference has no such step, its users simplify the mesh in another tool) ---------------
+ * q = floor(p / cell) per axis in fp64 (IEEE division); the vertices with equal q form a cluster, whose representative is its smallest member index.
+ * Per axis max q - min q must be below 2^21 (the three offsets pack into one 63-bit key; negative coordinates are legal).  Triangle (a, b, c) maps to
+ * its corners' clusters; it is degenerate, and dropped, iff two mapped corners are equal; of the others, those over the same SET of three clusters are
+ * duplicates whatever their orientation or rotation, and the first in face order is kept.  Kept triangles keep face order, corner order and
+ * orientation.  A cluster is kept iff a kept triangle references it; kept clusters are numbered by an exclusive scan of "is a kept representative" over
+ * the old vertex order.  Position of a kept cluster, per coordinate: acc = 0; acc = acc + p[u] over its members u in ascending index order, one
+ * sequential sum; acc / count.  Exact and deterministic: equal to mesh_io.decimate_mesh to the last bit.  No manifoldness is promised: where a thin part
+ * collapses, clustering leaves edges with more than two triangles, or open ones.
+ * verts device fp64 [nv,3], tris device int32 / int64 [nt,3] (index_bytes 4 / 8), both only read; 0 <= nv < 2^30, 3 * nt < 2^31; cell finite and > 0.
+ * workspace: mesh_decimate_workspace_bytes(nv, nt) bytes (0 for bad sizes), 16-byte aligned.  count() does all the work inside the workspace and
+ * returns on the HOST (synchronises the stream once) the number of clusters, of output vertices and triangles, and of degenerate and duplicate
+ * triangles dropped.  Errors: a bad cell, bad sizes, a workspace that is too small, a non-finite coordinate, a triangle index outside [0, nv), an
+ * extent of 2^21 cells or more; the last three are counted on the device, never dereferenced.  emit() (same workspace, nv and nt, untouched in between)
+ * writes verts_out device fp64 [nv_out,3], tris_out [nt_out,3] of the input's width and cluster device int32 [nv] (the new index of every old vertex's
+ * cluster, or -1); any of the three may be NULL. */
+size_t o2345_mesh_decimate_workspace_bytes(long long nv, long long nt);
+int o2345_mesh_decimate_count(const double* verts, const void* tris, int index_bytes, long long nv, long long nt, double cell, void* workspace,
+                              size_t workspace_bytes, long long* n_clusters_host, long long* nv_out_host, long long* nt_out_host,
+                              long long* n_degenerate_host, long long* n_duplicate_host, void* stream);
+int o2345_mesh_decimate_emit(const double* verts, const void* tris, int index_bytes, long long nv, long long nt, void* workspace, double* verts_out,
+                             void* tris_out, int* cluster, void* stream);
 
 /* ---- mesh serialisation (replaces the numpy / trimesh tail of validate_mesh and validate_colored_mesh,
  * models/trainer_generic.py:1287-1303, 1365-1382: index -> world frame, scale_mat, trans_mat, uint8 colours, PLY records) -----

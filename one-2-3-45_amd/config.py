@@ -148,3 +148,17 @@ def mesh_smooth_mu(mu=None):
 
 def mesh_smooth_pin_boundary(p=None):
     return MESH_SMOOTH_PIN_BOUNDARY if p is None else bool(p)
+
+
+# ---- mesh decimation (csrc/mesh_decimate.hip; mesh_io.decimate_mesh is the host twin) -------------------------------------------------------------------
+# O2345_MESH_DECIMATE_CELL=c merges the vertices of the extracted mesh that share a lattice cell of edge c (in units of the extraction grid's spacing) into
+# one vertex at their mean and drops the triangles that collapse, on the device, after the component filter and before the vertices are coloured ("" or
+# "0" = off, the default: the mesh is then what marching cubes found, and nothing is launched).
+MESH_DECIMATE_CELL = _finite_float("O2345_MESH_DECIMATE_CELL", os.environ.get("O2345_MESH_DECIMATE_CELL", ""), 0.0, lambda x: x >= 0.0, "a finite float >= 0")
+
+
+def mesh_decimate_cell(x=None):
+    """None -> the configured default; anything else must be a finite float >= 0 (an explicit 0 is off whatever the default)."""
+    if x is None:
+        return MESH_DECIMATE_CELL
+    return _finite_float("decimate_cell", repr(float(x)), None, lambda c: c >= 0.0, "a finite float >= 0")

@@ -1,4 +1,5 @@
-// Small non-matrix kernels and block-level steps shared by several translation units (costvol.hip, sparse.hip, mcubes.hip, mesh_components.hip, convnet.hip).
+// Small non-matrix kernels and block-level steps shared by several translation units (costvol.hip, sparse.hip, mcubes.hip, mesh_components.hip,
+// mesh_smooth.hip, mesh_decimate.hip, convnet.hip).
 // The kernels live in an anonymous namespace: every unit that launches one instantiates its own copy in its own code object, so o2345_preload
 // and the runtime's per-unit loading see them as before.
 #pragma once
@@ -38,6 +39,30 @@ __device__ __forceinline__ int block_scan_excl(int v, int* lds /*[5]*/, int& tot
     total = tot;
     __syncthreads();
     return base + inc - v;
+}
+
+// ascending bitonic network over N registers (N a power of two; every index is a compile-time constant after unrolling): mesh_smooth.hip, mesh_decimate.hip
+__device__ __forceinline__ void regs_cmpswap(int& x, int& y) {
+    const int lo = min(x, y), hi = max(x, y);
+    x = lo; y = hi;
+}
+
+template <int N>
+__device__ __forceinline__ void sort_regs(int (&r)[N]) {
+#pragma unroll
+    for (int k = 2; k <= N; k <<= 1) {
+#pragma unroll
+        for (int j = k >> 1; j > 0; j >>= 1) {
+#pragma unroll
+            for (int i = 0; i < N; ++i) {
+                const int l = i ^ j;
+                if (l > i) {
+                    if ((i & k) == 0) regs_cmpswap(r[i], r[l]);
+                    else regs_cmpswap(r[l], r[i]);
+                }
+            }
+        }
+    }
 }
 
 // batch statistics of channel c -> the (scale, shift) pair of InPlaceABN: s = sum x, q = sum x^2 over `count` values, biased variance;
@@ -82,6 +107,40 @@ __global__ __launch_bounds__(1024) void k_scan_small(int* __restrict__ a, int n,
         run += v;
     }
     if (t == 1023) *total = (Total)part[1023];
+}
+
+// exclusive scan of a long int array in three launches: k_tile_sum (one block per tile of 256 * ITEMS entries -> block_total), k_scan_small over the block
+// totals, k_tile_scan (block_base = the scanned block totals) -> out[i], and out2[i] when that is not null.  mesh_smooth.hip, mesh_decimate.hip
+template <int ITEMS>
+__global__ __launch_bounds__(256) void k_tile_sum(const int* __restrict__ a, long long n, int* __restrict__ block_total) {
+    __shared__ int lds[5];
+    const long long i0 = (long long)blockIdx.x * (IDX_BLOCK * ITEMS) + threadIdx.x;
+    int s = 0;
+#pragma unroll
+    for (int k = 0; k < ITEMS; ++k) s += (i0 + k * 256 < n) ? a[i0 + k * 256] : 0;
+    int total;
+    (void)block_scan_excl(s, lds, total);
+    if (threadIdx.x == 0) block_total[blockIdx.x] = total;
+}
+
+template <int ITEMS>
+__global__ __launch_bounds__(256) void k_tile_scan(const int* __restrict__ a, long long n, const int* __restrict__ block_base, int* __restrict__ out,
+                                                   int* __restrict__ out2) {
+    __shared__ int lds[5];
+    const long long i0 = (long long)blockIdx.x * (IDX_BLOCK * ITEMS) + threadIdx.x;
+    int run = block_base[blockIdx.x];
+#pragma unroll
+    for (int k = 0; k < ITEMS; ++k) {
+        const long long i = i0 + k * 256;
+        const int x = i < n ? a[i] : 0;
+        int total;
+        const int at = run + block_scan_excl(x, lds, total);
+        if (i < n) {
+            out[i] = at;
+            if (out2) out2[i] = at;
+        }
+        run += total;
+    }
 }
 
 // [V,C,HW] -> [V,HW,C] through a 64-pixel x C LDS tile (coalesced reads and writes).  ACT: y = leaky_relu(x * ss[c] + ss[C + c], slope) on the

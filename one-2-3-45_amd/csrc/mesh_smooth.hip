@@ -59,38 +59,6 @@ __global__ __launch_bounds__(256) void k_adj_capacity(const IDX* __restrict__ tr
     if (nc) atomicAdd(cap + c, nc);
 }
 
-// sum of a[] per tile of ADJ_TILE -> block_total[blockIdx.x]
-__global__ __launch_bounds__(256) void k_adj_tile_sum(const int* __restrict__ a, long long n, int* __restrict__ block_total) {
-    __shared__ int lds[5];
-    const long long i0 = (long long)blockIdx.x * ADJ_TILE + threadIdx.x;
-    int s = 0;
-#pragma unroll
-    for (int k = 0; k < ADJ_ITEMS; ++k) s += (i0 + k * 256 < n) ? a[i0 + k * 256] : 0;
-    int total;
-    (void)block_scan_excl(s, lds, total);
-    if (threadIdx.x == 0) block_total[blockIdx.x] = total;
-}
-
-// out[i] (and out2[i]) = exclusive scan of a[] (block_base: the exclusive scan of block_total)
-__global__ __launch_bounds__(256) void k_adj_tile_scan(const int* __restrict__ a, long long n, const int* __restrict__ block_base, int* __restrict__ out,
-                                                       int* __restrict__ out2) {
-    __shared__ int lds[5];
-    const long long i0 = (long long)blockIdx.x * ADJ_TILE + threadIdx.x;
-    int run = block_base[blockIdx.x];
-#pragma unroll
-    for (int k = 0; k < ADJ_ITEMS; ++k) {
-        const long long i = i0 + k * 256;
-        const int x = i < n ? a[i] : 0;
-        int total;
-        const int at = run + block_scan_excl(x, lds, total);
-        if (i < n) {
-            out[i] = at;
-            if (out2) out2[i] = at;
-        }
-        run += total;
-    }
-}
-
 // every corner claims the slots of its (at most two) pairs with one atomic; cursor[v] starts at the row's first slot and ends behind its last
 template <typename IDX>
 __global__ __launch_bounds__(256) void k_adj_fill(const IDX* __restrict__ tris, long long nt, int nv, int* __restrict__ cursor, int* __restrict__ raw) {
@@ -104,37 +72,13 @@ __global__ __launch_bounds__(256) void k_adj_fill(const IDX* __restrict__ tris, 
     if (nc) { int s = atomicAdd(cursor + c, nc); if (c != a) raw[s++] = a; if (c != b) raw[s] = b; }
 }
 
-__device__ __forceinline__ void adj_cmpswap(int& x, int& y) {
-    const int lo = min(x, y), hi = max(x, y);
-    x = lo; y = hi;
-}
-
-// bitonic network over N registers, ascending (every index is a compile-time constant after unrolling)
-template <int N>
-__device__ __forceinline__ void adj_sort_regs(int (&r)[N]) {
-#pragma unroll
-    for (int k = 2; k <= N; k <<= 1) {
-#pragma unroll
-        for (int j = k >> 1; j > 0; j >>= 1) {
-#pragma unroll
-            for (int i = 0; i < N; ++i) {
-                const int l = i ^ j;
-                if (l > i) {
-                    if ((i & k) == 0) adj_cmpswap(r[i], r[l]);
-                    else adj_cmpswap(r[l], r[i]);
-                }
-            }
-        }
-    }
-}
-
 // a row of at most N raw entries: sorted, duplicates collapsed, written back to the head of its own raw segment -> degree; boundary flag by reference
 template <int N>
 __device__ __forceinline__ int adj_short_row(int* __restrict__ row, int d, int& boundary) {
     int r[N];
 #pragma unroll
     for (int k = 0; k < N; ++k) r[k] = k < d ? row[k] : ADJ_PAD;
-    adj_sort_regs<N>(r);
+    sort_regs<N>(r);
     int deg = 0, bnd = 0;
 #pragma unroll
     for (int k = 0; k < N; ++k) {
@@ -319,18 +263,18 @@ int o2345_mesh_adjacency_count(const void* tris, int index_bytes, long long nv, 
             if (index_bytes == 4) hipLaunchKernelGGL(k_adj_capacity<int>, dim3(gt), dim3(256), 0, s, (const int*)tris, nt, n, c.cap, c.tot);
             else hipLaunchKernelGGL(k_adj_capacity<long long>, dim3(gt), dim3(256), 0, s, (const long long*)tris, nt, n, c.cap, c.tot);
         }
-        hipLaunchKernelGGL(k_adj_tile_sum, dim3(c.nbv), dim3(256), 0, s, c.cap, nv, c.vblock);
+        hipLaunchKernelGGL(k_tile_sum<ADJ_ITEMS>, dim3(c.nbv), dim3(256), 0, s, c.cap, nv, c.vblock);
         hipLaunchKernelGGL(k_scan_small<long long>, dim3(1), dim3(1024), 0, s, c.vblock, (int)c.nbv, &c.tot->n_raw);
-        hipLaunchKernelGGL(k_adj_tile_scan, dim3(c.nbv), dim3(256), 0, s, c.cap, nv, c.vblock, c.rawoff, c.cursor);
+        hipLaunchKernelGGL(k_tile_scan<ADJ_ITEMS>, dim3(c.nbv), dim3(256), 0, s, c.cap, nv, c.vblock, c.rawoff, c.cursor);
         if (nt > 0) {
             if (index_bytes == 4) hipLaunchKernelGGL(k_adj_fill<int>, dim3(gt), dim3(256), 0, s, (const int*)tris, nt, n, c.cursor, c.raw);
             else hipLaunchKernelGGL(k_adj_fill<long long>, dim3(gt), dim3(256), 0, s, (const long long*)tris, nt, n, c.cursor, c.raw);
         }
         hipLaunchKernelGGL(k_adj_rows, dim3(gv), dim3(256), 0, s, n, c.rawoff, c.cap, c.raw, c.bnd, c.long_list, c.tot);
         if (nt > 0) hipLaunchKernelGGL(k_adj_long_rows, dim3(ADJ_LONG_GRID), dim3(256), 0, s, c.rawoff, c.cursor, c.cap, c.raw, c.tmp, c.bnd, c.long_list, c.tot);
-        hipLaunchKernelGGL(k_adj_tile_sum, dim3(c.nbv), dim3(256), 0, s, c.cap, nv, c.vblock);
+        hipLaunchKernelGGL(k_tile_sum<ADJ_ITEMS>, dim3(c.nbv), dim3(256), 0, s, c.cap, nv, c.vblock);
         hipLaunchKernelGGL(k_scan_small<long long>, dim3(1), dim3(1024), 0, s, c.vblock, (int)c.nbv, &c.tot->n_entries);
-        hipLaunchKernelGGL(k_adj_tile_scan, dim3(c.nbv), dim3(256), 0, s, c.cap, nv, c.vblock, c.off, (int*)nullptr);
+        hipLaunchKernelGGL(k_tile_scan<ADJ_ITEMS>, dim3(c.nbv), dim3(256), 0, s, c.cap, nv, c.vblock, c.off, (int*)nullptr);
     } else if (nt > 0) {                                            // no vertex: every triangle is out of range
         if (index_bytes == 4) hipLaunchKernelGGL(k_adj_capacity<int>, dim3(gt), dim3(256), 0, s, (const int*)tris, nt, n, c.cap, c.tot);
         else hipLaunchKernelGGL(k_adj_capacity<long long>, dim3(gt), dim3(256), 0, s, (const long long*)tris, nt, n, c.cap, c.tot);

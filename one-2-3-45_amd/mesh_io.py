@@ -486,19 +486,124 @@ def smooth_vertices(verts, faces, iterations, lam=0.5, mu=-0.53, pin_boundary=Tr
     return p
 
 
-def convert_mesh(ply_path, out_path, min_component_faces=0, keep_largest=False, smooth_iterations=0):
+# ------------------------------------------------------------------------------------------------------------------ decimation
+def _check_cell(cell):
+    """-> 0.0 for off (None or 0), else the finite positive float"""
+    if cell is None:
+        return 0.0
+    c = float(cell)
+    if not (np.isfinite(c) and c >= 0.0):
+        raise ValueError(f"decimate: cell must be a finite float >= 0, got {cell!r}")
+    return c
+
+
+def decimate_mesh(verts, faces, cell, colors=None):
+    """Decimation by vertex clustering (host twin of ops.mesh_decimate, and the definition of its result, to the last bit) -> (verts float64 [Nc,3], faces
+    [Mk,3] in the dtype of ``faces``, colors, cluster int32 [N], info).  ``cell`` None or 0: off, the inputs are returned as they are (cluster, info: None).
+    Cell of a vertex: q = floor(p / cell) per axis in float64; equal q = one cluster; per axis max q - min q must be below 2^21 (the offsets q - min q pack
+    into one 63-bit key; the shift does not change the partition, negative coordinates are legal).  Representative: the smallest member index.  Face
+    (a, b, c) maps to its corners' clusters; degenerate (two mapped corners equal) faces are dropped; of the others, those over the same SET of three
+    clusters are duplicates whatever their orientation or rotation, and the first in face order is kept.  Kept faces keep face order, corner order and
+    orientation.  A cluster is kept iff a kept face references it; kept clusters are numbered by an exclusive scan of "is a kept representative" over the
+    old vertex order; ``cluster[v]`` is that number, or -1 (clusters that only fed degenerate faces, specks inside one cell, unreferenced vertices).
+    Position, per coordinate: acc = 0; acc = acc + p[u] over the members u in ascending index order (one sequential sum); acc / count.  ``colors`` uint8
+    [N,3] or [N,4]: per channel (2 * sum + n) // (2 * n) over the members, the mean rounded half up, exact.  ``info`` = {"clusters" (distinct cells),
+    "vertices", "triangles", "degenerate", "duplicate"}.  NOT promised: manifoldness -- where a thin part collapses, clustering leaves edges with more
+    than two faces, or open ones.  Refused (ValueError): a negative or non-finite cell, a non-finite coordinate, a face index outside [0, N), an extent
+    of 2^21 cells or more, N >= 2^30 or 3 M >= 2^31, colours that are not uint8."""
+    cell = _check_cell(cell)
+    if cell == 0.0:
+        return verts, faces, colors, None, None
+    p = np.asarray(verts, dtype=np.float64).reshape(-1, 3)
+    fin = np.asarray(faces).reshape(-1, 3)
+    f = fin.astype(np.int64, copy=False)
+    n, m = p.shape[0], f.shape[0]
+    if n >= 2 ** 30 or 3 * m >= 2 ** 31:
+        raise ValueError(f"decimate: bad sizes ({n} vertices, {m} faces; the tables are int32)")
+    if not np.isfinite(p).all():
+        raise ValueError("decimate: non-finite vertex coordinate")
+    if f.size and (f.min() < 0 or f.max() >= n):
+        raise ValueError(f"faces index outside 0 .. {n - 1}")
+    col = None
+    if colors is not None:
+        col = np.asarray(colors)
+        if col.dtype != np.uint8 or col.ndim != 2 or col.shape[0] != n or col.shape[1] not in (3, 4):
+            raise ValueError(f"decimate: colours must be uint8 [N,3] or [N,4], got {col.dtype} {col.shape}")
+    info = {"clusters": 0, "vertices": 0, "triangles": 0, "degenerate": m, "duplicate": 0}
+    empty = (np.zeros((0, 3), np.float64), np.zeros((0, 3), fin.dtype), None if col is None else np.zeros((0, col.shape[1]), np.uint8))
+    if n == 0:
+        return (*empty, np.zeros(0, np.int32), info)
+    with np.errstate(over="ignore", invalid="ignore"):
+        q = np.floor(p / cell)
+        q0 = q.min(axis=0)
+        if not ((q.max(axis=0) - q0) < 2.0 ** 21).all():
+            raise ValueError(f"decimate: the mesh extends over 2^21 cells or more of size {cell!r} along an axis")
+    r = (q - q0).astype(np.int64)                                      # exact: both are integers less than 2^21 apart
+    key = (r[:, 0] << 42) | (r[:, 1] << 21) | r[:, 2]
+    _, first, inverse = np.unique(key, return_index=True, return_inverse=True)      # first occurrence = smallest member index
+    rep = first[inverse.reshape(-1)]
+    info["clusters"] = int(first.size)
+    mf = rep[f]                                                        # mapped faces
+    alive = (mf[:, 0] != mf[:, 1]) & (mf[:, 1] != mf[:, 2]) & (mf[:, 0] != mf[:, 2]) if m else np.zeros(0, bool)
+    keep_f = np.zeros(m, bool)
+    live = np.flatnonzero(alive)
+    if live.size:
+        _, first_f = np.unique(np.sort(mf[live], axis=1), axis=0, return_index=True)          # first in face order of every vertex set
+        keep_f[live[first_f]] = True
+    info["degenerate"], info["triangles"] = int(m - live.size), int(np.count_nonzero(keep_f))
+    info["duplicate"] = int(live.size) - info["triangles"]
+    used = np.zeros(n, bool)
+    used[mf[keep_f].reshape(-1)] = True                                # kept representatives
+    new_index = np.cumsum(used) - used                                 # exclusive scan over the old vertex order
+    cluster = np.where(used[rep], new_index[rep], -1).astype(np.int32)
+    nc = int(np.count_nonzero(used))
+    info["vertices"] = nc
+    f_out = new_index[mf[keep_f]].astype(fin.dtype)
+    if nc == 0:
+        return (empty[0], f_out.reshape(-1, 3), empty[2], cluster, info)
+    # members of every kept cluster in ascending index order: a stable sort by cluster.  The sum is sequential over the member RANK k, vectorised over the
+    # clusters that have a k-th member: with the clusters sorted by falling count those are a prefix, as in smooth_vertices (np.add.reduceat / sum(axis)
+    # would add in numpy's own pairwise order, which is not the definition)
+    members = np.flatnonzero(cluster >= 0)
+    members = members[np.argsort(cluster[members], kind="stable")]
+    count = np.bincount(cluster[members], minlength=nc)
+    start = np.cumsum(count) - count
+    rows = np.argsort(-count, kind="stable")
+    rcount, rstart = count[rows], start[rows]
+    have = np.searchsorted(-rcount, -np.arange(int(rcount[0])), side="left")       # clusters with more than k members = the first have[k] rows
+    acc = np.zeros((nc, 3), np.float64)
+    for k, h in enumerate(have):
+        acc[:h] = acc[:h] + p[members[rstart[:h] + k]]
+    v_out = np.empty((nc, 3), np.float64)
+    v_out[rows] = acc / rcount.astype(np.float64)[:, None]
+    c_out = None
+    if col is not None:
+        cm = cluster[members]
+        total = np.stack([np.bincount(cm, weights=col[members, k], minlength=nc) for k in range(col.shape[1])], 1).astype(np.int64)      # < 2^53: exact
+        c_out = ((2 * total + count[:, None]) // (2 * count[:, None])).astype(np.uint8)
+    return v_out, f_out, c_out, cluster, info
+
+
+def convert_mesh(ply_path, out_path, min_component_faces=0, keep_largest=False, smooth_iterations=0, decimate_cell=0):
     """convert_mesh_format (utils/utils.py:31-47) for a mesh already on disk: read the PLY, exchange y and z, reverse the faces, write ``out_path`` by its
     extension (.glb or .obj) with the PLY's vertex colours.  ``min_component_faces`` / ``keep_largest``: filter_components on the way (off by default).
     ``smooth_iterations`` (0 = off): smooth_vertices with its default factors and pinning, after the filter, on the file's float32 positions cast to
     float64, the result cast back to float32.  That is NOT byte-equal to the device export with the same count, which smooths the float64 index
-    coordinates before the frame transform rounds them to float32.  Returns ``out_path``."""
+    coordinates before the frame transform rounds them to float32.
+    ``decimate_cell`` (0 = off): decimate_mesh after the filter and before the smoothing, with the cell in the FILE's own units, on the float32 positions
+    cast to float64, the result cast back to float32, the colours merged as decimate_mesh defines.  For the same reason that is not byte-equal to the
+    device export, which clusters the index coordinates (cell in units of the grid spacing) and colours the new vertices.  Returns ``out_path``."""
     ext = _asset_ext(out_path)
     if ext == ".ply":
         raise ValueError("convert_mesh: the output is .glb or .obj")
     smooth_iterations = _check_smooth_args(smooth_iterations, 0.5, -0.53)[0]
+    decimate_cell = _check_cell(decimate_cell)
     v, f, c = read_ply(ply_path)
     if min_component_faces or keep_largest:
         v, f, c, _, _, _ = filter_components(v, f, c, None, min_component_faces, keep_largest)
+    if decimate_cell:
+        v, f, c, _, _ = decimate_mesh(v.astype(np.float64), f, decimate_cell, c)
+        v = v.astype(np.float32)
     if smooth_iterations:
         v = smooth_vertices(v.astype(np.float64), f, smooth_iterations).astype(np.float32)
     v, f = to_asset_frame(v, f)

@@ -967,3 +967,33 @@ def mesh_smooth(verts_idx, tris, iterations, lam=None, mu=None, pin_boundary=Non
     check(_lib.lib().o2345_mesh_smooth(_p(verts_idx, torch.float64), nv, _p(offsets, torch.int32), _p(neighbours, torch.int32), _p(boundary, torch.uint8) if pin else None,
                                        iterations, lam, mu, _p(tmp, torch.uint8), _p(out, torch.float64), _stream()), "mesh_smooth")
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------- mesh decimation
+@_on_device
+def mesh_decimate(verts_idx, tris, cell=None):
+    """Decimation by vertex clustering on the device (== mesh_io.decimate_mesh, to the last bit; definitions in csrc/mesh_decimate.hip).  verts_idx fp64
+    [N,3], tris [M,3] int32 / int64, ``cell`` in the units of ``verts_idx`` (None: the config default) -> (verts fp64 [Nc,3], tris [Mk,3] of the same dtype,
+    cluster int32 [N]: the new index of every old vertex's cluster or -1, info = {"clusters", "vertices", "triangles", "degenerate", "duplicate"}).  The
+    inputs are not written; Nc = 0 and Mk = 0 are legal.  With ``cell == 0`` no kernel is launched: the inputs are returned as they are, ``cluster`` and
+    ``info`` are None."""
+    cell = config.mesh_decimate_cell(cell)
+    if cell == 0.0:
+        return verts_idx, tris, None, None
+    if tris.dtype not in (torch.int32, torch.int64) or tris.dim() != 2 or tris.shape[1] != 3:
+        raise ValueError(f"expected triangles [M,3] int32 or int64, got {tuple(tris.shape)} {tris.dtype}")
+    if verts_idx.dtype != torch.float64 or verts_idx.dim() != 2 or verts_idx.shape[1] != 3:
+        raise ValueError(f"expected vertices [N,3] float64, got {tuple(verts_idx.shape)} {verts_idx.dtype}")
+    L = _lib.lib()
+    nv, nt, dev, ib = verts_idx.shape[0], tris.shape[0], verts_idx.device, 8 if tris.dtype == torch.int64 else 4
+    wsb = L.o2345_mesh_decimate_workspace_bytes(nv, nt)
+    ws = _workspace(wsb, dev, "mesh_decimate")
+    ncl, nvo, nto, ndeg, ndup = (ctypes.c_longlong() for _ in range(5))
+    check(L.o2345_mesh_decimate_count(_p(verts_idx, torch.float64), _p(tris, tris.dtype), ib, nv, nt, cell, _p(ws, torch.uint8), wsb, ctypes.byref(ncl),
+                                      ctypes.byref(nvo), ctypes.byref(nto), ctypes.byref(ndeg), ctypes.byref(ndup), _stream()), "mesh_decimate_count")
+    verts = torch.empty(nvo.value, 3, dtype=torch.float64, device=dev)
+    tris_out = torch.empty(nto.value, 3, dtype=tris.dtype, device=dev)
+    cluster = torch.empty(nv, dtype=torch.int32, device=dev)
+    check(L.o2345_mesh_decimate_emit(_p(verts_idx, torch.float64), _p(tris, tris.dtype), ib, nv, nt, _p(ws, torch.uint8), _p(verts, torch.float64),
+                                     _p(tris_out, tris.dtype), _p(cluster, torch.int32), _stream()), "mesh_decimate_emit")
+    return verts, tris_out, cluster, {"clusters": ncl.value, "vertices": nvo.value, "triangles": nto.value, "degenerate": ndeg.value, "duplicate": ndup.value}

@@ -508,6 +508,10 @@ class SparseNeuSRenderer(nn.Module):
         # the device, so the unchanged runner's validate_colored_mesh colours and writes the filtered mesh; u is returned as it is
         if config.MESH_MIN_COMPONENT_FACES or config.MESH_KEEP_LARGEST:
             v, t, _, _ = ops.mesh_filter_components(v, t, config.MESH_MIN_COMPONENT_FACES, config.MESH_KEEP_LARGEST)
+        # O2345_MESH_DECIMATE_CELL (off by default: nothing is launched): vertex clustering of the index coordinates on the device, cell in grid spacings;
+        # the unchanged runner then colours and writes the decimated mesh
+        if config.MESH_DECIMATE_CELL:
+            v, t, _, _ = ops.mesh_decimate(v, t, config.MESH_DECIMATE_CELL)
         # O2345_MESH_SMOOTH_ITERATIONS (off by default: nothing is launched): Taubin smoothing of the index coordinates on the device; the unchanged runner
         # colours whatever vertices it is handed, so here the colours are taken at the SMOOTHED positions (pipeline._mesh_fields colours first)
         if config.MESH_SMOOTH_ITERATIONS:

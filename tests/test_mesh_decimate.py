@@ -1,0 +1,291 @@
+"""Decimation by vertex clustering on the CPU: the host twin (mesh_io.decimate_mesh / convert_mesh's decimation), which DEFINES what the device op
+(csrc/mesh_decimate.hip) returns.  Expected values are brute force over the written definition or facts derived from it, never the function under test."""
+import ctypes
+import importlib
+import importlib.util
+import os
+
+import numpy as np
+import pytest
+
+import mesh_components_util as mcu
+
+mio = importlib.import_module("one-2-3-45_amd.mesh_io")
+HERE = os.path.dirname(os.path.abspath(__file__))
+GOLDEN = os.path.join(HERE, "golden", "mc_skimage.npz")
+
+
+def _cloud(n=400, m=900, seed=0):
+    """random points in [-3, 3)^3 (negative coordinates), a third of them snapped onto multiples of 0.5 = exactly on cell faces of cell 0.5 and 1.0;
+    random faces over them, some vertices unreferenced"""
+    rng = np.random.default_rng(seed)
+    p = rng.uniform(-3.0, 3.0, (n, 3))
+    p[::3] = np.round(p[::3] * 2.0) / 2.0
+    f = rng.integers(0, n - 7, (m, 3)).astype(np.int64)
+    return p, f
+
+
+def _brute(p, f, cell):
+    """the definition, vertex by vertex and face by face -> (verts, faces, cluster, info)"""
+    cells, rep = {}, []
+    for v, x in enumerate(p):
+        k = tuple(float(np.floor(c / cell)) for c in x)
+        rep.append(cells.setdefault(k, v))
+    kept, seen, deg, dup = [], set(), 0, 0
+    for a, b, c in f:
+        m = (rep[a], rep[b], rep[c])
+        if len(set(m)) < 3:
+            deg += 1
+        elif frozenset(m) in seen:
+            dup += 1
+        else:
+            seen.add(frozenset(m))
+            kept.append(m)
+    used = sorted({r for m in kept for r in m})
+    new = {r: i for i, r in enumerate(used)}
+    cluster = np.array([new.get(r, -1) for r in rep], np.int32)
+    verts = np.zeros((len(used), 3))
+    for i, r in enumerate(used):
+        for d in range(3):
+            acc, cnt = 0.0, 0
+            for u in range(len(p)):
+                if rep[u] == r:
+                    acc = acc + float(p[u, d])
+                    cnt += 1
+            verts[i, d] = acc / cnt
+    faces = np.array([[new[r] for r in m] for m in kept], np.int64).reshape(-1, 3)
+    return verts, faces, cluster, {"clusters": len(cells), "vertices": len(used), "triangles": len(kept), "degenerate": deg, "duplicate": dup}
+
+
+@pytest.mark.parametrize("cell", [0.5, 1.0, 1.7])
+def test_twin_is_the_written_definition(cell):
+    p, f = _cloud()
+    v, fo, c, cluster, info = mio.decimate_mesh(p, f, cell)
+    wv, wf, wcluster, winfo = _brute(p, f, cell)
+    assert info == winfo and info["degenerate"] > 0 and info["vertices"] <= info["clusters"] < p.shape[0]
+    assert c is None and cluster.dtype == np.int32 and np.array_equal(cluster, wcluster)
+    assert fo.dtype == f.dtype and np.array_equal(fo, wf)
+    assert v.dtype == np.float64 and v.tobytes() == wv.tobytes()
+
+
+def test_duplicates_whatever_their_orientation_or_rotation():
+    # four cells on a line at x = 0, 10, 20, 30; faces over the cells {0,1,2} in three guises, {1,2,3} once
+    p = np.array([[0.1, 0, 0], [10.1, 0, 0], [20.1, 0, 0], [30.1, 0, 0], [0.2, 0, 0], [10.2, 0, 0], [20.2, 0, 0]])
+    f = np.array([[4, 1, 2], [2, 0, 1], [1, 0, 6], [5, 6, 3], [0, 4, 1]])
+    v, fo, _, cluster, info = mio.decimate_mesh(p, f, 1.0)
+    assert info == {"clusters": 4, "vertices": 4, "triangles": 2, "degenerate": 1, "duplicate": 2}
+    assert np.array_equal(fo, [[0, 1, 2], [1, 2, 3]])                # the first guise, corner order kept: (rep 4, rep 1, rep 2) = (0, 1, 2)
+    assert np.array_equal(cluster, [0, 1, 2, 3, 0, 1, 2])
+    assert v[0, 0] == (0.0 + 0.1 + 0.2) / 2 and v[3, 0] == 30.1
+
+
+def test_invariants_on_a_marching_cubes_mesh():
+    d = np.load(GOLDEN)
+    p, f = d["noise_cube:verts"].astype(np.float64), d["noise_cube:faces"]
+    cell = 2.0
+    v, fo, _, cluster, info = mio.decimate_mesh(p, f, cell)
+    n = p.shape[0]
+    q = np.floor(p / cell)
+    # cluster partitions the kept vertices exactly by q; output order = order of the representatives
+    kept = np.flatnonzero(cluster >= 0)
+    assert mcu.partition_equal(cluster[kept], np.unique(q[kept], axis=0, return_inverse=True)[1].reshape(-1))
+    reps = np.array([kept[cluster[kept] == c][0] for c in range(info["vertices"])])
+    assert (np.diff(reps) > 0).all()
+    # kept faces: a subsequence of the mapped input faces, corner order preserved
+    rep_of = np.full(n, -1)
+    first = {}
+    for i, x in enumerate(map(tuple, q)):
+        rep_of[i] = first.setdefault(x, i)
+    mapped = cluster[rep_of[f]]
+    j = 0
+    for row in mapped:
+        if j < len(fo) and np.array_equal(row, fo[j]):
+            j += 1
+    assert j == len(fo) == info["triangles"] > 0
+    assert ((fo[:, 0] != fo[:, 1]) & (fo[:, 1] != fo[:, 2]) & (fo[:, 0] != fo[:, 2])).all()
+    assert len(np.unique(np.sort(fo, axis=1), axis=0)) == len(fo)
+    assert np.array_equal(np.unique(fo), np.arange(info["vertices"]))
+    assert info["degenerate"] + info["duplicate"] + info["triangles"] == f.shape[0] and info["degenerate"] > 0
+    # the mean of points of one cell lies in that cell: within one cell of every member, per coordinate
+    gap = np.abs(v[cluster[kept]] - p[kept])
+    assert (gap <= cell * (1 + 1e-12)).all() and gap.max() > 0.1 * cell
+    # the inputs are not written, and the result does not depend on the faces' dtype
+    p0, f0 = p.copy(), f.copy()
+    v32, f32, _, c32, i32 = mio.decimate_mesh(p, f.astype(np.int32), cell)
+    assert f32.dtype == np.int32 and np.array_equal(f32, fo) and v32.tobytes() == v.tobytes() and np.array_equal(c32, cluster) and i32 == info
+    assert np.array_equal(p, p0) and np.array_equal(f, f0)
+
+
+def test_a_tiny_cell_only_drops_the_unreferenced_vertices():
+    rng = np.random.default_rng(4)
+    p = rng.uniform(-2, 2, (60, 3))
+    f = rng.permutation(54).reshape(-1, 3).astype(np.int32) + 3          # vertices 0-2 and 57-59 are unreferenced
+    c = rng.integers(0, 256, (60, 4)).astype(np.uint8)
+    v, fo, co, cluster, info = mio.decimate_mesh(p, f, 1e-5, c)
+    used = np.zeros(60, bool)
+    used[f.reshape(-1)] = True
+    scan = np.cumsum(used) - used
+    assert np.array_equal(cluster, np.where(used, scan, -1))
+    assert v.tobytes() == p[used].tobytes() and np.array_equal(co, c[used]) and np.array_equal(fo, scan[f]) and fo.dtype == np.int32
+    assert info == {"clusters": 60, "vertices": 54, "triangles": 18, "degenerate": 0, "duplicate": 0}
+
+
+def test_a_cell_larger_than_the_mesh_leaves_nothing():
+    p, f = _cloud()
+    v, fo, co, cluster, info = mio.decimate_mesh(p + 3.5, f, 100.0, np.zeros((p.shape[0], 3), np.uint8))
+    assert v.shape == (0, 3) and fo.shape == (0, 3) and co.shape == (0, 3) and (cluster == -1).all()
+    assert info == {"clusters": 1, "vertices": 0, "triangles": 0, "degenerate": f.shape[0], "duplicate": 0}
+    # no vertex, no face
+    v, fo, _, cluster, info = mio.decimate_mesh(np.zeros((0, 3)), np.zeros((0, 3), np.int64), 1.0)
+    assert v.shape == (0, 3) and fo.shape == (0, 3) and cluster.shape == (0,) and info["clusters"] == 0 and info["vertices"] == 0
+    # vertices without faces
+    v, fo, _, cluster, info = mio.decimate_mesh(p, np.zeros((0, 3), np.int64), 1.0)
+    assert v.shape == (0, 3) and (cluster == -1).all() and info["clusters"] > 1 and info["vertices"] == 0
+
+
+def test_the_sum_is_sequential_in_ascending_member_order():
+    # one cluster of three members (0, 2, 3) in the cell [0, 2e16): left to right (1e16 + 1) + 1 = 1e16 (each 1 is rounded away), any order that adds
+    # the two 1s first gives 1e16 + 2
+    x = np.array([1e16, 5e16, 1.0, 1.0, 9e16])
+    p = np.stack([x, x[[2, 1, 0, 3, 4]], x[[2, 1, 3, 0, 4]]], 1)        # y: 1, 1e16, 1 ; z: 1, 1, 1e16
+    f = np.array([[0, 1, 4], [2, 1, 4], [3, 4, 1]])
+    v, fo, _, cluster, info = mio.decimate_mesh(p, f, 2e16)
+    assert np.array_equal(cluster, [0, 1, 0, 0, 2]) and info["duplicate"] == 2 and np.array_equal(fo, [[0, 1, 2]])
+    left_to_right = lambda a, b, c: ((0.0 + a) + b) + c
+    want = [left_to_right(1e16, 1.0, 1.0) / 3.0, left_to_right(1.0, 1e16, 1.0) / 3.0, left_to_right(1.0, 1.0, 1e16) / 3.0]
+    assert want[0] != want[2] and want[0] == 1e16 / 3.0 and want[2] == (1e16 + 2.0) / 3.0
+    assert v[0].tobytes() == np.array(want).tobytes()
+
+
+def test_colours_round_half_up():
+    p = np.array([[0.1, 0, 0], [0.2, 0, 0], [0.3, 0, 0], [5.1, 0, 0], [5.2, 0, 0], [9.1, 0, 0], [0, 9.1, 0]])
+    f = np.array([[0, 3, 5], [3, 5, 6]])
+    c = np.array([[1, 1, 255], [1, 2, 255], [2, 3, 254], [1, 0, 0], [2, 255, 1], [7, 8, 9], [3, 3, 3]], np.uint8)
+    v, fo, co, cluster, _ = mio.decimate_mesh(p, f, 1.0, c)
+    assert np.array_equal(cluster, [0, 0, 0, 1, 1, 2, 3])
+    # members 1, 1, 2 -> 4/3 -> 1; 1, 2, 3 -> 2; 255, 255, 254 -> 254.67 -> 255; members 1, 2 -> 1.5 -> 2; 0, 255 -> 127.5 -> 128; 0, 1 -> 0.5 -> 1
+    assert co.dtype == np.uint8 and np.array_equal(co, [[1, 2, 255], [2, 128, 1], [7, 8, 9], [3, 3, 3]])
+    c4 = np.concatenate([c, np.full((7, 1), 255, np.uint8)], 1)
+    assert np.array_equal(mio.decimate_mesh(p, f, 1.0, c4)[2], np.concatenate([co, np.full((4, 1), 255, np.uint8)], 1))
+
+
+def test_refusals():
+    p, f = _cloud(50, 40)
+    for cell in (-1.0, float("nan"), float("inf"), float("-inf")):
+        with pytest.raises(ValueError, match="cell"):
+            mio.decimate_mesh(p, f, cell)
+    for cell in (None, 0, 0.0):                                          # off: the very objects come back
+        out = mio.decimate_mesh(p, f, cell, None)
+        assert out[0] is p and out[1] is f and out[2:] == (None, None, None)
+    for bad in (float("nan"), float("inf")):
+        q = p.copy()
+        q[17, 1] = bad
+        with pytest.raises(ValueError, match="non-finite"):
+            mio.decimate_mesh(q, f, 1.0)
+    for bad in (-1, 50):
+        g = f.copy()
+        g[3, 2] = bad
+        with pytest.raises(ValueError, match="index outside"):
+            mio.decimate_mesh(p, g, 1.0)
+    # the extent, with two vertices: 2^21 - 1 cells apart is legal, 2^21 is not; negative coordinates all the same
+    one = np.zeros((0, 3), np.int64)
+    far = lambda k: np.array([[-5.5, 0.5, 0.5], [-5.5 + k, 0.5, 0.5]])
+    assert mio.decimate_mesh(far(2.0 ** 21 - 1), one, 1.0)[4]["clusters"] == 2
+    with pytest.raises(ValueError, match="2\\^21"):
+        mio.decimate_mesh(far(2.0 ** 21), one, 1.0)
+    with pytest.raises(ValueError, match="2\\^21"):
+        mio.decimate_mesh(np.array([[0.0, 0.0, -1e300], [0.0, 0.0, 1e300]]), one, 1e-300)          # p / cell overflows
+    for c in (np.zeros((50, 3), np.float32), np.zeros((50, 3), np.int32), np.zeros((50, 2), np.uint8), np.zeros((49, 3), np.uint8)):
+        with pytest.raises(ValueError, match="colours"):
+            mio.decimate_mesh(p, f, 1.0, c)
+
+
+@pytest.mark.parametrize("ext", [".glb", ".obj"])
+def test_convert_mesh_with_decimation_is_filter_then_twin_then_smoothing_then_writer(tmp_path, ext):
+    d = np.load(GOLDEN)
+    v, f = d["noise_cube:verts"].astype(np.float32), d["noise_cube:faces"]
+    c = np.random.default_rng(2).integers(0, 256, (v.shape[0], 4)).astype(np.uint8)
+    c[:, 3] = 255
+    ply = str(tmp_path / "m.ply")
+    mio.write_ply(ply, v, f, c)
+    writer = mio.write_glb if ext == ".glb" else mio.write_obj
+    B = lambda p: open(p, "rb").read()
+    for i, kw in enumerate((dict(), dict(keep_largest=True), dict(smooth_iterations=2), dict(min_component_faces=20, smooth_iterations=1))):
+        out = mio.convert_mesh(ply, str(tmp_path / f"s{i}{ext}"), decimate_cell=1.5, **kw)
+        rv, rf, rc = mio.read_ply(ply)
+        if "keep_largest" in kw or "min_component_faces" in kw:
+            rv, rf, rc, _, _, _ = mio.filter_components(rv, rf, rc, None, kw.get("min_component_faces", 0), kw.get("keep_largest", False))
+        dv, df, dc, _, info = mio.decimate_mesh(rv.astype(np.float64), rf, 1.5, rc)
+        assert 0 < info["vertices"] < rv.shape[0] and dc.shape == (info["vertices"], rc.shape[1])
+        dv = dv.astype(np.float32)
+        if kw.get("smooth_iterations"):
+            dv = mio.smooth_vertices(dv.astype(np.float64), df, kw["smooth_iterations"]).astype(np.float32)
+        av, af = mio.to_asset_frame(dv, df)
+        want = str(tmp_path / f"want{i}{ext}")
+        writer(want, av, af, dc)
+        assert B(out) == B(want), kw
+        # decimation off: the file convert_mesh always wrote
+        plain, off = str(tmp_path / f"p{i}{ext}"), str(tmp_path / f"o{i}{ext}")
+        mio.convert_mesh(ply, plain, **kw)
+        mio.convert_mesh(ply, off, decimate_cell=0, **kw)
+        assert B(plain) == B(off) != B(out)
+    for bad in (-2, float("nan")):
+        with pytest.raises(ValueError):
+            mio.convert_mesh(ply, str(tmp_path / ("bad" + ext)), decimate_cell=bad)
+
+
+def test_cabi_declares_and_exports_the_decimation_entries():
+    L = importlib.import_module("one-2-3-45_amd._lib")
+    protos = L.parse_header()
+    names = ("o2345_mesh_decimate_workspace_bytes", "o2345_mesh_decimate_count", "o2345_mesh_decimate_emit")
+    assert all(n in protos for n in names)
+    assert protos["o2345_mesh_decimate_count"][1][5] is ctypes.c_double and protos["o2345_mesh_decimate_workspace_bytes"][0] is ctypes.c_size_t
+    lib = L.lib()
+    assert all(hasattr(lib, n) for n in names) and lib.o2345_version() == 210
+    wsb = lib.o2345_mesh_decimate_workspace_bytes
+    assert 0 < wsb(0, 0) < wsb(1000, 2000) and wsb(1000, 2000) >= 12 * 2048 + 4 * 4096 and wsb(2 ** 30, 0) == 0 and wsb(3, (2 ** 31 + 2) // 3) == 0 and wsb(-1, 0) == 0
+    # argument checks come before any device work
+    out = [ctypes.c_longlong() for _ in range(5)]
+    refs = [ctypes.byref(x) for x in out]
+    err = lambda: lib.o2345_last_error()
+    count = lambda ib, nv, nt, cell, wsbytes=0: lib.o2345_mesh_decimate_count(None, None, ib, nv, nt, cell, None, wsbytes, *refs, None)
+    assert count(2, 3, 1, 1.0) != 0 and b"index_bytes" in err()
+    for cell in (0.0, -1.0, float("nan"), float("inf")):
+        assert count(4, 3, 1, cell) != 0 and b"cell" in err(), cell
+    assert count(4, 2 ** 30, 1, 1.0) != 0 and b"bad sizes" in err()
+    assert count(8, 3, (2 ** 31 + 2) // 3, 1.0) != 0 and b"bad sizes" in err()
+    assert count(8, -1, 0, 1.0) != 0 and b"bad sizes" in err()
+    assert count(4, 3, 1, 1.0) != 0 and b"null pointer" in err()
+    host = (ctypes.c_char * 64)()
+    small = lambda: lib.o2345_mesh_decimate_count(host, host, 4, 3, 1, 1.0, host, 64, *refs, None)
+    assert small() != 0 and b"workspace too small" in err()
+    assert lib.o2345_mesh_decimate_emit(None, None, 4, 3, 1, None, None, None, None, None) != 0 and b"null pointer" in err()
+    assert lib.o2345_mesh_decimate_emit(None, None, 3, 3, 1, None, None, None, None, None) != 0 and b"index_bytes" in err()
+    assert lib.o2345_mesh_decimate_emit(None, None, 4, 2 ** 30, 1, None, None, None, None, None) != 0 and b"bad sizes" in err()
+
+
+def _fresh_config(monkeypatch, **env):
+    monkeypatch.delenv("O2345_MESH_DECIMATE_CELL", raising=False)
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    path = importlib.import_module("one-2-3-45_amd.config").__file__
+    spec = importlib.util.spec_from_file_location("o2345_config_under_test", path)
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)                      # a private copy: the package's own config module is not touched
+    return mod
+
+
+def test_config_knob(monkeypatch):
+    c = _fresh_config(monkeypatch)
+    assert c.MESH_DECIMATE_CELL == 0.0 and c.mesh_decimate_cell() == 0.0
+    for off in ("", " ", "0", "0.0"):
+        assert _fresh_config(monkeypatch, O2345_MESH_DECIMATE_CELL=off).MESH_DECIMATE_CELL == 0.0
+    c = _fresh_config(monkeypatch, O2345_MESH_DECIMATE_CELL=" 2.5 ")
+    assert c.MESH_DECIMATE_CELL == 2.5 and c.mesh_decimate_cell() == 2.5 and c.mesh_decimate_cell(None) == 2.5
+    assert c.mesh_decimate_cell(0) == 0.0 and c.mesh_decimate_cell(3) == 3.0          # an explicit argument wins, 0 included
+    for bad in ("-1", "nan", "inf", "-inf", "two"):
+        with pytest.raises(ValueError, match="O2345_MESH_DECIMATE_CELL"):
+            _fresh_config(monkeypatch, O2345_MESH_DECIMATE_CELL=bad)
+    for bad in (-0.5, float("nan"), float("inf")):
+        with pytest.raises(ValueError):
+            c.mesh_decimate_cell(bad)

@@ -10,6 +10,10 @@ fed the same arrays.  Two meshes: BASELINE config 2 (8 views, 128^3 volume, 256^
   smooth     Taubin smoothing (csrc/mesh_smooth.hip), 10 iterations with the config's factors, on the config's mesh: the adjacency build alone (two-call
              protocol, one synchronisation), the 20 step launches alone on a table built before, the whole op, the host twin (mesh_io.smooth_vertices,
              host clock, one call) on the same mesh, and whole-export variants inside the same alternating loop as the unsmoothed ones
+  decimate   vertex clustering (csrc/mesh_decimate.hip) at cell 2 on the config's mesh: the sizes out, bytes-equality with the host twin
+             (mesh_io.decimate_mesh, host clock, one call), the op alone (HIP events around the two-call protocol, which synchronises once in the
+             middle), the gradient + colour time on the decimated vertices next to grad_color_all, and whole-export variants inside the same
+             alternating loop as the others
 Medians over --reps calls after --warmup calls; the ratio against the PLY of the SAME run is what to read.  Prints one JSON line.
 
     python tools/time_mesh_export.py [--reps 9] [--warmup 3] [--skip-512]
@@ -149,6 +153,19 @@ def one_mesh(dev, wt, tmp, D, R, ray_scale, a, numpy_writer):
                                    "steps": med_events(steps, a.reps, a.warmup),
                                    "mesh_smooth": med_events(lambda: ops.mesh_smooth(verts_idx, tris, IT), a.reps, a.warmup)},
                      "host_adjacency_ms_once": (t1 - t0) * 1e3, "host_twin_ms_once": (t2 - t1) * 1e3}
+    # decimation at cell 2: the op alone, the host twin on the same arrays, and the gradient + colour work that is left
+    CELL = 2.0
+    d_verts, d_tris, _, d_info = ops.mesh_decimate(verts_idx, tris, CELL)
+    t0 = time.perf_counter()
+    twin = mio.decimate_mesh(hv, hf, CELL)
+    t1 = time.perf_counter()
+    res["decimate"] = dict(d_info, cell=CELL, largest_cluster=int(np.bincount(twin[3][twin[3] >= 0]).max()) if d_info["vertices"] else 0,
+                           equals_host_twin=bool(d_verts.cpu().numpy().tobytes() == twin[0].tobytes() and np.array_equal(d_tris.cpu().numpy(), twin[1])
+                                                 and d_info == twin[4]),
+                           kernel_ms={"mesh_decimate": med_events(lambda: ops.mesh_decimate(verts_idx, tris, CELL), a.reps, a.warmup),
+                                      "grad_color_all": med_events(lambda: grad_color(verts_idx), a.reps, a.warmup),
+                                      "grad_color_decimated": med_events(lambda: grad_color(d_verts), a.reps, a.warmup)},
+                           host_twin_ms_once=(t1 - t0) * 1e3)
     A = (wt, vol, inp["proj"], inp["cam_pos"], R)
     whole = {
         "ply": lambda: pipeline.export_mesh_ply(P(".ply"), *A),
@@ -160,6 +177,9 @@ def one_mesh(dev, wt, tmp, D, R, ray_scale, a, numpy_writer):
         "ply_smooth10": lambda: pipeline.export_mesh_ply(P("_s.ply"), *A, smooth_iterations=IT),
         "glb_smooth10": lambda: pipeline.export_mesh_asset(P("_s.glb"), *A, smooth_iterations=IT),
         "obj_smooth10": lambda: pipeline.export_mesh_asset(P("_s.obj"), *A, smooth_iterations=IT),
+        "ply_decimate2": lambda: pipeline.export_mesh_ply(P("_d.ply"), *A, decimate_cell=CELL),
+        "glb_decimate2": lambda: pipeline.export_mesh_asset(P("_d.glb"), *A, decimate_cell=CELL),
+        "obj_decimate2": lambda: pipeline.export_mesh_asset(P("_d.obj"), *A, decimate_cell=CELL),
     }
     # alternated like the stage variants; the spread (min .. max) of each is what a difference between two of them has to exceed
     for fn in whole.values():
