@@ -49,7 +49,8 @@ const char* o2345_last_error(void);
  * o2345_mesh_asset_vertices, o2345_mesh_asset_indices, o2345_obj_text_bytes, o2345_obj_text, o2345_obj_text_host; the mesh component entries
  * o2345_mesh_components_workspace_bytes, o2345_mesh_components_count, o2345_mesh_components_emit; the adjacency and smoothing entries
  * o2345_mesh_adjacency_workspace_bytes, o2345_mesh_adjacency_count, o2345_mesh_adjacency_emit, o2345_mesh_smooth; the decimation entries
- * o2345_mesh_decimate_workspace_bytes, o2345_mesh_decimate_count, o2345_mesh_decimate_emit. */
+ * o2345_mesh_decimate_workspace_bytes, o2345_mesh_decimate_count, o2345_mesh_decimate_emit; the projection entries
+ * o2345_mesh_project_workspace_bytes, o2345_mesh_project. */
 int o2345_version(void);
 /* Layout self-description of O2345RenderIO as THIS library was compiled (sizeof, and offsetof of every field in declaration order): a binding
  * asserts its own struct against it at load time (one-2-3-45_amd/_lib.py does) -- a field added on one side only cannot corrupt calls silently.
@@ -403,6 +404,35 @@ int o2345_mesh_decimate_count(const double* verts, const void* tris, int index_b
                               long long* n_degenerate_host, long long* n_duplicate_host, void* stream);
 int o2345_mesh_decimate_emit(const double* verts, const void* tris, int index_bytes, long long nv, long long nt, void* workspace, double* verts_out,
                              void* tris_out, int* cluster, void* stream);
+
+/* ---- projection of the vertices onto a level set of the SDF (additive since 2.1; the reference has no such step: its marching-cubes vertices,
+ * sparse_neus_renderer.py:907-937, lie on the zero set only as far as linear interpolation along a grid edge allows, and validate_colored_mesh,
+ * trainer_generic.py:1309-1363, colours them where they are) ------------------------------------------------------------------------------------------
+ * A few Newton steps p <- p - (s - level) g / |g|^2 per vertex, (s, g) from the SDF kernels of this library (sdf_mode 0: o2345_sdf_mlp_ex variant 2;
+ * 2: o2345_sdf_grad_x3; sign 1).  Index units (one grid spacing = 1); bmin / bmax = the float32 bounds widened to fp64, ext = bmax - bmin; all of the
+ * following in fp64, one operation at a time, in the order written, without a square root.  World point w_k = x_k / (R - 1) * ext_k + bmin_k; the network
+ * sees float32(w).  A round evaluates (s, g) at every ACTIVE vertex (all in round 0); then, o the input position and x the current one:
+ *   r = |double(s) - level|;  s or g non-finite, or g2 = (gx gx + gy gy) + gz gz not > 0: STALLED, the vertex leaves the active set and keeps x;
+ *   else r <= tol: CONVERGED, leaves and keeps x;  else, in rounds 0 .. iterations - 1: t = (double(s) - level) / g2, d_k = t g_k,
+ *   e_k = d_k / ext_k * (R - 1) clamped to [-max_step, max_step] per axis, y_k = x_k - e_k clamped to [o_k - max_move, o_k + max_move], then to
+ *   [0, R - 1], x <- y; each of the three clamps that changes a value counts one clamped event;  else (round `iterations` only classifies): UNCONVERGED.
+ * Exact and deterministic: equal to mesh_io.project_vertices, given these kernels as its field, to the last bit; the order of the active lists
+ * changes between runs and does not change a result.  Not promised: that a vertex stays on its sheet of the surface beyond the max_move box, or that
+ * triangles keep their orientation where the surface folds inside one cell.
+ * blob, vol_cl, D as for o2345_sdf_mlp; verts device fp64 [nv,3], only read; 0 <= nv < 2^30; grid_R >= 2; bound_min / bound_max HOST float32 [3] as
+ * for o2345_mesh_pack_vertices, bound_max > bound_min; iterations in [1, 64]; level finite; tol finite, >= 0; max_step, max_move finite, > 0.
+ * workspace: mesh_project_workspace_bytes(nv) bytes (0 for bad sizes), 16-byte aligned.  verts_out device fp64 [nv,3], not verts.  stats: device,
+ * 328 bytes, 8-byte aligned, written by this call:
+ *   uint64 [8]  = vertices with a non-finite coordinate, converged, unconverged, stalled, clamped events, max_before, max_after, 0 -- the two maxima
+ *                 as the bit pattern of a non-negative double (max of r in round 0; max of the r at which the vertices left or ended; non-finite r
+ *                 take no part; 0 for an empty mesh);
+ *   int32 [66]  = active vertices per round, entries 0 .. iterations; the rest 0.
+ * No host synchronisation: all rounds are queued at once, the counts stay on the device.  A non-zero first counter means bad input: the caller raises
+ * (the affected vertices stall, nothing is dereferenced through them).  Errors: bad arguments, a workspace that is too small. */
+size_t o2345_mesh_project_workspace_bytes(long long nv);
+int o2345_mesh_project(const float* blob, const float* vol_cl, int D, int sdf_mode, const double* verts, long long nv, int grid_R, const float* bound_min,
+                       const float* bound_max, int iterations, double level, double tol, double max_step, double max_move, void* workspace,
+                       size_t workspace_bytes, double* verts_out, void* stats, void* stream);
 
 /* ---- mesh serialisation (replaces the numpy / trimesh tail of validate_mesh and validate_colored_mesh,
  * models/trainer_generic.py:1287-1303, 1365-1382: index -> world frame, scale_mat, trans_mat, uint8 colours, PLY records) -----

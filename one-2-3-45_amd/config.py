@@ -162,3 +162,53 @@ def mesh_decimate_cell(x=None):
     if x is None:
         return MESH_DECIMATE_CELL
     return _finite_float("decimate_cell", repr(float(x)), None, lambda c: c >= 0.0, "a finite float >= 0")
+
+
+# ---- mesh projection (csrc/mesh_project.hip; mesh_io.project_vertices is the host twin) -----------------------------------------------------------------
+# O2345_MESH_PROJECT_ITERATIONS=n moves the vertices of the extracted mesh onto the SDF's zero set with up to n Newton steps p <- p - s g / |g|^2 on the
+# device, after the decimation and before the vertices are coloured ("" or "0" = off, the default: nothing is launched; at most 64).
+# O2345_MESH_PROJECT_TOL (5e-5: the SDF tolerance DESIGN.md section 4 states -- projecting further than the field is accurate is pointless) is the |sdf| at
+# which a vertex counts as converged, O2345_MESH_PROJECT_MAX_STEP (0.5) the largest step per axis and round and O2345_MESH_PROJECT_MAX_MOVE ("" = max(1,
+# decimate cell), so that a cluster mean can travel back as far as its cell allows) the half edge of the box around its start that a vertex never leaves,
+# both in grid spacings.
+def _project_iterations(name, n):
+    if n > 64:
+        raise ValueError(f"{name} must be an integer in [0, 64], got {n!r}")
+    return n
+
+
+MESH_PROJECT_ITERATIONS = _project_iterations("O2345_MESH_PROJECT_ITERATIONS",
+                                              _non_negative_int("O2345_MESH_PROJECT_ITERATIONS", os.environ.get("O2345_MESH_PROJECT_ITERATIONS", "")))
+MESH_PROJECT_TOL = _finite_float("O2345_MESH_PROJECT_TOL", os.environ.get("O2345_MESH_PROJECT_TOL", ""), 5e-5, lambda x: x >= 0.0, "a finite float >= 0")
+MESH_PROJECT_MAX_STEP = _finite_float("O2345_MESH_PROJECT_MAX_STEP", os.environ.get("O2345_MESH_PROJECT_MAX_STEP", ""), 0.5, lambda x: x > 0.0, "a finite float > 0")
+MESH_PROJECT_MAX_MOVE = _finite_float("O2345_MESH_PROJECT_MAX_MOVE", os.environ.get("O2345_MESH_PROJECT_MAX_MOVE", ""), None, lambda x: x > 0.0, "a finite float > 0")
+
+
+def mesh_project_iterations(n=None):
+    """None -> the configured default; anything else must be an integer in [0, 64] (an explicit 0 is off whatever the default)."""
+    if n is None:
+        return MESH_PROJECT_ITERATIONS
+    if isinstance(n, bool) or int(n) != n or n < 0:
+        raise ValueError(f"project_iterations must be an integer in [0, 64], got {n!r}")
+    return _project_iterations("project_iterations", int(n))
+
+
+def mesh_project_tol(x=None):
+    if x is None:
+        return MESH_PROJECT_TOL
+    return _finite_float("tol", repr(float(x)), None, lambda t: t >= 0.0, "a finite float >= 0")
+
+
+def mesh_project_max_step(x=None):
+    if x is None:
+        return MESH_PROJECT_MAX_STEP
+    return _finite_float("max_step", repr(float(x)), None, lambda t: t > 0.0, "a finite float > 0")
+
+
+def mesh_project_max_move(x=None, decimate_cell=None):
+    """None -> the configured default, and where that is unset max(1, decimate cell) with the cell of this call (None: the configured one)."""
+    if x is not None:
+        return _finite_float("max_move", repr(float(x)), None, lambda t: t > 0.0, "a finite float > 0")
+    if MESH_PROJECT_MAX_MOVE is not None:
+        return MESH_PROJECT_MAX_MOVE
+    return max(1.0, mesh_decimate_cell(decimate_cell))

@@ -584,6 +584,111 @@ def decimate_mesh(verts, faces, cell, colors=None):
     return v_out, f_out, c_out, cluster, info
 
 
+# ------------------------------------------------------------------------------------------------------------------ projection
+def _check_project_args(resolution, iterations, level, tol, max_step, max_move, bound_min, bound_max):
+    if isinstance(iterations, (bool, np.bool_)) or not isinstance(iterations, (int, np.integer)) or not 1 <= iterations <= 64:
+        raise ValueError(f"project: iterations must be an integer in [1, 64], got {iterations!r}")
+    if isinstance(resolution, (bool, np.bool_)) or not isinstance(resolution, (int, np.integer)) or resolution < 2:
+        raise ValueError(f"project: resolution must be an integer >= 2, got {resolution!r}")
+    level, tol, max_step, max_move = float(level), float(tol), float(max_step), float(max_move)
+    if not np.isfinite(level):
+        raise ValueError(f"project: level must be finite, got {level!r}")
+    if not (np.isfinite(tol) and tol >= 0.0):
+        raise ValueError(f"project: tol must be finite and >= 0, got {tol!r}")
+    if not (np.isfinite(max_step) and max_step > 0.0):
+        raise ValueError(f"project: max_step must be finite and > 0, got {max_step!r}")
+    if not (np.isfinite(max_move) and max_move > 0.0):
+        raise ValueError(f"project: max_move must be finite and > 0, got {max_move!r}")
+    b0 = np.asarray(bound_min, np.float32).reshape(-1).astype(np.float64)          # float32 values, widened
+    b1 = np.asarray(bound_max, np.float32).reshape(-1).astype(np.float64)
+    if b0.shape != (3,) or b1.shape != (3,) or not (np.isfinite(b0).all() and np.isfinite(b1).all() and (b1 > b0).all()):
+        raise ValueError(f"project: bound_max must be above bound_min on every axis, both finite, got {bound_min!r} and {bound_max!r}")
+    return int(resolution), int(iterations), level, tol, max_step, max_move, b0, b1 - b0
+
+
+def project_vertices(verts_idx, field, resolution, iterations, level=0.0, tol=5e-5, max_step=0.5, max_move=1.0, bound_min=(-1.0, -1.0, -1.0),
+                     bound_max=(1.0, 1.0, 1.0)):
+    """Newton projection of mesh vertices onto the level set ``sdf == level`` (host twin of ops.mesh_project, and the definition of its result, to the last
+    bit when ``field`` is the device's own SDF kernel) -> (verts float64 [n,3] in index coordinates, info).  ``verts_idx`` float64 [n,3], index coordinates
+    on a ``resolution``^3 grid (one grid spacing = 1); ``field(pts32 [m,3] float32) -> (s float32 [m], g float32 [m,3])`` is the SDF and its gradient at
+    world points.  All arithmetic below is float64, every operation separate (never fused) and in the order written; there is no square root.
+    With o the input position of a vertex and x its current one, bmin / bmax the float32 bounds widened to float64, ext = bmax - bmin:
+    world point w_k = x_k / (R - 1) * ext_k + bmin_k, and the field sees float32(w) -- for (-1, 1) the pipeline's verts_idx / (R - 1) * 2 - 1 to the bit.
+    A round evaluates (s, g) at every ACTIVE vertex (all in round 0), then per vertex: r = |float64(s) - level|;
+      * s or g non-finite, or g2 = (gx gx + gy gy) + gz gz not > 0: STALLED -- the vertex leaves the active set and keeps x;
+      * else r <= tol: CONVERGED -- leaves and keeps x;
+      * else, in rounds 0 .. iterations - 1: t = (float64(s) - level) / g2; d_k = t g_k; e_k = d_k / ext_k * (R - 1), clamped to [-max_step, max_step] per
+        axis; y_k = x_k - e_k, clamped to [o_k - max_move, o_k + max_move], then to [0, R - 1]; x <- y.  Each of the three clamps that changes a value
+        counts one ``clamped`` event (up to nine per vertex and round);
+      * else (round ``iterations``, the last, only classifies): UNCONVERGED.
+    (s, g) -> (-s, -g) with level -> -level gives the same steps.  ``info`` = {"evaluated": the active count of each of the iterations + 1 rounds,
+    "converged", "unconverged", "stalled", "clamped", "max_before": the largest r of round 0, "max_after": the largest r at which a vertex left or ended};
+    the two maxima are Python floats, 0.0 for an empty mesh, and a non-finite r takes no part in them.  NOT promised: that a vertex stays on its sheet of
+    the surface beyond the max_move box, or that triangles keep their orientation where the surface folds inside one cell.  Refused (ValueError): a
+    non-finite coordinate, iterations outside [1, 64], a non-finite level, tol not finite or < 0, max_step or max_move not finite or <= 0, a bound with
+    bmax <= bmin, resolution < 2."""
+    R, iterations, level, tol, max_step, max_move, b0, ext = _check_project_args(resolution, iterations, level, tol, max_step, max_move, bound_min, bound_max)
+    o = np.array(verts_idx, dtype=np.float64).reshape(-1, 3)            # a copy: the input is never written
+    if not np.isfinite(o).all():
+        raise ValueError("project: non-finite vertex coordinate")
+    n = o.shape[0]
+    rm1 = float(R - 1)
+    x = o.copy()
+    lo, hi = o - max_move, o + max_move
+    info = {"evaluated": [], "converged": 0, "unconverged": 0, "stalled": 0, "clamped": 0, "max_before": 0.0, "max_after": 0.0}
+
+    def finite_max(r):
+        r = r[np.isfinite(r)]
+        return float(r.max()) if r.size else 0.0
+
+    def clamp(a, low, high):
+        """-> (a limited to [low, high] by comparison, the number of values that changed)"""
+        under, over = a < low, a > high
+        return np.where(under, low, np.where(over, high, a)), int(np.count_nonzero(under)) + int(np.count_nonzero(over))
+
+    active = np.arange(n)
+    for rnd in range(iterations + 1):
+        info["evaluated"].append(int(active.size))
+        if active.size == 0:
+            continue
+        with np.errstate(over="ignore"):
+            pts32 = np.ascontiguousarray((x[active] / rm1 * ext + b0).astype(np.float32))
+        s, g = field(pts32)
+        s, g = np.asarray(s).reshape(-1), np.asarray(g).reshape(-1, 3)
+        if s.dtype != np.float32 or g.dtype != np.float32 or s.shape[0] != active.size or g.shape[0] != active.size:
+            raise ValueError("project: the field must return float32 (s [m], g [m,3]) for the m points it is given")
+        finite = np.isfinite(s) & np.isfinite(g).all(axis=1)
+        with np.errstate(invalid="ignore", over="ignore"):
+            s64, g64 = s.astype(np.float64), g.astype(np.float64)
+            ds = s64 - level
+            r = np.abs(ds)
+            g2 = g64[:, 0] * g64[:, 0] + g64[:, 1] * g64[:, 1] + g64[:, 2] * g64[:, 2]
+            stalled = ~finite | ~(g2 > 0.0)
+        converged = ~stalled & (r <= tol)
+        moving = ~stalled & ~converged
+        if rnd == 0:
+            info["max_before"] = finite_max(r)
+        info["stalled"] += int(np.count_nonzero(stalled))
+        info["converged"] += int(np.count_nonzero(converged))
+        if rnd == iterations:
+            info["unconverged"] += int(np.count_nonzero(moving))
+            info["max_after"] = max(info["max_after"], finite_max(r))
+            break
+        info["max_after"] = max(info["max_after"], finite_max(r[~moving]))
+        idx = active[moving]
+        t = ds[moving] / g2[moving]
+        d = t[:, None] * g64[moving]
+        e = d / ext * rm1
+        e, c0 = clamp(e, -max_step, max_step)
+        y = x[idx] - e
+        y, c1 = clamp(y, lo[idx], hi[idx])
+        y, c2 = clamp(y, 0.0, rm1)
+        x[idx] = y
+        info["clamped"] += c0 + c1 + c2
+        active = idx
+    return x, info
+
+
 def convert_mesh(ply_path, out_path, min_component_faces=0, keep_largest=False, smooth_iterations=0, decimate_cell=0):
     """convert_mesh_format (utils/utils.py:31-47) for a mesh already on disk: read the PLY, exchange y and z, reverse the faces, write ``out_path`` by its
     extension (.glb or .obj) with the PLY's vertex colours.  ``min_component_faces`` / ``keep_largest``: filter_components on the way (off by default).
@@ -592,7 +697,9 @@ def convert_mesh(ply_path, out_path, min_component_faces=0, keep_largest=False, 
     coordinates before the frame transform rounds them to float32.
     ``decimate_cell`` (0 = off): decimate_mesh after the filter and before the smoothing, with the cell in the FILE's own units, on the float32 positions
     cast to float64, the result cast back to float32, the colours merged as decimate_mesh defines.  For the same reason that is not byte-equal to the
-    device export, which clusters the index coordinates (cell in units of the grid spacing) and colours the new vertices.  Returns ``out_path``."""
+    device export, which clusters the index coordinates (cell in units of the grid spacing) and colours the new vertices.
+    There is no ``project_iterations`` here: projecting vertices onto the SDF's zero set (project_vertices, ops.mesh_project) needs the network, and a
+    mesh file has none.  Returns ``out_path``."""
     ext = _asset_ext(out_path)
     if ext == ".ply":
         raise ValueError("convert_mesh: the output is .glb or .obj")

@@ -997,3 +997,51 @@ def mesh_decimate(verts_idx, tris, cell=None):
     check(L.o2345_mesh_decimate_emit(_p(verts_idx, torch.float64), _p(tris, tris.dtype), ib, nv, nt, _p(ws, torch.uint8), _p(verts, torch.float64),
                                      _p(tris_out, tris.dtype), _p(cluster, torch.int32), _stream()), "mesh_decimate_emit")
     return verts, tris_out, cluster, {"clusters": ncl.value, "vertices": nvo.value, "triangles": nto.value, "degenerate": ndeg.value, "duplicate": ndup.value}
+
+
+# ---------------------------------------------------------------------------------------------------------- mesh projection
+_PROJECT_STATS_BYTES = 328          # include/o2345.h: uint64 [8] + int32 [66]
+
+
+@_on_device
+def mesh_project(blob, vol_cl, verts_idx, resolution, iterations, level=0.0, tol=None, max_step=None, max_move=None, bound_min=(-1.0, -1.0, -1.0),
+                 bound_max=(1.0, 1.0, 1.0), precision=None):
+    """Newton projection of mesh vertices onto the level set ``sdf == level`` on the device (== mesh_io.project_vertices with
+    ``ops.sdf_mlp(blob, vol_cl, pts, variant=2, precision=precision)`` as its field, to the last bit; definitions in csrc/mesh_project.hip).  verts_idx
+    fp64 [N,3] index coordinates on a ``resolution``^3 grid over ``bound_min`` .. ``bound_max``; ``iterations`` in [0, 64] (None: the config default);
+    ``tol`` / ``max_step`` / ``max_move`` None: the config defaults -> (verts fp64 [N,3], info = {"evaluated", "converged", "unconverged", "stalled",
+    "clamped", "max_before", "max_after"}).  All rounds are queued at once; one small D2H copy of the counters and one synchronisation at the end.  The
+    input is not written.  With 0 iterations nothing is launched: ``verts_idx`` itself is returned, and ``info`` is None."""
+    iterations = config.mesh_project_iterations(iterations)
+    if iterations == 0:
+        return verts_idx, None
+    tol, max_step, max_move = config.mesh_project_tol(tol), config.mesh_project_max_step(max_step), config.mesh_project_max_move(max_move)
+    level = float(level)
+    if not np.isfinite(level):
+        raise ValueError(f"mesh_project: level must be finite, got {level!r}")
+    if isinstance(resolution, bool) or int(resolution) != resolution or resolution < 2:
+        raise ValueError(f"mesh_project: resolution must be an integer >= 2, got {resolution!r}")
+    if verts_idx.dtype != torch.float64 or verts_idx.dim() != 2 or verts_idx.shape[1] != 3:
+        raise ValueError(f"expected vertices [N,3] float64, got {tuple(verts_idx.shape)} {verts_idx.dtype}")
+    (bmin, pmin), (bmax, pmax) = _host3(bound_min), _host3(bound_max)
+    if bmin.shape != (3,) or bmax.shape != (3,) or not (np.isfinite(bmin).all() and np.isfinite(bmax).all() and (bmax > bmin).all()):
+        raise ValueError(f"mesh_project: bound_max must be above bound_min on every axis, both finite, got {bound_min!r} and {bound_max!r}")
+    mode = 2 if config.sdf_precision(precision) == "f16x3" else 0
+    L = _lib.lib()
+    nv, dev = verts_idx.shape[0], verts_idx.device
+    wsb = L.o2345_mesh_project_workspace_bytes(nv)
+    ws = _workspace(wsb, dev, "mesh_project")
+    out = torch.empty(nv, 3, dtype=torch.float64, device=dev)
+    stats = torch.empty(_PROJECT_STATS_BYTES, dtype=torch.uint8, device=dev)
+    check(L.o2345_mesh_project(_p(blob), _p(vol_cl), vol_cl.shape[0], mode, _p(verts_idx, torch.float64), nv, int(resolution), pmin, pmax, iterations, level,
+                               tol, max_step, max_move, _p(ws, torch.uint8), wsb, _p(out, torch.float64), _p(stats, torch.uint8), _stream()), "mesh_project")
+    return out, project_info(stats.cpu().numpy(), iterations)
+
+
+def project_info(stats, iterations):
+    """The stats block of o2345_mesh_project (328 bytes, on the host) -> the info dict of mesh_io.project_vertices; raises on a non-finite coordinate."""
+    head, counts = stats[:64].view(np.uint64), stats[64:_PROJECT_STATS_BYTES].view(np.int32)
+    if int(head[0]):
+        raise RuntimeError(f"o2345 mesh_project: {int(head[0])} vertices have a non-finite coordinate")
+    return {"evaluated": [int(c) for c in counts[:iterations + 1]], "converged": int(head[1]), "unconverged": int(head[2]), "stalled": int(head[3]),
+            "clamped": int(head[4]), "max_before": float(head[5:6].view(np.float64)[0]), "max_after": float(head[6:7].view(np.float64)[0])}

@@ -186,7 +186,8 @@ def render_scene_split(wt, imgs, affine_mats, origin, D, voxel_size, proj, cam_p
     return sh.gather_ray_blocks(block, rays_o.shape[0], per, device=dev), vol
 
 
-def _mesh_fields(wt, vol, proj, cam_pos, resolution, min_component_faces=None, keep_largest=None, info=None, smooth_iterations=None, decimate_cell=None):
+def _mesh_fields(wt, vol, proj, cam_pos, resolution, min_component_faces=None, keep_largest=None, info=None, smooth_iterations=None, decimate_cell=None,
+                 project_iterations=None):
     """The device work of extract_mesh, once: (verts fp64 in [-1, 1], verts_idx fp64 index coordinates, tris, rgb, u, grad).  ``grad`` is the SDF gradient
     at the vertices that the colour network takes as its normal input (None for an empty mesh): the asset export reuses it for the NORMAL attribute.
     ``min_component_faces`` / ``keep_largest`` (None: the config default, off unless set): the component filter (ops.mesh_filter_components) right after
@@ -197,10 +198,15 @@ def _mesh_fields(wt, vol, proj, cam_pos, resolution, min_component_faces=None, k
     ``verts_idx`` differ from an unsmoothed call; with 0 nothing is launched.
     ``decimate_cell`` (None: the config default, 0 = off): decimation by vertex clustering (ops.mesh_decimate), the cell in units of the extraction grid's
     spacing (index coordinates), after the component filter and BEFORE gradient and colours, which are therefore taken at the new vertices; smoothing
-    runs on the decimated mesh.  ``info`` also receives "decimate" (the op's counts, or None when it is off: nothing is launched then)."""
+    runs on the decimated mesh.  ``info`` also receives "decimate" (the op's counts, or None when it is off: nothing is launched then).
+    ``project_iterations`` (None: the config default, 0 = off): Newton projection of the vertices onto the SDF's zero set (ops.mesh_project; tolerance,
+    step and move limits from config, the move limit max(1, cell) unless configured) after the decimation and BEFORE gradient and colours, which are
+    therefore taken at the projected vertices; triangles and ``u`` are untouched.  Smoothing still runs last and deliberately leaves the surface: its
+    result is not projected again.  ``info`` also receives "project" (the op's info, or None when it is off: nothing is launched then)."""
     min_faces, largest = config.mesh_min_component_faces(min_component_faces), config.mesh_keep_largest(keep_largest)
     smooth = config.mesh_smooth_iterations(smooth_iterations)
     cell = config.mesh_decimate_cell(decimate_cell)
+    project = config.mesh_project_iterations(project_iterations)
     prec = wt.sdf_precision
     u = ops.sdf_mlp(wt.sdf_blob, vol["vol_cl"], None, variant=0, grid_R=resolution, sign=-1.0, precision=prec, grid_tables=wt.grid_tables(resolution))["sdf"]
     u = u.view(resolution, resolution, resolution)
@@ -211,9 +217,14 @@ def _mesh_fields(wt, vol, proj, cam_pos, resolution, min_component_faces=None, k
     dec = None
     if cell:
         verts_idx, tris, _, dec = ops.mesh_decimate(verts_idx, tris, cell)
+    pro = None
+    if project:
+        verts_idx, pro = ops.mesh_project(wt.sdf_blob, vol["vol_cl"], verts_idx, resolution, project, max_move=config.mesh_project_max_move(None, cell),
+                                          precision=prec)
     if info is not None:
         info["components"], info["components_kept"] = (cc["components"], cc["components_kept"]) if cc else (None, None)
         info["decimate"] = dec
+        info["project"] = pro
     verts = (verts_idx / (resolution - 1.0) * 2.0 - 1.0)                      # sparse_neus_renderer.py:936
     pts = verts.to(torch.float32).contiguous()
     if pts.shape[0] == 0:
@@ -230,53 +241,56 @@ def _mesh_fields(wt, vol, proj, cam_pos, resolution, min_component_faces=None, k
 
 @torch.no_grad()
 def extract_mesh(wt, vol, proj, cam_pos, resolution, return_index_verts=False, min_component_faces=None, keep_largest=None, smooth_iterations=None,
-                 decimate_cell=None):
-    """extract_fields + marching cubes [+ component filter] [+ decimation] + vertex colouring (trainer_generic.py:1309-1363) [+ smoothing], all on the
-    device."""
+                 decimate_cell=None, project_iterations=None):
+    """extract_fields + marching cubes [+ component filter] [+ decimation] [+ projection onto the zero set] + vertex colouring
+    (trainer_generic.py:1309-1363) [+ smoothing], all on the device."""
     verts, verts_idx, tris, rgb, u, _ = _mesh_fields(wt, vol, proj, cam_pos, resolution, min_component_faces, keep_largest, smooth_iterations=smooth_iterations,
-                                                     decimate_cell=decimate_cell)
+                                                     decimate_cell=decimate_cell, project_iterations=project_iterations)
     return (verts_idx if return_index_verts else verts), tris, rgb, u
 
 
 @torch.no_grad()
 def export_mesh_ply(path, wt, vol, proj, cam_pos, resolution, scale_mat=None, trans_mat=None, min_component_faces=None, keep_largest=None,
-                    smooth_iterations=None, decimate_cell=None):
+                    smooth_iterations=None, decimate_cell=None, project_iterations=None):
     """validate_colored_mesh end to end (trainer_generic.py:1309-1382): SDF grid, marching cubes, vertex colours, frame transforms,
     uint8 colours and the binary PLY -- records packed on the device (csrc/mesh_pack.hip), one D2H copy, one file write.
-    ``min_component_faces`` / ``keep_largest`` / ``decimate_cell`` / ``smooth_iterations``: the component filter, the decimation and the smoothing of
-    _mesh_fields.
+    ``min_component_faces`` / ``keep_largest`` / ``decimate_cell`` / ``project_iterations`` / ``smooth_iterations``: the component filter, the
+    decimation, the projection and the smoothing of _mesh_fields.
     Returns (n_vertices, n_triangles)."""
     from . import mesh_io
     verts_idx, tris, rgb, _ = extract_mesh(wt, vol, proj, cam_pos, resolution, return_index_verts=True, min_component_faces=min_component_faces,
-                                           keep_largest=keep_largest, smooth_iterations=smooth_iterations, decimate_cell=decimate_cell)
+                                           keep_largest=keep_largest, smooth_iterations=smooth_iterations, decimate_cell=decimate_cell,
+                                           project_iterations=project_iterations)
     return mesh_io.export_mesh(path, verts_idx, tris, resolution, scale_mat=scale_mat, trans_mat=trans_mat,
                                vertex_colors=rgb if verts_idx.shape[0] else None)
 
 
 @torch.no_grad()
 def export_mesh_asset(path, wt, vol, proj, cam_pos, resolution, scale_mat=None, trans_mat=None, normals=False, min_component_faces=None, keep_largest=None,
-                      smooth_iterations=None, decimate_cell=None):
+                      smooth_iterations=None, decimate_cell=None, project_iterations=None):
     """export_mesh_ply followed by convert_mesh_format (utils/utils.py:31-47) without the PLY in between: the coloured mesh as ``.glb`` or ``.obj`` in the
     asset frame ((x, y, z) -> (x, z, y), faces reversed), buffers / text packed on the device (csrc/mesh_export.hip).  ``normals=True`` adds unit vertex
-    normals from the SDF gradient the vertex colouring already computed (at the unsmoothed vertices when ``smooth_iterations`` is on).  A ``.ply`` path
+    normals from the SDF gradient the vertex colouring already computed (at the unsmoothed vertices when ``smooth_iterations`` is on, at the projected ones
+    when ``project_iterations`` is).  A ``.ply`` path
     gives export_mesh_ply's file.  Returns (n_vertices, n_triangles)."""
     from . import mesh_io
     _, verts_idx, tris, rgb, _, g = _mesh_fields(wt, vol, proj, cam_pos, resolution, min_component_faces, keep_largest, smooth_iterations=smooth_iterations,
-                                                 decimate_cell=decimate_cell)
+                                                 decimate_cell=decimate_cell, project_iterations=project_iterations)
     return mesh_io.export_asset(path, verts_idx, tris, resolution, scale_mat=scale_mat, trans_mat=trans_mat,
                                 vertex_colors=rgb if verts_idx.shape[0] else None, normals=g if normals else None)
 
 
 @torch.no_grad()
 def reconstruct_folder(root_dir, name, wt, out_ply, D=96, resolution=256, render_val_image=False, output_format=None, min_component_faces=None,
-                       keep_largest=None, smooth_iterations=None, decimate_cell=None):
+                       keep_largest=None, smooth_iterations=None, decimate_cell=None, project_iterations=None):
     """run.py's reconstruction stage without the reference tree: Zero123-style folder (dataset.SceneFolder) -> coloured mesh (binary PLY in
     the original frame), optionally the val image of the target view.  ``output_format`` ".obj" / ".glb" (run.py --output_format) also writes
     ``mesh<ext>`` next to ``out_ply`` in the asset frame, from the same device buffers.  ``min_component_faces`` / ``keep_largest``: the component filter of
     _mesh_fields (None: the config default); ``smooth_iterations``: its smoothing (None: the config default, 0 = off); ``decimate_cell``: its decimation
-    (None: the config default, 0 = off).  Returns dict(vertices, triangles, kept_voxels, ply, components, components_kept, smooth_iterations, decimate_cell,
-    decimate[, asset][, color, depth]); the two component counts are None when the filter is off, ``decimate`` (the counts of ops.mesh_decimate) when
-    decimation is."""
+    (None: the config default, 0 = off); ``project_iterations``: its projection onto the zero set (None: the config default, 0 = off).  Returns
+    dict(vertices, triangles, kept_voxels, ply, components, components_kept, smooth_iterations, decimate_cell, decimate, project_iterations, project[, asset]
+    [, color, depth]); the two component counts are None when the filter is off, ``decimate`` (the counts of ops.mesh_decimate) when decimation is, and
+    ``project`` (the info of ops.mesh_project) when projection is."""
     import os
     from . import dataset, mesh_io
     if output_format not in (None, ".ply", ".obj", ".glb"):
@@ -289,12 +303,14 @@ def reconstruct_folder(root_dir, name, wt, out_ply, D=96, resolution=256, render
     cc = {}
     smooth = config.mesh_smooth_iterations(smooth_iterations)
     cell = config.mesh_decimate_cell(decimate_cell)
+    project = config.mesh_project_iterations(project_iterations)
     _, verts_idx, tris, rgb, _, _ = _mesh_fields(wt, vol, proj, cam_pos, resolution, min_component_faces, keep_largest, info=cc, smooth_iterations=smooth,
-                                                 decimate_cell=cell)
+                                                 decimate_cell=cell, project_iterations=project)
     rgb = rgb if verts_idx.shape[0] else None
     nv, nt = mesh_io.export_mesh(out_ply, verts_idx, tris, resolution, scale_mat=s["scale_mat"], trans_mat=s["trans_mat"], vertex_colors=rgb)
     out = {"vertices": nv, "triangles": nt, "kept_voxels": int(vol["n_voxels"]), "ply": str(out_ply), "components": cc["components"],
-           "components_kept": cc["components_kept"], "smooth_iterations": smooth, "decimate_cell": cell, "decimate": cc["decimate"]}
+           "components_kept": cc["components_kept"], "smooth_iterations": smooth, "decimate_cell": cell, "decimate": cc["decimate"],
+           "project_iterations": project, "project": cc["project"]}
     if output_format in (".obj", ".glb"):
         out["asset"] = os.path.join(os.path.dirname(str(out_ply)), "mesh" + output_format)
         mesh_io.export_asset(out["asset"], verts_idx, tris, resolution, scale_mat=s["scale_mat"], trans_mat=s["trans_mat"], vertex_colors=rgb)

@@ -512,6 +512,12 @@ class SparseNeuSRenderer(nn.Module):
         # the unchanged runner then colours and writes the decimated mesh
         if config.MESH_DECIMATE_CELL:
             v, t, _, _ = ops.mesh_decimate(v, t, config.MESH_DECIMATE_CELL)
+        # O2345_MESH_PROJECT_ITERATIONS (off by default: nothing is launched): Newton projection of the index coordinates onto sdf = -threshold (u = -sdf)
+        # inside the call's own bounds, on the device; the unchanged runner then colours the projected vertices.  Not with an occupancy mask: the
+        # vertices on the mask's walls (u = -100 next to the surface) are not on the level set, and projecting would pull them off the wall
+        if config.MESH_PROJECT_ITERATIONS and occupancy_mask is None:
+            v, _ = ops.mesh_project(self.sdf_network.sdf_layer.blob(), channel_last(kwargs["conditional_volume"]), v, int(resolution),
+                                    config.MESH_PROJECT_ITERATIONS, level=-float(threshold), bound_min=bound_min, bound_max=bound_max)
         # O2345_MESH_SMOOTH_ITERATIONS (off by default: nothing is launched): Taubin smoothing of the index coordinates on the device; the unchanged runner
         # colours whatever vertices it is handed, so here the colours are taken at the SMOOTHED positions (pipeline._mesh_fields colours first)
         if config.MESH_SMOOTH_ITERATIONS:

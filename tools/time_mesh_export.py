@@ -14,6 +14,10 @@ fed the same arrays.  Two meshes: BASELINE config 2 (8 views, 128^3 volume, 256^
              (mesh_io.decimate_mesh, host clock, one call), the op alone (HIP events around the two-call protocol, which synchronises once in the
              middle), the gradient + colour time on the decimated vertices next to grad_color_all, and whole-export variants inside the same
              alternating loop as the others
+  project    Newton projection onto the SDF's zero set (csrc/mesh_project.hip), 4 iterations, on the config's mesh and on its cell-2 decimation (move
+             limit 2): the op alone (HIP events around the queued rounds, the small D2H copy of the counters and its synchronisation), the active
+             vertices per round, max |sdf| before -> after, and whole-export variants with and without it, with and without decimation, inside the
+             same alternating loop as the others
 Medians over --reps calls after --warmup calls; the ratio against the PLY of the SAME run is what to read.  Prints one JSON line.
 
     python tools/time_mesh_export.py [--reps 9] [--warmup 3] [--skip-512]
@@ -166,6 +170,12 @@ def one_mesh(dev, wt, tmp, D, R, ray_scale, a, numpy_writer):
                                       "grad_color_all": med_events(lambda: grad_color(verts_idx), a.reps, a.warmup),
                                       "grad_color_decimated": med_events(lambda: grad_color(d_verts), a.reps, a.warmup)},
                            host_twin_ms_once=(t1 - t0) * 1e3)
+    # projection onto the zero set, 4 rounds: the op alone on the marching-cubes vertices and on the decimated ones
+    PIT = 4
+    proj_op = lambda v, mm: ops.mesh_project(wt.sdf_blob, vol["vol_cl"], v, R, PIT, max_move=mm, precision=wt.sdf_precision)
+    res["project"] = {"iterations": PIT}
+    for key, v, mm in (("all", verts_idx, 1.0), ("decimated", d_verts, max(1.0, CELL))):
+        res["project"][key] = dict(proj_op(v, mm)[1], vertices=int(v.shape[0]), max_move=mm, mesh_project_ms=med_events(lambda: proj_op(v, mm), a.reps, a.warmup))
     A = (wt, vol, inp["proj"], inp["cam_pos"], R)
     whole = {
         "ply": lambda: pipeline.export_mesh_ply(P(".ply"), *A),
@@ -180,6 +190,10 @@ def one_mesh(dev, wt, tmp, D, R, ray_scale, a, numpy_writer):
         "ply_decimate2": lambda: pipeline.export_mesh_ply(P("_d.ply"), *A, decimate_cell=CELL),
         "glb_decimate2": lambda: pipeline.export_mesh_asset(P("_d.glb"), *A, decimate_cell=CELL),
         "obj_decimate2": lambda: pipeline.export_mesh_asset(P("_d.obj"), *A, decimate_cell=CELL),
+        "ply_project4": lambda: pipeline.export_mesh_ply(P("_p.ply"), *A, project_iterations=PIT),
+        "glb_project4": lambda: pipeline.export_mesh_asset(P("_p.glb"), *A, project_iterations=PIT),
+        "ply_decimate2_project4": lambda: pipeline.export_mesh_ply(P("_dp.ply"), *A, decimate_cell=CELL, project_iterations=PIT),
+        "glb_decimate2_project4": lambda: pipeline.export_mesh_asset(P("_dp.glb"), *A, decimate_cell=CELL, project_iterations=PIT),
     }
     # alternated like the stage variants; the spread (min .. max) of each is what a difference between two of them has to exceed
     for fn in whole.values():
