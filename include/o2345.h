@@ -485,8 +485,47 @@ int o2345_obj_text(const float* positions, const uint8_t* rgba, const float* nor
  * layouts above, text host uint8 [obj_text_bytes].  Plain host code (up to four threads), no device work, no stream. */
 int o2345_obj_text_host(const float* positions, const uint8_t* rgba, const float* normals, long long n, const uint32_t* indices, long long m, int K,
                         uint8_t* text);
+/* ---- texture atlas of the exported mesh (additive since 2.1; none in the reference: its assets carry vertex colours only, trainer_generic.py:1377-1382,
+ * utils/utils.py:31-47) ------------------------------------------------------------------------------------------------------------------------------
+ * Layout for nt >= 1 triangles and texel = c in [4, 64], the edge of a cell in texels: triangles 2k and 2k + 1, in face order, share square cell k;
+ * cells = ceil(nt / 2), G = ceil(sqrt(cells)); cell k sits at column k mod G, row k div G; the image is W = G c wide, H = ceil(cells / G) c high, row 0
+ * on top.  Refused: W or H over 16384, cells c^2 >= 2^31.  Local texel (i, j) of a cell has its centre at (i + 0.5, j + 0.5).  Triangle A = 2k has its
+ * corners at local uv (0.5, 0.5), (c - 1.5, 0.5), (0.5, c - 1.5) and owns the texels with i + j <= c - 1; triangle B = min(2k + 1, nt - 1) has them at
+ * (c - 0.5, c - 0.5), (2.5, c - 0.5), (c - 0.5, 2.5) and owns those with i + j >= c (for an odd nt the B half of the last cell repeats the last
+ * triangle).  A bilinear fetch (texel centres at + 0.5, clamp to edge, no mipmaps) anywhere in a triangle reads only texels that triangle owns.
+ * mesh_texture_texels (HOST function): cells c^2, the length of the texel lists, and W, H through the two host pointers (either may be NULL); 0 for a
+ * refused layout.
+ * mesh_texture_points: the surface point of every texel of every used cell, cell-major (entry k c^2 + j c + i).  Barycentric weights of the centre with
+ * respect to the owner's uv corners -- A: w1 = i / (c - 2), w2 = j / (c - 2); B: w1 = (c - 1 - i) / (c - 3), w2 = (c - 1 - j) / (c - 3); w0 = (1 - w1)
+ * - w2; never clamped: gutter texels extrapolate -- then p = (w0 P0 + w1 P1) + w2 P2 on the index-space corners, each coordinate clamped to [0, R - 1],
+ * and the world point float32(p / (R - 1) * ext + bmin) as o2345_mesh_project defines it; fp64, one operation at a time, in the order written: equal to
+ * mesh_io.texture_points to the last bit.  verts device fp64 [nv,3], tris device int32 / int64 [nt,3] (index_bytes 4 / 8), both only read; 1 <= nv <
+ * 2^30; bound_min / bound_max HOST float32 [3], bound_max > bound_min.  Outputs, device: points_idx fp64 [texels,3], points_world float32 [texels,3],
+ * stats (16 bytes, 8-byte aligned) = uint64 [2]: triangles with a non-finite corner coordinate, triangles with an index outside [0, nv).  Such an index is
+ * read as vertex 0, never dereferenced; a non-zero counter means bad input and the caller raises.  No host synchronisation.
+ * mesh_texture_pack: rgb device fp32 [texels,3] in the order above -> image device uint8 [H,W,4], 4-byte aligned, raster order: the truncating
+ * quantisation of the vertex colours, alpha 255; texels of unused cells are 0, 0, 0, 0.
+ * mesh_texture_corners: the unwelded vertices.  Triangle t = (a, b, c) gives vertices 3t, 3t + 1, 3t + 2 = c, b, a (the asset frame's reversed winding):
+ * positions float32 [3 nt,3] = that vertex's position of o2345_mesh_asset_vertices, bit for bit; uv float32 [3 nt,2] = ((cell_x c + u_local) / W,
+ * (cell_y c + v_local) / H), fp64 rounded once; normals float32 [3 nt,3] (written iff grad, device fp32 [nv,3]) = that vertex's normal of
+ * o2345_mesh_asset_vertices; indices uint32 [3 nt] = 0, 1, 2, ...; bounds float32 [6] and workspace (o2345_mesh_bounds_workspace_bytes(3 nt) bytes) as
+ * for o2345_mesh_asset_vertices.  Bounds and matrices as for o2345_mesh_pack_vertices. */
+size_t o2345_mesh_texture_texels(long long nt, int texel, int* width_host, int* height_host);
+int o2345_mesh_texture_points(const double* verts, long long nv, const void* tris, int index_bytes, long long nt, int texel, int grid_R,
+                              const float* bound_min, const float* bound_max, double* points_idx, float* points_world, void* stats, void* stream);
+int o2345_mesh_texture_pack(const float* rgb, long long nt, int texel, uint8_t* image, void* stream);
+int o2345_mesh_texture_corners(const double* verts, long long nv, const void* tris, int index_bytes, long long nt, int texel, int grid_R,
+                               const float* bound_min, const float* bound_max, const float* scale_mat, const float* trans_mat, const float* grad,
+                               float* positions, float* uv, float* normals, uint32_t* indices, float* bounds, void* workspace, size_t workspace_bytes,
+                               void* stream);
+/* The records of the textured OBJ (none in the reference), for n = 3 nt unwelded vertices as written by mesh_texture_corners: n "v" records without
+ * colours, n "vt" + 2 x " %10.8f" records (u, then float32(1 - v): OBJ's origin is bottom-left), n "vn" records when normals are given, n / 3 records
+ * "f a/a b/b c/c" (with normals "a/a/a") over the corners 1 .. n in order, each token right-aligned in 2 d + 1 (3 d + 2) bytes, d = decimal digits of n.
+ * Fields and K as for o2345_obj_text.  obj_texture_text_bytes: the byte count (HOST function; 0 for K outside 1 .. 9 or n not a multiple of 3). */
+size_t o2345_obj_texture_text_bytes(long long n, int K, int normals);
+int o2345_obj_texture_text(const float* positions, const float* uv, const float* normals, long long n, int K, uint8_t* text, void* stream);
 /* Load every code object of the library on the current device now (the HIP runtime loads a translation unit's kernels at its first launch: 5 - 60 ms
- * each for the 17 units of this library, which otherwise land inside the first calls of a fresh process).  Launches nothing that touches user memory. */
+ * each for the units of this library, which otherwise land inside the first calls of a fresh process).  Launches nothing that touches user memory. */
 int o2345_preload(void);
 
 #ifdef __cplusplus

@@ -212,3 +212,43 @@ def mesh_project_max_move(x=None, decimate_cell=None):
     if MESH_PROJECT_MAX_MOVE is not None:
         return MESH_PROJECT_MAX_MOVE
     return max(1.0, mesh_decimate_cell(decimate_cell))
+
+
+# ---- texture atlas (csrc/mesh_texture.hip; mesh_io.texture_points / pack_texture / texture_corners are the host twins) -------------------------------------
+# O2345_MESH_TEXTURE_TEXEL=c bakes a texture atlas for the exported .glb / .obj asset on the device: every pair of triangles gets a square cell of c x c
+# texels (an integer in [4, 64]), the colour network is evaluated at every texel's surface point, and the asset carries texture coordinates and a PNG
+# instead of vertex colours ("" or "0" = off, the default: nothing is launched and every file keeps its bytes).  O2345_MESH_TEXTURE_PNG_LEVEL (1) is the
+# zlib level of that PNG, 0 .. 9, 0 = stored: compression is host time and dominates the textured export.
+def _texture_texel(name, n):
+    if not (n == 0 or 4 <= n <= 64):
+        raise ValueError(f"{name} must be 0 (off) or an integer in [4, 64], got {n!r}")
+    return n
+
+
+def _png_level(name, n):
+    if n > 9:
+        raise ValueError(f"{name} must be an integer in [0, 9], got {n!r}")
+    return n
+
+
+MESH_TEXTURE_TEXEL = _texture_texel("O2345_MESH_TEXTURE_TEXEL", _non_negative_int("O2345_MESH_TEXTURE_TEXEL", os.environ.get("O2345_MESH_TEXTURE_TEXEL", "")))
+_lvl = os.environ.get("O2345_MESH_TEXTURE_PNG_LEVEL", "")
+MESH_TEXTURE_PNG_LEVEL = 1 if _lvl.strip() == "" else _png_level("O2345_MESH_TEXTURE_PNG_LEVEL", _non_negative_int("O2345_MESH_TEXTURE_PNG_LEVEL", _lvl))
+del _lvl
+
+
+def mesh_texture_texel(n=None):
+    """None -> the configured default; anything else must be 0 (off, whatever the default) or an integer in [4, 64]."""
+    if n is None:
+        return MESH_TEXTURE_TEXEL
+    if isinstance(n, bool) or int(n) != n or n < 0:
+        raise ValueError(f"texture_texel must be 0 (off) or an integer in [4, 64], got {n!r}")
+    return _texture_texel("texture_texel", int(n))
+
+
+def mesh_texture_png_level(n=None):
+    if n is None:
+        return MESH_TEXTURE_PNG_LEVEL
+    if isinstance(n, bool) or int(n) != n or n < 0:
+        raise ValueError(f"png_level must be an integer in [0, 9], got {n!r}")
+    return _png_level("png_level", int(n))

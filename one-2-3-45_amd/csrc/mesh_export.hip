@@ -14,30 +14,6 @@
 
 namespace o2345 {
 
-// min / max of six per-thread values over a 256-thread block -> red[0..5] valid in threads 0..5 after the call (lds: 4 x 6 floats)
-__device__ __forceinline__ void block_minmax(float mn[3], float mx[3], float* lds, float out[6]) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-#pragma unroll
-        for (int d = 0; d < 3; ++d) {
-            mn[d] = fminf(mn[d], __shfl_xor(mn[d], off));
-            mx[d] = fmaxf(mx[d], __shfl_xor(mx[d], off));
-        }
-    }
-    const int w = threadIdx.x >> 6;
-    if (lane_id() == 0) {
-#pragma unroll
-        for (int d = 0; d < 3; ++d) { lds[w * 6 + d] = mn[d]; lds[w * 6 + 3 + d] = mx[d]; }
-    }
-    __syncthreads();
-    if (threadIdx.x < 6) {
-        const int k = threadIdx.x;
-        float r = lds[k];
-        for (int i = 1; i < 4; ++i) r = k < 3 ? fminf(r, lds[i * 6 + k]) : fmaxf(r, lds[i * 6 + k]);
-        out[k] = r;
-    }
-}
-
 // One vertex per thread: position (swapped), rgba, unit normal (swapped); per-block min / max of the float32 positions -> partials[block][6]
 __global__ __launch_bounds__(256) void k_asset_vertices(const double* __restrict__ vidx, long long n, MeshXform x, const float* __restrict__ rgb,
                                                         const float* __restrict__ grad, float* __restrict__ pos, uint8_t* __restrict__ rgba,
@@ -56,24 +32,9 @@ __global__ __launch_bounds__(256) void k_asset_vertices(const double* __restrict
             *reinterpret_cast<uchar4*>(rgba + 4 * i) = c;
         }
         if (grad) {
-            // normalize(g) -> 3x3 of trans_mat -> renormalise, in fp64; scale_mat is a positive uniform scale and leaves a direction alone
-            double g[3] = {(double)grad[3 * i], (double)grad[3 * i + 1], (double)grad[3 * i + 2]};
-            double l = sqrt(g[0] * g[0] + g[1] * g[1] + g[2] * g[2]);
-            bool ok = l > 0.0 && l < (double)INFINITY;
-            if (ok) {
-                g[0] /= l; g[1] /= l; g[2] /= l;
-                if (x.has_trans) {
-                    double w[3];
-#pragma unroll
-                    for (int r = 0; r < 3; ++r) w[r] = (x.T[4 * r] * g[0] + x.T[4 * r + 1] * g[1]) + x.T[4 * r + 2] * g[2];
-                    l = sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]);
-                    ok = l > 0.0 && l < (double)INFINITY;
-                    g[0] = w[0] / l; g[1] = w[1] / l; g[2] = w[2] / l;
-                }
-            }
-            nrm[3 * i] = ok ? (float)g[0] : 0.f;
-            nrm[3 * i + 1] = ok ? (float)g[2] : 1.f;
-            nrm[3 * i + 2] = ok ? (float)g[1] : 0.f;
+            float nn[3];
+            mesh_normal_f32(grad, i, x, nn);                 // mesh_math.h: shared with the textured corners (mesh_texture.hip)
+            nrm[3 * i] = nn[0]; nrm[3 * i + 1] = nn[1]; nrm[3 * i + 2] = nn[2];
         }
     }
     float out[6];
@@ -106,14 +67,15 @@ __global__ __launch_bounds__(256) void k_asset_indices(const IDX* __restrict__ t
 
 // 256 records of one kind per block.  Each thread formats its record into LDS at the byte phase the block's output has in global memory
 // (so a 16-byte piece of LDS is a 16-byte aligned piece of the file), then the block copies head bytes / uint4 body / tail bytes.
-constexpr int OBJ_KIND_V = 0, OBJ_KIND_VN = 1, OBJ_KIND_F = 2, OBJ_TABLE_BYTES = 256 * 11;
+// Kinds VT ("vt u v" of the textured file) and FT (its "f a/a b/b c/c" over unwelded corners, which needs no index buffer) came with mesh_texture.hip.
+constexpr int OBJ_KIND_V = 0, OBJ_KIND_VN = 1, OBJ_KIND_F = 2, OBJ_KIND_VT = 3, OBJ_KIND_FT = 4, OBJ_TABLE_BYTES = 256 * 11;
 __global__ __launch_bounds__(256) void k_obj_records(int kind, ObjLayout L, const float* __restrict__ pos, const uint8_t* __restrict__ rgba,
-                                                     const float* __restrict__ nrm, const uint32_t* __restrict__ idx,
+                                                     const float* __restrict__ nrm, const uint32_t* __restrict__ idx, const float* __restrict__ uv,
                                                      const uint8_t* __restrict__ table, long long count, uint8_t* __restrict__ out) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];         // colour table (2,816 = 176 x 16 bytes) | 16 + 256 * len: all LDS is dynamic,
     uint8_t* tab = lds;                                                   // so the staging area starts 16-byte aligned
     uint8_t* stage = lds + OBJ_TABLE_BYTES;
-    const int len = kind == OBJ_KIND_V ? L.v_len : kind == OBJ_KIND_VN ? L.vn_len : L.f_len;
+    const int len = kind == OBJ_KIND_V ? L.v_len : kind == OBJ_KIND_VN ? L.vn_len : kind == OBJ_KIND_F ? L.f_len : kind == OBJ_KIND_VT ? L.vt_len : L.ft_len;
     const long long r0 = (long long)blockIdx.x * 256;
     const int nrec = (int)(count - r0 < 256 ? count - r0 : 256);
     uint8_t* g = out + r0 * len;
@@ -134,9 +96,14 @@ __global__ __launch_bounds__(256) void k_obj_records(int kind, ObjLayout L, cons
         } else if (kind == OBJ_KIND_VN) {
             const float p[3] = {nrm[3 * i], nrm[3 * i + 1], nrm[3 * i + 2]};
             obj_normal_record(dst, p);
-        } else {
+        } else if (kind == OBJ_KIND_F) {
             const uint32_t t[3] = {idx[3 * i], idx[3 * i + 1], idx[3 * i + 2]};
             obj_face_record(dst, L, t);
+        } else if (kind == OBJ_KIND_VT) {
+            const float t[2] = {uv[2 * i], uv[2 * i + 1]};
+            obj_texcoord_record(dst, t);
+        } else {
+            obj_corner_face_record(dst, L, (unsigned)i);
         }
     }
     __syncthreads();
@@ -151,6 +118,10 @@ __global__ __launch_bounds__(256) void k_obj_records(int kind, ObjLayout L, cons
     for (int v = tid; v < nvec; v += 256) gv[v] = sv[v];
     const int t0 = head + (nvec << 4);
     if (tid < tail) g[t0 + tid] = stage[phase + t0 + tid];
+}
+
+void mesh_bounds_finish(const float* partials, long long nblocks, float* bounds, hipStream_t stream) {
+    hipLaunchKernelGGL(k_asset_bounds_finish, dim3(1), dim3(256), 0, stream, partials, nblocks, bounds);
 }
 
 static void obj_colour_table(uint8_t* table /*[256 * 11]*/) {
@@ -179,7 +150,7 @@ int o2345_mesh_asset_vertices(const double* verts_idx, long long n, int grid_R, 
     const MeshXform x = mesh_xform(grid_R, bound_min, bound_max, scale_mat, trans_mat);
     const unsigned nb = cdiv(n, 256);
     hipLaunchKernelGGL(k_asset_vertices, dim3(nb), dim3(256), 0, (hipStream_t)stream, verts_idx, n, x, rgb, grad, positions, rgba, normals, (float*)workspace);
-    hipLaunchKernelGGL(k_asset_bounds_finish, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float*)workspace, (long long)nb, bounds);
+    mesh_bounds_finish((const float*)workspace, (long long)nb, bounds, (hipStream_t)stream);
     return check_launch("mesh_asset_vertices");
 }
 
@@ -208,13 +179,37 @@ int o2345_obj_text(const float* positions, const uint8_t* rgba, const float* nor
     uint8_t* o = text;
     auto launch = [&](int kind, long long count, int len) {
         if (count > 0) hipLaunchKernelGGL(k_obj_records, dim3(cdiv(count, 256)), dim3(256), (size_t)(OBJ_TABLE_BYTES + 16 + 256 * len), (hipStream_t)stream, kind, L, positions, rgba, normals, indices,
-                                          color_table, count, o);
+                                          (const float*)nullptr, color_table, count, o);
         o += count * len;
     };
     launch(OBJ_KIND_V, n, L.v_len);
     if (normals) launch(OBJ_KIND_VN, n, L.vn_len);
     launch(OBJ_KIND_F, m, L.f_len);
     return check_launch("obj_text");
+}
+
+size_t o2345_obj_texture_text_bytes(long long n, int K, int normals) {
+    if (n < 0 || n % 3 || K < 1 || K > 9) return 0;
+    const ObjLayout L = obj_layout(n, K, 0, normals);
+    return (size_t)n * L.v_len + (size_t)n * L.vt_len + (normals ? (size_t)n * L.vn_len : 0) + (size_t)(n / 3) * L.ft_len;
+}
+
+int o2345_obj_texture_text(const float* positions, const float* uv, const float* normals, long long n, int K, uint8_t* text, void* stream) {
+    O2345_REQUIRE(K >= 1 && K <= 9, "obj_texture_text: K = %d integer digits (1 .. 9)", K);
+    O2345_REQUIRE(n >= 0 && n % 3 == 0 && n < 4294967295ll, "obj_texture_text: bad size (n = 3 x triangles, below 2^32)");
+    O2345_REQUIRE(n == 0 || (positions && uv && text), "obj_texture_text: null pointer");
+    const ObjLayout L = obj_layout(n, K, 0, normals != nullptr);
+    uint8_t* o = text;
+    auto launch = [&](int kind, long long count, int len) {
+        if (count > 0) hipLaunchKernelGGL(k_obj_records, dim3(cdiv(count, 256)), dim3(256), (size_t)(OBJ_TABLE_BYTES + 16 + 256 * len), (hipStream_t)stream, kind, L, positions,
+                                          (const uint8_t*)nullptr, normals, (const uint32_t*)nullptr, uv, (const uint8_t*)nullptr, count, o);
+        o += count * len;
+    };
+    launch(OBJ_KIND_V, n, L.v_len);
+    launch(OBJ_KIND_VT, n, L.vt_len);
+    if (normals) launch(OBJ_KIND_VN, n, L.vn_len);
+    launch(OBJ_KIND_FT, n / 3, L.ft_len);
+    return check_launch("obj_texture_text");
 }
 
 int o2345_obj_text_host(const float* positions, const uint8_t* rgba, const float* normals, long long n, const uint32_t* indices, long long m, int K,

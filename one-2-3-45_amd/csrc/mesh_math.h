@@ -45,8 +45,57 @@ O2345_HD void mesh_vertex_f32(const double* __restrict__ vidx, long long i, cons
     f[0] = (float)v[0]; f[1] = (float)v[1]; f[2] = (float)v[2];
 }
 
+// SDF gradient of vertex i -> unit normal of the asset frame: normalize(g) -> 3x3 of trans_mat -> renormalise, in fp64, y and z exchanged; scale_mat is
+// a positive uniform scale and leaves a direction alone.  (0, 1, 0) for a zero or non-finite gradient.
+O2345_HD void mesh_normal_f32(const float* __restrict__ grad, long long i, const MeshXform& x, float n[3]) {
+    double g[3] = {(double)grad[3 * i], (double)grad[3 * i + 1], (double)grad[3 * i + 2]};
+    double l = sqrt(g[0] * g[0] + g[1] * g[1] + g[2] * g[2]);
+    bool ok = l > 0.0 && l < (double)INFINITY;
+    if (ok) {
+        g[0] /= l; g[1] /= l; g[2] /= l;
+        if (x.has_trans) {
+            double w[3];
+#pragma unroll
+            for (int r = 0; r < 3; ++r) w[r] = (x.T[4 * r] * g[0] + x.T[4 * r + 1] * g[1]) + x.T[4 * r + 2] * g[2];
+            l = sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]);
+            ok = l > 0.0 && l < (double)INFINITY;
+            g[0] = w[0] / l; g[1] = w[1] / l; g[2] = w[2] / l;
+        }
+    }
+    n[0] = ok ? (float)g[0] : 0.f;
+    n[1] = ok ? (float)g[2] : 1.f;
+    n[2] = ok ? (float)g[1] : 0.f;
+}
+
 // np.array(color * 255, dtype=uint8) (trainer_generic.py:1377): truncation
 O2345_HD uint8_t mesh_colour_u8(float c) { return (uint8_t)(int)(c * 255.f); }
+
+// ---- per-axis bounds of float32 positions: stage one per block (block_minmax -> partials[block][6]), stage two in mesh_export.hip -----------------
+// min / max of six per-thread values over a 256-thread block -> out[0..5] valid in threads 0..5 after the call (lds: 4 x 6 floats)
+__device__ __forceinline__ void block_minmax(float mn[3], float mx[3], float* lds, float out[6]) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+#pragma unroll
+        for (int d = 0; d < 3; ++d) {
+            mn[d] = fminf(mn[d], __shfl_xor(mn[d], off));
+            mx[d] = fmaxf(mx[d], __shfl_xor(mx[d], off));
+        }
+    }
+    const int w = threadIdx.x >> 6;
+    if (lane_id() == 0) {
+#pragma unroll
+        for (int d = 0; d < 3; ++d) { lds[w * 6 + d] = mn[d]; lds[w * 6 + 3 + d] = mx[d]; }
+    }
+    __syncthreads();
+    if (threadIdx.x < 6) {
+        const int k = threadIdx.x;
+        float r = lds[k];
+        for (int i = 1; i < 4; ++i) r = k < 3 ? fminf(r, lds[i * 6 + k]) : fmaxf(r, lds[i * 6 + k]);
+        out[k] = r;
+    }
+}
+// stage two (mesh_export.hip): ONE block folds nblocks x 6 partials -> bounds[0..2] = min, bounds[3..5] = max, queued on `stream`
+void mesh_bounds_finish(const float* partials, long long nblocks, float* bounds, hipStream_t stream);
 
 // ---- OBJ text fields ------------------------------------------------------------------------------------------------------------------------
 // Every field is written right to left into exactly `width` bytes, whatever the value: a value that needs more room than the host planned for
@@ -85,6 +134,7 @@ struct ObjLayout {
     int dn;            // decimal digits of the vertex count
     int colours, normals;
     int v_len, vn_len, f_len;
+    int vt_len, ft_len;    // the textured file's "vt" record and its "f a/a b/b c/c" record over unwelded corners
 };
 
 O2345_HD int obj_digits(unsigned long long v) { int d = 1; while (v >= 10ull) { v /= 10ull; ++d; } return d; }
@@ -95,6 +145,8 @@ O2345_HD ObjLayout obj_layout(long long n, int K, int colours, int normals) {
     L.v_len = 1 + 3 * (K + 11) + (colours ? 33 : 0) + 1;
     L.vn_len = 2 + 3 * 12 + 1;
     L.f_len = 1 + 3 * (1 + (normals ? 2 * L.dn + 2 : L.dn)) + 1;
+    L.vt_len = 2 + 2 * 11 + 1;
+    L.ft_len = 1 + 3 * (1 + (normals ? 3 * L.dn + 2 : 2 * L.dn + 1)) + 1;
     return L;
 }
 
@@ -132,6 +184,31 @@ O2345_HD void obj_face_record(uint8_t* dst, const ObjLayout& L, const uint32_t* 
         int p = obj_uint(o, w - 1, a);
         if (L.normals) {
             if (p >= 0) o[p--] = '/';
+            if (p >= 0) o[p--] = '/';
+            p = obj_uint(o, p, a);
+        }
+        while (p >= 0) o[p--] = ' ';
+    }
+    dst[1 + 3 * w] = '\n';
+}
+
+// "vt" + 2 x " %10.8f" + "\n": u, then float32(1 - v) -- the image's row 0 is its top, OBJ's v = 0 its bottom
+O2345_HD void obj_texcoord_record(uint8_t* dst, const float* uv) {
+    dst[0] = 'v'; dst[1] = 't';
+    obj_fixed8(dst + 2, 11, uv[0]);
+    obj_fixed8(dst + 13, 11, (float)(1.0 - (double)uv[1]));
+    dst[24] = '\n';
+}
+
+// "f" + 3 x " a/a" (or " a/a/a" with normals) over the unwelded corners 3t + 1 .. 3t + 3 of triangle t, each token right-aligned in 2 dn + 1 (3 dn + 2) bytes
+O2345_HD void obj_corner_face_record(uint8_t* dst, const ObjLayout& L, unsigned t) {
+    dst[0] = 'f';
+    const int w = 1 + (L.normals ? 3 * L.dn + 2 : 2 * L.dn + 1);
+    for (int d = 0; d < 3; ++d) {
+        uint8_t* o = dst + 1 + d * w;
+        const unsigned a = 3u * t + (unsigned)d + 1u;
+        int p = obj_uint(o, w - 1, a);
+        for (int k = L.normals ? 2 : 1; k > 0; --k) {
             if (p >= 0) o[p--] = '/';
             p = obj_uint(o, p, a);
         }

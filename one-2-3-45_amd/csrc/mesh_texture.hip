@@ -1,0 +1,232 @@
+// Texture atlas of the exported mesh on the device: the surface point of every texel (k_tex_points), the image from the texel colours (k_tex_pack) and
+// the unwelded, uv-carrying vertices (k_tex_corners).  The colours in between come from the library's own network kernels over the point list.  Equal to
+// the host twins (mesh_io.texture_points / pack_texture / texture_corners) to the last bit: everything here is fp64, one operation at a time, in a
+// defined order, or integer.
+//
+// Layout (c = texel, the edge of a cell in texels, 4 .. 64; nt triangles)
+//   cells      triangles 2k and 2k + 1, in face order, share square cell k; cells = ceil(nt / 2), G = ceil(sqrt(cells)); cell k sits at column k mod G,
+//              row k div G; the image is W = G c wide and H = ceil(cells / G) c high.  W, H <= 16384 and cells c^2 < 2^31.
+//   in a cell  local texel (i, j) has its centre at (i + 0.5, j + 0.5).  Triangle A = 2k has its corners at local uv (0.5, 0.5), (c - 1.5, 0.5),
+//              (0.5, c - 1.5) and owns the texels with i + j <= c - 1; triangle B = min(2k + 1, nt - 1) has them at (c - 0.5, c - 0.5), (2.5, c - 0.5),
+//              (c - 0.5, 2.5) and owns those with i + j >= c.  For an odd nt the B half of the last cell repeats the last triangle.
+//   why        a bilinear fetch (texel centres at + 0.5, clamp to edge, no mipmaps) anywhere in a triangle, edges and corners included, reads only texels
+//              its triangle owns: for A the centre-relative coordinates x, y >= 0 have x + y <= c - 2, so ceil(x) + ceil(y) <= c - 1 wherever the weight
+//              is not zero; for B x, y <= c - 1 and x + y >= c + 1, so floor(x) + floor(y) >= c.  Nothing bleeds, no dilation pass is needed.
+//   texel      barycentric weights of the centre with respect to the owner's uv corners -- A: w1 = i / (c - 2), w2 = j / (c - 2); B: w1 = (c - 1 - i) /
+//              (c - 3), w2 = (c - 1 - j) / (c - 3); w0 = (1 - w1) - w2 -- NOT clamped: gutter texels extrapolate, which makes the bilinear fetch of a
+//              function linear over the triangle's plane exact.  p = (w0 P0 + w1 P1) + w2 P2 on the index-space vertices, each coordinate clamped to
+//              [0, R - 1]; world point float32(p / (R - 1) * ext + bmin), bmin / bmax the float32 bounds widened, ext = bmax - bmin: mesh_project's.
+//   order      texel points and colours are cell-major: entry k c^2 + j c + i.  Exactly cells c^2 entries, no compaction.
+//   corners    triangle t = (a, b, c) gives unwelded vertices 3t, 3t + 1, 3t + 2 = c, b, a (the asset frame's reversed winding); uv = ((cell_x c + u_local)
+//              / W, (cell_y c + v_local) / H) in fp64, rounded once; position and normal are the welded export's for that vertex (mesh_math.h).
+// Bad input never faults: a triangle index outside [0, nv) is read as vertex 0, and it and a non-finite coordinate are counted once per triangle in two
+// integer counters that the caller raises on.  No other atomics.  Nothing here synchronises with the host.
+#include "common.h"
+#include "mesh_math.h"
+#include <float.h>
+
+namespace o2345 {
+
+struct TexLayout {
+    int c, G, W, H;
+    long long cells, texels;
+};
+
+// host: the layout, or false for what the definition refuses
+static bool tex_layout(long long nt, int c, TexLayout& L) {
+    if (nt < 1 || nt >= (1ll << 40) || c < 4 || c > 64) return false;
+    const long long cells = (nt + 1) / 2;
+    long long g = (long long)sqrt((double)cells);
+    while (g * g < cells) ++g;
+    while (g > 1 && (g - 1) * (g - 1) >= cells) --g;
+    const long long rows = (cells + g - 1) / g;
+    if (g * c > 16384 || rows * c > 16384 || cells * c * c >= (1ll << 31)) return false;
+    L.c = c; L.G = (int)g; L.W = (int)(g * c); L.H = (int)(rows * c); L.cells = cells; L.texels = cells * c * c;
+    return true;
+}
+
+struct TexFrame {
+    double rm1;                                       // R - 1
+    double bmin[3], bext[3];
+};
+
+// the device block of k_tex_points; its layout is part of the C ABI (include/o2345.h)
+struct TexStats {
+    unsigned long long n_nonfinite, n_bad;
+};
+
+// thread per texel of a used cell, cell-major
+template <typename IDX>
+__global__ __launch_bounds__(256) void k_tex_points(const double* __restrict__ verts, long long nv, const IDX* __restrict__ tris, long long nt, int c,
+                                                    long long texels, TexFrame f, double* __restrict__ pidx, float* __restrict__ pworld,
+                                                    TexStats* __restrict__ st) {
+    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+    bool bad = false, nonfinite = false;
+    if (e < texels) {
+        const int cc = c * c;
+        const long long k = e / cc;
+        const int r = (int)(e - k * cc), j = r / c, i = r - j * c;
+        const bool isB = i + j >= c;
+        const bool hasB = 2 * k + 1 < nt;
+        const long long t = isB && hasB ? 2 * k + 1 : 2 * k;
+        const bool counts = isB ? (hasB && i == c - 1 && j == c - 1) : (i == 0 && j == 0);       // one texel speaks for its triangle
+        double w1, w2;
+        if (isB) { w1 = __ddiv_rn((double)(c - 1 - i), (double)(c - 3)); w2 = __ddiv_rn((double)(c - 1 - j), (double)(c - 3)); }
+        else { w1 = __ddiv_rn((double)i, (double)(c - 2)); w2 = __ddiv_rn((double)j, (double)(c - 2)); }
+        const double w0 = __dsub_rn(__dsub_rn(1.0, w1), w2);
+        double P[3][3];
+        bool tb = false, tn = false;
+#pragma unroll
+        for (int q = 0; q < 3; ++q) {
+            long long v = (long long)tris[3 * t + q];
+            if (v < 0 || v >= nv) { tb = true; v = 0; }
+#pragma unroll
+            for (int d = 0; d < 3; ++d) {
+                P[q][d] = verts[3 * v + d];
+                tn |= !(fabs(P[q][d]) <= DBL_MAX);
+            }
+        }
+        bad = counts && tb;
+        nonfinite = counts && tn && !tb;
+#pragma unroll
+        for (int d = 0; d < 3; ++d) {
+            double y = __dadd_rn(__dadd_rn(__dmul_rn(w0, P[0][d]), __dmul_rn(w1, P[1][d])), __dmul_rn(w2, P[2][d]));
+            if (y < 0.0) y = 0.0; else if (y > f.rm1) y = f.rm1;
+            pidx[3 * e + d] = y;
+            pworld[3 * e + d] = (float)__dadd_rn(__dmul_rn(__ddiv_rn(y, f.rm1), f.bext[d]), f.bmin[d]);
+        }
+    }
+    const unsigned long long mb = __ballot(bad), mn = __ballot(nonfinite);
+    if (lane_id() == 0) {
+        if (mb) atomicAdd(&st->n_bad, (unsigned long long)__popcll(mb));
+        if (mn) atomicAdd(&st->n_nonfinite, (unsigned long long)__popcll(mn));
+    }
+}
+
+// thread per image texel, raster order: one aligned uchar4 store each
+__global__ __launch_bounds__(256) void k_tex_pack(const float* __restrict__ rgb, TexLayout L, uchar4* __restrict__ image) {
+    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= (long long)L.W * L.H) return;
+    const int y = (int)(e / L.W), x = (int)(e - (long long)y * L.W);
+    const int cx = x / L.c, cy = y / L.c;
+    const long long k = (long long)cy * L.G + cx;
+    uchar4 o = make_uchar4(0, 0, 0, 0);
+    if (k < L.cells) {
+        const long long s = k * L.c * L.c + (long long)(y - cy * L.c) * L.c + (x - cx * L.c);
+        o = make_uchar4(mesh_colour_u8(rgb[3 * s]), mesh_colour_u8(rgb[3 * s + 1]), mesh_colour_u8(rgb[3 * s + 2]), 255);
+    }
+    image[e] = o;
+}
+
+// thread per unwelded vertex q = 3t + d, which is corner 2 - d of triangle t; per-block min / max of the float32 positions -> partials[block][6]
+template <typename IDX>
+__global__ __launch_bounds__(256) void k_tex_corners(const double* __restrict__ verts, long long nv, const IDX* __restrict__ tris, long long n3, TexLayout L,
+                                                     MeshXform x, const float* __restrict__ grad, float* __restrict__ pos, float* __restrict__ uv,
+                                                     float* __restrict__ nrm, uint32_t* __restrict__ idx, float* __restrict__ partials) {
+    __shared__ float red[24];
+    const long long q = (long long)blockIdx.x * 256 + threadIdx.x;
+    float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
+    if (q < n3) {
+        const long long t = q / 3;
+        const int s = 2 - (int)(q - 3 * t);
+        long long v = (long long)tris[3 * t + s];
+        if (v < 0 || v >= nv) v = 0;                                    // counted by k_tex_points; never dereferenced
+        float p[3];
+        mesh_vertex_f32(verts, v, x, p);
+        const float a[3] = {p[0], p[2], p[1]};
+#pragma unroll
+        for (int d = 0; d < 3; ++d) { pos[3 * q + d] = a[d]; mn[d] = a[d]; mx[d] = a[d]; }
+        const long long k = t >> 1;
+        const int cx = (int)(k % L.G), cy = (int)(k / L.G), c = L.c;
+        double ul, vl;
+        if (t & 1) { ul = s == 1 ? 2.5 : (double)c - 0.5; vl = s == 2 ? 2.5 : (double)c - 0.5; }
+        else { ul = s == 1 ? (double)c - 1.5 : 0.5; vl = s == 2 ? (double)c - 1.5 : 0.5; }
+        uv[2 * q] = (float)__ddiv_rn(__dadd_rn((double)(cx * c), ul), (double)L.W);
+        uv[2 * q + 1] = (float)__ddiv_rn(__dadd_rn((double)(cy * c), vl), (double)L.H);
+        if (grad) mesh_normal_f32(grad, v, x, nrm + 3 * q);
+        idx[q] = (uint32_t)q;
+    }
+    float out[6];
+    block_minmax(mn, mx, red, out);
+    if (threadIdx.x < 6) partials[(long long)blockIdx.x * 6 + threadIdx.x] = out[threadIdx.x];
+}
+
+}  // namespace o2345
+
+using namespace o2345;
+
+extern "C" {
+
+size_t o2345_mesh_texture_texels(long long nt, int texel, int* width_host, int* height_host) {
+    TexLayout L;
+    if (!tex_layout(nt, texel, L)) return 0;
+    if (width_host) *width_host = L.W;
+    if (height_host) *height_host = L.H;
+    return (size_t)L.texels;
+}
+
+int o2345_mesh_texture_points(const double* verts, long long nv, const void* tris, int index_bytes, long long nt, int texel, int grid_R,
+                              const float* bound_min, const float* bound_max, double* points_idx, float* points_world, void* stats, void* stream) {
+    O2345_REQUIRE(index_bytes == 4 || index_bytes == 8, "mesh_texture_points: index_bytes must be 4 or 8");
+    TexLayout L;
+    O2345_REQUIRE(tex_layout(nt, texel, L), "mesh_texture_points: bad layout (nt = %lld >= 1, texel = %d in [4, 64], sides <= 16384, texels < 2^31)", nt, texel);
+    O2345_REQUIRE(nv >= 1 && nv < (1ll << 30), "mesh_texture_points: bad size (nv must be in [1, 2^30))");
+    O2345_REQUIRE(grid_R >= 2, "mesh_texture_points: bad resolution %d", grid_R);
+    O2345_REQUIRE(verts && tris && bound_min && bound_max && points_idx && points_world && stats, "mesh_texture_points: null pointer");
+    O2345_REQUIRE(((uintptr_t)stats & 7) == 0, "mesh_texture_points: stats must be 8-byte aligned");
+    TexFrame f;
+    f.rm1 = (double)grid_R - 1.0;
+    for (int k = 0; k < 3; ++k) {
+        f.bmin[k] = (double)bound_min[k];
+        f.bext[k] = (double)bound_max[k] - (double)bound_min[k];
+        O2345_REQUIRE(f.bext[k] > 0.0 && f.bext[k] <= DBL_MAX && fabs(f.bmin[k]) <= DBL_MAX, "mesh_texture_points: bound_max must be above bound_min on every axis, both finite");
+    }
+    hipStream_t s = (hipStream_t)stream;
+    O2345_HIP(hipMemsetAsync(stats, 0, sizeof(TexStats), s));
+    const dim3 grid(cdiv(L.texels, 256));
+    if (index_bytes == 8) hipLaunchKernelGGL(k_tex_points<long long>, grid, dim3(256), 0, s, verts, nv, (const long long*)tris, nt, L.c, L.texels, f, points_idx, points_world, (TexStats*)stats);
+    else hipLaunchKernelGGL(k_tex_points<int32_t>, grid, dim3(256), 0, s, verts, nv, (const int32_t*)tris, nt, L.c, L.texels, f, points_idx, points_world, (TexStats*)stats);
+    return check_launch("mesh_texture_points");
+}
+
+int o2345_mesh_texture_pack(const float* rgb, long long nt, int texel, uint8_t* image, void* stream) {
+    TexLayout L;
+    O2345_REQUIRE(tex_layout(nt, texel, L), "mesh_texture_pack: bad layout (nt = %lld >= 1, texel = %d in [4, 64], sides <= 16384, texels < 2^31)", nt, texel);
+    O2345_REQUIRE(rgb && image, "mesh_texture_pack: null pointer");
+    O2345_REQUIRE(((uintptr_t)image & 3) == 0, "mesh_texture_pack: image must be 4-byte aligned");
+    hipLaunchKernelGGL(k_tex_pack, dim3(cdiv((long long)L.W * L.H, 256)), dim3(256), 0, (hipStream_t)stream, rgb, L, (uchar4*)image);
+    return check_launch("mesh_texture_pack");
+}
+
+int o2345_mesh_texture_corners(const double* verts, long long nv, const void* tris, int index_bytes, long long nt, int texel, int grid_R,
+                               const float* bound_min, const float* bound_max, const float* scale_mat, const float* trans_mat, const float* grad,
+                               float* positions, float* uv, float* normals, uint32_t* indices, float* bounds, void* workspace, size_t workspace_bytes,
+                               void* stream) {
+    O2345_REQUIRE(index_bytes == 4 || index_bytes == 8, "mesh_texture_corners: index_bytes must be 4 or 8");
+    TexLayout L;
+    O2345_REQUIRE(tex_layout(nt, texel, L), "mesh_texture_corners: bad layout (nt = %lld >= 1, texel = %d in [4, 64], sides <= 16384, texels < 2^31)", nt, texel);
+    O2345_REQUIRE(nv >= 1 && nv < (1ll << 30), "mesh_texture_corners: bad size (nv must be in [1, 2^30))");
+    O2345_REQUIRE(bound_min && bound_max && grid_R >= 2, "mesh_texture_corners: bad bounds / resolution");
+    O2345_REQUIRE(verts && tris && positions && uv && indices && bounds && workspace && (!grad || normals), "mesh_texture_corners: null pointer");
+    const long long n3 = 3 * nt;
+    O2345_REQUIRE(workspace_bytes >= o2345_mesh_bounds_workspace_bytes(n3), "mesh_texture_corners: workspace of %zu bytes, need %zu", workspace_bytes,
+                  o2345_mesh_bounds_workspace_bytes(n3));
+    O2345_REQUIRE(((uintptr_t)workspace & 3) == 0, "mesh_texture_corners: workspace must be 4-byte aligned");
+    const MeshXform x = mesh_xform(grid_R, bound_min, bound_max, scale_mat, trans_mat);
+    const unsigned nb = cdiv(n3, 256);
+    hipStream_t s = (hipStream_t)stream;
+    if (index_bytes == 8) hipLaunchKernelGGL(k_tex_corners<long long>, dim3(nb), dim3(256), 0, s, verts, nv, (const long long*)tris, n3, L, x, grad, positions, uv, normals, indices, (float*)workspace);
+    else hipLaunchKernelGGL(k_tex_corners<int32_t>, dim3(nb), dim3(256), 0, s, verts, nv, (const int32_t*)tris, n3, L, x, grad, positions, uv, normals, indices, (float*)workspace);
+    mesh_bounds_finish((const float*)workspace, (long long)nb, bounds, s);
+    return check_launch("mesh_texture_corners");
+}
+
+}  // extern "C"
+
+// o2345_preload (csrc/api.cpp): querying one kernel makes the HIP runtime load this translation unit's code object on the current device
+namespace o2345 {
+int preload_mesh_texture() {
+    hipFuncAttributes at;
+    return (int)hipFuncGetAttributes(&at, (const void*)k_tex_pack);
+}
+}  // namespace o2345

@@ -13,7 +13,9 @@ x flip compose to exactly that.  ``write_glb`` / ``write_obj`` / ``read_glb`` / 
 DEFINITION of the two files; ``export_asset`` is the device path (csrc/mesh_export.hip): buffers and OBJ text are produced on the device, one D2H copy
 per buffer, one file write.  ``component_labels`` / ``filter_components`` are the host twin (and definition) of the device component filter
 (csrc/mesh_components.hip); ``vertex_adjacency`` / ``smooth_vertices`` are the host twin (and definition) of the device adjacency table and Taubin
-smoothing (csrc/mesh_smooth.hip).  No byte parity with trimesh's own OBJ / GLB writers is claimed (trimesh is not available to compare against)."""
+smoothing (csrc/mesh_smooth.hip).  ``texture_layout`` / ``texture_points`` / ``texture_corners`` / ``pack_texture`` are the host twins (and definition)
+of the texture atlas (csrc/mesh_texture.hip); ``png_bytes`` / ``read_png`` its image file, ``write_textured`` / ``read_glb_texture`` / ``read_obj_texture``
+the textured GLB and the OBJ + MTL + PNG triple.  No byte parity with trimesh's own OBJ / GLB writers is claimed (trimesh is not available to compare against)."""
 import json
 import os
 import struct
@@ -154,9 +156,12 @@ def _host_mesh(positions, faces, colors, normals):
 _GLB_MAGIC, _GLB_JSON, _GLB_BIN = 0x46546C67, 0x4E4F534A, 0x004E4942
 
 
-def glb_json(n, m, colors, normals, pos_min, pos_max):
+def glb_json(n, m, colors, normals, pos_min, pos_max, texcoords=False, image_bytes=0):
     """The JSON chunk (bytes, space-padded to a multiple of 4): one buffer, views in the order indices / POSITION / COLOR_0 / NORMAL, one accessor per
-    view, one mesh with one triangle primitive, one node, one scene.  Fixed key order and separators: the bytes are reproducible."""
+    view, one mesh with one triangle primitive, one node, one scene.  Fixed key order and separators: the bytes are reproducible.
+    ``texcoords`` adds TEXCOORD_0 (VEC2 float32) after NORMAL; ``image_bytes`` > 0 adds a last view without a target that holds a PNG of that many bytes,
+    and behind "buffers" the keys "materials" (baseColorTexture, metallic 0, roughness 1), "textures", "images", "samplers" (LINEAR / LINEAR,
+    CLAMP_TO_EDGE: what texture_layout's gutters are made for); the primitive then names material 0.  Without the two the bytes are what they were."""
     views, accessors, off = [], [], 0
 
     def add(nbytes, target, accessor):
@@ -173,22 +178,40 @@ def glb_json(n, m, colors, normals, pos_min, pos_max):
         attrs["COLOR_0"] = add(4 * n, 34962, {"componentType": 5121, "normalized": True, "count": n, "type": "VEC4"})
     if normals:
         attrs["NORMAL"] = add(12 * n, 34962, {"componentType": 5126, "count": n, "type": "VEC3"})
+    if texcoords:
+        attrs["TEXCOORD_0"] = add(8 * n, 34962, {"componentType": 5126, "count": n, "type": "VEC2"})
+    prim = {"attributes": attrs, "indices": indices, "mode": 4}
+    if image_bytes:
+        views.append({"buffer": 0, "byteOffset": off, "byteLength": int(image_bytes)})
+        off += (int(image_bytes) + 3) // 4 * 4
+        prim["material"] = 0
     doc = {"asset": {"version": "2.0", "generator": "o2345-hip"}, "scene": 0, "scenes": [{"nodes": [0]}], "nodes": [{"mesh": 0}],
-           "meshes": [{"primitives": [{"attributes": attrs, "indices": indices, "mode": 4}]}], "accessors": accessors, "bufferViews": views,
+           "meshes": [{"primitives": [prim]}], "accessors": accessors, "bufferViews": views,
            "buffers": [{"byteLength": off}]}
+    if image_bytes:
+        doc["materials"] = [{"pbrMetallicRoughness": {"baseColorTexture": {"index": 0}, "metallicFactor": 0.0, "roughnessFactor": 1.0}}]
+        doc["textures"] = [{"sampler": 0, "source": 0}]
+        doc["images"] = [{"bufferView": len(views) - 1, "mimeType": "image/png"}]
+        doc["samplers"] = [{"magFilter": 9729, "minFilter": 9729, "wrapS": 33071, "wrapT": 33071}]
     js = json.dumps(doc, separators=(",", ":")).encode("ascii")
     return js + b" " * (-len(js) % 4)
 
 
-def write_glb_buffers(path, indices, positions, rgba, normals, bounds):
-    """GLB from its four buffers as they sit in the file (host arrays: indices uint32 [M,3], positions float32 [N,3], rgba uint8 [N,4] or None, normals
-    float32 [N,3] or None; bounds [2,3] = per-axis min, max of positions): 12-byte header, JSON chunk, BIN chunk; every view is a multiple of 4 bytes."""
+def write_glb_buffers(path, indices, positions, rgba, normals, bounds, uv=None, png=None):
+    """GLB from its buffers as they sit in the file (host arrays: indices uint32 [M,3], positions float32 [N,3], rgba uint8 [N,4] or None, normals
+    float32 [N,3] or None; bounds [2,3] = per-axis min, max of positions): 12-byte header, JSON chunk, BIN chunk; every view is a multiple of 4 bytes.
+    A textured file also has ``uv`` float32 [N,2] and ``png`` (the bytes of the image, zero-padded to a multiple of 4 in the file), and no ``rgba``."""
     n, m = positions.shape[0], indices.shape[0]
     if n == 0 or m == 0:
         raise ValueError("GLB export: an empty mesh has no valid glTF form (accessors need count >= 1)")
+    if (uv is None) != (png is None) or (uv is not None and rgba is not None):
+        raise ValueError("GLB export: a textured file has uv and png and no vertex colours")
     bounds = np.asarray(bounds, np.float32).reshape(2, 3)
-    js = glb_json(n, m, rgba is not None, normals is not None, bounds[0], bounds[1])
-    parts = [np.ascontiguousarray(a).reshape(-1).view(np.uint8) for a in (indices, positions, rgba, normals) if a is not None]
+    js = glb_json(n, m, rgba is not None, normals is not None, bounds[0], bounds[1], uv is not None, 0 if png is None else len(png))
+    image = None if png is None else np.frombuffer(bytes(png) + b"\0" * (-len(png) % 4), np.uint8)
+    if uv is not None:
+        uv = np.ascontiguousarray(uv, np.float32).reshape(n, 2)
+    parts = [np.ascontiguousarray(a).reshape(-1).view(np.uint8) for a in (indices, positions, rgba, normals, uv, image) if a is not None]
     nbin = sum(a.size for a in parts)
     assert indices.dtype.itemsize == 4 and positions.dtype == np.float32 and nbin % 4 == 0
     with open(path, "wb") as f:
@@ -206,11 +229,21 @@ def write_glb(path, positions, faces, colors=None, normals=None):
 
 
 _GLB_TYPES = {5121: ("u1", 1), 5125: ("<u4", 4), 5126: ("<f4", 4)}
-_GLB_WIDTH = {"SCALAR": 1, "VEC3": 3, "VEC4": 4}
+_GLB_WIDTH = {"SCALAR": 1, "VEC2": 2, "VEC3": 3, "VEC4": 4}
 
 
 def read_glb(path):
-    """Parser for the files written above -> (positions float32 [N,3], faces int32 [M,3], colors uint8 [N,4] or None, normals float32 [N,3] or None)."""
+    """Parser for the files written above -> (positions float32 [N,3], faces int32 [M,3], colors uint8 [N,4] or None, normals float32 [N,3] or None).
+    The texture of a textured file: read_glb_texture."""
+    return _read_glb(path)[:4]
+
+
+def read_glb_texture(path):
+    """-> (uv float32 [N,2], image uint8 [H,W,4], sampler dict) of a textured file written above, or None for a file without a texture."""
+    return _read_glb(path)[4]
+
+
+def _read_glb(path):
     raw = open(path, "rb").read()
     magic, version, total = struct.unpack_from("<III", raw, 0)
     assert magic == _GLB_MAGIC and version == 2 and total == len(raw)
@@ -231,8 +264,16 @@ def read_glb(path):
     prim = doc["meshes"][0]["primitives"][0]
     at = prim["attributes"]
     faces = accessor(prim["indices"]).reshape(-1, 3).astype(np.int32)
+    texture = None
+    if "TEXCOORD_0" in at:
+        mat = doc["materials"][prim["material"]]["pbrMetallicRoughness"]
+        tex = doc["textures"][mat["baseColorTexture"]["index"]]
+        img = doc["images"][tex["source"]]
+        v = doc["bufferViews"][img["bufferView"]]
+        assert img["mimeType"] == "image/png" and "target" not in v
+        texture = (accessor(at["TEXCOORD_0"]).copy(), png_image(raw[base + v["byteOffset"]:base + v["byteOffset"] + v["byteLength"]]), doc["samplers"][tex["sampler"]])
     return (accessor(at["POSITION"]).copy(), faces, accessor(at["COLOR_0"]).copy() if "COLOR_0" in at else None,
-            accessor(at["NORMAL"]).copy() if "NORMAL" in at else None)
+            accessor(at["NORMAL"]).copy() if "NORMAL" in at else None, texture)
 
 
 def obj_coordinate_digits(bounds):
@@ -689,6 +730,353 @@ def project_vertices(verts_idx, field, resolution, iterations, level=0.0, tol=5e
     return x, info
 
 
+# ------------------------------------------------------------------------------------------------------------------ texture atlas
+# One square cell of c x c texels per PAIR of triangles, cells in face order, row-major in a grid G cells wide.  DESIGN.md section 7 has the derivation;
+# the functions below are the host twin of csrc/mesh_texture.hip and the DEFINITION of its results, to the last bit.
+TEXTURE_MAX_SIDE = 16384
+
+
+def _check_texel(texel):
+    """-> 0 for off (None or 0), else the integer in [4, 64]"""
+    if texel is None:
+        return 0
+    if isinstance(texel, (bool, np.bool_)) or not isinstance(texel, (int, np.integer)) or not (texel == 0 or 4 <= texel <= 64):
+        raise ValueError(f"texture: texel must be 0 (off) or an integer in [4, 64], got {texel!r}")
+    return int(texel)
+
+
+def texture_layout(nt, texel):
+    """The atlas of ``nt`` triangles at ``texel`` = c texels per cell edge -> {"texel": c, "cells": ceil(nt / 2), "grid": G = ceil(sqrt(cells)), "rows":
+    ceil(cells / G), "width": G c, "height": rows c, "texels": cells c^2 (the texels of used cells: the length of the texel point list)}.  Triangles 2k
+    and 2k + 1 share cell k, which sits at column k mod G, row k div G; the image need not be square.  Refused (ValueError): c outside [4, 64], nt < 1,
+    a side over 16384, cells c^2 >= 2^31."""
+    c = _check_texel(texel)
+    if c == 0:
+        raise ValueError("texture: texel must be an integer in [4, 64], got 0 (off)")
+    if isinstance(nt, (bool, np.bool_)) or int(nt) != nt or nt < 1:
+        raise ValueError(f"texture: the triangle count must be a positive integer, got {nt!r}")
+    import math
+    cells = (int(nt) + 1) // 2
+    G = math.isqrt(cells - 1) + 1
+    rows = (cells + G - 1) // G
+    W, H = G * c, rows * c
+    if W > TEXTURE_MAX_SIDE or H > TEXTURE_MAX_SIDE or cells * c * c >= 2 ** 31:
+        raise ValueError(f"texture: {nt} triangles at texel {c} need an image of {W} x {H}; a side is limited to {TEXTURE_MAX_SIDE} and the texel list to 2^31")
+    return {"texel": c, "cells": cells, "grid": G, "rows": rows, "width": W, "height": H, "texels": cells * c * c}
+
+
+def texture_cell(texel):
+    """The inside of one cell -> (owner uint8 [c, c] indexed [j, i]: 0 = triangle A (i + j <= c - 1), 1 = triangle B (i + j >= c); w float64 [c, c, 3]: the
+    barycentric weights of the texel centre (i + 0.5, j + 0.5) with respect to its owner's UV corners; corners float64 [2, 3, 2]: those corners, A's
+    (0.5, 0.5), (c - 1.5, 0.5), (0.5, c - 1.5) and B's (c - 0.5, c - 0.5), (2.5, c - 0.5), (c - 0.5, 2.5)).  A: w1 = i / (c - 2), w2 = j / (c - 2);
+    B: w1 = (c - 1 - i) / (c - 3), w2 = (c - 1 - j) / (c - 3); both: w0 = (1 - w1) - w2.  Never clamped: texels in the gutter extrapolate, which is what
+    makes bilinear sampling inside a triangle reproduce a linear function exactly."""
+    c = int(texel)
+    j, i = np.meshgrid(np.arange(c), np.arange(c), indexing="ij")
+    owner = (i + j >= c).astype(np.uint8)
+    fi, fj = i.astype(np.float64), j.astype(np.float64)
+    w1 = np.where(owner == 0, fi / float(c - 2), (float(c - 1) - fi) / float(c - 3))
+    w2 = np.where(owner == 0, fj / float(c - 2), (float(c - 1) - fj) / float(c - 3))
+    w0 = (1.0 - w1) - w2
+    corners = np.array([[[0.5, 0.5], [c - 1.5, 0.5], [0.5, c - 1.5]], [[c - 0.5, c - 0.5], [2.5, c - 0.5], [c - 0.5, 2.5]]], np.float64)
+    return owner, np.stack([w0, w1, w2], -1), corners
+
+
+def _texture_mesh(verts_idx, faces, what):
+    p = np.asarray(verts_idx, dtype=np.float64).reshape(-1, 3)
+    f = np.asarray(faces).reshape(-1, 3).astype(np.int64, copy=False)
+    if f.size and (f.min() < 0 or f.max() >= p.shape[0]):
+        raise ValueError(f"{what}: faces index outside 0 .. {p.shape[0] - 1}")
+    return p, f
+
+
+def _bounds64(bounds, what):
+    b0 = np.asarray(bounds[0], np.float32).reshape(-1).astype(np.float64)           # float32 values, widened
+    b1 = np.asarray(bounds[1], np.float32).reshape(-1).astype(np.float64)
+    if b0.shape != (3,) or b1.shape != (3,) or not (np.isfinite(b0).all() and np.isfinite(b1).all() and (b1 > b0).all()):
+        raise ValueError(f"{what}: bound_max must be above bound_min on every axis, both finite, got {bounds!r}")
+    return b0, b1 - b0
+
+
+def texture_points(verts_idx, faces, texel, resolution, bounds=((-1.0, -1.0, -1.0), (1.0, 1.0, 1.0))):
+    """The surface point of every texel of every used cell (host twin of ops.mesh_texture_points, and the definition of its result, to the last bit) ->
+    (points float64 [cells c^2, 3] in index coordinates, world float32 [cells c^2, 3]).  Cell-major: point k c^2 + j c + i is local texel (i, j) of cell k.
+    Its owner (texture_cell) is triangle 2k or min(2k + 1, nt - 1) -- for an odd count the B half of the last cell repeats the last triangle -- with
+    corners P0, P1, P2 in ``verts_idx``; p = (w0 P0 + w1 P1) + w2 P2 in float64, every operation separate, then each coordinate clamped to [0, R - 1].
+    World point: float32(p / (R - 1) * ext + bmin) with the float32 ``bounds`` = (bound_min, bound_max) widened to float64, ext = bmax - bmin: what
+    project_vertices shows the network.  Refused (ValueError): a non-finite coordinate of a referenced vertex, a face index outside [0, N), and what
+    texture_layout refuses."""
+    p, f = _texture_mesh(verts_idx, faces, "texture_points")
+    L = texture_layout(f.shape[0], texel)
+    if isinstance(resolution, (bool, np.bool_)) or int(resolution) != resolution or resolution < 2:
+        raise ValueError(f"texture_points: resolution must be an integer >= 2, got {resolution!r}")
+    b0, ext = _bounds64(bounds, "texture_points")
+    if not np.isfinite(p[f.reshape(-1)]).all():
+        raise ValueError("texture_points: non-finite vertex coordinate")
+    c, cells, nt, rm1 = L["texel"], L["cells"], f.shape[0], float(int(resolution) - 1)
+    owner, w, _ = texture_cell(c)
+    tri = np.minimum(2 * np.arange(cells)[:, None] + owner.reshape(1, -1), nt - 1)          # [cells, c^2]
+    P = p[f[tri]]                                                                           # [cells, c^2, 3 corners, 3]
+    w = w.reshape(1, c * c, 3, 1)
+    x = (w[:, :, 0] * P[:, :, 0] + w[:, :, 1] * P[:, :, 1]) + w[:, :, 2] * P[:, :, 2]
+    x = np.where(x < 0.0, 0.0, np.where(x > rm1, rm1, x)).reshape(-1, 3)
+    return x, np.ascontiguousarray((x / rm1 * ext + b0).astype(np.float32))
+
+
+def pack_texture(rgb, nt, texel):
+    """Cell-major texel colours (float [cells c^2, 3], the order of texture_points) -> the image, uint8 [height, width, 4] in raster order (row 0 on top,
+    where v = 0): colour = uint8(int(float32(x) * 255)), the truncation the vertex colours use, alpha 255; the texels of unused cells are 0, 0, 0, 0.
+    Host twin of ops.mesh_texture_pack."""
+    L = texture_layout(nt, texel)
+    c, G, cells = L["texel"], L["grid"], L["cells"]
+    a = np.asarray(rgb, np.float32).reshape(-1, 3)
+    if a.shape[0] != L["texels"]:
+        raise ValueError(f"pack_texture: {L['texels']} texel colours expected, got {a.shape[0]}")
+    with np.errstate(invalid="ignore"):
+        q = (a * np.float32(255.0)).astype(np.int32).astype(np.uint8)
+    cell = np.zeros((L["rows"] * G, c, c, 4), np.uint8)
+    cell[:cells, :, :, :3] = q.reshape(cells, c, c, 3)
+    cell[:cells, :, :, 3] = 255
+    return np.ascontiguousarray(cell.reshape(L["rows"], G, c, c, 4).transpose(0, 2, 1, 3, 4).reshape(L["height"], L["width"], 4))
+
+
+def _mat44(m):
+    return None if m is None else np.asarray(m.detach().cpu().numpy() if hasattr(m, "detach") else m, np.float32).reshape(-1, 4, 4)[0].astype(np.float64)
+
+
+def frame_positions(verts_idx, resolution, bound_min=(-1.0, -1.0, -1.0), bound_max=(1.0, 1.0, 1.0), scale_mat=None, trans_mat=None):
+    """Index coordinates -> the float32 positions of the PLY (csrc/mesh_math.h, mesh_vertex_f32, operation for operation): v / (R - 1) * ext + bmin with
+    ext the FLOAT32 difference of the bounds; * s + t of scale_mat; the rows of trans_mat as ((T0 x + T1 y) + T2 z) + T3; rounded to float32 once."""
+    p = np.asarray(verts_idx, dtype=np.float64).reshape(-1, 3)
+    b0, b1 = np.asarray(bound_min, np.float32).reshape(3), np.asarray(bound_max, np.float32).reshape(3)
+    v = p / float(int(resolution) - 1) * (b1 - b0).astype(np.float64) + b0.astype(np.float64)
+    S, T = _mat44(scale_mat), _mat44(trans_mat)
+    if S is not None:
+        v = v * S[0, 0] + S[:3, 3]
+    if T is not None:
+        v = np.stack([((T[r, 0] * v[:, 0] + T[r, 1] * v[:, 1]) + T[r, 2] * v[:, 2]) + T[r, 3] for r in range(3)], 1)
+    with np.errstate(over="ignore"):
+        return v.astype(np.float32)
+
+
+def frame_normals(grad, trans_mat=None):
+    """SDF gradients float32 [N,3] -> the float32 unit normals of the asset frame (csrc/mesh_math.h, mesh_normal_f32, operation for operation, float64):
+    g / |g|, through the 3x3 of trans_mat when given and renormalised, y and z exchanged; (0, 1, 0) for a zero or non-finite gradient."""
+    g = np.asarray(grad, np.float32).reshape(-1, 3).astype(np.float64)
+    T = _mat44(trans_mat)
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        l = np.sqrt((g[:, 0] * g[:, 0] + g[:, 1] * g[:, 1]) + g[:, 2] * g[:, 2])
+        ok = (l > 0.0) & (l < np.inf)
+        g = g / l[:, None]
+        if T is not None:
+            w = np.stack([(T[r, 0] * g[:, 0] + T[r, 1] * g[:, 1]) + T[r, 2] * g[:, 2] for r in range(3)], 1)
+            l = np.sqrt((w[:, 0] * w[:, 0] + w[:, 1] * w[:, 1]) + w[:, 2] * w[:, 2])
+            ok2 = ok & (l > 0.0) & (l < np.inf)
+            g = np.where(ok[:, None], w / l[:, None], g)
+            ok = ok2
+        out = np.where(ok[:, None], g[:, [0, 2, 1]], np.array([0.0, 1.0, 0.0])).astype(np.float32)
+    return out
+
+
+def texture_corner_pixels(nt, texel):
+    """The corners of every triangle in the image, in texels, float64 [nt, 3, 2] in the triangle's own corner order: (cell_x c + u_local, cell_y c +
+    v_local) with the local UV corners of texture_cell; exact (multiples of 0.5 below 2^15)."""
+    L = texture_layout(nt, texel)
+    c, G = L["texel"], L["grid"]
+    t = np.arange(int(nt))
+    k = t // 2
+    local = texture_cell(c)[2][t % 2]
+    return np.stack([((k % G) * c).astype(np.float64)[:, None] + local[:, :, 0], ((k // G) * c).astype(np.float64)[:, None] + local[:, :, 1]], -1)
+
+
+def texture_corners(verts_idx, faces, texel, resolution, bound_min=(-1.0, -1.0, -1.0), bound_max=(1.0, 1.0, 1.0), scale_mat=None, trans_mat=None, grad=None):
+    """The unwelded vertices of the textured mesh (host twin of ops.mesh_texture_corners, and the definition of its result, to the last bit) -> (positions
+    float32 [3 nt, 3] in the asset frame, uv float32 [3 nt, 2], normals float32 [3 nt, 3] or None, bounds float32 [2, 3]).  Triangle t = (a, b, c) gives
+    corners 3t, 3t + 1, 3t + 2 = c, b, a (the asset frame's reversed winding), so the index buffer is 0, 1, 2, ...  A corner's position is its vertex's
+    position (frame_positions, y and z exchanged: the welded export's bits); its uv is ((cell_x c + u_local) / W, (cell_y c + v_local) / H) with the
+    local UV corner of texture_cell, in float64, rounded to float32 once; its normal is its vertex's (frame_normals of ``grad`` float32 [N,3])."""
+    p, f = _texture_mesh(verts_idx, faces, "texture_corners")
+    L = texture_layout(f.shape[0], texel)
+    c, nt = L["texel"], f.shape[0]
+    vid = f[:, ::-1].reshape(-1)
+    pos = np.ascontiguousarray(frame_positions(p, resolution, bound_min, bound_max, scale_mat, trans_mat)[:, [0, 2, 1]][vid])
+    px = texture_corner_pixels(nt, c)[:, ::-1]                                               # corners reversed
+    uv = np.stack([px[:, :, 0] / float(L["width"]), px[:, :, 1] / float(L["height"])], -1).reshape(-1, 2).astype(np.float32)
+    nrm = None if grad is None else np.ascontiguousarray(frame_normals(grad, trans_mat)[vid])
+    return pos, uv, nrm, np.stack([pos.min(0), pos.max(0)])
+
+
+def sample_texture(image, uv):
+    """Bilinear sample the way a glTF viewer does with the file's sampler (LINEAR, CLAMP_TO_EDGE, texel centres at +0.5, no mipmaps) -> (value float64
+    [n, C], touched: per sample the four (x, y, weight) it read).  ``image`` float [H, W, C], ``uv`` [n, 2] in [0, 1].  For tests and inspection."""
+    img = np.asarray(image, np.float64)
+    H, W = img.shape[:2]
+    uv = np.asarray(uv, np.float64).reshape(-1, 2)
+    x, y = uv[:, 0] * W - 0.5, uv[:, 1] * H - 0.5
+    x0, y0 = np.floor(x), np.floor(y)
+    fx, fy = x - x0, y - y0
+    out, touched = np.zeros((uv.shape[0], img.shape[2])), []
+    for dx, dy, wgt in ((0, 0, (1 - fx) * (1 - fy)), (1, 0, fx * (1 - fy)), (0, 1, (1 - fx) * fy), (1, 1, fx * fy)):
+        xi, yi = np.clip(x0 + dx, 0, W - 1).astype(np.int64), np.clip(y0 + dy, 0, H - 1).astype(np.int64)
+        out += wgt[:, None] * img[yi, xi]
+        touched.append((xi, yi, wgt))
+    return out, touched
+
+
+# ---- PNG: 8-bit RGBA, one IDAT, filter 0 on every row; stdlib zlib only
+_PNG_MAGIC = b"\x89PNG\r\n\x1a\n"
+
+
+def _png_chunk(kind, data):
+    import zlib
+    return struct.pack(">I", len(data)) + kind + data + struct.pack(">I", zlib.crc32(kind + data) & 0xFFFFFFFF)
+
+
+def png_bytes(rgba, level=1):
+    """uint8 [H, W, 4] -> the bytes of an 8-bit RGBA PNG: IHDR, one IDAT (zlib at ``level`` 0 .. 9, 0 = stored; every row has filter type 0), IEND."""
+    import zlib
+    a = np.ascontiguousarray(rgba, np.uint8)
+    if a.ndim != 3 or a.shape[2] != 4 or a.shape[0] < 1 or a.shape[1] < 1:
+        raise ValueError(f"png_bytes: expected uint8 [H, W, 4], got {a.shape}")
+    if isinstance(level, (bool, np.bool_)) or int(level) != level or not 0 <= level <= 9:
+        raise ValueError(f"png_bytes: level must be an integer in [0, 9], got {level!r}")
+    H, W = a.shape[:2]
+    rows = np.zeros((H, 1 + 4 * W), np.uint8)
+    rows[:, 1:] = a.reshape(H, 4 * W)
+    return (_PNG_MAGIC + _png_chunk(b"IHDR", struct.pack(">IIBBBBB", W, H, 8, 6, 0, 0, 0)) + _png_chunk(b"IDAT", zlib.compress(rows.data, int(level)))
+            + _png_chunk(b"IEND", b""))
+
+
+def png_image(raw):
+    """The bytes of a PNG written by png_bytes -> uint8 [H, W, 4]; checks every chunk's CRC.  Not a general PNG reader: 8-bit RGBA, filter 0 only."""
+    import zlib
+    if raw[:8] != _PNG_MAGIC:
+        raise ValueError("png: bad signature")
+    off, idat, head = 8, [], None
+    while off < len(raw):
+        n, = struct.unpack_from(">I", raw, off)
+        kind, data = raw[off + 4:off + 8], raw[off + 8:off + 8 + n]
+        if struct.unpack_from(">I", raw, off + 8 + n)[0] != zlib.crc32(kind + data) & 0xFFFFFFFF:
+            raise ValueError(f"png: bad CRC in chunk {kind!r}")
+        off += 12 + n
+        if kind == b"IHDR":
+            head = struct.unpack(">IIBBBBB", data)
+        elif kind == b"IDAT":
+            idat.append(data)
+        elif kind == b"IEND":
+            break
+    if head is None or head[2:] != (8, 6, 0, 0, 0):
+        raise ValueError(f"png: not an 8-bit RGBA image without interlace ({head})")
+    W, H = head[:2]
+    rows = np.frombuffer(zlib.decompress(b"".join(idat)), np.uint8).reshape(H, 1 + 4 * W)
+    if rows[:, 0].any():
+        raise ValueError("png: a row filter other than 0")
+    return np.ascontiguousarray(rows[:, 1:]).reshape(H, W, 4)
+
+
+def read_png(path):
+    """A file written with png_bytes -> uint8 [H, W, 4]."""
+    return png_image(open(path, "rb").read())
+
+
+# ---- textured OBJ: mesh.obj + mesh.mtl + mesh.png side by side
+OBJ_MATERIAL = "material_0"
+
+
+def obj_texture_text_bytes(n, K, normals):
+    """Closed-form size of the textured OBJ's records (== o2345_obj_texture_text_bytes) for n = 3 nt unwelded vertices: n "v", n "vt", [n "vn",] n / 3 "f"."""
+    dn = len(str(int(n)))
+    return n * (1 + 3 * (K + 11) + 1) + n * 25 + (n * 39 if normals else 0) + (n // 3) * (1 + 3 * (1 + (3 * dn + 2 if normals else 2 * dn + 1)) + 1)
+
+
+def obj_texture_text_numpy(positions, uv, normals, K):
+    """The records of the textured OBJ from printf-style formatting on the host (the definition the device packer is tested against): "v" records as in
+    obj_text_numpy without colours; "vt %10.8f %10.8f" with the second field float32(1 - v) (OBJ's origin is bottom-left); "vn" as before; "f a/a b/b c/c"
+    or "f a/a/a b/b/b c/c/c" over the unwelded corners 1 .. n in order, each token right-aligned in 2 d + 1 or 3 d + 2 bytes, d = decimal digits of n."""
+    n, dn, w = positions.shape[0], len(str(positions.shape[0])), K + 10
+    vfmt = "v" + (" %%%d.8f" % w) * 3 + "\n"
+    out = [vfmt % tuple(r) for r in positions.astype(np.float64).tolist()]
+    uv = np.asarray(uv, np.float32)
+    flipped = (1.0 - uv[:, 1].astype(np.float64)).astype(np.float32)
+    out += ["vt %10.8f %10.8f\n" % (a, b) for a, b in zip(uv[:, 0].astype(np.float64).tolist(), flipped.astype(np.float64).tolist())]
+    if normals is not None:
+        out += ["vn %11.8f %11.8f %11.8f\n" % tuple(r) for r in normals.astype(np.float64).tolist()]
+    tok = (lambda a: "%d/%d/%d" % (a, a, a)) if normals is not None else (lambda a: "%d/%d" % (a, a))
+    ffmt = "f" + (" %%%ds" % (3 * dn + 2 if normals is not None else 2 * dn + 1)) * 3 + "\n"
+    out += [ffmt % (tok(3 * t + 1), tok(3 * t + 2), tok(3 * t + 3)) for t in range(n // 3)]
+    return "".join(out).encode("ascii")
+
+
+def obj_texture_names(path):
+    """-> (path of the .mtl, path of the .png) next to ``path``, same stem"""
+    stem = os.path.splitext(str(path))[0]
+    return stem + ".mtl", stem + ".png"
+
+
+def obj_texture_header(path):
+    return ("mtllib %s\nusemtl %s\n" % (os.path.basename(obj_texture_names(path)[0]), OBJ_MATERIAL)).encode("ascii")
+
+
+def write_obj_texture_files(path, text, png):
+    """``path`` (the header + ``text``: bytes or a uint8 array), its .mtl (one material, map_Kd) and its .png"""
+    mtl, img = obj_texture_names(path)
+    with open(path, "wb") as fh:
+        fh.write(obj_texture_header(path))
+        fh.write(text if isinstance(text, (bytes, bytearray)) else np.ascontiguousarray(text, np.uint8).data)
+    with open(mtl, "wb") as fh:
+        fh.write(("newmtl %s\nKa 1.00000000 1.00000000 1.00000000\nKd 1.00000000 1.00000000 1.00000000\nKs 0.00000000 0.00000000 0.00000000\nmap_Kd %s\n"
+                  % (OBJ_MATERIAL, os.path.basename(img))).encode("ascii"))
+    with open(img, "wb") as fh:
+        fh.write(png)
+
+
+def read_obj_texture(path):
+    """A textured OBJ written above -> (positions float64 [N,3], uv float64 [N,2] with v flipped back to the image's top-left origin, normals or None,
+    faces int32 [M,3] 0-based position indices, image uint8 [H,W,4]); checks that every face token names the same index for every attribute and that
+    mtllib / usemtl / map_Kd lead to the image."""
+    v, vt, vn, f, mtllib, usemtl = [], [], [], [], None, None
+    with open(path, "r", encoding="ascii") as fh:
+        for line in fh:
+            t = line.split()
+            if not t:
+                continue
+            if t[0] == "v":
+                v.append([float(x) for x in t[1:4]])
+            elif t[0] == "vt":
+                vt.append([float(t[1]), 1.0 - float(t[2])])
+            elif t[0] == "vn":
+                vn.append([float(x) for x in t[1:4]])
+            elif t[0] == "f":
+                parts = [x.split("/") for x in t[1:]]
+                assert all(len(set(q)) == 1 and len(q) == (3 if vn else 2) for q in parts), line
+                f.append([int(q[0]) - 1 for q in parts])
+            elif t[0] == "mtllib":
+                mtllib = t[1]
+            elif t[0] == "usemtl":
+                usemtl = t[1]
+    here = os.path.dirname(str(path))
+    mtl = open(os.path.join(here, mtllib), "r", encoding="ascii").read().split("\n")
+    assert mtl[0] == "newmtl " + usemtl
+    image = [l.split()[1] for l in mtl if l.startswith("map_Kd ")][0]
+    return (np.asarray(v, np.float64).reshape(-1, 3), np.asarray(vt, np.float64).reshape(-1, 2), np.asarray(vn, np.float64).reshape(-1, 3) if vn else None,
+            np.asarray(f, np.int32).reshape(-1, 3), read_png(os.path.join(here, image)))
+
+
+def write_textured(path, positions, uv, normals, image, bounds=None, png_level=1):
+    """Host arrays of a textured mesh (texture_corners + pack_texture) -> ``path`` by its extension: a ``.glb`` with the PNG inside, or the ``.obj`` /
+    ``.mtl`` / ``.png`` triple.  The host layer and the DEFINITION of both files; export_asset with ``texture=`` is the device path."""
+    ext = _asset_ext(path)
+    if ext == ".ply":
+        raise ValueError("texture: a .ply has no texture coordinates; the output is .glb or .obj")
+    p = np.ascontiguousarray(positions, np.float32).reshape(-1, 3)
+    png = png_bytes(image, png_level)
+    if ext == ".glb":
+        idx = np.arange(p.shape[0], dtype=np.uint32).reshape(-1, 3)
+        write_glb_buffers(path, idx, p, None, normals, np.stack([p.min(0), p.max(0)]) if bounds is None else bounds, uv=uv, png=png)
+    else:
+        write_obj_texture_files(path, obj_texture_text_numpy(p, uv, normals, obj_coordinate_digits(p if bounds is None else bounds)), png)
+
+
 def convert_mesh(ply_path, out_path, min_component_faces=0, keep_largest=False, smooth_iterations=0, decimate_cell=0):
     """convert_mesh_format (utils/utils.py:31-47) for a mesh already on disk: read the PLY, exchange y and z, reverse the faces, write ``out_path`` by its
     extension (.glb or .obj) with the PLY's vertex colours.  ``min_component_faces`` / ``keep_largest``: filter_components on the way (off by default).
@@ -699,7 +1087,7 @@ def convert_mesh(ply_path, out_path, min_component_faces=0, keep_largest=False, 
     cast to float64, the result cast back to float32, the colours merged as decimate_mesh defines.  For the same reason that is not byte-equal to the
     device export, which clusters the index coordinates (cell in units of the grid spacing) and colours the new vertices.
     There is no ``project_iterations`` here: projecting vertices onto the SDF's zero set (project_vertices, ops.mesh_project) needs the network, and a
-    mesh file has none.  Returns ``out_path``."""
+    mesh file has none; for the same reason there is no ``texture_texel``.  Returns ``out_path``."""
     ext = _asset_ext(out_path)
     if ext == ".ply":
         raise ValueError("convert_mesh: the output is .glb or .obj")
@@ -719,15 +1107,38 @@ def convert_mesh(ply_path, out_path, min_component_faces=0, keep_largest=False, 
 
 
 def export_asset(path, verts_idx, tris, grid_R, bound_min=(-1.0, -1.0, -1.0), bound_max=(1.0, 1.0, 1.0), scale_mat=None, trans_mat=None,
-                 vertex_colors=None, normals=None):
+                 vertex_colors=None, normals=None, texture=None, png_level=None):
     """Device path by extension: ``.ply`` -> export_mesh (reconstruction frame, unchanged); ``.glb`` / ``.obj`` -> asset frame.  Arguments as for export_mesh;
     ``normals``: the SDF gradient at the vertices, fp32 [N,3] on the device (exported as unit normals), or None.  Buffers and OBJ text are produced on
-    the device (csrc/mesh_export.hip), copied to the host once each and written in one go.  Returns (n_vertices, n_triangles)."""
+    the device (csrc/mesh_export.hip), copied to the host once each and written in one go.  Returns (n_vertices, n_triangles).
+    ``texture`` = {"texel": c, "rgb": fp32 [cells c^2, 3] on the device, the colours at ops.mesh_texture_points' points[, "stats": that op's counters]}:
+    the textured asset instead (csrc/mesh_texture.hip) -- 3 M unwelded vertices with TEXCOORD_0 and no vertex colours, the atlas as a PNG inside the
+    ``.glb`` or as ``.mtl`` + ``.png`` next to the ``.obj`` (zlib level ``png_level``, None: the config default); a ``.ply`` path is refused."""
     ext = _asset_ext(path)
+    if texture is not None and ext == ".ply":
+        raise ValueError("texture: a .ply has no texture coordinates; the output is .glb or .obj")
     if ext == ".ply":
         return export_mesh(path, verts_idx, tris, grid_R, bound_min, bound_max, scale_mat, trans_mat, vertex_colors)
     from . import ops
     n, m = int(verts_idx.shape[0]), int(tris.shape[0])
+    if texture is not None and n and m:
+        from . import config
+        level = config.mesh_texture_png_level(png_level)
+        image = ops.mesh_texture_pack(texture["rgb"], m, texture["texel"])
+        pos, uv, nrm, idx, bounds = ops.mesh_texture_corners(verts_idx, tris, texture["texel"], grid_R, bound_min, bound_max, scale_mat, trans_mat, normals)
+        text = ops.obj_texture_text(pos, uv, nrm, bounds=bounds) if ext == ".obj" else None
+        stats = texture.get("stats")
+        dev = [t for t in ((image, text, stats) if ext == ".obj" else (image, idx, pos, nrm, uv, bounds, stats)) if t is not None]
+        host = ops.to_host_numpy(*dev)                                 # the one synchronisation of the whole chain
+        if stats is not None:
+            ops.texture_check(host[-1])
+        png = png_bytes(host[0], level)
+        if ext == ".obj":
+            write_obj_texture_files(path, host[1], png)
+        else:
+            k = 3 + (nrm is not None)                                 # image, indices, positions, [normals,] uv, bounds
+            write_glb_buffers(path, host[1].view(np.uint32), host[2], None, host[3] if nrm is not None else None, host[k + 1], uv=host[k], png=png)
+        return 3 * m, m
     if n == 0 or m == 0:
         if ext == ".glb":
             raise ValueError("GLB export: an empty mesh has no valid glTF form (accessors need count >= 1)")

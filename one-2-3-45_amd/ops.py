@@ -1045,3 +1045,111 @@ def project_info(stats, iterations):
         raise RuntimeError(f"o2345 mesh_project: {int(head[0])} vertices have a non-finite coordinate")
     return {"evaluated": [int(c) for c in counts[:iterations + 1]], "converged": int(head[1]), "unconverged": int(head[2]), "stalled": int(head[3]),
             "clamped": int(head[4]), "max_before": float(head[5:6].view(np.float64)[0]), "max_after": float(head[6:7].view(np.float64)[0])}
+
+
+# ---------------------------------------------------------------------------------------------------------- texture atlas
+_TEXTURE_STATS_BYTES = 16           # include/o2345.h: uint64 [2]
+
+
+def _texture_mesh(verts_idx, tris, what):
+    if tris.dtype not in (torch.int32, torch.int64) or tris.dim() != 2 or tris.shape[1] != 3:
+        raise ValueError(f"{what}: expected triangles [M,3] int32 or int64, got {tuple(tris.shape)} {tris.dtype}")
+    if verts_idx.dtype != torch.float64 or verts_idx.dim() != 2 or verts_idx.shape[1] != 3:
+        raise ValueError(f"{what}: expected vertices [N,3] float64, got {tuple(verts_idx.shape)} {verts_idx.dtype}")
+    if verts_idx.shape[0] < 1:
+        raise ValueError(f"{what}: a mesh with triangles has vertices")
+
+
+def texture_check(stats):
+    """The stats block of o2345_mesh_texture_points (16 bytes, on the host): raises on a non-finite coordinate or a triangle index out of range."""
+    n_nonfinite, n_bad = (int(x) for x in np.asarray(stats).reshape(-1)[:_TEXTURE_STATS_BYTES].view(np.uint64))
+    if n_bad:
+        raise RuntimeError(f"o2345 mesh_texture_points: {n_bad} triangles index outside the vertex array")
+    if n_nonfinite:
+        raise RuntimeError(f"o2345 mesh_texture_points: {n_nonfinite} triangles have a non-finite vertex coordinate")
+
+
+@_on_device
+def mesh_texture_points(verts_idx, tris, texel, resolution, bound_min=(-1.0, -1.0, -1.0), bound_max=(1.0, 1.0, 1.0), validate=True):
+    """The surface point of every texel of the atlas (== mesh_io.texture_points, to the last bit; definitions in csrc/mesh_texture.hip).  verts_idx fp64
+    [N,3] index coordinates on a ``resolution``^3 grid, tris [M,3] int32 / int64, ``texel`` in [4, 64] -> (points fp64 [cells c^2, 3] index coordinates,
+    world fp32 [cells c^2, 3], stats uint8 [16]), cell-major; the inputs are not written.  ``validate`` copies the counters to the host (one
+    synchronisation) and raises on a non-finite coordinate or a triangle index out of range; a caller that queues more work passes False and hands the
+    counters to texture_check after its own copy."""
+    _texture_mesh(verts_idx, tris, "mesh_texture_points")
+    lay = mesh_io.texture_layout(tris.shape[0], texel)
+    if isinstance(resolution, bool) or int(resolution) != resolution or resolution < 2:
+        raise ValueError(f"mesh_texture_points: resolution must be an integer >= 2, got {resolution!r}")
+    (bmin, pmin), (bmax, pmax) = _host3(bound_min), _host3(bound_max)
+    if bmin.shape != (3,) or bmax.shape != (3,) or not (np.isfinite(bmin).all() and np.isfinite(bmax).all() and (bmax > bmin).all()):
+        raise ValueError(f"mesh_texture_points: bound_max must be above bound_min on every axis, both finite, got {bound_min!r} and {bound_max!r}")
+    L = _lib.lib()
+    dev, n = verts_idx.device, lay["texels"]
+    assert L.o2345_mesh_texture_texels(tris.shape[0], lay["texel"], None, None) == n
+    pts = torch.empty(n, 3, dtype=torch.float64, device=dev)
+    world = torch.empty(n, 3, dtype=torch.float32, device=dev)
+    stats = torch.empty(_TEXTURE_STATS_BYTES, dtype=torch.uint8, device=dev)
+    check(L.o2345_mesh_texture_points(_p(verts_idx, torch.float64), verts_idx.shape[0], _p(tris, tris.dtype), 8 if tris.dtype == torch.int64 else 4, tris.shape[0],
+                                       lay["texel"], int(resolution), pmin, pmax, _p(pts, torch.float64), _p(world), _p(stats, torch.uint8), _stream()),
+           "mesh_texture_points")
+    if validate:
+        texture_check(stats.cpu().numpy())
+    return pts, world, stats
+
+
+@_on_device
+def mesh_texture_pack(rgb, nt, texel):
+    """Cell-major texel colours fp32 [cells c^2, 3] -> the atlas image uint8 [H, W, 4] on the device (== mesh_io.pack_texture, exactly)."""
+    lay = mesh_io.texture_layout(nt, texel)
+    if rgb.dim() != 2 or tuple(rgb.shape) != (lay["texels"], 3):
+        raise ValueError(f"mesh_texture_pack: expected colours [{lay['texels']}, 3], got {tuple(rgb.shape)}")
+    image = torch.empty(lay["height"], lay["width"], 4, dtype=torch.uint8, device=rgb.device)
+    check(_lib.lib().o2345_mesh_texture_pack(_p(rgb), int(nt), lay["texel"], _p(image, torch.uint8), _stream()), "mesh_texture_pack")
+    return image
+
+
+@_on_device
+def mesh_texture_corners(verts_idx, tris, texel, grid_R, bound_min=(-1.0, -1.0, -1.0), bound_max=(1.0, 1.0, 1.0), scale_mat=None, trans_mat=None, grad=None):
+    """The unwelded vertices of the textured asset (== mesh_io.texture_corners, to the last bit): (positions float32 [3M,3] in the asset frame, uv float32
+    [3M,2], normals float32 [3M,3] or None, indices uint32-valued int32 storage [M,3] = 0, 1, 2, ..., bounds float32 [2,3]), all on the device.
+    ``grad`` fp32 [N,3]: the SDF gradient at the (welded) vertices."""
+    _texture_mesh(verts_idx, tris, "mesh_texture_corners")
+    lay = mesh_io.texture_layout(tris.shape[0], texel)
+    dev, m = verts_idx.device, tris.shape[0]
+    if grad is not None and tuple(grad.shape) != (verts_idx.shape[0], 3):
+        raise ValueError(f"mesh_texture_corners: expected gradients [{verts_idx.shape[0]}, 3], got {tuple(grad.shape)}")
+    host = lambda a: None if a is None else np.ascontiguousarray((a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)), np.float32)
+    bmin, bmax = host(bound_min).reshape(3), host(bound_max).reshape(3)
+    sm, tm = host(scale_mat), host(trans_mat)
+    sm = None if sm is None else sm.reshape(-1, 4, 4)[0].copy()
+    tm = None if tm is None else tm.reshape(-1, 4, 4)[0].copy()
+    cp = lambda a: None if a is None else a.ctypes.data_as(ctypes.c_void_p)
+    pos = torch.empty(3 * m, 3, dtype=torch.float32, device=dev)
+    uv = torch.empty(3 * m, 2, dtype=torch.float32, device=dev)
+    nrm = None if grad is None else torch.empty(3 * m, 3, dtype=torch.float32, device=dev)
+    idx = torch.empty(m, 3, dtype=torch.int32, device=dev)
+    bounds = torch.empty(2, 3, dtype=torch.float32, device=dev)
+    L = _lib.lib()
+    wsb = L.o2345_mesh_bounds_workspace_bytes(3 * m)
+    ws = _workspace(wsb, dev, "mesh_bounds")
+    check(L.o2345_mesh_texture_corners(_p(verts_idx, torch.float64), verts_idx.shape[0], _p(tris, tris.dtype), 8 if tris.dtype == torch.int64 else 4, m, lay["texel"],
+                                        int(grid_R), cp(bmin), cp(bmax), cp(sm), cp(tm), _p(grad), _p(pos), _p(uv), _p(nrm), _p(idx, torch.int32), _p(bounds),
+                                        _p(ws, torch.uint8), wsb, _stream()), "mesh_texture_corners")
+    return pos, uv, nrm, idx, bounds
+
+
+@_on_device
+def obj_texture_text(positions, uv, normals=None, K=None, bounds=None):
+    """The buffers of mesh_texture_corners -> the records of the textured Wavefront OBJ (uint8 tensor on the device; == mesh_io.obj_texture_text_numpy):
+    "v", "vt", ["vn",] "f a/a b/b c/c" (include/o2345.h).  ``K`` as for obj_text."""
+    n = positions.shape[0]
+    if K is None:
+        K = mesh_io.obj_coordinate_digits(bounds.cpu().numpy() if torch.is_tensor(bounds) else bounds) if n else 1
+    if not 1 <= int(K) <= 9:
+        raise ValueError(f"obj_texture_text: K = {K} integer digits (1 .. 9)")
+    if n % 3 or tuple(uv.shape) != (n, 2):
+        raise ValueError(f"obj_texture_text: expected 3 M unwelded vertices and uv [3 M, 2], got {n} and {tuple(uv.shape)}")
+    L = _lib.lib()
+    text = torch.empty(L.o2345_obj_texture_text_bytes(n, int(K), int(normals is not None)), dtype=torch.uint8, device=positions.device)
+    check(L.o2345_obj_texture_text(_p(positions), _p(uv), _p(normals), n, int(K), _p(text, torch.uint8), _stream()), "obj_texture_text")
+    return text

@@ -187,7 +187,7 @@ def render_scene_split(wt, imgs, affine_mats, origin, D, voxel_size, proj, cam_p
 
 
 def _mesh_fields(wt, vol, proj, cam_pos, resolution, min_component_faces=None, keep_largest=None, info=None, smooth_iterations=None, decimate_cell=None,
-                 project_iterations=None):
+                 project_iterations=None, texture=None):
     """The device work of extract_mesh, once: (verts fp64 in [-1, 1], verts_idx fp64 index coordinates, tris, rgb, u, grad).  ``grad`` is the SDF gradient
     at the vertices that the colour network takes as its normal input (None for an empty mesh): the asset export reuses it for the NORMAL attribute.
     ``min_component_faces`` / ``keep_largest`` (None: the config default, off unless set): the component filter (ops.mesh_filter_components) right after
@@ -202,7 +202,13 @@ def _mesh_fields(wt, vol, proj, cam_pos, resolution, min_component_faces=None, k
     ``project_iterations`` (None: the config default, 0 = off): Newton projection of the vertices onto the SDF's zero set (ops.mesh_project; tolerance,
     step and move limits from config, the move limit max(1, cell) unless configured) after the decimation and BEFORE gradient and colours, which are
     therefore taken at the projected vertices; triangles and ``u`` are untouched.  Smoothing still runs last and deliberately leaves the surface: its
-    result is not projected again.  ``info`` also receives "project" (the op's info, or None when it is off: nothing is launched then)."""
+    result is not projected again.  ``info`` also receives "project" (the op's info, or None when it is off: nothing is launched then).
+    ``texture`` (None = off: nothing is launched): a dict with "texel" = c in [4, 64] that receives the baked atlas -- "rgb", the colour network at the
+    surface point of every texel (ops.mesh_texture_points on the final unsmoothed mesh; with projection on, those points go through ops.mesh_project
+    with the same tolerance, step and move limits first, so that the texture is taken on the surface and not on the chord planes of a coarse mesh; then
+    the same gradient and colour calls as the vertices), "stats" (the point op's error counters, still on the device: nothing here synchronises for
+    them; mesh_io.export_asset raises on them after its copy), "layout" (mesh_io.texture_layout) and "project" (the info of the texel projection or
+    None).  Texels, like vertex colours, are taken before the smoothing."""
     min_faces, largest = config.mesh_min_component_faces(min_component_faces), config.mesh_keep_largest(keep_largest)
     smooth = config.mesh_smooth_iterations(smooth_iterations)
     cell = config.mesh_decimate_cell(decimate_cell)
@@ -233,10 +239,28 @@ def _mesh_fields(wt, vol, proj, cam_pos, resolution, min_component_faces=None, k
     x3 = wt.color_precision == "f16x3"
     rgb, _ = ops.color_points(wt.color_xblob if x3 else wt.color_mblob, vol["vol_cl"], vol["maskvol"], vol["cmaps"], proj, cam_pos, pts, normals=g,
                               want_nviews=False, mfma="x3" if x3 else True)
+    if texture is not None and tris.shape[0]:
+        tpts, tworld, tstats = ops.mesh_texture_points(verts_idx, tris, texture["texel"], resolution, validate=False)
+        tpro = None
+        if project:
+            tpts, tpro = ops.mesh_project(wt.sdf_blob, vol["vol_cl"], tpts, resolution, project, max_move=config.mesh_project_max_move(None, cell), precision=prec)
+            tworld = (tpts / (resolution - 1.0) * 2.0 - 1.0).to(torch.float32).contiguous()
+        tg = ops.sdf_mlp(wt.sdf_blob, vol["vol_cl"], tworld, variant=2, precision=prec)["grad"]
+        trgb, _ = ops.color_points(wt.color_xblob if x3 else wt.color_mblob, vol["vol_cl"], vol["maskvol"], vol["cmaps"], proj, cam_pos, tworld, normals=tg,
+                                   want_nviews=False, mfma="x3" if x3 else True)
+        texture.update(rgb=trgb, stats=tstats, project=tpro, layout=ops.mesh_io.texture_layout(tris.shape[0], texture["texel"]))
     if smooth:
         verts_idx = ops.mesh_smooth(verts_idx, tris, smooth)
         verts = (verts_idx / (resolution - 1.0) * 2.0 - 1.0)
     return verts, verts_idx, tris, rgb, u, g
+
+
+def _texture_block(texture):
+    """-> the "texture" entry of a result dict: {width, height, texel, texels} or None"""
+    if not texture or "layout" not in texture:
+        return None
+    L = texture["layout"]
+    return {"width": L["width"], "height": L["height"], "texel": L["texel"], "texels": L["texels"]}
 
 
 @torch.no_grad()
@@ -267,22 +291,30 @@ def export_mesh_ply(path, wt, vol, proj, cam_pos, resolution, scale_mat=None, tr
 
 @torch.no_grad()
 def export_mesh_asset(path, wt, vol, proj, cam_pos, resolution, scale_mat=None, trans_mat=None, normals=False, min_component_faces=None, keep_largest=None,
-                      smooth_iterations=None, decimate_cell=None, project_iterations=None):
+                      smooth_iterations=None, decimate_cell=None, project_iterations=None, texture_texel=None):
     """export_mesh_ply followed by convert_mesh_format (utils/utils.py:31-47) without the PLY in between: the coloured mesh as ``.glb`` or ``.obj`` in the
     asset frame ((x, y, z) -> (x, z, y), faces reversed), buffers / text packed on the device (csrc/mesh_export.hip).  ``normals=True`` adds unit vertex
     normals from the SDF gradient the vertex colouring already computed (at the unsmoothed vertices when ``smooth_iterations`` is on, at the projected ones
     when ``project_iterations`` is).  A ``.ply`` path
-    gives export_mesh_ply's file.  Returns (n_vertices, n_triangles)."""
+    gives export_mesh_ply's file.  Returns (n_vertices, n_triangles).
+    ``texture_texel`` (None: the config default, 0 = off) = c in [4, 64]: the textured asset instead -- the colour network baked into an atlas of one
+    c x c cell per pair of triangles (_mesh_fields, ``texture``), 3 M unwelded vertices with texture coordinates and no vertex colours; the PNG sits inside
+    the ``.glb``, or as ``.mtl`` + ``.png`` next to the ``.obj``.  A ``.ply`` path with a texture requested raises ValueError."""
     from . import mesh_io
+    texel = config.mesh_texture_texel(texture_texel)
+    if texel and mesh_io._asset_ext(path) == ".ply":
+        raise ValueError("texture: a .ply has no texture coordinates; the output is .glb or .obj")
+    tex = {"texel": texel} if texel else None
     _, verts_idx, tris, rgb, _, g = _mesh_fields(wt, vol, proj, cam_pos, resolution, min_component_faces, keep_largest, smooth_iterations=smooth_iterations,
-                                                 decimate_cell=decimate_cell, project_iterations=project_iterations)
+                                                 decimate_cell=decimate_cell, project_iterations=project_iterations, texture=tex)
     return mesh_io.export_asset(path, verts_idx, tris, resolution, scale_mat=scale_mat, trans_mat=trans_mat,
-                                vertex_colors=rgb if verts_idx.shape[0] else None, normals=g if normals else None)
+                                vertex_colors=rgb if verts_idx.shape[0] else None, normals=g if normals else None,
+                                texture=tex if tex and "rgb" in tex else None)
 
 
 @torch.no_grad()
 def reconstruct_folder(root_dir, name, wt, out_ply, D=96, resolution=256, render_val_image=False, output_format=None, min_component_faces=None,
-                       keep_largest=None, smooth_iterations=None, decimate_cell=None, project_iterations=None):
+                       keep_largest=None, smooth_iterations=None, decimate_cell=None, project_iterations=None, texture_texel=None):
     """run.py's reconstruction stage without the reference tree: Zero123-style folder (dataset.SceneFolder) -> coloured mesh (binary PLY in
     the original frame), optionally the val image of the target view.  ``output_format`` ".obj" / ".glb" (run.py --output_format) also writes
     ``mesh<ext>`` next to ``out_ply`` in the asset frame, from the same device buffers.  ``min_component_faces`` / ``keep_largest``: the component filter of
@@ -290,7 +322,9 @@ def reconstruct_folder(root_dir, name, wt, out_ply, D=96, resolution=256, render
     (None: the config default, 0 = off); ``project_iterations``: its projection onto the zero set (None: the config default, 0 = off).  Returns
     dict(vertices, triangles, kept_voxels, ply, components, components_kept, smooth_iterations, decimate_cell, decimate, project_iterations, project[, asset]
     [, color, depth]); the two component counts are None when the filter is off, ``decimate`` (the counts of ops.mesh_decimate) when decimation is, and
-    ``project`` (the info of ops.mesh_project) when projection is."""
+    ``project`` (the info of ops.mesh_project) when projection is.  ``texture_texel`` (None: the config default, 0 = off): the texture atlas of
+    export_mesh_asset for the ``output_format`` asset only -- the PLY stays vertex-coloured; the result's "texture" is {width, height, texel, texels},
+    or None when no textured asset was written."""
     import os
     from . import dataset, mesh_io
     if output_format not in (None, ".ply", ".obj", ".glb"):
@@ -304,16 +338,19 @@ def reconstruct_folder(root_dir, name, wt, out_ply, D=96, resolution=256, render
     smooth = config.mesh_smooth_iterations(smooth_iterations)
     cell = config.mesh_decimate_cell(decimate_cell)
     project = config.mesh_project_iterations(project_iterations)
+    texel = config.mesh_texture_texel(texture_texel)
+    tex = {"texel": texel} if texel and output_format in (".obj", ".glb") else None
     _, verts_idx, tris, rgb, _, _ = _mesh_fields(wt, vol, proj, cam_pos, resolution, min_component_faces, keep_largest, info=cc, smooth_iterations=smooth,
-                                                 decimate_cell=cell, project_iterations=project)
+                                                 decimate_cell=cell, project_iterations=project, texture=tex)
     rgb = rgb if verts_idx.shape[0] else None
     nv, nt = mesh_io.export_mesh(out_ply, verts_idx, tris, resolution, scale_mat=s["scale_mat"], trans_mat=s["trans_mat"], vertex_colors=rgb)
     out = {"vertices": nv, "triangles": nt, "kept_voxels": int(vol["n_voxels"]), "ply": str(out_ply), "components": cc["components"],
            "components_kept": cc["components_kept"], "smooth_iterations": smooth, "decimate_cell": cell, "decimate": cc["decimate"],
-           "project_iterations": project, "project": cc["project"]}
+           "project_iterations": project, "project": cc["project"], "texture": _texture_block(tex)}
     if output_format in (".obj", ".glb"):
         out["asset"] = os.path.join(os.path.dirname(str(out_ply)), "mesh" + output_format)
-        mesh_io.export_asset(out["asset"], verts_idx, tris, resolution, scale_mat=s["scale_mat"], trans_mat=s["trans_mat"], vertex_colors=rgb)
+        mesh_io.export_asset(out["asset"], verts_idx, tris, resolution, scale_mat=s["scale_mat"], trans_mat=s["trans_mat"], vertex_colors=rgb,
+                             texture=tex if tex and "rgb" in tex else None)
     if render_val_image:
         r = render(wt, vol, proj, cam_pos, T(s["rays"]["rays_o"]), T(s["rays"]["rays_v"]), float(s["query_near_far"][0]), float(s["query_near_far"][1]),
                    T(s["query_c2w"][:3, 3]))

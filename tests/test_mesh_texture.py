@@ -1,0 +1,360 @@
+"""Texture atlas on the CPU: the host twins of mesh_io (texture_layout / texture_points / texture_corners / pack_texture), which are the definition
+the device path (tests/test_gpu_mesh_texture.py) is compared against, the PNG writer and reader, and the textured GLB / OBJ files.
+
+Layout, restated: triangles 2k and 2k + 1 share square cell k of c x c texels, cells row-major in a grid G = ceil(sqrt(cells)) wide.  Local texel (i, j)
+has its centre at (i + 0.5, j + 0.5); triangle A owns i + j <= c - 1 and has its corners at (0.5, 0.5), (c - 1.5, 0.5), (0.5, c - 1.5); triangle B owns
+i + j >= c and has them at (c - 0.5, c - 0.5), (2.5, c - 0.5), (c - 0.5, 2.5).  Expected values come from this definition, never from the code under
+test."""
+import importlib
+import json
+import math
+import os
+import struct
+import zlib
+
+import numpy as np
+import pytest
+
+mio = importlib.import_module("one-2-3-45_amd.mesh_io")
+
+COUNTS = (1, 2, 3, 41)            # 41 triangles: 21 cells in a 5 x 5 grid, five rows of which the last holds one cell
+TEXELS = (4, 5, 8)
+
+
+def _strip(nt, seed, spread=3.0, lo=100.0, hi=400.0):
+    """nt small triangles (edges of a few grid spacings) around a random point with coordinates <= 512: gutter texels extrapolate by up to three
+    triangle sizes (c = 4, triangle B) and must stay inside the grid, where the clamp to [0, R - 1] does nothing"""
+    rng = np.random.default_rng(seed)
+    v = rng.uniform(lo, hi, 3) + rng.uniform(-spread, spread, (nt + 2, 3))
+    f = np.stack([np.arange(nt), np.arange(nt) + 1, np.arange(nt) + 2], 1)
+    f[1::2] = f[1::2, ::-1]
+    return v, f
+
+
+def _place(cells_data, L):
+    """[cells, c, c, C] cell-major values -> the image [H, W, C], unused cells zero: the definition of the raster order, written independently"""
+    c, G = L["texel"], L["grid"]
+    img = np.zeros((L["height"], L["width"], cells_data.shape[-1]), cells_data.dtype)
+    for k in range(L["cells"]):
+        x0, y0 = (k % G) * c, (k // G) * c
+        img[y0:y0 + c, x0:x0 + c] = cells_data[k]
+    return img
+
+
+@pytest.mark.parametrize("c", TEXELS)
+@pytest.mark.parametrize("nt", COUNTS)
+def test_layout_facts(nt, c):
+    L = mio.texture_layout(nt, c)
+    cells = -(-nt // 2)
+    G = math.ceil(math.sqrt(cells))
+    assert (G - 1) ** 2 < cells <= G * G
+    assert L == {"texel": c, "cells": cells, "grid": G, "rows": -(-cells // G), "width": G * c, "height": -(-cells // G) * c, "texels": cells * c * c}
+    if nt == 41:
+        assert (L["grid"], L["rows"], L["width"], L["height"]) == (5, 5, 5 * c, 5 * c)
+    # every texel of a used cell has exactly one owner: A (i + j <= c - 1) or B (i + j >= c)
+    owner, w, corners = mio.texture_cell(c)
+    assert owner.shape == (c, c) and w.shape == (c, c, 3) and corners.shape == (2, 3, 2)
+    for j in range(c):
+        for i in range(c):
+            assert (i + j <= c - 1) != (i + j >= c) and owner[j, i] == (i + j >= c)
+    assert np.allclose(w.sum(-1), 1.0, atol=1e-15)
+    # the weights reproduce the texel centre from the owner's corners
+    centre = np.stack(np.meshgrid(np.arange(c) + 0.5, np.arange(c) + 0.5, indexing="xy"), -1)         # [j, i] -> (i + 0.5, j + 0.5)
+    assert np.allclose(np.einsum("jik,jikd->jid", w, corners[owner]), centre, atol=1e-12)
+    # unused cells are transparent, used ones opaque
+    img = mio.pack_texture(np.full((L["texels"], 3), 0.5, np.float32), nt, c)
+    assert img.shape == (L["height"], L["width"], 4) and img.dtype == np.uint8
+    want = _place(np.broadcast_to(np.array([127, 127, 127, 255], np.uint8), (cells, c, c, 4)), L)
+    assert np.array_equal(img, want)
+    assert int((img[..., 3] == 0).sum()) == (L["rows"] * G - cells) * c * c
+
+
+def test_pack_texture_order_and_quantisation():
+    nt, c = 5, 4
+    L = mio.texture_layout(nt, c)
+    rng = np.random.default_rng(3)
+    rgb = rng.uniform(-0.5, 1.5, (L["texels"], 3)).astype(np.float32)
+    rgb[7] = [1.0, 0.0, -0.0]
+    rgb[8] = [0.999999, 1.0 / 255.0, 254.999 / 255.0]
+    img = mio.pack_texture(rgb, nt, c)
+    q = np.array([[int(np.float32(x) * np.float32(255.0)) % 256 for x in row] + [255] for row in rgb], np.uint8)      # C: (uint8_t)(int)(x * 255.f)
+    assert np.array_equal(img, _place(q.reshape(L["cells"], c, c, 4), L))
+    assert tuple(q[7]) == (255, 0, 0, 255)
+
+
+@pytest.mark.parametrize("c", TEXELS + (11,))
+@pytest.mark.parametrize("nt", COUNTS)
+def test_bilinear_sampling_reproduces_a_linear_colour_and_never_leaves_the_owner(nt, c):
+    """1e-9: the sample is about ten float64 operations on values of order 1e3 (coordinates <= 512, slopes of order 1), each with a relative rounding
+    error of 1.1e-16 -- of order 1e-12, with three decades of head-room."""
+    v, f = _strip(nt, 100 * nt + c)
+    R = 513
+    L = mio.texture_layout(nt, c)
+    pts, world = mio.texture_points(v, f, c, R)
+    assert pts.shape == (L["texels"], 3) and pts.dtype == np.float64 and world.dtype == np.float32 and world.shape == pts.shape
+    assert pts.min() > 0.0 and pts.max() < R - 1.0                       # nothing was clamped
+    assert np.array_equal(world, (pts / (R - 1.0) * 2.0 + -1.0).astype(np.float32))
+    rng = np.random.default_rng(c)
+    a, b = rng.normal(0, 1, (3, 3)), rng.normal(0, 1, 3)
+    img = _place((pts @ a.T + b).reshape(L["cells"], c, c, 3), L)
+    px = mio.texture_corner_pixels(nt, c)
+    # the corners are where the definition puts them
+    for t in range(nt):
+        k, x0, y0 = t // 2, (t // 2 % L["grid"]) * c, (t // 2 // L["grid"]) * c
+        local = [(0.5, 0.5), (c - 1.5, 0.5), (0.5, c - 1.5)] if t % 2 == 0 else [(c - 0.5, c - 0.5), (2.5, c - 0.5), (c - 0.5, 2.5)]
+        assert px[t].tolist() == [[x0 + u, y0 + w] for u, w in local]
+    bary = np.concatenate([np.eye(3), [[0.5, 0.5, 0], [0, 0.5, 0.5], [0.5, 0, 0.5]], rng.dirichlet([1, 1, 1], 24)])
+    P = v[f]
+    t = np.arange(nt)
+    x0, y0 = (t // 2 % L["grid"]) * c, (t // 2 // L["grid"]) * c
+    worst = 0.0
+    for w in bary:
+        q = np.einsum("k,tkd->td", w, px)
+        got, touched = mio.sample_texture(img, q / [L["width"], L["height"]])
+        want = np.einsum("k,tkd->td", w, P) @ a.T + b
+        worst = max(worst, float(np.abs(got - want).max()))
+        for xi, yi, wgt in touched:
+            live = wgt > 1e-12                                         # a weight that is rounding noise of an exact 0 reads nothing a viewer can see
+            i, j = xi - x0, yi - y0
+            inside = (i >= 0) & (i < c) & (j >= 0) & (j < c)
+            owned = np.where(t % 2 == 0, i + j <= c - 1, i + j >= c)
+            assert (inside & owned)[live].all(), (nt, c, w)
+    print(f"nt {nt} c {c}: worst |sample - linear| {worst:.3e}")
+    assert worst <= 1e-9
+
+
+def test_texel_points_definition_by_hand():
+    """a few texels of a 3-triangle mesh against the formula written out; the odd count repeats the last triangle in the B half of its cell"""
+    c, R = 5, 64
+    v = np.array([[10.0, 11.0, 12.0], [13.0, 11.5, 12.0], [10.5, 14.0, 12.5], [12.0, 14.0, 15.0], [14.0, 12.0, 13.0]])
+    f = np.array([[0, 1, 2], [2, 1, 3], [3, 1, 4]])
+    pts, world = mio.texture_points(v, f, c, R, ((-1.0, -2.0, -1.0), (1.0, 2.0, 3.0)))
+    ext, b0 = np.array([2.0, 4.0, 4.0]), np.array([-1.0, -2.0, -1.0])
+
+    def at(k, i, j):
+        if i + j <= c - 1:
+            t, w1, w2 = 2 * k, i / (c - 2), j / (c - 2)
+        else:
+            t, w1, w2 = min(2 * k + 1, 2), (c - 1 - i) / (c - 3), (c - 1 - j) / (c - 3)
+        w0 = (1.0 - w1) - w2
+        P = v[f[t]]
+        return (w0 * P[0] + w1 * P[1]) + w2 * P[2]
+    for k, i, j in ((0, 0, 0), (0, 3, 0), (0, 0, 3), (0, 4, 4), (0, 2, 4), (0, 4, 0), (1, 1, 1), (1, 4, 4), (1, 4, 2), (1, 2, 3)):
+        e = k * c * c + j * c + i
+        assert pts[e].tobytes() == at(k, i, j).tobytes(), (k, i, j)
+        assert world[e].tobytes() == (at(k, i, j) / (R - 1.0) * ext + b0).astype(np.float32).tobytes()
+    assert pts[0].tolist() == v[0].tolist() and pts[3].tolist() == v[1].tolist() and pts[3 * c].tolist() == v[2].tolist()          # A's corners are texel centres
+    assert pts[4 * c + 4].tolist() == v[2].tolist() and pts[4 * c + 2].tolist() == v[1].tolist() and pts[2 * c + 4].tolist() == v[3].tolist()
+    assert pts[c * c + 4 * c + 4].tolist() == v[3].tolist()                # cell 1, B half: triangle 2 again
+    # the clamp: a mesh at the grid's rim extrapolates past it and is held at [0, R - 1]
+    rim = v - v.min(0)
+    p2, _ = mio.texture_points(rim, f, c, R)
+    assert p2.min() == 0.0 and (p2 >= 0.0).all() and (p2 <= R - 1.0).all()
+    assert not np.shares_memory(p2, rim) and rim.min() == 0.0
+
+
+def test_png_round_trip():
+    rng = np.random.default_rng(0)
+    img = rng.integers(0, 256, (13, 21, 4)).astype(np.uint8)
+    img[4:9] = 7                                                         # something to compress
+    sizes = {}
+    for level in (0, 1):
+        raw = mio.png_bytes(img, level)
+        sizes[level] = len(raw)
+        assert np.array_equal(mio.png_image(raw), img)
+        # the container, parsed independently: signature, IHDR, one IDAT, IEND, each CRC by zlib.crc32
+        assert raw[:8] == b"\x89PNG\r\n\x1a\n"
+        off, kinds = 8, []
+        while off < len(raw):
+            n, = struct.unpack_from(">I", raw, off)
+            kind, data = raw[off + 4:off + 8], raw[off + 8:off + 8 + n]
+            assert struct.unpack_from(">I", raw, off + 8 + n)[0] == zlib.crc32(kind + data)
+            kinds.append(kind)
+            if kind == b"IHDR":
+                assert struct.unpack(">IIBBBBB", data) == (21, 13, 8, 6, 0, 0, 0)
+            if kind == b"IDAT":
+                rows = np.frombuffer(zlib.decompress(data), np.uint8).reshape(13, 1 + 4 * 21)
+                assert not rows[:, 0].any() and np.array_equal(rows[:, 1:].reshape(13, 21, 4), img)
+            off += 12 + n
+        assert kinds == [b"IHDR", b"IDAT", b"IEND"] and off == len(raw)
+    assert sizes[0] > 13 * (1 + 4 * 21) and sizes[1] < sizes[0]          # level 0 is stored
+    bad = bytearray(mio.png_bytes(img, 1))
+    bad[40] ^= 1
+    with pytest.raises(ValueError, match="CRC"):
+        mio.png_image(bytes(bad))
+    for wrong in (img[..., :3], img.reshape(-1, 4)):
+        with pytest.raises(ValueError):
+            mio.png_bytes(wrong)
+    with pytest.raises(ValueError):
+        mio.png_bytes(img, 10)
+
+
+def _textured(nt, c, seed, with_normals=True, with_mats=True):
+    v, f = _strip(nt, seed, lo=10.0, hi=50.0)
+    rng = np.random.default_rng(seed)
+    R = 64
+    L = mio.texture_layout(nt, c)
+    scale = trans = None
+    if with_mats:
+        scale = np.eye(4, dtype=np.float32); scale[:3, :3] *= 0.9; scale[:3, 3] = [0.01, 0.02, -0.03]
+        trans = np.eye(4, dtype=np.float32); trans[:3, :3] = np.array([[0.0, -1.1, 0.0], [1.0, 0.0, 0.1], [0.0, 0.2, 1.0]], np.float32); trans[:3, 3] = [0.5, -0.25, 0.125]
+    g = rng.normal(0, 1, (v.shape[0], 3)).astype(np.float32) if with_normals else None
+    image = mio.pack_texture(rng.uniform(0, 1, (L["texels"], 3)).astype(np.float32), nt, c)
+    return dict(v=v, f=f, R=R, L=L, scale=scale, trans=trans, g=g, image=image, corners=mio.texture_corners(v, f, c, R, scale_mat=scale, trans_mat=trans, grad=g))
+
+
+@pytest.mark.parametrize("with_normals", [False, True])
+def test_textured_glb_round_trip(tmp_path, with_normals):
+    nt, c = 7, 5
+    S = _textured(nt, c, 11, with_normals)
+    pos, uv, nrm, bounds = S["corners"]
+    assert pos.shape == (3 * nt, 3) and uv.shape == (3 * nt, 2) and pos.dtype == uv.dtype == np.float32 and (nrm is not None) == with_normals
+    # the welded export of the same mesh: its positions (and normals), gathered by corner in the reversed winding, are the textured file's, bytes
+    welded = mio.frame_positions(S["v"], S["R"], scale_mat=S["scale"], trans_mat=S["trans"])[:, [0, 2, 1]]
+    wn = mio.frame_normals(S["g"], S["trans"]) if with_normals else None
+    wpath, tpath = str(tmp_path / "w.glb"), str(tmp_path / "t.glb")
+    mio.write_glb(wpath, welded, S["f"][:, ::-1], None, wn)
+    wp, wf, _, wnr = mio.read_glb(wpath)
+    mio.write_textured(tpath, pos, uv, nrm, S["image"])
+    p, f, col, nr = mio.read_glb(tpath)
+    assert col is None and np.array_equal(f, np.arange(3 * nt).reshape(-1, 3))
+    assert p.tobytes() == wp[wf.reshape(-1)].tobytes() == pos.tobytes()
+    if with_normals:
+        assert nr.tobytes() == wnr[wf.reshape(-1)].tobytes() and np.allclose(np.linalg.norm(nr, axis=1), 1.0, atol=1e-6)
+    tuv, timg, sampler = mio.read_glb_texture(tpath)
+    assert tuv.tobytes() == uv.tobytes() and np.array_equal(timg, S["image"])
+    assert sampler == {"magFilter": 9729, "minFilter": 9729, "wrapS": 33071, "wrapT": 33071}                 # LINEAR / LINEAR, CLAMP_TO_EDGE
+    assert mio.read_glb_texture(wpath) is None
+    # uv against the definition: ((cell_x c + u_local) / W, (cell_y c + v_local) / H) in float64, rounded once, corners reversed
+    px = mio.texture_corner_pixels(nt, c)[:, ::-1].reshape(-1, 2)
+    assert uv.tobytes() == (px / [S["L"]["width"], S["L"]["height"]]).astype(np.float32).tobytes()
+    # the JSON, parsed independently
+    raw = open(tpath, "rb").read()
+    jlen, = struct.unpack_from("<I", raw, 12)
+    doc = json.loads(raw[20:20 + jlen])
+    prim = doc["meshes"][0]["primitives"][0]
+    assert list(prim["attributes"]) == ["POSITION"] + (["NORMAL"] if with_normals else []) + ["TEXCOORD_0"] and prim["material"] == 0
+    assert doc["materials"] == [{"pbrMetallicRoughness": {"baseColorTexture": {"index": 0}, "metallicFactor": 0.0, "roughnessFactor": 1.0}}]
+    assert doc["textures"] == [{"sampler": 0, "source": 0}] and doc["images"] == [{"bufferView": len(doc["bufferViews"]) - 1, "mimeType": "image/png"}]
+    view = doc["bufferViews"][-1]
+    assert "target" not in view and view["byteOffset"] % 4 == 0 and doc["buffers"][0]["byteLength"] == view["byteOffset"] + (view["byteLength"] + 3) // 4 * 4
+    assert raw[28 + jlen + view["byteOffset"]:][:view["byteLength"]] == mio.png_bytes(S["image"], 1)
+    acc = doc["accessors"][prim["attributes"]["TEXCOORD_0"]]
+    assert (acc["type"], acc["componentType"], acc["count"]) == ("VEC2", 5126, 3 * nt)
+    assert list(doc)[-4:] == ["materials", "textures", "images", "samplers"]
+    with pytest.raises(ValueError):
+        mio.write_glb_buffers(tpath, f.astype(np.uint32), p, np.zeros((3 * nt, 4), np.uint8), None, bounds, uv=uv, png=b"x")
+
+
+@pytest.mark.parametrize("with_normals", [False, True])
+def test_textured_obj_triple_parses(tmp_path, with_normals):
+    nt, c = 7, 4
+    S = _textured(nt, c, 12, with_normals)
+    pos, uv, nrm, _ = S["corners"]
+    path = str(tmp_path / "mesh.obj")
+    mio.write_textured(path, pos, uv, nrm, S["image"], png_level=0)
+    assert sorted(os.listdir(tmp_path)) == ["mesh.mtl", "mesh.obj", "mesh.png"]
+    lines = open(path).read().split("\n")
+    assert lines[:2] == ["mtllib mesh.mtl", "usemtl material_0"]
+    mtl = open(tmp_path / "mesh.mtl").read().split("\n")
+    assert mtl[0] == "newmtl material_0" and "map_Kd mesh.png" in mtl
+    assert np.array_equal(mio.read_png(str(tmp_path / "mesh.png")), S["image"])
+    p, t, n, f, img = mio.read_obj_texture(path)
+    assert np.array_equal(img, S["image"]) and np.array_equal(f, np.arange(3 * nt).reshape(-1, 3))
+    assert np.abs(p - pos).max() <= 0.5e-8 and np.abs(t - uv).max() <= 0.5e-8 + 6e-8           # the flip 1 - v is rounded to float32 once more
+    assert (n is None) == (not with_normals) and (n is None or np.abs(n - nrm).max() <= 0.5e-8)
+    # every record of a kind has one length, and the closed form knows the total
+    K = mio.obj_coordinate_digits(pos)
+    text = mio.obj_texture_text_numpy(pos, uv, nrm, K)
+    assert len(text) == mio.obj_texture_text_bytes(3 * nt, K, with_normals)
+    assert open(path, "rb").read() == mio.obj_texture_header(path) + text
+    for kind, width in (("vt ", 25), ("f ", None)):
+        lens = {len(l) + 1 for l in lines if l.startswith(kind)}
+        assert len(lens) == 1 and (width is None or lens == {width})
+    vt0 = [l for l in lines if l.startswith("vt ")][0]
+    assert vt0 == "vt %10.8f %10.8f" % (float(uv[0, 0]), float(np.float32(1.0 - float(uv[0, 1]))))
+    flast = [l for l in lines if l.startswith("f ")][-1].split()
+    assert flast[1:] == ["/".join([str(a)] * (3 if with_normals else 2)) for a in (3 * nt - 2, 3 * nt - 1, 3 * nt)]
+
+
+# the JSON chunk of two untextured files as the commit before this feature wrote them (its glb_json, called with the six arguments it had)
+_OLD_JSON = (
+    ((5, 3, True, False, [-1.0, 0.0, 0.25], [1.5, 2.0, 3.0]),
+     b'{"asset":{"version":"2.0","generator":"o2345-hip"},"scene":0,"scenes":[{"nodes":[0]}],"nodes":[{"mesh":0}],"meshes":[{"primitives":[{"attributes":'
+     b'{"POSITION":1,"COLOR_0":2},"indices":0,"mode":4}]}],"accessors":[{"bufferView":0,"byteOffset":0,"componentType":5125,"count":9,"type":"SCALAR"},'
+     b'{"bufferView":1,"byteOffset":0,"componentType":5126,"count":5,"type":"VEC3","min":[-1.0,0.0,0.25],"max":[1.5,2.0,3.0]},{"bufferView":2,'
+     b'"byteOffset":0,"componentType":5121,"normalized":true,"count":5,"type":"VEC4"}],"bufferViews":[{"buffer":0,"byteOffset":0,"byteLength":36,'
+     b'"target":34963},{"buffer":0,"byteOffset":36,"byteLength":60,"target":34962},{"buffer":0,"byteOffset":96,"byteLength":20,"target":34962}],'
+     b'"buffers":[{"byteLength":116}]} '),
+    ((7, 2, False, True, [0.0, -0.0, 1e-3], [1.0, 2.0, 3.0]),
+     b'{"asset":{"version":"2.0","generator":"o2345-hip"},"scene":0,"scenes":[{"nodes":[0]}],"nodes":[{"mesh":0}],"meshes":[{"primitives":[{"attributes":'
+     b'{"POSITION":1,"NORMAL":2},"indices":0,"mode":4}]}],"accessors":[{"bufferView":0,"byteOffset":0,"componentType":5125,"count":6,"type":"SCALAR"},'
+     b'{"bufferView":1,"byteOffset":0,"componentType":5126,"count":7,"type":"VEC3","min":[0.0,0.0,0.001],"max":[1.0,2.0,3.0]},{"bufferView":2,'
+     b'"byteOffset":0,"componentType":5126,"count":7,"type":"VEC3"}],"bufferViews":[{"buffer":0,"byteOffset":0,"byteLength":24,"target":34963},'
+     b'{"buffer":0,"byteOffset":24,"byteLength":84,"target":34962},{"buffer":0,"byteOffset":108,"byteLength":84,"target":34962}],'
+     b'"buffers":[{"byteLength":192}]}   '),
+)
+
+
+def test_untextured_glb_json_keeps_its_bytes(tmp_path):
+    for args, want in _OLD_JSON:
+        assert mio.glb_json(*args) == want
+    # and read_glb still returns its four values for such a file
+    v = np.random.default_rng(0).normal(0, 1, (5, 3)).astype(np.float32)
+    f = np.array([[0, 1, 2], [2, 1, 3], [3, 1, 4]])
+    mio.write_glb(str(tmp_path / "a.glb"), v, f, np.full((5, 3), 9, np.uint8))
+    out = mio.read_glb(str(tmp_path / "a.glb"))
+    assert len(out) == 4 and out[0].tobytes() == v.tobytes() and np.array_equal(out[1], f) and out[2].shape == (5, 4) and out[3] is None
+
+
+def test_argument_errors(tmp_path):
+    v, f = _strip(4, 0)
+    for texel in (3, 65, -4, 4.0, True, "4"):
+        with pytest.raises(ValueError):
+            mio.texture_layout(4, texel)
+        with pytest.raises(ValueError):
+            mio.texture_points(v, f, texel, 513)
+    for texel in (0, None):                                             # off is not a layout
+        with pytest.raises(ValueError):
+            mio.texture_layout(4, texel)
+    with pytest.raises(ValueError):
+        mio.texture_layout(0, 4)
+    # the caps: a side over 16384 (64-texel cells: 257 x 257 cells is one column too many), and the largest legal one
+    assert mio.texture_layout(2 * 256 * 256, 64)["width"] == 16384
+    with pytest.raises(ValueError, match="16384"):
+        mio.texture_layout(2 * 256 * 256 + 1, 64)
+    with pytest.raises(ValueError, match="16384"):
+        mio.texture_layout(2 * 4096 * 4096 + 1, 4)
+    # a .ply path has no texture
+    S = _textured(3, 4, 5, False, False)
+    pos, uv, nrm, _ = S["corners"]
+    with pytest.raises(ValueError, match="ply"):
+        mio.write_textured(str(tmp_path / "a.ply"), pos, uv, nrm, S["image"])
+    with pytest.raises(ValueError, match="ply"):
+        mio.export_asset(str(tmp_path / "a.ply"), None, None, 64, texture={"texel": 4})
+    assert not os.listdir(tmp_path)
+    # bad meshes
+    bad = v.copy(); bad[2, 1] = np.nan
+    with pytest.raises(ValueError, match="non-finite"):
+        mio.texture_points(bad, f, 4, 513)
+    with pytest.raises(ValueError, match="index"):
+        mio.texture_points(v, f + 3, 4, 513)
+    with pytest.raises(ValueError):
+        mio.texture_points(v, f, 4, 1)
+    with pytest.raises(ValueError):
+        mio.texture_points(v, f, 4, 513, ((1.0, -1.0, -1.0), (1.0, 1.0, 1.0)))
+    with pytest.raises(ValueError):
+        mio.pack_texture(np.zeros((5, 3), np.float32), 4, 4)
+
+
+def test_config_knobs():
+    config = importlib.import_module("one-2-3-45_amd.config")
+    assert config.MESH_TEXTURE_TEXEL == 0 and config.MESH_TEXTURE_PNG_LEVEL == 1          # the environment of the test run leaves them unset
+    assert config.mesh_texture_texel(None) == 0 and config.mesh_texture_texel(0) == 0 and config.mesh_texture_texel(4) == 4 and config.mesh_texture_texel(64) == 64
+    for bad in (3, 65, -1, 4.5, True):
+        with pytest.raises(ValueError):
+            config.mesh_texture_texel(bad)
+    assert config.mesh_texture_png_level(None) == 1 and config.mesh_texture_png_level(0) == 0 and config.mesh_texture_png_level(9) == 9
+    for bad in (10, -1, 1.5):
+        with pytest.raises(ValueError):
+            config.mesh_texture_png_level(bad)

@@ -18,6 +18,10 @@ fed the same arrays.  Two meshes: BASELINE config 2 (8 views, 128^3 volume, 256^
              limit 2): the op alone (HIP events around the queued rounds, the small D2H copy of the counters and its synchronisation), the active
              vertices per round, max |sdf| before -> after, and whole-export variants with and without it, with and without decimation, inside the
              same alternating loop as the others
+  texture    the texture atlas (csrc/mesh_texture.hip) of the cell-2 decimation at texel 4 and 8 and of the config's full mesh at texel 4: the texel
+             count and image size, the three kernels alone (HIP events), the gradient + colour calls over the texel points, the D2H copy of the
+             textured GLB's buffers, mesh_io.png_bytes at zlib levels 0 and 1 (host clock), and whole-export variants textured against
+             vertex-coloured inside the same alternating loop as the others
 Medians over --reps calls after --warmup calls; the ratio against the PLY of the SAME run is what to read.  Prints one JSON line.
 
     python tools/time_mesh_export.py [--reps 9] [--warmup 3] [--skip-512]
@@ -176,6 +180,32 @@ def one_mesh(dev, wt, tmp, D, R, ray_scale, a, numpy_writer):
     res["project"] = {"iterations": PIT}
     for key, v, mm in (("all", verts_idx, 1.0), ("decimated", d_verts, max(1.0, CELL))):
         res["project"][key] = dict(proj_op(v, mm)[1], vertices=int(v.shape[0]), max_move=mm, mesh_project_ms=med_events(lambda: proj_op(v, mm), a.reps, a.warmup))
+    # the texture atlas: kernels alone, the network calls over the texels, the copy and the PNG
+    def grad_color_pts(pts):
+        gg = ops.sdf_mlp(wt.sdf_blob, vol["vol_cl"], pts, variant=2, precision=wt.sdf_precision)["grad"]
+        x3 = wt.color_precision == "f16x3"
+        return ops.color_points(wt.color_xblob if x3 else wt.color_mblob, vol["vol_cl"], vol["maskvol"], vol["cmaps"], inp["proj"], inp["cam_pos"], pts, normals=gg,
+                                want_nviews=False, mfma="x3" if x3 else True)[0]
+    res["texture"] = {}
+    for key, tv, tt, c in (("decimated_texel4", d_verts, d_tris, 4), ("decimated_texel8", d_verts, d_tris, 8), ("all_texel4", verts_idx, tris, 4)):
+        lay = mio.texture_layout(int(tt.shape[0]), c)
+        _, tworld, _ = ops.mesh_texture_points(tv, tt, c, R)
+        trgb = grad_color_pts(tworld)
+        image = ops.mesh_texture_pack(trgb, int(tt.shape[0]), c)
+        bufs = [image] + [t for t in ops.mesh_texture_corners(tv, tt, c, R) if t is not None]
+        h_image = image.cpu().numpy()
+        png = {}
+        for level in (0, 1):
+            r = med(lambda: mio.png_bytes(h_image, level), max(3, a.reps // 3), 1)
+            png[f"level{level}"] = dict(r, bytes=len(mio.png_bytes(h_image, level)))
+        res["texture"][key] = {
+            "triangles": int(tt.shape[0]), "texel": c, "texels": lay["texels"], "width": lay["width"], "height": lay["height"],
+            "kernel_ms": {"tex_points": med_events(lambda: ops.mesh_texture_points(tv, tt, c, R, validate=False), a.reps, a.warmup),
+                          "tex_pack": med_events(lambda: ops.mesh_texture_pack(trgb, int(tt.shape[0]), c), a.reps, a.warmup),
+                          "tex_corners": med_events(lambda: ops.mesh_texture_corners(tv, tt, c, R), a.reps, a.warmup),
+                          "grad_color_texels": med_events(lambda: grad_color_pts(tworld), a.reps, a.warmup)},
+            "d2h_ms": med(lambda: ops.to_host_numpy(*bufs), a.reps, a.warmup), "png_ms": png}
+        del trgb, image, bufs, tworld
     A = (wt, vol, inp["proj"], inp["cam_pos"], R)
     whole = {
         "ply": lambda: pipeline.export_mesh_ply(P(".ply"), *A),
@@ -194,6 +224,11 @@ def one_mesh(dev, wt, tmp, D, R, ray_scale, a, numpy_writer):
         "glb_project4": lambda: pipeline.export_mesh_asset(P("_p.glb"), *A, project_iterations=PIT),
         "ply_decimate2_project4": lambda: pipeline.export_mesh_ply(P("_dp.ply"), *A, decimate_cell=CELL, project_iterations=PIT),
         "glb_decimate2_project4": lambda: pipeline.export_mesh_asset(P("_dp.glb"), *A, decimate_cell=CELL, project_iterations=PIT),
+        "glb_decimate2_texture4": lambda: pipeline.export_mesh_asset(P("_dt4.glb"), *A, decimate_cell=CELL, texture_texel=4),
+        "glb_decimate2_texture8": lambda: pipeline.export_mesh_asset(P("_dt8.glb"), *A, decimate_cell=CELL, texture_texel=8),
+        "obj_decimate2_texture4": lambda: pipeline.export_mesh_asset(P("_dt4.obj"), *A, decimate_cell=CELL, texture_texel=4),
+        "glb_decimate2_project4_texture4": lambda: pipeline.export_mesh_asset(P("_dpt4.glb"), *A, decimate_cell=CELL, project_iterations=PIT, texture_texel=4),
+        "glb_texture4": lambda: pipeline.export_mesh_asset(P("_t4.glb"), *A, texture_texel=4),
     }
     # alternated like the stage variants; the spread (min .. max) of each is what a difference between two of them has to exceed
     for fn in whole.values():
