@@ -1,5 +1,5 @@
-// Small non-matrix kernels and block-level steps shared by several translation units (costvol.hip, sparse.hip, mcubes.hip, mesh_components.hip,
-// mesh_smooth.hip, mesh_decimate.hip, convnet.hip).
+// Small non-matrix kernels and block-level steps shared by several translation units (costvol.hip, sparse.hip, convnet.hip, and through
+// mesh_common.h, which adds what only the mesh units share, mcubes.hip, mesh_components.hip, mesh_smooth.hip, mesh_decimate.hip).
 // The kernels live in an anonymous namespace: every unit that launches one instantiates its own copy in its own code object, so o2345_preload
 // and the runtime's per-unit loading see them as before.
 #pragma once
@@ -110,7 +110,7 @@ __global__ __launch_bounds__(1024) void k_scan_small(int* __restrict__ a, int n,
 }
 
 // exclusive scan of a long int array in three launches: k_tile_sum (one block per tile of 256 * ITEMS entries -> block_total), k_scan_small over the block
-// totals, k_tile_scan (block_base = the scanned block totals) -> out[i], and out2[i] when that is not null.  mesh_smooth.hip, mesh_decimate.hip
+// totals, k_tile_scan (block_base = the scanned block totals) -> out[i], and out2[i] when that is not null.  Launched by exclusive_scan (mesh_common.h)
 template <int ITEMS>
 __global__ __launch_bounds__(256) void k_tile_sum(const int* __restrict__ a, long long n, int* __restrict__ block_total) {
     __shared__ int lds[5];

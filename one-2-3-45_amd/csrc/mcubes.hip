@@ -6,8 +6,7 @@
 // (= PyMCubes' creation order for surfaces that do not touch the volume boundary); triangles are emitted cell by
 // cell in traversal order, table order inside a cell.  Deterministic: counts -> exclusive scans -> emit, no atomics.
 // Everything stays on the device; u (67 MB at 256^3) is read three times, HBM-bound.
-#include "common.h"
-#include "block_kernels.h"
+#include "mesh_common.h"
 #include <math.h>
 #include "mc_tables.h"
 
@@ -169,6 +168,28 @@ __global__ __launch_bounds__(256) void k_mc_tris(const float* __restrict__ u, Mc
     }
 }
 
+// device scalars of one call
+struct McTotals { long long nv, nt; };
+
+struct McCarve { uint8_t* vcnt; uint16_t* tcase; int *vbase, *tbase, *vblock, *tblock; McTotals* tot; };
+
+// the one walk through the workspace: carves it, or sizes it when ws is null; returns its size
+static size_t mc_carve(void* ws, size_t n, McCarve& c) {
+    const size_t nb = (n + MC_TILE - 1) / MC_TILE;
+    Carver w(ws);
+    c.vcnt = w.take<uint8_t>(n);
+    c.tcase = w.take<uint16_t>(n);
+    c.vbase = w.take_bytes<int>(n * sizeof(int));              // unpadded, like the two block arrays: ints need 4 bytes, the totals behind them 8
+    c.tbase = w.take_bytes<int>(n * sizeof(int));
+    c.tot = w.take_bytes<McTotals>(32);
+    c.vblock = w.take_bytes<int>((nb + 4) * sizeof(int));
+    c.tblock = w.take_bytes<int>((nb + 4) * sizeof(int));
+    w.skip(32);                                                // never used: the size has always included it, and callers may have recorded that size
+    return w.bytes();
+}
+
+static_assert(sizeof(McTotals) <= 32, "McTotals must fit its region");
+
 }  // namespace o2345
 
 using namespace o2345;
@@ -176,21 +197,8 @@ using namespace o2345;
 extern "C" {
 
 size_t o2345_mc_workspace_bytes(int n0, int n1, int n2) {
-    const size_t n = (size_t)n0 * n1 * n2;
-    const size_t nb = (n + MC_TILE - 1) / MC_TILE;
-    return ((n + 15) / 16 * 16) + ((2 * n + 15) / 16 * 16) + 2 * n * sizeof(int) + (2 * nb + 8) * sizeof(int) + 64;
-}
-
-static void mc_carve(void* ws, size_t n, uint8_t*& vcnt, uint16_t*& tcase, int*& vbase, int*& tbase, int*& vblock, int*& tblock, long long*& totals) {
-    char* p = (char*)ws;
-    vcnt = (uint8_t*)p; p += (n + 15) / 16 * 16;
-    tcase = (uint16_t*)p; p += (2 * n + 15) / 16 * 16;
-    vbase = (int*)p; p += n * sizeof(int);
-    tbase = (int*)p; p += n * sizeof(int);
-    const size_t nb = (n + MC_TILE - 1) / MC_TILE;
-    totals = (long long*)p; p += 32;
-    vblock = (int*)p; p += (nb + 4) * sizeof(int);
-    tblock = (int*)p;
+    McCarve c;
+    return mc_carve(nullptr, (size_t)n0 * n1 * n2, c);
 }
 
 // Pass 1 of the two-call protocol: classifies, scans, and returns the vertex / triangle counts on the HOST
@@ -202,22 +210,20 @@ int o2345_marching_cubes_count(const float* u, int n0, int n1, int n2, double is
     O2345_REQUIRE(workspace_bytes >= o2345_mc_workspace_bytes(n0, n1, n2), "marching_cubes_count: workspace too small");
     const size_t n = (size_t)n0 * n1 * n2;
     O2345_REQUIRE(n < (1ull << 31), "marching_cubes_count: grid too large");
-    uint8_t* vcnt; uint16_t* tcase; int *vbase, *tbase, *vblock, *tblock; long long* totals;
-    mc_carve(workspace, n, vcnt, tcase, vbase, tbase, vblock, tblock, totals);
+    McCarve c;
+    (void)mc_carve(workspace, n, c);
     const McGrid g = mc_grid(n0, n1, n2, iso);
     const unsigned nb = (unsigned)((n + MC_TILE - 1) / MC_TILE);
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_mc_count, dim3(nb), dim3(256), 0, s, u, g, vcnt, tcase, vblock, tblock);
-    hipLaunchKernelGGL(k_scan_small<long long>, dim3(1), dim3(1024), 0, s, vblock, (int)nb, totals);
-    hipLaunchKernelGGL(k_scan_small<long long>, dim3(1), dim3(1024), 0, s, tblock, (int)nb, totals + 1);
-    hipLaunchKernelGGL(k_mc_offsets, dim3(nb), dim3(256), 0, s, g, vcnt, tcase, vblock, tblock, vbase, tbase);
+    hipLaunchKernelGGL(k_mc_count, dim3(nb), dim3(256), 0, s, u, g, c.vcnt, c.tcase, c.vblock, c.tblock);
+    hipLaunchKernelGGL(k_scan_small<long long>, dim3(1), dim3(1024), 0, s, c.vblock, (int)nb, &c.tot->nv);
+    hipLaunchKernelGGL(k_scan_small<long long>, dim3(1), dim3(1024), 0, s, c.tblock, (int)nb, &c.tot->nt);
+    hipLaunchKernelGGL(k_mc_offsets, dim3(nb), dim3(256), 0, s, g, c.vcnt, c.tcase, c.vblock, c.tblock, c.vbase, c.tbase);
     int rc = check_launch("marching_cubes_count");
     if (rc) return rc;
-    long long h[2];
-    hipError_t e = hipMemcpyAsync(h, totals, sizeof h, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    O2345_REQUIRE(e == hipSuccess, "marching_cubes_count: %s", hipGetErrorString(e));
-    *nv_host = h[0]; *nt_host = h[1];
+    McTotals h;
+    if ((rc = read_totals(h, c.tot, s, "marching_cubes_count"))) return rc;
+    *nv_host = h.nv; *nt_host = h.nt;
     return 0;
 }
 
@@ -227,15 +233,12 @@ int o2345_marching_cubes_emit(const float* u, int n0, int n1, int n2, double iso
     O2345_REQUIRE(u && workspace, "marching_cubes_emit: null pointer");
     O2345_REQUIRE(index_bytes == 4 || index_bytes == 8, "marching_cubes_emit: index_bytes must be 4 or 8");
     const size_t n = (size_t)n0 * n1 * n2;
-    uint8_t* vcnt; uint16_t* tcase; int *vbase, *tbase, *vblock, *tblock; long long* totals;
-    mc_carve(workspace, n, vcnt, tcase, vbase, tbase, vblock, tblock, totals);
+    McCarve c;
+    (void)mc_carve(workspace, n, c);
     const McGrid g = mc_grid(n0, n1, n2, iso);
     hipStream_t s = (hipStream_t)stream;
-    if (verts) hipLaunchKernelGGL(k_mc_verts, dim3(cdiv(n, 256)), dim3(256), 0, s, u, g, vcnt, vbase, verts);
-    if (tris) {
-        if (index_bytes == 4) hipLaunchKernelGGL(k_mc_tris<int>, dim3(cdiv(n, 256)), dim3(256), 0, s, u, g, tcase, vbase, tbase, (int*)tris);
-        else hipLaunchKernelGGL(k_mc_tris<long long>, dim3(cdiv(n, 256)), dim3(256), 0, s, u, g, tcase, vbase, tbase, (long long*)tris);
-    }
+    if (verts) hipLaunchKernelGGL(k_mc_verts, dim3(cdiv(n, 256)), dim3(256), 0, s, u, g, c.vcnt, c.vbase, verts);
+    if (tris) with_index_type(index_bytes, tris, [&](auto* t) { hipLaunchKernelGGL(k_mc_tris<index_type<decltype(t)>>, dim3(cdiv(n, 256)), dim3(256), 0, s, u, g, c.tcase, c.vbase, c.tbase, t); });
     return check_launch("marching_cubes_emit");
 }
 

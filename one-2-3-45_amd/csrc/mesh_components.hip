@@ -18,13 +18,9 @@
 // means another thread's CAS succeeded, and the union retries from the new roots: no thread waits for another, and every walk strictly descends, so
 // everything terminates.  Path halving stores only values read from an ancestor.  A separate launch then makes parent[v] the root = the label.
 // Face counts are integer atomicAdd, the largest component one 64-bit integer atomicMax of (faces << 32 | ~label): order-independent, no float atomics.
-#include "common.h"
-#include "block_kernels.h"
+#include "mesh_common.h"
 
 namespace o2345 {
-
-constexpr int CC_ITEMS = 8;                       // items per thread of the flag / scan kernels
-constexpr int CC_TILE = IDX_BLOCK * CC_ITEMS;     // per block
 
 // device scalars of one call (workspace head)
 struct CcTotals {
@@ -60,13 +56,6 @@ __device__ __forceinline__ void cc_union(int* parent, int a, int b) {
     }
 }
 
-template <typename IDX>
-__device__ __forceinline__ bool cc_triangle(const IDX* __restrict__ tris, long long t, int nv, int& a, int& b, int& c) {
-    const long long ia = (long long)tris[3 * t], ib = (long long)tris[3 * t + 1], ic = (long long)tris[3 * t + 2];
-    a = (int)ia; b = (int)ib; c = (int)ic;
-    return ia >= 0 && ia < nv && ib >= 0 && ib < nv && ic >= 0 && ic < nv;
-}
-
 __global__ __launch_bounds__(256) void k_cc_init(int* __restrict__ parent, int* __restrict__ faces, int nv, CcTotals* __restrict__ tot) {
     const long long v = (long long)blockIdx.x * 256 + threadIdx.x;
     if (v == 0) *tot = CcTotals{0ull, 0ll, 0ll, 0ull, 0ull, 0ull};
@@ -78,7 +67,7 @@ __global__ __launch_bounds__(256) void k_cc_hook(const IDX* __restrict__ tris, l
     const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
     if (t >= nt) return;
     int a, b, c;
-    if (!cc_triangle(tris, t, nv, a, b, c)) { atomicAdd(&tot->n_bad, 1ull); return; }
+    if (!mesh_triangle(tris, t, nv, a, b, c)) { atomicAdd(&tot->n_bad, 1ull); return; }
     cc_union(parent, a, b);
     cc_union(parent, b, c);
 }
@@ -99,7 +88,7 @@ template <typename IDX>
 __global__ __launch_bounds__(256) void k_cc_faces(const IDX* __restrict__ tris, long long nt, int nv, const int* __restrict__ label, int* __restrict__ faces) {
     const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
     int a, b, c;
-    const bool active = t < nt && cc_triangle(tris, t, nv, a, b, c);
+    const bool active = t < nt && mesh_triangle(tris, t, nv, a, b, c);
     const int l = active ? label[a] : -1;
     unsigned long long todo = __ballot(active);
     while (todo) {                                                  // wave-uniform
@@ -117,11 +106,8 @@ __global__ __launch_bounds__(256) void k_cc_select(const int* __restrict__ label
     const bool root = v < nv && label[v] == (int)v;
     const int f = root ? faces[v] : 0;
     const bool cand = root && f >= (min_faces > 1 ? min_faces : 1);
-    const unsigned long long mr = __ballot(root), mc = __ballot(cand);
-    if (lane_id() == 0) {
-        if (mr) atomicAdd(&tot->n_components, (unsigned long long)__popcll(mr));
-        if (mc) atomicAdd(&tot->n_candidates, (unsigned long long)__popcll(mc));
-    }
+    wave_count(root, &tot->n_components);
+    wave_count(cand, &tot->n_candidates);
     if (cand) atomicMax(&tot->key, ((unsigned long long)(unsigned)f << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)v));
 }
 
@@ -138,20 +124,20 @@ __device__ __forceinline__ bool cc_item_kept(const CcSelect& s, const IDX* __res
     if (i >= n) return false;
     if (!TRI) return cc_label_kept(s, label[i], faces, key);
     int a, b, c;
-    if (!cc_triangle(tris, i, nv, a, b, c)) return false;
+    if (!mesh_triangle(tris, i, nv, a, b, c)) return false;
     return cc_label_kept(s, label[a], faces, key);
 }
 
-// kept items per tile of CC_TILE -> block_total[blockIdx.x]
+// kept items per tile of SCAN_TILE -> block_total[blockIdx.x]
 template <typename IDX, bool TRI>
 __global__ __launch_bounds__(256) void k_cc_keep_count(CcSelect s, const IDX* __restrict__ tris, long long n, int nv, const int* __restrict__ label,
                                                        const int* __restrict__ faces, const CcTotals* __restrict__ tot, int* __restrict__ block_total) {
     __shared__ int lds[5];
     const unsigned long long key = tot->key;
-    const long long i0 = (long long)blockIdx.x * CC_TILE + threadIdx.x;
+    const long long i0 = (long long)blockIdx.x * SCAN_TILE + threadIdx.x;
     int cnt = 0;
 #pragma unroll
-    for (int k = 0; k < CC_ITEMS; ++k) cnt += cc_item_kept<IDX, TRI>(s, tris, i0 + k * 256, n, nv, label, faces, key);
+    for (int k = 0; k < SCAN_ITEMS; ++k) cnt += cc_item_kept<IDX, TRI>(s, tris, i0 + k * 256, n, nv, label, faces, key);
     int total;
     (void)block_scan_excl(cnt, lds, total);
     if (threadIdx.x == 0) block_total[blockIdx.x] = total;
@@ -164,10 +150,10 @@ __global__ __launch_bounds__(256) void k_cc_keep_offsets(CcSelect s, const IDX* 
                                                          int* __restrict__ map) {
     __shared__ int lds[5];
     const unsigned long long key = tot->key;
-    const long long i0 = (long long)blockIdx.x * CC_TILE + threadIdx.x;
+    const long long i0 = (long long)blockIdx.x * SCAN_TILE + threadIdx.x;
     int run = block_base[blockIdx.x];
 #pragma unroll
-    for (int k = 0; k < CC_ITEMS; ++k) {                            // row k of the tile = 256 consecutive items: coalesced, and in item order
+    for (int k = 0; k < SCAN_ITEMS; ++k) {                            // row k of the tile = 256 consecutive items: coalesced, and in item order
         const long long i = i0 + k * 256;
         const bool kept = cc_item_kept<IDX, TRI>(s, tris, i, n, nv, label, faces, key);
         int total;
@@ -208,20 +194,18 @@ struct CcCarve {
     unsigned nbv, nbt;
 };
 
-static size_t cc_pad(size_t bytes) { return (bytes + 15) / 16 * 16; }
-
-static CcCarve cc_carve(void* ws, long long nv, long long nt) {
-    CcCarve c;
-    c.nbv = cdiv(nv, CC_TILE); c.nbt = cdiv(nt, CC_TILE);
-    char* p = (char*)ws;
-    c.tot = (CcTotals*)p; p += 64;
-    c.label = (int*)p; p += cc_pad((size_t)nv * sizeof(int));
-    c.faces = (int*)p; p += cc_pad((size_t)nv * sizeof(int));
-    c.vmap = (int*)p; p += cc_pad((size_t)nv * sizeof(int));
-    c.tmap = (int*)p; p += cc_pad((size_t)nt * sizeof(int));
-    c.vblock = (int*)p; p += cc_pad((size_t)c.nbv * sizeof(int));
-    c.tblock = (int*)p;
-    return c;
+// the one walk through the workspace: carves it, or sizes it when ws is null; returns its size
+static size_t cc_carve(void* ws, long long nv, long long nt, CcCarve& c) {
+    c.nbv = cdiv(nv, SCAN_TILE); c.nbt = cdiv(nt, SCAN_TILE);
+    Carver w(ws);
+    c.tot = w.take_bytes<CcTotals>(64);
+    c.label = w.take<int>(nv);
+    c.faces = w.take<int>(nv);
+    c.vmap = w.take<int>(nv);
+    c.tmap = w.take<int>(nt);
+    c.vblock = w.take<int>(c.nbv);
+    c.tblock = w.take<int>(c.nbt);
+    return w.bytes();
 }
 
 static_assert(sizeof(CcTotals) <= 64, "CcTotals must fit the workspace head");
@@ -234,8 +218,8 @@ extern "C" {
 
 size_t o2345_mesh_components_workspace_bytes(long long nv, long long nt) {
     if (nv < 0 || nt < 0) return 0;
-    return 64 + 3 * cc_pad((size_t)nv * sizeof(int)) + cc_pad((size_t)nt * sizeof(int)) + cc_pad((size_t)cdiv(nv, CC_TILE) * sizeof(int)) +
-           cc_pad((size_t)cdiv(nt, CC_TILE) * sizeof(int));
+    CcCarve c;
+    return cc_carve(nullptr, nv, nt, c);
 }
 
 // Pass 1 of the two-call protocol: labels, face counts, selection, keep flags and their scans; returns the counts on the HOST (synchronises the
@@ -249,7 +233,8 @@ int o2345_mesh_components_count(const void* tris, int index_bytes, long long nv,
     O2345_REQUIRE(workspace && (nt == 0 || tris), "mesh_components_count: null pointer");
     O2345_REQUIRE(workspace_bytes >= o2345_mesh_components_workspace_bytes(nv, nt), "mesh_components_count: workspace too small");
     O2345_REQUIRE(((uintptr_t)workspace & 15) == 0, "mesh_components_count: workspace must be 16-byte aligned");
-    const CcCarve c = cc_carve(workspace, nv, nt);
+    CcCarve c;
+    (void)cc_carve(workspace, nv, nt, c);
     CcSelect sel;
     sel.active = (min_faces > 0 || keep_largest) ? 1 : 0;
     sel.keep_largest = keep_largest ? 1 : 0;
@@ -258,34 +243,25 @@ int o2345_mesh_components_count(const void* tris, int index_bytes, long long nv,
     const int n = (int)nv;
     const unsigned gv = cdiv(nv > 0 ? nv : 1, 256), gt = cdiv(nt, 256);
     hipLaunchKernelGGL(k_cc_init, dim3(gv), dim3(256), 0, s, c.label, c.faces, n, c.tot);
-    if (nt > 0) {
-        if (index_bytes == 4) hipLaunchKernelGGL(k_cc_hook<int>, dim3(gt), dim3(256), 0, s, (const int*)tris, nt, n, c.label, c.tot);
-        else hipLaunchKernelGGL(k_cc_hook<long long>, dim3(gt), dim3(256), 0, s, (const long long*)tris, nt, n, c.label, c.tot);
-    }
+    if (nt > 0) with_index_type(index_bytes, tris, [&](auto* t) { hipLaunchKernelGGL(k_cc_hook<index_type<decltype(t)>>, dim3(gt), dim3(256), 0, s, t, nt, n, c.label, c.tot); });
     if (nv > 0) hipLaunchKernelGGL(k_cc_flatten, dim3(gv), dim3(256), 0, s, c.label, n, labels);
-    if (nt > 0) {
-        if (index_bytes == 4) hipLaunchKernelGGL(k_cc_faces<int>, dim3(gt), dim3(256), 0, s, (const int*)tris, nt, n, c.label, c.faces);
-        else hipLaunchKernelGGL(k_cc_faces<long long>, dim3(gt), dim3(256), 0, s, (const long long*)tris, nt, n, c.label, c.faces);
-    }
+    if (nt > 0) with_index_type(index_bytes, tris, [&](auto* t) { hipLaunchKernelGGL(k_cc_faces<index_type<decltype(t)>>, dim3(gt), dim3(256), 0, s, t, nt, n, c.label, c.faces); });
     if (nv > 0) {
         hipLaunchKernelGGL(k_cc_select, dim3(gv), dim3(256), 0, s, c.label, c.faces, n, sel.min_faces, c.tot);
         hipLaunchKernelGGL((k_cc_keep_count<int, false>), dim3(c.nbv), dim3(256), 0, s, sel, (const int*)nullptr, nv, n, c.label, c.faces, c.tot, c.vblock);
         hipLaunchKernelGGL(k_scan_small<long long>, dim3(1), dim3(1024), 0, s, c.vblock, (int)c.nbv, &c.tot->nv_kept);
         hipLaunchKernelGGL((k_cc_keep_offsets<int, false>), dim3(c.nbv), dim3(256), 0, s, sel, (const int*)nullptr, nv, n, c.label, c.faces, c.tot, c.vblock, c.vmap);
     }
-    if (nt > 0) {
-        if (index_bytes == 4) hipLaunchKernelGGL((k_cc_keep_count<int, true>), dim3(c.nbt), dim3(256), 0, s, sel, (const int*)tris, nt, n, c.label, c.faces, c.tot, c.tblock);
-        else hipLaunchKernelGGL((k_cc_keep_count<long long, true>), dim3(c.nbt), dim3(256), 0, s, sel, (const long long*)tris, nt, n, c.label, c.faces, c.tot, c.tblock);
+    if (nt > 0) with_index_type(index_bytes, tris, [&](auto* t) {
+        using IDX = index_type<decltype(t)>;
+        hipLaunchKernelGGL((k_cc_keep_count<IDX, true>), dim3(c.nbt), dim3(256), 0, s, sel, t, nt, n, c.label, c.faces, c.tot, c.tblock);
         hipLaunchKernelGGL(k_scan_small<long long>, dim3(1), dim3(1024), 0, s, c.tblock, (int)c.nbt, &c.tot->nt_kept);
-        if (index_bytes == 4) hipLaunchKernelGGL((k_cc_keep_offsets<int, true>), dim3(c.nbt), dim3(256), 0, s, sel, (const int*)tris, nt, n, c.label, c.faces, c.tot, c.tblock, c.tmap);
-        else hipLaunchKernelGGL((k_cc_keep_offsets<long long, true>), dim3(c.nbt), dim3(256), 0, s, sel, (const long long*)tris, nt, n, c.label, c.faces, c.tot, c.tblock, c.tmap);
-    }
+        hipLaunchKernelGGL((k_cc_keep_offsets<IDX, true>), dim3(c.nbt), dim3(256), 0, s, sel, t, nt, n, c.label, c.faces, c.tot, c.tblock, c.tmap);
+    });
     int rc = check_launch("mesh_components_count");
     if (rc) return rc;
     CcTotals h;
-    hipError_t e = hipMemcpyAsync(&h, c.tot, sizeof h, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    O2345_REQUIRE(e == hipSuccess, "mesh_components_count: %s", hipGetErrorString(e));
+    if ((rc = read_totals(h, c.tot, s, "mesh_components_count"))) return rc;
     O2345_REQUIRE(h.n_bad == 0, "mesh_components_count: %llu triangles index outside 0 .. %lld", h.n_bad, nv - 1);
     *n_components_host = (long long)h.n_components;
     *n_components_kept_host = !sel.active ? (long long)h.n_components : sel.keep_largest ? (h.key ? 1 : 0) : (long long)h.n_candidates;
@@ -301,13 +277,14 @@ int o2345_mesh_components_emit(const double* verts, const void* tris, int index_
     O2345_REQUIRE(index_bytes == 4 || index_bytes == 8, "mesh_components_emit: index_bytes must be 4 or 8");
     O2345_REQUIRE(nv >= 0 && nt >= 0 && 3 * nv < (1ll << 31) && nt < (1ll << 31), "mesh_components_emit: bad sizes");
     O2345_REQUIRE(workspace && (!verts_out || verts || nv == 0) && (!tris_out || tris || nt == 0), "mesh_components_emit: null pointer");
-    const CcCarve c = cc_carve(workspace, nv, nt);
+    CcCarve c;
+    (void)cc_carve(workspace, nv, nt, c);
     hipStream_t s = (hipStream_t)stream;
     if (nv > 0 && (verts_out || kept_out)) hipLaunchKernelGGL(k_cc_emit_verts, dim3(cdiv(3 * nv, 256)), dim3(256), 0, s, verts, 3 * nv, c.vmap, verts_out, kept_out);
-    if (nt > 0 && tris_out) {
-        if (index_bytes == 4) hipLaunchKernelGGL(k_cc_emit_tris<int>, dim3(cdiv(3 * nt, 256)), dim3(256), 0, s, (const int*)tris, 3 * nt, c.vmap, c.tmap, (int*)tris_out);
-        else hipLaunchKernelGGL(k_cc_emit_tris<long long>, dim3(cdiv(3 * nt, 256)), dim3(256), 0, s, (const long long*)tris, 3 * nt, c.vmap, c.tmap, (long long*)tris_out);
-    }
+    if (nt > 0 && tris_out) with_index_type(index_bytes, tris, [&](auto* t) {
+        using IDX = index_type<decltype(t)>;
+        hipLaunchKernelGGL(k_cc_emit_tris<IDX>, dim3(cdiv(3 * nt, 256)), dim3(256), 0, s, t, 3 * nt, c.vmap, c.tmap, (IDX*)tris_out);
+    });
     return check_launch("mesh_components_emit");
 }
 

@@ -20,19 +20,13 @@
 // index; a thread claims an empty slot with atomicCAS, or compares its sorted triple with that of the triangle the slot holds (all holders of one slot
 // have the same set, so the set of a slot never changes) and does atomicMin(slot, t); a triangle is kept iff its slot ends up holding its own index =
 // the first in face order.  The cell bounds are integer atomicMin / atomicMax of an order-preserving encoding of q.  Member lists are filled through an
-// atomic cursor in any order and then sorted, rows of up to DEC_SHORT members in registers, longer ones by one block each (rank sort).  The sum itself is
+// atomic cursor in any order and then sorted, rows of up to ROW_SHORT members in registers, longer ones by one block each (rank sort).  The sum itself is
 // one thread per cluster adding in row order.  No float atomics; every probe loop is bounded by its table's capacity (running out is an error status).
 // Inside the two inserting kernels every access to a table is an atomic; plain loads of the tables happen in later launches only.
-#include "common.h"
-#include "block_kernels.h"
+#include "mesh_common.h"
 
 namespace o2345 {
 
-constexpr int DEC_ITEMS = 8;                          // items per thread of the scan kernels
-constexpr int DEC_TILE = IDX_BLOCK * DEC_ITEMS;       // per block
-constexpr int DEC_SHORT = 32;                         // members a thread sorts in registers
-constexpr int DEC_LONG_GRID = 64;                     // blocks of the long-row kernel (each loops over the list)
-constexpr int DEC_PAD = 0x7FFFFFFF;                   // sorts behind every vertex index; also the value of an unclaimed cluster slot
 constexpr unsigned long long DEC_EMPTY = ~0ull;       // key of an empty cluster slot (a packed key has 63 bits)
 constexpr double DEC_EXTENT = 2097152.0;              // 2^21 cells per axis
 
@@ -64,13 +58,6 @@ __device__ __forceinline__ unsigned long long dec_mix(unsigned long long x) {   
     return x ^ (x >> 31);
 }
 
-template <typename IDX>
-__device__ __forceinline__ bool dec_triangle(const IDX* __restrict__ tris, long long t, int nv, int& a, int& b, int& c) {
-    const long long ia = (long long)tris[3 * t], ib = (long long)tris[3 * t + 1], ic = (long long)tris[3 * t + 2];
-    a = (int)ia; b = (int)ib; c = (int)ic;
-    return ia >= 0 && ia < nv && ib >= 0 && ib < nv && ic >= 0 && ic < nv;
-}
-
 __device__ __forceinline__ void dec_sort3(int& x, int& y, int& z) {
     regs_cmpswap(x, y); regs_cmpswap(y, z); regs_cmpswap(x, y);
 }
@@ -94,7 +81,7 @@ __global__ __launch_bounds__(256) void k_dec_init(unsigned long long* __restrict
         for (int d = 0; d < 3; ++d) z.qmin[d] = ~0ull;
         *tot = z;
     }
-    if (i < vcap) { keys[i] = DEC_EMPTY; vals[i] = DEC_PAD; }
+    if (i < vcap) { keys[i] = DEC_EMPTY; vals[i] = ROW_PAD; }          // above every vertex index: the atomicMin of k_dec_insert replaces it
     if (i < tcap) tslots[i] = -1;
     if (i < nv) { flag[i] = 0; cnt[i] = 0; }
 }
@@ -165,8 +152,7 @@ __global__ __launch_bounds__(256) void k_dec_rep(const int* __restrict__ vals, c
         if (r < 0 || r > v) r = (int)v;                             // only after a probe ran out (an error status): keep every index usable
         rep[v] = r;
     }
-    const unsigned long long m = __ballot(v < nv && r == (int)v);
-    if (lane_id() == 0 && m) atomicAdd(&tot->n_clusters, (unsigned long long)__popcll(m));
+    wave_count(v < nv && r == (int)v, &tot->n_clusters);
 }
 
 // tslot[t] = the slot of triangle t's set of representatives in the second table, or -1 for a degenerate (or unusable) triangle
@@ -177,7 +163,7 @@ __global__ __launch_bounds__(256) void k_dec_tris(const IDX* __restrict__ tris, 
     bool bad = false, degenerate = false, lost = false;
     if (t < nt) {
         int a, b, c, state = -1;
-        if (!dec_triangle(tris, t, nv, a, b, c)) bad = true;
+        if (!mesh_triangle(tris, t, nv, a, b, c)) bad = true;
         else {
             int x = rep[a], y = rep[b], z = rep[c];
             if (x == y || y == z || x == z) degenerate = true;
@@ -190,7 +176,7 @@ __global__ __launch_bounds__(256) void k_dec_tris(const IDX* __restrict__ tris, 
                     if (cur < 0) cur = atomicCAS(tslots + s, -1, (int)t);
                     if (cur < 0) { state = (int)s; lost = false; break; }          // claimed an empty slot
                     int a2, b2, c2;                                     // the slot holds triangle cur: in range and not degenerate, or it would not be there
-                    (void)dec_triangle(tris, cur, nv, a2, b2, c2);
+                    (void)mesh_triangle(tris, cur, nv, a2, b2, c2);
                     int x2 = rep[a2], y2 = rep[b2], z2 = rep[c2];
                     dec_sort3(x2, y2, z2);
                     if (x2 == x && y2 == y && z2 == z) {
@@ -205,12 +191,9 @@ __global__ __launch_bounds__(256) void k_dec_tris(const IDX* __restrict__ tris, 
         }
         tslot[t] = state;
     }
-    const unsigned long long mb = __ballot(bad), md = __ballot(degenerate), ml = __ballot(lost);
-    if (lane_id() == 0) {
-        if (mb) atomicAdd(&tot->n_bad, (unsigned long long)__popcll(mb));
-        if (md) atomicAdd(&tot->n_degenerate, (unsigned long long)__popcll(md));
-        if (ml) atomicAdd(&tot->n_overflow, (unsigned long long)__popcll(ml));
-    }
+    wave_count(bad, &tot->n_bad);
+    wave_count(degenerate, &tot->n_degenerate);
+    wave_count(lost, &tot->n_overflow);
 }
 
 // tkeep[t] = 1 iff the slot of t holds t; the kept triangles flag the representatives they reference (every writer stores the same 1)
@@ -228,8 +211,7 @@ __global__ __launch_bounds__(256) void k_dec_keep(const IDX* __restrict__ tris, 
             flag[rep[tris[3 * t]]] = 1; flag[rep[tris[3 * t + 1]]] = 1; flag[rep[tris[3 * t + 2]]] = 1;
         }
     }
-    const unsigned long long m = __ballot(duplicate);
-    if (lane_id() == 0 && m) atomicAdd(&tot->n_duplicate, (unsigned long long)__popcll(m));
+    wave_count(duplicate, &tot->n_duplicate);
 }
 
 // cluster_of[v] = the new index of v's cluster or -1; cnt[new index] = its members
@@ -254,9 +236,7 @@ __global__ __launch_bounds__(256) void k_dec_fill(int nv, const int* __restrict_
 template <int N>
 __device__ __forceinline__ void dec_short_row(int* __restrict__ row, int d) {
     int r[N];
-#pragma unroll
-    for (int k = 0; k < N; ++k) r[k] = k < d ? row[k] : DEC_PAD;
-    sort_regs<N>(r);
+    row_sorted_regs<N>(row, d, r);
 #pragma unroll
     for (int k = 0; k < N; ++k)
         if (k < d) row[k] = r[k];
@@ -268,14 +248,13 @@ __global__ __launch_bounds__(256) void k_dec_rows(int nv, const int* __restrict_
     const long long c = (long long)blockIdx.x * 256 + threadIdx.x;
     if (c >= nv) return;
     const int d = cnt[c];
-    if (d > DEC_SHORT) long_list[atomicAdd(&tot->n_long, 1)] = (int)c;
-    else if (d > 16) dec_short_row<DEC_SHORT>(members + off[c], d);
+    if (d > ROW_SHORT) long_list[atomicAdd(&tot->n_long, 1)] = (int)c;
+    else if (d > 16) dec_short_row<ROW_SHORT>(members + off[c], d);
     else if (d > 4) dec_short_row<16>(members + off[c], d);
     else if (d > 1) dec_short_row<4>(members + off[c], d);
 }
 
-// one block per listed row: rank sort through tmp (members are distinct: position = members that are smaller).  O(d^2 / 256) comparisons per thread:
-// the slow path of a mesh with thousands of vertices in one cell.
+// one block per listed row: rank sort through tmp (row_rank_sort): the slow path of a mesh with thousands of vertices in one cell
 __global__ __launch_bounds__(256) void k_dec_long_rows(const int* __restrict__ off, const int* __restrict__ cnt, int* __restrict__ members, int* __restrict__ tmp,
                                                        const int* __restrict__ long_list, const DecTotals* __restrict__ tot) {
     const int n_long = tot->n_long;
@@ -284,13 +263,7 @@ __global__ __launch_bounds__(256) void k_dec_long_rows(const int* __restrict__ o
         const int base = off[c], d = cnt[c];
         int* row = members + base;
         int* srt = tmp + base;
-        for (int i = threadIdx.x; i < d; i += 256) {
-            const int x = row[i];
-            int pos = 0;
-            for (int j = 0; j < d; ++j) pos += row[j] < x ? 1 : 0;
-            srt[pos] = x;
-        }
-        __syncthreads();                                            // srt complete (this block wrote all of it)
+        row_rank_sort(row, srt, d);                                 // srt complete (this block wrote all of it)
         for (int i = threadIdx.x; i < d; i += 256) row[i] = srt[i];
     }
 }
@@ -335,8 +308,6 @@ struct DecCarve {
     unsigned nbv, nbt;
 };
 
-static size_t dec_pad(size_t bytes) { return (bytes + 15) / 16 * 16; }
-
 static long long dec_capacity(long long n) {                        // the power of two >= 2 n (and >= 2)
     long long c = 2;
     while (c < 2 * n) c <<= 1;
@@ -347,31 +318,21 @@ static_assert(sizeof(DecTotals) <= 128, "DecTotals must fit the workspace head")
 
 static bool dec_sizes_ok(long long nv, long long nt) { return nv >= 0 && nt >= 0 && nv < (1ll << 30) && 3 * nt < (1ll << 31); }
 
-// carves the workspace; returns its size
+// the one walk through the workspace: carves it, or sizes it when ws is null; returns its size
 static size_t dec_carve(void* ws, long long nv, long long nt, DecCarve& c) {
     c.vcap = dec_capacity(nv); c.tcap = dec_capacity(nt);
-    c.nbv = cdiv(nv, DEC_TILE); c.nbt = cdiv(nt, DEC_TILE);
-    const size_t vb = dec_pad((size_t)nv * sizeof(int)), tb = dec_pad((size_t)nt * sizeof(int));
-    char* p = (char*)ws;
-    c.tot = (DecTotals*)p; p += 128;
-    c.keys = (unsigned long long*)p; p += (size_t)c.vcap * sizeof(unsigned long long);
-    c.vals = (int*)p; p += (size_t)c.vcap * sizeof(int);
-    c.tslots = (int*)p; p += (size_t)c.tcap * sizeof(int);
-    c.slot = (unsigned*)p; p += vb;
-    int** const per_vertex[] = {&c.rep, &c.flag, &c.vmap, &c.cluster_of, &c.cnt, &c.off, &c.cursor, &c.long_list, &c.members, &c.tmp};
-    for (int** a : per_vertex) { *a = (int*)p; p += vb; }
-    int** const per_triangle[] = {&c.tslot, &c.tkeep, &c.tmap};
-    for (int** a : per_triangle) { *a = (int*)p; p += tb; }
-    c.vblock = (int*)p; p += dec_pad((size_t)c.nbv * sizeof(int));
-    c.tblock = (int*)p; p += dec_pad((size_t)c.nbt * sizeof(int));
-    return (size_t)(p - (char*)ws);
-}
-
-// exclusive scan of a[0 .. n) -> out (and out2), the sum -> *total
-static void dec_scan(const int* a, long long n, unsigned blocks, int* block_total, int* out, int* out2, long long* total, hipStream_t s) {
-    hipLaunchKernelGGL(k_tile_sum<DEC_ITEMS>, dim3(blocks), dim3(256), 0, s, a, n, block_total);
-    hipLaunchKernelGGL(k_scan_small<long long>, dim3(1), dim3(1024), 0, s, block_total, (int)blocks, total);
-    hipLaunchKernelGGL(k_tile_scan<DEC_ITEMS>, dim3(blocks), dim3(256), 0, s, a, n, block_total, out, out2);
+    c.nbv = cdiv(nv, SCAN_TILE); c.nbt = cdiv(nt, SCAN_TILE);
+    Carver w(ws);
+    c.tot = w.take_bytes<DecTotals>(128);
+    c.keys = w.take_bytes<unsigned long long>((size_t)c.vcap * sizeof(unsigned long long));      // the tables: powers of two, unpadded (8 bytes at the
+    c.vals = w.take_bytes<int>((size_t)c.vcap * sizeof(int));                                    // smallest, which keeps every int array behind aligned)
+    c.tslots = w.take_bytes<int>((size_t)c.tcap * sizeof(int));
+    c.slot = w.take<unsigned>(nv);
+    for (int** a : {&c.rep, &c.flag, &c.vmap, &c.cluster_of, &c.cnt, &c.off, &c.cursor, &c.long_list, &c.members, &c.tmp}) *a = w.take<int>(nv);
+    for (int** a : {&c.tslot, &c.tkeep, &c.tmap}) *a = w.take<int>(nt);
+    c.vblock = w.take<int>(c.nbv);
+    c.tblock = w.take<int>(c.nbt);
+    return w.bytes();
 }
 
 }  // namespace o2345
@@ -412,29 +373,25 @@ int o2345_mesh_decimate_count(const double* verts, const void* tris, int index_b
         hipLaunchKernelGGL(k_dec_rep, dim3(gv), dim3(256), 0, s, c.vals, c.slot, n, c.rep, c.tot);
     }
     if (nt > 0) {
-        if (index_bytes == 4) {
-            hipLaunchKernelGGL(k_dec_tris<int>, dim3(gt), dim3(256), 0, s, (const int*)tris, nt, n, c.rep, c.tslots, tmask, c.tslot, c.tot);
-            hipLaunchKernelGGL(k_dec_keep<int>, dim3(gt), dim3(256), 0, s, (const int*)tris, nt, c.rep, c.tslots, c.tslot, c.tkeep, c.flag, c.tot);
-        } else {
-            hipLaunchKernelGGL(k_dec_tris<long long>, dim3(gt), dim3(256), 0, s, (const long long*)tris, nt, n, c.rep, c.tslots, tmask, c.tslot, c.tot);
-            hipLaunchKernelGGL(k_dec_keep<long long>, dim3(gt), dim3(256), 0, s, (const long long*)tris, nt, c.rep, c.tslots, c.tslot, c.tkeep, c.flag, c.tot);
-        }
-        dec_scan(c.tkeep, nt, c.nbt, c.tblock, c.tmap, nullptr, &c.tot->nt_out, s);
+        with_index_type(index_bytes, tris, [&](auto* t) {
+            using IDX = index_type<decltype(t)>;
+            hipLaunchKernelGGL(k_dec_tris<IDX>, dim3(gt), dim3(256), 0, s, t, nt, n, c.rep, c.tslots, tmask, c.tslot, c.tot);
+            hipLaunchKernelGGL(k_dec_keep<IDX>, dim3(gt), dim3(256), 0, s, t, nt, c.rep, c.tslots, c.tslot, c.tkeep, c.flag, c.tot);
+        });
+        exclusive_scan<SCAN_ITEMS>(c.tkeep, nt, c.nbt, c.tblock, c.tmap, nullptr, &c.tot->nt_out, s);
     }
     if (nv > 0) {
-        dec_scan(c.flag, nv, c.nbv, c.vblock, c.vmap, nullptr, &c.tot->nv_out, s);
+        exclusive_scan<SCAN_ITEMS>(c.flag, nv, c.nbv, c.vblock, c.vmap, nullptr, &c.tot->nv_out, s);
         hipLaunchKernelGGL(k_dec_assign, dim3(gv), dim3(256), 0, s, n, c.rep, c.flag, c.vmap, c.cluster_of, c.cnt);
-        dec_scan(c.cnt, nv, c.nbv, c.vblock, c.off, c.cursor, &c.tot->n_members, s);
+        exclusive_scan<SCAN_ITEMS>(c.cnt, nv, c.nbv, c.vblock, c.off, c.cursor, &c.tot->n_members, s);
         hipLaunchKernelGGL(k_dec_fill, dim3(gv), dim3(256), 0, s, n, c.cluster_of, c.cursor, c.members);
         hipLaunchKernelGGL(k_dec_rows, dim3(gv), dim3(256), 0, s, n, c.off, c.cnt, c.members, c.long_list, c.tot);
-        hipLaunchKernelGGL(k_dec_long_rows, dim3(DEC_LONG_GRID), dim3(256), 0, s, c.off, c.cnt, c.members, c.tmp, c.long_list, c.tot);
+        hipLaunchKernelGGL(k_dec_long_rows, dim3(ROW_LONG_GRID), dim3(256), 0, s, c.off, c.cnt, c.members, c.tmp, c.long_list, c.tot);
     }
     int rc = check_launch("mesh_decimate_count");
     if (rc) return rc;
     DecTotals h;
-    hipError_t e = hipMemcpyAsync(&h, c.tot, sizeof h, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    O2345_REQUIRE(e == hipSuccess, "mesh_decimate_count: %s", hipGetErrorString(e));
+    if ((rc = read_totals(h, c.tot, s, "mesh_decimate_count"))) return rc;
     O2345_REQUIRE(h.n_nonfinite == 0, "mesh_decimate_count: %llu vertices have a non-finite coordinate", h.n_nonfinite);
     O2345_REQUIRE(h.n_bad == 0, "mesh_decimate_count: %llu triangles index outside 0 .. %lld", h.n_bad, nv - 1);
     O2345_REQUIRE(h.bad_extent == 0, "mesh_decimate_count: the mesh extends over 2^21 cells or more of size %g along an axis", cell);
@@ -459,10 +416,10 @@ int o2345_mesh_decimate_emit(const double* verts, const void* tris, int index_by
     hipStream_t s = (hipStream_t)stream;
     if (nv > 0 && (verts_out || cluster))
         hipLaunchKernelGGL(k_dec_emit_verts, dim3(cdiv(nv, 256)), dim3(256), 0, s, verts, (int)nv, c.cluster_of, c.off, c.cnt, c.members, c.tot, verts_out, cluster);
-    if (nt > 0 && tris_out) {
-        if (index_bytes == 4) hipLaunchKernelGGL(k_dec_emit_tris<int>, dim3(cdiv(3 * nt, 256)), dim3(256), 0, s, (const int*)tris, 3 * nt, c.cluster_of, c.tkeep, c.tmap, (int*)tris_out);
-        else hipLaunchKernelGGL(k_dec_emit_tris<long long>, dim3(cdiv(3 * nt, 256)), dim3(256), 0, s, (const long long*)tris, 3 * nt, c.cluster_of, c.tkeep, c.tmap, (long long*)tris_out);
-    }
+    if (nt > 0 && tris_out) with_index_type(index_bytes, tris, [&](auto* t) {
+        using IDX = index_type<decltype(t)>;
+        hipLaunchKernelGGL(k_dec_emit_tris<IDX>, dim3(cdiv(3 * nt, 256)), dim3(256), 0, s, t, 3 * nt, c.cluster_of, c.tkeep, c.tmap, (IDX*)tris_out);
+    });
     return check_launch("mesh_decimate_emit");
 }
 

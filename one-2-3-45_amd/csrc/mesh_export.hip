@@ -6,7 +6,7 @@
 //            1 and 2 exchanged, bit for bit.
 //   GLB:     float32 positions + their per-axis min / max (required on the POSITION accessor), uint8 rgba, optional float32 unit normals, uint32 indices.
 //   OBJ:     fixed-width records (record i of a kind starts at i * len: no scan), built per block in LDS and copied out in 16-byte pieces.
-#include "common.h"
+#include "mesh_common.h"
 #include "mesh_math.h"
 #include <string.h>
 #include <thread>
@@ -158,8 +158,7 @@ int o2345_mesh_asset_indices(const void* tris, int index_bytes, long long m, uin
     O2345_REQUIRE(index_bytes == 4 || index_bytes == 8, "mesh_asset_indices: index_bytes must be 4 or 8");
     if (m <= 0) return 0;
     O2345_REQUIRE(tris && indices, "mesh_asset_indices: null pointer");
-    if (index_bytes == 8) hipLaunchKernelGGL(k_asset_indices<long long>, dim3(cdiv(3 * m, 256)), dim3(256), 0, (hipStream_t)stream, (const long long*)tris, 3 * m, indices);
-    else hipLaunchKernelGGL(k_asset_indices<int32_t>, dim3(cdiv(3 * m, 256)), dim3(256), 0, (hipStream_t)stream, (const int32_t*)tris, 3 * m, indices);
+    with_index_type(index_bytes, tris, [&](auto* t) { hipLaunchKernelGGL(k_asset_indices<index_type<decltype(t)>>, dim3(cdiv(3 * m, 256)), dim3(256), 0, (hipStream_t)stream, t, 3 * m, indices); });
     return check_launch("mesh_asset_indices");
 }
 

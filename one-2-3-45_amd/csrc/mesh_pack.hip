@@ -5,7 +5,7 @@
 // are produced on the device, so export is one D2H copy of 16 B/vertex + 13 B/face followed by a single file write.
 // Arithmetic follows the reference's numpy expressions in fp64 (verts / (R-1) * (bmax - bmin) + bmin; * s + t; trans @ [v,1])
 // and rounds to float32 only in the record, as trimesh's PLY exporter does.
-#include "common.h"
+#include "mesh_common.h"
 #include "mesh_math.h"
 #include <string.h>
 #include <thread>
@@ -119,8 +119,7 @@ int o2345_mesh_pack_faces(const void* tris, int index_bytes, long long m, uint8_
     O2345_REQUIRE(index_bytes == 4 || index_bytes == 8, "mesh_pack_faces: index_bytes must be 4 or 8");
     if (m <= 0) return 0;
     O2345_REQUIRE(tris && face_records, "mesh_pack_faces: null pointer");
-    if (index_bytes == 8) hipLaunchKernelGGL(k_pack_faces<long long>, dim3(cdiv(m, 256)), dim3(256), 0, (hipStream_t)stream, (const long long*)tris, m, face_records);
-    else hipLaunchKernelGGL(k_pack_faces<int32_t>, dim3(cdiv(m, 256)), dim3(256), 0, (hipStream_t)stream, (const int32_t*)tris, m, face_records);
+    with_index_type(index_bytes, tris, [&](auto* t) { hipLaunchKernelGGL(k_pack_faces<index_type<decltype(t)>>, dim3(cdiv(m, 256)), dim3(256), 0, (hipStream_t)stream, t, m, face_records); });
     return check_launch("mesh_pack_faces");
 }
 

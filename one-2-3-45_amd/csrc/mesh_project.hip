@@ -21,7 +21,7 @@
 // go to slot list[i]), and a point's SDF and gradient do not depend on its place in a tile.  The counters are integer atomics, the maxima 64-bit integer
 // atomicMax of the bit pattern of a non-negative double (which orders like the double).  No float atomics.  Counter r of the 66 is written before round
 // r and read in it, never reused, so the list of counts is also the `evaluated` of the twin.
-#include "common.h"
+#include "mesh_common.h"
 #include <float.h>
 
 namespace o2345 {
@@ -74,8 +74,7 @@ __global__ __launch_bounds__(256) void k_proj_init(const double* __restrict__ ve
         proj_world(p, f, pts + 3 * v);
         list[v] = (int)v;
     }
-    const unsigned long long m = __ballot(nonfinite);
-    if (lane_id() == 0 && m) atomicAdd(&st->n_nonfinite, (unsigned long long)__popcll(m));
+    wave_count(nonfinite, &st->n_nonfinite);
 }
 
 // Every thread takes PROJ_ITEMS entries of this round's list, a block PROJ_TILE consecutive ones: classify, step, and append the survivors to the other
@@ -179,20 +178,17 @@ struct ProjCarve {
     int* list[2];
 };
 
-static size_t proj_pad(size_t bytes) { return (bytes + 15) / 16 * 16; }
-
 static bool proj_size_ok(long long nv) { return nv >= 0 && nv < (1ll << 30); }
 
-// carves the workspace; returns its size
+// the one walk through the workspace: carves it, or sizes it when ws is null; returns its size
 static size_t proj_carve(void* ws, long long nv, ProjCarve& c) {
-    const size_t one = proj_pad((size_t)nv * sizeof(float)), three = proj_pad((size_t)nv * 3 * sizeof(float));
-    char* p = (char*)ws;
-    c.pts = (float*)p; p += three;
-    c.grad = (float*)p; p += three;
-    c.sdf = (float*)p; p += one;
-    c.list[0] = (int*)p; p += one;
-    c.list[1] = (int*)p; p += one;
-    return (size_t)(p - (char*)ws);
+    Carver w(ws);
+    c.pts = w.take<float>(nv * 3);
+    c.grad = w.take<float>(nv * 3);
+    c.sdf = w.take<float>(nv);
+    c.list[0] = w.take<int>(nv);
+    c.list[1] = w.take<int>(nv);
+    return w.bytes();
 }
 
 static bool proj_positive(double x) { return x > 0.0 && x <= DBL_MAX; }

@@ -12,19 +12,12 @@
 //   smooth     `iterations` times: step(lam), then step(mu) unless mu == 0.
 //
 // Build: capacities by integer atomicAdd per triangle corner, exclusive scan, slots claimed with an integer atomic cursor (the order inside a raw row is
-// arbitrary), then every row is sorted and its duplicates collapsed, which makes the result independent of that order.  Rows of at most ADJ_SHORT raw
+// arbitrary), then every row is sorted and its duplicates collapsed, which makes the result independent of that order.  Rows of at most ROW_SHORT raw
 // entries (marching-cubes meshes: 8 - 24) are sorted by their own thread in registers; longer ones (the centre of a fan) go on a list and get one block
 // each, which rank-sorts the row.  No float atomics anywhere.
-#include "common.h"
-#include "block_kernels.h"
+#include "mesh_common.h"
 
 namespace o2345 {
-
-constexpr int ADJ_ITEMS = 8;                        // items per thread of the scan kernels
-constexpr int ADJ_TILE = IDX_BLOCK * ADJ_ITEMS;     // per block
-constexpr int ADJ_SHORT = 32;                       // raw entries a thread sorts in registers
-constexpr int ADJ_LONG_GRID = 64;                   // blocks of the long-row kernels (each loops over the list)
-constexpr int ADJ_PAD = 0x7FFFFFFF;                 // sorts behind every vertex index
 
 // device scalars of one build (workspace head)
 struct AdjTotals {
@@ -32,13 +25,6 @@ struct AdjTotals {
     unsigned long long n_bad;                       // triangles with an index outside [0, nv)
     int n_long;                                     // rows on the long list
 };
-
-template <typename IDX>
-__device__ __forceinline__ bool adj_triangle(const IDX* __restrict__ tris, long long t, int nv, int& a, int& b, int& c) {
-    const long long ia = (long long)tris[3 * t], ib = (long long)tris[3 * t + 1], ic = (long long)tris[3 * t + 2];
-    a = (int)ia; b = (int)ib; c = (int)ic;
-    return ia >= 0 && ia < nv && ib >= 0 && ib < nv && ic >= 0 && ic < nv;
-}
 
 __global__ __launch_bounds__(256) void k_adj_init(int* __restrict__ cap, int nv, AdjTotals* __restrict__ tot) {
     const long long v = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -52,7 +38,7 @@ __global__ __launch_bounds__(256) void k_adj_capacity(const IDX* __restrict__ tr
     const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
     if (t >= nt) return;
     int a, b, c;
-    if (!adj_triangle(tris, t, nv, a, b, c)) { atomicAdd(&tot->n_bad, 1ull); return; }
+    if (!mesh_triangle(tris, t, nv, a, b, c)) { atomicAdd(&tot->n_bad, 1ull); return; }
     const int na = (a != b) + (a != c), nb = (b != a) + (b != c), nc = (c != a) + (c != b);
     if (na) atomicAdd(cap + a, na);
     if (nb) atomicAdd(cap + b, nb);
@@ -65,7 +51,7 @@ __global__ __launch_bounds__(256) void k_adj_fill(const IDX* __restrict__ tris, 
     const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
     if (t >= nt) return;
     int a, b, c;
-    if (!adj_triangle(tris, t, nv, a, b, c)) return;
+    if (!mesh_triangle(tris, t, nv, a, b, c)) return;
     const int na = (a != b) + (a != c), nb = (b != a) + (b != c), nc = (c != a) + (c != b);      // as k_adj_capacity counted them
     if (na) { int s = atomicAdd(cursor + a, na); if (a != b) raw[s++] = b; if (a != c) raw[s] = c; }
     if (nb) { int s = atomicAdd(cursor + b, nb); if (b != c) raw[s++] = c; if (b != a) raw[s] = a; }
@@ -76,13 +62,11 @@ __global__ __launch_bounds__(256) void k_adj_fill(const IDX* __restrict__ tris, 
 template <int N>
 __device__ __forceinline__ int adj_short_row(int* __restrict__ row, int d, int& boundary) {
     int r[N];
-#pragma unroll
-    for (int k = 0; k < N; ++k) r[k] = k < d ? row[k] : ADJ_PAD;
-    sort_regs<N>(r);
+    row_sorted_regs<N>(row, d, r);
     int deg = 0, bnd = 0;
 #pragma unroll
     for (int k = 0; k < N; ++k) {
-        const bool valid = r[k] != ADJ_PAD;
+        const bool valid = r[k] != ROW_PAD;
         const bool first = k == 0 || r[k] != r[k - 1];
         const bool last = k == N - 1 || r[k] != r[k + 1];
         if (valid && first) {
@@ -100,16 +84,15 @@ __global__ __launch_bounds__(256) void k_adj_rows(int nv, const int* __restrict_
     const long long v = (long long)blockIdx.x * 256 + threadIdx.x;
     if (v >= nv) return;
     const int d = cap[v];
-    if (d > ADJ_SHORT) { long_list[atomicAdd(&tot->n_long, 1)] = (int)v; return; }
+    if (d > ROW_SHORT) { long_list[atomicAdd(&tot->n_long, 1)] = (int)v; return; }
     int b = 0, deg = 0;
-    if (d > 16) deg = adj_short_row<ADJ_SHORT>(raw + rawoff[v], d, b);
+    if (d > 16) deg = adj_short_row<ROW_SHORT>(raw + rawoff[v], d, b);
     else if (d > 0) deg = adj_short_row<16>(raw + rawoff[v], d, b);
     cap[v] = deg;
     bnd[v] = (unsigned char)b;
 }
 
-// one block per listed row: rank sort into tmp (position = entries that are smaller + equal entries in front), then heads of runs compacted back into
-// the row's own raw segment in order.  O(d^2 / 256) comparisons per thread.
+// one block per listed row: rank sort into tmp (row_rank_sort), then heads of runs compacted back into the row's own raw segment in order
 __global__ __launch_bounds__(256) void k_adj_long_rows(const int* __restrict__ rawoff, const int* __restrict__ cursor, int* __restrict__ cap, int* __restrict__ raw,
                                                        int* __restrict__ tmp, unsigned char* __restrict__ bnd, const int* __restrict__ long_list,
                                                        const AdjTotals* __restrict__ tot) {
@@ -122,20 +105,11 @@ __global__ __launch_bounds__(256) void k_adj_long_rows(const int* __restrict__ r
         int* row = raw + base;
         int* srt = tmp + base;
         if (threadIdx.x == 0) any_single = 0;
-        for (int i = threadIdx.x; i < d; i += 256) {
-            const int x = row[i];
-            int pos = 0;
-            for (int j = 0; j < d; ++j) {
-                const int y = row[j];
-                pos += (y < x || (y == x && j < i)) ? 1 : 0;
-            }
-            srt[pos] = x;
-        }
-        __syncthreads();                                            // srt complete (this block wrote all of it); row is free from here on
+        row_rank_sort(row, srt, d);                                 // srt complete (this block wrote all of it); row is free from here on
         int run = 0;
         for (int k0 = 0; k0 < d; k0 += 256) {                       // uniform trip count: block_scan_excl synchronises
             const int k = k0 + threadIdx.x;
-            const int x = k < d ? srt[k] : ADJ_PAD;
+            const int x = k < d ? srt[k] : ROW_PAD;
             const bool first = k < d && (k == 0 || srt[k - 1] != x);
             const bool last = k < d && (k == d - 1 || srt[k + 1] != x);
             int total;
@@ -150,7 +124,7 @@ __global__ __launch_bounds__(256) void k_adj_long_rows(const int* __restrict__ r
     }
 }
 
-// CSR out: one thread per vertex copies its row unless the row is on the long list (raw count above ADJ_SHORT); the ADJ_LONG_GRID blocks behind the
+// CSR out: one thread per vertex copies its row unless the row is on the long list (raw count above ROW_SHORT); the ROW_LONG_GRID blocks behind the
 // vertex blocks copy the listed rows, one block per row (an empty list costs them one load)
 __global__ __launch_bounds__(256) void k_adj_emit(int nv, unsigned vertex_blocks, const int* __restrict__ rawoff, const int* __restrict__ cursor,
                                                   const int* __restrict__ deg, const int* __restrict__ off, const int* __restrict__ raw,
@@ -171,7 +145,7 @@ __global__ __launch_bounds__(256) void k_adj_emit(int nv, unsigned vertex_blocks
     const int o = off[v], base = rawoff[v];
     offsets[v] = o;
     boundary[v] = bnd[v];
-    if (cursor[v] - base > ADJ_SHORT) return;
+    if (cursor[v] - base > ROW_SHORT) return;
     const int d = deg[v];
     for (int k = 0; k < d; ++k) neighbours[o + k] = raw[base + k];
 }
@@ -207,25 +181,22 @@ struct AdjCarve {
     unsigned nbv;
 };
 
-static size_t adj_pad(size_t bytes) { return (bytes + 15) / 16 * 16; }
-
-// everything pass 2 reads lies in front of the one nt-sized buffer it needs (raw), so the layout up to there depends on nv alone
-static AdjCarve adj_carve(void* ws, long long nv, long long nt) {
-    AdjCarve c;
-    c.nbv = cdiv(nv, ADJ_TILE);
-    const size_t vb = adj_pad((size_t)nv * sizeof(int));
-    char* p = (char*)ws;
-    c.tot = (AdjTotals*)p; p += 64;
-    c.cap = (int*)p; p += vb;                       // raw entries per row, then the degree
-    c.rawoff = (int*)p; p += vb;
-    c.cursor = (int*)p; p += vb;
-    c.off = (int*)p; p += vb;                       // exclusive scan of the degrees
-    c.long_list = (int*)p; p += vb;
-    c.vblock = (int*)p; p += adj_pad((size_t)c.nbv * sizeof(int));
-    c.bnd = (unsigned char*)p; p += adj_pad((size_t)nv);
-    c.raw = (int*)p; p += adj_pad((size_t)nt * 6 * sizeof(int));
-    c.tmp = (int*)p;                                // long rows only
-    return c;
+// the one walk through the workspace: carves it, or sizes it when ws is null; returns its size.  Everything pass 2 reads lies in front of the one
+// nt-sized buffer it needs (raw), so the layout up to there depends on nv alone
+static size_t adj_carve(void* ws, long long nv, long long nt, AdjCarve& c) {
+    c.nbv = cdiv(nv, SCAN_TILE);
+    Carver w(ws);
+    c.tot = w.take_bytes<AdjTotals>(64);
+    c.cap = w.take<int>(nv);                        // raw entries per row, then the degree
+    c.rawoff = w.take<int>(nv);
+    c.cursor = w.take<int>(nv);
+    c.off = w.take<int>(nv);                        // exclusive scan of the degrees
+    c.long_list = w.take<int>(nv);
+    c.vblock = w.take<int>(c.nbv);
+    c.bnd = w.take<unsigned char>(nv);
+    c.raw = w.take<int>(nt * 6);
+    c.tmp = w.take<int>(nt * 6);                    // long rows only
+    return w.bytes();
 }
 
 static_assert(sizeof(AdjTotals) <= 64, "AdjTotals must fit the workspace head");
@@ -240,8 +211,8 @@ extern "C" {
 
 size_t o2345_mesh_adjacency_workspace_bytes(long long nv, long long nt) {
     if (!adj_sizes_ok(nv, nt)) return 0;
-    return 64 + 5 * adj_pad((size_t)nv * sizeof(int)) + adj_pad((size_t)cdiv(nv, ADJ_TILE) * sizeof(int)) + 2 * adj_pad((size_t)nt * 6 * sizeof(int)) +
-           adj_pad((size_t)nv);
+    AdjCarve c;
+    return adj_carve(nullptr, nv, nt, c);
 }
 
 // Pass 1 of the two-call protocol: the whole build into the workspace; returns the number of CSR entries on the HOST (synchronises the stream once --
@@ -253,38 +224,25 @@ int o2345_mesh_adjacency_count(const void* tris, int index_bytes, long long nv, 
     O2345_REQUIRE(n_entries_host && workspace && (nt == 0 || tris), "mesh_adjacency_count: null pointer");
     O2345_REQUIRE(workspace_bytes >= o2345_mesh_adjacency_workspace_bytes(nv, nt), "mesh_adjacency_count: workspace too small");
     O2345_REQUIRE(((uintptr_t)workspace & 15) == 0, "mesh_adjacency_count: workspace must be 16-byte aligned");
-    const AdjCarve c = adj_carve(workspace, nv, nt);
+    AdjCarve c;
+    (void)adj_carve(workspace, nv, nt, c);
     hipStream_t s = (hipStream_t)stream;
     const int n = (int)nv;
     const unsigned gv = cdiv(nv > 0 ? nv : 1, 256), gt = cdiv(nt, 256);
     hipLaunchKernelGGL(k_adj_init, dim3(gv), dim3(256), 0, s, c.cap, n, c.tot);
+    // with no vertex every triangle is out of range: the capacity kernel only counts them
+    if (nt > 0) with_index_type(index_bytes, tris, [&](auto* t) { hipLaunchKernelGGL(k_adj_capacity<index_type<decltype(t)>>, dim3(gt), dim3(256), 0, s, t, nt, n, c.cap, c.tot); });
     if (nv > 0) {
-        if (nt > 0) {
-            if (index_bytes == 4) hipLaunchKernelGGL(k_adj_capacity<int>, dim3(gt), dim3(256), 0, s, (const int*)tris, nt, n, c.cap, c.tot);
-            else hipLaunchKernelGGL(k_adj_capacity<long long>, dim3(gt), dim3(256), 0, s, (const long long*)tris, nt, n, c.cap, c.tot);
-        }
-        hipLaunchKernelGGL(k_tile_sum<ADJ_ITEMS>, dim3(c.nbv), dim3(256), 0, s, c.cap, nv, c.vblock);
-        hipLaunchKernelGGL(k_scan_small<long long>, dim3(1), dim3(1024), 0, s, c.vblock, (int)c.nbv, &c.tot->n_raw);
-        hipLaunchKernelGGL(k_tile_scan<ADJ_ITEMS>, dim3(c.nbv), dim3(256), 0, s, c.cap, nv, c.vblock, c.rawoff, c.cursor);
-        if (nt > 0) {
-            if (index_bytes == 4) hipLaunchKernelGGL(k_adj_fill<int>, dim3(gt), dim3(256), 0, s, (const int*)tris, nt, n, c.cursor, c.raw);
-            else hipLaunchKernelGGL(k_adj_fill<long long>, dim3(gt), dim3(256), 0, s, (const long long*)tris, nt, n, c.cursor, c.raw);
-        }
+        exclusive_scan<SCAN_ITEMS>(c.cap, nv, c.nbv, c.vblock, c.rawoff, c.cursor, &c.tot->n_raw, s);
+        if (nt > 0) with_index_type(index_bytes, tris, [&](auto* t) { hipLaunchKernelGGL(k_adj_fill<index_type<decltype(t)>>, dim3(gt), dim3(256), 0, s, t, nt, n, c.cursor, c.raw); });
         hipLaunchKernelGGL(k_adj_rows, dim3(gv), dim3(256), 0, s, n, c.rawoff, c.cap, c.raw, c.bnd, c.long_list, c.tot);
-        if (nt > 0) hipLaunchKernelGGL(k_adj_long_rows, dim3(ADJ_LONG_GRID), dim3(256), 0, s, c.rawoff, c.cursor, c.cap, c.raw, c.tmp, c.bnd, c.long_list, c.tot);
-        hipLaunchKernelGGL(k_tile_sum<ADJ_ITEMS>, dim3(c.nbv), dim3(256), 0, s, c.cap, nv, c.vblock);
-        hipLaunchKernelGGL(k_scan_small<long long>, dim3(1), dim3(1024), 0, s, c.vblock, (int)c.nbv, &c.tot->n_entries);
-        hipLaunchKernelGGL(k_tile_scan<ADJ_ITEMS>, dim3(c.nbv), dim3(256), 0, s, c.cap, nv, c.vblock, c.off, (int*)nullptr);
-    } else if (nt > 0) {                                            // no vertex: every triangle is out of range
-        if (index_bytes == 4) hipLaunchKernelGGL(k_adj_capacity<int>, dim3(gt), dim3(256), 0, s, (const int*)tris, nt, n, c.cap, c.tot);
-        else hipLaunchKernelGGL(k_adj_capacity<long long>, dim3(gt), dim3(256), 0, s, (const long long*)tris, nt, n, c.cap, c.tot);
+        if (nt > 0) hipLaunchKernelGGL(k_adj_long_rows, dim3(ROW_LONG_GRID), dim3(256), 0, s, c.rawoff, c.cursor, c.cap, c.raw, c.tmp, c.bnd, c.long_list, c.tot);
+        exclusive_scan<SCAN_ITEMS>(c.cap, nv, c.nbv, c.vblock, c.off, nullptr, &c.tot->n_entries, s);
     }
     int rc = check_launch("mesh_adjacency_count");
     if (rc) return rc;
     AdjTotals h;
-    hipError_t e = hipMemcpyAsync(&h, c.tot, sizeof h, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    O2345_REQUIRE(e == hipSuccess, "mesh_adjacency_count: %s", hipGetErrorString(e));
+    if ((rc = read_totals(h, c.tot, s, "mesh_adjacency_count"))) return rc;
     O2345_REQUIRE(h.n_bad == 0, "mesh_adjacency_count: %llu triangles index outside 0 .. %lld", h.n_bad, nv - 1);
     *n_entries_host = h.n_entries;
     return 0;
@@ -295,9 +253,10 @@ int o2345_mesh_adjacency_count(const void* tris, int index_bytes, long long nv, 
 int o2345_mesh_adjacency_emit(void* workspace, long long nv, int* offsets, int* neighbours, unsigned char* boundary, void* stream) {
     O2345_REQUIRE(nv >= 0 && nv < (1ll << 30), "mesh_adjacency_emit: bad sizes");
     O2345_REQUIRE(workspace && offsets && (nv == 0 || boundary), "mesh_adjacency_emit: null pointer");
-    const AdjCarve c = adj_carve(workspace, nv, 0);
+    AdjCarve c;
+    (void)adj_carve(workspace, nv, 0, c);                          // nt = 0: see adj_carve
     const unsigned vertex_blocks = cdiv(nv + 1, 256);
-    hipLaunchKernelGGL(k_adj_emit, dim3(vertex_blocks + ADJ_LONG_GRID), dim3(256), 0, (hipStream_t)stream, (int)nv, vertex_blocks, c.rawoff, c.cursor, c.cap, c.off, c.raw,
+    hipLaunchKernelGGL(k_adj_emit, dim3(vertex_blocks + ROW_LONG_GRID), dim3(256), 0, (hipStream_t)stream, (int)nv, vertex_blocks, c.rawoff, c.cursor, c.cap, c.off, c.raw,
                        c.bnd, c.long_list, c.tot, offsets, neighbours, boundary);
     return check_launch("mesh_adjacency_emit");
 }

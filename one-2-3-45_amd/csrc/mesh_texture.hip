@@ -21,7 +21,7 @@
 //              / W, (cell_y c + v_local) / H) in fp64, rounded once; position and normal are the welded export's for that vertex (mesh_math.h).
 // Bad input never faults: a triangle index outside [0, nv) is read as vertex 0, and it and a non-finite coordinate are counted once per triangle in two
 // integer counters that the caller raises on.  No other atomics.  Nothing here synchronises with the host.
-#include "common.h"
+#include "mesh_common.h"
 #include "mesh_math.h"
 #include <float.h>
 
@@ -96,11 +96,8 @@ __global__ __launch_bounds__(256) void k_tex_points(const double* __restrict__ v
             pworld[3 * e + d] = (float)__dadd_rn(__dmul_rn(__ddiv_rn(y, f.rm1), f.bext[d]), f.bmin[d]);
         }
     }
-    const unsigned long long mb = __ballot(bad), mn = __ballot(nonfinite);
-    if (lane_id() == 0) {
-        if (mb) atomicAdd(&st->n_bad, (unsigned long long)__popcll(mb));
-        if (mn) atomicAdd(&st->n_nonfinite, (unsigned long long)__popcll(mn));
-    }
+    wave_count(bad, &st->n_bad);
+    wave_count(nonfinite, &st->n_nonfinite);
 }
 
 // thread per image texel, raster order: one aligned uchar4 store each
@@ -184,8 +181,9 @@ int o2345_mesh_texture_points(const double* verts, long long nv, const void* tri
     hipStream_t s = (hipStream_t)stream;
     O2345_HIP(hipMemsetAsync(stats, 0, sizeof(TexStats), s));
     const dim3 grid(cdiv(L.texels, 256));
-    if (index_bytes == 8) hipLaunchKernelGGL(k_tex_points<long long>, grid, dim3(256), 0, s, verts, nv, (const long long*)tris, nt, L.c, L.texels, f, points_idx, points_world, (TexStats*)stats);
-    else hipLaunchKernelGGL(k_tex_points<int32_t>, grid, dim3(256), 0, s, verts, nv, (const int32_t*)tris, nt, L.c, L.texels, f, points_idx, points_world, (TexStats*)stats);
+    with_index_type(index_bytes, tris, [&](auto* t) {
+        hipLaunchKernelGGL(k_tex_points<index_type<decltype(t)>>, grid, dim3(256), 0, s, verts, nv, t, nt, L.c, L.texels, f, points_idx, points_world, (TexStats*)stats);
+    });
     return check_launch("mesh_texture_points");
 }
 
@@ -215,8 +213,9 @@ int o2345_mesh_texture_corners(const double* verts, long long nv, const void* tr
     const MeshXform x = mesh_xform(grid_R, bound_min, bound_max, scale_mat, trans_mat);
     const unsigned nb = cdiv(n3, 256);
     hipStream_t s = (hipStream_t)stream;
-    if (index_bytes == 8) hipLaunchKernelGGL(k_tex_corners<long long>, dim3(nb), dim3(256), 0, s, verts, nv, (const long long*)tris, n3, L, x, grad, positions, uv, normals, indices, (float*)workspace);
-    else hipLaunchKernelGGL(k_tex_corners<int32_t>, dim3(nb), dim3(256), 0, s, verts, nv, (const int32_t*)tris, n3, L, x, grad, positions, uv, normals, indices, (float*)workspace);
+    with_index_type(index_bytes, tris, [&](auto* t) {
+        hipLaunchKernelGGL(k_tex_corners<index_type<decltype(t)>>, dim3(nb), dim3(256), 0, s, verts, nv, t, n3, L, x, grad, positions, uv, normals, indices, (float*)workspace);
+    });
     mesh_bounds_finish((const float*)workspace, (long long)nb, bounds, s);
     return check_launch("mesh_texture_corners");
 }

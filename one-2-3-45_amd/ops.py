@@ -773,24 +773,35 @@ def render_core(scene, rays_o, rays_d, z, sample_dist, inv_s, alpha_inter_ratio=
 
 
 # ---------------------------------------------------------------------------------------------------------- marching cubes
+def _triangles(tris, what=None):
+    """A triangle tensor, validated -> (pointer, index_bytes) as the library's entries take them."""
+    if tris.dtype not in (torch.int32, torch.int64) or tris.dim() != 2 or tris.shape[1] != 3:
+        raise ValueError((f"{what}: " if what else "") + f"expected triangles [M,3] int32 or int64, got {tuple(tris.shape)} {tris.dtype}")
+    return _p(tris, tris.dtype), 8 if tris.dtype == torch.int64 else 4
+
+
+def _mesh_frame(bound_min, bound_max, scale_mat, trans_mat):
+    """Bounds (3 numbers each) and the two 4x4 matrices (tensors, arrays or None) -> ([four host pointers or None], the float32 arrays behind them, which
+    the caller keeps alive over the call)."""
+    host = lambda a: None if a is None else np.ascontiguousarray((a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)), np.float32)
+    mat = lambda a: None if a is None else host(a).reshape(-1, 4, 4)[0].copy()
+    keep = [host(bound_min).reshape(3), host(bound_max).reshape(3), mat(scale_mat), mat(trans_mat)]
+    return [None if a is None else a.ctypes.data_as(ctypes.c_void_p) for a in keep], keep
+
+
 @_on_device
 def mesh_pack(verts_idx, tris, grid_R, bound_min=(-1.0, -1.0, -1.0), bound_max=(1.0, 1.0, 1.0), scale_mat=None, trans_mat=None, rgb=None):
     """Index-space vertices (fp64 [N,3]) + triangles -> (vertex records uint8 [N,16|12], face records uint8 [M,13]) of a binary PLY;
     frame transforms and colour quantisation as in trainer_generic.py:1365-1377.  Matrices / bounds are small host arrays."""
     dev = verts_idx.device
     n, m = verts_idx.shape[0], tris.shape[0]
-    host = lambda a: None if a is None else np.ascontiguousarray((a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)), np.float32)
-    bmin, bmax = host(bound_min).reshape(3), host(bound_max).reshape(3)
-    sm, tm = host(scale_mat), host(trans_mat)
-    sm = None if sm is None else sm.reshape(-1, 4, 4)[0].copy()
-    tm = None if tm is None else tm.reshape(-1, 4, 4)[0].copy()
-    cp = lambda a: None if a is None else a.ctypes.data_as(ctypes.c_void_p)
+    frame, _keep = _mesh_frame(bound_min, bound_max, scale_mat, trans_mat)
     vrec = torch.empty(n, 16 if rgb is not None else 12, dtype=torch.uint8, device=dev)
     frec = torch.empty(m, 13, dtype=torch.uint8, device=dev)
     L = _lib.lib()
-    check(L.o2345_mesh_pack_vertices(_p(verts_idx, torch.float64), n, int(grid_R), cp(bmin), cp(bmax), cp(sm), cp(tm), _p(rgb),
+    check(L.o2345_mesh_pack_vertices(_p(verts_idx, torch.float64), n, int(grid_R), *frame, _p(rgb),
                                      _p(vrec, torch.uint8), _stream()), "mesh_pack_vertices")
-    check(L.o2345_mesh_pack_faces(_p(tris, tris.dtype), 8 if tris.dtype == torch.int64 else 4, m, _p(frec, torch.uint8), _stream()), "mesh_pack_faces")
+    check(L.o2345_mesh_pack_faces(*_triangles(tris), m, _p(frec, torch.uint8), _stream()), "mesh_pack_faces")
     return vrec, frec
 
 
@@ -801,12 +812,7 @@ def mesh_asset_pack(verts_idx, tris, grid_R, bound_min=(-1.0, -1.0, -1.0), bound
     bounds float32 [2,3] = per-axis min, max of positions), all on the device.  ``rgb`` fp32 [N,3] in [0,1]; ``grad`` fp32 [N,3], the SDF gradient."""
     dev = verts_idx.device
     n, m = verts_idx.shape[0], tris.shape[0]
-    host = lambda a: None if a is None else np.ascontiguousarray((a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)), np.float32)
-    bmin, bmax = host(bound_min).reshape(3), host(bound_max).reshape(3)
-    sm, tm = host(scale_mat), host(trans_mat)
-    sm = None if sm is None else sm.reshape(-1, 4, 4)[0].copy()
-    tm = None if tm is None else tm.reshape(-1, 4, 4)[0].copy()
-    cp = lambda a: None if a is None else a.ctypes.data_as(ctypes.c_void_p)
+    frame, _keep = _mesh_frame(bound_min, bound_max, scale_mat, trans_mat)
     pos = torch.empty(n, 3, dtype=torch.float32, device=dev)
     rgba = None if rgb is None else torch.empty(n, 4, dtype=torch.uint8, device=dev)
     nrm = None if grad is None else torch.empty(n, 3, dtype=torch.float32, device=dev)
@@ -815,9 +821,9 @@ def mesh_asset_pack(verts_idx, tris, grid_R, bound_min=(-1.0, -1.0, -1.0), bound
     L = _lib.lib()
     wsb = L.o2345_mesh_bounds_workspace_bytes(n)
     ws = _workspace(wsb, dev, "mesh_bounds")
-    check(L.o2345_mesh_asset_vertices(_p(verts_idx, torch.float64), n, int(grid_R), cp(bmin), cp(bmax), cp(sm), cp(tm), _p(rgb), _p(grad), _p(pos),
+    check(L.o2345_mesh_asset_vertices(_p(verts_idx, torch.float64), n, int(grid_R), *frame, _p(rgb), _p(grad), _p(pos),
                                       _p(rgba, torch.uint8), _p(nrm), _p(bounds), _p(ws, torch.uint8), wsb, _stream()), "mesh_asset_vertices")
-    check(L.o2345_mesh_asset_indices(_p(tris, tris.dtype), 8 if tris.dtype == torch.int64 else 4, m, _p(idx, torch.int32), _stream()), "mesh_asset_indices")
+    check(L.o2345_mesh_asset_indices(*_triangles(tris), m, _p(idx, torch.int32), _stream()), "mesh_asset_indices")
     return pos, rgba, nrm, idx, bounds
 
 
@@ -876,21 +882,20 @@ def marching_cubes(u, iso=0.0, index_dtype=torch.int64):
     verts = torch.empty(nv.value, 3, dtype=torch.float64, device=u.device)
     tris = torch.empty(nt.value, 3, dtype=index_dtype, device=u.device)
     check(L.o2345_marching_cubes_emit(_p(u), n0, n1, n2, float(iso), _p(ws, torch.uint8), _p(verts, torch.float64),
-                                      _p(tris, index_dtype), 8 if index_dtype == torch.int64 else 4, _stream()), "marching_cubes_emit")
+                                      *_triangles(tris), _stream()), "marching_cubes_emit")
     return verts, tris
 
 
 # ---------------------------------------------------------------------------------------------------------- mesh components
 def _mesh_components_count(tris, nv, min_faces, keep_largest, labels):
     """Pass 1 of the two-call protocol -> (workspace, components, components_kept, nv_kept, nt_kept)."""
-    if tris.dtype not in (torch.int32, torch.int64) or tris.dim() != 2 or tris.shape[1] != 3:
-        raise ValueError(f"expected triangles [M,3] int32 or int64, got {tuple(tris.shape)} {tris.dtype}")
+    tp, ib = _triangles(tris)
     L = _lib.lib()
     nt = tris.shape[0]
     wsb = L.o2345_mesh_components_workspace_bytes(nv, nt)
     ws = _workspace(wsb, tris.device, "mesh_components")
     nc, nck, nvk, ntk = (ctypes.c_longlong() for _ in range(4))
-    check(L.o2345_mesh_components_count(_p(tris, tris.dtype), 8 if tris.dtype == torch.int64 else 4, nv, nt, min(int(min_faces), 2 ** 31 - 1), int(bool(keep_largest)),
+    check(L.o2345_mesh_components_count(tp, ib, nv, nt, min(int(min_faces), 2 ** 31 - 1), int(bool(keep_largest)),
                                         _p(ws, torch.uint8), wsb, _p(labels, torch.int32), ctypes.byref(nc), ctypes.byref(nck), ctypes.byref(nvk),
                                         ctypes.byref(ntk), _stream()), "mesh_components_count")
     return ws, nc.value, nck.value, nvk.value, ntk.value
@@ -920,7 +925,7 @@ def mesh_filter_components(verts_idx, tris, min_faces=0, keep_largest=False):
     verts = torch.empty(nvk, 3, dtype=torch.float64, device=dev)
     tris_out = torch.empty(ntk, 3, dtype=tris.dtype, device=dev)
     kept = torch.empty(nvk, dtype=torch.int32, device=dev)
-    check(_lib.lib().o2345_mesh_components_emit(_p(verts_idx, torch.float64), _p(tris, tris.dtype), 8 if tris.dtype == torch.int64 else 4, nv, tris.shape[0],
+    check(_lib.lib().o2345_mesh_components_emit(_p(verts_idx, torch.float64), *_triangles(tris), nv, tris.shape[0],
                                                 _p(ws, torch.uint8), _p(verts, torch.float64), _p(tris_out, tris.dtype), _p(kept, torch.int32), _stream()),
           "mesh_components_emit")
     return verts, tris_out, kept, {"components": nc, "components_kept": nck}
@@ -932,14 +937,13 @@ def mesh_vertex_adjacency(tris, n_vertices):
     """tris [M,3] int32 / int64 on the device -> (offsets int32 [n + 1], neighbours int32 [E], boundary uint8 [n]): the vertex -> neighbours table in CSR
     form, rows ascending, and the flag of the vertices on an edge with one triangle (== mesh_io.vertex_adjacency, exactly; definitions in
     csrc/mesh_smooth.hip)."""
-    if tris.dtype not in (torch.int32, torch.int64) or tris.dim() != 2 or tris.shape[1] != 3:
-        raise ValueError(f"expected triangles [M,3] int32 or int64, got {tuple(tris.shape)} {tris.dtype}")
+    tp, ib = _triangles(tris)
     L = _lib.lib()
     nv, nt, dev = int(n_vertices), tris.shape[0], tris.device
     wsb = L.o2345_mesh_adjacency_workspace_bytes(nv, nt)
     ws = _workspace(wsb, dev, "mesh_adjacency")
     ne = ctypes.c_longlong()
-    check(L.o2345_mesh_adjacency_count(_p(tris, tris.dtype), 8 if tris.dtype == torch.int64 else 4, nv, nt, _p(ws, torch.uint8), wsb, ctypes.byref(ne), _stream()),
+    check(L.o2345_mesh_adjacency_count(tp, ib, nv, nt, _p(ws, torch.uint8), wsb, ctypes.byref(ne), _stream()),
           "mesh_adjacency_count")
     offsets = torch.empty(nv + 1, dtype=torch.int32, device=dev)
     neighbours = torch.empty(ne.value, dtype=torch.int32, device=dev)
@@ -980,21 +984,20 @@ def mesh_decimate(verts_idx, tris, cell=None):
     cell = config.mesh_decimate_cell(cell)
     if cell == 0.0:
         return verts_idx, tris, None, None
-    if tris.dtype not in (torch.int32, torch.int64) or tris.dim() != 2 or tris.shape[1] != 3:
-        raise ValueError(f"expected triangles [M,3] int32 or int64, got {tuple(tris.shape)} {tris.dtype}")
+    tp, ib = _triangles(tris)
     if verts_idx.dtype != torch.float64 or verts_idx.dim() != 2 or verts_idx.shape[1] != 3:
         raise ValueError(f"expected vertices [N,3] float64, got {tuple(verts_idx.shape)} {verts_idx.dtype}")
     L = _lib.lib()
-    nv, nt, dev, ib = verts_idx.shape[0], tris.shape[0], verts_idx.device, 8 if tris.dtype == torch.int64 else 4
+    nv, nt, dev = verts_idx.shape[0], tris.shape[0], verts_idx.device
     wsb = L.o2345_mesh_decimate_workspace_bytes(nv, nt)
     ws = _workspace(wsb, dev, "mesh_decimate")
     ncl, nvo, nto, ndeg, ndup = (ctypes.c_longlong() for _ in range(5))
-    check(L.o2345_mesh_decimate_count(_p(verts_idx, torch.float64), _p(tris, tris.dtype), ib, nv, nt, cell, _p(ws, torch.uint8), wsb, ctypes.byref(ncl),
+    check(L.o2345_mesh_decimate_count(_p(verts_idx, torch.float64), tp, ib, nv, nt, cell, _p(ws, torch.uint8), wsb, ctypes.byref(ncl),
                                       ctypes.byref(nvo), ctypes.byref(nto), ctypes.byref(ndeg), ctypes.byref(ndup), _stream()), "mesh_decimate_count")
     verts = torch.empty(nvo.value, 3, dtype=torch.float64, device=dev)
     tris_out = torch.empty(nto.value, 3, dtype=tris.dtype, device=dev)
     cluster = torch.empty(nv, dtype=torch.int32, device=dev)
-    check(L.o2345_mesh_decimate_emit(_p(verts_idx, torch.float64), _p(tris, tris.dtype), ib, nv, nt, _p(ws, torch.uint8), _p(verts, torch.float64),
+    check(L.o2345_mesh_decimate_emit(_p(verts_idx, torch.float64), tp, ib, nv, nt, _p(ws, torch.uint8), _p(verts, torch.float64),
                                      _p(tris_out, tris.dtype), _p(cluster, torch.int32), _stream()), "mesh_decimate_emit")
     return verts, tris_out, cluster, {"clusters": ncl.value, "vertices": nvo.value, "triangles": nto.value, "degenerate": ndeg.value, "duplicate": ndup.value}
 
@@ -1052,12 +1055,12 @@ _TEXTURE_STATS_BYTES = 16           # include/o2345.h: uint64 [2]
 
 
 def _texture_mesh(verts_idx, tris, what):
-    if tris.dtype not in (torch.int32, torch.int64) or tris.dim() != 2 or tris.shape[1] != 3:
-        raise ValueError(f"{what}: expected triangles [M,3] int32 or int64, got {tuple(tris.shape)} {tris.dtype}")
+    t = _triangles(tris, what)
     if verts_idx.dtype != torch.float64 or verts_idx.dim() != 2 or verts_idx.shape[1] != 3:
         raise ValueError(f"{what}: expected vertices [N,3] float64, got {tuple(verts_idx.shape)} {verts_idx.dtype}")
     if verts_idx.shape[0] < 1:
         raise ValueError(f"{what}: a mesh with triangles has vertices")
+    return t
 
 
 def texture_check(stats):
@@ -1076,7 +1079,7 @@ def mesh_texture_points(verts_idx, tris, texel, resolution, bound_min=(-1.0, -1.
     world fp32 [cells c^2, 3], stats uint8 [16]), cell-major; the inputs are not written.  ``validate`` copies the counters to the host (one
     synchronisation) and raises on a non-finite coordinate or a triangle index out of range; a caller that queues more work passes False and hands the
     counters to texture_check after its own copy."""
-    _texture_mesh(verts_idx, tris, "mesh_texture_points")
+    tp, ib = _texture_mesh(verts_idx, tris, "mesh_texture_points")
     lay = mesh_io.texture_layout(tris.shape[0], texel)
     if isinstance(resolution, bool) or int(resolution) != resolution or resolution < 2:
         raise ValueError(f"mesh_texture_points: resolution must be an integer >= 2, got {resolution!r}")
@@ -1089,7 +1092,7 @@ def mesh_texture_points(verts_idx, tris, texel, resolution, bound_min=(-1.0, -1.
     pts = torch.empty(n, 3, dtype=torch.float64, device=dev)
     world = torch.empty(n, 3, dtype=torch.float32, device=dev)
     stats = torch.empty(_TEXTURE_STATS_BYTES, dtype=torch.uint8, device=dev)
-    check(L.o2345_mesh_texture_points(_p(verts_idx, torch.float64), verts_idx.shape[0], _p(tris, tris.dtype), 8 if tris.dtype == torch.int64 else 4, tris.shape[0],
+    check(L.o2345_mesh_texture_points(_p(verts_idx, torch.float64), verts_idx.shape[0], tp, ib, tris.shape[0],
                                        lay["texel"], int(resolution), pmin, pmax, _p(pts, torch.float64), _p(world), _p(stats, torch.uint8), _stream()),
            "mesh_texture_points")
     if validate:
@@ -1113,17 +1116,12 @@ def mesh_texture_corners(verts_idx, tris, texel, grid_R, bound_min=(-1.0, -1.0, 
     """The unwelded vertices of the textured asset (== mesh_io.texture_corners, to the last bit): (positions float32 [3M,3] in the asset frame, uv float32
     [3M,2], normals float32 [3M,3] or None, indices uint32-valued int32 storage [M,3] = 0, 1, 2, ..., bounds float32 [2,3]), all on the device.
     ``grad`` fp32 [N,3]: the SDF gradient at the (welded) vertices."""
-    _texture_mesh(verts_idx, tris, "mesh_texture_corners")
+    tp, ib = _texture_mesh(verts_idx, tris, "mesh_texture_corners")
     lay = mesh_io.texture_layout(tris.shape[0], texel)
     dev, m = verts_idx.device, tris.shape[0]
     if grad is not None and tuple(grad.shape) != (verts_idx.shape[0], 3):
         raise ValueError(f"mesh_texture_corners: expected gradients [{verts_idx.shape[0]}, 3], got {tuple(grad.shape)}")
-    host = lambda a: None if a is None else np.ascontiguousarray((a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)), np.float32)
-    bmin, bmax = host(bound_min).reshape(3), host(bound_max).reshape(3)
-    sm, tm = host(scale_mat), host(trans_mat)
-    sm = None if sm is None else sm.reshape(-1, 4, 4)[0].copy()
-    tm = None if tm is None else tm.reshape(-1, 4, 4)[0].copy()
-    cp = lambda a: None if a is None else a.ctypes.data_as(ctypes.c_void_p)
+    frame, _keep = _mesh_frame(bound_min, bound_max, scale_mat, trans_mat)
     pos = torch.empty(3 * m, 3, dtype=torch.float32, device=dev)
     uv = torch.empty(3 * m, 2, dtype=torch.float32, device=dev)
     nrm = None if grad is None else torch.empty(3 * m, 3, dtype=torch.float32, device=dev)
@@ -1132,8 +1130,8 @@ def mesh_texture_corners(verts_idx, tris, texel, grid_R, bound_min=(-1.0, -1.0, 
     L = _lib.lib()
     wsb = L.o2345_mesh_bounds_workspace_bytes(3 * m)
     ws = _workspace(wsb, dev, "mesh_bounds")
-    check(L.o2345_mesh_texture_corners(_p(verts_idx, torch.float64), verts_idx.shape[0], _p(tris, tris.dtype), 8 if tris.dtype == torch.int64 else 4, m, lay["texel"],
-                                        int(grid_R), cp(bmin), cp(bmax), cp(sm), cp(tm), _p(grad), _p(pos), _p(uv), _p(nrm), _p(idx, torch.int32), _p(bounds),
+    check(L.o2345_mesh_texture_corners(_p(verts_idx, torch.float64), verts_idx.shape[0], tp, ib, m, lay["texel"],
+                                        int(grid_R), *frame, _p(grad), _p(pos), _p(uv), _p(nrm), _p(idx, torch.int32), _p(bounds),
                                         _p(ws, torch.uint8), wsb, _stream()), "mesh_texture_corners")
     return pos, uv, nrm, idx, bounds
 

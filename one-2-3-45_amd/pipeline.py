@@ -186,6 +186,19 @@ def render_scene_split(wt, imgs, affine_mats, origin, D, voxel_size, proj, cam_p
     return sh.gather_ray_blocks(block, rays_o.shape[0], per, device=dev), vol
 
 
+def _index_to_world(idx, resolution):
+    return idx / (resolution - 1.0) * 2.0 - 1.0                               # sparse_neus_renderer.py:936: index coordinates -> [-1, 1]
+
+
+def _colours_at(wt, vol, proj, cam_pos, pts):
+    """SDF gradient, and the colour network with it as the normal input, at float32 world points [N,3] -> (rgb, grad)"""
+    g = ops.sdf_mlp(wt.sdf_blob, vol["vol_cl"], pts, variant=2, precision=wt.sdf_precision)["grad"]
+    x3 = wt.color_precision == "f16x3"
+    rgb, _ = ops.color_points(wt.color_xblob if x3 else wt.color_mblob, vol["vol_cl"], vol["maskvol"], vol["cmaps"], proj, cam_pos, pts, normals=g,
+                              want_nviews=False, mfma="x3" if x3 else True)
+    return rgb, g
+
+
 def _mesh_fields(wt, vol, proj, cam_pos, resolution, min_component_faces=None, keep_largest=None, info=None, smooth_iterations=None, decimate_cell=None,
                  project_iterations=None, texture=None):
     """The device work of extract_mesh, once: (verts fp64 in [-1, 1], verts_idx fp64 index coordinates, tris, rgb, u, grad).  ``grad`` is the SDF gradient
@@ -231,27 +244,22 @@ def _mesh_fields(wt, vol, proj, cam_pos, resolution, min_component_faces=None, k
         info["components"], info["components_kept"] = (cc["components"], cc["components_kept"]) if cc else (None, None)
         info["decimate"] = dec
         info["project"] = pro
-    verts = (verts_idx / (resolution - 1.0) * 2.0 - 1.0)                      # sparse_neus_renderer.py:936
+    verts = _index_to_world(verts_idx, resolution)
     pts = verts.to(torch.float32).contiguous()
     if pts.shape[0] == 0:
         return verts, verts_idx, tris, torch.zeros(0, 3, device=pts.device), u, None
-    g = ops.sdf_mlp(wt.sdf_blob, vol["vol_cl"], pts, variant=2, precision=prec)["grad"]
-    x3 = wt.color_precision == "f16x3"
-    rgb, _ = ops.color_points(wt.color_xblob if x3 else wt.color_mblob, vol["vol_cl"], vol["maskvol"], vol["cmaps"], proj, cam_pos, pts, normals=g,
-                              want_nviews=False, mfma="x3" if x3 else True)
+    rgb, g = _colours_at(wt, vol, proj, cam_pos, pts)
     if texture is not None and tris.shape[0]:
         tpts, tworld, tstats = ops.mesh_texture_points(verts_idx, tris, texture["texel"], resolution, validate=False)
         tpro = None
         if project:
             tpts, tpro = ops.mesh_project(wt.sdf_blob, vol["vol_cl"], tpts, resolution, project, max_move=config.mesh_project_max_move(None, cell), precision=prec)
-            tworld = (tpts / (resolution - 1.0) * 2.0 - 1.0).to(torch.float32).contiguous()
-        tg = ops.sdf_mlp(wt.sdf_blob, vol["vol_cl"], tworld, variant=2, precision=prec)["grad"]
-        trgb, _ = ops.color_points(wt.color_xblob if x3 else wt.color_mblob, vol["vol_cl"], vol["maskvol"], vol["cmaps"], proj, cam_pos, tworld, normals=tg,
-                                   want_nviews=False, mfma="x3" if x3 else True)
+            tworld = _index_to_world(tpts, resolution).to(torch.float32).contiguous()
+        trgb, _ = _colours_at(wt, vol, proj, cam_pos, tworld)
         texture.update(rgb=trgb, stats=tstats, project=tpro, layout=ops.mesh_io.texture_layout(tris.shape[0], texture["texel"]))
     if smooth:
         verts_idx = ops.mesh_smooth(verts_idx, tris, smooth)
-        verts = (verts_idx / (resolution - 1.0) * 2.0 - 1.0)
+        verts = _index_to_world(verts_idx, resolution)
     return verts, verts_idx, tris, rgb, u, g
 
 

@@ -82,6 +82,26 @@ def test_render_workspace_size_is_pinned(lib_instance):
     assert lib_instance({"O2345_RAY_STREAM_MIN": "1"}).o2345_render_workspace_bytes(512, 64, 64, 8) == 2236928
 
 
+def test_mesh_workspace_sizes_are_pinned():
+    """Every mesh unit has one function that walks its workspace layout (a Carver, csrc/mesh_common.h); o2345_*_workspace_bytes is that walk on a null
+    base.  The expected sizes were recorded from the library at commit 6d6058e, where components, adjacency and marching cubes had hand-written sums
+    next to their carving code: empty and one-element meshes, sizes around the scan tile (2048 vertices, 4096 triangles: one more int of block totals,
+    and for decimation the next power of two of the hash tables), the config-2 mesh, and the shapes every unit refuses with 0."""
+    lib = importlib.import_module("one-2-3-45_amd._lib").lib()
+    mesh = {(0, 0): (64, 64, 160, 16), (1, 1): (160, 240, 416, 80), (1000, 2000): (20096, 117088, 109120, 36000),
+            (2047, 4095): (41056, 239664, 221344, 73728), (2048, 4096): (41056, 239696, 221344, 73728), (2049, 4097): (41120, 239856, 303488, 73808),
+            (207728, 418240): (4167008, 24438288, 24646048, 7478208)}
+    for (nv, nt), want in mesh.items():
+        got = (lib.o2345_mesh_components_workspace_bytes(nv, nt), lib.o2345_mesh_adjacency_workspace_bytes(nv, nt),
+               lib.o2345_mesh_decimate_workspace_bytes(nv, nt), lib.o2345_mesh_project_workspace_bytes(nv))
+        assert got == want, (nv, nt)
+    grids = {(2, 2, 2): 200, (3, 5, 7): 1280, (64, 64, 64): 2884704, (256, 256, 256): 184615008}
+    for shape, size in grids.items():
+        assert lib.o2345_mc_workspace_bytes(*shape) == size, shape
+    assert lib.o2345_mesh_decimate_workspace_bytes(2 ** 30, 0) == 0 and lib.o2345_mesh_decimate_workspace_bytes(-1, 0) == 0
+    assert lib.o2345_mesh_adjacency_workspace_bytes(2 ** 30, 0) == 0 and lib.o2345_mesh_components_workspace_bytes(-1, 0) == 0
+
+
 def test_render_io_has_one_declaration_and_the_binding_checks_it(tmp_path):
     """O2345RenderIO is declared in include/o2345.h only: csrc/ compiles that header (common.h includes it), the ctypes Structure is generated from its
     text, and the loaded library's own sizeof / offsetof table is compared at load time.  A field added to ONE side only must fail loudly."""

@@ -143,6 +143,41 @@ def test_strip_and_fans(dev, dtype):
     assert info["clusters"] > 1 and info["vertices"] == 0
 
 
+ROW_SIZES = [1, 2, 3, 4, 5, 15, 16, 17, 31, 32, 33, 34, 65]    # around the register networks of 4, 16 and 32 members, and the first rows of the block sort
+
+
+def _sequential_sum(x):
+    acc = np.float64(0.0)
+    for v in x:
+        acc = acc + v
+    return acc
+
+
+@pytest.fixture(scope="module")
+def row_mesh():
+    """258 vertices in 13 clusters of ROW_SIZES members, cluster k in the cell at x = 2k; the vertex indices are shuffled, so the members of a
+    cluster lie all over the index range and reach their row in any order; the offsets inside a cell have random mantissas over four binades, so a cluster's fp64 sum depends on the order of its
+    members; one triangle over every three consecutive clusters keeps all of them.  -> (vertices, triangles, the twin's result)"""
+    rng = np.random.default_rng(13)
+    owner = rng.permutation(np.repeat(np.arange(len(ROW_SIZES)), ROW_SIZES))
+    hv = rng.uniform(0.5, 1.0, (owner.size, 3)) * 2.0 ** -rng.integers(0, 4, (owner.size, 3))
+    hv[:, 0] += 2.0 * owner
+    first = np.array([np.flatnonzero(owner == k)[0] for k in range(len(ROW_SIZES))], np.int64)
+    hf = np.stack([first[:-2], first[1:-1], first[2:]], 1)
+    rows = [np.flatnonzero(owner == k) for k in range(len(ROW_SIZES)) if ROW_SIZES[k] >= 15]
+    assert any(_sequential_sum(hv[r, d]) != _sequential_sum(hv[r[::-1], d]) for r in rows for d in range(3))       # the order is visible in the result
+    return hv, hf, mio.decimate_mesh(hv, hf, 1.0)
+
+
+@pytest.mark.parametrize("dtype", [torch.int32, torch.int64])
+def test_member_rows_around_the_register_sort_limits(dev, row_mesh, dtype):
+    hv, hf, twin = row_mesh
+    cluster, info = twin[3], twin[4]
+    assert np.sort(np.bincount(cluster[cluster >= 0])).tolist() == ROW_SIZES and (cluster >= 0).all()
+    assert info == {"clusters": len(ROW_SIZES), "vertices": len(ROW_SIZES), "triangles": len(ROW_SIZES) - 2, "degenerate": 0, "duplicate": 0}
+    _check(hv, hf, dev, dtype, 1.0, want=twin)
+
+
 def test_two_runs_and_a_second_stream_give_identical_bytes(dev, closed_mesh):
     verts, tris = torch.from_numpy(closed_mesh["hv"].copy()).to(dev), _dev_tris(closed_mesh["hf"], dev, torch.int64)
     torch.cuda.synchronize()
