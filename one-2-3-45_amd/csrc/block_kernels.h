@@ -81,6 +81,19 @@ __device__ __forceinline__ void abn_scale_shift(double s, double q, double count
     if (mean_var) { mean_var[c] = (float)mean; mean_var[C + c] = (float)var; }
 }
 
+// A producer's InPlaceABN applied by its consumer on load: leaky ReLU of t = x * scale + shift, in the two spellings the library's kernels were written
+// with.  For 0 <= slope < 1 (every caller: 0 or 0.01) they agree in value on every non-NaN t, signed zeros included: t >= 0 gives t * slope <= t with
+// the product keeping t's sign, t < 0 gives t * slope >= t.  They compile to different instructions (v_mul + v_max against v_cmp + v_mul + v_cndmask),
+// so each site keeps the one it was tuned with.
+__device__ __forceinline__ float abn_act_max(float x, float scale, float shift, float slope) {        // the matrix-core convolutions' staging
+    const float t = x * scale + shift;
+    return fmaxf(t, t * slope);
+}
+__device__ __forceinline__ float abn_act_select(float x, float scale, float shift, float slope) {     // the fp32 kernels
+    const float t = x * scale + shift;
+    return t >= 0.f ? t : t * slope;
+}
+
 namespace {
 
 // exclusive scan of n ints in place by ONE 1024-thread block (n <= a few 100k block totals); *total = the sum
@@ -157,8 +170,7 @@ __global__ __launch_bounds__(256) void k_nchw_to_nhwc(const float* __restrict__ 
         if (p0 + p < HW) {
             t = src[(size_t)c * HW + p0 + p];
             if (ACT) {
-                t = t * ss[c] + ss[C + c];
-                t = t >= 0.f ? t : t * slope;
+                t = abn_act_select(t, ss[c], ss[C + c], slope);
                 if (y_nchw) y_nchw[((size_t)v * C + c) * HW + p0 + p] = t;
             }
         }

@@ -2,7 +2,7 @@
 // `FeatureNet`; models/sparse_sdf_network.py:171-173 `compress_layer`).  nn.Conv2d + InPlaceABN pairs become ONE pass per layer:
 //
 //   * the convolution reads the RAW output of the previous convolution and applies that layer's batch-norm + leaky ReLU while it stages
-//     the input tile in LDS (y = max(t, slope t), t = x scale + shift -- the same arithmetic as k_nchw_to_nhwc<C, true> of block_kernels.h);
+//     the input tile in LDS (abn_act_max / abn_act_select of block_kernels.h);
 //   * it writes its own raw output once and, for layers followed by InPlaceABN, the per-channel sum / sum of squares of its tile
 //     (fp32 inside a wave, doubles across waves and blocks, fixed order: deterministic);  k_conv_stats_finish turns them into the
 //     (scale, shift) pair the NEXT kernel applies on load.  The activated tensor is never materialised unless a caller asks for it.
@@ -33,6 +33,17 @@ struct ConvArgs {
 };
 
 constexpr int CV_TX = 32, CV_TH = 8;          // threads of a block: 32 x 8; a thread owns PX horizontally adjacent output pixels
+
+// the four waves' sums of a block's tile, red[wave][channel][sum | sum of squares], in a fixed order -> the block's slot of `part` for channels
+// c0 .. c0 + nch - 1 of view v
+template <int NCH>
+__device__ __forceinline__ void conv_part_write(double* part, int nblk, const double (*red)[NCH][2], int nch, int c0, int v) {
+    if (threadIdx.x < 2 * nch) {
+        const int co = threadIdx.x >> 1, k = threadIdx.x & 1;
+        const double t = (red[0][co][k] + red[1][co][k]) + (red[2][co][k] + red[3][co][k]);
+        part[((size_t)(c0 + co) * nblk + (size_t)v * gridDim.x + blockIdx.x) * 2 + k] = t;
+    }
+}
 
 // CPB: output channels per block (blockIdx.z selects the group); CC: input channels per LDS stage; PX: output pixels per thread.
 // Inside a stage a thread first pulls the input patch of one channel row out of LDS into registers and then runs the FMAs of that row with the
@@ -67,10 +78,7 @@ __global__ __launch_bounds__(256) void k_conv2d(ConvArgs a) {
             float t = 0.f;                                                     // zero padding applies to the ACTIVATED input
             if (gy >= 0 && gy < a.Hi && gx >= 0 && gx < a.Wi) {
                 t = src[(size_t)(c0 + c) * a.chan_stride + ((size_t)gy * a.Wi + gx) * a.pix_stride];
-                if (a.in_ss) {
-                    t = t * a.in_ss[c0 + c] + a.in_ss[CIN + c0 + c];
-                    t = t >= 0.f ? t : t * a.slope;
-                }
+                if (a.in_ss) t = abn_act_select(t, a.in_ss[c0 + c], a.in_ss[CIN + c0 + c], a.slope);
             }
             tile[c][iy][ix] = t;
         }
@@ -135,11 +143,7 @@ __global__ __launch_bounds__(256) void k_conv2d(ConvArgs a) {
         if (lane == 0) { red[wave][co][0] = (double)s; red[wave][co][1] = (double)q; }
     }
     __syncthreads();
-    if (threadIdx.x < CPB * 2) {
-        const int co = threadIdx.x >> 1, k = threadIdx.x & 1;
-        const double t = (red[0][co][k] + red[1][co][k]) + (red[2][co][k] + red[3][co][k]);
-        a.part[((size_t)(cg * CPB + co) * a.nblk + (size_t)v * gridDim.x + blockIdx.x) * 2 + k] = t;
-    }
+    conv_part_write(a.part, a.nblk, red, CPB, cg * CPB, v);
 }
 
 // one block per channel: batch statistics -> (scale, shift) of InPlaceABN (|gamma| + eps convention selectable, as in sparse.hip)
@@ -167,13 +171,21 @@ __global__ void k_conv_pack(const float* __restrict__ w, int cout, int cin, int 
 // channels: activation (the producer's ABN, on load) and the f16 split happen ONCE per staged value, the halves go to LDS as 16-byte items
 // [hi|lo][channel octet][pixel] so that a B operand is one conflict-free ds_read_b128; one barrier, then the wave runs its K*K*CINP/16 steps.
 // The A operands (weights, [tap][group][hi|lo][64 lanes][8 f16], packed by k_conv_pack_x3) stream from L2 through a buffer descriptor a few
-// steps ahead -- 2 KB per step, identical for every wave of the grid.
-struct AOpX { h16x8 hi, lo; };
-__device__ __forceinline__ AOpX conv_a_fetch(__amdgpu_buffer_rsrc_t rs, int step, int lane) {
-    AOpX r;
-    r.hi = __builtin_bit_cast(h16x8, __builtin_amdgcn_raw_buffer_load_b128(rs, lane * 16, step * 2048, 0));
-    r.lo = __builtin_bit_cast(h16x8, __builtin_amdgcn_raw_buffer_load_b128(rs, lane * 16, step * 2048 + 1024, 0));
-    return r;
+// steps ahead -- 2 KB per step, identical for every wave of the grid (AOp<1> / a_fetch<1> of split_f16.h).
+// The two kernels below share conv_x3_channel, conv_x3_load_ssl, abn_act_max, split8, mfma_x3<1> and conv_part_write.  Their index prologue, source-pixel
+// set-up and epilogue (bias, store, wave tree) are written out in both: as device functions they changed the kernels' register allocation (DESIGN.md,
+// "Volume front end").  A change to one of those blocks goes into both kernels.
+
+// register q = 4g + i of a lane holds output channel 8g + 4h + i of pixel column j (the accumulator layout of v_mfma_f32_32x32x16_f16)
+__device__ __forceinline__ int conv_x3_channel(int q, int h) { return 8 * (q >> 2) + 4 * h + (q & 3); }
+
+// the producer's (scale | shift), zero beyond cin: read once per staged value, kept in LDS
+template <int CINP>
+__device__ __forceinline__ void conv_x3_load_ssl(const float* in_ss, int cin, float (&ssl)[2][CINP]) {
+    if (in_ss && threadIdx.x < 2 * CINP) {
+        const int k = threadIdx.x / CINP, c = threadIdx.x % CINP;
+        ssl[k][c] = c < cin ? in_ss[k * cin + c] : 0.f;
+    }
 }
 
 template <int CINP, int K, int STRIDE, int ROWS>
@@ -183,11 +195,8 @@ __global__ __launch_bounds__(256) void k_conv2d_x3(ConvArgs a, int cin, int cout
     __shared__ float4 plane[2][2 * NU][NPIX];                                     // [hi | lo][channel octet][pixel]: a B operand is one 16-byte item
     static_assert(sizeof(plane) >= 4 * 32 * 2 * sizeof(double), "the statistics scratch reuses the tile memory");
     double (*red)[32][2] = reinterpret_cast<double (*)[32][2]>(&plane[0][0][0]);  // [wave][channel][sum | sum of squares], after the MFMAs
-    __shared__ float ssl[2][CINP];                                                // the producer's (scale | shift): read per staged value, kept in LDS
-    if (a.in_ss && threadIdx.x < 2 * CINP) {
-        const int k = threadIdx.x / CINP, c = threadIdx.x % CINP;
-        ssl[k][c] = c < cin ? a.in_ss[k * cin + c] : 0.f;
-    }
+    __shared__ float ssl[2][CINP];
+    conv_x3_load_ssl(a.in_ss, cin, ssl);
     const int lane = threadIdx.x & 63, j = lane & 31, h = lane >> 5, wave = threadIdx.x >> 6;
     const int bx = blockIdx.x % a.nbx, by = blockIdx.x / a.nbx, v = blockIdx.y;
     const int ox = bx * 32 + j, oy0 = by * TH + wave * ROWS;
@@ -225,17 +234,12 @@ __global__ __launch_bounds__(256) void k_conv2d_x3(ConvArgs a, int cin, int cout
                     for (int t = 0; t < 8; ++t) {
                         const int c = 8 * oct + t;
                         float val = pre[jj][c];
-                        if (a.in_ss) {
-                            val = val * ssl[0][c] + ssl[1][c];
-                            val = fmaxf(val, val * a.slope);                     // leaky ReLU, 0 <= slope < 1
-                        }
+                        if (a.in_ss) val = abn_act_max(val, ssl[0][c], ssl[1][c], a.slope);
                         x[t] = (pix_in[jj] && c < cin) ? val : 0.f;
                     }
-                    union { h16x2 v2[4]; float4 f4; } bh, bl;
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) split_pair(x[2 * q], x[2 * q + 1], m1, bh.v2[q], bl.v2[q]);
-                    plane[0][oct][r] = bh.f4;
-                    plane[1][oct][r] = bl.f4;
+                    const Split8 b = split8(x, 0, m1);
+                    plane[0][oct][r] = __builtin_bit_cast(float4, b.hi);
+                    plane[1][oct][r] = __builtin_bit_cast(float4, b.lo);
                 }
             }
         }
@@ -243,9 +247,9 @@ __global__ __launch_bounds__(256) void k_conv2d_x3(ConvArgs a, int cin, int cout
     // ---- k steps (tap, channel group) in the order of the operand records; the A operands stream from L2 PD steps ahead (nothing else is in
     //      flight on the vector-memory counter, so a wait for one record waits for nothing else)
     constexpr int NS = K * K * NU, PD = NS < 4 ? NS : 4;
-    AOpX abuf[PD];
+    AOp<1> abuf[PD];
 #pragma unroll
-    for (int st = 0; st < PD; ++st) abuf[st] = conv_a_fetch(rs, st, lane);
+    for (int st = 0; st < PD; ++st) abuf[st] = a_fetch<1>(rs, st, lane);
     f32x16 acc[ROWS];
 #pragma unroll
     for (int r = 0; r < ROWS; ++r)
@@ -254,25 +258,21 @@ __global__ __launch_bounds__(256) void k_conv2d_x3(ConvArgs a, int cin, int cout
     __syncthreads();                                                             // the tile is staged
 #pragma unroll
     for (int st = 0; st < NS; ++st) {
-        const AOpX A = abuf[st % PD];
-        if (st + PD < NS) abuf[st % PD] = conv_a_fetch(rs, st + PD, lane);
+        const AOp<1> A = abuf[st % PD];
+        if (st + PD < NS) abuf[st % PD] = a_fetch<1>(rs, st + PD, lane);
         const int tap = st / NU, u = st % NU, ky = tap / K, kx = tap % K;
 #pragma unroll
         for (int r = 0; r < ROWS; ++r) {
             const int pix = ((wave * ROWS + r) * STRIDE + ky) * IW + j * STRIDE + kx;
-            const h16x8 bh = __builtin_bit_cast(h16x8, plane[0][2 * u + h][pix]), bl = __builtin_bit_cast(h16x8, plane[1][2 * u + h][pix]);
-            acc[r] = MFMA_F16(A.lo, bh, acc[r]);
-            acc[r] = MFMA_F16(A.hi, bl, acc[r]);
-            acc[r] = MFMA_F16(A.hi, bh, acc[r]);
+            mfma_x3<1>(&acc[r], A.hi, A.lo, Split8{__builtin_bit_cast(h16x8, plane[0][2 * u + h][pix]), __builtin_bit_cast(h16x8, plane[1][2 * u + h][pix])});
         }
     }
-    // register 4g + i of a lane holds output channel 8g + 4h + i of pixel column j
     float s[16], q2[16], bv[16];
 #pragma unroll
     for (int q = 0; q < 16; ++q) { s[q] = 0.f; q2[q] = 0.f; bv[q] = 0.f; }
     if (a.bias) {                                                                // all 16 loads in flight together (clamped index: no branch per value)
 #pragma unroll
-        for (int q = 0; q < 16; ++q) bv[q] = a.bias[min(8 * (q >> 2) + 4 * h + (q & 3), cout - 1)];
+        for (int q = 0; q < 16; ++q) bv[q] = a.bias[min(conv_x3_channel(q, h), cout - 1)];
     }
 #pragma unroll
     for (int r = 0; r < ROWS; ++r) {
@@ -281,7 +281,7 @@ __global__ __launch_bounds__(256) void k_conv2d_x3(ConvArgs a, int cin, int cout
         float* dst = a.out + ((size_t)v * cout * a.Ho + (live ? oy : 0)) * a.Wo + (live ? ox : 0);
 #pragma unroll
         for (int q = 0; q < 16; ++q) {
-            const int co = 8 * (q >> 2) + 4 * h + (q & 3);
+            const int co = conv_x3_channel(q, h);
             const float val = acc[r][q] + bv[q];
             if (live && co < cout) {
                 dst[(size_t)co * a.Ho * a.Wo] = val;
@@ -295,14 +295,10 @@ __global__ __launch_bounds__(256) void k_conv2d_x3(ConvArgs a, int cin, int cout
     for (int q = 0; q < 16; ++q) {
 #pragma unroll
         for (int off = 16; off; off >>= 1) { s[q] += __shfl_xor(s[q], off); q2[q] += __shfl_xor(q2[q], off); }
-        if (j == 0) { const int co = 8 * (q >> 2) + 4 * h + (q & 3); red[wave][co][0] = (double)s[q]; red[wave][co][1] = (double)q2[q]; }
+        if (j == 0) { const int co = conv_x3_channel(q, h); red[wave][co][0] = (double)s[q]; red[wave][co][1] = (double)q2[q]; }
     }
     __syncthreads();
-    if (threadIdx.x < 2 * cout) {
-        const int co = threadIdx.x >> 1, k = threadIdx.x & 1;
-        const double t = (red[0][co][k] + red[1][co][k]) + (red[2][co][k] + red[3][co][k]);
-        a.part[((size_t)co * a.nblk + (size_t)v * gridDim.x + blockIdx.x) * 2 + k] = t;
-    }
+    conv_part_write(a.part, a.nblk, red, cout, 0, v);
 }
 
 // The same kernel with the input tile staged one 16-channel group at a time (two barriers and one global round trip per group, the next group's
@@ -319,11 +315,8 @@ __global__ __launch_bounds__(256) void k_conv2d_x3_staged(ConvArgs a, int cin, i
     constexpr int NLD = CL ? (NPIX + 15) / 16 : (NPIX + 255) / 256;
     __shared__ float4 plane[2][2][NPIX];                                          // [hi | lo][channel octet][pixel]: a B operand is one 16-byte item
     __shared__ double red[4][32][2];
-    __shared__ float ssl[2][CINP];                                                // the producer's (scale | shift): read per staged value, kept in LDS
-    if (a.in_ss && threadIdx.x < 2 * CINP) {
-        const int k = threadIdx.x / CINP, c = threadIdx.x % CINP;
-        ssl[k][c] = c < cin ? a.in_ss[k * cin + c] : 0.f;
-    }
+    __shared__ float ssl[2][CINP];
+    conv_x3_load_ssl(a.in_ss, cin, ssl);
     const int lane = threadIdx.x & 63, j = lane & 31, h = lane >> 5, wave = threadIdx.x >> 6;
     const int bx = blockIdx.x % a.nbx, by = blockIdx.x / a.nbx, v = blockIdx.y;
     const int ox = bx * 32 + j, oy0 = by * TH + wave * ROWS;
@@ -362,7 +355,7 @@ __global__ __launch_bounds__(256) void k_conv2d_x3_staged(ConvArgs a, int cin, i
 #pragma unroll 1
     for (int u = 0; u < NU; ++u) {
         __syncthreads();                                                         // the previous group's MFMAs have read their operands
-        if constexpr (CL) {
+        if constexpr (CL) {                                                      // one value per thread: its own store (two bytes into each half's item)
             const int c = 16 * u + my_c;
             const float sc = a.in_ss ? ssl[0][c] : 1.f, sh = a.in_ss ? ssl[1][c] : 0.f;
             _Float16* const ph = reinterpret_cast<_Float16*>(&plane[0][my_c >> 3][0]) + (my_c & 7);
@@ -372,10 +365,7 @@ __global__ __launch_bounds__(256) void k_conv2d_x3_staged(ConvArgs a, int cin, i
                 const int r = (int)(threadIdx.x >> 4) + 16 * jj;
                 if (r < NPIX) {
                     float val = pre[jj][0];
-                    if (a.in_ss) {
-                        val = val * sc + sh;
-                        val = fmaxf(val, val * a.slope);
-                    }
+                    if (a.in_ss) val = abn_act_max(val, sc, sh, a.slope);
                     val = (pix_in[jj] && c < cin) ? val : 0.f;
                     _Float16 hi, lo;
                     split_one(val, m1, hi, lo);
@@ -385,67 +375,58 @@ __global__ __launch_bounds__(256) void k_conv2d_x3_staged(ConvArgs a, int cin, i
             }
         } else {
 #pragma unroll
-        for (int jj = 0; jj < NLD; ++jj) {
-            const int r = threadIdx.x + 256 * jj;
-            if (r < NPIX) {
+            for (int jj = 0; jj < NLD; ++jj) {
+                const int r = threadIdx.x + 256 * jj;
+                if (r < NPIX) {
 #pragma unroll
-                for (int oct = 0; oct < 2; ++oct) {
-                    float x[8];
+                    for (int oct = 0; oct < 2; ++oct) {
+                        float x[8];
 #pragma unroll
-                    for (int t = 0; t < 8; ++t) {
-                        const int c = 16 * u + 8 * oct + t;
-                        float val = pre[jj][8 * oct + t];
-                        if (a.in_ss) {
-                            val = val * ssl[0][c] + ssl[1][c];
-                            val = fmaxf(val, val * a.slope);                     // leaky ReLU, 0 <= slope < 1
+                        for (int t = 0; t < 8; ++t) {
+                            const int c = 16 * u + 8 * oct + t;
+                            float val = pre[jj][8 * oct + t];
+                            if (a.in_ss) val = abn_act_max(val, ssl[0][c], ssl[1][c], a.slope);
+                            x[t] = (pix_in[jj] && c < cin) ? val : 0.f;
                         }
-                        x[t] = (pix_in[jj] && c < cin) ? val : 0.f;
+                        const Split8 b = split8(x, 0, m1);
+                        plane[0][oct][r] = __builtin_bit_cast(float4, b.hi);
+                        plane[1][oct][r] = __builtin_bit_cast(float4, b.lo);
                     }
-                    union { h16x2 v2[4]; float4 f4; } bh, bl;
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) split_pair(x[2 * q], x[2 * q + 1], m1, bh.v2[q], bl.v2[q]);
-                    plane[0][oct][r] = bh.f4;
-                    plane[1][oct][r] = bl.f4;
                 }
             }
-        }
         }
         __syncthreads();
         // A operands of the first taps, THEN the next group's raw values, then the MFMAs: the vector-memory counter retires in order, so a wait for
         // an A operand issued after the prefetch would wait for the whole prefetch
         constexpr int KK = K * K, NA0 = KK <= 9 ? KK : 13;
-        AOpX aop[NA0];
+        AOp<1> aop[NA0];
 #pragma unroll
-        for (int tap = 0; tap < NA0; ++tap) aop[tap] = conv_a_fetch(rs, tap * NU + u, lane);
+        for (int tap = 0; tap < NA0; ++tap) aop[tap] = a_fetch<1>(rs, tap * NU + u, lane);
         if (u + 1 < NU) fetch(u + 1);                                            // in flight during this group's MFMAs
-        auto taps = [&](int tap, const AOpX& A) {
+        auto taps = [&](int tap, const AOp<1>& A) {
             const int ky = tap / K, kx = tap % K;
 #pragma unroll
             for (int r = 0; r < ROWS; ++r) {
                 const int pix = ((wave * ROWS + r) * STRIDE + ky) * IW + j * STRIDE + kx;
-                const h16x8 bh = __builtin_bit_cast(h16x8, plane[0][h][pix]), bl = __builtin_bit_cast(h16x8, plane[1][h][pix]);
-                acc[r] = MFMA_F16(A.lo, bh, acc[r]);
-                acc[r] = MFMA_F16(A.hi, bl, acc[r]);
-                acc[r] = MFMA_F16(A.hi, bh, acc[r]);
+                mfma_x3<1>(&acc[r], A.hi, A.lo, Split8{__builtin_bit_cast(h16x8, plane[0][h][pix]), __builtin_bit_cast(h16x8, plane[1][h][pix])});
             }
         };
 #pragma unroll
         for (int tap = 0; tap < NA0; ++tap) taps(tap, aop[tap]);
         if constexpr (KK > NA0) {
-            AOpX bop[KK - NA0];
+            AOp<1> bop[KK - NA0];
 #pragma unroll
-            for (int tap = NA0; tap < KK; ++tap) bop[tap - NA0] = conv_a_fetch(rs, tap * NU + u, lane);
+            for (int tap = NA0; tap < KK; ++tap) bop[tap - NA0] = a_fetch<1>(rs, tap * NU + u, lane);
 #pragma unroll
             for (int tap = NA0; tap < KK; ++tap) taps(tap, bop[tap - NA0]);
         }
     }
-    // register 4g + i of a lane holds output channel 8g + 4h + i of pixel column j
     float s[16], q2[16], bv[16];
 #pragma unroll
     for (int q = 0; q < 16; ++q) { s[q] = 0.f; q2[q] = 0.f; bv[q] = 0.f; }
     if (a.bias) {                                                                // all 16 loads in flight together (clamped index: no branch per value)
 #pragma unroll
-        for (int q = 0; q < 16; ++q) bv[q] = a.bias[min(8 * (q >> 2) + 4 * h + (q & 3), cout - 1)];
+        for (int q = 0; q < 16; ++q) bv[q] = a.bias[min(conv_x3_channel(q, h), cout - 1)];
     }
 #pragma unroll
     for (int r = 0; r < ROWS; ++r) {
@@ -454,7 +435,7 @@ __global__ __launch_bounds__(256) void k_conv2d_x3_staged(ConvArgs a, int cin, i
         float* dst = a.out + ((size_t)v * cout * a.Ho + (live ? oy : 0)) * a.Wo + (live ? ox : 0);
 #pragma unroll
         for (int q = 0; q < 16; ++q) {
-            const int co = 8 * (q >> 2) + 4 * h + (q & 3);
+            const int co = conv_x3_channel(q, h);
             const float val = acc[r][q] + bv[q];
             if (live && co < cout) {
                 dst[(size_t)co * a.Ho * a.Wo] = val;
@@ -467,14 +448,10 @@ __global__ __launch_bounds__(256) void k_conv2d_x3_staged(ConvArgs a, int cin, i
     for (int q = 0; q < 16; ++q) {
 #pragma unroll
         for (int off = 16; off; off >>= 1) { s[q] += __shfl_xor(s[q], off); q2[q] += __shfl_xor(q2[q], off); }
-        if (j == 0) { const int co = 8 * (q >> 2) + 4 * h + (q & 3); red[wave][co][0] = (double)s[q]; red[wave][co][1] = (double)q2[q]; }
+        if (j == 0) { const int co = conv_x3_channel(q, h); red[wave][co][0] = (double)s[q]; red[wave][co][1] = (double)q2[q]; }
     }
     __syncthreads();
-    if (threadIdx.x < 2 * cout) {
-        const int co = threadIdx.x >> 1, k = threadIdx.x & 1;
-        const double t = (red[0][co][k] + red[1][co][k]) + (red[2][co][k] + red[3][co][k]);
-        a.part[((size_t)co * a.nblk + (size_t)v * gridDim.x + blockIdx.x) * 2 + k] = t;
-    }
+    conv_part_write(a.part, a.nblk, red, cout, 0, v);
 }
 
 // nn.Conv2d weight [cout][cin][K][K] -> A operands [tap][group][hi|lo][64 lanes][8 f16]: lane (i = lane & 31, h = lane >> 5) of step (tap, u) holds
@@ -490,18 +467,28 @@ __global__ void k_conv_pack_x3(const float* __restrict__ w, int cout, int cin, i
     out[(size_t)step * 1024 + 512 + lane * 8 + t] = lo;
 }
 
+// the smallest output tile of any variant below (k_conv2d_x3 with one row per wave, the stride-2 layers): what o2345_conv2d_workspace_bytes assumes
+constexpr int CV_MIN_TILE_W = 32, CV_MIN_TILE_H = 4;
+
+// per-block partial sums -> this layer's (scale | shift); nblk and the tile sizes as the convolution launch set them
+template <int TILE_W, int TILE_H>
+static void launch_conv_stats_finish(const ConvArgs& a, int V, int cout, hipStream_t s) {
+    static_assert(TILE_W >= CV_MIN_TILE_W && TILE_H >= CV_MIN_TILE_H, "o2345_conv2d_workspace_bytes bounds the block count by the smallest tile");
+    if (a.part)
+        hipLaunchKernelGGL(k_conv_stats_finish, dim3(cout), dim3(256), 0, s, a.part, a.nblk, (double)V * a.Ho * a.Wo, cout, a.gamma, a.beta, a.eps, a.abs_gamma, a.out_ss);
+}
+
 template <int CINP, int K, int STRIDE, int ROWS, bool STAGED = false>
 static void launch_conv_x3(ConvArgs a, int V, int cin, int cout, hipStream_t s) {
     a.nbx = (int)cdiv(a.Wo, 32);
     const int nby = (int)cdiv(a.Ho, 4 * ROWS);
-    a.nblk = a.nbx * nby * V;                                                       // <= cdiv(Wo, 32) * cdiv(Ho, 4) * V (workspace bound)
+    a.nblk = a.nbx * nby * V;
     if constexpr (STAGED) {
         if (a.chan_stride == 1) hipLaunchKernelGGL((k_conv2d_x3_staged<CINP, K, STRIDE, ROWS, true>), dim3(a.nbx * nby, V), dim3(256), 0, s, a, cin, cout);
         else hipLaunchKernelGGL((k_conv2d_x3_staged<CINP, K, STRIDE, ROWS, false>), dim3(a.nbx * nby, V), dim3(256), 0, s, a, cin, cout);
     }
     else hipLaunchKernelGGL((k_conv2d_x3<CINP, K, STRIDE, ROWS>), dim3(a.nbx * nby, V), dim3(256), 0, s, a, cin, cout);
-    if (a.part)
-        hipLaunchKernelGGL(k_conv_stats_finish, dim3(cout), dim3(256), 0, s, a.part, a.nblk, (double)V * a.Ho * a.Wo, cout, a.gamma, a.beta, a.eps, a.abs_gamma, a.out_ss);
+    launch_conv_stats_finish<32, 4 * ROWS>(a, V, cout, s);
 }
 
 template <int CIN, int COUT, int CPB, int K, int STRIDE, int CC, int PX>
@@ -509,8 +496,35 @@ static void launch_conv(ConvArgs a, int V, hipStream_t s) {
     a.nbx = (int)cdiv(a.Wo, CV_TX * PX);
     a.nblk = a.nbx * (int)cdiv(a.Ho, CV_TH) * V;
     hipLaunchKernelGGL((k_conv2d<CIN, COUT, CPB, K, STRIDE, CC, PX>), dim3(a.nbx * cdiv(a.Ho, CV_TH), V, COUT / CPB), dim3(256), 0, s, a);
-    if (a.part)
-        hipLaunchKernelGGL(k_conv_stats_finish, dim3(COUT), dim3(256), 0, s, a.part, a.nblk, (double)V * a.Ho * a.Wo, COUT, a.gamma, a.beta, a.eps, a.abs_gamma, a.out_ss);
+    launch_conv_stats_finish<CV_TX * PX, CV_TH>(a, V, COUT, s);
+}
+
+// What o2345_conv2d and o2345_conv2d_x3 check and set up alike (`name`: the entry point, for the messages), in two steps with the entry's own checks
+// between them, so that a call with several faults reports the one it always did.  First the pointers, the sizes and the channel-last addressing:
+static int conv_check_input(const char* name, const float* in, const float* w_packed, const float* out, int V, int cin, int Hi, int Wi, int in_pixel_stride,
+                            int in_channel_offset) {
+    O2345_REQUIRE(in && w_packed && out && V >= 1 && Hi >= 1 && Wi >= 1, "%s: bad arguments", name);
+    O2345_REQUIRE(in_pixel_stride <= 0 || (in_channel_offset >= 0 && in_channel_offset + cin <= in_pixel_stride), "%s: channel-last input: offset + cin must fit the pixel stride", name);
+    return 0;
+}
+
+// then the output size, the workspace of the statistics pass and the input addressing
+static int conv_args(const char* name, ConvArgs& a, const float* in, int V, int cin, int Hi, int Wi, int in_pixel_stride, int in_channel_offset,
+                     const float* in_scale_shift, float slope, const float* w_packed, const float* bias, int cout, int k, int stride, float* out,
+                     const float* gamma, const float* beta, float eps, int abs_gamma, float* out_scale_shift, void* workspace, size_t workspace_bytes) {
+    const int pad = k / 2;
+    const int Ho = (Hi + 2 * pad - k) / stride + 1, Wo = (Wi + 2 * pad - k) / stride + 1;
+    const bool stats = out_scale_shift != nullptr;
+    if (stats) {
+        O2345_REQUIRE(gamma && beta && workspace, "%s: batch statistics need gamma, beta and a workspace", name);
+        O2345_REQUIRE(workspace_bytes >= o2345_conv2d_workspace_bytes(V, cout, Ho, Wo), "%s: workspace too small", name);
+    }
+    a = ConvArgs{in, in_scale_shift, slope, w_packed, bias, Hi, Wi, Ho, Wo, out, stats ? (double*)workspace : nullptr, 0, 0,
+                 gamma, beta, eps, abs_gamma, out_scale_shift, 0, 0, 0};
+    // element (v, c, y, x) of the input: channel-first [V,cin,Hi,Wi], or channel-last with in_pixel_stride floats per pixel from channel in_channel_offset on
+    if (in_pixel_stride <= 0) { a.view_stride = (long long)cin * Hi * Wi; a.chan_stride = (long long)Hi * Wi; a.pix_stride = 1; }
+    else { a.view_stride = (long long)Hi * Wi * in_pixel_stride; a.chan_stride = 1; a.pix_stride = in_pixel_stride; a.in += in_channel_offset; }
+    return 0;
 }
 
 }  // namespace o2345
@@ -526,39 +540,25 @@ int o2345_conv2d_pack_weights(const float* w_oihw, int cout, int cin, int k, flo
 }
 
 size_t o2345_conv2d_workspace_bytes(int V, int cout, int Ho, int Wo) {
-    // one (sum, sum of squares) pair of doubles per channel and block; the smallest tile of any kernel here is 32 x 4 output pixels
-    // (k_conv2d_x3 with one row per wave, the stride-2 layers), so this bounds the block count of every variant
-    return (size_t)cout * cdiv(Wo, 32) * cdiv(Ho, 4) * V * 2 * sizeof(double);
+    // one (sum, sum of squares) pair of doubles per channel and block, for the variant with the most blocks (launch_conv_stats_finish checks every variant)
+    return (size_t)cout * cdiv(Wo, CV_MIN_TILE_W) * cdiv(Ho, CV_MIN_TILE_H) * V * 2 * sizeof(double);
 }
 
 // out = conv2d(act(in), w) (+ bias); act = leaky(in * scale + shift) when in_scale_shift is given.  padding = k / 2.
 // When gamma / beta / out_scale_shift are given, the batch statistics of `out` over (V, Ho, Wo) are reduced and out_scale_shift [2*cout] receives
 // the InPlaceABN (scale, shift) of this layer -- to be applied by the consumer (o2345_conv2d / o2345_fpn_level_act / o2345_scale_shift_act).
-static void set_input_layout(ConvArgs& a, int cin, int in_pixel_stride, int in_channel_offset) {
-    if (in_pixel_stride <= 0) { a.view_stride = (long long)cin * a.Hi * a.Wi; a.chan_stride = (long long)a.Hi * a.Wi; a.pix_stride = 1; }
-    else { a.view_stride = (long long)a.Hi * a.Wi * in_pixel_stride; a.chan_stride = 1; a.pix_stride = in_pixel_stride; a.in += in_channel_offset; }
-}
-
 int o2345_conv2d(const float* in, int V, int cin, int Hi, int Wi, int in_pixel_stride, int in_channel_offset, const float* in_scale_shift, float slope,
                  const float* w_packed, const float* bias, int cout, int k, int stride, float* out, const float* gamma, const float* beta, float eps,
                  int abs_gamma, float* out_scale_shift, void* workspace, size_t workspace_bytes, void* stream) {
-    O2345_REQUIRE(in && w_packed && out && V >= 1 && Hi >= 1 && Wi >= 1, "conv2d: bad arguments");
-    O2345_REQUIRE(in_pixel_stride <= 0 || (in_channel_offset >= 0 && in_channel_offset + cin <= in_pixel_stride), "conv2d: channel-last input: offset + cin must fit the pixel stride");
+    if (const int rc = conv_check_input("conv2d", in, w_packed, out, V, cin, Hi, Wi, in_pixel_stride, in_channel_offset)) return rc;
     O2345_REQUIRE(stride == 1 || stride == 2, "conv2d: stride 1 or 2 (got %d)", stride);
-    const int pad = k / 2;
-    const int Ho = (Hi + 2 * pad - k) / stride + 1, Wo = (Wi + 2 * pad - k) / stride + 1;
-    const bool stats = out_scale_shift != nullptr;
-    if (stats) {
-        O2345_REQUIRE(gamma && beta && workspace, "conv2d: batch statistics need gamma, beta and a workspace");
-        O2345_REQUIRE(workspace_bytes >= o2345_conv2d_workspace_bytes(V, cout, Ho, Wo), "conv2d: workspace too small");
-    }
-    ConvArgs a{in, in_scale_shift, slope, w_packed, bias, Hi, Wi, Ho, Wo, out, stats ? (double*)workspace : nullptr, 0, 0,
-               gamma, beta, eps, abs_gamma, out_scale_shift, 0, 0, 0};
-    set_input_layout(a, cin, in_pixel_stride, in_channel_offset);
+    ConvArgs a;
+    if (const int rc = conv_args("conv2d", a, in, V, cin, Hi, Wi, in_pixel_stride, in_channel_offset, in_scale_shift, slope, w_packed, bias, cout, k, stride, out,
+                                 gamma, beta, eps, abs_gamma, out_scale_shift, workspace, workspace_bytes)) return rc;
     hipStream_t s = (hipStream_t)stream;
     // pixels per thread / output channels per block by map size, so that a launch covers the chip (1024 SIMDs) a few times over:
     // 4 pixels x <= 16 channels on large maps (most FMAs per scalar weight load), 1 pixel x 8 channels on small ones
-    const long long pix = (long long)V * Ho * Wo;
+    const long long pix = (long long)V * a.Ho * a.Wo;
     const int tier = pix >= 400000 ? 2 : pix >= 100000 ? 1 : 0;
     bool done = false;
 #define O2345_CONV(CI, CO, KK, ST, CC, PX4, B4, B2, B1)                                   \
@@ -598,20 +598,12 @@ int o2345_conv2d_pack_weights_x3(const float* w_oihw, int cout, int cin, int k, 
 int o2345_conv2d_x3(const float* in, int V, int cin, int Hi, int Wi, int in_pixel_stride, int in_channel_offset, const float* in_scale_shift, float slope,
                     const float* w_packed_x3, const float* bias, int cout, int k, int stride, float* out, const float* gamma, const float* beta, float eps,
                     int abs_gamma, float* out_scale_shift, void* workspace, size_t workspace_bytes, void* stream) {
-    O2345_REQUIRE(in && w_packed_x3 && out && V >= 1 && Hi >= 1 && Wi >= 1, "conv2d_x3: bad arguments");
-    O2345_REQUIRE(in_pixel_stride <= 0 || (in_channel_offset >= 0 && in_channel_offset + cin <= in_pixel_stride), "conv2d_x3: channel-last input: offset + cin must fit the pixel stride");
+    if (const int rc = conv_check_input("conv2d_x3", in, w_packed_x3, out, V, cin, Hi, Wi, in_pixel_stride, in_channel_offset)) return rc;
     O2345_REQUIRE(cout >= 1 && cout <= 32 && cin >= 1 && cin <= 64, "conv2d_x3: at most 64 input and 32 output channels (got %d -> %d)", cin, cout);
     O2345_REQUIRE((long long)Hi * Wi * (in_pixel_stride > 0 ? in_pixel_stride : 1) < (1ll << 31), "conv2d_x3: a view must have fewer than 2^31 elements per channel plane");
-    const int pad = k / 2;
-    const int Ho = (Hi + 2 * pad - k) / stride + 1, Wo = (Wi + 2 * pad - k) / stride + 1;
-    const bool stats = out_scale_shift != nullptr;
-    if (stats) {
-        O2345_REQUIRE(gamma && beta && workspace, "conv2d_x3: batch statistics need gamma, beta and a workspace");
-        O2345_REQUIRE(workspace_bytes >= o2345_conv2d_workspace_bytes(V, cout, Ho, Wo), "conv2d_x3: workspace too small");
-    }
-    ConvArgs a{in, in_scale_shift, slope, w_packed_x3, bias, Hi, Wi, Ho, Wo, out, stats ? (double*)workspace : nullptr, 0, 0,
-               gamma, beta, eps, abs_gamma, out_scale_shift, 0, 0, 0};
-    set_input_layout(a, cin, in_pixel_stride, in_channel_offset);
+    ConvArgs a;
+    if (const int rc = conv_args("conv2d_x3", a, in, V, cin, Hi, Wi, in_pixel_stride, in_channel_offset, in_scale_shift, slope, w_packed_x3, bias, cout, k, stride, out,
+                                 gamma, beta, eps, abs_gamma, out_scale_shift, workspace, workspace_bytes)) return rc;
     hipStream_t s = (hipStream_t)stream;
     const int cinp = (cin + 15) / 16 * 16;
     bool done = true;

@@ -16,6 +16,7 @@
 #include "geom_math.h"
 #include "costvol_math.h"
 #include "block_kernels.h"
+#include <type_traits>
 
 namespace o2345 {
 
@@ -69,24 +70,6 @@ __device__ __forceinline__ int quad_bcast_i(int v) { return __builtin_amdgcn_mov
 template <int K>
 __device__ __forceinline__ float quad_bcast_f(float v) { return __builtin_bit_cast(float, quad_bcast_i<K>(__builtin_bit_cast(int, v))); }
 
-__device__ __forceinline__ void tap4_accumulate(const float4* __restrict__ base, const int (&idx)[4], const float (&w)[4],
-                                                float4& s1, float4& s2) {
-    float4 f = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        if (w[k] != 0.f) {              // fully-outside taps: no load (zero padding)
-#ifdef O2345_COSTVOL_TAPMASK      // timing experiment only (wrong results): every tap falls into a few L1-resident lines -> what is left is issue + VALU
-            const float4 a = base[(size_t)(idx[k] & O2345_COSTVOL_TAPMASK) * 4];
-#else
-            const float4 a = base[(size_t)idx[k] * 4];
-#endif
-            f.x += a.x * w[k]; f.y += a.y * w[k]; f.z += a.z * w[k]; f.w += a.w * w[k];
-        }
-    }
-    s1.x += f.x; s1.y += f.y; s1.z += f.z; s1.w += f.w;
-    s2.x += f.x * f.x; s2.y += f.y * f.y; s2.z += f.z * f.z; s2.w += f.w * f.w;
-}
-
 __device__ __forceinline__ void costvol_row_quad16(const float* __restrict__ feats, const float* __restrict__ proj, int V, int H, int W,
                                                    const VolGeom& g, const uint8_t* __restrict__ cnt, const int* __restrict__ coords,
                                                    int row, int q, float* __restrict__ out) {
@@ -105,58 +88,18 @@ __device__ __forceinline__ void costvol_row_quad16(const float* __restrict__ fea
 #pragma unroll
             for (int k = 0; k < 4; ++k) { idx[k] = tp.idx[k]; w[k] = tp.w[k]; }
         }
-#ifndef O2345_COSTVOL_BATCH
-#define O2345_COSTVOL_BATCH 0      // measured (round 3): 0.166 ms batched vs 0.139 ms one view at a time -- see the comment below and profiles/NOTES.md
-#endif
-#if O2345_COSTVOL_BATCH
-        // A/B form: the taps of the round's four views requested TOGETHER (up to 16 independent 16-byte loads per lane in flight), accumulated afterwards in
-        // the same order (bit-identical sums).  If the kernel were bound by the latency of its dependent gathers this would win; it LOSES (130 registers,
-        // 3 instead of 8 waves per SIMD): the kernel is bound by what the L2 -> L1 path delivers for 64-byte taps, and more waves beat more loads per wave.
-        float4 tv[4][4];
-        float wv[4][4];
-#define O2345_QUAD_LOAD(K)                                                                                             \
-        {                                                                                                              \
-            const float4* base = reinterpret_cast<const float4*>(feats + (size_t)(vb + K < V ? vb + K : 0) * plane * 16) + q;   \
-            _Pragma("unroll") for (int k = 0; k < 4; ++k) {                                                         \
-                const int ik = quad_bcast_i<K>(idx[k]);                                                                \
-                wv[K][k] = (vb + K < V) ? quad_bcast_f<K>(w[k]) : 0.f;                                                 \
-                tv[K][k] = make_float4(0.f, 0.f, 0.f, 0.f);                                                            \
-                if (wv[K][k] != 0.f) tv[K][k] = base[(size_t)ik * 4];                                                  \
-            }                                                                                                          \
-        }
-        O2345_QUAD_LOAD(0) O2345_QUAD_LOAD(1) O2345_QUAD_LOAD(2) O2345_QUAD_LOAD(3)
-#undef O2345_QUAD_LOAD
-#pragma unroll
-        for (int K = 0; K < 4; ++K)
-            if (vb + K < V) {
-                float4 f = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-                for (int k = 0; k < 4; ++k)
-                    if (wv[K][k] != 0.f) {
-                        const float4 a = tv[K][k];
-                        f.x += a.x * wv[K][k]; f.y += a.y * wv[K][k]; f.z += a.z * wv[K][k]; f.w += a.w * wv[K][k];
-                    }
-                s1.x += f.x; s1.y += f.y; s1.z += f.z; s1.w += f.w;
-                s2.x += f.x * f.x; s2.y += f.y * f.y; s2.z += f.z * f.z; s2.w += f.w * f.w;
-            }
-#else
+        // one view at a time: requesting the taps of the round's four views together measured slower (profiles/NOTES.md)
 #define O2345_QUAD_VIEW(K)                                                                                             \
         if (vb + K < V) {                                                                                              \
             int ik[4]; float wk[4];                                                                                    \
             _Pragma("unroll") for (int k = 0; k < 4; ++k) { ik[k] = quad_bcast_i<K>(idx[k]); wk[k] = quad_bcast_f<K>(w[k]); } \
-            tap4_accumulate(reinterpret_cast<const float4*>(feats + (size_t)(vb + K) * plane * 16) + q, ik, wk, s1, s2); \
+            tap4_accumulate<4>(reinterpret_cast<const float4*>(feats + (size_t)(vb + K) * plane * 16) + q, ik, wk, s1, s2); \
         }
         O2345_QUAD_VIEW(0) O2345_QUAD_VIEW(1) O2345_QUAD_VIEW(2) O2345_QUAD_VIEW(3)
 #undef O2345_QUAD_VIEW
-#endif
     }
     const long long v = ((long long)c.x * g.dy + c.y) * g.dz + c.z;
-    const float ic = 1.f / ((float)cnt[v] + 1e-5f);           // sparse_sdf_network.py:242
-    float4 mean = make_float4(s1.x * ic, s1.y * ic, s1.z * ic, s1.w * ic);
-    float4 var = make_float4(s2.x * ic - mean.x * mean.x, s2.y * ic - mean.y * mean.y, s2.z * ic - mean.z * mean.z, s2.w * ic - mean.w * mean.w);
-    float4* o = reinterpret_cast<float4*>(out + (size_t)row * 32);
-    o[q] = var;
-    o[4 + q] = mean;
+    costvol_var_mean<4>(s1, s2, cnt[v], out + (size_t)row * 32, q);
 }
 
 template <int C>
@@ -256,6 +199,13 @@ __global__ __launch_bounds__(256) void k_scatter_dense(const float* __restrict__
     }
 }
 
+// calls f with the channel count of the rows, 8 or 16 (the caller has checked it), as a compile-time constant
+template <typename F>
+static void with_channels(int C, F&& f) {
+    if (C == 16) f(std::integral_constant<int, 16>{});
+    else f(std::integral_constant<int, 8>{});
+}
+
 }  // namespace o2345
 
 using namespace o2345;
@@ -292,12 +242,9 @@ int o2345_costvol_gather(const float* feats_nhwc, const float* proj, int V, int 
     if (n_rows == 0) return 0;
     VolGeom g{dx, dy, dz, voxel_size, origin_host[0], origin_host[1], origin_host[2]};
     hipStream_t s = (hipStream_t)stream;
-    if (C == 16)
-        hipLaunchKernelGGL(k_costvol_gather<16>, dim3(cdiv((long long)n_rows * 4, 256)), dim3(256), 0, s, feats_nhwc, proj,
-                           V, H, W, g, cnt, coords, n_rows, out_rows);
-    else
-        hipLaunchKernelGGL(k_costvol_gather<8>, dim3(cdiv((long long)n_rows * 2, 256)), dim3(256), 0, s, feats_nhwc, proj,
-                           V, H, W, g, cnt, coords, n_rows, out_rows);
+    with_channels(C, [&](auto c) {
+        hipLaunchKernelGGL(k_costvol_gather<c.value>, dim3(cdiv((long long)n_rows * (c.value / 4), 256)), dim3(256), 0, s, feats_nhwc, proj, V, H, W, g, cnt, coords, n_rows, out_rows);
+    });
     return check_launch("costvol_gather");
 }
 
@@ -318,8 +265,9 @@ int o2345_costvol_gather_list(const float* feats_nhwc, const float* proj, int V,
     if (n_rows == 0) return 0;
     VolGeom g{0, 0, 0, voxel_size, origin_host[0], origin_host[1], origin_host[2]};
     hipStream_t s = (hipStream_t)stream;
-    if (C == 16) hipLaunchKernelGGL(k_costvol_gather_list<16>, dim3(cdiv((long long)n_rows * 4, 256)), dim3(256), 0, s, feats_nhwc, proj, V, H, W, g, cnt_row, coords, n_rows, out_rows);
-    else hipLaunchKernelGGL(k_costvol_gather_list<8>, dim3(cdiv((long long)n_rows * 2, 256)), dim3(256), 0, s, feats_nhwc, proj, V, H, W, g, cnt_row, coords, n_rows, out_rows);
+    with_channels(C, [&](auto c) {
+        hipLaunchKernelGGL(k_costvol_gather_list<c.value>, dim3(cdiv((long long)n_rows * (c.value / 4), 256)), dim3(256), 0, s, feats_nhwc, proj, V, H, W, g, cnt_row, coords, n_rows, out_rows);
+    });
     return check_launch("costvol_gather_list");
 }
 
@@ -349,10 +297,9 @@ int o2345_scatter_dense(const float* rows, const int32_t* row_of_voxel, int C, l
     O2345_REQUIRE(rows && row_of_voxel, "scatter_dense: null pointer");
     O2345_REQUIRE(C == 16 || C == 8, "scatter_dense: C must be 8 or 16 (got %d)", C);
     hipStream_t s = (hipStream_t)stream;
-    if (C == 16)
-        hipLaunchKernelGGL(k_scatter_dense<16>, dim3(cdiv(nvox, 256)), dim3(256), 0, s, rows, row_of_voxel, nvox, dense_cl, dense_cf, mask);
-    else
-        hipLaunchKernelGGL(k_scatter_dense<8>, dim3(cdiv(nvox, 256)), dim3(256), 0, s, rows, row_of_voxel, nvox, dense_cl, dense_cf, mask);
+    with_channels(C, [&](auto c) {
+        hipLaunchKernelGGL(k_scatter_dense<c.value>, dim3(cdiv(nvox, 256)), dim3(256), 0, s, rows, row_of_voxel, nvox, dense_cl, dense_cf, mask);
+    });
     return check_launch("scatter_dense");
 }
 

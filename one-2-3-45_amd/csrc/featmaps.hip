@@ -10,6 +10,7 @@
 // Bilinear weights follow ATen's upsample_bilinear2d (align_corners: src = dst * (in - 1) / (out - 1) in fp32, i1 = i0 + (i0 < in - 1),
 // value = l0y (l0x a + l1x b) + l1y (l0x c + l1x d)).
 #include "common.h"
+#include "block_kernels.h"
 
 namespace o2345 {
 
@@ -44,10 +45,7 @@ __global__ __launch_bounds__(256) void k_fpn_level(const float* __restrict__ fin
 #pragma unroll
     for (int c = 0; c < CIN; ++c) {
         float t = fine[((size_t)v * CIN + c) * H * W + p];
-        if (fine_ss) {                                      // `fine` is a raw convolution output: its InPlaceABN is applied here (csrc/convnet.hip)
-            t = t * fine_ss[c] + fine_ss[CIN + c];
-            t = t >= 0.f ? t : t * slope;
-        }
+        if (fine_ss) t = abn_act_select(t, fine_ss[c], fine_ss[CIN + c], slope);      // `fine` is a raw convolution output: its InPlaceABN is applied here (csrc/convnet.hip)
         in[c] = t;
     }
     const Lerp ly = up_coord(y, hc, H), lx = up_coord(x, wc, W);

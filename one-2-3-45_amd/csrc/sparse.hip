@@ -13,12 +13,9 @@
 // two-stage reduction, then a fused normalise + ReLU (+ skip add) pass.
 #include "common.h"
 #include "block_kernels.h"
+#include "sparse_common.h"
 
 namespace o2345 {
-
-struct Lattice {
-    int nx, ny, nz;   // cells per axis of this level's index grid
-};
 
 // ---- coarse-level construction (spdownsample, kernel 3 stride 2) --------------------------------------------------
 // fine cell c marks coarse cells (c+o)/2 for o in {-1,0,1} with (c+o) even, subject to (c+o) >= cmin (cell units)
@@ -62,7 +59,7 @@ __global__ void k_mark_coarse(const int* __restrict__ coords, int n, int ts, con
     for (int ix = 0; ix < nc[0]; ++ix)
         for (int iy = 0; iy < nc[1]; ++iy)
             for (int iz = 0; iz < nc[2]; ++iz)
-                flag[((size_t)cand[0][ix] * lc.ny + cand[1][iy]) * lc.nz + cand[2][iz]] = 1;
+                flag[lc.cell(cand[0][ix], cand[1][iy], cand[2][iz])] = 1;
 }
 
 __global__ __launch_bounds__(IDX_BLOCK) void k_flag_count(const uint8_t* __restrict__ flag, long long ncell,
@@ -109,19 +106,7 @@ __global__ __launch_bounds__(256) void k_sparse_conv(const float* __restrict__ i
 #pragma unroll
     for (int o = 0; o < COUT; ++o) acc[o] = 0.f;
     for (int k = 0; k < 27; ++k) {
-        const int ox = k % 3 - 1, oy = (k / 3) % 3 - 1, oz = k / 9 - 1;
-        int nx, ny, nz;
-        bool ok = true;
-        if (MODE == 0) { nx = cx + ox; ny = cy + oy; nz = cz + oz; }
-        else if (MODE == 1) { nx = 2 * cx + ox; ny = 2 * cy + oy; nz = 2 * cz + oz; }
-        else {
-            nx = cx - ox; ny = cy - oy; nz = cz - oz;
-            ok = !((nx | ny | nz) & 1);
-            nx >>= 1; ny >>= 1; nz >>= 1;
-        }
-        ok = ok && nx >= 0 && ny >= 0 && nz >= 0 && nx < lin.nx && ny < lin.ny && nz < lin.nz;
-        int r = -1;
-        if (ok) r = in_grid[((size_t)nx * lin.ny + ny) * lin.nz + nz];
+        const int r = neighbour_row<MODE>(in_grid, lin, cx, cy, cz, k);
         if (r < 0) continue;
         const float4* src = reinterpret_cast<const float4*>(in + (size_t)r * CIN);
         const float* w = Wk + (size_t)k * CIN * COUT;
@@ -186,9 +171,7 @@ __global__ __launch_bounds__(256) void k_bn_act(const float* __restrict__ x, lon
     float r[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
-        float t = r[u] * scale_shift[c + u] + scale_shift[C + c + u];
-        t = t >= 0.f ? t : t * slope;
-        r[u] = t;
+        r[u] = abn_act_select(r[u], scale_shift[c + u], scale_shift[C + c + u], slope);
     }
     if (skip) {
         const float4 s = *reinterpret_cast<const float4*>(skip + i);
@@ -212,7 +195,7 @@ __global__ __launch_bounds__(256) void k_nchw_partial(const float* __restrict__ 
     for (int off = 32; off; off >>= 1) { s += __shfl_xor(s, off); s2 += __shfl_xor(s2, off); }
     if ((threadIdx.x & 63) == 0) { sm[0][threadIdx.x >> 6] = s; sm[1][threadIdx.x >> 6] = s2; }
     __syncthreads();
-    if (threadIdx.x == 0) {
+    if (threadIdx.x == 0) {      // wave totals summed left to right (block_sum2_256 sums them pairwise: folding this into it would change last bits)
         part[((size_t)c * nb_per_c + b) * 2 + 0] = sm[0][0] + sm[0][1] + sm[0][2] + sm[0][3];
         part[((size_t)c * nb_per_c + b) * 2 + 1] = sm[1][0] + sm[1][1] + sm[1][2] + sm[1][3];
     }
@@ -268,14 +251,6 @@ int o2345_sparse_downsample(const int32_t* coords_fine, int n_fine, int ts, int 
     return check_launch("sparse_downsample");
 }
 
-#define O2345_CONV_CASE(CI, CO)                                                                                        \
-    if (cin == CI && cout == CO) {                                                                                     \
-        if (mode == 0) hipLaunchKernelGGL((k_sparse_conv<CI, CO, 0>), grid, dim3(256), 0, s, in, out_coords, n_out, ts_out, in_grid, lin, kernel, out); \
-        else if (mode == 1) hipLaunchKernelGGL((k_sparse_conv<CI, CO, 1>), grid, dim3(256), 0, s, in, out_coords, n_out, ts_out, in_grid, lin, kernel, out); \
-        else hipLaunchKernelGGL((k_sparse_conv<CI, CO, 2>), grid, dim3(256), 0, s, in, out_coords, n_out, ts_out, in_grid, lin, kernel, out); \
-        return check_launch("sparse_conv3d");                                                                          \
-    }
-
 // mode 0: stride 1 (in level == out level), 1: stride-2 down (in = finer level), 2: transposed stride-2 up (in = coarser)
 int o2345_sparse_conv3d(int mode, const float* in, int cin, const int32_t* in_grid, int gx, int gy, int gz,
                         const int32_t* out_coords, int n_out, int ts_out, const float* kernel, int cout, float* out,
@@ -286,8 +261,15 @@ int o2345_sparse_conv3d(int mode, const float* in, int cin, const int32_t* in_gr
     hipStream_t s = (hipStream_t)stream;
     Lattice lin{gx, gy, gz};
     dim3 grid(cdiv(n_out, 256));
-    O2345_CONV_CASE(32, 16) O2345_CONV_CASE(16, 16) O2345_CONV_CASE(16, 32) O2345_CONV_CASE(32, 32)
-    O2345_CONV_CASE(32, 64) O2345_CONV_CASE(64, 64) O2345_CONV_CASE(64, 32) O2345_CONV_CASE(48, 16)
+#define O2345_CONV_CASE(CI, CO)                                                                                        \
+    if (cin == CI && cout == CO) {                                                                                     \
+        with_conv_mode(mode, [&](auto m) {                                                                             \
+            hipLaunchKernelGGL((k_sparse_conv<CI, CO, m.value>), grid, dim3(256), 0, s, in, out_coords, n_out, ts_out, in_grid, lin, kernel, out); \
+        });                                                                                                            \
+        return check_launch("sparse_conv3d");                                                                          \
+    }
+    O2345_SPARSE_CHANNEL_PAIRS(O2345_CONV_CASE)
+#undef O2345_CONV_CASE
     O2345_REQUIRE(false, "sparse_conv3d: unsupported channels %d -> %d", cin, cout);
     return -1;
 }

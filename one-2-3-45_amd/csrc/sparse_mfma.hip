@@ -13,43 +13,16 @@
 // The thread-per-row fp32 VALU kernel remains the strict-fp32 path.
 #include "common.h"
 #include "split_f16.h"
+#include "sparse_common.h"
 
 namespace o2345 {
-
-struct Lattice3 { int nx, ny, nz; };
-
-template <int NB>
-struct AOp { h16x8 hi[NB], lo[NB]; };
-
-template <int NB>
-__device__ __forceinline__ AOp<NB> a_fetch_lds(const float* wlds, int step, int lane) {
-    AOp<NB> r;
-    const float4* A = reinterpret_cast<const float4*>(wlds);
-#pragma unroll
-    for (int nb = 0; nb < NB; ++nb) {
-        r.hi[nb] = __builtin_bit_cast(h16x8, A[((step * NB + nb) * 2 + 0) * 64 + lane]);
-        r.lo[nb] = __builtin_bit_cast(h16x8, A[((step * NB + nb) * 2 + 1) * 64 + lane]);
-    }
-    return r;
-}
-template <int NB>
-__device__ __forceinline__ AOp<NB> a_fetch(__amdgpu_buffer_rsrc_t rs, int step, int lane) {
-    AOp<NB> r;
-#pragma unroll
-    for (int nb = 0; nb < NB; ++nb) {
-        const int base = ((step * NB + nb) * 2) * 1024;          // bytes: [step][block][hi|lo][64 lanes][16 B]
-        r.hi[nb] = __builtin_bit_cast(h16x8, __builtin_amdgcn_raw_buffer_load_b128(rs, lane * 16, base, 0));
-        r.lo[nb] = __builtin_bit_cast(h16x8, __builtin_amdgcn_raw_buffer_load_b128(rs, lane * 16, base + 1024, 0));
-    }
-    return r;
-}
 
 // LDSW: the layer's operand blob (27 * CIN/16 * blocks * 2 KB) fits in LDS -- persistent 1024-thread workgroups (one per CU, four
 // waves per SIMD) stage it once and loop over the tiles; otherwise (the 64-channel layers, which only exist at the coarse levels)
 // 256-thread workgroups stream it from L2.
 template <int CIN, int COUT, int MODE, bool LDSW>
 __global__ __launch_bounds__(LDSW ? 1024 : 256) void k_sparse_conv_x3(const float* __restrict__ in, const int* __restrict__ out_coords,
-                                                                      int n_out, int ts_out, const int* __restrict__ in_grid, Lattice3 lin,
+                                                                      int n_out, int ts_out, const int* __restrict__ in_grid, Lattice lin,
                                                                       const float* __restrict__ wblob, float* __restrict__ out) {
     constexpr int NU = CIN / 16, NB = (COUT + 31) / 32;
     extern __shared__ __attribute__((aligned(16))) float wlds[];
@@ -84,18 +57,7 @@ __global__ __launch_bounds__(LDSW ? 1024 : 256) void k_sparse_conv_x3(const floa
     int nbr[27];
 #pragma unroll
     for (int k = 0; k < 27; ++k) {
-        const int ox = k % 3 - 1, oy = (k / 3) % 3 - 1, oz = k / 9 - 1;
-        int nx, ny, nz;
-        bool ok = live;
-        if (MODE == 0) { nx = cx + ox; ny = cy + oy; nz = cz + oz; }
-        else if (MODE == 1) { nx = 2 * cx + ox; ny = 2 * cy + oy; nz = 2 * cz + oz; }
-        else {
-            nx = cx - ox; ny = cy - oy; nz = cz - oz;
-            ok = ok && !((nx | ny | nz) & 1);
-            nx >>= 1; ny >>= 1; nz >>= 1;
-        }
-        ok = ok && nx >= 0 && ny >= 0 && nz >= 0 && nx < lin.nx && ny < lin.ny && nz < lin.nz;
-        nbr[k] = ok ? in_grid[((size_t)nx * lin.ny + ny) * lin.nz + nz] : -1;
+        nbr[k] = neighbour_row<MODE>(in_grid, lin, cx, cy, cz, k, live);
     }
 #pragma unroll
     for (int k = 0; k < 27; ++k) {
@@ -143,7 +105,7 @@ constexpr int BRICK_THREADS = 512;
 constexpr int BRICK_W_F = 27 * 2 * 64 * 4;   // weights in LDS: [27][hi|lo][64 lanes][8 f16]
 constexpr size_t BRICK_LDS = (size_t)(BRICK_W_F + HALO * SITE_F) * 4;
 
-__global__ __launch_bounds__(BRICK_THREADS) void k_sparse_conv_brick_32_16(const float* __restrict__ in, const int* __restrict__ grid, Lattice3 lin,
+__global__ __launch_bounds__(BRICK_THREADS) void k_sparse_conv_brick_32_16(const float* __restrict__ in, const int* __restrict__ grid, Lattice lin,
                                                                             const float* __restrict__ wblob, float* __restrict__ out) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float* wl = lds;
@@ -169,7 +131,7 @@ __global__ __launch_bounds__(BRICK_THREADS) void k_sparse_conv_brick_32_16(const
         int occ = 0;
         if (threadIdx.x < BRX * BRY * BRZ) {
             const int t = threadIdx.x, z = z0 + t % BRZ, y = y0 + (t / BRZ) % BRY, x = x0 + t / (BRZ * BRY);
-            occ = (x < lin.nx && y < lin.ny && z < lin.nz) ? (grid[((size_t)x * lin.ny + y) * lin.nz + z] >= 0) : 0;
+            occ = lin.row_or_none(grid, x, y, z) >= 0;
         }
         if (!__syncthreads_or(occ)) continue;        // (also the barrier that protects the halo buffer of the previous brick)
         // ---- stage the halo: item = (site, 8-channel chunk); hi | lo halves, zeros for empty / outside sites.  Three batched phases so that the
@@ -182,7 +144,7 @@ __global__ __launch_bounds__(BRICK_THREADS) void k_sparse_conv_brick_32_16(const
             const int site = it >> 2;
             const int hz = site % HZ, hy = (site / HZ) % HY, hx = site / (HZ * HY);
             const int x = x0 + hx - 1, y = y0 + hy - 1, z = z0 + hz - 1;
-            rr[i] = (it < HALO * 4 && x >= 0 && y >= 0 && z >= 0 && x < lin.nx && y < lin.ny && z < lin.nz) ? grid[((size_t)x * lin.ny + y) * lin.nz + z] : -1;
+            rr[i] = lin.row_or_none(grid, x, y, z, it < HALO * 4);
         }
         float4 va[NIT], vb[NIT];
 #pragma unroll
@@ -199,20 +161,18 @@ __global__ __launch_bounds__(BRICK_THREADS) void k_sparse_conv_brick_32_16(const
             const int it = threadIdx.x + i * BRICK_THREADS;
             if (it >= HALO * 4) break;
             const int site = it >> 2, c8 = it & 3;
-            union { h16x2 v2[4]; float4 f4; } bh, bl;
             const float xv[8] = {va[i].x, va[i].y, va[i].z, va[i].w, vb[i].x, vb[i].y, vb[i].z, vb[i].w};
-#pragma unroll
-            for (int j = 0; j < 4; ++j) split_pair(xv[2 * j], xv[2 * j + 1], m1, bh.v2[j], bl.v2[j]);
+            const Split8 b = split8(xv, 0, m1);
             float4* d = reinterpret_cast<float4*>(hl + site * SITE_F);
-            d[c8] = bh.f4;
-            d[4 + c8] = bl.f4;
+            d[c8] = __builtin_bit_cast(float4, b.hi);
+            d[4 + c8] = __builtin_bit_cast(float4, b.lo);
         }
         __syncthreads();
         // ---- compute: 16 z-runs, two per wave ---------------------------------------------------------------------------------------------
         for (int run = wave; run < BRX * BRY; run += BRICK_THREADS / 64) {
             const int rx = run / BRY, ry = run % BRY;
             const int x = x0 + rx, y = y0 + ry, z = z0 + n16;
-            const int q = (x < lin.nx && y < lin.ny && z < lin.nz) ? grid[((size_t)x * lin.ny + y) * lin.nz + z] : -1;
+            const int q = lin.row_or_none(grid, x, y, z);
             if (__ballot(q >= 0) == 0ull) continue;
             f32x4v acc = {0.f, 0.f, 0.f, 0.f}, acc1 = acc, acc2 = acc;      // three independent accumulation chains (the three partial products)
             // halo coordinates of this lane's site: (rx + 1, ry + 1, n16 + 1); neighbour k adds (ox, oy, oz)
@@ -241,21 +201,6 @@ extern "C" {
 
 int o2345_sparse_conv_x3_blob_floats(int cin, int cout) { return 27 * (cin / 16) * ((cout + 31) / 32) * 2 * 256; }
 
-#define O2345_CONVX_LAUNCH(CI, CO, MD, LW)                                                                             \
-    {                                                                                                                   \
-        if (LW) O2345_ENSURE_LDS((k_sparse_conv_x3<CI, CO, MD, LW>), lds);                                                \
-        hipLaunchKernelGGL((k_sparse_conv_x3<CI, CO, MD, LW>), LW ? pgrid : grid, dim3(LW ? 1024 : 256), LW ? lds : 0, s, in, out_coords, n_out, ts_out, in_grid, lin, wblob, out); \
-    }
-#define O2345_CONVX_CASE(CI, CO)                                                                                        \
-    if (cin == CI && cout == CO) {                                                                                      \
-        constexpr size_t lds = (size_t)27 * (CI / 16) * ((CO + 31) / 32) * 2048;                                        \
-        constexpr bool LW = lds <= 120 * 1024;                                                                          \
-        if (mode == 0) O2345_CONVX_LAUNCH(CI, CO, 0, LW)                                                                \
-        else if (mode == 1) O2345_CONVX_LAUNCH(CI, CO, 1, LW)                                                           \
-        else O2345_CONVX_LAUNCH(CI, CO, 2, LW)                                                                          \
-        return check_launch("sparse_conv3d_x3");                                                                        \
-    }
-
 // Same contract as o2345_sparse_conv3d; wblob = the layer's kernel packed by weights.pack_sparse_conv_x3
 // (o2345_sparse_conv_x3_blob_floats(cin, cout) floats).  identity_rows: the caller guarantees output row q = input row q (out_coords IS the list in_grid
 // was built from) -- the precondition of the brick form, which writes out[in_grid[site]] and never reads out_coords (include/o2345.h).
@@ -265,7 +210,7 @@ int o2345_sparse_conv3d_x3(int mode, const float* in, int cin, const int32_t* in
     O2345_REQUIRE(mode >= 0 && mode <= 2, "sparse_conv3d_x3: bad mode %d", mode);
     if (n_out == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
-    Lattice3 lin{gx, gy, gz};
+    Lattice lin{gx, gy, gz};
     dim3 grid(cdiv(n_out, 128));
     const int n_cu = cu_count();
     const unsigned want = cdiv(n_out, 32 * 16);                       // 16 tiles (waves) per persistent workgroup round
@@ -279,8 +224,19 @@ int o2345_sparse_conv3d_x3(int mode, const float* in, int cin, const int32_t* in
             return check_launch("sparse_conv3d_x3 (brick form)");
         }
     }
-    O2345_CONVX_CASE(32, 16) O2345_CONVX_CASE(16, 16) O2345_CONVX_CASE(16, 32) O2345_CONVX_CASE(32, 32)
-    O2345_CONVX_CASE(32, 64) O2345_CONVX_CASE(64, 64) O2345_CONVX_CASE(64, 32) O2345_CONVX_CASE(48, 16)
+    // LW: the layer's operand blob fits in LDS (persistent 1024-thread workgroups); otherwise 256-thread workgroups stream it from L2
+#define O2345_CONVX_CASE(CI, CO)                                                                                        \
+    if (cin == CI && cout == CO) {                                                                                      \
+        constexpr size_t lds = (size_t)27 * (CI / 16) * ((CO + 31) / 32) * 2048;                                        \
+        constexpr bool LW = lds <= 120 * 1024;                                                                          \
+        return with_conv_mode(mode, [&](auto m) {                                                                       \
+            if (LW) O2345_ENSURE_LDS((k_sparse_conv_x3<CI, CO, m.value, LW>), lds);                                      \
+            hipLaunchKernelGGL((k_sparse_conv_x3<CI, CO, m.value, LW>), LW ? pgrid : grid, dim3(LW ? 1024 : 256), LW ? lds : 0, s, in, out_coords, n_out, ts_out, in_grid, lin, wblob, out); \
+            return check_launch("sparse_conv3d_x3");                                                                    \
+        });                                                                                                             \
+    }
+    O2345_SPARSE_CHANNEL_PAIRS(O2345_CONVX_CASE)
+#undef O2345_CONVX_CASE
     O2345_REQUIRE(false, "sparse_conv3d_x3: unsupported channels %d -> %d", cin, cout);
     return -1;
 }

@@ -87,4 +87,32 @@ __device__ __forceinline__ void mfma_x3(f32x16* acc, const h16x8* ahi, const h16
     for (int nb = 0; nb < NB; ++nb) acc[nb] = MFMA_F16(ahi[nb], b.hi, acc[nb]);
 }
 
+// The A operands (weights) of one k step of NB output blocks, as the packers lay them out: [step][block][hi | lo][64 lanes][8 f16], 2 KB per block and
+// step, identical for every wave of a grid.  a_fetch streams them from L2 through a buffer descriptor, a_fetch_lds reads a copy staged in LDS.
+template <int NB>
+struct AOp { h16x8 hi[NB], lo[NB]; };
+
+template <int NB>
+__device__ __forceinline__ AOp<NB> a_fetch_lds(const float* wlds, int step, int lane) {
+    AOp<NB> r;
+    const float4* A = reinterpret_cast<const float4*>(wlds);
+#pragma unroll
+    for (int nb = 0; nb < NB; ++nb) {
+        r.hi[nb] = __builtin_bit_cast(h16x8, A[((step * NB + nb) * 2 + 0) * 64 + lane]);
+        r.lo[nb] = __builtin_bit_cast(h16x8, A[((step * NB + nb) * 2 + 1) * 64 + lane]);
+    }
+    return r;
+}
+template <int NB>
+__device__ __forceinline__ AOp<NB> a_fetch(__amdgpu_buffer_rsrc_t rs, int step, int lane) {
+    AOp<NB> r;
+#pragma unroll
+    for (int nb = 0; nb < NB; ++nb) {
+        const int base = ((step * NB + nb) * 2) * 1024;          // bytes
+        r.hi[nb] = __builtin_bit_cast(h16x8, __builtin_amdgcn_raw_buffer_load_b128(rs, lane * 16, base, 0));
+        r.lo[nb] = __builtin_bit_cast(h16x8, __builtin_amdgcn_raw_buffer_load_b128(rs, lane * 16, base + 1024, 0));
+    }
+    return r;
+}
+
 }  // namespace o2345

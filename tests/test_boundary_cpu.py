@@ -102,6 +102,20 @@ def test_mesh_workspace_sizes_are_pinned():
     assert lib.o2345_mesh_adjacency_workspace_bytes(2 ** 30, 0) == 0 and lib.o2345_mesh_components_workspace_bytes(-1, 0) == 0
 
 
+def test_conv_workspace_sizes_are_pinned():
+    """o2345_conv2d_workspace_bytes bounds the per-block partial sums of every convolution variant by the smallest output tile, 32 x 4 pixels; the
+    constants are those the launches check themselves against (csrc/convnet.hip, CV_MIN_TILE_W / CV_MIN_TILE_H).  The expected sizes were recorded from
+    the library at commit bbd8316, which had the tile size as literals: (V, cout, Ho, Wo) of one pixel, ragged maps, the full-size maps, and one size
+    either side of the 32-column and of the 4-row boundary."""
+    import ctypes
+    lib = importlib.import_module("one-2-3-45_amd._lib").lib()
+    lib.o2345_conv2d_workspace_bytes.restype = ctypes.c_size_t
+    want = {(1, 8, 1, 1): 128, (3, 16, 21, 67): 13824, (3, 32, 130, 258): 456192, (8, 32, 256, 256): 2097152,
+            (2, 16, 4, 32): 512, (2, 16, 4, 33): 1024, (2, 16, 5, 32): 1024, (2, 16, 5, 33): 2048}
+    for shape, size in want.items():
+        assert lib.o2345_conv2d_workspace_bytes(*shape) == size, shape
+
+
 def test_render_io_has_one_declaration_and_the_binding_checks_it(tmp_path):
     """O2345RenderIO is declared in include/o2345.h only: csrc/ compiles that header (common.h includes it), the ctypes Structure is generated from its
     text, and the loaded library's own sizeof / offsetof table is compared at load time.  A field added to ONE side only must fail loudly."""

@@ -913,3 +913,130 @@ def test_render_with_other_sample_counts(dev, ops, ns, ni, lib_instance):
         outs[name] = ops.render_rays(scene, torch.from_numpy(ro).to(dev), torch.from_numpy(rd).to(dev), near, far, ns, ni, 7.4, 1.0, 1.0, qcam, want_z=True)
     for k, v in outs["group"].items():
         assert torch.equal(v, outs["stream"][k]), k
+
+
+# ---- edges of the units that build the volume (csrc/convnet.hip, sparse.hip, sparse_mfma.hip, costvol.hip) which their shared stages own: the producer's
+#      ABN applied on load through a channel-last input, maps smaller than one tile, a lattice whose three axes differ, and the cost-volume entry points
+#      that take an explicit voxel list
+def _f32(rng_array):
+    return torch.from_numpy(np.ascontiguousarray(rng_array, dtype=np.float32))
+
+
+def _abn_act(x, in_ss, slope=0.01):
+    cin = x.shape[1]
+    t = x * in_ss[:cin].view(1, -1, 1, 1) + in_ss[cin:].view(1, -1, 1, 1)
+    return torch.where(t >= 0, t, t * slope)
+
+
+@pytest.mark.parametrize("cin,offset", [(56, 3), (32, 5)])
+@pytest.mark.parametrize("prec", ["f16x3", "fp32"])
+def test_conv2d_abn_on_load_through_channel_last_input(dev, ops, prec, cin, offset):
+    """in_scale_shift together with nhwc_offset: 56 -> 16 at channel 3 runs the staged kernel's channel-last arm, which has its own activation code,
+    32 -> 16 at channel 5 the whole-tile kernel with chan_stride 1.  Same kernel arithmetic as the channel-first copy with other addressing: bit
+    equality of the output and of this layer's (scale | shift); ATen's fp32 convolution of the activated input at the tolerances of
+    test_conv2d_vs_torch; and a repeated call is bit-identical (the statistics are reduced in a fixed order)."""
+    rng = np.random.default_rng(cin + offset)
+    V, H, W, cout = 2, 9, 35, 16
+    cm = _f32(rng.normal(0, 1, (V, H, W, 64)))
+    x = cm[..., offset:offset + cin].permute(0, 3, 1, 2).contiguous()
+    w = _f32(rng.normal(0, 1, (cout, cin, 3, 3)) / np.sqrt(cin * 9))
+    in_ss = _f32(np.concatenate([rng.uniform(-1.5, 1.5, cin), rng.normal(0, 0.3, cin)]))
+    assert (in_ss[:cin] > 0).any() and (in_ss[:cin] < 0).any()
+    gamma, beta = _f32(rng.uniform(-1.5, 1.5, cout)), _f32(rng.normal(0, 0.2, cout))
+    bn = (gamma.to(dev), beta.to(dev), 1e-5, True)
+    y0, ss0 = ops.conv2d(x.to(dev), w.to(dev), None, 1, in_ss.to(dev), 0.01, bn=bn, precision=prec)
+    y1, ss1 = ops.conv2d(cm.to(dev), w.to(dev), None, 1, in_ss.to(dev), 0.01, bn=bn, precision=prec, nhwc_offset=offset)
+    assert torch.equal(y0, y1) and torch.equal(ss0, ss1)
+    ref = torch.nn.functional.conv2d(_abn_act(x, in_ss), w, None, 1, 1)
+    close(y1, ref, rel=1e-5, what="conv2d of the activated channel-last input")
+    rd = ref.double()
+    scale = (gamma.double().abs() + 1e-5) / torch.sqrt(rd.var((0, 2, 3), unbiased=False) + 1e-5)
+    close(ss1[:cout], scale.float(), rel=2e-5, what="ABN scale from the fused statistics")
+    close(ss1[cout:], (beta.double() - rd.mean((0, 2, 3)) * scale).float(), rel=2e-5, what="ABN shift from the fused statistics")
+    y2, ss2 = ops.conv2d(cm.to(dev), w.to(dev), None, 1, in_ss.to(dev), 0.01, bn=bn, precision=prec, nhwc_offset=offset)
+    assert torch.equal(y1, y2) and torch.equal(ss1, ss2)
+
+
+@pytest.mark.parametrize("cin,cout,k,stride", CONV_SHAPES)
+@pytest.mark.parametrize("prec", ["f16x3", "fp32"])
+def test_conv2d_maps_smaller_than_a_tile(dev, ops, cin, cout, k, stride, prec):
+    """One view of 1 x 1, 2 x 3 and 5 x 4 pixels: every staged pixel but a few lies outside the image, every tile is ragged on both axes.  Outputs
+    only, against ATen's fp32 convolution on the CPU (itself within 1e-6 of a float64 convolution here, same scale rule): with so few values the batch
+    variance is within fp32 rounding of zero and 1 / sqrt(var + 1e-5) magnifies rounding far beyond 2e-5, so the statistics are not compared."""
+    rng = np.random.default_rng(cin * 100 + cout + k)
+    for hw in ((1, 1), (2, 3), (5, 4)):
+        x = _f32(rng.normal(0.2, 1.0, (1, cin) + hw))
+        w = _f32(rng.normal(0, 1.0, (cout, cin, k, k)) / np.sqrt(cin * k * k))
+        b = _f32(rng.normal(0, 0.3, cout))
+        in_ss = _f32(np.concatenate([rng.uniform(-1.5, 1.5, cin), rng.normal(0, 0.3, cin)]))
+        xa = _abn_act(x, in_ss)
+        for inp, bias, ss in ((x, b, None), (xa, None, in_ss)):
+            ref = torch.nn.functional.conv2d(inp, w, bias, stride, k // 2)
+            ref64 = torch.nn.functional.conv2d(inp.double(), w.double(), None if bias is None else bias.double(), stride, k // 2)
+            close(ref, ref64, rel=1e-6, what=f"ATen fp32 vs float64 {hw}")
+            y, _ = ops.conv2d(x.to(dev), w.to(dev), None if bias is None else bias.to(dev), stride, None if ss is None else ss.to(dev), 0.01, precision=prec)
+            assert y.shape == ref.shape
+            close(y, ref, rel=1e-5, what=f"conv2d {hw} " + ("with bias" if ss is None else "of the activated input"))
+
+
+@pytest.mark.parametrize("occupancy", ["full", "random"])
+@pytest.mark.parametrize("cin,cout,mode,identity_rows", [(32, 16, 0, True), (32, 16, 0, False), (16, 32, 1, False), (64, 32, 2, False)])
+def test_sparse_conv_on_a_lattice_with_three_different_axes(dev, ops, cin, cout, mode, identity_rows, occupancy):
+    """The lattice (9, 6, 20): an index expression that takes ny for nz is wrong here (it is not on a cube), and the 4 x 4 x 16 brick is partial on all
+    three axes.  Fully occupied, every face and corner runs the bounds test of the neighbour rule; 30 % random as in test_sparse_conv_x3_single_layer.
+    Matrix-core form (brick with identity_rows, gather without), fp32 form and the oracle's sparse convolution at that test's tolerance."""
+    Wn = importlib.import_module("one-2-3-45_amd.weights")
+    rng = np.random.default_rng(cin * 100 + cout + mode)
+    cells = (9, 6, 20)
+    occ = np.ones(cells, bool) if occupancy == "full" else rng.random(cells) < 0.3
+    xyz = np.argwhere(occ).astype(np.int32)                             # x-major order
+    coords = torch.from_numpy(np.ascontiguousarray(np.concatenate([xyz, np.zeros((len(xyz), 1), np.int32)], 1))).to(dev).contiguous()
+    grid0 = ops.build_index_grid(coords, 1, cells)
+    g1, co1, n1, cells1 = ops.sparse_downsample(coords, 1, cells)
+    L0 = O.SparseLevel(torch.from_numpy(xyz).long(), 1)
+    L1 = O.downsample_coords(L0)
+    assert torch.equal(L1.xyz, co1[:, :3].cpu().long())                 # the coarse coordinate set, in torch.unique order
+    assert all(int(L1.xyz[:, a].max()) // 2 < cells1[a] for a in range(3))
+    K = _f32(rng.normal(0, 0.2, (27, cin, cout))).to(dev)
+    blob = torch.from_numpy(Wn.pack_sparse_conv_x3(K)).to(dev)
+    if mode == 0:
+        x = _f32(rng.normal(0, 1, (len(xyz), cin))).to(dev)
+        args = (x, grid0, cells, coords, 1)
+    elif mode == 1:
+        x = _f32(rng.normal(0, 1, (len(xyz), cin))).to(dev)
+        args = (x, grid0, cells, co1, 2)
+    else:
+        x = _f32(rng.normal(0, 1, (n1, cin))).to(dev)
+        args = (x, g1, cells1, coords, 1)
+    ref = ops.sparse_conv3d(mode, *args, K)
+    got = ops.sparse_conv3d_x3(mode, *args, blob, cout, identity_rows=identity_rows)
+    kmap = O.build_kmap(L0, L0) if mode == 0 else O.build_kmap(L0, L1)
+    want = O.sparse_conv(x.cpu(), kmap, K.cpu(), transposed=(mode == 2), n_out=len(xyz) if mode == 2 else None)
+    close(got, ref, rel=2e-5, what=f"sparse conv x3 vs fp32 {cin}->{cout} mode {mode}")
+    close(got, want, rel=2e-5, what=f"sparse conv x3 vs oracle {cin}->{cout} mode {mode}")
+    close(ref, want, rel=2e-5, what=f"sparse conv fp32 vs oracle {cin}->{cout} mode {mode}")
+
+
+def test_costvol_list_forms(dev, ops):
+    """o2345_visible_count_list and o2345_costvol_gather_list (the lod > 0 path: an explicit voxel list in any order) on the kept voxels of the grid
+    form, reversed: the counts equal the grid's (integer work of the same function), the rows match the oracle's, and with 8 channels both forms run
+    costvol_row<8> and agree bit for bit.  With 16 channels the grid form exchanges its tap sets inside lane quads; it accumulates the same four taps
+    in the same order (tap4_accumulate, costvol_var_mean of csrc/costvol_math.h), and the library this test was written against (commit bbd8316)
+    already gave bit-equal rows, so bit equality is asserted there too."""
+    s = small_scene()
+    d = dev_scene(s, dev, ops)
+    D, V, H, W = s["D"], s["V"], s["H"], s["W"]
+    vs, origin = s["voxel_size"], s["sc"]["partial_vol_origin"]
+    nhwc = ops.nchw_to_nhwc(d["feats"])
+    cnt, row, coords, n = ops.costvol_index(d["aff"], V, H, W, (D, D, D), vs, origin)
+    rev = coords[:n].flip(0).contiguous()
+    lin = (rev[:, 0].long() * D + rev[:, 1].long()) * D + rev[:, 2].long()
+    cnt_row = ops.visible_count_list(d["aff"], H, W, vs, origin, rev)
+    assert torch.equal(cnt_row, cnt[lin])
+    rows_list = ops.costvol_gather_list(nhwc, d["aff"], vs, origin, cnt_row, rev)
+    close(rows_list, s["vol"].flip(0), what="cost volume rows of a reversed list")
+    nhwc8 = nhwc[..., :8].contiguous()
+    assert torch.equal(ops.costvol_gather(nhwc8, d["aff"], (D, D, D), vs, origin, cnt, rev), ops.costvol_gather_list(nhwc8, d["aff"], vs, origin, cnt_row, rev))
+    rows_grid = ops.costvol_gather(nhwc, d["aff"], (D, D, D), vs, origin, cnt, rev)
+    close(rows_grid, s["vol"].flip(0), what="cost volume rows, grid form on the reversed list")
+    assert torch.equal(rows_grid, rows_list)
