@@ -50,7 +50,8 @@ const char* o2345_last_error(void);
  * o2345_mesh_components_workspace_bytes, o2345_mesh_components_count, o2345_mesh_components_emit; the adjacency and smoothing entries
  * o2345_mesh_adjacency_workspace_bytes, o2345_mesh_adjacency_count, o2345_mesh_adjacency_emit, o2345_mesh_smooth; the decimation entries
  * o2345_mesh_decimate_workspace_bytes, o2345_mesh_decimate_count, o2345_mesh_decimate_emit; the projection entries
- * o2345_mesh_project_workspace_bytes, o2345_mesh_project. */
+ * o2345_mesh_project_workspace_bytes, o2345_mesh_project; the sparse lattice entries o2345_sdf_grid_sparse_workspace_bytes,
+ * o2345_sdf_grid_sparse_x3. */
 int o2345_version(void);
 /* Layout self-description of O2345RenderIO as THIS library was compiled (sizeof, and offsetof of every field in declaration order): a binding
  * asserts its own struct against it at load time (one-2-3-45_amd/_lib.py does) -- a field added on one side only cannot corrupt calls silently.
@@ -200,6 +201,17 @@ int o2345_sdf_grad_x3(const float* blob, const float* vol_cl, int D, const float
 int o2345_sdf_grid_tables(const float* tab_axes, const float* bias_lane_order, int grid_R, float* tab_xy, void* stream);
 int o2345_sdf_grid_x3(const float* blob, const float* vol_cl, int D, int grid_R, float sign, const float* tab_xy, const float* tab_z,
                       float* out_sdf, void* stream);
+/* o2345_sdf_grid_x3 evaluated only where the scene has a latent (additive since 2.1).  maskvol [D^3]: the occupancy volume (0 = unkept).
+ * The CALLER GUARANTEES (a) that vol_cl is zero wherever maskvol is zero -- what o2345_scatter_dense writes -- and (b) that background [R^3] is
+ * o2345_sdf_grid_x3's out_sdf for the same blob, tab_xy and tab_z with sign = +1 on a latent volume of zeros (any D: a 2^3 one will do).
+ * A lattice point whose trilinear sampler is off (index 0 of an axis) or none of whose eight corner voxels is kept samples a latent of exactly
+ * zero, so its SDF is the background's: a pre-pass copies sign * background into every aligned tile of 32 slots without an active point and lists
+ * the slots of the other tiles (device-side count, no read-back); only those run the network.  out_sdf equals o2345_sdf_grid_x3's bit for bit.
+ * With a volume that breaks (a), the points whose corners are all unkept get the background's value instead of the volume's.
+ * workspace: o2345_sdf_grid_sparse_workspace_bytes(grid_R) bytes, 16-byte aligned (0 = grid_R out of range: needs 2 <= grid_R, grid_R^3 < 2^31). */
+size_t o2345_sdf_grid_sparse_workspace_bytes(int grid_R);
+int o2345_sdf_grid_sparse_x3(const float* blob, const float* vol_cl, const float* maskvol, int D, int grid_R, float sign, const float* tab_xy,
+                             const float* tab_z, const float* background, float* out_sdf, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- ray rendering (replaces models/sparse_neus_renderer.py:457 render and everything it calls) ------------------
  * Per-sample arrays are sample-major [S][R]. */

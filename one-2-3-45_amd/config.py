@@ -69,10 +69,6 @@ def prepack_resolutions():
     return tuple(int(x) for x in v.replace(",", " ").split())
 
 
-# ---- mesh component filter (csrc/mesh_components.hip; mesh_io.filter_components is the host twin) ----------------------------------------------------
-# O2345_MESH_MIN_COMPONENT_FACES=n drops the connected components of the extracted mesh with fewer than n faces; O2345_MESH_KEEP_LARGEST=1 keeps only the
-# component with the most faces (ties: the smaller label), among what the threshold left.  Both off by default ("" or "0" = off, like the other knobs): the
-# mesh is then what marching cubes found, as before.  The filter runs on the device between marching cubes and vertex colouring.
 def _non_negative_int(name, text):
     t = text.strip()
     if t == "":
@@ -82,6 +78,30 @@ def _non_negative_int(name, text):
     return int(t)
 
 
+# ---- background table of the extraction lattice (csrc/sdf_mlp_x3.hip, o2345_sdf_grid_sparse_x3) ---------------------------------------------------------
+# A lattice point without a kept voxel among its trilinear corners has the SDF of an empty scene, which depends on the weights and the resolution only:
+# pipeline.SceneWeights.grid_background keeps that field, R^3 floats per (weights, R), from the SECOND extraction at a resolution on, and the lattice
+# kernel then runs on the tiles that touch the scene only.  O2345_GRID_BACKGROUND_MB is the largest table kept, in MiB: unset or "" = 256 (R <= 406),
+# 0 = never (every extraction evaluates the whole lattice, as before); a table over the budget or R^3 >= 2^31 means the same.  Results are identical.
+_gb = os.environ.get("O2345_GRID_BACKGROUND_MB", "")
+GRID_BACKGROUND_MB = 256 if _gb.strip() == "" else _non_negative_int("O2345_GRID_BACKGROUND_MB", _gb)
+del _gb
+
+
+def grid_background_mb():
+    return GRID_BACKGROUND_MB
+
+
+def grid_background_allowed(resolution):
+    """True when a background table for this resolution fits the budget and the sparse evaluation's 32-bit slots."""
+    n = int(resolution) ** 3
+    return n < 2 ** 31 and 4 * n <= grid_background_mb() << 20
+
+
+# ---- mesh component filter (csrc/mesh_components.hip; mesh_io.filter_components is the host twin) ----------------------------------------------------
+# O2345_MESH_MIN_COMPONENT_FACES=n drops the connected components of the extracted mesh with fewer than n faces; O2345_MESH_KEEP_LARGEST=1 keeps only the
+# component with the most faces (ties: the smaller label), among what the threshold left.  Both off by default ("" or "0" = off, like the other knobs): the
+# mesh is then what marching cubes found, as before.  The filter runs on the device between marching cubes and vertex colouring.
 MESH_MIN_COMPONENT_FACES = _non_negative_int("O2345_MESH_MIN_COMPONENT_FACES", os.environ.get("O2345_MESH_MIN_COMPONENT_FACES", ""))
 MESH_KEEP_LARGEST = _non_negative_int("O2345_MESH_KEEP_LARGEST", os.environ.get("O2345_MESH_KEEP_LARGEST", "")) != 0
 

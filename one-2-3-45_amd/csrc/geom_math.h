@@ -75,6 +75,37 @@ O2345_HD Taps3D trilinear_ref_taps(float px, float py, float pz, int D) {
     return t;
 }
 
+// torch.linspace(-1, 1, R)[i] in fp32, bit-exact with ATen's CPU kernel (symmetric evaluation, fused multiply-add)
+O2345_HD float lin11(int i, int R) {
+    const float step = 2.f / (float)(R - 1);
+    return (i < R / 2) ? fmaf(step, (float)i, -1.f) : fmaf(-step, (float)(R - 1 - i), 1.f);
+}
+
+// Activity of a point of the extraction lattice linspace(-1,1,R)^3 (x-major slot = (ix * R + iy) * R + iz, R^3 < 2^31) against the occupancy volume
+// maskvol [D^3]: the trilinear sampler reads a latent there (`ok`) and at least one of the eight corner voxels it reads is kept (mask != 0).  The corner
+// indices are trilinear_ref_taps' own; the weights are ignored (a corner of weight 0 still counts: conservative, never the other way).  In a latent volume
+// that is zero wherever the mask is zero, an inactive point samples a latent of exactly zero.
+O2345_HD bool grid_point_active(long long slot, int R, int D, const float* __restrict__ maskvol) {
+    const unsigned us = (unsigned)slot, uR = (unsigned)R, uq = us / uR;
+    const int iz = (int)(us - uq * uR), ix = (int)(uq / uR), iy = (int)(uq - (uq / uR) * uR);
+    const Taps3D tp = trilinear_ref_taps(lin11(ix, R), lin11(iy, R), lin11(iz, R), D);
+    bool kept = false;
+    for (int dx = 0; dx < 2; ++dx)
+        for (int dy = 0; dy < 2; ++dy)
+            for (int dz = 0; dz < 2; ++dz) kept |= maskvol[((size_t)tp.ix[dx] * D + tp.iy[dy]) * D + tp.iz[dz]] != 0.f;
+    return tp.ok && kept;
+}
+
+// A tile is an aligned run of GRID_TILE consecutive slots (the last one may be partial, and with R no multiple of GRID_TILE tiles straddle rows); it is
+// active if any of its points is.  The pre-pass of the sparse lattice evaluation (csrc/sdf_mlp_x3.hip) forms this OR with a ballot over 32 lanes.
+constexpr int GRID_TILE = 32;
+O2345_HD bool grid_tile_active(long long tile, int R, int D, const float* __restrict__ maskvol) {
+    const long long n = (long long)R * R * R, lo = tile * GRID_TILE, hi = lo + GRID_TILE < n ? lo + GRID_TILE : n;
+    for (long long s = lo; s < hi; ++s)
+        if (grid_point_active(s, R, D, maskvol)) return true;
+    return false;
+}
+
 // F.grid_sample(mode='nearest', align_corners=False, zeros) on the occupancy volume
 // (sparse_neus_renderer.py:153-169): index = nearbyint(((g+1)*D-1)/2) (half-to-even); out of range -> -1.
 O2345_HD int nearest_index(float g, int D) {

@@ -1,4 +1,4 @@
-// Shared pieces of the SDF-network kernels (csrc/sdf_mlp.hip: exact fp32 MFMA; csrc/sdf_mlp_x3.hip: split-f16 operands): blob geometry, LDS layouts, argument block, softplus, ATen-exact linspace, the per-point stages every kernel runs (point of the tile lane, latent gather, positional encoding, bias, softplus + split, chain rule, latent Jacobian), A-operand fetch, the pinned MFMA step loop and the launch body.
+// Shared pieces of the SDF-network kernels (csrc/sdf_mlp.hip: exact fp32 MFMA; csrc/sdf_mlp_x3.hip: split-f16 operands): blob geometry, LDS layouts, argument block, softplus, the per-point stages every kernel runs (point of the tile lane, latent gather, positional encoding, bias, softplus + split, chain rule, latent Jacobian), A-operand fetch, the pinned MFMA step loop and the launch body.
 #pragma once
 #include "common.h"
 #include "geom_math.h"
@@ -150,12 +150,6 @@ __device__ __forceinline__ float softplus_t_d(float t) {
 // derivative only (the gradient kernels re-evaluate layer 0 just for this): sigmoid(100 a) = 1 / (1 + exp(-100 a))
 __device__ __forceinline__ float softplus100_d(float a) {
     return __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(a * -144.269504088896340736f));
-}
-
-// torch.linspace(-1, 1, R)[i] in fp32, bit-exact with ATen's CPU kernel (symmetric evaluation, fused multiply-add)
-__device__ __forceinline__ float lin11(int i, int R) {
-    const float step = 2.f / (float)(R - 1);
-    return (i < R / 2) ? fmaf(step, (float)i, -1.f) : fmaf(-step, (float)(R - 1 - i), 1.f);
 }
 
 // ---- per-point stages: a wave owns 32 points (column j = lane & 31), both wave halves h = lane >> 5 hold the same point ---------------------------

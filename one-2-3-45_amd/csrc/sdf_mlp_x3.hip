@@ -244,6 +244,43 @@ __global__ __launch_bounds__(512) void k_sdf_grad_x3(SdfArgs a) {
     }
 }
 
+// Pre-pass of the sparse lattice evaluation (o2345_sdf_grid_sparse_x3): one lane per lattice point, 32 lanes per tile.  A tile none of whose points is
+// active (geom_math.h grid_point_active) gets out = sign * background; the slots of every other tile are appended to `index`, 32 per tile, and
+// *n_active (zeroed by the launcher) counts them -- the per-point list and device-side count that k_sdf_mlp_x3 already takes.  A workgroup owns
+// GRID_CHUNK_TILES consecutive tiles and reserves its stretch of the list with ONE atomic; the order of the stretches is free, results are scattered by
+// slot.  The pad lanes of a partial last tile repeat the last slot: the same point, evaluated to the same value, stored to the same address.
+constexpr int GRID_CHUNK_TILES = 256;     // = threads per workgroup: the compaction gives every tile of the chunk one thread
+constexpr size_t GRID_WS_HEAD = 256;      // workspace: the count (int32) in a block of its own, then the list
+static_assert(GRID_TILE == 32 && GRID_CHUNK_TILES % 64 == 0, "a tile is one half of a wave, as in k_sdf_mlp_x3");
+__global__ __launch_bounds__(GRID_CHUNK_TILES) void k_grid_active_tiles(const float* __restrict__ maskvol, int D, int R, const float* __restrict__ background,
+                                                                        float sign, float* __restrict__ out, int32_t* __restrict__ index, int32_t* n_active) {
+    __shared__ int s_active[GRID_CHUNK_TILES], s_list[GRID_CHUNK_TILES], s_wave[GRID_CHUNK_TILES / 64 + 1], s_base;
+    const long long n = (long long)R * R * R;
+    const long long tile0 = (long long)blockIdx.x * GRID_CHUNK_TILES;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, half = lane >> 5;
+    for (int it = 0; it < GRID_CHUNK_TILES / 8; ++it) {
+        const int t = it * 8 + wave * 2 + half;                       // tile of the chunk: two per wave and iteration
+        const long long slot = (tile0 + t) * GRID_TILE + (lane & 31);
+        const bool live = slot < n;
+        const unsigned long long b = __ballot(live && grid_point_active(slot, R, D, maskvol));
+        const bool tile_active = (half ? (b >> 32) : (b & 0xffffffffull)) != 0;
+        if (live && !tile_active) out[slot] = sign * background[slot];
+        if ((lane & 31) == 0) s_active[t] = tile_active;
+    }
+    __syncthreads();
+    const bool mine = s_active[threadIdx.x] != 0;
+    int total;
+    const int pos = block_prefix<GRID_CHUNK_TILES / 64>(mine, s_wave, total);
+    if (mine) s_list[pos] = threadIdx.x;
+    if (threadIdx.x == 0) s_base = total ? atomicAdd(n_active, total * GRID_TILE) : 0;
+    __syncthreads();
+    const int base = s_base;
+    for (int e = threadIdx.x; e < total * GRID_TILE; e += GRID_CHUNK_TILES) {
+        const long long slot = (tile0 + s_list[e >> 5]) * GRID_TILE + (e & 31);
+        index[base + e] = (int32_t)(slot < n ? slot : n - 1);
+    }
+}
+
 }  // namespace o2345
 
 using namespace o2345;
@@ -295,6 +332,34 @@ int o2345_sdf_grid_x3(const float* blob, const float* vol_cl, int D, int grid_R,
     const long long n = (long long)grid_R * grid_R * grid_R;
     const SdfArgs a{blob, vol_cl, D, nullptr, nullptr, nullptr, n, grid_R, sign, out_sdf, nullptr, nullptr, nullptr, nullptr, tab_xy, tab_z};
     return sdf_launch<k_sdf_mlp_x3<true>, LDSX_MLP_FLOATS>("sdf_grid_x3", a, stream);
+}
+
+size_t o2345_sdf_grid_sparse_workspace_bytes(int grid_R) {
+    if (grid_R < 2 || (long long)grid_R * grid_R * grid_R >= (1ll << 31)) return 0;
+    const long long ntiles = ((long long)grid_R * grid_R * grid_R + GRID_TILE - 1) / GRID_TILE;
+    return GRID_WS_HEAD + (size_t)ntiles * GRID_TILE * sizeof(int32_t);
+}
+
+// o2345_sdf_grid_x3 evaluated only where the scene has a latent (the caller's two guarantees: include/o2345.h).  An inactive point samples a latent of
+// exactly zero: the latent k-step and the W2L dot product of k_sdf_mlp_x3 add exact zeros, so its value is the background's, and sign = -1 is an exact
+// negation.  Every other 32-slot tile goes through k_sdf_mlp_x3<true> with the same inputs as in o2345_sdf_grid_x3: out_sdf is that entry's bit for bit.
+int o2345_sdf_grid_sparse_x3(const float* blob, const float* vol_cl, const float* maskvol, int D, int grid_R, float sign, const float* tab_xy,
+                             const float* tab_z, const float* background, float* out_sdf, void* workspace, size_t workspace_bytes, void* stream) {
+    if (const int rc = sdf_x3_check("sdf_grid_sparse_x3", blob && vol_cl && maskvol && background && out_sdf && tab_xy && tab_z && workspace, D, false, grid_R))
+        return rc;
+    const long long n = (long long)grid_R * grid_R * grid_R;
+    O2345_REQUIRE(n < (1ll << 31), "sdf_grid_sparse_x3: grid_R^3 must stay below 2^31 (got %d)", grid_R);
+    O2345_REQUIRE(workspace_bytes >= o2345_sdf_grid_sparse_workspace_bytes(grid_R) && ((uintptr_t)workspace & 15) == 0,
+                  "sdf_grid_sparse_x3: workspace too small or misaligned");
+    int32_t* n_active = reinterpret_cast<int32_t*>(workspace);
+    int32_t* index = reinterpret_cast<int32_t*>(static_cast<char*>(workspace) + GRID_WS_HEAD);
+    O2345_HIP(hipMemsetAsync(n_active, 0, sizeof(int32_t), (hipStream_t)stream));
+    const long long ntiles = (n + GRID_TILE - 1) / GRID_TILE;
+    hipLaunchKernelGGL(k_grid_active_tiles, dim3(cdiv(ntiles, GRID_CHUNK_TILES)), dim3(256), 0, (hipStream_t)stream, maskvol, D, grid_R, background, sign,
+                       out_sdf, index, n_active);
+    if (const int rc = check_launch("sdf_grid_sparse_x3 (active tiles)")) return rc;
+    const SdfArgs a{blob, vol_cl, D, nullptr, index, n_active, n, grid_R, sign, out_sdf, nullptr, nullptr, nullptr, nullptr, tab_xy, tab_z};
+    return sdf_launch<k_sdf_mlp_x3<true>, LDSX_MLP_FLOATS>("sdf_grid_sparse_x3", a, stream);
 }
 
 }  // extern "C"

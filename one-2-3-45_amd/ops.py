@@ -425,11 +425,16 @@ def sdf_grid_tables(tab_axes, bias_lane_order):
 
 @_on_device
 def sdf_mlp(blob, vol_cl, pts=None, variant=0, grid_R=0, sign=1.0, index=None, n_dev=None, want_lat=False, out=None, lat_in=None,
-            precision=None, grid_tables=None):
+            precision=None, grid_tables=None, maskvol=None, grid_background=None):
     """variant 0: sdf; 1: sdf + 128 features; 2: sdf + gradient.  pts [P,3] or grid_R.  lat_in [P,16]: given latents instead of
     sampling the volume (get_sdf_volume).  precision "f16x3" (default): split-f16 MFMA at fp32-class accuracy (variants 0 and 2; variant 1 / lat_in
     run on the fp32 kernel); "fp32": the exact fp32 MFMA kernels.  grid_tables (f16x3, variant 0, lattice mode): (tab_xy, tab_z) from
-    ops.sdf_grid_tables -- layer 0 read from per-axis tables instead of being evaluated per point.  Returns dict of tensors."""
+    ops.sdf_grid_tables -- layer 0 read from per-axis tables instead of being evaluated per point.
+    maskvol [D^3] + grid_background [R^3] (with grid_tables only; both or neither): the lattice is evaluated only where the scene has a latent
+    (o2345_sdf_grid_sparse_x3).  The caller guarantees that vol_cl is zero wherever maskvol is zero (ops.scatter_dense's pair) and that grid_background
+    is this call's own result with sign = +1 on a volume of zeros (pipeline.SceneWeights.grid_background); the result is the full evaluation's bit for
+    bit.  Every other form -- the fp32 lattice mode (k_sdf_mlp<0>) among them -- keeps the full evaluation and rejects the two arguments.
+    Returns dict of tensors."""
     precision = config.sdf_precision(precision)
     D = vol_cl.shape[0]
     dev = vol_cl.device
@@ -447,6 +452,10 @@ def sdf_mlp(blob, vol_cl, pts=None, variant=0, grid_R=0, sign=1.0, index=None, n
         res["grad"] = torch.empty(P, 3, dtype=torch.float32, device=dev)
     if want_lat and "lat" not in res:
         res["lat"] = torch.empty(P, 16, dtype=torch.float32, device=dev)
+    sparse = maskvol is not None or grid_background is not None
+    if sparse and not (maskvol is not None and grid_background is not None and precision == "f16x3" and variant == 0 and not want_lat and lat_in is None
+                       and grid_tables is not None and pts is None and index is None and n_dev is None):
+        raise ValueError("sdf_mlp: maskvol and grid_background come together and with grid_tables only (f16x3, variant 0, the whole lattice)")
     if P == 0 or (n == 0 and n_dev is None):
         return res
     if precision == "f16x3" and variant == 0 and not want_lat and lat_in is None:
@@ -454,6 +463,16 @@ def sdf_mlp(blob, vol_cl, pts=None, variant=0, grid_R=0, sign=1.0, index=None, n
             tab_xy, tab_z = grid_tables                  # lattice mode with layer 0 tabulated (weights.sdf_grid_tables + ops.sdf_grid_tables)
             if tuple(tab_xy.shape) != (int(grid_R) ** 2, 128) or tuple(tab_z.shape) != (int(grid_R), 128):
                 raise ValueError(f"sdf_mlp: grid tables were built for another resolution than {grid_R}")
+            if sparse:
+                if maskvol.numel() != D ** 3 or grid_background.numel() != P or P >= 2 ** 31:
+                    raise ValueError(f"sdf_mlp: maskvol [{D}^3] and grid_background [{grid_R}^3 < 2^31] expected, got {maskvol.numel()} and "
+                                     f"{grid_background.numel()} elements")
+                L = _lib.lib()
+                wsb = L.o2345_sdf_grid_sparse_workspace_bytes(int(grid_R))
+                ws = _workspace(wsb, dev, "sdf_grid_sparse")
+                check(L.o2345_sdf_grid_sparse_x3(_p(blob), _p(vol_cl), _p(maskvol), D, int(grid_R), float(sign), _p(tab_xy), _p(tab_z), _p(grid_background),
+                                                 _p(res["sdf"]), _p(ws, torch.uint8), wsb, _stream()), "sdf_grid_sparse_x3")
+                return res
             check(_lib.lib().o2345_sdf_grid_x3(_p(blob), _p(vol_cl), D, int(grid_R), float(sign), _p(tab_xy), _p(tab_z), _p(res["sdf"]), _stream()),
                   "sdf_grid_x3")
             return res
@@ -468,6 +487,14 @@ def sdf_mlp(blob, vol_cl, pts=None, variant=0, grid_R=0, sign=1.0, index=None, n
                                       n, int(grid_R), float(sign), _p(lat_in), _p(res["sdf"]), _p(res.get("feat")), _p(res.get("lat")),
                                       _p(res.get("grad")), _stream()), "sdf_mlp")
     return res
+
+
+def sdf_grid_active_points(device):
+    """Lattice slots that the last sdf_mlp(..., maskvol=, grid_background=) call on the current stream of ``device`` listed for evaluation (32 per active
+    tile), read from the device-side count in its workspace, or None before any such call.  Synchronises: for tests and profiling notes."""
+    with torch.cuda.device(device):
+        ws = _ws_cache.get(("sdf_grid_sparse", str(torch.device(device)), torch.cuda.current_stream(device).cuda_stream))
+    return None if ws is None else int(ws[:4].view(torch.int32).item())
 
 
 # ---------------------------------------------------------------------------------------------------------- colour

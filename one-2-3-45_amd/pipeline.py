@@ -41,6 +41,8 @@ class SceneWeights:
         self.color_xblob = t(weights.pack_color_x3_blob(self.color_sd))
         self.costreg = CostRegNet(self.costreg_sd, device, precision=color_precision)      # sparse convolutions follow the same mode
         self._grid_tabs = {}
+        self._grid_bg = {}                # resolution -> background table (grid_background)
+        self._grid_extractions = {}       # resolution -> extractions that asked for one
         self.variance = float(variance)
         self.inv_s = float(np.clip(np.exp(10.0 * variance), 1e-6, 1e6))
 
@@ -54,6 +56,24 @@ class SceneWeights:
             dev = self.sdf_blob.device
             self._grid_tabs[R] = ops.sdf_grid_tables(torch.from_numpy(axes).to(dev), torch.from_numpy(bias).to(dev))
         return self._grid_tabs[R]
+
+    def grid_background(self, resolution):
+        """u of an EMPTY scene on the extraction lattice, [R^3] for sign +1: the lattice kernel itself on a volume of zeros, so that a point without a
+        kept voxel among its trilinear corners has exactly this value in every scene these weights reconstruct (ops.sdf_mlp, ``grid_background``).
+        Owned like the layer-0 tables, next to them; built and used on the caller's current stream.  Built at the SECOND extraction at a resolution,
+        never at the first: a process that extracts one mesh pays nothing and allocates nothing.  None (= evaluate the whole lattice) for that first
+        extraction, in fp32 mode, and wherever config.grid_background_allowed says no (O2345_GRID_BACKGROUND_MB)."""
+        R = int(resolution)
+        if self.sdf_precision != "f16x3" or not config.grid_background_allowed(R):
+            return None
+        if R not in self._grid_bg:
+            seen = self._grid_extractions.get(R, 0)
+            self._grid_extractions[R] = seen + 1
+            if seen == 0:
+                return None
+            empty = torch.zeros(2, 2, 2, 16, dtype=torch.float32, device=self.sdf_blob.device)
+            self._grid_bg[R] = ops.sdf_mlp(self.sdf_blob, empty, None, variant=0, grid_R=R, sign=1.0, precision="f16x3", grid_tables=self.grid_tables(R))["sdf"]
+        return self._grid_bg[R]
 
     @classmethod
     def from_state_dicts(cls, device, sdf_network_sd, rendering_network_sd, variance, featurenet_sd=None, sdf_precision=None, color_precision=None):
@@ -227,7 +247,11 @@ def _mesh_fields(wt, vol, proj, cam_pos, resolution, min_component_faces=None, k
     cell = config.mesh_decimate_cell(decimate_cell)
     project = config.mesh_project_iterations(project_iterations)
     prec = wt.sdf_precision
-    u = ops.sdf_mlp(wt.sdf_blob, vol["vol_cl"], None, variant=0, grid_R=resolution, sign=-1.0, precision=prec, grid_tables=wt.grid_tables(resolution))["sdf"]
+    # build_volume's pair: ops.scatter_dense writes zeros into vol_cl wherever maskvol is zero, which is what the sparse lattice evaluation needs (a
+    # hand-made ``vol`` must keep that: points without a kept corner voxel get the empty scene's value from the second extraction on)
+    bg = wt.grid_background(resolution)
+    u = ops.sdf_mlp(wt.sdf_blob, vol["vol_cl"], None, variant=0, grid_R=resolution, sign=-1.0, precision=prec, grid_tables=wt.grid_tables(resolution),
+                    maskvol=vol["maskvol"] if bg is not None else None, grid_background=bg)["sdf"]
     u = u.view(resolution, resolution, resolution)
     verts_idx, tris = ops.marching_cubes(u, 0.0)
     cc = None

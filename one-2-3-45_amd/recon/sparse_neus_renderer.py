@@ -480,7 +480,8 @@ class SparseNeuSRenderer(nn.Module):
         """u = -sdf on linspace(bound_min, bound_max, resolution)^3 (:881-905), as a DEVICE tensor [R,R,R].  The reference's own bounds (-1, 1): one fused
         launch, lattice generated in-kernel, layer 0 from per-axis tables.  Any other box: the three axes from torch.linspace on the host exactly as the
         reference builds them (:887-889), the lattice points materialised once on the device, one launch of the point kernel (instead of 64 chunks with a
-        device -> host copy each)."""
+        device -> host copy each).  Always the whole lattice: the call receives a conditional volume without the mask it was scattered with, so the
+        guarantee of the sparse evaluation (ops.sdf_mlp, ``maskvol`` / ``grid_background``) cannot be given here; pipeline.extract_mesh uses it."""
         vol = kwargs["conditional_volume"]
         layer = self.sdf_network.sdf_layer
         R = int(resolution)
