@@ -1,7 +1,7 @@
 // Device helpers shared by the two colour-network kernels (csrc/color_mfma.hip: columns = (point, view) pairs;
 // csrc/color_pts.hip: columns = points, views looped): blob layout, matrix-step loops in both numerical forms, the scaled-domain
-// ELU, DPP group reductions, projection.  See csrc/color_mfma.hip for the layer structure and weights.pack_color_mfma_blob /
-// pack_color_x3_blob for the operand order.
+// ELU, DPP group reductions, projection, and the per-point / per-view stages both evaluate (gather, ray_dir_fc, the per-view network).
+// See csrc/color_mfma.hip for the layer structure and weights.pack_color_mfma_blob / pack_color_x3_blob for the operand order.
 #pragma once
 #include "common.h"
 #include "geom_math.h"
@@ -62,7 +62,7 @@ struct ColorMArgs {
     const float* f_mask;      // [V,P]     non-zero = the projection is valid
     unsigned long long* stats;  // optional caller-owned device counters (stats_dev of o2345_color_points_*): [0] += (tile, view) pairs evaluated in pass A, [1] += in pass B,
                               // [2] += tiles, [3] += tiles that evaluated every view in pass B because one of their points has no visible view
-    int sched;                // scheduling knobs (O2345_COLOR_SCHED; default 10 = bits 1 + 3, measured on MI355X with tools/ab_sched.py):
+    int sched;                // scheduling knobs (O2345_COLOR_SCHED; default 10 = bits 1 + 3, measured on MI355X, profiles/NOTES.md "Wave priorities in the colour kernels"):
                               //   bit 0  static wave priority by SIMD slot (the k-th wave of a SIMD runs at priority k): no gain
                               //   bit 1  priority 3 while a wave issues its pixel gathers: -1.5 %
                               //   bit 2  k_color_pts evaluates EVERY view (no skipping of views that see none of a tile's points): +13 % (the round-2 kernel)
@@ -212,6 +212,57 @@ __device__ __forceinline__ void cm_project(const float* __restrict__ P, float x,
 
 
 #if defined(__HIPCC__)
+// Per-point and per-view stages that every colour kernel evaluates the same way (k_color_pts and k_project_features of csrc/color_pts.hip, the
+// test-only k_color_mfma of csrc/color_mfma.hip).  What differs between the kernels -- work decomposition, reductions over the views, the LDS exchange of
+// the shared rows -- stays with them.
+
+// d[4q .. 4q+3] += w * p4[q] for Q consecutive 16-byte loads (the taps of the geometry feature)
+template <int Q>
+__device__ __forceinline__ void fma_rows(const float4* p4, float w, float* d) {
+#pragma unroll
+    for (int q = 0; q < Q; ++q) {
+        const float4 t = p4[q];
+        d[4 * q] = fmaf(t.x, w, d[4 * q]); d[4 * q + 1] = fmaf(t.y, w, d[4 * q + 1]);
+        d[4 * q + 2] = fmaf(t.z, w, d[4 * q + 2]); d[4 * q + 3] = fmaf(t.w, w, d[4 * q + 3]);
+    }
+}
+
+// The non-zero ones of the 8 trilinear taps of point p in the D^3 volumes: f(voxel index, weight) for each, in tap order; returns the mask sum.
+template <class F>
+__device__ __forceinline__ float trilinear_taps(float px, float py, float pz, int D, const float* __restrict__ maskvol, F&& f) {
+    const Axis2 ax = axis_taps_zeros(px, D), ay = axis_taps_zeros(py, D), az = axis_taps_zeros(pz, D);
+    float msum = 0.f;
+#pragma unroll
+    for (int tap = 0; tap < 8; ++tap) {
+        const int ia = (tap >> 2) & 1, ib = (tap >> 1) & 1, ic = tap & 1;
+        const float w = ax.w[ia] * ay.w[ib] * az.w[ic];
+        if (w != 0.f) {
+            const size_t vox = ((size_t)ax.i[ia] * D + ay.i[ib]) * D + az.i[ic];
+            msum += w * maskvol[vox];
+            f(vox, w);
+        }
+    }
+    return msum;
+}
+// the geometry feature of a point counts if the point lies inside the volume and its taps' mask sum is positive
+__device__ __forceinline__ bool point_valid(float px, float py, float pz, float msum) {
+    return fabsf(px) < 1.f && fabsf(py) < 1.f && fabsf(pz) < 1.f && msum > 0.f;
+}
+
+// direction the point is looked at from: its normalised normal (compute_view_independent) or the normalised query_cam - p (Projector.compute)
+__device__ __forceinline__ void query_direction(const float* __restrict__ normals, const float* __restrict__ query_cam, long long slot, float px, float py,
+                                                float pz, float& qx, float& qy, float& qz) {
+    if (normals) {
+        const float nx = normals[3 * slot], ny = normals[3 * slot + 1], nz = normals[3 * slot + 2];
+        const float rn = crcp(fmaxf(sqrtf(nx * nx + ny * ny + nz * nz), 1e-6f));
+        qx = nx * rn; qy = ny * rn; qz = nz * rn;
+    } else {
+        const float tx = query_cam[0] - px, ty = query_cam[1] - py, tz = query_cam[2] - pz;
+        const float rn = crcp(sqrtf(tx * tx + ty * ty + tz * tz) + 1e-6f);
+        qx = tx * rn; qy = ty * rn; qz = tz * rn;
+    }
+}
+
 // geometry of one source view for this lane's point: ray_diff (4), pooling exponent, projection mask and the bilinear taps
 struct ViewGeom {
     float rd[4];
@@ -236,16 +287,135 @@ __device__ __forceinline__ ViewGeom view_geom(const ColorMArgs& a, int v, float 
     return g;
 }
 
+// this half's 32 pixel floats of view v at (g.gx, g.gy), bilinear, ATen zero padding, in the log2(e)-scaled domain.
+// (Measured alternatives in k_color_pts, all slower on MI355X: branch-free taps 50-59 ms; taps of view v + 1 requested during the network of view v
+// -- one tap, 32 registers, at a time -- 48.4 ms; lane octets fetching whole 128-byte half pixels through global_load_lds into a per-wave
+// LDS staging area (8 lines per instruction instead of up to 64) 48.9 ms; this form 44.5-45.2 ms.  See DESIGN.md section 8.)
+// The tap is written out: through fma_rows<8> k_color_pts accumulates in place and moves 112 registers more per gather.
+__device__ __forceinline__ void gather_now(const ColorMArgs& a, int h, int v, const ViewGeom& g, float (&rf)[32]) {
+#pragma unroll
+    for (int c = 0; c < 32; ++c) rf[c] = 0.f;
+    const Taps2D tp = bilinear_taps(g.gx, g.gy, a.H, a.W_img);
+    const float4* img = reinterpret_cast<const float4*>(a.cmaps + (size_t)v * a.H * a.W_img * 64) + 8 * h;
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        if (tp.w[k] != 0.f) {
+            const float4* px4 = img + (size_t)tp.idx[k] * 16;
+            const float wk = tp.w[k] * LOG2E;                       // pixel floats enter the network in the scaled domain
+#pragma unroll
+            for (int q = 0; q < 8; ++q) {
+                const float4 t = px4[q];
+                rf[4 * q] = fmaf(t.x, wk, rf[4 * q]); rf[4 * q + 1] = fmaf(t.y, wk, rf[4 * q + 1]);
+                rf[4 * q + 2] = fmaf(t.z, wk, rf[4 * q + 2]); rf[4 * q + 3] = fmaf(t.w, wk, rf[4 * q + 3]);
+            }
+        }
+}
+
+// ray_dir_fc (4 -> 16 -> 59) of ray difference rd, added to this half's 32 gathered pixel floats.  `tail`: shift of the bias block in the staged blob
+// (X3 ? CX_A_END - CM_BIAS0 : 0), here and below.
+template <bool X3>
+__device__ __forceinline__ void add_direction_feature(const float* lds, int tail, int lane, int h, const float (&rd)[4], float m1, float (&rf)[32]) {
+    f32x16 acc1[1];
+    cm_bias<1>(acc1, lds + tail + CM_B_RD0, h);
+    const float b0[2] = {h ? rd[1] : rd[0], h ? rd[3] : rd[2]};
+    cm_layer<X3, 1, 2>(acc1, lds, lane, CM_A_RD0, CX_A_RD0, b0, m1);
+    float d16[8];
+#pragma unroll
+    for (int r = 0; r < 8; r += 2) { const f32x2 e2 = celu2(acc1[0][r], acc1[0][r + 1]); d16[r] = e2[0]; d16[r + 1] = e2[1]; }
+    f32x16 acc2[2];
+    cm_bias<2>(acc2, lds + tail + CM_B_RD1, h);
+    cm_layer<X3, 2, 8>(acc2, lds, lane, CM_A_RD1, CX_A_RD1, d16, m1);
+#pragma unroll
+    for (int b = 0; b < 2; ++b)
+#pragma unroll
+        for (int r = 0; r < 16; r += 2) { const f32x2 e2 = celu2(acc2[b][r], acc2[b][r + 1]); rf[16 * b + r] += e2[0]; rf[16 * b + r + 1] += e2[1]; }
+}
+
+// The network of one (point, view) pair behind the view-independent rows: base_fc -> vis_fc -> vis_fc2 -> rgb_fc, returns the pair's blending score
+// (scaled domain).  acc: the starting accumulator of base_fc.0, i.e. bias + view-independent rows (geo | mean | var) of the point; rf: this half's
+// pixel floats + direction feature; wgt: normalised pooling weight; m: the view's mask; sc: the four scalars of the blob (CM_S).
+template <bool X3>
+__device__ __forceinline__ float view_network(f32x16 (&acc)[2], const float (&rf)[32], const float (&rd)[4], float wgt, float m, float m1,
+                                              const float* lds, int tail, const float* sc, int lane, int h) {
+    // ---- base_fc: (shared + 59 per-view features) -> 64 -> 32
+    f32x16 x32[1];
+    {
+        cm_layer<X3, 2, 32>(acc, lds, lane, CM_A_B0, CX_A_B0, rf, m1);
+        float hb[32];
+#pragma unroll
+        for (int b = 0; b < 2; ++b)
+#pragma unroll
+            for (int r = 0; r < 16; r += 2) { const f32x2 e2 = celu2(acc[b][r], acc[b][r + 1]); hb[16 * b + r] = e2[0]; hb[16 * b + r + 1] = e2[1]; }
+        cm_bias<1>(x32, lds + tail + CM_B_B1, h);
+        cm_layer<X3, 1, 32>(x32, lds, lane, CM_A_B1, CX_A_B1, hb, m1);
+#pragma unroll
+        for (int r = 0; r < 16; r += 2) { const f32x2 e2 = celu2(x32[0][r], x32[0][r + 1]); x32[0][r] = e2[0]; x32[0][r + 1] = e2[1]; }
+    }
+    // ---- vis_fc
+    float vis;
+    {
+        float bin[16];
+#pragma unroll
+        for (int r = 0; r < 16; ++r) bin[r] = x32[0][r] * wgt;
+        f32x16 t1[1];
+        cm_bias<1>(t1, lds + tail + CM_B_V0, h);
+        cm_layer<X3, 1, 16>(t1, lds, lane, CM_A_V0, CX_A_V0, bin, m1);
+#pragma unroll
+        for (int r = 0; r < 16; r += 2) { const f32x2 e2 = celu2(t1[0][r], t1[0][r + 1]); bin[r] = e2[0]; bin[r + 1] = e2[1]; }
+        f32x16 t2[1];
+        cm_bias<1>(t2, lds + tail + CM_B_V1, h);
+        cm_layer<X3, 1, 16>(t2, lds, lane, CM_A_V1, CX_A_V1, bin, m1);
+        float vr = 0.f;                                           // output 32 of vis_fc.2: dot product over both halves
+#pragma unroll
+        for (int r = 0; r < 16; ++r) vr = fmaf(bin[r], lds[tail + CM_V_V1X + h * 16 + r], vr);
+        vr += __shfl_xor(vr, 32);
+#pragma unroll
+        for (int r = 0; r < 16; r += 2) { const f32x2 e2 = celu2(t2[0][r], t2[0][r + 1]); x32[0][r] += e2[0]; x32[0][r + 1] += e2[1]; }
+        vis = csigm(celu(vr + sc[1])) * m;
+    }
+    // ---- vis_fc2
+    {
+        float bin[16];
+#pragma unroll
+        for (int r = 0; r < 16; ++r) bin[r] = x32[0][r] * vis;
+        f32x16 t1[1];
+        cm_bias<1>(t1, lds + tail + CM_B_V20, h);
+        cm_layer<X3, 1, 16>(t1, lds, lane, CM_A_V20, CX_A_V20, bin, m1);
+#pragma unroll
+        for (int r = 0; r < 16; r += 2) { const f32x2 e2 = celu2(t1[0][r], t1[0][r + 1]); bin[r] = e2[0]; bin[r + 1] = e2[1]; }
+        float vr = 0.f;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) vr = fmaf(bin[r], lds[tail + CM_V_V21 + h * 16 + r], vr);
+        vr += __shfl_xor(vr, 32);
+        vis = csigm(vr + sc[2]) * m;
+    }
+    // ---- rgb_fc: [x | vis | ray_diff] (37) -> 16 -> 8 -> 1
+    float bin[19];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) bin[r] = x32[0][r];
+    bin[16] = h ? rd[0] : vis; bin[17] = h ? rd[2] : rd[1]; bin[18] = h ? 0.f : rd[3];
+    f32x16 t1[1];
+    cm_bias<1>(t1, lds + tail + CM_B_R0, h);
+    cm_layer<X3, 1, 19>(t1, lds, lane, CM_A_R0, CX_A_R0, bin, m1);
+    float r16[8];
+#pragma unroll
+    for (int r = 0; r < 8; r += 2) { const f32x2 e2 = celu2(t1[0][r], t1[0][r + 1]); r16[r] = e2[0]; r16[r + 1] = e2[1]; }
+    f32x16 t2[1];
+    cm_bias<1>(t2, lds + tail + CM_B_R1, h);
+    cm_layer<X3, 1, 8>(t2, lds, lane, CM_A_R1, CX_A_R1, r16, m1);
+    float r8[4];
+#pragma unroll
+    for (int r = 0; r < 4; r += 2) { const f32x2 e2 = celu2(t2[0][r], t2[0][r + 1]); r8[r] = e2[0]; r8[r + 1] = e2[1]; }
+    float sr = 0.f;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) sr = fmaf(r8[r], lds[tail + CM_V_R2 + h * 16 + r], sr);
+    return sr + __shfl_xor(sr, 32) + sc[3];
+}
 #endif
 
-// csrc/color_pts.hip: the points-as-columns kernel (the product kernel; k_color_mfma of csrc/color_mfma.hip exists only in -DO2345_TILES_KERNEL test builds)
-int project_features_launch(const float* vol_cl, const float* maskvol, int D, const float* cmaps, const float* proj, const float* cam_pos, int V, int H, int W,
-                            const float* pts, long long n, const float* query_cam, const float* normals, float* geo, float* rgb_feat, float* rdiff, float* mask,
-                            void* stream);
-int color_feats_launch(int x3, const float* blob, const float* geo, const float* rgb_feat, const float* ray_diff, const float* mask, int V, long long n,
-                       float* out_rgb, uint8_t* out_nviews, void* stream);
-int color_pts_launch(int x3, const float* blob, const float* vol_cl, const float* maskvol, int D, const float* cmaps, const float* proj,
-                     const float* cam_pos, int V, int H, int W, const float* pts, const int32_t* index, const int32_t* n_dev, long long n,
-                     const float* query_cam, const float* normals, float* out_rgb, uint8_t* out_nviews, unsigned long long* stats_dev, void* stream);
+// csrc/color_pts.hip (the product kernels; csrc/color_mfma.hip holds the entry points, which check their arguments and fill the ColorMArgs).
+// k_color_pts<x3, feats> on a: feats = the materialised inputs f_* instead of the point's own projection
+int color_pts_launch(const ColorMArgs& a, int x3, bool feats, const char* what, void* stream);
+int project_features_launch(const ColorMArgs& a, float* geo, float* rgb_feat, float* rdiff, float* mask, void* stream);
 
 }  // namespace o2345

@@ -15,35 +15,13 @@
 //   shared   view-independent rows of base_fc.0 (geo | mean | var -> 64) ONCE per point on the matrix cores (N = 32 points): the
 //            result (incl. bias) is the accumulator input of every view's base_fc.0;
 //   pass B   per view: gather + ray_dir_fc again (recomputed: 59 floats x V per point do not fit anywhere), base_fc, vis_fc,
-//            vis_fc2, rgb_fc exactly as in color_mfma.hip, and an online softmax over the views (running max / sum / rgb).
+//            vis_fc2, rgb_fc (view_network of color_net.h, the function k_color_mfma calls), and an online softmax over the views
+//            (running max / sum / rgb).
 // View-uniform data (projection rows, camera centres) is read through scalar loads.  V is a run-time loop bound: no power-of-two
 // padding of the view count, any V >= 1.  LDS holds the operand blobs (without A_S) and one slot of shared rows per wave (<= 148 KB).
 #include "color_net.h"
 
 namespace o2345 {
-
-// this half's 32 pixel floats of view v at (g.gx, g.gy), bilinear, ATen zero padding, in the log2(e)-scaled domain.
-// (Measured alternatives, all slower on MI355X: branch-free taps 50-59 ms; taps of view v + 1 requested during the network of view v
-// -- one tap, 32 registers, at a time -- 48.4 ms; lane octets fetching whole 128-byte half pixels through global_load_lds into a per-wave
-// LDS staging area (8 lines per instruction instead of up to 64) 48.9 ms; this form 44.5-45.2 ms.  See DESIGN.md section 8.)
-__device__ __forceinline__ void gather_now(const ColorMArgs& a, int h, int v, const ViewGeom& g, float (&rf)[32]) {
-#pragma unroll
-    for (int c = 0; c < 32; ++c) rf[c] = 0.f;
-    const Taps2D tp = bilinear_taps(g.gx, g.gy, a.H, a.W_img);
-    const float4* img = reinterpret_cast<const float4*>(a.cmaps + (size_t)v * a.H * a.W_img * 64) + 8 * h;
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-        if (tp.w[k] != 0.f) {
-            const float4* px4 = img + (size_t)tp.idx[k] * 16;
-            const float wk = tp.w[k] * LOG2E;                       // pixel floats enter the network in the scaled domain
-#pragma unroll
-            for (int q = 0; q < 8; ++q) {
-                const float4 t = px4[q];
-                rf[4 * q] = fmaf(t.x, wk, rf[4 * q]); rf[4 * q + 1] = fmaf(t.y, wk, rf[4 * q + 1]);
-                rf[4 * q + 2] = fmaf(t.z, wk, rf[4 * q + 2]); rf[4 * q + 3] = fmaf(t.w, wk, rf[4 * q + 3]);
-            }
-        }
-}
 
 // FEATS form (GeneralRenderingNetwork.forward on materialised tensors, rendering_network.py:75-129): the same per-view quantities read from the
 // reference's view-major inputs instead of being derived from the point
@@ -62,25 +40,15 @@ __device__ __forceinline__ void load_feats(const ColorMArgs& a, int h, int v, lo
     for (int c = 0; c < 32; ++c) rf[c] = (h == 0 || c < 27) ? src[(h == 0 || c < 27) ? c : 0] * LOG2E : 0.f;
 }
 
-// ray_dir_fc (4 -> 16 -> 59) of view geometry g in two steps: layer 1 -> d16, layer 2 added to this half's 32 gathered pixel floats
-template <bool X3>
-__device__ __forceinline__ void direction_layer1(const float* lds, int tail, int lane, int h, const ViewGeom& g, float m1, float (&d16)[8]) {
-    f32x16 acc1[1];
-    cm_bias<1>(acc1, lds + tail + CM_B_RD0, h);
-    const float b0[2] = {h ? g.rd[1] : g.rd[0], h ? g.rd[3] : g.rd[2]};
-    cm_layer<X3, 1, 2>(acc1, lds, lane, CM_A_RD0, CX_A_RD0, b0, m1);
-#pragma unroll
-    for (int r = 0; r < 8; r += 2) { const f32x2 e2 = celu2(acc1[0][r], acc1[0][r + 1]); d16[r] = e2[0]; d16[r + 1] = e2[1]; }
-}
-template <bool X3>
-__device__ __forceinline__ void direction_layer2(const float* lds, int tail, int lane, int h, const float (&d16)[8], float m1, float (&rf)[32]) {
-    f32x16 acc2[2];
-    cm_bias<2>(acc2, lds + tail + CM_B_RD1, h);
-    cm_layer<X3, 2, 8>(acc2, lds, lane, CM_A_RD1, CX_A_RD1, d16, m1);
-#pragma unroll
-    for (int b = 0; b < 2; ++b)
-#pragma unroll
-        for (int r = 0; r < 16; r += 2) { const f32x2 e2 = celu2(acc2[b][r], acc2[b][r + 1]); rf[16 * b + r] += e2[0]; rf[16 * b + r + 1] += e2[1]; }
+// this half's 32 pixel floats of view v, before the direction feature: read (FEATS) or gathered with the wave's priority raised (bit 1 of a.sched)
+template <bool FEATS>
+__device__ __forceinline__ void pixel_floats(const ColorMArgs& a, int h, int v, long long slot, const ViewGeom& g, int base_prio, float (&rf)[32]) {
+    if constexpr (FEATS) load_feats(a, h, v, slot, rf);
+    else {
+        if (a.sched & 2) set_wave_prio(3);
+        gather_now(a, h, v, g, rf);
+        if (a.sched & 2) set_wave_prio(base_prio);
+    }
 }
 
 // The view-independent rows of base_fc.0 (A_S, 36 KB in either form, read once per tile) come straight from the blob in global memory, where they stay
@@ -208,37 +176,13 @@ __global__ __launch_bounds__(CP_THREADS) void k_color_pts(ColorMArgs a) {
         } else {
 #pragma unroll
             for (int c = 0; c < 8; ++c) bs[c] = 0.f;
-            float msum = 0.f;
-            const Axis2 ax = axis_taps_zeros(px, a.D), ay = axis_taps_zeros(py, a.D), az = axis_taps_zeros(pz, a.D);
-#pragma unroll
-            for (int tap = 0; tap < 8; ++tap) {
-                const int ia = (tap >> 2) & 1, ib = (tap >> 1) & 1, ic = tap & 1;
-                const float w = ax.w[ia] * ay.w[ib] * az.w[ic];
-                if (w != 0.f) {
-                    const size_t vox = ((size_t)ax.i[ia] * a.D + ay.i[ib]) * a.D + az.i[ic];
-                    msum += w * a.maskvol[vox];
-                    const float4* p4 = reinterpret_cast<const float4*>(a.vol_cl + vox * 16) + 2 * h;
-#pragma unroll
-                    for (int q = 0; q < 2; ++q) {
-                        const float4 t = p4[q];
-                        bs[4 * q] = fmaf(t.x, w, bs[4 * q]); bs[4 * q + 1] = fmaf(t.y, w, bs[4 * q + 1]);
-                        bs[4 * q + 2] = fmaf(t.z, w, bs[4 * q + 2]); bs[4 * q + 3] = fmaf(t.w, w, bs[4 * q + 3]);
-                    }
-                }
-            }
-            gvalid = fabsf(px) < 1.f && fabsf(py) < 1.f && fabsf(pz) < 1.f && msum > 0.f;
+            const float msum = trilinear_taps(px, py, pz, a.D, a.maskvol, [&](size_t vox, float w) {
+                fma_rows<2>(reinterpret_cast<const float4*>(a.vol_cl + vox * 16) + 2 * h, w, bs);
+            });
+            gvalid = point_valid(px, py, pz, msum);
         }
         float qx = 0.f, qy = 0.f, qz = 0.f;
-        if constexpr (FEATS) {
-        } else if (a.normals) {
-            const float nx = a.normals[3 * slot], ny = a.normals[3 * slot + 1], nz = a.normals[3 * slot + 2];
-            const float rn = crcp(fmaxf(sqrtf(nx * nx + ny * ny + nz * nz), 1e-6f));
-            qx = nx * rn; qy = ny * rn; qz = nz * rn;
-        } else {
-            const float tx = a.query_cam[0] - px, ty = a.query_cam[1] - py, tz = a.query_cam[2] - pz;
-            const float rn = crcp(sqrtf(tx * tx + ty * ty + tz * tz) + 1e-6f);
-            qx = tx * rn; qy = ty * rn; qz = tz * rn;
-        }
+        if constexpr (!FEATS) query_direction(a.normals, a.query_cam, slot, px, py, pz, qx, qy, qz);
         // min over ALL views of the pooling exponent (rendering_network.py:94: exp(...).min over the view axis, mask or not)
         float emin = INFINITY;
         for (int v = 0; v < V; ++v) {
@@ -279,17 +223,8 @@ __global__ __launch_bounds__(CP_THREADS) void k_color_pts(ColorMArgs a) {
                 if (skip_zero && __builtin_amdgcn_ballot_w64(live && raw != 0.f) == 0ull) continue;
                 ++st_a;
                 float rf[32];
-                if constexpr (FEATS) load_feats(a, h, v, slot, rf);
-                else {
-                    if (a.sched & 2) set_wave_prio(3);
-                    gather_now(a, h, v, g, rf);
-                    if (a.sched & 2) set_wave_prio(base_prio);
-                }
-                {
-                    float d16[8];
-                    direction_layer1<X3>(lds, TAIL, lane, h, g, m1, d16);
-                    direction_layer2<X3>(lds, TAIL, lane, h, d16, m1, rf);
-                }
+                pixel_floats<FEATS>(a, h, v, slot, g, base_prio, rf);
+                add_direction_feature<X3>(lds, TAIL, lane, h, g.rd, m1, rf);
                 wsum += raw;
                 const float r0 = raw > 0.f ? raw * crcp(wsum) : 0.f;
                 // one Newton step on the quotient: raw / wsum to <= 1 ulp
@@ -351,97 +286,13 @@ __global__ __launch_bounds__(CP_THREADS) void k_color_pts(ColorMArgs a) {
             const ViewGeom g = FEATS ? feat_geom(a, v, slot, s_abs) : view_geom(a, v, px, py, pz, qx, qy, qz, gvalid, s_abs);
             const float m = g.m;
             float rf[32];
-            if constexpr (FEATS) load_feats(a, h, v, slot, rf);
-            else {
-                if (a.sched & 2) set_wave_prio(3);
-                gather_now(a, h, v, g, rf);
-                if (a.sched & 2) set_wave_prio(base_prio);
-            }
+            pixel_floats<FEATS>(a, h, v, slot, g, base_prio, rf);
             const float rgb0 = rf[0], rgb1 = rf[1], rgb2 = rf[2];   // log2(e) * colours (meaningful in half 0), before the direction feature
-            {
-                float d16[8];
-                direction_layer1<X3>(lds, TAIL, lane, h, g, m1, d16);
-                direction_layer2<X3>(lds, TAIL, lane, h, d16, m1, rf);
-            }
-            const float wgt = (g.e - emin) * m * rden;
-            // ---- base_fc: (shared + 59 per-view features) -> 64 -> 32
-            f32x16 x32[1];
-            {
-                f32x16 acc[2];
-                sh_load(acc, sh_slot);
-                cm_layer<X3, 2, 32>(acc, lds, lane, CM_A_B0, CX_A_B0, rf, m1);
-                float hb[32];
-#pragma unroll
-                for (int b = 0; b < 2; ++b)
-#pragma unroll
-                    for (int r = 0; r < 16; r += 2) { const f32x2 e2 = celu2(acc[b][r], acc[b][r + 1]); hb[16 * b + r] = e2[0]; hb[16 * b + r + 1] = e2[1]; }
-                cm_bias<1>(x32, lds + TAIL + CM_B_B1, h);
-                cm_layer<X3, 1, 32>(x32, lds, lane, CM_A_B1, CX_A_B1, hb, m1);
-#pragma unroll
-                for (int r = 0; r < 16; r += 2) { const f32x2 e2 = celu2(x32[0][r], x32[0][r + 1]); x32[0][r] = e2[0]; x32[0][r + 1] = e2[1]; }
-            }
-            // ---- vis_fc
-            float vis;
-            {
-                float bin[16];
-#pragma unroll
-                for (int r = 0; r < 16; ++r) bin[r] = x32[0][r] * wgt;
-                f32x16 t1[1];
-                cm_bias<1>(t1, lds + TAIL + CM_B_V0, h);
-                cm_layer<X3, 1, 16>(t1, lds, lane, CM_A_V0, CX_A_V0, bin, m1);
-#pragma unroll
-                for (int r = 0; r < 16; r += 2) { const f32x2 e2 = celu2(t1[0][r], t1[0][r + 1]); bin[r] = e2[0]; bin[r + 1] = e2[1]; }
-                f32x16 t2[1];
-                cm_bias<1>(t2, lds + TAIL + CM_B_V1, h);
-                cm_layer<X3, 1, 16>(t2, lds, lane, CM_A_V1, CX_A_V1, bin, m1);
-                float vr = 0.f;                                           // output 32 of vis_fc.2: dot product over both halves
-#pragma unroll
-                for (int r = 0; r < 16; ++r) vr = fmaf(bin[r], lds[TAIL + CM_V_V1X + h * 16 + r], vr);
-                vr += __shfl_xor(vr, 32);
-#pragma unroll
-                for (int r = 0; r < 16; r += 2) { const f32x2 e2 = celu2(t2[0][r], t2[0][r + 1]); x32[0][r] += e2[0]; x32[0][r + 1] += e2[1]; }
-                vis = csigm(celu(vr + lds[L_S + 1])) * m;
-            }
-            // ---- vis_fc2
-            {
-                float bin[16];
-#pragma unroll
-                for (int r = 0; r < 16; ++r) bin[r] = x32[0][r] * vis;
-                f32x16 t1[1];
-                cm_bias<1>(t1, lds + TAIL + CM_B_V20, h);
-                cm_layer<X3, 1, 16>(t1, lds, lane, CM_A_V20, CX_A_V20, bin, m1);
-#pragma unroll
-                for (int r = 0; r < 16; r += 2) { const f32x2 e2 = celu2(t1[0][r], t1[0][r + 1]); bin[r] = e2[0]; bin[r + 1] = e2[1]; }
-                float vr = 0.f;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) vr = fmaf(bin[r], lds[TAIL + CM_V_V21 + h * 16 + r], vr);
-                vr += __shfl_xor(vr, 32);
-                vis = csigm(vr + lds[L_S + 2]) * m;
-            }
-            // ---- rgb_fc: [x | vis | ray_diff] (37) -> 16 -> 8 -> 1
-            float score;
-            {
-                float bin[19];
-#pragma unroll
-                for (int r = 0; r < 16; ++r) bin[r] = x32[0][r];
-                bin[16] = h ? g.rd[0] : vis; bin[17] = h ? g.rd[2] : g.rd[1]; bin[18] = h ? 0.f : g.rd[3];
-                f32x16 t1[1];
-                cm_bias<1>(t1, lds + TAIL + CM_B_R0, h);
-                cm_layer<X3, 1, 19>(t1, lds, lane, CM_A_R0, CX_A_R0, bin, m1);
-                float r16[8];
-#pragma unroll
-                for (int r = 0; r < 8; r += 2) { const f32x2 e2 = celu2(t1[0][r], t1[0][r + 1]); r16[r] = e2[0]; r16[r + 1] = e2[1]; }
-                f32x16 t2[1];
-                cm_bias<1>(t2, lds + TAIL + CM_B_R1, h);
-                cm_layer<X3, 1, 8>(t2, lds, lane, CM_A_R1, CX_A_R1, r16, m1);
-                float r8[4];
-#pragma unroll
-                for (int r = 0; r < 4; r += 2) { const f32x2 e2 = celu2(t2[0][r], t2[0][r + 1]); r8[r] = e2[0]; r8[r + 1] = e2[1]; }
-                float sr = 0.f;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) sr = fmaf(r8[r], lds[TAIL + CM_V_R2 + h * 16 + r], sr);
-                score = sr + __shfl_xor(sr, 32) + lds[L_S + 3];
-            }
+            add_direction_feature<X3>(lds, TAIL, lane, h, g.rd, m1, rf);
+            // ---- base_fc (on top of the shared rows), vis_fc, vis_fc2, rgb_fc
+            f32x16 acc[2];
+            sh_load(acc, sh_slot);
+            float score = view_network<X3>(acc, rf, g.rd, (g.e - emin) * m * rden, m, m1, lds, TAIL, lds + L_S, lane, h);
             // ---- masked softmax over the views, running form (scores are in the scaled domain: base 2)
             if (m == 0.f) score = -1e9f;
             const float nmax = fmaxf(smax, score);
@@ -462,30 +313,18 @@ __global__ __launch_bounds__(CP_THREADS) void k_color_pts(ColorMArgs a) {
     }
 }
 
-}  // namespace o2345
-
-namespace o2345 {
-
-// launcher shared by o2345_color_points_mfma / o2345_color_points_x3 (csrc/color_mfma.hip decides which kernel runs)
-int color_pts_launch(int x3, const float* blob, const float* vol_cl, const float* maskvol, int D, const float* cmaps, const float* proj,
-                           const float* cam_pos, int V, int H, int W, const float* pts, const int32_t* index, const int32_t* n_dev,
-                           long long n, const float* query_cam, const float* normals, float* out_rgb, uint8_t* out_nviews,
-                           unsigned long long* stats_dev /* optional, caller-owned work counters [4] */, void* stream) {
-    ColorMArgs a{blob, vol_cl, maskvol, D, cmaps, proj, cam_pos, V, H, W, pts, index, n_dev, n, query_cam, normals, out_rgb, out_nviews};
-    a.sched = color_sched_mode();
-    a.stats = stats_dev;
-    const int threads = CP_THREADS;
-    const unsigned grid = network_grid(n, n_dev, threads, 32);
-    const size_t lds = color_pts_lds_bytes(x3);
-    hipStream_t s = (hipStream_t)stream;
-    if (x3) {
-        O2345_ENSURE_LDS((k_color_pts<true, false>), lds);
-        hipLaunchKernelGGL((k_color_pts<true, false>), dim3(grid), dim3(threads), lds, s, a);
-    } else {
-        O2345_ENSURE_LDS((k_color_pts<false, false>), lds);
-        hipLaunchKernelGGL((k_color_pts<false, false>), dim3(grid), dim3(threads), lds, s, a);
-    }
-    return check_launch("color_points (points-as-columns kernel)");
+// One launch of k_color_pts.  x3: the split-f16 form and its blob; feats: GeneralRenderingNetwork.forward on the reference's materialised tensors
+// a.f_* (the drop-in form) instead of the fused Projector path, which is the fast one.
+template <auto KERNEL>
+static int color_pts_launch_kernel(const ColorMArgs& a, size_t lds, const char* what, void* stream) {
+    O2345_ENSURE_LDS(KERNEL, lds);
+    hipLaunchKernelGGL(KERNEL, dim3(network_grid(a.n, a.n_dev, CP_THREADS, 32)), dim3(CP_THREADS), lds, (hipStream_t)stream, a);
+    return check_launch(what);
+}
+int color_pts_launch(const ColorMArgs& a, int x3, bool feats, const char* what, void* stream) {
+    const auto launch = x3 ? (feats ? color_pts_launch_kernel<k_color_pts<true, true>> : color_pts_launch_kernel<k_color_pts<true, false>>)
+                           : (feats ? color_pts_launch_kernel<k_color_pts<false, true>> : color_pts_launch_kernel<k_color_pts<false, false>>);
+    return launch(a, color_pts_lds_bytes(x3), what, stream);
 }
 
 // Projector.compute / compute_view_independent MATERIALISED (models/projector.py:96-425): the four tensors the reference's own
@@ -498,31 +337,13 @@ __global__ __launch_bounds__(256) void k_project_features(ColorMArgs a, float* _
     const long long p = w / a.V;
     const int v = (int)(w - p * a.V), c = threadIdx.x & 63;
     const float px = a.pts[3 * p], py = a.pts[3 * p + 1], pz = a.pts[3 * p + 2];
-    float msum = 0.f, gch = 0.f;
-    {
-        const Axis2 ax = axis_taps_zeros(px, a.D), ay = axis_taps_zeros(py, a.D), az = axis_taps_zeros(pz, a.D);
-#pragma unroll
-        for (int tap = 0; tap < 8; ++tap) {
-            const int ia = (tap >> 2) & 1, ib = (tap >> 1) & 1, ic = tap & 1;
-            const float wt = ax.w[ia] * ay.w[ib] * az.w[ic];
-            if (wt != 0.f) {
-                const size_t vox = ((size_t)ax.i[ia] * a.D + ay.i[ib]) * a.D + az.i[ic];
-                msum += wt * a.maskvol[vox];
-                if (c < 16) gch = fmaf(a.vol_cl[vox * 16 + c], wt, gch);
-            }
-        }
-    }
-    const bool gvalid = fabsf(px) < 1.f && fabsf(py) < 1.f && fabsf(pz) < 1.f && msum > 0.f;
+    float gch = 0.f;
+    const float msum = trilinear_taps(px, py, pz, a.D, a.maskvol, [&](size_t vox, float wt) {
+        if (c < 16) gch = fmaf(a.vol_cl[vox * 16 + c], wt, gch);
+    });
+    const bool gvalid = point_valid(px, py, pz, msum);
     float qx, qy, qz;
-    if (a.normals) {
-        const float nx = a.normals[3 * p], ny = a.normals[3 * p + 1], nz = a.normals[3 * p + 2];
-        const float rn = crcp(fmaxf(sqrtf(nx * nx + ny * ny + nz * nz), 1e-6f));
-        qx = nx * rn; qy = ny * rn; qz = nz * rn;
-    } else {
-        const float tx = a.query_cam[0] - px, ty = a.query_cam[1] - py, tz = a.query_cam[2] - pz;
-        const float rn = crcp(sqrtf(tx * tx + ty * ty + tz * tz) + 1e-6f);
-        qx = tx * rn; qy = ty * rn; qz = tz * rn;
-    }
+    query_direction(a.normals, a.query_cam, p, px, py, pz, qx, qy, qz);
     const ViewGeom g = view_geom(a, v, px, py, pz, qx, qy, qz, gvalid, 0.f);
     float val = 0.f;
     {
@@ -539,37 +360,12 @@ __global__ __launch_bounds__(256) void k_project_features(ColorMArgs a, float* _
     if (v == 0 && c < 16) geo[(size_t)p * 16 + c] = gch;
 }
 
-int project_features_launch(const float* vol_cl, const float* maskvol, int D, const float* cmaps, const float* proj, const float* cam_pos, int V, int H, int W,
-                            const float* pts, long long n, const float* query_cam, const float* normals, float* geo, float* rgb_feat, float* rdiff, float* mask,
-                            void* stream) {
-    ColorMArgs a{nullptr, vol_cl, maskvol, D, cmaps, proj, cam_pos, V, H, W, pts, nullptr, nullptr, n, query_cam, normals, nullptr, nullptr};
-    hipLaunchKernelGGL(k_project_features, dim3(cdiv(n * V, 4)), dim3(256), 0, (hipStream_t)stream, a, geo, rgb_feat, rdiff, mask);
+int project_features_launch(const ColorMArgs& a, float* geo, float* rgb_feat, float* rdiff, float* mask, void* stream) {
+    hipLaunchKernelGGL(k_project_features, dim3(cdiv(a.n * a.V, 4)), dim3(256), 0, (hipStream_t)stream, a, geo, rgb_feat, rdiff, mask);
     return check_launch("project_features");
 }
 
-// GeneralRenderingNetwork.forward on the reference's materialised tensors (the drop-in form; the fused Projector path above is the fast one)
-int color_feats_launch(int x3, const float* blob, const float* geo, const float* rgb_feat, const float* ray_diff, const float* mask, int V, long long n,
-                       float* out_rgb, uint8_t* out_nviews, void* stream) {
-    ColorMArgs a{};
-    a.blob = blob; a.V = V; a.n = n; a.out_rgb = out_rgb; a.out_nviews = out_nviews;
-    a.f_geo = geo; a.f_rgb = rgb_feat; a.f_rdiff = ray_diff; a.f_mask = mask;
-    const unsigned grid = network_grid(n, nullptr, CP_THREADS, 32);
-    const size_t lds = color_pts_lds_bytes(x3);
-    hipStream_t s = (hipStream_t)stream;
-    if (x3) {
-        O2345_ENSURE_LDS((k_color_pts<true, true>), lds);
-        hipLaunchKernelGGL((k_color_pts<true, true>), dim3(grid), dim3(CP_THREADS), lds, s, a);
-    } else {
-        O2345_ENSURE_LDS((k_color_pts<false, true>), lds);
-        hipLaunchKernelGGL((k_color_pts<false, true>), dim3(grid), dim3(CP_THREADS), lds, s, a);
-    }
-    return check_launch("color_from_features");
-}
-
-}  // namespace o2345
-
 // o2345_preload (csrc/api.cpp): querying one kernel makes the HIP runtime load this translation unit's code object on the current device
-namespace o2345 {
 int preload_color_pts() {
     hipFuncAttributes at;
     return (int)hipFuncGetAttributes(&at, (const void*)(k_project_features));
