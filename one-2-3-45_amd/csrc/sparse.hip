@@ -127,7 +127,10 @@ __global__ __launch_bounds__(256) void k_sparse_conv(const float* __restrict__ i
 
 // ---- batch-statistics BatchNorm + ReLU (+ skip) ---------------------------------------------------------------------
 // stage 1: per-block fp64 partial sums of x and x^2 per channel; stage 2: one block reduces the partials in a fixed
-// order -> scale/shift; stage 3: y = relu(x*scale + shift) [+ skip].  Deterministic (no float atomics).
+// order -> scale and mean; stage 3: y = relu((x - mean)*scale + beta) [+ skip].  Deterministic (no float atomics).
+// Stage 3 centres x before it scales: x*scale + (beta - mean*scale) cancels two terms of size |mean|*scale and keeps their rounding errors,
+// which 1/sqrt(var + eps) makes large in a channel of (near) zero variance -- a single row, a constant channel: up to 1.7e-4 where the exact result is
+// beta.  The mean is carried as a float pair (hi + lo), so that its own rounding is not amplified either.
 template <int C>
 __global__ __launch_bounds__(256) void k_col_partial(const float* __restrict__ x, int n, double* __restrict__ part /*[nb,2,C]*/) {
     __shared__ double sm[256 / C][2][C];
@@ -152,17 +155,25 @@ __global__ __launch_bounds__(256) void k_col_partial(const float* __restrict__ x
 template <int C>
 __global__ __launch_bounds__(256) void k_col_finish(const double* __restrict__ part, int nblocks, int n, const float* __restrict__ gamma,
                                                     const float* __restrict__ beta, float eps, int abs_gamma,
-                                                    float* __restrict__ scale_shift /*[2,C]*/, float* __restrict__ mean_var /*[2,C] or null*/) {
+                                                    float* __restrict__ scale_shift /*[4,C]: scale | shift | mean hi | mean lo*/,
+                                                    float* __restrict__ mean_var /*[2,C] or null*/) {
     const int c = blockIdx.x;
     double s = 0.0, s2 = 0.0;
     for (int b = threadIdx.x; b < nblocks; b += 256) { s += part[((size_t)b * 2 + 0) * C + c]; s2 += part[((size_t)b * 2 + 1) * C + c]; }
-    if (block_sum2_256(s, s2)) abn_scale_shift(s, s2, (double)n, c, C, gamma, beta, eps, abs_gamma, scale_shift, mean_var);
+    if (block_sum2_256(s, s2)) {
+        abn_scale_shift(s, s2, (double)n, c, C, gamma, beta, eps, abs_gamma, scale_shift, mean_var);
+        const double mean = s / (double)n;
+        const float hi = (float)mean;
+        scale_shift[2 * C + c] = hi;
+        scale_shift[3 * C + c] = (float)(mean - (double)hi);
+    }
 }
 
 // x: [n, C] rows (channel-last).  slope = 0 -> ReLU, 0.01 -> leaky ReLU (InPlaceABN).  skip may be null.
 template <int C>
 __global__ __launch_bounds__(256) void k_bn_act(const float* __restrict__ x, long long n_elems,
-                                                const float* __restrict__ scale_shift, float slope,
+                                                const float* __restrict__ scale_shift /*[4,C] of k_col_finish*/,
+                                                const float* __restrict__ beta, float slope,
                                                 const float* __restrict__ skip, float* __restrict__ y) {
     const long long i = ((long long)blockIdx.x * 256 + threadIdx.x) * 4;
     if (i >= n_elems) return;
@@ -171,7 +182,8 @@ __global__ __launch_bounds__(256) void k_bn_act(const float* __restrict__ x, lon
     float r[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
-        r[u] = abn_act_select(r[u], scale_shift[c + u], scale_shift[C + c + u], slope);
+        const float centred = (r[u] - scale_shift[2 * C + c + u]) - scale_shift[3 * C + c + u];
+        r[u] = abn_act_select(centred, scale_shift[c + u], beta[c + u], slope);
     }
     if (skip) {
         const float4 s = *reinterpret_cast<const float4*>(skip + i);
@@ -295,7 +307,7 @@ int o2345_bn_act_rows(const float* x, int n, int C, const float* gamma, const fl
     if (C == CC) {                                                                                                    \
         hipLaunchKernelGGL(k_col_partial<CC>, dim3(nb), dim3(256), 0, s, x, n, part);                                 \
         hipLaunchKernelGGL(k_col_finish<CC>, dim3(CC), dim3(256), 0, s, part, nb, n, gamma, beta, eps, abs_gamma, ss, mean_var_out); \
-        hipLaunchKernelGGL(k_bn_act<CC>, dim3(cdiv(ne, 1024)), dim3(256), 0, s, x, ne, ss, slope, skip, y);          \
+        hipLaunchKernelGGL(k_bn_act<CC>, dim3(cdiv(ne, 1024)), dim3(256), 0, s, x, ne, ss, beta, slope, skip, y);    \
     }
     O2345_BN_CASE(16) O2345_BN_CASE(32) O2345_BN_CASE(64)
     return check_launch("bn_act_rows");

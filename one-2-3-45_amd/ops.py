@@ -221,6 +221,8 @@ def fpn_level(fine, coarse, weight, bias, fine_scale_shift=None, slope=0.01):
     """FeatureNet._upsample_add(coarse, lateral_1x1(fine)) in one kernel: fine [V,C,H,W] (C = 8 | 16), coarse [V,32,H/2,W/2] -> [V,32,H,W].
     ``fine_scale_shift``: fine is a raw convolution output, its InPlaceABN is applied on load."""
     V, C, H, W = fine.shape
+    if C not in (8, 16) or H % 2 or W % 2 or H < 2 or W < 2:
+        raise ValueError(f"fpn_level: fine map must be [V,8|16,H,W] with even H and W, got {tuple(fine.shape)}")
     if tuple(coarse.shape) != (V, 32, H // 2, W // 2):
         raise ValueError(f"fpn_level: coarse map must be [V,32,H/2,W/2], got {tuple(coarse.shape)} for fine {tuple(fine.shape)}")
     out = torch.empty(V, 32, H, W, dtype=torch.float32, device=fine.device)
@@ -233,6 +235,8 @@ def fpn_level(fine, coarse, weight, bias, fine_scale_shift=None, slope=0.01):
 def pyramid_pack(f2, s1, s0, rgb, want_nchw=True):
     """Fused pyramid -> (fmaps [V,56,H,W] or None, cmaps [V,H,W,64] = rgb | 56 features | pad)."""
     V, _, H, W = s0.shape
+    if H % 4 or W % 4 or H < 4 or W < 4:
+        raise ValueError(f"pyramid_pack: map sizes must be multiples of 4, got {H} x {W}")
     if tuple(f2.shape) != (V, 32, H // 4, W // 4) or tuple(s1.shape) != (V, 16, H // 2, W // 2) or tuple(rgb.shape) != (V, 3, H, W) or s0.shape[1] != 8:
         raise ValueError("pyramid_pack: expected f2 [V,32,H/4,W/4], s1 [V,16,H/2,W/2], s0 [V,8,H,W], rgb [V,3,H,W]")
     fm = torch.empty(V, 56, H, W, dtype=torch.float32, device=s0.device) if want_nchw else None
