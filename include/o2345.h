@@ -536,6 +536,52 @@ int o2345_mesh_texture_corners(const double* verts, long long nv, const void* tr
  * Fields and K as for o2345_obj_text.  obj_texture_text_bytes: the byte count (HOST function; 0 for K outside 1 .. 9 or n not a multiple of 3). */
 size_t o2345_obj_texture_text_bytes(long long n, int K, int normals);
 int o2345_obj_texture_text(const float* positions, const float* uv, const float* normals, long long n, int K, uint8_t* text, void* stream);
+/* ---- surface render (additive since 2.1; none in the reference: models/fast_renderer.py calls sdf_from_sdfvolume with a keyword it does not accept) ----
+ * Depth, hit point and kind per ray by an exhaustive fixed-stride march through the TRILINEAR R^3 lattice u (device float32 [R,R,R], x-major, 2 <= R <=
+ * 2048), equal to the host twin (surface.py) to the last bit: fp64, one operation at a time, in the order written, no square root in the trace.
+ *   field    g(node) = double(u) - level, or level - double(u) with inside_positive (the extraction lattice is -sdf); a value is OUTSIDE iff it is > 0.
+ *   bricks   8 x 8 x 8 cells, nb = ceil((R - 1) / 8) per axis; surface_bricks writes flags uint8 [nb,nb,nb]: 1 iff some node with index in [8 b_k,
+ *            min(8 b_k + 8, R - 1)] on every axis fails g > 0 (a NaN node sets it).
+ *   ray      o, d device float32 [n,3] widened; bound_min / bound_max HOST float32 [3] widened, ext = bmax - bmin.  Per axis k with d_k == 0: nothing is
+ *            constrained when bmin_k <= o_k <= bmax_k, else the ray misses the box; with d_k != 0: a = (bmin_k - o_k) / d_k, b = (bmax_k - o_k) / d_k,
+ *            low = min(a, b), high = max(a, b).  t0 = max(near, lows), t1 = min(far, highs); a ray that fails t0 <= t1 misses the box.  A non-finite o or
+ *            d is a BAD ray: counted, never dereferenced.
+ *   samples  h = stride * min_k(ext_k) / (R - 1) -- `stride` lattice spacings for a unit direction; h is a step in t, so a non-unit direction scales
+ *            it.  n = floor((t1 - t0) / h), n > 2^20 is a bad ray; t_j = t0 + j h (a product) for j = 0 .. n, one more sample at t1 when t_n < t1.
+ *   value    p_k = o_k + t d_k; x_k = (p_k - bmin_k) / ext_k * (R - 1), clamped to [0, R - 1] (a NaN clamps to 0); i_k = min(floor(x_k), R - 2), f_k =
+ *            x_k - i_k; v = sum over the eight corners of ((wx wy) wz) g(corner), w = f or 1 - f, dx outer, dy, dz inner, from 0, left to right.
+ *   skip     with flags given, a sample whose cell lies in a brick with flag 0 is outside without a lookup (exact in floating point: eight corners > 0
+ *            give a sum of non-negative products, one of them >= g / 8 > 0); a skipped predecessor is evaluated when a bracket needs it.  flags NULL:
+ *            every sample is looked up; the outputs are the same bytes, only the lookup counter differs.
+ *   march    j = the first sample that is not outside.  Its value NaN: the ray is STALLED (kind 0, counted).  j = 0: an entry hit at t0, kind 2.  Else
+ *            lo = t_{j-1}, hi = t_j and `refine` (0 .. 32) steps tm = lo + (hi - lo) * (s_lo / (s_lo - s_hi)) on even, lo + (hi - lo) * 0.5 on odd
+ *            steps; an outside value at tm replaces lo, anything else hi; depth = lo + (hi - lo) * (s_lo / (s_lo - s_hi)), kind 1 (a non-finite depth
+ *            -- infinite lattice values -- is stalled).  No such j: a miss, kind 0.
+ *   outputs  device: depth float32 [n] = float32(t), 0 without a hit; kind uint8 [n]; point float32 [n,3] = float32(o_k + t d_k), 0 without a hit;
+ *            the hit list, int32 at the start of `workspace` (surface_trace_workspace_bytes(n) bytes, 16-byte aligned): the slots with kind != 0, each
+ *            once, in an order that changes between runs (ballot compaction, one integer atomicAdd per wave) -- the network kernels take it as `index`
+ *            with its device-side count as `n_dev`; stats (72 bytes, 8-byte aligned) = uint64 [8]: hits, entry hits, box misses, marched-through misses,
+ *            stalled, bad rays, samples visited (march samples + refinement evaluations), lattice lookups; then int32 [2]: the hit list's count, 0.
+ *   img_h, img_w: 0, 0, or the image the n = img_h img_w rays fill in raster order: a wave then takes an 8 x 8 pixel tile instead of 64 consecutive rays
+ *            (lanes of similar march length together); the results are the same bytes.
+ * No host synchronisation.  Errors: bad arguments, a workspace that is too small.
+ * camera_rays: rays through the pixel grid of a pinhole camera without skew, raster order -- K_host float32 [9] = [[fx, 0, cx], [0, fy, cy], [0, 0, 1]]
+ * (anything else is refused), c2w_host float32 [12] (rows 0 .. 2 of the 4x4), both HOST.  In fp64: v = ((px - cx) / fx, (py - cy) / fy, 1), divided by
+ * sqrt((vx vx + vy vy) + vz vz), rotated by c2w's 3x3 with sums left to right, rounded to float32 once -> rays_d device float32 [H W,3]; rays_o = c2w's
+ * translation.
+ * surface_pack: kind uint8 [H W], depth float32 [H W], rgb and grad float32 [H W,3] (read at kind != 0 only), raster order -> color uint8 [H,W,4]: the
+ * truncating quantisation of the vertex colours, alpha 255, and background_host (HOST uint8 [4]) without a hit; normal uint8 [H,W,4]: that quantisation of
+ * float32(n 0.5 + 0.5), n = grad / sqrt((gx gx + gy gy) + gz gz) in fp64 (0 for a zero or non-finite gradient), alpha 255, and 0, 0, 0, 0 without a hit;
+ * depth_out float32 [H,W]: depth, 0 without a hit.  The two images are 4-byte aligned. */
+int o2345_surface_bricks(const float* u, int grid_R, double level, int inside_positive, uint8_t* flags, void* stream);
+size_t o2345_surface_trace_workspace_bytes(long long n);
+int o2345_surface_trace(const float* u, int grid_R, const uint8_t* flags, const float* rays_o, const float* rays_d, long long n, int img_h, int img_w,
+                        double t_near, double t_far, double stride, int refine, double level, int inside_positive, const float* bound_min,
+                        const float* bound_max, void* workspace, size_t workspace_bytes, float* depth, uint8_t* kind, float* point, void* stats,
+                        void* stream);
+int o2345_camera_rays(const float* K_host, const float* c2w_host, int H, int W, float* rays_o, float* rays_d, void* stream);
+int o2345_surface_pack(const uint8_t* kind, const float* depth, const float* rgb, const float* grad, int H, int W, const uint8_t* background_host,
+                       uint8_t* color, uint8_t* normal, float* depth_out, void* stream);
 /* Load every code object of the library on the current device now (the HIP runtime loads a translation unit's kernels at its first launch: 5 - 60 ms
  * each for the units of this library, which otherwise land inside the first calls of a fresh process).  Launches nothing that touches user memory. */
 int o2345_preload(void);

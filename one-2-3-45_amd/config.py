@@ -272,3 +272,40 @@ def mesh_texture_png_level(n=None):
     if isinstance(n, bool) or int(n) != n or n < 0:
         raise ValueError(f"png_level must be an integer in [0, 9], got {n!r}")
     return _png_level("png_level", int(n))
+
+
+# ---- surface render (csrc/surface_trace.hip; surface.py is the host twin) ---------------------------------------------------------------------------------
+# pipeline.render_surface marches rays through the extraction lattice.  O2345_SURFACE_STRIDE (1.0, in (0, 8]) is the distance between two samples in
+# lattice spacings -- above 1 the march may step over parts thinner than the stride; O2345_SURFACE_REFINE (8, in [0, 32]) the number of bracket
+# refinements per hit.  O2345_PREVIEW_VIEWS=n makes pipeline.reconstruct_folder write n preview images next to the mesh ("" or "0" = off, the default:
+# nothing is launched and the result keeps its keys).
+SURFACE_STRIDE = _finite_float("O2345_SURFACE_STRIDE", os.environ.get("O2345_SURFACE_STRIDE", ""), 1.0, lambda x: 0.0 < x <= 8.0, "in (0, 8]")
+_ref = os.environ.get("O2345_SURFACE_REFINE", "")
+SURFACE_REFINE = 8 if _ref.strip() == "" else _non_negative_int("O2345_SURFACE_REFINE", _ref)
+del _ref
+if SURFACE_REFINE > 32:
+    raise ValueError(f"O2345_SURFACE_REFINE must be an integer in [0, 32], got {SURFACE_REFINE!r}")
+PREVIEW_VIEWS = _non_negative_int("O2345_PREVIEW_VIEWS", os.environ.get("O2345_PREVIEW_VIEWS", ""))
+
+
+def surface_stride(x=None):
+    if x is None:
+        return SURFACE_STRIDE
+    return _finite_float("stride", repr(float(x)), None, lambda s: 0.0 < s <= 8.0, "in (0, 8]")
+
+
+def surface_refine(n=None):
+    if n is None:
+        return SURFACE_REFINE
+    if isinstance(n, bool) or int(n) != n or not 0 <= n <= 32:
+        raise ValueError(f"refine must be an integer in [0, 32], got {n!r}")
+    return int(n)
+
+
+def preview_views(n=None):
+    """None -> the configured default; anything else must be a non-negative integer (an explicit 0 is off whatever the default)."""
+    if n is None:
+        return PREVIEW_VIEWS
+    if isinstance(n, bool) or int(n) != n or n < 0:
+        raise ValueError(f"preview_views must be a non-negative integer, got {n!r}")
+    return int(n)

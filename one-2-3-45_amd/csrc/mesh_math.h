@@ -67,6 +67,15 @@ O2345_HD void mesh_normal_f32(const float* __restrict__ grad, long long i, const
     n[2] = ok ? (float)g[1] : 0.f;
 }
 
+// n = g / l with l = sqrt((gx gx + gy gy) + gz gz) in fp64, the length mesh_normal_f32 takes -> true; a zero or non-finite length gives n = 0 and false
+O2345_HD bool unit_normal(const double (&g)[3], double (&n)[3]) {
+    const double l = sqrt(g[0] * g[0] + g[1] * g[1] + g[2] * g[2]);
+    const bool ok = l > 0.0 && l < (double)INFINITY;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) n[k] = ok ? g[k] / l : 0.0;
+    return ok;
+}
+
 // np.array(color * 255, dtype=uint8) (trainer_generic.py:1377): truncation
 O2345_HD uint8_t mesh_colour_u8(float c) { return (uint8_t)(int)(c * 255.f); }
 

@@ -1182,3 +1182,127 @@ def obj_texture_text(positions, uv, normals=None, K=None, bounds=None):
     text = torch.empty(L.o2345_obj_texture_text_bytes(n, int(K), int(normals is not None)), dtype=torch.uint8, device=positions.device)
     check(L.o2345_obj_texture_text(_p(positions), _p(uv), _p(normals), n, int(K), _p(text, torch.uint8), _stream()), "obj_texture_text")
     return text
+
+
+# ---------------------------------------------------------------------------------------------------------- surface render
+_SURFACE_STATS_BYTES = 72           # include/o2345.h: uint64 [8] + int32 [2]
+_SURFACE_INFO = ("hits", "entry_hits", "box_misses", "misses", "stalled", "bad_rays", "samples", "lookups")
+
+
+def _surface_lattice(u, what):
+    if u.dim() != 3 or len(set(u.shape)) != 1 or not 2 <= u.shape[0] <= 2048:
+        raise ValueError(f"{what}: the lattice is float32 [R,R,R] with 2 <= R <= 2048, got {tuple(u.shape)}")
+    _p(u)
+    return int(u.shape[0])
+
+
+@_on_device
+def surface_bricks(u, level=0.0, inside_positive=False):
+    """Brick flags of the surface trace (== surface.brick_flags, exactly): u float32 [R,R,R] on the device -> uint8 [nb,nb,nb], nb = ceil((R - 1) / 8);
+    1 iff a node of the brick fails g > 0, g = u - level (level - u with ``inside_positive``)."""
+    R = _surface_lattice(u, "surface_bricks")
+    nb = (R - 1 + 7) // 8
+    flags = torch.empty(nb, nb, nb, dtype=torch.uint8, device=u.device)
+    check(_lib.lib().o2345_surface_bricks(_p(u), R, float(level), int(bool(inside_positive)), _p(flags, torch.uint8), _stream()), "surface_bricks")
+    return flags
+
+
+def surface_info(stats, n_rays):
+    """The stats block of o2345_surface_trace (72 bytes, on the host) -> the info dict of surface.trace_rays"""
+    head = np.asarray(stats).reshape(-1)[:64].view(np.uint64)
+    info = {"rays": int(n_rays)}
+    info.update((k, int(v)) for k, v in zip(_SURFACE_INFO, head))
+    return info
+
+
+@_on_device
+def surface_trace(u, rays_o, rays_d, near, far, stride=None, refine=None, level=0.0, inside_positive=False, bound_min=(-1.0, -1.0, -1.0),
+                  bound_max=(1.0, 1.0, 1.0), skip=True, flags=None, image_hw=None, want_info=True):
+    """March rays through the trilinear lattice u (== surface.trace_rays, to the last bit; definitions in csrc/surface_trace.hip).  u float32 [R,R,R],
+    rays_o / rays_d float32 [n,3], all on the device; ``stride`` / ``refine`` None: the config defaults -> dict(depth f32 [n], kind u8 [n] (0 none, 1
+    hit, 2 the ray enters inside), point f32 [n,3], hits int32 [n] (the slots with kind != 0 in its first ``n_hits`` entries, in an arbitrary order),
+    n_hits int32 [1] on the device (for ``index=`` / ``n_dev=`` of the network ops), stats uint8 [72], info).  ``skip``: the empty-space skip over
+    ``flags`` (ops.surface_bricks of the same lattice, level and sign; computed here when None); the result does not depend on it.  ``image_hw`` = (H, W)
+    with H W = n: waves take 8 x 8 pixel tiles.  ``info`` (surface.trace_rays' exact counts) costs one 72-byte copy and a synchronisation; a caller that
+    queues more work passes ``want_info=False`` and reads ``stats`` later (ops.surface_info)."""
+    stride, refine = config.surface_stride(stride), config.surface_refine(refine)
+    R = _surface_lattice(u, "surface_trace")
+    near, far, level = float(near), float(far), float(level)
+    if not (np.isfinite(near) and np.isfinite(far) and np.isfinite(level)):
+        raise ValueError(f"surface_trace: near, far and level must be finite, got {near!r}, {far!r}, {level!r}")
+    if rays_o.dim() != 2 or rays_o.shape[1] != 3 or rays_d.shape != rays_o.shape:
+        raise ValueError(f"surface_trace: rays_o / rays_d must both be [n,3] (got {tuple(rays_o.shape)}, {tuple(rays_d.shape)})")
+    (bmin, pmin), (bmax, pmax) = _host3(bound_min), _host3(bound_max)
+    if bmin.shape != (3,) or bmax.shape != (3,) or not (np.isfinite(bmin).all() and np.isfinite(bmax).all() and (bmax > bmin).all()):
+        raise ValueError(f"surface_trace: bound_max must be above bound_min on every axis, both finite, got {bound_min!r} and {bound_max!r}")
+    n, dev = rays_o.shape[0], u.device
+    H, W = (0, 0) if image_hw is None else (int(image_hw[0]), int(image_hw[1]))
+    if image_hw is not None and (H < 1 or W < 1 or H * W != n):
+        raise ValueError(f"surface_trace: image_hw {image_hw!r} does not hold {n} rays")
+    if skip and flags is None:
+        flags = surface_bricks(u, level, inside_positive)
+    nb = (R - 1 + 7) // 8
+    if skip and tuple(flags.shape) != (nb, nb, nb):
+        raise ValueError(f"surface_trace: flags must be uint8 [{nb},{nb},{nb}] for R = {R}, got {tuple(flags.shape)}")
+    L = _lib.lib()
+    wsb = L.o2345_surface_trace_workspace_bytes(n)
+    if wsb == 0:
+        raise ValueError(f"surface_trace: {n} rays are too many (n < 2^31)")
+    hits = torch.empty(wsb // 4, dtype=torch.int32, device=dev)                # the workspace IS the hit list: owned by the result, not by the stream's cache
+    depth = torch.empty(n, dtype=torch.float32, device=dev)
+    kind = torch.empty(n, dtype=torch.uint8, device=dev)
+    point = torch.empty(n, 3, dtype=torch.float32, device=dev)
+    stats = torch.empty(_SURFACE_STATS_BYTES, dtype=torch.uint8, device=dev)
+    check(L.o2345_surface_trace(_p(u), R, _p(flags, torch.uint8) if skip else None, _p(rays_o), _p(rays_d), n, H, W, near, far, stride, refine, level,
+                                int(bool(inside_positive)), pmin, pmax, _p(hits, torch.int32), wsb, _p(depth), _p(kind, torch.uint8), _p(point),
+                                _p(stats, torch.uint8), _stream()), "surface_trace")
+    out = dict(depth=depth, kind=kind, point=point, hits=hits[:n], n_hits=stats[64:68].view(torch.int32), stats=stats, info=None)
+    if want_info:
+        out["info"] = surface_info(stats.cpu().numpy(), n)
+    return out
+
+
+def _camera(K, c2w, what):
+    K = np.ascontiguousarray(np.asarray(K.detach().cpu() if torch.is_tensor(K) else K, np.float32))
+    M = np.ascontiguousarray(np.asarray(c2w.detach().cpu() if torch.is_tensor(c2w) else c2w, np.float32))
+    if K.shape != (3, 3) or M.shape not in ((3, 4), (4, 4)):
+        raise ValueError(f"{what}: K [3,3] and c2w [3,4] or [4,4] expected, got {K.shape} and {M.shape}")
+    from . import surface
+    surface._pinhole(K, M)                                 # the twin's refusals: skew, a zero focal length, non-finite entries
+    return K, np.ascontiguousarray(M[:3])
+
+
+def camera_rays(K, c2w, H, W, device):
+    """Rays through the pixel grid of a pinhole camera without skew (== surface.camera_rays, exactly): K [3,3], c2w [4,4] or [3,4] on the host (or tensors:
+    copied) -> (rays_o, rays_d) float32 [H W, 3] on ``device``, raster order."""
+    K, M = _camera(K, c2w, "camera_rays")
+    H, W = int(H), int(W)
+    if H < 1 or W < 1 or H * W >= 2 ** 31:
+        raise ValueError(f"camera_rays: bad image size {H} x {W}")
+    device = torch.device(device)
+    with torch.cuda.device(device):
+        o = torch.empty(H * W, 3, dtype=torch.float32, device=device)
+        d = torch.empty(H * W, 3, dtype=torch.float32, device=device)
+        check(_lib.lib().o2345_camera_rays(K.ctypes.data_as(ctypes.c_void_p), M.ctypes.data_as(ctypes.c_void_p), H, W, _p(o), _p(d), _stream()), "camera_rays")
+    return o, d
+
+
+@_on_device
+def surface_pack(kind, depth, rgb, grad, H, W, background=(0, 0, 0, 0)):
+    """Per-ray results in raster order -> (color u8 [H,W,4], normal u8 [H,W,4], depth f32 [H,W]) on the device (== surface.pack_images, exactly): kind u8
+    [H W], depth f32 [H W], rgb / grad f32 [H W, 3], read at hits only; ``background``: four integers in [0, 255], the colour image without a hit."""
+    H, W = int(H), int(W)
+    bg = np.asarray(background)
+    if bg.shape != (4,) or not np.array_equal(bg, bg.astype(np.uint8)):
+        raise ValueError(f"surface_pack: background is four integers in [0, 255], got {background!r}")
+    bg = np.ascontiguousarray(bg, np.uint8)
+    n = H * W
+    if H < 1 or W < 1 or kind.numel() != n or depth.numel() != n or tuple(rgb.shape) != (n, 3) or tuple(grad.shape) != (n, 3):
+        raise ValueError(f"surface_pack: kind / depth [{n}] and rgb / grad [{n},3] expected for {H} x {W}")
+    dev = kind.device
+    color = torch.empty(H, W, 4, dtype=torch.uint8, device=dev)
+    normal = torch.empty(H, W, 4, dtype=torch.uint8, device=dev)
+    out = torch.empty(H, W, dtype=torch.float32, device=dev)
+    check(_lib.lib().o2345_surface_pack(_p(kind, torch.uint8), _p(depth), _p(rgb), _p(grad), H, W, bg.ctypes.data_as(ctypes.c_void_p), _p(color, torch.uint8),
+                                        _p(normal, torch.uint8), _p(out), _stream()), "surface_pack")
+    return color, normal, out

@@ -219,6 +219,14 @@ def _colours_at(wt, vol, proj, cam_pos, pts):
     return rgb, g
 
 
+def _extraction_lattice(wt, vol, resolution):
+    """u = -sdf on the resolution^3 lattice over [-1, 1]^3, float32 [R,R,R]: what marching cubes meshes and the surface render marches through"""
+    bg = wt.grid_background(resolution)
+    u = ops.sdf_mlp(wt.sdf_blob, vol["vol_cl"], None, variant=0, grid_R=resolution, sign=-1.0, precision=wt.sdf_precision, grid_tables=wt.grid_tables(resolution),
+                    maskvol=vol["maskvol"] if bg is not None else None, grid_background=bg)["sdf"]
+    return u.view(resolution, resolution, resolution)
+
+
 def _mesh_fields(wt, vol, proj, cam_pos, resolution, min_component_faces=None, keep_largest=None, info=None, smooth_iterations=None, decimate_cell=None,
                  project_iterations=None, texture=None):
     """The device work of extract_mesh, once: (verts fp64 in [-1, 1], verts_idx fp64 index coordinates, tris, rgb, u, grad).  ``grad`` is the SDF gradient
@@ -249,10 +257,7 @@ def _mesh_fields(wt, vol, proj, cam_pos, resolution, min_component_faces=None, k
     prec = wt.sdf_precision
     # build_volume's pair: ops.scatter_dense writes zeros into vol_cl wherever maskvol is zero, which is what the sparse lattice evaluation needs (a
     # hand-made ``vol`` must keep that: points without a kept corner voxel get the empty scene's value from the second extraction on)
-    bg = wt.grid_background(resolution)
-    u = ops.sdf_mlp(wt.sdf_blob, vol["vol_cl"], None, variant=0, grid_R=resolution, sign=-1.0, precision=prec, grid_tables=wt.grid_tables(resolution),
-                    maskvol=vol["maskvol"] if bg is not None else None, grid_background=bg)["sdf"]
-    u = u.view(resolution, resolution, resolution)
+    u = _extraction_lattice(wt, vol, resolution)
     verts_idx, tris = ops.marching_cubes(u, 0.0)
     cc = None
     if min_faces or largest:
@@ -344,9 +349,78 @@ def export_mesh_asset(path, wt, vol, proj, cam_pos, resolution, scale_mat=None, 
                                 texture=tex if tex and "rgb" in tex else None)
 
 
+def _surface_view(wt, vol, proj, cam_pos, u, flags, intrinsic, c2w, H, W, near, far, stride, refine, background):
+    """one image of render_surface from a lattice and its brick flags"""
+    dev = u.device
+    rays_o, rays_d = ops.camera_rays(intrinsic, c2w, H, W, dev)
+    tr = ops.surface_trace(u, rays_o, rays_d, near, far, stride=stride, refine=refine, inside_positive=True, flags=flags, image_hw=(H, W), want_info=False)
+    pts, hits, n_hits = tr["point"], tr["hits"], tr["n_hits"]
+    g = ops.sdf_mlp(wt.sdf_blob, vol["vol_cl"], pts, variant=2, precision=wt.sdf_precision, index=hits, n_dev=n_hits)["grad"]
+    x3 = wt.color_precision == "f16x3"
+    cam = torch.as_tensor(np.asarray(c2w.detach().cpu() if torch.is_tensor(c2w) else c2w, np.float32)[:3, 3].copy()).to(dev)
+    rgb, _ = ops.color_points(wt.color_xblob if x3 else wt.color_mblob, vol["vol_cl"], vol["maskvol"], vol["cmaps"], proj, cam_pos, pts, query_cam=cam,
+                              index=hits, n_dev=n_hits, want_nviews=False, mfma="x3" if x3 else True)
+    color, normal, depth = ops.surface_pack(tr["kind"], tr["depth"], rgb, g, H, W, background)
+    return dict(color=color, normal=normal, depth=depth, kind=tr["kind"].view(H, W), point=pts.view(H, W, 3),
+                info=ops.surface_info(tr["stats"].cpu().numpy(), H * W), u=u)
+
+
+@torch.no_grad()
+def render_surface(wt, vol, proj, cam_pos, intrinsic, c2w, H, W, resolution=256, near=0.0, far=1.0e6, stride=None, refine=None, u=None,
+                   background=(0, 0, 0, 0)):
+    """Depth, normal and colour image of the reconstruction's surface for the pinhole camera (intrinsic [3,3] without skew, c2w [4,4]), H x W pixels, by
+    marching the extraction lattice (ops.surface_trace; definitions in surface.py, limits in DESIGN.md section 7): the image shows the zero set of the
+    TRILINEAR resolution^3 lattice, the surface extract_mesh's marching cubes meshes, one sample per pixel.  The lattice is computed as _mesh_fields
+    computes it, or taken from ``u`` (float32 [R,R,R] = -sdf, e.g. the one extract_mesh returned: no lattice kernel runs then).  Steps: brick flags,
+    rays, trace, then on the hit list only the SDF gradient (the normal image) and the colour network as seen from the camera (ops.color_points with
+    query_cam = the camera position), then the packer.  ``near`` / ``far`` bound t along the ray on top of the [-1, 1]^3 box; ``stride`` / ``refine``
+    None: the config defaults (O2345_SURFACE_STRIDE, O2345_SURFACE_REFINE).  One synchronisation, for the counts.
+    -> dict(color u8 [H,W,4], normal u8 [H,W,4], depth f32 [H,W], kind u8 [H,W], point f32 [H,W,3], info, u)."""
+    if u is None:
+        u = _extraction_lattice(wt, vol, int(resolution))
+    flags = ops.surface_bricks(u, 0.0, True)
+    return _surface_view(wt, vol, proj, cam_pos, u, flags, intrinsic, c2w, int(H), int(W), near, far, stride, refine, background)
+
+
+@torch.no_grad()
+def render_turntable(wt, vol, proj, cam_pos, intrinsic, H, W, n_views, elevation_deg=20.0, radius=2.0, resolution=256, near=0.0, far=1.0e6, stride=None,
+                     refine=None, u=None, background=(0, 0, 0, 0), up=(0.0, 0.0, 1.0)):
+    """render_surface from ``n_views`` look-at cameras on a circle around the origin (surface.orbit_c2w: ``elevation_deg`` above the plane normal to
+    ``up``, at ``radius``); the lattice and the brick flags are computed once.  -> (list of render_surface results, c2w float32 [n,4,4])."""
+    from . import surface
+    c2ws = surface.orbit_c2w(n_views, elevation_deg, radius, up)
+    if u is None:
+        u = _extraction_lattice(wt, vol, int(resolution))
+    flags = ops.surface_bricks(u, 0.0, True)
+    return [_surface_view(wt, vol, proj, cam_pos, u, flags, intrinsic, c, int(H), int(W), near, far, stride, refine, background) for c in c2ws], c2ws
+
+
+def _write_previews(wt, vol, proj, cam_pos, u, s, n, folder):
+    """n surface renders of a folder's scene as PNGs in ``folder``: the query camera, then an orbit through it"""
+    import os
+    from . import mesh_io, surface
+    K, c2w = s["query_intrinsic"].numpy()[:3, :3], s["query_c2w"].numpy()
+    H, W = int(s["img_wh"][1]), int(s["img_wh"][0])
+    pos = c2w[:3, 3].astype(np.float64)
+    up = -c2w[:3, 1].astype(np.float64)                                   # the camera's y axis points down
+    dist = float(np.linalg.norm(pos))
+    elev = float(np.degrees(np.arcsin(np.clip(np.dot(pos, up) / dist, -0.99, 0.99))))
+    cams = [c2w] + list(surface.orbit_c2w(n, elev, dist, up)[1:])
+    flags = ops.surface_bricks(u, 0.0, True)
+    out = []
+    for k, c in enumerate(cams):
+        r = _surface_view(wt, vol, proj, cam_pos, u, flags, K, c, H, W, 0.0, 1.0e6, None, None, (0, 0, 0, 0))
+        color, normal, depth = ops.to_host_numpy(r["color"], r["normal"], r["depth"])
+        path = os.path.join(folder, f"preview_{k:03d}.png")
+        with open(path, "wb") as f:
+            f.write(mesh_io.png_bytes(color, config.mesh_texture_png_level()))
+        out.append({"path": path, "color": color, "normal": normal, "depth": depth, "c2w": np.array(c, np.float32), "info": r["info"]})
+    return out
+
+
 @torch.no_grad()
 def reconstruct_folder(root_dir, name, wt, out_ply, D=96, resolution=256, render_val_image=False, output_format=None, min_component_faces=None,
-                       keep_largest=None, smooth_iterations=None, decimate_cell=None, project_iterations=None, texture_texel=None):
+                       keep_largest=None, smooth_iterations=None, decimate_cell=None, project_iterations=None, texture_texel=None, preview_views=None):
     """run.py's reconstruction stage without the reference tree: Zero123-style folder (dataset.SceneFolder) -> coloured mesh (binary PLY in
     the original frame), optionally the val image of the target view.  ``output_format`` ".obj" / ".glb" (run.py --output_format) also writes
     ``mesh<ext>`` next to ``out_ply`` in the asset frame, from the same device buffers.  ``min_component_faces`` / ``keep_largest``: the component filter of
@@ -356,7 +430,10 @@ def reconstruct_folder(root_dir, name, wt, out_ply, D=96, resolution=256, render
     [, color, depth]); the two component counts are None when the filter is off, ``decimate`` (the counts of ops.mesh_decimate) when decimation is, and
     ``project`` (the info of ops.mesh_project) when projection is.  ``texture_texel`` (None: the config default, 0 = off): the texture atlas of
     export_mesh_asset for the ``output_format`` asset only -- the PLY stays vertex-coloured; the result's "texture" is {width, height, texel, texels},
-    or None when no textured asset was written."""
+    or None when no textured asset was written.  ``preview_views`` (None: the config default O2345_PREVIEW_VIEWS, 0 = off: nothing is launched and the
+    result keeps its keys) = n >= 1: n surface renders (render_surface on the lattice the mesh was extracted from) written as ``preview_000.png`` ... next to
+    the PLY -- view 0 is the folder's query camera, the others an orbit around the origin at its distance and elevation about its up axis; the result's
+    "previews" is the list of {path, color, normal, depth, c2w}."""
     import os
     from . import dataset, mesh_io
     if output_format not in (None, ".ply", ".obj", ".glb"):
@@ -372,7 +449,8 @@ def reconstruct_folder(root_dir, name, wt, out_ply, D=96, resolution=256, render
     project = config.mesh_project_iterations(project_iterations)
     texel = config.mesh_texture_texel(texture_texel)
     tex = {"texel": texel} if texel and output_format in (".obj", ".glb") else None
-    _, verts_idx, tris, rgb, _, _ = _mesh_fields(wt, vol, proj, cam_pos, resolution, min_component_faces, keep_largest, info=cc, smooth_iterations=smooth,
+    previews = config.preview_views(preview_views)
+    _, verts_idx, tris, rgb, u, _ = _mesh_fields(wt, vol, proj, cam_pos, resolution, min_component_faces, keep_largest, info=cc, smooth_iterations=smooth,
                                                  decimate_cell=cell, project_iterations=project, texture=tex)
     rgb = rgb if verts_idx.shape[0] else None
     nv, nt = mesh_io.export_mesh(out_ply, verts_idx, tris, resolution, scale_mat=s["scale_mat"], trans_mat=s["trans_mat"], vertex_colors=rgb)
@@ -383,6 +461,8 @@ def reconstruct_folder(root_dir, name, wt, out_ply, D=96, resolution=256, render
         out["asset"] = os.path.join(os.path.dirname(str(out_ply)), "mesh" + output_format)
         mesh_io.export_asset(out["asset"], verts_idx, tris, resolution, scale_mat=s["scale_mat"], trans_mat=s["trans_mat"], vertex_colors=rgb,
                              texture=tex if tex and "rgb" in tex else None)
+    if previews:
+        out["previews"] = _write_previews(wt, vol, proj, cam_pos, u, s, previews, os.path.dirname(str(out_ply)))
     if render_val_image:
         r = render(wt, vol, proj, cam_pos, T(s["rays"]["rays_o"]), T(s["rays"]["rays_v"]), float(s["query_near_far"][0]), float(s["query_near_far"][1]),
                    T(s["query_c2w"][:3, 3]))
