@@ -14,6 +14,7 @@ The convolutions (FeatureNet, compress layer, sparse cost-regularisation network
 default, fp32 VALU kernels in ``"fp32"`` mode -- per object when a mode is handed to ``pipeline.SceneWeights`` / ``featurenet.set_precision``,
 else this global one.  Cost-volume gather, sampling, compositing and marching cubes are precision-independent (fp32 / fp64 / integer)."""
 import os
+from collections import namedtuple
 
 PRECISIONS = ("f16x3", "fp32")
 PRECISION = os.environ.get("O2345_PRECISION", "f16x3")
@@ -264,6 +265,17 @@ def mesh_texture_texel(n=None):
     if isinstance(n, bool) or int(n) != n or n < 0:
         raise ValueError(f"texture_texel must be 0 (off) or an integer in [4, 64], got {n!r}")
     return _texture_texel("texture_texel", int(n))
+
+
+# the options of the mesh path, resolved and validated (mesh_options; 0 / False = off); project_max_move: the projection's move limit for this decimate_cell
+MeshOptions = namedtuple("MeshOptions", "min_component_faces keep_largest decimate_cell project_iterations project_max_move smooth_iterations texture_texel")
+
+
+def mesh_options(min_component_faces=None, keep_largest=None, decimate_cell=None, project_iterations=None, smooth_iterations=None, texture_texel=None):
+    """Every option of the mesh path through its validator, once per call: None -> the module constant as it is NOW, anything else as given."""
+    cell = mesh_decimate_cell(decimate_cell)
+    return MeshOptions(mesh_min_component_faces(min_component_faces), mesh_keep_largest(keep_largest), cell, mesh_project_iterations(project_iterations),
+                       mesh_project_max_move(None, cell), mesh_smooth_iterations(smooth_iterations), mesh_texture_texel(texture_texel))
 
 
 def mesh_texture_png_level(n=None):

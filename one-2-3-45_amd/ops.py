@@ -54,9 +54,41 @@ def _f(t):
     return t.detach().to(torch.float32).contiguous()
 
 
+def host_f32(a):                          # a tensor or an array -> a contiguous float32 host array (the small arguments: bounds, matrices, cameras)
+    return np.ascontiguousarray(np.asarray(a.detach().cpu() if torch.is_tensor(a) else a, np.float32))
+
+
 def _host3(v):
-    a = np.ascontiguousarray(np.asarray(v.detach().cpu() if torch.is_tensor(v) else v, np.float32).reshape(-1)[:3])
+    a = host_f32(v).reshape(-1)[:3]
     return a, a.ctypes.data_as(ctypes.c_void_p)
+
+
+def _bounds(bound_min, bound_max, what):
+    """The box of a lattice, validated -> ((bound_min, its pointer), (bound_max, its pointer)): three float32 each, on the host."""
+    (bmin, pmin), (bmax, pmax) = _host3(bound_min), _host3(bound_max)
+    if bmin.shape != (3,) or bmax.shape != (3,) or not (np.isfinite(bmin).all() and np.isfinite(bmax).all() and (bmax > bmin).all()):
+        raise ValueError(f"{what}: bound_max must be above bound_min on every axis, both finite, got {bound_min!r} and {bound_max!r}")
+    return (bmin, pmin), (bmax, pmax)
+
+
+def _vertices(verts_idx, what=None):
+    if verts_idx.dtype != torch.float64 or verts_idx.dim() != 2 or verts_idx.shape[1] != 3:
+        raise ValueError((f"{what}: " if what else "") + f"expected vertices [N,3] float64, got {tuple(verts_idx.shape)} {verts_idx.dtype}")
+
+
+def _resolution(resolution, what):
+    if isinstance(resolution, bool) or int(resolution) != resolution or resolution < 2:
+        raise ValueError(f"{what}: resolution must be an integer >= 2, got {resolution!r}")
+    return int(resolution)
+
+
+def _obj_digits(K, bounds, n, what):
+    """The integer digits of an OBJ's coordinate fields: ``K``, or taken from ``bounds`` (one small D2H copy); range-checked before any use."""
+    if K is None:
+        K = mesh_io.obj_coordinate_digits(bounds.cpu().numpy() if torch.is_tensor(bounds) else bounds) if n else 1
+    if not 1 <= int(K) <= 9:
+        raise ValueError(f"{what}: K = {K} integer digits (1 .. 9)")
+    return int(K)
 
 
 def to_host_numpy(*tensors):
@@ -814,9 +846,8 @@ def _triangles(tris, what=None):
 def _mesh_frame(bound_min, bound_max, scale_mat, trans_mat):
     """Bounds (3 numbers each) and the two 4x4 matrices (tensors, arrays or None) -> ([four host pointers or None], the float32 arrays behind them, which
     the caller keeps alive over the call)."""
-    host = lambda a: None if a is None else np.ascontiguousarray((a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)), np.float32)
-    mat = lambda a: None if a is None else host(a).reshape(-1, 4, 4)[0].copy()
-    keep = [host(bound_min).reshape(3), host(bound_max).reshape(3), mat(scale_mat), mat(trans_mat)]
+    mat = lambda a: None if a is None else host_f32(a).reshape(-1, 4, 4)[0].copy()
+    keep = [host_f32(bound_min).reshape(3), host_f32(bound_max).reshape(3), mat(scale_mat), mat(trans_mat)]
     return [None if a is None else a.ctypes.data_as(ctypes.c_void_p) for a in keep], keep
 
 
@@ -874,15 +905,12 @@ def obj_text(positions, indices, rgba=None, normals=None, K=None, bounds=None):
     """The buffers of mesh_asset_pack -> the bytes of a Wavefront OBJ (uint8 tensor on the device): fixed-width "v" [+ colour], "vn", "f" records
     (include/o2345.h).  ``K``: integer digits of the coordinate fields; taken from ``bounds`` (one small D2H copy) when not given."""
     n, m = positions.shape[0], indices.shape[0]
-    if K is None:
-        K = mesh_io.obj_coordinate_digits(bounds.cpu().numpy() if torch.is_tensor(bounds) else bounds) if n else 1
+    K = _obj_digits(K, bounds, n, "obj_text")
     L = _lib.lib()
-    nbytes = L.o2345_obj_text_bytes(n, m, int(K), int(rgba is not None), int(normals is not None))
-    if not 1 <= int(K) <= 9:
-        raise ValueError(f"obj_text: K = {K} integer digits (1 .. 9)")
+    nbytes = L.o2345_obj_text_bytes(n, m, K, int(rgba is not None), int(normals is not None))
     text = torch.empty(nbytes, dtype=torch.uint8, device=positions.device)
     table = _obj_color_table(positions.device) if rgba is not None else None
-    check(L.o2345_obj_text(_p(positions), _p(rgba, torch.uint8), _p(normals), n, _p(indices, torch.int32), m, int(K), _p(table, torch.uint8),
+    check(L.o2345_obj_text(_p(positions), _p(rgba, torch.uint8), _p(normals), n, _p(indices, torch.int32), m, K, _p(table, torch.uint8),
                            _p(text, torch.uint8), _stream()), "obj_text")
     return text
 
@@ -891,8 +919,7 @@ def obj_text(positions, indices, rgba=None, normals=None, K=None, bounds=None):
 def mc_verts_to_world(verts_idx, grid_R, bound_min, bound_max):
     """Index-space marching-cubes vertices (fp64 [N,3] on the device) -> world coordinates IN PLACE: v / (R - 1) * (bound_max - bound_min) + bound_min in
     fp64 (sparse_neus_renderer.py:936), the same IEEE expression numpy evaluates on the host.  bound_min / bound_max: three float32 numbers each."""
-    b0 = np.asarray(bound_min.detach().cpu() if torch.is_tensor(bound_min) else bound_min, np.float32).reshape(3)
-    b1 = np.asarray(bound_max.detach().cpu() if torch.is_tensor(bound_max) else bound_max, np.float32).reshape(3)
+    b0, b1 = host_f32(bound_min).reshape(3), host_f32(bound_max).reshape(3)
     ext = np.ascontiguousarray((b1 - b0).astype(np.float64))          # the reference subtracts its float32 bound arrays, numpy promotes afterwards
     off = np.ascontiguousarray(b0.astype(np.float64))
     check(_lib.lib().o2345_mc_verts_to_world(_p(verts_idx, torch.float64), verts_idx.shape[0], int(grid_R), ext.ctypes.data_as(ctypes.c_void_p),
@@ -1016,8 +1043,7 @@ def mesh_decimate(verts_idx, tris, cell=None):
     if cell == 0.0:
         return verts_idx, tris, None, None
     tp, ib = _triangles(tris)
-    if verts_idx.dtype != torch.float64 or verts_idx.dim() != 2 or verts_idx.shape[1] != 3:
-        raise ValueError(f"expected vertices [N,3] float64, got {tuple(verts_idx.shape)} {verts_idx.dtype}")
+    _vertices(verts_idx)
     L = _lib.lib()
     nv, nt, dev = verts_idx.shape[0], tris.shape[0], verts_idx.device
     wsb = L.o2345_mesh_decimate_workspace_bytes(nv, nt)
@@ -1053,13 +1079,9 @@ def mesh_project(blob, vol_cl, verts_idx, resolution, iterations, level=0.0, tol
     level = float(level)
     if not np.isfinite(level):
         raise ValueError(f"mesh_project: level must be finite, got {level!r}")
-    if isinstance(resolution, bool) or int(resolution) != resolution or resolution < 2:
-        raise ValueError(f"mesh_project: resolution must be an integer >= 2, got {resolution!r}")
-    if verts_idx.dtype != torch.float64 or verts_idx.dim() != 2 or verts_idx.shape[1] != 3:
-        raise ValueError(f"expected vertices [N,3] float64, got {tuple(verts_idx.shape)} {verts_idx.dtype}")
-    (bmin, pmin), (bmax, pmax) = _host3(bound_min), _host3(bound_max)
-    if bmin.shape != (3,) or bmax.shape != (3,) or not (np.isfinite(bmin).all() and np.isfinite(bmax).all() and (bmax > bmin).all()):
-        raise ValueError(f"mesh_project: bound_max must be above bound_min on every axis, both finite, got {bound_min!r} and {bound_max!r}")
+    resolution = _resolution(resolution, "mesh_project")
+    _vertices(verts_idx)
+    (bmin, pmin), (bmax, pmax) = _bounds(bound_min, bound_max, "mesh_project")
     mode = 2 if config.sdf_precision(precision) == "f16x3" else 0
     L = _lib.lib()
     nv, dev = verts_idx.shape[0], verts_idx.device
@@ -1081,14 +1103,31 @@ def project_info(stats, iterations):
             "clamped": int(head[4]), "max_before": float(head[5:6].view(np.float64)[0]), "max_after": float(head[6:7].view(np.float64)[0])}
 
 
+def mesh_cleanup(verts_idx, tris, opts, blob, vol_cl, resolution, level=0.0, bound_min=(-1.0, -1.0, -1.0), bound_max=(1.0, 1.0, 1.0), precision=None,
+                 project=True):
+    """What follows marching cubes, in its one order: component filter -> decimation (the cell in grid spacings) -> Newton projection onto ``sdf ==
+    level`` (the field: ``blob``, ``vol_cl``, ``precision``), so that a caller's gradient, colours, packing and copies run on the kept, decimated,
+    projected vertices.  ``opts``: a config.MeshOptions; ``project=False`` withholds the projection.  A stage that is off launches nothing and leaves
+    its entry None -> (verts_idx, tris, {"components", "components_kept", "decimate", "project"})."""
+    info = {"components": None, "components_kept": None, "decimate": None, "project": None}
+    if opts.min_component_faces or opts.keep_largest:
+        verts_idx, tris, _, cc = mesh_filter_components(verts_idx, tris, opts.min_component_faces, opts.keep_largest)
+        info.update(cc)
+    if opts.decimate_cell:
+        verts_idx, tris, _, info["decimate"] = mesh_decimate(verts_idx, tris, opts.decimate_cell)
+    if opts.project_iterations and project:
+        verts_idx, info["project"] = mesh_project(blob, vol_cl, verts_idx, resolution, opts.project_iterations, level=level, max_move=opts.project_max_move,
+                                                  bound_min=bound_min, bound_max=bound_max, precision=precision)
+    return verts_idx, tris, info
+
+
 # ---------------------------------------------------------------------------------------------------------- texture atlas
 _TEXTURE_STATS_BYTES = 16           # include/o2345.h: uint64 [2]
 
 
 def _texture_mesh(verts_idx, tris, what):
     t = _triangles(tris, what)
-    if verts_idx.dtype != torch.float64 or verts_idx.dim() != 2 or verts_idx.shape[1] != 3:
-        raise ValueError(f"{what}: expected vertices [N,3] float64, got {tuple(verts_idx.shape)} {verts_idx.dtype}")
+    _vertices(verts_idx, what)
     if verts_idx.shape[0] < 1:
         raise ValueError(f"{what}: a mesh with triangles has vertices")
     return t
@@ -1112,11 +1151,8 @@ def mesh_texture_points(verts_idx, tris, texel, resolution, bound_min=(-1.0, -1.
     counters to texture_check after its own copy."""
     tp, ib = _texture_mesh(verts_idx, tris, "mesh_texture_points")
     lay = mesh_io.texture_layout(tris.shape[0], texel)
-    if isinstance(resolution, bool) or int(resolution) != resolution or resolution < 2:
-        raise ValueError(f"mesh_texture_points: resolution must be an integer >= 2, got {resolution!r}")
-    (bmin, pmin), (bmax, pmax) = _host3(bound_min), _host3(bound_max)
-    if bmin.shape != (3,) or bmax.shape != (3,) or not (np.isfinite(bmin).all() and np.isfinite(bmax).all() and (bmax > bmin).all()):
-        raise ValueError(f"mesh_texture_points: bound_max must be above bound_min on every axis, both finite, got {bound_min!r} and {bound_max!r}")
+    resolution = _resolution(resolution, "mesh_texture_points")
+    (bmin, pmin), (bmax, pmax) = _bounds(bound_min, bound_max, "mesh_texture_points")
     L = _lib.lib()
     dev, n = verts_idx.device, lay["texels"]
     assert L.o2345_mesh_texture_texels(tris.shape[0], lay["texel"], None, None) == n
@@ -1172,15 +1208,12 @@ def obj_texture_text(positions, uv, normals=None, K=None, bounds=None):
     """The buffers of mesh_texture_corners -> the records of the textured Wavefront OBJ (uint8 tensor on the device; == mesh_io.obj_texture_text_numpy):
     "v", "vt", ["vn",] "f a/a b/b c/c" (include/o2345.h).  ``K`` as for obj_text."""
     n = positions.shape[0]
-    if K is None:
-        K = mesh_io.obj_coordinate_digits(bounds.cpu().numpy() if torch.is_tensor(bounds) else bounds) if n else 1
-    if not 1 <= int(K) <= 9:
-        raise ValueError(f"obj_texture_text: K = {K} integer digits (1 .. 9)")
+    K = _obj_digits(K, bounds, n, "obj_texture_text")
     if n % 3 or tuple(uv.shape) != (n, 2):
         raise ValueError(f"obj_texture_text: expected 3 M unwelded vertices and uv [3 M, 2], got {n} and {tuple(uv.shape)}")
     L = _lib.lib()
-    text = torch.empty(L.o2345_obj_texture_text_bytes(n, int(K), int(normals is not None)), dtype=torch.uint8, device=positions.device)
-    check(L.o2345_obj_texture_text(_p(positions), _p(uv), _p(normals), n, int(K), _p(text, torch.uint8), _stream()), "obj_texture_text")
+    text = torch.empty(L.o2345_obj_texture_text_bytes(n, K, int(normals is not None)), dtype=torch.uint8, device=positions.device)
+    check(L.o2345_obj_texture_text(_p(positions), _p(uv), _p(normals), n, K, _p(text, torch.uint8), _stream()), "obj_texture_text")
     return text
 
 
@@ -1232,9 +1265,7 @@ def surface_trace(u, rays_o, rays_d, near, far, stride=None, refine=None, level=
         raise ValueError(f"surface_trace: near, far and level must be finite, got {near!r}, {far!r}, {level!r}")
     if rays_o.dim() != 2 or rays_o.shape[1] != 3 or rays_d.shape != rays_o.shape:
         raise ValueError(f"surface_trace: rays_o / rays_d must both be [n,3] (got {tuple(rays_o.shape)}, {tuple(rays_d.shape)})")
-    (bmin, pmin), (bmax, pmax) = _host3(bound_min), _host3(bound_max)
-    if bmin.shape != (3,) or bmax.shape != (3,) or not (np.isfinite(bmin).all() and np.isfinite(bmax).all() and (bmax > bmin).all()):
-        raise ValueError(f"surface_trace: bound_max must be above bound_min on every axis, both finite, got {bound_min!r} and {bound_max!r}")
+    (bmin, pmin), (bmax, pmax) = _bounds(bound_min, bound_max, "surface_trace")
     n, dev = rays_o.shape[0], u.device
     H, W = (0, 0) if image_hw is None else (int(image_hw[0]), int(image_hw[1]))
     if image_hw is not None and (H < 1 or W < 1 or H * W != n):
@@ -1263,8 +1294,7 @@ def surface_trace(u, rays_o, rays_d, near, far, stride=None, refine=None, level=
 
 
 def _camera(K, c2w, what):
-    K = np.ascontiguousarray(np.asarray(K.detach().cpu() if torch.is_tensor(K) else K, np.float32))
-    M = np.ascontiguousarray(np.asarray(c2w.detach().cpu() if torch.is_tensor(c2w) else c2w, np.float32))
+    K, M = host_f32(K), host_f32(c2w)
     if K.shape != (3, 3) or M.shape not in ((3, 4), (4, 4)):
         raise ValueError(f"{what}: K [3,3] and c2w [3,4] or [4,4] expected, got {K.shape} and {M.shape}")
     from . import surface

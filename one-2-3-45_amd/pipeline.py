@@ -1,6 +1,8 @@
 """Per-scene reconstruction on one MI355X: the hot path of export_mesh_step / val_step (trainer_generic.py:359-622,
 827-979) as a sequence of HIP calls with no host synchronisation except the three size read-backs
 (kept-voxel count, coarse-level sizes, mesh size)."""
+from collections import namedtuple
+
 import numpy as np
 import torch
 import torch.nn.functional as F
@@ -46,6 +48,10 @@ class SceneWeights:
         self.variance = float(variance)
         self.inv_s = float(np.clip(np.exp(10.0 * variance), 1e-6, 1e6))
 
+    def color_network(self):
+        """-> (blob, mfma): the colour network's weights as ops.color_points takes them in this object's colour precision"""
+        return (self.color_xblob, "x3") if self.color_precision == "f16x3" else (self.color_mblob, True)
+
     def grid_tables(self, resolution):
         """Layer 0 of the SDF network tabulated for the extraction lattice of this resolution (built once per resolution; f16x3 mode only)."""
         if self.sdf_precision != "f16x3":
@@ -90,7 +96,6 @@ class SceneWeights:
         if featurenet_sd is not None:
             _load_checked(self.featurenet, {k: t(v) for k, v in featurenet_sd.items()}, "pyramid_feature_network")
         return self
-
 
     @staticmethod
     def _read_checkpoint(path, names, allow_pickle=None):
@@ -213,9 +218,8 @@ def _index_to_world(idx, resolution):
 def _colours_at(wt, vol, proj, cam_pos, pts):
     """SDF gradient, and the colour network with it as the normal input, at float32 world points [N,3] -> (rgb, grad)"""
     g = ops.sdf_mlp(wt.sdf_blob, vol["vol_cl"], pts, variant=2, precision=wt.sdf_precision)["grad"]
-    x3 = wt.color_precision == "f16x3"
-    rgb, _ = ops.color_points(wt.color_xblob if x3 else wt.color_mblob, vol["vol_cl"], vol["maskvol"], vol["cmaps"], proj, cam_pos, pts, normals=g,
-                              want_nviews=False, mfma="x3" if x3 else True)
+    blob, mfma = wt.color_network()
+    rgb, _ = ops.color_points(blob, vol["vol_cl"], vol["maskvol"], vol["cmaps"], proj, cam_pos, pts, normals=g, want_nviews=False, mfma=mfma)
     return rgb, g
 
 
@@ -227,87 +231,59 @@ def _extraction_lattice(wt, vol, resolution):
     return u.view(resolution, resolution, resolution)
 
 
-def _mesh_fields(wt, vol, proj, cam_pos, resolution, min_component_faces=None, keep_largest=None, info=None, smooth_iterations=None, decimate_cell=None,
-                 project_iterations=None, texture=None):
-    """The device work of extract_mesh, once: (verts fp64 in [-1, 1], verts_idx fp64 index coordinates, tris, rgb, u, grad).  ``grad`` is the SDF gradient
-    at the vertices that the colour network takes as its normal input (None for an empty mesh): the asset export reuses it for the NORMAL attribute.
-    ``min_component_faces`` / ``keep_largest`` (None: the config default, off unless set): the component filter (ops.mesh_filter_components) right after
-    marching cubes, so that gradient, colours, packing and copies run on kept vertices only; a dict given as ``info`` receives its component counts
-    (None when the filter is off: nothing is launched then).
-    ``smooth_iterations`` (None: the config default, 0 = off): Taubin smoothing of the vertex positions (ops.mesh_smooth; lambda, mu and boundary pinning
-    from config) as the LAST step: gradient and colours are taken at the unsmoothed vertices, which lie on the network's zero set, so only ``verts`` and
-    ``verts_idx`` differ from an unsmoothed call; with 0 nothing is launched.
-    ``decimate_cell`` (None: the config default, 0 = off): decimation by vertex clustering (ops.mesh_decimate), the cell in units of the extraction grid's
-    spacing (index coordinates), after the component filter and BEFORE gradient and colours, which are therefore taken at the new vertices; smoothing
-    runs on the decimated mesh.  ``info`` also receives "decimate" (the op's counts, or None when it is off: nothing is launched then).
-    ``project_iterations`` (None: the config default, 0 = off): Newton projection of the vertices onto the SDF's zero set (ops.mesh_project; tolerance,
-    step and move limits from config, the move limit max(1, cell) unless configured) after the decimation and BEFORE gradient and colours, which are
-    therefore taken at the projected vertices; triangles and ``u`` are untouched.  Smoothing still runs last and deliberately leaves the surface: its
-    result is not projected again.  ``info`` also receives "project" (the op's info, or None when it is off: nothing is launched then).
-    ``texture`` (None = off: nothing is launched): a dict with "texel" = c in [4, 64] that receives the baked atlas -- "rgb", the colour network at the
-    surface point of every texel (ops.mesh_texture_points on the final unsmoothed mesh; with projection on, those points go through ops.mesh_project
-    with the same tolerance, step and move limits first, so that the texture is taken on the surface and not on the chord planes of a coarse mesh; then
-    the same gradient and colour calls as the vertices), "stats" (the point op's error counters, still on the device: nothing here synchronises for
-    them; mesh_io.export_asset raises on them after its copy), "layout" (mesh_io.texture_layout) and "project" (the info of the texel projection or
-    None).  Texels, like vertex colours, are taken before the smoothing."""
-    min_faces, largest = config.mesh_min_component_faces(min_component_faces), config.mesh_keep_largest(keep_largest)
-    smooth = config.mesh_smooth_iterations(smooth_iterations)
-    cell = config.mesh_decimate_cell(decimate_cell)
-    project = config.mesh_project_iterations(project_iterations)
+# _mesh_fields' result: verts fp64 [N,3] in [-1, 1], verts_idx the same in index coordinates, tris, rgb fp32 [N,3], the lattice u [R,R,R], grad (the SDF
+# gradient at the vertices; None for an empty mesh), info (ops.mesh_cleanup's), texture (None, or mesh_io.export_asset's ``texture`` dict)
+MeshFields = namedtuple("MeshFields", "verts verts_idx tris rgb u grad info texture")
+
+
+def _mesh_fields(wt, vol, proj, cam_pos, resolution, opts):
+    """The device work of extract_mesh, once -> MeshFields; ``opts``: a config.MeshOptions.  Marching cubes, then the clean-up chain (ops.mesh_cleanup),
+    then gradient and colours at the resulting vertices: the asset export reuses that gradient, the colour network's normal input, for NORMAL.
+    ``texture_texel`` = c in [4, 64]: ``texture`` is the baked atlas -- "rgb", the colour network at the surface point of every texel
+    (ops.mesh_texture_points on the final unsmoothed mesh; with projection on, those points go through ops.mesh_project with the same limits first, so
+    that the texture is taken on the surface and not on the chord planes of a coarse mesh), "stats" (the point op's error counters, still on the
+    device: mesh_io.export_asset raises on them after its copy), "layout" (mesh_io.texture_layout), "project" (the texel projection's info) and "texel".
+    ``smooth_iterations``: Taubin smoothing (ops.mesh_smooth; factors and pinning from config) as the LAST step: gradient, colours and texels are taken
+    at the unsmoothed vertices, which lie on the zero set, so only ``verts`` and ``verts_idx`` differ; the result is not projected again."""
     prec = wt.sdf_precision
     # build_volume's pair: ops.scatter_dense writes zeros into vol_cl wherever maskvol is zero, which is what the sparse lattice evaluation needs (a
     # hand-made ``vol`` must keep that: points without a kept corner voxel get the empty scene's value from the second extraction on)
     u = _extraction_lattice(wt, vol, resolution)
     verts_idx, tris = ops.marching_cubes(u, 0.0)
-    cc = None
-    if min_faces or largest:
-        verts_idx, tris, _, cc = ops.mesh_filter_components(verts_idx, tris, min_faces, largest)
-    dec = None
-    if cell:
-        verts_idx, tris, _, dec = ops.mesh_decimate(verts_idx, tris, cell)
-    pro = None
-    if project:
-        verts_idx, pro = ops.mesh_project(wt.sdf_blob, vol["vol_cl"], verts_idx, resolution, project, max_move=config.mesh_project_max_move(None, cell),
-                                          precision=prec)
-    if info is not None:
-        info["components"], info["components_kept"] = (cc["components"], cc["components_kept"]) if cc else (None, None)
-        info["decimate"] = dec
-        info["project"] = pro
+    verts_idx, tris, info = ops.mesh_cleanup(verts_idx, tris, opts, wt.sdf_blob, vol["vol_cl"], resolution, precision=prec)
     verts = _index_to_world(verts_idx, resolution)
     pts = verts.to(torch.float32).contiguous()
     if pts.shape[0] == 0:
-        return verts, verts_idx, tris, torch.zeros(0, 3, device=pts.device), u, None
+        return MeshFields(verts, verts_idx, tris, torch.zeros(0, 3, device=pts.device), u, None, info, None)
     rgb, g = _colours_at(wt, vol, proj, cam_pos, pts)
-    if texture is not None and tris.shape[0]:
-        tpts, tworld, tstats = ops.mesh_texture_points(verts_idx, tris, texture["texel"], resolution, validate=False)
+    texture = None
+    if opts.texture_texel and tris.shape[0]:
+        tpts, tworld, tstats = ops.mesh_texture_points(verts_idx, tris, opts.texture_texel, resolution, validate=False)
         tpro = None
-        if project:
-            tpts, tpro = ops.mesh_project(wt.sdf_blob, vol["vol_cl"], tpts, resolution, project, max_move=config.mesh_project_max_move(None, cell), precision=prec)
+        if opts.project_iterations:
+            tpts, tpro = ops.mesh_project(wt.sdf_blob, vol["vol_cl"], tpts, resolution, opts.project_iterations, max_move=opts.project_max_move, precision=prec)
             tworld = _index_to_world(tpts, resolution).to(torch.float32).contiguous()
         trgb, _ = _colours_at(wt, vol, proj, cam_pos, tworld)
-        texture.update(rgb=trgb, stats=tstats, project=tpro, layout=ops.mesh_io.texture_layout(tris.shape[0], texture["texel"]))
-    if smooth:
-        verts_idx = ops.mesh_smooth(verts_idx, tris, smooth)
+        texture = dict(texel=opts.texture_texel, rgb=trgb, stats=tstats, project=tpro, layout=ops.mesh_io.texture_layout(tris.shape[0], opts.texture_texel))
+    if opts.smooth_iterations:
+        verts_idx = ops.mesh_smooth(verts_idx, tris, opts.smooth_iterations)
         verts = _index_to_world(verts_idx, resolution)
-    return verts, verts_idx, tris, rgb, u, g
+    return MeshFields(verts, verts_idx, tris, rgb, u, g, info, texture)
 
 
 def _texture_block(texture):
     """-> the "texture" entry of a result dict: {width, height, texel, texels} or None"""
-    if not texture or "layout" not in texture:
-        return None
-    L = texture["layout"]
-    return {"width": L["width"], "height": L["height"], "texel": L["texel"], "texels": L["texels"]}
+    return {k: texture["layout"][k] for k in ("width", "height", "texel", "texels")} if texture else None
 
 
 @torch.no_grad()
 def extract_mesh(wt, vol, proj, cam_pos, resolution, return_index_verts=False, min_component_faces=None, keep_largest=None, smooth_iterations=None,
                  decimate_cell=None, project_iterations=None):
     """extract_fields + marching cubes [+ component filter] [+ decimation] [+ projection onto the zero set] + vertex colouring
-    (trainer_generic.py:1309-1363) [+ smoothing], all on the device."""
-    verts, verts_idx, tris, rgb, u, _ = _mesh_fields(wt, vol, proj, cam_pos, resolution, min_component_faces, keep_largest, smooth_iterations=smooth_iterations,
-                                                     decimate_cell=decimate_cell, project_iterations=project_iterations)
-    return (verts_idx if return_index_verts else verts), tris, rgb, u
+    (trainer_generic.py:1309-1363) [+ smoothing], all on the device.  The options: None = the config default, off unless set (config.mesh_options)."""
+    m = _mesh_fields(wt, vol, proj, cam_pos, resolution,
+                     config.mesh_options(min_component_faces, keep_largest, decimate_cell, project_iterations, smooth_iterations, texture_texel=0))
+    return (m.verts_idx if return_index_verts else m.verts), m.tris, m.rgb, m.u
 
 
 @torch.no_grad()
@@ -315,15 +291,11 @@ def export_mesh_ply(path, wt, vol, proj, cam_pos, resolution, scale_mat=None, tr
                     smooth_iterations=None, decimate_cell=None, project_iterations=None):
     """validate_colored_mesh end to end (trainer_generic.py:1309-1382): SDF grid, marching cubes, vertex colours, frame transforms,
     uint8 colours and the binary PLY -- records packed on the device (csrc/mesh_pack.hip), one D2H copy, one file write.
-    ``min_component_faces`` / ``keep_largest`` / ``decimate_cell`` / ``project_iterations`` / ``smooth_iterations``: the component filter, the
-    decimation, the projection and the smoothing of _mesh_fields.
-    Returns (n_vertices, n_triangles)."""
+    The options are extract_mesh's.  Returns (n_vertices, n_triangles)."""
     from . import mesh_io
-    verts_idx, tris, rgb, _ = extract_mesh(wt, vol, proj, cam_pos, resolution, return_index_verts=True, min_component_faces=min_component_faces,
-                                           keep_largest=keep_largest, smooth_iterations=smooth_iterations, decimate_cell=decimate_cell,
-                                           project_iterations=project_iterations)
-    return mesh_io.export_mesh(path, verts_idx, tris, resolution, scale_mat=scale_mat, trans_mat=trans_mat,
-                               vertex_colors=rgb if verts_idx.shape[0] else None)
+    verts_idx, tris, rgb, _ = extract_mesh(wt, vol, proj, cam_pos, resolution, True, min_component_faces, keep_largest, smooth_iterations, decimate_cell,
+                                           project_iterations)
+    return mesh_io.export_mesh(path, verts_idx, tris, resolution, scale_mat=scale_mat, trans_mat=trans_mat, vertex_colors=rgb if verts_idx.shape[0] else None)
 
 
 @torch.no_grad()
@@ -332,21 +304,17 @@ def export_mesh_asset(path, wt, vol, proj, cam_pos, resolution, scale_mat=None, 
     """export_mesh_ply followed by convert_mesh_format (utils/utils.py:31-47) without the PLY in between: the coloured mesh as ``.glb`` or ``.obj`` in the
     asset frame ((x, y, z) -> (x, z, y), faces reversed), buffers / text packed on the device (csrc/mesh_export.hip).  ``normals=True`` adds unit vertex
     normals from the SDF gradient the vertex colouring already computed (at the unsmoothed vertices when ``smooth_iterations`` is on, at the projected ones
-    when ``project_iterations`` is).  A ``.ply`` path
-    gives export_mesh_ply's file.  Returns (n_vertices, n_triangles).
+    when ``project_iterations`` is).  A ``.ply`` path gives export_mesh_ply's file.  Returns (n_vertices, n_triangles).
     ``texture_texel`` (None: the config default, 0 = off) = c in [4, 64]: the textured asset instead -- the colour network baked into an atlas of one
     c x c cell per pair of triangles (_mesh_fields, ``texture``), 3 M unwelded vertices with texture coordinates and no vertex colours; the PNG sits inside
     the ``.glb``, or as ``.mtl`` + ``.png`` next to the ``.obj``.  A ``.ply`` path with a texture requested raises ValueError."""
     from . import mesh_io
-    texel = config.mesh_texture_texel(texture_texel)
-    if texel and mesh_io._asset_ext(path) == ".ply":
+    opts = config.mesh_options(min_component_faces, keep_largest, decimate_cell, project_iterations, smooth_iterations, texture_texel)
+    if opts.texture_texel and mesh_io._asset_ext(path) == ".ply":
         raise ValueError("texture: a .ply has no texture coordinates; the output is .glb or .obj")
-    tex = {"texel": texel} if texel else None
-    _, verts_idx, tris, rgb, _, g = _mesh_fields(wt, vol, proj, cam_pos, resolution, min_component_faces, keep_largest, smooth_iterations=smooth_iterations,
-                                                 decimate_cell=decimate_cell, project_iterations=project_iterations, texture=tex)
-    return mesh_io.export_asset(path, verts_idx, tris, resolution, scale_mat=scale_mat, trans_mat=trans_mat,
-                                vertex_colors=rgb if verts_idx.shape[0] else None, normals=g if normals else None,
-                                texture=tex if tex and "rgb" in tex else None)
+    m = _mesh_fields(wt, vol, proj, cam_pos, resolution, opts)
+    return mesh_io.export_asset(path, m.verts_idx, m.tris, resolution, scale_mat=scale_mat, trans_mat=trans_mat,
+                                vertex_colors=m.rgb if m.verts_idx.shape[0] else None, normals=m.grad if normals else None, texture=m.texture)
 
 
 def _surface_view(wt, vol, proj, cam_pos, u, flags, intrinsic, c2w, H, W, near, far, stride, refine, background):
@@ -356,10 +324,10 @@ def _surface_view(wt, vol, proj, cam_pos, u, flags, intrinsic, c2w, H, W, near, 
     tr = ops.surface_trace(u, rays_o, rays_d, near, far, stride=stride, refine=refine, inside_positive=True, flags=flags, image_hw=(H, W), want_info=False)
     pts, hits, n_hits = tr["point"], tr["hits"], tr["n_hits"]
     g = ops.sdf_mlp(wt.sdf_blob, vol["vol_cl"], pts, variant=2, precision=wt.sdf_precision, index=hits, n_dev=n_hits)["grad"]
-    x3 = wt.color_precision == "f16x3"
-    cam = torch.as_tensor(np.asarray(c2w.detach().cpu() if torch.is_tensor(c2w) else c2w, np.float32)[:3, 3].copy()).to(dev)
-    rgb, _ = ops.color_points(wt.color_xblob if x3 else wt.color_mblob, vol["vol_cl"], vol["maskvol"], vol["cmaps"], proj, cam_pos, pts, query_cam=cam,
-                              index=hits, n_dev=n_hits, want_nviews=False, mfma="x3" if x3 else True)
+    blob, mfma = wt.color_network()
+    cam = torch.as_tensor(ops.host_f32(c2w)[:3, 3].copy()).to(dev)
+    rgb, _ = ops.color_points(blob, vol["vol_cl"], vol["maskvol"], vol["cmaps"], proj, cam_pos, pts, query_cam=cam, index=hits, n_dev=n_hits,
+                              want_nviews=False, mfma=mfma)
     color, normal, depth = ops.surface_pack(tr["kind"], tr["depth"], rgb, g, H, W, background)
     return dict(color=color, normal=normal, depth=depth, kind=tr["kind"].view(H, W), point=pts.view(H, W, 3),
                 info=ops.surface_info(tr["stats"].cpu().numpy(), H * W), u=u)
@@ -423,9 +391,7 @@ def reconstruct_folder(root_dir, name, wt, out_ply, D=96, resolution=256, render
                        keep_largest=None, smooth_iterations=None, decimate_cell=None, project_iterations=None, texture_texel=None, preview_views=None):
     """run.py's reconstruction stage without the reference tree: Zero123-style folder (dataset.SceneFolder) -> coloured mesh (binary PLY in
     the original frame), optionally the val image of the target view.  ``output_format`` ".obj" / ".glb" (run.py --output_format) also writes
-    ``mesh<ext>`` next to ``out_ply`` in the asset frame, from the same device buffers.  ``min_component_faces`` / ``keep_largest``: the component filter of
-    _mesh_fields (None: the config default); ``smooth_iterations``: its smoothing (None: the config default, 0 = off); ``decimate_cell``: its decimation
-    (None: the config default, 0 = off); ``project_iterations``: its projection onto the zero set (None: the config default, 0 = off).  Returns
+    ``mesh<ext>`` next to ``out_ply`` in the asset frame, from the same device buffers.  The mesh options are extract_mesh's.  Returns
     dict(vertices, triangles, kept_voxels, ply, components, components_kept, smooth_iterations, decimate_cell, decimate, project_iterations, project[, asset]
     [, color, depth]); the two component counts are None when the filter is off, ``decimate`` (the counts of ops.mesh_decimate) when decimation is, and
     ``project`` (the info of ops.mesh_project) when projection is.  ``texture_texel`` (None: the config default, 0 = off): the texture atlas of
@@ -443,26 +409,21 @@ def reconstruct_folder(root_dir, name, wt, out_ply, D=96, resolution=256, render
     T = lambda t: t.to(dev).contiguous().float()
     vol = build_volume(wt, T(s["images"]), T(s["affine_mats"]), s["partial_vol_origin"].numpy(), D, 2.0 / (D - 1))
     proj, cam_pos = camera_terms(T(s["intrinsics"]), T(s["w2cs"]))
-    cc = {}
-    smooth = config.mesh_smooth_iterations(smooth_iterations)
-    cell = config.mesh_decimate_cell(decimate_cell)
-    project = config.mesh_project_iterations(project_iterations)
-    texel = config.mesh_texture_texel(texture_texel)
-    tex = {"texel": texel} if texel and output_format in (".obj", ".glb") else None
+    opts = config.mesh_options(min_component_faces, keep_largest, decimate_cell, project_iterations, smooth_iterations, texture_texel)
     previews = config.preview_views(preview_views)
-    _, verts_idx, tris, rgb, u, _ = _mesh_fields(wt, vol, proj, cam_pos, resolution, min_component_faces, keep_largest, info=cc, smooth_iterations=smooth,
-                                                 decimate_cell=cell, project_iterations=project, texture=tex)
-    rgb = rgb if verts_idx.shape[0] else None
-    nv, nt = mesh_io.export_mesh(out_ply, verts_idx, tris, resolution, scale_mat=s["scale_mat"], trans_mat=s["trans_mat"], vertex_colors=rgb)
-    out = {"vertices": nv, "triangles": nt, "kept_voxels": int(vol["n_voxels"]), "ply": str(out_ply), "components": cc["components"],
-           "components_kept": cc["components_kept"], "smooth_iterations": smooth, "decimate_cell": cell, "decimate": cc["decimate"],
-           "project_iterations": project, "project": cc["project"], "texture": _texture_block(tex)}
-    if output_format in (".obj", ".glb"):
+    asset = output_format in (".obj", ".glb")
+    m = _mesh_fields(wt, vol, proj, cam_pos, resolution, opts if asset else opts._replace(texture_texel=0))          # the atlas is for the asset only
+    rgb = m.rgb if m.verts_idx.shape[0] else None
+    nv, nt = mesh_io.export_mesh(out_ply, m.verts_idx, m.tris, resolution, scale_mat=s["scale_mat"], trans_mat=s["trans_mat"], vertex_colors=rgb)
+    out = {"vertices": nv, "triangles": nt, "kept_voxels": int(vol["n_voxels"]), "ply": str(out_ply), "components": m.info["components"],
+           "components_kept": m.info["components_kept"], "smooth_iterations": opts.smooth_iterations, "decimate_cell": opts.decimate_cell,
+           "decimate": m.info["decimate"], "project_iterations": opts.project_iterations, "project": m.info["project"], "texture": _texture_block(m.texture)}
+    if asset:
         out["asset"] = os.path.join(os.path.dirname(str(out_ply)), "mesh" + output_format)
-        mesh_io.export_asset(out["asset"], verts_idx, tris, resolution, scale_mat=s["scale_mat"], trans_mat=s["trans_mat"], vertex_colors=rgb,
-                             texture=tex if tex and "rgb" in tex else None)
+        mesh_io.export_asset(out["asset"], m.verts_idx, m.tris, resolution, scale_mat=s["scale_mat"], trans_mat=s["trans_mat"], vertex_colors=rgb,
+                             texture=m.texture)
     if previews:
-        out["previews"] = _write_previews(wt, vol, proj, cam_pos, u, s, previews, os.path.dirname(str(out_ply)))
+        out["previews"] = _write_previews(wt, vol, proj, cam_pos, m.u, s, previews, os.path.dirname(str(out_ply)))
     if render_val_image:
         r = render(wt, vol, proj, cam_pos, T(s["rays"]["rays_o"]), T(s["rays"]["rays_v"]), float(s["query_near_far"][0]), float(s["query_near_far"][1]),
                    T(s["query_c2w"][:3, 3]))

@@ -97,14 +97,17 @@ class GeneralRenderingNetwork(nn.Module):
             dev = self.s.device
             ops.preload(dev)
             with torch.cuda.device(dev):
-                xb, mb = self._blobs()
-                x3 = config.color_precision() == "f16x3"
+                blob, mfma = self.color_network()
                 z = lambda *sh: torch.zeros(*sh, device=dev)
                 eye = torch.eye(4, device=dev)[None]
                 proj, cam = ops.camera_terms(torch.eye(3, device=dev)[None].contiguous(), eye.contiguous())
-                ops.color_points(xb if x3 else mb, z(2, 2, 2, 16), z(8), z(1, 2, 2, 64), proj, cam, z(32, 3), normals=z(32, 3) + 1.0, want_nviews=False,
-                                 mfma="x3" if x3 else True)
+                ops.color_points(blob, z(2, 2, 2, 16), z(8), z(1, 2, 2, 64), proj, cam, z(32, 3), normals=z(32, 3) + 1.0, want_nviews=False, mfma=mfma)
         return self
+
+    def color_network(self):
+        """-> (blob, mfma): the weights as ops.color_points takes them in the configured colour precision"""
+        xb, mb = self._blobs()
+        return (xb, "x3") if config.color_precision() == "f16x3" else (mb, True)
 
     def mfma_blob(self):
         return self._blobs()[1]
@@ -118,10 +121,7 @@ class GeneralRenderingNetwork(nn.Module):
         (rgb [n_rays, n_samples, 3], valid_mask [n_rays]) like rendering_network.py:122-129."""
         if isinstance(geometry_feat, DeferredColour):
             d = geometry_feat
-            if config.color_precision() == "f16x3":
-                blob, mode = self.x3_blob(), "x3"
-            else:
-                blob, mode = self.mfma_blob(), True
+            blob, mode = self.color_network()
             rgb, nv = ops.color_points(blob, d.vol_cl, d.maskvol, d.cmaps, d.proj, d.cam_pos, d.pts,
                                        query_cam=d.query_cam, normals=d.normals, want_nviews=True, mfma=mode)
             R, S = d.shape
@@ -133,8 +133,8 @@ class GeneralRenderingNetwork(nn.Module):
             raise ValueError("o2345 GeneralRenderingNetwork.forward: pass a DeferredColour or the reference's four tensors")
         R, S = geometry_feat.shape[:2]
         V = rgb_feat.shape[0]
-        x3 = config.color_precision() == "f16x3"
-        rgb, nv = ops.color_from_features(self.x3_blob() if x3 else self.mfma_blob(), geometry_feat.reshape(R * S, -1), rgb_feat.reshape(V, R * S, -1),
-                                          ray_diff.reshape(V, R * S, 4), mask.reshape(V, R * S).float(), x3=x3)
+        blob, mode = self.color_network()
+        rgb, nv = ops.color_from_features(blob, geometry_feat.reshape(R * S, -1), rgb_feat.reshape(V, R * S, -1),
+                                          ray_diff.reshape(V, R * S, 4), mask.reshape(V, R * S).float(), x3=mode == "x3")
         valid = ((nv.view(R, S) >= 2).float().sum(1) > 8)
         return rgb.view(R, S, 3), valid

@@ -505,24 +505,16 @@ class SparseNeuSRenderer(nn.Module):
             e = torch.nn.functional.interpolate((1 - occupancy_mask)[None, None].float(), [resolution] * 3, mode="nearest")[0, 0] > 0
             u = torch.where(e.to(u.device), torch.full_like(u, -100.0), u)
         v, t = ops.marching_cubes(u.contiguous(), float(threshold))
-        # O2345_MESH_MIN_COMPONENT_FACES / O2345_MESH_KEEP_LARGEST (config.py; both off by default: nothing is launched): small components are dropped on
-        # the device, so the unchanged runner's validate_colored_mesh colours and writes the filtered mesh; u is returned as it is
-        if config.MESH_MIN_COMPONENT_FACES or config.MESH_KEEP_LARGEST:
-            v, t, _, _ = ops.mesh_filter_components(v, t, config.MESH_MIN_COMPONENT_FACES, config.MESH_KEEP_LARGEST)
-        # O2345_MESH_DECIMATE_CELL (off by default: nothing is launched): vertex clustering of the index coordinates on the device, cell in grid spacings;
-        # the unchanged runner then colours and writes the decimated mesh
-        if config.MESH_DECIMATE_CELL:
-            v, t, _, _ = ops.mesh_decimate(v, t, config.MESH_DECIMATE_CELL)
-        # O2345_MESH_PROJECT_ITERATIONS (off by default: nothing is launched): Newton projection of the index coordinates onto sdf = -threshold (u = -sdf)
-        # inside the call's own bounds, on the device; the unchanged runner then colours the projected vertices.  Not with an occupancy mask: the
-        # vertices on the mask's walls (u = -100 next to the surface) are not on the level set, and projecting would pull them off the wall
-        if config.MESH_PROJECT_ITERATIONS and occupancy_mask is None:
-            v, _ = ops.mesh_project(self.sdf_network.sdf_layer.blob(), channel_last(kwargs["conditional_volume"]), v, int(resolution),
-                                    config.MESH_PROJECT_ITERATIONS, level=-float(threshold), bound_min=bound_min, bound_max=bound_max)
-        # O2345_MESH_SMOOTH_ITERATIONS (off by default: nothing is launched): Taubin smoothing of the index coordinates on the device; the unchanged runner
-        # colours whatever vertices it is handed, so here the colours are taken at the SMOOTHED positions (pipeline._mesh_fields colours first)
-        if config.MESH_SMOOTH_ITERATIONS:
-            v = ops.mesh_smooth(v, t, config.MESH_SMOOTH_ITERATIONS)
+        # the configured clean-up (config.py, O2345_MESH_*; all off by default: nothing is launched) on the device: the unchanged runner's
+        # validate_colored_mesh colours and writes the mesh it is handed; u is returned as it is.  The projection goes onto sdf = -threshold (u = -sdf)
+        # inside the call's own bounds.  Not with an occupancy mask: the vertices on the mask's walls (u = -100 next to the surface) are not on the
+        # level set, and projecting would pull them off the wall
+        opts = config.mesh_options()
+        v, t, _ = ops.mesh_cleanup(v, t, opts, self.sdf_network.sdf_layer.blob(), channel_last(kwargs["conditional_volume"]), int(resolution),
+                                   level=-float(threshold), bound_min=bound_min, bound_max=bound_max, project=occupancy_mask is None)
+        # Taubin smoothing last: the runner colours after this call, so here at the SMOOTHED positions (pipeline._mesh_fields colours first)
+        if opts.smooth_iterations:
+            v = ops.mesh_smooth(v, t, opts.smooth_iterations)
         # the reference returns numpy (vertices float64 in world units, triangles, u): index -> world on the device (fp64, the expression numpy would
         # evaluate), then three copies into pinned memory and one synchronisation
         if v.shape[0]:

@@ -12,6 +12,8 @@ import numpy as np
 import pytest
 import torch
 
+from guard_util import PATTERN, POST, PRE, Guard
+
 pytestmark = pytest.mark.gpu
 
 pkg = importlib.import_module("one-2-3-45_amd")
@@ -19,9 +21,6 @@ ops = importlib.import_module("one-2-3-45_amd.ops")
 pipeline = importlib.import_module("one-2-3-45_amd.pipeline")
 costreg = importlib.import_module("one-2-3-45_amd.costreg")
 featurenet = importlib.import_module("one-2-3-45_amd.featurenet")
-
-PRE, POST, PATTERN = 512, 4096, 0xA5             # PRE keeps the buffer at the alignment torch's allocator gives (512 B); the kernels assume 16 B
-
 
 class GuardedTorch:
     """Stands in for the `torch` module inside the product modules: the allocation functions return guarded device buffers, everything else is torch's."""
@@ -172,3 +171,19 @@ def test_the_guard_itself_catches_a_one_byte_overrun(guard):
     base[PRE + 7] = PATTERN
     base[PRE - 1] = 0
     assert guard.check()[0][2] == "underrun"
+
+
+def test_the_buffer_guard_catches_a_one_byte_overrun():
+    """tests/guard_util.py::Guard, the hand-carved form of the mesh and surface tests: a one-byte overrun is reported, in both call forms."""
+    g = Guard(torch.device("cuda:0"))
+    t = g.buf(7, "probe")
+    raw = g.live[-1][0]
+    assert t.data_ptr() == raw.data_ptr() + PRE and not g.damaged()
+    raw[PRE + 7] = 0
+    assert g.damaged() == [("probe", 7)]
+    raw[PRE + 7] = PATTERN
+    src = np.arange(5, dtype=np.float32)
+    for t in (g.buf(src, what="copy"), g.buf(src=src, what="copy")):
+        assert t.numel() == 20 and t.cpu().numpy().tobytes() == src.tobytes() and not g.damaged()
+    g.live[-1][0][PRE - 1] = 0
+    assert g.damaged() == [("copy", 20)]

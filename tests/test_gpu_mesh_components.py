@@ -9,6 +9,8 @@ import pytest
 import torch
 
 import mesh_components_util as mcu
+from guard_util import Guard
+from mesh_scene_util import args as _args, dev, dev_tris as _dev_tris, golden_mirror, stored_scene  # noqa: F401 (dev: a fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -23,13 +25,6 @@ NTS = (0, 1, 255, 256, 257, 2047, 2048, 2049, 4097)          # every block (256)
 
 
 @pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    _lib.lib()
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module")
 def field_mesh(dev):
     """(a): HIP marching cubes of the three-spheres-and-specks field -> device tensors, host copies and the host twin's labels."""
     u = torch.from_numpy(np.array(mcu.spheres_field(40))).to(dev)
@@ -39,10 +34,6 @@ def field_mesh(dev):
     sizes = np.sort(np.bincount(lab[hf[:, 0]], minlength=hv.shape[0])[np.unique(lab)])[::-1]
     assert len(sizes) >= 10 and sizes[0] > sizes[1] > 100 and sizes[-1] == 8, sizes          # not vacuous: three big surfaces, a dozen octahedra
     return dict(verts=verts, tris=tris, hv=hv, hf=hf, lab=lab, sizes=sizes)
-
-
-def _dev_tris(f, dev, dtype):
-    return torch.from_numpy(np.array(f)).to(dev).to(dtype).contiguous()          # a copy: the shared meshes are read-only
 
 
 def _check_labels(f, nv, dev, dtype, want=None):
@@ -144,24 +135,7 @@ def test_out_of_range_triangle_is_an_error(dev):
         ops.mesh_component_labels(tris, 4)
 
 
-# ---- guard bands (the idea of tests/test_gpu_guard.py, local to this file): every output and the workspace at their EXACT sizes ---------------
-PRE, POST, PATTERN = 512, 4096, 0xA5
-
-
-class _Guard:
-    def __init__(self, dev):
-        self.dev, self.live = dev, []
-
-    def buf(self, nbytes, what):
-        raw = torch.full((PRE + nbytes + POST,), PATTERN, dtype=torch.uint8, device=self.dev)
-        self.live.append((raw, nbytes, what))
-        return raw[PRE:PRE + nbytes]
-
-    def damaged(self):
-        torch.cuda.synchronize()
-        return [(what, n) for raw, n, what in self.live if not (bool((raw[:PRE] == PATTERN).all()) and bool((raw[PRE + n:] == PATTERN).all()))]
-
-
+# ---- guard bands (tests/guard_util.py): every output and the workspace at their EXACT sizes ---------------------------------------------------------
 def _guarded_run(g, dev, hv, hf, dtype, min_faces, keep_largest):
     """The two-call protocol through the C ABI itself, every buffer carved at its exact size -> (labels, verts, tris, kept) as numpy"""
     L = _lib.lib()
@@ -184,7 +158,7 @@ def _guarded_run(g, dev, hv, hf, dtype, min_faces, keep_largest):
 
 @pytest.mark.parametrize("dtype", [torch.int32, torch.int64])
 def test_no_component_kernel_writes_outside_its_buffers(dev, field_mesh, dtype):
-    g = _Guard(dev)
+    g = Guard(dev)
     cases = [(field_mesh["hv"], field_mesh["hf"], kw) for kw in ((0, False), (9, False), (1, True), (10 ** 9, True))]
     rng = np.random.default_rng(3)
     for nt in NTS:
@@ -201,36 +175,13 @@ def test_no_component_kernel_writes_outside_its_buffers(dev, field_mesh, dtype):
     assert len(g.live) == 5 * len(cases)
 
 
-def test_the_local_guard_catches_a_one_byte_overrun(dev):
-    g = _Guard(dev)
-    t = g.buf(7, "probe")
-    raw = g.live[-1][0]
-    assert t.data_ptr() == raw.data_ptr() + PRE and not g.damaged()
-    raw[PRE + 7] = 0
-    assert g.damaged() == [("probe", 7)]
-
-
 # ---- the pipeline on the stored small scene (D = 20, R = 64) ------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def scene(dev):
-    from scene_util import small_scene, stored_small_scene_dense
-    s = small_scene()
-    sc = s["sc"]
-    t = lambda a: torch.as_tensor(np.asarray(a)).to(dev)
-    wt = pipeline.SceneWeights(dev, seed=0)
-    vol = dict(vol_cl=stored_small_scene_dense()[0].permute(1, 2, 3, 0).contiguous().to(dev), maskvol=s["mask"][0, 0].contiguous().to(dev).view(-1),
-               cmaps=ops.pack_color_maps(t(s["fmaps"]).contiguous(), t(sc["images"]).contiguous()))
-    proj, cam_pos = pipeline.camera_terms(t(sc["intrinsics"]).float(), t(sc["w2cs"]).float())
-    R = 64
-    plain = pipeline.extract_mesh(wt, vol, proj, cam_pos, R, return_index_verts=True)
-    hv, hf = plain[0].cpu().numpy(), plain[1].cpu().numpy()
-    lab = mio.component_labels(hf, hv.shape[0])
+    S = stored_scene(dev)
+    lab = mio.component_labels(S["hf"], S["hv"].shape[0])
     assert len(np.unique(lab)) >= 2, "the scene's mesh must have floaters for these tests to mean anything"
-    return dict(wt=wt, vol=vol, proj=proj, cam_pos=cam_pos, R=R, plain=plain, hv=hv, hf=hf)
-
-
-def _args(S):
-    return S["wt"], S["vol"], S["proj"], S["cam_pos"], S["R"]
+    return S
 
 
 def test_extract_mesh_with_the_filter(scene):
@@ -315,16 +266,7 @@ def test_reconstruct_folder_reports_the_components(tmp_path):
 
 # ---- the drop-in mirror ---------------------------------------------------------------------------------------------------------------------------
 def test_mirror_extract_geometry_applies_the_configured_filter(dev, monkeypatch):
-    from golden_util import load
-    recon = importlib.import_module("one-2-3-45_amd.recon")
-    G = load()
-    D = G["cfg"]["D"]
-    sdf = recon.SparseSdfNetwork(lod=0, ch_in=56, voxel_size=2.0 / (D - 1), vol_dims=[D, D, D], hidden_dim=128, cost_type="variance_mean",
-                                 d_pyramid_feature_compress=16, regnet_d_out=16, num_sdf_layers=4, multires=6).to(dev)
-    sdf.load_state_dict(G["sdf_sd"], strict=False)
-    ren = recon.SparseNeuSRenderer(None, sdf, recon.SingleVarianceNetwork(0.2).to(dev), recon.GeneralRenderingNetwork(16, 56, True).to(dev), 64, 64, 0, 1.0,
-                                   alpha_type="div", conf=None)
-    dense = torch.from_numpy(np.ascontiguousarray(G["g"]["dense"])).to(dev)[None]
+    ren, sdf, dense = golden_mirror(dev)
     call = lambda: ren.extract_geometry(sdf, torch.tensor([-1.0] * 3), torch.tensor([1.0] * 3), resolution=48, threshold=0, device=dev,
                                         conditional_volume=dense, lod=0)
     v0, t0, u0 = call()

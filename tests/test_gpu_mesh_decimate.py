@@ -10,6 +10,8 @@ import torch
 
 import mesh_components_util as mcu
 import mesh_smooth_util as msu
+from guard_util import PRE, Guard
+from mesh_scene_util import args as _args, bits as _bits, dev, dev_tris as _dev_tris, fields_at as _fields_at, golden_mirror, mc, stored_scene  # noqa: F401 (dev: a fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -24,16 +26,9 @@ NVS = (0, 1, 255, 256, 257, 2047, 2048, 2049, 4097)          # every block (256)
 INFO_KEYS = {"clusters", "vertices", "triangles", "degenerate", "duplicate"}
 
 
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    _lib.lib()
-    return torch.device("cuda:0")
-
-
 def _mc(dev, field, shift=0.0):
-    verts, tris = ops.marching_cubes(torch.from_numpy(np.array(field)).to(dev), 0.0)
-    hv, hf = verts.cpu().numpy() + shift, tris.cpu().numpy()
+    m = mc(dev, field)
+    hv, hf = m["hv"] + shift, m["hf"]
     hv.setflags(write=False)
     hf.setflags(write=False)
     return dict(hv=hv, hf=hf)
@@ -52,10 +47,6 @@ def closed_mesh(dev):
 @pytest.fixture(scope="module")
 def cut_mesh(dev):
     return _mc(dev, msu.cut_sphere_field(24))
-
-
-def _dev_tris(f, dev, dtype):
-    return torch.from_numpy(np.array(f)).to(dev).to(dtype).contiguous().view(-1, 3)          # a copy: the shared meshes are read-only
 
 
 def _check(hv, hf, dev, dtype, cell, want=None):
@@ -237,24 +228,7 @@ def test_errors_are_statuses_not_faults(dev):
     _check(good.cpu().numpy(), tris.cpu().numpy(), dev, torch.int64, 1.0)
 
 
-# ---- guard bands (the idea of tests/test_gpu_mesh_components.py::_Guard, local to this file): every output and the workspace at their EXACT sizes ----
-PRE, POST, PATTERN = 512, 4096, 0xA5
-
-
-class _Guard:
-    def __init__(self, dev):
-        self.dev, self.live = dev, []
-
-    def buf(self, nbytes, what):
-        raw = torch.full((PRE + nbytes + POST,), PATTERN, dtype=torch.uint8, device=self.dev)
-        self.live.append((raw, nbytes, what))
-        return raw[PRE:PRE + nbytes]
-
-    def damaged(self):
-        torch.cuda.synchronize()
-        return [(what, n) for raw, n, what in self.live if not (bool((raw[:PRE] == PATTERN).all()) and bool((raw[PRE + n:] == PATTERN).all()))]
-
-
+# ---- guard bands (tests/guard_util.py): every output and the workspace at their EXACT sizes ---------------------------------------------------------
 def _guarded_run(g, dev, hv, hf, dtype, cell):
     """The two-call protocol through the C ABI itself, every buffer carved at its exact size -> (verts, tris, cluster, info) as numpy"""
     L = _lib.lib()
@@ -281,7 +255,7 @@ def _guarded_run(g, dev, hv, hf, dtype, cell):
 
 @pytest.mark.parametrize("dtype", [torch.int32, torch.int64])
 def test_no_kernel_writes_outside_its_buffers(dev, closed_mesh, cut_mesh, dtype):
-    g = _Guard(dev)
+    g = Guard(dev)
     cases = [(closed_mesh["hv"], closed_mesh["hf"], c) for c in (0.5, 2.0, 3.0, 100.0)] + [(cut_mesh["hv"] - 11.3, cut_mesh["hf"], 2.0)]
     rng = np.random.default_rng(13)
     for nv in NVS:
@@ -299,52 +273,14 @@ def test_no_kernel_writes_outside_its_buffers(dev, closed_mesh, cut_mesh, dtype)
     assert len(g.live) == 4 * len(cases)
 
 
-def test_the_local_guard_catches_a_one_byte_overrun(dev):
-    g = _Guard(dev)
-    t = g.buf(7, "probe")
-    raw = g.live[-1][0]
-    assert t.data_ptr() == raw.data_ptr() + PRE and not g.damaged()
-    raw[PRE + 7] = 0
-    assert g.damaged() == [("probe", 7)]
-
-
 # ---- the pipeline on the stored small scene (D = 20, R = 64) ------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def scene(dev):
-    from scene_util import small_scene, stored_small_scene_dense
-    s = small_scene()
-    sc = s["sc"]
-    t = lambda a: torch.as_tensor(np.asarray(a)).to(dev)
-    wt = pipeline.SceneWeights(dev, seed=0)
-    vol = dict(vol_cl=stored_small_scene_dense()[0].permute(1, 2, 3, 0).contiguous().to(dev), maskvol=s["mask"][0, 0].contiguous().to(dev).view(-1),
-               cmaps=ops.pack_color_maps(t(s["fmaps"]).contiguous(), t(sc["images"]).contiguous()))
-    proj, cam_pos = pipeline.camera_terms(t(sc["intrinsics"]).float(), t(sc["w2cs"]).float())
-    R = 64
-    plain = pipeline.extract_mesh(wt, vol, proj, cam_pos, R, return_index_verts=True)
-    hv, hf = plain[0].cpu().numpy(), plain[1].cpu().numpy()
-    assert hf.shape[0] > 100
-    twin = mio.decimate_mesh(hv, hf, 2.0)
-    assert 0 < twin[4]["vertices"] < hv.shape[0] // 2
-    return dict(wt=wt, vol=vol, proj=proj, cam_pos=cam_pos, R=R, plain=plain, hv=hv, hf=hf, twin=twin)
-
-
-def _args(S):
-    return S["wt"], S["vol"], S["proj"], S["cam_pos"], S["R"]
-
-
-def _bits(a, b):
-    return a.dtype == b.dtype and a.shape == b.shape and torch.equal(a.contiguous().view(torch.uint8), b.contiguous().view(torch.uint8))
-
-
-def _fields_at(S, verts_idx):
-    """gradient and colours of the pipeline's two networks at given index coordinates -> (rgb, grad)"""
-    wt, vol = S["wt"], S["vol"]
-    pts = (verts_idx / (S["R"] - 1.0) * 2.0 - 1.0).to(torch.float32).contiguous()
-    g = ops.sdf_mlp(wt.sdf_blob, vol["vol_cl"], pts, variant=2, precision=wt.sdf_precision)["grad"]
-    x3 = wt.color_precision == "f16x3"
-    rgb, _ = ops.color_points(wt.color_xblob if x3 else wt.color_mblob, vol["vol_cl"], vol["maskvol"], vol["cmaps"], S["proj"], S["cam_pos"], pts, normals=g,
-                              want_nviews=False, mfma="x3" if x3 else True)
-    return rgb, g
+    S = stored_scene(dev)
+    assert S["hf"].shape[0] > 100
+    twin = mio.decimate_mesh(S["hv"], S["hf"], 2.0)
+    assert 0 < twin[4]["vertices"] < S["hv"].shape[0] // 2
+    return dict(S, twin=twin)
 
 
 def test_extract_mesh_with_decimation(scene):
@@ -354,8 +290,8 @@ def test_extract_mesh_with_decimation(scene):
     v, t, rgb, u = pipeline.extract_mesh(*_args(S), return_index_verts=True, decimate_cell=2)
     assert v.cpu().numpy().tobytes() == wv.tobytes() and np.array_equal(t.cpu().numpy(), wf) and t.dtype == S["plain"][1].dtype and _bits(u, S["plain"][3])
     # gradient and colours are taken at the NEW vertices
-    info = {}
-    fields = pipeline._mesh_fields(*_args(S), info=info, decimate_cell=2.0)
+    fields = pipeline._mesh_fields(*_args(S), config.mesh_options(decimate_cell=2.0))
+    info = fields.info
     want_rgb, want_g = _fields_at(S, torch.from_numpy(wv).to(dev))
     assert _bits(rgb, want_rgb) and _bits(fields[3], want_rgb) and _bits(fields[5], want_g)
     assert info["decimate"] == winfo and info["components"] is None
@@ -402,8 +338,7 @@ def test_decimation_off_is_todays_output(scene, tmp_path, monkeypatch):
         off = pipeline.extract_mesh(*_args(S), return_index_verts=True, **kw)
         for a, b in zip(S["plain"], off):
             assert _bits(a, b)
-        info = {}
-        pipeline._mesh_fields(*_args(S), info=info, **kw)
+        info = pipeline._mesh_fields(*_args(S), config.mesh_options(**kw)).info
         assert info["decimate"] is None
         for ext in (".ply", ".glb", ".obj"):
             p0, p1 = str(tmp_path / ("a" + ext)), str(tmp_path / ("b" + ext))
@@ -447,16 +382,7 @@ def test_reconstruct_folder_reports_the_cell_and_the_counts(tmp_path, dev):
 
 # ---- the drop-in mirror ---------------------------------------------------------------------------------------------------------------------------
 def test_mirror_extract_geometry_applies_the_configured_decimation(dev, monkeypatch):
-    from golden_util import load
-    recon = importlib.import_module("one-2-3-45_amd.recon")
-    G = load()
-    D = G["cfg"]["D"]
-    sdf = recon.SparseSdfNetwork(lod=0, ch_in=56, voxel_size=2.0 / (D - 1), vol_dims=[D, D, D], hidden_dim=128, cost_type="variance_mean",
-                                 d_pyramid_feature_compress=16, regnet_d_out=16, num_sdf_layers=4, multires=6).to(dev)
-    sdf.load_state_dict(G["sdf_sd"], strict=False)
-    ren = recon.SparseNeuSRenderer(None, sdf, recon.SingleVarianceNetwork(0.2).to(dev), recon.GeneralRenderingNetwork(16, 56, True).to(dev), 64, 64, 0, 1.0,
-                                   alpha_type="div", conf=None)
-    dense = torch.from_numpy(np.ascontiguousarray(G["g"]["dense"])).to(dev)[None]
+    ren, sdf, dense = golden_mirror(dev)
     R = 48
     call = lambda: ren.extract_geometry(sdf, torch.tensor([-1.0] * 3), torch.tensor([1.0] * 3), resolution=R, threshold=0, device=dev,
                                         conditional_volume=dense, lod=0)

@@ -10,6 +10,8 @@ import numpy as np
 import pytest
 import torch
 
+from test_gpu_guard import GuardedTorch
+
 pytestmark = pytest.mark.gpu
 
 ops = importlib.import_module("one-2-3-45_amd.ops")
@@ -197,38 +199,11 @@ def test_extract_mesh_is_unchanged_by_an_asset_export(tmp_path):
         assert a.dtype == b.dtype and a.shape == b.shape and torch.equal(a.view(torch.uint8), b.view(torch.uint8))
 
 
-# ---- guard bands (the idea of tests/test_gpu_guard.py, local to this file) ------------------------------------------------------------------
-PRE, POST, PATTERN = 512, 4096, 0xA5
-
-
-class _GuardedTorch:
-    """Stands in for ``torch`` inside ops: ``empty`` on the device returns a buffer with canary bytes immediately before and after it."""
-
-    def __init__(self):
-        self.live = []
-
-    def __getattr__(self, name):
-        return getattr(torch, name)
-
-    def empty(self, *shape, dtype=None, device=None, **kw):
-        if device is None or torch.device(device).type != "cuda" or kw.get("pin_memory"):
-            return torch.empty(*shape, dtype=dtype, device=device, **kw)
-        dtype = dtype or torch.float32
-        shape = tuple(int(x) for x in (shape[0] if len(shape) == 1 and isinstance(shape[0], (tuple, list, torch.Size)) else shape))
-        nbytes = int(np.prod(shape, dtype=np.int64)) * torch.empty((), dtype=dtype).element_size()
-        raw = torch.full((PRE + nbytes + POST,), PATTERN, dtype=torch.uint8, device=device)
-        self.live.append((raw, nbytes, shape))
-        return raw[PRE:PRE + nbytes].view(dtype).view(shape)
-
-    def damaged(self):
-        torch.cuda.synchronize()
-        return [(shape, nbytes) for raw, nbytes, shape in self.live if not (bool((raw[:PRE] == PATTERN).all()) and bool((raw[PRE + nbytes:] == PATTERN).all()))]
-
-
+# ---- guard bands (tests/test_gpu_guard.py::GuardedTorch stands in for ``torch`` inside ops) --------------------------------------------------------------
 @pytest.mark.parametrize("index_dtype", [torch.int64, torch.int32])
 def test_no_export_kernel_writes_outside_its_buffers(monkeypatch, index_dtype):
     dev = torch.device("cuda:0")
-    g = _GuardedTorch()
+    g = GuardedTorch()
     monkeypatch.setattr(ops, "torch", g)
     monkeypatch.setattr(ops, "_ws_cache", {})
     rng = np.random.default_rng(5)
@@ -245,7 +220,7 @@ def test_no_export_kernel_writes_outside_its_buffers(monkeypatch, index_dtype):
             pos, rgba, nrm, idx, bounds = ops.mesh_asset_pack(verts, tris, R, scale_mat=scale, rgb=rgb if use_rgb else None, grad=grad if use_grad else None)
             text = ops.obj_text(pos, idx, rgba, nrm, bounds=bounds)
             assert len(g.live) >= live0 + 4 + use_rgb + use_grad               # positions, indices, bounds, text [, rgba] [, normals] (+ the workspace when it grows)
-            bad = g.damaged()
+            bad = g.check()
             assert not bad, (n, m, s, use_rgb, use_grad, bad)
             # and what they wrote inside is the host definition
             h = lambda t: None if t is None else t.cpu().numpy()
@@ -255,12 +230,3 @@ def test_no_export_kernel_writes_outside_its_buffers(monkeypatch, index_dtype):
             dn = len(str(n))
             lens |= {1 + 3 * (K + 11) + (33 if use_rgb else 0) + 1, 1 + 3 * (1 + (2 * dn + 2 if use_grad else dn)) + 1} | ({39} if use_grad else set())
     assert sum(1 for l in lens if l % 16) >= 8, lens                            # record lengths that are not multiples of 16
-
-
-def test_the_local_guard_catches_a_one_byte_overrun():
-    g = _GuardedTorch()
-    t = g.empty(7, dtype=torch.uint8, device=torch.device("cuda:0"))
-    raw = g.live[-1][0]
-    assert t.data_ptr() == raw.data_ptr() + PRE and not g.damaged()
-    raw[PRE + 7] = 0
-    assert g.damaged()

@@ -9,6 +9,9 @@ import numpy as np
 import pytest
 import torch
 
+from guard_util import PRE, Guard
+from mesh_scene_util import args as _args, bits as _bits, dev, fields_at as _fields_at, golden_mirror, sdf_field as _field, stored_scene  # noqa: F401 (dev: a fixture)
+
 pytestmark = pytest.mark.gpu
 
 pkg = importlib.import_module("one-2-3-45_amd")
@@ -25,39 +28,15 @@ TOL = 5e-5
 
 
 @pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    _lib.lib()
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module")
 def scene(dev):
     """the stored small scene (D = 20), its marching-cubes mesh at R = 64 and the twin's cell-2 decimation of it"""
-    from scene_util import small_scene, stored_small_scene_dense
-    s = small_scene()
-    sc = s["sc"]
-    t = lambda a: torch.as_tensor(np.asarray(a)).to(dev)
-    wt = pipeline.SceneWeights(dev, seed=0)
-    vol = dict(vol_cl=stored_small_scene_dense()[0].permute(1, 2, 3, 0).contiguous().to(dev), maskvol=s["mask"][0, 0].contiguous().to(dev).view(-1),
-               cmaps=ops.pack_color_maps(t(s["fmaps"]).contiguous(), t(sc["images"]).contiguous()))
-    proj, cam_pos = pipeline.camera_terms(t(sc["intrinsics"]).float(), t(sc["w2cs"]).float())
-    R = 64
-    plain = pipeline.extract_mesh(wt, vol, proj, cam_pos, R, return_index_verts=True)
-    hv, hf = plain[0].cpu().numpy(), plain[1].cpu().numpy()
+    S = stored_scene(dev)
+    hv, hf = S["hv"], S["hf"]
     assert hv.shape[0] > 2049 and hf.shape[0] > 100
     dec = mio.decimate_mesh(hv, hf, 2.0)
     assert 100 < dec[4]["vertices"] < hv.shape[0] // 2
     hv.setflags(write=False)
-    return dict(wt=wt, vol=vol, proj=proj, cam_pos=cam_pos, R=R, plain=plain, hv=hv, hf=hf, dec=dec, twins={})
-
-
-def _field(blob, vol_cl, prec):
-    """the twin's field: the device's own SDF + gradient kernel at the given float32 world points"""
-    def field(pts32):
-        o = ops.sdf_mlp(blob, vol_cl, torch.from_numpy(pts32).to(vol_cl.device), variant=2, precision=prec)
-        return o["sdf"].cpu().numpy(), o["grad"].cpu().numpy()
-    return field
+    return dict(S, dec=dec, twins={})
 
 
 def _twin(S, hv, prec, iterations, key=None, **kw):
@@ -201,29 +180,12 @@ def test_errors_are_statuses_not_faults(scene, dev):
     assert out.cpu().numpy().tobytes() == want[0].tobytes() and ops.project_info(stats.cpu().numpy(), 2) == want[1]
 
 
-# ---- guard bands (the idea of tests/test_gpu_mesh_decimate.py::_Guard, local to this file): the output, the stats block and the workspace at their EXACT sizes
-PRE, POST, PATTERN = 512, 4096, 0xA5
-
-
-class _Guard:
-    def __init__(self, dev):
-        self.dev, self.live = dev, []
-
-    def buf(self, nbytes, what):
-        raw = torch.full((PRE + nbytes + POST,), PATTERN, dtype=torch.uint8, device=self.dev)
-        self.live.append((raw, nbytes, what))
-        return raw[PRE:PRE + nbytes]
-
-    def damaged(self):
-        torch.cuda.synchronize()
-        return [(what, n) for raw, n, what in self.live if not (bool((raw[:PRE] == PATTERN).all()) and bool((raw[PRE + n:] == PATTERN).all()))]
-
-
+# ---- guard bands (tests/guard_util.py): the output, the stats block and the workspace at their EXACT sizes --------------------------------------------
 @pytest.mark.parametrize("prec", PRECISIONS)
 def test_no_kernel_writes_outside_its_buffers(scene, dev, prec):
     S = scene
     L = _lib.lib()
-    g = _Guard(dev)
+    g = Guard(dev)
     blob, vol_cl, R = S["wt"].sdf_blob, S["vol"]["vol_cl"], S["R"]
     b0, b1 = np.full(3, -1.0, np.float32), np.full(3, 1.0, np.float32)
     P = lambda t: ctypes.c_void_p(t.data_ptr())
@@ -246,35 +208,7 @@ def test_no_kernel_writes_outside_its_buffers(scene, dev, prec):
     assert len(g.live) == 3 * len(NVS)
 
 
-def test_the_local_guard_catches_a_one_byte_overrun(dev):
-    g = _Guard(dev)
-    t = g.buf(7, "probe")
-    raw = g.live[-1][0]
-    assert t.data_ptr() == raw.data_ptr() + PRE and not g.damaged()
-    raw[PRE + 7] = 0
-    assert g.damaged() == [("probe", 7)]
-
-
 # ---- the pipeline on the stored small scene (D = 20, R = 64) ------------------------------------------------------------------------------------
-def _args(S):
-    return S["wt"], S["vol"], S["proj"], S["cam_pos"], S["R"]
-
-
-def _bits(a, b):
-    return a.dtype == b.dtype and a.shape == b.shape and torch.equal(a.contiguous().view(torch.uint8), b.contiguous().view(torch.uint8))
-
-
-def _fields_at(S, verts_idx):
-    """gradient and colours of the pipeline's two networks at given index coordinates -> (rgb, grad)"""
-    wt, vol = S["wt"], S["vol"]
-    pts = (verts_idx / (S["R"] - 1.0) * 2.0 - 1.0).to(torch.float32).contiguous()
-    g = ops.sdf_mlp(wt.sdf_blob, vol["vol_cl"], pts, variant=2, precision=wt.sdf_precision)["grad"]
-    x3 = wt.color_precision == "f16x3"
-    rgb, _ = ops.color_points(wt.color_xblob if x3 else wt.color_mblob, vol["vol_cl"], vol["maskvol"], vol["cmaps"], S["proj"], S["cam_pos"], pts, normals=g,
-                              want_nviews=False, mfma="x3" if x3 else True)
-    return rgb, g
-
-
 def _pipeline_twins(S):
     """(vertices, faces, info) the pipeline must produce with project_iterations = 4: without decimation, and after the twin's cell-2 decimation, where
     the move limit is max(1, cell) = 2"""
@@ -292,8 +226,8 @@ def test_extract_mesh_with_projection(scene, dev):
         assert v.cpu().numpy().tobytes() == wv.tobytes() and _bits(t, unprojected[1]) and np.array_equal(t.cpu().numpy(), wf) and _bits(u, S["plain"][3])
         assert v.cpu().numpy().tobytes() != unprojected[0].cpu().numpy().tobytes()
         # gradient and colours are taken at the PROJECTED vertices
-        info = {}
-        fields = pipeline._mesh_fields(*_args(S), info=info, project_iterations=4, **kw)
+        fields = pipeline._mesh_fields(*_args(S), config.mesh_options(project_iterations=4, **kw))
+        info = fields.info
         want_rgb, want_g = _fields_at(S, torch.from_numpy(np.array(wv)).to(dev))
         assert _bits(rgb, want_rgb) and _bits(fields[3], want_rgb) and _bits(fields[5], want_g)
         assert info["project"] == winfo and (info["decimate"] is None) == (not kw)
@@ -330,8 +264,7 @@ def test_projection_off_is_todays_output(scene, tmp_path, monkeypatch):
         off = pipeline.extract_mesh(*_args(S), return_index_verts=True, **kw)
         for a, b in zip(S["plain"], off):
             assert _bits(a, b)
-        info = {}
-        pipeline._mesh_fields(*_args(S), info=info, **kw)
+        info = pipeline._mesh_fields(*_args(S), config.mesh_options(**kw)).info
         assert info["project"] is None
         for ext in (".ply", ".glb", ".obj"):
             p0, p1 = str(tmp_path / ("a" + ext)), str(tmp_path / ("b" + ext))
@@ -374,16 +307,8 @@ def test_reconstruct_folder_reports_the_iterations_and_the_info(tmp_path, dev):
 
 # ---- the drop-in mirror ---------------------------------------------------------------------------------------------------------------------------
 def test_mirror_extract_geometry_applies_the_configured_projection(dev, monkeypatch):
-    from golden_util import load
-    recon = importlib.import_module("one-2-3-45_amd.recon")
-    G = load()
-    D = G["cfg"]["D"]
-    sdf = recon.SparseSdfNetwork(lod=0, ch_in=56, voxel_size=2.0 / (D - 1), vol_dims=[D, D, D], hidden_dim=128, cost_type="variance_mean",
-                                 d_pyramid_feature_compress=16, regnet_d_out=16, num_sdf_layers=4, multires=6).to(dev)
-    sdf.load_state_dict(G["sdf_sd"], strict=False)
-    ren = recon.SparseNeuSRenderer(None, sdf, recon.SingleVarianceNetwork(0.2).to(dev), recon.GeneralRenderingNetwork(16, 56, True).to(dev), 64, 64, 0, 1.0,
-                                   alpha_type="div", conf=None)
-    dense = torch.from_numpy(np.ascontiguousarray(G["g"]["dense"])).to(dev)[None]
+    ren, sdf, dense = golden_mirror(dev)
+    D = dense.shape[2]
     R = 48
     call = lambda threshold=0, **kw: ren.extract_geometry(sdf, torch.tensor([-1.0] * 3), torch.tensor([1.0] * 3), resolution=R, threshold=threshold, device=dev,
                                                           conditional_volume=dense, lod=0, **kw)

@@ -10,6 +10,8 @@ import torch
 
 import mesh_components_util as mcu
 import mesh_smooth_util as msu
+from guard_util import Guard
+from mesh_scene_util import args as _args, bits as _bits, dev, dev_tris as _dev_tris, golden_mirror, mc, stored_scene  # noqa: F401 (dev: a fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -23,17 +25,9 @@ _lib = importlib.import_module("one-2-3-45_amd._lib")
 NTS = (0, 1, 255, 256, 257, 2047, 2048, 2049, 4097)          # every block (256) and scan-tile (2048) boundary; from 17 triangles on a fan's centre is a long row
 
 
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    _lib.lib()
-    return torch.device("cuda:0")
-
-
 def _mc(dev, field):
-    verts, tris = ops.marching_cubes(torch.from_numpy(np.array(field)).to(dev), 0.0)
-    hv, hf = verts.cpu().numpy(), tris.cpu().numpy()
-    return dict(verts=verts, tris=tris, hv=hv, hf=hf, adj=mio.vertex_adjacency(hf, hv.shape[0]))
+    m = mc(dev, field)
+    return dict(m, adj=mio.vertex_adjacency(m["hf"], m["hv"].shape[0]))
 
 
 @pytest.fixture(scope="module")
@@ -52,10 +46,6 @@ def cut_mesh(dev):
     bnd = m["adj"][2].astype(bool)
     assert 0 < bnd.sum() < bnd.size and (m["hv"][bnd, 0] == 23.0).all(), (bnd.sum(), bnd.size)
     return m
-
-
-def _dev_tris(f, dev, dtype):
-    return torch.from_numpy(np.array(f)).to(dev).to(dtype).contiguous()          # a copy: the shared meshes are read-only
 
 
 def _check_adjacency(f, nv, dev, dtype, want=None):
@@ -172,24 +162,7 @@ def test_bad_arguments(dev, closed_mesh):
         ops.mesh_vertex_adjacency(m["tris"].float(), 4)
 
 
-# ---- guard bands (the idea of tests/test_gpu_mesh_components.py::_Guard, local to this file): every output and the workspace at their EXACT sizes ----
-PRE, POST, PATTERN = 512, 4096, 0xA5
-
-
-class _Guard:
-    def __init__(self, dev):
-        self.dev, self.live = dev, []
-
-    def buf(self, nbytes, what):
-        raw = torch.full((PRE + nbytes + POST,), PATTERN, dtype=torch.uint8, device=self.dev)
-        self.live.append((raw, nbytes, what))
-        return raw[PRE:PRE + nbytes]
-
-    def damaged(self):
-        torch.cuda.synchronize()
-        return [(what, n) for raw, n, what in self.live if not (bool((raw[:PRE] == PATTERN).all()) and bool((raw[PRE + n:] == PATTERN).all()))]
-
-
+# ---- guard bands (tests/guard_util.py): every output and the workspace at their EXACT sizes ---------------------------------------------------------
 def _guarded_run(g, dev, hv, hf, dtype, iterations, mu, pin):
     """Both protocols through the C ABI itself, every buffer carved at its exact size -> (offsets, neighbours, boundary, verts_out) as numpy"""
     L = _lib.lib()
@@ -213,7 +186,7 @@ def _guarded_run(g, dev, hv, hf, dtype, iterations, mu, pin):
 
 @pytest.mark.parametrize("dtype", [torch.int32, torch.int64])
 def test_no_kernel_writes_outside_its_buffers(dev, closed_mesh, cut_mesh, dtype):
-    g = _Guard(dev)
+    g = Guard(dev)
     cases = [(m["hv"], m["hf"], kw) for m in (closed_mesh, cut_mesh) for kw in ((1, -0.53, True), (2, 0.0, True), (3, 0.0, False), (0, -0.53, True))]
     rng = np.random.default_rng(3)
     for nt in NTS:
@@ -231,39 +204,12 @@ def test_no_kernel_writes_outside_its_buffers(dev, closed_mesh, cut_mesh, dtype)
     assert len(g.live) == 6 * len(cases)
 
 
-def test_the_local_guard_catches_a_one_byte_overrun(dev):
-    g = _Guard(dev)
-    t = g.buf(7, "probe")
-    raw = g.live[-1][0]
-    assert t.data_ptr() == raw.data_ptr() + PRE and not g.damaged()
-    raw[PRE + 7] = 0
-    assert g.damaged() == [("probe", 7)]
-
-
 # ---- the pipeline on the stored small scene (D = 20, R = 64) ------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def scene(dev):
-    from scene_util import small_scene, stored_small_scene_dense
-    s = small_scene()
-    sc = s["sc"]
-    t = lambda a: torch.as_tensor(np.asarray(a)).to(dev)
-    wt = pipeline.SceneWeights(dev, seed=0)
-    vol = dict(vol_cl=stored_small_scene_dense()[0].permute(1, 2, 3, 0).contiguous().to(dev), maskvol=s["mask"][0, 0].contiguous().to(dev).view(-1),
-               cmaps=ops.pack_color_maps(t(s["fmaps"]).contiguous(), t(sc["images"]).contiguous()))
-    proj, cam_pos = pipeline.camera_terms(t(sc["intrinsics"]).float(), t(sc["w2cs"]).float())
-    R = 64
-    plain = pipeline.extract_mesh(wt, vol, proj, cam_pos, R, return_index_verts=True)
-    hv, hf = plain[0].cpu().numpy(), plain[1].cpu().numpy()
-    assert hf.shape[0] > 100
-    return dict(wt=wt, vol=vol, proj=proj, cam_pos=cam_pos, R=R, plain=plain, hv=hv, hf=hf)
-
-
-def _args(S):
-    return S["wt"], S["vol"], S["proj"], S["cam_pos"], S["R"]
-
-
-def _bits(a, b):
-    return a.dtype == b.dtype and a.shape == b.shape and torch.equal(a.contiguous().view(torch.uint8), b.contiguous().view(torch.uint8))
+    S = stored_scene(dev)
+    assert S["hf"].shape[0] > 100
+    return S
 
 
 def test_extract_mesh_with_smoothing(scene):
@@ -359,16 +305,7 @@ def test_reconstruct_folder_reports_the_count_and_writes_the_twins_file(tmp_path
 
 # ---- the drop-in mirror ---------------------------------------------------------------------------------------------------------------------------
 def test_mirror_extract_geometry_applies_the_configured_smoothing(dev, monkeypatch):
-    from golden_util import load
-    recon = importlib.import_module("one-2-3-45_amd.recon")
-    G = load()
-    D = G["cfg"]["D"]
-    sdf = recon.SparseSdfNetwork(lod=0, ch_in=56, voxel_size=2.0 / (D - 1), vol_dims=[D, D, D], hidden_dim=128, cost_type="variance_mean",
-                                 d_pyramid_feature_compress=16, regnet_d_out=16, num_sdf_layers=4, multires=6).to(dev)
-    sdf.load_state_dict(G["sdf_sd"], strict=False)
-    ren = recon.SparseNeuSRenderer(None, sdf, recon.SingleVarianceNetwork(0.2).to(dev), recon.GeneralRenderingNetwork(16, 56, True).to(dev), 64, 64, 0, 1.0,
-                                   alpha_type="div", conf=None)
-    dense = torch.from_numpy(np.ascontiguousarray(G["g"]["dense"])).to(dev)[None]
+    ren, sdf, dense = golden_mirror(dev)
     R = 48
     call = lambda: ren.extract_geometry(sdf, torch.tensor([-1.0] * 3), torch.tensor([1.0] * 3), resolution=R, threshold=0, device=dev,
                                         conditional_volume=dense, lod=0)

@@ -10,6 +10,9 @@ import numpy as np
 import pytest
 import torch
 
+from guard_util import Guard
+from mesh_scene_util import args as _args, colours_at, dev, stored_scene  # noqa: F401 (dev: a fixture)
+
 pytestmark = pytest.mark.gpu
 
 pkg = importlib.import_module("one-2-3-45_amd")
@@ -24,13 +27,6 @@ _lib = importlib.import_module("one-2-3-45_amd._lib")
 COUNTS = (1, 2, 3, 5, 6, 7, 8, 9, 31, 32, 33, 41)
 TEXELS = (4, 5, 8)
 R = 64
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    _lib.lib()
-    return torch.device("cuda:0")
 
 
 def _mesh(nt, seed):
@@ -154,28 +150,7 @@ def test_corners_and_obj_text_equal_the_twin(dev, c, with_normals, with_mats):
 # ---- the pipeline on the stored small scene (D = 20, R = 64), the scene of tests/test_gpu_mesh_project.py -------------------------------------------------
 @pytest.fixture(scope="module")
 def scene(dev):
-    from scene_util import small_scene, stored_small_scene_dense
-    s = small_scene()
-    sc = s["sc"]
-    t = lambda a: torch.as_tensor(np.asarray(a)).to(dev)
-    wt = pipeline.SceneWeights(dev, seed=0)
-    vol = dict(vol_cl=stored_small_scene_dense()[0].permute(1, 2, 3, 0).contiguous().to(dev), maskvol=s["mask"][0, 0].contiguous().to(dev).view(-1),
-               cmaps=ops.pack_color_maps(t(s["fmaps"]).contiguous(), t(sc["images"]).contiguous()))
-    proj, cam_pos = pipeline.camera_terms(t(sc["intrinsics"]).float(), t(sc["w2cs"]).float())
-    return dict(wt=wt, vol=vol, proj=proj, cam_pos=cam_pos, R=64, cache={})
-
-
-def _args(S):
-    return S["wt"], S["vol"], S["proj"], S["cam_pos"], S["R"]
-
-
-def _colours_at(S, world):
-    """the pipeline's two networks at float32 world points -> rgb"""
-    wt, vol = S["wt"], S["vol"]
-    g = ops.sdf_mlp(wt.sdf_blob, vol["vol_cl"], world, variant=2, precision=wt.sdf_precision)["grad"]
-    x3 = wt.color_precision == "f16x3"
-    return ops.color_points(wt.color_xblob if x3 else wt.color_mblob, vol["vol_cl"], vol["maskvol"], vol["cmaps"], S["proj"], S["cam_pos"], world, normals=g,
-                            want_nviews=False, mfma="x3" if x3 else True)[0]
+    return dict(stored_scene(dev, extract=False), cache={})
 
 
 def _expected_image(S, project):
@@ -191,7 +166,7 @@ def _expected_image(S, project):
         if project:
             p, _ = ops.mesh_project(S["wt"].sdf_blob, S["vol"]["vol_cl"], torch.from_numpy(pts).to(dev), S["R"], project, max_move=2.0, precision=S["wt"].sdf_precision)
             world = (p / (S["R"] - 1.0) * 2.0 - 1.0).to(torch.float32).contiguous()
-        image = mio.pack_texture(_colours_at(S, world).cpu().numpy(), hf.shape[0], 4)
+        image = mio.pack_texture(colours_at(S, world)[0].cpu().numpy(), hf.shape[0], 4)
         S["cache"][key] = (v, t, hv, hf, image)
     return S["cache"][key]
 
@@ -350,28 +325,11 @@ def test_errors_are_statuses_not_faults(dev, tmp_path):
     assert L.o2345_obj_texture_text_bytes(4, 1, 0) == 0 and L.o2345_obj_texture_text_bytes(3, 0, 0) == 0
 
 
-# ---- guard bands (the idea of tests/test_gpu_mesh_project.py::_Guard, local to this file): every output and the workspace at their EXACT sizes
-PRE, POST, PATTERN = 512, 4096, 0xA5
-
-
-class _Guard:
-    def __init__(self, dev):
-        self.dev, self.live = dev, []
-
-    def buf(self, nbytes, what):
-        raw = torch.full((PRE + nbytes + POST,), PATTERN, dtype=torch.uint8, device=self.dev)
-        self.live.append((raw, nbytes, what))
-        return raw[PRE:PRE + nbytes]
-
-    def damaged(self):
-        torch.cuda.synchronize()
-        return [(what, n) for raw, n, what in self.live if not (bool((raw[:PRE] == PATTERN).all()) and bool((raw[PRE + n:] == PATTERN).all()))]
-
-
+# ---- guard bands (tests/guard_util.py): every output and the workspace at their EXACT sizes ---------------------------------------------------------
 @pytest.mark.parametrize("dtype", [torch.int32, torch.int64])
 def test_no_kernel_writes_outside_its_buffers(dev, dtype):
     L = _lib.lib()
-    g = _Guard(dev)
+    g = Guard(dev)
     b0, b1 = np.full(3, -1.0, np.float32), np.full(3, 1.0, np.float32)
     P = lambda t: ctypes.c_void_p(t.data_ptr())
     H = lambda a: a.ctypes.data_as(ctypes.c_void_p)
@@ -408,12 +366,3 @@ def test_no_kernel_writes_outside_its_buffers(dev, dtype):
         assert _B(text) == mio.obj_texture_text_numpy(wpos, wuv, wnrm, K)
         assert _B(verts) == v.tobytes() and np.array_equal(tris.cpu().numpy(), f)
     assert len(g.live) == 11 * 5
-
-
-def test_the_local_guard_catches_a_one_byte_overrun(dev):
-    g = _Guard(dev)
-    t = g.buf(7, "probe")
-    raw = g.live[-1][0]
-    assert t.data_ptr() == raw.data_ptr() + PRE and not g.damaged()
-    raw[PRE + 7] = 0
-    assert g.damaged() == [("probe", 7)]

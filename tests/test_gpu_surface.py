@@ -8,7 +8,9 @@ import numpy as np
 import pytest
 import torch
 
+from guard_util import Guard
 from mesh_components_util import spheres_field
+from mesh_scene_util import dev, stored_scene  # noqa: F401 (dev: a fixture)
 from test_surface import look_at, sphere_lattice
 
 pytestmark = pytest.mark.gpu
@@ -23,13 +25,6 @@ _lib = importlib.import_module("one-2-3-45_amd._lib")
 NS = (0, 1, 63, 64, 65, 255, 256, 257, 1025)                  # the lane, wave and block boundaries
 R = 24
 NEAR, FAR = 0.25, 1.0e9
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    _lib.lib()
-    return torch.device("cuda:0")
 
 
 @pytest.fixture(scope="module")
@@ -234,27 +229,6 @@ def test_hits_along_lattice_lines_are_the_marching_cubes_vertices(field, dev):
 
 
 # ---- canaries: every buffer the new entries are handed, at its exact size, carved out of pattern-filled allocations ------------------------------------
-PRE, POST, PATTERN = 512, 4096, 0xA5
-
-
-class _Guard:
-    def __init__(self, dev):
-        self.dev, self.live = dev, []
-
-    def buf(self, src=None, nbytes=None, what=""):
-        """a guarded buffer holding the bytes of numpy array ``src``, or ``nbytes`` bytes of the pattern; the first canary byte comes right after it"""
-        nbytes = src.nbytes if src is not None else nbytes
-        raw = torch.full((PRE + nbytes + POST,), PATTERN, dtype=torch.uint8, device=self.dev)
-        if src is not None and nbytes:
-            raw[PRE:PRE + nbytes] = torch.from_numpy(np.ascontiguousarray(src).reshape(-1).view(np.uint8).copy()).to(self.dev)
-        self.live.append((raw, nbytes, what))
-        return raw[PRE:PRE + nbytes]
-
-    def damaged(self):
-        torch.cuda.synchronize()
-        return [(what, n) for raw, n, what in self.live if not (bool((raw[:PRE] == PATTERN).all()) and bool((raw[PRE + n:] == PATTERN).all()))]
-
-
 def _np(t, dtype, shape):
     return t.cpu().numpy().view(dtype).reshape(shape)
 
@@ -262,7 +236,7 @@ def _np(t, dtype, shape):
 def test_no_kernel_writes_outside_its_buffers(field, dev):
     F = field
     L = _lib.lib()
-    g = _Guard(dev)
+    g = Guard(dev)
     P = lambda t: ctypes.c_void_p(t.data_ptr()) if t.numel() else None
     Hp = lambda a: a.ctypes.data_as(ctypes.c_void_p)
     s = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
@@ -317,15 +291,6 @@ def test_no_kernel_writes_outside_its_buffers(field, dev):
         assert _np(dout, np.float32, (H, W)).tobytes() == want[2].tobytes()
 
 
-def test_the_local_guard_catches_a_one_byte_overrun(dev):
-    g = _Guard(dev)
-    t = g.buf(nbytes=7, what="probe")
-    raw = g.live[-1][0]
-    assert t.data_ptr() == raw.data_ptr() + PRE and not g.damaged()
-    raw[PRE + 7] = 0
-    assert g.damaged() == [("probe", 7)]
-
-
 def test_errors_are_statuses(field, dev):
     F = field
     o, d = F["do"][:70].contiguous(), F["dd"][:70].contiguous()
@@ -347,14 +312,9 @@ def test_errors_are_statuses(field, dev):
 # ---- the pipeline on the stored small scene (D = 20, lattice 64^3, the 48 x 48 query camera) -----------------------------------------------------------
 @pytest.fixture(scope="module")
 def scene(dev):
-    from scene_util import small_scene, stored_small_scene_dense
-    s = small_scene()
-    sc = s["sc"]
-    t = lambda a: torch.as_tensor(np.asarray(a)).to(dev)
-    vol = dict(vol_cl=stored_small_scene_dense()[0].permute(1, 2, 3, 0).contiguous().to(dev), maskvol=s["mask"][0, 0].contiguous().to(dev).view(-1),
-               cmaps=ops.pack_color_maps(t(s["fmaps"]).contiguous(), t(sc["images"]).contiguous()))
-    proj, cam_pos = pipeline.camera_terms(t(sc["intrinsics"]).float(), t(sc["w2cs"]).float())
-    return dict(vol=vol, proj=proj, cam_pos=cam_pos, K=sc["query_intrinsic"], c2w=sc["query_c2w"], H=s["H"], W=s["W"])
+    S0 = stored_scene(dev, extract=False)
+    s = S0["host"]
+    return dict(vol=S0["vol"], proj=S0["proj"], cam_pos=S0["cam_pos"], K=s["sc"]["query_intrinsic"], c2w=s["sc"]["query_c2w"], H=s["H"], W=s["W"])
 
 
 @pytest.mark.parametrize("prec", ["f16x3", "fp32"])
@@ -377,10 +337,10 @@ def test_render_surface_equals_the_twin_and_the_networks_at_the_hit_points(scene
     hit = np.flatnonzero(kind != 0)
     pts = torch.from_numpy(point[hit]).to(dev)
     g = ops.sdf_mlp(wt.sdf_blob, Sc["vol"]["vol_cl"], pts, variant=2, precision=prec)["grad"]
-    x3 = prec == "f16x3"
+    blob, mfma = wt.color_network()
     cam = torch.from_numpy(np.asarray(c2w, np.float32)[:3, 3].copy()).to(dev)
-    rgb, _ = ops.color_points(wt.color_xblob if x3 else wt.color_mblob, Sc["vol"]["vol_cl"], Sc["vol"]["maskvol"], Sc["vol"]["cmaps"], Sc["proj"], Sc["cam_pos"],
-                              pts, query_cam=cam, want_nviews=False, mfma="x3" if x3 else True)
+    rgb, _ = ops.color_points(blob, Sc["vol"]["vol_cl"], Sc["vol"]["maskvol"], Sc["vol"]["cmaps"], Sc["proj"], Sc["cam_pos"], pts, query_cam=cam,
+                              want_nviews=False, mfma=mfma)
     full_rgb, full_g = np.zeros((H * W, 3), np.float32), np.zeros((H * W, 3), np.float32)
     full_rgb[hit], full_g[hit] = rgb.cpu().numpy(), g.cpu().numpy()
     color, normal, dimg = S.pack_images(kind, depth, full_rgb, full_g, H, W, background=(9, 8, 7, 6))

@@ -45,6 +45,7 @@ import bench  # noqa: E402
 
 pipeline = bench.pipeline
 ops = importlib.import_module("one-2-3-45_amd.ops")
+config = importlib.import_module("one-2-3-45_amd.config")
 mio = importlib.import_module("one-2-3-45_amd.mesh_io")
 
 
@@ -76,10 +77,10 @@ def med_events(fn, reps, warmup):
 def one_mesh(dev, wt, tmp, D, R, ray_scale, a, numpy_writer):
     inp = bench.make_inputs(dev, 8, 0, ray_scale)
     vol = pipeline.build_volume(wt, inp["imgs"], inp["aff"], inp["origin"], D, 2.0 / (D - 1))
-    _, verts_idx, tris, rgb, u, g = pipeline._mesh_fields(wt, vol, inp["proj"], inp["cam_pos"], R)
+    _, verts_idx, tris, rgb, u, g, _, _ = pipeline._mesh_fields(wt, vol, inp["proj"], inp["cam_pos"], R, config.mesh_options())
     n, m = int(verts_idx.shape[0]), int(tris.shape[0])
-    cc = {}
-    _, f_verts, f_tris, f_rgb, _, _ = pipeline._mesh_fields(wt, vol, inp["proj"], inp["cam_pos"], R, keep_largest=True, info=cc)
+    _, f_verts, f_tris, f_rgb, _, _, cc, _ = pipeline._mesh_fields(wt, vol, inp["proj"], inp["cam_pos"], R, config.mesh_options(keep_largest=True))
+    cc = {k: cc[k] for k in ("components", "components_kept")}
     P = lambda e: os.path.join(tmp, "mesh" + e)
     res = {"volume": D, "grid": R, "vertices": n, "triangles": m}
     stage = {
@@ -138,7 +139,6 @@ def one_mesh(dev, wt, tmp, D, R, ray_scale, a, numpy_writer):
         "grad_color_kept": med_events(lambda: grad_color(f_verts), a.reps, a.warmup),
     })
     # Taubin smoothing, 10 iterations: table, steps, both; the host twin on the same arrays as the yardstick
-    config = importlib.import_module("one-2-3-45_amd.config")
     L = importlib.import_module("one-2-3-45_amd._lib").lib()
     IT = 10
     offsets, neighbours, boundary = ops.mesh_vertex_adjacency(tris, n)
