@@ -8,8 +8,9 @@
 namespace o2345 {
 
 // torch.linspace(start, end, steps)[i] for fp32, bit-exact with ATen's CPU kernel (RangeFactories.cpp: symmetric
-// evaluation, step*i + start contracted to ONE fused multiply-add by its vectorised path)
+// evaluation, step*i + start contracted to ONE fused multiply-add by its vectorised path); steps = 1: [start] (the step would be 0 / 0)
 O2345_HD float linspace_at(float start, float end, int steps, int i) {
+    if (steps == 1) return start;
     const float step = (end - start) / (float)(steps - 1);
     return (i < steps / 2) ? fmaf(step, (float)i, start) : fmaf(-step, (float)(steps - 1 - i), end);
 }

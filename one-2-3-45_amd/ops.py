@@ -753,11 +753,62 @@ def render_rays(scene, rays_o, rays_d, near, far, n_samples=64, n_importance=64,
 
 
 @_on_device
-def ray_upsample(rays_o, rays_d, z, sdf, inv_s, maskvol, D, n_imp, streaming=None):
+def ray_coarse(rays_o, rays_d, near, far, n_samples, t_rand=None):
+    """Stage entry points of the coarse samples (sparse_neus_renderer.py:486-515): z = near + (far - near) * linspace(0, 1, n_samples), with the
+    stratified jitter t_rand [R, n_samples] (ray-major, what torch.rand(z_vals.shape) returns) when given.  near / far: python floats
+    (o2345_ray_coarse, o2345_ray_coarse_jitter), or two float32 tensors [R] on the device (o2345_ray_coarse_per_ray).
+    -> (z SAMPLE-MAJOR [n_samples,R], pts [n_samples,R,3])."""
+    L = _lib.lib()
+    if rays_d.shape != rays_o.shape or rays_o.dim() != 2 or rays_o.shape[1] != 3:
+        raise ValueError(f"ray_coarse: rays_o / rays_d must both be [R,3] (got {tuple(rays_o.shape)}, {tuple(rays_d.shape)})")
+    R, S = rays_o.shape[0], int(n_samples)
+    if S < 2:
+        raise ValueError(f"ray_coarse: at least 2 samples per ray (got {S})")
+    if t_rand is not None and tuple(t_rand.shape) != (R, S):
+        raise ValueError(f"ray_coarse: t_rand must be [R, n_samples] = {(R, S)}, got {tuple(t_rand.shape)}")
+    dev = rays_o.device
+    z = torch.empty(S, R, dtype=torch.float32, device=dev)
+    pts = torch.empty(S, R, 3, dtype=torch.float32, device=dev)
+    if torch.is_tensor(near) or torch.is_tensor(far):
+        if not (torch.is_tensor(near) and torch.is_tensor(far)) or near.numel() != R or far.numel() != R:
+            raise ValueError("ray_coarse: per-ray near / far are two tensors of R elements")
+        check(L.o2345_ray_coarse_per_ray(_p(rays_o), _p(rays_d), R, _p(near), _p(far), S, _p(t_rand), _p(z), _p(pts), _stream()), "ray_coarse_per_ray")
+    elif t_rand is not None:
+        check(L.o2345_ray_coarse_jitter(_p(rays_o), _p(rays_d), R, float(near), float(far), S, _p(t_rand), _p(z), _p(pts), _stream()), "ray_coarse_jitter")
+    else:
+        check(L.o2345_ray_coarse(_p(rays_o), _p(rays_d), R, float(near), float(far), S, _p(z), _p(pts), _stream()), "ray_coarse")
+    return z, pts
+
+
+@_on_device
+def ray_merge(z, sdf, new_z, new_sdf):
+    """Stage entry point of cat_z_vals' merge (sparse_neus_renderer.py:139-149): the sorted lists z, sdf SAMPLE-MAJOR [S,R] and a block of new samples
+    new_z, new_sdf [n_new,R] in any order -> (z, sdf) [S + n_new,R], a stable merge in which, among equal depths, existing samples stay in front of
+    new ones.  The arguments are left as they are."""
+    if z.dim() != 2 or sdf.shape != z.shape or new_z.dim() != 2 or new_sdf.shape != new_z.shape or new_z.shape[1] != z.shape[1]:
+        raise ValueError(f"ray_merge: z / sdf [S,R] and new_z / new_sdf [n_new,R] expected (got {tuple(z.shape)}, {tuple(sdf.shape)}, "
+                         f"{tuple(new_z.shape)}, {tuple(new_sdf.shape)})")
+    (S, R), n_new = z.shape, new_z.shape[0]
+    if S < 1 or n_new < 1 or R < 1:
+        raise ValueError(f"ray_merge: at least one ray, one sample and one new sample (got R = {R}, S = {S}, n_new = {n_new})")
+    _p(z), _p(sdf)
+    zm = torch.cat([z, torch.zeros_like(new_z)], 0)           # capacity S + n_new: merged in place
+    sm = torch.cat([sdf, torch.zeros_like(new_sdf)], 0)
+    nz, ns = new_z.clone(), new_sdf.clone()
+    check(_lib.lib().o2345_ray_merge(R, _p(zm), _p(sm), S, _p(nz), _p(ns), n_new, _stream()), "ray_merge")
+    return zm, sm
+
+
+@_on_device
+def ray_upsample(rays_o, rays_d, z, sdf, inv_s, maskvol, D, n_imp, streaming=None, want_weights=False):
     """Stage entry point of the hierarchical sampler (up_sample + sample_pdf, sparse_neus_renderer.py:73-115, render_utils.py:8-51):
-    z, sdf SAMPLE-MAJOR [S,R] -> (new_z [n_imp,R], new_pts [n_imp,R,3], valid-point list int32 [<= n_imp*R] of slots t*R + r)."""
+    z, sdf SAMPLE-MAJOR [S,R] -> (new_z [n_imp,R], new_pts [n_imp,R,3], valid-point list int32 [<= n_imp*R] of slots t*R + r).
+    want_weights: also the scratch rows [S-1,R] -- the streaming kernel leaves its section weights alpha * T + 1e-5 there (sample_pdf's
+    `weights + 1e-5`); the sixteen-lane kernel keeps them in LDS and does not write the rows."""
     S, R = z.shape
     dev = z.device
+    if want_weights and streaming is False:
+        raise ValueError("ray_upsample: want_weights needs the scratch rows (streaming=False hands none over)")
     # streaming=None: scratch is handed over and the library picks the kernel by R (O2345_RAY_STREAM_MIN); False: no scratch -> the LDS-staged kernel
     wbuf = None if streaming is False else torch.empty(S, R, dtype=torch.float32, device=dev)
     new_z = torch.empty(n_imp, R, dtype=torch.float32, device=dev)
@@ -767,6 +818,8 @@ def ray_upsample(rays_o, rays_d, z, sdf, inv_s, maskvol, D, n_imp, streaming=Non
     cnt = torch.zeros(1, dtype=torch.int32, device=dev)
     check(_lib.lib().o2345_ray_upsample(_p(rays_o), _p(rays_d), R, _p(z), _p(sdf), S, float(inv_s), _p(maskvol), int(D), _p(wbuf), int(n_imp),
                                         _p(new_z), _p(new_pts), _p(new_sdf), _p(lst, torch.int32), _p(cnt, torch.int32), _stream()), "ray_upsample")
+    if want_weights:
+        return new_z, new_pts, lst[:int(cnt.item())], wbuf[:S - 1]
     return new_z, new_pts, lst[:int(cnt.item())]
 
 

@@ -34,7 +34,7 @@ def P(a):
 
 
 def test_linspace_matches_torch(hc):
-    for a, b, n in ((0.0, 1.0, 64), (-1.0, 1.0, 256), (-1.0, 1.0, 360), (-1.0, 1.0, 37), (0.03125, 0.96875, 16), (-0.147, 1.937, 64)):
+    for a, b, n in ((0.0, 1.0, 64), (-1.0, 1.0, 256), (-1.0, 1.0, 360), (-1.0, 1.0, 37), (0.03125, 0.96875, 16), (-0.147, 1.937, 64), (0.5, 0.5, 1)):
         ref = torch.linspace(a, b, n)
         got = np.array([hc.hc_linspace(a, b, n, i) for i in range(n)], np.float32)
         assert np.array_equal(got, ref.numpy()), (a, b, n)          # bit-exact with ATen's CPU linspace
