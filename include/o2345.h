@@ -51,7 +51,9 @@ const char* o2345_last_error(void);
  * o2345_mesh_adjacency_workspace_bytes, o2345_mesh_adjacency_count, o2345_mesh_adjacency_emit, o2345_mesh_smooth; the decimation entries
  * o2345_mesh_decimate_workspace_bytes, o2345_mesh_decimate_count, o2345_mesh_decimate_emit; the projection entries
  * o2345_mesh_project_workspace_bytes, o2345_mesh_project; the sparse lattice entries o2345_sdf_grid_sparse_workspace_bytes,
- * o2345_sdf_grid_sparse_x3. */
+ * o2345_sdf_grid_sparse_x3; the mesh distance entries o2345_mesh_samples_workspace_bytes, o2345_mesh_samples_count, o2345_mesh_samples_emit,
+ * o2345_mesh_distance_grid_workspace_bytes, o2345_mesh_distance_grid_bytes, o2345_mesh_distance_grid_count, o2345_mesh_distance_grid_emit,
+ * o2345_mesh_distance_query, o2345_mesh_distance_reduce_workspace_bytes, o2345_mesh_distance_reduce. */
 int o2345_version(void);
 /* Layout self-description of O2345RenderIO as THIS library was compiled (sizeof, and offsetof of every field in declaration order): a binding
  * asserts its own struct against it at load time (one-2-3-45_amd/_lib.py does) -- a field added on one side only cannot corrupt calls silently.
@@ -582,6 +584,54 @@ int o2345_surface_trace(const float* u, int grid_R, const uint8_t* flags, const 
 int o2345_camera_rays(const float* K_host, const float* c2w_host, int H, int W, float* rays_o, float* rays_d, void* stream);
 int o2345_surface_pack(const uint8_t* kind, const float* depth, const float* rgb, const float* grad, int H, int W, const uint8_t* background_host,
                        uint8_t* color, uint8_t* normal, float* depth_out, void* stream);
+/* ---- mesh-to-mesh distance (additive since 2.1; none in the reference: its meshes are never compared as surfaces) ----------------------------------------
+ * Everything is fp64, one operation at a time, in the order written, a dot product (x x + y y) + z z; equal to the host twin (mesh_io.surface_samples,
+ * closest_triangles) to the last bit.  verts device fp64 [nv,3], tris device int32 / int64 [nt,3] (index_bytes 4 / 8), both only read; 0 <= nv < 2^30,
+ * 3 * nt < 2^31.  Workspaces and the grid object are 16-byte aligned; every *_bytes function returns 0 for bad sizes.
+ *   samples   triangle t (corners P0, P1, P2) at `spacing` (finite, > 0; 0 = one sample per triangle): L2 = the largest squared edge length, k_t = the
+ *             smallest k in [1, 64] with (k spacing)(k spacing) >= L2, 64 if there is none (1 without a spacing).  The triangle is split regularly into
+ *             k^2 sub-triangles and sampled at their centroids: the upright ones first, j = 0 .. k - 1, i = 0 .. k - 1 - j: w1 = (3 i + 1) / (3 k), w2 =
+ *             (3 j + 1) / (3 k); then the inverted ones, j = 0 .. k - 2, i = 0 .. k - 2 - j: w1 = (3 i + 2) / (3 k), w2 = (3 j + 2) / (3 k); w0 = (1 - w1)
+ *             - w2, p = (w0 P0 + w1 P1) + w2 P2.  Weight: area_t / k^2, area_t = 0.5 sqrt(n . n), n = (P1 - P0) x (P2 - P0).  Samples are numbered
+ *             triangle-major.  samples_count returns their number on the HOST (synchronises the stream once); errors: 2^28 samples or more, a non-finite
+ *             coordinate, an index outside [0, nv) -- counted on the device, never dereferenced.  samples_emit (same workspace, nv, nt, untouched in
+ *             between; n_samples as counted) writes points fp64 [n,3], weights fp64 [n], triangle int32 [n]; any of the three may be NULL.
+ *   d2        squared distance from p to triangle (A, B, C): |p - q|^2, q from the region walk of Ericson, Real-Time Collision Detection 5.1.5, regions
+ *             tested in the book's order (csrc/mesh_distance_math.h, md_point_triangle, is the text).  A target triangle is USABLE iff its indices are in
+ *             range, its coordinates finite and n . n != 0.  d2 [i] = the minimum over the usable triangles, nearest [i] = the smallest index that
+ *             attains it; +inf and -1 without a usable triangle.
+ *   grid      a uniform grid of cells of edge `cell` (finite, > 0; 0 = the default: about as many cells as usable triangles) aligned to the multiples of
+ *             the edge, over the bounds of the usable triangles; an edge that gives more than 256 cells along an axis or more than max_cells (1 .. 2^24)
+ *             in all is enlarged by factors of 1.25.  Every usable triangle is listed in each cell its bounding box touches; a list is ascending.
+ *             grid_count returns on the HOST (one synchronisation) the number of list entries, and optionally the degenerate triangles, the cells per
+ *             axis and the edge in use; errors as for samples, plus a target without a usable triangle, plus 2^31 entries or more.  grid_emit (same
+ *             workspace and arguments, n_entries as counted) writes the grid object: grid_bytes(max_cells, n_entries) bytes.
+ *   query     points device fp64 [n,3], n < 2^28 -> d2 fp64 [n], nearest int32 [n].  grid NULL: every point against every triangle.  grid given (with
+ *             the max_cells it was built with, over the same verts and tris): the same bits through the grid -- shells of cells outward from the
+ *             point's cell, stopping when a conservative lower bound on the distance to everything unvisited exceeds the best distance found.
+ *   reduce    d2, nearest (may be NULL), weights (NULL = 1) over n samples; thresholds HOST fp64 [n_thresholds <= 8], finite and >= 0 -> stats, 128
+ *             bytes, 8-byte aligned: fp64 sum w, sum w d, sum w d^2, sum w [d <= tau_k] for k = 0 .. 7 (d = sqrt(d2)), then uint64: the bit pattern of
+ *             the largest d2, n, the samples left out (d2 not finite or negative, or nearest < 0), and of the optional target (tris NULL = none) its
+ *             degenerate triangles and those with a bad index or a non-finite coordinate.  The sums are the same bits on every run (fixed tree, no
+ *             floating-point atomics; at most 288 additions in a chain).  No host synchronisation. */
+size_t o2345_mesh_samples_workspace_bytes(long long nt);
+int o2345_mesh_samples_count(const double* verts, const void* tris, int index_bytes, long long nv, long long nt, double spacing, void* workspace,
+                             size_t workspace_bytes, long long* n_samples_host, void* stream);
+int o2345_mesh_samples_emit(const double* verts, const void* tris, int index_bytes, long long nv, long long nt, void* workspace, long long n_samples,
+                            double* points, double* weights, int* triangle, void* stream);
+size_t o2345_mesh_distance_grid_workspace_bytes(long long nt, long long max_cells);
+size_t o2345_mesh_distance_grid_bytes(long long max_cells, long long n_entries);
+int o2345_mesh_distance_grid_count(const double* verts, const void* tris, int index_bytes, long long nv, long long nt, double cell, long long max_cells,
+                                   void* workspace, size_t workspace_bytes, long long* n_entries_host, long long* n_degenerate_host, int* dims_host,
+                                   double* cell_host, void* stream);
+int o2345_mesh_distance_grid_emit(const double* verts, const void* tris, int index_bytes, long long nv, long long nt, long long max_cells, void* workspace,
+                                  long long n_entries, void* grid, size_t grid_bytes, void* stream);
+int o2345_mesh_distance_query(const double* points, long long n, const double* verts, const void* tris, int index_bytes, long long nv, long long nt,
+                              const void* grid, size_t grid_bytes, long long max_cells, double* d2, int* nearest, void* stream);
+size_t o2345_mesh_distance_reduce_workspace_bytes(long long n);
+int o2345_mesh_distance_reduce(const double* d2, const int* nearest, const double* weights, long long n, const double* thresholds, int n_thresholds,
+                               const double* verts, const void* tris, int index_bytes, long long nv, long long nt, void* workspace, size_t workspace_bytes,
+                               void* stats, void* stream);
 /* Load every code object of the library on the current device now (the HIP runtime loads a translation unit's kernels at its first launch: 5 - 60 ms
  * each for the units of this library, which otherwise land inside the first calls of a fresh process).  Launches nothing that touches user memory. */
 int o2345_preload(void);

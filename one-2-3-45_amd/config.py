@@ -286,6 +286,17 @@ def mesh_texture_png_level(n=None):
     return _png_level("png_level", int(n))
 
 
+# ---- mesh error report (csrc/mesh_distance.hip; mesh_io.mesh_distance is the host twin) -------------------------------------------------------------------
+# O2345_MESH_ERROR=1 makes pipeline.reconstruct_folder report how far the mesh it wrote is from the raw marching-cubes mesh it started from, as surfaces:
+# Chamfer, Hausdorff and F-score (ops.mesh_distance) in units of the extraction grid's spacing ("" or "0" = off, the default: nothing is launched and the
+# result keeps its keys).
+MESH_ERROR = _non_negative_int("O2345_MESH_ERROR", os.environ.get("O2345_MESH_ERROR", "")) != 0
+
+
+def mesh_error(x=None):
+    return MESH_ERROR if x is None else bool(x)
+
+
 # ---- surface render (csrc/surface_trace.hip; surface.py is the host twin) ---------------------------------------------------------------------------------
 # pipeline.render_surface marches rays through the extraction lattice.  O2345_SURFACE_STRIDE (1.0, in (0, 8]) is the distance between two samples in
 # lattice spacings -- above 1 the march may step over parts thinner than the stride; O2345_SURFACE_REFINE (8, in [0, 32]) the number of bracket

@@ -1156,3 +1156,258 @@ def export_asset(path, verts_idx, tris, grid_R, bound_min=(-1.0, -1.0, -1.0), bo
         with open(path, "wb") as fh:
             fh.write(ops.to_host_numpy(text)[0].data)
     return n, m
+
+
+# ------------------------------------------------------------------------------------------------------------------ mesh-to-mesh distance
+# the functions below are the host twin of csrc/mesh_distance.hip and the DEFINITION of its results: samples, d2 and nearest to the last bit.  All
+# arithmetic is float64, one operation at a time, in the order written; a dot product is (x x + y y) + z z.
+DISTANCE_MAX_LEVEL = 64
+DISTANCE_MAX_SAMPLES = 2 ** 28
+DISTANCE_MAX_THRESHOLDS = 8
+
+
+def _dot3(a, b):
+    return (a[..., 0] * b[..., 0] + a[..., 1] * b[..., 1]) + a[..., 2] * b[..., 2]
+
+
+def _check_spacing(spacing):
+    """-> None (one sample per triangle) or the finite float > 0"""
+    if spacing is None:
+        return None
+    if isinstance(spacing, (bool, np.bool_)) or not isinstance(spacing, (int, float, np.integer, np.floating)) or not (np.isfinite(spacing) and spacing > 0):
+        raise ValueError(f"mesh_distance: spacing must be None or a finite float > 0, got {spacing!r}")
+    return float(spacing)
+
+
+def _check_thresholds(thresholds):
+    th = [float(t) for t in thresholds]
+    if len(th) > DISTANCE_MAX_THRESHOLDS:
+        raise ValueError(f"mesh_distance: {len(th)} thresholds; at most {DISTANCE_MAX_THRESHOLDS}")
+    if not all(np.isfinite(t) and t >= 0 for t in th):
+        raise ValueError(f"mesh_distance: thresholds must be finite and >= 0, got {thresholds!r}")
+    return th
+
+
+def _distance_mesh(verts, faces, what):
+    """-> (vertices float64 [N,3], faces int64 [M,3]); raises on an index out of range or a non-finite coordinate of a referenced vertex"""
+    p = np.ascontiguousarray(np.asarray(verts, dtype=np.float64).reshape(-1, 3))
+    f = np.asarray(faces).reshape(-1, 3).astype(np.int64, copy=False)
+    if f.size and (f.min() < 0 or f.max() >= p.shape[0]):
+        raise ValueError(f"{what}: faces index outside 0 .. {p.shape[0] - 1}")
+    if f.size and not np.isfinite(p[f.reshape(-1)]).all():
+        raise ValueError(f"{what}: non-finite vertex coordinate")
+    return p, f
+
+
+def _normal2(P0, P1, P2):
+    e1, e2 = P1 - P0, P2 - P0
+    n = np.stack([e1[..., 1] * e2[..., 2] - e1[..., 2] * e2[..., 1], e1[..., 2] * e2[..., 0] - e1[..., 0] * e2[..., 2],
+                  e1[..., 0] * e2[..., 1] - e1[..., 1] * e2[..., 0]], -1)
+    return _dot3(n, n)
+
+
+def sample_levels(verts, faces, spacing):
+    """k_t of every triangle: 1 without a spacing, else the smallest integer k in [1, 64] with (k spacing)(k spacing) >= L2, L2 the largest of the squared
+    lengths of P1 - P0, P2 - P1, P0 - P2, and 64 if there is none.  No square root and no division decide it."""
+    p, f = _distance_mesh(verts, faces, "sample_levels")
+    spacing = _check_spacing(spacing)
+    k = np.ones(f.shape[0], np.int64)
+    if spacing is None or not f.shape[0]:
+        return k
+    P = p[f]
+    e = [P[:, 1] - P[:, 0], P[:, 2] - P[:, 1], P[:, 0] - P[:, 2]]
+    L2 = np.maximum(np.maximum(_dot3(e[0], e[0]), _dot3(e[1], e[1])), _dot3(e[2], e[2]))
+    k[:] = DISTANCE_MAX_LEVEL
+    for kk in range(DISTANCE_MAX_LEVEL - 1, 0, -1):                   # descending: the smallest k that passes is written last
+        ks = float(kk) * spacing
+        k[ks * ks >= L2] = kk
+    # the test is monotone in k (products of non-negative floats round monotonically), so "the smallest" and "the last written" agree
+    return k
+
+
+def sample_weights(k):
+    """The barycentric weights of the k^2 samples of one triangle, float64 [k^2, 3]: upright sub-triangles first (j = 0 .. k - 1, i = 0 .. k - 1 - j: w1 =
+    (3 i + 1) / (3 k), w2 = (3 j + 1) / (3 k)), then the inverted ones (j = 0 .. k - 2, i = 0 .. k - 2 - j: w1 = (3 i + 2) / (3 k), w2 = (3 j + 2) / (3 k));
+    w0 = (1 - w1) - w2."""
+    rows = [(i, j, 1) for j in range(k) for i in range(k - j)] + [(i, j, 2) for j in range(k - 1) for i in range(k - 1 - j)]
+    ij = np.asarray(rows, np.int64)
+    w1 = (3 * ij[:, 0] + ij[:, 2]) / float(3 * k)
+    w2 = (3 * ij[:, 1] + ij[:, 2]) / float(3 * k)
+    return np.stack([(1.0 - w1) - w2, w1, w2], 1)
+
+
+def surface_samples(verts, faces, spacing=None):
+    """Area-weighted samples of a mesh's surface (host twin of ops.mesh_surface_samples) -> (points float64 [n,3], weight float64 [n], triangle int32
+    [n]).  Triangle t is split regularly into k_t^2 sub-triangles (sample_levels) and sampled at their centroids (sample_weights): p = (w0 P0 + w1 P1) +
+    w2 P2; every sample of t weighs area_t / k_t^2, area_t = 0.5 sqrt(n . n), n = (P1 - P0) x (P2 - P0) -- a triangle without an area still yields its
+    samples, of weight 0.  Samples are numbered triangle-major.  Refused (ValueError): 2^28 samples or more, a non-finite coordinate, an index outside
+    [0, N), a spacing that is not None or a finite float > 0."""
+    p, f = _distance_mesh(verts, faces, "surface_samples")
+    k = sample_levels(p, f, spacing)
+    k2 = k * k
+    n = int(k2.sum())
+    if n >= DISTANCE_MAX_SAMPLES:
+        raise ValueError(f"surface_samples: {n} samples; the limit is 2^28 - 1 (raise the spacing)")
+    off = np.cumsum(k2) - k2
+    pts, wgt, tri = np.zeros((n, 3)), np.zeros(n), np.zeros(n, np.int32)
+    for K in np.unique(k):
+        idx = np.nonzero(k == K)[0]
+        w = sample_weights(int(K))
+        for s in range(0, idx.size, 4096):
+            sel = idx[s:s + 4096]
+            P = p[f[sel]]                                             # [m, 3 corners, 3]
+            x = (w[None, :, 0, None] * P[:, None, 0] + w[None, :, 1, None] * P[:, None, 1]) + w[None, :, 2, None] * P[:, None, 2]
+            at = (off[sel][:, None] + np.arange(int(K) * int(K))[None]).reshape(-1)
+            pts[at] = x.reshape(-1, 3)
+            wgt[at] = np.repeat(0.5 * np.sqrt(_normal2(P[:, 0], P[:, 1], P[:, 2])) / float(int(K) * int(K)), int(K) * int(K))
+            tri[at] = np.repeat(sel, int(K) * int(K)).astype(np.int32)
+    return pts, wgt, tri
+
+
+def closest_point_triangle(p, A, B, C):
+    """Squared distance from points to triangles, broadcast over the leading axes (all [..., 3]) -> (d2 float64, region uint8): |p - q|^2 with q from the
+    region walk of Ericson, Real-Time Collision Detection 5.1.5, the regions tested in the book's order -- 0 vertex A, 1 vertex B, 2 edge AB, 3 vertex C,
+    4 edge AC, 5 edge BC, 6 face.  The first region whose test passes gives q; this code, one operation per line, is the definition."""
+    with np.errstate(all="ignore"):
+        ab = B - A
+        ac = C - A
+        ap = p - A
+        d1 = _dot3(ab, ap)
+        d2 = _dot3(ac, ap)
+        bp = p - B
+        d3 = _dot3(ab, bp)
+        d4 = _dot3(ac, bp)
+        cp = p - C
+        d5 = _dot3(ab, cp)
+        d6 = _dot3(ac, cp)
+        t1 = d1 * d4
+        t2 = d3 * d2
+        vc = t1 - t2
+        t1 = d5 * d2
+        t2 = d1 * d6
+        vb = t1 - t2
+        t1 = d3 * d6
+        t2 = d5 * d4
+        va = t1 - t2
+        s43 = d4 - d3
+        s56 = d5 - d6
+        tests = [(d1 <= 0.0) & (d2 <= 0.0),
+                 (d3 >= 0.0) & (d4 <= d3),
+                 (vc <= 0.0) & (d1 >= 0.0) & (d3 <= 0.0),
+                 (d6 >= 0.0) & (d5 <= d6),
+                 (vb <= 0.0) & (d2 >= 0.0) & (d6 <= 0.0),
+                 (va <= 0.0) & (s43 >= 0.0) & (s56 >= 0.0)]
+        region = np.full(tests[0].shape, 6, np.uint8)
+        for r in range(5, -1, -1):                                    # the first test that passes wins
+            region = np.where(tests[r], np.uint8(r), region)
+        shape = region.shape + (3,)
+        v_ab = d1 / (d1 - d3)
+        w_ac = d2 / (d2 - d6)
+        w_bc = s43 / (s43 + s56)
+        den = 1.0 / ((va + vb) + vc)
+        v = vb * den
+        w = vc * den
+        q = (A + ab * v[..., None]) + ac * w[..., None]
+        q = np.where((region == 5)[..., None], B + w_bc[..., None] * (C - B), q)
+        q = np.where((region == 4)[..., None], A + w_ac[..., None] * ac, q)
+        q = np.where((region == 2)[..., None], A + v_ab[..., None] * ab, q)
+        q = np.where((region == 3)[..., None], np.broadcast_to(C, shape), q)
+        q = np.where((region == 1)[..., None], np.broadcast_to(B, shape), q)
+        q = np.where((region == 0)[..., None], np.broadcast_to(A, shape), q)
+        d = p - q
+        return _dot3(d, d), region
+
+
+def closest_triangles(points, verts, faces, chunk=256):
+    """For every point its closest triangle of a target mesh (host twin of ops.mesh_closest_triangle), by brute force -> (d2 float64 [n], nearest int32
+    [n], region uint8 [n], ties int32 [n], degenerate).  A target triangle whose normal has n . n == 0 takes no part and is counted in ``degenerate``; d2
+    is the minimum of closest_point_triangle over the others, ``nearest`` the smallest index among those that attain it, ``region`` that triangle's
+    region, ``ties`` how many triangles attain the minimum bit for bit.  A target with no triangle left is an error."""
+    p, f = _distance_mesh(verts, faces, "closest_triangles")
+    x = np.ascontiguousarray(np.asarray(points, np.float64).reshape(-1, 3))
+    P = p[f]
+    usable = _normal2(P[:, 0], P[:, 1], P[:, 2]) != 0.0 if f.shape[0] else np.zeros(0, bool)
+    index = np.nonzero(usable)[0]
+    if not index.size:
+        raise ValueError(f"closest_triangles: the target has no triangle with an area ({f.shape[0]} triangles, all degenerate)")
+    A, B, C = P[index, 0][None], P[index, 1][None], P[index, 2][None]
+    n = x.shape[0]
+    d2, nearest, region, ties = np.zeros(n), np.zeros(n, np.int32), np.zeros(n, np.uint8), np.zeros(n, np.int32)
+    for s in range(0, n, chunk):
+        m, reg = closest_point_triangle(x[s:s + chunk, None, :], A, B, C)
+        m = np.where(np.isnan(m), np.inf, m)
+        j = m.argmin(1)                                               # the first of equal minima: the smallest index
+        rows = np.arange(j.size)
+        best = m[rows, j]
+        d2[s:s + chunk], nearest[s:s + chunk], region[s:s + chunk] = best, index[j], reg[rows, j]
+        ties[s:s + chunk] = (m == best[:, None]).sum(1)
+    return d2, nearest, region, ties, int(f.shape[0] - index.size)
+
+
+def distance_summary(d2, weight, thresholds=()):
+    """One direction's summary from the samples' squared distances and weights, d = sqrt(d2), W = sum w -> {"mean": sum w d / W, "rms": sqrt(sum w d^2 /
+    W), "max": max d, "within": [sum w [d <= tau] / W per threshold], "samples", "area": W}.  The sums are math.fsum's (the device sums in another
+    order; they agree to 1e-12)."""
+    import math
+    th = _check_thresholds(thresholds)
+    d2, w = np.asarray(d2, np.float64), np.asarray(weight, np.float64)
+    d = np.sqrt(d2)
+    W = math.fsum(w)
+    div = lambda s: s / W if W > 0 else float("nan")
+    return {"mean": div(math.fsum(w * d)), "rms": math.sqrt(div(math.fsum(w * d2))) if W > 0 else float("nan"), "max": float(d.max()) if d.size else 0.0,
+            "within": [div(math.fsum(w[d <= t])) for t in th], "samples": int(d.size), "area": W}
+
+
+def distance_report(a_to_b, b_to_a, thresholds, degenerate_a, degenerate_b):
+    """The two one-sided summaries -> the result of mesh_distance (shared with ops.mesh_distance)"""
+    P, R = a_to_b["within"], b_to_a["within"]
+    return {"a_to_b": a_to_b, "b_to_a": b_to_a, "chamfer": 0.5 * (a_to_b["mean"] + b_to_a["mean"]), "hausdorff": max(a_to_b["max"], b_to_a["max"]),
+            "thresholds": list(thresholds), "precision": list(P), "recall": list(R),
+            "fscore": [2.0 * p * r / (p + r) if p + r > 0 else 0.0 for p, r in zip(P, R)], "degenerate_targets": {"a": degenerate_a, "b": degenerate_b}}
+
+
+def mesh_distance(va, fa, vb, fb, spacing=None, thresholds=(), return_samples=False):
+    """Distance between mesh A (under test) and mesh B (the reference) as surfaces, on the host (the twin of ops.mesh_distance) -> {"a_to_b", "b_to_a": the
+    one-sided summaries (distance_summary) of A's samples against B and of B's against A; "chamfer": the mean of the two means; "hausdorff": the larger
+    of the two maxima; "thresholds"; "precision" = a_to_b.within, "recall" = b_to_a.within and "fscore" = 2 P R / (P + R) (0 when P + R == 0) per
+    threshold; "degenerate_targets": {"a", "b"}, the triangles without an area that took no part as targets}.  Samples: surface_samples at ``spacing``
+    (None: one per triangle).  ``return_samples`` adds "samples": {"a", "b"} -> {"points", "weight", "triangle", "d2", "nearest"}."""
+    th = _check_thresholds(thresholds)
+    spacing = _check_spacing(spacing)
+    va, fa = _distance_mesh(va, fa, "mesh_distance")
+    vb, fb = _distance_mesh(vb, fb, "mesh_distance")
+    sides, degenerate, samples = {}, {}, {}
+    for name, (v, f), (tv, tf), other in (("a_to_b", (va, fa), (vb, fb), "b"), ("b_to_a", (vb, fb), (va, fa), "a")):
+        pts, w, tri = surface_samples(v, f, spacing)
+        d2, nearest, _, _, degenerate[other] = closest_triangles(pts, tv, tf)
+        sides[name] = distance_summary(d2, w, th)
+        samples[name[0]] = {"points": pts, "weight": w, "triangle": tri, "d2": d2, "nearest": nearest}
+    out = distance_report(sides["a_to_b"], sides["b_to_a"], th, degenerate["a"], degenerate["b"])
+    if return_samples:
+        out["samples"] = samples
+    return out
+
+
+def read_mesh(path):
+    """A mesh file by its extension (.ply, .glb, .obj) -> (vertices float64 [N,3], faces int32 [M,3], extension)"""
+    ext = _asset_ext(path)
+    v, f = {".ply": read_ply, ".glb": read_glb, ".obj": read_obj}[ext](path)[:2]
+    return np.asarray(v, np.float64), f, ext
+
+
+def load_mesh_pair(path_a, path_b):
+    """Two mesh files in one frame -> ((va, fa), (vb, fb)): where one is a PLY and the other an asset, the PLY's mesh goes through to_asset_frame (an
+    isometry, so nothing else needs converting)."""
+    va, fa, ea = read_mesh(path_a)
+    vb, fb, eb = read_mesh(path_b)
+    if ea == ".ply" and eb != ".ply":
+        va, fa = to_asset_frame(va, fa)
+    if eb == ".ply" and ea != ".ply":
+        vb, fb = to_asset_frame(vb, fb)
+    return (va, fa), (vb, fb)
+
+
+def compare_mesh_files(path_a, path_b, spacing=None, thresholds=(), return_samples=False):
+    """mesh_distance of two mesh files (.ply, .glb, .obj; load_mesh_pair brings them into one frame)"""
+    (va, fa), (vb, fb) = load_mesh_pair(path_a, path_b)
+    return mesh_distance(va, fa, vb, fb, spacing, thresholds, return_samples)

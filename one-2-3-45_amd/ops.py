@@ -2,6 +2,7 @@
 Every function validates dtype / device / contiguity, passes raw pointers, and raises on a non-zero status."""
 import ctypes
 import functools
+from collections import namedtuple
 import threading
 
 import numpy as np
@@ -1172,6 +1173,146 @@ def mesh_cleanup(verts_idx, tris, opts, blob, vol_cl, resolution, level=0.0, bou
         verts_idx, info["project"] = mesh_project(blob, vol_cl, verts_idx, resolution, opts.project_iterations, level=level, max_move=opts.project_max_move,
                                                   bound_min=bound_min, bound_max=bound_max, precision=precision)
     return verts_idx, tris, info
+
+
+# ---------------------------------------------------------------------------------------------------------- mesh-to-mesh distance
+_DISTANCE_STATS_BYTES = 128         # include/o2345.h: fp64 [11] + uint64 [5]
+_DISTANCE_EXHAUSTIVE_BELOW = 64     # a target with fewer triangles is searched exhaustively: a grid costs more launches than it saves
+
+# a target mesh's uniform grid (ops.mesh_distance_grid): the device buffer, the max_cells it was sized for, and what the count pass reported
+MeshGrid = namedtuple("MeshGrid", "buffer max_cells entries dims cell degenerate")
+
+
+def _distance_spacing(spacing):
+    spacing = mesh_io._check_spacing(spacing)
+    return 0.0 if spacing is None else spacing
+
+
+@_on_device
+def mesh_surface_samples(verts, tris, spacing=None):
+    """Area-weighted samples of a mesh's surface on the device (== mesh_io.surface_samples, to the last bit; definitions in csrc/mesh_distance.hip).  verts
+    fp64 [N,3], tris [M,3] int32 / int64, ``spacing`` None (one sample per triangle) or a finite float > 0 -> (points fp64 [n,3], weight fp64 [n], triangle
+    int32 [n]), triangle-major.  One synchronisation, for the count; raises on 2^28 samples or more, a non-finite coordinate, an index out of range."""
+    spacing = _distance_spacing(spacing)
+    tp, ib = _triangles(tris, "mesh_surface_samples")
+    _vertices(verts, "mesh_surface_samples")
+    L = _lib.lib()
+    nv, nt, dev = verts.shape[0], tris.shape[0], verts.device
+    wsb = L.o2345_mesh_samples_workspace_bytes(nt)
+    ws = _workspace(wsb, dev, "mesh_samples")
+    n = ctypes.c_longlong()
+    check(L.o2345_mesh_samples_count(_p(verts, torch.float64), tp, ib, nv, nt, spacing, _p(ws, torch.uint8), wsb, ctypes.byref(n), _stream()), "mesh_samples_count")
+    points = torch.empty(n.value, 3, dtype=torch.float64, device=dev)
+    weight = torch.empty(n.value, dtype=torch.float64, device=dev)
+    triangle = torch.empty(n.value, dtype=torch.int32, device=dev)
+    check(L.o2345_mesh_samples_emit(_p(verts, torch.float64), tp, ib, nv, nt, _p(ws, torch.uint8), n.value, _p(points, torch.float64), _p(weight, torch.float64),
+                                    _p(triangle, torch.int32), _stream()), "mesh_samples_emit")
+    return points, weight, triangle
+
+
+@_on_device
+def mesh_distance_grid(verts, tris, cell=None, max_cells=None):
+    """The uniform grid over a target mesh that ops.mesh_closest_triangle walks (definitions in csrc/mesh_distance.hip) -> MeshGrid.  ``cell``: the cell
+    edge in the units of ``verts`` (None: about as many cells as triangles with an area); ``max_cells`` (None: max(2^20, 2 M), at most 2^24) bounds the
+    number of cells, and with it the memory: an edge that would need more, or more than 256 cells along an axis, is enlarged -- ``MeshGrid.cell`` and
+    ``.dims`` say what is in use.  The choice changes the speed of a query, never its result.  One synchronisation, for the count; raises on a non-finite
+    coordinate, an index out of range, a target without a triangle that has an area."""
+    if cell is not None and not (np.isfinite(cell) and cell > 0):
+        raise ValueError(f"mesh_distance_grid: cell must be None or a finite float > 0, got {cell!r}")
+    tp, ib = _triangles(tris, "mesh_distance_grid")
+    _vertices(verts, "mesh_distance_grid")
+    L = _lib.lib()
+    nv, nt, dev = verts.shape[0], tris.shape[0], verts.device
+    max_cells = min(2 ** 24, max(2 ** 20, 2 * nt)) if max_cells is None else int(max_cells)
+    wsb = L.o2345_mesh_distance_grid_workspace_bytes(nt, max_cells)
+    if not wsb:
+        raise ValueError(f"mesh_distance_grid: bad sizes ({nt} triangles, max_cells = {max_cells}: 1 .. 2^24)")
+    ws = _workspace(wsb, dev, "mesh_distance_grid")
+    ne, ndeg, dims, edge = ctypes.c_longlong(), ctypes.c_longlong(), (ctypes.c_int * 3)(), ctypes.c_double()
+    check(L.o2345_mesh_distance_grid_count(_p(verts, torch.float64), tp, ib, nv, nt, 0.0 if cell is None else float(cell), max_cells, _p(ws, torch.uint8), wsb,
+                                           ctypes.byref(ne), ctypes.byref(ndeg), dims, ctypes.byref(edge), _stream()), "mesh_distance_grid_count")
+    nbytes = L.o2345_mesh_distance_grid_bytes(max_cells, ne.value)
+    buf = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    check(L.o2345_mesh_distance_grid_emit(_p(verts, torch.float64), tp, ib, nv, nt, max_cells, _p(ws, torch.uint8), ne.value, _p(buf, torch.uint8), nbytes,
+                                          _stream()), "mesh_distance_grid_emit")
+    return MeshGrid(buf, max_cells, ne.value, tuple(dims), edge.value, ndeg.value)
+
+
+@_on_device
+def mesh_closest_triangle(points, verts, tris, grid=None):
+    """For every point its closest triangle of a target mesh on the device (== mesh_io.closest_triangles, to the last bit) -> (d2 fp64 [n], nearest int32
+    [n]): the squared distance and the smallest index among the triangles that attain it; +inf and -1 where the target has no triangle with an area.
+    points fp64 [n,3]; ``grid``: a MeshGrid of the same ``verts`` and ``tris`` (ops.mesh_distance_grid), or None for the exhaustive search -- the same
+    bits either way.  No synchronisation."""
+    tp, ib = _triangles(tris, "mesh_closest_triangle")
+    _vertices(verts, "mesh_closest_triangle")
+    _vertices(points, "mesh_closest_triangle")
+    n, dev = points.shape[0], points.device
+    d2 = torch.empty(n, dtype=torch.float64, device=dev)
+    nearest = torch.empty(n, dtype=torch.int32, device=dev)
+    gp, gb, gm = (_p(grid.buffer, torch.uint8), grid.buffer.numel(), grid.max_cells) if grid is not None else (None, 0, 0)
+    check(_lib.lib().o2345_mesh_distance_query(_p(points, torch.float64), n, _p(verts, torch.float64), tp, ib, verts.shape[0], tris.shape[0], gp, gb, gm,
+                                               _p(d2, torch.float64), _p(nearest, torch.int32), _stream()), "mesh_distance_query")
+    return d2, nearest
+
+
+@_on_device
+def mesh_distance_stats(d2, nearest, weight, thresholds=(), target=None, out=None):
+    """The summary of one direction on the device -> the 128-byte stats block (uint8 [128], or ``out``): sums, the largest d2 as its bit pattern, counts;
+    ``target`` = (verts, tris) adds the target's counters.  The same bytes on every run; no synchronisation.  ops.distance_summary reads it on the host."""
+    th = np.ascontiguousarray(mesh_io._check_thresholds(thresholds), np.float64)
+    L = _lib.lib()
+    n, dev = d2.shape[0], d2.device
+    wsb = L.o2345_mesh_distance_reduce_workspace_bytes(n)
+    ws = _workspace(wsb, dev, "mesh_distance_reduce")
+    stats = torch.empty(_DISTANCE_STATS_BYTES, dtype=torch.uint8, device=dev) if out is None else out
+    tv, (tp, ib), tnv, tnt = (None, (None, 4), 0, 0) if target is None else (target[0], _triangles(target[1], "mesh_distance_stats"), target[0].shape[0], target[1].shape[0])
+    check(L.o2345_mesh_distance_reduce(_p(d2, torch.float64), _p(nearest, torch.int32), _p(weight, torch.float64), n, th.ctypes.data_as(ctypes.c_void_p), len(th),
+                                       _p(tv, torch.float64), tp, ib, tnv, tnt, _p(ws, torch.uint8), wsb, _p(stats, torch.uint8), _stream()), "mesh_distance_reduce")
+    return stats
+
+
+def distance_summary(stats, n_thresholds, target_triangles=None):
+    """The stats block of o2345_mesh_distance_reduce (128 bytes, on the host) -> (the summary dict of mesh_io.distance_summary, the target's degenerate
+    triangles); raises on a target without a usable triangle."""
+    raw = np.ascontiguousarray(np.asarray(stats).reshape(-1)[:_DISTANCE_STATS_BYTES])
+    f, u = raw[:88].view(np.float64), raw[88:].view(np.uint64)
+    n, unmatched, degenerate, bad = int(u[1]), int(u[2]), int(u[3]), int(u[4])
+    if bad:
+        raise RuntimeError(f"o2345 mesh_distance: {bad} target triangles have an index out of range or a non-finite coordinate")
+    if unmatched:
+        raise RuntimeError(f"o2345 mesh_distance: {unmatched} of {n} samples found no triangle: the target has no triangle with an area"
+                           + (f" ({target_triangles} triangles, {degenerate} degenerate)" if target_triangles is not None else ""))
+    W = float(f[0])
+    div = lambda s: float(s) / W if W > 0 else float("nan")
+    return {"mean": div(f[1]), "rms": float(np.sqrt(div(f[2]))) if W > 0 else float("nan"), "max": float(np.sqrt(u[0:1].view(np.float64)[0])),
+            "within": [div(f[3 + k]) for k in range(n_thresholds)], "samples": n, "area": W}, degenerate
+
+
+def mesh_distance(va, ta, vb, tb, spacing=None, thresholds=(), return_samples=False, cell=None):
+    """Distance between mesh A (under test) and mesh B (the reference) as surfaces, on the device -> the dict of mesh_io.mesh_distance (its host twin):
+    one-sided summaries "a_to_b" / "b_to_a" (mean, rms, max, within, samples, area), "chamfer", "hausdorff", "precision" / "recall" / "fscore" per
+    threshold, "degenerate_targets".  va / vb fp64 [N,3], ta / tb [M,3] int32 / int64 on one device.  Per direction: samples at ``spacing``
+    (mesh_surface_samples), the target's grid (mesh_distance_grid with ``cell``; a target of fewer than 64 triangles is searched exhaustively), the query,
+    the summary; ONE read-back of the two stats blocks at the end (the counts of the samples and grids synchronise before it).  d2 and nearest equal the
+    twin's to the last bit, the sums to 1e-12.  ``return_samples`` adds "samples": {"a", "b"} -> {"points", "weight", "triangle", "d2", "nearest"},
+    device tensors."""
+    th = mesh_io._check_thresholds(thresholds)
+    stats = torch.empty(2, _DISTANCE_STATS_BYTES, dtype=torch.uint8, device=va.device)
+    samples = {}
+    for k, (name, (v, t), (tv, tt)) in enumerate((("a", (va, ta), (vb, tb)), ("b", (vb, tb), (va, ta)))):
+        points, weight, triangle = mesh_surface_samples(v, t, spacing)
+        grid = mesh_distance_grid(tv, tt, cell) if tt.shape[0] >= _DISTANCE_EXHAUSTIVE_BELOW else None
+        d2, nearest = mesh_closest_triangle(points, tv, tt, grid)
+        mesh_distance_stats(d2, nearest, weight, th, target=(tv, tt), out=stats[k])
+        samples[name] = {"points": points, "weight": weight, "triangle": triangle, "d2": d2, "nearest": nearest}
+    host = stats.cpu().numpy()
+    a_to_b, deg_b = distance_summary(host[0], len(th), tb.shape[0])
+    b_to_a, deg_a = distance_summary(host[1], len(th), ta.shape[0])
+    out = mesh_io.distance_report(a_to_b, b_to_a, th, deg_a, deg_b)
+    if return_samples:
+        out["samples"] = samples
+    return out
 
 
 # ---------------------------------------------------------------------------------------------------------- texture atlas

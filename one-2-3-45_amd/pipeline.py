@@ -317,6 +317,33 @@ def export_mesh_asset(path, wt, vol, proj, cam_pos, resolution, scale_mat=None, 
                                 vertex_colors=m.rgb if m.verts_idx.shape[0] else None, normals=m.grad if normals else None, texture=m.texture)
 
 
+def _device_mesh(mesh, dev):
+    """(verts, tris) as device tensors or host arrays -> (verts fp64 [N,3], tris int32 / int64 [M,3]) contiguous on ``dev``"""
+    v, t = mesh
+    v = v if torch.is_tensor(v) else torch.from_numpy(np.ascontiguousarray(np.asarray(v, np.float64)))
+    if not torch.is_tensor(t):
+        t = np.asarray(t)
+        t = torch.from_numpy(np.ascontiguousarray(t if t.dtype in (np.int32, np.int64) else t.astype(np.int64)))
+    return v.to(dev).contiguous(), t.to(dev).contiguous()
+
+
+# reconstruct_folder's mesh_error report: samples every half grid spacing, F-score at a quarter, a half, one and two spacings
+MESH_ERROR_SPACING = 0.5
+MESH_ERROR_THRESHOLDS = (0.25, 0.5, 1.0, 2.0)
+
+
+@torch.no_grad()
+def mesh_distance(a, b, spacing=None, thresholds=(), return_samples=False):
+    """Distance between two meshes as surfaces on the device (ops.mesh_distance; definitions in mesh_io.mesh_distance, its host twin): ``a`` (the mesh
+    under test) and ``b`` (the reference) are (verts [N,3], tris [M,3]) pairs of device tensors or host arrays -- host arrays are uploaded, to the device
+    of the first device tensor among the four, else the current one.  -> dict(a_to_b, b_to_a: {mean, rms, max, within, samples, area}; chamfer;
+    hausdorff; thresholds, precision, recall, fscore; degenerate_targets).  ``spacing`` None: one sample per triangle."""
+    dev = next((x.device for x in (*a, *b) if torch.is_tensor(x) and x.is_cuda), None)
+    dev = torch.device("cuda", torch.cuda.current_device()) if dev is None else dev
+    (va, ta), (vb, tb) = _device_mesh(a, dev), _device_mesh(b, dev)
+    return ops.mesh_distance(va, ta, vb, tb, spacing, thresholds, return_samples)
+
+
 def _surface_view(wt, vol, proj, cam_pos, u, flags, intrinsic, c2w, H, W, near, far, stride, refine, background):
     """one image of render_surface from a lattice and its brick flags"""
     dev = u.device
@@ -388,7 +415,7 @@ def _write_previews(wt, vol, proj, cam_pos, u, s, n, folder):
 
 @torch.no_grad()
 def reconstruct_folder(root_dir, name, wt, out_ply, D=96, resolution=256, render_val_image=False, output_format=None, min_component_faces=None,
-                       keep_largest=None, smooth_iterations=None, decimate_cell=None, project_iterations=None, texture_texel=None, preview_views=None):
+                       keep_largest=None, smooth_iterations=None, decimate_cell=None, project_iterations=None, texture_texel=None, preview_views=None, mesh_error=None):
     """run.py's reconstruction stage without the reference tree: Zero123-style folder (dataset.SceneFolder) -> coloured mesh (binary PLY in
     the original frame), optionally the val image of the target view.  ``output_format`` ".obj" / ".glb" (run.py --output_format) also writes
     ``mesh<ext>`` next to ``out_ply`` in the asset frame, from the same device buffers.  The mesh options are extract_mesh's.  Returns
@@ -399,7 +426,10 @@ def reconstruct_folder(root_dir, name, wt, out_ply, D=96, resolution=256, render
     or None when no textured asset was written.  ``preview_views`` (None: the config default O2345_PREVIEW_VIEWS, 0 = off: nothing is launched and the
     result keeps its keys) = n >= 1: n surface renders (render_surface on the lattice the mesh was extracted from) written as ``preview_000.png`` ... next to
     the PLY -- view 0 is the folder's query camera, the others an orbit around the origin at its distance and elevation about its up axis; the result's
-    "previews" is the list of {path, color, normal, depth, c2w}."""
+    "previews" is the list of {path, color, normal, depth, c2w}.  ``mesh_error`` (None: the config default O2345_MESH_ERROR, off: nothing is launched and
+    the result has no new key): the result gains "mesh_error", mesh_distance between the final mesh (A) and the raw marching-cubes mesh before the
+    clean-up chain (B, extracted again from the same lattice), in index coordinates -- units of the extraction grid's spacing -- with samples every 0.5
+    and thresholds 0.25, 0.5, 1 and 2.  "a_to_b" is the geometric error of what was kept; "b_to_a" also contains whatever the component filter dropped."""
     import os
     from . import dataset, mesh_io
     if output_format not in (None, ".ply", ".obj", ".glb"):
@@ -422,6 +452,9 @@ def reconstruct_folder(root_dir, name, wt, out_ply, D=96, resolution=256, render
         out["asset"] = os.path.join(os.path.dirname(str(out_ply)), "mesh" + output_format)
         mesh_io.export_asset(out["asset"], m.verts_idx, m.tris, resolution, scale_mat=s["scale_mat"], trans_mat=s["trans_mat"], vertex_colors=rgb,
                              texture=m.texture)
+    if config.mesh_error(mesh_error):
+        raw_verts, raw_tris = ops.marching_cubes(m.u, 0.0)                # what _mesh_fields meshed before its clean-up chain: the same lattice, the same bits
+        out["mesh_error"] = ops.mesh_distance(m.verts_idx, m.tris, raw_verts, raw_tris, MESH_ERROR_SPACING, MESH_ERROR_THRESHOLDS)
     if previews:
         out["previews"] = _write_previews(wt, vol, proj, cam_pos, m.u, s, previews, os.path.dirname(str(out_ply)))
     if render_val_image:

@@ -1,0 +1,198 @@
+"""CPU: the host twin of the mesh distance (mesh_io.surface_samples / closest_triangles / mesh_distance: the definition of what csrc/mesh_distance.hip
+computes), the unit's workspace sizes, its exported symbols and its kernels' resource usage.  No GPU needed."""
+import ctypes
+import importlib
+import math
+
+import numpy as np
+import pytest
+
+import mesh_distance_util as U
+import resource_usage
+
+mesh_io = importlib.import_module("one-2-3-45_amd.mesh_io")
+_lib = importlib.import_module("one-2-3-45_amd._lib")
+
+TRI = (np.array([[0.0, 0.0, 0.0], [3.0, 0.0, 0.0], [1.0, 1.0, 0.0]]), np.array([[0, 1, 2]]))          # longest edge 3: L2 = 9, area 1.5
+
+
+def bits(a, b):
+    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+    return a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes()
+
+
+@pytest.mark.parametrize("spacing, k", [(None, 1), (3.0, 1), (1.5, 2), (1.4999, 3), (1.0, 3), (0.99, 4), (1e-3, 64), (3.0 / 64, 64), (3.0 / 63, 63)])
+def test_sample_counts_weights_and_positions(spacing, k):
+    """k^2 samples per triangle; at spacing 1.5 (k spacing)^2 equals L2 = 9 exactly for k = 2, which must not go up; the weights sum to the area; every
+    sample lies strictly inside its triangle"""
+    v, f = TRI
+    assert mesh_io.sample_levels(v, f, spacing).tolist() == [k]
+    pts, w, tri = mesh_io.surface_samples(v, f, spacing)
+    assert pts.shape == (k * k, 3) and w.shape == (k * k,) and tri.dtype == np.int32 and not tri.any()
+    assert abs(math.fsum(w) - 1.5) <= 1e-15 * 1.5 and (w == w[0]).all()
+    bary = np.linalg.solve(np.vstack([v[:, :2].T, np.ones(3)]), np.vstack([pts[:, :2].T, np.ones(k * k)]))
+    assert (bary > 0).all() and (pts[:, 2] == 0).all()
+    wt = mesh_io.sample_weights(k)
+    assert (wt > 0).all() and len({tuple(r) for r in wt.tolist()}) == k * k
+    assert np.abs(bary.T - wt).max() < 1e-12
+
+
+def test_samples_are_triangle_major_and_zero_area_triangles_keep_theirs():
+    v = np.array([[0.0, 0, 0], [2, 0, 0], [0, 2, 0], [1, 0, 0], [5, 5, 5]])
+    f = np.array([[0, 1, 2], [0, 3, 1], [4, 4, 4], [0, 1, 2]])                      # a proper one, a collinear one, a repeated index, the first again
+    pts, w, tri = mesh_io.surface_samples(v, f, 1.0)
+    k = mesh_io.sample_levels(v, f, 1.0)
+    assert k.tolist() == [3, 2, 1, 3] and tri.tolist() == [0] * 9 + [1] * 4 + [2] + [3] * 9
+    assert (w[9:14] == 0).all() and (w[:9] > 0).all() and bits(pts[:9], pts[14:]) and bits(pts[13], v[4])
+
+
+def test_parallel_squares_are_a_quarter_apart_to_the_bit():
+    """A's samples lie at z = 0 exactly, so every d2 of theirs is 0.0625 to the bit at any level.  B's sit at (w0 + w1 + w2) 0.25, which is 0.25 to the bit
+    where the rounded weights add up to 1 exactly -- levels 1 and 3 (no spacing; 0.125) -- and one ulp below it for 32 of the 512 samples at level 4
+    (spacing 0.1): the sample point is a rounded combination, as in the self-distance below."""
+    a, b = U.square(0.0), U.square(0.25)
+    for spacing, n in ((None, 32), (0.125, 288)):
+        r = mesh_io.mesh_distance(*a, *b, spacing=spacing, thresholds=(0.2, 0.25, 0.3), return_samples=True)
+        for side in ("a", "b"):
+            assert (r["samples"][side]["d2"] == 0.0625).all() and r["samples"][side]["d2"].size == n
+        for side in ("a_to_b", "b_to_a"):
+            assert r[side]["mean"] == 0.25 and r[side]["rms"] == 0.25 and r[side]["max"] == 0.25 and r[side]["within"] == [0.0, 1.0, 1.0]
+            assert abs(r[side]["area"] - 1.0) < 1e-15 and r[side]["samples"] == n
+        assert r["chamfer"] == 0.25 and r["hausdorff"] == 0.25 and r["precision"] == [0.0, 1.0, 1.0] and r["fscore"] == [0.0, 1.0, 1.0]
+    r = mesh_io.mesh_distance(*a, *b, spacing=0.1, thresholds=(0.2, 0.25, 0.3), return_samples=True)
+    assert (r["samples"]["a"]["d2"] == 0.0625).all() and r["samples"]["a"]["d2"].size == 512
+    assert r["a_to_b"]["mean"] == 0.25 and r["a_to_b"]["rms"] == 0.25 and r["a_to_b"]["max"] == 0.25 and r["a_to_b"]["within"] == [0.0, 1.0, 1.0]
+    assert np.abs(r["samples"]["b"]["d2"] - 0.0625).max() <= 0.0625 * 2.0 ** -51 and abs(r["b_to_a"]["mean"] - 0.25) <= 0.25 * 2.0 ** -52
+
+
+def test_a_mesh_against_itself_swap_and_face_permutation():
+    (va, fa), (vb, fb) = U.spheres()
+    r = mesh_io.mesh_distance(va, fa, va, fa, spacing=0.75)
+    assert 0.0 < r["hausdorff"] <= 1e-13 * 24.0                      # the sample is a rounded combination of the corners: small, not zero
+    ab = mesh_io.mesh_distance(va, fa, vb, fb, thresholds=(0.3,))
+    ba = mesh_io.mesh_distance(vb, fb, va, fa, thresholds=(0.3,))
+    assert ab["a_to_b"] == ba["b_to_a"] and ab["b_to_a"] == ba["a_to_b"] and ab["precision"] == ba["recall"] and ab["fscore"] == ba["fscore"]
+    assert ab["degenerate_targets"] == {"a": 0, "b": 0}
+    q = U.all_queries()[::7]
+    d2, nearest, _, ties, _ = mesh_io.closest_triangles(q, vb, fb)
+    perm = np.random.default_rng(3).permutation(len(fb))
+    d2p, nearestp, _, tiesp, _ = mesh_io.closest_triangles(q, vb, fb[perm])
+    assert bits(d2, d2p) and bits(ties, tiesp) and (ties > 1).sum() > 50
+    # the permuted answer is the first, in the permuted order, of the same set of minimisers: of equal distance to the original's
+    check = mesh_io.closest_point_triangle(q, vb[fb[perm[nearestp], 0]], vb[fb[perm[nearestp], 1]], vb[fb[perm[nearestp], 2]])[0]
+    assert bits(check, d2)
+    inv = np.argsort(perm)
+    single = ties == 1
+    assert (perm[nearestp[single]] == nearest[single]).all() and (nearestp <= inv[nearest]).all()
+
+
+def test_query_sets_reach_every_region_and_tie():
+    """the conditions the GPU comparisons rely on: every branch of the region walk decides some query's nearest triangle, and many queries have several
+    triangles at the bit-identical minimum"""
+    d2, nearest, region, ties = U.twin_answers()
+    sets = U.query_sets()
+    assert sets["a_samples"].shape == (8616, 3) and d2.shape == (U.all_queries().shape[0],)
+    counts = np.bincount(region, minlength=7)
+    assert counts.shape == (7,) and (counts >= 8).all(), counts
+    assert int((ties > 1).sum()) >= 100
+    lo = 8616
+    assert (ties[lo:lo + len(sets["b_vertices"])] > 1).all()          # a vertex is equally far (0) from every triangle around it
+
+
+def test_degenerate_targets_are_counted_and_left_out():
+    v, f = U.square(0.0)
+    f2 = np.concatenate([[[0, 0, 1], [0, 1, 2]], f])                   # a repeated index; three collinear lattice points
+    q = np.array([[0.1, 0.2, 0.5], [2.0, 2.0, 0.0]])
+    d2, nearest, _, _, deg = mesh_io.closest_triangles(q, v, f2)
+    ref = mesh_io.closest_triangles(q, v, f)
+    assert deg == 2 and bits(d2, ref[0]) and (nearest == ref[1] + 2).all() and d2[0] == 0.25 and d2[1] == 2.0
+
+
+@pytest.mark.parametrize("what, call", [
+    ("non-finite", lambda v, f: mesh_io.mesh_distance(np.where(np.arange(len(v))[:, None] == 3, np.nan, v), f, v, f)),
+    ("index outside", lambda v, f: mesh_io.mesh_distance(v, np.concatenate([f, [[0, 1, len(v)]]]), v, f)),
+    ("no triangle with an area", lambda v, f: mesh_io.mesh_distance(v, f, v, np.array([[0, 0, 1], [2, 2, 2]]))),
+    ("thresholds", lambda v, f: mesh_io.mesh_distance(v, f, v, f, thresholds=[0.1] * 9)),
+    ("spacing", lambda v, f: mesh_io.mesh_distance(v, f, v, f, spacing=0.0)),
+    ("spacing", lambda v, f: mesh_io.mesh_distance(v, f, v, f, spacing=-1.0)),
+    ("spacing", lambda v, f: mesh_io.surface_samples(v, f, float("inf"))),
+    ("samples", lambda v, f: mesh_io.surface_samples(v[[0, 4, 20]] * 1e3, np.tile([[0, 1, 2]], (2 ** 16, 1)), 1e-6)),          # 2^16 triangles at k = 64: 2^28
+])
+def test_bad_input_raises_and_names_the_cause(what, call):
+    v, f = U.square(0.0)
+    with pytest.raises(ValueError, match=what):
+        call(v, f)
+
+
+def test_compare_mesh_files_across_formats(tmp_path):
+    (va, fa), _ = U.spheres()
+    ply = str(tmp_path / "a.ply")
+    mesh_io.write_ply_numpy(ply, va.astype(np.float32), fa.astype(np.int32))
+    for ext in (".glb", ".obj"):
+        other = mesh_io.convert_mesh(ply, str(tmp_path / ("a" + ext)))
+        for pair in ((ply, other), (other, ply)):
+            r = mesh_io.compare_mesh_files(*pair, spacing=1.0, thresholds=(1e-4,))
+            assert r["hausdorff"] <= 1e-6 * 24.0 and r["precision"] == [1.0] and r["a_to_b"]["samples"] >= len(fa)
+    r = mesh_io.compare_mesh_files(ply, ply)
+    assert r["a_to_b"]["samples"] == len(fa) and r["hausdorff"] <= 1e-6 * 24.0
+
+
+# ---- the device unit, as far as this machine can see it ---------------------------------------------------------------------------------------------
+NEW_SYMBOLS = ("o2345_mesh_samples_workspace_bytes", "o2345_mesh_samples_count", "o2345_mesh_samples_emit", "o2345_mesh_distance_grid_workspace_bytes",
+               "o2345_mesh_distance_grid_bytes", "o2345_mesh_distance_grid_count", "o2345_mesh_distance_grid_emit", "o2345_mesh_distance_query",
+               "o2345_mesh_distance_reduce_workspace_bytes", "o2345_mesh_distance_reduce")
+
+
+def test_new_entries_are_declared_exported_and_additive():
+    protos = _lib.parse_header()
+    lib = _lib.lib()
+    for name in NEW_SYMBOLS:
+        assert name in protos and getattr(lib, name) is not None, name
+        assert name in open(_lib.HEADER).read().split("int o2345_version(void);")[0], f"{name} is missing from the header's list of additive entries"
+    assert lib.o2345_version() == 210 and _lib.ABI_VERSION == 210
+    assert protos["o2345_mesh_samples_workspace_bytes"][0] is ctypes.c_size_t and protos["o2345_mesh_distance_query"][0] is ctypes.c_int
+
+
+def test_workspace_sizes_are_pinned():
+    """each is its unit's carver walk on a null base: a 128-byte head (two for the grid), then arrays padded to 16 bytes"""
+    lib = _lib.lib()
+    assert [lib.o2345_mesh_samples_workspace_bytes(n) for n in (0, 1, 1964, 500000)] == [128, 176, 15856, 4001120]
+    assert 15856 == 128 + 2 * 4 * 1964 + 16                                                        # totals, k^2 and offsets, one scan block
+    assert [lib.o2345_mesh_distance_grid_workspace_bytes(*a) for a in ((1964, 4096), (500000, 2 ** 20), (0, 1))] == [67824, 17279584, 336]
+    assert 67824 == 256 + 3 * 16400 + 16384 + 16 + 1968                                            # heads, three cell arrays of 4097, the long list, the scan, usable
+    assert [lib.o2345_mesh_distance_grid_bytes(*a) for a in ((4096, 0), (4096, 5000), (2 ** 20, 10 ** 6))] == [16528, 36528, 8194448]
+    assert [lib.o2345_mesh_distance_reduce_workspace_bytes(n) for n in (0, 1, 4096, 4097, 10 ** 6)] == [128, 224, 224, 304, 21696]
+    bad = [lib.o2345_mesh_samples_workspace_bytes(-1), lib.o2345_mesh_samples_workspace_bytes(2 ** 30), lib.o2345_mesh_distance_grid_workspace_bytes(10, 0),
+           lib.o2345_mesh_distance_grid_workspace_bytes(10, 2 ** 24 + 1), lib.o2345_mesh_distance_grid_workspace_bytes(-1, 16), lib.o2345_mesh_distance_grid_bytes(0, 0),
+           lib.o2345_mesh_distance_grid_bytes(16, 2 ** 31), lib.o2345_mesh_distance_grid_bytes(16, -1), lib.o2345_mesh_distance_reduce_workspace_bytes(2 ** 28),
+           lib.o2345_mesh_distance_reduce_workspace_bytes(-1)]
+    assert bad == [0] * len(bad)
+
+
+@pytest.mark.skipif(not resource_usage.HAVE_HIPCC, reason="needs hipcc")
+def test_kernels_use_no_scratch(tmp_path):
+    usage = resource_usage.kernel_usage("mesh_distance.hip", r"(\S+)", lambda m: m.group(1), tmp_path)
+    mine = {k: u for k, u in usage.items() if "k_md_" in k}
+    for stem in ("k_md_levels", "k_md_emit", "k_md_grid_init", "k_md_grid_bounds", "k_md_grid_head", "k_md_grid_register", "k_md_grid_rows",
+                 "k_md_grid_long_rows", "k_md_grid_finish", "k_md_query_grid", "k_md_query_all", "k_md_reduce", "k_md_reduce_final", "k_md_reduce_target"):
+        assert any(stem in k for k in mine), stem
+    assert len(usage) >= len(mine) + 3                               # the three scan kernels of mesh_common.h are instantiated here too
+    for name, u in usage.items():
+        assert u["ScratchSize"] == 0, (name, u)
+
+
+def test_command_line_tool_prints_the_twins_report(tmp_path, capsys):
+    import os
+    import sys
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
+    try:
+        tool = importlib.import_module("mesh_distance")
+    finally:
+        sys.path.pop(0)
+    a, b = U.square(0.0), U.square(0.25)
+    for name, (v, f) in (("a.ply", a), ("b.ply", b)):
+        mesh_io.write_ply_numpy(str(tmp_path / name), v.astype(np.float32), f.astype(np.int32))
+    out = tool.main([str(tmp_path / "a.ply"), str(tmp_path / "b.ply"), "--spacing", "0.125", "--threshold", "0.2", "--threshold", "0.25", "--host"])
+    import json
+    assert json.loads(capsys.readouterr().out) == out == mesh_io.mesh_distance(*a, *b, 0.125, (0.2, 0.25))
+    assert out["hausdorff"] == 0.25 and out["fscore"] == [0.0, 1.0]
