@@ -7,8 +7,11 @@
  * (paths relative to /root/reference/reconstruction).
  *
  * Conventions
- *   - extern "C", plain pointers and sizes, no torch / C++ types.  All pointers are DEVICE pointers unless the name
- *     ends in _host.  The caller owns every buffer; the library never allocates, frees or retains them.
+ *   - extern "C", plain pointers and sizes, no torch / C++ types.  A pointer is a HOST pointer if and only if its name
+ *     ends in _host, or the function's name ends in _host, or it points to a struct (O2345RenderIO* io); every other
+ *     pointer, the struct's fields among them, is a DEVICE pointer.  A binding reads this, and every pointer's element
+ *     type, from the declarations below (one-2-3-45_amd/_lib.py does).  The caller owns every buffer; the library
+ *     never allocates, frees or retains them.
  *   - every function returns 0 on success, a negative code on error; o2345_last_error() (thread-local) explains.
  *   - `stream` is a hipStream_t (NULL = default stream).  Functions are asynchronous unless stated otherwise and
  *     re-entrant (one Python thread per device under nn.DataParallel is fine).
@@ -444,8 +447,8 @@ int o2345_mesh_decimate_emit(const double* verts, const void* tris, int index_by
  * No host synchronisation: all rounds are queued at once, the counts stay on the device.  A non-zero first counter means bad input: the caller raises
  * (the affected vertices stall, nothing is dereferenced through them).  Errors: bad arguments, a workspace that is too small. */
 size_t o2345_mesh_project_workspace_bytes(long long nv);
-int o2345_mesh_project(const float* blob, const float* vol_cl, int D, int sdf_mode, const double* verts, long long nv, int grid_R, const float* bound_min,
-                       const float* bound_max, int iterations, double level, double tol, double max_step, double max_move, void* workspace,
+int o2345_mesh_project(const float* blob, const float* vol_cl, int D, int sdf_mode, const double* verts, long long nv, int grid_R, const float* bound_min_host,
+                       const float* bound_max_host, int iterations, double level, double tol, double max_step, double max_move, void* workspace,
                        size_t workspace_bytes, double* verts_out, void* stats, void* stream);
 
 /* ---- mesh serialisation (replaces the numpy / trimesh tail of validate_mesh and validate_colored_mesh,
@@ -453,8 +456,8 @@ int o2345_mesh_project(const float* blob, const float* vol_cl, int D, int sdf_mo
  * verts_idx: device fp64 [n,3] index coordinates on an R^3 grid (o2345_marching_cubes_emit); bound_min/max [3], scale_mat and
  * trans_mat (4x4 row-major fp32, may be NULL) are HOST arrays; rgb device fp32 [n,3] or NULL.
  * vertex_records: n x (3 x float32 [+ rgba uint8]) = 16 (12 without colours) bytes each; face_records: m x (uint8 3, 3 x int32). */
-int o2345_mesh_pack_vertices(const double* verts_idx, long long n, int grid_R, const float* bound_min, const float* bound_max,
-                             const float* scale_mat, const float* trans_mat, const float* rgb, uint8_t* vertex_records, void* stream);
+int o2345_mesh_pack_vertices(const double* verts_idx, long long n, int grid_R, const float* bound_min_host, const float* bound_max_host,
+                             const float* scale_mat_host, const float* trans_mat_host, const float* rgb, uint8_t* vertex_records, void* stream);
 int o2345_mesh_pack_faces(const void* tris, int index_bytes, long long m, uint8_t* face_records, void* stream);
 /* extract_geometry's index -> world step on the device, in place and in fp64 (sparse_neus_renderer.py:936: vertices / (R - 1) * (bound_max - bound_min)
  * + bound_min; the same IEEE expression numpy evaluates): verts [n,3] device fp64; extent = bound_max - bound_min (the reference subtracts the fp32 bounds,
@@ -477,8 +480,8 @@ int o2345_ply_records_host(const double* vertices, long long n, const uint8_t* c
  * positions (glTF's POSITION accessor needs them), from a two-stage reduction through `workspace` (o2345_mesh_bounds_workspace_bytes(n) bytes, 4-byte
  * aligned): deterministic, no floating-point atomics.  n = 0 writes nothing. */
 size_t o2345_mesh_bounds_workspace_bytes(long long n);
-int o2345_mesh_asset_vertices(const double* verts_idx, long long n, int grid_R, const float* bound_min, const float* bound_max, const float* scale_mat,
-                              const float* trans_mat, const float* rgb, const float* grad, float* positions, uint8_t* rgba, float* normals,
+int o2345_mesh_asset_vertices(const double* verts_idx, long long n, int grid_R, const float* bound_min_host, const float* bound_max_host, const float* scale_mat_host,
+                              const float* trans_mat_host, const float* rgb, const float* grad, float* positions, uint8_t* rgba, float* normals,
                               float* bounds, void* workspace, size_t workspace_bytes, void* stream);
 /* replaces utils/utils.py:41 (np.fliplr(mesh.faces)): tris device int32 / int64 [m,3] (index_bytes 4 / 8) -> indices uint32 [m,3], winding reversed. */
 int o2345_mesh_asset_indices(const void* tris, int index_bytes, long long m, uint32_t* indices, void* stream);
@@ -526,10 +529,10 @@ int o2345_obj_text_host(const float* positions, const uint8_t* rgba, const float
  * for o2345_mesh_asset_vertices.  Bounds and matrices as for o2345_mesh_pack_vertices. */
 size_t o2345_mesh_texture_texels(long long nt, int texel, int* width_host, int* height_host);
 int o2345_mesh_texture_points(const double* verts, long long nv, const void* tris, int index_bytes, long long nt, int texel, int grid_R,
-                              const float* bound_min, const float* bound_max, double* points_idx, float* points_world, void* stats, void* stream);
+                              const float* bound_min_host, const float* bound_max_host, double* points_idx, float* points_world, void* stats, void* stream);
 int o2345_mesh_texture_pack(const float* rgb, long long nt, int texel, uint8_t* image, void* stream);
 int o2345_mesh_texture_corners(const double* verts, long long nv, const void* tris, int index_bytes, long long nt, int texel, int grid_R,
-                               const float* bound_min, const float* bound_max, const float* scale_mat, const float* trans_mat, const float* grad,
+                               const float* bound_min_host, const float* bound_max_host, const float* scale_mat_host, const float* trans_mat_host, const float* grad,
                                float* positions, float* uv, float* normals, uint32_t* indices, float* bounds, void* workspace, size_t workspace_bytes,
                                void* stream);
 /* The records of the textured OBJ (none in the reference), for n = 3 nt unwelded vertices as written by mesh_texture_corners: n "v" records without
@@ -578,8 +581,8 @@ int o2345_obj_texture_text(const float* positions, const float* uv, const float*
 int o2345_surface_bricks(const float* u, int grid_R, double level, int inside_positive, uint8_t* flags, void* stream);
 size_t o2345_surface_trace_workspace_bytes(long long n);
 int o2345_surface_trace(const float* u, int grid_R, const uint8_t* flags, const float* rays_o, const float* rays_d, long long n, int img_h, int img_w,
-                        double t_near, double t_far, double stride, int refine, double level, int inside_positive, const float* bound_min,
-                        const float* bound_max, void* workspace, size_t workspace_bytes, float* depth, uint8_t* kind, float* point, void* stats,
+                        double t_near, double t_far, double stride, int refine, double level, int inside_positive, const float* bound_min_host,
+                        const float* bound_max_host, void* workspace, size_t workspace_bytes, float* depth, uint8_t* kind, float* point, void* stats,
                         void* stream);
 int o2345_camera_rays(const float* K_host, const float* c2w_host, int H, int W, float* rays_o, float* rays_d, void* stream);
 int o2345_surface_pack(const uint8_t* kind, const float* depth, const float* rgb, const float* grad, int H, int W, const uint8_t* background_host,
@@ -629,7 +632,7 @@ int o2345_mesh_distance_grid_emit(const double* verts, const void* tris, int ind
 int o2345_mesh_distance_query(const double* points, long long n, const double* verts, const void* tris, int index_bytes, long long nv, long long nt,
                               const void* grid, size_t grid_bytes, long long max_cells, double* d2, int* nearest, void* stream);
 size_t o2345_mesh_distance_reduce_workspace_bytes(long long n);
-int o2345_mesh_distance_reduce(const double* d2, const int* nearest, const double* weights, long long n, const double* thresholds, int n_thresholds,
+int o2345_mesh_distance_reduce(const double* d2, const int* nearest, const double* weights, long long n, const double* thresholds_host, int n_thresholds,
                                const double* verts, const void* tris, int index_bytes, long long nv, long long nt, void* workspace, size_t workspace_bytes,
                                void* stats, void* stream);
 /* Load every code object of the library on the current device now (the HIP runtime loads a translation unit's kernels at its first launch: 5 - 60 ms

@@ -39,6 +39,22 @@ def ply_header(n_vertices, n_faces, colors):
 _WARNED = False
 
 
+def _host_packer(what, instead):
+    """-> the binding (_lib) for a host-side packer of the library, or None after one warning.  FILE FORMATTING on the host, not device work: without a
+    loadable library (a machine that only converts meshes) the numpy writers produce the same bytes (tests/test_mesh_io.py), 6 - 8 ms slower per million
+    PLY records, seconds per million OBJ records.  Every compute op still refuses to run without the library."""
+    from . import _lib
+    try:
+        _lib.lib()
+        return _lib
+    except (RuntimeError, OSError, AttributeError) as e:
+        global _WARNED
+        if not _WARNED:
+            import warnings
+            warnings.warn(f"o2345 mesh_io.{what}: libo2345_hip.so is not loadable ({e}); {instead} (same bytes)")
+            _WARNED = True
+
+
 def write_records(path, vertex_records, face_records, colors):
     """vertex_records / face_records: contiguous uint8 arrays (16 or 12 bytes per vertex, 13 per face)."""
     vertex_records = np.ascontiguousarray(vertex_records, np.uint8).reshape(-1)
@@ -55,28 +71,17 @@ def write_ply(path, vertices, faces, vertex_colors=None):
     """Host arrays in (vertices [N,3] float, faces [M,3] int, vertex_colors [N,3|4] uint8 or None).  The two record arrays are packed by the library's
     host-side packer (o2345_ply_records_host: float64 -> float32, int64 -> int32, rgba; a few threads, no device work) -- numpy's 12 -> 13-byte row
     copies took 6 - 8 ms for the 1 M records of a 256^3 mesh, inside the reference's "export mesh time" bracket."""
-    import ctypes
-    from . import _lib
     v = np.ascontiguousarray(vertices, np.float64).reshape(-1, 3)
     f = np.ascontiguousarray(faces, np.int64).reshape(-1, 3)
     c = None if vertex_colors is None else np.ascontiguousarray(vertex_colors, np.uint8)
     if c is not None and (c.ndim != 2 or c.shape[0] != v.shape[0] or c.shape[1] not in (3, 4)):
         raise ValueError(f"write_ply: vertex_colors must be [N,3] or [N,4] uint8 for N = {v.shape[0]} vertices, got {c.shape}")
-    try:
-        L = _lib.lib()
-    except (RuntimeError, OSError, AttributeError) as e:
-        # FILE FORMATTING on the host, not device work: without a loadable library (a machine that only converts meshes) the numpy writer produces the
-        # same bytes (tests/test_mesh_io.py), 6 - 8 ms slower per million records.  Every compute op still refuses to run without the library.
-        global _WARNED
-        if not _WARNED:
-            import warnings
-            warnings.warn(f"o2345 mesh_io.write_ply: libo2345_hip.so is not loadable ({e}); writing the PLY with the numpy packer (same bytes)")
-            _WARNED = True
+    _lib = _host_packer("write_ply", "writing the PLY with the numpy packer")
+    if _lib is None:
         return write_ply_numpy(path, v, f, c)
     vrec = np.empty((v.shape[0], 16 if c is not None else 12), np.uint8)
     frec = np.empty((f.shape[0], 13), np.uint8)
-    P = lambda a: None if a is None or a.size == 0 else a.ctypes.data_as(ctypes.c_void_p)
-    _lib.check(L.o2345_ply_records_host(P(v), v.shape[0], P(c), 0 if c is None else c.shape[1], P(f), f.shape[0], P(vrec), P(frec)), "ply_records_host")
+    _lib.call("o2345_ply_records_host", v, v.shape[0], c, 0 if c is None else c.shape[1], f, f.shape[0], vrec, frec)
     write_records(path, vrec, frec, c is not None)
 
 
@@ -338,27 +343,18 @@ def write_obj(path, positions, faces, colors=None, normals=None):
     """Host arrays in (as write_glb), ALREADY in the asset frame -> vertex-coloured OBJ of fixed-width records ("v x y z [r g b]", "vn", "f a b c" or
     "f a//a b//b c//c", 1-based).  The text is packed by the library's host-side packer (o2345_obj_text_host; a few threads, no device work); without a
     loadable library the host formatter writes the same bytes, seconds slower per million records."""
-    import ctypes
-    from . import _lib
     p, f, c, nr = _host_mesh(positions, faces, colors, normals)
     K = obj_coordinate_digits(p)
-    try:
-        L = _lib.lib()
-    except (RuntimeError, OSError, AttributeError) as e:
-        global _WARNED
-        if not _WARNED:
-            import warnings
-            warnings.warn(f"o2345 mesh_io.write_obj: libo2345_hip.so is not loadable ({e}); formatting the OBJ on the host (same bytes)")
-            _WARNED = True
-        with open(path, "wb") as fh:
-            fh.write(obj_text_numpy(p, f, c, nr, K))
-        return
-    text = np.empty(obj_text_bytes(p.shape[0], f.shape[0], K, c is not None, nr is not None), np.uint8)
-    assert text.size == L.o2345_obj_text_bytes(p.shape[0], f.shape[0], K, int(c is not None), int(nr is not None))
-    P = lambda a: None if a is None or a.size == 0 else a.ctypes.data_as(ctypes.c_void_p)
-    _lib.check(L.o2345_obj_text_host(P(p), P(c), P(nr), p.shape[0], P(f), f.shape[0], K, P(text)), "obj_text_host")
+    _lib = _host_packer("write_obj", "formatting the OBJ on the host")
+    if _lib is None:
+        text = obj_text_numpy(p, f, c, nr, K)
+    else:
+        text = np.empty(obj_text_bytes(p.shape[0], f.shape[0], K, c is not None, nr is not None), np.uint8)
+        assert text.size == _lib.call("o2345_obj_text_bytes", p.shape[0], f.shape[0], K, int(c is not None), int(nr is not None))
+        _lib.call("o2345_obj_text_host", p, c, nr, p.shape[0], f, f.shape[0], K, text)
+        text = text.data
     with open(path, "wb") as fh:
-        fh.write(text.data)
+        fh.write(text)
 
 
 def read_obj(path):

@@ -1,5 +1,6 @@
 """Torch-tensor wrappers over the C ABI (include/o2345.h).  PyTorch is plumbing only: device memory + streams.
-Every function validates dtype / device / contiguity, passes raw pointers, and raises on a non-zero status."""
+Every library call goes through ``call``: _lib checks dtype / device / contiguity of every pointer and the range of every integer against the
+header's declaration, passes raw pointers, and raises on a non-zero status."""
 import ctypes
 import functools
 from collections import namedtuple
@@ -9,13 +10,11 @@ import numpy as np
 import torch
 
 from . import _lib, config, mesh_io
-from ._lib import check
 
 
-def _stream():
-    """The current HIP stream of the CURRENT device; every public op runs under _on_device, which makes the device of its
-    tensor arguments current first (the C side sizes persistent grids from hipGetDevice())."""
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+# No call below names its stream: _lib.call fills in the current HIP stream of the CURRENT device, and every public op runs under _on_device, which makes
+# the device of its tensor arguments current first (the C side sizes persistent grids from hipGetDevice()).
+call = _lib.call
 
 
 def _first_cuda_tensor(objs):
@@ -43,14 +42,6 @@ def _on_device(fn):
     return wrapped
 
 
-def _p(t, dtype=torch.float32):
-    if t is None:
-        return None
-    if not (t.is_cuda and t.is_contiguous() and t.dtype == dtype):
-        raise ValueError(f"expected contiguous cuda {dtype} tensor, got {t.dtype} {t.device} contiguous={t.is_contiguous()}")
-    return ctypes.c_void_p(t.data_ptr())
-
-
 def _f(t):
     return t.detach().to(torch.float32).contiguous()
 
@@ -60,16 +51,15 @@ def host_f32(a):                          # a tensor or an array -> a contiguous
 
 
 def _host3(v):
-    a = host_f32(v).reshape(-1)[:3]
-    return a, a.ctypes.data_as(ctypes.c_void_p)
+    return host_f32(v).reshape(-1)[:3]
 
 
 def _bounds(bound_min, bound_max, what):
-    """The box of a lattice, validated -> ((bound_min, its pointer), (bound_max, its pointer)): three float32 each, on the host."""
-    (bmin, pmin), (bmax, pmax) = _host3(bound_min), _host3(bound_max)
+    """The box of a lattice, validated -> (bound_min, bound_max): three float32 each, on the host."""
+    bmin, bmax = _host3(bound_min), _host3(bound_max)
     if bmin.shape != (3,) or bmax.shape != (3,) or not (np.isfinite(bmin).all() and np.isfinite(bmax).all() and (bmax > bmin).all()):
         raise ValueError(f"{what}: bound_max must be above bound_min on every axis, both finite, got {bound_min!r} and {bound_max!r}")
-    return (bmin, pmin), (bmax, pmax)
+    return bmin, bmax
 
 
 def _vertices(verts_idx, what=None):
@@ -125,7 +115,7 @@ def preload(device):
         if device in _preloaded:
             return
         with torch.cuda.device(device):
-            check(_lib.lib().o2345_preload(), "preload")
+            call("o2345_preload")
             if config.warm_aten():
                 _warm_aten(device)
         _preloaded.add(device)
@@ -160,13 +150,19 @@ def _workspace(nbytes, device, tag="ws"):
     """Scratch buffer per (purpose, device, stream): two streams of one device never share scratch memory.  Host threads are safe as long as each
     enqueues on its OWN stream: nn.DataParallel gives every replica its own device (its thread's key differs by device); two threads that launch onto
     ONE stream of ONE device would overwrite each other's scratch between launches -- code that runs replicas on one device (tests) gives each thread
-    its own stream."""
+    its own stream.  ``nbytes`` None: the buffer that is there, or None -- a reader, which allocates nothing."""
     key = (tag, str(device), torch.cuda.current_stream(device).cuda_stream)
     t = _ws_cache.get(key)
-    if t is None or t.numel() < nbytes:
+    if nbytes is not None and (t is None or t.numel() < nbytes):
         t = torch.empty(int(nbytes) + 256, dtype=torch.uint8, device=device)
         _ws_cache[key] = t
     return t
+
+
+def _scratch(entry, sizes, device, tag="ws"):
+    """-> (the scratch buffer of _workspace, its size): as many bytes as the library's ``entry`` (an o2345_*_workspace_bytes function) asks for ``sizes``."""
+    nbytes = call(entry, *sizes)
+    return _workspace(nbytes, device, tag), nbytes
 
 
 # ---------------------------------------------------------------------------------------------------------- cost volume
@@ -174,7 +170,7 @@ def _workspace(nbytes, device, tag="ws"):
 def nchw_to_nhwc(x):
     V, C, H, W = x.shape
     out = torch.empty(V, H, W, C, device=x.device, dtype=torch.float32)
-    check(_lib.lib().o2345_nchw_to_nhwc(_p(x), _p(out), V, C, H, W, _stream()), "nchw_to_nhwc")
+    call("o2345_nchw_to_nhwc", x, out, V, C, H, W)
     return out
 
 
@@ -191,13 +187,12 @@ def conv2d_pack(weight, precision=None):
     cout, cin, k, k2 = weight.shape
     if k != k2:
         raise ValueError("conv2d: square kernels only")
-    L = _lib.lib()
     if conv_x3(precision):
-        t = torch.empty(L.o2345_conv2d_x3_weight_floats(cin, k), dtype=torch.float32, device=weight.device)
-        check(L.o2345_conv2d_pack_weights_x3(_p(_f(weight)), cout, cin, k, _p(t), _stream()), "conv2d_pack_weights_x3")
+        t = torch.empty(call("o2345_conv2d_x3_weight_floats", cin, k), dtype=torch.float32, device=weight.device)
+        call("o2345_conv2d_pack_weights_x3", _f(weight), cout, cin, k, t)
     else:
         t = torch.empty(cin * k * k * cout, dtype=torch.float32, device=weight.device)
-        check(L.o2345_conv2d_pack_weights(_p(_f(weight)), cout, cin, k, _p(t), _stream()), "conv2d_pack_weights")
+        call("o2345_conv2d_pack_weights", _f(weight), cout, cin, k, t)
     return t
 
 
@@ -223,19 +218,16 @@ def conv2d(x, weight, bias=None, stride=1, in_scale_shift=None, slope=0.01, bn=N
             raise ValueError(f"conv2d: channels {c0}..{c0 + cin} do not fit a channel-last map with {pix_stride} channels")
     pad = k // 2
     Ho, Wo = (Hi + 2 * pad - k) // stride + 1, (Wi + 2 * pad - k) // stride + 1
-    L = _lib.lib()
     out = torch.empty(V, cout, Ho, Wo, dtype=torch.float32, device=x.device)
     ss = gamma = beta = ws = None
     eps, abs_gamma, wsb = 0.0, 0, 0
     if bn is not None:
         gamma, beta, eps, abs_gamma = bn
         ss = torch.empty(2 * cout, dtype=torch.float32, device=x.device)
-        wsb = L.o2345_conv2d_workspace_bytes(V, cout, Ho, Wo)
-        ws = _workspace(wsb, x.device, "conv2d")
-    fn = L.o2345_conv2d_x3 if conv_x3(precision) else L.o2345_conv2d
-    check(fn(_p(x), V, cin, Hi, Wi, int(pix_stride), c0, _p(in_scale_shift), float(slope), _p(packed if packed is not None else conv2d_pack(weight, precision)),
-             _p(None if bias is None else _f(bias)), cout, k, int(stride), _p(out), _p(None if gamma is None else _f(gamma)),
-             _p(None if beta is None else _f(beta)), float(eps), int(abs_gamma), _p(ss), _p(ws, torch.uint8), wsb, _stream()), "conv2d")
+        ws, wsb = _scratch("o2345_conv2d_workspace_bytes", (V, cout, Ho, Wo), x.device, "conv2d")
+    call("o2345_conv2d_x3" if conv_x3(precision) else "o2345_conv2d", x, V, cin, Hi, Wi, int(pix_stride), c0, in_scale_shift, float(slope),
+         packed if packed is not None else conv2d_pack(weight, precision), None if bias is None else _f(bias), cout, k, int(stride), out,
+         None if gamma is None else _f(gamma), None if beta is None else _f(beta), float(eps), int(abs_gamma), ss, ws, wsb)
     return out, ss
 
 
@@ -245,7 +237,7 @@ def scale_shift_act(x, scale_shift, slope=0.01, want_nchw=True, want_nhwc=False)
     V, C, H, W = x.shape
     y1 = torch.empty_like(x) if want_nchw else None
     y2 = torch.empty(V, H, W, C, dtype=torch.float32, device=x.device) if want_nhwc else None
-    check(_lib.lib().o2345_scale_shift_act(_p(x), V, C, H, W, _p(scale_shift), float(slope), _p(y1), _p(y2), _stream()), "scale_shift_act")
+    call("o2345_scale_shift_act", x, V, C, H, W, scale_shift, float(slope), y1, y2)
     return y1, y2
 
 
@@ -259,8 +251,7 @@ def fpn_level(fine, coarse, weight, bias, fine_scale_shift=None, slope=0.01):
     if tuple(coarse.shape) != (V, 32, H // 2, W // 2):
         raise ValueError(f"fpn_level: coarse map must be [V,32,H/2,W/2], got {tuple(coarse.shape)} for fine {tuple(fine.shape)}")
     out = torch.empty(V, 32, H, W, dtype=torch.float32, device=fine.device)
-    check(_lib.lib().o2345_fpn_level_act(_p(fine), _p(fine_scale_shift), float(slope), C, _p(coarse), _p(_f(weight).reshape(32, C)), _p(_f(bias)), V, H, W,
-                                         _p(out), _stream()), "fpn_level")
+    call("o2345_fpn_level_act", fine, fine_scale_shift, float(slope), C, coarse, _f(weight).reshape(32, C), _f(bias), V, H, W, out)
     return out
 
 
@@ -274,14 +265,13 @@ def pyramid_pack(f2, s1, s0, rgb, want_nchw=True):
         raise ValueError("pyramid_pack: expected f2 [V,32,H/4,W/4], s1 [V,16,H/2,W/2], s0 [V,8,H,W], rgb [V,3,H,W]")
     fm = torch.empty(V, 56, H, W, dtype=torch.float32, device=s0.device) if want_nchw else None
     cm = torch.empty(V, H, W, 64, dtype=torch.float32, device=s0.device)
-    check(_lib.lib().o2345_pyramid_pack(_p(f2), _p(s1), _p(s0), _p(rgb), V, H, W, _p(fm), _p(cm), _stream()), "pyramid_pack")
+    call("o2345_pyramid_pack", f2, s1, s0, rgb, V, H, W, fm, cm)
     return fm, cm
 
 
 @_on_device
 def costvol_index(proj, V, H, W, dims, voxel_size, origin, min_views=1):
     """-> cnt u8 [D^3], row_of_voxel i32 [D^3], coords i32 [N,4] (x,y,z,b), N (python int; one 4-byte D2H read)."""
-    L = _lib.lib()
     dx, dy, dz = (int(d) for d in dims)
     nvox = dx * dy * dz
     dev = proj.device
@@ -289,12 +279,8 @@ def costvol_index(proj, V, H, W, dims, voxel_size, origin, min_views=1):
     row = torch.empty(nvox, dtype=torch.int32, device=dev)
     coords = torch.empty(nvox, 4, dtype=torch.int32, device=dev)
     n_dev = torch.zeros(1, dtype=torch.int32, device=dev)
-    wsb = L.o2345_costvol_workspace_bytes(dx, dy, dz)
-    ws = _workspace(wsb, dev)
-    oh, ohp = _host3(origin)
-    check(L.o2345_costvol_index(_p(proj), V, H, W, dx, dy, dz, float(voxel_size), ohp, int(min_views), _p(cnt, torch.uint8),
-                                _p(row, torch.int32), _p(coords, torch.int32), _p(n_dev, torch.int32), _p(ws, torch.uint8),
-                                wsb, _stream()), "costvol_index")
+    ws, wsb = _scratch("o2345_costvol_workspace_bytes", (dx, dy, dz), dev)
+    call("o2345_costvol_index", proj, V, H, W, dx, dy, dz, float(voxel_size), _host3(origin), int(min_views), cnt, row, coords, n_dev, ws, wsb)
     n = int(n_dev.item())
     return cnt, row, coords[:n], n
 
@@ -306,10 +292,8 @@ def costvol_gather(feats_nhwc, proj, dims, voxel_size, origin, cnt, coords):
     out = torch.empty(n, 2 * C, dtype=torch.float32, device=feats_nhwc.device)
     if n == 0:
         return out
-    oh, ohp = _host3(origin)
     dx, dy, dz = (int(d) for d in dims)
-    check(_lib.lib().o2345_costvol_gather(_p(feats_nhwc), _p(proj), V, H, W, C, dx, dy, dz, float(voxel_size), ohp,
-                                          _p(cnt, torch.uint8), _p(coords, torch.int32), n, _p(out), _stream()), "costvol_gather")
+    call("o2345_costvol_gather", feats_nhwc, proj, V, H, W, C, dx, dy, dz, float(voxel_size), _host3(origin), cnt, coords, n, out)
     return out
 
 
@@ -320,9 +304,7 @@ def visible_count_list(proj, H, W, voxel_size, origin, coords):
     cnt = torch.empty(M, dtype=torch.uint8, device=coords.device)
     if M == 0:
         return cnt
-    oh, ohp = _host3(origin)
-    check(_lib.lib().o2345_visible_count_list(_p(proj), proj.shape[0], H, W, float(voxel_size), ohp, _p(coords, torch.int32), M,
-                                             _p(cnt, torch.uint8), _stream()), "visible_count_list")
+    call("o2345_visible_count_list", proj, proj.shape[0], H, W, float(voxel_size), _host3(origin), coords, M, cnt)
     return cnt
 
 
@@ -333,9 +315,7 @@ def costvol_gather_list(feats_nhwc, proj, voxel_size, origin, cnt_row, coords):
     out = torch.empty(n, 2 * C, dtype=torch.float32, device=feats_nhwc.device)
     if n == 0:
         return out
-    oh, ohp = _host3(origin)
-    check(_lib.lib().o2345_costvol_gather_list(_p(feats_nhwc), _p(proj), V, H, W, C, float(voxel_size), ohp, _p(cnt_row, torch.uint8),
-                                              _p(coords, torch.int32), n, _p(out), _stream()), "costvol_gather_list")
+    call("o2345_costvol_gather_list", feats_nhwc, proj, V, H, W, C, float(voxel_size), _host3(origin), cnt_row, coords, n, out)
     return out
 
 
@@ -343,15 +323,14 @@ def costvol_gather_list(feats_nhwc, proj, voxel_size, origin, cnt_row, coords):
 def build_index_grid(coords, ts, cells):
     nx, ny, nz = (int(c) for c in cells)
     grid = torch.empty(nx * ny * nz, dtype=torch.int32, device=coords.device)
-    check(_lib.lib().o2345_build_index_grid(_p(coords, torch.int32) if coords.shape[0] else None, coords.shape[0], int(ts), nx, ny, nz,
-                                           _p(grid, torch.int32), _stream()), "build_index_grid")
+    call("o2345_build_index_grid", coords if coords.shape[0] else None, coords.shape[0], int(ts), nx, ny, nz, grid)
     return grid
 
 
 @_on_device
 def prune_dilate(sdf_vol, mask_vol, D, threshold, radius=3):
     out = torch.empty(D * D * D, dtype=torch.uint8, device=sdf_vol.device)
-    check(_lib.lib().o2345_prune_dilate(_p(sdf_vol), _p(mask_vol), D, float(threshold), int(radius), _p(out, torch.uint8), _stream()), "prune_dilate")
+    call("o2345_prune_dilate", sdf_vol, mask_vol, D, float(threshold), int(radius), out)
     return out
 
 
@@ -366,7 +345,7 @@ def scatter_dense(rows, row_of_voxel, dims, want_cf=True):
     cl = torch.empty(dx, dy, dz, C, dtype=torch.float32, device=dev)
     cf = torch.empty(1, C, dx, dy, dz, dtype=torch.float32, device=dev) if want_cf else None
     mask = torch.empty(1, 1, dx, dy, dz, dtype=torch.float32, device=dev)
-    check(_lib.lib().o2345_scatter_dense(_p(rows), _p(row_of_voxel, torch.int32), C, nvox, _p(cl), _p(cf), _p(mask), _stream()), "scatter_dense")
+    call("o2345_scatter_dense", rows, row_of_voxel, C, nvox, cl, cf, mask)
     return cl, cf, mask
 
 
@@ -374,21 +353,15 @@ def scatter_dense(rows, row_of_voxel, dims, want_cf=True):
 @_on_device
 def sparse_downsample(coords, ts, fine_cells):
     """coords [n,4] int32 at tensor stride ts on a lattice of fine_cells cells/axis -> (grid, coords_c, n_c, cells_c)."""
-    L = _lib.lib()
     nc = tuple((int(c) + 1) // 2 + 1 for c in fine_cells)
-    dev = coords.device
+    dev, ncell = coords.device, nc[0] * nc[1] * nc[2]
     if coords.shape[0] == 0:
-        ncell = nc[0] * nc[1] * nc[2]
         return torch.full((ncell,), -1, dtype=torch.int32, device=dev), torch.zeros(0, 4, dtype=torch.int32, device=dev), 0, nc
-    ncell = nc[0] * nc[1] * nc[2]
     grid = torch.empty(ncell, dtype=torch.int32, device=dev)
     cc = torch.empty(ncell, 4, dtype=torch.int32, device=dev)
     n_dev = torch.zeros(1, dtype=torch.int32, device=dev)
-    wsb = L.o2345_sparse_downsample_workspace_bytes(*nc)
-    ws = _workspace(wsb, dev)
-    check(L.o2345_sparse_downsample(_p(coords, torch.int32), coords.shape[0], int(ts), nc[0], nc[1], nc[2],
-                                    _p(grid, torch.int32), _p(cc, torch.int32), _p(n_dev, torch.int32), _p(ws, torch.uint8),
-                                    wsb, _stream()), "sparse_downsample")
+    ws, wsb = _scratch("o2345_sparse_downsample_workspace_bytes", nc, dev)
+    call("o2345_sparse_downsample", coords, coords.shape[0], int(ts), nc[0], nc[1], nc[2], grid, cc, n_dev, ws, wsb)
     n = int(n_dev.item())
     return grid, cc[:n], n, nc
 
@@ -399,8 +372,7 @@ def sparse_conv3d(mode, x, in_grid, in_cells, out_coords, ts_out, kernel):
     out = torch.empty(n_out, cout, dtype=torch.float32, device=x.device)
     if n_out == 0 or x.shape[0] == 0:
         return out.zero_()
-    check(_lib.lib().o2345_sparse_conv3d(int(mode), _p(x), cin, _p(in_grid, torch.int32), in_cells[0], in_cells[1], in_cells[2],
-                                         _p(out_coords, torch.int32), n_out, int(ts_out), _p(kernel), cout, _p(out), _stream()), "sparse_conv3d")
+    call("o2345_sparse_conv3d", int(mode), x, cin, in_grid, in_cells[0], in_cells[1], in_cells[2], out_coords, n_out, int(ts_out), kernel, cout, out)
     return out
 
 
@@ -416,37 +388,30 @@ def sparse_conv3d_x3(mode, x, in_grid, in_cells, out_coords, ts_out, wblob, cout
         return out.zero_()
     if identity_rows and (int(mode) != 0 or n_out != x.shape[0]):
         raise ValueError(f"sparse_conv3d_x3: identity_rows needs mode 0 and one output row per input row (mode {mode}, {n_out} vs {x.shape[0]} rows)")
-    check(_lib.lib().o2345_sparse_conv3d_x3(int(mode), _p(x), cin, _p(in_grid, torch.int32), in_cells[0], in_cells[1], in_cells[2],
-                                            _p(out_coords, torch.int32), n_out, int(ts_out), _p(wblob), int(cout), int(bool(identity_rows)), _p(out),
-                                            _stream()), "sparse_conv3d_x3")
+    call("o2345_sparse_conv3d_x3", int(mode), x, cin, in_grid, in_cells[0], in_cells[1], in_cells[2], out_coords, n_out, int(ts_out), wblob, int(cout),
+         int(bool(identity_rows)), out)
     return out
 
 
 @_on_device
 def bn_act_rows(x, gamma, beta, eps=1e-5, slope=0.0, abs_gamma=False, skip=None, want_stats=False):
-    L = _lib.lib()
     n, C = x.shape
     y = torch.empty_like(x)
     if n == 0:
         return (y, torch.zeros(2, C, device=x.device)) if want_stats else y
-    wsb = L.o2345_bn_workspace_bytes(C)
-    ws = _workspace(wsb, x.device, "bn")
+    ws, wsb = _scratch("o2345_bn_workspace_bytes", (C,), x.device, "bn")
     mv = torch.empty(2, C, dtype=torch.float32, device=x.device) if want_stats else None
-    check(L.o2345_bn_act_rows(_p(x), n, C, _p(gamma), _p(beta), float(eps), float(slope), int(abs_gamma), _p(skip), _p(y),
-                              _p(mv), _p(ws, torch.uint8), wsb, _stream()), "bn_act_rows")
+    call("o2345_bn_act_rows", x, n, C, gamma, beta, float(eps), float(slope), int(abs_gamma), skip, y, mv, ws, wsb)
     return (y, mv) if want_stats else y
 
 
 @_on_device
 def abn_nchw(x, gamma, beta, eps=1e-5, slope=0.01, abs_gamma=True, want_nchw=True, want_nhwc=False):
-    L = _lib.lib()
     V, C, H, W = x.shape
-    wsb = L.o2345_abn_workspace_bytes(C)
-    ws = _workspace(wsb, x.device, "abn")
+    ws, wsb = _scratch("o2345_abn_workspace_bytes", (C,), x.device, "abn")
     y1 = torch.empty_like(x) if want_nchw else None
     y2 = torch.empty(V, H, W, C, dtype=torch.float32, device=x.device) if want_nhwc else None
-    check(L.o2345_abn_nchw(_p(x), V, C, H, W, _p(gamma), _p(beta), float(eps), float(slope), int(abs_gamma), _p(y1), _p(y2),
-                           _p(ws, torch.uint8), wsb, _stream()), "abn_nchw")
+    call("o2345_abn_nchw", x, V, C, H, W, gamma, beta, float(eps), float(slope), int(abs_gamma), y1, y2, ws, wsb)
     return y1, y2
 
 
@@ -456,7 +421,7 @@ def sdf_grid_tables(tab_axes, bias_lane_order):
     """(tab_axes [3,R,128], bias [128]) from weights.sdf_grid_tables, on the device -> (tab_xy [R*R,128] = x + y + bias, tab_z [R,128])."""
     R = tab_axes.shape[1]
     tab_xy = torch.empty(R * R, 128, dtype=torch.float32, device=tab_axes.device)
-    check(_lib.lib().o2345_sdf_grid_tables(_p(tab_axes), _p(bias_lane_order), R, _p(tab_xy), _stream()), "sdf_grid_tables")
+    call("o2345_sdf_grid_tables", tab_axes, bias_lane_order, R, tab_xy)
     return tab_xy, tab_axes[2]
 
 
@@ -504,25 +469,17 @@ def sdf_mlp(blob, vol_cl, pts=None, variant=0, grid_R=0, sign=1.0, index=None, n
                 if maskvol.numel() != D ** 3 or grid_background.numel() != P or P >= 2 ** 31:
                     raise ValueError(f"sdf_mlp: maskvol [{D}^3] and grid_background [{grid_R}^3 < 2^31] expected, got {maskvol.numel()} and "
                                      f"{grid_background.numel()} elements")
-                L = _lib.lib()
-                wsb = L.o2345_sdf_grid_sparse_workspace_bytes(int(grid_R))
-                ws = _workspace(wsb, dev, "sdf_grid_sparse")
-                check(L.o2345_sdf_grid_sparse_x3(_p(blob), _p(vol_cl), _p(maskvol), D, int(grid_R), float(sign), _p(tab_xy), _p(tab_z), _p(grid_background),
-                                                 _p(res["sdf"]), _p(ws, torch.uint8), wsb, _stream()), "sdf_grid_sparse_x3")
-                return res
-            check(_lib.lib().o2345_sdf_grid_x3(_p(blob), _p(vol_cl), D, int(grid_R), float(sign), _p(tab_xy), _p(tab_z), _p(res["sdf"]), _stream()),
-                  "sdf_grid_x3")
-            return res
-        check(_lib.lib().o2345_sdf_mlp_x3(_p(blob), _p(vol_cl), D, _p(pts), _p(index, torch.int32), _p(n_dev, torch.int32), n, int(grid_R),
-                                          float(sign), _p(res["sdf"]), _stream()), "sdf_mlp_x3")
-        return res
-    if precision == "f16x3" and variant == 2 and not want_lat and lat_in is None:
-        check(_lib.lib().o2345_sdf_grad_x3(_p(blob), _p(vol_cl), D, _p(pts), _p(index, torch.int32), _p(n_dev, torch.int32), n, int(grid_R),
-                                           float(sign), _p(res["sdf"]), _p(res["grad"]), _stream()), "sdf_grad_x3")
-        return res
-    check(_lib.lib().o2345_sdf_mlp_ex(int(variant), _p(blob), _p(vol_cl), D, _p(pts), _p(index, torch.int32), _p(n_dev, torch.int32),
-                                      n, int(grid_R), float(sign), _p(lat_in), _p(res["sdf"]), _p(res.get("feat")), _p(res.get("lat")),
-                                      _p(res.get("grad")), _stream()), "sdf_mlp")
+                ws, wsb = _scratch("o2345_sdf_grid_sparse_workspace_bytes", (int(grid_R),), dev, "sdf_grid_sparse")
+                call("o2345_sdf_grid_sparse_x3", blob, vol_cl, maskvol, D, int(grid_R), float(sign), tab_xy, tab_z, grid_background, res["sdf"], ws, wsb)
+            else:
+                call("o2345_sdf_grid_x3", blob, vol_cl, D, int(grid_R), float(sign), tab_xy, tab_z, res["sdf"])
+        else:
+            call("o2345_sdf_mlp_x3", blob, vol_cl, D, pts, index, n_dev, n, int(grid_R), float(sign), res["sdf"])
+    elif precision == "f16x3" and variant == 2 and not want_lat and lat_in is None:
+        call("o2345_sdf_grad_x3", blob, vol_cl, D, pts, index, n_dev, n, int(grid_R), float(sign), res["sdf"], res["grad"])
+    else:
+        call("o2345_sdf_mlp_ex", int(variant), blob, vol_cl, D, pts, index, n_dev, n, int(grid_R), float(sign), lat_in, res["sdf"], res.get("feat"),
+             res.get("lat"), res.get("grad"))
     return res
 
 
@@ -530,7 +487,7 @@ def sdf_grid_active_points(device):
     """Lattice slots that the last sdf_mlp(..., maskvol=, grid_background=) call on the current stream of ``device`` listed for evaluation (32 per active
     tile), read from the device-side count in its workspace, or None before any such call.  Synchronises: for tests and profiling notes."""
     with torch.cuda.device(device):
-        ws = _ws_cache.get(("sdf_grid_sparse", str(torch.device(device)), torch.cuda.current_stream(device).cuda_stream))
+        ws = _workspace(None, torch.device(device), "sdf_grid_sparse")
     return None if ws is None else int(ws[:4].view(torch.int32).item())
 
 
@@ -539,7 +496,7 @@ def sdf_grid_active_points(device):
 def pack_color_maps(feat_nchw, color_nchw):
     V, _, H, W = feat_nchw.shape
     out = torch.empty(V, H, W, 64, dtype=torch.float32, device=feat_nchw.device)
-    check(_lib.lib().o2345_pack_color_maps(_p(feat_nchw), _p(color_nchw), V, H, W, _p(out), _stream()), "pack_color_maps")
+    call("o2345_pack_color_maps", feat_nchw, color_nchw, V, H, W, out)
     return out
 
 
@@ -552,7 +509,7 @@ def camera_terms(intrinsics, w2cs):
         raise ValueError(f"camera_terms: intrinsics [V,3,3] and w2cs [V,4,4] expected, got {tuple(intrinsics.shape)}, {tuple(w2cs.shape)}")
     proj = torch.empty(V, 3, 4, dtype=torch.float32, device=w2cs.device)
     cam = torch.empty(V, 3, dtype=torch.float32, device=w2cs.device)
-    check(_lib.lib().o2345_camera_terms(_p(_f(intrinsics)), _p(_f(w2cs)), V, _p(proj), _p(cam), _stream()), "camera_terms")
+    call("o2345_camera_terms", _f(intrinsics), _f(w2cs), V, proj, cam)
     return proj, cam
 
 
@@ -581,11 +538,8 @@ def color_points(blob, vol_cl, maskvol, cmaps, proj, cam_pos, pts, query_cam=Non
     nv = torch.zeros(P, dtype=torch.uint8, device=pts.device) if want_nviews else None
     if P == 0 or (n == 0 and n_dev is None):
         return rgb, nv
-    L = _lib.lib()
-    fn = L.o2345_color_points_x3 if mfma == "x3" else L.o2345_color_points_mfma
-    check(fn(_p(blob), _p(vol_cl), _p(maskvol), vol_cl.shape[0], _p(cmaps), _p(proj), _p(cam_pos),
-             V, H, W, _p(pts), _p(index, torch.int32), _p(n_dev, torch.int32), n, _p(query_cam),
-             _p(normals), _p(rgb), _p(nv, torch.uint8), _p(stats, torch.int64), _stream()), "color_points")
+    call("o2345_color_points_x3" if mfma == "x3" else "o2345_color_points_mfma", blob, vol_cl, maskvol, vol_cl.shape[0], cmaps, proj, cam_pos,
+         V, H, W, pts, index, n_dev, n, query_cam, normals, rgb, nv, stats)
     return rgb, nv
 
 
@@ -600,8 +554,7 @@ def project_features(vol_cl, maskvol, cmaps, proj, cam_pos, pts, query_cam=None,
     rf = torch.empty(V, P, 59, dtype=torch.float32, device=dev)
     rd = torch.empty(V, P, 4, dtype=torch.float32, device=dev)
     m = torch.empty(V, P, dtype=torch.float32, device=dev)
-    check(_lib.lib().o2345_project_features(_p(vol_cl), _p(maskvol), vol_cl.shape[0], _p(cmaps), _p(proj), _p(cam_pos), V, H, W, _p(pts), P, _p(query_cam),
-                                            _p(normals), _p(geo), _p(rf), _p(rd), _p(m), _stream()), "project_features")
+    call("o2345_project_features", vol_cl, maskvol, vol_cl.shape[0], cmaps, proj, cam_pos, V, H, W, pts, P, query_cam, normals, geo, rf, rd, m)
     return geo, rf, rd, m
 
 
@@ -616,15 +569,14 @@ def color_from_features(blob, geometry_feat, rgb_feat, ray_diff, mask, x3=True, 
     rgb = torch.empty(P, 3, dtype=torch.float32, device=rgb_feat.device)
     nv = torch.empty(P, dtype=torch.uint8, device=rgb_feat.device) if want_nviews else None
     if P:
-        check(_lib.lib().o2345_color_from_features(_p(blob), int(bool(x3)), _p(_f(geometry_feat)), _p(_f(rgb_feat)), _p(_f(ray_diff)), _p(_f(mask)), V, P,
-                                                   _p(rgb), _p(nv, torch.uint8), _stream()), "color_from_features")
+        call("o2345_color_from_features", blob, int(bool(x3)), _f(geometry_feat), _f(rgb_feat), _f(ray_diff), _f(mask), V, P, rgb, nv)
     return rgb, nv
 
 
 @_on_device
 def view_count(pts, maskvol, D, proj, V, H, W):
     out = torch.empty(pts.shape[0], dtype=torch.uint8, device=pts.device)
-    check(_lib.lib().o2345_view_count(_p(pts), pts.shape[0], _p(maskvol), D, _p(proj), V, H, W, _p(out, torch.uint8), _stream()), "view_count")
+    call("o2345_view_count", pts, pts.shape[0], maskvol, D, proj, V, H, W, out)
     return out
 
 
@@ -632,7 +584,6 @@ def view_count(pts, maskvol, D, proj, V, H, W):
 def list_sort_by_visibility(pts, index, proj, H, W, count=None, want_keys=False):
     """index [n] int32 slots into pts [P,3] -> the same entries grouped, stably, by view-visibility signature (what o2345_render_rays does to its
     occupied-point list before the network kernels; csrc/list_sort.hip).  count (optional int32[1] on the device): number of valid entries."""
-    L = _lib.lib()
     n = int(index.shape[0])
     V = int(proj.shape[0])
     out = torch.empty_like(index)
@@ -641,10 +592,8 @@ def list_sort_by_visibility(pts, index, proj, H, W, count=None, want_keys=False)
     if count is None:
         count = torch.tensor([n], dtype=torch.int32, device=index.device)
     keys = torch.empty(n, dtype=torch.int32, device=index.device) if want_keys else None
-    wsb = L.o2345_list_sort_workspace_bytes(n, V)
-    ws = _workspace(wsb, index.device, "lsort")
-    check(L.o2345_list_sort_by_visibility(_p(pts), _p(index, torch.int32), _p(count, torch.int32), n, _p(proj), V, int(H), int(W), _p(out, torch.int32),
-                                          _p(keys, torch.int32), _p(ws, torch.uint8), wsb, _stream()), "list_sort_by_visibility")
+    ws, wsb = _scratch("o2345_list_sort_workspace_bytes", (n, V), index.device, "lsort")
+    call("o2345_list_sort_by_visibility", pts, index, count, n, proj, V, int(H), int(W), out, keys, ws, wsb)
     return (out, keys) if want_keys else out
 
 
@@ -653,15 +602,14 @@ _SCENE_KEYS = ("sdf_blob", "vol_cl", "maskvol", "cmaps", "proj", "cam_pos")
 
 
 def _color_network(scene, what):
-    """-> (entry point, blob) of the colour network the scene's precision selects: o2345_color_points_x3 with color_x3_blob in f16x3 mode (when the scene
-    has that blob), else o2345_color_points_mfma with color_mfma_blob."""
+    """-> (entry point's name, blob) of the colour network the scene's precision selects: o2345_color_points_x3 with color_x3_blob in f16x3 mode (when
+    the scene has that blob), else o2345_color_points_mfma with color_mfma_blob."""
     xb, mb = scene.get("color_x3_blob"), scene.get("color_mfma_blob")
-    L = _lib.lib()
     if xb is not None and config.color_precision(scene.get("color_precision")) == "f16x3":
-        return L.o2345_color_points_x3, xb
+        return "o2345_color_points_x3", xb
     if mb is None:
         raise ValueError(f"{what}: scene needs color_x3_blob (f16x3 mode) or color_mfma_blob (fp32 mode)")
-    return L.o2345_color_points_mfma, mb
+    return "o2345_color_points_mfma", mb
 
 
 @_on_device
@@ -677,7 +625,6 @@ def render_rays(scene, rays_o, rays_d, near, far, n_samples=64, n_importance=64,
     compositing weight is >= weight_cull -- a ray's colour moves by <= (n_samples + n_importance) * weight_cull (include/o2345.h, O2345RenderIO.weight_cull).
     segment_rays (0: one render() call): the rays are consecutive render() calls of that many rays evaluated together (O2345RenderIO.segment_rays).
     Returns dict of SAMPLE-MAJOR tensors ([S,R,...]) + per-ray results."""
-    L = _lib.lib()
     R = rays_o.shape[0]
     if query_cam is None:
         raise ValueError("render_rays: query_cam [3] (the query camera centre, query_c2w[:3, 3]) is required")
@@ -688,8 +635,9 @@ def render_rays(scene, rays_o, rays_d, near, far, n_samples=64, n_importance=64,
     if (n_samples + n_importance) * R >= 2 ** 31:
         raise ValueError("render_rays: R * (n_samples + n_importance) must stay below 2^31; split the ray batch")
     dev = rays_o.device
+    io = _lib.RenderIO()
     for k in _SCENE_KEYS:
-        _p(scene[k])                                   # contiguous cuda float32, or ValueError
+        io.point(**{k: scene[k]})                      # contiguous cuda float32, or ValueError
         if scene[k].device != dev:
             raise ValueError(f"render_rays: scene[{k!r}] is on {scene[k].device}, the rays on {dev}")
     Dv = scene["vol_cl"].shape[0]
@@ -715,41 +663,24 @@ def render_rays(scene, rays_o, rays_d, near, far, n_samples=64, n_importance=64,
     n_seg = (R + segment_rays - 1) // segment_rays if segment_rays else 0
     if want_scalars:
         o["scalars"] = f(n_seg, 4) if segment_rays else f(4)
-    io = _lib.RenderIO()
-    for k in _SCENE_KEYS:
-        setattr(io, k, scene[k].data_ptr())
-    fn, blob = _color_network(scene, "render_rays")
-    mb = scene.get("color_mfma_blob")
-    io.color_x3_blob = _p(blob).value if fn is L.o2345_color_points_x3 else None
-    io.color_mfma_blob = _p(mb).value if mb is not None else None
-    io.t_rand = _p(t_rand).value if t_rand is not None else None
+    entry, blob = _color_network(scene, "render_rays")
+    io.point(color_x3_blob=blob if entry == "o2345_color_points_x3" else None, color_mfma_blob=scene.get("color_mfma_blob"), t_rand=t_rand,
+             rays_o=rays_o, rays_d=rays_d, query_cam=query_cam, color_stats=color_stats, **o)         # z_vals / scalars stay NULL unless asked for
     io.sdf_mode = 2 if config.sdf_precision(scene.get("sdf_precision")) == "f16x3" else 0
-    io.D, io.V, io.H, io.W = Dv, V, H, W
-    io.rays_o, io.rays_d, io.R = _p(rays_o).value, _p(rays_d).value, R
+    io.D, io.V, io.H, io.W, io.R = Dv, V, H, W, R
     if torch.is_tensor(near) or torch.is_tensor(far):
         if not (torch.is_tensor(near) and torch.is_tensor(far)) or near.numel() != R or far.numel() != R or sample_dist is None:
             raise ValueError("render_rays: per-ray near / far are two tensors of R elements, and sample_dist must be given")
-        io.near_ray, io.far_ray = _p(near).value, _p(far).value
-        io.near = io.far = 0.0
+        io.point(near_ray=near, far_ray=far)                   # near = far = 0.0, as the fresh struct has them
     else:
-        io.near_ray = io.far_ray = None
         io.near, io.far = float(near), float(far)
     io.sample_dist = float(sample_dist) if sample_dist is not None else 0.0
     io.n_samples, io.n_importance = n_samples, n_importance
     io.inv_s, io.alpha_inter_ratio, io.background = float(inv_s), float(alpha_inter_ratio), float(background)
     io.weight_cull = float(config.weight_cull(scene.get("weight_cull") if weight_cull is None else weight_cull))
     io.segment_rays = int(segment_rays)
-    io.query_cam = _p(query_cam).value
-    for k, t in o.items():
-        setattr(io, k, t.data_ptr())
-    if not want_z:
-        io.z_vals = None
-    if not want_scalars:
-        io.scalars = None
-    io.color_stats = _p(color_stats, torch.int64).value if color_stats is not None else None
-    wsb = L.o2345_render_workspace_bytes(R, n_samples, n_importance, V)
-    ws = _workspace(wsb, dev, "render")
-    check(L.o2345_render_rays(ctypes.byref(io), _p(ws, torch.uint8), wsb, _stream()), "render_rays")
+    ws, wsb = _scratch("o2345_render_workspace_bytes", (R, n_samples, n_importance, V), dev, "render")
+    call("o2345_render_rays", io, ws, wsb)
     return o
 
 
@@ -759,7 +690,6 @@ def ray_coarse(rays_o, rays_d, near, far, n_samples, t_rand=None):
     stratified jitter t_rand [R, n_samples] (ray-major, what torch.rand(z_vals.shape) returns) when given.  near / far: python floats
     (o2345_ray_coarse, o2345_ray_coarse_jitter), or two float32 tensors [R] on the device (o2345_ray_coarse_per_ray).
     -> (z SAMPLE-MAJOR [n_samples,R], pts [n_samples,R,3])."""
-    L = _lib.lib()
     if rays_d.shape != rays_o.shape or rays_o.dim() != 2 or rays_o.shape[1] != 3:
         raise ValueError(f"ray_coarse: rays_o / rays_d must both be [R,3] (got {tuple(rays_o.shape)}, {tuple(rays_d.shape)})")
     R, S = rays_o.shape[0], int(n_samples)
@@ -773,11 +703,11 @@ def ray_coarse(rays_o, rays_d, near, far, n_samples, t_rand=None):
     if torch.is_tensor(near) or torch.is_tensor(far):
         if not (torch.is_tensor(near) and torch.is_tensor(far)) or near.numel() != R or far.numel() != R:
             raise ValueError("ray_coarse: per-ray near / far are two tensors of R elements")
-        check(L.o2345_ray_coarse_per_ray(_p(rays_o), _p(rays_d), R, _p(near), _p(far), S, _p(t_rand), _p(z), _p(pts), _stream()), "ray_coarse_per_ray")
+        call("o2345_ray_coarse_per_ray", rays_o, rays_d, R, near, far, S, t_rand, z, pts)
     elif t_rand is not None:
-        check(L.o2345_ray_coarse_jitter(_p(rays_o), _p(rays_d), R, float(near), float(far), S, _p(t_rand), _p(z), _p(pts), _stream()), "ray_coarse_jitter")
+        call("o2345_ray_coarse_jitter", rays_o, rays_d, R, float(near), float(far), S, t_rand, z, pts)
     else:
-        check(L.o2345_ray_coarse(_p(rays_o), _p(rays_d), R, float(near), float(far), S, _p(z), _p(pts), _stream()), "ray_coarse")
+        call("o2345_ray_coarse", rays_o, rays_d, R, float(near), float(far), S, z, pts)
     return z, pts
 
 
@@ -792,11 +722,11 @@ def ray_merge(z, sdf, new_z, new_sdf):
     (S, R), n_new = z.shape, new_z.shape[0]
     if S < 1 or n_new < 1 or R < 1:
         raise ValueError(f"ray_merge: at least one ray, one sample and one new sample (got R = {R}, S = {S}, n_new = {n_new})")
-    _p(z), _p(sdf)
+    _lib.bind("o2345_ray_merge", (R, z, sdf, S, new_z, new_sdf, n_new, None))          # the merge runs in place on copies: refuse bad originals before copying
     zm = torch.cat([z, torch.zeros_like(new_z)], 0)           # capacity S + n_new: merged in place
     sm = torch.cat([sdf, torch.zeros_like(new_sdf)], 0)
     nz, ns = new_z.clone(), new_sdf.clone()
-    check(_lib.lib().o2345_ray_merge(R, _p(zm), _p(sm), S, _p(nz), _p(ns), n_new, _stream()), "ray_merge")
+    call("o2345_ray_merge", R, zm, sm, S, nz, ns, n_new)
     return zm, sm
 
 
@@ -817,8 +747,7 @@ def ray_upsample(rays_o, rays_d, z, sdf, inv_s, maskvol, D, n_imp, streaming=Non
     new_sdf = torch.empty(n_imp, R, dtype=torch.float32, device=dev)
     lst = torch.empty(n_imp * R, dtype=torch.int32, device=dev)
     cnt = torch.zeros(1, dtype=torch.int32, device=dev)
-    check(_lib.lib().o2345_ray_upsample(_p(rays_o), _p(rays_d), R, _p(z), _p(sdf), S, float(inv_s), _p(maskvol), int(D), _p(wbuf), int(n_imp),
-                                        _p(new_z), _p(new_pts), _p(new_sdf), _p(lst, torch.int32), _p(cnt, torch.int32), _stream()), "ray_upsample")
+    call("o2345_ray_upsample", rays_o, rays_d, R, z, sdf, S, float(inv_s), maskvol, int(D), wbuf, int(n_imp), new_z, new_pts, new_sdf, lst, cnt)
     if want_weights:
         return new_z, new_pts, lst[:int(cnt.item())], wbuf[:S - 1]
     return new_z, new_pts, lst[:int(cnt.item())]
@@ -833,9 +762,8 @@ def ray_finalize(rays_o, rays_d, z, sample_dist, maskvol, D):
     f = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
     o = dict(mid_z=f(S, R), dists=f(S, R), pts=f(S, R, 3), pm=f(S, R), sdf=f(S, R), grad=f(S, R, 3), rgb=f(S, R, 3),
              list=torch.empty(S * R, dtype=torch.int32, device=dev), count=torch.zeros(1, dtype=torch.int32, device=dev))
-    check(_lib.lib().o2345_ray_finalize(_p(rays_o), _p(rays_d), R, _p(z), S, float(sample_dist), _p(maskvol), int(D), _p(o["mid_z"]), _p(o["dists"]),
-                                        _p(o["pts"]), _p(o["pm"]), _p(o["sdf"]), _p(o["grad"]), _p(o["rgb"]), _p(o["list"], torch.int32),
-                                        _p(o["count"], torch.int32), _stream()), "ray_finalize")
+    call("o2345_ray_finalize", rays_o, rays_d, R, z, S, float(sample_dist), maskvol, int(D), o["mid_z"], o["dists"], o["pts"], o["pm"], o["sdf"], o["grad"],
+         o["rgb"], o["list"], o["count"])
     return o
 
 
@@ -850,10 +778,8 @@ def ray_composite(rays_o, rays_d, mid_z, dists, pm, sdf, grad, rgb, nviews, inv_
     f = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
     o = dict(color=f(R, 3), depth=f(R), weights=f(S, R), cdf=f(S, R), weights_sum=f(R), weights_max=f(R), depth_var=f(R), alpha_sum=f(R),
              grad_err=f(R, 2), color_mask=torch.empty(R, dtype=torch.uint8, device=dev))
-    check(_lib.lib().o2345_ray_composite(_p(rays_o), _p(rays_d), R, S, _p(mid_z), _p(dists), _p(pm), _p(sdf), _p(grad), _p(rgb), _p(nviews, torch.uint8),
-                                         float(inv_s), float(alpha_inter_ratio), float(background), _p(o["color"]), _p(o["depth"]), _p(o["weights"]),
-                                         _p(o["cdf"]), _p(o["weights_sum"]), _p(o["weights_max"]), _p(o["depth_var"]), _p(o["alpha_sum"]),
-                                         _p(o["grad_err"]), _p(o["color_mask"], torch.uint8), _stream()), "ray_composite")
+    call("o2345_ray_composite", rays_o, rays_d, R, S, mid_z, dists, pm, sdf, grad, rgb, nviews, float(inv_s), float(alpha_inter_ratio), float(background),
+         o["color"], o["depth"], o["weights"], o["cdf"], o["weights_sum"], o["weights_max"], o["depth_var"], o["alpha_sum"], o["grad_err"], o["color_mask"])
     return o
 
 
@@ -879,11 +805,10 @@ def render_core(scene, rays_o, rays_d, z, sample_dist, inv_s, alpha_inter_ratio=
     res = {"sdf": o["sdf"].view(-1), "grad": o["grad"].view(-1, 3)}
     sdf_mlp(scene["sdf_blob"], scene["vol_cl"], pts, variant=2, index=lst, out=res, precision=sdf_precision)
     nviews = torch.zeros(S * R, dtype=torch.uint8, device=z.device)
-    check(_lib.lib().o2345_view_count_unlisted(_p(pts), S * R, _p(o["pm"]), _p(scene["maskvol"]), D, _p(scene["proj"]), V, H, W,
-                                               _p(nviews, torch.uint8), _stream()), "view_count_unlisted")
-    fn, blob = _color_network(scene, "render_core")
-    check(fn(_p(blob), _p(scene["vol_cl"]), _p(scene["maskvol"]), D, _p(scene["cmaps"]), _p(scene["proj"]), _p(scene["cam_pos"]), V, H, W,
-             _p(pts), _p(lst, torch.int32), None, n, _p(query_cam), None, _p(o["rgb"]), _p(nviews, torch.uint8), None, _stream()), "color_points")
+    call("o2345_view_count_unlisted", pts, S * R, o["pm"], scene["maskvol"], D, scene["proj"], V, H, W, nviews)
+    entry, blob = _color_network(scene, "render_core")
+    call(entry, blob, scene["vol_cl"], scene["maskvol"], D, scene["cmaps"], scene["proj"], scene["cam_pos"], V, H, W, pts, lst, None, n, query_cam, None,
+         o["rgb"], nviews, None)
     c = ray_composite(rays_o, rays_d, o["mid_z"], o["dists"], o["pm"], o["sdf"], o["grad"], o["rgb"], nviews.view(S, R), inv_s, alpha_inter_ratio, background)
     c.update(mid_z=o["mid_z"], dists=o["dists"], pm=o["pm"], sdf=o["sdf"], grad=o["grad"], rgb=o["rgb"], nviews=nviews.view(S, R), list=lst, z_vals=z)
     return c
@@ -891,18 +816,16 @@ def render_core(scene, rays_o, rays_d, z, sample_dist, inv_s, alpha_inter_ratio=
 
 # ---------------------------------------------------------------------------------------------------------- marching cubes
 def _triangles(tris, what=None):
-    """A triangle tensor, validated -> (pointer, index_bytes) as the library's entries take them."""
+    """A triangle tensor, validated -> (the tensor, index_bytes) as the library's entries take them (`void* tris`: the width is this check's)."""
     if tris.dtype not in (torch.int32, torch.int64) or tris.dim() != 2 or tris.shape[1] != 3:
         raise ValueError((f"{what}: " if what else "") + f"expected triangles [M,3] int32 or int64, got {tuple(tris.shape)} {tris.dtype}")
-    return _p(tris, tris.dtype), 8 if tris.dtype == torch.int64 else 4
+    return tris, 8 if tris.dtype == torch.int64 else 4
 
 
 def _mesh_frame(bound_min, bound_max, scale_mat, trans_mat):
-    """Bounds (3 numbers each) and the two 4x4 matrices (tensors, arrays or None) -> ([four host pointers or None], the float32 arrays behind them, which
-    the caller keeps alive over the call)."""
+    """Bounds (3 numbers each) and the two 4x4 matrices (tensors, arrays or None) -> four float32 host arrays or None, as the entries take them."""
     mat = lambda a: None if a is None else host_f32(a).reshape(-1, 4, 4)[0].copy()
-    keep = [host_f32(bound_min).reshape(3), host_f32(bound_max).reshape(3), mat(scale_mat), mat(trans_mat)]
-    return [None if a is None else a.ctypes.data_as(ctypes.c_void_p) for a in keep], keep
+    return [host_f32(bound_min).reshape(3), host_f32(bound_max).reshape(3), mat(scale_mat), mat(trans_mat)]
 
 
 @_on_device
@@ -911,13 +834,11 @@ def mesh_pack(verts_idx, tris, grid_R, bound_min=(-1.0, -1.0, -1.0), bound_max=(
     frame transforms and colour quantisation as in trainer_generic.py:1365-1377.  Matrices / bounds are small host arrays."""
     dev = verts_idx.device
     n, m = verts_idx.shape[0], tris.shape[0]
-    frame, _keep = _mesh_frame(bound_min, bound_max, scale_mat, trans_mat)
+    frame = _mesh_frame(bound_min, bound_max, scale_mat, trans_mat)
     vrec = torch.empty(n, 16 if rgb is not None else 12, dtype=torch.uint8, device=dev)
     frec = torch.empty(m, 13, dtype=torch.uint8, device=dev)
-    L = _lib.lib()
-    check(L.o2345_mesh_pack_vertices(_p(verts_idx, torch.float64), n, int(grid_R), *frame, _p(rgb),
-                                     _p(vrec, torch.uint8), _stream()), "mesh_pack_vertices")
-    check(L.o2345_mesh_pack_faces(*_triangles(tris), m, _p(frec, torch.uint8), _stream()), "mesh_pack_faces")
+    call("o2345_mesh_pack_vertices", verts_idx, n, int(grid_R), *frame, rgb, vrec)
+    call("o2345_mesh_pack_faces", *_triangles(tris), m, frec)
     return vrec, frec
 
 
@@ -928,18 +849,15 @@ def mesh_asset_pack(verts_idx, tris, grid_R, bound_min=(-1.0, -1.0, -1.0), bound
     bounds float32 [2,3] = per-axis min, max of positions), all on the device.  ``rgb`` fp32 [N,3] in [0,1]; ``grad`` fp32 [N,3], the SDF gradient."""
     dev = verts_idx.device
     n, m = verts_idx.shape[0], tris.shape[0]
-    frame, _keep = _mesh_frame(bound_min, bound_max, scale_mat, trans_mat)
+    frame = _mesh_frame(bound_min, bound_max, scale_mat, trans_mat)
     pos = torch.empty(n, 3, dtype=torch.float32, device=dev)
     rgba = None if rgb is None else torch.empty(n, 4, dtype=torch.uint8, device=dev)
     nrm = None if grad is None else torch.empty(n, 3, dtype=torch.float32, device=dev)
     idx = torch.empty(m, 3, dtype=torch.int32, device=dev)              # uint32 bit patterns (torch has no general uint32): vertex counts stay below 2^31
     bounds = torch.empty(2, 3, dtype=torch.float32, device=dev)
-    L = _lib.lib()
-    wsb = L.o2345_mesh_bounds_workspace_bytes(n)
-    ws = _workspace(wsb, dev, "mesh_bounds")
-    check(L.o2345_mesh_asset_vertices(_p(verts_idx, torch.float64), n, int(grid_R), *frame, _p(rgb), _p(grad), _p(pos),
-                                      _p(rgba, torch.uint8), _p(nrm), _p(bounds), _p(ws, torch.uint8), wsb, _stream()), "mesh_asset_vertices")
-    check(L.o2345_mesh_asset_indices(*_triangles(tris), m, _p(idx, torch.int32), _stream()), "mesh_asset_indices")
+    ws, wsb = _scratch("o2345_mesh_bounds_workspace_bytes", (n,), dev, "mesh_bounds")
+    call("o2345_mesh_asset_vertices", verts_idx, n, int(grid_R), *frame, rgb, grad, pos, rgba, nrm, bounds, ws, wsb)
+    call("o2345_mesh_asset_indices", *_triangles(tris), m, idx)
     return pos, rgba, nrm, idx, bounds
 
 
@@ -960,12 +878,9 @@ def obj_text(positions, indices, rgba=None, normals=None, K=None, bounds=None):
     (include/o2345.h).  ``K``: integer digits of the coordinate fields; taken from ``bounds`` (one small D2H copy) when not given."""
     n, m = positions.shape[0], indices.shape[0]
     K = _obj_digits(K, bounds, n, "obj_text")
-    L = _lib.lib()
-    nbytes = L.o2345_obj_text_bytes(n, m, K, int(rgba is not None), int(normals is not None))
-    text = torch.empty(nbytes, dtype=torch.uint8, device=positions.device)
+    text = torch.empty(call("o2345_obj_text_bytes", n, m, K, int(rgba is not None), int(normals is not None)), dtype=torch.uint8, device=positions.device)
     table = _obj_color_table(positions.device) if rgba is not None else None
-    check(L.o2345_obj_text(_p(positions), _p(rgba, torch.uint8), _p(normals), n, _p(indices, torch.int32), m, K, _p(table, torch.uint8),
-                           _p(text, torch.uint8), _stream()), "obj_text")
+    call("o2345_obj_text", positions, rgba, normals, n, indices, m, K, table, text)
     return text
 
 
@@ -976,40 +891,31 @@ def mc_verts_to_world(verts_idx, grid_R, bound_min, bound_max):
     b0, b1 = host_f32(bound_min).reshape(3), host_f32(bound_max).reshape(3)
     ext = np.ascontiguousarray((b1 - b0).astype(np.float64))          # the reference subtracts its float32 bound arrays, numpy promotes afterwards
     off = np.ascontiguousarray(b0.astype(np.float64))
-    check(_lib.lib().o2345_mc_verts_to_world(_p(verts_idx, torch.float64), verts_idx.shape[0], int(grid_R), ext.ctypes.data_as(ctypes.c_void_p),
-                                             off.ctypes.data_as(ctypes.c_void_p), _stream()), "mc_verts_to_world")
+    call("o2345_mc_verts_to_world", verts_idx, verts_idx.shape[0], int(grid_R), ext, off)
     return verts_idx
 
 
 @_on_device
 def marching_cubes(u, iso=0.0, index_dtype=torch.int64):
     """u: float32 cuda tensor [n0,n1,n2].  Returns (verts float64 [Nv,3] index coords, tris [Nt,3]) on the device."""
-    L = _lib.lib()
     n0, n1, n2 = u.shape
-    wsb = L.o2345_mc_workspace_bytes(n0, n1, n2)
-    ws = _workspace(wsb, u.device, "mc")
+    ws, wsb = _scratch("o2345_mc_workspace_bytes", (n0, n1, n2), u.device, "mc")
     nv, nt = ctypes.c_longlong(), ctypes.c_longlong()
-    check(L.o2345_marching_cubes_count(_p(u), n0, n1, n2, float(iso), _p(ws, torch.uint8), wsb, ctypes.byref(nv), ctypes.byref(nt),
-                                       _stream()), "marching_cubes_count")
+    call("o2345_marching_cubes_count", u, n0, n1, n2, float(iso), ws, wsb, nv, nt)
     verts = torch.empty(nv.value, 3, dtype=torch.float64, device=u.device)
     tris = torch.empty(nt.value, 3, dtype=index_dtype, device=u.device)
-    check(L.o2345_marching_cubes_emit(_p(u), n0, n1, n2, float(iso), _p(ws, torch.uint8), _p(verts, torch.float64),
-                                      *_triangles(tris), _stream()), "marching_cubes_emit")
+    call("o2345_marching_cubes_emit", u, n0, n1, n2, float(iso), ws, verts, *_triangles(tris))
     return verts, tris
 
 
 # ---------------------------------------------------------------------------------------------------------- mesh components
 def _mesh_components_count(tris, nv, min_faces, keep_largest, labels):
     """Pass 1 of the two-call protocol -> (workspace, components, components_kept, nv_kept, nt_kept)."""
-    tp, ib = _triangles(tris)
-    L = _lib.lib()
+    tris, ib = _triangles(tris)
     nt = tris.shape[0]
-    wsb = L.o2345_mesh_components_workspace_bytes(nv, nt)
-    ws = _workspace(wsb, tris.device, "mesh_components")
+    ws, wsb = _scratch("o2345_mesh_components_workspace_bytes", (nv, nt), tris.device, "mesh_components")
     nc, nck, nvk, ntk = (ctypes.c_longlong() for _ in range(4))
-    check(L.o2345_mesh_components_count(tp, ib, nv, nt, min(int(min_faces), 2 ** 31 - 1), int(bool(keep_largest)),
-                                        _p(ws, torch.uint8), wsb, _p(labels, torch.int32), ctypes.byref(nc), ctypes.byref(nck), ctypes.byref(nvk),
-                                        ctypes.byref(ntk), _stream()), "mesh_components_count")
+    call("o2345_mesh_components_count", tris, ib, nv, nt, min(int(min_faces), 2 ** 31 - 1), int(bool(keep_largest)), ws, wsb, labels, nc, nck, nvk, ntk)
     return ws, nc.value, nck.value, nvk.value, ntk.value
 
 
@@ -1037,9 +943,7 @@ def mesh_filter_components(verts_idx, tris, min_faces=0, keep_largest=False):
     verts = torch.empty(nvk, 3, dtype=torch.float64, device=dev)
     tris_out = torch.empty(ntk, 3, dtype=tris.dtype, device=dev)
     kept = torch.empty(nvk, dtype=torch.int32, device=dev)
-    check(_lib.lib().o2345_mesh_components_emit(_p(verts_idx, torch.float64), *_triangles(tris), nv, tris.shape[0],
-                                                _p(ws, torch.uint8), _p(verts, torch.float64), _p(tris_out, tris.dtype), _p(kept, torch.int32), _stream()),
-          "mesh_components_emit")
+    call("o2345_mesh_components_emit", verts_idx, *_triangles(tris), nv, tris.shape[0], ws, verts, tris_out, kept)
     return verts, tris_out, kept, {"components": nc, "components_kept": nck}
 
 
@@ -1049,19 +953,15 @@ def mesh_vertex_adjacency(tris, n_vertices):
     """tris [M,3] int32 / int64 on the device -> (offsets int32 [n + 1], neighbours int32 [E], boundary uint8 [n]): the vertex -> neighbours table in CSR
     form, rows ascending, and the flag of the vertices on an edge with one triangle (== mesh_io.vertex_adjacency, exactly; definitions in
     csrc/mesh_smooth.hip)."""
-    tp, ib = _triangles(tris)
-    L = _lib.lib()
+    tris, ib = _triangles(tris)
     nv, nt, dev = int(n_vertices), tris.shape[0], tris.device
-    wsb = L.o2345_mesh_adjacency_workspace_bytes(nv, nt)
-    ws = _workspace(wsb, dev, "mesh_adjacency")
+    ws, wsb = _scratch("o2345_mesh_adjacency_workspace_bytes", (nv, nt), dev, "mesh_adjacency")
     ne = ctypes.c_longlong()
-    check(L.o2345_mesh_adjacency_count(tp, ib, nv, nt, _p(ws, torch.uint8), wsb, ctypes.byref(ne), _stream()),
-          "mesh_adjacency_count")
+    call("o2345_mesh_adjacency_count", tris, ib, nv, nt, ws, wsb, ne)
     offsets = torch.empty(nv + 1, dtype=torch.int32, device=dev)
     neighbours = torch.empty(ne.value, dtype=torch.int32, device=dev)
     boundary = torch.empty(nv, dtype=torch.uint8, device=dev)
-    check(L.o2345_mesh_adjacency_emit(_p(ws, torch.uint8), nv, _p(offsets, torch.int32), _p(neighbours, torch.int32), _p(boundary, torch.uint8), _stream()),
-          "mesh_adjacency_emit")
+    call("o2345_mesh_adjacency_emit", ws, nv, offsets, neighbours, boundary)
     return offsets, neighbours, boundary
 
 
@@ -1080,8 +980,7 @@ def mesh_smooth(verts_idx, tris, iterations, lam=None, mu=None, pin_boundary=Non
     offsets, neighbours, boundary = mesh_vertex_adjacency(tris, nv)
     out = torch.empty(nv, 3, dtype=torch.float64, device=verts_idx.device)
     tmp = _workspace(24 * nv, verts_idx.device, "mesh_smooth")
-    check(_lib.lib().o2345_mesh_smooth(_p(verts_idx, torch.float64), nv, _p(offsets, torch.int32), _p(neighbours, torch.int32), _p(boundary, torch.uint8) if pin else None,
-                                       iterations, lam, mu, _p(tmp, torch.uint8), _p(out, torch.float64), _stream()), "mesh_smooth")
+    call("o2345_mesh_smooth", verts_idx, nv, offsets, neighbours, boundary if pin else None, iterations, lam, mu, tmp.view(torch.float64), out)
     return out
 
 
@@ -1096,20 +995,16 @@ def mesh_decimate(verts_idx, tris, cell=None):
     cell = config.mesh_decimate_cell(cell)
     if cell == 0.0:
         return verts_idx, tris, None, None
-    tp, ib = _triangles(tris)
+    tris, ib = _triangles(tris)
     _vertices(verts_idx)
-    L = _lib.lib()
     nv, nt, dev = verts_idx.shape[0], tris.shape[0], verts_idx.device
-    wsb = L.o2345_mesh_decimate_workspace_bytes(nv, nt)
-    ws = _workspace(wsb, dev, "mesh_decimate")
+    ws, wsb = _scratch("o2345_mesh_decimate_workspace_bytes", (nv, nt), dev, "mesh_decimate")
     ncl, nvo, nto, ndeg, ndup = (ctypes.c_longlong() for _ in range(5))
-    check(L.o2345_mesh_decimate_count(_p(verts_idx, torch.float64), tp, ib, nv, nt, cell, _p(ws, torch.uint8), wsb, ctypes.byref(ncl),
-                                      ctypes.byref(nvo), ctypes.byref(nto), ctypes.byref(ndeg), ctypes.byref(ndup), _stream()), "mesh_decimate_count")
+    call("o2345_mesh_decimate_count", verts_idx, tris, ib, nv, nt, cell, ws, wsb, ncl, nvo, nto, ndeg, ndup)
     verts = torch.empty(nvo.value, 3, dtype=torch.float64, device=dev)
     tris_out = torch.empty(nto.value, 3, dtype=tris.dtype, device=dev)
     cluster = torch.empty(nv, dtype=torch.int32, device=dev)
-    check(L.o2345_mesh_decimate_emit(_p(verts_idx, torch.float64), tp, ib, nv, nt, _p(ws, torch.uint8), _p(verts, torch.float64),
-                                     _p(tris_out, tris.dtype), _p(cluster, torch.int32), _stream()), "mesh_decimate_emit")
+    call("o2345_mesh_decimate_emit", verts_idx, tris, ib, nv, nt, ws, verts, tris_out, cluster)
     return verts, tris_out, cluster, {"clusters": ncl.value, "vertices": nvo.value, "triangles": nto.value, "degenerate": ndeg.value, "duplicate": ndup.value}
 
 
@@ -1135,16 +1030,14 @@ def mesh_project(blob, vol_cl, verts_idx, resolution, iterations, level=0.0, tol
         raise ValueError(f"mesh_project: level must be finite, got {level!r}")
     resolution = _resolution(resolution, "mesh_project")
     _vertices(verts_idx)
-    (bmin, pmin), (bmax, pmax) = _bounds(bound_min, bound_max, "mesh_project")
+    bmin, bmax = _bounds(bound_min, bound_max, "mesh_project")
     mode = 2 if config.sdf_precision(precision) == "f16x3" else 0
-    L = _lib.lib()
     nv, dev = verts_idx.shape[0], verts_idx.device
-    wsb = L.o2345_mesh_project_workspace_bytes(nv)
-    ws = _workspace(wsb, dev, "mesh_project")
+    ws, wsb = _scratch("o2345_mesh_project_workspace_bytes", (nv,), dev, "mesh_project")
     out = torch.empty(nv, 3, dtype=torch.float64, device=dev)
     stats = torch.empty(_PROJECT_STATS_BYTES, dtype=torch.uint8, device=dev)
-    check(L.o2345_mesh_project(_p(blob), _p(vol_cl), vol_cl.shape[0], mode, _p(verts_idx, torch.float64), nv, int(resolution), pmin, pmax, iterations, level,
-                               tol, max_step, max_move, _p(ws, torch.uint8), wsb, _p(out, torch.float64), _p(stats, torch.uint8), _stream()), "mesh_project")
+    call("o2345_mesh_project", blob, vol_cl, vol_cl.shape[0], mode, verts_idx, nv, int(resolution), bmin, bmax, iterations, level, tol, max_step, max_move,
+         ws, wsb, out, stats)
     return out, project_info(stats.cpu().numpy(), iterations)
 
 
@@ -1194,19 +1087,16 @@ def mesh_surface_samples(verts, tris, spacing=None):
     fp64 [N,3], tris [M,3] int32 / int64, ``spacing`` None (one sample per triangle) or a finite float > 0 -> (points fp64 [n,3], weight fp64 [n], triangle
     int32 [n]), triangle-major.  One synchronisation, for the count; raises on 2^28 samples or more, a non-finite coordinate, an index out of range."""
     spacing = _distance_spacing(spacing)
-    tp, ib = _triangles(tris, "mesh_surface_samples")
+    tris, ib = _triangles(tris, "mesh_surface_samples")
     _vertices(verts, "mesh_surface_samples")
-    L = _lib.lib()
     nv, nt, dev = verts.shape[0], tris.shape[0], verts.device
-    wsb = L.o2345_mesh_samples_workspace_bytes(nt)
-    ws = _workspace(wsb, dev, "mesh_samples")
+    ws, wsb = _scratch("o2345_mesh_samples_workspace_bytes", (nt,), dev, "mesh_samples")
     n = ctypes.c_longlong()
-    check(L.o2345_mesh_samples_count(_p(verts, torch.float64), tp, ib, nv, nt, spacing, _p(ws, torch.uint8), wsb, ctypes.byref(n), _stream()), "mesh_samples_count")
+    call("o2345_mesh_samples_count", verts, tris, ib, nv, nt, spacing, ws, wsb, n)
     points = torch.empty(n.value, 3, dtype=torch.float64, device=dev)
     weight = torch.empty(n.value, dtype=torch.float64, device=dev)
     triangle = torch.empty(n.value, dtype=torch.int32, device=dev)
-    check(L.o2345_mesh_samples_emit(_p(verts, torch.float64), tp, ib, nv, nt, _p(ws, torch.uint8), n.value, _p(points, torch.float64), _p(weight, torch.float64),
-                                    _p(triangle, torch.int32), _stream()), "mesh_samples_emit")
+    call("o2345_mesh_samples_emit", verts, tris, ib, nv, nt, ws, n.value, points, weight, triangle)
     return points, weight, triangle
 
 
@@ -1219,22 +1109,19 @@ def mesh_distance_grid(verts, tris, cell=None, max_cells=None):
     coordinate, an index out of range, a target without a triangle that has an area."""
     if cell is not None and not (np.isfinite(cell) and cell > 0):
         raise ValueError(f"mesh_distance_grid: cell must be None or a finite float > 0, got {cell!r}")
-    tp, ib = _triangles(tris, "mesh_distance_grid")
+    tris, ib = _triangles(tris, "mesh_distance_grid")
     _vertices(verts, "mesh_distance_grid")
-    L = _lib.lib()
     nv, nt, dev = verts.shape[0], tris.shape[0], verts.device
     max_cells = min(2 ** 24, max(2 ** 20, 2 * nt)) if max_cells is None else int(max_cells)
-    wsb = L.o2345_mesh_distance_grid_workspace_bytes(nt, max_cells)
+    wsb = call("o2345_mesh_distance_grid_workspace_bytes", nt, max_cells)
     if not wsb:
         raise ValueError(f"mesh_distance_grid: bad sizes ({nt} triangles, max_cells = {max_cells}: 1 .. 2^24)")
     ws = _workspace(wsb, dev, "mesh_distance_grid")
     ne, ndeg, dims, edge = ctypes.c_longlong(), ctypes.c_longlong(), (ctypes.c_int * 3)(), ctypes.c_double()
-    check(L.o2345_mesh_distance_grid_count(_p(verts, torch.float64), tp, ib, nv, nt, 0.0 if cell is None else float(cell), max_cells, _p(ws, torch.uint8), wsb,
-                                           ctypes.byref(ne), ctypes.byref(ndeg), dims, ctypes.byref(edge), _stream()), "mesh_distance_grid_count")
-    nbytes = L.o2345_mesh_distance_grid_bytes(max_cells, ne.value)
+    call("o2345_mesh_distance_grid_count", verts, tris, ib, nv, nt, 0.0 if cell is None else float(cell), max_cells, ws, wsb, ne, ndeg, dims, edge)
+    nbytes = call("o2345_mesh_distance_grid_bytes", max_cells, ne.value)
     buf = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    check(L.o2345_mesh_distance_grid_emit(_p(verts, torch.float64), tp, ib, nv, nt, max_cells, _p(ws, torch.uint8), ne.value, _p(buf, torch.uint8), nbytes,
-                                          _stream()), "mesh_distance_grid_emit")
+    call("o2345_mesh_distance_grid_emit", verts, tris, ib, nv, nt, max_cells, ws, ne.value, buf, nbytes)
     return MeshGrid(buf, max_cells, ne.value, tuple(dims), edge.value, ndeg.value)
 
 
@@ -1244,15 +1131,14 @@ def mesh_closest_triangle(points, verts, tris, grid=None):
     [n]): the squared distance and the smallest index among the triangles that attain it; +inf and -1 where the target has no triangle with an area.
     points fp64 [n,3]; ``grid``: a MeshGrid of the same ``verts`` and ``tris`` (ops.mesh_distance_grid), or None for the exhaustive search -- the same
     bits either way.  No synchronisation."""
-    tp, ib = _triangles(tris, "mesh_closest_triangle")
+    tris, ib = _triangles(tris, "mesh_closest_triangle")
     _vertices(verts, "mesh_closest_triangle")
     _vertices(points, "mesh_closest_triangle")
     n, dev = points.shape[0], points.device
     d2 = torch.empty(n, dtype=torch.float64, device=dev)
     nearest = torch.empty(n, dtype=torch.int32, device=dev)
-    gp, gb, gm = (_p(grid.buffer, torch.uint8), grid.buffer.numel(), grid.max_cells) if grid is not None else (None, 0, 0)
-    check(_lib.lib().o2345_mesh_distance_query(_p(points, torch.float64), n, _p(verts, torch.float64), tp, ib, verts.shape[0], tris.shape[0], gp, gb, gm,
-                                               _p(d2, torch.float64), _p(nearest, torch.int32), _stream()), "mesh_distance_query")
+    gp, gb, gm = (grid.buffer, grid.buffer.numel(), grid.max_cells) if grid is not None else (None, 0, 0)
+    call("o2345_mesh_distance_query", points, n, verts, tris, ib, verts.shape[0], tris.shape[0], gp, gb, gm, d2, nearest)
     return d2, nearest
 
 
@@ -1261,14 +1147,11 @@ def mesh_distance_stats(d2, nearest, weight, thresholds=(), target=None, out=Non
     """The summary of one direction on the device -> the 128-byte stats block (uint8 [128], or ``out``): sums, the largest d2 as its bit pattern, counts;
     ``target`` = (verts, tris) adds the target's counters.  The same bytes on every run; no synchronisation.  ops.distance_summary reads it on the host."""
     th = np.ascontiguousarray(mesh_io._check_thresholds(thresholds), np.float64)
-    L = _lib.lib()
     n, dev = d2.shape[0], d2.device
-    wsb = L.o2345_mesh_distance_reduce_workspace_bytes(n)
-    ws = _workspace(wsb, dev, "mesh_distance_reduce")
+    ws, wsb = _scratch("o2345_mesh_distance_reduce_workspace_bytes", (n,), dev, "mesh_distance_reduce")
     stats = torch.empty(_DISTANCE_STATS_BYTES, dtype=torch.uint8, device=dev) if out is None else out
-    tv, (tp, ib), tnv, tnt = (None, (None, 4), 0, 0) if target is None else (target[0], _triangles(target[1], "mesh_distance_stats"), target[0].shape[0], target[1].shape[0])
-    check(L.o2345_mesh_distance_reduce(_p(d2, torch.float64), _p(nearest, torch.int32), _p(weight, torch.float64), n, th.ctypes.data_as(ctypes.c_void_p), len(th),
-                                       _p(tv, torch.float64), tp, ib, tnv, tnt, _p(ws, torch.uint8), wsb, _p(stats, torch.uint8), _stream()), "mesh_distance_reduce")
+    tv, (tt, ib), tnv, tnt = (None, (None, 4), 0, 0) if target is None else (target[0], _triangles(target[1], "mesh_distance_stats"), target[0].shape[0], target[1].shape[0])
+    call("o2345_mesh_distance_reduce", d2, nearest, weight, n, th, len(th), tv, tt, ib, tnv, tnt, ws, wsb, stats)
     return stats
 
 
@@ -1343,19 +1226,16 @@ def mesh_texture_points(verts_idx, tris, texel, resolution, bound_min=(-1.0, -1.
     world fp32 [cells c^2, 3], stats uint8 [16]), cell-major; the inputs are not written.  ``validate`` copies the counters to the host (one
     synchronisation) and raises on a non-finite coordinate or a triangle index out of range; a caller that queues more work passes False and hands the
     counters to texture_check after its own copy."""
-    tp, ib = _texture_mesh(verts_idx, tris, "mesh_texture_points")
+    tris, ib = _texture_mesh(verts_idx, tris, "mesh_texture_points")
     lay = mesh_io.texture_layout(tris.shape[0], texel)
     resolution = _resolution(resolution, "mesh_texture_points")
-    (bmin, pmin), (bmax, pmax) = _bounds(bound_min, bound_max, "mesh_texture_points")
-    L = _lib.lib()
+    bmin, bmax = _bounds(bound_min, bound_max, "mesh_texture_points")
     dev, n = verts_idx.device, lay["texels"]
-    assert L.o2345_mesh_texture_texels(tris.shape[0], lay["texel"], None, None) == n
+    assert call("o2345_mesh_texture_texels", tris.shape[0], lay["texel"], None, None) == n
     pts = torch.empty(n, 3, dtype=torch.float64, device=dev)
     world = torch.empty(n, 3, dtype=torch.float32, device=dev)
     stats = torch.empty(_TEXTURE_STATS_BYTES, dtype=torch.uint8, device=dev)
-    check(L.o2345_mesh_texture_points(_p(verts_idx, torch.float64), verts_idx.shape[0], tp, ib, tris.shape[0],
-                                       lay["texel"], int(resolution), pmin, pmax, _p(pts, torch.float64), _p(world), _p(stats, torch.uint8), _stream()),
-           "mesh_texture_points")
+    call("o2345_mesh_texture_points", verts_idx, verts_idx.shape[0], tris, ib, tris.shape[0], lay["texel"], int(resolution), bmin, bmax, pts, world, stats)
     if validate:
         texture_check(stats.cpu().numpy())
     return pts, world, stats
@@ -1368,7 +1248,7 @@ def mesh_texture_pack(rgb, nt, texel):
     if rgb.dim() != 2 or tuple(rgb.shape) != (lay["texels"], 3):
         raise ValueError(f"mesh_texture_pack: expected colours [{lay['texels']}, 3], got {tuple(rgb.shape)}")
     image = torch.empty(lay["height"], lay["width"], 4, dtype=torch.uint8, device=rgb.device)
-    check(_lib.lib().o2345_mesh_texture_pack(_p(rgb), int(nt), lay["texel"], _p(image, torch.uint8), _stream()), "mesh_texture_pack")
+    call("o2345_mesh_texture_pack", rgb, int(nt), lay["texel"], image)
     return image
 
 
@@ -1377,23 +1257,19 @@ def mesh_texture_corners(verts_idx, tris, texel, grid_R, bound_min=(-1.0, -1.0, 
     """The unwelded vertices of the textured asset (== mesh_io.texture_corners, to the last bit): (positions float32 [3M,3] in the asset frame, uv float32
     [3M,2], normals float32 [3M,3] or None, indices uint32-valued int32 storage [M,3] = 0, 1, 2, ..., bounds float32 [2,3]), all on the device.
     ``grad`` fp32 [N,3]: the SDF gradient at the (welded) vertices."""
-    tp, ib = _texture_mesh(verts_idx, tris, "mesh_texture_corners")
+    tris, ib = _texture_mesh(verts_idx, tris, "mesh_texture_corners")
     lay = mesh_io.texture_layout(tris.shape[0], texel)
     dev, m = verts_idx.device, tris.shape[0]
     if grad is not None and tuple(grad.shape) != (verts_idx.shape[0], 3):
         raise ValueError(f"mesh_texture_corners: expected gradients [{verts_idx.shape[0]}, 3], got {tuple(grad.shape)}")
-    frame, _keep = _mesh_frame(bound_min, bound_max, scale_mat, trans_mat)
+    frame = _mesh_frame(bound_min, bound_max, scale_mat, trans_mat)
     pos = torch.empty(3 * m, 3, dtype=torch.float32, device=dev)
     uv = torch.empty(3 * m, 2, dtype=torch.float32, device=dev)
     nrm = None if grad is None else torch.empty(3 * m, 3, dtype=torch.float32, device=dev)
     idx = torch.empty(m, 3, dtype=torch.int32, device=dev)
     bounds = torch.empty(2, 3, dtype=torch.float32, device=dev)
-    L = _lib.lib()
-    wsb = L.o2345_mesh_bounds_workspace_bytes(3 * m)
-    ws = _workspace(wsb, dev, "mesh_bounds")
-    check(L.o2345_mesh_texture_corners(_p(verts_idx, torch.float64), verts_idx.shape[0], tp, ib, m, lay["texel"],
-                                        int(grid_R), *frame, _p(grad), _p(pos), _p(uv), _p(nrm), _p(idx, torch.int32), _p(bounds),
-                                        _p(ws, torch.uint8), wsb, _stream()), "mesh_texture_corners")
+    ws, wsb = _scratch("o2345_mesh_bounds_workspace_bytes", (3 * m,), dev, "mesh_bounds")
+    call("o2345_mesh_texture_corners", verts_idx, verts_idx.shape[0], tris, ib, m, lay["texel"], int(grid_R), *frame, grad, pos, uv, nrm, idx, bounds, ws, wsb)
     return pos, uv, nrm, idx, bounds
 
 
@@ -1405,9 +1281,8 @@ def obj_texture_text(positions, uv, normals=None, K=None, bounds=None):
     K = _obj_digits(K, bounds, n, "obj_texture_text")
     if n % 3 or tuple(uv.shape) != (n, 2):
         raise ValueError(f"obj_texture_text: expected 3 M unwelded vertices and uv [3 M, 2], got {n} and {tuple(uv.shape)}")
-    L = _lib.lib()
-    text = torch.empty(L.o2345_obj_texture_text_bytes(n, K, int(normals is not None)), dtype=torch.uint8, device=positions.device)
-    check(L.o2345_obj_texture_text(_p(positions), _p(uv), _p(normals), n, K, _p(text, torch.uint8), _stream()), "obj_texture_text")
+    text = torch.empty(call("o2345_obj_texture_text_bytes", n, K, int(normals is not None)), dtype=torch.uint8, device=positions.device)
+    call("o2345_obj_texture_text", positions, uv, normals, n, K, text)
     return text
 
 
@@ -1419,7 +1294,6 @@ _SURFACE_INFO = ("hits", "entry_hits", "box_misses", "misses", "stalled", "bad_r
 def _surface_lattice(u, what):
     if u.dim() != 3 or len(set(u.shape)) != 1 or not 2 <= u.shape[0] <= 2048:
         raise ValueError(f"{what}: the lattice is float32 [R,R,R] with 2 <= R <= 2048, got {tuple(u.shape)}")
-    _p(u)
     return int(u.shape[0])
 
 
@@ -1430,7 +1304,7 @@ def surface_bricks(u, level=0.0, inside_positive=False):
     R = _surface_lattice(u, "surface_bricks")
     nb = (R - 1 + 7) // 8
     flags = torch.empty(nb, nb, nb, dtype=torch.uint8, device=u.device)
-    check(_lib.lib().o2345_surface_bricks(_p(u), R, float(level), int(bool(inside_positive)), _p(flags, torch.uint8), _stream()), "surface_bricks")
+    call("o2345_surface_bricks", u, R, float(level), int(bool(inside_positive)), flags)
     return flags
 
 
@@ -1459,7 +1333,7 @@ def surface_trace(u, rays_o, rays_d, near, far, stride=None, refine=None, level=
         raise ValueError(f"surface_trace: near, far and level must be finite, got {near!r}, {far!r}, {level!r}")
     if rays_o.dim() != 2 or rays_o.shape[1] != 3 or rays_d.shape != rays_o.shape:
         raise ValueError(f"surface_trace: rays_o / rays_d must both be [n,3] (got {tuple(rays_o.shape)}, {tuple(rays_d.shape)})")
-    (bmin, pmin), (bmax, pmax) = _bounds(bound_min, bound_max, "surface_trace")
+    bmin, bmax = _bounds(bound_min, bound_max, "surface_trace")
     n, dev = rays_o.shape[0], u.device
     H, W = (0, 0) if image_hw is None else (int(image_hw[0]), int(image_hw[1]))
     if image_hw is not None and (H < 1 or W < 1 or H * W != n):
@@ -1469,8 +1343,7 @@ def surface_trace(u, rays_o, rays_d, near, far, stride=None, refine=None, level=
     nb = (R - 1 + 7) // 8
     if skip and tuple(flags.shape) != (nb, nb, nb):
         raise ValueError(f"surface_trace: flags must be uint8 [{nb},{nb},{nb}] for R = {R}, got {tuple(flags.shape)}")
-    L = _lib.lib()
-    wsb = L.o2345_surface_trace_workspace_bytes(n)
+    wsb = call("o2345_surface_trace_workspace_bytes", n)
     if wsb == 0:
         raise ValueError(f"surface_trace: {n} rays are too many (n < 2^31)")
     hits = torch.empty(wsb // 4, dtype=torch.int32, device=dev)                # the workspace IS the hit list: owned by the result, not by the stream's cache
@@ -1478,9 +1351,8 @@ def surface_trace(u, rays_o, rays_d, near, far, stride=None, refine=None, level=
     kind = torch.empty(n, dtype=torch.uint8, device=dev)
     point = torch.empty(n, 3, dtype=torch.float32, device=dev)
     stats = torch.empty(_SURFACE_STATS_BYTES, dtype=torch.uint8, device=dev)
-    check(L.o2345_surface_trace(_p(u), R, _p(flags, torch.uint8) if skip else None, _p(rays_o), _p(rays_d), n, H, W, near, far, stride, refine, level,
-                                int(bool(inside_positive)), pmin, pmax, _p(hits, torch.int32), wsb, _p(depth), _p(kind, torch.uint8), _p(point),
-                                _p(stats, torch.uint8), _stream()), "surface_trace")
+    call("o2345_surface_trace", u, R, flags if skip else None, rays_o, rays_d, n, H, W, near, far, stride, refine, level, int(bool(inside_positive)), bmin, bmax,
+         hits, wsb, depth, kind, point, stats)
     out = dict(depth=depth, kind=kind, point=point, hits=hits[:n], n_hits=stats[64:68].view(torch.int32), stats=stats, info=None)
     if want_info:
         out["info"] = surface_info(stats.cpu().numpy(), n)
@@ -1507,7 +1379,7 @@ def camera_rays(K, c2w, H, W, device):
     with torch.cuda.device(device):
         o = torch.empty(H * W, 3, dtype=torch.float32, device=device)
         d = torch.empty(H * W, 3, dtype=torch.float32, device=device)
-        check(_lib.lib().o2345_camera_rays(K.ctypes.data_as(ctypes.c_void_p), M.ctypes.data_as(ctypes.c_void_p), H, W, _p(o), _p(d), _stream()), "camera_rays")
+        call("o2345_camera_rays", K, M, H, W, o, d)
     return o, d
 
 
@@ -1527,6 +1399,5 @@ def surface_pack(kind, depth, rgb, grad, H, W, background=(0, 0, 0, 0)):
     color = torch.empty(H, W, 4, dtype=torch.uint8, device=dev)
     normal = torch.empty(H, W, 4, dtype=torch.uint8, device=dev)
     out = torch.empty(H, W, dtype=torch.float32, device=dev)
-    check(_lib.lib().o2345_surface_pack(_p(kind, torch.uint8), _p(depth), _p(rgb), _p(grad), H, W, bg.ctypes.data_as(ctypes.c_void_p), _p(color, torch.uint8),
-                                        _p(normal, torch.uint8), _p(out), _stream()), "surface_pack")
+    call("o2345_surface_pack", kind, depth, rgb, grad, H, W, bg, color, normal, out)
     return color, normal, out
