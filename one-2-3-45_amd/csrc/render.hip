@@ -128,7 +128,8 @@ struct RoundArgs {
     // finalize
     float sample_dist;
     float* mid_z; float* dists; float* pts; float* pm; float* o_sdf; float* grad; float* rgb; int defaults_everywhere;
-    int merge_all_lists;                             // finalize + merge: also write the merged sdf / occupancy lists back (nobody reads them after the last round)
+    int merge_all_lists;                             // finalize + merge: also read the new samples' sdf / occupancy and write the merged lists back.  Set nowhere:
+                                                     // nobody reads them after the last round, and o2345_render_rays does not evaluate that SDF (it holds the default 100)
     // O2345RenderIO.segment_rays: the rays are consecutive render() calls of seg_rays rays evaluated together; the two per-call rules per segment
     int seg_rays, n_seg;                             // 0: the launch is one call
     int* seg_cnt;                                    // [n_seg] zeroed: list entries this round appends, per segment
@@ -893,7 +894,12 @@ int o2345_render_rays(const O2345RenderIO* io, void* workspace, size_t workspace
     if ((rc = ray_coarse_launch(io->rays_o, io->rays_d, R, io->near, io->far, io->near_ray, io->far_ray, NS, io->t_rand, z, pts, io->maskvol, io->D, msk, stream, counters))) return rc;
     // coarse SDF on ALL points (not masked, :525-528)
     if ((rc = sdf_eval(0, pts, nullptr, nullptr, (long long)NS * R, sdf, nullptr))) return rc;
-    // four up-sampling rounds (:531-547); round i > 0 first merges round i - 1's samples (cat_z_vals) inside the same kernel
+    // four up-sampling rounds (:531-547); round i > 0 first merges round i - 1's samples (cat_z_vals) inside the same kernel.  The SDF of the new
+    // samples is evaluated after rounds 0 - 2 only: round 3's samples are merged by the finalize round, which takes their depths alone (z_only in
+    // load_new_sample), and render_core evaluates the SDF again at the mid points -- the reference deletes the SDF its last cat_z_vals returns unread
+    // (:540-547).  A call is 1 + 3 launches of the SDF kernel and one of the SDF-gradient kernel.  Round 3 still writes its samples' points, default SDF
+    // (100 in every slot: what k_ray_merge_any carries along when NI != NFIX), occupancy bytes and list: a depths-only form of the round was measured
+    // and not kept (profiles/NOTES.md, round 10).
     RoundArgs ra{};
     ra.g = RayGeom{io->rays_o, io->rays_d, R};
     ra.z = z; ra.sdf = sdf; ra.msk = msk; ra.maskvol = io->maskvol; ra.D = io->D;
@@ -905,7 +911,7 @@ int o2345_render_rays(const O2345RenderIO* io, void* workspace, size_t workspace
         ra.seg_rays = G; ra.n_seg = n_seg; ra.seg_cnt = G ? segc + (size_t)i * n_seg : nullptr; ra.seg_prev = (G && i) ? segc + (size_t)(i - 1) * n_seg : nullptr;
         if ((rc = ray_round_launch(RM_UPSAMPLE, ra, wbuf, stream))) return rc;             // incl. cat_z_vals' "more than one point" rule (round_epilogue)
         cur += ra.n_new;
-        if ((rc = sdf_eval(0, pts, list, counters + RC_ROUND + i, 0, new_sdf, nullptr))) return rc;
+        if (i < 3 && (rc = sdf_eval(0, pts, list, counters + RC_ROUND + i, 0, new_sdf, nullptr))) return rc;      // round 3: nobody reads that SDF
     }
     int* count = counters + RC_FINAL;            // occupied mid-points: what the network kernels evaluate
     // :484 -- the caller passes the mean over the rays for per-ray near / far; the scalar form is (far - near) / n_samples

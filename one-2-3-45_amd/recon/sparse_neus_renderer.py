@@ -153,7 +153,7 @@ class SparseNeuSRenderer(nn.Module):
 
     # ---- the whole image behind the trainer's unchanged chunk loop ------------------------------------------------------------
     # GenericTrainer.val_step renders an image as `for ro, rd in zip(rays_o.split(512), rays_d.split(512)): render(ro, rd, ...)` (trainer_generic.py:503-524):
-    # 128 calls of 16 launches each for a 256^2 image, every launch latency-bound.  The chunks are VIEWS of one ray tensor, so the first call can see the
+    # 128 calls of 15 launches each for a 256^2 image, every launch latency-bound.  The chunks are VIEWS of one ray tensor, so the first call can see the
     # whole image: it renders EVERY 512-ray segment in one fused call (O2345RenderIO.segment_rays: the reference's two per-call rules and the per-call
     # scalars per segment -- bit-identical to the separate calls, tests/test_gpu_segments.py), draws the host random numbers of every chunk in the
     # reference's interleaved order (t_rand, pts_random, t_rand, ...), and the later calls return slices.  What a later call checks before it trusts the

@@ -322,7 +322,7 @@ def _run(dev, reps, resolution, cold, val, out_dir):
         tr.val_step(sample, st=st)
         res["val_step_warm_stages_ms"] = st.ms()
         res["val_rays_per_s_chunked"] = 65536 / (res["val_step_warm_ms_median"] * 1e-3)
-        # A/B: the same loop with the whole-image mode off (O2345_WHOLE_IMAGE=0): every 512-ray chunk is its own render call of 16 launches (round 4's path)
+        # A/B: the same loop with the whole-image mode off (O2345_WHOLE_IMAGE=0): every 512-ray chunk is its own render call of 15 launches (round 4's path)
         tr.sdf_renderer_lod0.whole_image = False
         try:
             tr.val_step(sample)
