@@ -338,6 +338,17 @@ int o2345_color_points_x3(const float* blob, const float* vol_cl, const float* m
                           const float* proj, const float* cam_pos, int V, int H, int W, const float* pts,
                           const int32_t* index, const int32_t* n_dev, long long n, const float* query_cam,
                           const float* normals, float* out_rgb, uint8_t* out_nviews, unsigned long long* stats_dev, void* stream);
+/* the two entries above with a tile queue: the 32-point tiles are not dealt to the waves in advance but claimed by whichever wave is free.
+ * tile_queue: 8 ints of caller device memory, cleared by the call on `stream` and in use until the launch has finished (one per launch in flight).
+ * Outputs and the sums in stats_dev are bit-identical to theirs. */
+int o2345_color_points_mfma_q(const float* blob, const float* vol_cl, const float* maskvol, int D, const float* cmaps,
+                              const float* proj, const float* cam_pos, int V, int H, int W, const float* pts,
+                              const int32_t* index, const int32_t* n_dev, long long n, const float* query_cam,
+                              const float* normals, float* out_rgb, uint8_t* out_nviews, unsigned long long* stats_dev, int32_t* tile_queue, void* stream);
+int o2345_color_points_x3_q(const float* blob, const float* vol_cl, const float* maskvol, int D, const float* cmaps,
+                            const float* proj, const float* cam_pos, int V, int H, int W, const float* pts,
+                            const int32_t* index, const int32_t* n_dev, long long n, const float* query_cam,
+                            const float* normals, float* out_rgb, uint8_t* out_nviews, unsigned long long* stats_dev, int32_t* tile_queue, void* stream);
 /* GeneralRenderingNetwork.forward on MATERIALISED inputs in the reference's own (view-major) layout (models/rendering_network.py:75-129):
  * geometry_feat [P,16], rgb_feat [V,P,59] (colours | features), ray_diff [V,P,4], mask [V,P] (non-zero = valid) -> rgb [P,3] and the number of
  * valid views [P] (optional).  blob: the x3 (x3 = 1) or fp32-MFMA (x3 = 0) packing of the network.  The fused Projector path above is the fast

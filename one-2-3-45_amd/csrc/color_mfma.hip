@@ -174,16 +174,21 @@ int o2345_color_x3_blob_floats(void) { return CX_TOTAL2; }
 
 // both numerical forms of o2345_color_points_*: x3 = 1 takes the blob of weights.pack_color_x3_blob (o2345_color_x3_blob_floats() floats), 0 that of
 // weights.pack_color_mfma_blob
-static int color_points(int x3, const float* blob, const float* vol_cl, const float* maskvol, int D, const float* cmaps, const float* proj,
-                        const float* cam_pos, int V, int H, int W, const float* pts, const int32_t* index, const int32_t* n_dev, long long n,
-                        const float* query_cam, const float* normals, float* out_rgb, uint8_t* out_nviews, unsigned long long* stats_dev, void* stream) {
+}  // extern "C"
+
+int o2345::color_points_launch(int x3, const float* blob, const float* vol_cl, const float* maskvol, int D, const float* cmaps, const float* proj,
+                               const float* cam_pos, int V, int H, int W, const float* pts, const int32_t* index, const int32_t* n_dev, long long n,
+                               const float* query_cam, const float* normals, float* out_rgb, uint8_t* out_nviews, unsigned long long* stats_dev,
+                               int32_t* tile_queue, void* stream) {
     O2345_REQUIRE(blob && vol_cl && maskvol && cmaps && proj && cam_pos && pts && out_rgb, "color_points: null pointer");
     O2345_REQUIRE((query_cam != nullptr) != (normals != nullptr), "color_points: give exactly one of query_cam / normals");
     O2345_REQUIRE(V >= 1 && V <= 255, "color_points: V must be in [1,255] (valid-view counts are stored as uint8; got %d)", V);
     if (n <= 0 && !n_dev) return 0;
+    O2345_REQUIRE(!tile_queue || n <= TQ_MAX_TILES * 32, "color_points: a tile queue indexes at most %lld tiles", TQ_MAX_TILES);
     ColorMArgs a{blob, vol_cl, maskvol, D, cmaps, proj, cam_pos, V, H, W, pts, index, n_dev, n, query_cam, normals, out_rgb, out_nviews};
     a.sched = color_sched_mode();
     a.stats = stats_dev;                         // optional, caller-owned work counters [4] (k_color_pts only)
+    a.tile_queue = tile_queue;                   // optional, zero at launch (k_color_pts only)
 #ifdef O2345_TILES_KERNEL
     // test-only variant: O2345_COLOR_KERNEL=tiles selects k_color_mfma (columns = (point, view) pairs, view count padded to a power of two <= 32, every
     // pair evaluated) -- the A/B partner of k_color_pts in tests/test_gpu_parity.py::test_color_points and tests/test_gpu_edges_and_fullsize.py
@@ -208,17 +213,44 @@ static int color_points(int x3, const float* blob, const float* vol_cl, const fl
     return color_pts_launch(a, x3, false, "color_points (points-as-columns kernel)", stream);
 }
 
+extern "C" {
+
+// the _q forms: the tail of the tile list goes through `tile_queue` (8 ints of caller memory, cleared here on the launch stream)
+static int color_points_q(int x3, const float* blob, const float* vol_cl, const float* maskvol, int D, const float* cmaps, const float* proj,
+                          const float* cam_pos, int V, int H, int W, const float* pts, const int32_t* index, const int32_t* n_dev, long long n,
+                          const float* query_cam, const float* normals, float* out_rgb, uint8_t* out_nviews, unsigned long long* stats_dev,
+                          int32_t* tile_queue, void* stream) {
+    O2345_REQUIRE(tile_queue, "color_points_q: null tile queue");
+    O2345_HIP(hipMemsetAsync(tile_queue, 0, TQ_HEADS * sizeof(int32_t), (hipStream_t)stream));
+    return color_points_launch(x3, blob, vol_cl, maskvol, D, cmaps, proj, cam_pos, V, H, W, pts, index, n_dev, n, query_cam, normals, out_rgb, out_nviews, stats_dev,
+                               tile_queue, stream);
+}
+int o2345_color_points_x3_q(const float* blob, const float* vol_cl, const float* maskvol, int D, const float* cmaps,
+                            const float* proj, const float* cam_pos, int V, int H, int W, const float* pts,
+                            const int32_t* index, const int32_t* n_dev, long long n, const float* query_cam,
+                            const float* normals, float* out_rgb, uint8_t* out_nviews, unsigned long long* stats_dev, int32_t* tile_queue, void* stream) {
+    return color_points_q(1, blob, vol_cl, maskvol, D, cmaps, proj, cam_pos, V, H, W, pts, index, n_dev, n, query_cam, normals, out_rgb, out_nviews, stats_dev,
+                          tile_queue, stream);
+}
+int o2345_color_points_mfma_q(const float* blob, const float* vol_cl, const float* maskvol, int D, const float* cmaps,
+                              const float* proj, const float* cam_pos, int V, int H, int W, const float* pts,
+                              const int32_t* index, const int32_t* n_dev, long long n, const float* query_cam,
+                              const float* normals, float* out_rgb, uint8_t* out_nviews, unsigned long long* stats_dev, int32_t* tile_queue, void* stream) {
+    return color_points_q(0, blob, vol_cl, maskvol, D, cmaps, proj, cam_pos, V, H, W, pts, index, n_dev, n, query_cam, normals, out_rgb, out_nviews, stats_dev,
+                          tile_queue, stream);
+}
+
 int o2345_color_points_mfma(const float* blob, const float* vol_cl, const float* maskvol, int D, const float* cmaps,
                             const float* proj, const float* cam_pos, int V, int H, int W, const float* pts,
                             const int32_t* index, const int32_t* n_dev, long long n, const float* query_cam,
                             const float* normals, float* out_rgb, uint8_t* out_nviews, unsigned long long* stats_dev, void* stream) {
-    return color_points(0, blob, vol_cl, maskvol, D, cmaps, proj, cam_pos, V, H, W, pts, index, n_dev, n, query_cam, normals, out_rgb, out_nviews, stats_dev, stream);
+    return color_points_launch(0, blob, vol_cl, maskvol, D, cmaps, proj, cam_pos, V, H, W, pts, index, n_dev, n, query_cam, normals, out_rgb, out_nviews, stats_dev, nullptr, stream);
 }
 int o2345_color_points_x3(const float* blob, const float* vol_cl, const float* maskvol, int D, const float* cmaps,
                           const float* proj, const float* cam_pos, int V, int H, int W, const float* pts,
                           const int32_t* index, const int32_t* n_dev, long long n, const float* query_cam,
                           const float* normals, float* out_rgb, uint8_t* out_nviews, unsigned long long* stats_dev, void* stream) {
-    return color_points(1, blob, vol_cl, maskvol, D, cmaps, proj, cam_pos, V, H, W, pts, index, n_dev, n, query_cam, normals, out_rgb, out_nviews, stats_dev, stream);
+    return color_points_launch(1, blob, vol_cl, maskvol, D, cmaps, proj, cam_pos, V, H, W, pts, index, n_dev, n, query_cam, normals, out_rgb, out_nviews, stats_dev, nullptr, stream);
 }
 
 // Projector.compute (query_cam) / compute_view_independent (normals) materialised: geometry_feat [P,16], rgb_feat [V,P,59], ray_diff [V,P,4],

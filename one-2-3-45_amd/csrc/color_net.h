@@ -67,9 +67,12 @@ struct ColorMArgs {
                               //   bit 1  priority 3 while a wave issues its pixel gathers: -1.5 %
                               //   bit 2  k_color_pts evaluates EVERY view (no skipping of views that see none of a tile's points): +13 % (the round-2 kernel)
                               //   bit 3  k_color_pts: block-interleaved tile schedule instead of one contiguous eighth of the list per XCD -- with view
-                              //          skipping a tile's cost depends on where its rays look: -1 % at 8 views, -20 % at 32 views
+                              //          skipping a tile's cost depends on where its rays look: -1 % at 8 views, -20 % at 32 views (the statically dealt
+                              //          tiles only: with a tile queue, below, the render call deals none)
                               //   bit 4  k_color_pts evaluates zero-weight pooling views (no skipping, in pass A, of a view that every point of the tile
                               //          sees with pooling weight 0; bit 2 turns this skipping off as well)
+    int* tile_queue;          // optional tile queue of k_color_pts (common.h: TQ_HEADS ints, zero at launch): the tail of the tile list is claimed by the waves
+                              // that have finished their static share.  Null: the static schedule alone.
 };
 
 inline int color_sched_mode() { return knobs().color_sched; }

@@ -125,6 +125,13 @@ __device__ __forceinline__ void sh_load(f32x16 (&acc)[2], const float4* slot) {
 // addresses) in scratch.  (Earlier forms: 512 threads at 199 VGPRs; a 768-thread build that kept the shared rows in registers spilled 140 B and lost,
 // 46.0 vs 45.2 ms.)
 constexpr int CP_THREADS = 768;
+// tile queue (a.tile_queue): share of the tile list that is claimed instead of dealt, 1 / 2^shift (0: all of it), and tiles per claim (a tile is about
+// 37 us: a claim's latency is noise).  Measured at 1/16, 1/8, 1/4, 1/2 and everything: the more is claimed the faster (profiles/NOTES.md, round 11) --
+// every wave starts at its XCD's head, so an XCD still works through one contiguous eighth of the list and then helps the others.
+#ifndef O2345_CP_TQ_SHARE_SHIFT
+#define O2345_CP_TQ_SHARE_SHIFT 0
+#endif
+constexpr int CP_TQ_SHARE_SHIFT = O2345_CP_TQ_SHARE_SHIFT, CP_TQ_CLAIM = 1;
 constexpr int CP_SH_FLOATS = 2 * 16 * 64;                                  // one wave's slot of shared rows
 // dynamic LDS: [A segments | biases and per-lane vectors] [scalars (4)] [one shared-row slot per wave]
 constexpr size_t color_pts_lds_bytes(int x3) {
@@ -155,11 +162,14 @@ __global__ __launch_bounds__(CP_THREADS) void k_color_pts(ColorMArgs a) {
     const int base_prio = (a.sched & 1) ? (wave >> 2) : 0;          // waves w, w + 4 and w + 8 share a SIMD (cyclic SIMD assignment over 4 SIMDs)
     if (a.sched & 1) set_wave_prio(base_prio);
     // bit 3 of O2345_COLOR_SCHED: block-interleaved tiles instead of one contiguous eighth of the list per XCD (A/B: with view skipping the
-    // cost of a tile depends on where its rays look, and a contiguous eighth of the image is not an eighth of the work)
-    const TileSched ts = (a.sched & 8) ? TileSched{(long long)blockIdx.x * nwave + wave, (n + 31) / 32, (long long)gridDim.x * nwave}
-                                       : tile_schedule(n, 32, wave, nwave);
+    // cost of a tile depends on where its rays look, and a contiguous eighth of the image is not an eighth of the work).  With a tile queue the last
+    // 1 / 2^CP_TQ_SHARE_SHIFT of the list is not dealt but claimed, CP_TQ_CLAIM tiles at a time (common.h; profiles/NOTES.md round 11 has the arms).
+    const TileQueue tq = tile_queue_split((n + 31) / 32, (long long)gridDim.x * nwave, CP_TQ_SHARE_SHIFT, a.tile_queue != nullptr);
+    const TileSched ts = (a.sched & 8) ? tile_schedule_flat_at(tq.n_static, blockIdx.x, gridDim.x, wave, nwave) : tile_schedule_tiles(tq.n_static, wave, nwave);
+    const auto static_end = [&](long long n_static) { return (a.sched & 8) ? n_static : tile_schedule_tiles(n_static, wave, nwave).end; };
+    TileCursor cur;
     unsigned st_a = 0, st_b = 0, st_t = 0, st_full = 0;          // wave-uniform work counters (a.stats)
-    for (long long tile = ts.first; tile < ts.end; tile += ts.stride) {
+    for (long long tile = tile_first<CP_TQ_CLAIM>(cur, ts, tq, a.tile_queue); tile >= 0; tile = tile_next<CP_TQ_CLAIM>(cur, tile, (n + 31) / 32, a.tile_queue, static_end)) {
         const long long i = tile * 32 + j;
         const bool live = i < n;
         const long long slot = live ? (a.index ? (long long)a.index[i] : i) : 0;

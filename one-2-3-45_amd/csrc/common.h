@@ -96,10 +96,12 @@ __device__ __forceinline__ int block_prefix(bool pred, int* lds_wave_tot /*[NWAV
 //   O2345_COLOR_KERNEL=tiles  (only in a -DO2345_TILES_KERNEL test build) the (point, view)-column colour kernel instead of k_color_pts
 //   O2345_RAY_STREAM_MIN=n  render call: ray batches of at least n rays run the streaming sampler kernels (one lane per ray, lists read from global
 //                         memory at full occupancy), smaller ones the sixteen-lanes-per-ray kernels (default 4096; 0 = always streaming, a huge value = never)
+//   O2345_TILE_QUEUE=0    render call: the persistent network kernels run their static tile schedule alone (no tile queue for the tail; A/B switch)
 struct Knobs {
     bool list_sort, sparse_brick, flat_sched, color_tiles;
     int color_sched;
     long long ray_stream_min;
+    bool tile_queue;
 };
 inline const Knobs& knobs() {
     static const Knobs k = [] {
@@ -107,7 +109,7 @@ inline const Knobs& knobs() {
         const char* cs = getenv("O2345_COLOR_SCHED");
         const char* rs = getenv("O2345_RAY_STREAM_MIN");
         return Knobs{!is("O2345_LIST_SORT", '0'), !is("O2345_SPARSE_BRICK", '0'), is("O2345_FLAT_SCHED", '1'), is("O2345_COLOR_KERNEL", 't'), cs ? atoi(cs) : 10,
-                     rs ? atoll(rs) : 4096};
+                     rs ? atoll(rs) : 4096, !is("O2345_TILE_QUEUE", '0')};
     }();
     return k;
 }
@@ -148,20 +150,112 @@ inline unsigned network_grid(long long n, const void* n_dev, int threads, int un
     return persistent_grid(n_dev ? n_cu : (n + per_block - 1) / per_block, n_cu);
 }
 
-#if defined(__HIPCC__)
 // Tile schedule of the persistent network kernels.  Workgroups are dispatched round-robin over the 8 XCDs (block b runs on XCD
 // b % 8) and every XCD has its own 4 MB L2: handing consecutive tiles to consecutive blocks makes each XCD stream the whole
 // working set (source-view maps, latent volume) through its L2.  Instead every XCD gets one contiguous eighth of the tile list
 // (neighbouring rays / samples share map pixels and voxels), interleaved over its own blocks and waves.
 struct TileSched { long long first, end, stride; };
-__device__ __forceinline__ TileSched tile_schedule(long long n_units, int units_per_tile, int wave, int nwave) {
-    const long long ntiles = (n_units + units_per_tile - 1) / units_per_tile;
-    if ((gridDim.x & 7) == 0) {
-        const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, per_xcd = gridDim.x >> 3;
+O2345_HD TileSched tile_schedule_flat_at(long long ntiles, int block, int grid, int wave, int nwave) {      // block-interleaved over the whole list
+    return {(long long)block * nwave + wave, ntiles, (long long)grid * nwave};
+}
+O2345_HD TileSched tile_schedule_at(long long ntiles, int block, int grid, int wave, int nwave) {
+    if ((grid & 7) == 0) {
+        const int xcd = block & 7, slot = block >> 3, per_xcd = grid >> 3;
         const long long chunk = (ntiles + 7) / 8, lo = xcd * chunk, hi = lo + chunk;
         return {lo + (long long)slot * nwave + wave, hi < ntiles ? hi : ntiles, (long long)per_xcd * nwave};
     }
-    return {(long long)blockIdx.x * nwave + wave, ntiles, (long long)gridDim.x * nwave};
+    return tile_schedule_flat_at(ntiles, block, grid, wave, nwave);
+}
+
+// Tile queue: the static schedule above ends a kernel when its slowest wave ends.  With a queue (eight int32 heads in caller memory, zero at launch) only
+// tiles [0, n_static) are dealt statically -- the same number to every wave -- and the tail [n_static, n_tiles) is claimed, C consecutive tiles per claim, by
+// whichever wave has finished its share.  The tail is cut into eight sub-ranges with one head each: a wave starts at head block % 8 (its XCD: one head word
+// takes about 88 claims per microsecond, and thousands of waves drain the tail of a short launch at once) and moves on cyclically when a sub-range is
+// exhausted.  A claim orders nothing (no wave reads what another wrote): one relaxed atomic add, no fence.  The index arithmetic is host-callable
+// (tests/hostcheck/tile_queue_check.hip simulates the claims).
+constexpr int TQ_HEADS = 8;
+constexpr long long TQ_MAX_TILES = (1ll << 31) - 64;                     // the tail is indexed with 32-bit integers (the heads are int32)
+struct TileQueue { long long n_static; int n_dyn, per_head; };            // tiles dealt statically, tiles in the tail, tiles per sub-range
+O2345_HD TileQueue tile_queue_of(long long ntiles, int n_dyn) { return {ntiles - n_dyn, n_dyn, (n_dyn + TQ_HEADS - 1) / TQ_HEADS}; }
+// share_shift: the tail is 1 / 2^share_shift of the list (0: everything); queued = false: the static schedule alone.  ntiles <= TQ_MAX_TILES.
+O2345_HD TileQueue tile_queue_split(long long ntiles, long long total_waves, int share_shift, bool queued) {
+    if (!queued) return {ntiles, 0, 0};
+    long long ns = ntiles - (ntiles >> share_shift);
+    ns -= ns % total_waves;
+    return tile_queue_of(ntiles, (int)(ntiles - ns));
+}
+O2345_HD int tile_queue_lo(const TileQueue& q, int head) {                // first tile of a sub-range, relative to n_static; head == TQ_HEADS: the tail's end
+    const long long lo = (long long)head * q.per_head;
+    return lo < q.n_dyn ? (int)lo : q.n_dyn;
+}
+struct TileWalk { int head, left; };                                      // current head, heads not yet found exhausted
+O2345_HD TileWalk tile_walk_begin(int block) { return {block & (TQ_HEADS - 1), TQ_HEADS}; }
+// outcome of one claim (`claimed`: what the atomic add of C to heads[w.head] returned): the claim's first tile and `end`, or -1 after moving to the next head
+O2345_HD long long tile_walk_take(const TileQueue& q, TileWalk& w, int claimed, int C, long long& end) {
+    const long long t = (long long)tile_queue_lo(q, w.head) + claimed, hi = tile_queue_lo(q, w.head + 1);
+    if (t < hi) {
+        end = q.n_static + (t + C < hi ? t + C : hi);
+        return q.n_static + t;
+    }
+    w.head = (w.head + 1) & (TQ_HEADS - 1);
+    --w.left;
+    return -1;
+}
+
+// The launch function behind o2345_color_points_{x3,mfma}[_q] (csrc/color_mfma.hip): the public entry points' arguments plus the queue, which must be zero
+// when the kernel starts (the _q entry points clear it on the stream; o2345_render_rays hands out counters that its first kernel clears).
+int color_points_launch(int x3, const float* blob, const float* vol_cl, const float* maskvol, int D, const float* cmaps, const float* proj,
+                        const float* cam_pos, int V, int H, int W, const float* pts, const int32_t* index, const int32_t* n_dev, long long n,
+                        const float* query_cam, const float* normals, float* out_rgb, uint8_t* out_nviews, unsigned long long* stats_dev, int32_t* tile_queue,
+                        void* stream);
+
+#if defined(__HIPCC__)
+__device__ __forceinline__ TileSched tile_schedule_tiles(long long ntiles, int wave, int nwave) {
+    return tile_schedule_at(ntiles, blockIdx.x, gridDim.x, wave, nwave);
+}
+__device__ __forceinline__ TileSched tile_schedule(long long n_units, int units_per_tile, int wave, int nwave) {
+    return tile_schedule_tiles((n_units + units_per_tile - 1) / units_per_tile, wave, nwave);
+}
+
+// The tile loop of a kernel that takes a queue:
+//     for (long long tile = tile_first<C>(cur, ts, q, heads); tile >= 0; tile = tile_next<C>(cur, tile, ntiles, heads, static_end))
+// with q = tile_queue_split(ntiles, ...) and ts the static schedule over q.n_static tiles.  heads == nullptr: the static loop.  All of the state is
+// wave-uniform, and what lives across a tile's body is kept small (these kernels have no scalar register to spare): the stride, the tail's length and the
+// packed walk.  The rest is derived again from them at the end of each tile (static_end: see tile_next); the empty asm keeps the compiler from hoisting
+// that out of the loop.
+struct TileCursor { int stride, n_dyn, walk; long long claim_end; };      // stride == 0: the static share is done; walk = head | left << 4; claim_end: C > 1 only
+template <int C>
+__device__ __forceinline__ long long tile_claim(TileCursor& c, const TileQueue& q, int* heads) {
+    c.stride = 0;
+    TileWalk w{c.walk & 15, c.walk >> 4};
+    long long first = -1;
+    while (first < 0 && w.left > 0) {
+        int t = 0;
+        if (lane_id() == 0) t = __hip_atomic_fetch_add(heads + w.head, C, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        first = tile_walk_take(q, w, __builtin_amdgcn_readfirstlane(t), C, c.claim_end);
+    }
+    c.walk = w.head | w.left << 4;
+    return first;
+}
+template <int C>
+__device__ __forceinline__ long long tile_first(TileCursor& c, const TileSched& ts, const TileQueue& q, int* heads) {
+    const TileWalk w = tile_walk_begin(blockIdx.x);
+    c = TileCursor{(int)ts.stride, q.n_dyn, w.head | w.left << 4, 0};
+    if (ts.first < ts.end) return ts.first;
+    return heads ? tile_claim<C>(c, q, heads) : -1;
+}
+template <int C, class StaticEnd>           // static_end(n_static): this wave's TileSched::end of the static schedule over n_static tiles
+__device__ __forceinline__ long long tile_next(TileCursor& c, long long tile, long long ntiles, int* heads, StaticEnd&& static_end) {
+    asm volatile("" : "+s"(c.n_dyn));
+    const TileQueue q = tile_queue_of(ntiles, c.n_dyn);
+    if (c.stride) {
+        tile += c.stride;
+        if (tile < static_end(q.n_static)) return tile;
+        if (!heads) return -1;
+    } else if (C > 1 && tile + 1 < c.claim_end) {
+        return tile + 1;
+    }
+    return tile_claim<C>(c, q, heads);
 }
 #endif
 

@@ -16,9 +16,11 @@ enum RenderCounter {
     RC_FINAL = 4,       // list entries of the finalize round (the occupied mid-points)
     RC_CULLED = 5,      // entries of the weight-culled list (k_ray_cull)
     RC_DONE = 8,        // + i, i < 5: finished workgroups of round i (4 = finalize): round_epilogue
-    RC_CLEARED = 16,    // counters cleared per call
+    RC_QUEUE = 16,      // + i, i < 8: the tile queue (common.h) of the call's colour launch
+    RC_CLEARED = 24,    // counters cleared per call
     RC_RESERVED = 64    // ints the workspace holds
 };
+static_assert(RC_QUEUE + TQ_HEADS <= RC_CLEARED && RC_CLEARED <= RC_RESERVED && RC_CLEARED <= 256, "k_ray_coarse clears the counters with one 256-thread workgroup");
 
 // coarse samples: z = near + (far-near) * linspace(0,1,S)  and their points, point index p = s*R + r
 // t_rand (optional): the reference's stratified jitter (sparse_neus_renderer.py:506-515).  The reference draws
@@ -962,9 +964,10 @@ int o2345_render_rays(const O2345RenderIO* io, void* workspace, size_t workspace
     // valid-view counts (feed the per-ray colour mask): the colour kernels write them for the points they evaluate (the occupied ones, 88 % at
     // BASELINE config 2); this pass covers the rest (four IEEE divisions per view make it VALU-bound: 0.48 ms over all points)
     if ((rc = o2345_view_count_unlisted(fpts, (long long)S * R, counted_elsewhere, io->maskvol, io->D, io->proj, io->V, io->H, io->W, io->nviews, stream))) return rc;
-    const auto color_points = io->color_x3_blob ? o2345_color_points_x3 : o2345_color_points_mfma;
-    rc = color_points(io->color_x3_blob ? io->color_x3_blob : io->color_mfma_blob, io->vol_cl, io->maskvol, io->D, io->cmaps, io->proj, io->cam_pos, io->V, io->H, io->W, fpts, clist,
-                      ccount, 0, io->query_cam, nullptr, io->rgb, io->nviews, io->color_stats, stream);
+    // the colour kernel's tile queue: eight of the call's counters (O2345_TILE_QUEUE=0: none, the static schedule)
+    rc = color_points_launch(io->color_x3_blob != nullptr, io->color_x3_blob ? io->color_x3_blob : io->color_mfma_blob, io->vol_cl, io->maskvol, io->D, io->cmaps, io->proj,
+                             io->cam_pos, io->V, io->H, io->W, fpts, clist, ccount, 0, io->query_cam, nullptr, io->rgb, io->nviews, io->color_stats,
+                             knobs().tile_queue ? counters + RC_QUEUE : nullptr, stream);
     if (rc) return rc;
     if ((rc = o2345_ray_composite(io->rays_o, io->rays_d, R, (int)S, io->mid_z, io->dists, io->pm, io->sdf, io->grad, io->rgb, io->nviews, io->inv_s, io->alpha_inter_ratio, io->background,
                                   io->color, io->depth, io->weights, io->cdf, io->weights_sum, io->weights_max, io->depth_var, io->alpha_sum, io->grad_err, io->color_mask, stream))) return rc;

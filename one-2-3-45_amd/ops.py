@@ -519,6 +519,18 @@ def color_stats_buffer(device):
     return torch.zeros(4, dtype=torch.int64, device=device)
 
 
+def tile_queue_buffer(device):
+    """Eight int32 on the device for ``color_points(..., tile_queue=buf)``: the heads of the launch's tile queue
+    (csrc/common.h).  The call clears them on its stream; a buffer serves one launch at a time."""
+    return torch.empty(8, dtype=torch.int32, device=device)
+
+
+def _tile_queue(buf):
+    if buf.dtype != torch.int32 or buf.numel() < 8 or not buf.is_contiguous():
+        raise ValueError("tile_queue: 8 contiguous int32 on the device expected (ops.tile_queue_buffer)")
+    return buf
+
+
 def color_stats_read(buf):
     out = [int(x) for x in buf.cpu().tolist()]
     return dict(pairs_pooling=out[0], pairs_network=out[1], tiles=out[2], tiles_all_views=out[3])
@@ -526,20 +538,31 @@ def color_stats_read(buf):
 
 @_on_device
 def color_points(blob, vol_cl, maskvol, cmaps, proj, cam_pos, pts, query_cam=None, normals=None, index=None, n_dev=None,
-                 want_nviews=True, mfma="x3", stats=None):
+                 want_nviews=True, mfma="x3", stats=None, tile_queue=None, out=None):
     """Projector + GeneralRenderingNetwork fused (k_color_pts).  mfma="x3": split-f16 matrix steps (blob from weights.pack_color_x3_blob, the default
-    numerical mode); mfma=True: fp32 matrix-core form (pack_color_mfma_blob).  Any view count up to 255.  stats: color_stats_buffer()."""
+    numerical mode); mfma=True: fp32 matrix-core form (pack_color_mfma_blob).  Any view count up to 255.  stats: color_stats_buffer().
+    tile_queue: tile_queue_buffer() -- the tail of the tile list is claimed by the waves that finish first (the _q entry points); same results bit for
+    bit.  out: (rgb [P,3] float32, nviews [P] uint8 or None) to write into instead of fresh zeroed tensors (slots not listed stay untouched)."""
     if mfma is False or mfma is None:
         raise ValueError("color_points: the pure-VALU colour kernel was removed in ABI 2.0; pass mfma='x3' (split-f16) or mfma=True (fp32 MFMA)")
     V, H, W, _ = cmaps.shape
     P = pts.shape[0]
     n = P if index is None else index.shape[0]
-    rgb = torch.zeros(P, 3, dtype=torch.float32, device=pts.device)
-    nv = torch.zeros(P, dtype=torch.uint8, device=pts.device) if want_nviews else None
+    if out is not None:
+        rgb, nv = out
+        if tuple(rgb.shape) != (P, 3) or rgb.dtype != torch.float32 or (nv is not None and (tuple(nv.shape) != (P,) or nv.dtype != torch.uint8)):
+            raise ValueError(f"color_points: out = (rgb [{P},3] float32, nviews [{P}] uint8 or None) expected")
+    else:
+        rgb = torch.zeros(P, 3, dtype=torch.float32, device=pts.device)
+        nv = torch.zeros(P, dtype=torch.uint8, device=pts.device) if want_nviews else None
     if P == 0 or (n == 0 and n_dev is None):
         return rgb, nv
-    call("o2345_color_points_x3" if mfma == "x3" else "o2345_color_points_mfma", blob, vol_cl, maskvol, vol_cl.shape[0], cmaps, proj, cam_pos,
-         V, H, W, pts, index, n_dev, n, query_cam, normals, rgb, nv, stats)
+    entry = "o2345_color_points_x3" if mfma == "x3" else "o2345_color_points_mfma"
+    if tile_queue is not None:
+        call(entry + "_q", blob, vol_cl, maskvol, vol_cl.shape[0], cmaps, proj, cam_pos, V, H, W, pts, index, n_dev, n, query_cam, normals, rgb, nv, stats,
+             _tile_queue(tile_queue))
+    else:
+        call(entry, blob, vol_cl, maskvol, vol_cl.shape[0], cmaps, proj, cam_pos, V, H, W, pts, index, n_dev, n, query_cam, normals, rgb, nv, stats)
     return rgb, nv
 
 
