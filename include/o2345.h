@@ -8,10 +8,11 @@
  *
  * Conventions
  *   - extern "C", plain pointers and sizes, no torch / C++ types.  A pointer is a HOST pointer if and only if its name
- *     ends in _host, or the function's name ends in _host, or it points to a struct (O2345RenderIO* io); every other
- *     pointer, the struct's fields among them, is a DEVICE pointer.  A binding reads this, and every pointer's element
- *     type, from the declarations below (one-2-3-45_amd/_lib.py does).  The caller owns every buffer; the library
- *     never allocates, frees or retains them.
+ *     ends in _host, or the function's name ends in _host; every other pointer, a struct's fields among them, is a
+ *     DEVICE pointer.  A binding reads this, and every pointer's element type, from the declarations below
+ *     (one-2-3-45_amd/_lib.py does).  The caller owns every buffer; the library never allocates, frees or retains them.
+ *   - every struct that crosses this boundary is declared below, once (typedef struct O2345...): csrc/ compiles that declaration, a binding
+ *     generates its own from the same text and checks it against o2345_struct_size / o2345_struct_layout of the loaded library.
  *   - every function returns 0 on success, a negative code on error; o2345_last_error() (thread-local) explains.
  *   - `stream` is a hipStream_t (NULL = default stream).  Functions are asynchronous unless stated otherwise and
  *     re-entrant (one Python thread per device under nn.DataParallel is fine).
@@ -57,12 +58,16 @@ const char* o2345_last_error(void);
  * o2345_sdf_grid_sparse_x3; the mesh distance entries o2345_mesh_samples_workspace_bytes, o2345_mesh_samples_count, o2345_mesh_samples_emit,
  * o2345_mesh_distance_grid_workspace_bytes, o2345_mesh_distance_grid_bytes, o2345_mesh_distance_grid_count, o2345_mesh_distance_grid_emit,
  * o2345_mesh_distance_query, o2345_mesh_distance_reduce_workspace_bytes, o2345_mesh_distance_reduce. */
+/* 220 = ABI 2.2: the four device stats blocks are declared structs (O2345ProjectStats, O2345TextureStats, O2345SurfaceStats, O2345DistanceStats; no byte
+ * of them moved, the untyped `stats` parameters became pointers to them); o2345_struct_size / o2345_struct_layout describe every declared struct and replace
+ * o2345_render_io_size / o2345_render_io_layout; the parameter of o2345_render_rays is called io_host. */
 int o2345_version(void);
-/* Layout self-description of O2345RenderIO as THIS library was compiled (sizeof, and offsetof of every field in declaration order): a binding
- * asserts its own struct against it at load time (one-2-3-45_amd/_lib.py does) -- a field added on one side only cannot corrupt calls silently.
- * render_io_layout writes min(n, number of fields) offsets and returns the number of fields. */
-size_t o2345_render_io_size(void);
-int o2345_render_io_layout(size_t* offsets_host, int n);
+/* Layout self-description of the declared structs as THIS library was compiled (sizeof, and offsetof of every field in declaration order): a binding
+ * asserts its own structs against it at load time (one-2-3-45_amd/_lib.py does) -- a field added on one side only cannot corrupt calls silently.
+ * which: the struct's position among the `typedef struct O2345...` declarations of this header, from 0.  struct_layout writes min(n, number of fields)
+ * offsets and returns the number of fields; both return 0 for a `which` out of range. */
+size_t o2345_struct_size(int which);
+int o2345_struct_layout(int which, size_t* offsets_host, int n);
 /* The debug / A-B knobs this library instance runs with, e.g. "list_sort=1 sparse_brick=1 flat_sched=0 color_tiles=0 color_sched=10".  They are read from
  * the environment (O2345_LIST_SORT, O2345_SPARSE_BRICK, O2345_FLAT_SCHED, O2345_COLOR_KERNEL, O2345_COLOR_SCHED) ONCE, at the first call that needs
  * them -- this call included --, never on a launch path. */
@@ -249,7 +254,7 @@ int o2345_ray_composite(const float* rays_o, const float* rays_d, int R, int S, 
                         float* alpha_sum, float* grad_err, uint8_t* color_mask, void* stream);
 
 /* One render() call (models/sparse_neus_renderer.py:457-635).  The struct is declared HERE only: csrc/ includes this header, the ctypes binding
- * generates its Structure from this text and checks it against o2345_render_io_size / o2345_render_io_layout of the loaded library. */
+ * generates its Structure from this text and checks it against o2345_struct_size / o2345_struct_layout of the loaded library. */
 typedef struct O2345RenderIO {
     /* scene */
     const float* sdf_blob;          /* weights.pack_sdf_blob */
@@ -302,7 +307,7 @@ int o2345_list_sort_by_visibility(const float* pts, const int32_t* list, const i
                                   int32_t* list_out, uint32_t* keys_out, void* workspace, size_t workspace_bytes, void* stream);
 /* V: the scene's view count -- the list-sort buffers are part of the workspace only when the call will sort its list (V <= 32 and at least 2^20 sample slots) */
 size_t o2345_render_workspace_bytes(int R, int n_samples, int n_importance, int V);
-int o2345_render_rays(const O2345RenderIO* io, void* workspace, size_t workspace_bytes, void* stream);
+int o2345_render_rays(const O2345RenderIO* io_host, void* workspace, size_t workspace_bytes, void* stream);
 
 /* proj [V,3,4] = intrinsics [V,3,3] @ w2cs[:, :3, :] (models/render_utils.py:106) and cam_pos [V,3] = inverse(w2cs)[:, :3, 3] (models/projector.py:60-70)
  * in ONE launch, no BLAS / solver library behind it (the first torch.matmul + torch.inverse of a process cost 180 ms of library initialisation
@@ -450,17 +455,22 @@ int o2345_mesh_decimate_emit(const double* verts, const void* tris, int index_by
  * blob, vol_cl, D as for o2345_sdf_mlp; verts device fp64 [nv,3], only read; 0 <= nv < 2^30; grid_R >= 2; bound_min / bound_max HOST float32 [3] as
  * for o2345_mesh_pack_vertices, bound_max > bound_min; iterations in [1, 64]; level finite; tol finite, >= 0; max_step, max_move finite, > 0.
  * workspace: mesh_project_workspace_bytes(nv) bytes (0 for bad sizes), 16-byte aligned.  verts_out device fp64 [nv,3], not verts.  stats: device,
- * 328 bytes, 8-byte aligned, written by this call:
- *   uint64 [8]  = vertices with a non-finite coordinate, converged, unconverged, stalled, clamped events, max_before, max_after, 0 -- the two maxima
- *                 as the bit pattern of a non-negative double (max of r in round 0; max of the r at which the vertices left or ended; non-finite r
- *                 take no part; 0 for an empty mesh);
- *   int32 [66]  = active vertices per round, entries 0 .. iterations; the rest 0.
- * No host synchronisation: all rounds are queued at once, the counts stay on the device.  A non-zero first counter means bad input: the caller raises
- * (the affected vertices stall, nothing is dereferenced through them).  Errors: bad arguments, a workspace that is too small. */
+ * 8-byte aligned, written by this call.  No host synchronisation: all rounds are queued at once, the counts stay on the device.  A non-zero
+ * n_nonfinite means bad input: the caller raises (the affected vertices stall, nothing is dereferenced through them).  Errors: bad arguments, a
+ * workspace that is too small. */
+typedef struct O2345ProjectStats {
+    unsigned long long n_nonfinite;                     /* vertices with a non-finite coordinate */
+    unsigned long long converged, unconverged, stalled;
+    unsigned long long clamped;                         /* clamped events */
+    unsigned long long max_before, max_after;           /* the bit pattern of a non-negative double: the max of r in round 0; the max of the r at which the
+                                                         * vertices left or ended; non-finite r take no part; 0 for an empty mesh */
+    unsigned long long reserved;                        /* 0 */
+    int count[66];                                      /* active vertices per round, entries 0 .. iterations; the rest 0 */
+} O2345ProjectStats;
 size_t o2345_mesh_project_workspace_bytes(long long nv);
 int o2345_mesh_project(const float* blob, const float* vol_cl, int D, int sdf_mode, const double* verts, long long nv, int grid_R, const float* bound_min_host,
                        const float* bound_max_host, int iterations, double level, double tol, double max_step, double max_move, void* workspace,
-                       size_t workspace_bytes, double* verts_out, void* stats, void* stream);
+                       size_t workspace_bytes, double* verts_out, O2345ProjectStats* stats, void* stream);
 
 /* ---- mesh serialisation (replaces the numpy / trimesh tail of validate_mesh and validate_colored_mesh,
  * models/trainer_generic.py:1287-1303, 1365-1382: index -> world frame, scale_mat, trans_mat, uint8 colours, PLY records) -----
@@ -529,8 +539,8 @@ int o2345_obj_text_host(const float* positions, const uint8_t* rgba, const float
  * and the world point float32(p / (R - 1) * ext + bmin) as o2345_mesh_project defines it; fp64, one operation at a time, in the order written: equal to
  * mesh_io.texture_points to the last bit.  verts device fp64 [nv,3], tris device int32 / int64 [nt,3] (index_bytes 4 / 8), both only read; 1 <= nv <
  * 2^30; bound_min / bound_max HOST float32 [3], bound_max > bound_min.  Outputs, device: points_idx fp64 [texels,3], points_world float32 [texels,3],
- * stats (16 bytes, 8-byte aligned) = uint64 [2]: triangles with a non-finite corner coordinate, triangles with an index outside [0, nv).  Such an index is
- * read as vertex 0, never dereferenced; a non-zero counter means bad input and the caller raises.  No host synchronisation.
+ * stats (8-byte aligned), written by this call.  An index outside [0, nv) is read as vertex 0, never dereferenced; a non-zero counter means bad input
+ * and the caller raises.  No host synchronisation.
  * mesh_texture_pack: rgb device fp32 [texels,3] in the order above -> image device uint8 [H,W,4], 4-byte aligned, raster order: the truncating
  * quantisation of the vertex colours, alpha 255; texels of unused cells are 0, 0, 0, 0.
  * mesh_texture_corners: the unwelded vertices.  Triangle t = (a, b, c) gives vertices 3t, 3t + 1, 3t + 2 = c, b, a (the asset frame's reversed winding):
@@ -538,9 +548,14 @@ int o2345_obj_text_host(const float* positions, const uint8_t* rgba, const float
  * (cell_y c + v_local) / H), fp64 rounded once; normals float32 [3 nt,3] (written iff grad, device fp32 [nv,3]) = that vertex's normal of
  * o2345_mesh_asset_vertices; indices uint32 [3 nt] = 0, 1, 2, ...; bounds float32 [6] and workspace (o2345_mesh_bounds_workspace_bytes(3 nt) bytes) as
  * for o2345_mesh_asset_vertices.  Bounds and matrices as for o2345_mesh_pack_vertices. */
+typedef struct O2345TextureStats {
+    unsigned long long n_nonfinite;                     /* triangles with a non-finite corner coordinate */
+    unsigned long long n_bad;                           /* triangles with an index outside [0, nv) */
+} O2345TextureStats;
 size_t o2345_mesh_texture_texels(long long nt, int texel, int* width_host, int* height_host);
 int o2345_mesh_texture_points(const double* verts, long long nv, const void* tris, int index_bytes, long long nt, int texel, int grid_R,
-                              const float* bound_min_host, const float* bound_max_host, double* points_idx, float* points_world, void* stats, void* stream);
+                              const float* bound_min_host, const float* bound_max_host, double* points_idx, float* points_world, O2345TextureStats* stats,
+                              void* stream);
 int o2345_mesh_texture_pack(const float* rgb, long long nt, int texel, uint8_t* image, void* stream);
 int o2345_mesh_texture_corners(const double* verts, long long nv, const void* tris, int index_bytes, long long nt, int texel, int grid_R,
                                const float* bound_min_host, const float* bound_max_host, const float* scale_mat_host, const float* trans_mat_host, const float* grad,
@@ -576,8 +591,7 @@ int o2345_obj_texture_text(const float* positions, const float* uv, const float*
  *   outputs  device: depth float32 [n] = float32(t), 0 without a hit; kind uint8 [n]; point float32 [n,3] = float32(o_k + t d_k), 0 without a hit;
  *            the hit list, int32 at the start of `workspace` (surface_trace_workspace_bytes(n) bytes, 16-byte aligned): the slots with kind != 0, each
  *            once, in an order that changes between runs (ballot compaction, one integer atomicAdd per wave) -- the network kernels take it as `index`
- *            with its device-side count as `n_dev`; stats (72 bytes, 8-byte aligned) = uint64 [8]: hits, entry hits, box misses, marched-through misses,
- *            stalled, bad rays, samples visited (march samples + refinement evaluations), lattice lookups; then int32 [2]: the hit list's count, 0.
+ *            with its device-side count (stats->n_list) as `n_dev`; stats (8-byte aligned), written by this call.
  *   img_h, img_w: 0, 0, or the image the n = img_h img_w rays fill in raster order: a wave then takes an 8 x 8 pixel tile instead of 64 consecutive rays
  *            (lanes of similar march length together); the results are the same bytes.
  * No host synchronisation.  Errors: bad arguments, a workspace that is too small.
@@ -589,12 +603,21 @@ int o2345_obj_texture_text(const float* positions, const float* uv, const float*
  * truncating quantisation of the vertex colours, alpha 255, and background_host (HOST uint8 [4]) without a hit; normal uint8 [H,W,4]: that quantisation of
  * float32(n 0.5 + 0.5), n = grad / sqrt((gx gx + gy gy) + gz gz) in fp64 (0 for a zero or non-finite gradient), alpha 255, and 0, 0, 0, 0 without a hit;
  * depth_out float32 [H,W]: depth, 0 without a hit.  The two images are 4-byte aligned. */
+typedef struct O2345SurfaceStats {
+    unsigned long long hits, entry_hits;
+    unsigned long long box_misses, misses;              /* rays that miss the box; rays marched through without a hit */
+    unsigned long long stalled, bad_rays;
+    unsigned long long samples;                         /* samples visited: march samples + refinement evaluations */
+    unsigned long long lookups;                         /* lattice lookups */
+    int n_list;                                         /* the hit list's count */
+    int reserved;                                       /* 0 */
+} O2345SurfaceStats;
 int o2345_surface_bricks(const float* u, int grid_R, double level, int inside_positive, uint8_t* flags, void* stream);
 size_t o2345_surface_trace_workspace_bytes(long long n);
 int o2345_surface_trace(const float* u, int grid_R, const uint8_t* flags, const float* rays_o, const float* rays_d, long long n, int img_h, int img_w,
                         double t_near, double t_far, double stride, int refine, double level, int inside_positive, const float* bound_min_host,
-                        const float* bound_max_host, void* workspace, size_t workspace_bytes, float* depth, uint8_t* kind, float* point, void* stats,
-                        void* stream);
+                        const float* bound_max_host, void* workspace, size_t workspace_bytes, float* depth, uint8_t* kind, float* point,
+                        O2345SurfaceStats* stats, void* stream);
 int o2345_camera_rays(const float* K_host, const float* c2w_host, int H, int W, float* rays_o, float* rays_d, void* stream);
 int o2345_surface_pack(const uint8_t* kind, const float* depth, const float* rgb, const float* grad, int H, int W, const uint8_t* background_host,
                        uint8_t* color, uint8_t* normal, float* depth_out, void* stream);
@@ -623,11 +646,17 @@ int o2345_surface_pack(const uint8_t* kind, const float* depth, const float* rgb
  *   query     points device fp64 [n,3], n < 2^28 -> d2 fp64 [n], nearest int32 [n].  grid NULL: every point against every triangle.  grid given (with
  *             the max_cells it was built with, over the same verts and tris): the same bits through the grid -- shells of cells outward from the
  *             point's cell, stopping when a conservative lower bound on the distance to everything unvisited exceeds the best distance found.
- *   reduce    d2, nearest (may be NULL), weights (NULL = 1) over n samples; thresholds HOST fp64 [n_thresholds <= 8], finite and >= 0 -> stats, 128
- *             bytes, 8-byte aligned: fp64 sum w, sum w d, sum w d^2, sum w [d <= tau_k] for k = 0 .. 7 (d = sqrt(d2)), then uint64: the bit pattern of
- *             the largest d2, n, the samples left out (d2 not finite or negative, or nearest < 0), and of the optional target (tris NULL = none) its
- *             degenerate triangles and those with a bad index or a non-finite coordinate.  The sums are the same bits on every run (fixed tree, no
+ *   reduce    d2, nearest (may be NULL), weights (NULL = 1) over n samples; thresholds HOST fp64 [n_thresholds <= 8], finite and >= 0 -> stats,
+ *             8-byte aligned (d = sqrt(d2); the target is optional, tris NULL = none).  The sums are the same bits on every run (fixed tree, no
  *             floating-point atomics; at most 288 additions in a chain).  No host synchronisation. */
+typedef struct O2345DistanceStats {
+    double sum_w, sum_wd, sum_wd2;                      /* sum w, sum w d, sum w d^2 */
+    double within[8];                                   /* sum w [d <= tau_k] */
+    unsigned long long max_d2_bits;                     /* the bit pattern of the largest d2 */
+    unsigned long long n;
+    unsigned long long n_unmatched;                     /* the samples left out: d2 not finite or negative, or nearest < 0 */
+    unsigned long long n_degenerate, n_bad;             /* of the target: degenerate triangles; those with a bad index or a non-finite coordinate */
+} O2345DistanceStats;
 size_t o2345_mesh_samples_workspace_bytes(long long nt);
 int o2345_mesh_samples_count(const double* verts, const void* tris, int index_bytes, long long nv, long long nt, double spacing, void* workspace,
                              size_t workspace_bytes, long long* n_samples_host, void* stream);
@@ -645,7 +674,7 @@ int o2345_mesh_distance_query(const double* points, long long n, const double* v
 size_t o2345_mesh_distance_reduce_workspace_bytes(long long n);
 int o2345_mesh_distance_reduce(const double* d2, const int* nearest, const double* weights, long long n, const double* thresholds_host, int n_thresholds,
                                const double* verts, const void* tris, int index_bytes, long long nv, long long nt, void* workspace, size_t workspace_bytes,
-                               void* stats, void* stream);
+                               O2345DistanceStats* stats, void* stream);
 /* Load every code object of the library on the current device now (the HIP runtime loads a translation unit's kernels at its first launch: 5 - 60 ms
  * each for the units of this library, which otherwise land inside the first calls of a fresh process).  Launches nothing that touches user memory. */
 int o2345_preload(void);

@@ -1,8 +1,8 @@
 """ctypes loader and call path for libo2345_hip.so.  Everything the binding knows about an entry point is read from include/o2345.h: the prototypes,
-the element type of every pointer, and whether a pointer is a host or a device pointer (the header's rule: host iff the parameter's or the function's
-name ends in _host, or it points to a struct).  ``call`` converts and checks the arguments of one entry against that table and raises on a non-zero
-status.  There is NO fallback: if the library is missing or a call fails, this raises.  torch is not imported here: a device tensor is recognised by
-what it offers (is_cuda, is_contiguous(), dtype, data_ptr())."""
+the element type of every pointer, whether a pointer is a host or a device pointer (the header's rule: a pointer is a HOST pointer if and only if its
+name ends in _host, or the function's name ends in _host), and every struct that crosses the boundary.  ``call`` converts and checks the arguments of
+one entry against that table and raises on a non-zero status.  There is NO fallback: if the library is missing or a call fails, this raises.  torch
+is not imported here: a device tensor is recognised by what it offers (is_cuda, is_contiguous(), dtype, data_ptr(), numel())."""
 import ctypes
 import os
 import re
@@ -15,9 +15,10 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 HEADER = os.path.join(os.path.dirname(HERE), "include", "o2345.h")
 LIB_PATH = os.environ.get("O2345_LIB") or os.path.join(HERE, "libo2345_hip.so")       # O2345_LIB: an A/B build variant (build.build_variant)
 
-ABI_VERSION = 210          # include/o2345.h: o2345_version()
+ABI_VERSION = 220          # include/o2345.h: o2345_version()
 
-_CT = {"int": ctypes.c_int, "float": ctypes.c_float, "long long": ctypes.c_longlong, "size_t": ctypes.c_size_t, "void": None, "double": ctypes.c_double}
+_CT = {"int": ctypes.c_int, "float": ctypes.c_float, "long long": ctypes.c_longlong, "size_t": ctypes.c_size_t, "void": None, "double": ctypes.c_double,
+       "unsigned long long": ctypes.c_ulonglong}
 # pointee C type -> element type: the dtype a device tensor must have ("void": any; "size_t": host arrays only)
 _ELEM = {"float": "float32", "double": "float64", "int": "int32", "int32_t": "int32", "uint32_t": "int32", "uint8_t": "uint8", "unsigned char": "uint8",
          "long long": "int64", "unsigned long long": "int64", "size_t": "size_t", "void": "void"}
@@ -28,16 +29,16 @@ Param = namedtuple("Param", "name ctype elem host")
 
 
 def _param(decl, fn, what):
-    m = re.fullmatch(r"(?:const\s+)?([\w ]+?)\s*(\*?)\s*(\w+)", " ".join(decl.split()))
-    if not m:
+    m = re.fullmatch(r"(?:const\s+)?([\w ]+?)\s*(\*?)\s*(\w+)(?:\s*\[(\d+)\])?", " ".join(decl.split()))
+    if not m or (m.group(4) and (m.group(2) or what != "field")):             # name[N]: a fixed-size array of scalars, in a struct only
         raise ValueError(f"cannot parse {what} {decl!r} of {fn}")
-    base, star, name = m.groups()
+    base, star, name, count = m.groups()
     if not star:
         if base not in _CT or _CT[base] is None:
             raise ValueError(f"cannot map C type {decl!r} in {fn}")
-        return Param(name, _CT[base], None, False)
+        return Param(name, _CT[base] * int(count) if count else _CT[base], None, False)
     struct = base.startswith("O2345")
-    host = struct or name.endswith("_host") or fn.endswith("_host")
+    host = name.endswith("_host") or fn.endswith("_host")
     if not struct and (base not in _ELEM or (base == "size_t" and not host)):
         raise ValueError(f"cannot map pointee type of {decl!r} in {fn}")
     return Param(name, ctypes.c_void_p, "struct " + base if struct else _ELEM[base], host)
@@ -61,22 +62,26 @@ def parse_header(path=HEADER):
     return {name: (rest, [p.ctype for p in params]) for name, (rest, params) in prototypes(path).items()}
 
 
+def struct_names(path=HEADER):
+    """-> the names of the header's ``typedef struct O2345...`` declarations, in order: a struct's position is its number in o2345_struct_layout."""
+    return re.findall(r"typedef struct (O2345\w+)\s*\{", re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S))
+
+
 def struct_fields(name, path=HEADER):
     """-> [Param] of ``typedef struct <name> {...} <name>;`` in the header, in declaration order: the binding's struct is GENERATED from the one
-    declaration the C side compiles (csrc/ includes the same header), never kept by hand.  Its pointers are device pointers."""
-    src = open(path).read()
+    declaration the C side compiles (csrc/ includes the same header), never kept by hand.  Its pointers are device pointers; ``name[N]`` is an array."""
+    src = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
     m = re.search(r"typedef struct %s\s*\{(.*?)\}\s*%s\s*;" % (name, name), src, flags=re.S)
     if not m:
         raise ValueError(f"{name} is not declared in {path}")
-    body = re.sub(r"/\*.*?\*/", "", m.group(1), flags=re.S)
     fields = []
-    for decl in body.split(";"):
+    for decl in m.group(1).split(";"):
         decl = " ".join(decl.split())
         if not decl:
             continue
         if "*" in decl and "," in decl:
             raise ValueError(f"{name}: one pointer per declaration, got {decl!r}")
-        typ, names = ("", decl) if "*" in decl else decl.split(" ", 1)
+        typ, names = ("", decl) if "*" in decl else re.fullmatch(r"(.*?)(\w+(?:\s*\[\d+\])?(?:\s*,.*)?)", decl).groups()      # "unsigned long long " + "a, b[8]"
         fields += [_param(f"{typ} {n}", name, "field") for n in names.split(",")]
     return fields
 
@@ -94,17 +99,21 @@ def _got(v):
 
 
 def _device_pointer(where, elem):
+    """A struct on the device is a uint8 tensor (torch has no struct dtype) of at least the struct's size."""
+    nbytes = ctypes.sizeof(STRUCTS[elem[7:]]) if elem.startswith("struct ") else 0
+    elem, what = ("uint8", f"uint8 [>= {nbytes}] ({elem[7:]})") if nbytes else (elem, elem)
     want = getattr(sys.modules.get("torch"), elem, None)           # None: any dtype, or torch is not imported yet (whoever holds a tensor has done that)
 
     def conv(v):
         if v is None:
             return None
         try:
-            if v.is_cuda and v.is_contiguous() and (v.dtype is want or elem == "void" or v.dtype is getattr(sys.modules["torch"], elem)):
+            if v.is_cuda and v.is_contiguous() and (v.dtype is want or elem == "void" or v.dtype is getattr(sys.modules["torch"], elem)) and (
+                    not nbytes or v.numel() >= nbytes):
                 return v.data_ptr()
         except AttributeError:
             pass
-        raise ValueError(f"{where}: expected None or a contiguous GPU tensor of {elem}, got {_got(v)}")
+        raise ValueError(f"{where}: expected None or a contiguous GPU tensor of {what}, got {_got(v)}" + (f" [{v.numel()}]" if nbytes and hasattr(v, "numel") else ""))
     return conv
 
 
@@ -201,34 +210,49 @@ class RenderIO(ctypes.Structure):
             setattr(self, k, self._pointers[k](t))
 
 
-def check_render_io_layout(L, path=LIB_PATH):
-    """The loaded library's own sizeof / offsetof table against the generated Structure: a field added to, removed from or reordered in only one of the
-    header the library was compiled with and the header this binding parsed fails HERE, at load time, instead of corrupting render calls."""
+# every struct the header declares, in its order -> the Structure generated from its text (RenderIO, ProjectStats, TextureStats, SurfaceStats, DistanceStats)
+STRUCTS = {name: RenderIO if name == "O2345RenderIO" else type(name[5:], (ctypes.Structure,), {"_fields_": parse_struct(name)}) for name in struct_names()}
+
+
+def read_struct(name, block):
+    """A host copy of a block (bytes, or an array of at least the struct's size: its first bytes) -> the generated Structure, fields by name."""
+    raw = block if isinstance(block, (bytes, bytearray)) else np.ascontiguousarray(block).reshape(-1).view(np.uint8)
+    if len(raw) < ctypes.sizeof(STRUCTS[name]):
+        raise ValueError(f"{name}: expected at least {ctypes.sizeof(STRUCTS[name])} bytes, got {len(raw)}")
+    return STRUCTS[name].from_buffer_copy(raw)
+
+
+def check_struct_layout(L, name, path=LIB_PATH, cls=None):
+    """The loaded library's own sizeof / offsetof table against the generated Structure (``cls``: another one, for a test): a field added to, removed
+    from or reordered in only one of the header the library was compiled with and the header this binding parsed fails HERE, at load time, instead of
+    corrupting calls."""
+    cls, which = cls or STRUCTS[name], list(STRUCTS).index(name)
     want = (ctypes.c_size_t * 256)()
-    n = L.o2345_render_io_layout(want, 256)
-    mine = [(f, getattr(RenderIO, f).offset) for f, _ in RenderIO._fields_]
-    if n != len(mine) or L.o2345_render_io_size() != ctypes.sizeof(RenderIO) or any(int(want[i]) != off for i, (_, off) in enumerate(mine)):
+    n, size = L.o2345_struct_layout(which, want, 256), L.o2345_struct_size(which)
+    mine = [(f, getattr(cls, f).offset) for f, _ in cls._fields_]
+    if n != len(mine) or size != ctypes.sizeof(cls) or any(int(want[i]) != off for i, (_, off) in enumerate(mine)):
         theirs = [int(want[i]) for i in range(min(n, 256))]
-        raise RuntimeError(f"O2345RenderIO layout mismatch between {path} ({n} fields, {L.o2345_render_io_size()} bytes, offsets {theirs}) and "
-                           f"{HEADER} ({len(mine)} fields, {ctypes.sizeof(RenderIO)} bytes, offsets {[o for _, o in mine]}): rebuild the library")
+        raise RuntimeError(f"{name} layout mismatch between {path} ({n} fields, {size} bytes, offsets {theirs}) and "
+                           f"{HEADER} ({len(mine)} fields, {ctypes.sizeof(cls)} bytes, offsets {[o for _, o in mine]}): rebuild the library")
 
 
 _LIB = None
 
 
 def load_library(path):
-    """dlopen ``path``, attach the header's prototypes, check ABI version and struct layout.  ``lib()`` does this once for the product library; tests load
+    """dlopen ``path``, attach the header's prototypes, check ABI version and struct layouts.  ``lib()`` does this once for the product library; tests load
     build variants (libo2345_hip_<tag>.so) next to it with this."""
     if not os.path.exists(path):
         raise RuntimeError(f"{path} is missing: run `python __graft_entry__.py build` (hipcc, gfx950). "
                            "There is no CPU fallback for the reconstruction path.")
     L = ctypes.CDLL(path)
+    if L.o2345_version() != ABI_VERSION:          # first: a library of another ABI need not export what this header declares
+        raise RuntimeError(f"{path} implements ABI {L.o2345_version()}, this binding expects {ABI_VERSION}: rebuild the library")
     for name, (rest, argt) in parse_header().items():
         fn = getattr(L, name)          # AttributeError if the library does not export a declared symbol
         fn.restype, fn.argtypes = rest, argt
-    if L.o2345_version() != ABI_VERSION:
-        raise RuntimeError(f"{path} implements ABI {L.o2345_version()}, this binding expects {ABI_VERSION}: rebuild the library")
-    check_render_io_layout(L, path)
+    for name in STRUCTS:
+        check_struct_layout(L, name, path)
     L.o2345_knobs()                    # the environment knobs are read now, once (csrc/common.h)
     return L
 

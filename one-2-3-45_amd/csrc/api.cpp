@@ -41,7 +41,7 @@ int preload_convnet();
 
 extern "C" {
 const char* o2345_last_error(void) { return o2345::g_err; }
-int o2345_version(void) { return 210; }     // 2.1: segment_rays + weight_cull in O2345RenderIO; 2.0: see include/o2345.h (1.5: o2345_list_sort_by_visibility; 1.4: color stats, bf16 entry removed; 1.3: o2345_conv2d family; 1.2: t_rand)
+int o2345_version(void) { return 220; }     // 2.2: declared stats structs, o2345_struct_size / _layout; 2.1: segment_rays + weight_cull in O2345RenderIO; 2.0: see include/o2345.h (1.5: o2345_list_sort_by_visibility; 1.4: color stats, bf16 entry removed; 1.3: o2345_conv2d family; 1.2: t_rand)
 
 int o2345_preload(void) {
     int e, bad = 0;
@@ -77,19 +77,41 @@ const char* o2345_knobs(void) {
     return t.s;
 }
 
-// layout of O2345RenderIO as compiled into this library, in declaration order (include/o2345.h); the ctypes binding compares its own struct with it
-size_t o2345_render_io_size(void) { return sizeof(O2345RenderIO); }
-int o2345_render_io_layout(size_t* offsets_host, int n) {
-#define F(name) offsetof(O2345RenderIO, name)
-    static const size_t off[] = {
-        F(sdf_blob), F(color_x3_blob), F(color_mfma_blob), F(vol_cl), F(maskvol), F(cmaps), F(proj), F(cam_pos), F(D), F(V), F(H), F(W),
-        F(rays_o), F(rays_d), F(near_ray), F(far_ray), F(query_cam), F(t_rand), F(R), F(n_samples), F(n_importance), F(sdf_mode), F(segment_rays),
-        F(near), F(far), F(sample_dist), F(inv_s), F(alpha_inter_ratio), F(background), F(weight_cull),
-        F(mid_z), F(dists), F(pm), F(sdf), F(grad), F(rgb), F(nviews), F(color), F(depth), F(weights), F(cdf), F(weights_sum), F(weights_max),
-        F(depth_var), F(alpha_sum), F(grad_err), F(color_mask), F(z_vals), F(scalars), F(color_stats)};
+// layout of every struct include/o2345.h declares, as compiled into this library: fields in declaration order, structs in the header's order; the ctypes
+// binding compares the structs it generated from the header's text with this
+#define F(name) offsetof(S, name)
+#define S O2345RenderIO
+static const size_t off_render_io[] = {
+    F(sdf_blob), F(color_x3_blob), F(color_mfma_blob), F(vol_cl), F(maskvol), F(cmaps), F(proj), F(cam_pos), F(D), F(V), F(H), F(W),
+    F(rays_o), F(rays_d), F(near_ray), F(far_ray), F(query_cam), F(t_rand), F(R), F(n_samples), F(n_importance), F(sdf_mode), F(segment_rays),
+    F(near), F(far), F(sample_dist), F(inv_s), F(alpha_inter_ratio), F(background), F(weight_cull),
+    F(mid_z), F(dists), F(pm), F(sdf), F(grad), F(rgb), F(nviews), F(color), F(depth), F(weights), F(cdf), F(weights_sum), F(weights_max),
+    F(depth_var), F(alpha_sum), F(grad_err), F(color_mask), F(z_vals), F(scalars), F(color_stats)};
+#undef S
+#define S O2345ProjectStats
+static const size_t off_project[] = {F(n_nonfinite), F(converged), F(unconverged), F(stalled), F(clamped), F(max_before), F(max_after), F(reserved), F(count)};
+#undef S
+#define S O2345TextureStats
+static const size_t off_texture[] = {F(n_nonfinite), F(n_bad)};
+#undef S
+#define S O2345SurfaceStats
+static const size_t off_surface[] = {F(hits), F(entry_hits), F(box_misses), F(misses), F(stalled), F(bad_rays), F(samples), F(lookups), F(n_list), F(reserved)};
+#undef S
+#define S O2345DistanceStats
+static const size_t off_distance[] = {F(sum_w), F(sum_wd), F(sum_wd2), F(within), F(max_d2_bits), F(n), F(n_unmatched), F(n_degenerate), F(n_bad)};
+#undef S
 #undef F
-    const int nf = (int)(sizeof off / sizeof off[0]);
-    for (int i = 0; i < n && i < nf && offsets_host; ++i) offsets_host[i] = off[i];
-    return nf;
+#define LAYOUT(type, off) {sizeof(type), off, (int)(sizeof off / sizeof off[0])}
+static const struct { size_t size; const size_t* off; int n; } layouts[] = {
+    LAYOUT(O2345RenderIO, off_render_io), LAYOUT(O2345ProjectStats, off_project), LAYOUT(O2345TextureStats, off_texture),
+    LAYOUT(O2345SurfaceStats, off_surface), LAYOUT(O2345DistanceStats, off_distance)};
+#undef LAYOUT
+static const int n_layouts = (int)(sizeof layouts / sizeof layouts[0]);
+
+size_t o2345_struct_size(int which) { return which >= 0 && which < n_layouts ? layouts[which].size : 0; }
+int o2345_struct_layout(int which, size_t* offsets_host, int n) {
+    if (which < 0 || which >= n_layouts) return 0;
+    for (int i = 0; i < n && i < layouts[which].n && offsets_host; ++i) offsets_host[i] = layouts[which].off[i];
+    return layouts[which].n;
 }
 }

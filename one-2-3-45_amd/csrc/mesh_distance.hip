@@ -33,7 +33,7 @@
 namespace o2345 {
 
 constexpr long long MD_MAX_SAMPLES = 1ll << 28;
-constexpr int MD_THRESHOLDS = 8;
+constexpr int MD_THRESHOLDS = sizeof(O2345DistanceStats::within) / sizeof(double);          // 8 (the device block of the reduction: include/o2345.h)
 constexpr int MD_AXIS = 256;                          // cells per axis at most
 constexpr long long MD_MAX_CELLS = 1ll << 24;
 constexpr int MD_RED_ITEMS = 16;                      // samples per thread of k_md_reduce
@@ -41,13 +41,6 @@ constexpr int MD_RED_TILE = 256 * MD_RED_ITEMS;
 constexpr int MD_RED_COLS = 3 + MD_THRESHOLDS;        // sum w, sum w d, sum w d^2, within[8]
 constexpr double MD_SLACK = 9.313225746154785e-10;    // 2^-30
 constexpr double MD_DOWN = 0.9999999999990905;        // 1 - 2^-40: a product rounded towards zero, and then some
-
-// the device block of o2345_mesh_distance_reduce; its layout is part of the C ABI (include/o2345.h)
-struct MdStats {
-    double sum_w, sum_wd, sum_wd2, within[MD_THRESHOLDS];
-    unsigned long long max_d2_bits, n, n_unmatched, n_degenerate, n_bad;
-};
-static_assert(sizeof(MdStats) == 128, "MdStats is 128 bytes in the C ABI");
 
 struct MdThresholds { double tau[MD_THRESHOLDS]; int n; };
 
@@ -410,7 +403,7 @@ __device__ __forceinline__ void md_block_sums(double (&v)[MD_RED_COLS]) {
 
 // block b: samples [b * MD_RED_TILE, (b + 1) * MD_RED_TILE), thread i its MD_RED_ITEMS consecutive ones -> partials[b][MD_RED_COLS]
 __global__ __launch_bounds__(256) void k_md_reduce(const double* __restrict__ d2, const int* __restrict__ nearest, const double* __restrict__ weights, long long n,
-                                                   MdThresholds th, double* __restrict__ partials, MdStats* __restrict__ st) {
+                                                   MdThresholds th, double* __restrict__ partials, O2345DistanceStats* __restrict__ st) {
     double v[MD_RED_COLS];
 #pragma unroll
     for (int k = 0; k < MD_RED_COLS; ++k) v[k] = 0.0;
@@ -448,7 +441,7 @@ __global__ __launch_bounds__(256) void k_md_reduce(const double* __restrict__ d2
 }
 
 // one block: thread i adds rows i, i + 256, ... in that order, then the block's tree
-__global__ __launch_bounds__(256) void k_md_reduce_final(const double* __restrict__ partials, long long rows, long long n, MdStats* __restrict__ st) {
+__global__ __launch_bounds__(256) void k_md_reduce_final(const double* __restrict__ partials, long long rows, long long n, O2345DistanceStats* __restrict__ st) {
     double v[MD_RED_COLS];
 #pragma unroll
     for (int k = 0; k < MD_RED_COLS; ++k) v[k] = 0.0;
@@ -466,7 +459,7 @@ __global__ __launch_bounds__(256) void k_md_reduce_final(const double* __restric
 }
 
 // the target's bad-input counters of the summary
-__global__ __launch_bounds__(64) void k_md_reduce_target(const MdGridTotals* __restrict__ tot, MdStats* __restrict__ st) {
+__global__ __launch_bounds__(64) void k_md_reduce_target(const MdGridTotals* __restrict__ tot, O2345DistanceStats* __restrict__ st) {
     if (blockIdx.x || threadIdx.x) return;
     st->n_degenerate = tot->n_degenerate;
     st->n_bad = tot->n_bad + tot->n_nonfinite;
@@ -708,7 +701,7 @@ size_t o2345_mesh_distance_reduce_workspace_bytes(long long n) {
 
 int o2345_mesh_distance_reduce(const double* d2, const int* nearest, const double* weights, long long n, const double* thresholds, int n_thresholds,
                                const double* verts, const void* tris, int index_bytes, long long nv, long long nt, void* workspace, size_t workspace_bytes,
-                               void* stats, void* stream) {
+                               O2345DistanceStats* stats, void* stream) {
     O2345_REQUIRE(n >= 0 && n < MD_MAX_SAMPLES, "mesh_distance_reduce: bad sample count %lld", n);
     O2345_REQUIRE(n_thresholds >= 0 && n_thresholds <= MD_THRESHOLDS && (n_thresholds == 0 || thresholds), "mesh_distance_reduce: %d thresholds; at most 8", n_thresholds);
     O2345_REQUIRE(stats && workspace && (n == 0 || d2), "mesh_distance_reduce: null pointer");
@@ -724,15 +717,15 @@ int o2345_mesh_distance_reduce(const double* d2, const int* nearest, const doubl
     MdReduceCarve c;
     (void)md_reduce_carve(workspace, n, c);
     hipStream_t s = (hipStream_t)stream;
-    O2345_HIP(hipMemsetAsync(stats, 0, sizeof(MdStats), s));
+    O2345_HIP(hipMemsetAsync(stats, 0, sizeof *stats, s));
     O2345_HIP(hipMemsetAsync(c.tot, 0, 128, s));
-    if (c.rows) hipLaunchKernelGGL(k_md_reduce, dim3((unsigned)c.rows), dim3(256), 0, s, d2, nearest, weights, n, th, c.partials, (MdStats*)stats);
-    hipLaunchKernelGGL(k_md_reduce_final, dim3(1), dim3(256), 0, s, c.partials, c.rows, n, (MdStats*)stats);
+    if (c.rows) hipLaunchKernelGGL(k_md_reduce, dim3((unsigned)c.rows), dim3(256), 0, s, d2, nearest, weights, n, th, c.partials, stats);
+    hipLaunchKernelGGL(k_md_reduce_final, dim3(1), dim3(256), 0, s, c.partials, c.rows, n, stats);
     if (tris && nt > 0) {
         with_index_type(index_bytes, tris, [&](auto* t) {
             hipLaunchKernelGGL(k_md_grid_bounds<index_type<decltype(t)>>, dim3(cdiv(nt, 256)), dim3(256), 0, s, verts, (int)nv, t, nt, (unsigned char*)nullptr, c.tot);
         });
-        hipLaunchKernelGGL(k_md_reduce_target, dim3(1), dim3(64), 0, s, c.tot, (MdStats*)stats);
+        hipLaunchKernelGGL(k_md_reduce_target, dim3(1), dim3(64), 0, s, c.tot, stats);
     }
     return check_launch("mesh_distance_reduce");
 }

@@ -26,16 +26,9 @@
 
 namespace o2345 {
 
-constexpr int PROJ_COUNTS = 66;                       // rounds 0 .. 64 and one behind
+constexpr int PROJ_COUNTS = sizeof(O2345ProjectStats::count) / sizeof(int);       // rounds 0 .. 64 and one behind (the device block of one call: include/o2345.h)
 constexpr int PROJ_ITEMS = 4;                         // list entries per thread of k_proj_step
 constexpr int PROJ_TILE = 256 * PROJ_ITEMS;           // per block
-
-// the device block of one call; its layout is part of the C ABI (include/o2345.h)
-struct ProjStats {
-    unsigned long long n_nonfinite, converged, unconverged, stalled, clamped, max_before, max_after, reserved;
-    int count[PROJ_COUNTS];
-};
-static_assert(sizeof(ProjStats) == 328, "ProjStats is 8 x uint64 + 66 x int32");
 
 struct ProjFrame {
     double rm1;                                       // R - 1
@@ -59,7 +52,7 @@ __device__ __forceinline__ int proj_wave_sum(int x) {
 
 // thread per vertex: x = the input, its float32 world point, the identity list, the count of round 0; the stats block was zeroed before (memset)
 __global__ __launch_bounds__(256) void k_proj_init(const double* __restrict__ verts, int nv, ProjFrame f, double* __restrict__ x, float* __restrict__ pts,
-                                                   int* __restrict__ list, ProjStats* __restrict__ st) {
+                                                   int* __restrict__ list, O2345ProjectStats* __restrict__ st) {
     const long long v = (long long)blockIdx.x * 256 + threadIdx.x;
     bool nonfinite = false;
     if (v == 0) st->count[0] = nv;
@@ -83,7 +76,7 @@ __global__ __launch_bounds__(256) void k_proj_init(const double* __restrict__ ve
 // stats block's two cache lines.
 __global__ __launch_bounds__(256) void k_proj_step(const double* __restrict__ origin, int nv, double* __restrict__ x, float* __restrict__ pts,
                                                    const float* __restrict__ sdf, const float* __restrict__ grad, const int* __restrict__ list,
-                                                   int* __restrict__ next, ProjStats* __restrict__ st, int round, int last, ProjFrame f, double level,
+                                                   int* __restrict__ next, O2345ProjectStats* __restrict__ st, int round, int last, ProjFrame f, double level,
                                                    double tol, double max_step, double max_move) {
     __shared__ int wave_tot[5], red_n[4][4], list_base;
     __shared__ unsigned long long red_m[4][2];
@@ -209,11 +202,11 @@ size_t o2345_mesh_project_workspace_bytes(long long nv) {
 // All rounds are queued at once: the count of every round's list stays on the device (the network kernels take it as n_dev).  No host synchronisation.
 int o2345_mesh_project(const float* blob, const float* vol_cl, int D, int sdf_mode, const double* verts, long long nv, int grid_R, const float* bound_min,
                        const float* bound_max, int iterations, double level, double tol, double max_step, double max_move, void* workspace,
-                       size_t workspace_bytes, double* verts_out, void* stats, void* stream) {
+                       size_t workspace_bytes, double* verts_out, O2345ProjectStats* stats, void* stream) {
     O2345_REQUIRE(sdf_mode == 0 || sdf_mode == 2, "mesh_project: sdf_mode must be 0 (fp32) or 2 (split-f16), got %d", sdf_mode);
     O2345_REQUIRE(proj_size_ok(nv), "mesh_project: bad size (nv must be in [0, 2^30))");
     O2345_REQUIRE(grid_R >= 2, "mesh_project: bad resolution %d", grid_R);
-    O2345_REQUIRE(iterations >= 1 && iterations <= 64, "mesh_project: iterations must be in [1, 64], got %d", iterations);
+    O2345_REQUIRE(iterations >= 1 && iterations <= PROJ_COUNTS - 2, "mesh_project: iterations must be in [1, 64], got %d", iterations);
     O2345_REQUIRE(fabs(level) <= DBL_MAX, "mesh_project: level must be finite, got %g", level);
     O2345_REQUIRE(tol >= 0.0 && tol <= DBL_MAX, "mesh_project: tol must be finite and >= 0, got %g", tol);
     O2345_REQUIRE(proj_positive(max_step), "mesh_project: max_step must be finite and > 0, got %g", max_step);
@@ -234,8 +227,8 @@ int o2345_mesh_project(const float* blob, const float* vol_cl, int D, int sdf_mo
     ProjCarve c;
     (void)proj_carve(workspace, nv, c);
     hipStream_t s = (hipStream_t)stream;
-    ProjStats* st = (ProjStats*)stats;
-    O2345_HIP(hipMemsetAsync(st, 0, sizeof(ProjStats), s));
+    O2345ProjectStats* st = stats;
+    O2345_HIP(hipMemsetAsync(st, 0, sizeof *st, s));
     const int n = (int)nv;
     const unsigned gv = nv ? cdiv(nv, 256) : 1;
     hipLaunchKernelGGL(k_proj_init, dim3(gv), dim3(256), 0, s, verts, n, f, verts_out, c.pts, c.list[0], st);

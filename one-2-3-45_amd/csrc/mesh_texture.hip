@@ -50,16 +50,11 @@ struct TexFrame {
     double bmin[3], bext[3];
 };
 
-// the device block of k_tex_points; its layout is part of the C ABI (include/o2345.h)
-struct TexStats {
-    unsigned long long n_nonfinite, n_bad;
-};
-
 // thread per texel of a used cell, cell-major
 template <typename IDX>
 __global__ __launch_bounds__(256) void k_tex_points(const double* __restrict__ verts, long long nv, const IDX* __restrict__ tris, long long nt, int c,
                                                     long long texels, TexFrame f, double* __restrict__ pidx, float* __restrict__ pworld,
-                                                    TexStats* __restrict__ st) {
+                                                    O2345TextureStats* __restrict__ st) {
     const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
     bool bad = false, nonfinite = false;
     if (e < texels) {
@@ -163,7 +158,7 @@ size_t o2345_mesh_texture_texels(long long nt, int texel, int* width_host, int* 
 }
 
 int o2345_mesh_texture_points(const double* verts, long long nv, const void* tris, int index_bytes, long long nt, int texel, int grid_R,
-                              const float* bound_min, const float* bound_max, double* points_idx, float* points_world, void* stats, void* stream) {
+                              const float* bound_min, const float* bound_max, double* points_idx, float* points_world, O2345TextureStats* stats, void* stream) {
     O2345_REQUIRE(index_bytes == 4 || index_bytes == 8, "mesh_texture_points: index_bytes must be 4 or 8");
     TexLayout L;
     O2345_REQUIRE(tex_layout(nt, texel, L), "mesh_texture_points: bad layout (nt = %lld >= 1, texel = %d in [4, 64], sides <= 16384, texels < 2^31)", nt, texel);
@@ -179,10 +174,10 @@ int o2345_mesh_texture_points(const double* verts, long long nv, const void* tri
         O2345_REQUIRE(f.bext[k] > 0.0 && f.bext[k] <= DBL_MAX && fabs(f.bmin[k]) <= DBL_MAX, "mesh_texture_points: bound_max must be above bound_min on every axis, both finite");
     }
     hipStream_t s = (hipStream_t)stream;
-    O2345_HIP(hipMemsetAsync(stats, 0, sizeof(TexStats), s));
+    O2345_HIP(hipMemsetAsync(stats, 0, sizeof *stats, s));
     const dim3 grid(cdiv(L.texels, 256));
     with_index_type(index_bytes, tris, [&](auto* t) {
-        hipLaunchKernelGGL(k_tex_points<index_type<decltype(t)>>, grid, dim3(256), 0, s, verts, nv, t, nt, L.c, L.texels, f, points_idx, points_world, (TexStats*)stats);
+        hipLaunchKernelGGL(k_tex_points<index_type<decltype(t)>>, grid, dim3(256), 0, s, verts, nv, t, nt, L.c, L.texels, f, points_idx, points_world, stats);
     });
     return check_launch("mesh_texture_points");
 }

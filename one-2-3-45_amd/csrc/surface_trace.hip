@@ -30,13 +30,6 @@ constexpr int SURF_BRICK = 8;
 constexpr int SURF_MAX_STEPS = 1 << 20;
 constexpr int SURF_MAX_R = 2048;
 
-// the device block of one trace; its layout is part of the C ABI (include/o2345.h)
-struct SurfStats {
-    unsigned long long hits, entry_hits, box_misses, misses, stalled, bad_rays, samples, lookups;
-    int n_list, reserved;
-};
-static_assert(sizeof(SurfStats) == 72, "SurfStats is 8 x uint64 + 2 x int32");
-
 struct SurfFrame {
     double bmin[3], bmax[3], ext[3];
     double rm1, h, t_near, t_far, level;
@@ -108,7 +101,7 @@ __global__ __launch_bounds__(256) void k_surface_bricks(const float* __restrict_
 __global__ __launch_bounds__(256) void k_surface_trace(const float* __restrict__ u, const uint8_t* __restrict__ flags, const float* __restrict__ rays_o,
                                                        const float* __restrict__ rays_d, long long n, int img_h, int img_w, SurfFrame f,
                                                        float* __restrict__ depth, uint8_t* __restrict__ kind, float* __restrict__ point,
-                                                       int* __restrict__ list, SurfStats* __restrict__ st) {
+                                                       int* __restrict__ list, O2345SurfaceStats* __restrict__ st) {
     long long r;
     bool valid;
     if (img_w > 0) {
@@ -317,8 +310,8 @@ size_t o2345_surface_trace_workspace_bytes(long long n) {
 
 int o2345_surface_trace(const float* u, int grid_R, const uint8_t* flags, const float* rays_o, const float* rays_d, long long n, int img_h, int img_w,
                         double t_near, double t_far, double stride, int refine, double level, int inside_positive, const float* bound_min,
-                        const float* bound_max, void* workspace, size_t workspace_bytes, float* depth, uint8_t* kind, float* point, void* stats,
-                        void* stream) {
+                        const float* bound_max, void* workspace, size_t workspace_bytes, float* depth, uint8_t* kind, float* point,
+                        O2345SurfaceStats* stats, void* stream) {
     SurfFrame f;
     O2345_REQUIRE(bound_min && bound_max && stats && workspace && u, "surface_trace: null pointer");
     if (!surf_frame("surface_trace", grid_R, level, inside_positive, bound_min, bound_max, f)) return -1;
@@ -341,11 +334,11 @@ int o2345_surface_trace(const float* u, int grid_R, const uint8_t* flags, const 
     int* list;
     (void)surf_carve(workspace, n, list);
     hipStream_t s = (hipStream_t)stream;
-    O2345_HIP(hipMemsetAsync(stats, 0, sizeof(SurfStats), s));
+    O2345_HIP(hipMemsetAsync(stats, 0, sizeof *stats, s));
     if (n == 0) return 0;
     const long long blocks = img_w > 0 ? cdiv((long long)((img_w + 7) / 8) * ((img_h + 7) / 8), 4) : cdiv(n, 256);
     hipLaunchKernelGGL(k_surface_trace, dim3((unsigned)blocks), dim3(256), 0, s, u, flags, rays_o, rays_d, n, img_h, img_w, f, depth, kind, point, list,
-                       (SurfStats*)stats);
+                       stats);
     return check_launch("surface_trace");
 }
 

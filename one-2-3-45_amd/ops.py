@@ -17,6 +17,11 @@ from . import _lib, config, mesh_io
 call = _lib.call
 
 
+def _stats_block(name, device, *rows):
+    """Device memory for a stats block the header declares (a struct has no torch dtype: uint8 of exactly its size), or ``rows`` of them."""
+    return torch.empty(*rows, ctypes.sizeof(_lib.STRUCTS[name]), dtype=torch.uint8, device=device)
+
+
 def _first_cuda_tensor(objs):
     for o in objs:
         if torch.is_tensor(o):
@@ -48,6 +53,10 @@ def _f(t):
 
 def host_f32(a):                          # a tensor or an array -> a contiguous float32 host array (the small arguments: bounds, matrices, cameras)
     return np.ascontiguousarray(np.asarray(a.detach().cpu() if torch.is_tensor(a) else a, np.float32))
+
+
+def _double_of_bits(u):                   # a double that a stats block carries as its bit pattern (uint64, so that the device can take integer maxima)
+    return float(np.uint64(u).view(np.float64))
 
 
 def _host3(v):
@@ -1032,9 +1041,6 @@ def mesh_decimate(verts_idx, tris, cell=None):
 
 
 # ---------------------------------------------------------------------------------------------------------- mesh projection
-_PROJECT_STATS_BYTES = 328          # include/o2345.h: uint64 [8] + int32 [66]
-
-
 @_on_device
 def mesh_project(blob, vol_cl, verts_idx, resolution, iterations, level=0.0, tol=None, max_step=None, max_move=None, bound_min=(-1.0, -1.0, -1.0),
                  bound_max=(1.0, 1.0, 1.0), precision=None):
@@ -1058,19 +1064,19 @@ def mesh_project(blob, vol_cl, verts_idx, resolution, iterations, level=0.0, tol
     nv, dev = verts_idx.shape[0], verts_idx.device
     ws, wsb = _scratch("o2345_mesh_project_workspace_bytes", (nv,), dev, "mesh_project")
     out = torch.empty(nv, 3, dtype=torch.float64, device=dev)
-    stats = torch.empty(_PROJECT_STATS_BYTES, dtype=torch.uint8, device=dev)
+    stats = _stats_block("O2345ProjectStats", dev)
     call("o2345_mesh_project", blob, vol_cl, vol_cl.shape[0], mode, verts_idx, nv, int(resolution), bmin, bmax, iterations, level, tol, max_step, max_move,
          ws, wsb, out, stats)
     return out, project_info(stats.cpu().numpy(), iterations)
 
 
 def project_info(stats, iterations):
-    """The stats block of o2345_mesh_project (328 bytes, on the host) -> the info dict of mesh_io.project_vertices; raises on a non-finite coordinate."""
-    head, counts = stats[:64].view(np.uint64), stats[64:_PROJECT_STATS_BYTES].view(np.int32)
-    if int(head[0]):
-        raise RuntimeError(f"o2345 mesh_project: {int(head[0])} vertices have a non-finite coordinate")
-    return {"evaluated": [int(c) for c in counts[:iterations + 1]], "converged": int(head[1]), "unconverged": int(head[2]), "stalled": int(head[3]),
-            "clamped": int(head[4]), "max_before": float(head[5:6].view(np.float64)[0]), "max_after": float(head[6:7].view(np.float64)[0])}
+    """The stats block of o2345_mesh_project (O2345ProjectStats, on the host) -> the info dict of mesh_io.project_vertices; raises on a non-finite coordinate."""
+    st = _lib.read_struct("O2345ProjectStats", stats)
+    if st.n_nonfinite:
+        raise RuntimeError(f"o2345 mesh_project: {st.n_nonfinite} vertices have a non-finite coordinate")
+    return {"evaluated": list(st.count[:iterations + 1]), "converged": st.converged, "unconverged": st.unconverged, "stalled": st.stalled,
+            "clamped": st.clamped, "max_before": _double_of_bits(st.max_before), "max_after": _double_of_bits(st.max_after)}
 
 
 def mesh_cleanup(verts_idx, tris, opts, blob, vol_cl, resolution, level=0.0, bound_min=(-1.0, -1.0, -1.0), bound_max=(1.0, 1.0, 1.0), precision=None,
@@ -1092,7 +1098,6 @@ def mesh_cleanup(verts_idx, tris, opts, blob, vol_cl, resolution, level=0.0, bou
 
 
 # ---------------------------------------------------------------------------------------------------------- mesh-to-mesh distance
-_DISTANCE_STATS_BYTES = 128         # include/o2345.h: fp64 [11] + uint64 [5]
 _DISTANCE_EXHAUSTIVE_BELOW = 64     # a target with fewer triangles is searched exhaustively: a grid costs more launches than it saves
 
 # a target mesh's uniform grid (ops.mesh_distance_grid): the device buffer, the max_cells it was sized for, and what the count pass reported
@@ -1167,32 +1172,31 @@ def mesh_closest_triangle(points, verts, tris, grid=None):
 
 @_on_device
 def mesh_distance_stats(d2, nearest, weight, thresholds=(), target=None, out=None):
-    """The summary of one direction on the device -> the 128-byte stats block (uint8 [128], or ``out``): sums, the largest d2 as its bit pattern, counts;
+    """The summary of one direction on the device -> the stats block (O2345DistanceStats as uint8, or ``out``): sums, the largest d2 as its bit pattern, counts;
     ``target`` = (verts, tris) adds the target's counters.  The same bytes on every run; no synchronisation.  ops.distance_summary reads it on the host."""
     th = np.ascontiguousarray(mesh_io._check_thresholds(thresholds), np.float64)
     n, dev = d2.shape[0], d2.device
     ws, wsb = _scratch("o2345_mesh_distance_reduce_workspace_bytes", (n,), dev, "mesh_distance_reduce")
-    stats = torch.empty(_DISTANCE_STATS_BYTES, dtype=torch.uint8, device=dev) if out is None else out
+    stats = _stats_block("O2345DistanceStats", dev) if out is None else out
     tv, (tt, ib), tnv, tnt = (None, (None, 4), 0, 0) if target is None else (target[0], _triangles(target[1], "mesh_distance_stats"), target[0].shape[0], target[1].shape[0])
     call("o2345_mesh_distance_reduce", d2, nearest, weight, n, th, len(th), tv, tt, ib, tnv, tnt, ws, wsb, stats)
     return stats
 
 
 def distance_summary(stats, n_thresholds, target_triangles=None):
-    """The stats block of o2345_mesh_distance_reduce (128 bytes, on the host) -> (the summary dict of mesh_io.distance_summary, the target's degenerate
-    triangles); raises on a target without a usable triangle."""
-    raw = np.ascontiguousarray(np.asarray(stats).reshape(-1)[:_DISTANCE_STATS_BYTES])
-    f, u = raw[:88].view(np.float64), raw[88:].view(np.uint64)
-    n, unmatched, degenerate, bad = int(u[1]), int(u[2]), int(u[3]), int(u[4])
+    """The stats block of o2345_mesh_distance_reduce (O2345DistanceStats, on the host) -> (the summary dict of mesh_io.distance_summary, the target's
+    degenerate triangles); raises on a target without a usable triangle."""
+    st = _lib.read_struct("O2345DistanceStats", stats)
+    n, unmatched, degenerate, bad = st.n, st.n_unmatched, st.n_degenerate, st.n_bad
     if bad:
         raise RuntimeError(f"o2345 mesh_distance: {bad} target triangles have an index out of range or a non-finite coordinate")
     if unmatched:
         raise RuntimeError(f"o2345 mesh_distance: {unmatched} of {n} samples found no triangle: the target has no triangle with an area"
                            + (f" ({target_triangles} triangles, {degenerate} degenerate)" if target_triangles is not None else ""))
-    W = float(f[0])
-    div = lambda s: float(s) / W if W > 0 else float("nan")
-    return {"mean": div(f[1]), "rms": float(np.sqrt(div(f[2]))) if W > 0 else float("nan"), "max": float(np.sqrt(u[0:1].view(np.float64)[0])),
-            "within": [div(f[3 + k]) for k in range(n_thresholds)], "samples": n, "area": W}, degenerate
+    W = st.sum_w
+    div = lambda s: s / W if W > 0 else float("nan")
+    return {"mean": div(st.sum_wd), "rms": float(np.sqrt(div(st.sum_wd2))) if W > 0 else float("nan"), "max": float(np.sqrt(_double_of_bits(st.max_d2_bits))),
+            "within": [div(st.within[k]) for k in range(n_thresholds)], "samples": n, "area": W}, degenerate
 
 
 def mesh_distance(va, ta, vb, tb, spacing=None, thresholds=(), return_samples=False, cell=None):
@@ -1204,7 +1208,7 @@ def mesh_distance(va, ta, vb, tb, spacing=None, thresholds=(), return_samples=Fa
     twin's to the last bit, the sums to 1e-12.  ``return_samples`` adds "samples": {"a", "b"} -> {"points", "weight", "triangle", "d2", "nearest"},
     device tensors."""
     th = mesh_io._check_thresholds(thresholds)
-    stats = torch.empty(2, _DISTANCE_STATS_BYTES, dtype=torch.uint8, device=va.device)
+    stats = _stats_block("O2345DistanceStats", va.device, 2)
     samples = {}
     for k, (name, (v, t), (tv, tt)) in enumerate((("a", (va, ta), (vb, tb)), ("b", (vb, tb), (va, ta)))):
         points, weight, triangle = mesh_surface_samples(v, t, spacing)
@@ -1222,9 +1226,6 @@ def mesh_distance(va, ta, vb, tb, spacing=None, thresholds=(), return_samples=Fa
 
 
 # ---------------------------------------------------------------------------------------------------------- texture atlas
-_TEXTURE_STATS_BYTES = 16           # include/o2345.h: uint64 [2]
-
-
 def _texture_mesh(verts_idx, tris, what):
     t = _triangles(tris, what)
     _vertices(verts_idx, what)
@@ -1234,19 +1235,19 @@ def _texture_mesh(verts_idx, tris, what):
 
 
 def texture_check(stats):
-    """The stats block of o2345_mesh_texture_points (16 bytes, on the host): raises on a non-finite coordinate or a triangle index out of range."""
-    n_nonfinite, n_bad = (int(x) for x in np.asarray(stats).reshape(-1)[:_TEXTURE_STATS_BYTES].view(np.uint64))
-    if n_bad:
-        raise RuntimeError(f"o2345 mesh_texture_points: {n_bad} triangles index outside the vertex array")
-    if n_nonfinite:
-        raise RuntimeError(f"o2345 mesh_texture_points: {n_nonfinite} triangles have a non-finite vertex coordinate")
+    """The stats block of o2345_mesh_texture_points (O2345TextureStats, on the host): raises on a non-finite coordinate or a triangle index out of range."""
+    st = _lib.read_struct("O2345TextureStats", stats)
+    if st.n_bad:
+        raise RuntimeError(f"o2345 mesh_texture_points: {st.n_bad} triangles index outside the vertex array")
+    if st.n_nonfinite:
+        raise RuntimeError(f"o2345 mesh_texture_points: {st.n_nonfinite} triangles have a non-finite vertex coordinate")
 
 
 @_on_device
 def mesh_texture_points(verts_idx, tris, texel, resolution, bound_min=(-1.0, -1.0, -1.0), bound_max=(1.0, 1.0, 1.0), validate=True):
     """The surface point of every texel of the atlas (== mesh_io.texture_points, to the last bit; definitions in csrc/mesh_texture.hip).  verts_idx fp64
     [N,3] index coordinates on a ``resolution``^3 grid, tris [M,3] int32 / int64, ``texel`` in [4, 64] -> (points fp64 [cells c^2, 3] index coordinates,
-    world fp32 [cells c^2, 3], stats uint8 [16]), cell-major; the inputs are not written.  ``validate`` copies the counters to the host (one
+    world fp32 [cells c^2, 3], stats uint8 [sizeof O2345TextureStats]), cell-major; the inputs are not written.  ``validate`` copies the counters to the host (one
     synchronisation) and raises on a non-finite coordinate or a triangle index out of range; a caller that queues more work passes False and hands the
     counters to texture_check after its own copy."""
     tris, ib = _texture_mesh(verts_idx, tris, "mesh_texture_points")
@@ -1257,7 +1258,7 @@ def mesh_texture_points(verts_idx, tris, texel, resolution, bound_min=(-1.0, -1.
     assert call("o2345_mesh_texture_texels", tris.shape[0], lay["texel"], None, None) == n
     pts = torch.empty(n, 3, dtype=torch.float64, device=dev)
     world = torch.empty(n, 3, dtype=torch.float32, device=dev)
-    stats = torch.empty(_TEXTURE_STATS_BYTES, dtype=torch.uint8, device=dev)
+    stats = _stats_block("O2345TextureStats", dev)
     call("o2345_mesh_texture_points", verts_idx, verts_idx.shape[0], tris, ib, tris.shape[0], lay["texel"], int(resolution), bmin, bmax, pts, world, stats)
     if validate:
         texture_check(stats.cpu().numpy())
@@ -1310,10 +1311,6 @@ def obj_texture_text(positions, uv, normals=None, K=None, bounds=None):
 
 
 # ---------------------------------------------------------------------------------------------------------- surface render
-_SURFACE_STATS_BYTES = 72           # include/o2345.h: uint64 [8] + int32 [2]
-_SURFACE_INFO = ("hits", "entry_hits", "box_misses", "misses", "stalled", "bad_rays", "samples", "lookups")
-
-
 def _surface_lattice(u, what):
     if u.dim() != 3 or len(set(u.shape)) != 1 or not 2 <= u.shape[0] <= 2048:
         raise ValueError(f"{what}: the lattice is float32 [R,R,R] with 2 <= R <= 2048, got {tuple(u.shape)}")
@@ -1332,11 +1329,9 @@ def surface_bricks(u, level=0.0, inside_positive=False):
 
 
 def surface_info(stats, n_rays):
-    """The stats block of o2345_surface_trace (72 bytes, on the host) -> the info dict of surface.trace_rays"""
-    head = np.asarray(stats).reshape(-1)[:64].view(np.uint64)
-    info = {"rays": int(n_rays)}
-    info.update((k, int(v)) for k, v in zip(_SURFACE_INFO, head))
-    return info
+    """The stats block of o2345_surface_trace (O2345SurfaceStats, on the host) -> the info dict of surface.trace_rays: its 64-bit counters, in its order"""
+    st = _lib.read_struct("O2345SurfaceStats", stats)
+    return {"rays": int(n_rays), **{k: getattr(st, k) for k, t in st._fields_ if t is ctypes.c_ulonglong}}
 
 
 @_on_device
@@ -1345,9 +1340,9 @@ def surface_trace(u, rays_o, rays_d, near, far, stride=None, refine=None, level=
     """March rays through the trilinear lattice u (== surface.trace_rays, to the last bit; definitions in csrc/surface_trace.hip).  u float32 [R,R,R],
     rays_o / rays_d float32 [n,3], all on the device; ``stride`` / ``refine`` None: the config defaults -> dict(depth f32 [n], kind u8 [n] (0 none, 1
     hit, 2 the ray enters inside), point f32 [n,3], hits int32 [n] (the slots with kind != 0 in its first ``n_hits`` entries, in an arbitrary order),
-    n_hits int32 [1] on the device (for ``index=`` / ``n_dev=`` of the network ops), stats uint8 [72], info).  ``skip``: the empty-space skip over
+    n_hits int32 [1] on the device (for ``index=`` / ``n_dev=`` of the network ops), stats uint8 [sizeof O2345SurfaceStats], info).  ``skip``: the empty-space skip over
     ``flags`` (ops.surface_bricks of the same lattice, level and sign; computed here when None); the result does not depend on it.  ``image_hw`` = (H, W)
-    with H W = n: waves take 8 x 8 pixel tiles.  ``info`` (surface.trace_rays' exact counts) costs one 72-byte copy and a synchronisation; a caller that
+    with H W = n: waves take 8 x 8 pixel tiles.  ``info`` (surface.trace_rays' exact counts) costs one small copy and a synchronisation; a caller that
     queues more work passes ``want_info=False`` and reads ``stats`` later (ops.surface_info)."""
     stride, refine = config.surface_stride(stride), config.surface_refine(refine)
     R = _surface_lattice(u, "surface_trace")
@@ -1373,10 +1368,11 @@ def surface_trace(u, rays_o, rays_d, near, far, stride=None, refine=None, level=
     depth = torch.empty(n, dtype=torch.float32, device=dev)
     kind = torch.empty(n, dtype=torch.uint8, device=dev)
     point = torch.empty(n, 3, dtype=torch.float32, device=dev)
-    stats = torch.empty(_SURFACE_STATS_BYTES, dtype=torch.uint8, device=dev)
+    stats = _stats_block("O2345SurfaceStats", dev)
+    at = _lib.STRUCTS["O2345SurfaceStats"].n_list.offset
     call("o2345_surface_trace", u, R, flags if skip else None, rays_o, rays_d, n, H, W, near, far, stride, refine, level, int(bool(inside_positive)), bmin, bmax,
          hits, wsb, depth, kind, point, stats)
-    out = dict(depth=depth, kind=kind, point=point, hits=hits[:n], n_hits=stats[64:68].view(torch.int32), stats=stats, info=None)
+    out = dict(depth=depth, kind=kind, point=point, hits=hits[:n], n_hits=stats[at:at + 4].view(torch.int32), stats=stats, info=None)
     if want_info:
         out["info"] = surface_info(stats.cpu().numpy(), n)
     return out

@@ -28,14 +28,19 @@ def test_every_pointer_has_an_element_type_and_the_host_rule_holds():
     for fn, p in ptrs:
         struct = p.elem.startswith("struct ")
         assert struct or p.elem in ELEMENTS, (fn, p)
-        assert p.host == (p.name.endswith("_host") or fn.endswith("_host") or struct), (fn, p)
+        assert p.host == (p.name.endswith("_host") or fn.endswith("_host")), (fn, p)
         assert p.elem != "size_t" or p.host, (fn, p)
     host = {(fn, p.name) for fn, p in ptrs if p.host}
     assert len(host) == 59
-    assert {("o2345_surface_trace", "bound_min_host"), ("o2345_mesh_distance_reduce", "thresholds_host"), ("o2345_render_rays", "io"),
-            ("o2345_ply_records_host", "faces"), ("o2345_render_io_layout", "offsets_host")} <= host
+    assert {("o2345_surface_trace", "bound_min_host"), ("o2345_mesh_distance_reduce", "thresholds_host"), ("o2345_render_rays", "io_host"),
+            ("o2345_ply_records_host", "faces"), ("o2345_struct_layout", "offsets_host")} <= host
     assert not {("o2345_sdf_grid_sparse_x3", "background"), ("o2345_mesh_decimate_count", "tris"), ("o2345_costvol_index", "n_rows_dev")} & host
     table = {(fn, p.name): p.elem for fn, p in ptrs}
+    structs = {(fn, p.name): p.elem[7:] for fn, p in ptrs if p.elem.startswith("struct ")}
+    assert structs == {("o2345_render_rays", "io_host"): "O2345RenderIO", ("o2345_mesh_project", "stats"): "O2345ProjectStats",
+                       ("o2345_mesh_texture_points", "stats"): "O2345TextureStats", ("o2345_surface_trace", "stats"): "O2345SurfaceStats",
+                       ("o2345_mesh_distance_reduce", "stats"): "O2345DistanceStats"}
+    assert not [k for k in structs if k[1] == "stats" and k in host] and "void* stats" not in open(L.HEADER).read()
     assert table["o2345_costvol_index", "origin_host"] == "float32" and table["o2345_mesh_smooth", "boundary_or_null"] == "uint8"
     assert table["o2345_list_sort_by_visibility", "keys_out"] == "int32" and table["o2345_color_points_x3", "stats_dev"] == "int64"
     assert table["o2345_mesh_decimate_count", "tris"] == "void" and table["o2345_mc_verts_to_world", "extent_host"] == "float64"
@@ -109,7 +114,7 @@ def args_of(name, **given):
     ("o2345_marching_cubes_count", "nv_host", ctypes.c_int(), "c_int"),                                 # c_int where long long* is declared
     ("o2345_mesh_distance_grid_count", "dims_host", (ctypes.c_longlong * 3)(), "_Array_3"),                # 8-byte integers where int* is declared
     ("o2345_mesh_distance_grid_count", "cell_host", ctypes.c_longlong(), "c_long"),                     # an integer where double* is declared
-    ("o2345_render_rays", "io", ctypes.c_int(), "c_int"),
+    ("o2345_render_rays", "io_host", ctypes.c_int(), "c_int"),
     ("o2345_costvol_index", "V", 2 ** 31, "2147483648"),                                                # does not fit int
     ("o2345_costvol_index", "V", -2 ** 31 - 1, "-2147483649"),
     ("o2345_costvol_index", "V", 1.0, "float"),
@@ -142,7 +147,7 @@ def test_bind_accepts():
 def test_call_returns_values_and_raises_on_a_failing_status():
     w, h = ctypes.c_int(), ctypes.c_int()
     assert L.call("o2345_mesh_texture_texels", 33, 8, w, h) == 17 * 64 and (w.value, h.value) == (5 * 8, 4 * 8)       # 17 cells, G = 5: 5 x 4 cells
-    assert L.call("o2345_version") == L.ABI_VERSION == 210
+    assert L.call("o2345_version") == L.ABI_VERSION == 220
     assert L.call("o2345_obj_text_bytes", 0, 0, 12, 0, 0) == 0 and b"=" in L.call("o2345_knobs")
     with pytest.raises(RuntimeError, match=r"o2345 sdf_mlp failed \(-?\d+\): .*null pointer") as e:
         L.call("o2345_sdf_mlp", 0, None, None, 8, None, None, None, 10, 0, 1.0, None, None, None, None, None)
@@ -167,11 +172,14 @@ class FakeTensor:
     """What the converter asks of a device tensor (_lib does not import torch): enough to check dtype and contiguity rules without a GPU."""
     is_cuda, device = True, "cuda:0"
 
-    def __init__(self, dtype, contiguous=True):
-        self.dtype, self._c = dtype, contiguous
+    def __init__(self, dtype, contiguous=True, numel=0):
+        self.dtype, self._c, self._n = dtype, contiguous, numel
 
     def is_contiguous(self):
         return self._c
+
+    def numel(self):
+        return self._n
 
     def data_ptr(self):
         return 4096
@@ -190,3 +198,159 @@ def test_device_pointers_check_dtype_and_contiguity():
     io.point(color_mask=FakeTensor(torch.uint8), color_stats=FakeTensor(torch.int64))
     assert io.color_mask == 4096 and io.color_stats == 4096
     assert L.bind("o2345_mesh_pack_faces", args_of("o2345_mesh_pack_faces", tris=FakeTensor(torch.int16)))[0] == 4096        # void*: any dtype
+
+
+# ---------------------------------------------------------------------------------------------------------- the declared structs
+# The stats blocks of the C ABI as they were when each was a private struct of its .hip file (ProjStats, TexStats, SurfStats, MdStats) and a list of
+# byte offsets in ops.py: the independent statement of their layout.  name -> (sizeof, [(field, offset)]).
+FROZEN = {
+    "O2345ProjectStats": (328, [("n_nonfinite", 0), ("converged", 8), ("unconverged", 16), ("stalled", 24), ("clamped", 32), ("max_before", 40),
+                                ("max_after", 48), ("reserved", 56), ("count", 64)]),
+    "O2345TextureStats": (16, [("n_nonfinite", 0), ("n_bad", 8)]),
+    "O2345SurfaceStats": (72, [("hits", 0), ("entry_hits", 8), ("box_misses", 16), ("misses", 24), ("stalled", 32), ("bad_rays", 40), ("samples", 48),
+                               ("lookups", 56), ("n_list", 64), ("reserved", 68)]),
+    "O2345DistanceStats": (128, [("sum_w", 0), ("sum_wd", 8), ("sum_wd2", 16), ("within", 24), ("max_d2_bits", 88), ("n", 96), ("n_unmatched", 104),
+                                 ("n_degenerate", 112), ("n_bad", 120)]),
+}
+STATS_ENTRY = {"O2345ProjectStats": "o2345_mesh_project", "O2345TextureStats": "o2345_mesh_texture_points", "O2345SurfaceStats": "o2345_surface_trace",
+               "O2345DistanceStats": "o2345_mesh_distance_reduce"}
+
+
+def test_stats_struct_layouts_are_frozen():
+    assert list(L.STRUCTS) == L.struct_names() == ["O2345RenderIO", "O2345ProjectStats", "O2345TextureStats", "O2345SurfaceStats", "O2345DistanceStats"]
+    assert L.STRUCTS["O2345RenderIO"] is L.RenderIO
+    for name, (size, offsets) in FROZEN.items():
+        cls = L.STRUCTS[name]
+        assert cls.__name__ == name[5:] and cls._fields_ == L.parse_struct(name)
+        assert ctypes.sizeof(cls) == size and [(f, getattr(cls, f).offset) for f, _ in cls._fields_] == offsets, name
+    P, D = L.STRUCTS["O2345ProjectStats"], L.STRUCTS["O2345DistanceStats"]
+    assert P.count.size == 66 * 4 and D.within.size == 8 * 8 and dict(D._fields_)["sum_w"] is ctypes.c_double and dict(P._fields_)["clamped"] is ctypes.c_ulonglong
+    lib = L.lib()                                                                  # the compiled side says the same
+    for which, name in enumerate(L.STRUCTS):
+        assert lib.o2345_struct_size(which) == ctypes.sizeof(L.STRUCTS[name]) and lib.o2345_struct_layout(which, None, 0) == len(L.STRUCTS[name]._fields_)
+    assert lib.o2345_struct_size(len(L.STRUCTS)) == 0 and lib.o2345_struct_layout(-1, None, 0) == 0
+
+
+def test_struct_parser_reads_arrays_and_several_names_per_declaration(tmp_path):
+    path = tmp_path / "h.h"
+    path.write_text("/* typedef struct O2345Ghost { int x; } O2345Ghost; */\n"
+                    "typedef struct O2345Demo { unsigned long long a, b;  /* two */ double w[8]; int n[3], m;\n const float* p; uint8_t* q; } O2345Demo;\n"
+                    "typedef struct O2345Next { float f; } O2345Next;\nint o2345_x(O2345Demo* demo, const O2345Next* next_host, void* stream);")
+    assert L.struct_names(str(path)) == ["O2345Demo", "O2345Next"]
+    assert L.parse_struct("O2345Demo", str(path)) == [("a", ctypes.c_ulonglong), ("b", ctypes.c_ulonglong), ("w", ctypes.c_double * 8), ("n", ctypes.c_int * 3),
+                                                       ("m", ctypes.c_int), ("p", ctypes.c_void_p), ("q", ctypes.c_void_p)]
+    fields = {p.name: p for p in L.struct_fields("O2345Demo", str(path))}
+    assert fields["p"].elem == "float32" and fields["q"].elem == "uint8" and fields["w"].elem is None and not any(p.host for p in fields.values())
+    params = L.prototypes(str(path))["o2345_x"][1]
+    assert [(p.name, p.elem, p.host) for p in params[:2]] == [("demo", "struct O2345Demo", False), ("next_host", "struct O2345Next", True)]
+    path.write_text("typedef struct O2345Demo { const float* a, *b; } O2345Demo;")
+    with pytest.raises(ValueError, match="O2345Demo: one pointer per declaration"):
+        L.struct_fields("O2345Demo", str(path))
+    for text in ("typedef struct O2345Demo { short s[4]; } O2345Demo;", "typedef struct O2345Demo { float* p[4]; } O2345Demo;"):
+        path.write_text(text)
+        with pytest.raises(ValueError, match="O2345Demo"):
+            L.struct_fields("O2345Demo", str(path))
+    path.write_text("int o2345_x(int n[3]);")                                       # an array is a field, never a parameter
+    with pytest.raises(ValueError, match="o2345_x"):
+        L.prototypes(str(path))
+    with pytest.raises(ValueError, match="O2345Missing is not declared"):
+        L.struct_fields("O2345Missing", str(path))
+
+
+@pytest.mark.parametrize("struct", sorted(FROZEN))
+def test_a_stats_tensor_smaller_than_its_struct_is_refused(struct):
+    name, size = STATS_ENTRY[struct], FROZEN[struct][0]
+    stats = [p.name for p in PROTOTYPES[name][1]].index("stats")
+    assert L.bind(name, args_of(name, stats=FakeTensor(torch.uint8, numel=size)))[stats] == 4096
+    assert L.bind(name, args_of(name, stats=FakeTensor(torch.uint8, numel=2 * size)))[stats] == 4096           # a row of a larger buffer, a guard band behind it
+    for t, got in ((FakeTensor(torch.uint8, numel=size - 1), rf"torch.uint8 .*\[{size - 1}\]"), (FakeTensor(torch.float32, numel=size), "torch.float32"),
+                   (FakeTensor(torch.uint8, False, numel=size), "contiguous=False"), (np.zeros(size, np.uint8), "numpy"), (bytes(size), "bytes")):
+        with pytest.raises(ValueError, match=rf"^{name}: stats: expected None or a contiguous GPU tensor of uint8 \[>= {size}\] \({struct}\), got .*{got}"):
+            L.bind(name, args_of(name, stats=t))
+
+
+def test_read_struct_takes_a_host_copy_and_checks_its_length():
+    raw = np.arange(72, dtype=np.uint8)
+    st = L.read_struct("O2345SurfaceStats", raw)
+    assert st.hits == int(raw[:8].view(np.uint64)[0]) and st.n_list == int(raw[64:68].view(np.int32)[0]) and st.reserved == int(raw[68:].view(np.int32)[0])
+    assert bytes(st) == raw.tobytes() == bytes(L.read_struct("O2345SurfaceStats", raw.tobytes())) == bytes(L.read_struct("O2345SurfaceStats", np.r_[raw, raw]))
+    raw[0] = 255
+    assert st.hits & 255 == 0                                                      # a copy
+    with pytest.raises(ValueError, match="O2345SurfaceStats: expected at least 72 bytes, got 71"):
+        L.read_struct("O2345SurfaceStats", raw[:71])
+
+
+# The four decoders of ops.py on synthetic blocks laid out with explicit byte offsets.  The expected values were recorded from the decoders at commit
+# 08e2544, which sliced the blocks at literal offsets (stats[:64].view(np.uint64), raw[88:].view(np.uint64), ...), for these same bytes.
+def _put(raw, offset, dtype, values):
+    v = np.atleast_1d(np.asarray(values, dtype))
+    raw[offset:offset + v.nbytes] = v.view(np.uint8)
+
+
+def _project_block(n_nonfinite=0):
+    raw = np.zeros(328, np.uint8)
+    _put(raw, 0, np.uint64, [n_nonfinite, 11, 12, 13, 14])
+    _put(raw, 40, np.float64, [0.1, 1.5e-7])                  # max_before, max_after: bit patterns of doubles
+    _put(raw, 56, np.uint64, 99)                              # reserved: not reported
+    _put(raw, 64, np.int32, 1000 - 7 * np.arange(66))
+    return raw
+
+
+def _surface_block():
+    raw = np.zeros(72, np.uint8)
+    _put(raw, 0, np.uint64, 2 ** 40 + 101 + np.arange(8))
+    _put(raw, 64, np.int32, [55, 7])
+    return raw
+
+
+def _texture_block(n_nonfinite=0, n_bad=0):
+    raw = np.zeros(16, np.uint8)
+    _put(raw, 0, np.uint64, [n_nonfinite, n_bad])
+    return raw
+
+
+def _distance_block(n_unmatched=0, n_bad=0, sum_w=7.3):
+    raw = np.zeros(128, np.uint8)
+    _put(raw, 0, np.float64, [sum_w, 2.1, 0.9])
+    _put(raw, 24, np.float64, 0.3 + 0.7 * np.arange(8))
+    _put(raw, 88, np.float64, 0.3)                            # max_d2_bits
+    _put(raw, 96, np.uint64, [4096, n_unmatched, 5, n_bad])
+    return raw
+
+
+def test_stats_decoders_return_what_they_returned():
+    ops = importlib.import_module("one-2-3-45_amd.ops")
+    want = {"evaluated": [1000, 993, 986, 979, 972, 965], "converged": 11, "unconverged": 12, "stalled": 13, "clamped": 14, "max_before": 0.1, "max_after": 1.5e-07}
+    got = ops.project_info(_project_block(), 5)
+    assert got == want and [type(v) for v in got.values()] == [list, int, int, int, int, float, float] and type(got["evaluated"][0]) is int
+    assert ops.project_info(_project_block(), 64)["evaluated"][-2:] == [559, 552] and len(ops.project_info(_project_block(), 65)["evaluated"]) == 66
+    got = ops.surface_info(_surface_block(), 640)
+    assert got == {"rays": 640, "hits": 1099511627877, "entry_hits": 1099511627878, "box_misses": 1099511627879, "misses": 1099511627880,
+                   "stalled": 1099511627881, "bad_rays": 1099511627882, "samples": 1099511627883, "lookups": 1099511627884}
+    assert list(got) == ["rays", "hits", "entry_hits", "box_misses", "misses", "stalled", "bad_rays", "samples", "lookups"] and all(type(v) is int for v in got.values())
+    assert ops.surface_info(torch.from_numpy(_surface_block()).numpy().reshape(1, 72), 640) == got            # as pipeline.py hands it over: stats.cpu().numpy()
+    assert ops.texture_check(_texture_block()) is None and ops.texture_check(np.stack([_texture_block(), _texture_block(1, 1)])[0]) is None
+    within = [0.0410958904109589, 0.136986301369863, 0.2328767123287671, 0.32876712328767116, 0.4246575342465753, 0.5205479452054794, 0.6164383561643835,
+              0.7123287671232876]
+    for k in (0, 3, 8):
+        got, degenerate = ops.distance_summary(_distance_block(), k, 12)
+        assert got == {"mean": 0.28767123287671237, "rms": 0.3511234415883917, "max": 0.5477225575051661, "within": within[:k], "samples": 4096, "area": 7.3}
+        assert degenerate == 5 and [type(v) for v in got.values()] == [float, float, float, list, int, float] and all(type(w) is float for w in got["within"])
+    got, degenerate = ops.distance_summary(_distance_block(sum_w=0.0), 2)
+    assert np.isnan([got["mean"], got["rms"]] + got["within"]).all() and len(got["within"]) == 2 and (got["max"], got["samples"], got["area"], degenerate) == (0.5477225575051661, 4096, 0.0, 5)
+    assert ops.distance_summary(np.stack([_distance_block(), _distance_block(3)])[0], 3) == ops.distance_summary(_distance_block(), 3)      # a row of the [2, 128] read-back
+
+
+@pytest.mark.parametrize("decode, message", [
+    (lambda ops: ops.project_info(_project_block(3), 5), "o2345 mesh_project: 3 vertices have a non-finite coordinate"),
+    (lambda ops: ops.texture_check(_texture_block(2, 0)), "o2345 mesh_texture_points: 2 triangles have a non-finite vertex coordinate"),
+    (lambda ops: ops.texture_check(_texture_block(2, 4)), "o2345 mesh_texture_points: 4 triangles index outside the vertex array"),
+    (lambda ops: ops.distance_summary(_distance_block(n_bad=6, n_unmatched=9), 1), "o2345 mesh_distance: 6 target triangles have an index out of range or a non-finite coordinate"),
+    (lambda ops: ops.distance_summary(_distance_block(n_unmatched=9), 1), "o2345 mesh_distance: 9 of 4096 samples found no triangle: the target has no triangle with an area"),
+    (lambda ops: ops.distance_summary(_distance_block(n_unmatched=9), 1, 12),
+     "o2345 mesh_distance: 9 of 4096 samples found no triangle: the target has no triangle with an area (12 triangles, 5 degenerate)"),
+])
+def test_stats_decoders_raise_what_they_raised(decode, message):
+    with pytest.raises(RuntimeError) as e:
+        decode(importlib.import_module("one-2-3-45_amd.ops"))
+    assert str(e.value) == message

@@ -19,9 +19,11 @@ def test_cabi_exports_every_declared_symbol():
     protos = L.parse_header()
     assert len(protos) >= 30 and "o2345_render_rays" in protos and "o2345_marching_cubes_emit" in protos
     lib = L.lib()                                    # raises if the .so is missing or a declared symbol is not exported
-    assert lib.o2345_version() == L.ABI_VERSION == 210
+    assert lib.o2345_version() == L.ABI_VERSION == 220
     assert lib.o2345_sdf_blob_floats() == pkg.weights.SDF_BLOB_FLOATS
     assert not hasattr(lib, "o2345_color_points") and "o2345_color_stats_enable" not in protos      # ABI 2.0: VALU colour kernel and library-global counters are gone
+    assert not hasattr(lib, "o2345_render_io_layout") and not hasattr(lib, "o2345_render_io_size")  # ABI 2.2: one layout description for every declared struct
+    assert "o2345_struct_layout" in protos and "o2345_struct_size" in protos
     assert lib.o2345_color_mfma_blob_floats() == pkg.weights.CM_BLOB_FLOATS
     assert lib.o2345_color_x3_blob_floats() == pkg.weights.CX_BLOB_FLOATS
     assert lib.o2345_costvol_workspace_bytes(128, 128, 128) > 0
@@ -126,7 +128,8 @@ def test_render_io_has_one_declaration_and_the_binding_checks_it(tmp_path):
     fields = L.parse_struct("O2345RenderIO")
     names = [f for f, _ in fields]
     assert "sdf_mode" in names and "sdf_bf16" not in names and "color_blob" not in names and names[0] == "sdf_blob" and names[-1] == "color_stats"
-    assert lib.o2345_render_io_layout(None, 0) == len(fields) and lib.o2345_render_io_size() == ctypes.sizeof(L.RenderIO)
+    which = L.struct_names().index("O2345RenderIO")
+    assert lib.o2345_struct_layout(which, None, 0) == len(fields) and lib.o2345_struct_size(which) == ctypes.sizeof(L.RenderIO)
     # no private copy of the struct anywhere in the library sources
     import glob
     import os
@@ -143,14 +146,45 @@ def test_render_io_has_one_declaration_and_the_binding_checks_it(tmp_path):
 
         class Mut(ctypes.Structure):
             _fields_ = L.parse_struct("O2345RenderIO", str(hp))
-        orig = L.RenderIO
-        L.RenderIO = Mut
-        try:
-            with pytest.raises(RuntimeError, match="layout mismatch"):
-                L.check_render_io_layout(lib)
-        finally:
-            L.RenderIO = orig
-    L.check_render_io_layout(lib)
+        with pytest.raises(RuntimeError, match="O2345RenderIO layout mismatch.*rebuild the library"):
+            L.check_struct_layout(lib, "O2345RenderIO", cls=Mut)
+    L.check_struct_layout(lib, "O2345RenderIO")
+
+
+def test_the_binding_checks_the_layout_of_every_stats_struct(tmp_path):
+    """The four device stats blocks are declared in include/o2345.h only, like O2345RenderIO: no private copy in csrc/, and a generated Structure that
+    differs from what the library was compiled with in an offset, the number of fields or the size -- a field moved, a field more, an array of another
+    length -- fails the load-time check with the struct's name.  (Names and types are not compared: two neighbours of one type may change places.)"""
+    import ctypes
+    import glob
+    import os
+    import re
+    L = importlib.import_module("one-2-3-45_amd._lib")
+    lib = L.lib()
+    for f in glob.glob(os.path.join(L.HERE, "csrc", "*")):
+        assert not re.search(r"struct\s+(O2345\w+|ProjStats|SurfStats|TexStats|MdStats)\s*\{", open(f).read()), f
+    src = open(L.HEADER).read()
+    for name, old, new in (("O2345SurfaceStats", "unsigned long long hits, entry_hits;", "int early; unsigned long long hits, entry_hits;"),     # every field moves
+                           ("O2345SurfaceStats", "int n_list;", "int n_list, n_more;"),
+                           ("O2345ProjectStats", "int count[66];", "int count[64];"),
+                           ("O2345TextureStats", "unsigned long long n_bad;", "int n_early; unsigned long long n_bad;"),
+                           ("O2345DistanceStats", "double within[8];", "double within[8]; double more;")):
+        assert src.count(old) == 1, old
+        hp = tmp_path / "o2345_mut.h"
+        hp.write_text(src.replace(old, new))
+
+        class Mut(ctypes.Structure):
+            _fields_ = L.parse_struct(name, str(hp))
+        assert Mut._fields_ != L.STRUCTS[name]._fields_
+        with pytest.raises(RuntimeError, match=name + " layout mismatch.*rebuild the library"):
+            L.check_struct_layout(lib, name, cls=Mut)
+        L.check_struct_layout(lib, name)
+
+    class Reordered(ctypes.Structure):                                   # the generated Structure itself, its fields in another order
+        _fields_ = L.STRUCTS["O2345ProjectStats"]._fields_[::-1]
+    assert ctypes.sizeof(Reordered) == ctypes.sizeof(L.STRUCTS["O2345ProjectStats"])
+    with pytest.raises(RuntimeError, match="O2345ProjectStats layout mismatch.*rebuild the library"):
+        L.check_struct_layout(lib, "O2345ProjectStats", cls=Reordered)
 
 
 def test_import_hook_and_shims():

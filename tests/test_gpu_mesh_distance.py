@@ -15,6 +15,8 @@ from mesh_scene_util import args, dev, ops, pipeline, stored_scene          # no
 
 mesh_io = importlib.import_module("one-2-3-45_amd.mesh_io")
 _lib = importlib.import_module("one-2-3-45_amd._lib")
+STATS = "O2345DistanceStats"
+STATS_BYTES = ctypes.sizeof(_lib.STRUCTS[STATS])        # the block at its exact size: one byte more written and a guard band shows it
 pytestmark = pytest.mark.gpu
 
 
@@ -177,15 +179,15 @@ def test_summary_integers_exact_sums_to_1e_12_and_bytes_repeat(dev, B):
     td2, tn, tw = up(d2, dev), up(nearest, dev), up(w, dev)
     runs = [ops.mesh_distance_stats(td2, tn, tw, th, target=(B["v"], B["f"])).cpu().numpy() for _ in range(2)]
     assert runs[0].tobytes() == runs[1].tobytes()
-    f, u = runs[0][:88].view(np.float64), runs[0][88:].view(np.uint64)
-    assert u.tolist() == [int(d2[keep].max().view(np.uint64)), n, 2, 0, 0]
+    st = _lib.read_struct(STATS, runs[0])
+    assert runs[0].nbytes == STATS_BYTES and [st.max_d2_bits, st.n, st.n_unmatched, st.n_degenerate, st.n_bad] == [int(d2[keep].max().view(np.uint64)), n, 2, 0, 0]
     want = [math.fsum(w[keep]), math.fsum(w[keep] * d), math.fsum(w[keep] * d2[keep])] + [math.fsum(w[keep][d <= t]) for t in th]
-    for got, ref in zip(f.tolist(), want):
+    for got, ref in zip([st.sum_w, st.sum_wd, st.sum_wd2] + list(st.within), want, strict=True):
         assert abs(got - ref) <= 1e-12 * ref, (got, ref)
     assert 0 < want[3] < want[5] < want[10] == want[0]               # some at distance 0, some within 0.3, the pushed-out ones beyond, all within 100
     # without weights and without nearest: every sample counts 1
-    s = ops.mesh_distance_stats(td2[:4096].contiguous(), None, None, (0.3,)).cpu().numpy()
-    assert s[:8].view(np.float64)[0] == 4095.0 and s[88:].view(np.uint64).tolist()[1:] == [4096, 1, 0, 0]
+    st = _lib.read_struct(STATS, ops.mesh_distance_stats(td2[:4096].contiguous(), None, None, (0.3,)).cpu().numpy())
+    assert st.sum_w == 4095.0 and [st.n, st.n_unmatched, st.n_degenerate, st.n_bad] == [4096, 1, 0, 0]
     with pytest.raises(ValueError, match="thresholds"):
         ops.mesh_distance_stats(td2, tn, tw, [0.1] * 9)
 
@@ -227,12 +229,12 @@ def test_every_entry_stays_inside_its_buffers(dev, ib, np_idx):
     assert torch.equal(out[0][0], out[1][0]) and torch.equal(out[0][1], out[1][1])
     # summary
     rwb = L.o2345_mesh_distance_reduce_workspace_bytes(n)
-    rws, stats = G.buf(rwb, "reduce workspace"), G.buf(128, "stats")
+    rws, stats = G.buf(rwb, "reduce workspace"), G.buf(STATS_BYTES, "stats")
     th = np.array([0.1, 0.2], np.float64)
     _lib.check(L.o2345_mesh_distance_reduce(P(out[0][0]), P(out[0][1]), P(w), n, th.ctypes.data_as(ctypes.c_void_p), 2, P(gv), P(gf), ib, nv, nt, P(rws), rwb,
                                             P(stats), stream), "reduce")
     assert G.damaged() == []
-    assert int(stats.cpu().numpy()[88:].view(np.uint64)[1]) == n and float(out[0][0].view(torch.float64).max()) < 1e-12 * 24 ** 2
+    assert _lib.read_struct(STATS, stats.cpu().numpy()).n == n and float(out[0][0].view(torch.float64).max()) < 1e-12 * 24 ** 2
 
 
 # ---- the whole thing -------------------------------------------------------------------------------------------------------------------------------

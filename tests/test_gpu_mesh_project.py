@@ -20,6 +20,7 @@ mio = importlib.import_module("one-2-3-45_amd.mesh_io")
 config = importlib.import_module("one-2-3-45_amd.config")
 pipeline = importlib.import_module("one-2-3-45_amd.pipeline")
 _lib = importlib.import_module("one-2-3-45_amd._lib")
+STATS_BYTES = ctypes.sizeof(_lib.STRUCTS["O2345ProjectStats"])        # the block at its exact size: one byte more written and a guard band shows it
 
 NVS = (0, 1, 31, 32, 33, 63, 64, 65, 255, 256, 257, 2049)          # the 32-point tile of the SDF kernels, the 64-lane ballot, the 256-thread block
 PRECISIONS = ("f16x3", "fp32")
@@ -161,7 +162,7 @@ def test_errors_are_statuses_not_faults(scene, dev):
     wsb = L.o2345_mesh_project_workspace_bytes(nv)
     assert wsb > 0 and L.o2345_mesh_project_workspace_bytes(-1) == 0 and L.o2345_mesh_project_workspace_bytes(2 ** 30) == 0
     ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
-    out, stats = torch.empty(nv, 3, dtype=torch.float64, device=dev), torch.empty(328, dtype=torch.uint8, device=dev)
+    out, stats = torch.empty(nv, 3, dtype=torch.float64, device=dev), torch.empty(STATS_BYTES, dtype=torch.uint8, device=dev)
     b0, b1 = np.full(3, -1.0, np.float32), np.full(3, 1.0, np.float32)
     P = lambda t: ctypes.c_void_p(t.data_ptr())
     H = lambda a: a.ctypes.data_as(ctypes.c_void_p)
@@ -197,7 +198,7 @@ def test_no_kernel_writes_outside_its_buffers(scene, dev, prec):
         verts = torch.from_numpy(hv).to(dev)
         wsb = L.o2345_mesh_project_workspace_bytes(nv)
         assert wsb > 0
-        ws, out, stats = g.buf(wsb, ("workspace", nv)), g.buf(24 * nv, ("verts_out", nv)), g.buf(328, ("stats", nv))
+        ws, out, stats = g.buf(wsb, ("workspace", nv)), g.buf(24 * nv, ("verts_out", nv)), g.buf(STATS_BYTES, ("stats", nv))
         _lib.check(L.o2345_mesh_project(P(blob), P(vol_cl), vol_cl.shape[0], 2 if prec == "f16x3" else 0, P(verts), nv, R, H(b0), H(b1), 4, 0.0, TOL, 0.5, 1.0,
                                         P(ws), wsb, P(out), P(stats), s), "mesh_project")
         bad = g.damaged()

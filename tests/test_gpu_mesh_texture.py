@@ -21,6 +21,7 @@ mio = importlib.import_module("one-2-3-45_amd.mesh_io")
 config = importlib.import_module("one-2-3-45_amd.config")
 pipeline = importlib.import_module("one-2-3-45_amd.pipeline")
 _lib = importlib.import_module("one-2-3-45_amd._lib")
+STATS_BYTES = ctypes.sizeof(_lib.STRUCTS["O2345TextureStats"])        # the block at its exact size: one byte more written and a guard band shows it
 
 # c = 4: 16 texels per cell, 16 cells per 256-thread block -- 31 and 32 triangles end at the block's last thread, 33 start the next block;
 # c = 8: 64 texels per cell, 4 cells per block -- 5 / 6 end inside the block, 7 / 8 at its end, 9 just after;  c = 5: 25 texels, no power of two.
@@ -69,7 +70,7 @@ def test_points_equal_the_twin_at_small_counts_and_block_boundaries(dev, c, dtyp
         wp, ww = _twin_points(nt, c)
         assert pts.dtype == torch.float64 and world.dtype == torch.float32 and tuple(pts.shape) == wp.shape == tuple(world.shape)
         assert _B(pts) == wp.tobytes() and _B(world) == ww.tobytes(), (nt, c)
-        assert _B(stats) == bytes(16)
+        assert _B(stats) == bytes(STATS_BYTES)
         assert _B(verts) == v.tobytes() and np.array_equal(tris.cpu().numpy(), f)                 # inputs are only read
         clamped += int(((wp == 0.0) | (wp == R - 1.0)).sum())
     assert clamped > 0                                                    # the clamp had something to do
@@ -344,7 +345,7 @@ def test_no_kernel_writes_outside_its_buffers(dev, dtype):
         rgb = torch.from_numpy(rng.uniform(0, 1, (n, 3)).astype(np.float32)).to(dev)
         grad = torch.from_numpy(rng.normal(0, 1, (nt + 2, 3)).astype(np.float32)).to(dev)
         wsb = L.o2345_mesh_bounds_workspace_bytes(3 * nt)
-        pts, world, stats = g.buf(24 * n, ("points", nt)), g.buf(12 * n, ("world", nt)), g.buf(16, ("stats", nt))
+        pts, world, stats = g.buf(24 * n, ("points", nt)), g.buf(12 * n, ("world", nt)), g.buf(STATS_BYTES, ("stats", nt))
         image = g.buf(4 * W * Hh, ("image", nt))
         pos, uv, nrm, idx = g.buf(36 * nt, ("positions", nt)), g.buf(24 * nt, ("uv", nt)), g.buf(36 * nt, ("normals", nt)), g.buf(12 * nt, ("indices", nt))
         bounds, ws = g.buf(24, ("bounds", nt)), g.buf(wsb, ("workspace", nt))
@@ -360,7 +361,7 @@ def test_no_kernel_writes_outside_its_buffers(dev, dtype):
         assert not bad, bad
         wp, ww = mio.texture_points(v, f, c, R)
         wpos, wuv, wnrm, wb = mio.texture_corners(v, f, c, R, grad=grad.cpu().numpy())
-        assert _B(pts) == wp.tobytes() and _B(world) == ww.tobytes() and _B(stats) == bytes(16)
+        assert _B(pts) == wp.tobytes() and _B(world) == ww.tobytes() and _B(stats) == bytes(STATS_BYTES)
         assert _B(image) == mio.pack_texture(rgb.cpu().numpy(), nt, c).tobytes()
         assert _B(pos) == wpos.tobytes() and _B(uv) == wuv.tobytes() and _B(nrm) == wnrm.tobytes() and _B(bounds) == wb.tobytes()
         assert _B(text) == mio.obj_texture_text_numpy(wpos, wuv, wnrm, K)

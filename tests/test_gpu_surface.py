@@ -21,6 +21,7 @@ mio = importlib.import_module("one-2-3-45_amd.mesh_io")
 config = importlib.import_module("one-2-3-45_amd.config")
 pipeline = importlib.import_module("one-2-3-45_amd.pipeline")
 _lib = importlib.import_module("one-2-3-45_amd._lib")
+STATS_BYTES = ctypes.sizeof(_lib.STRUCTS["O2345SurfaceStats"])        # the block at its exact size: one byte more written and a guard band shows it
 
 NS = (0, 1, 63, 64, 65, 255, 256, 257, 1025)                  # the lane, wave and block boundaries
 R = 24
@@ -251,7 +252,7 @@ def test_no_kernel_writes_outside_its_buffers(field, dev):
             o, d = g.buf(F["o"][:n], what=("o", n)), g.buf(F["d"][:n], what=("d", n))
             wsb = L.o2345_surface_trace_workspace_bytes(n)
             assert wsb >= max(4 * n, 16) and wsb % 16 == 0
-            ws, stats = g.buf(nbytes=wsb, what=("workspace", n)), g.buf(nbytes=72, what=("stats", n))
+            ws, stats = g.buf(nbytes=wsb, what=("workspace", n)), g.buf(nbytes=STATS_BYTES, what=("stats", n))
             depth, kind, point = g.buf(nbytes=4 * n, what=("depth", n)), g.buf(nbytes=n, what=("kind", n)), g.buf(nbytes=12 * n, what=("point", n))
             _lib.check(L.o2345_surface_trace(P(u), R, P(flags) if skip else None, P(o), P(d), n, 0, 0, NEAR, FAR, 1.0, 8, 0.0, 0, Hp(b0), Hp(b1), P(ws),
                                              wsb, P(depth), P(kind), P(point), P(stats), s), "surface_trace")
@@ -265,7 +266,7 @@ def test_no_kernel_writes_outside_its_buffers(field, dev):
     n = 33 * 31
     o, d = g.buf(F["o"][:n], what="o tiled"), g.buf(F["d"][:n], what="d tiled")
     wsb = L.o2345_surface_trace_workspace_bytes(n)
-    ws, stats = g.buf(nbytes=wsb, what="workspace tiled"), g.buf(nbytes=72, what="stats tiled")
+    ws, stats = g.buf(nbytes=wsb, what="workspace tiled"), g.buf(nbytes=STATS_BYTES, what="stats tiled")
     depth, kind, point = g.buf(nbytes=4 * n, what="depth tiled"), g.buf(nbytes=n, what="kind tiled"), g.buf(nbytes=12 * n, what="point tiled")
     _lib.check(L.o2345_surface_trace(P(u), R, P(flags), P(o), P(d), n, 33, 31, NEAR, FAR, 1.0, 8, 0.0, 0, Hp(b0), Hp(b1), P(ws), wsb, P(depth), P(kind),
                                      P(point), P(stats), s), "surface_trace")

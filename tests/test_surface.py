@@ -359,11 +359,11 @@ def test_config_defaults_and_ranges():
     assert S.march_params() == (1.0, 8) and S.march_params(2, 0) == (2.0, 0)
 
 
-def test_cabi_declares_the_surface_entries_and_stays_at_2_1():
+def test_cabi_declares_the_surface_entries():
     L = importlib.import_module("one-2-3-45_amd._lib")
     protos = L.parse_header()
     for name in ("o2345_surface_bricks", "o2345_surface_trace_workspace_bytes", "o2345_surface_trace", "o2345_camera_rays", "o2345_surface_pack"):
         assert name in protos, name
-    assert L.ABI_VERSION == 210 and len(protos["o2345_surface_trace"][1]) == 23
+    assert L.ABI_VERSION == 220 and len(protos["o2345_surface_trace"][1]) == 23
     build = importlib.import_module("one-2-3-45_amd.build")
     assert "surface_trace.hip" in build.SOURCES and "surface_trace.hip" not in build.EXTRA_FLAGS                # no extra flags
