@@ -60,7 +60,9 @@ const char* o2345_last_error(void);
  * o2345_mesh_distance_query, o2345_mesh_distance_reduce_workspace_bytes, o2345_mesh_distance_reduce. */
 /* 220 = ABI 2.2: the four device stats blocks are declared structs (O2345ProjectStats, O2345TextureStats, O2345SurfaceStats, O2345DistanceStats; no byte
  * of them moved, the untyped `stats` parameters became pointers to them); o2345_struct_size / o2345_struct_layout describe every declared struct and replace
- * o2345_render_io_size / o2345_render_io_layout; the parameter of o2345_render_rays is called io_host. */
+ * o2345_render_io_size / o2345_render_io_layout; the parameter of o2345_render_rays is called io_host.
+ * Additive since 2.2 (the version stays 220): the simplification entries o2345_mesh_simplify_workspace_bytes, o2345_mesh_simplify_count,
+ * o2345_mesh_simplify_emit. */
 int o2345_version(void);
 /* Layout self-description of the declared structs as THIS library was compiled (sizeof, and offsetof of every field in declaration order): a binding
  * asserts its own structs against it at load time (one-2-3-45_amd/_lib.py does) -- a field added on one side only cannot corrupt calls silently.
@@ -437,6 +439,43 @@ int o2345_mesh_decimate_count(const double* verts, const void* tris, int index_b
                               long long* n_degenerate_host, long long* n_duplicate_host, void* stream);
 int o2345_mesh_decimate_emit(const double* verts, const void* tris, int index_bytes, long long nv, long long nt, void* workspace, double* verts_out,
                              void* tris_out, int* cluster, void* stream);
+
+/* ---- simplification by quadric-error edge collapse (additive since 2.2; the reference has no such step, its users simplify the mesh in another tool) ----
+ * Rounds of independent half-edge collapses ordered by Garland - Heckbert's quadric error, subset placement: collapsing v -> u removes v, u keeps its
+ * bits, positions never change.  Everything is fp64, one operation at a time, in the order written (csrc/mesh_simplify_math.h is the text); equal to
+ * mesh_io.simplify_mesh to the last bit.  Triangle quadric, once, from the input: n = (P1 - P0) x (P2 - P0), nn = (nx nx + ny ny) + nz nz; nn > 0: s = 0.5 /
+ * sqrt(nn), d = -((nx P0x + ny P0y) + nz P0z), the ten entries (a b) s over (nx, ny, nz, d); else zeros.  Q_v = the sequential entrywise sum over the
+ * triangles of v in ascending face order; after a collapse Q_u <- Q_u + Q_v.  A round, on its live triangles, N(v) the adjacency row of v: the half-edge
+ * v -> u is eligible iff (1) every edge at v has exactly two triangles (boundary vertices and vertices on non-manifold edges are never removed, though they
+ * may be targets), (2) |N(v) & N(u)| = 2, (3) for every triangle at v without u the normal n' after replacing P_v by P_u has n . n' > 0 against the old
+ * normal, (4) e = p^T (Q_v + Q_u) p at p = P_u is finite and cost = max(0, e) <= max_error.  Candidate of v: its eligible u of least cost, ties to the
+ * smaller u.  With C candidates and need = ceil((live - target_faces) / 2): bin(cost) = the biased exponent field of the double, B = the smallest bin whose
+ * cumulative count reaches max(1, min(8 need, ceil(C / 2))); the candidates with bin <= B take part, priority (splitmix64's finaliser of v + (round << 32),
+ * v).  v is selected iff its priority is the smallest among the participants within graph distance 2; all selected collapses apply at once; triangles
+ * with two equal corners are dropped; face order, corner order and orientation stay.  Stop: live <= target_faces (TARGET), no candidate (BLOCKED),
+ * max_rounds rounds done (ROUNDS); the last round may go below the target.  A vertex is kept iff a kept triangle references it, in the old order; triangles
+ * are renumbered by an exclusive scan.  Not done: optimal placement, boundary and non-manifold collapses, a valence cap, an exact hit of the target.
+ * verts device fp64 [nv,3], tris device int32 / int64 [nt,3] (index_bytes 4 / 8), both only read; 0 <= nv < 2^30, 6 * nt < 2^31; target_faces >= 0;
+ * max_error >= 0, infinity = no limit; max_rounds >= 0.  workspace: mesh_simplify_workspace_bytes(nv, nt) bytes (0 for bad sizes), 16-byte aligned.
+ * stats: device int64 [O2345_SIMPLIFY_STATS + max_rounds], 8-byte aligned, written by count(): the entries named below, then the collapses of every round.
+ * The caller reads the two sizes from it to allocate the outputs.  count() runs all rounds inside the workspace; it synchronises the stream once after
+ * the input check and once per round.  Errors: bad arguments, a workspace that is too small, a non-finite coordinate, a triangle index outside [0, nv), a
+ * triangle with a repeated index; the last three are counted on the device, never dereferenced.  emit() (same workspace, nv and nt, untouched in
+ * between) writes verts_out device fp64 [vertices,3] (bit copies), tris_out [triangles,3] of width index_bytes, source device int32 [vertices] (new ->
+ * old) and merged device int32 [nv] (the new index of the vertex each old vertex ended in, following the collapses, or -1); any of the four may be NULL. */
+enum {
+    O2345_SIMPLIFY_ROUNDS = 0,                          /* rounds that applied collapses */
+    O2345_SIMPLIFY_VERTICES = 1, O2345_SIMPLIFY_TRIANGLES = 2,          /* of the output */
+    O2345_SIMPLIFY_STOPPED = 3,                         /* one of the three codes below */
+    O2345_SIMPLIFY_MAX_COST_BITS = 4,                   /* the bit pattern of a non-negative double: the largest cost applied; 0 without a collapse */
+    O2345_SIMPLIFY_STATS = 8,                           /* entries 5 .. 7: 0; entry STATS + r: the collapses of round r */
+    O2345_SIMPLIFY_STOPPED_TARGET = 0, O2345_SIMPLIFY_STOPPED_BLOCKED = 1, O2345_SIMPLIFY_STOPPED_ROUNDS = 2
+};
+size_t o2345_mesh_simplify_workspace_bytes(long long nv, long long nt);
+int o2345_mesh_simplify_count(const double* verts, const void* tris, int index_bytes, long long nv, long long nt, long long target_faces, double max_error,
+                              int max_rounds, void* workspace, size_t workspace_bytes, long long* stats, void* stream);
+int o2345_mesh_simplify_emit(const double* verts, int index_bytes, long long nv, long long nt, void* workspace, double* verts_out, void* tris_out, int* source,
+                             int* merged, void* stream);
 
 /* ---- projection of the vertices onto a level set of the SDF (additive since 2.1; the reference has no such step: its marching-cubes vertices,
  * sparse_neus_renderer.py:907-937, lie on the zero set only as far as linear interpolation along a grid edge allows, and validate_colored_mesh,

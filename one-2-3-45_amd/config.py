@@ -185,6 +185,56 @@ def mesh_decimate_cell(x=None):
     return _finite_float("decimate_cell", repr(float(x)), None, lambda c: c >= 0.0, "a finite float >= 0")
 
 
+# ---- mesh simplification (csrc/mesh_simplify.hip; mesh_io.simplify_mesh is the host twin) ---------------------------------------------------------------
+# O2345_MESH_SIMPLIFY_FACES=n simplifies the extracted mesh to at most n triangles, if reachable, by rounds of half-edge collapses ordered by quadric
+# error, on the device, after the decimation and before the projection ("" or "0" = off, the default: nothing is launched).  O2345_MESH_SIMPLIFY_MAX_ERROR
+# ("" = no limit) is the largest quadric error of a collapse, in squared grid spacings times area; O2345_MESH_SIMPLIFY_MAX_ROUNDS (256) the number of rounds.
+def _max_error(name, text):
+    t = text.strip()
+    try:
+        x = float("inf") if t == "" else float(t)
+    except ValueError:
+        x = float("nan")
+    if not x >= 0.0:
+        raise ValueError(f"{name} must be a float >= 0 (inf = no limit), got {text!r}")
+    return x
+
+
+def _below_2_31(name, n):
+    if n >= 2 ** 31:
+        raise ValueError(f"{name} must be a non-negative integer below 2^31, got {n!r}")
+    return n
+
+
+MESH_SIMPLIFY_FACES = _below_2_31("O2345_MESH_SIMPLIFY_FACES", _non_negative_int("O2345_MESH_SIMPLIFY_FACES", os.environ.get("O2345_MESH_SIMPLIFY_FACES", "")))
+MESH_SIMPLIFY_MAX_ERROR = _max_error("O2345_MESH_SIMPLIFY_MAX_ERROR", os.environ.get("O2345_MESH_SIMPLIFY_MAX_ERROR", ""))
+_rounds = os.environ.get("O2345_MESH_SIMPLIFY_MAX_ROUNDS", "")
+MESH_SIMPLIFY_MAX_ROUNDS = 256 if _rounds.strip() == "" else _below_2_31("O2345_MESH_SIMPLIFY_MAX_ROUNDS", _non_negative_int("O2345_MESH_SIMPLIFY_MAX_ROUNDS", _rounds))
+del _rounds
+
+
+def mesh_simplify_faces(n=None):
+    """None -> the configured default; anything else must be a non-negative integer below 2^31 (an explicit 0 is off whatever the default)."""
+    if n is None:
+        return MESH_SIMPLIFY_FACES
+    if isinstance(n, bool) or int(n) != n or n < 0:
+        raise ValueError(f"simplify_faces must be a non-negative integer below 2^31, got {n!r}")
+    return _below_2_31("simplify_faces", int(n))
+
+
+def mesh_simplify_max_error(x=None):
+    """None -> the configured default (inf: no limit); anything else must be a float >= 0."""
+    return MESH_SIMPLIFY_MAX_ERROR if x is None else _max_error("max_error", repr(float(x)))
+
+
+def mesh_simplify_max_rounds(n=None):
+    if n is None:
+        return MESH_SIMPLIFY_MAX_ROUNDS
+    if isinstance(n, bool) or int(n) != n or n < 0:
+        raise ValueError(f"max_rounds must be a non-negative integer below 2^31, got {n!r}")
+    return _below_2_31("max_rounds", int(n))
+
+
 # ---- mesh projection (csrc/mesh_project.hip; mesh_io.project_vertices is the host twin) -----------------------------------------------------------------
 # O2345_MESH_PROJECT_ITERATIONS=n moves the vertices of the extracted mesh onto the SDF's zero set with up to n Newton steps p <- p - s g / |g|^2 on the
 # device, after the decimation and before the vertices are coloured ("" or "0" = off, the default: nothing is launched; at most 64).
@@ -268,14 +318,18 @@ def mesh_texture_texel(n=None):
 
 
 # the options of the mesh path, resolved and validated (mesh_options; 0 / False = off); project_max_move: the projection's move limit for this decimate_cell
-MeshOptions = namedtuple("MeshOptions", "min_component_faces keep_largest decimate_cell project_iterations project_max_move smooth_iterations texture_texel")
+# simplify_faces is the last field and defaults to 0 (off), so that a record built from the seven older fields compares equal to one with the stage off
+MeshOptions = namedtuple("MeshOptions", "min_component_faces keep_largest decimate_cell project_iterations project_max_move smooth_iterations texture_texel "
+                         "simplify_faces", defaults=(0,))
 
 
-def mesh_options(min_component_faces=None, keep_largest=None, decimate_cell=None, project_iterations=None, smooth_iterations=None, texture_texel=None):
+def mesh_options(min_component_faces=None, keep_largest=None, decimate_cell=None, project_iterations=None, smooth_iterations=None, texture_texel=None,
+                 simplify_faces=None):
     """Every option of the mesh path through its validator, once per call: None -> the module constant as it is NOW, anything else as given."""
     cell = mesh_decimate_cell(decimate_cell)
     return MeshOptions(mesh_min_component_faces(min_component_faces), mesh_keep_largest(keep_largest), cell, mesh_project_iterations(project_iterations),
-                       mesh_project_max_move(None, cell), mesh_smooth_iterations(smooth_iterations), mesh_texture_texel(texture_texel))
+                       mesh_project_max_move(None, cell), mesh_smooth_iterations(smooth_iterations), mesh_texture_texel(texture_texel),
+                       mesh_simplify_faces(simplify_faces))
 
 
 def mesh_texture_png_level(n=None):

@@ -29,6 +29,7 @@ int preload_mcubes();
 int preload_mesh_components();
 int preload_mesh_smooth();
 int preload_mesh_decimate();
+int preload_mesh_simplify();
 int preload_mesh_project();
 int preload_mesh_pack();
 int preload_mesh_export();
@@ -58,6 +59,7 @@ int o2345_preload(void) {
     if ((e = o2345::preload_mesh_components())) bad = e;
     if ((e = o2345::preload_mesh_smooth())) bad = e;
     if ((e = o2345::preload_mesh_decimate())) bad = e;
+    if ((e = o2345::preload_mesh_simplify())) bad = e;
     if ((e = o2345::preload_mesh_project())) bad = e;
     if ((e = o2345::preload_mesh_pack())) bad = e;
     if ((e = o2345::preload_mesh_export())) bad = e;

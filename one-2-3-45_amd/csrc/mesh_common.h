@@ -1,5 +1,5 @@
-// What the mesh units share (mcubes.hip, mesh_components.hip, mesh_smooth.hip, mesh_decimate.hip, mesh_project.hip, mesh_texture.hip, mesh_export.hip,
-// mesh_pack.hip): the triangle reader, the wave-level counter, the row sorts, and on the host the workspace carver, the index-width dispatch, the
+// What the mesh units share (mcubes.hip, mesh_components.hip, mesh_smooth.hip, mesh_decimate.hip, mesh_simplify.hip, mesh_project.hip, mesh_texture.hip,
+// mesh_export.hip, mesh_pack.hip): the triangle reader, the wave-level counter, the row sorts, and on the host the workspace carver, the index-width dispatch, the
 // three-launch exclusive scan and the read-back of a call's device totals.  Everything is inline or a template: each unit keeps its own code object.
 #pragma once
 #include "common.h"
@@ -26,6 +26,13 @@ __device__ __forceinline__ bool mesh_triangle(const IDX* __restrict__ tris, long
 __device__ __forceinline__ void wave_count(bool pred, unsigned long long* counter) {
     const unsigned long long m = __ballot(pred);
     if (lane_id() == 0 && m) atomicAdd(counter, (unsigned long long)__popcll(m));
+}
+
+// the finaliser of splitmix64: keys that differ in high bits only spread too (decimation's tables, simplification's priorities)
+__device__ __forceinline__ unsigned long long dec_mix(unsigned long long x) {
+    x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull;
+    x ^= x >> 27; x *= 0x94D049BB133111EBull;
+    return x ^ (x >> 31);
 }
 
 // r = the d <= N entries of row, ascending, then ROW_PAD

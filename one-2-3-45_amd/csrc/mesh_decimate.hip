@@ -52,12 +52,6 @@ __device__ __forceinline__ double dec_decode(unsigned long long e) {
 // q of one coordinate; + 0.0 turns floor's -0.0 into +0.0, so that equal q have equal encodings
 __device__ __forceinline__ double dec_cell(double p, double cell) { return __dadd_rn(floor(__ddiv_rn(p, cell)), 0.0); }
 
-__device__ __forceinline__ unsigned long long dec_mix(unsigned long long x) {      // the finaliser of splitmix64: keys that differ in high bits only spread too
-    x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull;
-    x ^= x >> 27; x *= 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
-
 __device__ __forceinline__ void dec_sort3(int& x, int& y, int& z) {
     regs_cmpswap(x, y); regs_cmpswap(y, z); regs_cmpswap(x, y);
 }

@@ -621,6 +621,221 @@ def decimate_mesh(verts, faces, cell, colors=None):
     return v_out, f_out, c_out, cluster, info
 
 
+# ------------------------------------------------------------------------------------------------------------------ simplification
+SIMPLIFY_WIDE, SIMPLIFY_SHARE = 8, 2       # a round's participants: the cheapest max(1, min(WIDE need, ceil(C / SHARE))) candidates, by exponent bin
+_QUADRIC_PAIRS = ((0, 0), (0, 1), (0, 2), (0, 3), (1, 1), (1, 2), (1, 3), (2, 2), (2, 3), (3, 3))      # the ten entries over (nx, ny, nz, d)
+
+
+def _check_simplify_args(target_faces, max_error, max_rounds):
+    for name, x in (("target_faces", target_faces), ("max_rounds", max_rounds)):
+        if isinstance(x, (bool, np.bool_)) or not isinstance(x, (int, np.integer)) or x < 0 or x >= 2 ** 31:
+            raise ValueError(f"simplify: {name} must be a non-negative integer below 2^31, got {x!r}")
+    e = float(max_error)
+    if not e >= 0.0:
+        raise ValueError(f"simplify: max_error must be >= 0 (inf = no limit), got {max_error!r}")
+    return int(target_faces), e, int(max_rounds)
+
+
+def _cross(e1, e2):
+    return (e1[:, 1] * e2[:, 2] - e1[:, 2] * e2[:, 1], e1[:, 2] * e2[:, 0] - e1[:, 0] * e2[:, 2], e1[:, 0] * e2[:, 1] - e1[:, 1] * e2[:, 0])
+
+
+def simplify_quadrics(P0, P1, P2):
+    """The area-weighted plane quadric of every triangle (corners float64 [m,3] each) -> float64 [m,10], the entries xx xy xz xd yy yz yd zz zd dd:
+    n = (P1 - P0) x (P2 - P0), nn = (nx nx + ny ny) + nz nz; nn > 0: s = 0.5 / sqrt(nn), d = -((nx P0x + ny P0y) + nz P0z), entry = (a b) s; else zeros."""
+    with np.errstate(all="ignore"):
+        nx, ny, nz = _cross(P1 - P0, P2 - P0)
+        nn = (nx * nx + ny * ny) + nz * nz
+        s = 0.5 / np.sqrt(nn)
+        c = (nx, ny, nz, -((nx * P0[:, 0] + ny * P0[:, 1]) + nz * P0[:, 2]))
+        K = np.stack([(c[a] * c[b]) * s for a, b in _QUADRIC_PAIRS], 1)
+    K[~(nn > 0)] = 0.0
+    return K
+
+
+def simplify_error(Q, P):
+    """p^T Q p of the quadrics Q float64 [k,10] at the points P float64 [k,3], the ONE expression of the definition (the cost is max(0, .) of it)."""
+    x, y, z = P[:, 0], P[:, 1], P[:, 2]
+    q = Q.T
+    with np.errstate(all="ignore"):
+        r0 = ((q[0] * x + q[1] * y) + q[2] * z) + q[3]
+        r1 = ((q[1] * x + q[4] * y) + q[5] * z) + q[6]
+        r2 = ((q[2] * x + q[5] * y) + q[7] * z) + q[8]
+        r3 = ((q[3] * x + q[6] * y) + q[8] * z) + q[9]
+        return ((x * r0 + y * r1) + z * r2) + r3
+
+
+def simplify_keeps_side(T, corner, Pu):
+    """The flip test: triangles T float64 [k,3,3], ``corner`` [k] the corner that moves to Pu [k,3] -> bool [k]: n . n' > 0 for the normals before and
+    after ((P1 - P0) x (P2 - P0), the dot product (x x + y y) + z z); a zero normal on either side fails."""
+    T2 = T.copy()
+    T2[np.arange(T.shape[0]), corner] = Pu
+    with np.errstate(all="ignore"):
+        a = _cross(T[:, 1] - T[:, 0], T[:, 2] - T[:, 0])
+        b = _cross(T2[:, 1] - T2[:, 0], T2[:, 2] - T2[:, 0])
+        return ((a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]) > 0.0
+
+
+def _mix64(x):
+    """the finaliser of splitmix64 on a uint64 array (the hash of the device's decimation tables)"""
+    x = x ^ (x >> np.uint64(30))
+    x = x * np.uint64(0xBF58476D1CE4E5B9)
+    x = x ^ (x >> np.uint64(27))
+    x = x * np.uint64(0x94D049BB133111EB)
+    return x ^ (x >> np.uint64(31))
+
+
+def _expand(rows_start, rows_count):
+    """-> (owner, index): for every row r its entries rows_start[r] .. + rows_count[r], flattened"""
+    owner = np.repeat(np.arange(rows_count.size), rows_count)
+    first = np.cumsum(rows_count) - rows_count
+    return owner, rows_start[owner] + (np.arange(owner.size) - first[owner])
+
+
+def simplify_mesh(verts, faces, target_faces, max_error=np.inf, max_rounds=256, colors=None, trace=None):
+    """Simplification by rounds of independent half-edge collapses ordered by Garland - Heckbert's quadric error (host twin of ops.mesh_simplify, and the
+    definition of its result, to the last bit) -> (verts float64 [Nk,3], faces [Mk,3] in the dtype of ``faces``, colors, source int32 [Nk], merged int32 [N],
+    info).  ``target_faces``: rounds run while more faces are alive; the last round may go below it ("at most n").  Everything is float64, one operation at
+    a time, in the order written.  Placement is subset placement: collapsing v -> u removes v and u keeps its bits; positions never change.
+    Quadrics, once, from the input: K_t = simplify_quadrics of face t; Q_v = the sequential entrywise sum of K_t over the faces of v in ascending face
+    order.  After a collapse Q_u <- Q_u + Q_v.
+    A round, on its live faces, with N(v) the distinct neighbours of v (vertex_adjacency's rows) and their multiplicities.  The half-edge v -> u (u in
+    N(v)) is eligible iff (1) every edge at v has exactly two faces -- boundary vertices and vertices on non-manifold edges are never removed, though they
+    may be targets; (2) |N(v) & N(u)| = 2, the link condition; (3) every face at v without u passes simplify_keeps_side with P_v replaced by P_u; (4) e =
+    simplify_error(Q_v + Q_u, P_u) is finite and cost = (e if e > 0 else 0) <= max_error.  The candidate of v: its eligible u of least cost, ties to the
+    smaller u.  With C candidates and need = ceil((live faces - target) / 2): bin(cost) = the biased exponent field of the double; B = the smallest bin
+    whose cumulative count reaches max(1, min(8 need, ceil(C / 2))); the candidates with bin <= B take part, with priority (mix64(v + (round << 32)), v).
+    v is selected iff its priority is the smallest among the participants within graph distance 2 (m1[y] = min over y and N(y), m2[v] = min of m1 over v
+    and N(v), selected iff m2[v] is v's own): the closed 1-rings of the selected vertices are disjoint, so every test made on the round's mesh still holds
+    when all selected collapses are applied at once.  Faces are remapped, those with two equal corners dropped; face order, corner order and orientation
+    stay.  Stop: live faces <= target ("target"), no candidate ("blocked"), ``max_rounds`` rounds done ("rounds").
+    Output: a vertex is kept iff a kept face references it, in the old order, bit for bit; faces renumbered by an exclusive scan; ``source`` new -> old;
+    ``merged[v]`` the new index of the vertex v ended in, following the collapses, or -1; ``colors`` those of the kept vertices.  ``info`` = {"rounds",
+    "vertices", "triangles", "collapses" (per round), "max_cost" (the largest applied), "stopped"}.  ``trace``: a list that receives, per round,
+    {"faces" (the round's live faces, old indices), "selected", "targets"}.  NOT done: optimal (solved) placement, boundary and non-manifold collapses,
+    a valence cap, an exact hit of the target.  Refused (ValueError): a non-finite coordinate, a face index outside [0, N), a face with a repeated
+    index, N >= 2^30 or 6 M >= 2^31, bad arguments."""
+    target, max_error, max_rounds = _check_simplify_args(target_faces, max_error, max_rounds)
+    p = np.asarray(verts, dtype=np.float64).reshape(-1, 3)
+    fin = np.asarray(faces).reshape(-1, 3)
+    F = fin.astype(np.int64)                                           # a copy: the live faces, in face order
+    n, m0 = p.shape[0], F.shape[0]
+    if n >= 2 ** 30 or 6 * m0 >= 2 ** 31:
+        raise ValueError(f"simplify: bad sizes ({n} vertices, {m0} faces; the tables are int32)")
+    if not np.isfinite(p).all():
+        raise ValueError("simplify: non-finite vertex coordinate")
+    if F.size and (F.min() < 0 or F.max() >= n):
+        raise ValueError(f"faces index outside 0 .. {n - 1}")
+    repeated = int(np.count_nonzero((F[:, 0] == F[:, 1]) | (F[:, 1] == F[:, 2]) | (F[:, 0] == F[:, 2])))
+    if repeated:
+        raise ValueError(f"simplify: {repeated} faces repeat a vertex index")
+    # Q_v: sequential over the rank of a face in its vertex's row (rows by falling length: the rows with a k-th face are a prefix, as in smooth_vertices)
+    K = simplify_quadrics(p[F[:, 0]], p[F[:, 1]], p[F[:, 2]])
+    Q = np.zeros((n, 10), np.float64)
+    if m0:
+        cv = F.reshape(-1)
+        order = np.argsort(cv, kind="stable")                          # by vertex, faces ascending inside
+        cnt = np.bincount(cv, minlength=n)
+        start = np.cumsum(cnt) - cnt
+        rows = np.argsort(-cnt, kind="stable")
+        rcnt, rstart = cnt[rows], start[rows]
+        have = np.searchsorted(-rcnt, -np.arange(int(rcnt[0])), side="left")
+        acc = np.zeros((n, 10), np.float64)
+        for k, h in enumerate(have):
+            acc[:h] = acc[:h] + K[order[rstart[:h] + k] // 3]
+        Q[rows] = acc
+    parent = np.arange(n, dtype=np.int64)
+    collapses, max_cost, stopped = [], 0.0, None
+    while stopped is None:
+        m = F.shape[0]
+        if m <= target:
+            stopped = "target"
+            break
+        if len(collapses) == max_rounds:
+            stopped = "rounds"
+            break
+        rnd = len(collapses)
+        a, b, c = F[:, 0], F[:, 1], F[:, 2]
+        key, mult = np.unique(np.concatenate([a, b, b, c, c, a]) * n + np.concatenate([b, a, c, b, a, c]), return_counts=True)
+        first, second = key // n, key % n
+        deg = np.bincount(first, minlength=n)
+        off = np.cumsum(deg) - deg
+        ok1 = (deg > 0) & (np.bincount(first, weights=(mult != 2), minlength=n) == 0)
+        he = np.flatnonzero(ok1[first])
+        hv, hu = first[he], second[he]
+        # (2) the link condition: the w of N(v) that are in N(u)
+        own, at = _expand(off[hv], deg[hv])
+        q = hu[own] * n + second[at]
+        i = np.minimum(np.searchsorted(key, q), key.size - 1)
+        ok = np.bincount(own, weights=(key[i] == q), minlength=he.size) == 2
+        he, hv, hu = he[ok], hv[ok], hu[ok]
+        # (3) the faces at v without u keep their side
+        cv = F.reshape(-1)
+        order = np.argsort(cv, kind="stable")
+        tcnt = np.bincount(cv, minlength=n)
+        tstart = np.cumsum(tcnt) - tcnt
+        own, at = _expand(tstart[hv], tcnt[hv])
+        t, corner = order[at] // 3, order[at] % 3
+        other = ~(F[t] == hu[own][:, None]).any(1)
+        own, t, corner = own[other], t[other], corner[other]
+        flips = ~simplify_keeps_side(p[F[t]], corner, p[hu[own]])
+        ok = np.bincount(own, weights=flips, minlength=he.size) == 0
+        he, hv, hu = he[ok], hv[ok], hu[ok]
+        # (4) the cost
+        e = simplify_error(Q[hv] + Q[hu], p[hu])
+        cost = np.where(e > 0.0, e, 0.0)
+        ok = np.isfinite(e) & (cost <= max_error)
+        hv, hu, cost = hv[ok], hu[ok], cost[ok]
+        if hv.size == 0:
+            stopped = "blocked"
+            break
+        best = np.lexsort((hu, cost, hv))
+        best = best[np.concatenate([[True], hv[best][1:] != hv[best][:-1]])]
+        cv_, cu_, cc_ = hv[best], hu[best], cost[best]                 # the candidates, ascending v
+        C = cv_.size
+        need = (m - target + 1) // 2
+        want = max(1, min(SIMPLIFY_WIDE * need, (C + SIMPLIFY_SHARE - 1) // SIMPLIFY_SHARE))
+        bins = (cc_.view(np.uint64) >> np.uint64(52)).astype(np.int64) & 0x7FF
+        B = int(np.searchsorted(np.cumsum(np.bincount(bins, minlength=2048)), want, side="left"))
+        part = bins <= B
+        pv, pu, pc = cv_[part], cu_[part], cc_[part]
+        h = _mix64(pv.astype(np.uint64) + (np.uint64(rnd) << np.uint64(32)))
+        rank = np.empty(pv.size, np.int64)
+        rank[np.lexsort((pv, h))] = np.arange(pv.size)                 # the order of the pairs (hash, v)
+        R = np.full(n, n + 1, np.int64)
+        R[pv] = rank
+        m1 = R.copy()
+        np.minimum.at(m1, first, R[second])
+        m2 = m1.copy()
+        np.minimum.at(m2, first, m1[second])
+        sel = m2[pv] == rank
+        sv, su = pv[sel], pu[sel]
+        if trace is not None:
+            trace.append({"faces": F.copy(), "selected": sv.copy(), "targets": su.copy()})
+        parent[sv] = su
+        Q[su] = Q[su] + Q[sv]
+        remap = np.arange(n, dtype=np.int64)
+        remap[sv] = su
+        F = remap[F]
+        F = F[(F[:, 0] != F[:, 1]) & (F[:, 1] != F[:, 2]) & (F[:, 0] != F[:, 2])]
+        collapses.append(int(sv.size))
+        max_cost = max(max_cost, float(pc[sel].max()))
+    used = np.zeros(n, bool)
+    used[F.reshape(-1)] = True
+    new_index = np.cumsum(used) - used
+    source = np.flatnonzero(used).astype(np.int32)
+    root = parent
+    while True:
+        nxt = root[root]
+        if np.array_equal(nxt, root):
+            break
+        root = nxt
+    merged = np.where(used[root], new_index[root], -1).astype(np.int32)
+    info = {"rounds": len(collapses), "vertices": int(source.size), "triangles": int(F.shape[0]), "collapses": collapses, "max_cost": max_cost,
+            "stopped": stopped}
+    return p[source], new_index[F].astype(fin.dtype), None if colors is None else np.asarray(colors)[source], source, merged, info
+
+
 # ------------------------------------------------------------------------------------------------------------------ projection
 def _check_project_args(resolution, iterations, level, tol, max_step, max_move, bound_min, bound_max):
     if isinstance(iterations, (bool, np.bool_)) or not isinstance(iterations, (int, np.integer)) or not 1 <= iterations <= 64:
@@ -1073,7 +1288,7 @@ def write_textured(path, positions, uv, normals, image, bounds=None, png_level=1
         write_obj_texture_files(path, obj_texture_text_numpy(p, uv, normals, obj_coordinate_digits(p if bounds is None else bounds)), png)
 
 
-def convert_mesh(ply_path, out_path, min_component_faces=0, keep_largest=False, smooth_iterations=0, decimate_cell=0):
+def convert_mesh(ply_path, out_path, min_component_faces=0, keep_largest=False, smooth_iterations=0, decimate_cell=0, simplify_faces=0):
     """convert_mesh_format (utils/utils.py:31-47) for a mesh already on disk: read the PLY, exchange y and z, reverse the faces, write ``out_path`` by its
     extension (.glb or .obj) with the PLY's vertex colours.  ``min_component_faces`` / ``keep_largest``: filter_components on the way (off by default).
     ``smooth_iterations`` (0 = off): smooth_vertices with its default factors and pinning, after the filter, on the file's float32 positions cast to
@@ -1082,6 +1297,9 @@ def convert_mesh(ply_path, out_path, min_component_faces=0, keep_largest=False, 
     ``decimate_cell`` (0 = off): decimate_mesh after the filter and before the smoothing, with the cell in the FILE's own units, on the float32 positions
     cast to float64, the result cast back to float32, the colours merged as decimate_mesh defines.  For the same reason that is not byte-equal to the
     device export, which clusters the index coordinates (cell in units of the grid spacing) and colours the new vertices.
+    ``simplify_faces`` (0 = off): simplify_mesh down to that many faces after the decimation and before the smoothing, on the float32 positions cast to
+    float64 (the kept vertices keep their float32 bits), the colours those of the kept vertices.  Not byte-equal to the device export either, which
+    collapses the index coordinates and colours the kept vertices afterwards.
     There is no ``project_iterations`` here: projecting vertices onto the SDF's zero set (project_vertices, ops.mesh_project) needs the network, and a
     mesh file has none; for the same reason there is no ``texture_texel``.  Returns ``out_path``."""
     ext = _asset_ext(out_path)
@@ -1094,6 +1312,9 @@ def convert_mesh(ply_path, out_path, min_component_faces=0, keep_largest=False, 
         v, f, c, _, _, _ = filter_components(v, f, c, None, min_component_faces, keep_largest)
     if decimate_cell:
         v, f, c, _, _ = decimate_mesh(v.astype(np.float64), f, decimate_cell, c)
+        v = v.astype(np.float32)
+    if simplify_faces:
+        v, f, c, _, _, _ = simplify_mesh(v.astype(np.float64), f, simplify_faces, colors=c)
         v = v.astype(np.float32)
     if smooth_iterations:
         v = smooth_vertices(v.astype(np.float64), f, smooth_iterations).astype(np.float32)

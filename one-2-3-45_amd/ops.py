@@ -1040,6 +1040,57 @@ def mesh_decimate(verts_idx, tris, cell=None):
     return verts, tris_out, cluster, {"clusters": ncl.value, "vertices": nvo.value, "triangles": nto.value, "degenerate": ndeg.value, "duplicate": ndup.value}
 
 
+# ---------------------------------------------------------------------------------------------------------- mesh simplification
+_SIMPLIFY_STOPPED = ("target", "blocked", "rounds")
+_simplify_names = {}
+
+
+def _simplify_stats_index():
+    """The names of o2345_mesh_simplify_count's stats block (include/o2345.h, the O2345_SIMPLIFY_* enumerators) -> {name: value}, read from the header's
+    own text once: the block is declared there and nowhere else."""
+    if not _simplify_names:
+        import re
+        _simplify_names.update({k: int(v) for k, v in re.findall(r"O2345_SIMPLIFY_(\w+) = (\d+)", open(_lib.HEADER).read())})
+    return _simplify_names
+
+
+def simplify_info(stats):
+    """The stats block of o2345_mesh_simplify_count (int64, on the host) -> the info dict of mesh_io.simplify_mesh."""
+    ix = _simplify_stats_index()
+    st = [int(x) for x in stats]
+    rounds = st[ix["ROUNDS"]]
+    return {"rounds": rounds, "vertices": st[ix["VERTICES"]], "triangles": st[ix["TRIANGLES"]], "collapses": st[ix["STATS"]:ix["STATS"] + rounds],
+            "max_cost": _double_of_bits(st[ix["MAX_COST_BITS"]]), "stopped": _SIMPLIFY_STOPPED[st[ix["STOPPED"]]]}
+
+
+@_on_device
+def mesh_simplify(verts_idx, tris, target_faces=None, max_error=None, max_rounds=None):
+    """Simplification by quadric-error half-edge collapses on the device (== mesh_io.simplify_mesh, to the last bit; definitions in csrc/mesh_simplify.hip).
+    verts_idx fp64 [N,3], tris [M,3] int32 / int64; ``target_faces``: at most that many triangles if reachable; ``max_error``: the largest quadric error
+    of a collapse (inf: no limit); ``max_rounds``; None: the config defaults -> (verts fp64 [Nk,3], tris [Mk,3] of the same dtype, source int32 [Nk]: new
+    -> old vertex index, merged int32 [N]: the new index of the vertex every old vertex ended in or -1, info = {"rounds", "vertices", "triangles",
+    "collapses", "max_cost", "stopped"}).  The kept vertices are bit copies; the inputs are not written.  One synchronisation per round.  With a target of
+    0 and no error limit the stage is off: no kernel is launched, the inputs are returned as they are, ``source``, ``merged`` and ``info`` are None.  A
+    target of 0 WITH an error limit runs until the limit blocks every collapse."""
+    target = config.mesh_simplify_faces(target_faces)
+    max_error, max_rounds = config.mesh_simplify_max_error(max_error), config.mesh_simplify_max_rounds(max_rounds)
+    if target == 0 and max_error == float("inf"):
+        return verts_idx, tris, None, None, None
+    tris, ib = _triangles(tris)
+    _vertices(verts_idx)
+    nv, nt, dev = verts_idx.shape[0], tris.shape[0], verts_idx.device
+    ws, wsb = _scratch("o2345_mesh_simplify_workspace_bytes", (nv, nt), dev, "mesh_simplify")
+    stats = torch.empty(_simplify_stats_index()["STATS"] + max_rounds, dtype=torch.int64, device=dev)
+    call("o2345_mesh_simplify_count", verts_idx, tris, ib, nv, nt, target, max_error, max_rounds, ws, wsb, stats)
+    info = simplify_info(stats.cpu().numpy())
+    verts = torch.empty(info["vertices"], 3, dtype=torch.float64, device=dev)
+    tris_out = torch.empty(info["triangles"], 3, dtype=tris.dtype, device=dev)
+    source = torch.empty(info["vertices"], dtype=torch.int32, device=dev)
+    merged = torch.empty(nv, dtype=torch.int32, device=dev)
+    call("o2345_mesh_simplify_emit", verts_idx, ib, nv, nt, ws, verts, tris_out, source, merged)
+    return verts, tris_out, source, merged, info
+
+
 # ---------------------------------------------------------------------------------------------------------- mesh projection
 @_on_device
 def mesh_project(blob, vol_cl, verts_idx, resolution, iterations, level=0.0, tol=None, max_step=None, max_move=None, bound_min=(-1.0, -1.0, -1.0),
@@ -1081,16 +1132,19 @@ def project_info(stats, iterations):
 
 def mesh_cleanup(verts_idx, tris, opts, blob, vol_cl, resolution, level=0.0, bound_min=(-1.0, -1.0, -1.0), bound_max=(1.0, 1.0, 1.0), precision=None,
                  project=True):
-    """What follows marching cubes, in its one order: component filter -> decimation (the cell in grid spacings) -> Newton projection onto ``sdf ==
-    level`` (the field: ``blob``, ``vol_cl``, ``precision``), so that a caller's gradient, colours, packing and copies run on the kept, decimated,
-    projected vertices.  ``opts``: a config.MeshOptions; ``project=False`` withholds the projection.  A stage that is off launches nothing and leaves
-    its entry None -> (verts_idx, tris, {"components", "components_kept", "decimate", "project"})."""
-    info = {"components": None, "components_kept": None, "decimate": None, "project": None}
+    """What follows marching cubes, in its one order: component filter -> decimation (the cell in grid spacings) -> simplification (edge collapse down to
+    ``opts.simplify_faces`` triangles, error limit and rounds from config) -> Newton projection onto ``sdf == level`` (the field: ``blob``, ``vol_cl``,
+    ``precision``), so that a caller's gradient, colours, packing and copies run on the kept, decimated, simplified, projected vertices.  ``opts``: a
+    config.MeshOptions; ``project=False`` withholds the projection.  A stage that is off launches nothing and leaves its entry None -> (verts_idx, tris,
+    {"components", "components_kept", "decimate", "simplify", "project"})."""
+    info = {"components": None, "components_kept": None, "decimate": None, "simplify": None, "project": None}
     if opts.min_component_faces or opts.keep_largest:
         verts_idx, tris, _, cc = mesh_filter_components(verts_idx, tris, opts.min_component_faces, opts.keep_largest)
         info.update(cc)
     if opts.decimate_cell:
         verts_idx, tris, _, info["decimate"] = mesh_decimate(verts_idx, tris, opts.decimate_cell)
+    if opts.simplify_faces:
+        verts_idx, tris, _, _, info["simplify"] = mesh_simplify(verts_idx, tris, opts.simplify_faces)
     if opts.project_iterations and project:
         verts_idx, info["project"] = mesh_project(blob, vol_cl, verts_idx, resolution, opts.project_iterations, level=level, max_move=opts.project_max_move,
                                                   bound_min=bound_min, bound_max=bound_max, precision=precision)

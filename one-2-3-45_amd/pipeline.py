@@ -278,29 +278,30 @@ def _texture_block(texture):
 
 @torch.no_grad()
 def extract_mesh(wt, vol, proj, cam_pos, resolution, return_index_verts=False, min_component_faces=None, keep_largest=None, smooth_iterations=None,
-                 decimate_cell=None, project_iterations=None):
-    """extract_fields + marching cubes [+ component filter] [+ decimation] [+ projection onto the zero set] + vertex colouring
+                 decimate_cell=None, project_iterations=None, simplify_faces=None):
+    """extract_fields + marching cubes [+ component filter] [+ decimation] [+ simplification] [+ projection onto the zero set] + vertex colouring
     (trainer_generic.py:1309-1363) [+ smoothing], all on the device.  The options: None = the config default, off unless set (config.mesh_options)."""
     m = _mesh_fields(wt, vol, proj, cam_pos, resolution,
-                     config.mesh_options(min_component_faces, keep_largest, decimate_cell, project_iterations, smooth_iterations, texture_texel=0))
+                     config.mesh_options(min_component_faces, keep_largest, decimate_cell, project_iterations, smooth_iterations, texture_texel=0,
+                                         simplify_faces=simplify_faces))
     return (m.verts_idx if return_index_verts else m.verts), m.tris, m.rgb, m.u
 
 
 @torch.no_grad()
 def export_mesh_ply(path, wt, vol, proj, cam_pos, resolution, scale_mat=None, trans_mat=None, min_component_faces=None, keep_largest=None,
-                    smooth_iterations=None, decimate_cell=None, project_iterations=None):
+                    smooth_iterations=None, decimate_cell=None, project_iterations=None, simplify_faces=None):
     """validate_colored_mesh end to end (trainer_generic.py:1309-1382): SDF grid, marching cubes, vertex colours, frame transforms,
     uint8 colours and the binary PLY -- records packed on the device (csrc/mesh_pack.hip), one D2H copy, one file write.
     The options are extract_mesh's.  Returns (n_vertices, n_triangles)."""
     from . import mesh_io
     verts_idx, tris, rgb, _ = extract_mesh(wt, vol, proj, cam_pos, resolution, True, min_component_faces, keep_largest, smooth_iterations, decimate_cell,
-                                           project_iterations)
+                                           project_iterations, simplify_faces)
     return mesh_io.export_mesh(path, verts_idx, tris, resolution, scale_mat=scale_mat, trans_mat=trans_mat, vertex_colors=rgb if verts_idx.shape[0] else None)
 
 
 @torch.no_grad()
 def export_mesh_asset(path, wt, vol, proj, cam_pos, resolution, scale_mat=None, trans_mat=None, normals=False, min_component_faces=None, keep_largest=None,
-                      smooth_iterations=None, decimate_cell=None, project_iterations=None, texture_texel=None):
+                      smooth_iterations=None, decimate_cell=None, project_iterations=None, texture_texel=None, simplify_faces=None):
     """export_mesh_ply followed by convert_mesh_format (utils/utils.py:31-47) without the PLY in between: the coloured mesh as ``.glb`` or ``.obj`` in the
     asset frame ((x, y, z) -> (x, z, y), faces reversed), buffers / text packed on the device (csrc/mesh_export.hip).  ``normals=True`` adds unit vertex
     normals from the SDF gradient the vertex colouring already computed (at the unsmoothed vertices when ``smooth_iterations`` is on, at the projected ones
@@ -309,7 +310,7 @@ def export_mesh_asset(path, wt, vol, proj, cam_pos, resolution, scale_mat=None, 
     c x c cell per pair of triangles (_mesh_fields, ``texture``), 3 M unwelded vertices with texture coordinates and no vertex colours; the PNG sits inside
     the ``.glb``, or as ``.mtl`` + ``.png`` next to the ``.obj``.  A ``.ply`` path with a texture requested raises ValueError."""
     from . import mesh_io
-    opts = config.mesh_options(min_component_faces, keep_largest, decimate_cell, project_iterations, smooth_iterations, texture_texel)
+    opts = config.mesh_options(min_component_faces, keep_largest, decimate_cell, project_iterations, smooth_iterations, texture_texel, simplify_faces)
     if opts.texture_texel and mesh_io._asset_ext(path) == ".ply":
         raise ValueError("texture: a .ply has no texture coordinates; the output is .glb or .obj")
     m = _mesh_fields(wt, vol, proj, cam_pos, resolution, opts)
@@ -415,12 +416,14 @@ def _write_previews(wt, vol, proj, cam_pos, u, s, n, folder):
 
 @torch.no_grad()
 def reconstruct_folder(root_dir, name, wt, out_ply, D=96, resolution=256, render_val_image=False, output_format=None, min_component_faces=None,
-                       keep_largest=None, smooth_iterations=None, decimate_cell=None, project_iterations=None, texture_texel=None, preview_views=None, mesh_error=None):
+                       keep_largest=None, smooth_iterations=None, decimate_cell=None, project_iterations=None, texture_texel=None, preview_views=None, mesh_error=None,
+                       simplify_faces=None):
     """run.py's reconstruction stage without the reference tree: Zero123-style folder (dataset.SceneFolder) -> coloured mesh (binary PLY in
     the original frame), optionally the val image of the target view.  ``output_format`` ".obj" / ".glb" (run.py --output_format) also writes
     ``mesh<ext>`` next to ``out_ply`` in the asset frame, from the same device buffers.  The mesh options are extract_mesh's.  Returns
-    dict(vertices, triangles, kept_voxels, ply, components, components_kept, smooth_iterations, decimate_cell, decimate, project_iterations, project[, asset]
-    [, color, depth]); the two component counts are None when the filter is off, ``decimate`` (the counts of ops.mesh_decimate) when decimation is, and
+    dict(vertices, triangles, kept_voxels, ply, components, components_kept, smooth_iterations, decimate_cell, decimate, simplify_faces, simplify,
+    project_iterations, project[, asset][, color, depth]); the two component counts are None when the filter is off, ``decimate`` (the counts of
+    ops.mesh_decimate) when decimation is, ``simplify`` (the info of ops.mesh_simplify: rounds, counts, why it stopped) when simplification is, and
     ``project`` (the info of ops.mesh_project) when projection is.  ``texture_texel`` (None: the config default, 0 = off): the texture atlas of
     export_mesh_asset for the ``output_format`` asset only -- the PLY stays vertex-coloured; the result's "texture" is {width, height, texel, texels},
     or None when no textured asset was written.  ``preview_views`` (None: the config default O2345_PREVIEW_VIEWS, 0 = off: nothing is launched and the
@@ -439,7 +442,7 @@ def reconstruct_folder(root_dir, name, wt, out_ply, D=96, resolution=256, render
     T = lambda t: t.to(dev).contiguous().float()
     vol = build_volume(wt, T(s["images"]), T(s["affine_mats"]), s["partial_vol_origin"].numpy(), D, 2.0 / (D - 1))
     proj, cam_pos = camera_terms(T(s["intrinsics"]), T(s["w2cs"]))
-    opts = config.mesh_options(min_component_faces, keep_largest, decimate_cell, project_iterations, smooth_iterations, texture_texel)
+    opts = config.mesh_options(min_component_faces, keep_largest, decimate_cell, project_iterations, smooth_iterations, texture_texel, simplify_faces)
     previews = config.preview_views(preview_views)
     asset = output_format in (".obj", ".glb")
     m = _mesh_fields(wt, vol, proj, cam_pos, resolution, opts if asset else opts._replace(texture_texel=0))          # the atlas is for the asset only
@@ -447,7 +450,7 @@ def reconstruct_folder(root_dir, name, wt, out_ply, D=96, resolution=256, render
     nv, nt = mesh_io.export_mesh(out_ply, m.verts_idx, m.tris, resolution, scale_mat=s["scale_mat"], trans_mat=s["trans_mat"], vertex_colors=rgb)
     out = {"vertices": nv, "triangles": nt, "kept_voxels": int(vol["n_voxels"]), "ply": str(out_ply), "components": m.info["components"],
            "components_kept": m.info["components_kept"], "smooth_iterations": opts.smooth_iterations, "decimate_cell": opts.decimate_cell,
-           "decimate": m.info["decimate"], "project_iterations": opts.project_iterations, "project": m.info["project"], "texture": _texture_block(m.texture)}
+           "decimate": m.info["decimate"], "simplify_faces": opts.simplify_faces, "simplify": m.info["simplify"], "project_iterations": opts.project_iterations, "project": m.info["project"], "texture": _texture_block(m.texture)}
     if asset:
         out["asset"] = os.path.join(os.path.dirname(str(out_ply)), "mesh" + output_format)
         mesh_io.export_asset(out["asset"], m.verts_idx, m.tris, resolution, scale_mat=s["scale_mat"], trans_mat=s["trans_mat"], vertex_colors=rgb,

@@ -22,6 +22,10 @@ fed the same arrays.  Two meshes: BASELINE config 2 (8 views, 128^3 volume, 256^
              count and image size, the three kernels alone (HIP events), the gradient + colour calls over the texel points, the D2H copy of the
              textured GLB's buffers, mesh_io.png_bytes at zlib levels 0 and 1 (host clock), and whole-export variants textured against
              vertex-coloured inside the same alternating loop as the others
+  simplify   quadric-error edge collapse (csrc/mesh_simplify.hip) of the config's mesh down to the face count clustering reached at cell 2: the rounds and
+             the collapses of each, bytes-equality with the host twin (mesh_io.simplify_mesh, host clock, one call), the op as a whole (HIP events; it
+             synchronises once per round), ops.mesh_distance of the result against the raw mesh in both directions next to the same numbers for the
+             cell-2 clustering, each also after 4 projection rounds, and whole-export variants inside the same alternating loop as the others
 Medians over --reps calls after --warmup calls; the ratio against the PLY of the SAME run is what to read.  Prints one JSON line.
 
     python tools/time_mesh_export.py [--reps 9] [--warmup 3] [--skip-512]
@@ -180,6 +184,28 @@ def one_mesh(dev, wt, tmp, D, R, ray_scale, a, numpy_writer):
     res["project"] = {"iterations": PIT}
     for key, v, mm in (("all", verts_idx, 1.0), ("decimated", d_verts, max(1.0, CELL))):
         res["project"][key] = dict(proj_op(v, mm)[1], vertices=int(v.shape[0]), max_move=mm, mesh_project_ms=med_events(lambda: proj_op(v, mm), a.reps, a.warmup))
+    # edge collapse down to clustering's face count: the op, the twin, and both results as surfaces against the raw mesh
+    TARGET = int(d_info["triangles"])
+    s_verts, s_tris, _, _, s_info = ops.mesh_simplify(verts_idx, tris, TARGET)
+    t0 = time.perf_counter()
+    twin = mio.simplify_mesh(hv, hf, TARGET)
+    t1 = time.perf_counter()
+
+    def error_to_raw(v, t):
+        d = ops.mesh_distance(v, t, verts_idx, tris, 0.5, (0.25, 0.5, 1.0, 2.0))
+        return {"a_to_b": {k: d["a_to_b"][k] for k in ("mean", "max")}, "b_to_a": {k: d["b_to_a"][k] for k in ("mean", "max")}, "chamfer": d["chamfer"],
+                "fscore": d["fscore"], "vertices": int(v.shape[0]), "triangles": int(t.shape[0])}
+    res["simplify"] = dict(s_info, target=TARGET,
+                           equals_host_twin=bool(s_verts.cpu().numpy().tobytes() == twin[0].tobytes() and np.array_equal(s_tris.cpu().numpy(), twin[1])
+                                                 and s_info == twin[5]),
+                           kernel_ms={"mesh_simplify": med_events(lambda: ops.mesh_simplify(verts_idx, tris, TARGET), a.reps, a.warmup),
+                                      "mesh_decimate": med_events(lambda: ops.mesh_decimate(verts_idx, tris, CELL), a.reps, a.warmup),
+                                      "adjacency": med_events(lambda: ops.mesh_vertex_adjacency(tris, n), a.reps, a.warmup),
+                                      "grad_color_simplified": med_events(lambda: grad_color(s_verts), a.reps, a.warmup)},
+                           host_twin_ms_once=(t1 - t0) * 1e3,
+                           error_to_raw={"collapse": error_to_raw(s_verts, s_tris), "cluster": error_to_raw(d_verts, d_tris),
+                                         "collapse_project4": error_to_raw(proj_op(s_verts, 1.0)[0], s_tris),
+                                         "cluster_project4": error_to_raw(proj_op(d_verts, max(1.0, CELL))[0], d_tris)})
     # the texture atlas: kernels alone, the network calls over the texels, the copy and the PNG
     def grad_color_pts(pts):
         gg = ops.sdf_mlp(wt.sdf_blob, vol["vol_cl"], pts, variant=2, precision=wt.sdf_precision)["grad"]
@@ -229,6 +255,9 @@ def one_mesh(dev, wt, tmp, D, R, ray_scale, a, numpy_writer):
         "obj_decimate2_texture4": lambda: pipeline.export_mesh_asset(P("_dt4.obj"), *A, decimate_cell=CELL, texture_texel=4),
         "glb_decimate2_project4_texture4": lambda: pipeline.export_mesh_asset(P("_dpt4.glb"), *A, decimate_cell=CELL, project_iterations=PIT, texture_texel=4),
         "glb_texture4": lambda: pipeline.export_mesh_asset(P("_t4.glb"), *A, texture_texel=4),
+        "ply_simplify": lambda: pipeline.export_mesh_ply(P("_q.ply"), *A, simplify_faces=TARGET),
+        "glb_simplify": lambda: pipeline.export_mesh_asset(P("_q.glb"), *A, simplify_faces=TARGET),
+        "ply_simplify_project4": lambda: pipeline.export_mesh_ply(P("_qp.ply"), *A, simplify_faces=TARGET, project_iterations=PIT),
     }
     # alternated like the stage variants; the spread (min .. max) of each is what a difference between two of them has to exceed
     for fn in whole.values():
