@@ -78,7 +78,10 @@ const char* o2345_knobs(void);
 /* ---- cost volume -------------------------------------------------------------------------------------------------
  * replaces: ops/generate_grids.py:4 generate_grid, ops/back_project.py:5 back_project_sparse_type (both calls),
  * models/sparse_sdf_network.py:221 aggregate_multiview_features, the frustum filter at :330-334.
- * proj: [V,4,4] row-major affine matrices (sample['affine_mats']); voxel (x,y,z) -> world = xyz*voxel_size + origin. */
+ * proj: [V,4,4] row-major affine matrices (sample['affine_mats']); voxel (x,y,z) -> world = xyz*voxel_size + origin.
+ * H and W, the height and width of the source images, are independent (each > 1; the reference's sizeH, sizeW): a projected x is normalised by W - 1, a
+ * projected y by H - 1, maps are [V,H,W,C]; dx, dy, dz are independent too.  A voxel is seen by a view if |gx| <= 1, |gy| <= 1 and z > 0: the border of
+ * the image counts.  (tests/test_gpu_project_units.py runs these entries at 28 x 44, 45 x 24 and 2 x 3.) */
 size_t o2345_costvol_workspace_bytes(int dx, int dy, int dz);
 /* visible-view count per voxel, order-preserving compaction of the voxels seen by > min_views views:
  * cnt [dx*dy*dz] u8, row_of_voxel [dx*dy*dz] (row id or -1), coords [capacity,4] int32 (x,y,z,batch=0), *n_rows_dev. */
@@ -319,7 +322,14 @@ int o2345_camera_terms(const float* intrinsics, const float* w2cs, int V, float*
 
 /* ---- colour blending (replaces models/projector.py:96 Projector.compute / :231 compute_view_independent +
  * models/rendering_network.py:75 GeneralRenderingNetwork.forward) ---------------------------------------------------
- * cmaps [V,H,W,64] = rgb(3) | features(56) | pad; proj [V,3,4] = K @ w2c[:3]; cam_pos [V,3]. */
+ * cmaps [V,H,W,64] = rgb(3) | features(56) | pad; proj [V,3,4] = K @ w2c[:3]; cam_pos [V,3].
+ * H and W are independent (each > 1; the reference's img_wh = [W, H]).  A view sees a point if |gx| < 1 and |gy| < 1 -- the border of the image does
+ * NOT count here (models/projector.py:188-190), unlike in the cost volume -- and the point is geometrically valid; every entry below that reports a
+ * number of views (o2345_view_count*, out_nviews of the colour entries, the mask of o2345_project_features) reports the same number for the same
+ * point, also within rounding of a border: o2345_view_count* divides, the colour kernels multiply by a reciprocal and correct the quotient once, and
+ * tests/test_gpu_project_units.py holds the two to equal counts on points aimed at the borders.  The signature of o2345_list_sort_by_visibility above
+ * is the same strict test written without a division; it may differ from the mask within rounding of a border, which only affects how points are
+ * grouped. */
 int o2345_pack_color_maps(const float* feat_nchw, const float* color_nchw, int V, int H, int W, float* out_nhwc64,
                           void* stream);
 int o2345_view_count(const float* pts, long long n, const float* maskvol, int D, const float* proj, int V, int H, int W,

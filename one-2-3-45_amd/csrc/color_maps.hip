@@ -9,9 +9,9 @@ namespace o2345 {
 // cam2pixel (ops/back_project.py:89-129) with padding 'zeros': Z clamped to >= 1e-3, out-of-range coordinate -> 2
 __device__ __forceinline__ void project_point(const float* __restrict__ P /*[3][4]*/, float x, float y, float z, int H, int W,
                                               float& gx, float& gy) {
-    const float X = P[0] * x + P[1] * y + P[2] * z + P[3];
-    const float Y = P[4] * x + P[5] * y + P[6] * z + P[7];
-    const float Z = fmaxf(P[8] * x + P[9] * y + P[10] * z + P[11], 1e-3f);
+    const float X = project_row(P, x, y, z);
+    const float Y = project_row(P + 4, x, y, z);
+    const float Z = fmaxf(project_row(P + 8, x, y, z), 1e-3f);
     gx = 2.f * (X / Z) / (float)(W - 1) - 1.f;
     gy = 2.f * (Y / Z) / (float)(H - 1) - 1.f;
     if (gx > 1.f || gx < -1.f) gx = 2.f;

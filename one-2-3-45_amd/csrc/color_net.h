@@ -200,9 +200,9 @@ O2345_GROUP_REDUCE(gmax, fmaxf)
 #undef O2345_GROUP_REDUCE
 
 __device__ __forceinline__ void cm_project(const float* __restrict__ P, float x, float y, float z, int H, int W, float& gx, float& gy) {
-    const float X = P[0] * x + P[1] * y + P[2] * z + P[3];
-    const float Y = P[4] * x + P[5] * y + P[6] * z + P[7];
-    const float Z = fmaxf(P[8] * x + P[9] * y + P[10] * z + P[11], 1e-3f);
+    const float X = project_row(P, x, y, z);
+    const float Y = project_row(P + 4, x, y, z);
+    const float Z = fmaxf(project_row(P + 8, x, y, z), 1e-3f);
     // a / b as a * rcp(b) with one Newton step on the quotient (q += (a - b q) * r): within 1 ulp of the IEEE quotient (almost
     // always identical) in 3 instructions instead of the ~12 of the division sequence; the reciprocals are shared
     const float rz = crcp(Z), rw = crcp((float)(W - 1)), rh = crcp((float)(H - 1));

@@ -6,17 +6,25 @@
 
 namespace o2345 {
 
+// One row r = (r0, r1, r2 | t) of a projection applied to a point, the way the reference evaluates it in float32.  The reference forms the product with a
+// GEMM over k (proj_batch @ rs_grid, ops/back_project.py:52; proj_c2p_rot.bmm(cam_coords_flat) + proj_c2p_tr in cam2pixel, :105-110): BLAS kernels (MKL
+// on the host, cuBLAS / rocBLAS on a GPU) accumulate a tiny-K product as ONE FMA chain in k order, acc = fma(a_k, b_k, acc) -- which is also what
+// ATen's CPU matmul does (checked on 16.7 M voxels x 8 views: bit-identical to this chain, while the mul / add sequence differs in the last bit of ~15 %
+// of the values and flips the frustum test of 3 voxels in 256^3).  The translation is added last.  Every projection of the library goes through here:
+// project_voxel below, the colour kernels' cm_project (csrc/color_net.h), k_view_count's project_point (csrc/color_maps.hip) and the list sort's
+// signature (csrc/list_sort.hip).  The chain also rounds three times less than mul / add: where a row cancels (a point on the image's first row or
+// column), the mul / add form put one point of tests/test_gpu_project_units.py on the wrong side of a border from 11 * 2^-24 away.
+O2345_HD float project_row(const float* __restrict__ r, float x, float y, float z) {
+    return fmaf(r[2], z, fmaf(r[1], y, r[0] * x)) + r[3];
+}
+
 // ops/back_project.py:44-63.  P = rows of the 4x4 affine matrix (row-major, 16 floats).
 // z >= 0 is clamped to >= 1e-6, negative z untouched; valid = |gx|<=1 & |gy|<=1 & z>0.
 O2345_HD void project_voxel(const float* __restrict__ P, float wx, float wy, float wz, int H, int W,
                             float& gx, float& gy, bool& valid) {
-    // The reference forms these with a GEMM over k (proj_batch @ rs_grid, ops/back_project.py:52): BLAS kernels (MKL on the host, cuBLAS / rocBLAS on a GPU)
-    // accumulate a tiny-K product as ONE FMA chain in k order, acc = fma(a_k, b_k, acc) -- which is also what ATen's CPU matmul does (checked on
-    // 16.7 M voxels x 8 views: bit-identical to this chain, while the mul / add sequence differs in the last bit of ~15 % of the values and flips the
-    // frustum test of 3 voxels in 256^3).  The translation enters with b_3 = 1, so the last step is an exact add.
-    float x = fmaf(P[2], wz, fmaf(P[1], wy, P[0] * wx)) + P[3];
-    float y = fmaf(P[6], wz, fmaf(P[5], wy, P[4] * wx)) + P[7];
-    float z = fmaf(P[10], wz, fmaf(P[9], wy, P[8] * wx)) + P[11];
+    float x = project_row(P, wx, wy, wz);
+    float y = project_row(P + 4, wx, wy, wz);
+    float z = project_row(P + 8, wx, wy, wz);
     if (z >= 0.f) z = fmaxf(z, 1e-6f);
     gx = 2.f * (x / z) / (float)(W - 1) - 1.f;
     gy = 2.f * (y / z) / (float)(H - 1) - 1.f;

@@ -15,6 +15,7 @@
 //                    64 entries of a step are ranked by ballot among equal digits -- stable by construction, no atomics on global memory.
 // The number of entries is read from device memory (the render call never synchronises with the host); blocks past it do nothing.
 #include "common.h"
+#include "geom_math.h"
 
 namespace o2345 {
 
@@ -27,9 +28,9 @@ __device__ __forceinline__ unsigned vis_signature(const float* __restrict__ proj
     const float wm = (float)(W - 1), hm = (float)(H - 1);
     for (int v = 0; v < V; ++v) {
         const float* P = proj + 12 * v;
-        const float X = P[0] * x + P[1] * y + P[2] * z + P[3];
-        const float Y = P[4] * x + P[5] * y + P[6] * z + P[7];
-        const float Z = fmaxf(P[8] * x + P[9] * y + P[10] * z + P[11], 1e-3f);
+        const float X = project_row(P, x, y, z);
+        const float Y = project_row(P + 4, x, y, z);
+        const float Z = fmaxf(project_row(P + 8, x, y, z), 1e-3f);
         if (X > 0.f && X < wm * Z && Y > 0.f && Y < hm * Z) key |= 1u << v;
     }
     return key;

@@ -200,6 +200,59 @@ def main_featurenet(seed=21):
     print("wrote", path, os.path.getsize(path) // 1024, "KiB; fused", tuple(fused.shape), "max", float(fused.abs().max()))
 
 
+NONSQUARE = dict(H=28, W=44, V=5, D=14, n_random=257, n_offsets=160)
+
+
+def nonsquare_inputs():
+    """The (28, 44) scene of tests/project_ref.py and its points: the random family, then every n-th point of the offsets family with k >= 64."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import project_ref as PR
+    c = NONSQUARE
+    s = PR.scene(c["H"], c["W"], c["V"], c["D"])
+    off = PR.offset_points(s, k_min=64)
+    pts = torch.cat([PR.random_points(c["n_random"]), off[::max(1, len(off) // c["n_offsets"])][:c["n_offsets"]]])
+    return s, pts.contiguous()
+
+
+def main_nonsquare():
+    """tests/golden/ref_nonsquare.npz: the reference's own get_conditional_volume(sizeH=28, sizeW=44), Projector.compute and compute_view_independent
+    with img_wh=[44, 28], and GeneralRenderingNetwork on their tensors.  The networks are those of ref_small.npz (same seeds; asserted), so the file
+    stores no weights."""
+    torch.set_grad_enabled(False)
+    c = NONSQUARE
+    s, pts = nonsquare_inputs()
+    sc, H, W, D = s["sc"], c["H"], c["W"], c["D"]
+    sdfnet, rnet, var, renderer = networks(dict(CFG, D=D))
+    here = os.path.dirname(os.path.abspath(__file__))
+    g0 = np.load(os.path.join(here, "ref_small.npz"))
+    for prefix, net in (("sdf.", sdfnet), ("ren.", rnet)):
+        for k, v in net.state_dict().items():
+            if "num_batches_tracked" not in k and "running_" not in k:
+                assert np.array_equal(g0["w:" + prefix + k], v.numpy()), f"{prefix}{k} differs from ref_small.npz"
+    T = torch.from_numpy
+    cv = sdfnet.get_conditional_volume(feature_maps=s["fmaps"][None], partial_vol_origin=s["origin"][None], proj_mats=s["aff"][None],
+                                       sizeH=H, sizeW=W, lod=0)
+    dense, mask = cv["dense_volume_scale0"], cv["valid_mask_volume_scale0"]
+    out = {"dense": dense[0].numpy(), "mask": mask[0, 0].numpy(), "coords": torch.nonzero(mask[0, 0]).int().numpy(), "pts": pts.numpy()}
+    kw = dict(geometryVolume=dense[0], geometryVolumeMask=mask[0], rendering_feature_maps=s["fmaps"], color_maps=s["images"], w2cs=T(sc["w2cs"]),
+              intrinsics=T(sc["intrinsics"]), img_wh=[W, H], query_img_idx=0, query_c2w=T(sc["query_c2w"])[None])
+    geo, rf, rdiff, vm, _, _ = renderer.rendering_projector.compute(pts.clone(), **kw)
+    rgb, _ = rnet(geo, rf, rdiff, vm)
+    out.update(geo=geo[0].numpy(), rgb_feat=rf[:, 0].numpy(), ray_diff=rdiff[:, 0].numpy(), mask_views=vm[:, 0].numpy(), rgb=rgb[0].numpy())
+    with torch.enable_grad():
+        grad = sdfnet.gradient(pts.clone(), dense, 0).squeeze(1).detach()
+        geo2, rf2, rdiff2, vm2, _, _ = renderer.rendering_projector.compute_view_independent(
+            pts.clone(), lod=0, sdf_network=sdfnet, target_candidate_w2cs=None, **kw)
+    rgb2, _ = rnet(geo2.detach(), rf2.detach(), rdiff2.detach(), vm2)
+    assert torch.equal(geo2, geo) and torch.equal(rf2, rf) and torch.equal(vm2, vm)
+    out.update(vi_grad=grad.numpy(), vi_ray_diff=rdiff2[:, 0].detach().numpy(), vi_rgb=rgb2[0].detach().numpy())
+    out.update({"cfg_" + k: np.int64(v) for k, v in c.items()}, chk_fmaps=np.float64(s["fmaps"].double().sum()), chk_pts=np.float64(pts.double().sum()),
+               chk_aff=np.float64(s["aff"].double().sum()))
+    path = os.path.join(here, "ref_nonsquare.npz")
+    np.savez_compressed(path, **out)
+    print("wrote", path, os.path.getsize(path) // 1024, "KiB; kept voxels", int(mask.sum()), "points", len(pts), "valid pairs", int(vm.sum()))
+
+
 def main():
     torch.set_grad_enabled(False)
     cfg = CFG
@@ -292,5 +345,7 @@ if __name__ == "__main__":
         main_featurenet()
     elif "--trained" in sys.argv:
         main_trained()
+    elif "--nonsquare" in sys.argv:
+        main_nonsquare()
     else:
         main()
