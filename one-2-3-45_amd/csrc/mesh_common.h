@@ -1,9 +1,15 @@
-// What the mesh units share (mcubes.hip, mesh_components.hip, mesh_smooth.hip, mesh_decimate.hip, mesh_simplify.hip, mesh_project.hip, mesh_texture.hip,
-// mesh_export.hip, mesh_pack.hip): the triangle reader, the wave-level counter, the row sorts, and on the host the workspace carver, the index-width dispatch, the
-// three-launch exclusive scan and the read-back of a call's device totals.  Everything is inline or a template: each unit keeps its own code object.
+// What the mesh units share.  The units: mcubes.hip, mesh_components.hip, mesh_smooth.hip and mesh_simplify.hip (both through mesh_adjacency.h),
+// mesh_decimate.hip, mesh_project.hip, mesh_texture.hip, mesh_distance.hip, mesh_export.hip, mesh_pack.hip, and surface_trace.hip for the wave sums and
+// finite().  On the device: the triangle reader, the wave-level counter and reductions, finite(), the order-preserving fp64 <-> uint64 encoding, the row
+// sorts (registers, the short-row ladder, the block-wide long form) and the kernel that emits kept triangles.  On the host: the workspace carver, the
+// entry checks (sizes, index width, workspace), the index-width dispatch, the three-launch exclusive scan and the read-back of a call's device totals.
+// The index -> world frame of projection and texture is in mesh_math.h.  Everything is inline, a template or in an anonymous namespace: each unit keeps
+// its own code object.
 #pragma once
 #include "common.h"
 #include "block_kernels.h"
+#include <float.h>
+#include <math.h>
 #include <type_traits>
 
 namespace o2345 {
@@ -26,6 +32,34 @@ __device__ __forceinline__ bool mesh_triangle(const IDX* __restrict__ tris, long
 __device__ __forceinline__ void wave_count(bool pred, unsigned long long* counter) {
     const unsigned long long m = __ballot(pred);
     if (lane_id() == 0 && m) atomicAdd(counter, (unsigned long long)__popcll(m));
+}
+
+// min / max / sum over the 64 lanes of a wave by butterflies (off = 32 .. 1); every lane returns the result, and every lane must call
+__device__ __forceinline__ unsigned long long wave_min(unsigned long long x) {
+    for (int off = 32; off; off >>= 1) { const unsigned long long y = __shfl_xor(x, off); x = y < x ? y : x; }
+    return x;
+}
+__device__ __forceinline__ unsigned long long wave_max(unsigned long long x) {
+    for (int off = 32; off; off >>= 1) { const unsigned long long y = __shfl_xor(x, off); x = y > x ? y : x; }
+    return x;
+}
+template <typename T>
+__device__ __forceinline__ T wave_sum(T x) {
+    static_assert(std::is_same<T, int>::value || std::is_same<T, unsigned long long>::value, "integer sums only: a float sum has an order to document");
+    for (int off = 32; off; off >>= 1) x += __shfl_xor(x, off);
+    return x;
+}
+
+// neither an infinity nor a NaN.  (At global scope, behind `using namespace o2345`, write o2345::finite: the C library has a function of that name.)
+O2345_HD bool finite(double x) { return fabs(x) <= DBL_MAX; }
+
+// fp64 -> uint64 whose unsigned order is the order of the doubles (for integer atomicMin / atomicMax of a bound), and back
+__device__ __forceinline__ unsigned long long ordered_bits(double x) {
+    const unsigned long long b = (unsigned long long)__double_as_longlong(x);
+    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+}
+__device__ __forceinline__ double ordered_double(unsigned long long e) {
+    return __longlong_as_double((long long)((e >> 63) ? (e & 0x7FFFFFFFFFFFFFFFull) : ~e));
 }
 
 // the finaliser of splitmix64: keys that differ in high bits only spread too (decimation's tables, simplification's priorities)
@@ -59,6 +93,48 @@ __device__ __forceinline__ void row_rank_sort(const int* row, int* srt, int d) {
     __syncthreads();
 }
 
+// Sorting an unordered CSR row in place.  A kernel with one thread per row lists the rows above ROW_SHORT entries for a second kernel with one block per
+// listed row (row_sort_long) and sorts the others itself (row_sort_short); a row of one entry or none is sorted as it is.
+
+// row[0 .. d) ascending, d <= N, by its own thread in registers
+template <int N>
+__device__ __forceinline__ void row_sort_regs_in_place(int* __restrict__ row, int d) {
+    int r[N];
+    row_sorted_regs<N>(row, d, r);
+#pragma unroll
+    for (int k = 0; k < N; ++k)
+        if (k < d) row[k] = r[k];
+}
+
+// row[0 .. d) ascending for 1 < d <= ROW_SHORT: the smallest of three register networks that holds the row
+__device__ __forceinline__ void row_sort_short(int* __restrict__ row, int d) {
+    if (d > 16) row_sort_regs_in_place<ROW_SHORT>(row, d);
+    else if (d > 4) row_sort_regs_in_place<16>(row, d);
+    else row_sort_regs_in_place<4>(row, d);
+}
+
+// row[0 .. d) ascending by one 256-thread block: rank sort into tmp, copied back.  On return tmp[0 .. d) is the sorted row, complete for the whole
+// block; row[0 .. d) holds the same values once the block's stores have landed (its next barrier, or the kernel's end): a thread that reads other
+// threads' entries before that reads tmp.
+__device__ __forceinline__ void row_sort_long(int* row, int* tmp, int d) {
+    row_rank_sort(row, tmp, d);
+    for (int i = threadIdx.x; i < d; i += 256) row[i] = tmp[i];
+}
+
+// Kept triangles out: element j = 3 t + k of src goes to out[3 tmap[t] + k], renumbered through map, iff tkeep[t].  src is the input's triangle array
+// or a unit's working copy; kept triangles have three in-range corners with a map entry >= 0.  One thread per element, coalesced on both sides.
+namespace {
+template <typename SRC, typename IDX>
+__global__ __launch_bounds__(256) void k_mesh_emit_tris(const SRC* __restrict__ src, long long nt3, const int* __restrict__ map, const int* __restrict__ tkeep,
+                                                        const int* __restrict__ tmap, IDX* __restrict__ out) {
+    const long long j = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (j >= nt3) return;
+    const long long t = j / 3;
+    if (!tkeep[t]) return;
+    out[3 * (long long)tmap[t] + (j - 3 * t)] = (IDX)map[src[j]];
+}
+}  // namespace
+
 // Bump carver of a workspace.  A unit describes its layout in ONE function that walks a carver; run on a null base the walk is the size
 // (o2345_*_workspace_bytes), run on the caller's buffer it yields the pointers: the two cannot drift apart.
 struct Carver {
@@ -72,6 +148,20 @@ struct Carver {
     void skip(size_t n) { off += n; }
     size_t bytes() const { return off; }
 };
+
+// Entry checks.  The sizes at which vertex indices fit an int and 3 * nt a 31-bit element count (decimation, distance; the adjacency and the components
+// have limits of their own).  The two macros return -1 from the entry with the messages that callers match on; `unit` is a string literal.
+inline bool mesh_sizes_ok(long long nv, long long nt) { return nv >= 0 && nt >= 0 && nv < (1ll << 30) && 3 * nt < (1ll << 31); }
+
+#define O2345_REQUIRE_INDEX_BYTES(unit, index_bytes) O2345_REQUIRE((index_bytes) == 4 || (index_bytes) == 8, unit ": index_bytes must be 4 or 8")
+
+// need: the unit's o2345_*_workspace_bytes of the call's sizes, which the entry has checked before
+#define O2345_REQUIRE_WORKSPACE(unit, workspace, workspace_bytes, need)                                             \
+    do {                                                                                                            \
+        O2345_REQUIRE(workspace, unit ": null pointer");                                                            \
+        O2345_REQUIRE((workspace_bytes) >= (need), unit ": workspace too small");                                   \
+        O2345_REQUIRE(((uintptr_t)(workspace) & 15) == 0, unit ": workspace must be 16-byte aligned");              \
+    } while (0)
 
 // f(typed tris) once, with the triangle array typed by its index width: const int* / const long long*, or without the const for an output array.
 // The caller has checked index_bytes (4 or 8).  Inside f, index_type<decltype(typed)> names the element type for the kernel's template argument.

@@ -176,6 +176,7 @@ __global__ __launch_bounds__(256) void k_cc_emit_verts(const double* __restrict_
     if (kept_out && d == 0) kept_out[w] = (int)v;
 }
 
+// not k_mesh_emit_tris: the keep flag here is tmap[t] >= 0
 template <typename IDX>
 __global__ __launch_bounds__(256) void k_cc_emit_tris(const IDX* __restrict__ tris, long long nt3, const int* __restrict__ vmap, const int* __restrict__ tmap,
                                                       IDX* __restrict__ tris_out) {
@@ -210,6 +211,9 @@ static size_t cc_carve(void* ws, long long nv, long long nt, CcCarve& c) {
 
 static_assert(sizeof(CcTotals) <= 64, "CcTotals must fit the workspace head");
 
+// the emit kernels index 3 * nv coordinates, and min_faces is compared with an int count
+static bool cc_sizes_ok(long long nv, long long nt) { return nv >= 0 && nt >= 0 && 3 * nv < (1ll << 31) && nt < (1ll << 31); }
+
 }  // namespace o2345
 
 using namespace o2345;
@@ -227,12 +231,11 @@ size_t o2345_mesh_components_workspace_bytes(long long nv, long long nt) {
 int o2345_mesh_components_count(const void* tris, int index_bytes, long long nv, long long nt, long long min_faces, int keep_largest, void* workspace,
                                 size_t workspace_bytes, int* labels, long long* n_components_host, long long* n_components_kept_host,
                                 long long* nv_kept_host, long long* nt_kept_host, void* stream) {
-    O2345_REQUIRE(index_bytes == 4 || index_bytes == 8, "mesh_components_count: index_bytes must be 4 or 8");
-    O2345_REQUIRE(nv >= 0 && nt >= 0 && 3 * nv < (1ll << 31) && nt < (1ll << 31), "mesh_components_count: bad sizes (nv * 3 and nt must stay below 2^31)");
+    O2345_REQUIRE_INDEX_BYTES("mesh_components_count", index_bytes);
+    O2345_REQUIRE(cc_sizes_ok(nv, nt), "mesh_components_count: bad sizes (nv * 3 and nt must stay below 2^31)");
     O2345_REQUIRE(n_components_host && n_components_kept_host && nv_kept_host && nt_kept_host, "mesh_components_count: null pointer");
-    O2345_REQUIRE(workspace && (nt == 0 || tris), "mesh_components_count: null pointer");
-    O2345_REQUIRE(workspace_bytes >= o2345_mesh_components_workspace_bytes(nv, nt), "mesh_components_count: workspace too small");
-    O2345_REQUIRE(((uintptr_t)workspace & 15) == 0, "mesh_components_count: workspace must be 16-byte aligned");
+    O2345_REQUIRE(nt == 0 || tris, "mesh_components_count: null pointer");
+    O2345_REQUIRE_WORKSPACE("mesh_components_count", workspace, workspace_bytes, o2345_mesh_components_workspace_bytes(nv, nt));
     CcCarve c;
     (void)cc_carve(workspace, nv, nt, c);
     CcSelect sel;
@@ -274,8 +277,8 @@ int o2345_mesh_components_count(const void* tris, int index_bytes, long long nv,
 // kept_out int32 [nv_kept].  Any output may be NULL.  Same workspace, untouched since pass 1.
 int o2345_mesh_components_emit(const double* verts, const void* tris, int index_bytes, long long nv, long long nt, void* workspace, double* verts_out,
                                void* tris_out, int* kept_out, void* stream) {
-    O2345_REQUIRE(index_bytes == 4 || index_bytes == 8, "mesh_components_emit: index_bytes must be 4 or 8");
-    O2345_REQUIRE(nv >= 0 && nt >= 0 && 3 * nv < (1ll << 31) && nt < (1ll << 31), "mesh_components_emit: bad sizes");
+    O2345_REQUIRE_INDEX_BYTES("mesh_components_emit", index_bytes);
+    O2345_REQUIRE(cc_sizes_ok(nv, nt), "mesh_components_emit: bad sizes");
     O2345_REQUIRE(workspace && (!verts_out || verts || nv == 0) && (!tris_out || tris || nt == 0), "mesh_components_emit: null pointer");
     CcCarve c;
     (void)cc_carve(workspace, nv, nt, c);

@@ -32,38 +32,18 @@ constexpr double DEC_EXTENT = 2097152.0;              // 2^21 cells per axis
 
 // device scalars of one call (workspace head)
 struct DecTotals {
-    unsigned long long qmin[3], qmax[3];              // dec_encode of the per-axis bounds of q
+    unsigned long long qmin[3], qmax[3];              // ordered_bits of the per-axis bounds of q
     long long nv_out, nt_out, n_members;              // written by k_scan_small (n_members: the length of the member table, unused otherwise)
     unsigned long long n_nonfinite, n_bad, n_overflow;          // vertices with a non-finite coordinate; triangles with an index outside [0, nv); probes that ran out
     unsigned long long n_clusters, n_degenerate, n_duplicate;
     int bad_extent, n_long;
 };
 
-// fp64 -> uint64 whose unsigned order is the order of the doubles
-__device__ __forceinline__ unsigned long long dec_encode(double x) {
-    const unsigned long long b = (unsigned long long)__double_as_longlong(x);
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-
-__device__ __forceinline__ double dec_decode(unsigned long long e) {
-    return __longlong_as_double((long long)((e >> 63) ? (e & 0x7FFFFFFFFFFFFFFFull) : ~e));
-}
-
 // q of one coordinate; + 0.0 turns floor's -0.0 into +0.0, so that equal q have equal encodings
 __device__ __forceinline__ double dec_cell(double p, double cell) { return __dadd_rn(floor(__ddiv_rn(p, cell)), 0.0); }
 
 __device__ __forceinline__ void dec_sort3(int& x, int& y, int& z) {
     regs_cmpswap(x, y); regs_cmpswap(y, z); regs_cmpswap(x, y);
-}
-
-__device__ __forceinline__ unsigned long long wave_min(unsigned long long x) {
-    for (int off = 32; off; off >>= 1) { const unsigned long long y = __shfl_xor(x, off); x = y < x ? y : x; }
-    return x;
-}
-
-__device__ __forceinline__ unsigned long long wave_max(unsigned long long x) {
-    for (int off = 32; off; off >>= 1) { const unsigned long long y = __shfl_xor(x, off); x = y > x ? y : x; }
-    return x;
 }
 
 // one thread per slot / vertex / triangle of whichever array is longest
@@ -90,8 +70,8 @@ __global__ __launch_bounds__(256) void k_dec_bounds(const double* __restrict__ v
 #pragma unroll
         for (int d = 0; d < 3; ++d) {
             const double p = verts[3 * v + d];
-            nonfinite |= !(fabs(p) <= 1.7976931348623157e308);
-            lo[d] = hi[d] = dec_encode(dec_cell(p, cell));
+            nonfinite |= !finite(p);
+            lo[d] = hi[d] = ordered_bits(dec_cell(p, cell));
         }
     }
     const unsigned long long mn = __ballot(nonfinite);
@@ -114,8 +94,8 @@ __global__ __launch_bounds__(256) void k_dec_insert(const double* __restrict__ v
     bool wide = false;
 #pragma unroll
     for (int d = 0; d < 3; ++d) {
-        const double q0 = dec_decode(tot->qmin[d]);
-        wide |= !(__dsub_rn(dec_decode(tot->qmax[d]), q0) < DEC_EXTENT);
+        const double q0 = ordered_double(tot->qmin[d]);
+        wide |= !(__dsub_rn(ordered_double(tot->qmax[d]), q0) < DEC_EXTENT);
         double r = __dsub_rn(dec_cell(verts[3 * v + d], cell), q0);
         r = (r >= 0.0 && r < DEC_EXTENT) ? r : 0.0;
         key = (key << 21) | (unsigned long long)(long long)r;
@@ -227,15 +207,6 @@ __global__ __launch_bounds__(256) void k_dec_fill(int nv, const int* __restrict_
     if (c >= 0) members[atomicAdd(cursor + c, 1)] = (int)v;
 }
 
-template <int N>
-__device__ __forceinline__ void dec_short_row(int* __restrict__ row, int d) {
-    int r[N];
-    row_sorted_regs<N>(row, d, r);
-#pragma unroll
-    for (int k = 0; k < N; ++k)
-        if (k < d) row[k] = r[k];
-}
-
 // one thread per row (rows behind the last kept cluster are empty): short rows are sorted here, long ones are listed
 __global__ __launch_bounds__(256) void k_dec_rows(int nv, const int* __restrict__ off, const int* __restrict__ cnt, int* __restrict__ members,
                                                   int* __restrict__ long_list, DecTotals* __restrict__ tot) {
@@ -243,22 +214,17 @@ __global__ __launch_bounds__(256) void k_dec_rows(int nv, const int* __restrict_
     if (c >= nv) return;
     const int d = cnt[c];
     if (d > ROW_SHORT) long_list[atomicAdd(&tot->n_long, 1)] = (int)c;
-    else if (d > 16) dec_short_row<ROW_SHORT>(members + off[c], d);
-    else if (d > 4) dec_short_row<16>(members + off[c], d);
-    else if (d > 1) dec_short_row<4>(members + off[c], d);
+    else if (d > 1) row_sort_short(members + off[c], d);
 }
 
-// one block per listed row: rank sort through tmp (row_rank_sort): the slow path of a mesh with thousands of vertices in one cell
+// one block per listed row (row_sort_long): the slow path of a mesh with thousands of vertices in one cell
 __global__ __launch_bounds__(256) void k_dec_long_rows(const int* __restrict__ off, const int* __restrict__ cnt, int* __restrict__ members, int* __restrict__ tmp,
                                                        const int* __restrict__ long_list, const DecTotals* __restrict__ tot) {
     const int n_long = tot->n_long;
     for (int r = blockIdx.x; r < n_long; r += gridDim.x) {
         const int c = long_list[r];
         const int base = off[c], d = cnt[c];
-        int* row = members + base;
-        int* srt = tmp + base;
-        row_rank_sort(row, srt, d);                                 // srt complete (this block wrote all of it)
-        for (int i = threadIdx.x; i < d; i += 256) row[i] = srt[i];
+        row_sort_long(members + base, tmp + base, d);
     }
 }
 
@@ -283,16 +249,6 @@ __global__ __launch_bounds__(256) void k_dec_emit_verts(const double* __restrict
     verts_out[3 * i] = __ddiv_rn(ax, n); verts_out[3 * i + 1] = __ddiv_rn(ay, n); verts_out[3 * i + 2] = __ddiv_rn(az, n);
 }
 
-template <typename IDX>
-__global__ __launch_bounds__(256) void k_dec_emit_tris(const IDX* __restrict__ tris, long long nt3, const int* __restrict__ cluster_of, const int* __restrict__ tkeep,
-                                                       const int* __restrict__ tmap, IDX* __restrict__ tris_out) {
-    const long long j = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (j >= nt3) return;
-    const long long t = j / 3;
-    if (!tkeep[t]) return;                                          // kept triangles have three in-range vertices of kept clusters
-    tris_out[3 * (long long)tmap[t] + (j - 3 * t)] = (IDX)cluster_of[tris[j]];
-}
-
 struct DecCarve {
     DecTotals* tot;
     unsigned long long* keys;
@@ -309,8 +265,6 @@ static long long dec_capacity(long long n) {                        // the power
 }
 
 static_assert(sizeof(DecTotals) <= 128, "DecTotals must fit the workspace head");
-
-static bool dec_sizes_ok(long long nv, long long nt) { return nv >= 0 && nt >= 0 && nv < (1ll << 30) && 3 * nt < (1ll << 31); }
 
 // the one walk through the workspace: carves it, or sizes it when ws is null; returns its size
 static size_t dec_carve(void* ws, long long nv, long long nt, DecCarve& c) {
@@ -336,7 +290,7 @@ using namespace o2345;
 extern "C" {
 
 size_t o2345_mesh_decimate_workspace_bytes(long long nv, long long nt) {
-    if (!dec_sizes_ok(nv, nt)) return 0;
+    if (!mesh_sizes_ok(nv, nt)) return 0;
     DecCarve c;
     return dec_carve(nullptr, nv, nt, c);
 }
@@ -346,13 +300,12 @@ size_t o2345_mesh_decimate_workspace_bytes(long long nv, long long nt) {
 int o2345_mesh_decimate_count(const double* verts, const void* tris, int index_bytes, long long nv, long long nt, double cell, void* workspace,
                               size_t workspace_bytes, long long* n_clusters_host, long long* nv_out_host, long long* nt_out_host,
                               long long* n_degenerate_host, long long* n_duplicate_host, void* stream) {
-    O2345_REQUIRE(index_bytes == 4 || index_bytes == 8, "mesh_decimate_count: index_bytes must be 4 or 8");
-    O2345_REQUIRE(cell > 0.0 && cell <= 1.7976931348623157e308, "mesh_decimate_count: cell must be finite and > 0, got %g", cell);
-    O2345_REQUIRE(dec_sizes_ok(nv, nt), "mesh_decimate_count: bad sizes (nv must stay below 2^30 and 3 * nt below 2^31)");
+    O2345_REQUIRE_INDEX_BYTES("mesh_decimate_count", index_bytes);
+    O2345_REQUIRE(cell > 0.0 && o2345::finite(cell), "mesh_decimate_count: cell must be finite and > 0, got %g", cell);
+    O2345_REQUIRE(mesh_sizes_ok(nv, nt), "mesh_decimate_count: bad sizes (nv must stay below 2^30 and 3 * nt below 2^31)");
     O2345_REQUIRE(n_clusters_host && nv_out_host && nt_out_host && n_degenerate_host && n_duplicate_host, "mesh_decimate_count: null pointer");
-    O2345_REQUIRE(workspace && (nv == 0 || verts) && (nt == 0 || tris), "mesh_decimate_count: null pointer");
-    O2345_REQUIRE(workspace_bytes >= o2345_mesh_decimate_workspace_bytes(nv, nt), "mesh_decimate_count: workspace too small");
-    O2345_REQUIRE(((uintptr_t)workspace & 15) == 0, "mesh_decimate_count: workspace must be 16-byte aligned");
+    O2345_REQUIRE((nv == 0 || verts) && (nt == 0 || tris), "mesh_decimate_count: null pointer");
+    O2345_REQUIRE_WORKSPACE("mesh_decimate_count", workspace, workspace_bytes, o2345_mesh_decimate_workspace_bytes(nv, nt));
     DecCarve c;
     (void)dec_carve(workspace, nv, nt, c);
     hipStream_t s = (hipStream_t)stream;
@@ -402,8 +355,8 @@ int o2345_mesh_decimate_count(const double* verts, const void* tris, int index_b
 // untouched in between).  Any output may be NULL.
 int o2345_mesh_decimate_emit(const double* verts, const void* tris, int index_bytes, long long nv, long long nt, void* workspace, double* verts_out,
                              void* tris_out, int* cluster, void* stream) {
-    O2345_REQUIRE(index_bytes == 4 || index_bytes == 8, "mesh_decimate_emit: index_bytes must be 4 or 8");
-    O2345_REQUIRE(dec_sizes_ok(nv, nt), "mesh_decimate_emit: bad sizes");
+    O2345_REQUIRE_INDEX_BYTES("mesh_decimate_emit", index_bytes);
+    O2345_REQUIRE(mesh_sizes_ok(nv, nt), "mesh_decimate_emit: bad sizes");
     O2345_REQUIRE(workspace && (!verts_out || verts || nv == 0) && (!tris_out || tris || nt == 0), "mesh_decimate_emit: null pointer");
     DecCarve c;
     (void)dec_carve(workspace, nv, nt, c);
@@ -412,7 +365,7 @@ int o2345_mesh_decimate_emit(const double* verts, const void* tris, int index_by
         hipLaunchKernelGGL(k_dec_emit_verts, dim3(cdiv(nv, 256)), dim3(256), 0, s, verts, (int)nv, c.cluster_of, c.off, c.cnt, c.members, c.tot, verts_out, cluster);
     if (nt > 0 && tris_out) with_index_type(index_bytes, tris, [&](auto* t) {
         using IDX = index_type<decltype(t)>;
-        hipLaunchKernelGGL(k_dec_emit_tris<IDX>, dim3(cdiv(3 * nt, 256)), dim3(256), 0, s, t, 3 * nt, c.cluster_of, c.tkeep, c.tmap, (IDX*)tris_out);
+        hipLaunchKernelGGL((k_mesh_emit_tris<IDX, IDX>), dim3(cdiv(3 * nt, 256)), dim3(256), 0, s, t, 3 * nt, c.cluster_of, c.tkeep, c.tmap, (IDX*)tris_out);
     });
     return check_launch("mesh_decimate_emit");
 }

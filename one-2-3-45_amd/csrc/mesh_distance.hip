@@ -28,7 +28,6 @@
 // Bad input never faults: an index outside [0, nv) is counted and never dereferenced, a non-finite coordinate is counted; count() returns them as errors.
 #include "mesh_common.h"
 #include "mesh_distance_math.h"
-#include <float.h>
 
 namespace o2345 {
 
@@ -52,40 +51,22 @@ struct MdSampleTotals {
 
 // device scalars of a grid call (workspace head)
 struct MdGridTotals {
-    unsigned long long lo[3], hi[3];                  // md_encode of the bounds of the usable triangles' corners
+    unsigned long long lo[3], hi[3];                  // ordered_bits of the bounds of the usable triangles' corners
     unsigned long long n_bad, n_nonfinite, n_degenerate, n_usable;
     long long n_entries;                              // written by k_scan_small
     int n_long;
 };
 static_assert(sizeof(MdSampleTotals) <= 128 && sizeof(MdGridTotals) <= 128 && sizeof(MdGridHead) <= 128, "the heads are 128 bytes");
 
-// fp64 -> uint64 whose unsigned order is the order of the doubles, and back
-__device__ __forceinline__ unsigned long long md_encode(double x) {
-    const unsigned long long b = (unsigned long long)__double_as_longlong(x);
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-__device__ __forceinline__ double md_decode(unsigned long long e) {
-    return __longlong_as_double((long long)((e >> 63) ? (e & 0x7FFFFFFFFFFFFFFFull) : ~e));
-}
-
-__device__ __forceinline__ unsigned long long md_wave_min(unsigned long long x) {
-    for (int off = 32; off; off >>= 1) { const unsigned long long y = __shfl_xor(x, off); x = y < x ? y : x; }
-    return x;
-}
-__device__ __forceinline__ unsigned long long md_wave_max(unsigned long long x) {
-    for (int off = 32; off; off >>= 1) { const unsigned long long y = __shfl_xor(x, off); x = y > x ? y : x; }
-    return x;
-}
-
 // the corners of a triangle whose indices are in range -> true iff all nine coordinates are finite
 __device__ __forceinline__ bool md_corners(const double* __restrict__ verts, int a, int b, int c, double (&A)[3], double (&B)[3], double (&C)[3]) {
-    bool finite = true;
+    bool all_finite = true;
 #pragma unroll
     for (int d = 0; d < 3; ++d) {
         A[d] = verts[3 * (long long)a + d]; B[d] = verts[3 * (long long)b + d]; C[d] = verts[3 * (long long)c + d];
-        finite &= fabs(A[d]) <= DBL_MAX && fabs(B[d]) <= DBL_MAX && fabs(C[d]) <= DBL_MAX;
+        all_finite &= finite(A[d]) && finite(B[d]) && finite(C[d]);
     }
-    return finite;
+    return all_finite;
 }
 
 // ---- samples -------------------------------------------------------------------------------------------------------------------------------------
@@ -109,7 +90,7 @@ __global__ __launch_bounds__(256) void k_md_levels(const double* __restrict__ ve
     }
     wave_count(bad, &tot->n_bad);
     wave_count(nonfinite, &tot->n_nonfinite);
-    for (int off = 32; off; off >>= 1) mine += __shfl_xor(mine, off);
+    mine = wave_sum(mine);
     if (lane_id() == 0 && mine) atomicAdd(&tot->n_samples, mine);
 }
 
@@ -172,8 +153,8 @@ __global__ __launch_bounds__(256) void k_md_grid_bounds(const double* __restrict
                 ok = true;
 #pragma unroll
                 for (int d = 0; d < 3; ++d) {
-                    lo[d] = md_encode(fmin(A[d], fmin(B[d], C[d])));
-                    hi[d] = md_encode(fmax(A[d], fmax(B[d], C[d])));
+                    lo[d] = ordered_bits(fmin(A[d], fmin(B[d], C[d])));
+                    hi[d] = ordered_bits(fmax(A[d], fmax(B[d], C[d])));
                 }
             }
         }
@@ -186,7 +167,7 @@ __global__ __launch_bounds__(256) void k_md_grid_bounds(const double* __restrict
     if (!usable) return;                                             // the reduce entry wants the counters only
     const unsigned long long any = __ballot(ok);
 #pragma unroll
-    for (int d = 0; d < 3; ++d) { lo[d] = md_wave_min(lo[d]); hi[d] = md_wave_max(hi[d]); }
+    for (int d = 0; d < 3; ++d) { lo[d] = wave_min(lo[d]); hi[d] = wave_max(hi[d]); }
     if (lane_id() == 0 && any) {
 #pragma unroll
         for (int d = 0; d < 3; ++d) { atomicMin(&tot->lo[d], lo[d]); atomicMax(&tot->hi[d], hi[d]); }
@@ -201,7 +182,7 @@ __global__ void k_md_grid_head(const MdGridTotals* __restrict__ tot, double cell
     h.dims[0] = h.dims[1] = h.dims[2] = 1;
     if (tot->n_usable) {
         double lo[3], hi[3], widest = 0.0;
-        for (int d = 0; d < 3; ++d) { lo[d] = md_decode(tot->lo[d]); hi[d] = md_decode(tot->hi[d]); widest = fmax(widest, hi[d] - lo[d]); }
+        for (int d = 0; d < 3; ++d) { lo[d] = ordered_double(tot->lo[d]); hi[d] = ordered_double(tot->hi[d]); widest = fmax(widest, hi[d] - lo[d]); }
         double c = cell > 0.0 ? cell : (widest > 0.0 ? widest / (double)MD_AXIS : 1.0);
         const double want = cell > 0.0 ? (double)max_cells : fmin((double)max_cells, (double)tot->n_usable);
         for (int it = 0; it < 400; ++it) {
@@ -252,15 +233,6 @@ __global__ __launch_bounds__(256) void k_md_grid_register(const double* __restri
             }
 }
 
-template <int N>
-__device__ __forceinline__ void md_short_row(int* __restrict__ row, int d) {
-    int r[N];
-    row_sorted_regs<N>(row, d, r);
-#pragma unroll
-    for (int k = 0; k < N; ++k)
-        if (k < d) row[k] = r[k];
-}
-
 // one thread per cell: short rows are sorted here, long ones are listed
 __global__ __launch_bounds__(256) void k_md_grid_rows(const MdGridHead* __restrict__ head, const int* __restrict__ cell_start, int* __restrict__ entries,
                                                       int* __restrict__ long_list, MdGridTotals* __restrict__ tot) {
@@ -268,12 +240,11 @@ __global__ __launch_bounds__(256) void k_md_grid_rows(const MdGridHead* __restri
     if (c >= head->n_cells) return;
     const int lo = cell_start[c], d = cell_start[c + 1] - lo;
     if (d > ROW_SHORT) long_list[atomicAdd(&tot->n_long, 1)] = (int)c;
-    else if (d > 16) md_short_row<ROW_SHORT>(entries + lo, d);
-    else if (d > 4) md_short_row<16>(entries + lo, d);
-    else if (d > 1) md_short_row<4>(entries + lo, d);
+    else if (d > 1) row_sort_short(entries + lo, d);
 }
 
-// one block per listed row: odd-even transposition in place, d passes (a cell with thousands of triangles: a grid far too coarse for its mesh)
+// one block per listed row: odd-even transposition in place, d passes (a cell with thousands of triangles: a grid far too coarse for its mesh).  Not
+// row_sort_long: that needs a second buffer of the entries' size, and the grid's workspace and object have none (their sizes are part of the interface)
 __global__ __launch_bounds__(256) void k_md_grid_long_rows(const int* __restrict__ cell_start, int* entries, const int* __restrict__ long_list,
                                                            const MdGridTotals* __restrict__ tot) {
     const int n_long = tot->n_long;
@@ -386,7 +357,8 @@ __global__ __launch_bounds__(256) void k_md_query_all(const double* __restrict__
 }
 
 // ---- summary -------------------------------------------------------------------------------------------------------------------------------------
-// fixed-order sums of MD_RED_COLS values over a 256-thread block: wave butterflies, then (w0 + w1) + (w2 + w3); valid in thread 0
+// fixed-order sums of MD_RED_COLS values over a 256-thread block: wave butterflies, then (w0 + w1) + (w2 + w3); valid in thread 0.  The butterfly is
+// written out: these are doubles, and its order is part of the result (wave_sum is for integers)
 __device__ __forceinline__ void md_block_sums(double (&v)[MD_RED_COLS]) {
     __shared__ double sm[MD_RED_COLS][4];
 #pragma unroll
@@ -426,9 +398,8 @@ __global__ __launch_bounds__(256) void k_md_reduce(const double* __restrict__ d2
         const unsigned long long bits = (unsigned long long)__double_as_longlong(x);
         mx = bits > mx ? bits : mx;
     }
-    mx = md_wave_max(mx);
-    unsigned long long um = (unsigned long long)unmatched;
-    for (int off = 32; off; off >>= 1) um += __shfl_xor(um, off);
+    mx = wave_max(mx);
+    const unsigned long long um = wave_sum((unsigned long long)unmatched);
     if (lane_id() == 0) {
         if (mx) atomicMax(&st->max_d2_bits, mx);
         if (um) atomicAdd(&st->n_unmatched, um);
@@ -466,8 +437,6 @@ __global__ __launch_bounds__(64) void k_md_reduce_target(const MdGridTotals* __r
 }
 
 // ---- workspaces ----------------------------------------------------------------------------------------------------------------------------------
-static bool md_mesh_ok(long long nv, long long nt) { return nv >= 0 && nt >= 0 && nv < (1ll << 30) && 3 * nt < (1ll << 31); }
-
 struct MdSampleCarve {
     MdSampleTotals* tot;
     int *kk, *off, *block;
@@ -549,12 +518,11 @@ size_t o2345_mesh_samples_workspace_bytes(long long nt) {
 
 int o2345_mesh_samples_count(const double* verts, const void* tris, int index_bytes, long long nv, long long nt, double spacing, void* workspace,
                              size_t workspace_bytes, long long* n_samples_host, void* stream) {
-    O2345_REQUIRE(index_bytes == 4 || index_bytes == 8, "mesh_samples_count: index_bytes must be 4 or 8");
+    O2345_REQUIRE_INDEX_BYTES("mesh_samples_count", index_bytes);
     O2345_REQUIRE(spacing >= 0.0 && spacing <= DBL_MAX, "mesh_samples_count: spacing must be a finite float > 0, or 0 for one sample per triangle, got %g", spacing);
-    O2345_REQUIRE(md_mesh_ok(nv, nt), "mesh_samples_count: bad sizes (nv must stay below 2^30 and 3 * nt below 2^31)");
-    O2345_REQUIRE(workspace && n_samples_host && (nv == 0 || verts) && (nt == 0 || tris), "mesh_samples_count: null pointer");
-    O2345_REQUIRE(workspace_bytes >= o2345_mesh_samples_workspace_bytes(nt), "mesh_samples_count: workspace too small");
-    O2345_REQUIRE(((uintptr_t)workspace & 15) == 0, "mesh_samples_count: workspace must be 16-byte aligned");
+    O2345_REQUIRE(mesh_sizes_ok(nv, nt), "mesh_samples_count: bad sizes (nv must stay below 2^30 and 3 * nt below 2^31)");
+    O2345_REQUIRE(n_samples_host && (nv == 0 || verts) && (nt == 0 || tris), "mesh_samples_count: null pointer");
+    O2345_REQUIRE_WORKSPACE("mesh_samples_count", workspace, workspace_bytes, o2345_mesh_samples_workspace_bytes(nt));
     MdSampleCarve c;
     (void)md_sample_carve(workspace, nt, c);
     hipStream_t s = (hipStream_t)stream;
@@ -578,8 +546,8 @@ int o2345_mesh_samples_count(const double* verts, const void* tris, int index_by
 
 int o2345_mesh_samples_emit(const double* verts, const void* tris, int index_bytes, long long nv, long long nt, void* workspace, long long n_samples,
                             double* points, double* weights, int* triangle, void* stream) {
-    O2345_REQUIRE(index_bytes == 4 || index_bytes == 8, "mesh_samples_emit: index_bytes must be 4 or 8");
-    O2345_REQUIRE(md_mesh_ok(nv, nt), "mesh_samples_emit: bad sizes");
+    O2345_REQUIRE_INDEX_BYTES("mesh_samples_emit", index_bytes);
+    O2345_REQUIRE(mesh_sizes_ok(nv, nt), "mesh_samples_emit: bad sizes");
     O2345_REQUIRE(n_samples >= 0 && n_samples < MD_MAX_SAMPLES && (nt > 0 || n_samples == 0), "mesh_samples_emit: bad sample count %lld", n_samples);
     O2345_REQUIRE(workspace && (n_samples == 0 || (verts && tris)), "mesh_samples_emit: null pointer");
     if (n_samples == 0) return 0;
@@ -608,12 +576,11 @@ size_t o2345_mesh_distance_grid_bytes(long long max_cells, long long n_entries) 
 int o2345_mesh_distance_grid_count(const double* verts, const void* tris, int index_bytes, long long nv, long long nt, double cell, long long max_cells,
                                    void* workspace, size_t workspace_bytes, long long* n_entries_host, long long* n_degenerate_host, int* dims_host,
                                    double* cell_host, void* stream) {
-    O2345_REQUIRE(index_bytes == 4 || index_bytes == 8, "mesh_distance_grid_count: index_bytes must be 4 or 8");
+    O2345_REQUIRE_INDEX_BYTES("mesh_distance_grid_count", index_bytes);
     O2345_REQUIRE(cell >= 0.0 && cell <= DBL_MAX, "mesh_distance_grid_count: cell must be a finite float > 0, or 0 for the default, got %g", cell);
-    O2345_REQUIRE(md_mesh_ok(nv, nt) && md_grid_ok(nt, max_cells), "mesh_distance_grid_count: bad sizes (nv < 2^30, 3 * nt < 2^31, max_cells in [1, 2^24])");
-    O2345_REQUIRE(workspace && n_entries_host && (nv == 0 || verts) && (nt == 0 || tris), "mesh_distance_grid_count: null pointer");
-    O2345_REQUIRE(workspace_bytes >= o2345_mesh_distance_grid_workspace_bytes(nt, max_cells), "mesh_distance_grid_count: workspace too small");
-    O2345_REQUIRE(((uintptr_t)workspace & 15) == 0, "mesh_distance_grid_count: workspace must be 16-byte aligned");
+    O2345_REQUIRE(mesh_sizes_ok(nv, nt) && md_grid_ok(nt, max_cells), "mesh_distance_grid_count: bad sizes (nv < 2^30, 3 * nt < 2^31, max_cells in [1, 2^24])");
+    O2345_REQUIRE(n_entries_host && (nv == 0 || verts) && (nt == 0 || tris), "mesh_distance_grid_count: null pointer");
+    O2345_REQUIRE_WORKSPACE("mesh_distance_grid_count", workspace, workspace_bytes, o2345_mesh_distance_grid_workspace_bytes(nt, max_cells));
     MdGridCarve c;
     (void)md_grid_carve(workspace, nt, max_cells, c);
     hipStream_t s = (hipStream_t)stream;
@@ -644,8 +611,8 @@ int o2345_mesh_distance_grid_count(const double* verts, const void* tris, int in
 
 int o2345_mesh_distance_grid_emit(const double* verts, const void* tris, int index_bytes, long long nv, long long nt, long long max_cells, void* workspace,
                                   long long n_entries, void* grid, size_t grid_bytes, void* stream) {
-    O2345_REQUIRE(index_bytes == 4 || index_bytes == 8, "mesh_distance_grid_emit: index_bytes must be 4 or 8");
-    O2345_REQUIRE(md_mesh_ok(nv, nt) && md_grid_ok(nt, max_cells) && nt > 0, "mesh_distance_grid_emit: bad sizes");
+    O2345_REQUIRE_INDEX_BYTES("mesh_distance_grid_emit", index_bytes);
+    O2345_REQUIRE(mesh_sizes_ok(nv, nt) && md_grid_ok(nt, max_cells) && nt > 0, "mesh_distance_grid_emit: bad sizes");
     O2345_REQUIRE(workspace && grid && verts && tris, "mesh_distance_grid_emit: null pointer");
     const size_t need = o2345_mesh_distance_grid_bytes(max_cells, n_entries);
     O2345_REQUIRE(need && grid_bytes >= need, "mesh_distance_grid_emit: grid of %zu bytes, need %zu", grid_bytes, need);
@@ -670,8 +637,8 @@ int o2345_mesh_distance_grid_emit(const double* verts, const void* tris, int ind
 
 int o2345_mesh_distance_query(const double* points, long long n, const double* verts, const void* tris, int index_bytes, long long nv, long long nt,
                               const void* grid, size_t grid_bytes, long long max_cells, double* d2, int* nearest, void* stream) {
-    O2345_REQUIRE(index_bytes == 4 || index_bytes == 8, "mesh_distance_query: index_bytes must be 4 or 8");
-    O2345_REQUIRE(md_mesh_ok(nv, nt) && n >= 0 && n < MD_MAX_SAMPLES, "mesh_distance_query: bad sizes (nv < 2^30, 3 * nt < 2^31, n < 2^28)");
+    O2345_REQUIRE_INDEX_BYTES("mesh_distance_query", index_bytes);
+    O2345_REQUIRE(mesh_sizes_ok(nv, nt) && n >= 0 && n < MD_MAX_SAMPLES, "mesh_distance_query: bad sizes (nv < 2^30, 3 * nt < 2^31, n < 2^28)");
     O2345_REQUIRE((n == 0 || (points && d2 && nearest)) && (nv == 0 || verts) && (nt == 0 || tris), "mesh_distance_query: null pointer");
     if (n == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
@@ -705,7 +672,7 @@ int o2345_mesh_distance_reduce(const double* d2, const int* nearest, const doubl
     O2345_REQUIRE(n >= 0 && n < MD_MAX_SAMPLES, "mesh_distance_reduce: bad sample count %lld", n);
     O2345_REQUIRE(n_thresholds >= 0 && n_thresholds <= MD_THRESHOLDS && (n_thresholds == 0 || thresholds), "mesh_distance_reduce: %d thresholds; at most 8", n_thresholds);
     O2345_REQUIRE(stats && workspace && (n == 0 || d2), "mesh_distance_reduce: null pointer");
-    O2345_REQUIRE(!tris || ((index_bytes == 4 || index_bytes == 8) && md_mesh_ok(nv, nt) && (nv == 0 || verts)), "mesh_distance_reduce: bad target");
+    O2345_REQUIRE(!tris || ((index_bytes == 4 || index_bytes == 8) && mesh_sizes_ok(nv, nt) && (nv == 0 || verts)), "mesh_distance_reduce: bad target");
     O2345_REQUIRE(workspace_bytes >= o2345_mesh_distance_reduce_workspace_bytes(n), "mesh_distance_reduce: workspace too small");
     O2345_REQUIRE(((uintptr_t)workspace & 15) == 0 && ((uintptr_t)stats & 7) == 0, "mesh_distance_reduce: workspace must be 16-byte and stats 8-byte aligned");
     MdThresholds th = {};

@@ -1,11 +1,43 @@
 // Per-element mesh arithmetic shared by the serialisation kernels (mesh_pack.hip: PLY records; mesh_export.hip: GLB buffers and OBJ text) and by
 // their host-side packers: the marching-cubes index -> output frame transform, the colour quantisation, and the fixed-width decimal fields of the
-// OBJ records.  One definition each, so that a PLY, a GLB and an OBJ of one mesh carry the same float32 positions and the same uint8 colours.
+// OBJ records.  One definition each, so that a PLY, a GLB and an OBJ of one mesh carry the same float32 positions and the same uint8 colours.  Also the
+// index -> world frame of the units that evaluate the networks at mesh points (IndexFrame: mesh_project.hip, mesh_texture.hip).
 #pragma once
-#include "common.h"
+#include "mesh_common.h"
 #include <math.h>
 
 namespace o2345 {
+
+// The marching-cubes index -> world frame of the units that hand points to the network kernels (mesh_project.hip, mesh_texture.hip): the float32 bounds
+// widened to fp64 and subtracted there.  (MeshXform below subtracts in fp32, as the reference's export does, and carries the asset transforms.)
+struct IndexFrame {
+    double rm1;                                       // R - 1
+    double bmin[3], bext[3];                          // bound_min, bound_max - bound_min
+};
+
+// host: the frame from the C ABI's host arrays; false with the unit's error set
+inline bool index_frame(const char* unit, int grid_R, const float* bound_min, const float* bound_max, IndexFrame& f) {
+    f.rm1 = (double)grid_R - 1.0;
+    for (int k = 0; k < 3; ++k) {
+        f.bmin[k] = (double)bound_min[k];
+        f.bext[k] = (double)bound_max[k] - (double)bound_min[k];
+        if (!(f.bext[k] > 0.0 && finite(f.bext[k]) && finite(f.bmin[k]))) {
+            set_error("%s: bound_max must be above bound_min on every axis, both finite", unit);
+            return false;
+        }
+    }
+    return true;
+}
+
+// float32(x / (R - 1) * ext_k + bmin_k) for axis k, one rounding per operation: for the bounds (-1, 1) the pipeline's verts_idx / (R - 1) * 2 - 1 to the
+// bit; and the three axes of a point
+__device__ __forceinline__ float index_to_world_f32(double x, const IndexFrame& f, int k) {
+    return (float)__dadd_rn(__dmul_rn(__ddiv_rn(x, f.rm1), f.bext[k]), f.bmin[k]);
+}
+__device__ __forceinline__ void index_to_world_f32(const double (&x)[3], const IndexFrame& f, float* __restrict__ out) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) out[k] = index_to_world_f32(x[k], f, k);
+}
 
 struct MeshXform {
     double inv_rm1;            // 1 / (R - 1)   (the reference divides; kept as a division below)

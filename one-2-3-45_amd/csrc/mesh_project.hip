@@ -21,7 +21,7 @@
 // go to slot list[i]), and a point's SDF and gradient do not depend on its place in a tile.  The counters are integer atomics, the maxima 64-bit integer
 // atomicMax of the bit pattern of a non-negative double (which orders like the double).  No float atomics.  Counter r of the 66 is written before round
 // r and read in it, never reused, so the list of counts is also the `evaluated` of the twin.
-#include "mesh_common.h"
+#include "mesh_math.h"
 #include <float.h>
 
 namespace o2345 {
@@ -30,28 +30,8 @@ constexpr int PROJ_COUNTS = sizeof(O2345ProjectStats::count) / sizeof(int);     
 constexpr int PROJ_ITEMS = 4;                         // list entries per thread of k_proj_step
 constexpr int PROJ_TILE = 256 * PROJ_ITEMS;           // per block
 
-struct ProjFrame {
-    double rm1;                                       // R - 1
-    double bmin[3], bext[3];
-};
-
-__device__ __forceinline__ void proj_world(const double (&x)[3], const ProjFrame& f, float* __restrict__ p) {
-#pragma unroll
-    for (int k = 0; k < 3; ++k) p[k] = (float)__dadd_rn(__dmul_rn(__ddiv_rn(x[k], f.rm1), f.bext[k]), f.bmin[k]);
-}
-
-__device__ __forceinline__ unsigned long long proj_wave_max(unsigned long long x) {
-    for (int off = 32; off; off >>= 1) { const unsigned long long y = __shfl_xor(x, off); x = y > x ? y : x; }
-    return x;
-}
-
-__device__ __forceinline__ int proj_wave_sum(int x) {
-    for (int off = 32; off; off >>= 1) x += __shfl_xor(x, off);
-    return x;
-}
-
 // thread per vertex: x = the input, its float32 world point, the identity list, the count of round 0; the stats block was zeroed before (memset)
-__global__ __launch_bounds__(256) void k_proj_init(const double* __restrict__ verts, int nv, ProjFrame f, double* __restrict__ x, float* __restrict__ pts,
+__global__ __launch_bounds__(256) void k_proj_init(const double* __restrict__ verts, int nv, IndexFrame f, double* __restrict__ x, float* __restrict__ pts,
                                                    int* __restrict__ list, O2345ProjectStats* __restrict__ st) {
     const long long v = (long long)blockIdx.x * 256 + threadIdx.x;
     bool nonfinite = false;
@@ -61,10 +41,10 @@ __global__ __launch_bounds__(256) void k_proj_init(const double* __restrict__ ve
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
             p[k] = verts[3 * v + k];
-            nonfinite |= !(fabs(p[k]) <= DBL_MAX);
+            nonfinite |= !finite(p[k]);
             x[3 * v + k] = p[k];
         }
-        proj_world(p, f, pts + 3 * v);
+        index_to_world_f32(p, f, pts + 3 * v);
         list[v] = (int)v;
     }
     wave_count(nonfinite, &st->n_nonfinite);
@@ -76,7 +56,7 @@ __global__ __launch_bounds__(256) void k_proj_init(const double* __restrict__ ve
 // stats block's two cache lines.
 __global__ __launch_bounds__(256) void k_proj_step(const double* __restrict__ origin, int nv, double* __restrict__ x, float* __restrict__ pts,
                                                    const float* __restrict__ sdf, const float* __restrict__ grad, const int* __restrict__ list,
-                                                   int* __restrict__ next, O2345ProjectStats* __restrict__ st, int round, int last, ProjFrame f, double level,
+                                                   int* __restrict__ next, O2345ProjectStats* __restrict__ st, int round, int last, IndexFrame f, double level,
                                                    double tol, double max_step, double max_move) {
     __shared__ int wave_tot[5], red_n[4][4], list_base;
     __shared__ unsigned long long red_m[4][2];
@@ -97,14 +77,14 @@ __global__ __launch_bounds__(256) void k_proj_step(const double* __restrict__ or
         const long long v = list[i];
         vs[k] = (int)v;
         const float s32 = sdf[v], g32[3] = {grad[3 * v], grad[3 * v + 1], grad[3 * v + 2]};
-        const bool finite = fabsf(s32) <= FLT_MAX && fabsf(g32[0]) <= FLT_MAX && fabsf(g32[1]) <= FLT_MAX && fabsf(g32[2]) <= FLT_MAX;
+        const bool net_finite = fabsf(s32) <= FLT_MAX && fabsf(g32[0]) <= FLT_MAX && fabsf(g32[1]) <= FLT_MAX && fabsf(g32[2]) <= FLT_MAX;
         const double g[3] = {(double)g32[0], (double)g32[1], (double)g32[2]};
         const double ds = __dsub_rn((double)s32, level);
         const double r = fabs(ds);
         const double g2 = __dadd_rn(__dadd_rn(__dmul_rn(g[0], g[0]), __dmul_rn(g[1], g[1])), __dmul_rn(g[2], g[2]));
-        const unsigned long long rbits = r <= DBL_MAX ? (unsigned long long)__double_as_longlong(r) : 0ull;
+        const unsigned long long rbits = finite(r) ? (unsigned long long)__double_as_longlong(r) : 0ull;
         if (round == 0) before = rbits > before ? rbits : before;
-        if (!finite || !(g2 > 0.0)) ++n_stalled;
+        if (!net_finite || !(g2 > 0.0)) ++n_stalled;
         else if (r <= tol) ++n_converged;
         else if (last) ++n_unconverged;
         else {
@@ -123,7 +103,7 @@ __global__ __launch_bounds__(256) void k_proj_step(const double* __restrict__ or
                 y[d] = q;
                 x[3 * v + d] = q;
             }
-            proj_world(y, f, pts + 3 * v);
+            index_to_world_f32(y, f, pts + 3 * v);
         }
         if (!survives[k]) after = rbits > after ? rbits : after;
     }
@@ -135,8 +115,8 @@ __global__ __launch_bounds__(256) void k_proj_step(const double* __restrict__ or
         pos[k] = total + block_prefix<4>(survives[k], wave_tot, tk);
         total += tk;
     }
-    n_converged = proj_wave_sum(n_converged); n_stalled = proj_wave_sum(n_stalled); n_unconverged = proj_wave_sum(n_unconverged); clamps = proj_wave_sum(clamps);
-    before = proj_wave_max(before); after = proj_wave_max(after);
+    n_converged = wave_sum(n_converged); n_stalled = wave_sum(n_stalled); n_unconverged = wave_sum(n_unconverged); clamps = wave_sum(clamps);
+    before = wave_max(before); after = wave_max(after);
     const int w = threadIdx.x >> 6;
     if (lane_id() == 0) {
         red_n[w][0] = n_converged; red_n[w][1] = n_stalled; red_n[w][2] = n_unconverged; red_n[w][3] = clamps;
@@ -184,7 +164,7 @@ static size_t proj_carve(void* ws, long long nv, ProjCarve& c) {
     return w.bytes();
 }
 
-static bool proj_positive(double x) { return x > 0.0 && x <= DBL_MAX; }
+static bool proj_positive(double x) { return x > 0.0 && finite(x); }
 
 }  // namespace o2345
 
@@ -207,8 +187,8 @@ int o2345_mesh_project(const float* blob, const float* vol_cl, int D, int sdf_mo
     O2345_REQUIRE(proj_size_ok(nv), "mesh_project: bad size (nv must be in [0, 2^30))");
     O2345_REQUIRE(grid_R >= 2, "mesh_project: bad resolution %d", grid_R);
     O2345_REQUIRE(iterations >= 1 && iterations <= PROJ_COUNTS - 2, "mesh_project: iterations must be in [1, 64], got %d", iterations);
-    O2345_REQUIRE(fabs(level) <= DBL_MAX, "mesh_project: level must be finite, got %g", level);
-    O2345_REQUIRE(tol >= 0.0 && tol <= DBL_MAX, "mesh_project: tol must be finite and >= 0, got %g", tol);
+    O2345_REQUIRE(o2345::finite(level), "mesh_project: level must be finite, got %g", level);
+    O2345_REQUIRE(tol >= 0.0 && o2345::finite(tol), "mesh_project: tol must be finite and >= 0, got %g", tol);
     O2345_REQUIRE(proj_positive(max_step), "mesh_project: max_step must be finite and > 0, got %g", max_step);
     O2345_REQUIRE(proj_positive(max_move), "mesh_project: max_move must be finite and > 0, got %g", max_move);
     O2345_REQUIRE(bound_min && bound_max && stats && workspace, "mesh_project: null pointer");
@@ -217,13 +197,8 @@ int o2345_mesh_project(const float* blob, const float* vol_cl, int D, int sdf_mo
     O2345_REQUIRE(nv == 0 || D >= 2, "mesh_project: bad volume side %d", D);
     O2345_REQUIRE(workspace_bytes >= o2345_mesh_project_workspace_bytes(nv), "mesh_project: workspace too small");
     O2345_REQUIRE(((uintptr_t)workspace & 15) == 0 && ((uintptr_t)stats & 7) == 0, "mesh_project: workspace must be 16-byte and stats 8-byte aligned");
-    ProjFrame f;
-    f.rm1 = (double)grid_R - 1.0;
-    for (int k = 0; k < 3; ++k) {
-        f.bmin[k] = (double)bound_min[k];
-        f.bext[k] = (double)bound_max[k] - (double)bound_min[k];
-        O2345_REQUIRE(proj_positive(f.bext[k]) && fabs(f.bmin[k]) <= DBL_MAX, "mesh_project: bound_max must be above bound_min on every axis, both finite");
-    }
+    IndexFrame f;
+    if (!index_frame("mesh_project", grid_R, bound_min, bound_max, f)) return -1;
     ProjCarve c;
     (void)proj_carve(workspace, nv, c);
     hipStream_t s = (hipStream_t)stream;

@@ -72,7 +72,7 @@ __global__ __launch_bounds__(256) void k_sim_begin(const double* __restrict__ ve
     if (i < nv) {
         parent[i] = (int)i;
 #pragma unroll
-        for (int d = 0; d < 3; ++d) nonfinite |= !(fabs(verts[3 * i + d]) <= 1.7976931348623157e308);
+        for (int d = 0; d < 3; ++d) nonfinite |= !finite(verts[3 * i + d]);
     }
     wave_count(bad, &tot->n_bad);
     wave_count(repeated, &tot->n_repeated);
@@ -116,15 +116,6 @@ __device__ __forceinline__ void sim_sum_quadrics(const double* __restrict__ vert
     for (int i = 0; i < MS_Q; ++i) q[i] = acc[i];
 }
 
-template <int N>
-__device__ __forceinline__ void sim_sort_row(int* __restrict__ row, int d) {
-    int r[N];
-    row_sorted_regs<N>(row, d, r);
-#pragma unroll
-    for (int k = 0; k < N; ++k)
-        if (k < d) row[k] = r[k];
-}
-
 // round 0, one thread per vertex: rows of at most ROW_SHORT triangles are sorted here and summed, longer ones are listed
 __global__ __launch_bounds__(256) void k_sim_quadrics(const double* __restrict__ verts, int nv, const int* __restrict__ cur, const int* __restrict__ rawoff,
                                                       const int* __restrict__ tfill, int* __restrict__ trow, double* __restrict__ Q, int* __restrict__ long_list,
@@ -134,12 +125,11 @@ __global__ __launch_bounds__(256) void k_sim_quadrics(const double* __restrict__
     const int k = tfill[v];
     if (k > ROW_SHORT) { long_list[atomicAdd(&tot->n_long, 1)] = (int)v; return; }
     int* row = trow + (rawoff[v] >> 1);
-    if (k > 16) sim_sort_row<ROW_SHORT>(row, k);
-    else if (k > 1) sim_sort_row<16>(row, k);
+    if (k > 1) row_sort_short(row, k);
     sim_sum_quadrics(verts, cur, row, k, Q + MS_Q * v);
 }
 
-// one block per listed row: rank sort through tmp, copied back; thread 0 adds in row order
+// one block per listed row (row_sort_long); thread 0 adds in row order, reading the sorted row where the block has it complete: tmp
 __global__ __launch_bounds__(256) void k_sim_quadrics_long(const double* __restrict__ verts, const int* __restrict__ cur, const int* __restrict__ rawoff,
                                                            const int* __restrict__ tfill, int* __restrict__ trow, int* __restrict__ tmp, double* __restrict__ Q,
                                                            const int* __restrict__ long_list, const SimTotals* __restrict__ tot) {
@@ -147,8 +137,7 @@ __global__ __launch_bounds__(256) void k_sim_quadrics_long(const double* __restr
     for (int r = blockIdx.x; r < n_long; r += gridDim.x) {
         const int v = long_list[r];
         const int base = rawoff[v] >> 1, k = tfill[v];
-        row_rank_sort(trow + base, tmp + base, k);                  // tmp complete (this block wrote all of it)
-        for (int i = threadIdx.x; i < k; i += 256) trow[base + i] = tmp[base + i];
+        row_sort_long(trow + base, tmp + base, k);
         if (threadIdx.x == 0) sim_sum_quadrics(verts, cur, tmp + base, k, Q + MS_Q * (long long)v);
     }
 }
@@ -176,7 +165,7 @@ __global__ __launch_bounds__(256) void k_sim_candidate(const double* __restrict_
 #pragma unroll
                 for (int i = 0; i < MS_Q; ++i) q[i] = __dadd_rn(Qv[i], Q[MS_Q * (long long)u + i]);
                 const double e = ms_error(q, Pu);
-                if (!(fabs(e) <= 1.7976931348623157e308)) continue;
+                if (!finite(e)) continue;
                 const double c = e > 0.0 ? e : 0.0;
                 if (!(c <= max_error) || (best_u >= 0 && !(c < best_c))) continue;
                 // (2): the entries the two ascending rows share
@@ -326,16 +315,6 @@ __global__ __launch_bounds__(256) void k_sim_emit_verts(const double* __restrict
     if (source) source[o] = (int)v;
 }
 
-template <typename IDX>
-__global__ __launch_bounds__(256) void k_sim_emit_tris(const int* __restrict__ cur, long long nt3, const int* __restrict__ vmap, const int* __restrict__ tkeep,
-                                                       const int* __restrict__ tmap, IDX* __restrict__ tris_out) {
-    const long long j = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (j >= nt3) return;
-    const long long t = j / 3;
-    if (!tkeep[t]) return;
-    tris_out[3 * (long long)tmap[t] + (j - 3 * t)] = (IDX)vmap[cur[j]];
-}
-
 struct SimCarve {
     SimTotals* tot;
     double *Q, *cost;
@@ -384,7 +363,7 @@ size_t o2345_mesh_simplify_workspace_bytes(long long nv, long long nt) {
 // stream once after the input check and once per round (the host loop needs the round's counts to decide whether another one runs).
 int o2345_mesh_simplify_count(const double* verts, const void* tris, int index_bytes, long long nv, long long nt, long long target_faces, double max_error,
                               int max_rounds, void* workspace, size_t workspace_bytes, long long* stats, void* stream) {
-    O2345_REQUIRE(index_bytes == 4 || index_bytes == 8, "mesh_simplify_count: index_bytes must be 4 or 8");
+    O2345_REQUIRE_INDEX_BYTES("mesh_simplify_count", index_bytes);
     O2345_REQUIRE(sim_sizes_ok(nv, nt), "mesh_simplify_count: bad sizes (nv must stay below 2^30 and 6 * nt below 2^31)");
     O2345_REQUIRE(target_faces >= 0 && max_rounds >= 0, "mesh_simplify_count: target_faces and max_rounds must be >= 0, got %lld, %d", target_faces, max_rounds);
     O2345_REQUIRE(max_error >= 0.0, "mesh_simplify_count: max_error must be >= 0 (infinity = no limit), got %g", max_error);
@@ -447,7 +426,7 @@ int o2345_mesh_simplify_count(const double* verts, const void* tris, int index_b
 // (same nv and nt, untouched in between).  Any output may be NULL.
 int o2345_mesh_simplify_emit(const double* verts, int index_bytes, long long nv, long long nt, void* workspace, double* verts_out, void* tris_out, int* source,
                              int* merged, void* stream) {
-    O2345_REQUIRE(index_bytes == 4 || index_bytes == 8, "mesh_simplify_emit: index_bytes must be 4 or 8");
+    O2345_REQUIRE_INDEX_BYTES("mesh_simplify_emit", index_bytes);
     O2345_REQUIRE(sim_sizes_ok(nv, nt), "mesh_simplify_emit: bad sizes");
     O2345_REQUIRE(workspace && (!verts_out || verts || nv == 0), "mesh_simplify_emit: null pointer");
     SimCarve c;
@@ -456,7 +435,7 @@ int o2345_mesh_simplify_emit(const double* verts, int index_bytes, long long nv,
     if (nv > 0 && (verts_out || source || merged))
         hipLaunchKernelGGL(k_sim_emit_verts, dim3(cdiv(nv, 256)), dim3(256), 0, s, verts, (int)nv, c.parent, c.flag, c.vmap, verts_out, source, merged);
     if (nt > 0 && tris_out) with_index_type(index_bytes, tris_out, [&](auto* t) {
-        hipLaunchKernelGGL(k_sim_emit_tris<index_type<decltype(t)>>, dim3(cdiv(3 * nt, 256)), dim3(256), 0, s, c.cur, 3 * nt, c.vmap, c.tkeep, c.tmap, t);
+        hipLaunchKernelGGL((k_mesh_emit_tris<int, index_type<decltype(t)>>), dim3(cdiv(3 * nt, 256)), dim3(256), 0, s, c.cur, 3 * nt, c.vmap, c.tkeep, c.tmap, t);
     });
     return check_launch("mesh_simplify_emit");
 }

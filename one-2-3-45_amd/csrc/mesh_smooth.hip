@@ -77,11 +77,10 @@ size_t o2345_mesh_adjacency_workspace_bytes(long long nv, long long nt) {
 // the caller must allocate `neighbours`).
 int o2345_mesh_adjacency_count(const void* tris, int index_bytes, long long nv, long long nt, void* workspace, size_t workspace_bytes, long long* n_entries_host,
                                void* stream) {
-    O2345_REQUIRE(index_bytes == 4 || index_bytes == 8, "mesh_adjacency_count: index_bytes must be 4 or 8");
+    O2345_REQUIRE_INDEX_BYTES("mesh_adjacency_count", index_bytes);
     O2345_REQUIRE(adj_sizes_ok(nv, nt), "mesh_adjacency_count: bad sizes (nv must stay below 2^30 and 6 * nt below 2^31)");
-    O2345_REQUIRE(n_entries_host && workspace && (nt == 0 || tris), "mesh_adjacency_count: null pointer");
-    O2345_REQUIRE(workspace_bytes >= o2345_mesh_adjacency_workspace_bytes(nv, nt), "mesh_adjacency_count: workspace too small");
-    O2345_REQUIRE(((uintptr_t)workspace & 15) == 0, "mesh_adjacency_count: workspace must be 16-byte aligned");
+    O2345_REQUIRE(n_entries_host && (nt == 0 || tris), "mesh_adjacency_count: null pointer");
+    O2345_REQUIRE_WORKSPACE("mesh_adjacency_count", workspace, workspace_bytes, o2345_mesh_adjacency_workspace_bytes(nv, nt));
     AdjCarve c;
     (void)adj_carve(workspace, nv, nt, c);
     hipStream_t s = (hipStream_t)stream;
@@ -114,7 +113,7 @@ int o2345_mesh_smooth(const double* verts_in, long long nv, const int* offsets, 
                       double lam, double mu, double* verts_tmp, double* verts_out, void* stream) {
     O2345_REQUIRE(nv >= 0 && nv < (1ll << 30), "mesh_smooth: bad sizes (nv must stay below 2^30)");
     O2345_REQUIRE(iterations >= 0, "mesh_smooth: iterations must be >= 0, got %d", iterations);
-    O2345_REQUIRE(lam > 0.0 && lam <= 1.0 && mu <= 0.0 && mu >= -1.7976931348623157e308, "mesh_smooth: need 0 < lam <= 1 and finite mu <= 0, got %g, %g", lam, mu);
+    O2345_REQUIRE(lam > 0.0 && lam <= 1.0 && mu <= 0.0 && o2345::finite(mu), "mesh_smooth: need 0 < lam <= 1 and finite mu <= 0, got %g, %g", lam, mu);
     const long long steps = (long long)iterations * (mu != 0.0 ? 2 : 1);
     O2345_REQUIRE(nv == 0 || (verts_in && verts_out && offsets && (steps < 2 || verts_tmp)), "mesh_smooth: null pointer");
     if (nv == 0) return 0;

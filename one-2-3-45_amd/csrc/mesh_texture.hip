@@ -21,9 +21,7 @@
 //              / W, (cell_y c + v_local) / H) in fp64, rounded once; position and normal are the welded export's for that vertex (mesh_math.h).
 // Bad input never faults: a triangle index outside [0, nv) is read as vertex 0, and it and a non-finite coordinate are counted once per triangle in two
 // integer counters that the caller raises on.  No other atomics.  Nothing here synchronises with the host.
-#include "mesh_common.h"
 #include "mesh_math.h"
-#include <float.h>
 
 namespace o2345 {
 
@@ -45,15 +43,10 @@ static bool tex_layout(long long nt, int c, TexLayout& L) {
     return true;
 }
 
-struct TexFrame {
-    double rm1;                                       // R - 1
-    double bmin[3], bext[3];
-};
-
 // thread per texel of a used cell, cell-major
 template <typename IDX>
 __global__ __launch_bounds__(256) void k_tex_points(const double* __restrict__ verts, long long nv, const IDX* __restrict__ tris, long long nt, int c,
-                                                    long long texels, TexFrame f, double* __restrict__ pidx, float* __restrict__ pworld,
+                                                    long long texels, IndexFrame f, double* __restrict__ pidx, float* __restrict__ pworld,
                                                     O2345TextureStats* __restrict__ st) {
     const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
     bool bad = false, nonfinite = false;
@@ -78,7 +71,7 @@ __global__ __launch_bounds__(256) void k_tex_points(const double* __restrict__ v
 #pragma unroll
             for (int d = 0; d < 3; ++d) {
                 P[q][d] = verts[3 * v + d];
-                tn |= !(fabs(P[q][d]) <= DBL_MAX);
+                tn |= !finite(P[q][d]);
             }
         }
         bad = counts && tb;
@@ -88,7 +81,7 @@ __global__ __launch_bounds__(256) void k_tex_points(const double* __restrict__ v
             double y = __dadd_rn(__dadd_rn(__dmul_rn(w0, P[0][d]), __dmul_rn(w1, P[1][d])), __dmul_rn(w2, P[2][d]));
             if (y < 0.0) y = 0.0; else if (y > f.rm1) y = f.rm1;
             pidx[3 * e + d] = y;
-            pworld[3 * e + d] = (float)__dadd_rn(__dmul_rn(__ddiv_rn(y, f.rm1), f.bext[d]), f.bmin[d]);
+            pworld[3 * e + d] = index_to_world_f32(y, f, d);
         }
     }
     wave_count(bad, &st->n_bad);
@@ -159,20 +152,15 @@ size_t o2345_mesh_texture_texels(long long nt, int texel, int* width_host, int* 
 
 int o2345_mesh_texture_points(const double* verts, long long nv, const void* tris, int index_bytes, long long nt, int texel, int grid_R,
                               const float* bound_min, const float* bound_max, double* points_idx, float* points_world, O2345TextureStats* stats, void* stream) {
-    O2345_REQUIRE(index_bytes == 4 || index_bytes == 8, "mesh_texture_points: index_bytes must be 4 or 8");
+    O2345_REQUIRE_INDEX_BYTES("mesh_texture_points", index_bytes);
     TexLayout L;
     O2345_REQUIRE(tex_layout(nt, texel, L), "mesh_texture_points: bad layout (nt = %lld >= 1, texel = %d in [4, 64], sides <= 16384, texels < 2^31)", nt, texel);
     O2345_REQUIRE(nv >= 1 && nv < (1ll << 30), "mesh_texture_points: bad size (nv must be in [1, 2^30))");
     O2345_REQUIRE(grid_R >= 2, "mesh_texture_points: bad resolution %d", grid_R);
     O2345_REQUIRE(verts && tris && bound_min && bound_max && points_idx && points_world && stats, "mesh_texture_points: null pointer");
     O2345_REQUIRE(((uintptr_t)stats & 7) == 0, "mesh_texture_points: stats must be 8-byte aligned");
-    TexFrame f;
-    f.rm1 = (double)grid_R - 1.0;
-    for (int k = 0; k < 3; ++k) {
-        f.bmin[k] = (double)bound_min[k];
-        f.bext[k] = (double)bound_max[k] - (double)bound_min[k];
-        O2345_REQUIRE(f.bext[k] > 0.0 && f.bext[k] <= DBL_MAX && fabs(f.bmin[k]) <= DBL_MAX, "mesh_texture_points: bound_max must be above bound_min on every axis, both finite");
-    }
+    IndexFrame f;
+    if (!index_frame("mesh_texture_points", grid_R, bound_min, bound_max, f)) return -1;
     hipStream_t s = (hipStream_t)stream;
     O2345_HIP(hipMemsetAsync(stats, 0, sizeof *stats, s));
     const dim3 grid(cdiv(L.texels, 256));
@@ -195,7 +183,7 @@ int o2345_mesh_texture_corners(const double* verts, long long nv, const void* tr
                                const float* bound_min, const float* bound_max, const float* scale_mat, const float* trans_mat, const float* grad,
                                float* positions, float* uv, float* normals, uint32_t* indices, float* bounds, void* workspace, size_t workspace_bytes,
                                void* stream) {
-    O2345_REQUIRE(index_bytes == 4 || index_bytes == 8, "mesh_texture_corners: index_bytes must be 4 or 8");
+    O2345_REQUIRE_INDEX_BYTES("mesh_texture_corners", index_bytes);
     TexLayout L;
     O2345_REQUIRE(tex_layout(nt, texel, L), "mesh_texture_corners: bad layout (nt = %lld >= 1, texel = %d in [4, 64], sides <= 16384, texels < 2^31)", nt, texel);
     O2345_REQUIRE(nv >= 1 && nv < (1ll << 30), "mesh_texture_corners: bad size (nv must be in [1, 2^30))");

@@ -20,7 +20,6 @@
 //              No such j: a miss.  depth = float32(t), point_k = float32(o_k + t d_k); both 0 for kind 0.
 // Hit slots are appended to a list through a ballot and one integer atomicAdd per wave: its order changes between runs, its content does not, and nothing
 // reads its order (the network kernels scatter through it).  Counters are integer atomics of wave sums.  No float atomics.
-#include "mesh_common.h"
 #include "mesh_math.h"
 #include <float.h>
 
@@ -74,13 +73,6 @@ __device__ __forceinline__ double surf_value(const float* __restrict__ u, const 
     return v;
 }
 
-__device__ __forceinline__ bool surf_finite(double x) { return fabs(x) <= DBL_MAX; }
-
-__device__ __forceinline__ int surf_wave_sum(int x) {
-    for (int off = 32; off; off >>= 1) x += __shfl_xor(x, off);
-    return x;
-}
-
 // one wave per brick: its (up to) 9^3 nodes in strides of 64, one ballot
 __global__ __launch_bounds__(256) void k_surface_bricks(const float* __restrict__ u, SurfFrame f, uint8_t* __restrict__ flags) {
     const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -119,16 +111,16 @@ __global__ __launch_bounds__(256) void k_surface_trace(const float* __restrict__
     int what = NONE, samples = 0, lookups = 0;
     double t_hit = 0.0, o[3] = {0.0, 0.0, 0.0}, d[3] = {0.0, 0.0, 0.0};
     if (valid) {
-        bool finite = true;
+        bool ray_finite = true;
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
             o[k] = (double)rays_o[3 * r + k];
             d[k] = (double)rays_d[3 * r + k];
-            finite = finite && surf_finite(o[k]) && surf_finite(d[k]);
+            ray_finite = ray_finite && finite(o[k]) && finite(d[k]);
         }
         double t0 = f.t_near, t1 = f.t_far;
         bool miss = false;
-        if (finite) {
+        if (ray_finite) {
 #pragma unroll
             for (int k = 0; k < 3; ++k) {
                 if (d[k] == 0.0) {
@@ -143,7 +135,7 @@ __global__ __launch_bounds__(256) void k_surface_trace(const float* __restrict__
             miss = miss || !(t0 <= t1);
         }
         const double q = floor((t1 - t0) / f.h);
-        if (!finite) what = BAD;
+        if (!ray_finite) what = BAD;
         else if (miss) what = BOX_MISS;
         else if (!(q <= (double)SURF_MAX_STEPS)) what = BAD;
         else {
@@ -184,7 +176,7 @@ __global__ __launch_bounds__(256) void k_surface_trace(const float* __restrict__
                     if (vm > 0.0) { lo = tm; s_lo = vm; } else { hi = tm; s_hi = vm; }
                 }
                 t_hit = lo + (hi - lo) * (s_lo / (s_lo - s_hi));
-                what = surf_finite(t_hit) ? HIT : STALLED;
+                what = finite(t_hit) ? HIT : STALLED;
             }
         }
         const bool hit = what == HIT || what == ENTRY;
@@ -207,8 +199,8 @@ __global__ __launch_bounds__(256) void k_surface_trace(const float* __restrict__
     wave_count(what == MISS, &st->misses);
     wave_count(what == STALLED, &st->stalled);
     wave_count(what == BAD, &st->bad_rays);
-    samples = surf_wave_sum(samples);                                      // <= 64 x (2^20 + 34)
-    lookups = surf_wave_sum(lookups);
+    samples = wave_sum(samples);                                      // <= 64 x (2^20 + 34)
+    lookups = wave_sum(lookups);
     if (lane_id() == 0) {
         if (samples) atomicAdd(&st->samples, (unsigned long long)samples);
         if (lookups) atomicAdd(&st->lookups, (unsigned long long)lookups);
@@ -268,7 +260,7 @@ static size_t surf_carve(void* ws, long long n, int*& list) {
 // the frame of a call from the C ABI's host arrays; false with the error set
 static bool surf_frame(const char* unit, int grid_R, double level, int inside_positive, const float* bound_min, const float* bound_max, SurfFrame& f) {
     if (!(grid_R >= 2 && grid_R <= SURF_MAX_R)) { set_error("%s: resolution must be in [2, %d], got %d", unit, SURF_MAX_R, grid_R); return false; }
-    if (!(fabs(level) <= DBL_MAX)) { set_error("%s: level must be finite, got %g", unit, level); return false; }
+    if (!finite(level)) { set_error("%s: level must be finite, got %g", unit, level); return false; }
     f = SurfFrame{};
     f.R = grid_R;
     f.nb = (grid_R - 1 + SURF_BRICK - 1) / SURF_BRICK;
@@ -279,7 +271,7 @@ static bool surf_frame(const char* unit, int grid_R, double level, int inside_po
         f.bmin[k] = bound_min ? (double)bound_min[k] : -1.0;
         f.bmax[k] = bound_max ? (double)bound_max[k] : 1.0;
         f.ext[k] = f.bmax[k] - f.bmin[k];
-        if (!(f.ext[k] > 0.0 && f.ext[k] <= DBL_MAX && fabs(f.bmin[k]) <= DBL_MAX)) {
+        if (!(f.ext[k] > 0.0 && finite(f.ext[k]) && finite(f.bmin[k]))) {
             set_error("%s: bound_max must be above bound_min on every axis, both finite", unit);
             return false;
         }
@@ -319,7 +311,7 @@ int o2345_surface_trace(const float* u, int grid_R, const uint8_t* flags, const 
     O2345_REQUIRE(n == 0 || (rays_o && rays_d && depth && kind && point), "surface_trace: null pointer");
     O2345_REQUIRE(stride > 0.0 && stride <= 8.0, "surface_trace: stride must be in (0, 8], got %g", stride);
     O2345_REQUIRE(refine >= 0 && refine <= 32, "surface_trace: refine must be in [0, 32], got %d", refine);
-    O2345_REQUIRE(fabs(t_near) <= DBL_MAX && fabs(t_far) <= DBL_MAX, "surface_trace: near and far must be finite");
+    O2345_REQUIRE(o2345::finite(t_near) && o2345::finite(t_far), "surface_trace: near and far must be finite");
     O2345_REQUIRE((img_h == 0 && img_w == 0) || (img_h > 0 && img_w > 0 && (long long)img_h * img_w == n),
                   "surface_trace: img_h x img_w must be 0 x 0 or the ray count, got %d x %d for %lld rays", img_h, img_w, n);
     O2345_REQUIRE(workspace_bytes >= o2345_surface_trace_workspace_bytes(n), "surface_trace: workspace too small");

@@ -141,6 +141,36 @@ def test_grid_lists_are_ascending_and_complete(dev):
             assert np.array_equal(row, np.nonzero(inside)[0])
 
 
+ROW_SIZES = [1, 2, 3, 4, 5, 15, 16, 17, 31, 32, 33, 34, 65]          # around 4, 16 and 32 (the register sorts of 4, 16 and 32 entries); 33, 34 and 65: long rows
+
+
+@pytest.mark.parametrize("dtype", [torch.int32, torch.int64])
+def test_cell_lists_around_the_register_sort_limits(dev, dtype):
+    """258 small triangles with an area in 13 groups of ROW_SIZES; those of group k lie strictly inside the cell at x in (2k + 0.25, 2k + 0.75), y and z in
+    (0.25, 0.75) of a grid of edge 1.  The triangle indices are shuffled, so the members of a cell come from all over the index range and reach its list
+    in any order.  Every occupied cell's list is its group, ascending; every other cell is empty."""
+    rng = np.random.default_rng(17)
+    owner = rng.permutation(np.repeat(np.arange(len(ROW_SIZES)), ROW_SIZES))
+    nt = owner.size
+    assert nt == 258
+    corner = rng.uniform(0.3, 0.6, (nt, 1, 3)) + np.array([[0.0, 0.0, 0.0], [0.1, 0.0, 0.02], [0.0, 0.1, 0.03]])          # three corners per triangle
+    assert (corner > 0.25).all() and (corner < 0.75).all()
+    corner[:, :, 0] += 2.0 * owner[:, None]
+    v, f = corner.reshape(-1, 3), np.arange(3 * nt, dtype=np.int64).reshape(nt, 3)
+    grid = ops.mesh_distance_grid(up(v, dev), up(f, dev, dtype).view(-1, 3), 1.0, max_cells=4096)
+    assert grid.cell == 1.0 and grid.dims == (2 * len(ROW_SIZES) - 1, 1, 1) and grid.entries == nt
+    raw = grid.buffer.cpu().numpy()
+    n_cells = grid.dims[0]
+    assert (raw[:24].view(np.float64) == 0.0).all()                  # the origin: cell c is x in [c, c + 1)
+    start = raw[128:128 + 4 * (n_cells + 1)].view(np.int32)
+    entries = raw[128 + (4 * (4096 + 1) + 15) // 16 * 16:].view(np.int32)[:grid.entries]
+    assert start[0] == 0 and start[-1] == nt
+    for c in range(n_cells):
+        row = entries[start[c]:start[c + 1]]
+        want = np.flatnonzero(owner == c // 2) if c % 2 == 0 else np.zeros(0, np.int64)
+        assert np.array_equal(row, want), (c, row, want)
+
+
 def test_degenerate_targets_take_no_part(dev):
     v, f = U.square(0.0)
     f2 = np.concatenate([[[0, 0, 1], [0, 1, 2]], f, [[3, 3, 3]]])
