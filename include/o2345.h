@@ -62,7 +62,7 @@ const char* o2345_last_error(void);
  * of them moved, the untyped `stats` parameters became pointers to them); o2345_struct_size / o2345_struct_layout describe every declared struct and replace
  * o2345_render_io_size / o2345_render_io_layout; the parameter of o2345_render_rays is called io_host.
  * Additive since 2.2 (the version stays 220): the simplification entries o2345_mesh_simplify_workspace_bytes, o2345_mesh_simplify_count,
- * o2345_mesh_simplify_emit. */
+ * o2345_mesh_simplify_emit; the audit entries o2345_mesh_audit_workspace_bytes, o2345_mesh_audit. */
 int o2345_version(void);
 /* Layout self-description of the declared structs as THIS library was compiled (sizeof, and offsetof of every field in declaration order): a binding
  * asserts its own structs against it at load time (one-2-3-45_amd/_lib.py does) -- a field added on one side only cannot corrupt calls silently.
@@ -724,6 +724,44 @@ size_t o2345_mesh_distance_reduce_workspace_bytes(long long n);
 int o2345_mesh_distance_reduce(const double* d2, const int* nearest, const double* weights, long long n, const double* thresholds_host, int n_thresholds,
                                const double* verts, const void* tris, int index_bytes, long long nv, long long nt, void* workspace, size_t workspace_bytes,
                                O2345DistanceStats* stats, void* stream);
+
+/* ---- audit of a mesh: manifoldness, orientation, element quality (additive since 2.2; none in the reference: its meshes are never checked) -------------
+ * Read-only; equal to the host twin mesh_io.mesh_audit: integers, flags, quality, minima and maxima to the last bit, the three sums to 1e-12 of the sum of
+ * their terms' magnitudes.  Everything is fp64, one operation at a time, in the order written (csrc/mesh_audit_math.h is the text), a dot product (x x + y y)
+ * + z z.  verts device fp64 [nv,3], tris device int32 / int64 [nt,3] (index_bytes 4 / 8), both only read; 0 <= nv < 2^30, 6 * nt < 2^31.
+ *   triangles  two equal indices: REPEATED, counted, flagged, no part in anything else.  The others (FACES): n = (P1 - P0) x (P2 - P0), nn = n . n, ZERO_AREA iff
+ *              nn == 0; area_t = 0.5 sqrt(nn); v_t = P0 . (P1 x P2); l01, l12, l20 the squared edge lengths, s = (l01 + l12) + l20; quality q_t =
+ *              (6.928203230275509 area_t) / s (4 sqrt 3: 1 for an equilateral triangle), 0 when s == 0.  Histogram: bin min(9, floor(q 10)); a q that is not
+ *              >= 0 enters no bin and no minimum.
+ *   edges      half-edge 3 t + i runs from tris[t][i] to tris[t][(i + 1) % 3]; the undirected edge {lo, hi} has m half-edges, of which some run lo -> hi.
+ *              BOUNDARY m = 1, manifold m = 2, NONMANIFOLD m >= 3; a manifold edge is INCONSISTENT iff both half-edges run the same way; a manifold,
+ *              consistent edge whose two triangles have nn > 0 is CREASED iff n . n' < 0 (a right angle is not).
+ *   vertices   used: referenced by a face; boundary: on a boundary edge; non-manifold: on an edge with m >= 3.  Fans: over the corners (t, i) of the
+ *              faces, every manifold edge {u, w}, whatever its orientation, joins the two corners at u and the two corners at w; fans(v) = the classes
+ *              among the corners at v.  BOWTIE iff fans(v) >= 2 and v lies on no non-manifold edge.
+ *   sums       area = sum area_t, sum v_t (six times the volume of a closed, consistent mesh), sum q_t: every block folds its 256 triangles in a fixed
+ *              tree, one block folds the rows; the same bits on every run, no floating-point atomics.  min q_t, min and max squared edge length over the
+ *              faces' half-edges; without a face the two minima are +inf and the maximum is 0.
+ * stats: device int64 [O2345_AUDIT_STATS], 8-byte aligned: the entries named below; *_BITS is the bit pattern of a double.  vertex_flags uint8 [nv]: bit 0
+ * boundary, 1 on a non-manifold edge, 2 bow-tie, 3 unused.  face_flags uint8 [nt]: bit 0 repeated, 1 zero-area, 2 has a boundary edge, 3 a non-manifold
+ * edge, 4 an inconsistent edge, 5 a creased edge.  quality fp64 [nt]: 0 for a repeated triangle.  Any of the three may be NULL.  A triangle index outside
+ * [0, nv) and a vertex with a non-finite coordinate are counted (BAD_INDEX, NONFINITE), never dereferenced; the caller reads the two counts and treats
+ * the rest as void when one is not 0.  workspace: mesh_audit_workspace_bytes(nv, nt) bytes (0 for bad sizes), 16-byte aligned.  No host synchronisation.
+ * Not done: duplicate faces, per-component reports, dihedral statistics, any repair. */
+enum {
+    O2345_AUDIT_BAD_INDEX = 0, O2345_AUDIT_NONFINITE = 1,               /* triangles with an index outside [0, nv); vertices with a non-finite coordinate */
+    O2345_AUDIT_VERTICES = 2, O2345_AUDIT_EDGES = 3, O2345_AUDIT_FACES = 4,             /* used vertices, undirected edges, non-repeated triangles */
+    O2345_AUDIT_REPEATED = 5, O2345_AUDIT_ZERO_AREA = 6,
+    O2345_AUDIT_BOUNDARY_EDGES = 7, O2345_AUDIT_NONMANIFOLD_EDGES = 8, O2345_AUDIT_INCONSISTENT_EDGES = 9, O2345_AUDIT_CREASED_EDGES = 10,
+    O2345_AUDIT_BOUNDARY_VERTICES = 11, O2345_AUDIT_NONMANIFOLD_VERTICES = 12, O2345_AUDIT_BOWTIE_VERTICES = 13, O2345_AUDIT_UNUSED_VERTICES = 14,
+    O2345_AUDIT_HISTOGRAM = 16,                         /* entry 15: 0; entries 16 .. 25: the ten quality bins */
+    O2345_AUDIT_AREA_BITS = 26, O2345_AUDIT_VOLUME6_BITS = 27, O2345_AUDIT_QUALITY_SUM_BITS = 28,
+    O2345_AUDIT_QUALITY_MIN_BITS = 29, O2345_AUDIT_EDGE2_MIN_BITS = 30, O2345_AUDIT_EDGE2_MAX_BITS = 31,
+    O2345_AUDIT_STATS = 32
+};
+size_t o2345_mesh_audit_workspace_bytes(long long nv, long long nt);
+int o2345_mesh_audit(const double* verts, const void* tris, int index_bytes, long long nv, long long nt, void* workspace, size_t workspace_bytes,
+                     long long* stats, unsigned char* vertex_flags_or_null, unsigned char* face_flags_or_null, double* quality_or_null, void* stream);
 /* Load every code object of the library on the current device now (the HIP runtime loads a translation unit's kernels at its first launch: 5 - 60 ms
  * each for the units of this library, which otherwise land inside the first calls of a fresh process).  Launches nothing that touches user memory. */
 int o2345_preload(void);

@@ -351,6 +351,17 @@ def mesh_error(x=None):
     return MESH_ERROR if x is None else bool(x)
 
 
+# ---- mesh audit report (csrc/mesh_audit.hip; mesh_io.mesh_audit is the host twin) -------------------------------------------------------------------------
+# O2345_MESH_AUDIT=1 makes pipeline.reconstruct_folder report whether the mesh it wrote is a closed, oriented 2-manifold and how good its triangles are
+# (ops.mesh_audit: open, non-manifold and inconsistent edges, bow-tie vertices, Euler characteristic, genus, area, volume, quality), in units of the
+# extraction grid's spacing ("" or "0" = off, the default: nothing is launched and the result keeps its keys).
+MESH_AUDIT = _non_negative_int("O2345_MESH_AUDIT", os.environ.get("O2345_MESH_AUDIT", "")) != 0
+
+
+def mesh_audit(x=None):
+    return MESH_AUDIT if x is None else bool(x)
+
+
 # ---- surface render (csrc/surface_trace.hip; surface.py is the host twin) ---------------------------------------------------------------------------------
 # pipeline.render_surface marches rays through the extraction lattice.  O2345_SURFACE_STRIDE (1.0, in (0, 8]) is the distance between two samples in
 # lattice spacings -- above 1 the march may step over parts thinner than the stride; O2345_SURFACE_REFINE (8, in [0, 32]) the number of bracket

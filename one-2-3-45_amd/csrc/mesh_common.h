@@ -1,6 +1,7 @@
 // What the mesh units share.  The units: mcubes.hip, mesh_components.hip, mesh_smooth.hip and mesh_simplify.hip (both through mesh_adjacency.h),
-// mesh_decimate.hip, mesh_project.hip, mesh_texture.hip, mesh_distance.hip, mesh_export.hip, mesh_pack.hip, and surface_trace.hip for the wave sums and
-// finite().  On the device: the triangle reader, the wave-level counter and reductions, finite(), the order-preserving fp64 <-> uint64 encoding, the row
+// mesh_decimate.hip, mesh_project.hip, mesh_texture.hip, mesh_distance.hip, mesh_audit.hip, mesh_export.hip, mesh_pack.hip, and surface_trace.hip for the wave
+// sums and finite().  On the device: the triangle reader, the wave-level counter and reductions, finite(), the order-preserving fp64 <-> uint64 encoding,
+// the union-find of the components and the audit, the row
 // sorts (registers, the short-row ladder, the block-wide long form) and the kernel that emits kept triangles.  On the host: the workspace carver, the
 // entry checks (sizes, index width, workspace), the index-width dispatch, the three-launch exclusive scan and the read-back of a call's device totals.
 // The index -> world frame of projection and texture is in mesh_math.h.  Everything is inline, a template or in an anonymous namespace: each unit keeps
@@ -67,6 +68,33 @@ __device__ __forceinline__ unsigned long long dec_mix(unsigned long long x) {
     x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull;
     x ^= x >> 27; x *= 0x94D049BB133111EBull;
     return x ^ (x >> 31);
+}
+
+// Lock-free union-find over int nodes (the vertices of mesh_components.hip, the triangle corners of mesh_audit.hip): parent[x] <= x always, a union
+// attaches the LARGER root under the smaller with one atomicCAS, and a later launch reads the roots (see mesh_components.hip for why it terminates).
+__device__ __forceinline__ int cc_load(const int* p) { return __atomic_load_n(p, __ATOMIC_RELAXED); }
+__device__ __forceinline__ void cc_store(int* p, int v) { __atomic_store_n(p, v, __ATOMIC_RELAXED); }
+
+// root of x; on the way every visited node is re-pointed to its grandparent (a value read from an ancestor, so parent[.] stays an ancestor whatever
+// the interleaving; a non-root never becomes a root again, so these stores never disturb a CAS, which only succeeds on roots)
+__device__ __forceinline__ int cc_find(int* parent, int x) {
+    int p = cc_load(parent + x);
+    while (p != x) {
+        const int g = cc_load(parent + p);
+        if (g != p) cc_store(parent + x, g);
+        x = p; p = g;
+    }
+    return x;
+}
+
+__device__ __forceinline__ void cc_union(int* parent, int a, int b) {
+    for (;;) {
+        a = cc_find(parent, a);
+        b = cc_find(parent, b);
+        if (a == b) return;
+        if (a < b) { const int t = a; a = b; b = t; }
+        if (atomicCAS(parent + a, a, b) == a) return;          // lost: a is no root any more, go on from the new roots
+    }
 }
 
 // r = the d <= N entries of row, ascending, then ROW_PAD

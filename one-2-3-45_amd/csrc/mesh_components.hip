@@ -31,31 +31,6 @@ struct CcTotals {
 
 struct CcSelect { int active, keep_largest, min_faces; };       // min_faces already >= 1 when active
 
-__device__ __forceinline__ int cc_load(const int* p) { return __atomic_load_n(p, __ATOMIC_RELAXED); }
-__device__ __forceinline__ void cc_store(int* p, int v) { __atomic_store_n(p, v, __ATOMIC_RELAXED); }
-
-// root of x; on the way every visited node is re-pointed to its grandparent (a value read from an ancestor, so parent[.] stays an ancestor whatever
-// the interleaving; a non-root never becomes a root again, so these stores never disturb a CAS, which only succeeds on roots)
-__device__ __forceinline__ int cc_find(int* parent, int x) {
-    int p = cc_load(parent + x);
-    while (p != x) {
-        const int g = cc_load(parent + p);
-        if (g != p) cc_store(parent + x, g);
-        x = p; p = g;
-    }
-    return x;
-}
-
-__device__ __forceinline__ void cc_union(int* parent, int a, int b) {
-    for (;;) {
-        a = cc_find(parent, a);
-        b = cc_find(parent, b);
-        if (a == b) return;
-        if (a < b) { const int t = a; a = b; b = t; }
-        if (atomicCAS(parent + a, a, b) == a) return;          // lost: a is no root any more, go on from the new roots
-    }
-}
-
 __global__ __launch_bounds__(256) void k_cc_init(int* __restrict__ parent, int* __restrict__ faces, int nv, CcTotals* __restrict__ tot) {
     const long long v = (long long)blockIdx.x * 256 + threadIdx.x;
     if (v == 0) *tot = CcTotals{0ull, 0ll, 0ll, 0ull, 0ull, 0ull};

@@ -1628,3 +1628,159 @@ def compare_mesh_files(path_a, path_b, spacing=None, thresholds=(), return_sampl
     """mesh_distance of two mesh files (.ply, .glb, .obj; load_mesh_pair brings them into one frame)"""
     (va, fa), (vb, fb) = load_mesh_pair(path_a, path_b)
     return mesh_distance(va, fa, vb, fb, spacing, thresholds, return_samples)
+
+
+# ------------------------------------------------------------------------------------------------------------------ mesh audit
+# the functions below are the host twin of csrc/mesh_audit.hip and the DEFINITION of its results: counts, flags, per-triangle quality, minima and maxima
+# to the last bit.  All arithmetic is float64, one operation at a time, in the order written; a dot product is (x x + y y) + z z.
+AUDIT_QUALITY_SCALE = 6.928203230275509          # 4 sqrt(3): an equilateral triangle has quality 1
+AUDIT_BINS = 10
+AUDIT_VERTEX_BITS = {"boundary": 1, "nonmanifold": 2, "bowtie": 4, "unused": 8}
+AUDIT_FACE_BITS = {"repeated": 1, "zero_area": 2, "boundary": 4, "nonmanifold": 8, "inconsistent": 16, "creased": 32}
+# the integer counts of an audit, in the order of the device's stats block (include/o2345.h, O2345_AUDIT_*), and its doubles
+AUDIT_COUNTS = ("vertices", "edges", "faces", "repeated_faces", "zero_area_faces", "boundary_edges", "nonmanifold_edges", "inconsistent_edges", "creased_edges",
+                "boundary_vertices", "nonmanifold_vertices", "bowtie_vertices", "unused_vertices")
+
+
+def _cross3(a, b):
+    return np.stack([a[..., 1] * b[..., 2] - a[..., 2] * b[..., 1], a[..., 2] * b[..., 0] - a[..., 0] * b[..., 2],
+                     a[..., 0] * b[..., 1] - a[..., 1] * b[..., 0]], -1)
+
+
+def audit_triangles(P0, P1, P2):
+    """The per-triangle arithmetic of the audit (csrc/mesh_audit_math.h, au_triangle) on corner arrays [..., 3] -> dict(n, nn, area, vol, l, s, q): n = (P1 -
+    P0) x (P2 - P0), nn = n . n, area = 0.5 sqrt(nn), vol = P0 . (P1 x P2), l = the squared lengths of P0P1, P1P2, P2P0, s = (l01 + l12) + l20, q = (4
+    sqrt(3) area) / s, 0 where s == 0."""
+    P0, P1, P2 = (np.asarray(P, np.float64) for P in (P0, P1, P2))
+    with np.errstate(all="ignore"):                                     # products may overflow or underflow: the results are IEEE's either way
+        n = _cross3(P1 - P0, P2 - P0)
+        nn = _dot3(n, n)
+        area = 0.5 * np.sqrt(nn)
+        vol = _dot3(P0, _cross3(P1, P2))
+        e = (P1 - P0, P2 - P1, P0 - P2)
+        l = np.stack([_dot3(x, x) for x in e], -1)
+        s = (l[..., 0] + l[..., 1]) + l[..., 2]
+        q = np.where(s == 0.0, 0.0, (AUDIT_QUALITY_SCALE * area) / np.where(s == 0.0, 1.0, s))
+    return {"n": n, "nn": nn, "area": area, "vol": vol, "l": l, "s": s, "q": q}
+
+
+def audit_bins(q):
+    """Histogram bin of every quality: min(9, floor(q 10)), -1 for a q that is not >= 0 (it enters no bin and no minimum)"""
+    q = np.asarray(q, np.float64)
+    ok = q >= 0.0
+    with np.errstate(invalid="ignore"):
+        b = np.minimum(float(AUDIT_BINS - 1), np.floor(np.where(ok, q, 0.0) * 10.0))
+    return np.where(ok, b, -1.0).astype(np.int64)
+
+
+def audit_report(counts, histogram, area, volume6, quality_sum, quality_min, edge2_min, edge2_max, components):
+    """The raw results of an audit -> its report: what mesh_audit and ops.mesh_audit both return.  ``counts``: {name: int} over AUDIT_COUNTS; the doubles
+    as the device's stats block holds them (sum of the volume terms, squared edge lengths).  Derived: euler = used vertices - edges + faces; watertight =
+    no boundary, non-manifold or inconsistent edge, no bow-tie, no repeated triangle, at least one face; oriented = no inconsistent edge; genus =
+    components - euler / 2 when watertight, else None; the quality and edge-length entries are None without a face."""
+    import math
+    out = {k: int(counts[k]) for k in AUDIT_COUNTS}
+    faces = out["faces"]
+    out["histogram"] = [int(x) for x in histogram]
+    out["area"], out["volume"] = float(area), float(volume6) / 6.0
+    out["quality_mean"] = float(quality_sum) / faces if faces else None
+    out["quality_min"] = float(quality_min) if faces else None
+    out["edge_min"] = math.sqrt(float(edge2_min)) if faces else None
+    out["edge_max"] = math.sqrt(float(edge2_max)) if faces else None
+    out["euler"] = out["vertices"] - out["edges"] + faces
+    out["components"] = int(components)
+    out["oriented"] = out["inconsistent_edges"] == 0
+    out["watertight"] = bool(faces > 0 and out["boundary_edges"] == 0 and out["nonmanifold_edges"] == 0 and out["inconsistent_edges"] == 0
+                             and out["bowtie_vertices"] == 0 and out["repeated_faces"] == 0)
+    genus = out["components"] - out["euler"] / 2 if out["watertight"] else None
+    out["genus"] = int(genus) if genus is not None and genus == int(genus) else genus
+    return out
+
+
+def mesh_audit(verts, faces, return_elements=False):
+    """Audit of an indexed triangle mesh on the host (the twin of ops.mesh_audit, and the definition of its result): is it a closed, oriented 2-manifold,
+    and how good are its triangles.  verts [N,3] (float64), faces int32 / int64 [M,3]; an index outside [0, N) and a non-finite coordinate are errors.
+    Triangles: one with two equal indices is REPEATED -- counted, flagged, and no part of anything else; the others are the faces, with audit_triangles'
+    normal, area, volume term and quality; zero-area iff n . n == 0.  Edges: half-edge 3 t + i runs from faces[t, i] to faces[t, (i + 1) % 3]; an undirected
+    edge with m half-edges is boundary (m = 1), manifold (2) or non-manifold (>= 3); a manifold edge is inconsistent iff both half-edges run the same way,
+    and a manifold, consistent edge whose triangles both have n . n > 0 is creased iff n . n' < 0 (a symptom, not an error: a tetrahedron's acute edges
+    are creased).  Vertices: used (on a face), boundary (on a boundary edge), non-manifold (on an edge with m >= 3).  Fans: over the corners of the faces,
+    every manifold edge joins, at each of its two ends, the corners of its two triangles; a vertex with two or more classes of corners that lies on no
+    non-manifold edge is a bow-tie.  -> audit_report's dict: the counts of AUDIT_COUNTS, "histogram" (ten bins of quality), "area", "volume" (sum of the
+    volume terms / 6: meaningful for a closed, consistent mesh), "quality_mean", "quality_min", "edge_min", "edge_max", "euler", "components" (the labels
+    of component_labels that own a triangle), "oriented", "watertight", "genus".  The three sums are math.fsum's (the device sums in a fixed tree; they
+    agree to 1e-12 of the sum of the terms' magnitudes).  ``return_elements`` adds "vertex_flags" uint8 [N] (AUDIT_VERTEX_BITS), "face_flags" uint8 [M]
+    (AUDIT_FACE_BITS) and "quality" float64 [M] (0 for a repeated triangle).  Nothing depends on face order or on the rotation of a triangle's indices."""
+    import math
+    p = np.ascontiguousarray(np.asarray(verts, dtype=np.float64).reshape(-1, 3))
+    f = np.asarray(faces).reshape(-1, 3).astype(np.int64, copy=False)
+    nv, nt = p.shape[0], f.shape[0]
+    if nv >= 2 ** 30 or 6 * nt >= 2 ** 31:
+        raise ValueError(f"mesh_audit: bad sizes ({nv} vertices, {nt} faces; the tables are int32)")
+    if f.size and (f.min() < 0 or f.max() >= nv):
+        raise ValueError(f"mesh_audit: faces index outside 0 .. {nv - 1}")
+    if not np.isfinite(p).all():
+        raise ValueError("mesh_audit: non-finite vertex coordinate")
+    VB, FB = AUDIT_VERTEX_BITS, AUDIT_FACE_BITS
+    repeated = (f[:, 0] == f[:, 1]) | (f[:, 1] == f[:, 2]) | (f[:, 0] == f[:, 2])
+    live = np.flatnonzero(~repeated)                                    # the faces, ascending
+    F = f[live]
+    T = audit_triangles(p[F[:, 0]], p[F[:, 1]], p[F[:, 2]])
+    face_flags = np.zeros(nt, np.uint8)
+    face_flags[repeated] = FB["repeated"]
+    zero = T["nn"] == 0.0
+    face_flags[live[zero]] |= FB["zero_area"]
+    quality = np.zeros(nt, np.float64)
+    quality[live] = T["q"]
+    bins = audit_bins(T["q"])
+    # half-edges of the faces: id 3 t + i, from u to w
+    hid = (3 * live[:, None] + np.arange(3)[None, :]).reshape(-1)
+    u, w = F.reshape(-1), F[:, [1, 2, 0]].reshape(-1)
+    key, forward = np.minimum(u, w) * max(nv, 1) + np.maximum(u, w), u < w
+    _, edge, m = np.unique(key, return_inverse=True, return_counts=True)
+    edge = edge.reshape(-1)
+    n_edges = m.size
+    n_forward = np.bincount(edge, weights=forward, minlength=n_edges).astype(np.int64)
+    order = np.argsort(edge, kind="stable")                              # half-edges grouped by edge, ascending id inside
+    start = np.cumsum(m) - m
+    is_boundary, is_manifold, is_nonmanifold = m == 1, m == 2, m >= 3
+    inconsistent = is_manifold & (n_forward != 1)
+    h1, h2 = order[start[is_manifold]], order[start[is_manifold] + 1]    # positions (in the half-edge arrays) of a manifold edge's two half-edges
+    t1, t2 = h1 // 3, h2 // 3                                            # positions among the faces
+    consistent = n_forward[is_manifold] == 1
+    with np.errstate(all="ignore"):
+        creased_m = consistent & (T["nn"][t1] > 0.0) & (T["nn"][t2] > 0.0) & (_dot3(T["n"][t1], T["n"][t2]) < 0.0)
+    creased = np.zeros(n_edges, bool)
+    creased[np.flatnonzero(is_manifold)[creased_m]] = True
+    for name, on in (("boundary", is_boundary), ("nonmanifold", is_nonmanifold), ("inconsistent", inconsistent), ("creased", creased)):
+        hit = on[edge].reshape(-1, 3).any(1)
+        face_flags[live[hit]] |= FB[name]
+    vbits = np.zeros(nv, np.uint8)
+    for name, on in (("boundary", is_boundary), ("nonmanifold", is_nonmanifold)):
+        sel = on[edge]
+        vbits[u[sel]] |= VB[name]
+        vbits[w[sel]] |= VB[name]
+    # fans: union-find over the corners 3 t + i (component_labels on degenerate "faces" (x, y, y): the pairs to join)
+    same = u[h1] == u[h2]                                                # both half-edges start at the same end
+    c1u, c1w = hid[h1], 3 * live[t1] + (h1 % 3 + 1) % 3                  # the corners of triangle 1 at u (its half-edge's start) and at w
+    c2s, c2e = hid[h2], 3 * live[t2] + (h2 % 3 + 1) % 3                  # the corners of triangle 2 at its half-edge's start and end
+    x = np.concatenate([c1u, c1w])
+    y = np.concatenate([np.where(same, c2s, c2e), np.where(same, c2e, c2s)])
+    root = component_labels(np.stack([x, y, y], 1), 3 * nt)
+    is_root = root[hid] == hid
+    fans = np.bincount(u[is_root], minlength=nv)
+    used = fans > 0
+    bowtie = (fans >= 2) & ((vbits & VB["nonmanifold"]) == 0)
+    vertex_flags = vbits | (bowtie * VB["bowtie"]).astype(np.uint8) | ((~used) * VB["unused"]).astype(np.uint8)
+    counts = {"vertices": np.count_nonzero(used), "edges": n_edges, "faces": live.size, "repeated_faces": np.count_nonzero(repeated),
+              "zero_area_faces": np.count_nonzero(zero), "boundary_edges": np.count_nonzero(is_boundary), "nonmanifold_edges": np.count_nonzero(is_nonmanifold),
+              "inconsistent_edges": np.count_nonzero(inconsistent), "creased_edges": np.count_nonzero(creased),
+              "boundary_vertices": np.count_nonzero(vbits & VB["boundary"]), "nonmanifold_vertices": np.count_nonzero(vbits & VB["nonmanifold"]),
+              "bowtie_vertices": np.count_nonzero(bowtie), "unused_vertices": np.count_nonzero(~used)}
+    binned = T["q"][bins >= 0]
+    out = audit_report(counts, np.bincount(bins[bins >= 0], minlength=AUDIT_BINS), math.fsum(T["area"]), math.fsum(T["vol"]), math.fsum(T["q"]),
+                       binned.min() if binned.size else np.inf, T["l"].min() if live.size else np.inf, T["l"].max() if live.size else 0.0,
+                       np.unique(component_labels(f, nv)[f[:, 0]]).size)
+    if return_elements:
+        out.update(vertex_flags=vertex_flags, face_flags=face_flags, quality=quality)
+    return out

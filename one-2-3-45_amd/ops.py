@@ -1279,6 +1279,65 @@ def mesh_distance(va, ta, vb, tb, spacing=None, thresholds=(), return_samples=Fa
     return out
 
 
+# ---------------------------------------------------------------------------------------------------------- mesh audit
+_audit_names = {}
+# mesh_io.AUDIT_COUNTS -> the entry of the stats block that holds it
+_AUDIT_ENTRY = {"vertices": "VERTICES", "edges": "EDGES", "faces": "FACES", "repeated_faces": "REPEATED", "zero_area_faces": "ZERO_AREA",
+                "boundary_edges": "BOUNDARY_EDGES", "nonmanifold_edges": "NONMANIFOLD_EDGES", "inconsistent_edges": "INCONSISTENT_EDGES",
+                "creased_edges": "CREASED_EDGES", "boundary_vertices": "BOUNDARY_VERTICES", "nonmanifold_vertices": "NONMANIFOLD_VERTICES",
+                "bowtie_vertices": "BOWTIE_VERTICES", "unused_vertices": "UNUSED_VERTICES"}
+
+
+def _audit_stats_index():
+    """The names of o2345_mesh_audit's stats block (include/o2345.h, the O2345_AUDIT_* enumerators) -> {name: value}, read from the header's own text
+    once: the block is declared there and nowhere else."""
+    if not _audit_names:
+        import re
+        _audit_names.update({k: int(v) for k, v in re.findall(r"O2345_AUDIT_(\w+) = (\d+)", open(_lib.HEADER).read())})
+    return _audit_names
+
+
+def audit_info(stats, nv, components):
+    """The stats block of o2345_mesh_audit (int64, on the host) and the number of components that own a triangle -> the report of mesh_io.mesh_audit
+    (mesh_io.audit_report, shared with the twin).  ``components``: a number, or a function that returns it -- called after the two refusals.  Raises on a
+    triangle index out of range or a non-finite coordinate."""
+    ix = _audit_stats_index()
+    st = [int(x) for x in stats]
+    if st[ix["BAD_INDEX"]]:
+        raise RuntimeError(f"o2345 mesh_audit: {st[ix['BAD_INDEX']]} triangles index outside 0 .. {nv - 1}")
+    if st[ix["NONFINITE"]]:
+        raise RuntimeError(f"o2345 mesh_audit: {st[ix['NONFINITE']]} vertices have a non-finite coordinate")
+    dbl = lambda name: _double_of_bits(st[ix[name]] & 0xFFFFFFFFFFFFFFFF)
+    return mesh_io.audit_report({k: st[ix[e]] for k, e in _AUDIT_ENTRY.items()}, st[ix["HISTOGRAM"]:ix["HISTOGRAM"] + mesh_io.AUDIT_BINS], dbl("AREA_BITS"),
+                                dbl("VOLUME6_BITS"), dbl("QUALITY_SUM_BITS"), dbl("QUALITY_MIN_BITS"), dbl("EDGE2_MIN_BITS"), dbl("EDGE2_MAX_BITS"),
+                                components() if callable(components) else components)
+
+
+@_on_device
+def mesh_audit(verts, tris, return_elements=False):
+    """Audit of a mesh on the device (== mesh_io.mesh_audit, its host twin and the definition: counts, flags, quality, minima and maxima to the last bit,
+    the three sums to 1e-12; csrc/mesh_audit.hip): is it a closed, oriented 2-manifold, and how good are its triangles.  verts fp64 [N,3], tris [M,3]
+    int32 / int64, both only read -> the twin's dict (counts of used vertices, edges, faces, of repeated and zero-area triangles, of boundary,
+    non-manifold, inconsistent and creased edges, of boundary, non-manifold, bow-tie and unused vertices; "histogram", "area", "volume", "quality_mean",
+    "quality_min", "edge_min", "edge_max", "euler", "components", "oriented", "watertight", "genus").  One device-to-host copy, of the stats block;
+    "components" comes from the component unit (ops.mesh_component_labels' pass, which synchronises once more).  ``return_elements`` adds the device
+    tensors "vertex_flags" uint8 [N], "face_flags" uint8 [M] and "quality" fp64 [M].  Raises on an index out of range or a non-finite coordinate."""
+    tris, ib = _triangles(tris, "mesh_audit")
+    _vertices(verts, "mesh_audit")
+    nv, nt, dev = verts.shape[0], tris.shape[0], verts.device
+    ws, wsb = _scratch("o2345_mesh_audit_workspace_bytes", (nv, nt), dev, "mesh_audit")
+    if not wsb:
+        raise ValueError(f"mesh_audit: bad sizes ({nv} vertices, {nt} triangles; the tables are int32)")
+    stats = torch.empty(_audit_stats_index()["STATS"], dtype=torch.int64, device=dev)
+    vf, ff, q = (torch.empty(n, dtype=dt, device=dev) for n, dt in ((nv, torch.uint8), (nt, torch.uint8), (nt, torch.float64))) if return_elements else (None,) * 3
+    call("o2345_mesh_audit", verts, tris, ib, nv, nt, ws, wsb, stats, vf, ff, q)
+    # the components with at least one triangle: the selection count of the component unit at min_faces = 1
+    out = audit_info(stats.cpu().numpy(), nv, lambda: _mesh_components_count(tris, nv, 1, False, None)[2])
+    if return_elements:
+        out.update(vertex_flags=vf, face_flags=ff, quality=q)
+    return out
+
+
 # ---------------------------------------------------------------------------------------------------------- texture atlas
 def _texture_mesh(verts_idx, tris, what):
     t = _triangles(tris, what)

@@ -345,6 +345,17 @@ def mesh_distance(a, b, spacing=None, thresholds=(), return_samples=False):
     return ops.mesh_distance(va, ta, vb, tb, spacing, thresholds, return_samples)
 
 
+@torch.no_grad()
+def mesh_audit(mesh, return_elements=False):
+    """Audit of a mesh on the device (ops.mesh_audit; definitions in mesh_io.mesh_audit, its host twin): ``mesh`` is a (verts [N,3], tris [M,3]) pair of
+    device tensors or host arrays -- host arrays are uploaded, to the device of the first device tensor of the pair, else the current one.  -> the twin's
+    dict: counts of open, non-manifold, inconsistent and creased edges, of bow-tie and unused vertices, "euler", "components", "watertight", "oriented",
+    "genus", "area", "volume", the quality histogram, mean and minimum, the shortest and the longest edge."""
+    dev = next((x.device for x in mesh if torch.is_tensor(x) and x.is_cuda), None)
+    dev = torch.device("cuda", torch.cuda.current_device()) if dev is None else dev
+    return ops.mesh_audit(*_device_mesh(mesh, dev), return_elements)
+
+
 def _surface_view(wt, vol, proj, cam_pos, u, flags, intrinsic, c2w, H, W, near, far, stride, refine, background):
     """one image of render_surface from a lattice and its brick flags"""
     dev = u.device
@@ -417,7 +428,7 @@ def _write_previews(wt, vol, proj, cam_pos, u, s, n, folder):
 @torch.no_grad()
 def reconstruct_folder(root_dir, name, wt, out_ply, D=96, resolution=256, render_val_image=False, output_format=None, min_component_faces=None,
                        keep_largest=None, smooth_iterations=None, decimate_cell=None, project_iterations=None, texture_texel=None, preview_views=None, mesh_error=None,
-                       simplify_faces=None):
+                       simplify_faces=None, mesh_audit=None):
     """run.py's reconstruction stage without the reference tree: Zero123-style folder (dataset.SceneFolder) -> coloured mesh (binary PLY in
     the original frame), optionally the val image of the target view.  ``output_format`` ".obj" / ".glb" (run.py --output_format) also writes
     ``mesh<ext>`` next to ``out_ply`` in the asset frame, from the same device buffers.  The mesh options are extract_mesh's.  Returns
@@ -432,7 +443,10 @@ def reconstruct_folder(root_dir, name, wt, out_ply, D=96, resolution=256, render
     "previews" is the list of {path, color, normal, depth, c2w}.  ``mesh_error`` (None: the config default O2345_MESH_ERROR, off: nothing is launched and
     the result has no new key): the result gains "mesh_error", mesh_distance between the final mesh (A) and the raw marching-cubes mesh before the
     clean-up chain (B, extracted again from the same lattice), in index coordinates -- units of the extraction grid's spacing -- with samples every 0.5
-    and thresholds 0.25, 0.5, 1 and 2.  "a_to_b" is the geometric error of what was kept; "b_to_a" also contains whatever the component filter dropped."""
+    and thresholds 0.25, 0.5, 1 and 2.  "a_to_b" is the geometric error of what was kept; "b_to_a" also contains whatever the component filter dropped.
+    ``mesh_audit`` (None: the config default O2345_MESH_AUDIT, off: nothing is launched and the result has no new key): the result gains "mesh_audit",
+    the report of ops.mesh_audit on the final mesh in index coordinates -- is it a closed, oriented 2-manifold, and how good are its triangles; area and
+    volume in units of the extraction grid's spacing."""
     import os
     from . import dataset, mesh_io
     if output_format not in (None, ".ply", ".obj", ".glb"):
@@ -458,6 +472,8 @@ def reconstruct_folder(root_dir, name, wt, out_ply, D=96, resolution=256, render
     if config.mesh_error(mesh_error):
         raw_verts, raw_tris = ops.marching_cubes(m.u, 0.0)                # what _mesh_fields meshed before its clean-up chain: the same lattice, the same bits
         out["mesh_error"] = ops.mesh_distance(m.verts_idx, m.tris, raw_verts, raw_tris, MESH_ERROR_SPACING, MESH_ERROR_THRESHOLDS)
+    if config.mesh_audit(mesh_audit):
+        out["mesh_audit"] = ops.mesh_audit(m.verts_idx, m.tris)
     if previews:
         out["previews"] = _write_previews(wt, vol, proj, cam_pos, m.u, s, previews, os.path.dirname(str(out_ply)))
     if render_val_image:

@@ -1,0 +1,203 @@
+"""GPU: the mesh audit (csrc/mesh_audit.hip) against the host twin (mesh_io.mesh_audit), which defines the result.  Counts, histogram, flags, per-triangle
+quality, minima and maxima are compared EXACTLY (bytes); the three sums within 1e-12 of the sum of their terms' magnitudes (the twin sums with math.fsum,
+the device in a fixed tree).  Expected values are the twin applied to the same inputs, never the code under test; a twin result is computed once per mesh."""
+import importlib
+
+import numpy as np
+import pytest
+import torch
+
+import mesh_audit_util as U
+from guard_util import PRE, Guard
+from mesh_scene_util import args as _args, dev, dev_tris as _dev_tris, stored_scene  # noqa: F401 (dev: a fixture)
+
+pytestmark = pytest.mark.gpu
+
+ops = importlib.import_module("one-2-3-45_amd.ops")
+mio = importlib.import_module("one-2-3-45_amd.mesh_io")
+config = importlib.import_module("one-2-3-45_amd.config")
+pipeline = importlib.import_module("one-2-3-45_amd.pipeline")
+_lib = importlib.import_module("one-2-3-45_amd._lib")
+
+N_STATS = 32                                                            # include/o2345.h: O2345_AUDIT_STATS
+ELEMENTS = ("vertex_flags", "face_flags", "quality")
+_twins = {}
+
+
+def _twin(key, hv, hf):
+    if key not in _twins:
+        want = mio.mesh_audit(hv, hf, return_elements=True)
+        _twins[key] = (want, U.sum_bounds(want, np.asarray(hv, np.float64).reshape(-1, 3), np.asarray(hf).reshape(-1, 3)))
+    return _twins[key]
+
+
+def _host(out):
+    return {k: x.cpu().numpy() if torch.is_tensor(x) else x for k, x in out.items()}
+
+
+def _check(key, hv, hf, dev, dtype):
+    """ops.mesh_audit == the twin; the inputs are only read -> the twin's report"""
+    hv = np.array(hv, np.float64).reshape(-1, 3)                          # a copy: the shared meshes are read-only
+    verts, tris = torch.from_numpy(hv).to(dev), _dev_tris(hf, dev, dtype)
+    tris0 = tris.clone()
+    got = ops.mesh_audit(verts, tris, return_elements=True)
+    assert all(got[k].is_cuda for k in ELEMENTS)
+    want, bounds = _twin(key, hv, hf)
+    U.assert_equal_reports(_host(got), want, bounds)
+    plain = ops.mesh_audit(verts, tris)
+    assert set(plain) == set(want) - set(ELEMENTS) and all(plain[k] == got[k] for k in plain)
+    assert verts.cpu().numpy().tobytes() == hv.tobytes() and torch.equal(tris, tris0)
+    return want
+
+
+@pytest.mark.parametrize("dtype", [torch.int32, torch.int64])
+def test_every_mesh_equals_the_twin(dev, dtype):
+    """the table's hand meshes, the defects, the torus, nt = 0, 1, 255, 256, 257, fan(300) (a 300-corner class: deep union chains) and the relabelled cube
+    (other probe collisions)"""
+    for name, (v, f) in U.meshes().items():
+        want = _check(name, v, f, dev, dtype)
+        if name in U.TABLE:
+            assert tuple(want[k] for k in U.TABLE_KEYS) == U.TABLE[name]
+    assert _twin("fan300", *U.meshes()["fan300"])[0]["creased_edges"] == 300 and _twin("grid_nt257", *U.meshes()["grid_nt257"])[0]["bowtie_vertices"] == 1
+
+
+@pytest.fixture(scope="module")
+def scene(dev):
+    S = stored_scene(dev)
+    assert S["hf"].shape[0] > 100
+    dv, dt, _, _ = pipeline.extract_mesh(*_args(S), return_index_verts=True, decimate_cell=2)
+    return dict(S, dv=dv.cpu().numpy(), df=dt.cpu().numpy())
+
+
+@pytest.mark.parametrize("dtype", [torch.int32, torch.int64])
+def test_the_stored_scene_before_and_after_clustering(scene, dtype):
+    dev = scene["plain"][0].device
+    raw = _check("scene", scene["hv"], scene["hf"], dev, dtype)
+    dec = _check("scene_decimated", scene["dv"], scene["df"], dev, dtype)
+    assert raw["faces"] == scene["hf"].shape[0] and dec["faces"] == scene["df"].shape[0] < raw["faces"] and raw["repeated_faces"] == 0
+
+
+def _raw(dev, hv, hf, dtype, g=None, outputs=(True, True, True), stream=None):
+    """o2345_mesh_audit itself, every buffer at its exact size (inside guard bands when ``g`` is given) -> (stats int64 [32], vertex_flags, face_flags,
+    quality) as numpy, None for an output that was not asked for"""
+    nv, nt = hv.shape[0], hf.shape[0]
+    ib = 8 if dtype == torch.int64 else 4
+    verts, tris = torch.from_numpy(np.array(hv, np.float64)).to(dev), _dev_tris(hf, dev, dtype)
+    wsb = _lib.call("o2345_mesh_audit_workspace_bytes", nv, nt)
+    assert wsb > 0 and PRE % 16 == 0
+    new = (lambda n, what: g.buf(n, (what, nv, nt))) if g else (lambda n, what: torch.full((n,), 0xA5, dtype=torch.uint8, device=dev))
+    ws, stats = new(wsb, "workspace"), new(8 * N_STATS, "stats").view(torch.int64)
+    vf, ff, q = (new(n, what) if on else None for on, n, what in zip(outputs, (nv, nt, 8 * nt), ELEMENTS))
+    torch.cuda.synchronize()                                              # the buffers were filled on the current stream
+    with torch.cuda.stream(stream):
+        _lib.call("o2345_mesh_audit", verts, tris, ib, nv, nt, ws, wsb, stats, vf, ff, None if q is None else q.view(torch.float64))
+    torch.cuda.synchronize()
+    assert verts.cpu().numpy().tobytes() == np.ascontiguousarray(hv, np.float64).tobytes() and np.array_equal(tris.cpu().numpy(), hf)
+    h = lambda t, d: None if t is None else t.cpu().numpy().view(d)
+    return h(stats, np.int64), h(vf, np.uint8), h(ff, np.uint8), h(q, np.float64)
+
+
+GUARDED = ("defects", "three_on_an_edge", "two_tetrahedra", "cube10_relabelled", "fan300", "grid_nt0", "grid_nt1", "grid_nt255", "grid_nt256", "grid_nt257")
+
+
+@pytest.mark.parametrize("dtype", [torch.int32, torch.int64])
+def test_no_kernel_writes_outside_its_buffers(dev, dtype):
+    g = Guard(dev)
+    for name in GUARDED:
+        v, f = U.meshes()[name]
+        stats, vf, ff, q = _raw(dev, v, f, dtype, g)
+        bad = g.damaged()
+        assert not bad, bad
+        want, bounds = _twin(name, v, f)
+        got = dict(ops.audit_info(stats, v.shape[0], want["components"]), vertex_flags=vf, face_flags=ff, quality=q)
+        U.assert_equal_reports(got, want, bounds)
+    assert len(g.live) == 5 * len(GUARDED)
+
+
+def test_two_runs_and_a_second_stream_give_identical_bytes(dev, scene):
+    side = torch.cuda.Stream(device=dev)
+    for hv, hf in ((scene["dv"], scene["df"]), U.meshes()["fan300"], U.meshes()["defects"]):
+        runs = [[None if x is None else x.tobytes() for x in _raw(dev, hv, hf, torch.int64, stream=s)] for s in (None, None, side)]
+        assert runs[0] == runs[1] == runs[2] and len(runs[0][0]) == 8 * N_STATS
+
+
+def test_every_optional_output_may_be_null(dev):
+    v, f = U.meshes()["defects"]
+    full = _raw(dev, v, f, torch.int32)
+    for k in range(3):
+        outputs = tuple(i != k for i in range(3))
+        got = _raw(dev, v, f, torch.int32, outputs=outputs)
+        assert got[1 + k] is None and all(np.array_equal(a, b) for i, (a, b) in enumerate(zip(got, full)) if i != 1 + k)
+    none = _raw(dev, v, f, torch.int32, outputs=(False, False, False))
+    assert np.array_equal(none[0], full[0]) and none[1:] == (None, None, None)
+
+
+def test_refusals_are_statuses_not_faults(dev):
+    """counted on the device, raised on the host after the one copy; the input is not written, and the next call works"""
+    v, f = U.meshes()["fan40"]
+    good, tris = torch.from_numpy(v.copy()).to(dev), _dev_tris(f, dev, torch.int64)
+    for bad in (float("nan"), float("inf"), float("-inf")):
+        w = good.clone()
+        w[2, 1] = bad
+        w0 = w.clone()
+        with pytest.raises(RuntimeError, match="non-finite"):
+            ops.mesh_audit(w, tris)
+        assert torch.equal(w.view(torch.int64), w0.view(torch.int64))
+    for bad in (v.shape[0], -1, 2 ** 31 + 1):
+        for dtype in (torch.int64, torch.int32):
+            if dtype == torch.int32 and bad > 2 ** 31:
+                continue
+            t = tris.clone()
+            t[1, 2] = bad
+            t = t.to(dtype)
+            t0 = t.clone()
+            with pytest.raises(RuntimeError, match="index outside"):
+                ops.mesh_audit(good, t)
+            assert torch.equal(t, t0)
+    with pytest.raises(ValueError):
+        ops.mesh_audit(good, tris.float())
+    with pytest.raises(ValueError):
+        ops.mesh_audit(good.float(), tris)
+    # the C ABI itself: null pointers, a short workspace, bad sizes
+    nv, nt = v.shape[0], f.shape[0]
+    size = lambda a, b: _lib.call("o2345_mesh_audit_workspace_bytes", a, b)
+    wsb = size(nv, nt)
+    assert wsb > 0 and size(2 ** 30, 0) == 0 and size(-1, 0) == 0 and size(0, -1) == 0 and size(0, 2 ** 31 // 6 + 1) == 0 and size(0, 0) > 0
+    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    stats = torch.empty(N_STATS, dtype=torch.int64, device=dev)
+    for a, what in (((None, tris, 8, nv, nt, ws, wsb, stats), "null pointer"), ((good, None, 8, nv, nt, ws, wsb, stats), "null pointer"),
+                    ((good, tris, 8, nv, nt, None, wsb, stats), "null pointer"), ((good, tris, 8, nv, nt, ws, wsb, None), "null pointer"),
+                    ((good, tris, 8, nv, nt, ws, wsb - 1, stats), "workspace too small"), ((good, tris, 2, nv, nt, ws, wsb, stats), "index_bytes"),
+                    ((good, tris, 8, 2 ** 30, nt, ws, wsb, stats), "bad sizes")):
+        with pytest.raises(RuntimeError, match=what):
+            _lib.call("o2345_mesh_audit", *a, None, None, None)
+    _check("fan40", v, f, dev, torch.int64)
+
+
+def test_pipeline_report_is_there_when_on_and_nothing_runs_when_off(tmp_path, dev, monkeypatch):
+    ds = importlib.import_module("one-2-3-45_amd.dataset")
+    ds.write_synthetic_folder(str(tmp_path), "shape", seed=1)
+    wt = pipeline.SceneWeights(dev, seed=0)
+    on = pipeline.reconstruct_folder(str(tmp_path), "shape", wt, str(tmp_path / "a.ply"), D=48, resolution=64, mesh_audit=True)
+    s = ds.SceneFolder(str(tmp_path), "export_mesh", specific_dataset_name="shape")[0]
+    T = lambda t: t.to(dev).contiguous().float()
+    vol = pipeline.build_volume(wt, T(s["images"]), T(s["affine_mats"]), s["partial_vol_origin"].numpy(), 48, 2.0 / 47)
+    proj, cam_pos = pipeline.camera_terms(T(s["intrinsics"]), T(s["w2cs"]))
+    v, t, _, _ = pipeline.extract_mesh(wt, vol, proj, cam_pos, 64, return_index_verts=True)
+    hv, hf = v.cpu().numpy(), t.cpu().numpy()
+    want = mio.mesh_audit(hv, hf, return_elements=True)
+    bounds = U.sum_bounds(want, hv, hf)
+    plain = {k: x for k, x in want.items() if k not in ELEMENTS}
+    assert on["triangles"] == plain["faces"] + plain["repeated_faces"] > 0
+    U.assert_equal_reports(on["mesh_audit"], plain, bounds)
+    U.assert_equal_reports(pipeline.mesh_audit((v, t)), plain, bounds)
+    U.assert_equal_reports(pipeline.mesh_audit((hv, hf.astype(np.int32))), plain, bounds)              # host arrays are uploaded
+    # off, which is the default: no key, and the audit's entries are not reached
+    assert config.MESH_AUDIT is False                                     # the environment of the test run leaves it unset
+    monkeypatch.setattr(ops, "mesh_audit", lambda *a, **k: pytest.fail("the audit must not run when it is off"))
+    real = _lib.call
+    monkeypatch.setattr(ops, "call", lambda name, *a: pytest.fail("the audit entry was reached") if "audit" in name else real(name, *a))
+    for kw in (dict(), dict(mesh_audit=None), dict(mesh_audit=False)):
+        off = pipeline.reconstruct_folder(str(tmp_path), "shape", wt, str(tmp_path / "b.ply"), D=48, resolution=64, **kw)
+        assert "mesh_audit" not in off and set(off) == set(on) - {"mesh_audit"} and all(off[k] == on[k] for k in off if k != "ply")
+        assert open(off["ply"], "rb").read() == open(on["ply"], "rb").read()
