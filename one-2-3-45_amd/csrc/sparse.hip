@@ -110,6 +110,11 @@ __global__ __launch_bounds__(256) void k_sparse_conv(const float* __restrict__ i
         if (r < 0) continue;
         const float4* src = reinterpret_cast<const float4*>(in + (size_t)r * CIN);
         const float* w = Wk + (size_t)k * CIN * COUT;
+        // one offset's CIN products are summed on their own and then added to the total: one chain of 27 * CIN fused multiply-adds per output
+        // accumulated 6.8 times the error of 27 per-offset float32 products (2.6e-5 at 64 -> 64 channels and outputs of 22)
+        float part[COUT];
+#pragma unroll
+        for (int o = 0; o < COUT; ++o) part[o] = 0.f;
 #pragma unroll
         for (int i4 = 0; i4 < CIN / 4; ++i4) {
             const float4 v = src[i4];
@@ -117,8 +122,10 @@ __global__ __launch_bounds__(256) void k_sparse_conv(const float* __restrict__ i
 #pragma unroll
             for (int u = 0; u < 4; ++u)
 #pragma unroll
-                for (int o = 0; o < COUT; ++o) acc[o] = fmaf(xv[u], w[(i4 * 4 + u) * COUT + o], acc[o]);
+                for (int o = 0; o < COUT; ++o) part[o] = fmaf(xv[u], w[(i4 * 4 + u) * COUT + o], part[o]);
         }
+#pragma unroll
+        for (int o = 0; o < COUT; ++o) acc[o] += part[o];
     }
     float4* dst = reinterpret_cast<float4*>(out + (size_t)q * COUT);
 #pragma unroll
