@@ -60,9 +60,12 @@ const char* o2345_last_error(void);
  * o2345_mesh_distance_query, o2345_mesh_distance_reduce_workspace_bytes, o2345_mesh_distance_reduce. */
 /* 220 = ABI 2.2: the four device stats blocks are declared structs (O2345ProjectStats, O2345TextureStats, O2345SurfaceStats, O2345DistanceStats; no byte
  * of them moved, the untyped `stats` parameters became pointers to them); o2345_struct_size / o2345_struct_layout describe every declared struct and replace
- * o2345_render_io_size / o2345_render_io_layout; the parameter of o2345_render_rays is called io_host.
- * Additive since 2.2 (the version stays 220): the simplification entries o2345_mesh_simplify_workspace_bytes, o2345_mesh_simplify_count,
- * o2345_mesh_simplify_emit; the audit entries o2345_mesh_audit_workspace_bytes, o2345_mesh_audit. */
+ * o2345_render_io_size / o2345_render_io_layout; the parameter of o2345_render_rays is called io_host. */
+/* 230 = ABI 2.3: the stats blocks of the simplification and of the audit are declared structs too (O2345SimplifyStats, O2345AuditStats; no byte of them
+ * moved, the `long long* stats` parameters became pointers to them); the positional enumerators that named their entries (O2345_SIMPLIFY_ROUNDS ... _STATS,
+ * O2345_AUDIT_*) are removed, the three stop codes O2345_SIMPLIFY_STOPPED_* stay.  Both units were additive since 2.2: the simplification entries
+ * o2345_mesh_simplify_workspace_bytes, o2345_mesh_simplify_count, o2345_mesh_simplify_emit; the audit entries o2345_mesh_audit_workspace_bytes,
+ * o2345_mesh_audit. */
 int o2345_version(void);
 /* Layout self-description of the declared structs as THIS library was compiled (sizeof, and offsetof of every field in declaration order): a binding
  * asserts its own structs against it at load time (one-2-3-45_amd/_lib.py does) -- a field added on one side only cannot corrupt calls silently.
@@ -450,43 +453,6 @@ int o2345_mesh_decimate_count(const double* verts, const void* tris, int index_b
 int o2345_mesh_decimate_emit(const double* verts, const void* tris, int index_bytes, long long nv, long long nt, void* workspace, double* verts_out,
                              void* tris_out, int* cluster, void* stream);
 
-/* ---- simplification by quadric-error edge collapse (additive since 2.2; the reference has no such step, its users simplify the mesh in another tool) ----
- * Rounds of independent half-edge collapses ordered by Garland - Heckbert's quadric error, subset placement: collapsing v -> u removes v, u keeps its
- * bits, positions never change.  Everything is fp64, one operation at a time, in the order written (csrc/mesh_simplify_math.h is the text); equal to
- * mesh_io.simplify_mesh to the last bit.  Triangle quadric, once, from the input: n = (P1 - P0) x (P2 - P0), nn = (nx nx + ny ny) + nz nz; nn > 0: s = 0.5 /
- * sqrt(nn), d = -((nx P0x + ny P0y) + nz P0z), the ten entries (a b) s over (nx, ny, nz, d); else zeros.  Q_v = the sequential entrywise sum over the
- * triangles of v in ascending face order; after a collapse Q_u <- Q_u + Q_v.  A round, on its live triangles, N(v) the adjacency row of v: the half-edge
- * v -> u is eligible iff (1) every edge at v has exactly two triangles (boundary vertices and vertices on non-manifold edges are never removed, though they
- * may be targets), (2) |N(v) & N(u)| = 2, (3) for every triangle at v without u the normal n' after replacing P_v by P_u has n . n' > 0 against the old
- * normal, (4) e = p^T (Q_v + Q_u) p at p = P_u is finite and cost = max(0, e) <= max_error.  Candidate of v: its eligible u of least cost, ties to the
- * smaller u.  With C candidates and need = ceil((live - target_faces) / 2): bin(cost) = the biased exponent field of the double, B = the smallest bin whose
- * cumulative count reaches max(1, min(8 need, ceil(C / 2))); the candidates with bin <= B take part, priority (splitmix64's finaliser of v + (round << 32),
- * v).  v is selected iff its priority is the smallest among the participants within graph distance 2; all selected collapses apply at once; triangles
- * with two equal corners are dropped; face order, corner order and orientation stay.  Stop: live <= target_faces (TARGET), no candidate (BLOCKED),
- * max_rounds rounds done (ROUNDS); the last round may go below the target.  A vertex is kept iff a kept triangle references it, in the old order; triangles
- * are renumbered by an exclusive scan.  Not done: optimal placement, boundary and non-manifold collapses, a valence cap, an exact hit of the target.
- * verts device fp64 [nv,3], tris device int32 / int64 [nt,3] (index_bytes 4 / 8), both only read; 0 <= nv < 2^30, 6 * nt < 2^31; target_faces >= 0;
- * max_error >= 0, infinity = no limit; max_rounds >= 0.  workspace: mesh_simplify_workspace_bytes(nv, nt) bytes (0 for bad sizes), 16-byte aligned.
- * stats: device int64 [O2345_SIMPLIFY_STATS + max_rounds], 8-byte aligned, written by count(): the entries named below, then the collapses of every round.
- * The caller reads the two sizes from it to allocate the outputs.  count() runs all rounds inside the workspace; it synchronises the stream once after
- * the input check and once per round.  Errors: bad arguments, a workspace that is too small, a non-finite coordinate, a triangle index outside [0, nv), a
- * triangle with a repeated index; the last three are counted on the device, never dereferenced.  emit() (same workspace, nv and nt, untouched in
- * between) writes verts_out device fp64 [vertices,3] (bit copies), tris_out [triangles,3] of width index_bytes, source device int32 [vertices] (new ->
- * old) and merged device int32 [nv] (the new index of the vertex each old vertex ended in, following the collapses, or -1); any of the four may be NULL. */
-enum {
-    O2345_SIMPLIFY_ROUNDS = 0,                          /* rounds that applied collapses */
-    O2345_SIMPLIFY_VERTICES = 1, O2345_SIMPLIFY_TRIANGLES = 2,          /* of the output */
-    O2345_SIMPLIFY_STOPPED = 3,                         /* one of the three codes below */
-    O2345_SIMPLIFY_MAX_COST_BITS = 4,                   /* the bit pattern of a non-negative double: the largest cost applied; 0 without a collapse */
-    O2345_SIMPLIFY_STATS = 8,                           /* entries 5 .. 7: 0; entry STATS + r: the collapses of round r */
-    O2345_SIMPLIFY_STOPPED_TARGET = 0, O2345_SIMPLIFY_STOPPED_BLOCKED = 1, O2345_SIMPLIFY_STOPPED_ROUNDS = 2
-};
-size_t o2345_mesh_simplify_workspace_bytes(long long nv, long long nt);
-int o2345_mesh_simplify_count(const double* verts, const void* tris, int index_bytes, long long nv, long long nt, long long target_faces, double max_error,
-                              int max_rounds, void* workspace, size_t workspace_bytes, long long* stats, void* stream);
-int o2345_mesh_simplify_emit(const double* verts, int index_bytes, long long nv, long long nt, void* workspace, double* verts_out, void* tris_out, int* source,
-                             int* merged, void* stream);
-
 /* ---- projection of the vertices onto a level set of the SDF (additive since 2.1; the reference has no such step: its marching-cubes vertices,
  * sparse_neus_renderer.py:907-937, lie on the zero set only as far as linear interpolation along a grid edge allows, and validate_colored_mesh,
  * trainer_generic.py:1309-1363, colours them where they are) ------------------------------------------------------------------------------------------
@@ -725,6 +691,43 @@ int o2345_mesh_distance_reduce(const double* d2, const int* nearest, const doubl
                                const double* verts, const void* tris, int index_bytes, long long nv, long long nt, void* workspace, size_t workspace_bytes,
                                O2345DistanceStats* stats, void* stream);
 
+/* ---- simplification by quadric-error edge collapse (additive since 2.2; the reference has no such step, its users simplify the mesh in another tool) ----
+ * Rounds of independent half-edge collapses ordered by Garland - Heckbert's quadric error, subset placement: collapsing v -> u removes v, u keeps its
+ * bits, positions never change.  Everything is fp64, one operation at a time, in the order written (csrc/mesh_simplify_math.h is the text); equal to
+ * mesh_io.simplify_mesh to the last bit.  Triangle quadric, once, from the input: n = (P1 - P0) x (P2 - P0), nn = (nx nx + ny ny) + nz nz; nn > 0: s = 0.5 /
+ * sqrt(nn), d = -((nx P0x + ny P0y) + nz P0z), the ten entries (a b) s over (nx, ny, nz, d); else zeros.  Q_v = the sequential entrywise sum over the
+ * triangles of v in ascending face order; after a collapse Q_u <- Q_u + Q_v.  A round, on its live triangles, N(v) the adjacency row of v: the half-edge
+ * v -> u is eligible iff (1) every edge at v has exactly two triangles (boundary vertices and vertices on non-manifold edges are never removed, though they
+ * may be targets), (2) |N(v) & N(u)| = 2, (3) for every triangle at v without u the normal n' after replacing P_v by P_u has n . n' > 0 against the old
+ * normal, (4) e = p^T (Q_v + Q_u) p at p = P_u is finite and cost = max(0, e) <= max_error.  Candidate of v: its eligible u of least cost, ties to the
+ * smaller u.  With C candidates and need = ceil((live - target_faces) / 2): bin(cost) = the biased exponent field of the double, B = the smallest bin whose
+ * cumulative count reaches max(1, min(8 need, ceil(C / 2))); the candidates with bin <= B take part, priority (splitmix64's finaliser of v + (round << 32),
+ * v).  v is selected iff its priority is the smallest among the participants within graph distance 2; all selected collapses apply at once; triangles
+ * with two equal corners are dropped; face order, corner order and orientation stay.  Stop: live <= target_faces (TARGET), no candidate (BLOCKED),
+ * max_rounds rounds done (ROUNDS); the last round may go below the target.  A vertex is kept iff a kept triangle references it, in the old order; triangles
+ * are renumbered by an exclusive scan.  Not done: optimal placement, boundary and non-manifold collapses, a valence cap, an exact hit of the target.
+ * verts device fp64 [nv,3], tris device int32 / int64 [nt,3] (index_bytes 4 / 8), both only read; 0 <= nv < 2^30, 6 * nt < 2^31; target_faces >= 0;
+ * max_error >= 0, infinity = no limit; max_rounds >= 0.  workspace: mesh_simplify_workspace_bytes(nv, nt) bytes (0 for bad sizes), 16-byte aligned.
+ * stats: device, sizeof(O2345SimplifyStats) + 8 * max_rounds bytes, 8-byte aligned, written by count(): the struct, then long long collapses[max_rounds],
+ * the collapses of every round.  The caller reads the two sizes from it to allocate the outputs.  count() runs all rounds inside the workspace; it
+ * synchronises the stream once after the input check and once per round.  Errors: bad arguments, a workspace that is too small, a non-finite coordinate, a triangle index outside [0, nv), a
+ * triangle with a repeated index; the last three are counted on the device, never dereferenced.  emit() (same workspace, nv and nt, untouched in
+ * between) writes verts_out device fp64 [vertices,3] (bit copies), tris_out [triangles,3] of width index_bytes, source device int32 [vertices] (new ->
+ * old) and merged device int32 [nv] (the new index of the vertex each old vertex ended in, following the collapses, or -1); any of the four may be NULL. */
+typedef struct O2345SimplifyStats {
+    long long rounds;                                   /* rounds that applied collapses */
+    long long vertices, triangles;                      /* of the output */
+    long long stopped;                                  /* one of the three codes below */
+    unsigned long long max_cost_bits;                   /* the bit pattern of a non-negative double: the largest cost applied; 0 without a collapse */
+    long long reserved[3];                              /* 0 */
+} O2345SimplifyStats;                                   /* behind it in the same buffer: long long collapses[max_rounds], entry r the collapses of round r */
+enum { O2345_SIMPLIFY_STOPPED_TARGET = 0, O2345_SIMPLIFY_STOPPED_BLOCKED = 1, O2345_SIMPLIFY_STOPPED_ROUNDS = 2 };        /* the values of `stopped` */
+size_t o2345_mesh_simplify_workspace_bytes(long long nv, long long nt);
+int o2345_mesh_simplify_count(const double* verts, const void* tris, int index_bytes, long long nv, long long nt, long long target_faces, double max_error,
+                              int max_rounds, void* workspace, size_t workspace_bytes, O2345SimplifyStats* stats, void* stream);
+int o2345_mesh_simplify_emit(const double* verts, int index_bytes, long long nv, long long nt, void* workspace, double* verts_out, void* tris_out, int* source,
+                             int* merged, void* stream);
+
 /* ---- audit of a mesh: manifoldness, orientation, element quality (additive since 2.2; none in the reference: its meshes are never checked) -------------
  * Read-only; equal to the host twin mesh_io.mesh_audit: integers, flags, quality, minima and maxima to the last bit, the three sums to 1e-12 of the sum of
  * their terms' magnitudes.  Everything is fp64, one operation at a time, in the order written (csrc/mesh_audit_math.h is the text), a dot product (x x + y y)
@@ -742,26 +745,26 @@ int o2345_mesh_distance_reduce(const double* d2, const int* nearest, const doubl
  *   sums       area = sum area_t, sum v_t (six times the volume of a closed, consistent mesh), sum q_t: every block folds its 256 triangles in a fixed
  *              tree, one block folds the rows; the same bits on every run, no floating-point atomics.  min q_t, min and max squared edge length over the
  *              faces' half-edges; without a face the two minima are +inf and the maximum is 0.
- * stats: device int64 [O2345_AUDIT_STATS], 8-byte aligned: the entries named below; *_BITS is the bit pattern of a double.  vertex_flags uint8 [nv]: bit 0
+ * stats: device, 8-byte aligned, written by this call.  vertex_flags uint8 [nv]: bit 0
  * boundary, 1 on a non-manifold edge, 2 bow-tie, 3 unused.  face_flags uint8 [nt]: bit 0 repeated, 1 zero-area, 2 has a boundary edge, 3 a non-manifold
  * edge, 4 an inconsistent edge, 5 a creased edge.  quality fp64 [nt]: 0 for a repeated triangle.  Any of the three may be NULL.  A triangle index outside
- * [0, nv) and a vertex with a non-finite coordinate are counted (BAD_INDEX, NONFINITE), never dereferenced; the caller reads the two counts and treats
+ * [0, nv) and a vertex with a non-finite coordinate are counted (bad_index, nonfinite), never dereferenced; the caller reads the two counts and treats
  * the rest as void when one is not 0.  workspace: mesh_audit_workspace_bytes(nv, nt) bytes (0 for bad sizes), 16-byte aligned.  No host synchronisation.
  * Not done: duplicate faces, per-component reports, dihedral statistics, any repair. */
-enum {
-    O2345_AUDIT_BAD_INDEX = 0, O2345_AUDIT_NONFINITE = 1,               /* triangles with an index outside [0, nv); vertices with a non-finite coordinate */
-    O2345_AUDIT_VERTICES = 2, O2345_AUDIT_EDGES = 3, O2345_AUDIT_FACES = 4,             /* used vertices, undirected edges, non-repeated triangles */
-    O2345_AUDIT_REPEATED = 5, O2345_AUDIT_ZERO_AREA = 6,
-    O2345_AUDIT_BOUNDARY_EDGES = 7, O2345_AUDIT_NONMANIFOLD_EDGES = 8, O2345_AUDIT_INCONSISTENT_EDGES = 9, O2345_AUDIT_CREASED_EDGES = 10,
-    O2345_AUDIT_BOUNDARY_VERTICES = 11, O2345_AUDIT_NONMANIFOLD_VERTICES = 12, O2345_AUDIT_BOWTIE_VERTICES = 13, O2345_AUDIT_UNUSED_VERTICES = 14,
-    O2345_AUDIT_HISTOGRAM = 16,                         /* entry 15: 0; entries 16 .. 25: the ten quality bins */
-    O2345_AUDIT_AREA_BITS = 26, O2345_AUDIT_VOLUME6_BITS = 27, O2345_AUDIT_QUALITY_SUM_BITS = 28,
-    O2345_AUDIT_QUALITY_MIN_BITS = 29, O2345_AUDIT_EDGE2_MIN_BITS = 30, O2345_AUDIT_EDGE2_MAX_BITS = 31,
-    O2345_AUDIT_STATS = 32
-};
+typedef struct O2345AuditStats {
+    unsigned long long bad_index, nonfinite;            /* triangles with an index outside [0, nv); vertices with a non-finite coordinate */
+    unsigned long long vertices, edges, faces;          /* used vertices, undirected edges, non-repeated triangles */
+    unsigned long long repeated_faces, zero_area_faces;
+    unsigned long long boundary_edges, nonmanifold_edges, inconsistent_edges, creased_edges;
+    unsigned long long boundary_vertices, nonmanifold_vertices, bowtie_vertices, unused_vertices;
+    unsigned long long reserved;                        /* 0 */
+    unsigned long long histogram[10];                   /* the ten quality bins */
+    double area, volume6, quality_sum;                  /* the three sums */
+    double quality_min, edge2_min, edge2_max;           /* the smallest quality, the smallest and the largest squared edge length */
+} O2345AuditStats;
 size_t o2345_mesh_audit_workspace_bytes(long long nv, long long nt);
 int o2345_mesh_audit(const double* verts, const void* tris, int index_bytes, long long nv, long long nt, void* workspace, size_t workspace_bytes,
-                     long long* stats, unsigned char* vertex_flags_or_null, unsigned char* face_flags_or_null, double* quality_or_null, void* stream);
+                     O2345AuditStats* stats, unsigned char* vertex_flags_or_null, unsigned char* face_flags_or_null, double* quality_or_null, void* stream);
 /* Load every code object of the library on the current device now (the HIP runtime loads a translation unit's kernels at its first launch: 5 - 60 ms
  * each for the units of this library, which otherwise land inside the first calls of a fresh process).  Launches nothing that touches user memory. */
 int o2345_preload(void);

@@ -15,7 +15,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 HEADER = os.path.join(os.path.dirname(HERE), "include", "o2345.h")
 LIB_PATH = os.environ.get("O2345_LIB") or os.path.join(HERE, "libo2345_hip.so")       # O2345_LIB: an A/B build variant (build.build_variant)
 
-ABI_VERSION = 220          # include/o2345.h: o2345_version()
+ABI_VERSION = 230         # include/o2345.h: o2345_version()
 
 _CT = {"int": ctypes.c_int, "float": ctypes.c_float, "long long": ctypes.c_longlong, "size_t": ctypes.c_size_t, "void": None, "double": ctypes.c_double,
        "unsigned long long": ctypes.c_ulonglong}
@@ -210,7 +210,7 @@ class RenderIO(ctypes.Structure):
             setattr(self, k, self._pointers[k](t))
 
 
-# every struct the header declares, in its order -> the Structure generated from its text (RenderIO, ProjectStats, TextureStats, SurfaceStats, DistanceStats)
+# every struct the header declares, in its order -> the Structure generated from its text (RenderIO and the six stats blocks)
 STRUCTS = {name: RenderIO if name == "O2345RenderIO" else type(name[5:], (ctypes.Structure,), {"_fields_": parse_struct(name)}) for name in struct_names()}
 
 

@@ -43,7 +43,7 @@ int preload_convnet();
 
 extern "C" {
 const char* o2345_last_error(void) { return o2345::g_err; }
-int o2345_version(void) { return 220; }     // 2.2: declared stats structs, o2345_struct_size / _layout; 2.1: segment_rays + weight_cull in O2345RenderIO; 2.0: see include/o2345.h (1.5: o2345_list_sort_by_visibility; 1.4: color stats, bf16 entry removed; 1.3: o2345_conv2d family; 1.2: t_rand)
+int o2345_version(void) { return 230; }     // 2.3: O2345SimplifyStats, O2345AuditStats; 2.2: declared stats structs, o2345_struct_size / _layout; 2.1: segment_rays + weight_cull in O2345RenderIO; 2.0: see include/o2345.h (1.5: o2345_list_sort_by_visibility; 1.4: color stats, bf16 entry removed; 1.3: o2345_conv2d family; 1.2: t_rand)
 
 int o2345_preload(void) {
     int e, bad = 0;
@@ -104,11 +104,21 @@ static const size_t off_surface[] = {F(hits), F(entry_hits), F(box_misses), F(mi
 #define S O2345DistanceStats
 static const size_t off_distance[] = {F(sum_w), F(sum_wd), F(sum_wd2), F(within), F(max_d2_bits), F(n), F(n_unmatched), F(n_degenerate), F(n_bad)};
 #undef S
+#define S O2345SimplifyStats
+static const size_t off_simplify[] = {F(rounds), F(vertices), F(triangles), F(stopped), F(max_cost_bits), F(reserved)};
+#undef S
+#define S O2345AuditStats
+static const size_t off_audit[] = {
+    F(bad_index), F(nonfinite), F(vertices), F(edges), F(faces), F(repeated_faces), F(zero_area_faces), F(boundary_edges), F(nonmanifold_edges),
+    F(inconsistent_edges), F(creased_edges), F(boundary_vertices), F(nonmanifold_vertices), F(bowtie_vertices), F(unused_vertices), F(reserved), F(histogram),
+    F(area), F(volume6), F(quality_sum), F(quality_min), F(edge2_min), F(edge2_max)};
+#undef S
 #undef F
 #define LAYOUT(type, off) {sizeof(type), off, (int)(sizeof off / sizeof off[0])}
 static const struct { size_t size; const size_t* off; int n; } layouts[] = {
     LAYOUT(O2345RenderIO, off_render_io), LAYOUT(O2345ProjectStats, off_project), LAYOUT(O2345TextureStats, off_texture),
-    LAYOUT(O2345SurfaceStats, off_surface), LAYOUT(O2345DistanceStats, off_distance)};
+    LAYOUT(O2345SurfaceStats, off_surface), LAYOUT(O2345DistanceStats, off_distance), LAYOUT(O2345SimplifyStats, off_simplify),
+    LAYOUT(O2345AuditStats, off_audit)};
 #undef LAYOUT
 static const int n_layouts = (int)(sizeof layouts / sizeof layouts[0]);
 

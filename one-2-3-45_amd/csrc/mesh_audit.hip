@@ -41,16 +41,17 @@ static_assert(sizeof(AuSlot) == 32, "a slot is 32 bytes");
 
 // The triangle pass counts per block, not into the stats block: a wave's atomic on one word runs at some 88 per microsecond, all waves of a launch
 // bidding for the same two cache lines made that pass seven times slower than its memory traffic.  Block b writes row b of three tables -- AU_COUNTS
-// integers, AU_BOUNDS ordered_bits, AU_SUMS doubles -- and one block folds the rows (k_au_final).  Column k of the integers is stats entry au_entry(k).
+// integers, AU_BOUNDS ordered_bits, AU_SUMS doubles -- and one block folds the rows (k_au_final).  Column k of the integers is word au_entry(k) of the stats.
 constexpr int AU_COUNTS = 9 + AU_BINS;                // bad index, repeated, faces, edges, boundary / non-manifold / inconsistent / creased edges, zero area, bins
 constexpr int AU_BOUNDS = 3;                          // smallest quality, smallest and largest squared edge length
+static_assert(sizeof(O2345AuditStats::histogram) / sizeof(unsigned long long) == AU_BINS, "the stats block holds one entry per bin");
 __device__ __forceinline__ int au_entry(int k) {
-    constexpr int entry[9] = {O2345_AUDIT_BAD_INDEX, O2345_AUDIT_REPEATED, O2345_AUDIT_FACES, O2345_AUDIT_EDGES, O2345_AUDIT_BOUNDARY_EDGES,
-                              O2345_AUDIT_NONMANIFOLD_EDGES, O2345_AUDIT_INCONSISTENT_EDGES, O2345_AUDIT_CREASED_EDGES, O2345_AUDIT_ZERO_AREA};
-    return k < 9 ? entry[k] : O2345_AUDIT_HISTOGRAM + (k - 9);
+#define AU_WORD(field) (int)(offsetof(O2345AuditStats, field) / sizeof(unsigned long long))
+    constexpr int entry[9] = {AU_WORD(bad_index), AU_WORD(repeated_faces), AU_WORD(faces), AU_WORD(edges), AU_WORD(boundary_edges),
+                              AU_WORD(nonmanifold_edges), AU_WORD(inconsistent_edges), AU_WORD(creased_edges), AU_WORD(zero_area_faces)};
+    return k < 9 ? entry[k] : AU_WORD(histogram) + (k - 9);
+#undef AU_WORD
 }
-
-__device__ __forceinline__ unsigned long long* au_counter(long long* st, int entry) { return (unsigned long long*)(st + entry); }
 
 // *counter += the threads of this 256-thread block with pred: one atomic per block (k_au_vertices: a few hundred blocks).  Every thread must call it.
 __device__ __forceinline__ void au_block_count(bool pred, int* lds /*[4]*/, unsigned long long* counter) {
@@ -70,7 +71,7 @@ __device__ __forceinline__ void au_load(const double* __restrict__ verts, int v,
 
 // one thread per slot / corner / vertex of whichever array is longest; stats is zero already (a memset in front)
 __global__ __launch_bounds__(256) void k_au_init(const double* __restrict__ verts, int nv, AuSlot* __restrict__ slots, long long cap, int* __restrict__ parent, long long nc,
-                                                 int* __restrict__ vbits, int* __restrict__ fans, long long* __restrict__ st) {
+                                                 int* __restrict__ vbits, int* __restrict__ fans, O2345AuditStats* __restrict__ st) {
     __shared__ int lds[4];
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i < cap) slots[i] = AuSlot{AU_EMPTY, 0ull, 0x7FFFFFFF, -1, {0, 0}};
@@ -80,7 +81,7 @@ __global__ __launch_bounds__(256) void k_au_init(const double* __restrict__ vert
         vbits[i] = 0; fans[i] = 0;
         nonfinite = !(finite(verts[3 * i]) && finite(verts[3 * i + 1]) && finite(verts[3 * i + 2]));
     }
-    if ((long long)blockIdx.x * 256 < nv) au_block_count(nonfinite, lds, au_counter(st, O2345_AUDIT_NONFINITE));       // block-uniform
+    if ((long long)blockIdx.x * 256 < nv) au_block_count(nonfinite, lds, &st->nonfinite);       // block-uniform
 }
 
 // one thread per triangle: its three half-edges into the table.  The probe is bounded by the capacity; the table is at most half full, so it ends at a
@@ -266,7 +267,7 @@ __global__ __launch_bounds__(256) void k_au_corners(const IDX* __restrict__ tris
 
 // one thread per vertex: classifies, counts, packs the flags
 __global__ __launch_bounds__(256) void k_au_vertices(int nv, const int* __restrict__ fans, const int* __restrict__ vbits, unsigned char* __restrict__ vertex_flags,
-                                                     long long* __restrict__ st) {
+                                                     O2345AuditStats* __restrict__ st) {
     __shared__ int lds[4];
     const long long v = (long long)blockIdx.x * 256 + threadIdx.x;
     int flags = 0;
@@ -279,17 +280,17 @@ __global__ __launch_bounds__(256) void k_au_vertices(int nv, const int* __restri
         if (!used) flags |= AU_V_UNUSED;
         if (vertex_flags) vertex_flags[v] = (unsigned char)flags;
     }
-    au_block_count(used, lds, au_counter(st, O2345_AUDIT_VERTICES));
-    au_block_count(flags & AU_V_BOUNDARY, lds, au_counter(st, O2345_AUDIT_BOUNDARY_VERTICES));
-    au_block_count(flags & AU_V_NONMANIFOLD, lds, au_counter(st, O2345_AUDIT_NONMANIFOLD_VERTICES));
-    au_block_count(flags & AU_V_BOWTIE, lds, au_counter(st, O2345_AUDIT_BOWTIE_VERTICES));
-    au_block_count(flags & AU_V_UNUSED, lds, au_counter(st, O2345_AUDIT_UNUSED_VERTICES));
+    au_block_count(used, lds, &st->vertices);
+    au_block_count(flags & AU_V_BOUNDARY, lds, &st->boundary_vertices);
+    au_block_count(flags & AU_V_NONMANIFOLD, lds, &st->nonmanifold_vertices);
+    au_block_count(flags & AU_V_BOWTIE, lds, &st->bowtie_vertices);
+    au_block_count(flags & AU_V_UNUSED, lds, &st->unused_vertices);
 }
 
 // one block folds the rows: thread i takes rows i, i + 256, ... in that order, then the block's tree (the doubles: a fixed one); the minima and the
 // maximum leave their ordered encoding
 __global__ __launch_bounds__(256) void k_au_final(const int* __restrict__ counts, const unsigned long long* __restrict__ bounds, const double* __restrict__ partials,
-                                                  long long rows, long long* __restrict__ st) {
+                                                  long long rows, O2345AuditStats* __restrict__ st) {
     __shared__ unsigned long long sc[4][AU_COUNTS], sb[4][AU_BOUNDS];
     double v[AU_SUMS] = {0.0, 0.0, 0.0};
     unsigned long long c[AU_COUNTS], q_min = ~0ull, l_min = ~0ull, l_max = 0ull;
@@ -313,17 +314,17 @@ __global__ __launch_bounds__(256) void k_au_final(const int* __restrict__ counts
     if (lane_id() == 0) { sb[wv][0] = q_min; sb[wv][1] = l_min; sb[wv][2] = l_max; }
     au_block_sums(v);                                                // its barrier covers sc and sb
     const int k = threadIdx.x;
-    if (k < AU_COUNTS) st[au_entry(k)] = (long long)((sc[0][k] + sc[1][k]) + (sc[2][k] + sc[3][k]));
+    if (k < AU_COUNTS) ((unsigned long long*)st)[au_entry(k)] = (sc[0][k] + sc[1][k]) + (sc[2][k] + sc[3][k]);
     if (k == 0) {
         for (int w = 1; w < 4; ++w) {
             q_min = sb[w][0] < q_min ? sb[w][0] : q_min; l_min = sb[w][1] < l_min ? sb[w][1] : l_min; l_max = sb[w][2] > l_max ? sb[w][2] : l_max;
         }
-        st[O2345_AUDIT_AREA_BITS] = __double_as_longlong(v[0]);
-        st[O2345_AUDIT_VOLUME6_BITS] = __double_as_longlong(v[1]);
-        st[O2345_AUDIT_QUALITY_SUM_BITS] = __double_as_longlong(v[2]);
-        st[O2345_AUDIT_QUALITY_MIN_BITS] = __double_as_longlong(q_min == ~0ull ? (double)INFINITY : ordered_double(q_min));
-        st[O2345_AUDIT_EDGE2_MIN_BITS] = __double_as_longlong(l_min == ~0ull ? (double)INFINITY : ordered_double(l_min));
-        st[O2345_AUDIT_EDGE2_MAX_BITS] = __double_as_longlong(l_max == 0ull ? 0.0 : ordered_double(l_max));
+        st->area = v[0];
+        st->volume6 = v[1];
+        st->quality_sum = v[2];
+        st->quality_min = q_min == ~0ull ? (double)INFINITY : ordered_double(q_min);
+        st->edge2_min = l_min == ~0ull ? (double)INFINITY : ordered_double(l_min);
+        st->edge2_max = l_max == 0ull ? 0.0 : ordered_double(l_max);
     }
 }
 
@@ -369,7 +370,7 @@ size_t o2345_mesh_audit_workspace_bytes(long long nv, long long nt) {
 }
 
 int o2345_mesh_audit(const double* verts, const void* tris, int index_bytes, long long nv, long long nt, void* workspace, size_t workspace_bytes,
-                     long long* stats, unsigned char* vertex_flags_or_null, unsigned char* face_flags_or_null, double* quality_or_null, void* stream) {
+                     O2345AuditStats* stats, unsigned char* vertex_flags_or_null, unsigned char* face_flags_or_null, double* quality_or_null, void* stream) {
     O2345_REQUIRE_INDEX_BYTES("mesh_audit", index_bytes);
     O2345_REQUIRE(au_sizes_ok(nv, nt), "mesh_audit: bad sizes (nv must stay below 2^30 and 6 * nt below 2^31)");
     O2345_REQUIRE(stats && (nv == 0 || verts) && (nt == 0 || tris), "mesh_audit: null pointer");
@@ -381,7 +382,7 @@ int o2345_mesh_audit(const double* verts, const void* tris, int index_bytes, lon
     const int n = (int)nv;
     const long long nc = 3 * nt;
     const long long longest = c.cap > nc ? (c.cap > nv ? c.cap : nv) : (nc > nv ? nc : nv);
-    O2345_HIP(hipMemsetAsync(stats, 0, O2345_AUDIT_STATS * sizeof(long long), s));
+    O2345_HIP(hipMemsetAsync(stats, 0, sizeof(O2345AuditStats), s));
     hipLaunchKernelGGL(k_au_init, dim3(cdiv(longest, 256)), dim3(256), 0, s, verts, n, c.slots, c.cap, c.parent, nc, c.vbits, c.fans, stats);
     if (nt > 0) with_index_type(index_bytes, tris, [&](auto* t) {
         using IDX = index_type<decltype(t)>;

@@ -291,12 +291,15 @@ __global__ __launch_bounds__(256) void k_sim_keep(const int* __restrict__ cur, l
 }
 
 // the head of the stats block: what the host loop knows, and the two sizes
-__global__ void k_sim_finish(const SimTotals* __restrict__ tot, long long rounds, long long stopped, long long* __restrict__ stats) {
-    stats[O2345_SIMPLIFY_ROUNDS] = rounds;
-    stats[O2345_SIMPLIFY_STOPPED] = stopped;
-    stats[O2345_SIMPLIFY_VERTICES] = tot->nv_out;
-    stats[O2345_SIMPLIFY_TRIANGLES] = tot->nt_out;
+__global__ void k_sim_finish(const SimTotals* __restrict__ tot, long long rounds, long long stopped, O2345SimplifyStats* __restrict__ stats) {
+    stats->rounds = rounds;
+    stats->stopped = stopped;
+    stats->vertices = tot->nv_out;
+    stats->triangles = tot->nt_out;
 }
+
+// the collapses of every round, behind the struct in the same buffer (include/o2345.h); the round's kernel counts with an unsigned atomic
+static inline unsigned long long* sim_collapses(O2345SimplifyStats* stats) { return (unsigned long long*)(stats + 1); }
 
 // thread v: merged[v] (the end of v's chain of collapses, renumbered, or -1), and the copy of a kept v
 __global__ __launch_bounds__(256) void k_sim_emit_verts(const double* __restrict__ verts, int nv, const int* __restrict__ parent, const int* __restrict__ flag,
@@ -362,7 +365,7 @@ size_t o2345_mesh_simplify_workspace_bytes(long long nv, long long nt) {
 // Pass 1 of the two-call protocol: all rounds, the kept flags and the renumbering inside the workspace, the stats block on the device.  Synchronises the
 // stream once after the input check and once per round (the host loop needs the round's counts to decide whether another one runs).
 int o2345_mesh_simplify_count(const double* verts, const void* tris, int index_bytes, long long nv, long long nt, long long target_faces, double max_error,
-                              int max_rounds, void* workspace, size_t workspace_bytes, long long* stats, void* stream) {
+                              int max_rounds, void* workspace, size_t workspace_bytes, O2345SimplifyStats* stats, void* stream) {
     O2345_REQUIRE_INDEX_BYTES("mesh_simplify_count", index_bytes);
     O2345_REQUIRE(sim_sizes_ok(nv, nt), "mesh_simplify_count: bad sizes (nv must stay below 2^30 and 6 * nt below 2^31)");
     O2345_REQUIRE(target_faces >= 0 && max_rounds >= 0, "mesh_simplify_count: target_faces and max_rounds must be >= 0, got %lld, %d", target_faces, max_rounds);
@@ -376,7 +379,7 @@ int o2345_mesh_simplify_count(const double* verts, const void* tris, int index_b
     const int n = (int)nv;
     const unsigned gv = cdiv(nv, 256), gt = cdiv(nt, 256);
     O2345_HIP(hipMemsetAsync(c.tot, 0, sizeof(SimTotals), s));
-    O2345_HIP(hipMemsetAsync(stats, 0, sizeof(long long) * (size_t)(O2345_SIMPLIFY_STATS + max_rounds), s));
+    O2345_HIP(hipMemsetAsync(stats, 0, (size_t)((char*)(sim_collapses(stats) + max_rounds) - (char*)stats), s));      // the struct and collapses[max_rounds]
     if (nv > 0) O2345_HIP(hipMemsetAsync(c.flag, 0, sizeof(int) * (size_t)nv, s));
     if (nv > 0 || nt > 0) with_index_type(index_bytes, tris, [&](auto* t) {
         hipLaunchKernelGGL(k_sim_begin<index_type<decltype(t)>>, dim3(cdiv(nv > nt ? nv : nt, 256)), dim3(256), 0, s, verts, t, nt, n, c.cur, c.parent, c.tot);
@@ -406,7 +409,7 @@ int o2345_mesh_simplify_count(const double* verts, const void* tris, int index_b
         hipLaunchKernelGGL(k_sim_threshold, dim3(1), dim3(256), 0, s, c.hist, (live - target_faces + 1) / 2, c.tot);
         hipLaunchKernelGGL(k_sim_gather1, dim3(gv), dim3(256), 0, s, n, c.adj.rawoff, c.adj.cap, c.adj.raw, c.cand, c.cost, c.tot, salt, c.m1h, c.m1v);
         hipLaunchKernelGGL(k_sim_select, dim3(gv), dim3(256), 0, s, n, c.adj.rawoff, c.adj.cap, c.adj.raw, c.cand, c.cost, c.m1h, c.m1v, c.target, c.parent, c.Q, c.tot,
-                           (unsigned long long*)stats + O2345_SIMPLIFY_STATS + round, (unsigned long long*)stats + O2345_SIMPLIFY_MAX_COST_BITS);
+                           sim_collapses(stats) + round, &stats->max_cost_bits);
         hipLaunchKernelGGL(k_sim_apply, dim3(gt), dim3(256), 0, s, c.cur, nt, c.target);
         if ((rc = check_launch("mesh_simplify_count"))) return rc;
         if ((rc = read_totals(h, c.tot, s, "mesh_simplify_count"))) return rc;

@@ -1637,7 +1637,7 @@ AUDIT_QUALITY_SCALE = 6.928203230275509          # 4 sqrt(3): an equilateral tri
 AUDIT_BINS = 10
 AUDIT_VERTEX_BITS = {"boundary": 1, "nonmanifold": 2, "bowtie": 4, "unused": 8}
 AUDIT_FACE_BITS = {"repeated": 1, "zero_area": 2, "boundary": 4, "nonmanifold": 8, "inconsistent": 16, "creased": 32}
-# the integer counts of an audit, in the order of the device's stats block (include/o2345.h, O2345_AUDIT_*), and its doubles
+# the integer counts of an audit: the names of the fields that hold them in the device's stats block (include/o2345.h, O2345AuditStats)
 AUDIT_COUNTS = ("vertices", "edges", "faces", "repeated_faces", "zero_area_faces", "boundary_edges", "nonmanifold_edges", "inconsistent_edges", "creased_edges",
                 "boundary_vertices", "nonmanifold_vertices", "bowtie_vertices", "unused_vertices")
 

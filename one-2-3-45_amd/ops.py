@@ -1041,26 +1041,16 @@ def mesh_decimate(verts_idx, tris, cell=None):
 
 
 # ---------------------------------------------------------------------------------------------------------- mesh simplification
-_SIMPLIFY_STOPPED = ("target", "blocked", "rounds")
-_simplify_names = {}
-
-
-def _simplify_stats_index():
-    """The names of o2345_mesh_simplify_count's stats block (include/o2345.h, the O2345_SIMPLIFY_* enumerators) -> {name: value}, read from the header's
-    own text once: the block is declared there and nowhere else."""
-    if not _simplify_names:
-        import re
-        _simplify_names.update({k: int(v) for k, v in re.findall(r"O2345_SIMPLIFY_(\w+) = (\d+)", open(_lib.HEADER).read())})
-    return _simplify_names
+_SIMPLIFY_STOPPED = ("target", "blocked", "rounds")              # by O2345_SIMPLIFY_STOPPED_*
 
 
 def simplify_info(stats):
-    """The stats block of o2345_mesh_simplify_count (int64, on the host) -> the info dict of mesh_io.simplify_mesh."""
-    ix = _simplify_stats_index()
-    st = [int(x) for x in stats]
-    rounds = st[ix["ROUNDS"]]
-    return {"rounds": rounds, "vertices": st[ix["VERTICES"]], "triangles": st[ix["TRIANGLES"]], "collapses": st[ix["STATS"]:ix["STATS"] + rounds],
-            "max_cost": _double_of_bits(st[ix["MAX_COST_BITS"]]), "stopped": _SIMPLIFY_STOPPED[st[ix["STOPPED"]]]}
+    """The stats block of o2345_mesh_simplify_count (O2345SimplifyStats and the collapses of every round behind it, on the host) -> the info dict of
+    mesh_io.simplify_mesh."""
+    st = _lib.read_struct("O2345SimplifyStats", stats)
+    collapses = np.frombuffer(stats, np.int64, st.rounds, ctypes.sizeof(st))
+    return {"rounds": st.rounds, "vertices": st.vertices, "triangles": st.triangles, "collapses": collapses.tolist(),
+            "max_cost": _double_of_bits(st.max_cost_bits), "stopped": _SIMPLIFY_STOPPED[st.stopped]}
 
 
 @_on_device
@@ -1080,7 +1070,7 @@ def mesh_simplify(verts_idx, tris, target_faces=None, max_error=None, max_rounds
     _vertices(verts_idx)
     nv, nt, dev = verts_idx.shape[0], tris.shape[0], verts_idx.device
     ws, wsb = _scratch("o2345_mesh_simplify_workspace_bytes", (nv, nt), dev, "mesh_simplify")
-    stats = torch.empty(_simplify_stats_index()["STATS"] + max_rounds, dtype=torch.int64, device=dev)
+    stats = torch.empty(ctypes.sizeof(_lib.STRUCTS["O2345SimplifyStats"]) + 8 * max_rounds, dtype=torch.uint8, device=dev)
     call("o2345_mesh_simplify_count", verts_idx, tris, ib, nv, nt, target, max_error, max_rounds, ws, wsb, stats)
     info = simplify_info(stats.cpu().numpy())
     verts = torch.empty(info["vertices"], 3, dtype=torch.float64, device=dev)
@@ -1280,37 +1270,17 @@ def mesh_distance(va, ta, vb, tb, spacing=None, thresholds=(), return_samples=Fa
 
 
 # ---------------------------------------------------------------------------------------------------------- mesh audit
-_audit_names = {}
-# mesh_io.AUDIT_COUNTS -> the entry of the stats block that holds it
-_AUDIT_ENTRY = {"vertices": "VERTICES", "edges": "EDGES", "faces": "FACES", "repeated_faces": "REPEATED", "zero_area_faces": "ZERO_AREA",
-                "boundary_edges": "BOUNDARY_EDGES", "nonmanifold_edges": "NONMANIFOLD_EDGES", "inconsistent_edges": "INCONSISTENT_EDGES",
-                "creased_edges": "CREASED_EDGES", "boundary_vertices": "BOUNDARY_VERTICES", "nonmanifold_vertices": "NONMANIFOLD_VERTICES",
-                "bowtie_vertices": "BOWTIE_VERTICES", "unused_vertices": "UNUSED_VERTICES"}
-
-
-def _audit_stats_index():
-    """The names of o2345_mesh_audit's stats block (include/o2345.h, the O2345_AUDIT_* enumerators) -> {name: value}, read from the header's own text
-    once: the block is declared there and nowhere else."""
-    if not _audit_names:
-        import re
-        _audit_names.update({k: int(v) for k, v in re.findall(r"O2345_AUDIT_(\w+) = (\d+)", open(_lib.HEADER).read())})
-    return _audit_names
-
-
 def audit_info(stats, nv, components):
-    """The stats block of o2345_mesh_audit (int64, on the host) and the number of components that own a triangle -> the report of mesh_io.mesh_audit
-    (mesh_io.audit_report, shared with the twin).  ``components``: a number, or a function that returns it -- called after the two refusals.  Raises on a
-    triangle index out of range or a non-finite coordinate."""
-    ix = _audit_stats_index()
-    st = [int(x) for x in stats]
-    if st[ix["BAD_INDEX"]]:
-        raise RuntimeError(f"o2345 mesh_audit: {st[ix['BAD_INDEX']]} triangles index outside 0 .. {nv - 1}")
-    if st[ix["NONFINITE"]]:
-        raise RuntimeError(f"o2345 mesh_audit: {st[ix['NONFINITE']]} vertices have a non-finite coordinate")
-    dbl = lambda name: _double_of_bits(st[ix[name]] & 0xFFFFFFFFFFFFFFFF)
-    return mesh_io.audit_report({k: st[ix[e]] for k, e in _AUDIT_ENTRY.items()}, st[ix["HISTOGRAM"]:ix["HISTOGRAM"] + mesh_io.AUDIT_BINS], dbl("AREA_BITS"),
-                                dbl("VOLUME6_BITS"), dbl("QUALITY_SUM_BITS"), dbl("QUALITY_MIN_BITS"), dbl("EDGE2_MIN_BITS"), dbl("EDGE2_MAX_BITS"),
-                                components() if callable(components) else components)
+    """The stats block of o2345_mesh_audit (O2345AuditStats, on the host) and the number of components that own a triangle -> the report of
+    mesh_io.mesh_audit (mesh_io.audit_report, shared with the twin).  ``components``: a number, or a function that returns it -- called after the two
+    refusals.  Raises on a triangle index out of range or a non-finite coordinate."""
+    st = _lib.read_struct("O2345AuditStats", stats)
+    if st.bad_index:
+        raise RuntimeError(f"o2345 mesh_audit: {st.bad_index} triangles index outside 0 .. {nv - 1}")
+    if st.nonfinite:
+        raise RuntimeError(f"o2345 mesh_audit: {st.nonfinite} vertices have a non-finite coordinate")
+    return mesh_io.audit_report({k: getattr(st, k) for k in mesh_io.AUDIT_COUNTS}, list(st.histogram), st.area, st.volume6, st.quality_sum, st.quality_min,
+                                st.edge2_min, st.edge2_max, components() if callable(components) else components)
 
 
 @_on_device
@@ -1328,7 +1298,7 @@ def mesh_audit(verts, tris, return_elements=False):
     ws, wsb = _scratch("o2345_mesh_audit_workspace_bytes", (nv, nt), dev, "mesh_audit")
     if not wsb:
         raise ValueError(f"mesh_audit: bad sizes ({nv} vertices, {nt} triangles; the tables are int32)")
-    stats = torch.empty(_audit_stats_index()["STATS"], dtype=torch.int64, device=dev)
+    stats = _stats_block("O2345AuditStats", dev)
     vf, ff, q = (torch.empty(n, dtype=dt, device=dev) for n, dt in ((nv, torch.uint8), (nt, torch.uint8), (nt, torch.float64))) if return_elements else (None,) * 3
     call("o2345_mesh_audit", verts, tris, ib, nv, nt, ws, wsb, stats, vf, ff, q)
     # the components with at least one triangle: the selection count of the component unit at min_faces = 1

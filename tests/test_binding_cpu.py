@@ -39,7 +39,8 @@ def test_every_pointer_has_an_element_type_and_the_host_rule_holds():
     structs = {(fn, p.name): p.elem[7:] for fn, p in ptrs if p.elem.startswith("struct ")}
     assert structs == {("o2345_render_rays", "io_host"): "O2345RenderIO", ("o2345_mesh_project", "stats"): "O2345ProjectStats",
                        ("o2345_mesh_texture_points", "stats"): "O2345TextureStats", ("o2345_surface_trace", "stats"): "O2345SurfaceStats",
-                       ("o2345_mesh_distance_reduce", "stats"): "O2345DistanceStats"}
+                       ("o2345_mesh_distance_reduce", "stats"): "O2345DistanceStats", ("o2345_mesh_simplify_count", "stats"): "O2345SimplifyStats",
+                       ("o2345_mesh_audit", "stats"): "O2345AuditStats"}
     assert not [k for k in structs if k[1] == "stats" and k in host] and "void* stats" not in open(L.HEADER).read()
     assert table["o2345_costvol_index", "origin_host"] == "float32" and table["o2345_mesh_smooth", "boundary_or_null"] == "uint8"
     assert table["o2345_list_sort_by_visibility", "keys_out"] == "int32" and table["o2345_color_points_x3", "stats_dev"] == "int64"
@@ -147,7 +148,7 @@ def test_bind_accepts():
 def test_call_returns_values_and_raises_on_a_failing_status():
     w, h = ctypes.c_int(), ctypes.c_int()
     assert L.call("o2345_mesh_texture_texels", 33, 8, w, h) == 17 * 64 and (w.value, h.value) == (5 * 8, 4 * 8)       # 17 cells, G = 5: 5 x 4 cells
-    assert L.call("o2345_version") == L.ABI_VERSION == 220
+    assert L.call("o2345_version") == L.ABI_VERSION == 230
     assert L.call("o2345_obj_text_bytes", 0, 0, 12, 0, 0) == 0 and b"=" in L.call("o2345_knobs")
     with pytest.raises(RuntimeError, match=r"o2345 sdf_mlp failed \(-?\d+\): .*null pointer") as e:
         L.call("o2345_sdf_mlp", 0, None, None, 8, None, None, None, 10, 0, 1.0, None, None, None, None, None)
@@ -202,7 +203,8 @@ def test_device_pointers_check_dtype_and_contiguity():
 
 # ---------------------------------------------------------------------------------------------------------- the declared structs
 # The stats blocks of the C ABI as they were when each was a private struct of its .hip file (ProjStats, TexStats, SurfStats, MdStats) and a list of
-# byte offsets in ops.py: the independent statement of their layout.  name -> (sizeof, [(field, offset)]).
+# byte offsets in ops.py: the independent statement of their layout.  name -> (sizeof, [(field, offset)]).  The last two were int64 arrays whose entries
+# an enum of the header named (commit 7cbf4a6): their offsets are 8 x those enumerators' values, their sizes 8 x the two that counted the entries (8, 32).
 FROZEN = {
     "O2345ProjectStats": (328, [("n_nonfinite", 0), ("converged", 8), ("unconverged", 16), ("stalled", 24), ("clamped", 32), ("max_before", 40),
                                 ("max_after", 48), ("reserved", 56), ("count", 64)]),
@@ -211,13 +213,19 @@ FROZEN = {
                                ("lookups", 56), ("n_list", 64), ("reserved", 68)]),
     "O2345DistanceStats": (128, [("sum_w", 0), ("sum_wd", 8), ("sum_wd2", 16), ("within", 24), ("max_d2_bits", 88), ("n", 96), ("n_unmatched", 104),
                                  ("n_degenerate", 112), ("n_bad", 120)]),
+    "O2345SimplifyStats": (64, [("rounds", 0), ("vertices", 8), ("triangles", 16), ("stopped", 24), ("max_cost_bits", 32), ("reserved", 40)]),
+    "O2345AuditStats": (256, [("bad_index", 0), ("nonfinite", 8), ("vertices", 16), ("edges", 24), ("faces", 32), ("repeated_faces", 40), ("zero_area_faces", 48),
+                              ("boundary_edges", 56), ("nonmanifold_edges", 64), ("inconsistent_edges", 72), ("creased_edges", 80), ("boundary_vertices", 88),
+                              ("nonmanifold_vertices", 96), ("bowtie_vertices", 104), ("unused_vertices", 112), ("reserved", 120), ("histogram", 128),
+                              ("area", 208), ("volume6", 216), ("quality_sum", 224), ("quality_min", 232), ("edge2_min", 240), ("edge2_max", 248)]),
 }
 STATS_ENTRY = {"O2345ProjectStats": "o2345_mesh_project", "O2345TextureStats": "o2345_mesh_texture_points", "O2345SurfaceStats": "o2345_surface_trace",
-               "O2345DistanceStats": "o2345_mesh_distance_reduce"}
+               "O2345DistanceStats": "o2345_mesh_distance_reduce", "O2345SimplifyStats": "o2345_mesh_simplify_count", "O2345AuditStats": "o2345_mesh_audit"}
 
 
 def test_stats_struct_layouts_are_frozen():
-    assert list(L.STRUCTS) == L.struct_names() == ["O2345RenderIO", "O2345ProjectStats", "O2345TextureStats", "O2345SurfaceStats", "O2345DistanceStats"]
+    assert list(L.STRUCTS) == L.struct_names() == ["O2345RenderIO", "O2345ProjectStats", "O2345TextureStats", "O2345SurfaceStats", "O2345DistanceStats",
+                                                      "O2345SimplifyStats", "O2345AuditStats"]
     assert L.STRUCTS["O2345RenderIO"] is L.RenderIO
     for name, (size, offsets) in FROZEN.items():
         cls = L.STRUCTS[name]
@@ -229,6 +237,17 @@ def test_stats_struct_layouts_are_frozen():
     for which, name in enumerate(L.STRUCTS):
         assert lib.o2345_struct_size(which) == ctypes.sizeof(L.STRUCTS[name]) and lib.o2345_struct_layout(which, None, 0) == len(L.STRUCTS[name]._fields_)
     assert lib.o2345_struct_size(len(L.STRUCTS)) == 0 and lib.o2345_struct_layout(-1, None, 0) == 0
+
+
+def test_the_names_python_keeps_are_the_headers():
+    ops, mio = importlib.import_module("one-2-3-45_amd.ops"), importlib.import_module("one-2-3-45_amd.mesh_io")
+    A = L.STRUCTS["O2345AuditStats"]
+    fields = dict(A._fields_)
+    assert all(fields[k] is ctypes.c_ulonglong for k in mio.AUDIT_COUNTS) and len(set(mio.AUDIT_COUNTS)) == len(mio.AUDIT_COUNTS) == 13
+    assert A.histogram.size == 8 * mio.AUDIT_BINS and fields["histogram"] is ctypes.c_ulonglong * mio.AUDIT_BINS
+    assert all(fields[k] is ctypes.c_double for k in ("area", "volume6", "quality_sum", "quality_min", "edge2_min", "edge2_max"))
+    codes = {k.lower(): int(v) for k, v in re.findall(r"O2345_SIMPLIFY_STOPPED_(\w+) = (\d+)", open(L.HEADER).read())}
+    assert len(codes) == 3 == len(ops._SIMPLIFY_STOPPED) and all(ops._SIMPLIFY_STOPPED[v] == k for k, v in codes.items())
 
 
 def test_struct_parser_reads_arrays_and_several_names_per_declaration(tmp_path):
@@ -318,6 +337,27 @@ def _distance_block(n_unmatched=0, n_bad=0, sum_w=7.3):
     return raw
 
 
+# The two decoders of the mesh units that came later, likewise: the expected values were recorded from ops.simplify_info and ops.audit_info at commit
+# 7cbf4a6, which indexed an int64 array through the header's enumerators, for these same bytes.
+def _simplify_block(rounds, stopped, max_rounds=5):
+    raw = np.zeros(64 + 8 * max_rounds, np.uint8)
+    _put(raw, 0, np.int64, [rounds, 2 ** 33 + 7, 2 ** 34 + 9, stopped])
+    _put(raw, 32, np.float64, 0.0625 + 1e-9)                  # max_cost_bits
+    _put(raw, 40, np.int64, [97, 98, 99])                     # reserved: not reported
+    _put(raw, 64, np.int64, 500 - 3 * np.arange(max_rounds))  # behind the struct: the collapses of every round
+    return raw
+
+
+def _audit_block(bad_index=0, nonfinite=0):
+    raw = np.zeros(256, np.uint8)
+    _put(raw, 0, np.uint64, [bad_index, nonfinite])
+    _put(raw, 16, np.uint64, 2 ** 35 + 1000 + 11 * np.arange(13))
+    _put(raw, 120, np.uint64, 99)                             # reserved: not reported
+    _put(raw, 128, np.uint64, 3 + 7 * np.arange(10))          # histogram
+    _put(raw, 208, np.float64, [12.5, -7.75, 33.3, np.inf, 1e-4, 9.0])        # area, volume6, quality_sum, quality_min, edge2_min, edge2_max: doubles
+    return raw
+
+
 def test_stats_decoders_return_what_they_returned():
     ops = importlib.import_module("one-2-3-45_amd.ops")
     want = {"evaluated": [1000, 993, 986, 979, 972, 965], "converged": 11, "unconverged": 12, "stalled": 13, "clamped": 14, "max_before": 0.1, "max_after": 1.5e-07}
@@ -339,6 +379,23 @@ def test_stats_decoders_return_what_they_returned():
     got, degenerate = ops.distance_summary(_distance_block(sum_w=0.0), 2)
     assert np.isnan([got["mean"], got["rms"]] + got["within"]).all() and len(got["within"]) == 2 and (got["max"], got["samples"], got["area"], degenerate) == (0.5477225575051661, 4096, 0.0, 5)
     assert ops.distance_summary(np.stack([_distance_block(), _distance_block(3)])[0], 3) == ops.distance_summary(_distance_block(), 3)      # a row of the [2, 128] read-back
+    for (rounds, stopped), collapses, word in (((0, 0), [], "target"), ((3, 1), [500, 497, 494], "blocked"), ((5, 2), [500, 497, 494, 491, 488], "rounds")):
+        raw = _simplify_block(rounds, stopped)                                     # five rounds of room: the last case fills the buffer
+        got = ops.simplify_info(raw)
+        assert got == {"rounds": rounds, "vertices": 8589934599, "triangles": 17179869193, "collapses": collapses, "max_cost": 0.062500001, "stopped": word}
+        assert list(got) == ["rounds", "vertices", "triangles", "collapses", "max_cost", "stopped"]
+        assert [type(v) for v in got.values()] == [int, int, int, list, float, str] and all(type(c) is int for c in got["collapses"])
+        assert ops.simplify_info(raw.view(np.int64)) == got == ops.simplify_info(raw.tobytes())          # an int64 array, as it was handed over before; bytes
+    want = {"vertices": 34359739368, "edges": 34359739379, "faces": 34359739390, "repeated_faces": 34359739401, "zero_area_faces": 34359739412,
+            "boundary_edges": 34359739423, "nonmanifold_edges": 34359739434, "inconsistent_edges": 34359739445, "creased_edges": 34359739456,
+            "boundary_vertices": 34359739467, "nonmanifold_vertices": 34359739478, "bowtie_vertices": 34359739489, "unused_vertices": 34359739500,
+            "histogram": [3, 10, 17, 24, 31, 38, 45, 52, 59, 66], "area": 12.5, "volume": -1.2916666666666667, "quality_mean": 9.691575253824997e-10,
+            "quality_min": float("inf"), "edge_min": 0.01, "edge_max": 3.0, "euler": 34359739379, "components": 4, "oriented": False, "watertight": False,
+            "genus": None}
+    got = ops.audit_info(_audit_block(), 77, 4)
+    assert got == want and list(got) == list(want) and all(type(c) is int for c in got["histogram"])
+    assert [type(v) for v in got.values()] == [int] * 13 + [list] + [float] * 6 + [int, int, bool, bool, type(None)]
+    assert ops.audit_info(_audit_block().view(np.int64), 77, lambda: 4) == got == ops.audit_info(_audit_block().tobytes(), 77, 4)
 
 
 @pytest.mark.parametrize("decode, message", [
@@ -349,6 +406,9 @@ def test_stats_decoders_return_what_they_returned():
     (lambda ops: ops.distance_summary(_distance_block(n_unmatched=9), 1), "o2345 mesh_distance: 9 of 4096 samples found no triangle: the target has no triangle with an area"),
     (lambda ops: ops.distance_summary(_distance_block(n_unmatched=9), 1, 12),
      "o2345 mesh_distance: 9 of 4096 samples found no triangle: the target has no triangle with an area (12 triangles, 5 degenerate)"),
+    (lambda ops: ops.audit_info(_audit_block(3, 5), 77, 4), "o2345 mesh_audit: 3 triangles index outside 0 .. 76"),         # before the non-finite count
+    (lambda ops: ops.audit_info(_audit_block(3, 0), 77, 4), "o2345 mesh_audit: 3 triangles index outside 0 .. 76"),
+    (lambda ops: ops.audit_info(_audit_block(0, 5), 77, 4), "o2345 mesh_audit: 5 vertices have a non-finite coordinate"),
 ])
 def test_stats_decoders_raise_what_they_raised(decode, message):
     with pytest.raises(RuntimeError) as e:

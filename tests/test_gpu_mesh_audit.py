@@ -1,6 +1,7 @@
 """GPU: the mesh audit (csrc/mesh_audit.hip) against the host twin (mesh_io.mesh_audit), which defines the result.  Counts, histogram, flags, per-triangle
 quality, minima and maxima are compared EXACTLY (bytes); the three sums within 1e-12 of the sum of their terms' magnitudes (the twin sums with math.fsum,
 the device in a fixed tree).  Expected values are the twin applied to the same inputs, never the code under test; a twin result is computed once per mesh."""
+import ctypes
 import importlib
 
 import numpy as np
@@ -19,7 +20,7 @@ config = importlib.import_module("one-2-3-45_amd.config")
 pipeline = importlib.import_module("one-2-3-45_amd.pipeline")
 _lib = importlib.import_module("one-2-3-45_amd._lib")
 
-N_STATS = 32                                                            # include/o2345.h: O2345_AUDIT_STATS
+STATS_BYTES = ctypes.sizeof(_lib.STRUCTS["O2345AuditStats"])
 ELEMENTS = ("vertex_flags", "face_flags", "quality")
 _twins = {}
 
@@ -78,7 +79,7 @@ def test_the_stored_scene_before_and_after_clustering(scene, dtype):
 
 
 def _raw(dev, hv, hf, dtype, g=None, outputs=(True, True, True), stream=None):
-    """o2345_mesh_audit itself, every buffer at its exact size (inside guard bands when ``g`` is given) -> (stats int64 [32], vertex_flags, face_flags,
+    """o2345_mesh_audit itself, every buffer at its exact size (inside guard bands when ``g`` is given) -> (stats: its raw bytes, vertex_flags, face_flags,
     quality) as numpy, None for an output that was not asked for"""
     nv, nt = hv.shape[0], hf.shape[0]
     ib = 8 if dtype == torch.int64 else 4
@@ -86,7 +87,7 @@ def _raw(dev, hv, hf, dtype, g=None, outputs=(True, True, True), stream=None):
     wsb = _lib.call("o2345_mesh_audit_workspace_bytes", nv, nt)
     assert wsb > 0 and PRE % 16 == 0
     new = (lambda n, what: g.buf(n, (what, nv, nt))) if g else (lambda n, what: torch.full((n,), 0xA5, dtype=torch.uint8, device=dev))
-    ws, stats = new(wsb, "workspace"), new(8 * N_STATS, "stats").view(torch.int64)
+    ws, stats = new(wsb, "workspace"), new(STATS_BYTES, "stats")
     vf, ff, q = (new(n, what) if on else None for on, n, what in zip(outputs, (nv, nt, 8 * nt), ELEMENTS))
     torch.cuda.synchronize()                                              # the buffers were filled on the current stream
     with torch.cuda.stream(stream):
@@ -94,7 +95,7 @@ def _raw(dev, hv, hf, dtype, g=None, outputs=(True, True, True), stream=None):
     torch.cuda.synchronize()
     assert verts.cpu().numpy().tobytes() == np.ascontiguousarray(hv, np.float64).tobytes() and np.array_equal(tris.cpu().numpy(), hf)
     h = lambda t, d: None if t is None else t.cpu().numpy().view(d)
-    return h(stats, np.int64), h(vf, np.uint8), h(ff, np.uint8), h(q, np.float64)
+    return h(stats, np.uint8), h(vf, np.uint8), h(ff, np.uint8), h(q, np.float64)
 
 
 GUARDED = ("defects", "three_on_an_edge", "two_tetrahedra", "cube10_relabelled", "fan300", "grid_nt0", "grid_nt1", "grid_nt255", "grid_nt256", "grid_nt257")
@@ -108,6 +109,7 @@ def test_no_kernel_writes_outside_its_buffers(dev, dtype):
         stats, vf, ff, q = _raw(dev, v, f, dtype, g)
         bad = g.damaged()
         assert not bad, bad
+        assert _lib.read_struct("O2345AuditStats", stats).reserved == 0
         want, bounds = _twin(name, v, f)
         got = dict(ops.audit_info(stats, v.shape[0], want["components"]), vertex_flags=vf, face_flags=ff, quality=q)
         U.assert_equal_reports(got, want, bounds)
@@ -118,7 +120,7 @@ def test_two_runs_and_a_second_stream_give_identical_bytes(dev, scene):
     side = torch.cuda.Stream(device=dev)
     for hv, hf in ((scene["dv"], scene["df"]), U.meshes()["fan300"], U.meshes()["defects"]):
         runs = [[None if x is None else x.tobytes() for x in _raw(dev, hv, hf, torch.int64, stream=s)] for s in (None, None, side)]
-        assert runs[0] == runs[1] == runs[2] and len(runs[0][0]) == 8 * N_STATS
+        assert runs[0] == runs[1] == runs[2] and len(runs[0][0]) == STATS_BYTES
 
 
 def test_every_optional_output_may_be_null(dev):
@@ -164,7 +166,7 @@ def test_refusals_are_statuses_not_faults(dev):
     wsb = size(nv, nt)
     assert wsb > 0 and size(2 ** 30, 0) == 0 and size(-1, 0) == 0 and size(0, -1) == 0 and size(0, 2 ** 31 // 6 + 1) == 0 and size(0, 0) > 0
     ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
-    stats = torch.empty(N_STATS, dtype=torch.int64, device=dev)
+    stats = torch.empty(STATS_BYTES, dtype=torch.uint8, device=dev)
     for a, what in (((None, tris, 8, nv, nt, ws, wsb, stats), "null pointer"), ((good, None, 8, nv, nt, ws, wsb, stats), "null pointer"),
                     ((good, tris, 8, nv, nt, None, wsb, stats), "null pointer"), ((good, tris, 8, nv, nt, ws, wsb, None), "null pointer"),
                     ((good, tris, 8, nv, nt, ws, wsb - 1, stats), "workspace too small"), ((good, tris, 2, nv, nt, ws, wsb, stats), "index_bytes"),

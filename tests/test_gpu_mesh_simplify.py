@@ -22,6 +22,7 @@ config = importlib.import_module("one-2-3-45_amd.config")
 pipeline = importlib.import_module("one-2-3-45_amd.pipeline")
 _lib = importlib.import_module("one-2-3-45_amd._lib")
 
+STATS_BYTES = ctypes.sizeof(_lib.STRUCTS["O2345SimplifyStats"])         # behind it: 8 bytes per round
 INFO_KEYS = {"rounds", "vertices", "triangles", "collapses", "max_cost", "stopped"}
 SCAN_TILE = 2048                                                        # csrc/mesh_common.h
 SIZES = (0, 1, 255, 256, 257, SCAN_TILE - 1, SCAN_TILE + 1)             # every block, wave and scan-tile boundary
@@ -201,7 +202,7 @@ def test_errors_are_statuses_not_faults(dev):
     assert wsb > 0 and L.o2345_mesh_simplify_workspace_bytes(2 ** 30, 0) == 0 and L.o2345_mesh_simplify_workspace_bytes(-1, 0) == 0
     assert L.o2345_mesh_simplify_workspace_bytes(0, 2 ** 31 // 6 + 1) == 0
     ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
-    stats = torch.empty(8 + 16, dtype=torch.int64, device=dev)
+    stats = torch.empty(STATS_BYTES + 8 * 16, dtype=torch.uint8, device=dev)
     count = lambda *a: _lib.call("o2345_mesh_simplify_count", *a)
     for a, what in (((None, tris, 8, nv, nt, 4, INF, 16, ws, wsb, stats), "null pointer"), ((good, None, 8, nv, nt, 4, INF, 16, ws, wsb, stats), "null pointer"),
                     ((good, tris, 8, nv, nt, 4, INF, 16, None, wsb, stats), "null pointer"), ((good, tris, 8, nv, nt, 4, INF, 16, ws, wsb, None), "null pointer"),
@@ -227,11 +228,13 @@ def _guarded_run(g, dev, hv, hf, dtype, target, max_error, max_rounds):
     wsb = L.o2345_mesh_simplify_workspace_bytes(nv, nt)
     assert wsb > 0 and PRE % 16 == 0
     ws = g.buf(wsb, ("workspace", nv, nt))
-    stats = g.buf(8 * (8 + max_rounds), ("stats", nv, nt))
+    stats = g.buf(STATS_BYTES + 8 * max_rounds, ("stats", nv, nt))
     s = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
     _lib.check(L.o2345_mesh_simplify_count(P(verts), P(tris), ib, nv, nt, target, max_error, max_rounds, ctypes.c_void_p(ws.data_ptr()), wsb,
                                            ctypes.c_void_p(stats.data_ptr()), s), "mesh_simplify_count")
-    info = ops.simplify_info(stats.cpu().numpy().view(np.int64))
+    host = stats.cpu().numpy()
+    assert list(_lib.read_struct("O2345SimplifyStats", host).reserved) == [0, 0, 0]
+    info = ops.simplify_info(host)
     nvo, nto = info["vertices"], info["triangles"]
     vo, to = g.buf(24 * nvo, ("verts_out", nv, nt)), g.buf(3 * ib * nto, ("tris_out", nv, nt))
     so, me = g.buf(4 * nvo, ("source", nv, nt)), g.buf(4 * nv, ("merged", nv, nt))

@@ -64,7 +64,7 @@ def timings(reps, warmup, volume, grid):
     for name, (mv, mt) in (("raw", (v, t)), ("simplified", (sv, st))):
         nv, nt = mv.shape[0], mt.shape[0]
         ws, wsb = ops._scratch("o2345_mesh_audit_workspace_bytes", (nv, nt), dev, "mesh_audit")
-        stats = torch.empty(ops._audit_stats_index()["STATS"], dtype=torch.int64, device=dev)
+        stats = ops._stats_block("O2345AuditStats", dev)
         vf, ff, q = torch.empty(nv, dtype=torch.uint8, device=dev), torch.empty(nt, dtype=torch.uint8, device=dev), torch.empty(nt, dtype=torch.float64, device=dev)
         ib = 8 if mt.dtype == torch.int64 else 4
         report = ops.mesh_audit(mv, mt)
