@@ -65,7 +65,9 @@ const char* o2345_last_error(void);
  * moved, the `long long* stats` parameters became pointers to them); the positional enumerators that named their entries (O2345_SIMPLIFY_ROUNDS ... _STATS,
  * O2345_AUDIT_*) are removed, the three stop codes O2345_SIMPLIFY_STOPPED_* stay.  Both units were additive since 2.2: the simplification entries
  * o2345_mesh_simplify_workspace_bytes, o2345_mesh_simplify_count, o2345_mesh_simplify_emit; the audit entries o2345_mesh_audit_workspace_bytes,
- * o2345_mesh_audit. */
+ * o2345_mesh_audit.
+ * Additive since 2.3 (no existing entry changed, the version stays 230): the hole-filling entries o2345_mesh_fill_workspace_bytes, o2345_mesh_fill_count,
+ * o2345_mesh_fill_emit. */
 int o2345_version(void);
 /* Layout self-description of the declared structs as THIS library was compiled (sizeof, and offsetof of every field in declaration order): a binding
  * asserts its own structs against it at load time (one-2-3-45_amd/_lib.py does) -- a field added on one side only cannot corrupt calls silently.
@@ -750,7 +752,8 @@ int o2345_mesh_simplify_emit(const double* verts, int index_bytes, long long nv,
  * edge, 4 an inconsistent edge, 5 a creased edge.  quality fp64 [nt]: 0 for a repeated triangle.  Any of the three may be NULL.  A triangle index outside
  * [0, nv) and a vertex with a non-finite coordinate are counted (bad_index, nonfinite), never dereferenced; the caller reads the two counts and treats
  * the rest as void when one is not 0.  workspace: mesh_audit_workspace_bytes(nv, nt) bytes (0 for bad sizes), 16-byte aligned.  No host synchronisation.
- * Not done: duplicate faces, per-component reports, dihedral statistics, any repair. */
+ * Not done: duplicate faces, per-component reports, dihedral statistics, any repair (the hole filling below closes the
+ * boundary loops it reports). */
 typedef struct O2345AuditStats {
     unsigned long long bad_index, nonfinite;            /* triangles with an index outside [0, nv); vertices with a non-finite coordinate */
     unsigned long long vertices, edges, faces;          /* used vertices, undirected edges, non-repeated triangles */
@@ -765,6 +768,39 @@ typedef struct O2345AuditStats {
 size_t o2345_mesh_audit_workspace_bytes(long long nv, long long nt);
 int o2345_mesh_audit(const double* verts, const void* tris, int index_bytes, long long nv, long long nt, void* workspace, size_t workspace_bytes,
                      O2345AuditStats* stats, unsigned char* vertex_flags_or_null, unsigned char* face_flags_or_null, double* quality_or_null, void* stream);
+
+/* ---- hole filling: closes the boundary loops of a mesh (additive since 2.3; none in the reference: its users close the mesh in another tool) --------------
+ * Equal to the host twin mesh_io.fill_holes to the last bit.  verts device fp64 [nv,3], tris device int32 / int64 [nt,3] (index_bytes 4 / 8), both only
+ * read; max_edges in [3, 2^31).
+ *   half-edges h = 3 t + i runs from tris[t][i] to tris[t][(i + 1) % 3].  A triangle with two equal indices takes no part and is copied through.  The
+ *              undirected edge {lo, hi} has m half-edges; a half-edge is a BOUNDARY half-edge iff m == 1.
+ *   next       a vertex is SIMPLE iff exactly one boundary half-edge leaves it and exactly one enters it.  For a boundary half-edge h that enters a simple
+ *              vertex b, next(h) is the boundary half-edge that leaves b; otherwise next(h) is undefined.  next is injective where it is defined: the boundary
+ *              half-edges fall into disjoint cycles and chains.  A chain ends at a vertex that is not simple (a bow-tie on the rim, a non-manifold edge,
+ *              inconsistently oriented neighbours) and is left open.
+ *   holes      a HOLE is a cycle; its leader is its smallest half-edge, a half-edge's rank its distance from the leader along next, L its number of
+ *              half-edges (>= 3).  Holes are ordered by ascending leader.
+ *   fill       iff L <= max_edges, with o_k the origin of the hole's half-edge of rank k.  L == 3: one triangle (o_0, o_2, o_1), no new vertex.  L >= 4:
+ *              one new vertex c, per coordinate acc = 0, acc = acc + P[o_k] for k = 0 .. L - 1 in rank order (one sequential fp64 sum), c = acc / L, and
+ *              the L triangles (o_{k+1 mod L}, o_k, c) in rank order.  Every new triangle carries the half-edge opposite to the one it closes: an oriented
+ *              input stays oriented.
+ *   output     verts_out [nv_out,3] = verts bit for bit and in order, then the new vertices in hole order; tris_out [nt_out,3] (the input's width) = tris
+ *              unchanged and in order, then the new triangles in hole order, then rank order; hole int32 [nt_out - nt]: for every new triangle the number
+ *              of its hole among the filled holes.
+ * Two calls (the protocol of the components and the decimation): _count does all the topology inside the workspace (mesh_fill_workspace_bytes(nv, nt)
+ * bytes, 0 for bad sizes; 16-byte aligned) and writes counts, device int64 [8], 8-byte aligned: boundary half-edges, holes, filled holes, holes left
+ * because L > max_edges, boundary half-edges on chains, the longest hole, nv_out and nt_out -- the caller copies them to the host and allocates the
+ * outputs.  It synchronises the stream once, for the refusals that only the device can count: they are its status.  _emit writes the outputs from the same workspace, untouched
+ * in between; any output may be NULL.  A triangle index outside [0, nv) is counted on the device, never dereferenced, and fails _count; sizes beyond
+ * nv_out < 2^30 or 3 * nt_out < 2^31 are refused.  The pointer-doubling rounds are counted by the host before the first is launched; no floating-point
+ * atomics; the same bytes on every run.  A centroid fan is exact for a planar, star-shaped outline and may fold over itself for others (the mesh is
+ * combinatorially closed all the same).  Not done: ear clipping or minimum-area triangulation, refinement and fairing of the patch, holes with islands,
+ * fixing the vertices that are not simple. */
+size_t o2345_mesh_fill_workspace_bytes(long long nv, long long nt);
+int o2345_mesh_fill_count(const void* tris, int index_bytes, long long nv, long long nt, long long max_edges, void* workspace, size_t workspace_bytes,
+                          long long* counts, void* stream);
+int o2345_mesh_fill_emit(const double* verts, const void* tris, int index_bytes, long long nv, long long nt, void* workspace,
+                         double* verts_out, void* tris_out, int* hole, void* stream);
 /* Load every code object of the library on the current device now (the HIP runtime loads a translation unit's kernels at its first launch: 5 - 60 ms
  * each for the units of this library, which otherwise land inside the first calls of a fresh process).  Launches nothing that touches user memory. */
 int o2345_preload(void);

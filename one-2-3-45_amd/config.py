@@ -362,6 +362,32 @@ def mesh_audit(x=None):
     return MESH_AUDIT if x is None else bool(x)
 
 
+# ---- hole filling (csrc/mesh_fill.hip; mesh_io.fill_holes is the host twin) -------------------------------------------------------------------------------
+# O2345_MESH_FILL_HOLES=n closes the boundary loops of the extracted mesh that have at most n edges, on the device, directly after the clean-up chain and
+# before the vertices are coloured: a loop of three edges gets one triangle, a longer one a fan around its centroid ("" or "0" = off, the default: nothing
+# is launched and every file keeps its bytes; n >= 3; MESH_FILL_HOLES_ALL = every hole).  Not a field of MeshOptions: a keyword of its own.
+MESH_FILL_HOLES_ALL = 2 ** 31 - 1
+
+
+def _fill_holes(name, n):
+    if n in (1, 2):
+        raise ValueError(f"{name} must be 0 (off) or an integer >= 3 (a hole has at least three edges), got {n!r}")
+    return _below_2_31(name, n)
+
+
+MESH_FILL_HOLES = _fill_holes("O2345_MESH_FILL_HOLES", _non_negative_int("O2345_MESH_FILL_HOLES", os.environ.get("O2345_MESH_FILL_HOLES", "")))
+
+
+def mesh_fill_holes(n=None):
+    """None -> the configured default; anything else must be 0 (off, whatever the default) or an integer in [3, 2^31): the longest hole, in edges, that is
+    filled."""
+    if n is None:
+        return MESH_FILL_HOLES
+    if isinstance(n, bool) or int(n) != n or n < 0:
+        raise ValueError(f"fill_holes must be 0 (off) or an integer >= 3 below 2^31, got {n!r}")
+    return _fill_holes("fill_holes", int(n))
+
+
 # ---- surface render (csrc/surface_trace.hip; surface.py is the host twin) ---------------------------------------------------------------------------------
 # pipeline.render_surface marches rays through the extraction lattice.  O2345_SURFACE_STRIDE (1.0, in (0, 8]) is the distance between two samples in
 # lattice spacings -- above 1 the march may step over parts thinner than the stride; O2345_SURFACE_REFINE (8, in [0, 32]) the number of bracket

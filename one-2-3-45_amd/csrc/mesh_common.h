@@ -1,5 +1,5 @@
 // What the mesh units share.  The units: mcubes.hip, mesh_components.hip, mesh_smooth.hip and mesh_simplify.hip (both through mesh_adjacency.h),
-// mesh_decimate.hip, mesh_project.hip, mesh_texture.hip, mesh_distance.hip, mesh_audit.hip, mesh_export.hip, mesh_pack.hip, and surface_trace.hip for the wave
+// mesh_decimate.hip, mesh_project.hip, mesh_texture.hip, mesh_distance.hip, mesh_audit.hip, mesh_fill.hip, mesh_export.hip, mesh_pack.hip, and surface_trace.hip for the wave
 // sums and finite().  On the device: the triangle reader, the wave-level counter and reductions, finite(), the order-preserving fp64 <-> uint64 encoding,
 // the union-find of the components and the audit, the row
 // sorts (registers, the short-row ladder, the block-wide long form) and the kernel that emits kept triangles.  On the host: the workspace carver, the

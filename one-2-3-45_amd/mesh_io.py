@@ -1288,7 +1288,7 @@ def write_textured(path, positions, uv, normals, image, bounds=None, png_level=1
         write_obj_texture_files(path, obj_texture_text_numpy(p, uv, normals, obj_coordinate_digits(p if bounds is None else bounds)), png)
 
 
-def convert_mesh(ply_path, out_path, min_component_faces=0, keep_largest=False, smooth_iterations=0, decimate_cell=0, simplify_faces=0):
+def convert_mesh(ply_path, out_path, min_component_faces=0, keep_largest=False, smooth_iterations=0, decimate_cell=0, simplify_faces=0, fill_holes=0):
     """convert_mesh_format (utils/utils.py:31-47) for a mesh already on disk: read the PLY, exchange y and z, reverse the faces, write ``out_path`` by its
     extension (.glb or .obj) with the PLY's vertex colours.  ``min_component_faces`` / ``keep_largest``: filter_components on the way (off by default).
     ``smooth_iterations`` (0 = off): smooth_vertices with its default factors and pinning, after the filter, on the file's float32 positions cast to
@@ -1301,7 +1301,10 @@ def convert_mesh(ply_path, out_path, min_component_faces=0, keep_largest=False, 
     float64 (the kept vertices keep their float32 bits), the colours those of the kept vertices.  Not byte-equal to the device export either, which
     collapses the index coordinates and colours the kept vertices afterwards.
     There is no ``project_iterations`` here: projecting vertices onto the SDF's zero set (project_vertices, ops.mesh_project) needs the network, and a
-    mesh file has none; for the same reason there is no ``texture_texel``.  Returns ``out_path``."""
+    mesh file has none; for the same reason there is no ``texture_texel``.
+    ``fill_holes`` (0 = off): fill_holes with that ``max_edges`` (FILL_HOLES_ALL: every hole) after the simplification and before the smoothing, as in the
+    device chain, on the float32 positions cast to float64, the result cast back to float32; a new vertex takes the mean colour of its rim.  Returns
+    ``out_path``."""
     ext = _asset_ext(out_path)
     if ext == ".ply":
         raise ValueError("convert_mesh: the output is .glb or .obj")
@@ -1315,6 +1318,9 @@ def convert_mesh(ply_path, out_path, min_component_faces=0, keep_largest=False, 
         v = v.astype(np.float32)
     if simplify_faces:
         v, f, c, _, _, _ = simplify_mesh(v.astype(np.float64), f, simplify_faces, colors=c)
+        v = v.astype(np.float32)
+    if fill_holes:
+        v, f, c, _, _, _ = _fill_holes(v.astype(np.float64), f, fill_holes, c)
         v = v.astype(np.float32)
     if smooth_iterations:
         v = smooth_vertices(v.astype(np.float64), f, smooth_iterations).astype(np.float32)
@@ -1784,3 +1790,129 @@ def mesh_audit(verts, faces, return_elements=False):
     if return_elements:
         out.update(vertex_flags=vertex_flags, face_flags=face_flags, quality=quality)
     return out
+
+
+# ------------------------------------------------------------------------------------------------------------------ hole filling
+# the host twin of csrc/mesh_fill.hip and the DEFINITION of its result, to the last bit (include/o2345.h has the same text)
+FILL_HOLES_ALL = 2 ** 31 - 1                     # max_edges that fills every hole
+FILL_COUNTS = ("boundary", "holes", "filled", "too_long", "open", "longest", "vertices", "triangles")
+
+
+def _check_max_edges(max_edges):
+    """-> the longest hole that is filled, in edges: None = every hole, else an integer in [3, 2^31)"""
+    if max_edges is None:
+        return FILL_HOLES_ALL
+    if isinstance(max_edges, bool) or int(max_edges) != max_edges or not 3 <= max_edges < 2 ** 31:
+        raise ValueError(f"fill_holes: max_edges must be an integer in [3, 2^31) (a hole has at least three edges), got {max_edges!r}")
+    return int(max_edges)
+
+
+def boundary_loops(faces, n_vertices):
+    """The boundary of a mesh as fill_holes reads it -> (origin, holes, n_open): ``origin`` int64 [B] the start vertex of every boundary half-edge in
+    ascending half-edge order, ``holes`` the cycles as lists of positions in that order, each from its leader on in rank order, ordered by leader, and the
+    number of boundary half-edges on chains.  Half-edge 3 t + i runs from faces[t, i] to faces[t, (i + 1) % 3]; a triangle with two equal indices takes no
+    part; a half-edge is a boundary half-edge iff its undirected edge has no other half-edge.  A vertex is simple iff exactly one boundary half-edge
+    leaves it and exactly one enters it; next(h) of a boundary half-edge that enters a simple vertex is the one that leaves it.  next is injective, so the
+    boundary half-edges fall into cycles (the holes) and chains (which end at a vertex that is not simple)."""
+    f = np.asarray(faces).reshape(-1, 3).astype(np.int64, copy=False)
+    nv = int(n_vertices)
+    live = np.flatnonzero(~((f[:, 0] == f[:, 1]) | (f[:, 1] == f[:, 2]) | (f[:, 0] == f[:, 2])))
+    F = f[live]
+    u, w = F.reshape(-1), F[:, [1, 2, 0]].reshape(-1)                   # in ascending half-edge order: the faces ascend
+    _, edge, m = np.unique(np.minimum(u, w) * max(nv, 1) + np.maximum(u, w), return_inverse=True, return_counts=True)
+    on = m[edge.reshape(-1)] == 1
+    bu, bw = u[on], w[on]
+    nb = bu.size
+    simple = (np.bincount(bu, minlength=nv) == 1) & (np.bincount(bw, minlength=nv) == 1)
+    leaves = np.full(nv, -1, np.int64)
+    leaves[bu] = np.arange(nb)                                          # read at simple vertices only: one writer there
+    nxt = np.where(simple[bw], leaves[bw], -1)
+    seen = np.zeros(nb, bool)
+    starts = np.ones(nb, bool)
+    starts[nxt[nxt >= 0]] = False                                       # without a predecessor: the head of a chain
+    n_open = 0
+    for j in np.flatnonzero(starts).tolist():
+        while j >= 0:
+            seen[j] = True
+            n_open += 1
+            j = int(nxt[j])
+    holes = []
+    for j in range(nb):                                                 # ascending: the first half-edge of a cycle that turns up is its leader
+        if seen[j]:
+            continue
+        ring, k = [], j
+        while not seen[k]:
+            seen[k] = True
+            ring.append(k)
+            k = int(nxt[k])
+        assert k == j and len(ring) >= 3, "a cycle of boundary half-edges has at least three"
+        holes.append(ring)
+    return bu, holes, n_open
+
+
+def fill_holes(verts, faces, max_edges=None, colors=None, normals=None):
+    """Closes the boundary loops of a mesh (host twin of ops.mesh_fill_holes, and the definition of its result, to the last bit) -> (verts float64
+    [N + c,3], faces [M + k,3] in the dtype of ``faces``, colors, normals, hole int32 [k], info).  The holes are boundary_loops' cycles, ordered by their
+    leader (the smallest half-edge); L = a hole's number of half-edges, o_k the origin of its half-edge of rank k (the distance from the leader along
+    next).  A hole is filled iff L <= ``max_edges`` (None: every hole).  L == 3: one triangle (o_0, o_2, o_1), no new vertex.  L >= 4: one new vertex c,
+    per coordinate acc = 0; acc = acc + P[o_k] for k = 0 .. L - 1 (one sequential float64 sum); c = acc / L; and the L triangles (o_{k+1 mod L}, o_k, c)
+    in rank order.  Every new triangle carries the half-edge opposite to the one it closes: an oriented input stays oriented.  The input's vertices and
+    faces come first, bit for bit and in order; the new vertices follow in hole order, the new triangles in hole order, then rank order; ``hole`` holds
+    for every new triangle the number of its hole among the FILLED holes.  ``colors`` uint8 [N,3|4]: a new vertex takes, per channel, the mean of its
+    rim rounded half up, (2 sum + L) // (2 L); ``normals`` float [N,3]: the mean of the rim's (a sequential float64 sum / L, cast back; not
+    normalised).  ``info``: the counts of FILL_COUNTS -- boundary half-edges, holes, filled holes, holes left because L > max_edges, boundary half-edges
+    on chains (left open: they end at a bow-tie of the rim, a non-manifold edge or inconsistently oriented neighbours), the longest hole, and the sizes of
+    the output.  With no hole to fill the inputs themselves are returned.  A centroid fan is exact for a planar, star-shaped outline; for others it may
+    fold over itself, and the mesh is combinatorially closed all the same.  Refused (ValueError): max_edges below 3, a face index outside [0, N), sizes
+    beyond N + c < 2^30 or 3 (M + k) < 2^31."""
+    max_edges = _check_max_edges(max_edges)
+    p = np.ascontiguousarray(np.asarray(verts, dtype=np.float64).reshape(-1, 3))
+    fin = np.asarray(faces).reshape(-1, 3)
+    f = fin.astype(np.int64, copy=False)
+    nv, nt = p.shape[0], f.shape[0]
+    if nv >= 2 ** 30 or 3 * nt >= 2 ** 31:
+        raise ValueError(f"fill_holes: bad sizes ({nv} vertices, {nt} faces; the tables are int32)")
+    if f.size and (f.min() < 0 or f.max() >= nv):
+        raise ValueError(f"fill_holes: faces index outside 0 .. {nv - 1}")
+    origin, holes, n_open = boundary_loops(f, nv)
+    filled = [ring for ring in holes if len(ring) <= max_edges]
+    new_v, new_f, hole, new_c, new_n = [], [], [], [], []
+    for number, ring in enumerate(filled):
+        o, L = origin[ring], len(ring)
+        if L == 3:
+            new_f.append((o[0], o[2], o[1]))
+            hole.append(number)
+            continue
+        acc = np.zeros(3, np.float64)
+        for k in range(L):
+            acc = acc + p[o[k]]
+        c = nv + len(new_v)
+        new_v.append(acc / np.float64(L))
+        new_f += [(o[(k + 1) % L], o[k], c) for k in range(L)]
+        hole += [number] * L
+        if colors is not None:
+            total = np.asarray(colors)[o].astype(np.int64).sum(axis=0)
+            new_c.append(((2 * total + L) // (2 * L)).astype(np.uint8))
+        if normals is not None:
+            acc = np.zeros(3, np.float64)
+            for k in range(L):
+                acc = acc + np.asarray(normals)[o[k]].astype(np.float64)
+            new_n.append(acc / np.float64(L))
+    info = {"boundary": int(origin.size), "holes": len(holes), "filled": len(filled), "too_long": len(holes) - len(filled), "open": int(n_open),
+            "longest": max((len(r) for r in holes), default=0), "vertices": nv + len(new_v), "triangles": nt + len(new_f)}
+    if info["vertices"] >= 2 ** 30 or 3 * info["triangles"] >= 2 ** 31:
+        raise ValueError(f"fill_holes: bad sizes ({info['vertices']} vertices, {info['triangles']} faces after the fill; the tables are int32)")
+    hole = np.asarray(hole, np.int32).reshape(-1)
+    if not filled:
+        return verts, faces, colors, normals, hole, info
+    v_out = np.concatenate([p, np.asarray(new_v, np.float64).reshape(-1, 3)])
+    f_out = np.concatenate([fin, np.asarray(new_f, np.int64).reshape(-1, 3).astype(fin.dtype)])
+    c_out, n_out = colors, normals
+    if colors is not None and new_c:
+        c_out = np.concatenate([np.asarray(colors), np.asarray(new_c, np.uint8).reshape(-1, np.asarray(colors).shape[1])])
+    if normals is not None and new_n:
+        n_out = np.concatenate([np.asarray(normals), np.asarray(new_n).astype(np.asarray(normals).dtype).reshape(-1, 3)])
+    return v_out, f_out, c_out, n_out, hole, info
+
+
+_fill_holes = fill_holes                         # for convert_mesh, whose keyword of that name hides the function

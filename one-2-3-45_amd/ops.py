@@ -1309,6 +1309,37 @@ def mesh_audit(verts, tris, return_elements=False):
 
 
 # ---------------------------------------------------------------------------------------------------------- texture atlas
+# ---------------------------------------------------------------------------------------------------------- hole filling
+@_on_device
+def mesh_fill_holes(verts_idx, tris, max_edges=None):
+    """Closes the boundary loops of a mesh on the device (== mesh_io.fill_holes, to the last bit; definitions in csrc/mesh_fill.hip and include/o2345.h).
+    verts_idx fp64 [N,3], tris [M,3] int32 / int64, ``max_edges``: the longest hole, in edges, that is filled (None: the config default,
+    config.MESH_FILL_HOLES_ALL: every hole) -> (verts fp64 [N + c,3], tris [M + k,3] of the same dtype, hole int32 [k]: for every new triangle the number
+    of its hole among the filled holes, info = the counts of mesh_io.FILL_COUNTS: {"boundary", "holes", "filled", "too_long", "open", "longest",
+    "vertices", "triangles"}).  The input's vertices and triangles come first, bit for bit; a hole of three edges gets one triangle, a longer one a new
+    vertex at the mean of its rim and a fan.  The inputs are not written; the count synchronises once, and the 64-byte copy of the counts behind it finds the stream idle.  With no boundary half-edge the inputs themselves are
+    returned.  With ``max_edges == 0`` the stage is off: no kernel is launched, the inputs are returned as they are, ``hole`` and ``info`` are None."""
+    max_edges = config.mesh_fill_holes(max_edges)
+    if max_edges == 0:
+        return verts_idx, tris, None, None
+    tris, ib = _triangles(tris, "mesh_fill_holes")
+    _vertices(verts_idx, "mesh_fill_holes")
+    nv, nt, dev = verts_idx.shape[0], tris.shape[0], verts_idx.device
+    ws, wsb = _scratch("o2345_mesh_fill_workspace_bytes", (nv, nt), dev, "mesh_fill")
+    if wsb == 0:
+        raise ValueError(f"mesh_fill_holes: bad sizes ({nv} vertices, {nt} triangles; the tables are int32)")
+    counts = torch.empty(len(mesh_io.FILL_COUNTS), dtype=torch.int64, device=dev)
+    call("o2345_mesh_fill_count", tris, ib, nv, nt, max_edges, ws, wsb, counts)
+    info = dict(zip(mesh_io.FILL_COUNTS, counts.tolist()))
+    hole = torch.empty(info["triangles"] - nt, dtype=torch.int32, device=dev)
+    if info["boundary"] == 0:
+        return verts_idx, tris, hole, info
+    verts = torch.empty(info["vertices"], 3, dtype=torch.float64, device=dev)
+    tris_out = torch.empty(info["triangles"], 3, dtype=tris.dtype, device=dev)
+    call("o2345_mesh_fill_emit", verts_idx, tris, ib, nv, nt, ws, verts, tris_out, hole)
+    return verts, tris_out, hole, info
+
+
 def _texture_mesh(verts_idx, tris, what):
     t = _triangles(tris, what)
     _vertices(verts_idx, what)

@@ -236,7 +236,7 @@ def _extraction_lattice(wt, vol, resolution):
 MeshFields = namedtuple("MeshFields", "verts verts_idx tris rgb u grad info texture")
 
 
-def _mesh_fields(wt, vol, proj, cam_pos, resolution, opts):
+def _mesh_fields(wt, vol, proj, cam_pos, resolution, opts, fill_holes=0):
     """The device work of extract_mesh, once -> MeshFields; ``opts``: a config.MeshOptions.  Marching cubes, then the clean-up chain (ops.mesh_cleanup),
     then gradient and colours at the resulting vertices: the asset export reuses that gradient, the colour network's normal input, for NORMAL.
     ``texture_texel`` = c in [4, 64]: ``texture`` is the baked atlas -- "rgb", the colour network at the surface point of every texel
@@ -244,13 +244,19 @@ def _mesh_fields(wt, vol, proj, cam_pos, resolution, opts):
     that the texture is taken on the surface and not on the chord planes of a coarse mesh), "stats" (the point op's error counters, still on the
     device: mesh_io.export_asset raises on them after its copy), "layout" (mesh_io.texture_layout), "project" (the texel projection's info) and "texel".
     ``smooth_iterations``: Taubin smoothing (ops.mesh_smooth; factors and pinning from config) as the LAST step: gradient, colours and texels are taken
-    at the unsmoothed vertices, which lie on the zero set, so only ``verts`` and ``verts_idx`` differ; the result is not projected again."""
+    at the unsmoothed vertices, which lie on the zero set, so only ``verts`` and ``verts_idx`` differ; the result is not projected again.
+    ``fill_holes`` = n >= 3 (a keyword of its own, not a field of ``opts``; 0 = off: nothing is launched and ``info`` keeps its keys): ops.mesh_fill_holes
+    closes the boundary loops of at most n edges directly after the clean-up chain -- behind the projection, because a cap does not lie on the zero set
+    and must not be moved onto it, and in front of gradient, colours and texture, so that the cap's vertices and triangles are coloured and textured like
+    any other; ``info`` gains "fill", the counts of ops.mesh_fill_holes.  A filled rim is no boundary any more: the smoothing's pinning does not hold it."""
     prec = wt.sdf_precision
     # build_volume's pair: ops.scatter_dense writes zeros into vol_cl wherever maskvol is zero, which is what the sparse lattice evaluation needs (a
     # hand-made ``vol`` must keep that: points without a kept corner voxel get the empty scene's value from the second extraction on)
     u = _extraction_lattice(wt, vol, resolution)
     verts_idx, tris = ops.marching_cubes(u, 0.0)
     verts_idx, tris, info = ops.mesh_cleanup(verts_idx, tris, opts, wt.sdf_blob, vol["vol_cl"], resolution, precision=prec)
+    if fill_holes:
+        verts_idx, tris, _, info["fill"] = ops.mesh_fill_holes(verts_idx, tris, fill_holes)
     verts = _index_to_world(verts_idx, resolution)
     pts = verts.to(torch.float32).contiguous()
     if pts.shape[0] == 0:
@@ -278,42 +284,44 @@ def _texture_block(texture):
 
 @torch.no_grad()
 def extract_mesh(wt, vol, proj, cam_pos, resolution, return_index_verts=False, min_component_faces=None, keep_largest=None, smooth_iterations=None,
-                 decimate_cell=None, project_iterations=None, simplify_faces=None):
-    """extract_fields + marching cubes [+ component filter] [+ decimation] [+ simplification] [+ projection onto the zero set] + vertex colouring
-    (trainer_generic.py:1309-1363) [+ smoothing], all on the device.  The options: None = the config default, off unless set (config.mesh_options)."""
+                 decimate_cell=None, project_iterations=None, simplify_faces=None, fill_holes=None):
+    """extract_fields + marching cubes [+ component filter] [+ decimation] [+ simplification] [+ projection onto the zero set] [+ hole filling] + vertex
+    colouring (trainer_generic.py:1309-1363) [+ smoothing], all on the device.  The options: None = the config default, off unless set
+    (config.mesh_options; ``fill_holes``: config.mesh_fill_holes, the longest hole in edges that is closed)."""
     m = _mesh_fields(wt, vol, proj, cam_pos, resolution,
                      config.mesh_options(min_component_faces, keep_largest, decimate_cell, project_iterations, smooth_iterations, texture_texel=0,
-                                         simplify_faces=simplify_faces))
+                                         simplify_faces=simplify_faces), fill_holes=config.mesh_fill_holes(fill_holes))
     return (m.verts_idx if return_index_verts else m.verts), m.tris, m.rgb, m.u
 
 
 @torch.no_grad()
 def export_mesh_ply(path, wt, vol, proj, cam_pos, resolution, scale_mat=None, trans_mat=None, min_component_faces=None, keep_largest=None,
-                    smooth_iterations=None, decimate_cell=None, project_iterations=None, simplify_faces=None):
+                    smooth_iterations=None, decimate_cell=None, project_iterations=None, simplify_faces=None, fill_holes=None):
     """validate_colored_mesh end to end (trainer_generic.py:1309-1382): SDF grid, marching cubes, vertex colours, frame transforms,
     uint8 colours and the binary PLY -- records packed on the device (csrc/mesh_pack.hip), one D2H copy, one file write.
     The options are extract_mesh's.  Returns (n_vertices, n_triangles)."""
     from . import mesh_io
     verts_idx, tris, rgb, _ = extract_mesh(wt, vol, proj, cam_pos, resolution, True, min_component_faces, keep_largest, smooth_iterations, decimate_cell,
-                                           project_iterations, simplify_faces)
+                                           project_iterations, simplify_faces, fill_holes)
     return mesh_io.export_mesh(path, verts_idx, tris, resolution, scale_mat=scale_mat, trans_mat=trans_mat, vertex_colors=rgb if verts_idx.shape[0] else None)
 
 
 @torch.no_grad()
 def export_mesh_asset(path, wt, vol, proj, cam_pos, resolution, scale_mat=None, trans_mat=None, normals=False, min_component_faces=None, keep_largest=None,
-                      smooth_iterations=None, decimate_cell=None, project_iterations=None, texture_texel=None, simplify_faces=None):
+                      smooth_iterations=None, decimate_cell=None, project_iterations=None, texture_texel=None, simplify_faces=None, fill_holes=None):
     """export_mesh_ply followed by convert_mesh_format (utils/utils.py:31-47) without the PLY in between: the coloured mesh as ``.glb`` or ``.obj`` in the
     asset frame ((x, y, z) -> (x, z, y), faces reversed), buffers / text packed on the device (csrc/mesh_export.hip).  ``normals=True`` adds unit vertex
     normals from the SDF gradient the vertex colouring already computed (at the unsmoothed vertices when ``smooth_iterations`` is on, at the projected ones
     when ``project_iterations`` is).  A ``.ply`` path gives export_mesh_ply's file.  Returns (n_vertices, n_triangles).
     ``texture_texel`` (None: the config default, 0 = off) = c in [4, 64]: the textured asset instead -- the colour network baked into an atlas of one
     c x c cell per pair of triangles (_mesh_fields, ``texture``), 3 M unwelded vertices with texture coordinates and no vertex colours; the PNG sits inside
-    the ``.glb``, or as ``.mtl`` + ``.png`` next to the ``.obj``.  A ``.ply`` path with a texture requested raises ValueError."""
+    the ``.glb``, or as ``.mtl`` + ``.png`` next to the ``.obj``.  A ``.ply`` path with a texture requested raises ValueError.  ``fill_holes``:
+    extract_mesh's."""
     from . import mesh_io
     opts = config.mesh_options(min_component_faces, keep_largest, decimate_cell, project_iterations, smooth_iterations, texture_texel, simplify_faces)
     if opts.texture_texel and mesh_io._asset_ext(path) == ".ply":
         raise ValueError("texture: a .ply has no texture coordinates; the output is .glb or .obj")
-    m = _mesh_fields(wt, vol, proj, cam_pos, resolution, opts)
+    m = _mesh_fields(wt, vol, proj, cam_pos, resolution, opts, fill_holes=config.mesh_fill_holes(fill_holes))
     return mesh_io.export_asset(path, m.verts_idx, m.tris, resolution, scale_mat=scale_mat, trans_mat=trans_mat,
                                 vertex_colors=m.rgb if m.verts_idx.shape[0] else None, normals=m.grad if normals else None, texture=m.texture)
 
@@ -428,7 +436,7 @@ def _write_previews(wt, vol, proj, cam_pos, u, s, n, folder):
 @torch.no_grad()
 def reconstruct_folder(root_dir, name, wt, out_ply, D=96, resolution=256, render_val_image=False, output_format=None, min_component_faces=None,
                        keep_largest=None, smooth_iterations=None, decimate_cell=None, project_iterations=None, texture_texel=None, preview_views=None, mesh_error=None,
-                       simplify_faces=None, mesh_audit=None):
+                       simplify_faces=None, mesh_audit=None, fill_holes=None):
     """run.py's reconstruction stage without the reference tree: Zero123-style folder (dataset.SceneFolder) -> coloured mesh (binary PLY in
     the original frame), optionally the val image of the target view.  ``output_format`` ".obj" / ".glb" (run.py --output_format) also writes
     ``mesh<ext>`` next to ``out_ply`` in the asset frame, from the same device buffers.  The mesh options are extract_mesh's.  Returns
@@ -446,7 +454,9 @@ def reconstruct_folder(root_dir, name, wt, out_ply, D=96, resolution=256, render
     and thresholds 0.25, 0.5, 1 and 2.  "a_to_b" is the geometric error of what was kept; "b_to_a" also contains whatever the component filter dropped.
     ``mesh_audit`` (None: the config default O2345_MESH_AUDIT, off: nothing is launched and the result has no new key): the result gains "mesh_audit",
     the report of ops.mesh_audit on the final mesh in index coordinates -- is it a closed, oriented 2-manifold, and how good are its triangles; area and
-    volume in units of the extraction grid's spacing."""
+    volume in units of the extraction grid's spacing.  ``fill_holes`` (None: the config default O2345_MESH_FILL_HOLES, 0 = off: nothing is launched, the
+    result has no new key and every file keeps its bytes) = n >= 3: the boundary loops of at most n edges are closed after the clean-up chain
+    (ops.mesh_fill_holes; config.MESH_FILL_HOLES_ALL: every one); the result gains "fill_holes", its counts."""
     import os
     from . import dataset, mesh_io
     if output_format not in (None, ".ply", ".obj", ".glb"):
@@ -458,13 +468,16 @@ def reconstruct_folder(root_dir, name, wt, out_ply, D=96, resolution=256, render
     proj, cam_pos = camera_terms(T(s["intrinsics"]), T(s["w2cs"]))
     opts = config.mesh_options(min_component_faces, keep_largest, decimate_cell, project_iterations, smooth_iterations, texture_texel, simplify_faces)
     previews = config.preview_views(preview_views)
+    fill = config.mesh_fill_holes(fill_holes)
     asset = output_format in (".obj", ".glb")
-    m = _mesh_fields(wt, vol, proj, cam_pos, resolution, opts if asset else opts._replace(texture_texel=0))          # the atlas is for the asset only
+    m = _mesh_fields(wt, vol, proj, cam_pos, resolution, opts if asset else opts._replace(texture_texel=0), fill_holes=fill)          # the atlas is for the asset only
     rgb = m.rgb if m.verts_idx.shape[0] else None
     nv, nt = mesh_io.export_mesh(out_ply, m.verts_idx, m.tris, resolution, scale_mat=s["scale_mat"], trans_mat=s["trans_mat"], vertex_colors=rgb)
     out = {"vertices": nv, "triangles": nt, "kept_voxels": int(vol["n_voxels"]), "ply": str(out_ply), "components": m.info["components"],
            "components_kept": m.info["components_kept"], "smooth_iterations": opts.smooth_iterations, "decimate_cell": opts.decimate_cell,
            "decimate": m.info["decimate"], "simplify_faces": opts.simplify_faces, "simplify": m.info["simplify"], "project_iterations": opts.project_iterations, "project": m.info["project"], "texture": _texture_block(m.texture)}
+    if fill:
+        out["fill_holes"] = m.info["fill"]
     if asset:
         out["asset"] = os.path.join(os.path.dirname(str(out_ply)), "mesh" + output_format)
         mesh_io.export_asset(out["asset"], m.verts_idx, m.tris, resolution, scale_mat=s["scale_mat"], trans_mat=s["trans_mat"], vertex_colors=rgb,

@@ -512,6 +512,10 @@ class SparseNeuSRenderer(nn.Module):
         opts = config.mesh_options()
         v, t, _ = ops.mesh_cleanup(v, t, opts, self.sdf_network.sdf_layer.blob(), channel_last(kwargs["conditional_volume"]), int(resolution),
                                    level=-float(threshold), bound_min=bound_min, bound_max=bound_max, project=occupancy_mask is None)
+        # hole filling (O2345_MESH_FILL_HOLES, off by default: nothing is launched) behind the projection -- a cap is not on the level set -- and in front of
+        # the smoothing, whose pinning no longer holds a rim that was closed
+        if config.mesh_fill_holes():
+            v, t, _, _ = ops.mesh_fill_holes(v, t, config.mesh_fill_holes())
         # Taubin smoothing last: the runner colours after this call, so here at the SMOOTHED positions (pipeline._mesh_fields colours first)
         if opts.smooth_iterations:
             v = ops.mesh_smooth(v, t, opts.smooth_iterations)
