@@ -67,7 +67,7 @@ const char* o2345_last_error(void);
  * o2345_mesh_simplify_workspace_bytes, o2345_mesh_simplify_count, o2345_mesh_simplify_emit; the audit entries o2345_mesh_audit_workspace_bytes,
  * o2345_mesh_audit.
  * Additive since 2.3 (no existing entry changed, the version stays 230): the hole-filling entries o2345_mesh_fill_workspace_bytes, o2345_mesh_fill_count,
- * o2345_mesh_fill_emit. */
+ * o2345_mesh_fill_emit; the self-intersection entries o2345_mesh_intersect_workspace_bytes, o2345_mesh_intersect_count, o2345_mesh_intersect_emit. */
 int o2345_version(void);
 /* Layout self-description of the declared structs as THIS library was compiled (sizeof, and offsetof of every field in declaration order): a binding
  * asserts its own structs against it at load time (one-2-3-45_amd/_lib.py does) -- a field added on one side only cannot corrupt calls silently.
@@ -801,6 +801,37 @@ int o2345_mesh_fill_count(const void* tris, int index_bytes, long long nv, long 
                           long long* counts, void* stream);
 int o2345_mesh_fill_emit(const double* verts, const void* tris, int index_bytes, long long nv, long long nt, void* workspace,
                          double* verts_out, void* tris_out, int* hole, void* stream);
+/* ---- self-intersections of a mesh: which pairs of triangles cross (additive since 2.3; none in the reference: its users find out in another tool) ---------
+ * Read-only; equal to the host twin mesh_io.mesh_intersections to the last bit: counts, per-face hits and the pair list.  Everything is fp64, one operation
+ * at a time, in the order written (csrc/mesh_intersect_math.h is the text); only comparisons decide.  verts device fp64 [nv,3], tris device int32 / int64
+ * [nt,3] (index_bytes 4 / 8), both only read; 0 <= nv < 2^30, 3 * nt < 2^31.
+ *   orient     orient(A, B, C, D): a = A - D, b = B - D, c = C - D; X = b_y c_z - b_z c_y, Y = b_z c_x - b_x c_z, Z = b_x c_y - b_y c_x; the value is
+ *              (a_x X + a_y Y) + a_z Z.
+ *   crossing   the segment PQ crosses the triangle (A, B, C) iff, with sP = orient(A,B,C,P) and sQ = orient(A,B,C,Q), (sP > 0 and sQ < 0) or (sP < 0 and
+ *              sQ > 0), and orient(P,Q,A,B), orient(P,Q,B,C), orient(P,Q,C,A) are all > 0 or all < 0.  A zero or a NaN anywhere: no crossing.
+ *   faces      a triangle TAKES PART iff its indices lie in [0, nv), its coordinates are finite, n . n != 0 for n = (P1 - P0) x (P2 - P0) (the grid's
+ *              "usable") and its three indices are distinct; the others are skipped and counted.
+ *   candidates a pair t < u of faces that take part whose closed bounding boxes overlap on every axis (lo_t <= hi_u and lo_u <= hi_t) and that share at most
+ *              one vertex INDEX.  Pairs that share an edge are never tested: a fold along an edge is the audit's "creased".
+ *   pairs      a candidate intersects iff for (X, Y) = (t, u) or (u, t) and some i in 0, 1, 2 the edge (X[i], X[(i + 1) % 3]), neither of whose indices is
+ *              an index of Y, crosses Y, Y's corners in stored order.
+ * grid: the grid object of o2345_mesh_distance_grid_emit over the same verts and tris, with its size and the max_cells it was built with; two overlapping
+ * boxes both contain the point max(lo_t, lo_u), so a pair is handled in the one cell that holds that point, by one thread per grid entry against the
+ * later entries of its ascending row.  grid NULL: every t against every u > t, for nt <= 2^16; the same bytes either way, and whatever the cell edge.
+ * Two calls.  _count (workspace: mesh_intersect_workspace_bytes(nv, nt) bytes, 0 for bad sizes; 16-byte aligned) writes counts, device int64 [8], 8-byte
+ * aligned: triangles with an index outside [0, nv), triangles with a non-finite coordinate, faces that take part, faces skipped, candidates, pairs, faces
+ * in at least one pair, the most pairs one face is in -- the caller copies them; when one of the first two is not 0 the rest is void (such triangles are
+ * counted, never dereferenced, and take no part).  face_hits_or_null: device int32 [nt], the pairs each face is in.  No host synchronisation.  _emit (same
+ * arguments and workspace, untouched in between; n_pairs as counted, below 2^30) writes pairs, device int32 [n_pairs,2]: t < u, sorted lexicographically;
+ * the same bytes on every run.  Integer atomics only; no kernel waits for another workgroup.
+ * Not counted, not done: coplanar overlap and contacts that only touch (a zero determinant is no crossing); a closed component nested inside another
+ * without crossing it; the unfiltered fp64 determinant may take the wrong sign next to a degeneracy (the twin takes the same one); coincident vertices
+ * with different indices (an unwelded mesh) touch without being counted; no repair. */
+size_t o2345_mesh_intersect_workspace_bytes(long long nv, long long nt);
+int o2345_mesh_intersect_count(const double* verts, const void* tris, int index_bytes, long long nv, long long nt, const void* grid, size_t grid_bytes,
+                               long long max_cells, void* workspace, size_t workspace_bytes, long long* counts, int* face_hits_or_null, void* stream);
+int o2345_mesh_intersect_emit(const double* verts, const void* tris, int index_bytes, long long nv, long long nt, const void* grid, size_t grid_bytes,
+                              long long max_cells, void* workspace, long long n_pairs, int* pairs, void* stream);
 /* Load every code object of the library on the current device now (the HIP runtime loads a translation unit's kernels at its first launch: 5 - 60 ms
  * each for the units of this library, which otherwise land inside the first calls of a fresh process).  Launches nothing that touches user memory. */
 int o2345_preload(void);

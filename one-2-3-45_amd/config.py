@@ -362,6 +362,17 @@ def mesh_audit(x=None):
     return MESH_AUDIT if x is None else bool(x)
 
 
+# ---- self-intersection report (csrc/mesh_intersect.hip; mesh_io.mesh_intersections is the host twin) -----------------------------------------------------
+# O2345_MESH_INTERSECTIONS=1 makes pipeline.reconstruct_folder report how many pairs of triangles of the mesh it wrote cross each other
+# (ops.mesh_intersections: candidates, pairs, faces hit, the most pairs on one face) -- what the audit, a statement about connectivity, cannot say ("" or
+# "0" = off, the default: nothing is launched and the result keeps its keys).
+MESH_INTERSECTIONS = _non_negative_int("O2345_MESH_INTERSECTIONS", os.environ.get("O2345_MESH_INTERSECTIONS", "")) != 0
+
+
+def mesh_intersections(x=None):
+    return MESH_INTERSECTIONS if x is None else bool(x)
+
+
 # ---- hole filling (csrc/mesh_fill.hip; mesh_io.fill_holes is the host twin) -------------------------------------------------------------------------------
 # O2345_MESH_FILL_HOLES=n closes the boundary loops of the extracted mesh that have at most n edges, on the device, directly after the clean-up chain and
 # before the vertices are coloured: a loop of three edges gets one triangle, a longer one a fan around its centroid ("" or "0" = off, the default: nothing

@@ -37,6 +37,7 @@ int preload_mesh_texture();
 int preload_mesh_distance();
 int preload_mesh_audit();
 int preload_mesh_fill();
+int preload_mesh_intersect();
 int preload_surface_trace();
 int preload_featmaps();
 int preload_convnet();
@@ -69,6 +70,7 @@ int o2345_preload(void) {
     if ((e = o2345::preload_mesh_distance())) bad = e;
     if ((e = o2345::preload_mesh_audit())) bad = e;
     if ((e = o2345::preload_mesh_fill())) bad = e;
+    if ((e = o2345::preload_mesh_intersect())) bad = e;
     if ((e = o2345::preload_surface_trace())) bad = e;
     if ((e = o2345::preload_featmaps())) bad = e;
     if ((e = o2345::preload_convnet())) bad = e;

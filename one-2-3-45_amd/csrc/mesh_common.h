@@ -1,5 +1,5 @@
 // What the mesh units share.  The units: mcubes.hip, mesh_components.hip, mesh_smooth.hip and mesh_simplify.hip (both through mesh_adjacency.h),
-// mesh_decimate.hip, mesh_project.hip, mesh_texture.hip, mesh_distance.hip, mesh_audit.hip, mesh_fill.hip, mesh_export.hip, mesh_pack.hip, and surface_trace.hip for the wave
+// mesh_decimate.hip, mesh_project.hip, mesh_texture.hip, mesh_distance.hip, mesh_audit.hip, mesh_fill.hip, mesh_intersect.hip, mesh_export.hip, mesh_pack.hip, and surface_trace.hip for the wave
 // sums and finite().  On the device: the triangle reader, the wave-level counter and reductions, finite(), the order-preserving fp64 <-> uint64 encoding,
 // the union-find of the components and the audit, the row
 // sorts (registers, the short-row ladder, the block-wide long form) and the kernel that emits kept triangles.  On the host: the workspace carver, the
@@ -98,10 +98,10 @@ __device__ __forceinline__ void cc_union(int* parent, int a, int b) {
 }
 
 // r = the d <= N entries of row, ascending, then ROW_PAD
-template <int N>
+template <int N, int STRIDE = 1>
 __device__ __forceinline__ void row_sorted_regs(const int* __restrict__ row, int d, int (&r)[N]) {
 #pragma unroll
-    for (int k = 0; k < N; ++k) r[k] = k < d ? row[k] : ROW_PAD;
+    for (int k = 0; k < N; ++k) r[k] = k < d ? row[STRIDE * k] : ROW_PAD;
     sort_regs<N>(r);
 }
 
@@ -124,21 +124,23 @@ __device__ __forceinline__ void row_rank_sort(const int* row, int* srt, int d) {
 // Sorting an unordered CSR row in place.  A kernel with one thread per row lists the rows above ROW_SHORT entries for a second kernel with one block per
 // listed row (row_sort_long) and sorts the others itself (row_sort_short); a row of one entry or none is sorted as it is.
 
-// row[0 .. d) ascending, d <= N, by its own thread in registers
-template <int N>
+// row[0 .. d) ascending, d <= N, by its own thread in registers.  STRIDE: the distance in ints between two entries of the row (one column of an [n, STRIDE]
+// array: the pairs of mesh_intersect.hip)
+template <int N, int STRIDE = 1>
 __device__ __forceinline__ void row_sort_regs_in_place(int* __restrict__ row, int d) {
     int r[N];
-    row_sorted_regs<N>(row, d, r);
+    row_sorted_regs<N, STRIDE>(row, d, r);
 #pragma unroll
     for (int k = 0; k < N; ++k)
-        if (k < d) row[k] = r[k];
+        if (k < d) row[STRIDE * k] = r[k];
 }
 
 // row[0 .. d) ascending for 1 < d <= ROW_SHORT: the smallest of three register networks that holds the row
+template <int STRIDE = 1>
 __device__ __forceinline__ void row_sort_short(int* __restrict__ row, int d) {
-    if (d > 16) row_sort_regs_in_place<ROW_SHORT>(row, d);
-    else if (d > 4) row_sort_regs_in_place<16>(row, d);
-    else row_sort_regs_in_place<4>(row, d);
+    if (d > 16) row_sort_regs_in_place<ROW_SHORT, STRIDE>(row, d);
+    else if (d > 4) row_sort_regs_in_place<16, STRIDE>(row, d);
+    else row_sort_regs_in_place<4, STRIDE>(row, d);
 }
 
 // row[0 .. d) ascending by one 256-thread block: rank sort into tmp, copied back.  On return tmp[0 .. d) is the sorted row, complete for the whole

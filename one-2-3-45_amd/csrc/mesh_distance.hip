@@ -26,15 +26,13 @@
 //              the same tree).  The longest chain of additions is 16 + 8 + n / 2^20 + 8 <= 288: a relative error of at most 3.2e-14 for the
 //              non-negative terms, and the same bits on every run.  No floating-point atomics anywhere.
 // Bad input never faults: an index outside [0, nv) is counted and never dereferenced, a non-finite coordinate is counted; count() returns them as errors.
-#include "mesh_common.h"
-#include "mesh_distance_math.h"
+#include "mesh_grid.h"
 
 namespace o2345 {
 
 constexpr long long MD_MAX_SAMPLES = 1ll << 28;
 constexpr int MD_THRESHOLDS = sizeof(O2345DistanceStats::within) / sizeof(double);          // 8 (the device block of the reduction: include/o2345.h)
 constexpr int MD_AXIS = 256;                          // cells per axis at most
-constexpr long long MD_MAX_CELLS = 1ll << 24;
 constexpr int MD_RED_ITEMS = 16;                      // samples per thread of k_md_reduce
 constexpr int MD_RED_TILE = 256 * MD_RED_ITEMS;
 constexpr int MD_RED_COLS = 3 + MD_THRESHOLDS;        // sum w, sum w d, sum w d^2, within[8]
@@ -474,19 +472,6 @@ static size_t md_grid_carve(void* ws, long long nt, long long max_cells, MdGridC
     c.long_list = w.take<int>(max_cells);
     c.block = w.take<int>(c.nb);
     c.usable = w.take<unsigned char>(nt);
-    return w.bytes();
-}
-
-struct MdGridObject {
-    MdGridHead* head;
-    int *cell_start, *entries;
-};
-
-static size_t md_grid_object(void* grid, long long max_cells, long long n_entries, MdGridObject& g) {
-    Carver w(grid);
-    g.head = w.take_bytes<MdGridHead>(128);
-    g.cell_start = w.take<int>(max_cells + 1);
-    g.entries = w.take<int>(n_entries);
     return w.bytes();
 }
 

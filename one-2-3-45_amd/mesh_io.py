@@ -1916,3 +1916,93 @@ def fill_holes(verts, faces, max_edges=None, colors=None, normals=None):
 
 
 _fill_holes = fill_holes                         # for convert_mesh, whose keyword of that name hides the function
+
+
+# ------------------------------------------------------------------------------------------------------------------ self-intersections
+# the host twin of csrc/mesh_intersect.hip and the DEFINITION of its result, to the last bit (include/o2345.h has the same text; csrc/mesh_intersect_math.h
+# the device form).  All arithmetic is float64, one operation at a time, in the order written; only comparisons decide.
+INTERSECT_COUNTS = ("bad_index", "nonfinite", "faces", "skipped", "candidates", "pairs", "faces_hit", "max_hits")
+INTERSECT_EXHAUSTIVE_MAX = 2 ** 16               # the device's exhaustive path (no grid) takes at most this many triangles
+
+
+def intersect_orient(A, B, C, D):
+    """orient(A, B, C, D) on arrays [..., 3]: a = A - D, b = B - D, c = C - D, X = b_y c_z - b_z c_y, Y = b_z c_x - b_x c_z, Z = b_x c_y - b_y c_x ->
+    (a_x X + a_y Y) + a_z Z: six times the signed volume of the tetrahedron, unfiltered"""
+    with np.errstate(all="ignore"):                                     # products may overflow or underflow: the results are IEEE's either way
+        a, b, c = A - D, B - D, C - D
+        X = b[..., 1] * c[..., 2] - b[..., 2] * c[..., 1]
+        Y = b[..., 2] * c[..., 0] - b[..., 0] * c[..., 2]
+        Z = b[..., 0] * c[..., 1] - b[..., 1] * c[..., 0]
+        return (a[..., 0] * X + a[..., 1] * Y) + a[..., 2] * Z
+
+
+def segment_crosses_triangle(P, Q, A, B, C):
+    """Does the segment PQ cross the triangle (A, B, C), arrays [..., 3] -> bool [...]: P and Q strictly on opposite sides of the triangle's plane, and
+    orient(P,Q,A,B), orient(P,Q,B,C), orient(P,Q,C,A) all > 0 or all < 0.  A zero or a NaN anywhere: no crossing (touching and coplanar contacts are
+    not counted)."""
+    sP, sQ = intersect_orient(A, B, C, P), intersect_orient(A, B, C, Q)
+    o1, o2, o3 = intersect_orient(P, Q, A, B), intersect_orient(P, Q, B, C), intersect_orient(P, Q, C, A)
+    with np.errstate(invalid="ignore"):
+        return (((sP > 0.0) & (sQ < 0.0)) | ((sP < 0.0) & (sQ > 0.0))) & (((o1 > 0.0) & (o2 > 0.0) & (o3 > 0.0)) | ((o1 < 0.0) & (o2 < 0.0) & (o3 < 0.0)))
+
+
+def triangles_intersect(p, ft, fu):
+    """The narrow phase on candidates: vertices p [N,3], faces ft and fu int64 [n,3] that share at most one index -> bool [n]: some edge (X[i], X[(i + 1)
+    % 3]) of one face, neither end an index of the other face Y, crosses Y with Y's corners in stored order; (X, Y) = (t, u), then (u, t)."""
+    hit = np.zeros(ft.shape[0], bool)
+    for X, Y in ((ft, fu), (fu, ft)):
+        A, B, C = p[Y[:, 0]], p[Y[:, 1]], p[Y[:, 2]]
+        for i in range(3):
+            a, b = X[:, i], X[:, (i + 1) % 3]
+            free = ~((a[:, None] == Y).any(1) | (b[:, None] == Y).any(1))
+            hit |= free & segment_crosses_triangle(p[a], p[b], A, B, C)
+    return hit
+
+
+def intersect_report(counts):
+    """The eight counts of INTERSECT_COUNTS, in order -> the report both mesh_intersections and ops.mesh_intersections return"""
+    return {k: int(x) for k, x in zip(INTERSECT_COUNTS, counts)}
+
+
+def mesh_intersections(verts, faces, return_pairs=False):
+    """The self-intersections of an indexed triangle mesh on the host (the twin of ops.mesh_intersections, and the definition of its result): which
+    pairs of triangles cross.  verts [N,3] (float64), faces int32 / int64 [M,3]; an index outside [0, N) and a non-finite coordinate of a referenced
+    vertex are errors.  A face TAKES PART iff n . n != 0 for n = (P1 - P0) x (P2 - P0) (_normal2) and its three indices are distinct; the others are
+    skipped and counted.  A pair t < u of faces that take part is a CANDIDATE iff their closed bounding boxes overlap on every axis and they share at
+    most one vertex index (a fold along a shared edge is the audit's "creased"; coincident vertices with different indices share nothing).  A candidate
+    INTERSECTS iff triangles_intersect says so: an edge of one, free of the other's indices, crosses the other strictly (segment_crosses_triangle).
+    -> {"bad_index": 0, "nonfinite": 0, "faces", "skipped", "candidates", "pairs", "faces_hit": faces in at least one pair, "max_hits": the most pairs
+    one face is in}; ``return_pairs`` adds "pairs_list" int32 [n,2] (t < u, sorted lexicographically) and "face_hits" int32 [M].  Candidates are found by
+    brute force over t, vectorised over u.  Nothing depends on face order beyond the numbering of the pairs.  Not counted: coplanar overlap, contacts
+    that only touch, a closed component nested inside another; the unfiltered determinant may take the wrong sign next to a degeneracy (the device
+    takes the same one)."""
+    p, f = _distance_mesh(verts, faces, "mesh_intersections")
+    nv, nt = p.shape[0], f.shape[0]
+    if nv >= 2 ** 30 or 3 * nt >= 2 ** 31:
+        raise ValueError(f"mesh_intersections: bad sizes ({nv} vertices, {nt} faces; the tables are int32)")
+    P0, P1, P2 = p[f[:, 0]], p[f[:, 1]], p[f[:, 2]]
+    with np.errstate(all="ignore"):
+        part = (_normal2(P0, P1, P2) != 0.0) & (f[:, 0] != f[:, 1]) & (f[:, 1] != f[:, 2]) & (f[:, 0] != f[:, 2])
+    corners = np.stack([P0, P1, P2], 1)                                  # [M,3,3]
+    lo, hi = np.ascontiguousarray(corners.min(1).T), np.ascontiguousarray(corners.max(1).T)      # [3,M]: one contiguous row per axis
+    cand = []
+    for t in np.flatnonzero(part)[:-1] if part.any() else ():
+        near = part[t + 1:].copy()
+        for d in range(3):
+            near &= lo[d, t] <= hi[d, t + 1:]
+            near &= lo[d, t + 1:] <= hi[d, t]
+        u = t + 1 + np.flatnonzero(near)
+        u = u[(f[t][None, :, None] == f[u][:, None, :]).any(2).sum(1) <= 1]
+        cand.append(np.stack([np.full(u.size, t, np.int64), u], 1))
+    cand = np.concatenate(cand) if cand else np.zeros((0, 2), np.int64)
+    candidates = cand.shape[0]
+    hit = np.zeros(candidates, bool)
+    for k in range(0, candidates, 1 << 16):
+        hit[k:k + (1 << 16)] = triangles_intersect(p, f[cand[k:k + (1 << 16), 0]], f[cand[k:k + (1 << 16), 1]])
+    pairs = cand[hit].astype(np.int32)                                   # brute force over t, ascending u: sorted as it comes
+    face_hits = (np.bincount(pairs[:, 0], minlength=nt) + np.bincount(pairs[:, 1], minlength=nt)).astype(np.int32)
+    out = intersect_report((0, 0, np.count_nonzero(part), nt - np.count_nonzero(part), candidates, pairs.shape[0], np.count_nonzero(face_hits),
+                            face_hits.max() if nt else 0))
+    if return_pairs:
+        out.update(pairs_list=pairs, face_hits=face_hits)
+    return out

@@ -1308,6 +1308,59 @@ def mesh_audit(verts, tris, return_elements=False):
     return out
 
 
+# ---------------------------------------------------------------------------------------------------------- self-intersections
+def intersect_info(counts, nv):
+    """The eight counts of o2345_mesh_intersect_count, on the host -> the report of mesh_io.mesh_intersections; raises on a triangle index out of range
+    or a non-finite coordinate (the rest is void then)."""
+    out = mesh_io.intersect_report(counts)
+    if out["bad_index"]:
+        raise RuntimeError(f"o2345 mesh_intersections: {out['bad_index']} triangles index outside 0 .. {nv - 1}")
+    if out["nonfinite"]:
+        raise RuntimeError(f"o2345 mesh_intersections: {out['nonfinite']} triangles have a non-finite vertex coordinate")
+    return out
+
+
+@_on_device
+def mesh_intersections(verts, tris, return_pairs=False, cell=None, grid=True):
+    """The self-intersections of a mesh on the device (== mesh_io.mesh_intersections, its host twin and the definition, to the last bit;
+    csrc/mesh_intersect.hip): which pairs of triangles cross.  verts fp64 [N,3], tris [M,3] int32 / int64, both only read -> the twin's dict: "faces"
+    (that take part), "skipped", "candidates" (boxes overlap, at most one shared index), "pairs", "faces_hit", "max_hits" ("bad_index" and "nonfinite"
+    are 0: they raise).  The broad phase walks the grid of mesh_distance_grid(verts, tris, cell); a mesh of fewer than 64 triangles, or ``grid=False``
+    (at most 2^16 triangles), is searched exhaustively -- the same result either way, whatever the cell edge.  A mesh without a triangle that has an
+    area gives the all-zero report.  The grid's count synchronises once; the report is ONE copy of the eight counts.  ``return_pairs`` adds the device
+    tensors "pairs_list" int32 [n,2] (t < u, sorted lexicographically; the same bytes on every run) and "face_hits" int32 [M].  Not counted: coplanar
+    overlap, contacts that only touch, nested components, coincident vertices with different indices."""
+    tris, ib = _triangles(tris, "mesh_intersections")
+    _vertices(verts, "mesh_intersections")
+    nv, nt, dev = verts.shape[0], tris.shape[0], verts.device
+    ws, wsb = _scratch("o2345_mesh_intersect_workspace_bytes", (nv, nt), dev, "mesh_intersect")
+    if not wsb:
+        raise ValueError(f"mesh_intersections: bad sizes ({nv} vertices, {nt} triangles; the tables are int32)")
+    g = None
+    if grid and nt >= _DISTANCE_EXHAUSTIVE_BELOW:
+        try:
+            g = mesh_distance_grid(verts, tris, cell)
+        except RuntimeError as e:
+            if "no triangle with an area" not in str(e):
+                raise                                                     # a bad index and a non-finite coordinate are the grid's refusals too
+            g = None                                                      # nothing takes part: the exhaustive kernel finds that out per face
+            if nt > mesh_io.INTERSECT_EXHAUSTIVE_MAX:
+                out = mesh_io.intersect_report((0, 0, 0, nt, 0, 0, 0, 0))
+                if return_pairs:
+                    out.update(pairs_list=torch.zeros(0, 2, dtype=torch.int32, device=dev), face_hits=torch.zeros(nt, dtype=torch.int32, device=dev))
+                return out
+    gp, gb, gm = (g.buffer, g.buffer.numel(), g.max_cells) if g is not None else (None, 0, 0)
+    counts = torch.empty(len(mesh_io.INTERSECT_COUNTS), dtype=torch.int64, device=dev)
+    face_hits = torch.empty(nt, dtype=torch.int32, device=dev) if return_pairs else None
+    call("o2345_mesh_intersect_count", verts, tris, ib, nv, nt, gp, gb, gm, ws, wsb, counts, face_hits)
+    out = intersect_info(counts.tolist(), nv)
+    if return_pairs:
+        pairs = torch.empty(out["pairs"], 2, dtype=torch.int32, device=dev)
+        call("o2345_mesh_intersect_emit", verts, tris, ib, nv, nt, gp, gb, gm, ws, out["pairs"], pairs)
+        out.update(pairs_list=pairs, face_hits=face_hits)
+    return out
+
+
 # ---------------------------------------------------------------------------------------------------------- texture atlas
 # ---------------------------------------------------------------------------------------------------------- hole filling
 @_on_device

@@ -364,6 +364,17 @@ def mesh_audit(mesh, return_elements=False):
     return ops.mesh_audit(*_device_mesh(mesh, dev), return_elements)
 
 
+@torch.no_grad()
+def mesh_intersections(mesh, return_pairs=False):
+    """The self-intersections of a mesh on the device (ops.mesh_intersections; definitions in mesh_io.mesh_intersections, its host twin): ``mesh`` is a
+    (verts [N,3], tris [M,3]) pair of device tensors or host arrays -- host arrays are uploaded, to the device of the first device tensor of the pair,
+    else the current one.  -> the twin's dict: "faces", "skipped", "candidates", "pairs", "faces_hit", "max_hits"; ``return_pairs`` adds the device
+    tensors "pairs_list" int32 [n,2] and "face_hits" int32 [M]."""
+    dev = next((x.device for x in mesh if torch.is_tensor(x) and x.is_cuda), None)
+    dev = torch.device("cuda", torch.cuda.current_device()) if dev is None else dev
+    return ops.mesh_intersections(*_device_mesh(mesh, dev), return_pairs)
+
+
 def _surface_view(wt, vol, proj, cam_pos, u, flags, intrinsic, c2w, H, W, near, far, stride, refine, background):
     """one image of render_surface from a lattice and its brick flags"""
     dev = u.device
@@ -436,7 +447,7 @@ def _write_previews(wt, vol, proj, cam_pos, u, s, n, folder):
 @torch.no_grad()
 def reconstruct_folder(root_dir, name, wt, out_ply, D=96, resolution=256, render_val_image=False, output_format=None, min_component_faces=None,
                        keep_largest=None, smooth_iterations=None, decimate_cell=None, project_iterations=None, texture_texel=None, preview_views=None, mesh_error=None,
-                       simplify_faces=None, mesh_audit=None, fill_holes=None):
+                       simplify_faces=None, mesh_audit=None, fill_holes=None, mesh_intersections=None):
     """run.py's reconstruction stage without the reference tree: Zero123-style folder (dataset.SceneFolder) -> coloured mesh (binary PLY in
     the original frame), optionally the val image of the target view.  ``output_format`` ".obj" / ".glb" (run.py --output_format) also writes
     ``mesh<ext>`` next to ``out_ply`` in the asset frame, from the same device buffers.  The mesh options are extract_mesh's.  Returns
@@ -456,7 +467,9 @@ def reconstruct_folder(root_dir, name, wt, out_ply, D=96, resolution=256, render
     the report of ops.mesh_audit on the final mesh in index coordinates -- is it a closed, oriented 2-manifold, and how good are its triangles; area and
     volume in units of the extraction grid's spacing.  ``fill_holes`` (None: the config default O2345_MESH_FILL_HOLES, 0 = off: nothing is launched, the
     result has no new key and every file keeps its bytes) = n >= 3: the boundary loops of at most n edges are closed after the clean-up chain
-    (ops.mesh_fill_holes; config.MESH_FILL_HOLES_ALL: every one); the result gains "fill_holes", its counts."""
+    (ops.mesh_fill_holes; config.MESH_FILL_HOLES_ALL: every one); the result gains "fill_holes", its counts.  ``mesh_intersections`` (None: the config
+    default O2345_MESH_INTERSECTIONS, off: nothing is launched and the result has no new key): the result gains "mesh_intersections", the counts of
+    ops.mesh_intersections on the final mesh in index coordinates -- how many pairs of its triangles cross, which the audit cannot say."""
     import os
     from . import dataset, mesh_io
     if output_format not in (None, ".ply", ".obj", ".glb"):
@@ -487,6 +500,8 @@ def reconstruct_folder(root_dir, name, wt, out_ply, D=96, resolution=256, render
         out["mesh_error"] = ops.mesh_distance(m.verts_idx, m.tris, raw_verts, raw_tris, MESH_ERROR_SPACING, MESH_ERROR_THRESHOLDS)
     if config.mesh_audit(mesh_audit):
         out["mesh_audit"] = ops.mesh_audit(m.verts_idx, m.tris)
+    if config.mesh_intersections(mesh_intersections):
+        out["mesh_intersections"] = ops.mesh_intersections(m.verts_idx, m.tris)
     if previews:
         out["previews"] = _write_previews(wt, vol, proj, cam_pos, m.u, s, previews, os.path.dirname(str(out_ply)))
     if render_val_image:
