@@ -67,7 +67,8 @@ const char* o2345_last_error(void);
  * o2345_mesh_simplify_workspace_bytes, o2345_mesh_simplify_count, o2345_mesh_simplify_emit; the audit entries o2345_mesh_audit_workspace_bytes,
  * o2345_mesh_audit.
  * Additive since 2.3 (no existing entry changed, the version stays 230): the hole-filling entries o2345_mesh_fill_workspace_bytes, o2345_mesh_fill_count,
- * o2345_mesh_fill_emit; the self-intersection entries o2345_mesh_intersect_workspace_bytes, o2345_mesh_intersect_count, o2345_mesh_intersect_emit. */
+ * o2345_mesh_fill_emit; the self-intersection entries o2345_mesh_intersect_workspace_bytes, o2345_mesh_intersect_count, o2345_mesh_intersect_emit; the
+ * rasterizer entries o2345_mesh_raster_workspace_bytes, o2345_mesh_raster_count, o2345_mesh_raster_emit, o2345_mesh_raster_shade. */
 int o2345_version(void);
 /* Layout self-description of the declared structs as THIS library was compiled (sizeof, and offsetof of every field in declaration order): a binding
  * asserts its own structs against it at load time (one-2-3-45_amd/_lib.py does) -- a field added on one side only cannot corrupt calls silently.
@@ -832,6 +833,61 @@ int o2345_mesh_intersect_count(const double* verts, const void* tris, int index_
                                long long max_cells, void* workspace, size_t workspace_bytes, long long* counts, int* face_hits_or_null, void* stream);
 int o2345_mesh_intersect_emit(const double* verts, const void* tris, int index_bytes, long long nv, long long nt, const void* grid, size_t grid_bytes,
                               long long max_cells, void* workspace, long long n_pairs, int* pairs, void* stream);
+/* ---- mesh rasterizer: depth, barycentrics, face id, colour and normal per pixel of a mesh (additive since 2.3; none in the reference: its meshes are
+ * rendered offline in another program) ----
+ * Equal to the host twin one-2-3-45_amd/raster.py to the last bit.  All real arithmetic is fp64, one operation at a time, in the order written
+ * (csrc/mesh_raster_math.h is the text); coverage is decided in integers.  verts device fp64 [nv,3] in the world frame, tris device int32 / int64 [nt,3]
+ * (index_bytes 4 / 8), both only read; 0 <= nv < 2^30, 3 * nt < 2^31; nt = 0 is legal and gives an empty image.
+ *   camera     surface.camera_rays' one, K = [[fx, 0, cx], [0, fy, cy], [0, 0, 1]] and c2w [12], passed as float32 scalars (fx, fy, cx, cy; m00 .. m23: the
+ *              3 x 4 of c2w, row-major) and widened to fp64; here fx, fy > 0 and the 3 x 3 of c2w is a rotation (|R^T R - I| <= 1e-5 in every entry).  x right, y down, z forward; the sample of pixel
+ *              (px, py) is the integer point (px, py), without a half-pixel offset.  H, W >= 1, H W < 2^31; near finite and > 0.
+ *   corners    a face's corners are renumbered for the computation: corner 0 is the stored corner with the smallest vertex index, the others follow in
+ *              stored (cyclic) order, so that the result does not depend on which corner a face is stored from.  Outputs are in STORED order.
+ *   screen     q = p - t; x_c = (R00 q_x + R10 q_y) + R20 q_z, y_c with column 1 of R, z_c with column 2; X = x_c / z_c * fx + cx,
+ *              Y = y_c / z_c * fy + cy; snapped to 1/256 pixel: sx = (int64) floor(X * 256 + 0.5), sy likewise.
+ *   classes    a face is skipped, and counted under the first of these that applies: an index outside [0, nv) (never dereferenced); a non-finite
+ *              coordinate; a corner that fails z_c >= near (there is NO clipping: the scenes sit in a unit cube with the camera outside); a corner that
+ *              fails |X| <= 2^21 and |Y| <= 2^21 (so that every int64 product stays below 2^61); A2 = (x1 - x0)(y2 - y0) - (y1 - y0)(x2 - x0) == 0 on
+ *              the snapped integers; culled (cull 0 none, 1 back faces, 2 front faces; a face is FRONT iff A2 < 0: with y down, a triangle whose
+ *              (P1 - P0) x (P2 - P0) points at the camera has A2 < 0); the pixel box [ceil(min sx / 256), floor(max sx / 256)] x [the same of sy], clipped
+ *              to the image, is empty.
+ *   coverage   integers only.  When A2 < 0, corners 1 and 2 are exchanged for the computation (A2 > 0 afterwards).  With a = corner (i + 1) % 3,
+ *              b = corner (i + 2) % 3, d = b - a and P = (256 px, 256 py): w_i = d_x (P_y - a_y) - d_y (P_x - a_x), so w0 + w1 + w2 = A2.  The pixel is
+ *              covered iff for every i: w_i > 0, or w_i == 0 and (d_y > 0, or d_y == 0 and d_x < 0).  The tie rule accepts exactly one of d and -d: a
+ *              pixel on an edge shared by two faces that do not overlap on the screen belongs to exactly one of them, however the mesh is oriented.
+ *   depth      l_i = double(w_i) / double(A2); u_i = l_i / z_i with the z_c of the unsnapped corner; iz = (u_0 + u_1) + u_2; z = 1 / iz; b_i = u_i * z.
+ *              A face whose z fails z < inf does not cover the pixel.
+ *   visibility the covering face with the smallest z wins, by fp64 comparison; ties go to the smaller face index.  The result does not depend on face
+ *              order, binning, tile size or run.
+ *   outputs    face int32 [H,W] (-1 without a hit); depth float32 [H,W]: z, or with ray_depth z * sqrt((vx vx + vy vy) + 1) for v = ((px - cx) / fx,
+ *              (py - cy) / fy, 1), the t of the ray of camera_rays through the pixel (0 without a hit); bary float32 [H,W,3] in stored corner order (0
+ *              without a hit).
+ *   shading    from face and the float32 bary widened to fp64, corners in stored order: rgb = (b0 c0 + b1 c1) + b2 c2, rounded to float32 once, of the
+ *              vertex colours float32 [nv,3] (0.5 without them); nrm the same of the vertex normals float32 [nv,3], or without them the flat
+ *              (P1 - P0) x (P2 - P0) of the fp64 vertices; kind uint8 1 at a hit; all 0 without one.  o2345_surface_pack turns kind, depth, rgb and nrm
+ *              into images: the colour quantisation, the normal encoding and the background are the surface renderer's.
+ * counts: device int64 [O2345_RASTER_COUNTS], 8-byte aligned, read by the enumerators below: the faces skipped by class, the faces binned (that take
+ * part), the (tile, face) pairs over 8 x 8-pixel tiles (a face is listed in every tile its pixel box touches) and the covered pixels.
+ * Three calls.  _count (workspace: mesh_raster_workspace_bytes(nv, nt, H, W) bytes, 0 for bad sizes; 16-byte aligned) writes every count but the pixels;
+ * no host synchronisation.  _emit (same sizes, camera and workspace, untouched in between; n_pairs as counted, below 2^31; lists: device int32 [n_pairs]
+ * of scratch, sized by the counted total and by nothing else) writes face, depth, bary and counts[O2345_RASTER_PIXELS].  _shade writes kind, rgb, nrm.
+ * Integer atomics appear in the binning only, none on pixels; no kernel waits for another workgroup; the same bytes on every run.
+ * Limits: no near clipping (a face with a corner in front of `near` is dropped whole), one sample per pixel (no anti-aliasing), corners snapped to 1/256
+ * pixel, a face with a corner beyond 2^21 pixels is dropped.  Not done: texture-atlas sampling (face + bary are what an atlas lookup starts from). */
+enum { O2345_RASTER_BAD_INDEX = 0, O2345_RASTER_NONFINITE = 1, O2345_RASTER_NEAR = 2, O2345_RASTER_RANGE = 3, O2345_RASTER_DEGENERATE = 4,
+       O2345_RASTER_CULLED = 5, O2345_RASTER_OFFSCREEN = 6, O2345_RASTER_BINNED = 7, O2345_RASTER_PAIRS = 8, O2345_RASTER_PIXELS = 9,
+       O2345_RASTER_COUNTS = 10 };
+size_t o2345_mesh_raster_workspace_bytes(long long nv, long long nt, int H, int W);
+int o2345_mesh_raster_count(const double* verts, const void* tris, int index_bytes, long long nv, long long nt, float fx, float fy, float cx, float cy, float m00, float m01, float m02, float m03, float m10, float m11, float m12,
+                            float m13, float m20, float m21, float m22, float m23,
+                            int H, int W, double near, int cull, void* workspace, size_t workspace_bytes, long long* counts, void* stream);
+int o2345_mesh_raster_emit(long long nv, long long nt, float fx, float fy, float cx, float cy, float m00, float m01, float m02, float m03, float m10, float m11, float m12,
+                           float m13, float m20, float m21, float m22, float m23,
+                           int H, int W, double near, int cull, int ray_depth,
+                           void* workspace, size_t workspace_bytes, long long n_pairs, int* lists, int* face, float* depth, float* bary, long long* counts,
+                           void* stream);
+int o2345_mesh_raster_shade(const double* verts, const void* tris, int index_bytes, long long nv, long long nt, const int* face, const float* bary, int H, int W,
+                            const float* colors_or_null, const float* normals_or_null, uint8_t* kind, float* rgb, float* nrm, void* stream);
 /* Load every code object of the library on the current device now (the HIP runtime loads a translation unit's kernels at its first launch: 5 - 60 ms
  * each for the units of this library, which otherwise land inside the first calls of a fresh process).  Launches nothing that touches user memory. */
 int o2345_preload(void);

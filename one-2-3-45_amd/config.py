@@ -427,6 +427,21 @@ def surface_refine(n=None):
     return int(n)
 
 
+# O2345_MESH_PREVIEW_VIEWS=n makes pipeline.reconstruct_folder rasterize the FINAL mesh (after the clean-up chain and the hole filling; csrc/mesh_raster.hip,
+# raster.py is the host twin) from the cameras of the surface previews and write mesh_preview_000.png ... next to the PLY ("" or "0" = off, the default:
+# nothing is launched, the result gains no key and every file keeps its bytes).
+MESH_PREVIEW_VIEWS = _non_negative_int("O2345_MESH_PREVIEW_VIEWS", os.environ.get("O2345_MESH_PREVIEW_VIEWS", ""))
+
+
+def mesh_preview_views(n=None):
+    """None -> the configured default; anything else must be a non-negative integer (an explicit 0 is off whatever the default)."""
+    if n is None:
+        return MESH_PREVIEW_VIEWS
+    if isinstance(n, bool) or int(n) != n or n < 0:
+        raise ValueError(f"mesh_preview_views must be a non-negative integer, got {n!r}")
+    return int(n)
+
+
 def preview_views(n=None):
     """None -> the configured default; anything else must be a non-negative integer (an explicit 0 is off whatever the default)."""
     if n is None:

@@ -1587,3 +1587,55 @@ def surface_pack(kind, depth, rgb, grad, H, W, background=(0, 0, 0, 0)):
     out = torch.empty(H, W, dtype=torch.float32, device=dev)
     call("o2345_surface_pack", kind, depth, rgb, grad, H, W, bg, color, normal, out)
     return color, normal, out
+
+
+# ---------------------------------------------------------------------------------------------------------- mesh rasterizer
+def _raster_camera(K, c2w, near, cull, what):
+    """the twin's refusals (raster.camera) -> the sixteen float32 scalars of the C ABI (fx, fy, cx, cy, the 3 x 4 of c2w), near, cull"""
+    from . import raster
+    K, M = _camera(K, c2w, what)
+    cam = raster.camera(K, M, near, cull)
+    return [float(K[0, 0]), float(K[1, 1]), float(K[0, 2]), float(K[1, 2])] + [float(x) for x in M.reshape(-1)], cam["near"], cam["cull"]
+
+
+def raster_info(counts):
+    """The counts of o2345_mesh_raster_count / _emit, on the host -> the info dict of raster.rasterize, by O2345_RASTER_*"""
+    from . import raster
+    return dict(zip(raster.COUNTS, (int(c) for c in counts)))
+
+
+@_on_device
+def mesh_raster(verts, tris, K, c2w, H, W, near=1e-3, cull=0, ray_depth=False, vertex_colors=None, vertex_normals=None):
+    """Rasterize a triangle mesh on the device (== raster.rasterize, its host twin and the definition, to the last bit; csrc/mesh_raster.hip).  verts fp64
+    [N,3] in the world frame, tris [M,3] int32 / int64, vertex_colors / vertex_normals float32 [N,3] or None, all on the device and only read; K [3,3]
+    without skew (fx, fy > 0) and c2w [4,4] or [3,4] (a rotation) on the host -> dict(face int32 [H,W] (-1: no hit), depth float32 [H,W] (along the
+    camera's axis, or with ``ray_depth`` along the pixel's ray: the t of surface_trace), bary float32 [H,W,3], kind uint8 [H W], rgb float32 [H W,3], nrm
+    float32 [H W,3] (the inputs of surface_pack), info: the counts by raster.COUNTS).  ``cull``: 0 none, 1 back faces, 2 front faces.  One
+    synchronisation, for the size of the tile lists; the counts are read once more at the end."""
+    from . import raster
+    cam, near, cull = _raster_camera(K, c2w, near, cull, "mesh_raster")
+    H, W = raster._image_size(H, W)
+    tris, ib = _triangles(tris, "mesh_raster")
+    _vertices(verts, "mesh_raster")
+    nv, nt, dev = verts.shape[0], tris.shape[0], verts.device
+    for a, what in ((vertex_colors, "vertex_colors"), (vertex_normals, "vertex_normals")):
+        if a is not None and (a.dtype != torch.float32 or tuple(a.shape) != (nv, 3) or a.device != dev or not a.is_contiguous()):
+            raise ValueError(f"mesh_raster: {what} must be contiguous float32 [{nv},3] on {dev}, got {a.dtype} {tuple(a.shape)} on {a.device}")
+    ws, wsb = _scratch("o2345_mesh_raster_workspace_bytes", (nv, nt, H, W), dev, "mesh_raster")
+    if not wsb:
+        raise ValueError(f"mesh_raster: bad sizes ({nv} vertices, {nt} triangles; the tables are int32)")
+    counts = torch.empty(len(raster.COUNTS), dtype=torch.int64, device=dev)
+    call("o2345_mesh_raster_count", verts, tris, ib, nv, nt, *cam, H, W, near, cull, ws, wsb, counts)
+    n_pairs = raster_info(counts.tolist())["pairs"]
+    if n_pairs >= 2 ** 31:
+        raise ValueError(f"mesh_raster: {n_pairs} (tile, face) pairs; the tile lists hold fewer than 2^31")
+    lists = _workspace(4 * max(n_pairs, 1), dev, "mesh_raster_lists").view(torch.int32) if n_pairs else None
+    face = torch.empty(H, W, dtype=torch.int32, device=dev)
+    depth = torch.empty(H, W, dtype=torch.float32, device=dev)
+    bary = torch.empty(H, W, 3, dtype=torch.float32, device=dev)
+    call("o2345_mesh_raster_emit", nv, nt, *cam, H, W, near, cull, int(bool(ray_depth)), ws, wsb, n_pairs, lists, face, depth, bary, counts)
+    kind = torch.empty(H * W, dtype=torch.uint8, device=dev)
+    rgb = torch.empty(H * W, 3, dtype=torch.float32, device=dev)
+    nrm = torch.empty(H * W, 3, dtype=torch.float32, device=dev)
+    call("o2345_mesh_raster_shade", verts, tris, ib, nv, nt, face, bary, H, W, vertex_colors, vertex_normals, kind, rgb, nrm)
+    return dict(face=face, depth=depth, bary=bary, kind=kind, rgb=rgb, nrm=nrm, info=raster_info(counts.tolist()))

@@ -421,17 +421,81 @@ def render_turntable(wt, vol, proj, cam_pos, intrinsic, H, W, n_views, elevation
     return [_surface_view(wt, vol, proj, cam_pos, u, flags, intrinsic, c, int(H), int(W), near, far, stride, refine, background) for c in c2ws], c2ws
 
 
-def _write_previews(wt, vol, proj, cam_pos, u, s, n, folder):
-    """n surface renders of a folder's scene as PNGs in ``folder``: the query camera, then an orbit through it"""
-    import os
-    from . import mesh_io, surface
+def _raster_mesh(mesh, vertex_colors, vertex_normals):
+    """the camera-independent part of render_mesh: the mesh and its attributes on one device, in the dtypes ops.mesh_raster takes"""
+    tensors = [x for x in (*mesh, vertex_colors, vertex_normals) if torch.is_tensor(x) and x.is_cuda]
+    dev = tensors[0].device if tensors else torch.device("cuda", torch.cuda.current_device())
+    verts, tris = _device_mesh(mesh, dev)
+    if verts.dtype != torch.float64:
+        verts = verts.to(torch.float64)
+    attr = lambda a: None if a is None else (a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(np.asarray(a, np.float32)))).to(dev, torch.float32).contiguous()
+    return verts, tris, attr(vertex_colors), attr(vertex_normals)
+
+
+def _mesh_view(verts, tris, colors, normals, intrinsic, c2w, H, W, near, cull, ray_depth, background):
+    """one image of render_mesh from the prepared mesh"""
+    r = ops.mesh_raster(verts, tris, intrinsic, c2w, H, W, near=near, cull=cull, ray_depth=ray_depth, vertex_colors=colors, vertex_normals=normals)
+    color, normal, depth = ops.surface_pack(r["kind"], r["depth"].view(-1), r["rgb"], r["nrm"], H, W, background)
+    return dict(color=color, normal=normal, depth=depth, face=r["face"], bary=r["bary"], info=r["info"])
+
+
+@torch.no_grad()
+def render_mesh(mesh, intrinsic, c2w, H, W, vertex_colors=None, vertex_normals=None, background=(0, 0, 0, 0), near=1e-3, cull=0, ray_depth=True):
+    """Depth, normal, colour and face image of a triangle mesh for the pinhole camera (intrinsic [3,3] without skew, c2w [4,4]), H x W pixels, by
+    rasterizing it on the device (ops.mesh_raster; definitions in raster.py, limits in DESIGN.md section 7).  ``mesh`` is a (verts [N,3], tris [M,3]) pair
+    in the WORLD frame, device tensors or host arrays (uploaded); ``vertex_colors`` / ``vertex_normals`` float32 [N,3] or None (a 0.5 grey; the faces'
+    flat normals).  The images are registered pixel for pixel with render_surface's: the same camera, the same sample point per pixel, the same packer
+    (colour quantisation, normal encoding, ``background``), and with ``ray_depth`` (the default here) the same depth, the t along the pixel's ray.
+    ``cull``: 0 none, 1 back faces, 2 front faces.  -> dict(color u8 [H,W,4], normal u8 [H,W,4], depth f32 [H,W], face int32 [H,W] (-1: no hit), bary f32
+    [H,W,3], info: the counts of ops.mesh_raster)."""
+    return _mesh_view(*_raster_mesh(mesh, vertex_colors, vertex_normals), intrinsic, c2w, int(H), int(W), near, cull, ray_depth, background)
+
+
+@torch.no_grad()
+def render_mesh_turntable(mesh, intrinsic, H, W, n_views, elevation_deg=20.0, radius=2.0, vertex_colors=None, vertex_normals=None, background=(0, 0, 0, 0),
+                          near=1e-3, cull=0, ray_depth=True, up=(0.0, 0.0, 1.0)):
+    """render_mesh from ``n_views`` look-at cameras on a circle around the origin (surface.orbit_c2w, render_turntable's cameras); the mesh and its
+    attributes are uploaded and converted once.  -> (list of render_mesh results, c2w float32 [n,4,4])."""
+    from . import surface
+    c2ws = surface.orbit_c2w(n_views, elevation_deg, radius, up)
+    prepared = _raster_mesh(mesh, vertex_colors, vertex_normals)
+    return [_mesh_view(*prepared, intrinsic, c, int(H), int(W), near, cull, ray_depth, background) for c in c2ws], c2ws
+
+
+def _preview_cameras(s, n):
+    """the cameras of a folder's previews -> (K [3,3], list of n c2w [4,4], H, W): the query camera, then an orbit through it"""
+    from . import surface
     K, c2w = s["query_intrinsic"].numpy()[:3, :3], s["query_c2w"].numpy()
     H, W = int(s["img_wh"][1]), int(s["img_wh"][0])
     pos = c2w[:3, 3].astype(np.float64)
     up = -c2w[:3, 1].astype(np.float64)                                   # the camera's y axis points down
     dist = float(np.linalg.norm(pos))
     elev = float(np.degrees(np.arcsin(np.clip(np.dot(pos, up) / dist, -0.99, 0.99))))
-    cams = [c2w] + list(surface.orbit_c2w(n, elev, dist, up)[1:])
+    return K, [c2w] + list(surface.orbit_c2w(n, elev, dist, up)[1:]), H, W
+
+
+def _write_mesh_previews(verts, tris, rgb, s, n, folder):
+    """n rasterized views of a folder's final mesh (world frame, the PLY's vertex colours) as PNGs in ``folder``, from _write_previews' cameras"""
+    import os
+    from . import mesh_io
+    K, cams, H, W = _preview_cameras(s, n)
+    prepared = _raster_mesh((verts, tris), rgb, None)
+    out = []
+    for k, c in enumerate(cams):
+        r = _mesh_view(*prepared, K, c, H, W, 1e-3, 0, True, (0, 0, 0, 0))
+        color, normal, depth, face = ops.to_host_numpy(r["color"], r["normal"], r["depth"], r["face"])
+        path = os.path.join(folder, f"mesh_preview_{k:03d}.png")
+        with open(path, "wb") as f:
+            f.write(mesh_io.png_bytes(color, config.mesh_texture_png_level()))
+        out.append({"path": path, "color": color, "normal": normal, "depth": depth, "face": face, "c2w": np.array(c, np.float32), "info": r["info"]})
+    return out
+
+
+def _write_previews(wt, vol, proj, cam_pos, u, s, n, folder):
+    """n surface renders of a folder's scene as PNGs in ``folder``: the query camera, then an orbit through it"""
+    import os
+    from . import mesh_io
+    K, cams, H, W = _preview_cameras(s, n)
     flags = ops.surface_bricks(u, 0.0, True)
     out = []
     for k, c in enumerate(cams):
@@ -447,7 +511,7 @@ def _write_previews(wt, vol, proj, cam_pos, u, s, n, folder):
 @torch.no_grad()
 def reconstruct_folder(root_dir, name, wt, out_ply, D=96, resolution=256, render_val_image=False, output_format=None, min_component_faces=None,
                        keep_largest=None, smooth_iterations=None, decimate_cell=None, project_iterations=None, texture_texel=None, preview_views=None, mesh_error=None,
-                       simplify_faces=None, mesh_audit=None, fill_holes=None, mesh_intersections=None):
+                       simplify_faces=None, mesh_audit=None, fill_holes=None, mesh_intersections=None, mesh_preview_views=None):
     """run.py's reconstruction stage without the reference tree: Zero123-style folder (dataset.SceneFolder) -> coloured mesh (binary PLY in
     the original frame), optionally the val image of the target view.  ``output_format`` ".obj" / ".glb" (run.py --output_format) also writes
     ``mesh<ext>`` next to ``out_ply`` in the asset frame, from the same device buffers.  The mesh options are extract_mesh's.  Returns
@@ -469,7 +533,12 @@ def reconstruct_folder(root_dir, name, wt, out_ply, D=96, resolution=256, render
     result has no new key and every file keeps its bytes) = n >= 3: the boundary loops of at most n edges are closed after the clean-up chain
     (ops.mesh_fill_holes; config.MESH_FILL_HOLES_ALL: every one); the result gains "fill_holes", its counts.  ``mesh_intersections`` (None: the config
     default O2345_MESH_INTERSECTIONS, off: nothing is launched and the result has no new key): the result gains "mesh_intersections", the counts of
-    ops.mesh_intersections on the final mesh in index coordinates -- how many pairs of its triangles cross, which the audit cannot say."""
+    ops.mesh_intersections on the final mesh in index coordinates -- how many pairs of its triangles cross, which the audit cannot say.
+    ``mesh_preview_views`` (None: the config default O2345_MESH_PREVIEW_VIEWS, 0 = off: nothing is launched, the result gains no key and every file keeps
+    its bytes) = n >= 1: n rasterized views (render_mesh) of the FINAL mesh -- after the clean-up chain and the hole filling, in the world frame, with the
+    vertex colours the PLY gets -- from the cameras of ``preview_views``, written as ``mesh_preview_000.png`` ... next to the PLY; unlike the surface
+    previews they show what the mesh options did.  The result's "mesh_previews" is the list of {path, color, normal, depth, face, c2w, info}, and
+    "mesh_preview_mesh" the rendered mesh: {verts fp64 [N,3], tris, vertex_colors float32 [N,3] or None}, on the device."""
     import os
     from . import dataset, mesh_io
     if output_format not in (None, ".ply", ".obj", ".glb"):
@@ -502,6 +571,10 @@ def reconstruct_folder(root_dir, name, wt, out_ply, D=96, resolution=256, render
         out["mesh_audit"] = ops.mesh_audit(m.verts_idx, m.tris)
     if config.mesh_intersections(mesh_intersections):
         out["mesh_intersections"] = ops.mesh_intersections(m.verts_idx, m.tris)
+    mesh_previews = config.mesh_preview_views(mesh_preview_views)
+    if mesh_previews:
+        out["mesh_preview_mesh"] = {"verts": m.verts, "tris": m.tris, "vertex_colors": rgb}
+        out["mesh_previews"] = _write_mesh_previews(m.verts, m.tris, rgb, s, mesh_previews, os.path.dirname(str(out_ply)))
     if previews:
         out["previews"] = _write_previews(wt, vol, proj, cam_pos, m.u, s, previews, os.path.dirname(str(out_ply)))
     if render_val_image:
