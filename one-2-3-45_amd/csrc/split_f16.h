@@ -5,6 +5,8 @@
 // lo = f16(x - hi) (22 significant bits together; domain |x| < 65504).  A product of two split operands is accumulated in fp32 on
 // v_mfma_f32_32x32x16_f16 as lo*hi + hi*lo + hi*hi; the dropped lo*lo term is 2^-22 relative.  gfx950's MFMA honours f16 subnormals and forms
 // exact products (checked on hardware).  Weights are split on the host (weights.py), activations in registers by the helpers below.
+// The lower end of the domain -- lo is an f16 subnormal below |x| of about 2^-4, its absolute error stops shrinking with x -- is measured and stated in
+// DESIGN.md section 4, "split-f16 form: weight scale and accuracy".
 //
 // lo comes in two forms, identical up to the rounding of the residual (tools/ubench/mixlo_check.hip checks them value by value on hardware):
 //   C form (split_pair): x - hi is one v_fma_mix_f32 per value (the f16 operand is converted in flight, exact incl. f16 subnormals -- checked on
