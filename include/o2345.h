@@ -579,6 +579,32 @@ int o2345_mesh_texture_corners(const double* verts, long long nv, const void* tr
                                const float* bound_min_host, const float* bound_max_host, const float* scale_mat_host, const float* trans_mat_host, const float* grad,
                                float* positions, float* uv, float* normals, uint32_t* indices, float* bounds, void* workspace, size_t workspace_bytes,
                                void* stream);
+/* Tangent-space normal map of the textured asset (additive; none in the reference).  Everything is fp64, one operation at a time, in the order written;
+ * a dot product is (x x + y y) + z z; square roots and divisions are IEEE: equal to mesh_io.texture_frames / pack_normal_map to the last bit
+ * (csrc/mesh_normalmap_math.h is the one spelling of the arithmetic).
+ * mesh_texture_frames: one frame per triangle from the file's own buffers, the positions [3 nt,3] and uv [3 nt,2] of mesh_texture_corners (device float32,
+ * only read), promoted to fp64.  Triangle t has corners q = 3t, 3t + 1, 3t + 2 with positions p0, p1, p2 and texture coordinates uv0, uv1, uv2: e1 = p1 -
+ * p0, e2 = p2 - p0, N = unit(e1 x e2) (the front face of the file's winding); (du1, dv1) = uv1 - uv0, (du2, dv2) = uv2 - uv0, det = du1 dv2 - du2 dv1, Pu =
+ * (e1 dv2 - e2 dv1) / det, Pv = (e2 du1 - e1 du2) / det; T = unit(Pu - N (N . Pu)); w = +1 if (N x T) . (-Pv) >= 0, else -1 (green is up, and up is
+ * decreasing v: row 0 of the image is on top).  normals device float32 [3 nt,3] = N and tangents device float32 [3 nt,4] (16-byte aligned) = (T, w), the
+ * same for the three corners of a triangle (flat).  A triangle is degenerate when |e1 x e2|, det or |Pu - N (N . Pu)| is zero or not finite: it gets N =
+ * (0, 1, 0) and tangent (1, -0, 0, 1) and is counted once: the NEGATIVE zero of its y is the value of the definition and the mark of a degenerate
+ * triangle; a sound triangle never carries it, because every float32 component of its N and T has + 0 added, which turns a negative zero into a positive
+ * one and changes nothing else (a flat axis-aligned triangle has the frame (0, 1, 0), (1, 0, 0, 1) for good reasons).  1 <= nt < 2^31 / 3.
+ * mesh_texture_normal_pack: one RGBA8 texel per image texel, raster order as for mesh_texture_pack; image device uint8 [H,W,4], 4-byte aligned.  A texel
+ * of a used cell has its owner triangle t by the A / B rule above (the repeated last triangle of an odd nt included) and its cell-major entry s; grad
+ * device float32 [texels,3] is the raw SDF gradient at the texel points.  n = grad[s] through the operations of the asset normals (normalise; through
+ * rotation, device float32 [9] = the 3x3 of trans_mat, row-major, or NULL, and renormalise; y and z exchanged), kept in fp64.  With the float32 N, T, w of
+ * corner 3t promoted to fp64 and B = w (N x T): x = n . T, y = n . B, z = n . N, each channel clamp(floor((x 127.5 + 127.5) + 0.5), 0, 255), alpha 255.
+ * (128, 128, 255, 255) for a texel of an unused cell, for a texel whose triangle carries the degenerate mark above and for a texel whose gradient has a
+ * zero or non-finite length, before or behind the rotation.
+ * counters: device int64 [4], 8-byte aligned = {degenerate triangles, bad-gradient texels, back-facing texels, reserved}.  mesh_texture_frames zeroes all
+ * four and counts the first; mesh_texture_normal_pack zeroes and counts the last three and leaves the first alone, so that one block serves the chain.
+ * Bad gradients are counted over every texel of a used cell; back-facing ones (z < 0; informative, not an error) where z is computed.
+ * Bad input never faults; no host synchronisation. */
+int o2345_mesh_texture_frames(const float* positions, const float* uv, long long nt, float* normals, float* tangents, long long* counters, void* stream);
+int o2345_mesh_texture_normal_pack(const float* grad, const float* rotation, const float* normals, const float* tangents, long long nt, int texel,
+                                   uint8_t* image, long long* counters, void* stream);
 /* The records of the textured OBJ (none in the reference), for n = 3 nt unwelded vertices as written by mesh_texture_corners: n "v" records without
  * colours, n "vt" + 2 x " %10.8f" records (u, then float32(1 - v): OBJ's origin is bottom-left), n "vn" records when normals are given, n / 3 records
  * "f a/a b/b c/c" (with normals "a/a/a") over the corners 1 .. n in order, each token right-aligned in 2 d + 1 (3 d + 2) bytes, d = decimal digits of n.

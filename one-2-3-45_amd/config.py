@@ -340,6 +340,17 @@ def mesh_texture_png_level(n=None):
     return _png_level("png_level", int(n))
 
 
+# ---- normal map of the textured asset (csrc/mesh_texture.hip; mesh_io.texture_frames / pack_normal_map are the host twins) ----------------------------------
+# O2345_MESH_NORMAL_MAP=1 makes the textured export also bake a tangent-space normal map: the SDF gradient at every texel's surface point, which the colour
+# network needed anyway, in the tangent frame of the texel's triangle; the .glb gains TANGENT and a second image, the .obj a stem_normal.png ("" or "0" =
+# off, the default: nothing is launched and every file keeps its bytes).  It needs the texture atlas: with texture_texel off it is an error, not a no-op.
+MESH_NORMAL_MAP = _non_negative_int("O2345_MESH_NORMAL_MAP", os.environ.get("O2345_MESH_NORMAL_MAP", "")) != 0
+
+
+def mesh_normal_map(x=None):
+    return MESH_NORMAL_MAP if x is None else bool(x)
+
+
 # ---- mesh error report (csrc/mesh_distance.hip; mesh_io.mesh_distance is the host twin) -------------------------------------------------------------------
 # O2345_MESH_ERROR=1 makes pipeline.reconstruct_folder report how far the mesh it wrote is from the raw marching-cubes mesh it started from, as surfaces:
 # Chamfer, Hausdorff and F-score (ops.mesh_distance) in units of the extraction grid's spacing ("" or "0" = off, the default: nothing is launched and the

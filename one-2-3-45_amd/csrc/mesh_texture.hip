@@ -21,7 +21,12 @@
 //              / W, (cell_y c + v_local) / H) in fp64, rounded once; position and normal are the welded export's for that vertex (mesh_math.h).
 // Bad input never faults: a triangle index outside [0, nv) is read as vertex 0, and it and a non-finite coordinate are counted once per triangle in two
 // integer counters that the caller raises on.  No other atomics.  Nothing here synchronises with the host.
+//
+// Normal map (opt-in): k_tex_frames gives every triangle of the file a tangent frame from the float32 buffers k_tex_corners wrote, k_tex_normal_pack turns
+// the SDF gradients at the texel points -- which the colour network needed anyway -- into the RGBA8 tangent-space image.  The definition is in
+// include/o2345.h, the arithmetic in mesh_normalmap_math.h, the host twins are mesh_io.texture_frames / pack_normal_map.
 #include "mesh_math.h"
+#include "mesh_normalmap_math.h"
 
 namespace o2345 {
 
@@ -136,6 +141,46 @@ __global__ __launch_bounds__(256) void k_tex_corners(const double* __restrict__ 
     if (threadIdx.x < 6) partials[(long long)blockIdx.x * 6 + threadIdx.x] = out[threadIdx.x];
 }
 
+// Tangent-space normal map (mesh_normalmap_math.h has the arithmetic; mesh_io.texture_frames / pack_normal_map are the host twins).
+// thread per unwelded vertex q = 3t + d: every corner of a triangle computes, and stores, its triangle's frame; corner 0 speaks for it in the count
+__global__ __launch_bounds__(256) void k_tex_frames(const float* __restrict__ pos, const float* __restrict__ uv, long long n3, float* __restrict__ nrm,
+                                                    float4* __restrict__ tan, unsigned long long* __restrict__ counters) {
+    const long long q = (long long)blockIdx.x * 256 + threadIdx.x;
+    bool degenerate = false;
+    if (q < n3) {
+        const long long t = q / 3;
+        float N[3], T[4];
+        const bool ok = nm_frame(pos + 9 * t, uv + 6 * t, N, T);
+        degenerate = !ok && q == 3 * t;
+        nrm[3 * q] = N[0]; nrm[3 * q + 1] = N[1]; nrm[3 * q + 2] = N[2];
+        tan[q] = make_float4(T[0], T[1], T[2], T[3]);
+    }
+    wave_count(degenerate, counters);
+}
+
+// thread per image texel, raster order: one aligned uchar4 store each
+__global__ __launch_bounds__(256) void k_tex_normal_pack(const float* __restrict__ grad, const float* __restrict__ rotation, const float* __restrict__ nrm,
+                                                         const float* __restrict__ tan, long long nt, TexLayout L, uchar4* __restrict__ image,
+                                                         unsigned long long* __restrict__ counters) {
+    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+    int flags = 0;
+    if (e < (long long)L.W * L.H) {
+        const int y = (int)(e / L.W), x = (int)(e - (long long)y * L.W);
+        const int cx = x / L.c, cy = y / L.c;
+        const long long k = (long long)cy * L.G + cx;
+        uint8_t o[4] = {128, 128, 255, 255};
+        if (k < L.cells) {
+            const int i = x - cx * L.c, j = y - cy * L.c;
+            const long long s = k * L.c * L.c + (long long)j * L.c + i;
+            const long long t = i + j >= L.c && 2 * k + 1 < nt ? 2 * k + 1 : 2 * k;
+            flags = nm_texel(grad + 3 * s, rotation, nrm + 9 * t, tan + 12 * t, o);
+        }
+        image[e] = make_uchar4(o[0], o[1], o[2], o[3]);
+    }
+    wave_count((flags & NM_BAD_GRADIENT) != 0, counters + 1);
+    wave_count((flags & NM_BACK_FACING) != 0, counters + 2);
+}
+
 }  // namespace o2345
 
 using namespace o2345;
@@ -201,6 +246,31 @@ int o2345_mesh_texture_corners(const double* verts, long long nv, const void* tr
     });
     mesh_bounds_finish((const float*)workspace, (long long)nb, bounds, s);
     return check_launch("mesh_texture_corners");
+}
+
+int o2345_mesh_texture_frames(const float* positions, const float* uv, long long nt, float* normals, float* tangents, long long* counters, void* stream) {
+    O2345_REQUIRE(nt >= 1 && 3 * nt < (1ll << 31), "mesh_texture_frames: bad size (nt = %lld must be in [1, 2^31 / 3))", nt);
+    O2345_REQUIRE(positions && uv && normals && tangents && counters, "mesh_texture_frames: null pointer");
+    O2345_REQUIRE(((uintptr_t)tangents & 15) == 0, "mesh_texture_frames: tangents must be 16-byte aligned");
+    O2345_REQUIRE(((uintptr_t)counters & 7) == 0, "mesh_texture_frames: counters must be 8-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    O2345_HIP(hipMemsetAsync(counters, 0, 4 * sizeof(long long), s));
+    hipLaunchKernelGGL(k_tex_frames, dim3(cdiv(3 * nt, 256)), dim3(256), 0, s, positions, uv, 3 * nt, normals, (float4*)tangents, (unsigned long long*)counters);
+    return check_launch("mesh_texture_frames");
+}
+
+int o2345_mesh_texture_normal_pack(const float* grad, const float* rotation, const float* normals, const float* tangents, long long nt, int texel,
+                                   uint8_t* image, long long* counters, void* stream) {
+    TexLayout L;
+    O2345_REQUIRE(tex_layout(nt, texel, L), "mesh_texture_normal_pack: bad layout (nt = %lld >= 1, texel = %d in [4, 64], sides <= 16384, texels < 2^31)", nt, texel);
+    O2345_REQUIRE(grad && normals && tangents && image && counters, "mesh_texture_normal_pack: null pointer");
+    O2345_REQUIRE(((uintptr_t)image & 3) == 0, "mesh_texture_normal_pack: image must be 4-byte aligned");
+    O2345_REQUIRE(((uintptr_t)counters & 7) == 0, "mesh_texture_normal_pack: counters must be 8-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    O2345_HIP(hipMemsetAsync(counters + 1, 0, 3 * sizeof(long long), s));                 // entry 0 is the frames call's
+    hipLaunchKernelGGL(k_tex_normal_pack, dim3(cdiv((long long)L.W * L.H, 256)), dim3(256), 0, s, grad, rotation, normals, tangents, nt, L, (uchar4*)image,
+                       (unsigned long long*)counters);
+    return check_launch("mesh_texture_normal_pack");
 }
 
 }  // extern "C"

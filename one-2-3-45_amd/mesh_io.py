@@ -15,7 +15,8 @@ per buffer, one file write.  ``component_labels`` / ``filter_components`` are th
 (csrc/mesh_components.hip); ``vertex_adjacency`` / ``smooth_vertices`` are the host twin (and definition) of the device adjacency table and Taubin
 smoothing (csrc/mesh_smooth.hip).  ``texture_layout`` / ``texture_points`` / ``texture_corners`` / ``pack_texture`` are the host twins (and definition)
 of the texture atlas (csrc/mesh_texture.hip); ``png_bytes`` / ``read_png`` its image file, ``write_textured`` / ``read_glb_texture`` / ``read_obj_texture``
-the textured GLB and the OBJ + MTL + PNG triple.  No byte parity with trimesh's own OBJ / GLB writers is claimed (trimesh is not available to compare against)."""
+the textured GLB and the OBJ + MTL + PNG triple; ``texture_frames`` / ``pack_normal_map`` are the host twins (and definition) of the tangent-space normal
+map that goes with the atlas, ``decode_normal_map`` / ``read_glb_normal_map`` / ``read_obj_normal_map`` read it back.  No byte parity with trimesh's own OBJ / GLB writers is claimed (trimesh is not available to compare against)."""
 import json
 import os
 import struct
@@ -161,12 +162,17 @@ def _host_mesh(positions, faces, colors, normals):
 _GLB_MAGIC, _GLB_JSON, _GLB_BIN = 0x46546C67, 0x4E4F534A, 0x004E4942
 
 
-def glb_json(n, m, colors, normals, pos_min, pos_max, texcoords=False, image_bytes=0):
+def glb_json(n, m, colors, normals, pos_min, pos_max, texcoords=False, image_bytes=0, tangents=False, normal_image_bytes=0):
     """The JSON chunk (bytes, space-padded to a multiple of 4): one buffer, views in the order indices / POSITION / COLOR_0 / NORMAL, one accessor per
     view, one mesh with one triangle primitive, one node, one scene.  Fixed key order and separators: the bytes are reproducible.
     ``texcoords`` adds TEXCOORD_0 (VEC2 float32) after NORMAL; ``image_bytes`` > 0 adds a last view without a target that holds a PNG of that many bytes,
     and behind "buffers" the keys "materials" (baseColorTexture, metallic 0, roughness 1), "textures", "images", "samplers" (LINEAR / LINEAR,
-    CLAMP_TO_EDGE: what texture_layout's gutters are made for); the primitive then names material 0.  Without the two the bytes are what they were."""
+    CLAMP_TO_EDGE: what texture_layout's gutters are made for); the primitive then names material 0.  Without the two the bytes are what they were.
+    ``tangents`` adds TANGENT (VEC4 float32) after NORMAL; ``normal_image_bytes`` > 0 adds a second PNG view behind the first, "normalTexture": {"index":
+    1} in the material and a second entry in "textures" and "images" (same sampler).  The two come together and need normals, texcoords and the first
+    image; without them the bytes are, again, what they were."""
+    if bool(tangents) != bool(normal_image_bytes) or (tangents and not (normals and texcoords and image_bytes)):
+        raise ValueError("GLB export: a normal map is TANGENT and a second image, next to NORMAL, TEXCOORD_0 and the base colour image")
     views, accessors, off = [], [], 0
 
     def add(nbytes, target, accessor):
@@ -183,6 +189,8 @@ def glb_json(n, m, colors, normals, pos_min, pos_max, texcoords=False, image_byt
         attrs["COLOR_0"] = add(4 * n, 34962, {"componentType": 5121, "normalized": True, "count": n, "type": "VEC4"})
     if normals:
         attrs["NORMAL"] = add(12 * n, 34962, {"componentType": 5126, "count": n, "type": "VEC3"})
+    if tangents:
+        attrs["TANGENT"] = add(16 * n, 34962, {"componentType": 5126, "count": n, "type": "VEC4"})
     if texcoords:
         attrs["TEXCOORD_0"] = add(8 * n, 34962, {"componentType": 5126, "count": n, "type": "VEC2"})
     prim = {"attributes": attrs, "indices": indices, "mode": 4}
@@ -190,33 +198,46 @@ def glb_json(n, m, colors, normals, pos_min, pos_max, texcoords=False, image_byt
         views.append({"buffer": 0, "byteOffset": off, "byteLength": int(image_bytes)})
         off += (int(image_bytes) + 3) // 4 * 4
         prim["material"] = 0
+    if normal_image_bytes:
+        views.append({"buffer": 0, "byteOffset": off, "byteLength": int(normal_image_bytes)})
+        off += (int(normal_image_bytes) + 3) // 4 * 4
     doc = {"asset": {"version": "2.0", "generator": "o2345-hip"}, "scene": 0, "scenes": [{"nodes": [0]}], "nodes": [{"mesh": 0}],
            "meshes": [{"primitives": [prim]}], "accessors": accessors, "bufferViews": views,
            "buffers": [{"byteLength": off}]}
     if image_bytes:
         doc["materials"] = [{"pbrMetallicRoughness": {"baseColorTexture": {"index": 0}, "metallicFactor": 0.0, "roughnessFactor": 1.0}}]
         doc["textures"] = [{"sampler": 0, "source": 0}]
-        doc["images"] = [{"bufferView": len(views) - 1, "mimeType": "image/png"}]
+        doc["images"] = [{"bufferView": len(views) - 1 - bool(normal_image_bytes), "mimeType": "image/png"}]
         doc["samplers"] = [{"magFilter": 9729, "minFilter": 9729, "wrapS": 33071, "wrapT": 33071}]
+    if normal_image_bytes:
+        doc["materials"][0]["normalTexture"] = {"index": 1}
+        doc["textures"].append({"sampler": 0, "source": 1})
+        doc["images"].append({"bufferView": len(views) - 1, "mimeType": "image/png"})
     js = json.dumps(doc, separators=(",", ":")).encode("ascii")
     return js + b" " * (-len(js) % 4)
 
 
-def write_glb_buffers(path, indices, positions, rgba, normals, bounds, uv=None, png=None):
+def write_glb_buffers(path, indices, positions, rgba, normals, bounds, uv=None, png=None, tangents=None, normal_png=None):
     """GLB from its buffers as they sit in the file (host arrays: indices uint32 [M,3], positions float32 [N,3], rgba uint8 [N,4] or None, normals
     float32 [N,3] or None; bounds [2,3] = per-axis min, max of positions): 12-byte header, JSON chunk, BIN chunk; every view is a multiple of 4 bytes.
-    A textured file also has ``uv`` float32 [N,2] and ``png`` (the bytes of the image, zero-padded to a multiple of 4 in the file), and no ``rgba``."""
+    A textured file also has ``uv`` float32 [N,2] and ``png`` (the bytes of the image, zero-padded to a multiple of 4 in the file), and no ``rgba``.
+    A normal map is ``tangents`` float32 [N,4] (behind the normals, which it needs) and ``normal_png``, a second image behind the first."""
     n, m = positions.shape[0], indices.shape[0]
     if n == 0 or m == 0:
         raise ValueError("GLB export: an empty mesh has no valid glTF form (accessors need count >= 1)")
     if (uv is None) != (png is None) or (uv is not None and rgba is not None):
         raise ValueError("GLB export: a textured file has uv and png and no vertex colours")
     bounds = np.asarray(bounds, np.float32).reshape(2, 3)
-    js = glb_json(n, m, rgba is not None, normals is not None, bounds[0], bounds[1], uv is not None, 0 if png is None else len(png))
-    image = None if png is None else np.frombuffer(bytes(png) + b"\0" * (-len(png) % 4), np.uint8)
+    if (tangents is None) != (normal_png is None) or (tangents is not None and (normals is None or uv is None)):
+        raise ValueError("GLB export: a normal map is tangents and a second png, in a textured file with normals")
+    js = glb_json(n, m, rgba is not None, normals is not None, bounds[0], bounds[1], uv is not None, 0 if png is None else len(png), tangents is not None,
+                  0 if normal_png is None else len(normal_png))
+    image, normal_image = (None if b is None else np.frombuffer(bytes(b) + b"\0" * (-len(b) % 4), np.uint8) for b in (png, normal_png))
+    if tangents is not None:
+        tangents = np.ascontiguousarray(tangents, np.float32).reshape(n, 4)
     if uv is not None:
         uv = np.ascontiguousarray(uv, np.float32).reshape(n, 2)
-    parts = [np.ascontiguousarray(a).reshape(-1).view(np.uint8) for a in (indices, positions, rgba, normals, uv, image) if a is not None]
+    parts = [np.ascontiguousarray(a).reshape(-1).view(np.uint8) for a in (indices, positions, rgba, normals, tangents, uv, image, normal_image) if a is not None]
     nbin = sum(a.size for a in parts)
     assert indices.dtype.itemsize == 4 and positions.dtype == np.float32 and nbin % 4 == 0
     with open(path, "wb") as f:
@@ -248,6 +269,11 @@ def read_glb_texture(path):
     return _read_glb(path)[4]
 
 
+def read_glb_normal_map(path):
+    """-> (tangents float32 [N,4], image uint8 [H,W,4]) of a file written above with a normal map, or None for a file without one."""
+    return _read_glb(path)[5]
+
+
 def _read_glb(path):
     raw = open(path, "rb").read()
     magic, version, total = struct.unpack_from("<III", raw, 0)
@@ -269,16 +295,23 @@ def _read_glb(path):
     prim = doc["meshes"][0]["primitives"][0]
     at = prim["attributes"]
     faces = accessor(prim["indices"]).reshape(-1, 3).astype(np.int32)
-    texture = None
-    if "TEXCOORD_0" in at:
-        mat = doc["materials"][prim["material"]]["pbrMetallicRoughness"]
-        tex = doc["textures"][mat["baseColorTexture"]["index"]]
+    texture = normal_map = None
+
+    def image_of(tex):
         img = doc["images"][tex["source"]]
         v = doc["bufferViews"][img["bufferView"]]
         assert img["mimeType"] == "image/png" and "target" not in v
-        texture = (accessor(at["TEXCOORD_0"]).copy(), png_image(raw[base + v["byteOffset"]:base + v["byteOffset"] + v["byteLength"]]), doc["samplers"][tex["sampler"]])
+        return png_image(raw[base + v["byteOffset"]:base + v["byteOffset"] + v["byteLength"]])
+
+    if "TEXCOORD_0" in at:
+        mat = doc["materials"][prim["material"]]
+        tex = doc["textures"][mat["pbrMetallicRoughness"]["baseColorTexture"]["index"]]
+        texture = (accessor(at["TEXCOORD_0"]).copy(), image_of(tex), doc["samplers"][tex["sampler"]])
+        if "normalTexture" in mat:
+            assert "TANGENT" in at and "NORMAL" in at
+            normal_map = (accessor(at["TANGENT"]).copy(), image_of(doc["textures"][mat["normalTexture"]["index"]]))
     return (accessor(at["POSITION"]).copy(), faces, accessor(at["COLOR_0"]).copy() if "COLOR_0" in at else None,
-            accessor(at["NORMAL"]).copy() if "NORMAL" in at else None, texture)
+            accessor(at["NORMAL"]).copy() if "NORMAL" in at else None, texture, normal_map)
 
 
 def obj_coordinate_digits(bounds):
@@ -1117,6 +1150,122 @@ def texture_corners(verts_idx, faces, texel, resolution, bound_min=(-1.0, -1.0, 
     return pos, uv, nrm, np.stack([pos.min(0), pos.max(0)])
 
 
+# ---- tangent-space normal map: the host twin of k_tex_frames / k_tex_normal_pack (csrc/mesh_normalmap_math.h) and the DEFINITION of their results, to the
+# last bit.  All arithmetic is float64, one operation at a time, in the order written; a dot product is (x x + y y) + z z.
+NORMAL_MAP_FLAT = (128, 128, 255, 255)
+NORMAL_MAP_COUNTS = ("degenerate", "bad_gradient", "back_facing", "reserved")          # the counters block of the two device entries, int64 [4]
+_DEFAULT_NORMAL, _DEFAULT_TANGENT = (0.0, 1.0, 0.0), (1.0, -0.0, 0.0, 1.0)                   # the negative zero marks the degenerate frame
+
+
+def _length_ok(l):
+    return (l > 0.0) & (l < np.inf)
+
+
+def texture_frames(positions, uv):
+    """One tangent frame per triangle from the file's own float32 buffers (texture_corners' positions [3 nt, 3] and uv [3 nt, 2], promoted to float64) ->
+    (normals float32 [3 nt, 3], tangents float32 [3 nt, 4], degenerate: the number of degenerate triangles); host twin of ops.mesh_texture_frames.
+    Triangle t has corners 3t, 3t + 1, 3t + 2 = p0, p1, p2 with uv0, uv1, uv2: e1 = p1 - p0, e2 = p2 - p0, N = unit(e1 x e2), the front face of the file's
+    winding; (du1, dv1) = uv1 - uv0, (du2, dv2) = uv2 - uv0, det = du1 dv2 - du2 dv1, Pu = (e1 dv2 - e2 dv1) / det, Pv = (e2 du1 - e1 du2) / det; T =
+    unit(Pu - N (N . Pu)); w = +1 if (N x T) . (-Pv) >= 0, else -1: green is up, and up is decreasing v, because row 0 of the image is on top.  NORMAL = N and
+    TANGENT = (T, w) for all three corners (flat).  Degenerate -- |e1 x e2|, det or |Pu - N (N . Pu)| zero or not finite --: N = (0, 1, 0), TANGENT = (1, 0, 0,
+    1), counted once.  Its TANGENT.y is the NEGATIVE zero: the value of the definition, and the mark that pack_normal_map knows a degenerate triangle by
+    (frame_is_degenerate); a sound triangle never carries it, because every float32 component of its N and T has + 0 added, which turns a negative zero
+    into a positive one and changes nothing else.  (A flat axis-aligned triangle has the frame (0, 1, 0), (1, 0, 0, 1) for good reasons.)"""
+    p = np.asarray(positions, np.float32).reshape(-1, 3, 3).astype(np.float64)
+    t = np.asarray(uv, np.float32).reshape(-1, 3, 2).astype(np.float64)
+    if p.shape[0] != t.shape[0] or p.shape[0] < 1:
+        raise ValueError(f"texture_frames: expected positions [3 M, 3] and uv [3 M, 2] of M >= 1 triangles, got {np.shape(positions)} and {np.shape(uv)}")
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        e1, e2 = p[:, 1] - p[:, 0], p[:, 2] - p[:, 0]
+        c = _cross3(e1, e2)
+        l = np.sqrt(_dot3(c, c))
+        du1, dv1, du2, dv2 = (t[:, 1, 0] - t[:, 0, 0])[:, None], (t[:, 1, 1] - t[:, 0, 1])[:, None], (t[:, 2, 0] - t[:, 0, 0])[:, None], (t[:, 2, 1] - t[:, 0, 1])[:, None]
+        det = du1 * dv2 - du2 * dv1
+        n = c / l[:, None]
+        Pu = (e1 * dv2 - e2 * dv1) / det
+        Pv = (e2 * du1 - e1 * du2) / det
+        tv = Pu - n * _dot3(n, Pu)[:, None]
+        lt = np.sqrt(_dot3(tv, tv))
+        T = tv / lt[:, None]
+        w = np.where(_dot3(_cross3(n, T), -Pv) >= 0.0, 1.0, -1.0)
+        ok = _length_ok(l) & _length_ok(np.abs(det[:, 0])) & _length_ok(lt)
+        N = np.where(ok[:, None], n.astype(np.float32) + np.float32(0.0), np.array(_DEFAULT_NORMAL, np.float32))
+        TW = np.where(ok[:, None], np.concatenate([T.astype(np.float32) + np.float32(0.0), w[:, None].astype(np.float32)], 1), np.array(_DEFAULT_TANGENT, np.float32))
+    return np.ascontiguousarray(np.repeat(N, 3, 0)), np.ascontiguousarray(np.repeat(TW, 3, 0)), int((~ok).sum())
+
+
+def frame_is_degenerate(tangents):
+    """float32 [N,4] -> bool [N]: the mark texture_frames gives a degenerate triangle, a negative zero in TANGENT.y"""
+    t = np.asarray(tangents, np.float32).reshape(-1, 4)
+    return (t[:, 1] == 0.0) & np.signbit(t[:, 1])
+
+
+def _unit_gradients(grad, trans_mat=None):
+    """frame_normals' operations, kept in float64 -> (n [N,3] with y and z exchanged, ok [N]); n is undefined where ok is False"""
+    g = np.asarray(grad, np.float32).reshape(-1, 3).astype(np.float64)
+    T = _mat44(trans_mat)
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        l = np.sqrt(_dot3(g, g))
+        ok = _length_ok(l)
+        g = g / l[:, None]
+        if T is not None:
+            w = np.stack([(T[r, 0] * g[:, 0] + T[r, 1] * g[:, 1]) + T[r, 2] * g[:, 2] for r in range(3)], 1)
+            l = np.sqrt(_dot3(w, w))
+            ok = ok & _length_ok(l)
+            g = w / l[:, None]
+    return g[:, [0, 2, 1]], ok
+
+
+def _normal_channel(x):
+    with np.errstate(invalid="ignore"):
+        v = np.floor((x * 127.5 + 127.5) + 0.5)
+        return np.where(v >= 0.0, np.where(v <= 255.0, v, 255.0), 0.0).astype(np.uint8)
+
+
+def pack_normal_map(grad, normals, tangents, nt, texel, trans_mat=None):
+    """Cell-major raw SDF gradients at the texel points (float32 [cells c^2, 3], the order of texture_points) and the frames of texture_frames -> (image
+    uint8 [height, width, 4] in raster order like pack_texture, counts {"bad_gradient", "back_facing"}); host twin of ops.mesh_texture_normal_pack.
+    A texel of a used cell has its owner triangle t by the A / B rule of texture_cell (for an odd count the B half of the last cell repeats the last
+    triangle).  n = its gradient through the operations of frame_normals -- normalise, through the 3x3 of ``trans_mat`` (a 4x4, or a 3x3, float32) when given
+    and renormalise, y and z exchanged -- kept in float64.  With the float32 N, T, w of corner 3t promoted to float64 and B = w (N x T): x = n . T, y = n . B,
+    z = n . N; each channel is clamp(floor((x 127.5 + 127.5) + 0.5), 0, 255), alpha 255.  NORMAL_MAP_FLAT for a texel of an unused cell, of a triangle that
+    holds the degenerate mark of texture_frames (frame_is_degenerate), and for a gradient whose length, before or behind
+    the rotation, is zero or not finite.  Counts: bad gradients over every texel of a used cell; z < 0 (informative, no error) where z is computed."""
+    L = texture_layout(nt, texel)
+    c, G, cells, nt = L["texel"], L["grid"], L["cells"], int(nt)
+    g = np.asarray(grad, np.float32).reshape(-1, 3)
+    N = np.asarray(normals, np.float32).reshape(-1, 3)
+    TW = np.asarray(tangents, np.float32).reshape(-1, 4)
+    if g.shape[0] != L["texels"] or N.shape[0] != 3 * nt or TW.shape[0] != 3 * nt:
+        raise ValueError(f"pack_normal_map: expected {L['texels']} gradients and {3 * nt} normals and tangents, got {g.shape[0]}, {N.shape[0]} and {TW.shape[0]}")
+    if trans_mat is not None and np.size(trans_mat) == 9:
+        R = np.eye(4, dtype=np.float32)
+        R[:3, :3] = np.asarray(trans_mat, np.float32).reshape(3, 3)
+        trans_mat = R
+    n, ok = _unit_gradients(g, trans_mat)
+    owner = texture_cell(c)[0]
+    tri = np.minimum(2 * np.arange(cells)[:, None] + owner.reshape(1, -1), nt - 1).reshape(-1)          # [cells c^2]
+    Nf, Tf = N[3 * tri], TW[3 * tri]
+    degenerate = frame_is_degenerate(Tf)
+    Nd, Td, w = Nf.astype(np.float64), Tf[:, :3].astype(np.float64), Tf[:, 3:].astype(np.float64)
+    with np.errstate(invalid="ignore", over="ignore"):
+        B = w * _cross3(Nd, Td)
+        z = _dot3(n, Nd)
+        rgba = np.stack([_normal_channel(_dot3(n, Td)), _normal_channel(_dot3(n, B)), _normal_channel(z), np.full(z.shape, 255, np.uint8)], 1)
+        back = ok & ~degenerate & (z < 0.0)
+    rgba = np.where((ok & ~degenerate)[:, None], rgba, np.array(NORMAL_MAP_FLAT, np.uint8))
+    cell = np.empty((L["rows"] * G, c, c, 4), np.uint8)
+    cell[:] = np.array(NORMAL_MAP_FLAT, np.uint8)
+    cell[:cells] = rgba.reshape(cells, c, c, 4)
+    image = np.ascontiguousarray(cell.reshape(L["rows"], G, c, c, 4).transpose(0, 2, 1, 3, 4).reshape(L["height"], L["width"], 4))
+    return image, {"bad_gradient": int((~ok).sum()), "back_facing": int(back.sum())}
+
+
+def decode_normal_map(image):
+    """RGBA8 texels -> the tangent-space vectors they stand for, float64 [..., 3] = c / 255 * 2 - 1 (not normalised).  For tests and inspection."""
+    return np.asarray(image)[..., :3].astype(np.float64) / 255.0 * 2.0 - 1.0
+
+
 def sample_texture(image, uv):
     """Bilinear sample the way a glTF viewer does with the file's sampler (LINEAR, CLAMP_TO_EDGE, texel centres at +0.5, no mipmaps) -> (value float64
     [n, C], touched: per sample the four (x, y, weight) it read).  ``image`` float [H, W, C], ``uv`` [n, 2] in [0, 1].  For tests and inspection."""
@@ -1228,8 +1377,15 @@ def obj_texture_header(path):
     return ("mtllib %s\nusemtl %s\n" % (os.path.basename(obj_texture_names(path)[0]), OBJ_MATERIAL)).encode("ascii")
 
 
-def write_obj_texture_files(path, text, png):
-    """``path`` (the header + ``text``: bytes or a uint8 array), its .mtl (one material, map_Kd) and its .png"""
+def obj_normal_map_name(path):
+    """-> path of the normal map's .png next to ``path``: stem_normal.png"""
+    return os.path.splitext(str(path))[0] + "_normal.png"
+
+
+def write_obj_texture_files(path, text, png, normal_png=None):
+    """``path`` (the header + ``text``: bytes or a uint8 array), its .mtl (one material, map_Kd) and its .png.  ``normal_png``: the tangent-space normal
+    map as a second file, stem_normal.png, named by a ``map_Bump`` and a ``norm`` line of the .mtl (the two spellings readers know); the "vn" records of
+    ``text`` then carry the flat normals.  An OBJ has no place for tangents: a reader derives them from the texture coordinates, the GLB is the defined form."""
     mtl, img = obj_texture_names(path)
     with open(path, "wb") as fh:
         fh.write(obj_texture_header(path))
@@ -1237,8 +1393,25 @@ def write_obj_texture_files(path, text, png):
     with open(mtl, "wb") as fh:
         fh.write(("newmtl %s\nKa 1.00000000 1.00000000 1.00000000\nKd 1.00000000 1.00000000 1.00000000\nKs 0.00000000 0.00000000 0.00000000\nmap_Kd %s\n"
                   % (OBJ_MATERIAL, os.path.basename(img))).encode("ascii"))
+        if normal_png is not None:
+            name = os.path.basename(obj_normal_map_name(path))
+            fh.write(("map_Bump %s\nnorm %s\n" % (name, name)).encode("ascii"))
     with open(img, "wb") as fh:
         fh.write(png)
+    if normal_png is not None:
+        with open(obj_normal_map_name(path), "wb") as fh:
+            fh.write(normal_png)
+
+
+def read_obj_normal_map(path):
+    """The normal map of a textured OBJ written above -> uint8 [H,W,4], or None for a file without one; checks that ``map_Bump`` and ``norm`` agree."""
+    here = os.path.dirname(str(path))
+    mtl = open(obj_texture_names(path)[0], "r", encoding="ascii").read().split("\n")
+    names = {k: [l.split()[1] for l in mtl if l.startswith(k + " ")] for k in ("map_Bump", "norm")}
+    if not names["map_Bump"] and not names["norm"]:
+        return None
+    assert names["map_Bump"] == names["norm"] and len(names["norm"]) == 1
+    return read_png(os.path.join(here, names["norm"][0]))
 
 
 def read_obj_texture(path):
@@ -1273,19 +1446,25 @@ def read_obj_texture(path):
             np.asarray(f, np.int32).reshape(-1, 3), read_png(os.path.join(here, image)))
 
 
-def write_textured(path, positions, uv, normals, image, bounds=None, png_level=1):
+def write_textured(path, positions, uv, normals, image, bounds=None, png_level=1, tangents=None, normal_image=None):
     """Host arrays of a textured mesh (texture_corners + pack_texture) -> ``path`` by its extension: a ``.glb`` with the PNG inside, or the ``.obj`` /
-    ``.mtl`` / ``.png`` triple.  The host layer and the DEFINITION of both files; export_asset with ``texture=`` is the device path."""
+    ``.mtl`` / ``.png`` triple.  The host layer and the DEFINITION of both files; export_asset with ``texture=`` is the device path.
+    ``tangents`` + ``normal_image`` (texture_frames + pack_normal_map; ``normals`` are then texture_frames' flat normals, which glTF needs beside TANGENT):
+    the normal map too -- TANGENT and a second image in the ``.glb``, ``stem_normal.png`` next to the ``.obj`` (which cannot carry the tangents)."""
     ext = _asset_ext(path)
     if ext == ".ply":
         raise ValueError("texture: a .ply has no texture coordinates; the output is .glb or .obj")
+    if (tangents is None) != (normal_image is None) or (tangents is not None and normals is None):
+        raise ValueError("texture: a normal map is tangents and a normal image, next to the flat normals")
     p = np.ascontiguousarray(positions, np.float32).reshape(-1, 3)
     png = png_bytes(image, png_level)
+    normal_png = None if normal_image is None else png_bytes(normal_image, png_level)
     if ext == ".glb":
         idx = np.arange(p.shape[0], dtype=np.uint32).reshape(-1, 3)
-        write_glb_buffers(path, idx, p, None, normals, np.stack([p.min(0), p.max(0)]) if bounds is None else bounds, uv=uv, png=png)
+        write_glb_buffers(path, idx, p, None, normals, np.stack([p.min(0), p.max(0)]) if bounds is None else bounds, uv=uv, png=png, tangents=tangents,
+                          normal_png=normal_png)
     else:
-        write_obj_texture_files(path, obj_texture_text_numpy(p, uv, normals, obj_coordinate_digits(p if bounds is None else bounds)), png)
+        write_obj_texture_files(path, obj_texture_text_numpy(p, uv, normals, obj_coordinate_digits(p if bounds is None else bounds)), png, normal_png)
 
 
 def convert_mesh(ply_path, out_path, min_component_faces=0, keep_largest=False, smooth_iterations=0, decimate_cell=0, simplify_faces=0, fill_holes=0):
@@ -1336,7 +1515,11 @@ def export_asset(path, verts_idx, tris, grid_R, bound_min=(-1.0, -1.0, -1.0), bo
     the device (csrc/mesh_export.hip), copied to the host once each and written in one go.  Returns (n_vertices, n_triangles).
     ``texture`` = {"texel": c, "rgb": fp32 [cells c^2, 3] on the device, the colours at ops.mesh_texture_points' points[, "stats": that op's counters]}:
     the textured asset instead (csrc/mesh_texture.hip) -- 3 M unwelded vertices with TEXCOORD_0 and no vertex colours, the atlas as a PNG inside the
-    ``.glb`` or as ``.mtl`` + ``.png`` next to the ``.obj`` (zlib level ``png_level``, None: the config default); a ``.ply`` path is refused."""
+    ``.glb`` or as ``.mtl`` + ``.png`` next to the ``.obj`` (zlib level ``png_level``, None: the config default); a ``.ply`` path is refused.
+    ``texture["grad"]`` (fp32 [cells c^2, 3] on the device: the raw SDF gradient at the same points): a tangent-space normal map too -- ops.mesh_texture_frames
+    on the corner buffers, ops.mesh_texture_normal_pack with the 3x3 of ``trans_mat``; TANGENT and a second image in the ``.glb``, ``stem_normal.png`` next
+    to the ``.obj``.  NORMAL is then the flat normal of the file's triangles whatever ``normals`` says (glTF needs NORMAL beside TANGENT, and the map is
+    relative to it); ``texture["normal_counts"]`` is set to the three counts (ops.normal_map_counts).  Still one synchronisation."""
     ext = _asset_ext(path)
     if texture is not None and ext == ".ply":
         raise ValueError("texture: a .ply has no texture coordinates; the output is .glb or .obj")
@@ -1348,19 +1531,35 @@ def export_asset(path, verts_idx, tris, grid_R, bound_min=(-1.0, -1.0, -1.0), bo
         from . import config
         level = config.mesh_texture_png_level(png_level)
         image = ops.mesh_texture_pack(texture["rgb"], m, texture["texel"])
-        pos, uv, nrm, idx, bounds = ops.mesh_texture_corners(verts_idx, tris, texture["texel"], grid_R, bound_min, bound_max, scale_mat, trans_mat, normals)
+        tgrad = texture.get("grad")
+        pos, uv, nrm, idx, bounds = ops.mesh_texture_corners(verts_idx, tris, texture["texel"], grid_R, bound_min, bound_max, scale_mat, trans_mat,
+                                                             None if tgrad is not None else normals)
+        tan = nimage = counters = None
+        if tgrad is not None:                                          # the frames of the file's own buffers; NORMAL is the flat normal beside TANGENT
+            nrm, tan, counters = ops.mesh_texture_frames(pos, uv)
+            nimage = ops.mesh_texture_normal_pack(tgrad, nrm, tan, m, texture["texel"], rotation=trans_mat, counters=counters)
         text = ops.obj_texture_text(pos, uv, nrm, bounds=bounds) if ext == ".obj" else None
-        stats = texture.get("stats")
-        dev = [t for t in ((image, text, stats) if ext == ".obj" else (image, idx, pos, nrm, uv, bounds, stats)) if t is not None]
-        host = ops.to_host_numpy(*dev)                                 # the one synchronisation of the whole chain
-        if stats is not None:
-            ops.texture_check(host[-1])
-        png = png_bytes(host[0], level)
-        if ext == ".obj":
-            write_obj_texture_files(path, host[1], png)
+        dev = dict(image=image, text=text)
+        if ext == ".glb":
+            dev.update(idx=idx, pos=pos, nrm=nrm, tan=tan, uv=uv, bounds=bounds)
+        dev.update(nimage=nimage, stats=texture.get("stats"), counters=counters)
+        dev = {k: t for k, t in dev.items() if t is not None}
+        host = dict(zip(dev, ops.to_host_numpy(*dev.values())))       # the one synchronisation of the whole chain
+        if "stats" in host:
+            ops.texture_check(host["stats"])
+        if "counters" in host:
+            texture["normal_counts"] = ops.normal_map_counts(host["counters"])
+        if "nimage" in host:                                          # zlib releases the interpreter lock: the two images compress side by side
+            from concurrent.futures import ThreadPoolExecutor
+            with ThreadPoolExecutor(max_workers=2) as pool:
+                png, normal_png = pool.map(lambda a: png_bytes(a, level), (host["image"], host["nimage"]))
         else:
-            k = 3 + (nrm is not None)                                 # image, indices, positions, [normals,] uv, bounds
-            write_glb_buffers(path, host[1].view(np.uint32), host[2], None, host[3] if nrm is not None else None, host[k + 1], uv=host[k], png=png)
+            png, normal_png = png_bytes(host["image"], level), None
+        if ext == ".obj":
+            write_obj_texture_files(path, host["text"], png, normal_png)
+        else:
+            write_glb_buffers(path, host["idx"].view(np.uint32), host["pos"], None, host.get("nrm"), host["bounds"], uv=host["uv"], png=png,
+                              tangents=host.get("tan"), normal_png=normal_png)
         return 3 * m, m
     if n == 0 or m == 0:
         if ext == ".glb":

@@ -1464,6 +1464,76 @@ def mesh_texture_corners(verts_idx, tris, texel, grid_R, bound_min=(-1.0, -1.0, 
     return pos, uv, nrm, idx, bounds
 
 
+def normal_map_counts(counters):
+    """The counters block of the two normal-map entries on the host (int64 [4]) -> {"degenerate", "bad_gradient", "back_facing"}; none is an error."""
+    c = np.asarray(counters).reshape(-1)
+    if c.shape[0] != len(mesh_io.NORMAL_MAP_COUNTS):
+        raise ValueError(f"normal_map_counts: expected {len(mesh_io.NORMAL_MAP_COUNTS)} counters, got {c.shape[0]}")
+    return {k: int(v) for k, v in zip(mesh_io.NORMAL_MAP_COUNTS[:3], c)}
+
+
+def _corner_buffers(positions, uv, what):
+    if positions.dim() != 2 or positions.shape[1] != 3 or positions.shape[0] < 3 or positions.shape[0] % 3 or tuple(uv.shape) != (positions.shape[0], 2):
+        raise ValueError(f"{what}: expected positions [3 M, 3] and uv [3 M, 2] of M >= 1 triangles, got {tuple(positions.shape)} and {tuple(uv.shape)}")
+    return positions.shape[0] // 3
+
+
+def _normal_map_counters(counters, dev, what):
+    if counters is None:
+        return torch.empty(len(mesh_io.NORMAL_MAP_COUNTS), dtype=torch.int64, device=dev)
+    if not torch.is_tensor(counters) or counters.dtype != torch.int64 or tuple(counters.shape) != (len(mesh_io.NORMAL_MAP_COUNTS),):
+        raise ValueError(f"{what}: counters are int64 [{len(mesh_io.NORMAL_MAP_COUNTS)}] on the device, got {counters!r}")
+    return counters
+
+
+@_on_device
+def mesh_texture_frames(positions, uv):
+    """One tangent frame per triangle of the textured asset from the buffers of mesh_texture_corners (== mesh_io.texture_frames, to the last bit;
+    definitions in include/o2345.h): positions fp32 [3M,3], uv fp32 [3M,2] -> (normals fp32 [3M,3], the flat unit normal of the file's winding, tangents fp32
+    [3M,4] = (T, w), counters int64 [4] on the device: mesh_io.NORMAL_MAP_COUNTS, the first written here).  A degenerate triangle gets (0, 1, 0) and
+    (1, 0, 0, 1) and is counted; nothing synchronises: the caller reads the counters with its own copy (normal_map_counts)."""
+    m = _corner_buffers(positions, uv, "mesh_texture_frames")
+    dev = positions.device
+    nrm = torch.empty(3 * m, 3, dtype=torch.float32, device=dev)
+    tan = torch.empty(3 * m, 4, dtype=torch.float32, device=dev)
+    counters = _normal_map_counters(None, dev, "mesh_texture_frames")
+    call("o2345_mesh_texture_frames", positions, uv, m, nrm, tan, counters)
+    return nrm, tan, counters
+
+
+def _rotation(rotation, dev, what):
+    """None, a device fp32 tensor of 9 elements, or the 3x3 / the 4x4 trans_mat on the host (uploaded) -> device fp32 [9] or None"""
+    if rotation is None:
+        return None
+    if torch.is_tensor(rotation) and rotation.is_cuda:
+        if rotation.dtype != torch.float32 or rotation.numel() != 9:
+            raise ValueError(f"{what}: a rotation on the device is float32 [9] or [3,3], got {tuple(rotation.shape)} {rotation.dtype}")
+        return rotation.contiguous().view(9)
+    r = host_f32(rotation)
+    if r.size != 9 and (r.size == 0 or r.size % 16):
+        raise ValueError(f"{what}: rotation is a 3x3 or the 4x4 trans_mat, got {r.shape}")
+    return torch.from_numpy(np.ascontiguousarray(r if r.size == 9 else r.reshape(-1, 4, 4)[0, :3, :3]).reshape(9)).to(dev)
+
+
+@_on_device
+def mesh_texture_normal_pack(grad, normals, tangents, nt, texel, rotation=None, counters=None):
+    """Cell-major raw SDF gradients at the texel points fp32 [cells c^2, 3] and the frames of mesh_texture_frames -> the tangent-space normal map uint8
+    [H, W, 4] on the device (== mesh_io.pack_normal_map, exactly).  ``rotation``: the 3x3 of trans_mat (a device fp32 [9] / [3,3], or a host 3x3 / 4x4,
+    uploaded) or None.  ``counters``: the block of mesh_texture_frames, whose first entry is kept, or None (a block of its own, not returned); entries 1
+    and 2 count bad gradients and back-facing texels.  Nothing synchronises."""
+    lay = mesh_io.texture_layout(nt, texel)
+    nt = int(nt)
+    if grad.dim() != 2 or tuple(grad.shape) != (lay["texels"], 3):
+        raise ValueError(f"mesh_texture_normal_pack: expected gradients [{lay['texels']}, 3], got {tuple(grad.shape)}")
+    if tuple(normals.shape) != (3 * nt, 3) or tuple(tangents.shape) != (3 * nt, 4):
+        raise ValueError(f"mesh_texture_normal_pack: expected normals [{3 * nt}, 3] and tangents [{3 * nt}, 4], got {tuple(normals.shape)} and {tuple(tangents.shape)}")
+    dev = grad.device
+    image = torch.empty(lay["height"], lay["width"], 4, dtype=torch.uint8, device=dev)
+    call("o2345_mesh_texture_normal_pack", grad, _rotation(rotation, dev, "mesh_texture_normal_pack"), normals, tangents, nt, lay["texel"], image,
+         _normal_map_counters(counters, dev, "mesh_texture_normal_pack"))
+    return image
+
+
 @_on_device
 def obj_texture_text(positions, uv, normals=None, K=None, bounds=None):
     """The buffers of mesh_texture_corners -> the records of the textured Wavefront OBJ (uint8 tensor on the device; == mesh_io.obj_texture_text_numpy):

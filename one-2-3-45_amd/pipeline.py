@@ -236,7 +236,7 @@ def _extraction_lattice(wt, vol, resolution):
 MeshFields = namedtuple("MeshFields", "verts verts_idx tris rgb u grad info texture")
 
 
-def _mesh_fields(wt, vol, proj, cam_pos, resolution, opts, fill_holes=0):
+def _mesh_fields(wt, vol, proj, cam_pos, resolution, opts, fill_holes=0, normal_map=False):
     """The device work of extract_mesh, once -> MeshFields; ``opts``: a config.MeshOptions.  Marching cubes, then the clean-up chain (ops.mesh_cleanup),
     then gradient and colours at the resulting vertices: the asset export reuses that gradient, the colour network's normal input, for NORMAL.
     ``texture_texel`` = c in [4, 64]: ``texture`` is the baked atlas -- "rgb", the colour network at the surface point of every texel
@@ -248,7 +248,12 @@ def _mesh_fields(wt, vol, proj, cam_pos, resolution, opts, fill_holes=0):
     ``fill_holes`` = n >= 3 (a keyword of its own, not a field of ``opts``; 0 = off: nothing is launched and ``info`` keeps its keys): ops.mesh_fill_holes
     closes the boundary loops of at most n edges directly after the clean-up chain -- behind the projection, because a cap does not lie on the zero set
     and must not be moved onto it, and in front of gradient, colours and texture, so that the cap's vertices and triangles are coloured and textured like
-    any other; ``info`` gains "fill", the counts of ops.mesh_fill_holes.  A filled rim is no boundary any more: the smoothing's pinning does not hold it."""
+    any other; ``info`` gains "fill", the counts of ops.mesh_fill_holes.  A filled rim is no boundary any more: the smoothing's pinning does not hold it.
+    ``normal_map`` (a keyword of its own too; it needs ``texture_texel``): ``texture`` keeps "grad", the SDF gradient at the texel points -- the second
+    result of the colour call that bakes the atlas, thrown away otherwise -- from which mesh_io.export_asset bakes the tangent-space normal map.  Nothing
+    more is evaluated; the frames come from the exported (smoothed) positions, the gradients from the unsmoothed surface points."""
+    if normal_map and not opts.texture_texel:
+        raise ValueError("normal_map: the normal map belongs to the texture atlas; set texture_texel")
     prec = wt.sdf_precision
     # build_volume's pair: ops.scatter_dense writes zeros into vol_cl wherever maskvol is zero, which is what the sparse lattice evaluation needs (a
     # hand-made ``vol`` must keep that: points without a kept corner voxel get the empty scene's value from the second extraction on)
@@ -269,8 +274,10 @@ def _mesh_fields(wt, vol, proj, cam_pos, resolution, opts, fill_holes=0):
         if opts.project_iterations:
             tpts, tpro = ops.mesh_project(wt.sdf_blob, vol["vol_cl"], tpts, resolution, opts.project_iterations, max_move=opts.project_max_move, precision=prec)
             tworld = _index_to_world(tpts, resolution).to(torch.float32).contiguous()
-        trgb, _ = _colours_at(wt, vol, proj, cam_pos, tworld)
+        trgb, tgrad = _colours_at(wt, vol, proj, cam_pos, tworld)
         texture = dict(texel=opts.texture_texel, rgb=trgb, stats=tstats, project=tpro, layout=ops.mesh_io.texture_layout(tris.shape[0], opts.texture_texel))
+        if normal_map:
+            texture["grad"] = tgrad
     if opts.smooth_iterations:
         verts_idx = ops.mesh_smooth(verts_idx, tris, opts.smooth_iterations)
         verts = _index_to_world(verts_idx, resolution)
@@ -278,8 +285,9 @@ def _mesh_fields(wt, vol, proj, cam_pos, resolution, opts, fill_holes=0):
 
 
 def _texture_block(texture):
-    """-> the "texture" entry of a result dict: {width, height, texel, texels} or None"""
-    return {k: texture["layout"][k] for k in ("width", "height", "texel", "texels")} if texture else None
+    """-> the "texture" entry of a result dict: {width, height, texel, texels} or None; with a normal map also "normal_map": True (a result without one
+    keeps the keys it had)"""
+    return dict({k: texture["layout"][k] for k in ("width", "height", "texel", "texels")}, **({"normal_map": True} if "grad" in texture else {})) if texture else None
 
 
 @torch.no_grad()
@@ -308,7 +316,8 @@ def export_mesh_ply(path, wt, vol, proj, cam_pos, resolution, scale_mat=None, tr
 
 @torch.no_grad()
 def export_mesh_asset(path, wt, vol, proj, cam_pos, resolution, scale_mat=None, trans_mat=None, normals=False, min_component_faces=None, keep_largest=None,
-                      smooth_iterations=None, decimate_cell=None, project_iterations=None, texture_texel=None, simplify_faces=None, fill_holes=None):
+                      smooth_iterations=None, decimate_cell=None, project_iterations=None, texture_texel=None, simplify_faces=None, fill_holes=None,
+                      normal_map=None):
     """export_mesh_ply followed by convert_mesh_format (utils/utils.py:31-47) without the PLY in between: the coloured mesh as ``.glb`` or ``.obj`` in the
     asset frame ((x, y, z) -> (x, z, y), faces reversed), buffers / text packed on the device (csrc/mesh_export.hip).  ``normals=True`` adds unit vertex
     normals from the SDF gradient the vertex colouring already computed (at the unsmoothed vertices when ``smooth_iterations`` is on, at the projected ones
@@ -316,12 +325,15 @@ def export_mesh_asset(path, wt, vol, proj, cam_pos, resolution, scale_mat=None, 
     ``texture_texel`` (None: the config default, 0 = off) = c in [4, 64]: the textured asset instead -- the colour network baked into an atlas of one
     c x c cell per pair of triangles (_mesh_fields, ``texture``), 3 M unwelded vertices with texture coordinates and no vertex colours; the PNG sits inside
     the ``.glb``, or as ``.mtl`` + ``.png`` next to the ``.obj``.  A ``.ply`` path with a texture requested raises ValueError.  ``fill_holes``:
-    extract_mesh's."""
+    extract_mesh's.  ``normal_map`` (None: the config default O2345_MESH_NORMAL_MAP, off: nothing is launched and the file keeps its bytes): the textured
+    asset also carries a tangent-space normal map baked from the SDF gradient at the texel points (mesh_io.export_asset, ``texture["grad"]``), so that a
+    decimated or simplified mesh is lit like the full surface; NORMAL is then the flat face normal whatever ``normals`` says.  With ``texture_texel`` off
+    it raises ValueError."""
     from . import mesh_io
     opts = config.mesh_options(min_component_faces, keep_largest, decimate_cell, project_iterations, smooth_iterations, texture_texel, simplify_faces)
     if opts.texture_texel and mesh_io._asset_ext(path) == ".ply":
         raise ValueError("texture: a .ply has no texture coordinates; the output is .glb or .obj")
-    m = _mesh_fields(wt, vol, proj, cam_pos, resolution, opts, fill_holes=config.mesh_fill_holes(fill_holes))
+    m = _mesh_fields(wt, vol, proj, cam_pos, resolution, opts, fill_holes=config.mesh_fill_holes(fill_holes), normal_map=config.mesh_normal_map(normal_map))
     return mesh_io.export_asset(path, m.verts_idx, m.tris, resolution, scale_mat=scale_mat, trans_mat=trans_mat,
                                 vertex_colors=m.rgb if m.verts_idx.shape[0] else None, normals=m.grad if normals else None, texture=m.texture)
 
@@ -511,7 +523,7 @@ def _write_previews(wt, vol, proj, cam_pos, u, s, n, folder):
 @torch.no_grad()
 def reconstruct_folder(root_dir, name, wt, out_ply, D=96, resolution=256, render_val_image=False, output_format=None, min_component_faces=None,
                        keep_largest=None, smooth_iterations=None, decimate_cell=None, project_iterations=None, texture_texel=None, preview_views=None, mesh_error=None,
-                       simplify_faces=None, mesh_audit=None, fill_holes=None, mesh_intersections=None, mesh_preview_views=None):
+                       simplify_faces=None, mesh_audit=None, fill_holes=None, mesh_intersections=None, mesh_preview_views=None, normal_map=None):
     """run.py's reconstruction stage without the reference tree: Zero123-style folder (dataset.SceneFolder) -> coloured mesh (binary PLY in
     the original frame), optionally the val image of the target view.  ``output_format`` ".obj" / ".glb" (run.py --output_format) also writes
     ``mesh<ext>`` next to ``out_ply`` in the asset frame, from the same device buffers.  The mesh options are extract_mesh's.  Returns
@@ -538,11 +550,17 @@ def reconstruct_folder(root_dir, name, wt, out_ply, D=96, resolution=256, render
     its bytes) = n >= 1: n rasterized views (render_mesh) of the FINAL mesh -- after the clean-up chain and the hole filling, in the world frame, with the
     vertex colours the PLY gets -- from the cameras of ``preview_views``, written as ``mesh_preview_000.png`` ... next to the PLY; unlike the surface
     previews they show what the mesh options did.  The result's "mesh_previews" is the list of {path, color, normal, depth, face, c2w, info}, and
-    "mesh_preview_mesh" the rendered mesh: {verts fp64 [N,3], tris, vertex_colors float32 [N,3] or None}, on the device."""
+    "mesh_preview_mesh" the rendered mesh: {verts fp64 [N,3], tris, vertex_colors float32 [N,3] or None}, on the device.
+    ``normal_map`` (None: the config default O2345_MESH_NORMAL_MAP, off: nothing is launched and every file keeps its bytes): export_mesh_asset's
+    tangent-space normal map for the textured ``output_format`` asset; the result's "texture" block then has "normal_map": True.  With ``texture_texel`` off it
+    raises ValueError."""
     import os
     from . import dataset, mesh_io
     if output_format not in (None, ".ply", ".obj", ".glb"):
         raise ValueError(f"reconstruct_folder: output_format {output_format!r} is not one of '.ply', '.obj', '.glb'")
+    nmap = config.mesh_normal_map(normal_map)
+    if nmap and not config.mesh_texture_texel(texture_texel):
+        raise ValueError("normal_map: the normal map belongs to the texture atlas; set texture_texel")
     s = dataset.SceneFolder(root_dir, "export_mesh", specific_dataset_name=name)[0]
     dev = wt.device
     T = lambda t: t.to(dev).contiguous().float()
@@ -552,7 +570,7 @@ def reconstruct_folder(root_dir, name, wt, out_ply, D=96, resolution=256, render
     previews = config.preview_views(preview_views)
     fill = config.mesh_fill_holes(fill_holes)
     asset = output_format in (".obj", ".glb")
-    m = _mesh_fields(wt, vol, proj, cam_pos, resolution, opts if asset else opts._replace(texture_texel=0), fill_holes=fill)          # the atlas is for the asset only
+    m = _mesh_fields(wt, vol, proj, cam_pos, resolution, opts if asset else opts._replace(texture_texel=0), fill_holes=fill, normal_map=nmap and asset)   # the atlas is for the asset only
     rgb = m.rgb if m.verts_idx.shape[0] else None
     nv, nt = mesh_io.export_mesh(out_ply, m.verts_idx, m.tris, resolution, scale_mat=s["scale_mat"], trans_mat=s["trans_mat"], vertex_colors=rgb)
     out = {"vertices": nv, "triangles": nt, "kept_voxels": int(vol["n_voxels"]), "ply": str(out_ply), "components": m.info["components"],

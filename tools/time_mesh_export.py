@@ -22,13 +22,17 @@ fed the same arrays.  Two meshes: BASELINE config 2 (8 views, 128^3 volume, 256^
              count and image size, the three kernels alone (HIP events), the gradient + colour calls over the texel points, the D2H copy of the
              textured GLB's buffers, mesh_io.png_bytes at zlib levels 0 and 1 (host clock), and whole-export variants textured against
              vertex-coloured inside the same alternating loop as the others
+  normal map the tangent-space normal map next to the atlas (k_tex_frames, k_tex_normal_pack in the same unit): the two kernels alone in the texture
+             block, and the whole export with the map next to the textured one (glb_decimate2_texture4_normal against glb_decimate2_texture4)
   simplify   quadric-error edge collapse (csrc/mesh_simplify.hip) of the config's mesh down to the face count clustering reached at cell 2: the rounds and
              the collapses of each, bytes-equality with the host twin (mesh_io.simplify_mesh, host clock, one call), the op as a whole (HIP events; it
              synchronises once per round), ops.mesh_distance of the result against the raw mesh in both directions next to the same numbers for the
              cell-2 clustering, each also after 4 projection rounds, and whole-export variants inside the same alternating loop as the others
 Medians over --reps calls after --warmup calls; the ratio against the PLY of the SAME run is what to read.  Prints one JSON line.
 
-    python tools/time_mesh_export.py [--reps 9] [--warmup 3] [--skip-512]
+    python tools/time_mesh_export.py [--reps 9] [--warmup 3] [--skip-512] [--whole glb_decimate2_texture4,glb_decimate2_texture4_normal]
+
+--whole NAMES times only the named whole-export variants (those that need no simplification target) and skips every other block.
 """
 import argparse
 import ctypes
@@ -81,6 +85,9 @@ def med_events(fn, reps, warmup):
 def one_mesh(dev, wt, tmp, D, R, ray_scale, a, numpy_writer):
     inp = bench.make_inputs(dev, 8, 0, ray_scale)
     vol = pipeline.build_volume(wt, inp["imgs"], inp["aff"], inp["origin"], D, 2.0 / (D - 1))
+    if a.whole:
+        whole = whole_variants(lambda e: os.path.join(tmp, "mesh" + e), (wt, vol, inp["proj"], inp["cam_pos"], R), None)
+        return {"volume": D, "grid": R, "whole_ms": time_whole({k: whole[k] for k in a.whole.split(",")}, a.reps)}
     _, verts_idx, tris, rgb, u, g, _, _ = pipeline._mesh_fields(wt, vol, inp["proj"], inp["cam_pos"], R, config.mesh_options())
     n, m = int(verts_idx.shape[0]), int(tris.shape[0])
     _, f_verts, f_tris, f_rgb, _, _, cc, _ = pipeline._mesh_fields(wt, vol, inp["proj"], inp["cam_pos"], R, config.mesh_options(keep_largest=True))
@@ -144,7 +151,6 @@ def one_mesh(dev, wt, tmp, D, R, ray_scale, a, numpy_writer):
     })
     # Taubin smoothing, 10 iterations: table, steps, both; the host twin on the same arrays as the yardstick
     L = importlib.import_module("one-2-3-45_amd._lib").lib()
-    IT = 10
     offsets, neighbours, boundary = ops.mesh_vertex_adjacency(tris, n)
     s_tmp, s_out = torch.empty_like(verts_idx), torch.empty_like(verts_idx)
     ptr = lambda t: ctypes.c_void_p(t.data_ptr())
@@ -166,7 +172,6 @@ def one_mesh(dev, wt, tmp, D, R, ray_scale, a, numpy_writer):
                                    "mesh_smooth": med_events(lambda: ops.mesh_smooth(verts_idx, tris, IT), a.reps, a.warmup)},
                      "host_adjacency_ms_once": (t1 - t0) * 1e3, "host_twin_ms_once": (t2 - t1) * 1e3}
     # decimation at cell 2: the op alone, the host twin on the same arrays, and the gradient + colour work that is left
-    CELL = 2.0
     d_verts, d_tris, _, d_info = ops.mesh_decimate(verts_idx, tris, CELL)
     t0 = time.perf_counter()
     twin = mio.decimate_mesh(hv, hf, CELL)
@@ -179,7 +184,6 @@ def one_mesh(dev, wt, tmp, D, R, ray_scale, a, numpy_writer):
                                       "grad_color_decimated": med_events(lambda: grad_color(d_verts), a.reps, a.warmup)},
                            host_twin_ms_once=(t1 - t0) * 1e3)
     # projection onto the zero set, 4 rounds: the op alone on the marching-cubes vertices and on the decimated ones
-    PIT = 4
     proj_op = lambda v, mm: ops.mesh_project(wt.sdf_blob, vol["vol_cl"], v, R, PIT, max_move=mm, precision=wt.sdf_precision)
     res["project"] = {"iterations": PIT}
     for key, v, mm in (("all", verts_idx, 1.0), ("decimated", d_verts, max(1.0, CELL))):
@@ -217,8 +221,11 @@ def one_mesh(dev, wt, tmp, D, R, ray_scale, a, numpy_writer):
         lay = mio.texture_layout(int(tt.shape[0]), c)
         _, tworld, _ = ops.mesh_texture_points(tv, tt, c, R)
         trgb = grad_color_pts(tworld)
+        tgrad = ops.sdf_mlp(wt.sdf_blob, vol["vol_cl"], tworld, variant=2, precision=wt.sdf_precision)["grad"]
         image = ops.mesh_texture_pack(trgb, int(tt.shape[0]), c)
         bufs = [image] + [t for t in ops.mesh_texture_corners(tv, tt, c, R) if t is not None]
+        t_pos, t_uv = bufs[1], bufs[2]
+        t_nrm, t_tan, _ = ops.mesh_texture_frames(t_pos, t_uv)
         h_image = image.cpu().numpy()
         png = {}
         for level in (0, 1):
@@ -229,10 +236,20 @@ def one_mesh(dev, wt, tmp, D, R, ray_scale, a, numpy_writer):
             "kernel_ms": {"tex_points": med_events(lambda: ops.mesh_texture_points(tv, tt, c, R, validate=False), a.reps, a.warmup),
                           "tex_pack": med_events(lambda: ops.mesh_texture_pack(trgb, int(tt.shape[0]), c), a.reps, a.warmup),
                           "tex_corners": med_events(lambda: ops.mesh_texture_corners(tv, tt, c, R), a.reps, a.warmup),
+                          "tex_frames": med_events(lambda: ops.mesh_texture_frames(t_pos, t_uv), a.reps, a.warmup),
+                          "tex_normal_pack": med_events(lambda: ops.mesh_texture_normal_pack(tgrad, t_nrm, t_tan, int(tt.shape[0]), c), a.reps, a.warmup),
                           "grad_color_texels": med_events(lambda: grad_color_pts(tworld), a.reps, a.warmup)},
             "d2h_ms": med(lambda: ops.to_host_numpy(*bufs), a.reps, a.warmup), "png_ms": png}
-        del trgb, image, bufs, tworld
-    A = (wt, vol, inp["proj"], inp["cam_pos"], R)
+        del trgb, tgrad, image, bufs, tworld, t_pos, t_uv, t_nrm, t_tan
+    res["whole_ms"] = time_whole(whole_variants(P, (wt, vol, inp["proj"], inp["cam_pos"], R), TARGET), a.reps)
+    return res
+
+
+CELL, PIT, IT = 2.0, 4, 10            # one_mesh's decimation cell, projection rounds and smoothing iterations
+
+
+def whole_variants(P, A, TARGET):
+    """name -> call of every whole-export variant; TARGET: the face count of the simplification rows, None to leave them out"""
     whole = {
         "ply": lambda: pipeline.export_mesh_ply(P(".ply"), *A),
         "glb": lambda: pipeline.export_mesh_asset(P(".glb"), *A),
@@ -251,27 +268,34 @@ def one_mesh(dev, wt, tmp, D, R, ray_scale, a, numpy_writer):
         "ply_decimate2_project4": lambda: pipeline.export_mesh_ply(P("_dp.ply"), *A, decimate_cell=CELL, project_iterations=PIT),
         "glb_decimate2_project4": lambda: pipeline.export_mesh_asset(P("_dp.glb"), *A, decimate_cell=CELL, project_iterations=PIT),
         "glb_decimate2_texture4": lambda: pipeline.export_mesh_asset(P("_dt4.glb"), *A, decimate_cell=CELL, texture_texel=4),
+        "glb_decimate2_texture4_normal": lambda: pipeline.export_mesh_asset(P("_dt4n.glb"), *A, decimate_cell=CELL, texture_texel=4, normal_map=True),
         "glb_decimate2_texture8": lambda: pipeline.export_mesh_asset(P("_dt8.glb"), *A, decimate_cell=CELL, texture_texel=8),
         "obj_decimate2_texture4": lambda: pipeline.export_mesh_asset(P("_dt4.obj"), *A, decimate_cell=CELL, texture_texel=4),
         "glb_decimate2_project4_texture4": lambda: pipeline.export_mesh_asset(P("_dpt4.glb"), *A, decimate_cell=CELL, project_iterations=PIT, texture_texel=4),
         "glb_texture4": lambda: pipeline.export_mesh_asset(P("_t4.glb"), *A, texture_texel=4),
-        "ply_simplify": lambda: pipeline.export_mesh_ply(P("_q.ply"), *A, simplify_faces=TARGET),
-        "glb_simplify": lambda: pipeline.export_mesh_asset(P("_q.glb"), *A, simplify_faces=TARGET),
-        "ply_simplify_project4": lambda: pipeline.export_mesh_ply(P("_qp.ply"), *A, simplify_faces=TARGET, project_iterations=PIT),
     }
-    # alternated like the stage variants; the spread (min .. max) of each is what a difference between two of them has to exceed
+    if TARGET is not None:
+        whole.update({
+            "ply_simplify": lambda: pipeline.export_mesh_ply(P("_q.ply"), *A, simplify_faces=TARGET),
+            "glb_simplify": lambda: pipeline.export_mesh_asset(P("_q.glb"), *A, simplify_faces=TARGET),
+            "ply_simplify_project4": lambda: pipeline.export_mesh_ply(P("_qp.ply"), *A, simplify_faces=TARGET, project_iterations=PIT),
+        })
+    return whole
+
+
+def time_whole(whole, reps):
+    """alternated like the stage variants; the spread (min .. max) of each is what a difference between two of them has to exceed"""
     for fn in whole.values():
         fn()
     wacc = {k: [] for k in whole}
-    for _ in range(max(3, a.reps)):
+    for _ in range(max(3, reps)):
         for k, fn in whole.items():
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             fn()
             torch.cuda.synchronize()
             wacc[k].append((time.perf_counter() - t0) * 1e3)
-    res["whole_ms"] = {k: {"median_ms": statistics.median(v), "min_ms": min(v), "max_ms": max(v)} for k, v in wacc.items()}
-    return res
+    return {k: {"median_ms": statistics.median(v), "min_ms": min(v), "max_ms": max(v)} for k, v in wacc.items()}
 
 
 def main():
@@ -279,6 +303,7 @@ def main():
     ap.add_argument("--reps", type=int, default=9)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--skip-512", action="store_true")
+    ap.add_argument("--whole", default="", help="comma-separated whole-export variants: time only these")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "needs a GPU: nothing here can be timed without one"
     dev = torch.device("cuda:0")
