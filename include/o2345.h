@@ -346,6 +346,12 @@ int o2345_view_count_unlisted(const float* pts, long long n, const float* skip_i
 /* Projector + GeneralRenderingNetwork fused, every linear layer on fp32 MFMA (k_color_pts, csrc/color_pts.hip: a wave owns 32 points and walks the
  * views; any V in [1,255]); blob from weights.pack_color_mfma_blob.  pts [P,3]; index / n_dev: optional list of point slots + device-side count;
  * exactly one of query_cam [3] (Projector.compute) / normals [P,3] (compute_view_independent).  out_rgb [P,3], out_nviews [P] (optional).
+ * View counts, three regimes (tests/test_gpu_many_views.py runs each): counts of valid views are uint8, so every entry that takes V
+ * (o2345_color_points_*, o2345_color_from_features, o2345_project_features, o2345_view_count*, o2345_costvol_index) accepts 1 .. 255 and refuses 0 and
+ * 256 with an error status before it writes anything; the wave-uniform skip of the views that see none of a tile's 32 points keeps a 64-bit mask of
+ * active views and exists for V <= 64 -- from 65 views on every (tile, view) pair is evaluated, same results; o2345_list_sort_by_visibility has a
+ * 32-bit signature and refuses V > 32, and o2345_render_rays groups its point list with it only for V <= 32 (above, the list stays in emission
+ * order and o2345_render_workspace_bytes lays the workspace out without the sort's buffers).
  * stats_dev (optional, [4], caller-owned and caller-zeroed): work counters the launch ADDS to -- (32-point tile, view) pairs evaluated in the
  * pooling pass / the network pass, tiles, tiles that evaluated every view.  (ABI 1.x kept these in a process-global buffer; the pure-VALU
  * kernel o2345_color_points of ABI 1.x is gone: 206 ms against 37.) */

@@ -549,7 +549,10 @@ def color_stats_read(buf):
 def color_points(blob, vol_cl, maskvol, cmaps, proj, cam_pos, pts, query_cam=None, normals=None, index=None, n_dev=None,
                  want_nviews=True, mfma="x3", stats=None, tile_queue=None, out=None):
     """Projector + GeneralRenderingNetwork fused (k_color_pts).  mfma="x3": split-f16 matrix steps (blob from weights.pack_color_x3_blob, the default
-    numerical mode); mfma=True: fp32 matrix-core form (pack_color_mfma_blob).  Any view count up to 255.  stats: color_stats_buffer().
+    numerical mode); mfma=True: fp32 matrix-core form (pack_color_mfma_blob).  Any view count from 1 to 255 (nviews is uint8; 0 and 256 raise), in three
+    regimes with the same results: up to 32 views render_rays groups its point list by visibility before this kernel (list_sort_by_visibility, which
+    refuses more), up to 64 the kernel skips the views that see none of a tile's 32 points (a 64-bit mask of active views), from 65 on it evaluates
+    every (tile, view) pair -- tests/test_gpu_many_views.py runs V = 33, 64, 65 and 255.  stats: color_stats_buffer().
     tile_queue: tile_queue_buffer() -- the tail of the tile list is claimed by the waves that finish first (the _q entry points); same results bit for
     bit.  out: (rgb [P,3] float32, nviews [P] uint8 or None) to write into instead of fresh zeroed tensors (slots not listed stay untouched)."""
     if mfma is False or mfma is None:

@@ -63,8 +63,10 @@ def make_scene(n_views=8, image_seed=0, hw=(256, 256), polar=60.0, images="rand"
     """Return the hot path's input contract as numpy arrays, batch dim dropped.
 
     n_views = 32 reproduces the reference configuration (all stage-2 views); n_views = 8 takes one
-    stage-2 view per stage-1 view (files ``{k}_0.png``: source indices 0,4,...,28).
+    stage-2 view per stage-1 view (files ``{k}_0.png``: source indices 0,4,...,28).  The rig has 32 source views: more raises.
     """
+    if not 1 <= int(n_views) <= 32:
+        raise ValueError(f"make_scene: n_views = {n_views}, but the rig has 32 source views (1 to 32 can be taken from it)")
     h, w = hw
     K4 = np.eye(4)
     f = 280.0 * w / 256.0                                # reference: 280 at 256^2

@@ -239,6 +239,78 @@ def scene(H, W, V, D, dims=None):
     return _finish(s)
 
 
+SPHERE_RADIUS = 1.6
+SPHERE_QUERY = np.array([0.4, -1.9, 0.7])
+SPHERE_HW = (20, 28)
+MANY_VIEWS = (33, 34, 64, 65, 255)
+
+
+@functools.lru_cache(maxsize=None)
+def sphere_scene(H, W, V, D, dims=None):
+    """V distinct cameras for view counts the 32-view rig of synth.make_scene cannot give: centres on a Fibonacci spiral over the upper half (z > 0)
+    of the sphere of radius SPHERE_RADIUS around the volume, each looking at its own seeded point within 0.1 of the origin, x to the right, y down, z
+    forward; synth's intrinsics scaled to the image (f = 280 W / 256, principal point (W / 2, H / 2)).  At 20 x 28 a frustum's half angles are 18 and
+    25 degrees: it holds the ball of radius 0.3 around the origin and, from 1.6 away, only part of [-1, 1]^3, so a point is seen by anything from
+    none (low corners: every camera is above) to all of the views.  proj, aff and cam_pos are formed once in float64 and rounded once, as in
+    scene(); K [V,3,3] and w2cs [V,4,4] are the same cameras for the entries that take those.  A query camera of the same kind at SPHERE_QUERY:
+    query_cam [3], query_c2w [4,4], query_K [3,3]."""
+    g = _rng(12, V, H, W)
+    k = np.arange(V)
+    z = 1.0 - (k + 0.5) / V
+    phi = k * np.pi * (3.0 - np.sqrt(5.0))
+    r = np.sqrt(1.0 - z * z)
+    centre = np.concatenate([SPHERE_RADIUS * np.stack([r * np.cos(phi), r * np.sin(phi), z], 1), SPHERE_QUERY[None]])      # the query camera last
+    target = g.uniform(-1.0, 1.0, (V + 1, 3)) * (0.1 / np.sqrt(3.0))
+    fwd = target - centre
+    fwd /= np.linalg.norm(fwd, axis=1, keepdims=True)
+    up = np.where(np.abs(fwd[:, 2:3]) > 0.95, np.array([[1.0, 0.0, 0.0]]), np.array([[0.0, 0.0, 1.0]]))
+    right = np.cross(fwd, up)
+    right /= np.linalg.norm(right, axis=1, keepdims=True)
+    down = np.cross(fwd, right)
+    c2w = np.tile(np.eye(4)[None], (V + 1, 1, 1))
+    c2w[:, :3, 0], c2w[:, :3, 1], c2w[:, :3, 2], c2w[:, :3, 3] = right, down, fwd, centre
+    w2c = np.linalg.inv(c2w[:V])
+    f = 280.0 * W / 256.0
+    K = np.array([[f, 0, W / 2], [0, f, H / 2], [0, 0, 1]])
+    aff = np.tile(np.eye(4)[None], (V, 1, 1))
+    aff[:, :3, :4] = K @ w2c[:, :3, :4]
+    dims = (D, D, D) if dims is None else tuple(dims)
+    s = dict(sc=None, H=H, W=W, V=V, D=D, dims=dims, voxel_size=2.0 / (D - 1), origin=_t([-1, -1, -1]), aff=_t(aff), proj=_t(aff[:, :3, :4]),
+             cam_pos=_t(centre[:V]), query_cam=_t(SPHERE_QUERY), query_c2w=_t(c2w[V]), query_K=_t(K), K=_t(np.tile(K[None], (V, 1, 1))), w2cs=_t(w2c))
+    return _finish(s)
+
+
+SPHERE_TILES = dict(partial=0, none=1, all=2)            # the 32-point tiles the first 96 points of sphere_points are
+
+
+@functools.lru_cache(maxsize=None)
+def sphere_points(H, W, V, D, n=257):
+    """n points of sphere_scene(H, W, V, D), picked by the float64 reference from a seeded pool in (-1, 1)^3, none of them inside the border band.  The
+    first three 32-point tiles (one wave of the colour kernels each, SPHERE_TILES):
+      partial   occupied points around the one that the last view and the fewest others see: every point is seen by 1 to V - 1 views, some view
+                sees none of them
+      none      occupied points that project into no view at all
+      all       points seen by all V views
+    then pool points in seeded order.  -> (pts [n,3], nviews int64 [n] of the float64 reference, mask bool [V,n])."""
+    s = sphere_scene(H, W, V, D)
+    pool = _t(_rng(27, V, H, W, D).uniform(-1.0, 1.0, (8192, 3)))
+    pm = project_pts(pool, s["proj"], H, W, F64)["mask"]
+    gm = geometry_mask(s["maskvol"], pool, F64)
+    mask = pm & gm[None]
+    nv = mask.sum(0)
+    ok = ~ambiguous_points(s, pool)[0]
+    part = torch.nonzero(ok & gm & (nv > 0) & (nv < V))[:, 0]
+    last = part[mask[V - 1, part]]
+    anchor = last[torch.argmin(nv[last])]
+    near_anchor = part[torch.argsort((pool[part] - pool[anchor]).norm(dim=1))[:32]]
+    none = torch.nonzero(ok & gm & (pm.sum(0) == 0))[:32, 0]
+    every = torch.nonzero(ok & (nv == V))[:32, 0]
+    assert len(near_anchor) == len(none) == len(every) == 32, (V, len(near_anchor), len(none), len(every))
+    rest = torch.nonzero(ok)[:max(0, n - 96), 0]
+    sel = torch.cat([near_anchor, none, every, rest])[:n]
+    return pool[sel].contiguous(), nv[sel], mask[:, sel]
+
+
 RIG_H, RIG_W, RIG_D = 13, 17, 17
 
 

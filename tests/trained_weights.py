@@ -354,6 +354,48 @@ def color_case(V, P, seed=0):
     return dict(d, r32=r32, r64=r64, nviews=nv)
 
 
+MANY_VS = (33, 64, 65, 255)                  # past the list sort's 32 views | the last count with the view skip | the first without | the uint8 maximum
+MANY_CASES = [(V, P) for V in MANY_VS for P in COLOR_PS]
+MASK_KINDS = ("tile_hidden", "tile_hidden_one_blind", "all_views", "one_view")
+BLIND_POINT = 5
+
+
+def many_view_mask(V, P, kind, seed=0):
+    """The masks color_inputs' random 30 % never draws, on the first 32-point tile (one wave of k_color_pts; all P points when P < 32):
+      tile_hidden            every view from 32 on -- view 32 at V = 33, view 63 at V = 64 -- hidden from the whole tile, every point of which keeps a
+                             view below 32: the wave-uniform skip drops those views in both passes
+      tile_hidden_one_blind  the same, and point BLIND_POINT (point 0 when P is smaller) seen by no view: the network pass may skip nothing
+      all_views              every view valid for every point: the count reaches V
+      one_view               point p seen by view (V - 1 - p) mod V alone: point 0 by the last view
+    -> bool [V,P]"""
+    mask = color_inputs(V, P, seed)["mask"].clone()
+    n = min(P, 32)
+    if kind in ("tile_hidden", "tile_hidden_one_blind"):
+        mask[32:, :n] = False
+        mask[torch.arange(n) % 32, torch.arange(n)] = True
+        if kind == "tile_hidden_one_blind":
+            mask[:, min(BLIND_POINT, P - 1)] = False
+    elif kind == "all_views":
+        mask[:] = True
+    elif kind == "one_view":
+        mask[:] = False
+        mask[(V - 1 - torch.arange(P)) % V, torch.arange(P)] = True
+    else:
+        raise KeyError(kind)
+    return mask.contiguous()
+
+
+@functools.lru_cache(maxsize=None)
+def many_view_case(V, P, kind=None, seed=0):
+    """color_case(V, P) (kind None), or the same tensors under many_view_mask(V, P, kind) with the oracle's float32 / float64 colours for that mask"""
+    if kind is None:
+        return color_case(V, P, seed)
+    d = dict(color_inputs(V, P, seed), mask=many_view_mask(V, P, kind, seed))
+    sd = trained_color_state_dict(seed)
+    (r32, _), (r64, nv) = color_eval(d, sd, F32), color_eval(d, sd, F64)
+    return dict(d, r32=r32, r64=r64, nviews=nv)
+
+
 def color_bound(r32, r64, x3):
     """-> (e_ref, bound): rule E (+ 5e-6 for the split-f16 form), never above 1e-4 max(1, magnitude)"""
     return bounded(r32, r64, extra=5e-6 if x3 else 0.0, ceiling=1e-4)
