@@ -68,7 +68,8 @@ const char* o2345_last_error(void);
  * o2345_mesh_audit.
  * Additive since 2.3 (no existing entry changed, the version stays 230): the hole-filling entries o2345_mesh_fill_workspace_bytes, o2345_mesh_fill_count,
  * o2345_mesh_fill_emit; the self-intersection entries o2345_mesh_intersect_workspace_bytes, o2345_mesh_intersect_count, o2345_mesh_intersect_emit; the
- * rasterizer entries o2345_mesh_raster_workspace_bytes, o2345_mesh_raster_count, o2345_mesh_raster_emit, o2345_mesh_raster_shade. */
+ * rasterizer entries o2345_mesh_raster_workspace_bytes, o2345_mesh_raster_count, o2345_mesh_raster_emit, o2345_mesh_raster_shade; the textured
+ * shading entry o2345_mesh_raster_shade_textured. */
 int o2345_version(void);
 /* Layout self-description of the declared structs as THIS library was compiled (sizeof, and offsetof of every field in declaration order): a binding
  * asserts its own structs against it at load time (one-2-3-45_amd/_lib.py does) -- a field added on one side only cannot corrupt calls silently.
@@ -905,7 +906,8 @@ int o2345_mesh_intersect_emit(const double* verts, const void* tris, int index_b
  * of scratch, sized by the counted total and by nothing else) writes face, depth, bary and counts[O2345_RASTER_PIXELS].  _shade writes kind, rgb, nrm.
  * Integer atomics appear in the binning only, none on pixels; no kernel waits for another workgroup; the same bytes on every run.
  * Limits: no near clipping (a face with a corner in front of `near` is dropped whole), one sample per pixel (no anti-aliasing), corners snapped to 1/256
- * pixel, a face with a corner beyond 2^21 pixels is dropped.  Not done: texture-atlas sampling (face + bary are what an atlas lookup starts from). */
+ * pixel, a face with a corner beyond 2^21 pixels is dropped.  Texture-atlas sampling is o2345_mesh_raster_shade_textured's, below: it starts from face +
+ * bary. */
 enum { O2345_RASTER_BAD_INDEX = 0, O2345_RASTER_NONFINITE = 1, O2345_RASTER_NEAR = 2, O2345_RASTER_RANGE = 3, O2345_RASTER_DEGENERATE = 4,
        O2345_RASTER_CULLED = 5, O2345_RASTER_OFFSCREEN = 6, O2345_RASTER_BINNED = 7, O2345_RASTER_PAIRS = 8, O2345_RASTER_PIXELS = 9,
        O2345_RASTER_COUNTS = 10 };
@@ -920,6 +922,38 @@ int o2345_mesh_raster_emit(long long nv, long long nt, float fx, float fy, float
                            void* stream);
 int o2345_mesh_raster_shade(const double* verts, const void* tris, int index_bytes, long long nv, long long nt, const int* face, const float* bary, int H, int W,
                             const float* colors_or_null, const float* normals_or_null, uint8_t* kind, float* rgb, float* nrm, void* stream);
+/* Textured shading (additive since 2.3; none in the reference): a second shading stage behind the same visibility, on the buffers a textured asset file
+ * holds, in the asset's own frame.  Equal to raster.shade_textured to the last bit (csrc/mesh_raster_tex_math.h is the one spelling): fp64, one operation
+ * at a time, in the order written; a dot product is (x x + y y) + z z; every result is rounded to float32 once.  Inputs, device, only read: the soup
+ * verts fp64 [nv,3] and tris [nt,3] (a file: its positions widened, tris = 0, 1, 2, ...), face int32 [H W] and bary float32 [H W,3] of _emit, uv float32
+ * [nt,3,2] per stored corner (the file's TEXCOORD_0), image uint8 [tex_h,tex_w,4] (4-byte aligned; a side <= 16384, tex_h tex_w < 2^31), and all three or
+ * none of normal_image uint8 [tex_h,tex_w,4], normals float32 [3 nt,3], tangents float32 [3 nt,4] (the file's NORMAL / TANGENT; the frame of triangle t is
+ * read at corner 3t).  The camera as for the other raster entries; ambient in [0, 1].  Per pixel whose face is in [0, nt) and has its three indices in
+ * [0, nv) (any other pixel is a miss: kind 0, everything 0):
+ *   uv        u = (b0 u0 + b1 u1) + b2 u2, v likewise, bary widened.  u or v not finite: rgb 0, lit 0, nrm the flat normal (N of corner 3t with a normal
+ *             map), counted (bad_uv); the pixel is still a hit.
+ *   fetch     mesh_io.sample_texture: x = u Wt - 0.5, y = v Ht - 0.5, x0 = floor(x), fx = x - x0, y0 and fy likewise; taps (0,0), (1,0), (0,1), (1,1) at
+ *             column clamp(x0 + dx, 0, Wt - 1), row clamp(y0 + dy, 0, Ht - 1): the sum and the clamp are done in floating point, the conversion to an
+ *             integer comes last, so that no uv overflows an index; weights (1 - fx)(1 - fy), fx (1 - fy), (1 - fx) fy, fx fy; value = ((w00 c00 + w10
+ *             c10) + w01 c01) + w11 c11 per channel on the bytes widened.  Albedo rgb = float32(value / 255.0), channels 0 - 2.
+ *   normal    without a normal map: the unnormalised flat (P1 - P0) x (P2 - P0) of the fp64 vertices, as _shade gives it.  With one: s = the same fetch of
+ *             the normal image, (x, y, z) = s / 255.0 * 2.0 - 1.0; N, T, w of corner 3t promoted; B = w (N x T); m = (x T + y B) + z N; l = sqrt(m . m);
+ *             nrm = float32(m / l).  A triangle with mesh_texture_frames' degenerate mark (TANGENT.y is a negative zero), or an l that is zero or not
+ *             finite: nrm = N, counted (flat_frame).
+ *   lit       d_k = (R_k0 vx + R_k1 vy) + R_k2 with v as in the depth, divided by sqrt(d . d): the pixel's ray in the mesh's frame; n = nrm widened,
+ *             divided by sqrt(n . n), or 0 if that length is zero or not finite; c = n . d; s = -c if -c > 0, else 0; lit = float32(rgb (ambient + (1 -
+ *             ambient) s)) per channel, rgb the float32 albedo widened.  c > 0 is counted (back_lit, informative).  Both vectors live in the mesh's
+ *             frame: the term does not depend on the handedness of the camera matrix, whose 3 x 3 may be a reflection (|R^T R - I| is all that is tested).
+ * Outputs, device: kind uint8 [H W], rgb, nrm, lit float32 [H W,3]; counters int64 [4], 8-byte aligned = {bad_uv, flat_frame, back_lit, reserved}, zeroed
+ * and written by this call, read by the caller with its own copy.  Refused: bad sizes, an atlas over 16384 on a side or with tex_h tex_w >= 2^31, a normal
+ * image without frames or frames without one, ambient outside [0, 1] or not finite, the camera refusals of the other entries.  One lane per pixel, four
+ * (eight) 4-byte texel loads, no LDS, one ballot and at most one atomic per counter and wave; no host synchronisation.
+ * Limits: one bilinear sample per pixel, no mip maps, CLAMP_TO_EDGE only, a Lambert headlight and nothing else. */
+int o2345_mesh_raster_shade_textured(const double* verts, const void* tris, int index_bytes, long long nv, long long nt, const int* face, const float* bary,
+                                     const float* uv, const uint8_t* image, int tex_h, int tex_w, const uint8_t* normal_image_or_null,
+                                     const float* normals_or_null, const float* tangents_or_null, float fx, float fy, float cx, float cy, float m00, float m01,
+                                     float m02, float m03, float m10, float m11, float m12, float m13, float m20, float m21, float m22, float m23, int H, int W,
+                                     float ambient, uint8_t* kind, float* rgb, float* nrm, float* lit, long long* counters, void* stream);
 /* Load every code object of the library on the current device now (the HIP runtime loads a translation unit's kernels at its first launch: 5 - 60 ms
  * each for the units of this library, which otherwise land inside the first calls of a fresh process).  Launches nothing that touches user memory. */
 int o2345_preload(void);

@@ -453,6 +453,22 @@ def mesh_preview_views(n=None):
     return int(n)
 
 
+# O2345_TEXTURED_PREVIEW_VIEWS=n makes pipeline.reconstruct_folder render the TEXTURED asset as a viewer shows it (the atlas sampled bilinearly, the normal
+# map through the file's tangent frames, a headlight; csrc/mesh_raster.hip: k_rs_shade_tex) from the same cameras and write textured_000.png ... and
+# textured_lit_000.png ... next to the PLY ("" or "0" = off, the default: nothing is launched, the result gains no key and every file keeps its bytes).  It
+# needs a texture atlas (texture_texel) and an asset output format.
+TEXTURED_PREVIEW_VIEWS = _non_negative_int("O2345_TEXTURED_PREVIEW_VIEWS", os.environ.get("O2345_TEXTURED_PREVIEW_VIEWS", ""))
+
+
+def textured_preview_views(n=None):
+    """None -> the configured default; anything else must be a non-negative integer (an explicit 0 is off whatever the default)."""
+    if n is None:
+        return TEXTURED_PREVIEW_VIEWS
+    if isinstance(n, bool) or int(n) != n or n < 0:
+        raise ValueError(f"textured_preview_views must be a non-negative integer, got {n!r}")
+    return int(n)
+
+
 def preview_views(n=None):
     """None -> the configured default; anything else must be a non-negative integer (an explicit 0 is off whatever the default)."""
     if n is None:

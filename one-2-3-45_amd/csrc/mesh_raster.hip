@@ -12,10 +12,14 @@
 //   k_rs_tiles   one wave per tile, one lane per pixel (the arrangement of surface_trace.hip).  The list is staged through LDS 64 faces at a time, one
 //                face per lane; then every lane walks the batch and keeps its own (z, face) minimum in registers.  No atomics on pixels.
 //   k_rs_shade   one thread per pixel: colour and normal from face + bary.
+//   k_rs_shade_tex  one thread per pixel: the textured asset's shading from face + bary (mesh_raster_tex_math.h): albedo from the atlas, the normal from
+//                the normal map through the file's tangent frame, a headlight-lit colour.  Four (with the map eight) 4-byte texel loads per pixel straight
+//                from memory, nothing staged in LDS; one ballot per counter and wave.
 // No kernel waits for another workgroup.  Bad input never faults: an index outside [0, nv) is counted and never dereferenced; list entries, list bounds and
 // face ids are clamped to the sizes the caller states.
 #include "mesh_common.h"
 #include "mesh_raster_math.h"
+#include "mesh_raster_tex_math.h"
 
 namespace o2345 {
 
@@ -179,6 +183,69 @@ __global__ __launch_bounds__(256) void k_rs_shade(const double* __restrict__ ver
     for (int d = 0; d < 3; ++d) { rgb[3 * p + d] = c[d]; nrm[3 * p + d] = m[d]; }
 }
 
+// the textured asset's shading; counters: bad_uv, flat_frame, back_lit (zeroed by the entry)
+template <typename IDX>
+__global__ __launch_bounds__(256) void k_rs_shade_tex(const double* __restrict__ verts, int nv, const IDX* __restrict__ tris, long long nt,
+                                                      const int* __restrict__ face, const float* __restrict__ bary, long long n, const float* __restrict__ uv,
+                                                      const uint8_t* __restrict__ image, const uint8_t* __restrict__ nimage, int Ht, int Wt,
+                                                      const float* __restrict__ normals, const float* __restrict__ tangents, RsCamera cam, double ambient,
+                                                      unsigned char* __restrict__ kind, float* __restrict__ rgb, float* __restrict__ nrm, float* __restrict__ lit,
+                                                      unsigned long long* __restrict__ counters) {
+    const long long p = (long long)blockIdx.x * 256 + threadIdx.x;
+    bool bad_uv = false, flat_frame = false, back_lit = false;
+    if (p < n) {
+        const int t = face[p];
+        int idx[3];
+        float c[3] = {0.f, 0.f, 0.f}, m[3] = {0.f, 0.f, 0.f}, l[3] = {0.f, 0.f, 0.f};
+        const bool hit = t >= 0 && t < nt && mesh_triangle(tris, (long long)t, nv, idx[0], idx[1], idx[2]);
+        if (hit) {
+            const double b[3] = {(double)bary[3 * p], (double)bary[3 * p + 1], (double)bary[3 * p + 2]};
+            double u, v;
+            const bool good = rt_uv(b, uv + 6 * (long long)t, u, v);
+            bad_uv = !good;
+            RtTaps taps;
+            if (good) {
+                double value[3];
+                rt_taps(u, v, Ht, Wt, taps);
+                rt_fetch(image, Wt, taps, value);
+#pragma unroll
+                for (int d = 0; d < 3; ++d) c[d] = rt_albedo(value[d]);
+            }
+            if (nimage) {
+                const float* N = normals + 9 * (long long)t;
+                if (good) {
+                    double s[3];
+                    rt_fetch(nimage, Wt, taps, s);
+                    flat_frame = !rt_normal(s, N, tangents + 12 * (long long)t, m);
+                } else {
+#pragma unroll
+                    for (int d = 0; d < 3; ++d) m[d] = N[d];
+                }
+            } else {
+                double P[3][3], g[3];
+#pragma unroll
+                for (int k = 0; k < 3; ++k)
+#pragma unroll
+                    for (int d = 0; d < 3; ++d) P[k][d] = verts[3 * (long long)idx[k] + d];
+                rs_flat_normal(P, g);
+#pragma unroll
+                for (int d = 0; d < 3; ++d) m[d] = (float)g[d];
+            }
+            if (good) {
+                const double factor = rt_shade(cam, (int)(p % cam.W), (int)(p / cam.W), m, ambient, back_lit);
+#pragma unroll
+                for (int d = 0; d < 3; ++d) l[d] = rt_lit(c[d], factor);
+            }
+        }
+        kind[p] = hit ? 1 : 0;
+#pragma unroll
+        for (int d = 0; d < 3; ++d) { rgb[3 * p + d] = c[d]; nrm[3 * p + d] = m[d]; lit[3 * p + d] = l[d]; }
+    }
+    wave_count(bad_uv, counters);
+    wave_count(flat_frame, counters + 1);
+    wave_count(back_lit, counters + 2);
+}
+
 struct RsCarve {
     RsTotals* tot;
     RsFace* faces;
@@ -296,6 +363,38 @@ int o2345_mesh_raster_shade(const double* verts, const void* tris, int index_byt
                            colors_or_null, normals_or_null, kind, rgb, nrm);
     });
     return check_launch("mesh_raster_shade");
+}
+
+// The textured asset's shading from face and bary (include/o2345.h has the definition): kind, rgb (the atlas's albedo), nrm, lit and the counters.
+// No host synchronisation.
+int o2345_mesh_raster_shade_textured(const double* verts, const void* tris, int index_bytes, long long nv, long long nt, const int* face, const float* bary,
+                                     const float* uv, const uint8_t* image, int tex_h, int tex_w, const uint8_t* normal_image_or_null,
+                                     const float* normals_or_null, const float* tangents_or_null, float fx, float fy, float cx, float cy, float m00, float m01,
+                                     float m02, float m03, float m10, float m11, float m12, float m13, float m20, float m21, float m22, float m23, int H, int W,
+                                     float ambient, uint8_t* kind, float* rgb, float* nrm, float* lit, long long* counters, void* stream) {
+    O2345_REQUIRE_INDEX_BYTES("mesh_raster_shade_textured", index_bytes);
+    O2345_REQUIRE(mesh_sizes_ok(nv, nt), "mesh_raster_shade_textured: bad sizes (nv must stay below 2^30 and 3 * nt below 2^31)");
+    RsCamera cam;
+    const float K[4] = {fx, fy, cx, cy}, M[12] = {m00, m01, m02, m03, m10, m11, m12, m13, m20, m21, m22, m23};
+    if (!rs_entry_camera("mesh_raster_shade_textured", K, M, H, W, 1.0, 0, 0, cam)) return -1;
+    O2345_REQUIRE(tex_h >= 1 && tex_w >= 1 && tex_h <= RT_MAX_SIDE && tex_w <= RT_MAX_SIDE && (long long)tex_h * tex_w < (1ll << 31),
+                  "mesh_raster_shade_textured: bad atlas size %d x %d (a side is limited to %d)", tex_w, tex_h, RT_MAX_SIDE);
+    O2345_REQUIRE(!normal_image_or_null == !normals_or_null && !normals_or_null == !tangents_or_null,
+                  "mesh_raster_shade_textured: a normal map is the normal image, the normals and the tangents together");
+    O2345_REQUIRE(ambient >= 0.f && ambient <= 1.f, "mesh_raster_shade_textured: ambient must be in [0, 1], got %g", (double)ambient);
+    O2345_REQUIRE(face && bary && image && kind && rgb && nrm && lit && counters && (nt == 0 || (tris && uv)) && (nv == 0 || verts),
+                  "mesh_raster_shade_textured: null pointer");
+    O2345_REQUIRE(((uintptr_t)counters & 7) == 0 && ((uintptr_t)image & 3) == 0 && ((uintptr_t)normal_image_or_null & 3) == 0,
+                  "mesh_raster_shade_textured: counters must be 8-byte aligned and the images 4-byte aligned");
+    const long long n = (long long)H * W;
+    hipStream_t s = (hipStream_t)stream;
+    O2345_HIP(hipMemsetAsync(counters, 0, 4 * sizeof(long long), s));
+    with_index_type(index_bytes, tris, [&](auto* t) {
+        hipLaunchKernelGGL(k_rs_shade_tex<index_type<decltype(t)>>, dim3(cdiv(n, 256)), dim3(256), 0, s, verts, (int)nv, t, nt, face, bary, n, uv, image,
+                           normal_image_or_null, tex_h, tex_w, normals_or_null, tangents_or_null, cam, (double)ambient, kind, rgb, nrm, lit,
+                           (unsigned long long*)counters);
+    });
+    return check_launch("mesh_raster_shade_textured");
 }
 
 }  // extern "C"

@@ -1508,6 +1508,42 @@ def convert_mesh(ply_path, out_path, min_component_faces=0, keep_largest=False, 
     return out_path
 
 
+def textured_asset_buffers(verts_idx, tris, grid_R, bound_min=(-1.0, -1.0, -1.0), bound_max=(1.0, 1.0, 1.0), scale_mat=None, trans_mat=None, normals=None,
+                           texture=None):
+    """The device buffers of export_asset's textured branch, without a file (arguments as for export_asset; ``texture`` is required, the mesh not empty):
+    the same ops calls in the same order -> dict(pos float32 [3M,3] in the asset frame, uv float32 [3M,2], image uint8 [H,W,4], idx, bounds[, nrm]; with
+    ``texture["grad"]`` nrm float32 [3M,3] (the flat normals), tan float32 [3M,4], nimage uint8 [H,W,4] and counters), all on the device.  What
+    ops.mesh_raster_textured / pipeline.render_textured_mesh render; nothing synchronises."""
+    from . import ops
+    if texture is None or not int(verts_idx.shape[0]) or not int(tris.shape[0]):
+        raise ValueError("textured_asset_buffers: a texture dict and a mesh with triangles are needed")
+    m = int(tris.shape[0])
+    image = ops.mesh_texture_pack(texture["rgb"], m, texture["texel"])
+    tgrad = texture.get("grad")
+    pos, uv, nrm, idx, bounds = ops.mesh_texture_corners(verts_idx, tris, texture["texel"], grid_R, bound_min, bound_max, scale_mat, trans_mat,
+                                                         None if tgrad is not None else normals)
+    tan = nimage = counters = None
+    if tgrad is not None:                                              # the frames of the file's own buffers; NORMAL is the flat normal beside TANGENT
+        nrm, tan, counters = ops.mesh_texture_frames(pos, uv)
+        nimage = ops.mesh_texture_normal_pack(tgrad, nrm, tan, m, texture["texel"], rotation=trans_mat, counters=counters)
+    out = dict(pos=pos, uv=uv, image=image, nrm=nrm, tan=tan, nimage=nimage, idx=idx, bounds=bounds, counters=counters)
+    return {k: t for k, t in out.items() if t is not None}
+
+
+def read_textured_glb(path):
+    """A textured ``.glb`` written by this package -> the host arrays of textured_asset_buffers: dict(pos, uv, image[, nrm, tan, nimage]).  Refused
+    (ValueError): a file without a texture, or one whose index buffer is not 0, 1, 2, ... (the textured export is unwelded)."""
+    pos, faces, _, normals, texture, normal_map = _read_glb(path)
+    if texture is None:
+        raise ValueError(f"{path}: the file has no texture (export it with texture_texel)")
+    if pos.shape[0] != 3 * faces.shape[0] or not np.array_equal(faces.reshape(-1), np.arange(pos.shape[0])):
+        raise ValueError(f"{path}: a textured asset of this package has 3 M unwelded vertices and the indices 0, 1, 2, ...")
+    out = dict(pos=np.ascontiguousarray(pos, np.float32), uv=np.ascontiguousarray(texture[0], np.float32), image=np.ascontiguousarray(texture[1]))
+    if normal_map is not None:
+        out.update(nrm=np.ascontiguousarray(normals, np.float32), tan=np.ascontiguousarray(normal_map[0], np.float32), nimage=np.ascontiguousarray(normal_map[1]))
+    return out
+
+
 def export_asset(path, verts_idx, tris, grid_R, bound_min=(-1.0, -1.0, -1.0), bound_max=(1.0, 1.0, 1.0), scale_mat=None, trans_mat=None,
                  vertex_colors=None, normals=None, texture=None, png_level=None):
     """Device path by extension: ``.ply`` -> export_mesh (reconstruction frame, unchanged); ``.glb`` / ``.obj`` -> asset frame.  Arguments as for export_mesh;
@@ -1530,14 +1566,9 @@ def export_asset(path, verts_idx, tris, grid_R, bound_min=(-1.0, -1.0, -1.0), bo
     if texture is not None and n and m:
         from . import config
         level = config.mesh_texture_png_level(png_level)
-        image = ops.mesh_texture_pack(texture["rgb"], m, texture["texel"])
-        tgrad = texture.get("grad")
-        pos, uv, nrm, idx, bounds = ops.mesh_texture_corners(verts_idx, tris, texture["texel"], grid_R, bound_min, bound_max, scale_mat, trans_mat,
-                                                             None if tgrad is not None else normals)
-        tan = nimage = counters = None
-        if tgrad is not None:                                          # the frames of the file's own buffers; NORMAL is the flat normal beside TANGENT
-            nrm, tan, counters = ops.mesh_texture_frames(pos, uv)
-            nimage = ops.mesh_texture_normal_pack(tgrad, nrm, tan, m, texture["texel"], rotation=trans_mat, counters=counters)
+        b = textured_asset_buffers(verts_idx, tris, grid_R, bound_min, bound_max, scale_mat, trans_mat, normals, texture)
+        image, pos, uv, nrm, idx, bounds = b["image"], b["pos"], b["uv"], b.get("nrm"), b["idx"], b["bounds"]
+        tan, nimage, counters = b.get("tan"), b.get("nimage"), b.get("counters")
         text = ops.obj_texture_text(pos, uv, nrm, bounds=bounds) if ext == ".obj" else None
         dev = dict(image=image, text=text)
         if ext == ".glb":

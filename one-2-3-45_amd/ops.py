@@ -1712,3 +1712,71 @@ def mesh_raster(verts, tris, K, c2w, H, W, near=1e-3, cull=0, ray_depth=False, v
     nrm = torch.empty(H * W, 3, dtype=torch.float32, device=dev)
     call("o2345_mesh_raster_shade", verts, tris, ib, nv, nt, face, bary, H, W, vertex_colors, vertex_normals, kind, rgb, nrm)
     return dict(face=face, depth=depth, bary=bary, kind=kind, rgb=rgb, nrm=nrm, info=raster_info(counts.tolist()))
+
+
+def texture_raster_info(counters):
+    """The counters of o2345_mesh_raster_shade_textured, on the host (int64 [4]) -> {"bad_uv", "flat_frame", "back_lit"}; none is an error."""
+    from . import raster
+    c = np.asarray(counters).reshape(-1)
+    if c.shape[0] != len(raster.TEX_COUNTS):
+        raise ValueError(f"texture_raster_info: expected {len(raster.TEX_COUNTS)} counters, got {c.shape[0]}")
+    return {k: int(v) for k, v in zip(raster.TEX_COUNTS[:3], c)}
+
+
+@_on_device
+def mesh_raster_textured(positions, uv, image, K, c2w, H, W, near=1e-3, cull=0, ray_depth=False, normals=None, tangents=None, normal_image=None, ambient=0.25):
+    """Rasterize a textured asset on the device (== raster.rasterize_textured, its host twin and the definition, to the last bit): positions float32
+    [3M,3] in the asset's frame (widened to fp64 once; the triangles are 0, 1, 2, ...), uv float32 [3M,2], image uint8 [Ht,Wt,4], and with the normal map
+    normals float32 [3M,3], tangents float32 [3M,4] and normal_image uint8 [Ht,Wt,4] -- the buffers of mesh_io.textured_asset_buffers or of a ``.glb``, all on
+    the device and only read; K and c2w (asset_camera's, or any camera in the asset's frame) on the host -> mesh_raster's dict with rgb = the atlas's
+    albedo and nrm = the shading normal, plus lit float32 [H W,3] and tex_info (raster.TEX_COUNTS by name).  ``cull`` 1 drops what is seen from behind
+    whatever the camera's handedness.  Runs count, emit and the textured shade; mesh_raster's synchronisations, and one more copy for the counters."""
+    from . import raster
+    cull = raster.mirrored_cull(cull, host_f32(c2w))
+    cam, near, cull = _raster_camera(K, c2w, near, cull, "mesh_raster_textured")
+    H, W = raster._image_size(H, W)
+    ambient = raster._ambient(ambient)
+    dev = positions.device
+    m = _corner_buffers(positions, uv, "mesh_raster_textured")
+    if positions.dtype != torch.float32 or uv.dtype != torch.float32:
+        raise ValueError(f"mesh_raster_textured: positions and uv are float32, got {positions.dtype} and {uv.dtype}")
+
+    def atlas(a, what):
+        if a.dtype != torch.uint8 or a.dim() != 3 or a.shape[2] != 4 or a.shape[0] < 1 or a.shape[1] < 1 or a.device != dev:
+            raise ValueError(f"mesh_raster_textured: {what} is uint8 [Ht,Wt,4] on {dev}, got {a.dtype} {tuple(a.shape)} on {a.device}")
+        if max(a.shape[:2]) > raster.TEX_MAX_SIDE:
+            raise ValueError(f"mesh_raster_textured: {what} of {a.shape[1]} x {a.shape[0]}: a side is limited to {raster.TEX_MAX_SIDE}")
+        return a.contiguous()
+    image = atlas(image, "the atlas")
+    mapped = normal_image is not None
+    if (normals is None) != (tangents is None) or (normals is None) == mapped:
+        raise ValueError("mesh_raster_textured: a normal map is normals, tangents and a normal image together")
+    if mapped:
+        normal_image = atlas(normal_image, "the normal image")
+        if normal_image.shape != image.shape:
+            raise ValueError(f"mesh_raster_textured: the normal image has the atlas's size {tuple(image.shape[:2])}, got {tuple(normal_image.shape[:2])}")
+        if normals.dtype != torch.float32 or tuple(normals.shape) != (3 * m, 3) or tangents.dtype != torch.float32 or tuple(tangents.shape) != (3 * m, 4):
+            raise ValueError(f"mesh_raster_textured: normals are float32 [{3 * m},3] and tangents float32 [{3 * m},4], got {tuple(normals.shape)} and {tuple(tangents.shape)}")
+    verts = positions.contiguous().to(torch.float64)
+    tris = torch.arange(3 * m, dtype=torch.int32, device=dev).view(m, 3)
+    nv, nt, ib = 3 * m, m, 4
+    ws, wsb = _scratch("o2345_mesh_raster_workspace_bytes", (nv, nt, H, W), dev, "mesh_raster")
+    if not wsb:
+        raise ValueError(f"mesh_raster_textured: bad sizes ({nv} vertices, {nt} triangles; the tables are int32)")
+    counts = torch.empty(len(raster.COUNTS), dtype=torch.int64, device=dev)
+    call("o2345_mesh_raster_count", verts, tris, ib, nv, nt, *cam, H, W, near, cull, ws, wsb, counts)
+    n_pairs = raster_info(counts.tolist())["pairs"]
+    if n_pairs >= 2 ** 31:
+        raise ValueError(f"mesh_raster_textured: {n_pairs} (tile, face) pairs; the tile lists hold fewer than 2^31")
+    lists = _workspace(4 * max(n_pairs, 1), dev, "mesh_raster_lists").view(torch.int32) if n_pairs else None
+    face = torch.empty(H, W, dtype=torch.int32, device=dev)
+    depth = torch.empty(H, W, dtype=torch.float32, device=dev)
+    bary = torch.empty(H, W, 3, dtype=torch.float32, device=dev)
+    call("o2345_mesh_raster_emit", nv, nt, *cam, H, W, near, cull, int(bool(ray_depth)), ws, wsb, n_pairs, lists, face, depth, bary, counts)
+    kind = torch.empty(H * W, dtype=torch.uint8, device=dev)
+    rgb, nrm, lit = (torch.empty(H * W, 3, dtype=torch.float32, device=dev) for _ in range(3))
+    counters = torch.empty(len(raster.TEX_COUNTS), dtype=torch.int64, device=dev)
+    call("o2345_mesh_raster_shade_textured", verts, tris, ib, nv, nt, face, bary, uv.contiguous(), image, image.shape[0], image.shape[1], normal_image,
+         normals, tangents, *cam, H, W, ambient, kind, rgb, nrm, lit, counters)
+    return dict(face=face, depth=depth, bary=bary, kind=kind, rgb=rgb, nrm=nrm, lit=lit, info=raster_info(counts.tolist()),
+                tex_info=texture_raster_info(counters.tolist()))

@@ -474,6 +474,84 @@ def render_mesh_turntable(mesh, intrinsic, H, W, n_views, elevation_deg=20.0, ra
     return [_mesh_view(*prepared, intrinsic, c, int(H), int(W), near, cull, ray_depth, background) for c in c2ws], c2ws
 
 
+_TEXTURED_KEYS = ("pos", "uv", "image", "nrm", "tan", "nimage")
+
+
+def _textured_asset(asset):
+    """render_textured_mesh's ``asset`` -> the buffers ops.mesh_raster_textured takes, contiguous on one device: a ``.glb`` path is read
+    (mesh_io.read_textured_glb), host arrays are uploaded; NORMAL is used only beside TANGENT and the normal image"""
+    from . import mesh_io
+    if isinstance(asset, (str, bytes)) or hasattr(asset, "__fspath__"):
+        asset = mesh_io.read_textured_glb(asset)
+    missing = [k for k in _TEXTURED_KEYS[:3] if k not in asset]
+    if missing:
+        raise ValueError(f"render_textured_mesh: the asset lacks {missing}")
+    mapped = "tan" in asset or "nimage" in asset
+    if mapped and not all(k in asset for k in _TEXTURED_KEYS):
+        raise ValueError("render_textured_mesh: a normal map is nrm, tan and nimage together")
+    a = {k: asset[k] for k in (_TEXTURED_KEYS if mapped else _TEXTURED_KEYS[:3])}
+    tensors = [x for x in a.values() if torch.is_tensor(x) and x.is_cuda]
+    dev = tensors[0].device if tensors else torch.device("cuda", torch.cuda.current_device())
+    return {k: (x if torch.is_tensor(x) else torch.from_numpy(np.array(x, order="C"))).to(dev).contiguous() for k, x in a.items()}    # a copy: the array may be read-only
+
+
+def _textured_view(a, intrinsic, c2w, H, W, near, cull, ray_depth, ambient, background):
+    """one image of render_textured_mesh from the prepared buffers"""
+    r = ops.mesh_raster_textured(a["pos"], a["uv"], a["image"], intrinsic, c2w, H, W, near=near, cull=cull, ray_depth=ray_depth, normals=a.get("nrm"),
+                                 tangents=a.get("tan"), normal_image=a.get("nimage"), ambient=ambient)
+    color, normal, depth = ops.surface_pack(r["kind"], r["depth"].view(-1), r["rgb"], r["nrm"], H, W, background)
+    lit = ops.surface_pack(r["kind"], r["depth"].view(-1), r["lit"], r["nrm"], H, W, background)[0]
+    return dict(color=color, lit=lit, normal=normal, depth=depth, face=r["face"], info=r["info"], tex_info=r["tex_info"])
+
+
+@torch.no_grad()
+def render_textured_mesh(asset, intrinsic, c2w, H, W, background=(0, 0, 0, 0), near=1e-3, cull=0, ray_depth=True, ambient=0.25):
+    """The textured asset as a viewer shows it, rasterized on the device (ops.mesh_raster_textured; definitions in raster.py, limits in DESIGN.md section
+    7): the atlas sampled bilinearly, the normal map through the file's tangent frames, a headlight.  ``asset``: the dict of
+    mesh_io.textured_asset_buffers (device tensors), the same keys as host arrays, or the path of a ``.glb`` this package wrote with ``texture_texel`` --
+    all three render through the same code, in the ASSET's frame: ``c2w`` is raster.asset_camera's (which also gives the factor for ``near`` and the
+    depths), or any camera in that frame.  -> dict(color, lit, normal u8 [H,W,4], depth f32 [H,W], face int32 [H,W], info, tex_info); ``lit`` is the
+    colour under the headlight with the ``ambient`` floor, ``normal`` the shading normal (the decoded map, or the flat normal without one)."""
+    return _textured_view(_textured_asset(asset), intrinsic, c2w, int(H), int(W), near, cull, ray_depth, ambient, background)
+
+
+@torch.no_grad()
+def render_textured_turntable(asset, intrinsic, H, W, n_views, elevation_deg=20.0, radius=2.0, scale_mat=None, trans_mat=None, background=(0, 0, 0, 0),
+                              near=1e-3, cull=0, ray_depth=True, ambient=0.25, up=(0.0, 0.0, 1.0)):
+    """render_textured_mesh from render_turntable's ``n_views`` cameras of the RECONSTRUCTION frame (surface.orbit_c2w), each mapped into the asset's frame
+    by raster.asset_camera with the export's ``scale_mat`` / ``trans_mat`` (``near`` is multiplied by its scale); the buffers are read or uploaded once.
+    -> (list of render_textured_mesh results, c2w float32 [n,4,4] of the reconstruction frame)."""
+    from . import raster, surface
+    c2ws = surface.orbit_c2w(n_views, elevation_deg, radius, up)
+    a = _textured_asset(asset)
+    out = []
+    for c in c2ws:
+        M, s, _ = raster.asset_camera(c, scale_mat, trans_mat)
+        out.append(_textured_view(a, intrinsic, M, int(H), int(W), near * s, cull, ray_depth, ambient, background))
+    return out, c2ws
+
+
+def _write_textured_previews(buffers, s, n, folder):
+    """n views of a folder's textured asset (the device buffers of its export) as ``textured_XXX.png`` and ``textured_lit_XXX.png`` in ``folder``, from
+    _write_previews' cameras mapped into the asset's frame"""
+    import os
+    from . import mesh_io, raster
+    K, cams, H, W = _preview_cameras(s, n)
+    a = _textured_asset(buffers)
+    out = []
+    for k, c in enumerate(cams):
+        M, scale, _ = raster.asset_camera(c, s["scale_mat"], s["trans_mat"])
+        r = _textured_view(a, K, M, H, W, 1e-3 * scale, 0, True, 0.25, (0, 0, 0, 0))
+        color, lit, normal, depth, face = ops.to_host_numpy(r["color"], r["lit"], r["normal"], r["depth"], r["face"])
+        path, lit_path = os.path.join(folder, f"textured_{k:03d}.png"), os.path.join(folder, f"textured_lit_{k:03d}.png")
+        for p, image in ((path, color), (lit_path, lit)):
+            with open(p, "wb") as f:
+                f.write(mesh_io.png_bytes(image, config.mesh_texture_png_level()))
+        out.append({"path": path, "lit_path": lit_path, "color": color, "lit": lit, "normal": normal, "depth": depth, "face": face,
+                    "c2w": np.array(c, np.float32), "c2w_asset": M, "info": r["info"], "tex_info": r["tex_info"]})
+    return out
+
+
 def _preview_cameras(s, n):
     """the cameras of a folder's previews -> (K [3,3], list of n c2w [4,4], H, W): the query camera, then an orbit through it"""
     from . import surface
@@ -523,7 +601,8 @@ def _write_previews(wt, vol, proj, cam_pos, u, s, n, folder):
 @torch.no_grad()
 def reconstruct_folder(root_dir, name, wt, out_ply, D=96, resolution=256, render_val_image=False, output_format=None, min_component_faces=None,
                        keep_largest=None, smooth_iterations=None, decimate_cell=None, project_iterations=None, texture_texel=None, preview_views=None, mesh_error=None,
-                       simplify_faces=None, mesh_audit=None, fill_holes=None, mesh_intersections=None, mesh_preview_views=None, normal_map=None):
+                       simplify_faces=None, mesh_audit=None, fill_holes=None, mesh_intersections=None, mesh_preview_views=None, normal_map=None,
+                       textured_preview_views=None):
     """run.py's reconstruction stage without the reference tree: Zero123-style folder (dataset.SceneFolder) -> coloured mesh (binary PLY in
     the original frame), optionally the val image of the target view.  ``output_format`` ".obj" / ".glb" (run.py --output_format) also writes
     ``mesh<ext>`` next to ``out_ply`` in the asset frame, from the same device buffers.  The mesh options are extract_mesh's.  Returns
@@ -553,7 +632,13 @@ def reconstruct_folder(root_dir, name, wt, out_ply, D=96, resolution=256, render
     "mesh_preview_mesh" the rendered mesh: {verts fp64 [N,3], tris, vertex_colors float32 [N,3] or None}, on the device.
     ``normal_map`` (None: the config default O2345_MESH_NORMAL_MAP, off: nothing is launched and every file keeps its bytes): export_mesh_asset's
     tangent-space normal map for the textured ``output_format`` asset; the result's "texture" block then has "normal_map": True.  With ``texture_texel`` off it
-    raises ValueError."""
+    raises ValueError.
+    ``textured_preview_views`` (None: the config default O2345_TEXTURED_PREVIEW_VIEWS, 0 = off: nothing is launched, the result gains no key and every file
+    keeps its bytes) = n >= 1: n views of the TEXTURED asset as a viewer shows it (render_textured_mesh on the buffers the file is written from: the atlas,
+    and with ``normal_map`` the normal map) from the cameras of ``preview_views`` mapped into the asset's frame (raster.asset_camera), written as
+    ``textured_000.png`` ... (the albedo) and ``textured_lit_000.png`` ... (under the headlight) next to the PLY.  The result's "textured_previews" is the
+    list of {path, lit_path, color, lit, normal, depth, face, c2w, c2w_asset, info, tex_info}.  It needs ``texture_texel`` and an ``output_format`` asset,
+    otherwise ValueError."""
     import os
     from . import dataset, mesh_io
     if output_format not in (None, ".ply", ".obj", ".glb"):
@@ -561,6 +646,9 @@ def reconstruct_folder(root_dir, name, wt, out_ply, D=96, resolution=256, render
     nmap = config.mesh_normal_map(normal_map)
     if nmap and not config.mesh_texture_texel(texture_texel):
         raise ValueError("normal_map: the normal map belongs to the texture atlas; set texture_texel")
+    textured_previews = config.textured_preview_views(textured_preview_views)
+    if textured_previews and not (config.mesh_texture_texel(texture_texel) and output_format in (".obj", ".glb")):
+        raise ValueError("textured_preview_views: the textured previews show the textured asset; set texture_texel and output_format '.glb' or '.obj'")
     s = dataset.SceneFolder(root_dir, "export_mesh", specific_dataset_name=name)[0]
     dev = wt.device
     T = lambda t: t.to(dev).contiguous().float()
@@ -593,6 +681,9 @@ def reconstruct_folder(root_dir, name, wt, out_ply, D=96, resolution=256, render
     if mesh_previews:
         out["mesh_preview_mesh"] = {"verts": m.verts, "tris": m.tris, "vertex_colors": rgb}
         out["mesh_previews"] = _write_mesh_previews(m.verts, m.tris, rgb, s, mesh_previews, os.path.dirname(str(out_ply)))
+    if textured_previews and m.texture is not None and m.verts_idx.shape[0]:
+        buffers = mesh_io.textured_asset_buffers(m.verts_idx, m.tris, resolution, scale_mat=s["scale_mat"], trans_mat=s["trans_mat"], texture=m.texture)
+        out["textured_previews"] = _write_textured_previews(buffers, s, textured_previews, os.path.dirname(str(out_ply)))
     if previews:
         out["previews"] = _write_previews(wt, vol, proj, cam_pos, m.u, s, previews, os.path.dirname(str(out_ply)))
     if render_val_image:

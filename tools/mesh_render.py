@@ -1,6 +1,7 @@
 """Renders a mesh file to PNG images with the rasterizer (csrc/mesh_raster.hip; host twin one-2-3-45_amd/raster.py).
 
     python tools/mesh_render.py MESH OUT.png [--views n] [--size HxW] [--elevation deg] [--cull 0|1|2] [--normals] [--host] [--json]
+    python tools/mesh_render.py MESH.glb OUT.png --textured [--lit] [--ambient a] [--views n] [--size HxW] [--cull 0|1|2] [--normals] [--host] [--json]
     python tools/mesh_render.py --time [--reps 9] [--warmup 3] [--volume 128] [--grid 256]
 
 MESH is a ``.ply``, ``.glb`` or ``.obj`` as this package writes them (mesh_io's parsers); its vertex colours are used when it has them, else a grey.  The
@@ -8,6 +9,11 @@ cameras are an orbit (surface.orbit_c2w) around the centre of the mesh's boundin
 fills the image.  One view is written to OUT.png, n views to OUT_000.png ...; ``--normals`` writes the normal image instead of the colour image.  ``--json``
 prints one JSON line with the counts of every view.  Runs on the GPU (pipeline.render_mesh); ``--host`` uses the numpy twin (raster.render), which needs no
 GPU and gives the same bytes.
+
+``--textured`` renders a ``.glb`` written with ``texture_texel`` the way a viewer shows it (pipeline.render_textured_mesh; ``--host``: raster.render_textured):
+the atlas sampled bilinearly instead of vertex colours, with ``--normals`` the shading normal (the normal map through the file's tangent frames when the file
+has one), with ``--lit`` the colour under a headlight with the ``--ambient`` floor (0.25).  The cameras are the same orbit, in the file's own frame; ``--cull 1``
+drops what is seen from behind.  ``--json`` also prints the textured stage's counts.  Without the flag the tool does what it did before.
 
 ``--time`` takes no file: on BASELINE config 2's raw mesh at a 256^3 lattice and on the same mesh simplified to 5,000 faces, at 256^2 and 512^2 pixels from
 the scene's query camera, it times with HIP events (median of --reps calls after --warmup) the three entries of one image -- o2345_mesh_raster_count (the
@@ -109,6 +115,39 @@ def fit_cameras(v, n, H, W, elevation):
     return np.array([[focal, 0, (W - 1) / 2.0], [0, focal, (H - 1) / 2.0], [0, 0, 1]], np.float32), c2w, half
 
 
+def textured(a, H, W, mesh_io):
+    """--textured: the views of a textured .glb"""
+    if mesh_io._asset_ext(a.mesh) != ".glb":
+        raise SystemExit("--textured takes a .glb written with texture_texel (the GLB is the defined form of the textured asset)")
+    asset = mesh_io.read_textured_glb(a.mesh)
+    K, c2ws, half = fit_cameras(asset["pos"].astype(np.float64), a.views, H, W, a.elevation)
+    kw = dict(near=1e-3 * half, cull=a.cull, ambient=a.ambient)
+    which = "normal" if a.normals else "lit" if a.lit else "color"
+    stem, suffix = os.path.splitext(a.out)
+    report = []
+    if not a.host:
+        pipeline = importlib.import_module("one-2-3-45_amd.pipeline")
+        asset = pipeline._textured_asset(asset)                                 # uploaded once
+    for k, c2w in enumerate(c2ws):
+        if a.host:
+            r = importlib.import_module("one-2-3-45_amd.raster").render_textured(
+                asset["pos"], asset["uv"], asset["image"], K, c2w, H, W, normals=asset.get("nrm"), tangents=asset.get("tan"), normal_image=asset.get("nimage"), **kw)
+            image = r[which]
+        else:
+            r = pipeline.render_textured_mesh(asset, K, c2w, H, W, ray_depth=False, **kw)
+            image = r[which].cpu().numpy()
+        path = a.out if a.views == 1 else f"{stem}_{k:03d}{suffix or '.png'}"
+        with open(path, "wb") as fh:
+            fh.write(mesh_io.png_bytes(image))
+        report.append({"path": path, **r["info"], **r["tex_info"]})
+    if a.json:
+        print(json.dumps(report))
+    else:
+        for row in report:
+            print(row["path"], " ".join(f"{k}={row[k]}" for k in row if k != "path"))
+    return report
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("mesh", nargs="?")
@@ -119,6 +158,9 @@ def main(argv=None):
     ap.add_argument("--cull", type=int, default=0)
     ap.add_argument("--normals", action="store_true")
     ap.add_argument("--host", action="store_true")
+    ap.add_argument("--textured", action="store_true")
+    ap.add_argument("--lit", action="store_true")
+    ap.add_argument("--ambient", type=float, default=0.25)
     ap.add_argument("--json", action="store_true")
     ap.add_argument("--time", action="store_true")
     ap.add_argument("--reps", type=int, default=9)
@@ -137,6 +179,10 @@ def main(argv=None):
     if a.views < 1 or H < 1 or W < 1:
         ap.error("--views and both sides of --size must be at least 1")
     mesh_io = importlib.import_module("one-2-3-45_amd.mesh_io")
+    if a.lit and not a.textured:
+        ap.error("--lit belongs to --textured")
+    if a.textured:
+        return textured(a, H, W, mesh_io)
     ext = mesh_io._asset_ext(a.mesh)
     parsed = {".ply": mesh_io.read_ply, ".glb": mesh_io.read_glb, ".obj": mesh_io.read_obj}[ext](a.mesh)
     v, f, colours = np.ascontiguousarray(parsed[0], np.float64), np.ascontiguousarray(parsed[1]), parsed[2]
