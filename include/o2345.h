@@ -70,6 +70,8 @@ const char* o2345_last_error(void);
  * o2345_mesh_fill_emit; the self-intersection entries o2345_mesh_intersect_workspace_bytes, o2345_mesh_intersect_count, o2345_mesh_intersect_emit; the
  * rasterizer entries o2345_mesh_raster_workspace_bytes, o2345_mesh_raster_count, o2345_mesh_raster_emit, o2345_mesh_raster_shade; the textured
  * shading entry o2345_mesh_raster_shade_textured. */
+/* 231 = ABI 2.3.1: o2345_mesh_raster_count, o2345_mesh_raster_emit and o2345_mesh_raster_shade_textured take the camera as o2345_camera_rays does, K_host [9]
+ * and c2w_host [12], in place of sixteen float scalars at the same position; nothing else changed. */
 int o2345_version(void);
 /* Layout self-description of the declared structs as THIS library was compiled (sizeof, and offsetof of every field in declaration order): a binding
  * asserts its own structs against it at load time (one-2-3-45_amd/_lib.py does) -- a field added on one side only cannot corrupt calls silently.
@@ -871,9 +873,10 @@ int o2345_mesh_intersect_emit(const double* verts, const void* tris, int index_b
  * Equal to the host twin one-2-3-45_amd/raster.py to the last bit.  All real arithmetic is fp64, one operation at a time, in the order written
  * (csrc/mesh_raster_math.h is the text); coverage is decided in integers.  verts device fp64 [nv,3] in the world frame, tris device int32 / int64 [nt,3]
  * (index_bytes 4 / 8), both only read; 0 <= nv < 2^30, 3 * nt < 2^31; nt = 0 is legal and gives an empty image.
- *   camera     surface.camera_rays' one, K = [[fx, 0, cx], [0, fy, cy], [0, 0, 1]] and c2w [12], passed as float32 scalars (fx, fy, cx, cy; m00 .. m23: the
- *              3 x 4 of c2w, row-major) and widened to fp64; here fx, fy > 0 and the 3 x 3 of c2w is a rotation (|R^T R - I| <= 1e-5 in every entry).  x right, y down, z forward; the sample of pixel
- *              (px, py) is the integer point (px, py), without a half-pixel offset.  H, W >= 1, H W < 2^31; near finite and > 0.
+ *   camera     o2345_camera_rays' one, passed the same way: K_host float32 [9] = [[fx, 0, cx], [0, fy, cy], [0, 0, 1]] and c2w_host float32 [12] (the 3 x 4,
+ *              row-major) on the host, widened to fp64; here fx, fy > 0 and the 3 x 3 of c2w is a rotation (|R^T R - I| <= 1e-5 in every entry).  x right,
+ *              y down, z forward; the sample of pixel (px, py) is the integer point (px, py), without a half-pixel offset.  H, W >= 1, H W < 2^31; near
+ *              finite and > 0.
  *   corners    a face's corners are renumbered for the computation: corner 0 is the stored corner with the smallest vertex index, the others follow in
  *              stored (cyclic) order, so that the result does not depend on which corner a face is stored from.  Outputs are in STORED order.
  *   screen     q = p - t; x_c = (R00 q_x + R10 q_y) + R20 q_z, y_c with column 1 of R, z_c with column 2; X = x_c / z_c * fx + cx,
@@ -912,12 +915,9 @@ enum { O2345_RASTER_BAD_INDEX = 0, O2345_RASTER_NONFINITE = 1, O2345_RASTER_NEAR
        O2345_RASTER_CULLED = 5, O2345_RASTER_OFFSCREEN = 6, O2345_RASTER_BINNED = 7, O2345_RASTER_PAIRS = 8, O2345_RASTER_PIXELS = 9,
        O2345_RASTER_COUNTS = 10 };
 size_t o2345_mesh_raster_workspace_bytes(long long nv, long long nt, int H, int W);
-int o2345_mesh_raster_count(const double* verts, const void* tris, int index_bytes, long long nv, long long nt, float fx, float fy, float cx, float cy, float m00, float m01, float m02, float m03, float m10, float m11, float m12,
-                            float m13, float m20, float m21, float m22, float m23,
-                            int H, int W, double near, int cull, void* workspace, size_t workspace_bytes, long long* counts, void* stream);
-int o2345_mesh_raster_emit(long long nv, long long nt, float fx, float fy, float cx, float cy, float m00, float m01, float m02, float m03, float m10, float m11, float m12,
-                           float m13, float m20, float m21, float m22, float m23,
-                           int H, int W, double near, int cull, int ray_depth,
+int o2345_mesh_raster_count(const double* verts, const void* tris, int index_bytes, long long nv, long long nt, const float* K_host,
+                            const float* c2w_host, int H, int W, double near, int cull, void* workspace, size_t workspace_bytes, long long* counts, void* stream);
+int o2345_mesh_raster_emit(long long nv, long long nt, const float* K_host, const float* c2w_host, int H, int W, double near, int cull, int ray_depth,
                            void* workspace, size_t workspace_bytes, long long n_pairs, int* lists, int* face, float* depth, float* bary, long long* counts,
                            void* stream);
 int o2345_mesh_raster_shade(const double* verts, const void* tris, int index_bytes, long long nv, long long nt, const int* face, const float* bary, int H, int W,
@@ -951,8 +951,7 @@ int o2345_mesh_raster_shade(const double* verts, const void* tris, int index_byt
  * Limits: one bilinear sample per pixel, no mip maps, CLAMP_TO_EDGE only, a Lambert headlight and nothing else. */
 int o2345_mesh_raster_shade_textured(const double* verts, const void* tris, int index_bytes, long long nv, long long nt, const int* face, const float* bary,
                                      const float* uv, const uint8_t* image, int tex_h, int tex_w, const uint8_t* normal_image_or_null,
-                                     const float* normals_or_null, const float* tangents_or_null, float fx, float fy, float cx, float cy, float m00, float m01,
-                                     float m02, float m03, float m10, float m11, float m12, float m13, float m20, float m21, float m22, float m23, int H, int W,
+                                     const float* normals_or_null, const float* tangents_or_null, const float* K_host, const float* c2w_host, int H, int W,
                                      float ambient, uint8_t* kind, float* rgb, float* nrm, float* lit, long long* counters, void* stream);
 /* Load every code object of the library on the current device now (the HIP runtime loads a translation unit's kernels at its first launch: 5 - 60 ms
  * each for the units of this library, which otherwise land inside the first calls of a fresh process).  Launches nothing that touches user memory. */

@@ -46,7 +46,7 @@ int preload_convnet();
 
 extern "C" {
 const char* o2345_last_error(void) { return o2345::g_err; }
-int o2345_version(void) { return 230; }     // 2.3: O2345SimplifyStats, O2345AuditStats; 2.2: declared stats structs, o2345_struct_size / _layout; 2.1: segment_rays + weight_cull in O2345RenderIO; 2.0: see include/o2345.h (1.5: o2345_list_sort_by_visibility; 1.4: color stats, bf16 entry removed; 1.3: o2345_conv2d family; 1.2: t_rand)
+int o2345_version(void) { return 231; }     // 2.3.1: the raster entries take the camera as K_host, c2w_host; 2.3: O2345SimplifyStats, O2345AuditStats; 2.2: declared stats structs, o2345_struct_size / _layout; 2.1: segment_rays + weight_cull in O2345RenderIO; 2.0: see include/o2345.h (1.5: o2345_list_sort_by_visibility; 1.4: color stats, bf16 entry removed; 1.3: o2345_conv2d family; 1.2: t_rand)
 
 int o2345_preload(void) {
     int e, bad = 0;

@@ -147,6 +147,26 @@ __global__ __launch_bounds__(64) void k_rs_tiles(const RsFace* __restrict__ face
     wave_count(hit, &tot->pixels);
 }
 
+// What both shade kernels share.  The hit test: face t is a triangle of the mesh with its three indices in [0, nv) -> idx
+template <typename IDX>
+__device__ __forceinline__ bool rs_hit(const IDX* tris, long long nt, int nv, int t, int (&idx)[3]) { return t >= 0 && t < nt && mesh_triangle(tris, (long long)t, nv, idx[0], idx[1], idx[2]); }
+// pixel p's float32 barycentrics, widened
+__device__ __forceinline__ void rs_bary(const float* bary, long long p, double (&b)[3]) { b[0] = (double)bary[3 * p]; b[1] = (double)bary[3 * p + 1]; b[2] = (double)bary[3 * p + 2]; }
+// the flat (P1 - P0) x (P2 - P0) of the fp64 vertices, rounded to float32 once
+__device__ __forceinline__ void rs_flat_normal_f32(const double* verts, const int (&idx)[3], float (&m)[3]) {
+    double P[3][3], g[3];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) P[k / 3][k % 3] = verts[3 * (long long)idx[k / 3] + k % 3];
+    rs_flat_normal(P, g);
+    m[0] = (float)g[0]; m[1] = (float)g[1]; m[2] = (float)g[2];
+}
+// pixel p's outputs; l, lit: the textured stage's fourth image, or null
+__device__ __forceinline__ void rs_store(long long p, bool hit, const float (&c)[3], const float (&m)[3], const float* l, unsigned char* kind, float* rgb, float* nrm, float* lit) {
+    kind[p] = hit ? 1 : 0;
+#pragma unroll
+    for (int d = 0; d < 3; ++d) { rgb[3 * p + d] = c[d]; nrm[3 * p + d] = m[d]; if (l) lit[3 * p + d] = l[d]; }
+}
+
 template <typename IDX>
 __global__ __launch_bounds__(256) void k_rs_shade(const double* __restrict__ verts, int nv, const IDX* __restrict__ tris, long long nt,
                                                   const int* __restrict__ face, const float* __restrict__ bary, long long n,
@@ -154,12 +174,12 @@ __global__ __launch_bounds__(256) void k_rs_shade(const double* __restrict__ ver
                                                   float* __restrict__ rgb, float* __restrict__ nrm) {
     const long long p = (long long)blockIdx.x * 256 + threadIdx.x;
     if (p >= n) return;
-    const int t = face[p];
     int idx[3];
     float c[3] = {0.f, 0.f, 0.f}, m[3] = {0.f, 0.f, 0.f};
-    const bool hit = t >= 0 && t < nt && mesh_triangle(tris, (long long)t, nv, idx[0], idx[1], idx[2]);
+    const bool hit = rs_hit(tris, nt, nv, face[p], idx);
     if (hit) {
-        const double b[3] = {(double)bary[3 * p], (double)bary[3 * p + 1], (double)bary[3 * p + 2]};
+        double b[3];
+        rs_bary(bary, p, b);
 #pragma unroll
         for (int d = 0; d < 3; ++d)
             c[d] = colors ? rs_interpolate(b, (double)colors[3 * (long long)idx[0] + d], (double)colors[3 * (long long)idx[1] + d], (double)colors[3 * (long long)idx[2] + d]) : 0.5f;
@@ -167,20 +187,9 @@ __global__ __launch_bounds__(256) void k_rs_shade(const double* __restrict__ ver
 #pragma unroll
             for (int d = 0; d < 3; ++d)
                 m[d] = rs_interpolate(b, (double)normals[3 * (long long)idx[0] + d], (double)normals[3 * (long long)idx[1] + d], (double)normals[3 * (long long)idx[2] + d]);
-        } else {
-            double P[3][3], g[3];
-#pragma unroll
-            for (int k = 0; k < 3; ++k)
-#pragma unroll
-                for (int d = 0; d < 3; ++d) P[k][d] = verts[3 * (long long)idx[k] + d];
-            rs_flat_normal(P, g);
-#pragma unroll
-            for (int d = 0; d < 3; ++d) m[d] = (float)g[d];
-        }
+        } else rs_flat_normal_f32(verts, idx, m);
     }
-    kind[p] = hit ? 1 : 0;
-#pragma unroll
-    for (int d = 0; d < 3; ++d) { rgb[3 * p + d] = c[d]; nrm[3 * p + d] = m[d]; }
+    rs_store(p, hit, c, m, nullptr, kind, rgb, nrm, nullptr);
 }
 
 // the textured asset's shading; counters: bad_uv, flat_frame, back_lit (zeroed by the entry)
@@ -197,10 +206,10 @@ __global__ __launch_bounds__(256) void k_rs_shade_tex(const double* __restrict__
         const int t = face[p];
         int idx[3];
         float c[3] = {0.f, 0.f, 0.f}, m[3] = {0.f, 0.f, 0.f}, l[3] = {0.f, 0.f, 0.f};
-        const bool hit = t >= 0 && t < nt && mesh_triangle(tris, (long long)t, nv, idx[0], idx[1], idx[2]);
+        const bool hit = rs_hit(tris, nt, nv, t, idx);
         if (hit) {
-            const double b[3] = {(double)bary[3 * p], (double)bary[3 * p + 1], (double)bary[3 * p + 2]};
-            double u, v;
+            double b[3], u, v;
+            rs_bary(bary, p, b);
             const bool good = rt_uv(b, uv + 6 * (long long)t, u, v);
             bad_uv = !good;
             RtTaps taps;
@@ -221,25 +230,14 @@ __global__ __launch_bounds__(256) void k_rs_shade_tex(const double* __restrict__
 #pragma unroll
                     for (int d = 0; d < 3; ++d) m[d] = N[d];
                 }
-            } else {
-                double P[3][3], g[3];
-#pragma unroll
-                for (int k = 0; k < 3; ++k)
-#pragma unroll
-                    for (int d = 0; d < 3; ++d) P[k][d] = verts[3 * (long long)idx[k] + d];
-                rs_flat_normal(P, g);
-#pragma unroll
-                for (int d = 0; d < 3; ++d) m[d] = (float)g[d];
-            }
+            } else rs_flat_normal_f32(verts, idx, m);
             if (good) {
                 const double factor = rt_shade(cam, (int)(p % cam.W), (int)(p / cam.W), m, ambient, back_lit);
 #pragma unroll
                 for (int d = 0; d < 3; ++d) l[d] = rt_lit(c[d], factor);
             }
         }
-        kind[p] = hit ? 1 : 0;
-#pragma unroll
-        for (int d = 0; d < 3; ++d) { rgb[3 * p + d] = c[d]; nrm[3 * p + d] = m[d]; lit[3 * p + d] = l[d]; }
+        rs_store(p, hit, c, m, l, kind, rgb, nrm, lit);
     }
     wave_count(bad_uv, counters);
     wave_count(flat_frame, counters + 1);
@@ -254,8 +252,9 @@ struct RsCarve {
     unsigned nb;
 };
 
-static bool rs_sizes_ok(long long nv, long long nt, int H, int W) { return mesh_sizes_ok(nv, nt) && H >= 1 && W >= 1 && (long long)H * W < (1ll << 31); }
-
+static bool rs_image_ok(int H, int W) { return H >= 1 && W >= 1 && (long long)H * W < (1ll << 31); }
+static bool rs_sizes_ok(long long nv, long long nt, int H, int W) { return mesh_sizes_ok(nv, nt) && rs_image_ok(H, W); }
+#define RS_REQUIRE_SIZES(unit, nv, nt) O2345_REQUIRE(mesh_sizes_ok(nv, nt), unit ": bad sizes (nv must stay below 2^30 and 3 * nt below 2^31)")
 // the one walk through the workspace: carves it, or sizes it when ws is null; returns its size
 static size_t rs_carve(void* ws, long long nv, long long nt, int H, int W, RsCarve& c) {
     (void)nv;                                                        // nothing is kept per vertex
@@ -269,12 +268,17 @@ static size_t rs_carve(void* ws, long long nv, long long nt, int H, int W, RsCar
     return w.bytes();
 }
 
-// the checked camera of an entry; false: refused (the error is set)
-static bool rs_entry_camera(const char* unit, const float (&K)[4], const float (&c2w)[12], int H, int W, double near, int cull, int ray_depth, RsCamera& cam) {
-    if (!(H >= 1 && W >= 1 && (long long)H * W < (1ll << 31))) { set_error("%s: bad image size %d x %d", unit, H, W); return false; }
+// the checked camera of an entry from K [9] and c2w [12] on the host, both row-major; false: refused (the error is set)
+static bool rs_entry_camera(const char* unit, const float* K, const float* c2w, int H, int W, double near, int cull, int ray_depth, RsCamera& cam) {
+    if (!K || !c2w) { set_error("%s: null pointer", unit); return false; }
+    if (!rs_image_ok(H, W)) { set_error("%s: bad image size %d x %d", unit, H, W); return false; }
     if (!(near > 0.0 && near <= DBL_MAX)) { set_error("%s: near must be finite and > 0, got %g", unit, near); return false; }
     if (cull < 0 || cull > 2) { set_error("%s: cull is 0 (none), 1 (back faces) or 2 (front faces), got %d", unit, cull); return false; }
-    switch (rs_camera(K, c2w, H, W, near, cull, ray_depth, cam)) {
+    if (!(K[1] == 0.f && K[3] == 0.f && K[6] == 0.f && K[7] == 0.f && K[8] == 1.f)) {
+        set_error("%s: a pinhole camera without skew is [[fx, 0, cx], [0, fy, cy], [0, 0, 1]] with fx, fy != 0", unit); return false;
+    }
+    const float k4[4] = {K[0], K[4], K[2], K[5]}, m[12] = {c2w[0], c2w[1], c2w[2], c2w[3], c2w[4], c2w[5], c2w[6], c2w[7], c2w[8], c2w[9], c2w[10], c2w[11]};
+    switch (rs_camera(k4, m, H, W, near, cull, ray_depth, cam)) {
         case 0: return true;
         case 1: set_error("%s: K and c2w must be finite", unit); return false;
         case 2: set_error("%s: fx and fy must be > 0", unit); return false;
@@ -296,14 +300,12 @@ size_t o2345_mesh_raster_workspace_bytes(long long nv, long long nt, int H, int 
 
 // Pass 1: the faces to the screen, their classes, the tile counts and the starts of the tile lists, all inside the workspace; the counts go to `counts`
 // on the DEVICE (the covered pixels are pass 2's).  No host synchronisation.
-int o2345_mesh_raster_count(const double* verts, const void* tris, int index_bytes, long long nv, long long nt, float fx, float fy, float cx, float cy, float m00, float m01, float m02, float m03, float m10, float m11, float m12,
-                            float m13, float m20, float m21, float m22, float m23,
-                            int H, int W, double near, int cull, void* workspace, size_t workspace_bytes, long long* counts, void* stream) {
+int o2345_mesh_raster_count(const double* verts, const void* tris, int index_bytes, long long nv, long long nt, const float* K_host,
+                            const float* c2w_host, int H, int W, double near, int cull, void* workspace, size_t workspace_bytes, long long* counts, void* stream) {
     O2345_REQUIRE_INDEX_BYTES("mesh_raster_count", index_bytes);
-    O2345_REQUIRE(mesh_sizes_ok(nv, nt), "mesh_raster_count: bad sizes (nv must stay below 2^30 and 3 * nt below 2^31)");
+    RS_REQUIRE_SIZES("mesh_raster_count", nv, nt);
     RsCamera cam;
-    const float K[4] = {fx, fy, cx, cy}, M[12] = {m00, m01, m02, m03, m10, m11, m12, m13, m20, m21, m22, m23};
-    if (!rs_entry_camera("mesh_raster_count", K, M, H, W, near, cull, 0, cam)) return -1;
+    if (!rs_entry_camera("mesh_raster_count", K_host, c2w_host, H, W, near, cull, 0, cam)) return -1;
     O2345_REQUIRE(counts && (nt == 0 || tris) && (nv == 0 || verts), "mesh_raster_count: null pointer");
     O2345_REQUIRE(((uintptr_t)counts & 7) == 0, "mesh_raster_count: counts must be 8-byte aligned");
     O2345_REQUIRE_WORKSPACE("mesh_raster_count", workspace, workspace_bytes, o2345_mesh_raster_workspace_bytes(nv, nt, H, W));
@@ -324,15 +326,12 @@ int o2345_mesh_raster_count(const double* verts, const void* tris, int index_byt
 
 // Pass 2: the tile lists (lists: device int32 [n_pairs], n_pairs as counted) and the image, from the workspace of pass 1 (same sizes and camera,
 // untouched in between); counts[O2345_RASTER_PIXELS] is written
-int o2345_mesh_raster_emit(long long nv, long long nt, float fx, float fy, float cx, float cy, float m00, float m01, float m02, float m03, float m10, float m11, float m12,
-                           float m13, float m20, float m21, float m22, float m23,
-                           int H, int W, double near, int cull, int ray_depth,
+int o2345_mesh_raster_emit(long long nv, long long nt, const float* K_host, const float* c2w_host, int H, int W, double near, int cull, int ray_depth,
                            void* workspace, size_t workspace_bytes, long long n_pairs, int* lists, int* face, float* depth, float* bary, long long* counts,
                            void* stream) {
-    O2345_REQUIRE(mesh_sizes_ok(nv, nt), "mesh_raster_emit: bad sizes (nv must stay below 2^30 and 3 * nt below 2^31)");
+    RS_REQUIRE_SIZES("mesh_raster_emit", nv, nt);
     RsCamera cam;
-    const float K[4] = {fx, fy, cx, cy}, M[12] = {m00, m01, m02, m03, m10, m11, m12, m13, m20, m21, m22, m23};
-    if (!rs_entry_camera("mesh_raster_emit", K, M, H, W, near, cull, ray_depth, cam)) return -1;
+    if (!rs_entry_camera("mesh_raster_emit", K_host, c2w_host, H, W, near, cull, ray_depth, cam)) return -1;
     O2345_REQUIRE(n_pairs >= 0 && n_pairs < RS_MAX_PAIRS && (nt > 0 || n_pairs == 0), "mesh_raster_emit: bad pair count %lld (the limit is 2^31 - 1)", n_pairs);
     O2345_REQUIRE(face && depth && bary && counts && (n_pairs == 0 || lists), "mesh_raster_emit: null pointer");
     O2345_REQUIRE(((uintptr_t)counts & 7) == 0, "mesh_raster_emit: counts must be 8-byte aligned");
@@ -354,8 +353,8 @@ int o2345_mesh_raster_emit(long long nv, long long nt, float fx, float fy, float
 int o2345_mesh_raster_shade(const double* verts, const void* tris, int index_bytes, long long nv, long long nt, const int* face, const float* bary, int H, int W,
                             const float* colors_or_null, const float* normals_or_null, uint8_t* kind, float* rgb, float* nrm, void* stream) {
     O2345_REQUIRE_INDEX_BYTES("mesh_raster_shade", index_bytes);
-    O2345_REQUIRE(mesh_sizes_ok(nv, nt), "mesh_raster_shade: bad sizes (nv must stay below 2^30 and 3 * nt below 2^31)");
-    O2345_REQUIRE(H >= 1 && W >= 1 && (long long)H * W < (1ll << 31), "mesh_raster_shade: bad image size %d x %d", H, W);
+    RS_REQUIRE_SIZES("mesh_raster_shade", nv, nt);
+    O2345_REQUIRE(rs_image_ok(H, W), "mesh_raster_shade: bad image size %d x %d", H, W);
     O2345_REQUIRE(face && bary && kind && rgb && nrm && (nt == 0 || tris) && (nv == 0 || verts), "mesh_raster_shade: null pointer");
     const long long n = (long long)H * W;
     with_index_type(index_bytes, tris, [&](auto* t) {
@@ -369,14 +368,12 @@ int o2345_mesh_raster_shade(const double* verts, const void* tris, int index_byt
 // No host synchronisation.
 int o2345_mesh_raster_shade_textured(const double* verts, const void* tris, int index_bytes, long long nv, long long nt, const int* face, const float* bary,
                                      const float* uv, const uint8_t* image, int tex_h, int tex_w, const uint8_t* normal_image_or_null,
-                                     const float* normals_or_null, const float* tangents_or_null, float fx, float fy, float cx, float cy, float m00, float m01,
-                                     float m02, float m03, float m10, float m11, float m12, float m13, float m20, float m21, float m22, float m23, int H, int W,
+                                     const float* normals_or_null, const float* tangents_or_null, const float* K_host, const float* c2w_host, int H, int W,
                                      float ambient, uint8_t* kind, float* rgb, float* nrm, float* lit, long long* counters, void* stream) {
     O2345_REQUIRE_INDEX_BYTES("mesh_raster_shade_textured", index_bytes);
-    O2345_REQUIRE(mesh_sizes_ok(nv, nt), "mesh_raster_shade_textured: bad sizes (nv must stay below 2^30 and 3 * nt below 2^31)");
+    RS_REQUIRE_SIZES("mesh_raster_shade_textured", nv, nt);
     RsCamera cam;
-    const float K[4] = {fx, fy, cx, cy}, M[12] = {m00, m01, m02, m03, m10, m11, m12, m13, m20, m21, m22, m23};
-    if (!rs_entry_camera("mesh_raster_shade_textured", K, M, H, W, 1.0, 0, 0, cam)) return -1;
+    if (!rs_entry_camera("mesh_raster_shade_textured", K_host, c2w_host, H, W, 1.0, 0, 0, cam)) return -1;
     O2345_REQUIRE(tex_h >= 1 && tex_w >= 1 && tex_h <= RT_MAX_SIDE && tex_w <= RT_MAX_SIDE && (long long)tex_h * tex_w < (1ll << 31),
                   "mesh_raster_shade_textured: bad atlas size %d x %d (a side is limited to %d)", tex_w, tex_h, RT_MAX_SIDE);
     O2345_REQUIRE(!normal_image_or_null == !normals_or_null && !normals_or_null == !tangents_or_null,

@@ -48,6 +48,19 @@ static bool tex_layout(long long nt, int c, TexLayout& L) {
     return true;
 }
 
+#define TEX_REQUIRE_LAYOUT(unit, nt, texel, L) \
+    O2345_REQUIRE(tex_layout(nt, texel, L), unit ": bad layout (nt = %lld >= 1, texel = %d in [4, 64], sides <= 16384, texels < 2^31)", nt, texel)
+// the owner of a texel of cell k: the B half (i + j >= c) is triangle 2k + 1's where there is one
+__device__ __forceinline__ long long tex_owner(long long k, bool isB, long long nt) { return isB && 2 * k + 1 < nt ? 2 * k + 1 : 2 * k; }
+
+// the walk from image texel e (raster order) to its cell k, cell-major slot s, owner t and local (i, j); used: the cell holds triangles
+struct TexWalk { bool used; long long k, s, t; int i, j; };
+__device__ __forceinline__ TexWalk tex_walk(const TexLayout& L, long long e, long long nt) {
+    const int y = (int)(e / L.W), x = (int)(e - (long long)y * L.W), cx = x / L.c, cy = y / L.c, i = x - cx * L.c, j = y - cy * L.c;
+    const long long k = (long long)cy * L.G + cx;
+    return {k < L.cells, k, k * L.c * L.c + (long long)j * L.c + i, tex_owner(k, i + j >= L.c, nt), i, j};
+}
+
 // thread per texel of a used cell, cell-major
 template <typename IDX>
 __global__ __launch_bounds__(256) void k_tex_points(const double* __restrict__ verts, long long nv, const IDX* __restrict__ tris, long long nt, int c,
@@ -60,9 +73,8 @@ __global__ __launch_bounds__(256) void k_tex_points(const double* __restrict__ v
         const long long k = e / cc;
         const int r = (int)(e - k * cc), j = r / c, i = r - j * c;
         const bool isB = i + j >= c;
-        const bool hasB = 2 * k + 1 < nt;
-        const long long t = isB && hasB ? 2 * k + 1 : 2 * k;
-        const bool counts = isB ? (hasB && i == c - 1 && j == c - 1) : (i == 0 && j == 0);       // one texel speaks for its triangle
+        const long long t = tex_owner(k, isB, nt);
+        const bool counts = isB ? (t != 2 * k && i == c - 1 && j == c - 1) : (i == 0 && j == 0);  // one texel speaks for its triangle
         double w1, w2;
         if (isB) { w1 = __ddiv_rn((double)(c - 1 - i), (double)(c - 3)); w2 = __ddiv_rn((double)(c - 1 - j), (double)(c - 3)); }
         else { w1 = __ddiv_rn((double)i, (double)(c - 2)); w2 = __ddiv_rn((double)j, (double)(c - 2)); }
@@ -97,14 +109,9 @@ __global__ __launch_bounds__(256) void k_tex_points(const double* __restrict__ v
 __global__ __launch_bounds__(256) void k_tex_pack(const float* __restrict__ rgb, TexLayout L, uchar4* __restrict__ image) {
     const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
     if (e >= (long long)L.W * L.H) return;
-    const int y = (int)(e / L.W), x = (int)(e - (long long)y * L.W);
-    const int cx = x / L.c, cy = y / L.c;
-    const long long k = (long long)cy * L.G + cx;
+    const TexWalk w = tex_walk(L, e, 0);                                 // the owner is not read
     uchar4 o = make_uchar4(0, 0, 0, 0);
-    if (k < L.cells) {
-        const long long s = k * L.c * L.c + (long long)(y - cy * L.c) * L.c + (x - cx * L.c);
-        o = make_uchar4(mesh_colour_u8(rgb[3 * s]), mesh_colour_u8(rgb[3 * s + 1]), mesh_colour_u8(rgb[3 * s + 2]), 255);
-    }
+    if (w.used) o = make_uchar4(mesh_colour_u8(rgb[3 * w.s]), mesh_colour_u8(rgb[3 * w.s + 1]), mesh_colour_u8(rgb[3 * w.s + 2]), 255);
     image[e] = o;
 }
 
@@ -165,16 +172,9 @@ __global__ __launch_bounds__(256) void k_tex_normal_pack(const float* __restrict
     const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
     int flags = 0;
     if (e < (long long)L.W * L.H) {
-        const int y = (int)(e / L.W), x = (int)(e - (long long)y * L.W);
-        const int cx = x / L.c, cy = y / L.c;
-        const long long k = (long long)cy * L.G + cx;
+        const TexWalk w = tex_walk(L, e, nt);
         uint8_t o[4] = {128, 128, 255, 255};
-        if (k < L.cells) {
-            const int i = x - cx * L.c, j = y - cy * L.c;
-            const long long s = k * L.c * L.c + (long long)j * L.c + i;
-            const long long t = i + j >= L.c && 2 * k + 1 < nt ? 2 * k + 1 : 2 * k;
-            flags = nm_texel(grad + 3 * s, rotation, nrm + 9 * t, tan + 12 * t, o);
-        }
+        if (w.used) flags = nm_texel(grad + 3 * w.s, rotation, nrm + 9 * w.t, tan + 12 * w.t, o);
         image[e] = make_uchar4(o[0], o[1], o[2], o[3]);
     }
     wave_count((flags & NM_BAD_GRADIENT) != 0, counters + 1);
@@ -199,7 +199,7 @@ int o2345_mesh_texture_points(const double* verts, long long nv, const void* tri
                               const float* bound_min, const float* bound_max, double* points_idx, float* points_world, O2345TextureStats* stats, void* stream) {
     O2345_REQUIRE_INDEX_BYTES("mesh_texture_points", index_bytes);
     TexLayout L;
-    O2345_REQUIRE(tex_layout(nt, texel, L), "mesh_texture_points: bad layout (nt = %lld >= 1, texel = %d in [4, 64], sides <= 16384, texels < 2^31)", nt, texel);
+    TEX_REQUIRE_LAYOUT("mesh_texture_points", nt, texel, L);
     O2345_REQUIRE(nv >= 1 && nv < (1ll << 30), "mesh_texture_points: bad size (nv must be in [1, 2^30))");
     O2345_REQUIRE(grid_R >= 2, "mesh_texture_points: bad resolution %d", grid_R);
     O2345_REQUIRE(verts && tris && bound_min && bound_max && points_idx && points_world && stats, "mesh_texture_points: null pointer");
@@ -217,7 +217,7 @@ int o2345_mesh_texture_points(const double* verts, long long nv, const void* tri
 
 int o2345_mesh_texture_pack(const float* rgb, long long nt, int texel, uint8_t* image, void* stream) {
     TexLayout L;
-    O2345_REQUIRE(tex_layout(nt, texel, L), "mesh_texture_pack: bad layout (nt = %lld >= 1, texel = %d in [4, 64], sides <= 16384, texels < 2^31)", nt, texel);
+    TEX_REQUIRE_LAYOUT("mesh_texture_pack", nt, texel, L);
     O2345_REQUIRE(rgb && image, "mesh_texture_pack: null pointer");
     O2345_REQUIRE(((uintptr_t)image & 3) == 0, "mesh_texture_pack: image must be 4-byte aligned");
     hipLaunchKernelGGL(k_tex_pack, dim3(cdiv((long long)L.W * L.H, 256)), dim3(256), 0, (hipStream_t)stream, rgb, L, (uchar4*)image);
@@ -230,7 +230,7 @@ int o2345_mesh_texture_corners(const double* verts, long long nv, const void* tr
                                void* stream) {
     O2345_REQUIRE_INDEX_BYTES("mesh_texture_corners", index_bytes);
     TexLayout L;
-    O2345_REQUIRE(tex_layout(nt, texel, L), "mesh_texture_corners: bad layout (nt = %lld >= 1, texel = %d in [4, 64], sides <= 16384, texels < 2^31)", nt, texel);
+    TEX_REQUIRE_LAYOUT("mesh_texture_corners", nt, texel, L);
     O2345_REQUIRE(nv >= 1 && nv < (1ll << 30), "mesh_texture_corners: bad size (nv must be in [1, 2^30))");
     O2345_REQUIRE(bound_min && bound_max && grid_R >= 2, "mesh_texture_corners: bad bounds / resolution");
     O2345_REQUIRE(verts && tris && positions && uv && indices && bounds && workspace && (!grad || normals), "mesh_texture_corners: null pointer");
@@ -262,7 +262,7 @@ int o2345_mesh_texture_frames(const float* positions, const float* uv, long long
 int o2345_mesh_texture_normal_pack(const float* grad, const float* rotation, const float* normals, const float* tangents, long long nt, int texel,
                                    uint8_t* image, long long* counters, void* stream) {
     TexLayout L;
-    O2345_REQUIRE(tex_layout(nt, texel, L), "mesh_texture_normal_pack: bad layout (nt = %lld >= 1, texel = %d in [4, 64], sides <= 16384, texels < 2^31)", nt, texel);
+    TEX_REQUIRE_LAYOUT("mesh_texture_normal_pack", nt, texel, L);
     O2345_REQUIRE(grad && normals && tangents && image && counters, "mesh_texture_normal_pack: null pointer");
     O2345_REQUIRE(((uintptr_t)image & 3) == 0, "mesh_texture_normal_pack: image must be 4-byte aligned");
     O2345_REQUIRE(((uintptr_t)counters & 7) == 0, "mesh_texture_normal_pack: counters must be 8-byte aligned");

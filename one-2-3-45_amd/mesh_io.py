@@ -1042,6 +1042,20 @@ def _bounds64(bounds, what):
     return b0, b1 - b0
 
 
+def _texel_owners(L, nt):
+    """-> int64 [cells, c^2]: the owner triangle of every cell-major texel, 2k or min(2k + 1, nt - 1) by texture_cell's A / B rule"""
+    owner = texture_cell(L["texel"])[0]
+    return np.minimum(2 * np.arange(L["cells"])[:, None] + owner.reshape(1, -1), int(nt) - 1)
+
+
+def _cells_to_image(values, L, fill):
+    """cell-major RGBA8 texels (uint8 [cells c^2, 4]) -> the image uint8 [height, width, 4] in raster order; the texels of unused cells are ``fill``"""
+    c, G, cells = L["texel"], L["grid"], L["cells"]
+    cell = np.tile(np.array(fill, np.uint8), (L["rows"] * G, c, c, 1))
+    cell[:cells] = values.reshape(cells, c, c, 4)
+    return np.ascontiguousarray(cell.reshape(L["rows"], G, c, c, 4).transpose(0, 2, 1, 3, 4).reshape(L["height"], L["width"], 4))
+
+
 def texture_points(verts_idx, faces, texel, resolution, bounds=((-1.0, -1.0, -1.0), (1.0, 1.0, 1.0))):
     """The surface point of every texel of every used cell (host twin of ops.mesh_texture_points, and the definition of its result, to the last bit) ->
     (points float64 [cells c^2, 3] in index coordinates, world float32 [cells c^2, 3]).  Cell-major: point k c^2 + j c + i is local texel (i, j) of cell k.
@@ -1057,11 +1071,9 @@ def texture_points(verts_idx, faces, texel, resolution, bounds=((-1.0, -1.0, -1.
     b0, ext = _bounds64(bounds, "texture_points")
     if not np.isfinite(p[f.reshape(-1)]).all():
         raise ValueError("texture_points: non-finite vertex coordinate")
-    c, cells, nt, rm1 = L["texel"], L["cells"], f.shape[0], float(int(resolution) - 1)
-    owner, w, _ = texture_cell(c)
-    tri = np.minimum(2 * np.arange(cells)[:, None] + owner.reshape(1, -1), nt - 1)          # [cells, c^2]
-    P = p[f[tri]]                                                                           # [cells, c^2, 3 corners, 3]
-    w = w.reshape(1, c * c, 3, 1)
+    c, rm1 = L["texel"], float(int(resolution) - 1)
+    P = p[f[_texel_owners(L, f.shape[0])]]                                                  # [cells, c^2, 3 corners, 3]
+    w = texture_cell(c)[1].reshape(1, c * c, 3, 1)
     x = (w[:, :, 0] * P[:, :, 0] + w[:, :, 1] * P[:, :, 1]) + w[:, :, 2] * P[:, :, 2]
     x = np.where(x < 0.0, 0.0, np.where(x > rm1, rm1, x)).reshape(-1, 3)
     return x, np.ascontiguousarray((x / rm1 * ext + b0).astype(np.float32))
@@ -1072,16 +1084,12 @@ def pack_texture(rgb, nt, texel):
     where v = 0): colour = uint8(int(float32(x) * 255)), the truncation the vertex colours use, alpha 255; the texels of unused cells are 0, 0, 0, 0.
     Host twin of ops.mesh_texture_pack."""
     L = texture_layout(nt, texel)
-    c, G, cells = L["texel"], L["grid"], L["cells"]
     a = np.asarray(rgb, np.float32).reshape(-1, 3)
     if a.shape[0] != L["texels"]:
         raise ValueError(f"pack_texture: {L['texels']} texel colours expected, got {a.shape[0]}")
     with np.errstate(invalid="ignore"):
         q = (a * np.float32(255.0)).astype(np.int32).astype(np.uint8)
-    cell = np.zeros((L["rows"] * G, c, c, 4), np.uint8)
-    cell[:cells, :, :, :3] = q.reshape(cells, c, c, 3)
-    cell[:cells, :, :, 3] = 255
-    return np.ascontiguousarray(cell.reshape(L["rows"], G, c, c, 4).transpose(0, 2, 1, 3, 4).reshape(L["height"], L["width"], 4))
+    return _cells_to_image(np.concatenate([q, np.full((q.shape[0], 1), 255, np.uint8)], 1), L, (0, 0, 0, 0))
 
 
 def _mat44(m):
@@ -1232,7 +1240,7 @@ def pack_normal_map(grad, normals, tangents, nt, texel, trans_mat=None):
     holds the degenerate mark of texture_frames (frame_is_degenerate), and for a gradient whose length, before or behind
     the rotation, is zero or not finite.  Counts: bad gradients over every texel of a used cell; z < 0 (informative, no error) where z is computed."""
     L = texture_layout(nt, texel)
-    c, G, cells, nt = L["texel"], L["grid"], L["cells"], int(nt)
+    nt = int(nt)
     g = np.asarray(grad, np.float32).reshape(-1, 3)
     N = np.asarray(normals, np.float32).reshape(-1, 3)
     TW = np.asarray(tangents, np.float32).reshape(-1, 4)
@@ -1243,8 +1251,7 @@ def pack_normal_map(grad, normals, tangents, nt, texel, trans_mat=None):
         R[:3, :3] = np.asarray(trans_mat, np.float32).reshape(3, 3)
         trans_mat = R
     n, ok = _unit_gradients(g, trans_mat)
-    owner = texture_cell(c)[0]
-    tri = np.minimum(2 * np.arange(cells)[:, None] + owner.reshape(1, -1), nt - 1).reshape(-1)          # [cells c^2]
+    tri = _texel_owners(L, nt).reshape(-1)                                                              # [cells c^2]
     Nf, Tf = N[3 * tri], TW[3 * tri]
     degenerate = frame_is_degenerate(Tf)
     Nd, Td, w = Nf.astype(np.float64), Tf[:, :3].astype(np.float64), Tf[:, 3:].astype(np.float64)
@@ -1254,11 +1261,7 @@ def pack_normal_map(grad, normals, tangents, nt, texel, trans_mat=None):
         rgba = np.stack([_normal_channel(_dot3(n, Td)), _normal_channel(_dot3(n, B)), _normal_channel(z), np.full(z.shape, 255, np.uint8)], 1)
         back = ok & ~degenerate & (z < 0.0)
     rgba = np.where((ok & ~degenerate)[:, None], rgba, np.array(NORMAL_MAP_FLAT, np.uint8))
-    cell = np.empty((L["rows"] * G, c, c, 4), np.uint8)
-    cell[:] = np.array(NORMAL_MAP_FLAT, np.uint8)
-    cell[:cells] = rgba.reshape(cells, c, c, 4)
-    image = np.ascontiguousarray(cell.reshape(L["rows"], G, c, c, 4).transpose(0, 2, 1, 3, 4).reshape(L["height"], L["width"], 4))
-    return image, {"bad_gradient": int((~ok).sum()), "back_facing": int(back.sum())}
+    return _cells_to_image(rgba, L, NORMAL_MAP_FLAT), {"bad_gradient": int((~ok).sum()), "back_facing": int(back.sum())}
 
 
 def decode_normal_map(image):

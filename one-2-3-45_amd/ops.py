@@ -1664,17 +1664,35 @@ def surface_pack(kind, depth, rgb, grad, H, W, background=(0, 0, 0, 0)):
 
 # ---------------------------------------------------------------------------------------------------------- mesh rasterizer
 def _raster_camera(K, c2w, near, cull, what):
-    """the twin's refusals (raster.camera) -> the sixteen float32 scalars of the C ABI (fx, fy, cx, cy, the 3 x 4 of c2w), near, cull"""
+    """the twin's refusals (raster.camera) -> (K float32 [3,3], the 3 x 4 of c2w float32: the two host arrays of the C ABI), near, cull"""
     from . import raster
     K, M = _camera(K, c2w, what)
     cam = raster.camera(K, M, near, cull)
-    return [float(K[0, 0]), float(K[1, 1]), float(K[0, 2]), float(K[1, 2])] + [float(x) for x in M.reshape(-1)], cam["near"], cam["cull"]
+    return (K, M), cam["near"], cam["cull"]
 
 
 def raster_info(counts):
     """The counts of o2345_mesh_raster_count / _emit, on the host -> the info dict of raster.rasterize, by O2345_RASTER_*"""
     from . import raster
     return dict(zip(raster.COUNTS, (int(c) for c in counts)))
+
+
+def _raster_visibility(verts, tris, ib, cam, H, W, near, cull, ray_depth, what):
+    """count, one copy of the counts for the size of the tile lists, emit -> face int32 [H,W], depth float32 [H,W], bary float32 [H,W,3], the counts (device)"""
+    from . import raster
+    nv, nt, dev = verts.shape[0], tris.shape[0], verts.device
+    ws, wsb = _scratch("o2345_mesh_raster_workspace_bytes", (nv, nt, H, W), dev, "mesh_raster")
+    if not wsb:
+        raise ValueError(f"{what}: bad sizes ({nv} vertices, {nt} triangles; the tables are int32)")
+    counts = torch.empty(len(raster.COUNTS), dtype=torch.int64, device=dev)
+    call("o2345_mesh_raster_count", verts, tris, ib, nv, nt, *cam, H, W, near, cull, ws, wsb, counts)
+    n_pairs = raster_info(counts.tolist())["pairs"]
+    if n_pairs >= 2 ** 31:
+        raise ValueError(f"{what}: {n_pairs} (tile, face) pairs; the tile lists hold fewer than 2^31")
+    lists = _workspace(4 * max(n_pairs, 1), dev, "mesh_raster_lists").view(torch.int32) if n_pairs else None
+    face, depth, bary = (torch.empty(H, W, *s, dtype=d, device=dev) for s, d in (((), torch.int32), ((), torch.float32), ((3,), torch.float32)))
+    call("o2345_mesh_raster_emit", nv, nt, *cam, H, W, near, cull, int(bool(ray_depth)), ws, wsb, n_pairs, lists, face, depth, bary, counts)
+    return face, depth, bary, counts
 
 
 @_on_device
@@ -1694,19 +1712,7 @@ def mesh_raster(verts, tris, K, c2w, H, W, near=1e-3, cull=0, ray_depth=False, v
     for a, what in ((vertex_colors, "vertex_colors"), (vertex_normals, "vertex_normals")):
         if a is not None and (a.dtype != torch.float32 or tuple(a.shape) != (nv, 3) or a.device != dev or not a.is_contiguous()):
             raise ValueError(f"mesh_raster: {what} must be contiguous float32 [{nv},3] on {dev}, got {a.dtype} {tuple(a.shape)} on {a.device}")
-    ws, wsb = _scratch("o2345_mesh_raster_workspace_bytes", (nv, nt, H, W), dev, "mesh_raster")
-    if not wsb:
-        raise ValueError(f"mesh_raster: bad sizes ({nv} vertices, {nt} triangles; the tables are int32)")
-    counts = torch.empty(len(raster.COUNTS), dtype=torch.int64, device=dev)
-    call("o2345_mesh_raster_count", verts, tris, ib, nv, nt, *cam, H, W, near, cull, ws, wsb, counts)
-    n_pairs = raster_info(counts.tolist())["pairs"]
-    if n_pairs >= 2 ** 31:
-        raise ValueError(f"mesh_raster: {n_pairs} (tile, face) pairs; the tile lists hold fewer than 2^31")
-    lists = _workspace(4 * max(n_pairs, 1), dev, "mesh_raster_lists").view(torch.int32) if n_pairs else None
-    face = torch.empty(H, W, dtype=torch.int32, device=dev)
-    depth = torch.empty(H, W, dtype=torch.float32, device=dev)
-    bary = torch.empty(H, W, 3, dtype=torch.float32, device=dev)
-    call("o2345_mesh_raster_emit", nv, nt, *cam, H, W, near, cull, int(bool(ray_depth)), ws, wsb, n_pairs, lists, face, depth, bary, counts)
+    face, depth, bary, counts = _raster_visibility(verts, tris, ib, cam, H, W, near, cull, ray_depth, "mesh_raster")
     kind = torch.empty(H * W, dtype=torch.uint8, device=dev)
     rgb = torch.empty(H * W, 3, dtype=torch.float32, device=dev)
     nrm = torch.empty(H * W, 3, dtype=torch.float32, device=dev)
@@ -1760,19 +1766,7 @@ def mesh_raster_textured(positions, uv, image, K, c2w, H, W, near=1e-3, cull=0, 
     verts = positions.contiguous().to(torch.float64)
     tris = torch.arange(3 * m, dtype=torch.int32, device=dev).view(m, 3)
     nv, nt, ib = 3 * m, m, 4
-    ws, wsb = _scratch("o2345_mesh_raster_workspace_bytes", (nv, nt, H, W), dev, "mesh_raster")
-    if not wsb:
-        raise ValueError(f"mesh_raster_textured: bad sizes ({nv} vertices, {nt} triangles; the tables are int32)")
-    counts = torch.empty(len(raster.COUNTS), dtype=torch.int64, device=dev)
-    call("o2345_mesh_raster_count", verts, tris, ib, nv, nt, *cam, H, W, near, cull, ws, wsb, counts)
-    n_pairs = raster_info(counts.tolist())["pairs"]
-    if n_pairs >= 2 ** 31:
-        raise ValueError(f"mesh_raster_textured: {n_pairs} (tile, face) pairs; the tile lists hold fewer than 2^31")
-    lists = _workspace(4 * max(n_pairs, 1), dev, "mesh_raster_lists").view(torch.int32) if n_pairs else None
-    face = torch.empty(H, W, dtype=torch.int32, device=dev)
-    depth = torch.empty(H, W, dtype=torch.float32, device=dev)
-    bary = torch.empty(H, W, 3, dtype=torch.float32, device=dev)
-    call("o2345_mesh_raster_emit", nv, nt, *cam, H, W, near, cull, int(bool(ray_depth)), ws, wsb, n_pairs, lists, face, depth, bary, counts)
+    face, depth, bary, counts = _raster_visibility(verts, tris, ib, cam, H, W, near, cull, ray_depth, "mesh_raster_textured")
     kind = torch.empty(H * W, dtype=torch.uint8, device=dev)
     rgb, nrm, lit = (torch.empty(H * W, 3, dtype=torch.float32, device=dev) for _ in range(3))
     counters = torch.empty(len(raster.TEX_COUNTS), dtype=torch.int64, device=dev)

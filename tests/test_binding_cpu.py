@@ -31,7 +31,11 @@ def test_every_pointer_has_an_element_type_and_the_host_rule_holds():
         assert p.host == (p.name.endswith("_host") or fn.endswith("_host")), (fn, p)
         assert p.elem != "size_t" or p.host, (fn, p)
     host = {(fn, p.name) for fn, p in ptrs if p.host}
-    assert len(host) == 59
+    assert len(host) == 65                                # 59 + the camera of the three raster entries, passed as o2345_camera_rays takes it
+    for fn in ("o2345_mesh_raster_count", "o2345_mesh_raster_emit", "o2345_mesh_raster_shade_textured", "o2345_camera_rays"):
+        cam = {p.name: p for f, p in ptrs if f == fn and p.name in ("K_host", "c2w_host")}
+        assert set(cam) == {"K_host", "c2w_host"} and all(p.host and p.elem == "float32" for p in cam.values()), fn
+        assert not [p for p in PROTOTYPES[fn][1] if p.ctype is ctypes.c_float and p.name != "ambient"], fn          # no camera scalar is left
     assert {("o2345_surface_trace", "bound_min_host"), ("o2345_mesh_distance_reduce", "thresholds_host"), ("o2345_render_rays", "io_host"),
             ("o2345_ply_records_host", "faces"), ("o2345_struct_layout", "offsets_host")} <= host
     assert not {("o2345_sdf_grid_sparse_x3", "background"), ("o2345_mesh_decimate_count", "tris"), ("o2345_costvol_index", "n_rows_dev")} & host
@@ -148,7 +152,7 @@ def test_bind_accepts():
 def test_call_returns_values_and_raises_on_a_failing_status():
     w, h = ctypes.c_int(), ctypes.c_int()
     assert L.call("o2345_mesh_texture_texels", 33, 8, w, h) == 17 * 64 and (w.value, h.value) == (5 * 8, 4 * 8)       # 17 cells, G = 5: 5 x 4 cells
-    assert L.call("o2345_version") == L.ABI_VERSION == 230
+    assert L.call("o2345_version") == L.ABI_VERSION == 231
     assert L.call("o2345_obj_text_bytes", 0, 0, 12, 0, 0) == 0 and b"=" in L.call("o2345_knobs")
     with pytest.raises(RuntimeError, match=r"o2345 sdf_mlp failed \(-?\d+\): .*null pointer") as e:
         L.call("o2345_sdf_mlp", 0, None, None, 8, None, None, None, 10, 0, 1.0, None, None, None, None, None)

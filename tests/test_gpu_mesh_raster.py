@@ -31,8 +31,8 @@ def _host(out):
 
 
 def _camera_args(s):
-    K, M = np.asarray(s["K"], np.float32), np.asarray(s["c2w"], np.float32)
-    return [float(K[0, 0]), float(K[1, 1]), float(K[0, 2]), float(K[1, 2])] + [float(x) for x in M[:3].reshape(-1)]
+    """the two host arrays of the C ABI: K float32 [3,3] and the 3 x 4 of c2w"""
+    return np.ascontiguousarray(s["K"], np.float32), np.ascontiguousarray(np.asarray(s["c2w"], np.float32)[:3])
 
 
 def _raw(dev, s, dtype, cull=0, ray_depth=False, attrs=False, g=None, stream=None):
@@ -170,9 +170,18 @@ def test_every_refusal_is_a_status(dev):
     def shade(verts=verts, tris=tris, ib=4, nv=3, nt=1, face=face, bary=bary, H=8, W=8, kind=kind, rgb=rgb, nrm=nrm):
         _lib.call("o2345_mesh_raster_shade", verts, tris, ib, nv, nt, face, bary, H, W, None, None, kind, rgb, nrm)
     count(); emit(); shade()
-    changed = lambda i, x: cam[:i] + [x] + cam[i + 1:]
-    cameras = [(changed(0, 0.0), "fx and fy"), (changed(1, -4.0), "fx and fy"), (changed(2, float("nan")), "finite"), (changed(7, float("inf")), "finite"),
-               (changed(5, 1e-3), "rotation"), (changed(4, 2.0), "rotation")]
+    outs = (ws, counts, face, depth, bary, kind, rgb, nrm, lists)
+    for o in outs:
+        o.view(torch.uint8).fill_(0xA5)
+
+    def changed(which, at, x):
+        """the camera with entry ``at`` of K (which = 0) or of c2w (which = 1) replaced"""
+        new = [a.copy() for a in cam]
+        new[which][at] = x
+        return tuple(new)
+    cameras = [(changed(0, (0, 0), 0.0), "fx and fy"), (changed(0, (1, 1), -4.0), "fx and fy"), (changed(0, (0, 2), float("nan")), "finite"),
+               (changed(1, (0, 3), float("inf")), "finite"), (changed(1, (0, 1), 1e-3), "rotation"), (changed(1, (0, 0), 2.0), "rotation"),
+               ((None, cam[1]), "null pointer"), ((cam[0], None), "null pointer"), (changed(0, (0, 1), 0.5), "without skew"), (changed(0, (2, 2), 2.0), "without skew")]
     bad = [(count, dict(cam=c), m) for c, m in cameras] + [(emit, dict(cam=c), m) for c, m in cameras]
     for fn in (count, emit):
         bad += [(fn, dict(H=0), "image size"), (fn, dict(W=-1), "image size"), (fn, dict(H=1 << 16, W=1 << 15), "image size"), (fn, dict(near=0.0), "near"),
@@ -188,6 +197,7 @@ def test_every_refusal_is_a_status(dev):
         with pytest.raises(RuntimeError, match=message):
             fn(**kw)
     torch.cuda.synchronize()
+    assert all(bool((o.view(torch.uint8) == 0xA5).all()) for o in outs)          # nothing was launched, not even a memset
     # the Python side refuses before anything is launched
     for kw in (dict(cull=3), dict(near=0.0), dict(H=0), dict(K=np.array([[4, 0.5, 0], [0, 4, 0], [0, 0, 1]], np.float32)), dict(c2w=2.0 * np.eye(4, dtype=np.float32)),
                dict(vertex_colors=torch.zeros(3, 3, dtype=torch.float64, device=dev)), dict(verts=verts.float())):

@@ -36,8 +36,8 @@ def _host(out):
 
 
 def _camera_args(K, M):
-    K, M = np.asarray(K, np.float32), np.asarray(M, np.float32)
-    return [float(K[0, 0]), float(K[1, 1]), float(K[0, 2]), float(K[1, 2])] + [float(x) for x in M[:3].reshape(-1)]
+    """the two host arrays of the C ABI: K float32 [3,3] and the 3 x 4 of c2w"""
+    return np.ascontiguousarray(K, np.float32), np.ascontiguousarray(np.asarray(M, np.float32)[:3])
 
 
 def _shade(dev, verts, tris, face, bary, uv, image, frames, cam, H, W, ambient, g=None, stream=None):
@@ -244,9 +244,15 @@ def test_every_refusal_is_a_status_and_launches_nothing(dev):
               tan=tan, cam=cam, H=8, W=8, ambient=0.25, kind=kind, rgb=rgb, shn=shn, lit=lit, counters=counters):
         _lib.call("o2345_mesh_raster_shade_textured", verts, tris, ib, nv, nt, face, bary, uv, image, th, tw, nimage, nrm, tan, *cam, H, W, ambient, kind, rgb, shn,
                   lit, counters)
-    changed = lambda i, x: cam[:i] + [x] + cam[i + 1:]
-    bad = [(dict(cam=changed(0, 0.0)), "fx and fy"), (dict(cam=changed(2, float("nan"))), "finite"), (dict(cam=changed(5, 1e-3)), "rotation"),
-           (dict(cam=changed(4, 2.0)), "rotation"), (dict(H=0), "image size"), (dict(H=1 << 16, W=1 << 15), "image size"), (dict(ib=2), "index_bytes"),
+
+    def changed(which, at, x):
+        """the camera with entry ``at`` of K (which = 0) or of c2w (which = 1) replaced"""
+        new = [a.copy() for a in cam]
+        new[which][at] = x
+        return tuple(new)
+    bad = [(dict(cam=changed(0, (0, 0), 0.0)), "fx and fy"), (dict(cam=changed(0, (0, 2), float("nan"))), "finite"), (dict(cam=changed(1, (0, 1), 1e-3)), "rotation"),
+           (dict(cam=changed(1, (0, 0), 2.0)), "rotation"), (dict(cam=(None, cam[1])), "null pointer"), (dict(cam=(cam[0], None)), "null pointer"),
+           (dict(cam=changed(0, (0, 1), 0.5)), "without skew"), (dict(cam=changed(0, (2, 2), 2.0)), "without skew"), (dict(H=0), "image size"), (dict(H=1 << 16, W=1 << 15), "image size"), (dict(ib=2), "index_bytes"),
            (dict(nv=1 << 30), "bad sizes"), (dict(nt=-1), "bad sizes"), (dict(th=0), "atlas size"), (dict(tw=16385), "atlas size"), (dict(th=-5), "atlas size"),
            (dict(nimage=None), "together"), (dict(nrm=None), "together"), (dict(tan=None), "together"), (dict(nimage=None, nrm=None), "together"),
            (dict(ambient=-0.01), "ambient"), (dict(ambient=1.5), "ambient"), (dict(ambient=float("nan")), "ambient"), (dict(ambient=float("inf")), "ambient"),

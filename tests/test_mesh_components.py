@@ -154,7 +154,7 @@ def test_cabi_declares_and_exports_the_component_entries():
     names = ("o2345_mesh_components_workspace_bytes", "o2345_mesh_components_count", "o2345_mesh_components_emit")
     assert all(n in protos for n in names)
     lib = L.lib()
-    assert all(hasattr(lib, n) for n in names) and lib.o2345_version() == 230
+    assert all(hasattr(lib, n) for n in names) and lib.o2345_version() == 231
     small, big = lib.o2345_mesh_components_workspace_bytes(0, 0), lib.o2345_mesh_components_workspace_bytes(1000, 2000)
     assert 0 < small < big and big >= 4 * (3 * 1000 + 2000)
     # argument checks come before any device work

@@ -241,7 +241,7 @@ def test_cabi_declares_and_exports_the_decimation_entries():
     assert all(n in protos for n in names)
     assert protos["o2345_mesh_decimate_count"][1][5] is ctypes.c_double and protos["o2345_mesh_decimate_workspace_bytes"][0] is ctypes.c_size_t
     lib = L.lib()
-    assert all(hasattr(lib, n) for n in names) and lib.o2345_version() == 230
+    assert all(hasattr(lib, n) for n in names) and lib.o2345_version() == 231
     wsb = lib.o2345_mesh_decimate_workspace_bytes
     assert 0 < wsb(0, 0) < wsb(1000, 2000) and wsb(1000, 2000) >= 12 * 2048 + 4 * 4096 and wsb(2 ** 30, 0) == 0 and wsb(3, (2 ** 31 + 2) // 3) == 0 and wsb(-1, 0) == 0
     # argument checks come before any device work

@@ -149,7 +149,7 @@ def test_new_entries_are_declared_exported_and_additive():
     for name in NEW_SYMBOLS:
         assert name in protos and getattr(lib, name) is not None, name
         assert name in open(_lib.HEADER).read().split("int o2345_version(void);")[0], f"{name} is missing from the header's list of additive entries"
-    assert lib.o2345_version() == 230 and _lib.ABI_VERSION == 230
+    assert lib.o2345_version() == 231 and _lib.ABI_VERSION == 231
     assert protos["o2345_mesh_samples_workspace_bytes"][0] is ctypes.c_size_t and protos["o2345_mesh_distance_query"][0] is ctypes.c_int
 
 

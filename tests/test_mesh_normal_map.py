@@ -98,7 +98,7 @@ def test_a_gradient_along_the_face_normal_is_the_flat_texel(rot):
 
 
 @pytest.mark.parametrize("rot", [False, True])
-@pytest.mark.parametrize("nt, c", [(1, 4), (2, 5), (3, 4), (33, 4), (33, 5), (86, 4)])
+@pytest.mark.parametrize("nt, c", [(1, 4), (1, 5), (2, 4), (2, 5), (3, 4), (5, 4), (5, 5), (33, 4), (33, 5), (86, 4)])
 def test_the_twin_equals_the_definition_texel_by_texel(nt, c, rot):
     case = U.strip(nt, c, seed=nt * 100 + c, rot=U.rotation() if rot else None)
     N, TW, degenerate = mio.texture_frames(case["pos"], case["uv"])

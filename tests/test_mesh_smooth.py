@@ -220,7 +220,7 @@ def test_cabi_declares_and_exports_the_adjacency_and_smoothing_entries():
     assert all(n in protos for n in names)
     assert protos["o2345_mesh_smooth"][1][6:8] == [ctypes.c_double, ctypes.c_double] and protos["o2345_mesh_adjacency_workspace_bytes"][0] is ctypes.c_size_t
     lib = L.lib()
-    assert all(hasattr(lib, n) for n in names) and lib.o2345_version() == 230
+    assert all(hasattr(lib, n) for n in names) and lib.o2345_version() == 231
     small, big = lib.o2345_mesh_adjacency_workspace_bytes(0, 0), lib.o2345_mesh_adjacency_workspace_bytes(1000, 2000)
     assert 0 < small < big and big >= 4 * (1000 + 6 * 2000)
     # argument checks come before any device work

@@ -17,7 +17,7 @@ import pytest
 
 mio = importlib.import_module("one-2-3-45_amd.mesh_io")
 
-COUNTS = (1, 2, 3, 41)            # 41 triangles: 21 cells in a 5 x 5 grid, five rows of which the last holds one cell
+COUNTS = (1, 2, 3, 5, 33, 41)     # 5: three cells on a 2 x 2 grid, one unused; 41 triangles: 21 cells in a 5 x 5 grid, five rows of which the last holds one cell
 TEXELS = (4, 5, 8)
 
 

@@ -364,6 +364,6 @@ def test_cabi_declares_the_surface_entries():
     protos = L.parse_header()
     for name in ("o2345_surface_bricks", "o2345_surface_trace_workspace_bytes", "o2345_surface_trace", "o2345_camera_rays", "o2345_surface_pack"):
         assert name in protos, name
-    assert L.ABI_VERSION == 230 and len(protos["o2345_surface_trace"][1]) == 23
+    assert L.ABI_VERSION == 231 and len(protos["o2345_surface_trace"][1]) == 23
     build = importlib.import_module("one-2-3-45_amd.build")
     assert "surface_trace.hip" in build.SOURCES and "surface_trace.hip" not in build.EXTRA_FLAGS                # no extra flags
