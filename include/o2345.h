@@ -71,7 +71,9 @@ const char* o2345_last_error(void);
  * rasterizer entries o2345_mesh_raster_workspace_bytes, o2345_mesh_raster_count, o2345_mesh_raster_emit, o2345_mesh_raster_shade; the textured
  * shading entry o2345_mesh_raster_shade_textured. */
 /* 231 = ABI 2.3.1: o2345_mesh_raster_count, o2345_mesh_raster_emit and o2345_mesh_raster_shade_textured take the camera as o2345_camera_rays does, K_host [9]
- * and c2w_host [12], in place of sixteen float scalars at the same position; nothing else changed. */
+ * and c2w_host [12], in place of sixteen float scalars at the same position; nothing else changed.
+ * Additive since 2.3.1 (no existing entry changed, the version stays 231): the mesh alignment entries o2345_mesh_align_workspace_bytes,
+ * o2345_mesh_align_step. */
 int o2345_version(void);
 /* Layout self-description of the declared structs as THIS library was compiled (sizeof, and offsetof of every field in declaration order): a binding
  * asserts its own structs against it at load time (one-2-3-45_amd/_lib.py does) -- a field added on one side only cannot corrupt calls silently.
@@ -728,6 +730,34 @@ size_t o2345_mesh_distance_reduce_workspace_bytes(long long n);
 int o2345_mesh_distance_reduce(const double* d2, const int* nearest, const double* weights, long long n, const double* thresholds_host, int n_thresholds,
                                const double* verts, const void* tris, int index_bytes, long long nv, long long nt, void* workspace, size_t workspace_bytes,
                                O2345DistanceStats* stats, void* stream);
+
+/* ---- mesh alignment (additive since 2.3.1; the reference aligns its meshes in another tool before it reports an F-score) --------------------------------
+ * One step of aligning mesh A to mesh B by a similarity transform: the moments of the point-to-plane Gauss-Newton system of A's samples against B, for
+ * n_transforms (1 .. 64) candidate transforms at once.  The 7 x 7 solve and the loop are the caller's (mesh_io.similarity_step, align_meshes).  Everything
+ * is fp64, one operation at a time, in the order written (csrc/mesh_align_math.h is the text), equal to the host twin (mesh_io.align_terms) to the last bit
+ * per sample.  points device fp64 [n,3], weights device fp64 [n] (NULL = 1), n < 2^28; transforms device fp64 [n_transforms,12], the rows of [M | t].
+ *   pair      (transform k, sample e): x = M_k p_e + t_k, x_i = ((M_i0 p_0 + M_i1 p_1) + M_i2 p_2) + t_i; d2 and nearest of x are those of
+ *             o2345_mesh_distance_query over the same verts, tris and grid (grid NULL: every triangle), bit for bit; q is the closest point of triangle
+ *             `nearest` (A, B, C).  MATCHED: nearest >= 0 and d2 finite and >= 0.  INLIER: matched and (max_distance == 0 or d2 <= max_distance^2).
+ *   terms     x' = x - pivot, n = ((B - A) x (C - A)) / sqrt(n . n), J = (x' x n, n, n . x') (seven entries), b = n . (q - x): (w J_i) J_j for i <= j and
+ *             (w J_i) b.
+ *   moments   device fp64 [n_transforms,48], per transform: 0 .. 27 the upper triangle of sum w J J^T, row-major; 28 .. 34 sum w J b; 35 sum w and 36
+ *             sum w d2 (all over the inliers); 37 sum w and 38 sum w min(d2, max_distance^2) over the matched (max_distance == 0: sum w d2); 39 .. 41
+ *             sum w x' and 42 sum w |x'|^2 over the inliers; 43, 44, 45 the numbers of inliers, of matched samples that are no inliers, and of unmatched
+ *             samples, as doubles; 46, 47 zero.  The sums are the same bits on every run (the tree of o2345_mesh_distance_reduce per transform, at most
+ *             288 additions in a chain, no floating-point atomics).
+ *   tris NULL no target: every sample is an inlier with q = x and d2 = 0 and columns 0 .. 34 are 0 -- columns 35 and 39 .. 42 give the centroid and the rms
+ *             radius of a sample set; with `moved` it is the transform of a point set.
+ *   outputs   moved fp64 [n_transforms,n,3], d2 fp64 [n_transforms,n], nearest int32 [n_transforms,n]: each may be NULL, and nothing of that size is
+ *             written without them.
+ * Errors: bad sizes, max_distance negative or not finite, a pivot or a transform entry that is not finite (the transforms are read back to check them: one
+ * synchronisation of the stream).  A target index out of range or a non-finite target coordinate is skipped as the query skips it.
+ * workspace_bytes(n, n_transforms) is 0 for n < 0, n >= 2^28, n_transforms < 1 or > 64. */
+size_t o2345_mesh_align_workspace_bytes(long long n, int n_transforms);
+int o2345_mesh_align_step(const double* points, const double* weights, long long n, const double* transforms, int n_transforms, const double* verts,
+                          const void* tris, int index_bytes, long long nv, long long nt, const void* grid, size_t grid_bytes, long long max_cells,
+                          double max_distance, double pivot_x, double pivot_y, double pivot_z, void* workspace, size_t workspace_bytes, double* moments,
+                          double* moved, double* d2, int* nearest, void* stream);
 
 /* ---- simplification by quadric-error edge collapse (additive since 2.2; the reference has no such step, its users simplify the mesh in another tool) ----
  * Rounds of independent half-edge collapses ordered by Garland - Heckbert's quadric error, subset placement: collapsing v -> u removes v, u keeps its

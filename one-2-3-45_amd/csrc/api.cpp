@@ -35,6 +35,7 @@ int preload_mesh_pack();
 int preload_mesh_export();
 int preload_mesh_texture();
 int preload_mesh_distance();
+int preload_mesh_align();
 int preload_mesh_audit();
 int preload_mesh_fill();
 int preload_mesh_intersect();
@@ -69,6 +70,7 @@ int o2345_preload(void) {
     if ((e = o2345::preload_mesh_export())) bad = e;
     if ((e = o2345::preload_mesh_texture())) bad = e;
     if ((e = o2345::preload_mesh_distance())) bad = e;
+    if ((e = o2345::preload_mesh_align())) bad = e;
     if ((e = o2345::preload_mesh_audit())) bad = e;
     if ((e = o2345::preload_mesh_fill())) bad = e;
     if ((e = o2345::preload_mesh_intersect())) bad = e;

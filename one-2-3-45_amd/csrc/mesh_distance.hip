@@ -30,14 +30,9 @@
 
 namespace o2345 {
 
-constexpr long long MD_MAX_SAMPLES = 1ll << 28;
 constexpr int MD_THRESHOLDS = sizeof(O2345DistanceStats::within) / sizeof(double);          // 8 (the device block of the reduction: include/o2345.h)
 constexpr int MD_AXIS = 256;                          // cells per axis at most
-constexpr int MD_RED_ITEMS = 16;                      // samples per thread of k_md_reduce
-constexpr int MD_RED_TILE = 256 * MD_RED_ITEMS;
 constexpr int MD_RED_COLS = 3 + MD_THRESHOLDS;        // sum w, sum w d, sum w d^2, within[8]
-constexpr double MD_SLACK = 9.313225746154785e-10;    // 2^-30
-constexpr double MD_DOWN = 0.9999999999990905;        // 1 - 2^-40: a product rounded towards zero, and then some
 
 struct MdThresholds { double tau[MD_THRESHOLDS]; int n; };
 
@@ -55,17 +50,6 @@ struct MdGridTotals {
     int n_long;
 };
 static_assert(sizeof(MdSampleTotals) <= 128 && sizeof(MdGridTotals) <= 128 && sizeof(MdGridHead) <= 128, "the heads are 128 bytes");
-
-// the corners of a triangle whose indices are in range -> true iff all nine coordinates are finite
-__device__ __forceinline__ bool md_corners(const double* __restrict__ verts, int a, int b, int c, double (&A)[3], double (&B)[3], double (&C)[3]) {
-    bool all_finite = true;
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-        A[d] = verts[3 * (long long)a + d]; B[d] = verts[3 * (long long)b + d]; C[d] = verts[3 * (long long)c + d];
-        all_finite &= finite(A[d]) && finite(B[d]) && finite(C[d]);
-    }
-    return all_finite;
-}
 
 // ---- samples -------------------------------------------------------------------------------------------------------------------------------------
 // kk[t] = k_t^2 (1 for a triangle that is counted as bad input); the 64-bit total is an integer atomic: the int scan may wrap where it exceeds 2^28
@@ -274,22 +258,7 @@ __global__ __launch_bounds__(256) void k_md_grid_finish(const MdGridHead* __rest
 }
 
 // ---- query ---------------------------------------------------------------------------------------------------------------------------------------
-template <typename IDX>
-__device__ __forceinline__ void md_visit_cell(int ci, const int* __restrict__ cell_start, const int* __restrict__ entries, const double* __restrict__ verts, int nv,
-                                              const IDX* __restrict__ tris, const double (&p)[3], double& best, int& best_t) {
-    const int e1 = cell_start[ci + 1];
-    for (int e = cell_start[ci]; e < e1; ++e) {
-        const int t = entries[e];
-        int a, b, c, region;
-        (void)mesh_triangle(tris, t, nv, a, b, c);                   // registered: usable
-        double A[3], B[3], C[3];
-        (void)md_corners(verts, a, b, c, A, B, C);
-        const double d2 = md_point_triangle(p, A, B, C, region);
-        if (d2 < best || (d2 == best && t < best_t)) { best = d2; best_t = t; }
-    }
-}
-
-// one lane per point: shells of cells around the point's own cell (see "walk" above)
+// one lane per point: shells of cells around the point's own cell (md_walk_grid, mesh_grid.h; see "walk" above)
 template <typename IDX>
 __global__ __launch_bounds__(256) void k_md_query_grid(const double* __restrict__ pts, long long n, const double* __restrict__ verts, int nv,
                                                        const IDX* __restrict__ tris, const MdGridHead* __restrict__ head, const int* __restrict__ cell_start,
@@ -297,80 +266,29 @@ __global__ __launch_bounds__(256) void k_md_query_grid(const double* __restrict_
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     const double p[3] = {pts[3 * i], pts[3 * i + 1], pts[3 * i + 2]};
-    const double cell = head->cell;
-    const int nx = head->dims[0], ny = head->dims[1], nz = head->dims[2];
-    const double ox = head->origin[0], oy = head->origin[1], oz = head->origin[2];
-    const int cx = md_cell_index(p[0], ox, cell, nx), cy = md_cell_index(p[1], oy, cell, ny), cz = md_cell_index(p[2], oz, cell, nz);
-    const double slack = (head->scale + fmax(fabs(p[0]), fmax(fabs(p[1]), fabs(p[2])))) * MD_SLACK;
-    double best = INFINITY;
-    int best_t = -1;
-    const int rmax = max(max(max(cx, nx - 1 - cx), max(cy, ny - 1 - cy)), max(cz, nz - 1 - cz));
-    for (int r = 0; r <= rmax; ++r) {
-        const int z0 = max(cz - r, 0), z1 = min(cz + r, nz - 1), y0 = max(cy - r, 0), y1 = min(cy + r, ny - 1), x0 = max(cx - r, 0), x1 = min(cx + r, nx - 1);
-        for (int z = z0; z <= z1; ++z)
-            for (int y = y0; y <= y1; ++y) {
-                const int rowi = (z * ny + y) * nx;
-                if (abs(z - cz) == r || abs(y - cy) == r) {
-                    for (int x = x0; x <= x1; ++x) md_visit_cell(rowi + x, cell_start, entries, verts, nv, tris, p, best, best_t);
-                } else {                                             // inside the shell's z and y range: its two x faces
-                    if (cx - r >= 0) md_visit_cell(rowi + cx - r, cell_start, entries, verts, nv, tris, p, best, best_t);
-                    if (cx + r < nx) md_visit_cell(rowi + cx + r, cell_start, entries, verts, nv, tris, p, best, best_t);
-                }
-            }
-        // the closest that anything outside the cube of shells 0 .. r can be
-        double lb = INFINITY;
-        if (cx + r + 1 < nx) lb = fmin(lb, (ox + (double)(cx + r + 1) * cell) - p[0]);
-        if (cx - r > 0) lb = fmin(lb, p[0] - (ox + (double)(cx - r) * cell));
-        if (cy + r + 1 < ny) lb = fmin(lb, (oy + (double)(cy + r + 1) * cell) - p[1]);
-        if (cy - r > 0) lb = fmin(lb, p[1] - (oy + (double)(cy - r) * cell));
-        if (cz + r + 1 < nz) lb = fmin(lb, (oz + (double)(cz + r + 1) * cell) - p[2]);
-        if (cz - r > 0) lb = fmin(lb, p[2] - (oz + (double)(cz - r) * cell));
-        lb = lb - slack;
-        if (lb > 0.0 && (lb * lb) * MD_DOWN > best) break;
-    }
+    double best;
+    int best_t;
+    md_walk_grid(p, verts, nv, tris, head, cell_start, entries, best, best_t);
     d2_out[i] = best;
     nearest_out[i] = best_t;
 }
 
-// one lane per point against every triangle in index order: the definition on the device, and the path for tiny targets
+// one lane per point against every triangle in index order (md_walk_all, mesh_grid.h): the definition on the device, and the path for tiny targets
 template <typename IDX>
 __global__ __launch_bounds__(256) void k_md_query_all(const double* __restrict__ pts, long long n, const double* __restrict__ verts, int nv,
                                                       const IDX* __restrict__ tris, long long nt, double* __restrict__ d2_out, int* __restrict__ nearest_out) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     const double p[3] = {pts[3 * i], pts[3 * i + 1], pts[3 * i + 2]};
-    double best = INFINITY;
-    int best_t = -1;
-    for (long long t = 0; t < nt; ++t) {
-        int a, b, c, region;
-        if (!mesh_triangle(tris, t, nv, a, b, c)) continue;
-        double A[3], B[3], C[3];
-        if (!md_corners(verts, a, b, c, A, B, C)) continue;
-        if (md_normal2(A, B, C) == 0.0) continue;
-        const double d2 = md_point_triangle(p, A, B, C, region);
-        if (d2 < best) { best = d2; best_t = (int)t; }
-    }
+    double best;
+    int best_t;
+    md_walk_all(p, verts, nv, tris, nt, best, best_t);
     d2_out[i] = best;
     nearest_out[i] = best_t;
 }
 
 // ---- summary -------------------------------------------------------------------------------------------------------------------------------------
-// fixed-order sums of MD_RED_COLS values over a 256-thread block: wave butterflies, then (w0 + w1) + (w2 + w3); valid in thread 0.  The butterfly is
-// written out: these are doubles, and its order is part of the result (wave_sum is for integers)
-__device__ __forceinline__ void md_block_sums(double (&v)[MD_RED_COLS]) {
-    __shared__ double sm[MD_RED_COLS][4];
-#pragma unroll
-    for (int k = 0; k < MD_RED_COLS; ++k) {
-        for (int off = 32; off; off >>= 1) v[k] += __shfl_xor(v[k], off);
-        if ((threadIdx.x & 63) == 0) sm[k][threadIdx.x >> 6] = v[k];
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int k = 0; k < MD_RED_COLS; ++k) v[k] = (sm[k][0] + sm[k][1]) + (sm[k][2] + sm[k][3]);
-    }
-}
-
+// (the fixed-order block sums, md_block_sums, are in mesh_grid.h: the alignment step adds its moments by the same tree)
 // block b: samples [b * MD_RED_TILE, (b + 1) * MD_RED_TILE), thread i its MD_RED_ITEMS consecutive ones -> partials[b][MD_RED_COLS]
 __global__ __launch_bounds__(256) void k_md_reduce(const double* __restrict__ d2, const int* __restrict__ nearest, const double* __restrict__ weights, long long n,
                                                    MdThresholds th, double* __restrict__ partials, O2345DistanceStats* __restrict__ st) {

@@ -60,17 +60,18 @@ O2345_HD double md_weight(const double (&P0)[3], const double (&P1)[3], const do
     return 0.5 * sqrt(md_normal2(P0, P1, P2)) / (double)(k * k);
 }
 
-// |p - q|^2, q the point of triangle (A, B, C) closest to p: the region walk of Ericson, Real-Time Collision Detection 5.1.5, in the book's order;
-// region: 0 vertex A, 1 vertex B, 2 edge AB, 3 vertex C, 4 edge AC, 5 edge BC, 6 face
-O2345_HD double md_point_triangle(const double (&p)[3], const double (&A)[3], const double (&B)[3], const double (&C)[3], int& region) {
-    double ab[3], ac[3], ap[3], q[3], d[3];
+// |p - q|^2 and q, the point of triangle (A, B, C) closest to p: the region walk of Ericson, Real-Time Collision Detection 5.1.5, in the book's order;
+// region: 0 vertex A, 1 vertex B, 2 edge AB, 3 vertex C, 4 edge AC, 5 edge BC, 6 face.  At a vertex q is that corner and d2 is |p - corner|^2 as computed
+// for the region tests: the distance never depends on whether q is wanted
+O2345_HD double md_closest_point(const double (&p)[3], const double (&A)[3], const double (&B)[3], const double (&C)[3], int& region, double (&q)[3]) {
+    double ab[3], ac[3], ap[3], d[3];
     md_sub(B, A, ab); md_sub(C, A, ac); md_sub(p, A, ap);
     const double d1 = md_dot(ab, ap), d2 = md_dot(ac, ap);
-    if (d1 <= 0.0 && d2 <= 0.0) { region = 0; return md_dot(ap, ap); }
+    if (d1 <= 0.0 && d2 <= 0.0) { region = 0; q[0] = A[0]; q[1] = A[1]; q[2] = A[2]; return md_dot(ap, ap); }
     double bp[3];
     md_sub(p, B, bp);
     const double d3 = md_dot(ab, bp), d4 = md_dot(ac, bp);
-    if (d3 >= 0.0 && d4 <= d3) { region = 1; return md_dot(bp, bp); }
+    if (d3 >= 0.0 && d4 <= d3) { region = 1; q[0] = B[0]; q[1] = B[1]; q[2] = B[2]; return md_dot(bp, bp); }
     const double vc = d1 * d4 - d3 * d2;
     if (vc <= 0.0 && d1 >= 0.0 && d3 <= 0.0) {
         const double v = d1 / (d1 - d3);
@@ -83,7 +84,7 @@ O2345_HD double md_point_triangle(const double (&p)[3], const double (&A)[3], co
     double cp[3];
     md_sub(p, C, cp);
     const double d5 = md_dot(ab, cp), d6 = md_dot(ac, cp);
-    if (d6 >= 0.0 && d5 <= d6) { region = 3; return md_dot(cp, cp); }
+    if (d6 >= 0.0 && d5 <= d6) { region = 3; q[0] = C[0]; q[1] = C[1]; q[2] = C[2]; return md_dot(cp, cp); }
     const double vb = d5 * d2 - d1 * d6;
     if (vb <= 0.0 && d2 >= 0.0 && d6 <= 0.0) {
         const double w = d2 / (d2 - d6);
@@ -112,6 +113,12 @@ O2345_HD double md_point_triangle(const double (&p)[3], const double (&A)[3], co
     region = 6;
     md_sub(p, q, d);
     return md_dot(d, d);
+}
+
+// the distance alone: what the query walks with
+O2345_HD double md_point_triangle(const double (&p)[3], const double (&A)[3], const double (&B)[3], const double (&C)[3], int& region) {
+    double q[3];
+    return md_closest_point(p, A, B, C, region, q);
 }
 
 // ---- the uniform grid over a target mesh ---------------------------------------------------------------------------------------------------------

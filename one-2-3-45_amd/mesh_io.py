@@ -1720,10 +1720,11 @@ def surface_samples(verts, faces, spacing=None):
     return pts, wgt, tri
 
 
-def closest_point_triangle(p, A, B, C):
+def closest_point_triangle(p, A, B, C, return_point=False):
     """Squared distance from points to triangles, broadcast over the leading axes (all [..., 3]) -> (d2 float64, region uint8): |p - q|^2 with q from the
     region walk of Ericson, Real-Time Collision Detection 5.1.5, the regions tested in the book's order -- 0 vertex A, 1 vertex B, 2 edge AB, 3 vertex C,
-    4 edge AC, 5 edge BC, 6 face.  The first region whose test passes gives q; this code, one operation per line, is the definition."""
+    4 edge AC, 5 edge BC, 6 face.  The first region whose test passes gives q; this code, one operation per line, is the definition.  ``return_point``
+    adds q float64 [..., 3] as a third result (the alignment's point-to-plane terms need it)."""
     with np.errstate(all="ignore"):
         ab = B - A
         ac = C - A
@@ -1771,7 +1772,7 @@ def closest_point_triangle(p, A, B, C):
         q = np.where((region == 1)[..., None], np.broadcast_to(B, shape), q)
         q = np.where((region == 0)[..., None], np.broadcast_to(A, shape), q)
         d = p - q
-        return _dot3(d, d), region
+        return (_dot3(d, d), region, q) if return_point else (_dot3(d, d), region)
 
 
 def closest_triangles(points, verts, faces, chunk=256):
@@ -1822,16 +1823,22 @@ def distance_report(a_to_b, b_to_a, thresholds, degenerate_a, degenerate_b):
             "fscore": [2.0 * p * r / (p + r) if p + r > 0 else 0.0 for p, r in zip(P, R)], "degenerate_targets": {"a": degenerate_a, "b": degenerate_b}}
 
 
-def mesh_distance(va, fa, vb, fb, spacing=None, thresholds=(), return_samples=False):
+def mesh_distance(va, fa, vb, fb, spacing=None, thresholds=(), return_samples=False, align=None):
     """Distance between mesh A (under test) and mesh B (the reference) as surfaces, on the host (the twin of ops.mesh_distance) -> {"a_to_b", "b_to_a": the
     one-sided summaries (distance_summary) of A's samples against B and of B's against A; "chamfer": the mean of the two means; "hausdorff": the larger
     of the two maxima; "thresholds"; "precision" = a_to_b.within, "recall" = b_to_a.within and "fscore" = 2 P R / (P + R) (0 when P + R == 0) per
     threshold; "degenerate_targets": {"a", "b"}, the triangles without an area that took no part as targets}.  Samples: surface_samples at ``spacing``
-    (None: one per triangle).  ``return_samples`` adds "samples": {"a", "b"} -> {"points", "weight", "triangle", "d2", "nearest"}."""
+    (None: one per triangle).  ``return_samples`` adds "samples": {"a", "b"} -> {"points", "weight", "triangle", "d2", "nearest"}.  ``align`` (None: the
+    meshes are taken to share a frame): True or a dict of align_meshes arguments (align_arguments) -- A is moved onto B by align_meshes first, the
+    distances are those of the moved A, and "alignment" holds align_meshes' result."""
     th = _check_thresholds(thresholds)
     spacing = _check_spacing(spacing)
     va, fa = _distance_mesh(va, fa, "mesh_distance")
     vb, fb = _distance_mesh(vb, fb, "mesh_distance")
+    alignment = None
+    if align is not None and align is not False:
+        alignment = align_meshes(va, fa, vb, fb, **align_arguments(align, spacing))
+        va = transform_vertices(va, alignment["transform"])
     sides, degenerate, samples = {}, {}, {}
     for name, (v, f), (tv, tf), other in (("a_to_b", (va, fa), (vb, fb), "b"), ("b_to_a", (vb, fb), (va, fa), "a")):
         pts, w, tri = surface_samples(v, f, spacing)
@@ -1841,6 +1848,8 @@ def mesh_distance(va, fa, vb, fb, spacing=None, thresholds=(), return_samples=Fa
     out = distance_report(sides["a_to_b"], sides["b_to_a"], th, degenerate["a"], degenerate["b"])
     if return_samples:
         out["samples"] = samples
+    if alignment is not None:
+        out["alignment"] = alignment
     return out
 
 
@@ -1863,10 +1872,340 @@ def load_mesh_pair(path_a, path_b):
     return (va, fa), (vb, fb)
 
 
-def compare_mesh_files(path_a, path_b, spacing=None, thresholds=(), return_samples=False):
+def compare_mesh_files(path_a, path_b, spacing=None, thresholds=(), return_samples=False, align=None):
     """mesh_distance of two mesh files (.ply, .glb, .obj; load_mesh_pair brings them into one frame)"""
     (va, fa), (vb, fb) = load_mesh_pair(path_a, path_b)
-    return mesh_distance(va, fa, vb, fb, spacing, thresholds, return_samples)
+    return mesh_distance(va, fa, vb, fb, spacing, thresholds, return_samples, align)
+
+
+# ------------------------------------------------------------------------------------------------------------------ mesh alignment
+# the functions below are the host twin of csrc/mesh_align.hip and the DEFINITION of its results: the moved points, d2, nearest and the 48 terms of every
+# (transform, sample) pair to the last bit (float64, one operation at a time, in the order written), the sums of a moments row as math.fsum of the terms.
+# similarity_step and align_run -- the 7 x 7 solve and the loop -- are shared with the device path (ops.mesh_align), which only supplies the rows.
+ALIGN_MAX_TRANSFORMS = 64
+ALIGN_COLUMNS = 48
+ALIGN_DEFAULT_AZIMUTHS = 8                       # what ``align=True`` searches: the azimuth of a single-image reconstruction is unknown
+
+
+def _align_matrix(T, what):
+    """3 x 4, 4 x 4 or 12 numbers -> float64 [3,4], finite"""
+    T = np.asarray(T, np.float64)
+    if T.shape == (4, 4):
+        T = T[:3]
+    elif T.shape == (12,):
+        T = T.reshape(3, 4)
+    if T.shape != (3, 4):
+        raise ValueError(f"mesh_align: {what} must be a 3 x 4 or 4 x 4 matrix, got shape {T.shape}")
+    if not np.isfinite(T).all():
+        raise ValueError(f"mesh_align: {what} has a non-finite entry")
+    return np.ascontiguousarray(T)
+
+
+def _check_max_distance(max_distance):
+    """-> the truncation distance tau as a float; 0.0 (None) means none"""
+    if max_distance is None:
+        return 0.0
+    if isinstance(max_distance, (bool, np.bool_)) or not isinstance(max_distance, (int, float, np.integer, np.floating)) or not (
+            np.isfinite(max_distance) and max_distance >= 0):
+        raise ValueError(f"mesh_align: max_distance must be None or a finite float >= 0, got {max_distance!r}")
+    return float(max_distance)
+
+
+def _check_candidates(candidates):
+    """None (the identity alone) or [K,3,3], 1 <= K <= 64, finite -> float64 [K,3,3]"""
+    if candidates is None:
+        return np.eye(3)[None].copy()
+    R = np.asarray(candidates, np.float64)
+    if R.ndim != 3 or R.shape[1:] != (3, 3):
+        raise ValueError(f"mesh_align: candidates must be None or rotations [K,3,3], got shape {R.shape}")
+    if not 1 <= R.shape[0] <= ALIGN_MAX_TRANSFORMS:
+        raise ValueError(f"mesh_align: {R.shape[0]} candidates; between 1 and {ALIGN_MAX_TRANSFORMS}")
+    if not np.isfinite(R).all():
+        raise ValueError("mesh_align: candidates has a non-finite entry")
+    return R
+
+
+def rodrigues(omega):
+    """The rotation by |omega| about omega: I + (sin t / t) K + ((1 - cos t) / t^2) K^2, K the cross-product matrix; the series below t = 1e-4"""
+    w = np.asarray(omega, np.float64).reshape(3)
+    t2 = float(w @ w)
+    t = np.sqrt(t2)
+    a, b = (1.0 - t2 / 6.0, 0.5 - t2 / 24.0) if t < 1e-4 else (np.sin(t) / t, (1.0 - np.cos(t)) / t2)
+    K = np.array([[0.0, -w[2], w[1]], [w[2], 0.0, -w[0]], [-w[1], w[0], 0.0]])
+    return np.eye(3) + a * K + b * (K @ K)
+
+
+def rotation_candidates(n_azimuth, up=(0.0, 0.0, 1.0)):
+    """-> float64 [n,3,3]: the rotations by 360 j / n degrees about ``up``, j = 0 .. n - 1 (j = 0 is the identity, to the bit)"""
+    if isinstance(n_azimuth, (bool, np.bool_)) or not isinstance(n_azimuth, (int, np.integer)) or not 1 <= n_azimuth <= ALIGN_MAX_TRANSFORMS:
+        raise ValueError(f"mesh_align: n_azimuth must be an integer in 1 .. {ALIGN_MAX_TRANSFORMS}, got {n_azimuth!r}")
+    up = np.asarray(up, np.float64)
+    if up.shape != (3,) or not np.isfinite(up).all() or not up.any():
+        raise ValueError(f"mesh_align: up must be three finite numbers, not all zero, got {up!r}")
+    axis = up / np.sqrt(up @ up)
+    return np.stack([np.eye(3) if j == 0 else rodrigues(axis * (2.0 * np.pi * j / int(n_azimuth))) for j in range(int(n_azimuth))])
+
+
+def align_apply(T, p):
+    """ma_apply: T [..., 12] (the rows of [M | t]) and p [..., 3], broadcast -> x [..., 3], x_k = ((M_k0 p_0 + M_k1 p_1) + M_k2 p_2) + t_k"""
+    T, p = np.asarray(T, np.float64), np.asarray(p, np.float64)
+    return np.stack([((T[..., 4 * k] * p[..., 0] + T[..., 4 * k + 1] * p[..., 1]) + T[..., 4 * k + 2] * p[..., 2]) + T[..., 4 * k + 3] for k in range(3)], -1)
+
+
+def transform_vertices(verts, T):
+    """Vertices [N,3] under the transform T (3 x 4 or 4 x 4) -> float64 [N,3] (align_apply; ops.mesh_transform is its device form)"""
+    return align_apply(_align_matrix(T, "transform").reshape(12), np.asarray(verts, np.float64).reshape(-1, 3))
+
+
+def align_sample_terms(x, q, A, B, C, c, w):
+    """ma_jacobian and ma_terms of csrc/mesh_align_math.h: moved points x, their closest points q on triangles (A, B, C) (all [..., 3]), the pivot c [3]
+    and weights w [...] -> (terms [..., 35], J [..., 7], b [...]).  x' = x - c, n = ((B - A) x (C - A)) / sqrt(n . n), J = (x' x n, n, n . x'),
+    b = n . (q - x); terms: (w J_i) J_j for i <= j, row-major, then (w J_i) b."""
+    with np.errstate(all="ignore"):
+        e1, e2 = B - A, C - A
+        m = np.stack([e1[..., 1] * e2[..., 2] - e1[..., 2] * e2[..., 1], e1[..., 2] * e2[..., 0] - e1[..., 0] * e2[..., 2],
+                      e1[..., 0] * e2[..., 1] - e1[..., 1] * e2[..., 0]], -1)
+        l = np.sqrt(_dot3(m, m))
+        n = m / l[..., None]
+        xp = x - np.asarray(c, np.float64)
+        J = np.stack([xp[..., 1] * n[..., 2] - xp[..., 2] * n[..., 1], xp[..., 2] * n[..., 0] - xp[..., 0] * n[..., 2],
+                      xp[..., 0] * n[..., 1] - xp[..., 1] * n[..., 0], n[..., 0], n[..., 1], n[..., 2], _dot3(n, xp)], -1)
+        b = _dot3(n, q - x)
+        wj = w[..., None] * J
+        terms = [wj[..., i] * J[..., j] for i in range(7) for j in range(i, 7)] + [wj[..., i] * b for i in range(7)]
+        return np.stack(terms, -1), J, b
+
+
+def align_terms(points, weights, transforms, verts=None, faces=None, max_distance=None, pivot=(0.0, 0.0, 0.0)):
+    """What one step of the alignment adds up (host twin of o2345_mesh_align_step, per pair) -> {"terms" float64 [K,n,48], "moved" [K,n,3], "d2" [K,n],
+    "nearest" int32 [K,n]}.  points [n,3], weights [n] or None (1), transforms [K,12] or [K,3,4]; the target (verts, faces), or none.  Pair (k, e): x =
+    align_apply(T_k, p_e); d2 and nearest from closest_triangles of x (+inf and -1 when the target has no triangle with an area); MATCHED: nearest >= 0
+    and d2 finite and >= 0; INLIER: matched and (tau == 0 or d2 <= tau tau), tau = max_distance.  Columns: 0 .. 34 align_sample_terms, 35 w, 36 w d2 (all
+    for inliers); 37 w and 38 w min(d2, tau tau) for matched pairs; 39 .. 41 w x', 42 w |x'|^2 and 43 one for inliers (x' = x - pivot); 44 one for a
+    matched pair that is no inlier; 45 one for an unmatched pair; 46, 47 zero.  Without a target every pair is an inlier with q = x and d2 = 0, columns
+    0 .. 34 are zero, and nearest is -1."""
+    tau = _check_max_distance(max_distance)
+    p = np.ascontiguousarray(np.asarray(points, np.float64).reshape(-1, 3))
+    n = p.shape[0]
+    w = np.ones(n) if weights is None else np.asarray(weights, np.float64).reshape(n)
+    T = np.asarray(transforms, np.float64)
+    T = T.reshape(-1, 12)
+    K = T.shape[0]
+    if not 1 <= K <= ALIGN_MAX_TRANSFORMS:
+        raise ValueError(f"mesh_align: {K} transforms; between 1 and {ALIGN_MAX_TRANSFORMS}")
+    if not np.isfinite(T).all():
+        raise ValueError("mesh_align: a transform has a non-finite entry")
+    c = np.asarray(pivot, np.float64).reshape(3)
+    x = align_apply(T[:, None, :], p[None])
+    terms = np.zeros((K, n, ALIGN_COLUMNS))
+    d2, nearest = np.zeros((K, n)), np.full((K, n), -1, np.int32)
+    wk = np.broadcast_to(w, (K, n))
+    if faces is None:
+        matched = np.ones((K, n), bool)
+    else:
+        tv, tf = _distance_mesh(verts, faces, "mesh_align")
+        P = tv[tf]
+        if tf.shape[0] and (_normal2(P[:, 0], P[:, 1], P[:, 2]) != 0.0).any():
+            a, b = closest_triangles(x.reshape(-1, 3), tv, tf)[:2]
+            d2, nearest = a.reshape(K, n), b.reshape(K, n)
+        else:
+            d2 = np.full((K, n), np.inf)
+        matched = (nearest >= 0) & (d2 >= 0.0) & (d2 <= np.finfo(np.float64).max)
+    tau2 = tau * tau
+    inlier = matched & ((tau == 0.0) | (d2 <= tau2))
+    with np.errstate(all="ignore"):
+        xp = x - c
+        terms[..., 37] = np.where(matched, wk, 0.0)
+        terms[..., 38] = np.where(matched, wk * np.where(inlier, d2, tau2), 0.0)
+        terms[..., 35] = np.where(inlier, wk, 0.0)
+        terms[..., 36] = np.where(inlier, wk * d2, 0.0)
+        terms[..., 39:42] = np.where(inlier[..., None], wk[..., None] * xp, 0.0)
+        terms[..., 42] = np.where(inlier, wk * _dot3(xp, xp), 0.0)
+        terms[..., 43] = inlier
+        terms[..., 44] = matched & ~inlier
+        terms[..., 45] = ~matched
+        if faces is not None and inlier.any():
+            tri = tf[np.maximum(nearest, 0)]
+            A, B, C = tv[tri[..., 0]], tv[tri[..., 1]], tv[tri[..., 2]]
+            q = closest_point_triangle(x, A, B, C, return_point=True)[2]
+            terms[..., :35] = np.where(inlier[..., None], align_sample_terms(x, q, A, B, C, c, wk)[0], 0.0)
+    return {"terms": terms, "moved": x, "d2": d2, "nearest": nearest}
+
+
+def align_moments(terms):
+    """The moments rows [K,48] of terms [K,n,48]: every column math.fsum's (the device sums in a fixed tree; they agree to 1e-12 of sum |term|)"""
+    import math
+    return np.array([[math.fsum(t[:, j]) for j in range(t.shape[1])] for t in np.asarray(terms)]).reshape(len(terms), ALIGN_COLUMNS)
+
+
+def similarity_step(row, scale=True):
+    """The Gauss-Newton update of one moments row (columns 0 .. 34: the upper triangle of sum w J J^T, row-major, and sum w J b) -> None when the system
+    is singular or not finite ("degenerate"), else (M_inc float64 [3,3], shift float64 [3], u float64 [7]): u = (omega, tau, sigma) solves the 7 x 7
+    system (the leading 6 x 6 with sigma = 0 when ``scale`` is off), M_inc = exp(sigma) rodrigues(omega), shift = tau.  compose_similarity applies it."""
+    row = np.asarray(row, np.float64).reshape(-1)
+    H = np.zeros((7, 7))
+    H[np.triu_indices(7)] = row[:28]
+    H = H + np.triu(H, 1).T
+    g = row[28:35]
+    m = 7 if scale else 6
+    if not (np.isfinite(H).all() and np.isfinite(g).all()):
+        return None
+    try:
+        sol = np.linalg.solve(H[:m, :m], g[:m])
+    except np.linalg.LinAlgError:
+        return None
+    if not np.isfinite(sol).all():
+        return None
+    u = np.zeros(7)
+    u[:m] = sol
+    return np.exp(u[6]) * rodrigues(u[:3]), u[3:6].copy(), u
+
+
+def compose_similarity(T, M_inc, shift, pivot):
+    """T [3,4] followed by x -> pivot + M_inc (x - pivot) + shift: M <- M_inc M, t <- M_inc (t - pivot) + pivot + shift"""
+    c = np.asarray(pivot, np.float64)
+    return np.concatenate([M_inc @ T[:, :3], (M_inc @ (T[:, 3] - c) + c + shift)[:, None]], 1)
+
+
+def _align_score(row):
+    return float(row[38] / row[37]) if row[37] > 0 and np.isfinite(row[38]) else float("inf")
+
+
+def align_run(step, iterations=30, tol=1e-9, max_distance=None, scale=True, candidates=None, search_iterations=5, init=None):
+    """The alignment loop over a supplier of moments rows (shared by align_meshes and ops.mesh_align).  ``step(side, transforms [K,12], pivot [3], tau,
+    target)`` -> rows [K,48] of the samples of mesh ``side`` ("a" or "b") under the transforms, against B when ``target`` else without a target.
+      pivot c and radius rho_B: the centroid and the rms radius of B's samples (two rows without a target: sum w x / W, then sum w |x - c|^2 / W).
+      start of candidate rotation R_j: moment matching, s = rho_B / rho_A (1 without ``scale``), M = s R_j, t = c - s R_j c_A; with ``init`` (3 x 4 or
+      4 x 4) instead x -> c + R_j (init(x) - c).  ``candidates`` None: the identity alone.
+      search: all K > 1 candidates take ``search_iterations`` updates in lockstep (one row each per step; a degenerate one stops moving), then the one with
+      the smallest score col38 / col37 is kept, ties to the smallest index, and goes on alone.  ``iterations`` bounds the kept candidate's updates in all.
+      stop: an update with max(|omega|, |tau| / rho_B, |sigma|) < tol ("converged"), ``iterations`` updates, or a degenerate system.
+    -> {"transform" [4,4], "scale", "rotation" [3,3], "translation" [3], "score", "rms", "inlier_fraction", "iterations", "converged", "candidate",
+    "candidate_scores", "history": per evaluated transform of the kept candidate {"transform" [3,4], "score", "inliers", "rejected", "unmatched",
+    "update": the size of the update taken from it, or None}, "pivot" [3]: the c of every row}."""
+    for name, v in (("iterations", iterations), ("search_iterations", search_iterations)):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or v < 0:
+            raise ValueError(f"mesh_align: {name} must be an integer >= 0, got {v!r}")
+    if isinstance(tol, (bool, np.bool_)) or not isinstance(tol, (int, float, np.integer, np.floating)) or not (np.isfinite(tol) and tol >= 0):
+        raise ValueError(f"mesh_align: tol must be a finite float >= 0, got {tol!r}")
+    tau = _check_max_distance(max_distance)
+    R = _check_candidates(candidates)
+    T0 = None if init is None else _align_matrix(init, "init")
+    K = R.shape[0]
+    eye = np.eye(3, 4).reshape(1, 12)
+
+    def centroid_radius(side):
+        row = step(side, eye, np.zeros(3), 0.0, False)[0]
+        if not (row[35] > 0 and np.isfinite(row[35:43]).all()):
+            raise ValueError(f"mesh_align: mesh {side.upper()} has no surface to sample (total weight {float(row[35])!r})")
+        c = row[39:42] / row[35]
+        row = step(side, eye, c, 0.0, False)[0]
+        return c, float(np.sqrt(row[42] / row[35]))
+
+    c, rho_b = centroid_radius("b")
+    c_a, rho_a = centroid_radius("a")
+    if not (rho_a > 0 and rho_b > 0):
+        raise ValueError(f"mesh_align: a mesh has no extent (rms radii {rho_a!r}, {rho_b!r})")
+    T = np.zeros((K, 3, 4))
+    for j in range(K):
+        if T0 is None:
+            s = rho_b / rho_a if scale else 1.0
+            T[j, :, :3], T[j, :, 3] = s * R[j], c - s * (R[j] @ c_a)
+        else:
+            T[j] = compose_similarity(T0, R[j], np.zeros(3), c)
+
+    def evaluate(Ts):
+        rows = np.asarray(step("a", np.ascontiguousarray(Ts.reshape(-1, 12)), c, tau, True), np.float64).reshape(-1, ALIGN_COLUMNS)
+        return rows
+
+    def entry(Tk, row):
+        return {"transform": Tk.copy(), "score": _align_score(row), "inliers": int(row[43]), "rejected": int(row[44]), "unmatched": int(row[45]), "update": None}
+
+    def update(Tk, row):
+        sol = similarity_step(row, scale)
+        if sol is None:
+            return None, None
+        M_inc, shift, u = sol
+        size = max(float(np.sqrt(u[:3] @ u[:3])), float(np.sqrt(shift @ shift)) / rho_b, abs(float(u[6])))
+        return compose_similarity(Tk, M_inc, shift, c), size
+
+    n_search = min(search_iterations, iterations) if K > 1 else 0
+    alive, trails = [True] * K, [[] for _ in range(K)]
+    for _ in range(n_search):
+        rows = evaluate(T)
+        for j in range(K):
+            if alive[j]:
+                trails[j].append(entry(T[j], rows[j]))
+                new, size = update(T[j], rows[j])
+                if new is None:
+                    alive[j] = False
+                else:
+                    T[j], trails[j][-1]["update"] = new, size
+    rows = evaluate(T)
+    scores = [_align_score(r) for r in rows]
+    kept = int(np.argmin(scores))                                     # the first of equal minima
+    if not np.isfinite(scores[kept]):
+        raise ValueError("mesh_align: no sample of A found a triangle of B (the target has no triangle with an area, or max_distance leaves no inlier)")
+    Tk, row, history = T[kept].copy(), rows[kept], trails[kept]
+    done, converged, stuck = len(history) if alive[kept] else iterations, False, not alive[kept]
+    if history and alive[kept] and history[-1]["update"] < tol:
+        converged = True
+    while True:
+        history.append(entry(Tk, row))
+        if converged or stuck or done >= iterations:
+            break
+        new, size = update(Tk, row)
+        if new is None:
+            break
+        Tk, done, history[-1]["update"] = new, done + 1, size
+        row = evaluate(Tk[None])[0]
+        converged = size < tol
+    M = Tk[:, :3]
+    s = float(np.cbrt(np.linalg.det(M)))
+    full = np.eye(4)
+    full[:3] = Tk
+    n_updates = sum(1 for h in history if h["update"] is not None)
+    return {"transform": full, "scale": s, "rotation": M / s, "translation": Tk[:, 3].copy(), "score": _align_score(row),
+            "rms": float(np.sqrt(row[36] / row[35])) if row[35] > 0 else float("nan"), "inlier_fraction": float(row[35] / row[37]) if row[37] > 0 else 0.0,
+            "iterations": n_updates, "converged": bool(converged), "candidate": kept, "candidate_scores": scores, "history": history, "pivot": c.copy()}
+
+
+def align_meshes(va, fa, vb, fb, spacing=None, iterations=30, tol=1e-9, max_distance=None, scale=True, candidates=None, search_iterations=5, init=None):
+    """The similarity transform (rotation, translation, uniform scale unless ``scale`` is off) that moves mesh A onto mesh B, on the host (the twin of
+    ops.mesh_align and the definition): point-to-plane Gauss-Newton over A's surface samples (surface_samples at ``spacing``) against their closest
+    triangles of B, from each of the ``candidates`` rotations ([K,3,3], e.g. rotation_candidates; None: the identity) -- see align_run for the loop, the
+    stopping rule and the result.  ``max_distance``: samples farther than it from B take no part in the system, and count min(d2, max_distance^2) in the
+    score.  One-sided: B's samples only give the pivot and the radius.  Refused (ValueError): what surface_samples refuses, iterations < 0, more than 64
+    candidates, a negative or non-finite max_distance, an ``init`` that is not 3 x 4 or 4 x 4, non-finite entries."""
+    spacing = _check_spacing(spacing)
+    va, fa = _distance_mesh(va, fa, "mesh_align")
+    vb, fb = _distance_mesh(vb, fb, "mesh_align")
+    sets = {"a": surface_samples(va, fa, spacing)[:2], "b": surface_samples(vb, fb, spacing)[:2]}
+
+    def step(side, transforms, pivot, tau, target):
+        pts, w = sets[side]
+        return align_moments(align_terms(pts, w, transforms, vb if target else None, fb if target else None, tau, pivot)["terms"])
+    return align_run(step, iterations, tol, max_distance, scale, candidates, search_iterations, init)
+
+
+def align_arguments(align, spacing=None):
+    """The ``align`` argument of mesh_distance -> the keyword arguments of align_meshes: True searches ALIGN_DEFAULT_AZIMUTHS azimuths about z (the
+    identity alone does not survive an unknown azimuth), a dict is taken as it is; the distance's ``spacing`` is the default of the alignment's."""
+    if align is True:
+        kw = {"candidates": rotation_candidates(ALIGN_DEFAULT_AZIMUTHS)}
+    elif isinstance(align, dict):
+        kw = dict(align)
+    else:
+        raise ValueError(f"mesh_distance: align must be None, True or a dict of mesh_align arguments, got {align!r}")
+    kw.setdefault("spacing", spacing)
+    return kw
+
+
+def write_mesh(path, verts, faces):
+    """A bare mesh to a file by its extension (.ply, .glb, .obj), positions as they are"""
+    ext = _asset_ext(path)
+    v, f = np.asarray(verts, np.float32), np.asarray(faces, np.int32)
+    {".ply": write_ply_numpy, ".glb": write_glb, ".obj": write_obj_numpy}[ext](path, v, f)
 
 
 # ------------------------------------------------------------------------------------------------------------------ mesh audit

@@ -1246,15 +1246,82 @@ def distance_summary(stats, n_thresholds, target_triangles=None):
             "within": [div(st.within[k]) for k in range(n_thresholds)], "samples": n, "area": W}, degenerate
 
 
-def mesh_distance(va, ta, vb, tb, spacing=None, thresholds=(), return_samples=False, cell=None):
+@_on_device
+def mesh_align_step(points, weights, transforms, target=None, grid=None, max_distance=None, pivot=(0.0, 0.0, 0.0), moments=None, want=()):
+    """One step of the alignment on the device (o2345_mesh_align_step; definitions in csrc/mesh_align.hip, per pair == mesh_io.align_terms to the last bit)
+    -> (moments fp64 [K,48] on the device, {name: tensor for name in ``want``}).  points fp64 [n,3], weights fp64 [n] or None (1), transforms fp64
+    [K,12] on the device; ``target`` = (verts, tris) or None (no target: the centroid / radius / transform-only form); ``grid``: a MeshGrid of the target
+    or None for the exhaustive search; ``want``: any of "moved" [K,n,3], "d2" [K,n], "nearest" [K,n] -- nothing of that size is written otherwise.  One
+    synchronisation, for the library's check of the transforms."""
+    tau = mesh_io._check_max_distance(max_distance)
+    _vertices(points, "mesh_align_step")
+    n, dev = points.shape[0], points.device
+    if transforms.dtype != torch.float64 or transforms.dim() != 2 or transforms.shape[1] != 12:
+        raise ValueError(f"mesh_align_step: expected transforms [K,12] float64, got {tuple(transforms.shape)} {transforms.dtype}")
+    K = transforms.shape[0]
+    if not 1 <= K <= mesh_io.ALIGN_MAX_TRANSFORMS:
+        raise ValueError(f"mesh_align_step: {K} transforms; between 1 and {mesh_io.ALIGN_MAX_TRANSFORMS}")
+    tv, (tt, ib), nv, nt = (None, (None, 4), 0, 0) if target is None else (target[0], _triangles(target[1], "mesh_align_step"), target[0].shape[0], target[1].shape[0])
+    if tv is not None:
+        _vertices(tv, "mesh_align_step")
+    ws, wsb = _scratch("o2345_mesh_align_workspace_bytes", (n, K), dev, "mesh_align")
+    moments = torch.empty(K, mesh_io.ALIGN_COLUMNS, dtype=torch.float64, device=dev) if moments is None else moments
+    shapes = {"moved": ((K, n, 3), torch.float64), "d2": ((K, n), torch.float64), "nearest": ((K, n), torch.int32)}
+    extra = {k: torch.empty(shapes[k][0], dtype=shapes[k][1], device=dev) for k in want}
+    gp, gb, gm = (grid.buffer, grid.buffer.numel(), grid.max_cells) if grid is not None else (None, 0, 0)
+    c = [float(x) for x in np.asarray(pivot, np.float64).reshape(3)]
+    call("o2345_mesh_align_step", points, weights, n, transforms, K, tv, tt, ib, nv, nt, gp, gb, gm, tau, c[0], c[1], c[2], ws, wsb, moments,
+         extra.get("moved"), extra.get("d2"), extra.get("nearest"))
+    return moments, extra
+
+
+@_on_device
+def mesh_transform(verts, T):
+    """Vertices fp64 [N,3] under the transform T (3 x 4 or 4 x 4, host) on the device -> fp64 [N,3] (== mesh_io.transform_vertices to the last bit): the
+    alignment step without a target, with its ``moved`` output"""
+    _vertices(verts, "mesh_transform")
+    T = torch.from_numpy(mesh_io._align_matrix(T, "transform").reshape(1, 12).copy()).to(verts.device)
+    return mesh_align_step(verts.contiguous(), None, T, want=("moved",))[1]["moved"][0]
+
+
+def mesh_align_stepper(va, ta, vb, tb, spacing=None, cell=None):
+    """The supplier of moments rows that mesh_io.align_run asks for, on the device: the samples of both meshes are taken once (mesh_surface_samples at
+    ``spacing``) and B's grid is built once (mesh_distance_grid with ``cell``; a target of fewer than 64 triangles is searched exhaustively); a call is
+    ONE o2345_mesh_align_step over all its transforms and one read-back of [K,48] doubles."""
+    dev = va.device
+    sets = {"a": mesh_surface_samples(va, ta, spacing)[:2], "b": mesh_surface_samples(vb, tb, spacing)[:2]}
+    grid = mesh_distance_grid(vb, tb, cell) if tb.shape[0] >= _DISTANCE_EXHAUSTIVE_BELOW else None
+
+    def step(side, transforms, pivot, tau, target):
+        pts, w = sets[side]
+        T = torch.from_numpy(np.ascontiguousarray(transforms, np.float64)).to(dev)
+        rows, _ = mesh_align_step(pts, w, T, (vb, tb) if target else None, grid if target else None, tau, pivot)
+        return rows.cpu().numpy()
+    return step
+
+
+def mesh_align(va, ta, vb, tb, spacing=None, iterations=30, tol=1e-9, max_distance=None, scale=True, candidates=None, search_iterations=5, init=None,
+               cell=None):
+    """The similarity transform that moves mesh A onto mesh B, on the device -> the dict of mesh_io.align_meshes (its host twin; the loop and the 7 x 7
+    solve are mesh_io.align_run's, shared with it, over the rows of mesh_align_stepper).  va / vb fp64 [N,3], ta / tb [M,3] int32 / int64 on one device."""
+    step = mesh_align_stepper(va, ta, vb, tb, spacing, cell)
+    return mesh_io.align_run(step, iterations, tol, max_distance, scale, candidates, search_iterations, init)
+
+
+def mesh_distance(va, ta, vb, tb, spacing=None, thresholds=(), return_samples=False, cell=None, align=None):
     """Distance between mesh A (under test) and mesh B (the reference) as surfaces, on the device -> the dict of mesh_io.mesh_distance (its host twin):
     one-sided summaries "a_to_b" / "b_to_a" (mean, rms, max, within, samples, area), "chamfer", "hausdorff", "precision" / "recall" / "fscore" per
     threshold, "degenerate_targets".  va / vb fp64 [N,3], ta / tb [M,3] int32 / int64 on one device.  Per direction: samples at ``spacing``
     (mesh_surface_samples), the target's grid (mesh_distance_grid with ``cell``; a target of fewer than 64 triangles is searched exhaustively), the query,
     the summary; ONE read-back of the two stats blocks at the end (the counts of the samples and grids synchronise before it).  d2 and nearest equal the
     twin's to the last bit, the sums to 1e-12.  ``return_samples`` adds "samples": {"a", "b"} -> {"points", "weight", "triangle", "d2", "nearest"},
-    device tensors."""
+    device tensors.  ``align`` (None: nothing new is launched and the dict is as it always was): True or a dict of mesh_align arguments
+    (mesh_io.align_arguments) -- A is moved onto B first (mesh_align, mesh_transform), and "alignment" holds mesh_align's result."""
     th = mesh_io._check_thresholds(thresholds)
+    alignment = None
+    if align is not None and align is not False:
+        alignment = mesh_align(va, ta, vb, tb, cell=cell, **mesh_io.align_arguments(align, spacing))
+        va = mesh_transform(va, alignment["transform"])
     stats = _stats_block("O2345DistanceStats", va.device, 2)
     samples = {}
     for k, (name, (v, t), (tv, tt)) in enumerate((("a", (va, ta), (vb, tb)), ("b", (vb, tb), (va, ta)))):
@@ -1269,6 +1336,8 @@ def mesh_distance(va, ta, vb, tb, spacing=None, thresholds=(), return_samples=Fa
     out = mesh_io.distance_report(a_to_b, b_to_a, th, deg_a, deg_b)
     if return_samples:
         out["samples"] = samples
+    if alignment is not None:
+        out["alignment"] = alignment
     return out
 
 

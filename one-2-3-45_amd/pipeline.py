@@ -354,15 +354,30 @@ MESH_ERROR_THRESHOLDS = (0.25, 0.5, 1.0, 2.0)
 
 
 @torch.no_grad()
-def mesh_distance(a, b, spacing=None, thresholds=(), return_samples=False):
+def mesh_distance(a, b, spacing=None, thresholds=(), return_samples=False, align=None):
     """Distance between two meshes as surfaces on the device (ops.mesh_distance; definitions in mesh_io.mesh_distance, its host twin): ``a`` (the mesh
     under test) and ``b`` (the reference) are (verts [N,3], tris [M,3]) pairs of device tensors or host arrays -- host arrays are uploaded, to the device
     of the first device tensor among the four, else the current one.  -> dict(a_to_b, b_to_a: {mean, rms, max, within, samples, area}; chamfer;
-    hausdorff; thresholds, precision, recall, fscore; degenerate_targets).  ``spacing`` None: one sample per triangle."""
+    hausdorff; thresholds, precision, recall, fscore; degenerate_targets).  ``spacing`` None: one sample per triangle.  ``align`` (None: the meshes share
+    a frame; nothing else is launched and the dict is unchanged): True (an 8-azimuth search about z, then point-to-plane refinement) or a dict of
+    mesh_align's arguments -- ``a`` is moved onto ``b`` first and the dict gains "alignment", mesh_align's result."""
     dev = next((x.device for x in (*a, *b) if torch.is_tensor(x) and x.is_cuda), None)
     dev = torch.device("cuda", torch.cuda.current_device()) if dev is None else dev
     (va, ta), (vb, tb) = _device_mesh(a, dev), _device_mesh(b, dev)
-    return ops.mesh_distance(va, ta, vb, tb, spacing, thresholds, return_samples)
+    return ops.mesh_distance(va, ta, vb, tb, spacing, thresholds, return_samples, align=align)
+
+
+@torch.no_grad()
+def mesh_align(a, b, spacing=None, iterations=30, tol=1e-9, max_distance=None, scale=True, candidates=None, search_iterations=5, init=None):
+    """The similarity transform (rotation, translation, uniform scale unless ``scale`` is off) that moves mesh ``a`` onto mesh ``b``, on the device
+    (ops.mesh_align; definitions in mesh_io.align_meshes, its host twin): point-to-plane Gauss-Newton of a's surface samples against b, started from each
+    rotation of ``candidates`` ([K,3,3], e.g. mesh_io.rotation_candidates(8); None: the identity alone) after matching centroids and rms radii, the best
+    candidate after ``search_iterations`` steps refined to ``tol``.  Meshes as in mesh_distance.  -> dict(transform [4,4], scale, rotation, translation,
+    score, rms, inlier_fraction, iterations, converged, candidate, candidate_scores, history)."""
+    dev = next((x.device for x in (*a, *b) if torch.is_tensor(x) and x.is_cuda), None)
+    dev = torch.device("cuda", torch.cuda.current_device()) if dev is None else dev
+    (va, ta), (vb, tb) = _device_mesh(a, dev), _device_mesh(b, dev)
+    return ops.mesh_align(va, ta, vb, tb, spacing, iterations, tol, max_distance, scale, candidates, search_iterations, init)
 
 
 @torch.no_grad()

@@ -6,9 +6,13 @@ spacings, as pipeline.reconstruct_folder's ``mesh_error`` report takes them.
                   exhaustive query (HIP events) on all samples where one launch stays under 10 s by the rate of a 4,096-sample launch, else on that
                   sub-sample, with the grid query on the same sub-sample next to it, and the host twin's brute force on a stated sub-sample, extrapolated
   whole           ops.mesh_distance, and marching cubes + ops.mesh_distance: what ``mesh_error=True`` adds to reconstruct_folder
+  --align         instead of the above: the alignment (csrc/mesh_align.hip) of the decimated mesh A onto the plain mesh B moved by 170 degrees about z,
+                  scale 0.8, shift (0.3, -0.2, 0.1): ops.mesh_align with 8 azimuth candidates as a whole (host clock), one o2345_mesh_align_step at K = 8
+                  (the candidates' starting transforms) and at K = 1 (the result) (HIP events; the step's own check of the transforms synchronises
+                  inside), and next to each the grid query (o2345_mesh_distance_query) on the same K n moved points, with the ratio step / query
 Medians over --reps calls after --warmup calls.  Prints one JSON line.
 
-    python tools/time_mesh_distance.py [--reps 5] [--warmup 2] [--volume 128] [--grid 256] [--skip-small] [--skip-large]
+    python tools/time_mesh_distance.py [--reps 5] [--warmup 2] [--volume 128] [--grid 256] [--skip-small] [--skip-large] [--align]
 """
 import argparse
 import importlib
@@ -94,6 +98,41 @@ def pair(plain, dec, u, reps, warmup, twin_samples):
     return res
 
 
+def alignment(plain, dec, reps, warmup):
+    """A = the decimated mesh, B = the plain mesh under the large move"""
+    import numpy as np
+    (av, at), (pv, pt) = dec, plain
+    c, s = np.cos(np.deg2rad(170.0)), np.sin(np.deg2rad(170.0))
+    move = np.array([[0.8 * c, -0.8 * s, 0.0, 0.3], [0.8 * s, 0.8 * c, 0.0, -0.2], [0.0, 0.0, 0.8, 0.1]])
+    bv, bt = ops.mesh_transform(pv, move), pt
+    cand = mesh_io.rotation_candidates(8)
+    whole = lambda: ops.mesh_align(av, at, bv, bt, pipeline.MESH_ERROR_SPACING, candidates=cand)
+    res = whole()
+    out = {"source_triangles": at.shape[0], "target_triangles": bt.shape[0],
+           "result": {k: res[k] for k in ("scale", "score", "rms", "inlier_fraction", "iterations", "converged", "candidate", "candidate_scores")}}
+    out["mesh_align_ms"] = timed(whole, reps, warmup, False)
+    calls = []                                                        # the transforms of every step of one run: the first is the K = 8 start
+    step = ops.mesh_align_stepper(av, at, bv, bt, pipeline.MESH_ERROR_SPACING)
+
+    def recording(side, T, pivot, tau, target):
+        if target:
+            calls.append((T.copy(), np.array(pivot)))
+        return step(side, T, pivot, tau, target)
+    mesh_io.align_run(recording, candidates=cand)
+    out["steps_of_one_run"] = len(calls)
+    pts, w, _ = ops.mesh_surface_samples(av, at, pipeline.MESH_ERROR_SPACING)
+    grid = ops.mesh_distance_grid(bv, bt)
+    out["samples"] = pts.shape[0]
+    for name, (T, pivot) in (("k8_start", calls[0]), ("k1_result", calls[-1])):
+        Td = torch.from_numpy(np.ascontiguousarray(T)).to(pts.device)
+        moved = ops.mesh_align_step(pts, w, Td, (bv, bt), grid, None, pivot, want=("moved",))[1]["moved"].view(-1, 3).contiguous()
+        t_step = timed(lambda: ops.mesh_align_step(pts, w, Td, (bv, bt), grid, None, pivot), reps, warmup, True)
+        t_query = timed(lambda: ops.mesh_closest_triangle(moved, bv, bt, grid), reps, warmup, True)
+        out[name] = {"transforms": int(T.shape[0]), "points": moved.shape[0], "step_ms": t_step, "query_ms": t_query,
+                     "step_over_query": t_step["median_ms"] / t_query["median_ms"]}
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
@@ -102,6 +141,7 @@ def main():
     ap.add_argument("--grid", type=int, default=256)
     ap.add_argument("--skip-small", action="store_true")
     ap.add_argument("--skip-large", action="store_true")
+    ap.add_argument("--align", action="store_true")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     res = {"sources_sha": build.sources_sha(), "spacing": pipeline.MESH_ERROR_SPACING, "thresholds": list(pipeline.MESH_ERROR_THRESHOLDS)}
@@ -110,14 +150,14 @@ def main():
         S = stored_scene(dev)
         v, t, _, u = pipeline.extract_mesh(*args(S), return_index_verts=True)
         dv, dt, _, _ = pipeline.extract_mesh(*args(S), return_index_verts=True, decimate_cell=2)
-        res["small_scene_64"] = pair((v, t), (dv, dt), u, a.reps, a.warmup, twin_samples=4096)
+        res["small_scene_64"] = alignment((v, t), (dv, dt), a.reps, a.warmup) if a.align else pair((v, t), (dv, dt), u, a.reps, a.warmup, twin_samples=4096)
     if not a.skip_large:
         wt = pipeline.SceneWeights(dev, seed=0)
         inp = bench.make_inputs(dev, 8, 0, 1)
         vol = pipeline.build_volume(wt, inp["imgs"], inp["aff"], inp["origin"], a.volume, 2.0 / (a.volume - 1))
         v, t, _, u = pipeline.extract_mesh(wt, vol, inp["proj"], inp["cam_pos"], a.grid, return_index_verts=True)
         dv, dt, _, _ = pipeline.extract_mesh(wt, vol, inp["proj"], inp["cam_pos"], a.grid, return_index_verts=True, decimate_cell=2)
-        res[f"bench_scene_{a.grid}"] = pair((v, t), (dv, dt), u, a.reps, a.warmup, twin_samples=64)
+        res[f"bench_scene_{a.grid}"] = alignment((v, t), (dv, dt), a.reps, a.warmup) if a.align else pair((v, t), (dv, dt), u, a.reps, a.warmup, twin_samples=64)
     print(json.dumps(res))
 
 
