@@ -73,7 +73,7 @@ const char* o2345_last_error(void);
 /* 231 = ABI 2.3.1: o2345_mesh_raster_count, o2345_mesh_raster_emit and o2345_mesh_raster_shade_textured take the camera as o2345_camera_rays does, K_host [9]
  * and c2w_host [12], in place of sixteen float scalars at the same position; nothing else changed.
  * Additive since 2.3.1 (no existing entry changed, the version stays 231): the mesh alignment entries o2345_mesh_align_workspace_bytes,
- * o2345_mesh_align_step. */
+ * o2345_mesh_align_step; the ray cast entries o2345_mesh_ray_cast, o2345_mesh_occlusion. */
 int o2345_version(void);
 /* Layout self-description of the declared structs as THIS library was compiled (sizeof, and offsetof of every field in declaration order): a binding
  * asserts its own structs against it at load time (one-2-3-45_amd/_lib.py does) -- a field added on one side only cannot corrupt calls silently.
@@ -983,6 +983,43 @@ int o2345_mesh_raster_shade_textured(const double* verts, const void* tris, int 
                                      const float* uv, const uint8_t* image, int tex_h, int tex_w, const uint8_t* normal_image_or_null,
                                      const float* normals_or_null, const float* tangents_or_null, const float* K_host, const float* c2w_host, int H, int W,
                                      float ambient, uint8_t* kind, float* rgb, float* nrm, float* lit, long long* counters, void* stream);
+/* ---- ray cast against a mesh, and ambient occlusion (additive since 2.3.1; none in the reference: its meshes carry vertex colours only and are lit
+ * in another program) ----
+ * Read-only; equal to the host twins mesh_io.ray_cast and mesh_io.mesh_occlusion to the last bit, through a grid or without one.  Everything is fp64, one
+ * operation at a time, in the order written (csrc/mesh_raycast_math.h and csrc/mesh_intersect_math.h are the text); a dot product is (x x + y y) + z z;
+ * only comparisons decide.  verts device fp64 [nv,3], tris device int32 / int64 [nt,3] (index_bytes 4 / 8), both only read; 0 <= nv < 2^30, 3 * nt < 2^31;
+ * nt = 0 is legal (nothing is hit).  n < 2^28.
+ *   usable     a triangle takes part iff its indices lie in [0, nv), its nine coordinates are finite and n . n != 0 for n = (P1 - P0) x (P2 - P0).
+ *   hit        the segment P -> Q hits the triangle (A, B, C), corners in stored order, iff the "crossing" of the self-intersection entries above holds:
+ *              sP = orient(A,B,C,P) and sQ = orient(A,B,C,Q) strictly of opposite sign, and orient(P,Q,A,B), orient(P,Q,B,C), orient(P,Q,C,A) all > 0 or
+ *              all < 0.  A zero or a NaN anywhere: no hit.  A segment with a non-finite coordinate hits nothing.  t = sP / (sP - sQ).
+ *   nearest    the smallest t over the usable triangles that are hit, among equal t the smallest triangle index; a NaN t (overflowing determinants) never
+ *              wins.  (inf, -1) without a hit.
+ *   frame      of a direction n: len = sqrt((n_x n_x + n_y n_y) + n_z n_z); zero or not finite: no frame.  N = n / len per component; s = copysign(1, N_z);
+ *              a = -1 / (s + N_z); b = (N_x N_y) a; T = (1 + (s N_x)(N_x a), s b, -(s N_x)); B = (b, s + (N_y N_y) a, -N_y).
+ *   occlusion  of point p: n is dirs[i]; or, with owners, the face normal (P1 - P0) x (P2 - P0) of triangle owners[i], multiplied by -1 when dirs is given
+ *              too and its dot product with dirs[i] is < 0 (a zero or NaN direction turns nothing).  An owner outside [0, nt) or not usable, or a direction
+ *              without a frame, casts nothing and is counted.  P = p + bias N; Q_i = P + max_distance d_i with d_i = (x_i T + y_i B) + z_i N per
+ *              component, (x_i, y_i, z_i) row i of table (device fp64 [n_samples,3], 1 <= n_samples <= 1024: mesh_io.occlusion_directions; no sine is
+ *              evaluated on the device).  hits[i] = the number of i with any hit, int32 and exact.
+ * o2345_mesh_ray_cast: p, q device fp64 [n,3].  any_hit == 0: t device fp64 [n], tri device int32 [n] = the nearest hit.  any_hit != 0: tri[i] = 1 / 0,
+ * t is not touched and may be NULL.
+ * o2345_mesh_occlusion: points device fp64 [n,3]; dirs_or_null device fp64 [n,3]; owners_or_null device int32 [n]; one of the two at least.  max_distance
+ * finite and > 0, bias finite and >= 0.  hits device int32 [n]; counters device int64 [4], 8-byte aligned = {points with a non-finite coordinate, other
+ * points without a frame (direction or owner), rays cast, reserved}, zeroed and written by this call.  Points of the first two kinds have hits 0.
+ * grid: the grid object of o2345_mesh_distance_grid_emit over the same verts and tris, with its size and the max_cells it was built with: the segment is
+ * walked slab by slab along its dominant axis, each slab visiting the cells its part of the segment can touch, widened by 2^-30 of the coordinates; the
+ * nearest-hit walk stops at the first slab entered behind the best t, the any-hit walk at its first hit.  grid NULL: every triangle, for nt <= 2^16.  The
+ * same bytes either way and whatever the cell edge.  A segment outside the grid's box is legal.  No workspace, no host synchronisation; one lane per
+ * segment, or per (point, direction) with one ballot and one integer atomicAdd per point-row of a wave; no floating-point atomics.
+ * Limits: a segment through a shared edge or vertex of two triangles hits neither (rays leak there); the unfiltered fp64 determinants may take the wrong
+ * sign next to a degeneracy, and the t of a grazing hit is as inexact as they are (the twin computes the same one); binary visibility, no distance
+ * falloff; no all-hits list (hit parity needs de-duplicated hits). */
+int o2345_mesh_ray_cast(const double* p, const double* q, long long n, const double* verts, const void* tris, int index_bytes, long long nv, long long nt,
+                        const void* grid, size_t grid_bytes, long long max_cells, int any_hit, double* t, int* tri, void* stream);
+int o2345_mesh_occlusion(const double* points, const double* dirs_or_null, const int* owners_or_null, long long n, const double* table, int n_samples,
+                         double max_distance, double bias, const double* verts, const void* tris, int index_bytes, long long nv, long long nt, const void* grid,
+                         size_t grid_bytes, long long max_cells, int* hits, long long* counters, void* stream);
 /* Load every code object of the library on the current device now (the HIP runtime loads a translation unit's kernels at its first launch: 5 - 60 ms
  * each for the units of this library, which otherwise land inside the first calls of a fresh process).  Launches nothing that touches user memory. */
 int o2345_preload(void);

@@ -351,6 +351,44 @@ def mesh_normal_map(x=None):
     return MESH_NORMAL_MAP if x is None else bool(x)
 
 
+# ---- ambient occlusion map (csrc/mesh_raycast.hip; mesh_io.mesh_occlusion is the host twin) ---------------------------------------------------------------
+# O2345_MESH_OCCLUSION=1 makes the textured export also bake an ambient occlusion map: at every texel's point on the final mesh, the share of
+# O2345_MESH_OCCLUSION_SAMPLES cosine-weighted rays about the face normal (on the side the SDF gradient points to) that reach
+# O2345_MESH_OCCLUSION_DISTANCE index units without hitting the mesh; the .glb gains an occlusionTexture, the .obj a stem_occlusion.png ("" or "0" = off,
+# the default: nothing is launched and every file keeps its bytes).  It needs the texture atlas: with texture_texel off it is an error, not a no-op.
+# Samples: "" = 64, at most 1024.  Distance: "" = resolution / 8 index units (an eighth of the scene's box: contact shading, not sky visibility).  The rays
+# start MESH_OCCLUSION_BIAS = 1e-3 index units off the surface.
+MESH_OCCLUSION = _non_negative_int("O2345_MESH_OCCLUSION", os.environ.get("O2345_MESH_OCCLUSION", "")) != 0
+MESH_OCCLUSION_SAMPLES = _non_negative_int("O2345_MESH_OCCLUSION_SAMPLES", os.environ.get("O2345_MESH_OCCLUSION_SAMPLES", "")) or 64
+MESH_OCCLUSION_BIAS = 1e-3
+
+
+def _occlusion_distance(name, text):
+    if text.strip() == "":
+        return 0.0
+    try:
+        d = float(text)
+    except ValueError:
+        d = -1.0
+    if not (0.0 < d < float("inf")):
+        raise ValueError(f"{name} must be a finite number > 0 (index units), got {text!r}")
+    return d
+
+
+MESH_OCCLUSION_DISTANCE = _occlusion_distance("O2345_MESH_OCCLUSION_DISTANCE", os.environ.get("O2345_MESH_OCCLUSION_DISTANCE", ""))
+if not 1 <= MESH_OCCLUSION_SAMPLES <= 1024:
+    raise ValueError(f"O2345_MESH_OCCLUSION_SAMPLES must be in 1 .. 1024, got {MESH_OCCLUSION_SAMPLES}")
+
+
+def mesh_occlusion(x=None):
+    return MESH_OCCLUSION if x is None else bool(x)
+
+
+def mesh_occlusion_distance(resolution):
+    """the length of an occlusion ray in index units of a ``resolution``^3 lattice"""
+    return MESH_OCCLUSION_DISTANCE or resolution / 8.0
+
+
 # ---- mesh error report (csrc/mesh_distance.hip; mesh_io.mesh_distance is the host twin) -------------------------------------------------------------------
 # O2345_MESH_ERROR=1 makes pipeline.reconstruct_folder report how far the mesh it wrote is from the raw marching-cubes mesh it started from, as surfaces:
 # Chamfer, Hausdorff and F-score (ops.mesh_distance) in units of the extraction grid's spacing ("" or "0" = off, the default: nothing is launched and the

@@ -40,6 +40,7 @@ int preload_mesh_audit();
 int preload_mesh_fill();
 int preload_mesh_intersect();
 int preload_mesh_raster();
+int preload_mesh_raycast();
 int preload_surface_trace();
 int preload_featmaps();
 int preload_convnet();
@@ -75,6 +76,7 @@ int o2345_preload(void) {
     if ((e = o2345::preload_mesh_fill())) bad = e;
     if ((e = o2345::preload_mesh_intersect())) bad = e;
     if ((e = o2345::preload_mesh_raster())) bad = e;
+    if ((e = o2345::preload_mesh_raycast())) bad = e;
     if ((e = o2345::preload_surface_trace())) bad = e;
     if ((e = o2345::preload_featmaps())) bad = e;
     if ((e = o2345::preload_convnet())) bad = e;

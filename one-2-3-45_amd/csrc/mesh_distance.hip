@@ -31,7 +31,6 @@
 namespace o2345 {
 
 constexpr int MD_THRESHOLDS = sizeof(O2345DistanceStats::within) / sizeof(double);          // 8 (the device block of the reduction: include/o2345.h)
-constexpr int MD_AXIS = 256;                          // cells per axis at most
 constexpr int MD_RED_COLS = 3 + MD_THRESHOLDS;        // sum w, sum w d, sum w d^2, within[8]
 
 struct MdThresholds { double tau[MD_THRESHOLDS]; int n; };

@@ -1,4 +1,4 @@
-// The grid object of a target mesh (built by mesh_distance.hip, walked by its query, by mesh_align.hip and by mesh_intersect.hip): its one layout, the limit
+// The grid object of a target mesh (built by mesh_distance.hip, walked by its query, by mesh_align.hip, by mesh_intersect.hip and by mesh_raycast.hip): its one layout, the limit
 // on its cells, and the two closest-triangle searches of one point (through the grid, and over every triangle) that the distance query and the alignment
 // step share -- one text, so the step's d2 and nearest are the query's bits by construction.
 #pragma once
@@ -8,6 +8,7 @@
 namespace o2345 {
 
 constexpr long long MD_MAX_CELLS = 1ll << 24;
+constexpr int MD_AXIS = 256;                          // cells per axis at most
 constexpr long long MD_MAX_SAMPLES = 1ll << 28;
 constexpr int MD_RED_ITEMS = 16;                      // samples per thread of the fixed-order sums (k_md_reduce, k_ma_step)
 constexpr int MD_RED_TILE = 256 * MD_RED_ITEMS;
@@ -26,6 +27,32 @@ inline size_t md_grid_object(void* grid, long long max_cells, long long n_entrie
     g.cell_start = w.take<int>(max_cells + 1);
     g.entries = w.take<int>(n_entries);
     return w.bytes();
+}
+
+// what a walker that does not trust the grid reads of it (the pair test of mesh_intersect.hip, the segment walk of mesh_raycast.hip): entries and cells
+// are clamped to the sizes the caller states, so a grid of another mesh gives wrong results, not a fault
+struct MdGridView {
+    const MdGridHead* head;
+    const int *cell_start, *entries;
+    long long cap_entries, max_cells;
+};
+
+// the grid argument of an entry -> the view; grid NULL: the exhaustive path, for at most exhaustive_max triangles.  false: refused (the error is set)
+inline bool md_grid_view(const char* unit, const void* grid, size_t grid_bytes, long long max_cells, long long nt, long long exhaustive_max, MdGridView& g) {
+    g = MdGridView{};
+    if (!grid) {
+        if (nt > exhaustive_max) { set_error("%s: %lld triangles without a grid; the exhaustive path takes at most %lld", unit, nt, exhaustive_max); return false; }
+        return true;
+    }
+    if (max_cells < 1 || max_cells > MD_MAX_CELLS) { set_error("%s: a grid needs its max_cells (1 .. 2^24), got %lld", unit, max_cells); return false; }
+    MdGridObject o;
+    const size_t need = md_grid_object(const_cast<void*>(grid), max_cells, 0, o);
+    if (grid_bytes < need || ((uintptr_t)grid & 15) != 0) { set_error("%s: grid of %zu bytes (at least %zu, 16-byte aligned)", unit, grid_bytes, need); return false; }
+    const long long cap = (long long)((grid_bytes - need) / sizeof(int));
+    g.head = o.head; g.cell_start = o.cell_start; g.entries = o.entries;
+    g.cap_entries = cap < (1ll << 31) - 1 ? cap : (1ll << 31) - 1;
+    g.max_cells = max_cells;
+    return true;
 }
 
 // the corners of a triangle whose indices are in range -> true iff all nine coordinates are finite

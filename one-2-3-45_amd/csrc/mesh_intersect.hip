@@ -92,13 +92,6 @@ __global__ __launch_bounds__(256) void k_mi_faces(const double* __restrict__ ver
     wave_count(ok, &tot->n_faces);
 }
 
-// what the broad phase reads of the grid, clamped to what the caller states
-struct MiGrid {
-    const MdGridHead* head;
-    const int *cell_start, *entries;
-    long long cap_entries, max_cells;
-};
-
 // t against u > t, both taking part -> 0 nothing, 1 a candidate, 2 an intersecting pair.  HOME: the pair belongs to cell `home` only
 template <typename IDX, bool HOME>
 __device__ __forceinline__ int mi_test(const double* __restrict__ verts, int nv, const IDX* __restrict__ tris, const double* __restrict__ box, const MiFace& T,
@@ -123,7 +116,7 @@ __device__ __forceinline__ int mi_test(const double* __restrict__ verts, int nv,
 // counters; true: the pairs at their rows' cursors
 template <typename IDX, bool GRID, bool FILL>
 __global__ __launch_bounds__(256) void k_mi_pairs(const double* __restrict__ verts, int nv, const IDX* __restrict__ tris, long long nt,
-                                                  const unsigned char* __restrict__ part, const double* __restrict__ box, MiGrid g, int* __restrict__ hits,
+                                                  const unsigned char* __restrict__ part, const double* __restrict__ box, MdGridView g, int* __restrict__ hits,
                                                   int* __restrict__ first, const int* __restrict__ row_start, int* __restrict__ cursor, int* __restrict__ pairs,
                                                   long long n_pairs, MiTotals* __restrict__ tot) {
     const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -247,26 +240,8 @@ static size_t mi_carve(void* ws, long long nv, long long nt, MiCarve& c) {
     return w.bytes();
 }
 
-// the grid argument of both entries -> what the kernels read; false: refused (the error is set)
-static bool mi_grid(const char* unit, const void* grid, size_t grid_bytes, long long max_cells, long long nt, MiGrid& g) {
-    g = MiGrid{};
-    if (!grid) {
-        if (nt > MI_EXHAUSTIVE_MAX) { set_error("%s: %lld triangles without a grid; the exhaustive path takes at most 2^16", unit, nt); return false; }
-        return true;
-    }
-    if (max_cells < 1 || max_cells > MD_MAX_CELLS) { set_error("%s: a grid needs its max_cells (1 .. 2^24), got %lld", unit, max_cells); return false; }
-    MdGridObject o;
-    const size_t need = md_grid_object(const_cast<void*>(grid), max_cells, 0, o);
-    if (grid_bytes < need || ((uintptr_t)grid & 15) != 0) { set_error("%s: grid of %zu bytes (at least %zu, 16-byte aligned)", unit, grid_bytes, need); return false; }
-    const long long cap = (long long)((grid_bytes - need) / sizeof(int));
-    g.head = o.head; g.cell_start = o.cell_start; g.entries = o.entries;
-    g.cap_entries = cap < (1ll << 31) - 1 ? cap : (1ll << 31) - 1;
-    g.max_cells = max_cells;
-    return true;
-}
-
 template <bool FILL>
-static void mi_launch_pairs(const double* verts, const void* tris, int index_bytes, long long nv, long long nt, const MiGrid& g, const MiCarve& c, int* pairs,
+static void mi_launch_pairs(const double* verts, const void* tris, int index_bytes, long long nv, long long nt, const MdGridView& g, const MiCarve& c, int* pairs,
                             long long n_pairs, hipStream_t s) {
     with_index_type(index_bytes, tris, [&](auto* t) {
         using IDX = index_type<decltype(t)>;
@@ -301,8 +276,8 @@ int o2345_mesh_intersect_count(const double* verts, const void* tris, int index_
     O2345_REQUIRE(counts && (nv == 0 || verts) && (nt == 0 || tris), "mesh_intersect_count: null pointer");
     O2345_REQUIRE(((uintptr_t)counts & 7) == 0, "mesh_intersect_count: counts must be 8-byte aligned");
     O2345_REQUIRE_WORKSPACE("mesh_intersect_count", workspace, workspace_bytes, o2345_mesh_intersect_workspace_bytes(nv, nt));
-    MiGrid g;
-    if (!mi_grid("mesh_intersect_count", grid, grid_bytes, max_cells, nt, g)) return -1;
+    MdGridView g;
+    if (!md_grid_view("mesh_intersect_count", grid, grid_bytes, max_cells, nt, MI_EXHAUSTIVE_MAX, g)) return -1;
     MiCarve c;
     (void)mi_carve(workspace, nv, nt, c);
     hipStream_t s = (hipStream_t)stream;
@@ -327,8 +302,8 @@ int o2345_mesh_intersect_emit(const double* verts, const void* tris, int index_b
     O2345_REQUIRE(n_pairs >= 0 && n_pairs < MI_MAX_PAIRS && (nt > 1 || n_pairs == 0), "mesh_intersect_emit: bad pair count %lld (the limit is 2^30 - 1)", n_pairs);
     O2345_REQUIRE(workspace && (n_pairs == 0 || (pairs && verts && tris)), "mesh_intersect_emit: null pointer");
     O2345_REQUIRE(((uintptr_t)workspace & 15) == 0, "mesh_intersect_emit: workspace must be 16-byte aligned");
-    MiGrid g;
-    if (!mi_grid("mesh_intersect_emit", grid, grid_bytes, max_cells, nt, g)) return -1;
+    MdGridView g;
+    if (!md_grid_view("mesh_intersect_emit", grid, grid_bytes, max_cells, nt, MI_EXHAUSTIVE_MAX, g)) return -1;
     if (n_pairs == 0) return 0;
     MiCarve c;
     (void)mi_carve(workspace, nv, nt, c);

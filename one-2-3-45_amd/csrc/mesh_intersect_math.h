@@ -21,11 +21,19 @@ O2345_HD double mi_orient(const double (&A)[3], const double (&B)[3], const doub
 
 // the segment PQ crosses the triangle (A, B, C): P and Q strictly on opposite sides of its plane, and the three determinants around the segment all
 // > 0 or all < 0.  A zero or a NaN anywhere: no crossing.  (The last three are skipped when the first two decide: a flag, not a value, is the result.)
-O2345_HD bool mi_segment_crosses(const double (&P)[3], const double (&Q)[3], const double (&A)[3], const double (&B)[3], const double (&C)[3]) {
-    const double sP = mi_orient(A, B, C, P), sQ = mi_orient(A, B, C, Q);
+// mi_segment_hit also hands out the two plane determinants sP and sQ: the ray cast (mesh_raycast_math.h) takes its parameter from them.
+O2345_HD bool mi_segment_hit(const double (&P)[3], const double (&Q)[3], const double (&A)[3], const double (&B)[3], const double (&C)[3], double& sP,
+                             double& sQ) {
+    sP = mi_orient(A, B, C, P);
+    sQ = mi_orient(A, B, C, Q);
     if (!((sP > 0.0 && sQ < 0.0) || (sP < 0.0 && sQ > 0.0))) return false;
     const double o1 = mi_orient(P, Q, A, B), o2 = mi_orient(P, Q, B, C), o3 = mi_orient(P, Q, C, A);
     return (o1 > 0.0 && o2 > 0.0 && o3 > 0.0) || (o1 < 0.0 && o2 < 0.0 && o3 < 0.0);
+}
+
+O2345_HD bool mi_segment_crosses(const double (&P)[3], const double (&Q)[3], const double (&A)[3], const double (&B)[3], const double (&C)[3]) {
+    double sP, sQ;
+    return mi_segment_hit(P, Q, A, B, C, sP, sQ);
 }
 
 // closed boxes: lo_t <= hi_u and lo_u <= hi_t on every axis

@@ -162,7 +162,7 @@ def _host_mesh(positions, faces, colors, normals):
 _GLB_MAGIC, _GLB_JSON, _GLB_BIN = 0x46546C67, 0x4E4F534A, 0x004E4942
 
 
-def glb_json(n, m, colors, normals, pos_min, pos_max, texcoords=False, image_bytes=0, tangents=False, normal_image_bytes=0):
+def glb_json(n, m, colors, normals, pos_min, pos_max, texcoords=False, image_bytes=0, tangents=False, normal_image_bytes=0, occlusion_image_bytes=0):
     """The JSON chunk (bytes, space-padded to a multiple of 4): one buffer, views in the order indices / POSITION / COLOR_0 / NORMAL, one accessor per
     view, one mesh with one triangle primitive, one node, one scene.  Fixed key order and separators: the bytes are reproducible.
     ``texcoords`` adds TEXCOORD_0 (VEC2 float32) after NORMAL; ``image_bytes`` > 0 adds a last view without a target that holds a PNG of that many bytes,
@@ -170,9 +170,14 @@ def glb_json(n, m, colors, normals, pos_min, pos_max, texcoords=False, image_byt
     CLAMP_TO_EDGE: what texture_layout's gutters are made for); the primitive then names material 0.  Without the two the bytes are what they were.
     ``tangents`` adds TANGENT (VEC4 float32) after NORMAL; ``normal_image_bytes`` > 0 adds a second PNG view behind the first, "normalTexture": {"index":
     1} in the material and a second entry in "textures" and "images" (same sampler).  The two come together and need normals, texcoords and the first
-    image; without them the bytes are, again, what they were."""
+    image; without them the bytes are, again, what they were.
+    ``occlusion_image_bytes`` > 0 adds one more PNG view behind those, "occlusionTexture": {"index": k} as the LAST key of the material and entry k of
+    "textures" and "images" (same sampler, the base colour's TEXCOORD_0), k = 2 behind a normal map and 1 without one.  It needs texcoords and the first
+    image; without it the bytes are what they were."""
     if bool(tangents) != bool(normal_image_bytes) or (tangents and not (normals and texcoords and image_bytes)):
         raise ValueError("GLB export: a normal map is TANGENT and a second image, next to NORMAL, TEXCOORD_0 and the base colour image")
+    if occlusion_image_bytes and not (texcoords and image_bytes):
+        raise ValueError("GLB export: an occlusion map is one more image, next to TEXCOORD_0 and the base colour image")
     views, accessors, off = [], [], 0
 
     def add(nbytes, target, accessor):
@@ -201,27 +206,36 @@ def glb_json(n, m, colors, normals, pos_min, pos_max, texcoords=False, image_byt
     if normal_image_bytes:
         views.append({"buffer": 0, "byteOffset": off, "byteLength": int(normal_image_bytes)})
         off += (int(normal_image_bytes) + 3) // 4 * 4
+    if occlusion_image_bytes:
+        views.append({"buffer": 0, "byteOffset": off, "byteLength": int(occlusion_image_bytes)})
+        off += (int(occlusion_image_bytes) + 3) // 4 * 4
     doc = {"asset": {"version": "2.0", "generator": "o2345-hip"}, "scene": 0, "scenes": [{"nodes": [0]}], "nodes": [{"mesh": 0}],
            "meshes": [{"primitives": [prim]}], "accessors": accessors, "bufferViews": views,
            "buffers": [{"byteLength": off}]}
     if image_bytes:
         doc["materials"] = [{"pbrMetallicRoughness": {"baseColorTexture": {"index": 0}, "metallicFactor": 0.0, "roughnessFactor": 1.0}}]
         doc["textures"] = [{"sampler": 0, "source": 0}]
-        doc["images"] = [{"bufferView": len(views) - 1 - bool(normal_image_bytes), "mimeType": "image/png"}]
+        doc["images"] = [{"bufferView": len(views) - 1 - bool(normal_image_bytes) - bool(occlusion_image_bytes), "mimeType": "image/png"}]
         doc["samplers"] = [{"magFilter": 9729, "minFilter": 9729, "wrapS": 33071, "wrapT": 33071}]
     if normal_image_bytes:
         doc["materials"][0]["normalTexture"] = {"index": 1}
         doc["textures"].append({"sampler": 0, "source": 1})
+        doc["images"].append({"bufferView": len(views) - 1 - bool(occlusion_image_bytes), "mimeType": "image/png"})
+    if occlusion_image_bytes:
+        k = len(doc["textures"])
+        doc["materials"][0]["occlusionTexture"] = {"index": k}
+        doc["textures"].append({"sampler": 0, "source": k})
         doc["images"].append({"bufferView": len(views) - 1, "mimeType": "image/png"})
     js = json.dumps(doc, separators=(",", ":")).encode("ascii")
     return js + b" " * (-len(js) % 4)
 
 
-def write_glb_buffers(path, indices, positions, rgba, normals, bounds, uv=None, png=None, tangents=None, normal_png=None):
+def write_glb_buffers(path, indices, positions, rgba, normals, bounds, uv=None, png=None, tangents=None, normal_png=None, occlusion_png=None):
     """GLB from its buffers as they sit in the file (host arrays: indices uint32 [M,3], positions float32 [N,3], rgba uint8 [N,4] or None, normals
     float32 [N,3] or None; bounds [2,3] = per-axis min, max of positions): 12-byte header, JSON chunk, BIN chunk; every view is a multiple of 4 bytes.
     A textured file also has ``uv`` float32 [N,2] and ``png`` (the bytes of the image, zero-padded to a multiple of 4 in the file), and no ``rgba``.
-    A normal map is ``tangents`` float32 [N,4] (behind the normals, which it needs) and ``normal_png``, a second image behind the first."""
+    A normal map is ``tangents`` float32 [N,4] (behind the normals, which it needs) and ``normal_png``, a second image behind the first.
+    ``occlusion_png``: the ambient occlusion map of a textured file, one more image behind those (the material's occlusionTexture)."""
     n, m = positions.shape[0], indices.shape[0]
     if n == 0 or m == 0:
         raise ValueError("GLB export: an empty mesh has no valid glTF form (accessors need count >= 1)")
@@ -230,14 +244,18 @@ def write_glb_buffers(path, indices, positions, rgba, normals, bounds, uv=None, 
     bounds = np.asarray(bounds, np.float32).reshape(2, 3)
     if (tangents is None) != (normal_png is None) or (tangents is not None and (normals is None or uv is None)):
         raise ValueError("GLB export: a normal map is tangents and a second png, in a textured file with normals")
+    if occlusion_png is not None and uv is None:
+        raise ValueError("GLB export: an occlusion map is one more png in a textured file")
     js = glb_json(n, m, rgba is not None, normals is not None, bounds[0], bounds[1], uv is not None, 0 if png is None else len(png), tangents is not None,
-                  0 if normal_png is None else len(normal_png))
-    image, normal_image = (None if b is None else np.frombuffer(bytes(b) + b"\0" * (-len(b) % 4), np.uint8) for b in (png, normal_png))
+                  0 if normal_png is None else len(normal_png), **({} if occlusion_png is None else {"occlusion_image_bytes": len(occlusion_png)}))
+    image, normal_image, occlusion_image = (None if b is None else np.frombuffer(bytes(b) + b"\0" * (-len(b) % 4), np.uint8)
+                                            for b in (png, normal_png, occlusion_png))
     if tangents is not None:
         tangents = np.ascontiguousarray(tangents, np.float32).reshape(n, 4)
     if uv is not None:
         uv = np.ascontiguousarray(uv, np.float32).reshape(n, 2)
-    parts = [np.ascontiguousarray(a).reshape(-1).view(np.uint8) for a in (indices, positions, rgba, normals, tangents, uv, image, normal_image) if a is not None]
+    parts = [np.ascontiguousarray(a).reshape(-1).view(np.uint8) for a in (indices, positions, rgba, normals, tangents, uv, image, normal_image, occlusion_image)
+             if a is not None]
     nbin = sum(a.size for a in parts)
     assert indices.dtype.itemsize == 4 and positions.dtype == np.float32 and nbin % 4 == 0
     with open(path, "wb") as f:
@@ -274,6 +292,11 @@ def read_glb_normal_map(path):
     return _read_glb(path)[5]
 
 
+def read_glb_occlusion(path):
+    """-> the occlusion image uint8 [H,W,4] (the value in every colour channel) of a file written above with one, or None for a file without one."""
+    return _read_glb(path)[6]
+
+
 def _read_glb(path):
     raw = open(path, "rb").read()
     magic, version, total = struct.unpack_from("<III", raw, 0)
@@ -295,7 +318,7 @@ def _read_glb(path):
     prim = doc["meshes"][0]["primitives"][0]
     at = prim["attributes"]
     faces = accessor(prim["indices"]).reshape(-1, 3).astype(np.int32)
-    texture = normal_map = None
+    texture = normal_map = occlusion = None
 
     def image_of(tex):
         img = doc["images"][tex["source"]]
@@ -310,8 +333,10 @@ def _read_glb(path):
         if "normalTexture" in mat:
             assert "TANGENT" in at and "NORMAL" in at
             normal_map = (accessor(at["TANGENT"]).copy(), image_of(doc["textures"][mat["normalTexture"]["index"]]))
+        if "occlusionTexture" in mat:
+            occlusion = image_of(doc["textures"][mat["occlusionTexture"]["index"]])
     return (accessor(at["POSITION"]).copy(), faces, accessor(at["COLOR_0"]).copy() if "COLOR_0" in at else None,
-            accessor(at["NORMAL"]).copy() if "NORMAL" in at else None, texture, normal_map)
+            accessor(at["NORMAL"]).copy() if "NORMAL" in at else None, texture, normal_map, occlusion)
 
 
 def obj_coordinate_digits(bounds):
@@ -1385,10 +1410,17 @@ def obj_normal_map_name(path):
     return os.path.splitext(str(path))[0] + "_normal.png"
 
 
-def write_obj_texture_files(path, text, png, normal_png=None):
+def obj_occlusion_name(path):
+    """-> path of the occlusion map's .png next to ``path``: stem_occlusion.png"""
+    return os.path.splitext(str(path))[0] + "_occlusion.png"
+
+
+def write_obj_texture_files(path, text, png, normal_png=None, occlusion_png=None):
     """``path`` (the header + ``text``: bytes or a uint8 array), its .mtl (one material, map_Kd) and its .png.  ``normal_png``: the tangent-space normal
     map as a second file, stem_normal.png, named by a ``map_Bump`` and a ``norm`` line of the .mtl (the two spellings readers know); the "vn" records of
-    ``text`` then carry the flat normals.  An OBJ has no place for tangents: a reader derives them from the texture coordinates, the GLB is the defined form."""
+    ``text`` then carry the flat normals.  An OBJ has no place for tangents: a reader derives them from the texture coordinates, the GLB is the defined form.
+    ``occlusion_png``: the ambient occlusion map as stem_occlusion.png, named by a ``map_Ka`` line (the ambient colour's texture: an .mtl has no occlusion
+    slot, and this is the line readers map to one; the GLB is the defined form)."""
     mtl, img = obj_texture_names(path)
     with open(path, "wb") as fh:
         fh.write(obj_texture_header(path))
@@ -1399,11 +1431,16 @@ def write_obj_texture_files(path, text, png, normal_png=None):
         if normal_png is not None:
             name = os.path.basename(obj_normal_map_name(path))
             fh.write(("map_Bump %s\nnorm %s\n" % (name, name)).encode("ascii"))
+        if occlusion_png is not None:
+            fh.write(("map_Ka %s\n" % os.path.basename(obj_occlusion_name(path))).encode("ascii"))
     with open(img, "wb") as fh:
         fh.write(png)
     if normal_png is not None:
         with open(obj_normal_map_name(path), "wb") as fh:
             fh.write(normal_png)
+    if occlusion_png is not None:
+        with open(obj_occlusion_name(path), "wb") as fh:
+            fh.write(occlusion_png)
 
 
 def read_obj_normal_map(path):
@@ -1415,6 +1452,12 @@ def read_obj_normal_map(path):
         return None
     assert names["map_Bump"] == names["norm"] and len(names["norm"]) == 1
     return read_png(os.path.join(here, names["norm"][0]))
+
+
+def read_obj_occlusion(path):
+    """The occlusion map of a textured OBJ written above (its ``map_Ka`` line) -> uint8 [H,W,4], or None for a file without one."""
+    names = [l.split()[1] for l in open(obj_texture_names(path)[0], "r", encoding="ascii").read().split("\n") if l.startswith("map_Ka ")]
+    return read_png(os.path.join(os.path.dirname(str(path)), names[0])) if names else None
 
 
 def read_obj_texture(path):
@@ -1449,11 +1492,13 @@ def read_obj_texture(path):
             np.asarray(f, np.int32).reshape(-1, 3), read_png(os.path.join(here, image)))
 
 
-def write_textured(path, positions, uv, normals, image, bounds=None, png_level=1, tangents=None, normal_image=None):
+def write_textured(path, positions, uv, normals, image, bounds=None, png_level=1, tangents=None, normal_image=None, occlusion_image=None):
     """Host arrays of a textured mesh (texture_corners + pack_texture) -> ``path`` by its extension: a ``.glb`` with the PNG inside, or the ``.obj`` /
     ``.mtl`` / ``.png`` triple.  The host layer and the DEFINITION of both files; export_asset with ``texture=`` is the device path.
     ``tangents`` + ``normal_image`` (texture_frames + pack_normal_map; ``normals`` are then texture_frames' flat normals, which glTF needs beside TANGENT):
-    the normal map too -- TANGENT and a second image in the ``.glb``, ``stem_normal.png`` next to the ``.obj`` (which cannot carry the tangents)."""
+    the normal map too -- TANGENT and a second image in the ``.glb``, ``stem_normal.png`` next to the ``.obj`` (which cannot carry the tangents).
+    ``occlusion_image`` (occlusion_values through pack_texture): the occlusion map too -- one more image in the ``.glb``, ``stem_occlusion.png`` next to
+    the ``.obj``."""
     ext = _asset_ext(path)
     if ext == ".ply":
         raise ValueError("texture: a .ply has no texture coordinates; the output is .glb or .obj")
@@ -1462,12 +1507,14 @@ def write_textured(path, positions, uv, normals, image, bounds=None, png_level=1
     p = np.ascontiguousarray(positions, np.float32).reshape(-1, 3)
     png = png_bytes(image, png_level)
     normal_png = None if normal_image is None else png_bytes(normal_image, png_level)
+    occlusion_png = None if occlusion_image is None else png_bytes(occlusion_image, png_level)
     if ext == ".glb":
         idx = np.arange(p.shape[0], dtype=np.uint32).reshape(-1, 3)
         write_glb_buffers(path, idx, p, None, normals, np.stack([p.min(0), p.max(0)]) if bounds is None else bounds, uv=uv, png=png, tangents=tangents,
-                          normal_png=normal_png)
+                          normal_png=normal_png, occlusion_png=occlusion_png)
     else:
-        write_obj_texture_files(path, obj_texture_text_numpy(p, uv, normals, obj_coordinate_digits(p if bounds is None else bounds)), png, normal_png)
+        write_obj_texture_files(path, obj_texture_text_numpy(p, uv, normals, obj_coordinate_digits(p if bounds is None else bounds)), png, normal_png,
+                                occlusion_png)
 
 
 def convert_mesh(ply_path, out_path, min_component_faces=0, keep_largest=False, smooth_iterations=0, decimate_cell=0, simplify_faces=0, fill_holes=0):
@@ -1515,7 +1562,8 @@ def textured_asset_buffers(verts_idx, tris, grid_R, bound_min=(-1.0, -1.0, -1.0)
                            texture=None):
     """The device buffers of export_asset's textured branch, without a file (arguments as for export_asset; ``texture`` is required, the mesh not empty):
     the same ops calls in the same order -> dict(pos float32 [3M,3] in the asset frame, uv float32 [3M,2], image uint8 [H,W,4], idx, bounds[, nrm]; with
-    ``texture["grad"]`` nrm float32 [3M,3] (the flat normals), tan float32 [3M,4], nimage uint8 [H,W,4] and counters), all on the device.  What
+    ``texture["grad"]`` nrm float32 [3M,3] (the flat normals), tan float32 [3M,4], nimage uint8 [H,W,4] and counters; with ``texture["occlusion_hits"]``
+    oimage uint8 [H,W,4], occlusion_values in the colour atlas's own packing), all on the device.  What
     ops.mesh_raster_textured / pipeline.render_textured_mesh render; nothing synchronises."""
     from . import ops
     if texture is None or not int(verts_idx.shape[0]) or not int(tris.shape[0]):
@@ -1529,14 +1577,17 @@ def textured_asset_buffers(verts_idx, tris, grid_R, bound_min=(-1.0, -1.0, -1.0)
     if tgrad is not None:                                              # the frames of the file's own buffers; NORMAL is the flat normal beside TANGENT
         nrm, tan, counters = ops.mesh_texture_frames(pos, uv)
         nimage = ops.mesh_texture_normal_pack(tgrad, nrm, tan, m, texture["texel"], rotation=trans_mat, counters=counters)
-    out = dict(pos=pos, uv=uv, image=image, nrm=nrm, tan=tan, nimage=nimage, idx=idx, bounds=bounds, counters=counters)
+    oimage = None
+    if texture.get("occlusion_hits") is not None:
+        oimage = ops.mesh_texture_pack(ops.mesh_occlusion_values(texture["occlusion_hits"], texture["occlusion_samples"]), m, texture["texel"])
+    out = dict(pos=pos, uv=uv, image=image, nrm=nrm, tan=tan, nimage=nimage, oimage=oimage, idx=idx, bounds=bounds, counters=counters)
     return {k: t for k, t in out.items() if t is not None}
 
 
 def read_textured_glb(path):
-    """A textured ``.glb`` written by this package -> the host arrays of textured_asset_buffers: dict(pos, uv, image[, nrm, tan, nimage]).  Refused
+    """A textured ``.glb`` written by this package -> the host arrays of textured_asset_buffers: dict(pos, uv, image[, nrm, tan, nimage][, oimage]).  Refused
     (ValueError): a file without a texture, or one whose index buffer is not 0, 1, 2, ... (the textured export is unwelded)."""
-    pos, faces, _, normals, texture, normal_map = _read_glb(path)
+    pos, faces, _, normals, texture, normal_map, occlusion = _read_glb(path)
     if texture is None:
         raise ValueError(f"{path}: the file has no texture (export it with texture_texel)")
     if pos.shape[0] != 3 * faces.shape[0] or not np.array_equal(faces.reshape(-1), np.arange(pos.shape[0])):
@@ -1544,6 +1595,8 @@ def read_textured_glb(path):
     out = dict(pos=np.ascontiguousarray(pos, np.float32), uv=np.ascontiguousarray(texture[0], np.float32), image=np.ascontiguousarray(texture[1]))
     if normal_map is not None:
         out.update(nrm=np.ascontiguousarray(normals, np.float32), tan=np.ascontiguousarray(normal_map[0], np.float32), nimage=np.ascontiguousarray(normal_map[1]))
+    if occlusion is not None:
+        out.update(oimage=np.ascontiguousarray(occlusion))
     return out
 
 
@@ -1558,7 +1611,10 @@ def export_asset(path, verts_idx, tris, grid_R, bound_min=(-1.0, -1.0, -1.0), bo
     ``texture["grad"]`` (fp32 [cells c^2, 3] on the device: the raw SDF gradient at the same points): a tangent-space normal map too -- ops.mesh_texture_frames
     on the corner buffers, ops.mesh_texture_normal_pack with the 3x3 of ``trans_mat``; TANGENT and a second image in the ``.glb``, ``stem_normal.png`` next
     to the ``.obj``.  NORMAL is then the flat normal of the file's triangles whatever ``normals`` says (glTF needs NORMAL beside TANGENT, and the map is
-    relative to it); ``texture["normal_counts"]`` is set to the three counts (ops.normal_map_counts).  Still one synchronisation."""
+    relative to it); ``texture["normal_counts"]`` is set to the three counts (ops.normal_map_counts).  Still one synchronisation.
+    ``texture["occlusion_hits"]`` (int32 [cells c^2] on the device: ops.mesh_occlusion at the texel points) with ``texture["occlusion_samples"]``: the
+    ambient occlusion map too, (S - hits) / S in the atlas's own packing -- the occlusionTexture of the ``.glb``, ``stem_occlusion.png`` and a ``map_Ka``
+    line next to the ``.obj``; ``texture["occlusion_info"]`` is set to the dict of ``texture["occlusion_counts"]`` (device int64 [4]; occlusion_report).  Still one synchronisation."""
     ext = _asset_ext(path)
     if texture is not None and ext == ".ply":
         raise ValueError("texture: a .ply has no texture coordinates; the output is .glb or .obj")
@@ -1571,29 +1627,35 @@ def export_asset(path, verts_idx, tris, grid_R, bound_min=(-1.0, -1.0, -1.0), bo
         level = config.mesh_texture_png_level(png_level)
         b = textured_asset_buffers(verts_idx, tris, grid_R, bound_min, bound_max, scale_mat, trans_mat, normals, texture)
         image, pos, uv, nrm, idx, bounds = b["image"], b["pos"], b["uv"], b.get("nrm"), b["idx"], b["bounds"]
-        tan, nimage, counters = b.get("tan"), b.get("nimage"), b.get("counters")
+        tan, nimage, counters, oimage = b.get("tan"), b.get("nimage"), b.get("counters"), b.get("oimage")
         text = ops.obj_texture_text(pos, uv, nrm, bounds=bounds) if ext == ".obj" else None
         dev = dict(image=image, text=text)
         if ext == ".glb":
             dev.update(idx=idx, pos=pos, nrm=nrm, tan=tan, uv=uv, bounds=bounds)
-        dev.update(nimage=nimage, stats=texture.get("stats"), counters=counters)
+        dev.update(nimage=nimage, stats=texture.get("stats"), counters=counters, oimage=oimage, ocounts=texture.get("occlusion_counts") if oimage is not None else None)
         dev = {k: t for k, t in dev.items() if t is not None}
         host = dict(zip(dev, ops.to_host_numpy(*dev.values())))       # the one synchronisation of the whole chain
         if "stats" in host:
             ops.texture_check(host["stats"])
         if "counters" in host:
             texture["normal_counts"] = ops.normal_map_counts(host["counters"])
-        if "nimage" in host:                                          # zlib releases the interpreter lock: the two images compress side by side
+        if "ocounts" in host:
+            texture["occlusion_info"] = occlusion_report(host["ocounts"])
+        images = [host[k] for k in ("image", "nimage", "oimage") if k in host]
+        if len(images) > 1:                                           # zlib releases the interpreter lock: the images compress side by side
             from concurrent.futures import ThreadPoolExecutor
-            with ThreadPoolExecutor(max_workers=2) as pool:
-                png, normal_png = pool.map(lambda a: png_bytes(a, level), (host["image"], host["nimage"]))
+            with ThreadPoolExecutor(max_workers=len(images)) as pool:
+                pngs = list(pool.map(lambda a: png_bytes(a, level), images))
         else:
-            png, normal_png = png_bytes(host["image"], level), None
+            pngs = [png_bytes(images[0], level)]
+        png = pngs[0]
+        normal_png = pngs[1] if "nimage" in host else None
+        occlusion_png = pngs[-1] if "oimage" in host else None
         if ext == ".obj":
-            write_obj_texture_files(path, host["text"], png, normal_png)
+            write_obj_texture_files(path, host["text"], png, normal_png, occlusion_png)
         else:
             write_glb_buffers(path, host["idx"].view(np.uint32), host["pos"], None, host.get("nrm"), host["bounds"], uv=host["uv"], png=png,
-                              tangents=host.get("tan"), normal_png=normal_png)
+                              tangents=host.get("tan"), normal_png=normal_png, occlusion_png=occlusion_png)
         return 3 * m, m
     if n == 0 or m == 0:
         if ext == ".glb":
@@ -2578,3 +2640,206 @@ def mesh_intersections(verts, faces, return_pairs=False):
     if return_pairs:
         out.update(pairs_list=pairs, face_hits=face_hits)
     return out
+
+
+# ------------------------------------------------------------------------------------------------------------------ ray cast and ambient occlusion
+# the host twin of csrc/mesh_raycast.hip and the DEFINITION of its results, to the last bit (include/o2345.h has the same text; csrc/mesh_raycast_math.h
+# the device form).  All arithmetic is float64, one operation at a time, in the order written; a dot product is (x x + y y) + z z; only comparisons decide.
+OCCLUSION_COUNTS = ("bad_points", "bad_frames", "rays", "reserved")          # the counters block of o2345_mesh_occlusion, int64 [4]
+OCCLUSION_MAX_SAMPLES = 1024
+RAYCAST_EXHAUSTIVE_MAX = 2 ** 16                 # the device's exhaustive path (no grid) takes at most this many triangles
+RAYCAST_SLACK = 2.0 ** -30                       # MD_SLACK: what the device's walk, and the twin's optional box filter, widen by
+_GOLDEN = 0.6180339887498949
+
+
+def occlusion_directions(samples):
+    """The direction table of the occlusion, float64 [S,3], 1 <= S <= 1024: a cosine-weighted Fibonacci set about +z.  Entry i: r2 = (i + 0.5) / S,
+    phi = 2 pi frac(i 0.6180339887498949), (sqrt(r2) cos phi, sqrt(r2) sin phi, sqrt(1 - r2)).  Computed on the host only: the device receives the table
+    and never evaluates a sine."""
+    if isinstance(samples, (bool, np.bool_)) or not isinstance(samples, (int, np.integer)) or not 1 <= samples <= OCCLUSION_MAX_SAMPLES:
+        raise ValueError(f"mesh_occlusion: samples must be an integer in 1 .. {OCCLUSION_MAX_SAMPLES}, got {samples!r}")
+    i = np.arange(int(samples), dtype=np.float64)
+    r2 = (i + 0.5) / float(samples)
+    x = i * _GOLDEN
+    phi = (2.0 * np.pi) * (x - np.floor(x))
+    r = np.sqrt(r2)
+    return np.ascontiguousarray(np.stack([r * np.cos(phi), r * np.sin(phi), np.sqrt(1.0 - r2)], 1))
+
+
+def ray_frame(n):
+    """rc_frame on directions [..., 3] -> (T, B, N, ok): len = sqrt(n . n); ok iff len is finite and > 0; N = n / len per component; s = copysign(1, N_z);
+    a = -1 / (s + N_z); b = (N_x N_y) a; T = (1 + (s N_x)(N_x a), s b, -(s N_x)); B = (b, s + (N_y N_y) a, -N_y) (Duff et al., JCGT 2017).  Rows that are
+    not ok hold NaNs or garbage and are not to be used."""
+    n = np.asarray(n, np.float64)
+    with np.errstate(all="ignore"):
+        length = np.sqrt(_dot3(n, n))
+        ok = (length > 0.0) & np.isfinite(length)
+        N = n / length[..., None]
+        s = np.copysign(1.0, N[..., 2])
+        a = -1.0 / (s + N[..., 2])
+        b = (N[..., 0] * N[..., 1]) * a
+        T = np.stack([1.0 + (s * N[..., 0]) * (N[..., 0] * a), s * b, -(s * N[..., 0])], -1)
+        B = np.stack([b, s + (N[..., 1] * N[..., 1]) * a, -N[..., 1]], -1)
+    return T, B, N, ok
+
+
+def _raycast_mesh(verts, faces):
+    """-> (vertices float64 [N,3], faces int64 [M,3] with indices out of range replaced by 0, usable bool [M]): a triangle is usable iff its indices lie in
+    [0, N), its nine coordinates are finite and n . n != 0 (the grid's rule).  Nothing raises: the device skips the others too."""
+    p = np.ascontiguousarray(np.asarray(verts, dtype=np.float64).reshape(-1, 3))
+    f = np.asarray(faces).reshape(-1, 3).astype(np.int64)
+    inside = ((f >= 0) & (f < p.shape[0])).all(1)
+    f = np.where(inside[:, None], f, 0)
+    if p.shape[0] == 0:
+        return p, f, np.zeros(f.shape[0], bool)
+    P0, P1, P2 = p[f[:, 0]], p[f[:, 1]], p[f[:, 2]]
+    with np.errstate(all="ignore"):
+        usable = inside & np.isfinite(P0).all(1) & np.isfinite(P1).all(1) & np.isfinite(P2).all(1) & (_normal2(P0, P1, P2) != 0.0)
+    return p, f, usable
+
+
+def segment_hits(P, Q, verts, faces, any_hit=False, prefilter=False, chunk=4096):
+    """What the segments P -> Q ([n,3] each) hit on the mesh -> (t float64 [n], tri int32 [n]): the nearest hit, (inf, -1) without one; ``any_hit``: bool
+    [n] instead.  A segment hits a usable triangle (A, B, C), corners in stored order, iff segment_crosses_triangle's decisions hold: sP = orient(A,B,C,P)
+    and sQ = orient(A,B,C,Q) strictly of opposite sign, orient(P,Q,A,B), orient(P,Q,B,C), orient(P,Q,C,A) all > 0 or all < 0; a zero or a NaN anywhere is
+    no hit, so a segment through a shared edge or vertex hits neither neighbour.  A segment with a non-finite coordinate hits nothing.  t = sP / (sP - sQ);
+    the nearest hit has the smallest t, among equal t the smallest triangle index; a NaN t never wins.  Exhaustive over the triangles, vectorised over
+    chunks of segments.  ``prefilter``: only triangles whose bounding box meets the segment's, widened by 2^-30 of the largest coordinate, are tested --
+    the argument of the device's grid walk (a hit point lies in both boxes up to rounding), for inputs too large for the plain form; not the definition."""
+    p, f, usable = _raycast_mesh(verts, faces)
+    P, Q = (np.ascontiguousarray(np.asarray(x, np.float64).reshape(-1, 3)) for x in (P, Q))
+    n = P.shape[0]
+    ids = np.flatnonzero(usable)
+    A, B, C = p[f[ids, 0]], p[f[ids, 1]], p[f[ids, 2]]
+    best_t, best_tri, flags = np.full(n, np.inf), np.full(n, -1, np.int32), np.zeros(n, bool)
+    if prefilter and ids.size:
+        lo, hi = np.minimum(np.minimum(A, B), C), np.maximum(np.maximum(A, B), C)
+        scale = max(float(np.abs(lo).max()), float(np.abs(hi).max()))
+    chunk = max(1, min(int(chunk), (1 << (21 if prefilter else 18)) // max(1, ids.size)))          # the pairs of a chunk in flight
+    for k in range(0, n if ids.size else 0, chunk):
+        Pk, Qk = P[k:k + chunk], Q[k:k + chunk]
+        near = (np.isfinite(Pk).all(1) & np.isfinite(Qk).all(1))[:, None] & np.ones(ids.size, bool)[None, :]
+        if prefilter:
+            with np.errstate(all="ignore"):
+                slack = RAYCAST_SLACK * (scale + np.maximum(np.abs(Pk), np.abs(Qk)).max(1))[:, None, None]
+                near &= ((np.minimum(Pk, Qk)[:, None, :] - slack <= hi[None]) & (lo[None] <= np.maximum(Pk, Qk)[:, None, :] + slack)).all(2)
+        si, ti = np.nonzero(near)
+        sP, sQ = intersect_orient(A[ti], B[ti], C[ti], Pk[si]), intersect_orient(A[ti], B[ti], C[ti], Qk[si])
+        with np.errstate(all="ignore"):
+            sides = ((sP > 0.0) & (sQ < 0.0)) | ((sP < 0.0) & (sQ > 0.0))     # the pairs that fail here are no hits whatever the other three say
+            si, ti, sP, sQ = si[sides], ti[sides], sP[sides], sQ[sides]
+            Ps, Qs, At, Bt, Ct = Pk[si], Qk[si], A[ti], B[ti], C[ti]
+            o1, o2, o3 = intersect_orient(Ps, Qs, At, Bt), intersect_orient(Ps, Qs, Bt, Ct), intersect_orient(Ps, Qs, Ct, At)
+            hit = ((o1 > 0.0) & (o2 > 0.0) & (o3 > 0.0)) | ((o1 < 0.0) & (o2 < 0.0) & (o3 < 0.0))
+            t = sP / (sP - sQ)
+        if any_hit:
+            flags[k + si[hit]] = True
+            continue
+        good = hit & ~np.isnan(t)
+        s, tt, tr = si[good], t[good], ids[ti[good]]
+        order = np.lexsort((tr, tt, s))                                  # by segment, then t, then triangle index
+        s = s[order]
+        first = np.ones(s.size, bool)
+        first[1:] = s[1:] != s[:-1]
+        best_t[k + s[first]] = tt[order][first]
+        best_tri[k + s[first]] = tr[order][first]
+    return flags if any_hit else (best_t, best_tri)
+
+
+def _check_ray_length(what, max_distance):
+    if isinstance(max_distance, (bool, np.bool_)) or not isinstance(max_distance, (int, float, np.integer, np.floating)) or not (
+            np.isfinite(max_distance) and max_distance > 0):
+        raise ValueError(f"{what}: max_distance must be a finite float > 0, got {max_distance!r}")
+    return float(max_distance)
+
+
+def ray_cast(origins, directions, verts, faces, max_distance, any_hit=False, prefilter=False):
+    """Rays from ``origins`` along ``directions`` ([n,3] each, any length) up to ``max_distance`` direction lengths -> (distance float64 [n] in direction
+    lengths = t max_distance, inf without a hit; tri int32 [n], -1 without a hit); ``any_hit``: bool [n].  The segment is P = origin, Q = origin +
+    max_distance direction per component (segment_hits has the rules).  The twin of ops.mesh_ray_cast, and its definition."""
+    L = _check_ray_length("mesh_ray_cast", max_distance)
+    P = np.asarray(origins, np.float64).reshape(-1, 3)
+    with np.errstate(all="ignore"):
+        Q = P + L * np.asarray(directions, np.float64).reshape(-1, 3)
+        out = segment_hits(P, Q, verts, faces, any_hit, prefilter)
+        return out if any_hit else (out[0] * L, out[1])
+
+
+def occlusion_defaults(lo, hi, max_distance=None, bias=None):
+    """(max_distance, bias) of an occlusion call over a mesh whose vertices span [lo, hi]: None -> the box's diagonal sqrt((dx dx + dy dy) + dz dz) (no ray
+    ends inside the mesh's extent) and 1e-6 of it; both checked (max_distance finite and > 0, bias finite and >= 0)."""
+    d = [float(b) - float(a) for a, b in zip(lo, hi)]
+    diagonal = float(np.sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]))
+    L = _check_ray_length("mesh_occlusion", diagonal if max_distance is None and diagonal > 0 else (1.0 if max_distance is None else max_distance))
+    if bias is None:
+        bias = 1e-6 * L
+    if isinstance(bias, (bool, np.bool_)) or not isinstance(bias, (int, float, np.integer, np.floating)) or not (np.isfinite(bias) and bias >= 0):
+        raise ValueError(f"mesh_occlusion: bias must be a finite float >= 0, got {bias!r}")
+    return L, float(bias)
+
+
+def occlusion_rays(points, T, B, N, table, max_distance, bias):
+    """rc_occlusion_ray: points and their frames [n,3], the table [S,3] -> (P [n,3], Q [n,S,3]): P = p + bias N, d_i = (x_i T + y_i B) + z_i N,
+    Q_i = P + max_distance d_i, per component"""
+    with np.errstate(all="ignore"):
+        P = points + bias * N
+        d = (table[None, :, 0, None] * T[:, None, :] + table[None, :, 1, None] * B[:, None, :]) + table[None, :, 2, None] * N[:, None, :]
+        return P, P[:, None, :] + max_distance * d
+
+
+def occlusion_report(counts):
+    """The four counters of OCCLUSION_COUNTS, in order -> the dict both mesh_occlusion and ops.mesh_occlusion return (without the reserved entry)"""
+    return {k: int(x) for k, x in zip(OCCLUSION_COUNTS[:3], counts)}
+
+
+def mesh_occlusion(points, verts, faces, normals=None, owners=None, samples=64, max_distance=None, bias=None, prefilter=False):
+    """Ambient occlusion of ``points`` [n,3] against the mesh on the host (the twin of ops.mesh_occlusion, and the definition of its result) -> (hits
+    int32 [n], counts dict).  The direction n of a point: ``normals`` [n,3] alone; or with ``owners`` int [n] the face normal (P1 - P0) x (P2 - P0) of
+    that triangle in stored order, multiplied by -1 when ``normals`` is given too and its dot product with the given direction is < 0 (a zero or NaN
+    direction turns nothing).  An owner outside [0, M) or an unusable owner triangle, or a direction without a frame (ray_frame), casts nothing: hits 0,
+    counted as bad_frames; a point with a non-finite coordinate likewise, counted as bad_points.  Otherwise P = p + bias N and Q_i = P + max_distance d_i
+    with d_i = (x_i T + y_i B) + z_i N per component over occlusion_directions(samples); hits = the number of i whose segment hits anything
+    (segment_hits); counts["rays"] = samples times the points that cast.  The exposure of a point is (S - hits) / S (occlusion_values).  Defaults:
+    occlusion_defaults over all vertices.  Binary visibility, no distance falloff; face normals give faceted values on a coarse mesh."""
+    if normals is None and owners is None:
+        raise ValueError("mesh_occlusion: a point needs a direction (normals) or an owner triangle (owners)")
+    table = occlusion_directions(samples)
+    p, f, usable = _raycast_mesh(verts, faces)
+    pts = np.ascontiguousarray(np.asarray(points, np.float64).reshape(-1, 3))
+    n, S = pts.shape[0], table.shape[0]
+    finite_v = p[np.isfinite(p).all(1)]
+    L, bias = occlusion_defaults(*((finite_v.min(0), finite_v.max(0)) if finite_v.size else ((0, 0, 0), (0, 0, 0))), max_distance, bias)
+    bad_point = ~np.isfinite(pts).all(1)
+    with np.errstate(all="ignore"):
+        if owners is not None:
+            o = np.asarray(owners).reshape(-1).astype(np.int64)
+            ok = (o >= 0) & (o < f.shape[0])
+            o = np.where(ok, o, 0)
+            ok &= usable[o] if f.shape[0] else False
+            fo = f[o] if f.shape[0] else np.zeros((n, 3), np.int64)
+            P0, P1, P2 = (p[fo[:, k]] if p.shape[0] else np.zeros((n, 3)) for k in range(3))
+            e1, e2 = P1 - P0, P2 - P0
+            nrm = np.stack([e1[:, 1] * e2[:, 2] - e1[:, 2] * e2[:, 1], e1[:, 2] * e2[:, 0] - e1[:, 0] * e2[:, 2], e1[:, 0] * e2[:, 1] - e1[:, 1] * e2[:, 0]], 1)
+            if normals is not None:
+                nrm = np.where((_dot3(nrm, np.asarray(normals, np.float64).reshape(-1, 3)) < 0.0)[:, None], -nrm, nrm)
+        else:
+            nrm, ok = np.asarray(normals, np.float64).reshape(-1, 3), np.ones(n, bool)
+        T, B, N, framed = ray_frame(nrm)
+        cast = ~bad_point & ok & framed
+        hits = np.zeros(n, np.int32)
+        who = np.flatnonzero(cast)
+        step = max(1, 65536 // S)
+        for k in range(0, who.size, step):
+            w = who[k:k + step]
+            P, Q = occlusion_rays(pts[w], T[w], B[w], N[w], table, L, bias)
+            flags = segment_hits(np.broadcast_to(P[:, None, :], Q.shape).reshape(-1, 3), Q.reshape(-1, 3), p, np.where(usable[:, None], f, -1), True, prefilter)
+            hits[w] = flags.reshape(-1, S).sum(1)
+    counts = occlusion_report((np.count_nonzero(bad_point), np.count_nonzero(~bad_point & ~(ok & framed)), S * who.size))
+    return hits, counts
+
+
+def occlusion_values(hits, samples):
+    """hits int [n] of ``samples`` rays -> the exposure float32 [n,3]: float32((S - hits) / S) in every channel, what pack_texture turns into the occlusion
+    image (1 = open, 0 = closed; glTF reads the red channel)."""
+    v = ((float(samples) - np.asarray(hits, np.float64)) / float(samples)).astype(np.float32)
+    return np.ascontiguousarray(np.repeat(v.reshape(-1, 1), 3, 1))

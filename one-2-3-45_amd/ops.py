@@ -1433,6 +1433,91 @@ def mesh_intersections(verts, tris, return_pairs=False, cell=None, grid=True):
     return out
 
 
+# ---------------------------------------------------------------------------------------------------------- ray cast and ambient occlusion
+def _raycast_grid(verts, tris, grid):
+    """The grid argument of the two ray cast calls -> (buffer, bytes, max_cells, the mesh has no triangle with an area): a MeshGrid of the same mesh as it is; None: ops.mesh_distance_grid
+    unless the mesh is tiny (fewer than 64 triangles) or has no triangle with an area; False: the exhaustive path (at most 2^16 triangles)."""
+    if grid is None and tris.shape[0] >= _DISTANCE_EXHAUSTIVE_BELOW:
+        try:
+            grid = mesh_distance_grid(verts, tris)
+        except RuntimeError as e:
+            if "no triangle with an area" not in str(e):
+                raise
+            return None, 0, 0, True                                       # nothing can be hit
+    return (grid.buffer, grid.buffer.numel(), grid.max_cells, False) if grid else (None, 0, 0, False)
+
+
+@_on_device
+def mesh_ray_cast(origins, directions, verts, tris, max_distance, grid=None, any_hit=False):
+    """What rays hit on a mesh, on the device (== mesh_io.ray_cast, its host twin and the definition, to the last bit; csrc/mesh_raycast.hip).  origins,
+    directions fp64 [n,3] (directions of any length), verts fp64 [N,3], tris [M,3] int32 / int64, all only read; the segment of ray i ends at origin +
+    max_distance direction -> (distance fp64 [n] in direction lengths, inf without a hit; tri int32 [n], -1 without a hit), the nearest hit; ``any_hit``:
+    bool [n] instead.  ``grid``: a MeshGrid of the same mesh (ops.mesh_distance_grid), None to build one (a mesh of fewer than 64 triangles is searched
+    exhaustively), False for the exhaustive search (at most 2^16 triangles) -- the same result either way.  A ray through a shared edge or vertex hits
+    neither neighbour.  The grid's count synchronises once; the cast itself does not."""
+    L = mesh_io._check_ray_length("mesh_ray_cast", max_distance)
+    tris, ib = _triangles(tris, "mesh_ray_cast")
+    for x in (verts, origins, directions):
+        _vertices(x, "mesh_ray_cast")
+    if origins.shape != directions.shape:
+        raise ValueError(f"mesh_ray_cast: {origins.shape[0]} origins and {directions.shape[0]} directions")
+    n, dev = origins.shape[0], origins.device
+    gp, gb, gm, empty = _raycast_grid(verts, tris, grid)
+    t = None if any_hit else torch.empty(n, dtype=torch.float64, device=dev)
+    tri = torch.empty(n, dtype=torch.int32, device=dev)
+    call("o2345_mesh_ray_cast", origins, (origins + L * directions).contiguous(), n, verts, tris, ib, verts.shape[0], 0 if empty else tris.shape[0], gp, gb, gm,
+         1 if any_hit else 0, t, tri)                                     # empty: no triangle has an area, nothing is hit
+    return tri != 0 if any_hit else (t * L, tri)
+
+
+def _occlusion_table(samples, dev):
+    return torch.from_numpy(mesh_io.occlusion_directions(samples)).to(dev)
+
+
+@_on_device
+def mesh_occlusion(points, verts, tris, normals=None, owners=None, samples=64, max_distance=None, bias=None, grid=None, counters=None, validate=True):
+    """Ambient occlusion of points against a mesh on the device (== mesh_io.mesh_occlusion, its host twin and the definition, to the last bit;
+    csrc/mesh_raycast.hip): how many of ``samples`` cosine-weighted rays about the normal of each point are blocked within ``max_distance``.  points fp64
+    [n,3]; the normal is ``normals`` fp64 [n,3], or the face normal of triangle ``owners`` int32 [n], turned to the side of ``normals`` when both are
+    given -> (hits int32 [n], counts {"bad_points", "bad_frames", "rays"}); the exposure is (samples - hits) / samples (ops.mesh_occlusion_values).
+    Defaults (mesh_io.occlusion_defaults): max_distance the diagonal of the vertices' box, bias 1e-6 of it; they read the box back (one synchronisation
+    more).  ``grid`` as for ops.mesh_ray_cast.  ``validate=False`` returns the device counters int64 [4] in place of the dict and does not wait
+    (mesh_io.occlusion_report reads them)."""
+    if normals is None and owners is None:
+        raise ValueError("mesh_occlusion: a point needs a direction (normals) or an owner triangle (owners)")
+    tris, ib = _triangles(tris, "mesh_occlusion")
+    for x in (verts, points) + (() if normals is None else (normals,)):
+        _vertices(x, "mesh_occlusion")
+    n, dev = points.shape[0], points.device
+    if normals is not None and normals.shape[0] != n:
+        raise ValueError(f"mesh_occlusion: {n} points and {normals.shape[0]} normals")
+    if owners is not None and (owners.dtype != torch.int32 or tuple(owners.shape) != (n,)):
+        raise ValueError(f"mesh_occlusion: expected owners int32 [{n}], got {tuple(owners.shape)} {owners.dtype}")
+    table = _occlusion_table(samples, dev)
+    if max_distance is None or bias is None:
+        ok = torch.isfinite(verts).all(1)
+        box = torch.stack([verts[ok].amin(0), verts[ok].amax(0)]).tolist() if bool(ok.any()) else [[0.0] * 3] * 2
+        max_distance, bias = mesh_io.occlusion_defaults(box[0], box[1], max_distance, bias)
+    else:
+        max_distance, bias = mesh_io.occlusion_defaults((0, 0, 0), (0, 0, 0), max_distance, bias)
+    gp, gb, gm, empty = _raycast_grid(verts, tris, grid)
+    hits = torch.empty(n, dtype=torch.int32, device=dev)
+    if counters is None:
+        counters = torch.empty(len(mesh_io.OCCLUSION_COUNTS), dtype=torch.int64, device=dev)
+    if empty:
+        tris = tris[:0]                                                   # no triangle has an area: nothing is hit, and every owner is unusable
+    call("o2345_mesh_occlusion", points, normals, owners, n, table, table.shape[0], max_distance, bias, verts, tris, ib, verts.shape[0], tris.shape[0], gp, gb, gm,
+         hits, counters)
+    return hits, (mesh_io.occlusion_report(counters.tolist()) if validate else counters)
+
+
+def mesh_occlusion_values(hits, samples):
+    """hits int32 [n] of ``samples`` rays, on the device -> the exposure fp32 [n,3] (== mesh_io.occlusion_values, exactly): float32((S - hits) / S) in every
+    channel, what ops.mesh_texture_pack turns into the occlusion image"""
+    v = ((float(samples) - hits.to(torch.float64)) / float(samples)).to(torch.float32)
+    return v.reshape(-1, 1).expand(-1, 3).contiguous()
+
+
 # ---------------------------------------------------------------------------------------------------------- texture atlas
 # ---------------------------------------------------------------------------------------------------------- hole filling
 @_on_device

@@ -236,7 +236,7 @@ def _extraction_lattice(wt, vol, resolution):
 MeshFields = namedtuple("MeshFields", "verts verts_idx tris rgb u grad info texture")
 
 
-def _mesh_fields(wt, vol, proj, cam_pos, resolution, opts, fill_holes=0, normal_map=False):
+def _mesh_fields(wt, vol, proj, cam_pos, resolution, opts, fill_holes=0, normal_map=False, ambient_occlusion=False):
     """The device work of extract_mesh, once -> MeshFields; ``opts``: a config.MeshOptions.  Marching cubes, then the clean-up chain (ops.mesh_cleanup),
     then gradient and colours at the resulting vertices: the asset export reuses that gradient, the colour network's normal input, for NORMAL.
     ``texture_texel`` = c in [4, 64]: ``texture`` is the baked atlas -- "rgb", the colour network at the surface point of every texel
@@ -251,9 +251,17 @@ def _mesh_fields(wt, vol, proj, cam_pos, resolution, opts, fill_holes=0, normal_
     any other; ``info`` gains "fill", the counts of ops.mesh_fill_holes.  A filled rim is no boundary any more: the smoothing's pinning does not hold it.
     ``normal_map`` (a keyword of its own too; it needs ``texture_texel``): ``texture`` keeps "grad", the SDF gradient at the texel points -- the second
     result of the colour call that bakes the atlas, thrown away otherwise -- from which mesh_io.export_asset bakes the tangent-space normal map.  Nothing
-    more is evaluated; the frames come from the exported (smoothed) positions, the gradients from the unsmoothed surface points."""
+    more is evaluated; the frames come from the exported (smoothed) positions, the gradients from the unsmoothed surface points.
+    ``ambient_occlusion`` (a keyword of its own too; it needs ``texture_texel``): ``texture`` gains "occlusion_hits" int32 [cells c^2], "occlusion_samples"
+    and "occlusion_counts" (device int64 [4]; mesh_io.export_asset reads them with its one copy into "occlusion_info") -- ops.mesh_occlusion at the texel points ON
+    THE MESH, ops.mesh_texture_points' points before any projection (a projected point may lie under its own triangle), against the final unsmoothed
+    mesh, about the face normal of the texel's owner triangle (mesh_io._texel_owners) on the side of the texel gradient the colour call returns anyway:
+    that settles the side whatever the winding.  Samples, ray length and bias from config (64, resolution / 8 and 1e-3 index units).  No synchronisation
+    beyond the grid's count."""
     if normal_map and not opts.texture_texel:
         raise ValueError("normal_map: the normal map belongs to the texture atlas; set texture_texel")
+    if ambient_occlusion and not opts.texture_texel:
+        raise ValueError("ambient_occlusion: the occlusion map belongs to the texture atlas; set texture_texel")
     prec = wt.sdf_precision
     # build_volume's pair: ops.scatter_dense writes zeros into vol_cl wherever maskvol is zero, which is what the sparse lattice evaluation needs (a
     # hand-made ``vol`` must keep that: points without a kept corner voxel get the empty scene's value from the second extraction on)
@@ -270,7 +278,7 @@ def _mesh_fields(wt, vol, proj, cam_pos, resolution, opts, fill_holes=0, normal_
     texture = None
     if opts.texture_texel and tris.shape[0]:
         tpts, tworld, tstats = ops.mesh_texture_points(verts_idx, tris, opts.texture_texel, resolution, validate=False)
-        tpro = None
+        tpro, on_mesh = None, tpts
         if opts.project_iterations:
             tpts, tpro = ops.mesh_project(wt.sdf_blob, vol["vol_cl"], tpts, resolution, opts.project_iterations, max_move=opts.project_max_move, precision=prec)
             tworld = _index_to_world(tpts, resolution).to(torch.float32).contiguous()
@@ -278,6 +286,11 @@ def _mesh_fields(wt, vol, proj, cam_pos, resolution, opts, fill_holes=0, normal_
         texture = dict(texel=opts.texture_texel, rgb=trgb, stats=tstats, project=tpro, layout=ops.mesh_io.texture_layout(tris.shape[0], opts.texture_texel))
         if normal_map:
             texture["grad"] = tgrad
+        if ambient_occlusion:
+            owners = torch.from_numpy(ops.mesh_io._texel_owners(texture["layout"], tris.shape[0]).reshape(-1).astype(np.int32)).to(on_mesh.device)
+            hits, counts = ops.mesh_occlusion(on_mesh, verts_idx, tris, normals=tgrad.to(torch.float64), owners=owners, samples=config.MESH_OCCLUSION_SAMPLES,
+                                              max_distance=config.mesh_occlusion_distance(resolution), bias=config.MESH_OCCLUSION_BIAS, validate=False)
+            texture.update(occlusion_hits=hits, occlusion_samples=config.MESH_OCCLUSION_SAMPLES, occlusion_counts=counts)
     if opts.smooth_iterations:
         verts_idx = ops.mesh_smooth(verts_idx, tris, opts.smooth_iterations)
         verts = _index_to_world(verts_idx, resolution)
@@ -285,9 +298,12 @@ def _mesh_fields(wt, vol, proj, cam_pos, resolution, opts, fill_holes=0, normal_
 
 
 def _texture_block(texture):
-    """-> the "texture" entry of a result dict: {width, height, texel, texels} or None; with a normal map also "normal_map": True (a result without one
-    keeps the keys it had)"""
-    return dict({k: texture["layout"][k] for k in ("width", "height", "texel", "texels")}, **({"normal_map": True} if "grad" in texture else {})) if texture else None
+    """-> the "texture" entry of a result dict: {width, height, texel, texels} or None; with a normal map also "normal_map": True, with an occlusion map
+    "occlusion": True (a result without them keeps the keys it had)"""
+    if not texture:
+        return None
+    return dict({k: texture["layout"][k] for k in ("width", "height", "texel", "texels")}, **({"normal_map": True} if "grad" in texture else {}),
+                **({"occlusion": True} if "occlusion_hits" in texture else {}))
 
 
 @torch.no_grad()
@@ -317,7 +333,7 @@ def export_mesh_ply(path, wt, vol, proj, cam_pos, resolution, scale_mat=None, tr
 @torch.no_grad()
 def export_mesh_asset(path, wt, vol, proj, cam_pos, resolution, scale_mat=None, trans_mat=None, normals=False, min_component_faces=None, keep_largest=None,
                       smooth_iterations=None, decimate_cell=None, project_iterations=None, texture_texel=None, simplify_faces=None, fill_holes=None,
-                      normal_map=None):
+                      normal_map=None, ambient_occlusion=None):
     """export_mesh_ply followed by convert_mesh_format (utils/utils.py:31-47) without the PLY in between: the coloured mesh as ``.glb`` or ``.obj`` in the
     asset frame ((x, y, z) -> (x, z, y), faces reversed), buffers / text packed on the device (csrc/mesh_export.hip).  ``normals=True`` adds unit vertex
     normals from the SDF gradient the vertex colouring already computed (at the unsmoothed vertices when ``smooth_iterations`` is on, at the projected ones
@@ -328,12 +344,16 @@ def export_mesh_asset(path, wt, vol, proj, cam_pos, resolution, scale_mat=None, 
     extract_mesh's.  ``normal_map`` (None: the config default O2345_MESH_NORMAL_MAP, off: nothing is launched and the file keeps its bytes): the textured
     asset also carries a tangent-space normal map baked from the SDF gradient at the texel points (mesh_io.export_asset, ``texture["grad"]``), so that a
     decimated or simplified mesh is lit like the full surface; NORMAL is then the flat face normal whatever ``normals`` says.  With ``texture_texel`` off
-    it raises ValueError."""
+    it raises ValueError.  ``ambient_occlusion`` (None: the config default O2345_MESH_OCCLUSION, off: nothing is launched and the file keeps its bytes): the
+    textured asset also carries an ambient occlusion map baked by ray casting against the final mesh (_mesh_fields; csrc/mesh_raycast.hip), the
+    occlusionTexture of the ``.glb`` and ``stem_occlusion.png`` next to the ``.obj``, so that a decimated mesh keeps the contact shading of its
+    concavities.  With ``texture_texel`` off it raises ValueError."""
     from . import mesh_io
     opts = config.mesh_options(min_component_faces, keep_largest, decimate_cell, project_iterations, smooth_iterations, texture_texel, simplify_faces)
     if opts.texture_texel and mesh_io._asset_ext(path) == ".ply":
         raise ValueError("texture: a .ply has no texture coordinates; the output is .glb or .obj")
-    m = _mesh_fields(wt, vol, proj, cam_pos, resolution, opts, fill_holes=config.mesh_fill_holes(fill_holes), normal_map=config.mesh_normal_map(normal_map))
+    m = _mesh_fields(wt, vol, proj, cam_pos, resolution, opts, fill_holes=config.mesh_fill_holes(fill_holes), normal_map=config.mesh_normal_map(normal_map),
+                     ambient_occlusion=config.mesh_occlusion(ambient_occlusion))
     return mesh_io.export_asset(path, m.verts_idx, m.tris, resolution, scale_mat=scale_mat, trans_mat=trans_mat,
                                 vertex_colors=m.rgb if m.verts_idx.shape[0] else None, normals=m.grad if normals else None, texture=m.texture)
 
@@ -400,6 +420,54 @@ def mesh_intersections(mesh, return_pairs=False):
     dev = next((x.device for x in mesh if torch.is_tensor(x) and x.is_cuda), None)
     dev = torch.device("cuda", torch.cuda.current_device()) if dev is None else dev
     return ops.mesh_intersections(*_device_mesh(mesh, dev), return_pairs)
+
+
+def _mesh_device(mesh):
+    dev = next((x.device for x in mesh if torch.is_tensor(x) and x.is_cuda), None)
+    return torch.device("cuda", torch.cuda.current_device()) if dev is None else dev
+
+
+def _device_points(x, dev):
+    x = x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(np.asarray(x, np.float64).reshape(-1, 3)))
+    return x.to(dev, torch.float64).contiguous()
+
+
+@torch.no_grad()
+def mesh_ray_cast(mesh, origins, directions, max_distance, any_hit=False):
+    """What rays hit on a mesh, on the device (ops.mesh_ray_cast; definitions in mesh_io.ray_cast, its host twin): ``mesh`` is a (verts [N,3], tris [M,3])
+    pair, ``origins`` and ``directions`` [n,3], device tensors or host arrays -- host arrays are uploaded, to the device of the first device tensor of
+    the pair, else the current one.  -> (distance fp64 [n] in direction lengths up to ``max_distance``, inf without a hit; tri int32 [n], -1 without a
+    hit) on the device; ``any_hit``: bool [n]."""
+    dev = _mesh_device(mesh)
+    return ops.mesh_ray_cast(_device_points(origins, dev), _device_points(directions, dev), *_device_mesh(mesh, dev), max_distance, any_hit=any_hit)
+
+
+@torch.no_grad()
+def mesh_occlusion(mesh, samples=64, max_distance=None, bias=None, spacing=None, flip=False):
+    """Ambient occlusion of a mesh against itself on the device (ops.mesh_occlusion; definitions in mesh_io.mesh_occlusion, its host twin), per face:
+    ``mesh`` as in mesh_ray_cast.  The points are the triangle-major surface samples of ops.mesh_surface_samples at ``spacing`` (None: one per triangle,
+    at the centroid), each about the face normal of its own triangle in stored order (``flip``: about its negative, for a mesh wound the other way).
+    -> dict(exposure fp64 [M]: the mean of (samples - hits) / samples over a face's points, NaN for a face without a point; hits int32 [n], triangle
+    int32 [n], points fp64 [n,3], on the device; mean: the area-weighted mean exposure; counts: {"bad_points", "bad_frames", "rays"}; samples,
+    max_distance and bias as used)."""
+    dev = _mesh_device(mesh)
+    v, t = _device_mesh(mesh, dev)
+    points, weight, triangle = ops.mesh_surface_samples(v, t, spacing)
+    normals = None
+    if flip:
+        P = v[t.long()[triangle.long()]]                                  # [n,3 corners,3]
+        normals = -torch.linalg.cross(P[:, 1] - P[:, 0], P[:, 2] - P[:, 0])
+    ok = torch.isfinite(v).all(1)
+    box = torch.stack([v[ok].amin(0), v[ok].amax(0)]).tolist() if bool(ok.any()) else [[0.0] * 3] * 2
+    max_distance, bias = ops.mesh_io.occlusion_defaults(box[0], box[1], max_distance, bias)
+    hits, counts = ops.mesh_occlusion(points, v, t, normals=normals, owners=triangle, samples=samples, max_distance=max_distance, bias=bias)
+    value = (float(samples) - hits.to(torch.float64)) / float(samples)
+    M = t.shape[0]
+    total = torch.zeros(M, dtype=torch.float64, device=dev).index_add_(0, triangle.long(), value)
+    count = torch.zeros(M, dtype=torch.float64, device=dev).index_add_(0, triangle.long(), torch.ones_like(value))
+    wsum = float(weight.sum())
+    return dict(exposure=total / count, hits=hits, triangle=triangle, points=points, mean=float((weight * value).sum()) / wsum if wsum > 0 else float("nan"),
+                counts=counts, samples=int(samples), max_distance=max_distance, bias=bias)
 
 
 def _surface_view(wt, vol, proj, cam_pos, u, flags, intrinsic, c2w, H, W, near, far, stride, refine, background):
@@ -617,7 +685,7 @@ def _write_previews(wt, vol, proj, cam_pos, u, s, n, folder):
 def reconstruct_folder(root_dir, name, wt, out_ply, D=96, resolution=256, render_val_image=False, output_format=None, min_component_faces=None,
                        keep_largest=None, smooth_iterations=None, decimate_cell=None, project_iterations=None, texture_texel=None, preview_views=None, mesh_error=None,
                        simplify_faces=None, mesh_audit=None, fill_holes=None, mesh_intersections=None, mesh_preview_views=None, normal_map=None,
-                       textured_preview_views=None):
+                       textured_preview_views=None, ambient_occlusion=None):
     """run.py's reconstruction stage without the reference tree: Zero123-style folder (dataset.SceneFolder) -> coloured mesh (binary PLY in
     the original frame), optionally the val image of the target view.  ``output_format`` ".obj" / ".glb" (run.py --output_format) also writes
     ``mesh<ext>`` next to ``out_ply`` in the asset frame, from the same device buffers.  The mesh options are extract_mesh's.  Returns
@@ -648,6 +716,9 @@ def reconstruct_folder(root_dir, name, wt, out_ply, D=96, resolution=256, render
     ``normal_map`` (None: the config default O2345_MESH_NORMAL_MAP, off: nothing is launched and every file keeps its bytes): export_mesh_asset's
     tangent-space normal map for the textured ``output_format`` asset; the result's "texture" block then has "normal_map": True.  With ``texture_texel`` off it
     raises ValueError.
+    ``ambient_occlusion`` (None: the config default O2345_MESH_OCCLUSION, off: nothing is launched and every file keeps its bytes): export_mesh_asset's
+    ambient occlusion map for the textured ``output_format`` asset; the result's "texture" block then has "occlusion": True.  With ``texture_texel`` off it
+    raises ValueError.
     ``textured_preview_views`` (None: the config default O2345_TEXTURED_PREVIEW_VIEWS, 0 = off: nothing is launched, the result gains no key and every file
     keeps its bytes) = n >= 1: n views of the TEXTURED asset as a viewer shows it (render_textured_mesh on the buffers the file is written from: the atlas,
     and with ``normal_map`` the normal map) from the cameras of ``preview_views`` mapped into the asset's frame (raster.asset_camera), written as
@@ -661,6 +732,9 @@ def reconstruct_folder(root_dir, name, wt, out_ply, D=96, resolution=256, render
     nmap = config.mesh_normal_map(normal_map)
     if nmap and not config.mesh_texture_texel(texture_texel):
         raise ValueError("normal_map: the normal map belongs to the texture atlas; set texture_texel")
+    occlusion = config.mesh_occlusion(ambient_occlusion)
+    if occlusion and not config.mesh_texture_texel(texture_texel):
+        raise ValueError("ambient_occlusion: the occlusion map belongs to the texture atlas; set texture_texel")
     textured_previews = config.textured_preview_views(textured_preview_views)
     if textured_previews and not (config.mesh_texture_texel(texture_texel) and output_format in (".obj", ".glb")):
         raise ValueError("textured_preview_views: the textured previews show the textured asset; set texture_texel and output_format '.glb' or '.obj'")
@@ -673,7 +747,8 @@ def reconstruct_folder(root_dir, name, wt, out_ply, D=96, resolution=256, render
     previews = config.preview_views(preview_views)
     fill = config.mesh_fill_holes(fill_holes)
     asset = output_format in (".obj", ".glb")
-    m = _mesh_fields(wt, vol, proj, cam_pos, resolution, opts if asset else opts._replace(texture_texel=0), fill_holes=fill, normal_map=nmap and asset)   # the atlas is for the asset only
+    m = _mesh_fields(wt, vol, proj, cam_pos, resolution, opts if asset else opts._replace(texture_texel=0), fill_holes=fill, normal_map=nmap and asset,
+                     ambient_occlusion=occlusion and asset)                # the atlas is for the asset only
     rgb = m.rgb if m.verts_idx.shape[0] else None
     nv, nt = mesh_io.export_mesh(out_ply, m.verts_idx, m.tris, resolution, scale_mat=s["scale_mat"], trans_mat=s["trans_mat"], vertex_colors=rgb)
     out = {"vertices": nv, "triangles": nt, "kept_voxels": int(vol["n_voxels"]), "ply": str(out_ply), "components": m.info["components"],
